@@ -21,11 +21,22 @@ balanced_partition, datasets/data_parallel.py:32-48) and the gathered sites come
 this process never touches the GPU: it starts N children (RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* set), relays rank 0's
 JSON line and exits non-zero if any child fails.
 
-Rank 0 prints ONE JSON line (contract in the task statement) including
+Rank 0 prints ONE JSON line.  A plain run only sets up, warms up, times the `--steps` passes and reports them
+(`value`, `ms_per_step`, the site digest, per-category GPU time of the timed passes).  `--full` adds everything else
+the benchmark measures or checks, each with runs of its own:
   "roofline":     dominant kernel (fused message kernel, f32 MFMA bound), timed live with HIP
-                  events on the launch stream inside the library (adf_profile_*),
+                  events on the launch stream inside the library (adf_profile_*), against on-box peaks
+                  and the HBM traffic of two `rocprofv3 --pmc` child runs,
+  secondaries:    default API, incremental layers off, trajectory sink, 125 systems, B = 1 latency,
+                  exact f32 (N=1 only), and the EquiformerV2 and training lines of the same build,
   "cpu_baseline": the CPU oracle (oracle/painn_oracle.py, a PyTorch restatement of the
                   reference path) timed on the host cores on a bounded sample (N=1 only).
+
+    python bench.py --gpus 1 --steps 2 --warmup 1 --full
+
+`--dump-outputs DIR` writes what the last timed step returned (the sampled sites; for `--mode train` the loss, the
+gradient norm and a fixed sample of the updated parameters) as DIR/<name>.npy; the inputs are seeded, so two builds
+can be compared output for output.
 """
 from __future__ import annotations
 
@@ -64,12 +75,17 @@ def parse():
     ap.add_argument("--gather", choices=("torch", "rccl"), default="torch",
                     help="exchange step: torch.distributed.all_gather (nccl backend = RCCL) or the library's own "
                          "C-ABI adf_allgather_sites (RCCL communicator created by the library)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: roofline (live traffic probe, on-box peaks), the secondary passes, the "
+                         "embedded EquiformerV2 and training lines and the CPU baseline (off: only what `value` needs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32)")
     ap.add_argument("--no-secondary", action="store_true", help="skip the default-API (adsorbate-only outputs), exact-f32 and other extra passes")
     ap.add_argument("--no-incremental", action="store_true",
                     help="PaiNN: recompute every node row of every layer at every step, as the reference does "
                          "(denoising_pos_params['incremental_layers']=False) - timed like the default, warm-up included")
     ap.add_argument("--cpu-full", action="store_true",
-                    help="CPU baseline at SURVEY 8d's sizes (8 systems x 50 steps and 64 x 1 step; ~10 min)")
+                    help="CPU baseline at SURVEY 8d's sizes (8 systems x 50 steps and 64 x 1 step; ~10 min); implies --full")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-traffic-probe", action="store_true",
                     help="skip the two rocprofv3 --pmc child runs that measure roofline.traffic (then the committed "
@@ -81,6 +97,8 @@ def parse():
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only for "
                                                       "testing the N>1 path with several ranks on one GPU)")
     a = ap.parse_args()
+    if a.cpu_full:
+        a.full = True
     if a.systems is None:
         a.systems = 256 if a.mode == "train" else (1000 if a.model == "painn" else 128)
     if a.mode == "train":
@@ -230,6 +248,17 @@ def traffic_probe(args):
                "same runs reads FETCH %.3g / WRITE %.3g bytes)" % (fr[1], fr[2] or 0.0, wr[2] or 0.0))
 
 
+def dump_outputs(directory, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy, float64 kept, anything else as float32."""
+    import numpy as np
+
+    d = Path(directory)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+        np.save(d / f"{name}.npy", a if a.dtype == np.float64 else a.astype(np.float32))
+
+
 def traffic_probe_child(args):
     """The program rocprofv3 runs for traffic_probe(): the first two reverse steps of the benchmark batch + the peak kernels."""
     import torch
@@ -277,13 +306,94 @@ def bench_painn_model(args=None):
     return model
 
 
+def painn_roofline(prof, counters, f16, useful_rows, measured):
+    """--full: the roofline of the message kernel over the timed passes (`prof`, `counters`: the library's HIP-event
+    profile and device counters of those passes) against the nominal and the on-box peaks (`measured`)."""
+    H, R = 512, 128
+    E = counters.num_edges
+    N_atoms = counters.num_atoms
+    msg_ms, msg_launches = prof["message"]
+    products = 3 if f16 else 1  # f16x3 split issues three MFMA products per contraction step
+    peak = PEAK_F16_MFMA_TFLOPS if f16 else PEAK_F32_MFMA_TFLOPS
+    # incremental layers: a launch evaluates only the targets whose inputs changed; per-launch averages of the
+    # edges and targets actually evaluated (device-side totals of the last pass, adf_get_counters)
+    inc_on = counters.inc_msg_launches > 0
+    E_launch = counters.inc_msg_edges / counters.inc_msg_launches if inc_on else float(E)
+    T_launch = counters.inc_rows / counters.inc_msg_launches if inc_on else float(N_atoms)
+    dense_flops_per_launch = 2.0 * R * 3 * H * E_launch
+    # message_ksteps = sum over 32-edge blocks of (contracted k length x 32-column blocks that ran: 6, or 4 in the vec == 0
+    # launches of layer 0, whose xb columns are skipped)
+    issued_flops_per_launch = prof["message_ksteps"] * 32 * 32 * 2.0 * products / max(msg_launches, 1)
+    avg_s = msg_ms * 1e-3 / max(msg_launches, 1)
+    issued = issued_flops_per_launch / avg_s / 1e12 if avg_s > 0 else 0.0
+    dense_equiv = dense_flops_per_launch / avg_s / 1e12 if avg_s > 0 else 0.0
+    gathered_bytes = E_launch * 5 * H * 4.0  # per edge: the source's gather record (xa, xc, P0, P1, P2 per channel), from L2
+    # fused kernel (no rbfh): per edge geometry + index, per target x / vec in and out
+    hbm_alg_bytes = E_launch * (12 + 8) + T_launch * (4 * H * 4.0 + 4 * H * 4.0)
+    traffic = traffic_src = None
+    pmc = ROOT / "profiles" / "message_kernel_pmc.json"
+    if TRAFFIC_PROBE.get("hbm_bytes_per_launch"):
+        traffic = TRAFFIC_PROBE["hbm_bytes_per_launch"]
+        traffic_src = TRAFFIC_PROBE["source"]
+    elif pmc.exists():  # no live probe (rocprofv3 missing / --no-traffic-probe): the committed result, labelled static
+        try:
+            traffic = json.loads(pmc.read_text()).get("hbm_bytes_per_launch")
+            traffic_src = "static: profiles/message_kernel_pmc.json (separate rocprofv3 --pmc FETCH_SIZE / " \
+                          "WRITE_SIZE passes of this command, 2*FETCH+WRITE per full-size launch); not measured in this run"
+        except Exception:
+            traffic = None
+    peak_meas = measured["mfma_f16_tflops"] if f16 else measured["mfma_f32_tflops"]
+    roofline = {
+        "kernel": "adf_message_kernel (fused rbf-projection MFMA + gather + segmented sum), %s mode"
+                  % ("f16x3-split" if f16 else "exact-f32"),
+        "bound": "mfma",
+        "achieved": issued,
+        "peak": peak,
+        "unit": "TFLOP/s",
+        "frac": issued / peak,
+        "useful_row_share": useful_rows,
+        "achieved_useful_rows": issued * useful_rows if useful_rows else None,
+        "frac_useful_rows": issued * useful_rows / peak if useful_rows else None,
+        "measured_peak": peak_meas,
+        "frac_of_measured_peak": issued / peak_meas if peak_meas > 0 else None,
+        "traffic": traffic,
+        "traffic_source": traffic_src,
+        "traffic_probe_seconds": TRAFFIC_PROBE.get("seconds"),
+        "avg_launch_ms": avg_s * 1e3,
+        "launches": msg_launches,
+        "flops_per_launch": issued_flops_per_launch,
+        "dense_equivalent_tflops": dense_equiv,
+        "algorithmic_f16x3_tflops": dense_equiv * products,
+        "l2_gather_tbps": gathered_bytes / avg_s / 1e12 if avg_s > 0 else 0.0,
+        "hbm_algorithmic_gbps": hbm_alg_bytes / avg_s / 1e9 if avg_s > 0 else 0.0,
+        "hbm_algorithmic_frac": (hbm_alg_bytes / avg_s / 1e9) / PEAK_HBM_GBS if avg_s > 0 else 0.0,
+        "note": "achieved = matrix-core flops the kernel issues (k-window x 32 rows x the 32-column blocks that run x 2 "
+                "per 32-edge row block, padded rows and the 3 split products included) / launch time from HIP events on the "
+                "launch stream. This is the conservative count: the algorithm's dense contraction (SURVEY 8d: "
+                "2*R*3H*E per layer, x3 products in this arithmetic = algorithmic_f16x3_tflops) is ~1.9x larger, "
+                "the k-window skips Gaussian terms below 1.5e-8 of the leading one. useful_row_share = edges / (32 x "
+                "row blocks) of this batch's graph (the last block of a target is padded to 32 rows); "
+                "achieved_useful_rows / frac_useful_rows count only the real rows of the issued products. Timed on the "
+                "launch stream; measured_peak = the same MFMA instruction in a register-resident loop on this "
+                "box (non-zero operands). rbfh is never materialised, so neither SURVEY 8d roofline binds alone: "
+                "per 32-edge block the kernel issues ~560 vector instructions (8 FMA per gathered channel-row) "
+                "beside ~54 MFMAs and 10 KB/edge of L2-served record gathers (l2_gather_tbps); on gfx950 the "
+                "matrix-pipe time and the vector-issue time of the two waves of a SIMD ADD "
+                "(profiles/r05_mfma_valu_overlap.txt), which puts this formulation's floor at ~0.42 of nominal - "
+                "see DESIGN.md 4.",
+    }
+    if TRAFFIC_PROBE.get("error"):
+        roofline["traffic_probe_error"] = TRAFFIC_PROBE["error"]
+    return {"roofline": roofline, "measured_peaks": measured}
+
+
 def main():
     args = parse()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(launch_ranks(args))  # before anything touches the GPU
     if args.traffic_probe_child:
         return traffic_probe_child(args)
-    if (args.gpus == 1 and args.model == "painn" and args.mode == "sample" and not args.no_traffic_probe
+    if (args.full and args.gpus == 1 and args.model == "painn" and args.mode == "sample" and not args.no_traffic_probe
             and not args.no_secondary and "ADF_GEMM" not in os.environ and "ADF_MSG" not in os.environ):
         traffic_probe(args)  # children under rocprofv3 --pmc, before this process touches the GPU
     import torch
@@ -323,7 +433,7 @@ def main():
 
     # random-init weights of the reference architecture under seed 0 (+ shipped scale factors)
     model = bench_painn_model(args)
-    cpu_sd = {k: v.clone() for k, v in model.state_dict().items()} if rank == 0 else None
+    cpu_sd = {k: v.clone() for k, v in model.state_dict().items()} if rank == 0 and args.full else None
     scale_factors = model.scale_factors()
     trainer = DenoisingTrainer(model, device=dev)
 
@@ -393,7 +503,7 @@ def main():
         keep_sites(t, curve16)
 
     for i in range(args.warmup):
-        one_pass({"step_hook": hook} if i == 0 and rank == 0 and not args.no_incremental else None)
+        one_pass({"step_hook": hook} if args.full and i == 0 and rank == 0 and not args.no_incremental else None)
     row_frac = []
     for i, (r, f) in enumerate(rows_log):
         r0, f0 = rows_log[i - 1] if i and rows_log[i - 1][0] <= r else (0, 0)
@@ -418,11 +528,13 @@ def main():
         elapsed = max(a[0] for a in rank_ms) * args.steps / 1e3
     prof = eng.profile_read()
     eng.profile_enable(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"sites": sites})
     counters = eng.counters() if batch0 is not None else None   # (rank 0 always holds systems)
     # share of the message kernel's 32-row blocks that are real edges (a target's in-edges are processed 32 rows at a
     # time; the last block of a target is padded): from the in-degrees of the batch's own graph
     useful_rows = None
-    if rank == 0 and batch0 is not None:
+    if args.full and rank == 0 and batch0 is not None:
         try:
             eng.build_graph(batch0)
             ed_ = eng.export_graph()[4]
@@ -436,7 +548,7 @@ def main():
     # Secondary measurement, N = 1 only, never `value`: the same pass with the model outputs evaluated on the
     # adsorbate atoms only (the stepper reads nothing else; sampled positions are bit-identical, checked here).
     ads_only = exact_f32 = all_rows = small = traj_sink = b1_latency = None
-    if world == 1 and not args.no_secondary:
+    if args.full and world == 1 and not args.no_secondary:
         one_pass({"incremental_layers": False})   # untimed: the switch frees the 22 GB of kept layer state
         torch.cuda.synchronize(dev)
         t1 = time.perf_counter()
@@ -631,43 +743,10 @@ def main():
     if rank == 0:
         assert sites.shape[0] == total_systems, (sites.shape, total_systems)
         assert bool(torch.isfinite(sites).all())
-        H, R = 512, 128
         E = counters.num_edges
-        N_atoms = counters.num_atoms
-        msg_ms, msg_launches = prof["message"]
         f16 = os.environ.get("ADF_MSG", os.environ.get("ADF_GEMM", "f16")) != "f32"
-        products = 3 if f16 else 1  # f16x3 split issues three MFMA products per contraction step
-        peak = PEAK_F16_MFMA_TFLOPS if f16 else PEAK_F32_MFMA_TFLOPS
-        # incremental layers: a launch evaluates only the targets whose inputs changed; per-launch averages of the
-        # edges and targets actually evaluated (device-side totals of the last pass, adf_get_counters)
         inc_on = counters.inc_msg_launches > 0
-        E_launch = counters.inc_msg_edges / counters.inc_msg_launches if inc_on else float(E)
-        T_launch = counters.inc_rows / counters.inc_msg_launches if inc_on else float(N_atoms)
-        dense_flops_per_launch = 2.0 * R * 3 * H * E_launch
-        # message_ksteps = sum over 32-edge blocks of (contracted k length x 32-column blocks that ran: 6, or 4 in the vec == 0
-        # launches of layer 0, whose xb columns are skipped)
-        issued_flops_per_launch = prof["message_ksteps"] * 32 * 32 * 2.0 * products / max(msg_launches, 1)
-        avg_s = msg_ms * 1e-3 / max(msg_launches, 1)
-        issued = issued_flops_per_launch / avg_s / 1e12 if avg_s > 0 else 0.0
-        dense_equiv = dense_flops_per_launch / avg_s / 1e12 if avg_s > 0 else 0.0
-        gathered_bytes = E_launch * 5 * H * 4.0  # per edge: the source's gather record (xa, xc, P0, P1, P2 per channel), from L2
-        # fused kernel (no rbfh): per edge geometry + index, per target x / vec in and out
-        hbm_alg_bytes = E_launch * (12 + 8) + T_launch * (4 * H * 4.0 + 4 * H * 4.0)
-        traffic = traffic_src = None
-        pmc = ROOT / "profiles" / "message_kernel_pmc.json"
-        if TRAFFIC_PROBE.get("hbm_bytes_per_launch"):
-            traffic = TRAFFIC_PROBE["hbm_bytes_per_launch"]
-            traffic_src = TRAFFIC_PROBE["source"]
-        elif pmc.exists():  # no live probe (rocprofv3 missing / --no-traffic-probe): the committed result, labelled static
-            try:
-                traffic = json.loads(pmc.read_text()).get("hbm_bytes_per_launch")
-                traffic_src = "static: profiles/message_kernel_pmc.json (separate rocprofv3 --pmc FETCH_SIZE / " \
-                              "WRITE_SIZE passes of this command, 2*FETCH+WRITE per full-size launch); not measured in this run"
-            except Exception:
-                traffic = None
         gpu_ms = {k: round(v[0] / args.steps, 2) for k, v in prof.items() if isinstance(v, tuple)}
-        measured = eng.measure_peaks()  # stream copy + register-resident MFMA loops, on this box, after the timed region
-        peak_meas = measured["mfma_f16_tflops"] if f16 else measured["mfma_f32_tflops"]
         import hashlib
 
         sites_digest = hashlib.sha256(torch.nan_to_num(sites).cpu().numpy().tobytes()).hexdigest()[:16]
@@ -718,59 +797,21 @@ def main():
                         "kernels (HIP events), and its share of the batch; `ms_per_step` of the line is the maximum"},
             "system_steps_per_s": total_systems * args.steps * args.num_steps / elapsed,
             "gpu_ms_per_pass": gpu_ms,
-            "roofline": {
-                "kernel": "adf_message_kernel (fused rbf-projection MFMA + gather + segmented sum), %s mode"
-                          % ("f16x3-split" if f16 else "exact-f32"),
-                "bound": "mfma",
-                "achieved": issued,
-                "peak": peak,
-                "unit": "TFLOP/s",
-                "frac": issued / peak,
-                "useful_row_share": useful_rows,
-                "achieved_useful_rows": issued * useful_rows if useful_rows else None,
-                "frac_useful_rows": issued * useful_rows / peak if useful_rows else None,
-                "measured_peak": peak_meas,
-                "frac_of_measured_peak": issued / peak_meas if peak_meas > 0 else None,
-                "traffic": traffic,
-                "traffic_source": traffic_src,
-                "traffic_probe_seconds": TRAFFIC_PROBE.get("seconds"),
-                "avg_launch_ms": avg_s * 1e3,
-                "launches": msg_launches,
-                "flops_per_launch": issued_flops_per_launch,
-                "dense_equivalent_tflops": dense_equiv,
-                "algorithmic_f16x3_tflops": dense_equiv * products,
-                "l2_gather_tbps": gathered_bytes / avg_s / 1e12 if avg_s > 0 else 0.0,
-                "hbm_algorithmic_gbps": hbm_alg_bytes / avg_s / 1e9 if avg_s > 0 else 0.0,
-                "hbm_algorithmic_frac": (hbm_alg_bytes / avg_s / 1e9) / PEAK_HBM_GBS if avg_s > 0 else 0.0,
-                "note": "achieved = matrix-core flops the kernel issues (k-window x 32 rows x the 32-column blocks that run x 2 "
-                        "per 32-edge row block, padded rows and the 3 split products included) / launch time from HIP events on the "
-                        "launch stream. This is the conservative count: the algorithm's dense contraction (SURVEY 8d: "
-                        "2*R*3H*E per layer, x3 products in this arithmetic = algorithmic_f16x3_tflops) is ~1.9x larger, "
-                        "the k-window skips Gaussian terms below 1.5e-8 of the leading one. useful_row_share = edges / (32 x "
-                        "row blocks) of this batch's graph (the last block of a target is padded to 32 rows); "
-                        "achieved_useful_rows / frac_useful_rows count only the real rows of the issued products. Timed on the "
-                        "launch stream; measured_peak = the same MFMA instruction in a register-resident loop on this "
-                        "box (non-zero operands). rbfh is never materialised, so neither SURVEY 8d roofline binds alone: "
-                        "per 32-edge block the kernel issues ~560 vector instructions (8 FMA per gathered channel-row) "
-                        "beside ~54 MFMAs and 10 KB/edge of L2-served record gathers (l2_gather_tbps); on gfx950 the "
-                        "matrix-pipe time and the vector-issue time of the two waves of a SIMD ADD "
-                        "(profiles/r05_mfma_valu_overlap.txt), which puts this formulation's floor at ~0.42 of nominal - "
-                        "see DESIGN.md 4.",
-            },
-            "measured_peaks": measured,
-            "recomputed_row_fraction_per_step": row_frac or None,  # warm-up pass: layer x atom rows recomputed / all rows
-            "incremental_layers_off": all_rows,
-            "value_at_125_systems": small,
-            "with_trajectory_sink": traj_sink,
-            "value_default_api": ads_only,
-            "exact_f32": exact_f32,
-            "b1_latency": b1_latency,
         }
-        if TRAFFIC_PROBE.get("error"):
-            out["roofline"]["traffic_probe_error"] = TRAFFIC_PROBE["error"]
-        if world == 1 and not args.no_secondary:
-            # BASELINE configs 4 and 5 in the same line (bounded: 64 systems x 50 steps; 5 training steps), so that the
-            # driver's one `bench.py --gpus 1` run times them too.  Each is the object its own mode prints.
+        if args.full:
+            out.update(painn_roofline(prof, counters, f16, useful_rows, eng.measure_peaks()))
+            out.update({
+                "recomputed_row_fraction_per_step": row_frac or None,  # warm-up pass: layer x atom rows recomputed / all rows
+                "incremental_layers_off": all_rows,
+                "value_at_125_systems": small,
+                "with_trajectory_sink": traj_sink,
+                "value_default_api": ads_only,
+                "exact_f32": exact_f32,
+                "b1_latency": b1_latency,
+            })
+        if args.full and world == 1 and not args.no_secondary:
+            # BASELINE configs 4 and 5 in the same line (bounded: 64 systems x 50 steps; 5 training steps), so that one
+            # `bench.py --gpus 1 --full` run times them too.  Each is the object its own mode prints with --full.
             eng.close()
             del trainer
             torch.cuda.empty_cache()
@@ -778,19 +819,19 @@ def main():
 
             a4 = copy.copy(args)
             a4.model, a4.systems, a4.steps, a4.warmup, a4.no_secondary, a4.no_cpu_baseline = "eqv2", 64, 1, 1, True, args.no_cpu_baseline
-            a4.scaling, a4.warmup_num_steps = "strong", 3
+            a4.scaling, a4.warmup_num_steps, a4.dump_outputs = "strong", 3, None
             try:
                 out["eqv2"] = main_eqv2(a4, rank, world, dev, emit=False)
             except Exception as e:  # never lose the headline to a secondary
                 out["eqv2"] = {"error": repr(e)}
             torch.cuda.empty_cache()
             a5 = copy.copy(args)
-            a5.mode, a5.systems, a5.steps, a5.warmup = "train", 256, 5, 2
+            a5.mode, a5.systems, a5.steps, a5.warmup, a5.dump_outputs = "train", 256, 5, 2, None
             try:
                 out["train"] = main_train(a5, rank, world, dev, emit=False)
             except Exception as e:
                 out["train"] = {"error": repr(e)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cpu_sd, scale_factors, params, full=args.cpu_full)
         print(json.dumps(out), flush=True)
     if world > 1:
@@ -819,6 +860,10 @@ def main_train(args, rank, world, dev, emit=True):
     tr.setup_training(dict(ads_std_low=0.1, ads_std_high=10, rot_std_low=0.01, rot_std_high=1.55), lr=1e-4,
                       tables=Igso3Tables.shared())
     batch = make_batch(args.systems, seed=2000 + rank).to(dev)
+    import numpy as np
+
+    np.random.seed(2000 + rank)  # the rotation noise of every step draws from numpy's global stream: same inputs every run
+
     def fence():
         if world > 1:
             dist.barrier()
@@ -839,6 +884,14 @@ def main_train(args, rank, world, dev, emit=True):
         elapsed = float(t.item())
     ar_events = getattr(tr, "allreduce_wait_events", [])
     ar_ms = sum(a.elapsed_time(b) for a, b in ar_events) / max(len(ar_events), 1)
+    if args.dump_outputs and rank == 0:
+        # the updated parameters (21 M values) through a fixed, seeded sample of 2^20 of them, in storage order
+        flat = torch.cat([p.detach().reshape(-1) for p in model.parameters()])
+        pick = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(0))[:1 << 20].sort().values
+        arrays = {"loss": out["loss"], "parameters_sample": flat[pick.to(flat.device)]}
+        if out.get("grad_norm") is not None:
+            arrays["grad_norm"] = out["grad_norm"]
+        dump_outputs(args.dump_outputs, arrays)
     if rank == 0:
         H, R, L, n, E = 512, 128, 6, 200, 10100  # per graph: 200 atoms, ~10.1 k symmetrised edges
         fwd = L * (30 * H * H * n + 2 * R * 3 * H * E) + 2 * 1.6e9 / 2  # 34.6 GFLOP per graph forward
@@ -938,6 +991,58 @@ def eqv2_cpu_baseline(model, params):
                       "%d steps per site, LINEARLY EXTRAPOLATED" % (dt, 1.0 / dt, params["num_steps"])}
 
 
+def eqv2_roofline(prof, c, f16, forwards, dev):
+    """--full: the roofline of the SO(2) convolution products over the timed passes (`prof`, `c`: the library's HIP-event
+    profile and device counters of those passes) against the nominal and the on-box peaks."""
+    import ctypes as C
+
+    import torch
+
+    from adsorbdiff_amd import lib as _lib
+
+    conv_ms, conv_groups = prof["so2_conv"]
+    products = 3 if f16 else 1
+    conv_s = conv_ms * 1e-3
+    # summed by the library over the profiled forwards (incremental blocks: a forward's convolutions run on the edges of
+    # the targets it recomputes, which differs from forward to forward)
+    assert c.forwards_total == forwards, (c.forwards_total, forwards)
+    issued = c.conv_flops_total * products / conv_s / 1e12 if conv_s > 0 else 0.0
+    pk = (C.c_float * 3)()   # (peaks come from the library, any handle)
+    _lib.check(_lib.load().adf_measure_peaks(pk, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    measured = {"hbm_copy_gbps": float(pk[0]), "mfma_f16_tflops": float(pk[1]), "mfma_f32_tflops": float(pk[2])}
+    total_gpu_s = sum(v[0] for v in prof.values()) * 1e-3
+    conv_traffic = conv_traffic_src = None
+    pmc = ROOT / "profiles" / "eqv2_conv_pmc.json"
+    if pmc.exists():  # PMC counters need their own rocprofv3 passes: the committed result scaled to this run's edge count
+        try:
+            chunk = int(os.environ.get("ADF_EQV2_CHUNK_EDGES", 1 << 19))  # edges per launch: the engine's chunking
+            per_launch = c.num_edges / max(1, -(-c.num_edges // chunk))
+            conv_traffic = json.loads(pmc.read_text())["hbm_bytes_per_conv_launch_and_edge"] * per_launch
+            conv_traffic_src = ("static: profiles/eqv2_conv_pmc.json (separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes at "
+                                "64 systems, 2*FETCH+WRITE per launch of the convolution product kernels and per edge) x this "
+                                "run's edges per launch; not measured in this run")
+        except Exception:
+            conv_traffic = None
+    return {
+        "roofline": {
+            "kernel": "eq_gemm16pw_kernel + eq_gemm16_256_kernel (SO(2) convolution products of the %d attention blocks, f16x3 split)"
+                      % (EQV2_HP["num_layers"] + 2),
+            "bound": "mfma",
+            "achieved": issued, "peak": PEAK_F16_MFMA_TFLOPS if f16 else PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s",
+            "frac": issued / (PEAK_F16_MFMA_TFLOPS if f16 else PEAK_F32_MFMA_TFLOPS),
+            "measured_peak": measured["mfma_f16_tflops"] if f16 else measured["mfma_f32_tflops"],
+            "traffic": conv_traffic,
+            "traffic_source": conv_traffic_src,
+            "flops_per_forward": c.conv_flops_total * products / max(forwards, 1),
+            "share_of_gpu_time": conv_s / total_gpu_s if total_gpu_s > 0 else None,
+            "note": "achieved = 2 x multiply-adds of the SO(2) convolutions (5.83 M + 2.40 M per edge and block at this "
+                    "configuration) x 3 split products / HIP-event time of the convolution launches on the launch "
+                    "stream (includes the row-lift passes that feed them)",
+        },
+        "measured_peaks": measured,
+    }
+
+
 def main_eqv2(args, rank, world, dev, emit=True):
     """BASELINE config 4: EquiformerV2 denoiser (L_max = 6, M_max = 2, C = 128, 8 blocks, K = 20, 12 A: the shipped
     configs/denoising/eqv2_so3.yml with lmax 6), `--num-steps`-step ODE sampling on `--systems` synthetic systems."""
@@ -998,7 +1103,7 @@ def main_eqv2(args, rank, world, dev, emit=True):
     # secondary (one pass): Denoiser.run() without options = the force blocks evaluated for the adsorbate atoms only
     # inside the fused loop (adf_eqv2_forward_subset)
     sites_ads, ads_s = None, 0.0
-    if not args.no_secondary:
+    if args.full and not args.no_secondary:
         fence()
         t0 = time.perf_counter()
         sites_ads = one_pass({"scores_on_adsorbate_only": None})
@@ -1006,7 +1111,7 @@ def main_eqv2(args, rank, world, dev, emit=True):
         ads_s = time.perf_counter() - t0
     # secondary (one pass): every row of every block recomputed at every step, as the reference does
     sites_full, full_s = None, 0.0
-    if not args.no_secondary:
+    if args.full and not args.no_secondary:
         fence()
         t0 = time.perf_counter()
         sites_full = one_pass({"incremental_layers": False})
@@ -1032,40 +1137,14 @@ def main_eqv2(args, rank, world, dev, emit=True):
         elapsed = max(a[0] for a in rank_ms) * args.steps / 1e3
     prof = eng.profile_read()
     eng.profile_enable(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"sites": sites})
     c = eng.counters() if batch0 is not None else None
     if rank == 0:
         assert sites.shape[0] == total_systems and bool(torch.isfinite(sites).all())
         forwards = args.steps * args.num_steps
-        conv_ms, conv_groups = prof["so2_conv"]
         f16 = os.environ.get("ADF_GEMM") != "f32"
-        products = 3 if f16 else 1
-        conv_s = conv_ms * 1e-3
-        # summed by the library over the profiled forwards (incremental blocks: a forward's convolutions run on the edges of
-        # the targets it recomputes, which differs from forward to forward)
-        assert c.forwards_total == forwards, (c.forwards_total, forwards)
-        issued = c.conv_flops_total * products / conv_s / 1e12 if conv_s > 0 else 0.0
-        from adsorbdiff_amd.engine import PaiNNEngine  # noqa: F401  (peaks come from the library, any handle)
-        import ctypes as C
-
-        from adsorbdiff_amd import lib as _lib
-
-        pk = (C.c_float * 3)()
-        _lib.check(_lib.load().adf_measure_peaks(pk, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-        measured = {"hbm_copy_gbps": float(pk[0]), "mfma_f16_tflops": float(pk[1]), "mfma_f32_tflops": float(pk[2])}
         gpu_ms = {k: round(v[0] / args.steps, 2) for k, v in prof.items()}
-        total_gpu_s = sum(v[0] for v in prof.values()) * 1e-3
-        conv_traffic = conv_traffic_src = None
-        pmc = ROOT / "profiles" / "eqv2_conv_pmc.json"
-        if pmc.exists():  # PMC counters need their own rocprofv3 passes: the committed result scaled to this run's edge count
-            try:
-                chunk = int(os.environ.get("ADF_EQV2_CHUNK_EDGES", 1 << 19))  # edges per launch: the engine's chunking
-                per_launch = c.num_edges / max(1, -(-c.num_edges // chunk))
-                conv_traffic = json.loads(pmc.read_text())["hbm_bytes_per_conv_launch_and_edge"] * per_launch
-                conv_traffic_src = ("static: profiles/eqv2_conv_pmc.json (separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes at "
-                                    "64 systems, 2*FETCH+WRITE per launch of the convolution product kernels and per edge) x this "
-                                    "run's edges per launch; not measured in this run")
-            except Exception:
-                conv_traffic = None
         import hashlib
 
         out = {
@@ -1096,23 +1175,9 @@ def main_eqv2(args, rank, world, dev, emit=True):
             "dense_tflops_f32_equivalent": c.dense_flops * forwards / elapsed / 1e12,
             "gpu_ms_per_pass": gpu_ms,
             "recomputed_block_rows_fraction": round(c.inc_rows / c.inc_rows_full, 4) if c.inc_rows_full else 1.0,
-            "roofline": {
-                "kernel": "eq_gemm16pw_kernel + eq_gemm16_256_kernel (SO(2) convolution products of the %d attention blocks, f16x3 split)"
-                          % (EQV2_HP["num_layers"] + 2),
-                "bound": "mfma",
-                "achieved": issued, "peak": PEAK_F16_MFMA_TFLOPS if f16 else PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s",
-                "frac": issued / (PEAK_F16_MFMA_TFLOPS if f16 else PEAK_F32_MFMA_TFLOPS),
-                "measured_peak": measured["mfma_f16_tflops"] if f16 else measured["mfma_f32_tflops"],
-                "traffic": conv_traffic,
-                "traffic_source": conv_traffic_src,
-                "flops_per_forward": c.conv_flops_total * products / max(forwards, 1),
-                "share_of_gpu_time": conv_s / total_gpu_s if total_gpu_s > 0 else None,
-                "note": "achieved = 2 x multiply-adds of the SO(2) convolutions (5.83 M + 2.40 M per edge and block at this "
-                        "configuration) x 3 split products / HIP-event time of the convolution launches on the launch "
-                        "stream (includes the row-lift passes that feed them)",
-            },
-            "measured_peaks": measured,
         }
+        if args.full:
+            out.update(eqv2_roofline(prof, c, f16, forwards, dev))
         if sites_ads is not None:
             out["value_default_api"] = {
                 "value": total_systems / ads_s, "unit": "sites/s", "identical_sites": bool(torch.equal(sites_ads, sites)),
@@ -1126,7 +1191,7 @@ def main_eqv2(args, rank, world, dev, emit=True):
                 "note": "denoising_pos_params['incremental_layers']=False: every block recomputes every row at every step, as "
                         "the reference does; one pass, this rank's clock",
             }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = eqv2_cpu_baseline(model, params)
         if not emit:
             eng.close()

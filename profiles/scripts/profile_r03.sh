@@ -3,18 +3,18 @@
 set -euo pipefail
 cd "${GRAFT_REPO_ROOT:?GRAFT_REPO_ROOT is not set (run on the GPU box through gpurun)}"; export TMPDIR=/tmp
 o=gpurun_out/r03; rm -rf $o; mkdir -p $o
-python3 bench.py > $o/bench.json 2> $o/bench.err
+python3 bench.py --full > $o/bench.json 2> $o/bench.err
 python3 bench.py --mode train > $o/bench_train.json 2> $o/bench_train.err
-python3 bench.py --model eqv2 --systems 256 --steps 1 --warmup 0 > $o/bench_eqv2.json 2> $o/bench_eqv2.err
-rocprofv3 --kernel-trace --stats -d $o/stats -o r03 --output-format csv -- python3 bench.py --no-cpu-baseline --no-secondary > $o/under_rocprof.log 2>&1
+python3 bench.py --full --model eqv2 --systems 256 --steps 1 --warmup 0 > $o/bench_eqv2.json 2> $o/bench_eqv2.err
+rocprofv3 --kernel-trace --stats -d $o/stats -o r03 --output-format csv -- python3 bench.py --full --no-cpu-baseline --no-secondary > $o/under_rocprof.log 2>&1
 rocprofv3 --pmc FETCH_SIZE -d $o/pmc_fetch -o f --output-format csv -- python3 bench.py --no-cpu-baseline --no-secondary --steps 1 --warmup 0 --num-steps 3 > $o/pmc_fetch.log 2>&1
 rocprofv3 --pmc WRITE_SIZE -d $o/pmc_write -o w --output-format csv -- python3 bench.py --no-cpu-baseline --no-secondary --steps 1 --warmup 0 --num-steps 3 > $o/pmc_write.log 2>&1
 rocprofv3 --pmc MfmaUtil VALUBusy -d $o/pmc_util -o u --output-format csv -- python3 bench.py --no-cpu-baseline --no-secondary --steps 1 --warmup 0 --num-steps 3 > $o/pmc_util.log 2>&1
 # EquiformerV2 (config 4)
-rocprofv3 --kernel-trace --stats -d $o/eq_stats -o eq --output-format csv -- python3 bench.py --model eqv2 --systems 64 --steps 1 --warmup 0 --num-steps 10 --no-cpu-baseline > $o/eq_under_rocprof.log 2>&1
-rocprofv3 --pmc FETCH_SIZE -d $o/eq_pmc_fetch -o f --output-format csv -- python3 bench.py --model eqv2 --systems 64 --steps 1 --warmup 0 --num-steps 2 --no-cpu-baseline > $o/eq_pmc_fetch.log 2>&1
-rocprofv3 --pmc WRITE_SIZE -d $o/eq_pmc_write -o w --output-format csv -- python3 bench.py --model eqv2 --systems 64 --steps 1 --warmup 0 --num-steps 2 --no-cpu-baseline > $o/eq_pmc_write.log 2>&1
-rocprofv3 --pmc MfmaUtil VALUBusy -d $o/eq_pmc_util -o u --output-format csv -- python3 bench.py --model eqv2 --systems 64 --steps 1 --warmup 0 --num-steps 2 --no-cpu-baseline > $o/eq_pmc_util.log 2>&1
+rocprofv3 --kernel-trace --stats -d $o/eq_stats -o eq --output-format csv -- python3 bench.py --full --model eqv2 --systems 64 --steps 1 --warmup 0 --num-steps 10 --no-cpu-baseline > $o/eq_under_rocprof.log 2>&1
+rocprofv3 --pmc FETCH_SIZE -d $o/eq_pmc_fetch -o f --output-format csv -- python3 bench.py --full --model eqv2 --systems 64 --steps 1 --warmup 0 --num-steps 2 --no-cpu-baseline > $o/eq_pmc_fetch.log 2>&1
+rocprofv3 --pmc WRITE_SIZE -d $o/eq_pmc_write -o w --output-format csv -- python3 bench.py --full --model eqv2 --systems 64 --steps 1 --warmup 0 --num-steps 2 --no-cpu-baseline > $o/eq_pmc_write.log 2>&1
+rocprofv3 --pmc MfmaUtil VALUBusy -d $o/eq_pmc_util -o u --output-format csv -- python3 bench.py --full --model eqv2 --systems 64 --steps 1 --warmup 0 --num-steps 2 --no-cpu-baseline > $o/eq_pmc_util.log 2>&1
 # training step kernel stats
 rocprofv3 --kernel-trace --stats -d $o/train_stats -o tr --output-format csv -- python3 bench.py --mode train --steps 3 --warmup 1 > $o/train_under_rocprof.log 2>&1
 find $o -name "*agent_info.csv" -delete

@@ -6,11 +6,11 @@
 set -uo pipefail
 cd "${GRAFT_REPO_ROOT:?GRAFT_REPO_ROOT is not set (run on the GPU box through gpurun)}"; export TMPDIR=/tmp
 o=gpurun_out/r05; rm -rf "$o"; mkdir -p "$o"
-python3 bench.py > $o/bench.json 2> $o/bench.err
-rocprofv3 --kernel-trace --stats -d $o/stats -o r05 --output-format csv -- python3 bench.py --no-cpu-baseline --no-secondary > $o/under_rocprof.log 2>&1
+python3 bench.py --full > $o/bench.json 2> $o/bench.err
+rocprofv3 --kernel-trace --stats -d $o/stats -o r05 --output-format csv -- python3 bench.py --full --no-cpu-baseline --no-secondary > $o/under_rocprof.log 2>&1
 rocprofv3 --pmc MfmaUtil VALUBusy -d $o/pmc_util -o u --output-format csv -- python3 bench.py --no-cpu-baseline --no-secondary --steps 1 --warmup 0 --num-steps 3 > $o/pmc_util.log 2>&1
 rocprofv3 --kernel-trace --stats -d $o/train_stats -o tr --output-format csv -- python3 bench.py --mode train --steps 3 --warmup 1 > $o/train_under_rocprof.log 2>&1
-rocprofv3 --kernel-trace --stats -d $o/eq_stats -o eq --output-format csv -- python3 bench.py --model eqv2 --systems 64 --steps 1 --warmup 0 --num-steps 10 --no-cpu-baseline --no-secondary > $o/eq_under_rocprof.log 2>&1
+rocprofv3 --kernel-trace --stats -d $o/eq_stats -o eq --output-format csv -- python3 bench.py --full --model eqv2 --systems 64 --steps 1 --warmup 0 --num-steps 10 --no-cpu-baseline --no-secondary > $o/eq_under_rocprof.log 2>&1
 bash profiles/scripts/msg_pmc.sh adsorbdiff_amd/libadsorbdiff_hip.so 200 > $o/message_kernel_sq_counters_200_systems.txt 2>&1
 rm -rf gpurun_out/msgpmc
 for c in FETCH_SIZE WRITE_SIZE; do

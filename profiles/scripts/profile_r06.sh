@@ -6,8 +6,8 @@
 set -uo pipefail
 cd "${GRAFT_REPO_ROOT:?GRAFT_REPO_ROOT is not set (run on the GPU box through gpurun)}"; export TMPDIR=/tmp
 o=gpurun_out/r06; rm -rf "$o"; mkdir -p "$o"
-python3 bench.py > $o/bench.json 2> $o/bench.err
-rocprofv3 --kernel-trace --stats -d $o/stats -o r06 --output-format csv -- python3 bench.py --no-cpu-baseline --no-secondary > $o/under_rocprof.log 2>&1
+python3 bench.py --full > $o/bench.json 2> $o/bench.err
+rocprofv3 --kernel-trace --stats -d $o/stats -o r06 --output-format csv -- python3 bench.py --full --no-cpu-baseline --no-secondary > $o/under_rocprof.log 2>&1
 rocprofv3 --pmc MfmaUtil VALUBusy -d $o/pmc_util -o u --output-format csv -- python3 bench.py --no-cpu-baseline --no-secondary --no-traffic-probe --steps 1 --warmup 0 --num-steps 3 > $o/pmc_util.log 2>&1
 for c in FETCH_SIZE WRITE_SIZE; do
   rocprofv3 --pmc $c -d $o/hbm/$c -o p --output-format csv -- python3 bench.py --no-cpu-baseline --no-secondary --no-traffic-probe --steps 1 --warmup 0 --num-steps 3 > $o/hbm_$c.log 2>&1
@@ -15,7 +15,7 @@ for c in FETCH_SIZE WRITE_SIZE; do
   rocprofv3 --pmc $c -d $o/eq_hbm/$c -o p --output-format csv -- python3 bench.py --model eqv2 --systems 64 --steps 1 --warmup 0 --num-steps 2 --no-cpu-baseline --no-secondary > $o/eq_hbm_$c.log 2>&1
 done
 rocprofv3 --kernel-trace --stats -d $o/train_stats -o tr --output-format csv -- python3 bench.py --mode train --steps 3 --warmup 1 > $o/train_under_rocprof.log 2>&1
-rocprofv3 --kernel-trace --stats -d $o/eq_stats -o eq --output-format csv -- python3 bench.py --model eqv2 --systems 64 --steps 1 --warmup 0 --num-steps 10 --no-cpu-baseline --no-secondary > $o/eq_under_rocprof.log 2>&1
+rocprofv3 --kernel-trace --stats -d $o/eq_stats -o eq --output-format csv -- python3 bench.py --full --model eqv2 --systems 64 --steps 1 --warmup 0 --num-steps 10 --no-cpu-baseline --no-secondary > $o/eq_under_rocprof.log 2>&1
 find $o -name "*agent_info.csv" -delete
 python3 - <<'PY'
 import csv, glob, collections, os, json
