@@ -88,6 +88,12 @@ struct adf_eqv2 {
     eq_block blk[EQ_MAX_LAYERS];
     eq_norm final_norm;
     eq_attn force[2];
+    // conditional model (adf_eqv2_set_energy_embedding / adf_eqv2_set_system_energy): energy_embedding = nn.Linear(1, C)
+    bool ee_on, ee_ready;      // a layer is bound / ee_term matches the bound layer and energies
+    float* ee_wb;              // [2C] copy of W, b (fp32; rounded to fp16 by the term kernel)
+    float* ee_energy; int64_t ee_cap;   // [ee_B] copy of the per-system energies
+    int64_t ee_B;              // systems the energies were given for; 0 = none (sampling mode: e = 0 for every system)
+    float* ee_term; int64_t ee_term_rows;   // [max(ee_B, 1), C] the per-system term rows
     unsigned char* w16_arena; size_t w16_bytes; float* w16_scales; unsigned int* w16_scratch;
     unsigned char* wfrag_arena;   // fragment images (adf_w16::frag) of the split weights, for eq_launch_gemm16pw
     bool conv1_wr;                // first convolution with the weights streamed as fragments (ADF_EQV2_CONV1_WR, default on)
@@ -155,8 +161,12 @@ int32_t eq_launch_radial_pre(const adf_eqv2* h, const eq_radial* r, const float*
                              const int32_t* Z, int n0, int n1, float* out, int N, hipStream_t s);
 int32_t eq_launch_ln_silu(float* x, const float* w, const float* b, long long rows, int width, hipStream_t s);
 // pair_ne > 0: m0 / rad are tables with one row per element pair (Z_src * pair_ne + Z_tgt) instead of one row per edge
+// term != null (conditional model): term[batch[n] * term_stride + c] joins the element embedding on l = 0
 int32_t eq_launch_edge_degree(const adf_eqv2* h, const float* m0, const int32_t* Z, int pair_ne, int n0, int n1, float* x,
-                              hipStream_t s);
+                              hipStream_t s, const float* term = nullptr, const int32_t* batch = nullptr, int term_stride = 0,
+                              int term_rows = 1);
+// the conditional model's energy term table [rows, C] from wb = [W | b] (fp32, rounded to fp16 here); energy null = zeros
+int32_t eq_launch_energy_term(const float* wb, const float* energy, int rows, int C, float* term, hipStream_t s);
 int32_t eq_launch_radial_pre_pairs(const adf_eqv2* h, const eq_radial* r, const float* src_emb, const float* dst_emb,
                                    float* out, hipStream_t s);
 // rsp (optional): per-order arrays that receive the power-of-two lifts of the operand rows it writes

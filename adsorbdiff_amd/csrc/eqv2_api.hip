@@ -167,6 +167,7 @@ extern "C" int32_t adf_eqv2_destroy(adf_eqv2_t h) {
     (void)hipDeviceSynchronize();
     eq_free_workspaces(h);
     eq_free(h->flags); eq_free(h->d_dev);
+    eq_free(h->ee_wb); eq_free(h->ee_energy); eq_free(h->ee_term);
     eq_free(h->xe_src); eq_free(h->xe_dst); eq_free(h->xe_vec);
     { unsigned char* t = (unsigned char*)h->s2tab; eq_free(t); h->s2tab = nullptr; }
     { unsigned char* t = (unsigned char*)h->gtab_to; eq_free(t); h->gtab_to = nullptr; }
@@ -552,6 +553,62 @@ extern "C" int32_t adf_eqv2_set_arithmetic(adf_eqv2_t h, int32_t exact_f32) {
     if (!h) { adf_set_error("null handle"); return ADF_EINVAL; }
     h->exact_f32 = exact_f32 != 0;
     h->inc_valid = false;
+    return ADF_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- conditional model
+// The term table is (re)built by the first forward after either setter (eq_energy_term_ready): once per sampling loop,
+// not per step.  Either setter also drops the incremental blocks' kept state: the embedding of every atom of a system
+// whose term changed is stale, whatever moved.
+extern "C" int32_t adf_eqv2_set_energy_embedding(adf_eqv2_t h, const float* w, const float* b, void* stream) {
+    if (!h) { adf_set_error("null handle"); return ADF_EINVAL; }
+    if ((w == nullptr) != (b == nullptr)) { adf_set_error("eqv2_set_energy_embedding: need both weight and bias, or neither"); return ADF_EINVAL; }
+    h->inc_valid = false;
+    h->ee_ready = false;
+    if (!w) { h->ee_on = false; return ADF_OK; }
+    const int C = h->d.C;
+    if (!h->ee_wb) ADF_TRY(eq_alloc(&h->ee_wb, 2 * (size_t)C));
+    hipStream_t s = (hipStream_t)stream;
+    ADF_HIP_CHECK(hipMemcpyAsync(h->ee_wb, w, sizeof(float) * C, hipMemcpyDeviceToDevice, s));
+    ADF_HIP_CHECK(hipMemcpyAsync(h->ee_wb + C, b, sizeof(float) * C, hipMemcpyDeviceToDevice, s));
+    h->ee_on = true;
+    return ADF_OK;
+}
+
+extern "C" int32_t adf_eqv2_set_system_energy(adf_eqv2_t h, const float* energy, int32_t num_systems, void* stream) {
+    if (!h) { adf_set_error("null handle"); return ADF_EINVAL; }
+    if (energy && num_systems < 1) { adf_set_error("eqv2_set_system_energy: num_systems must be positive"); return ADF_EINVAL; }
+    h->inc_valid = false;
+    h->ee_ready = false;
+    if (!energy) { h->ee_B = 0; return ADF_OK; }
+    if (num_systems > h->ee_cap) {
+        ADF_HIP_CHECK(hipDeviceSynchronize());
+        eq_free(h->ee_energy);
+        h->ee_cap = 0;
+        ADF_TRY(eq_alloc(&h->ee_energy, (size_t)num_systems));
+        h->ee_cap = num_systems;
+    }
+    ADF_HIP_CHECK(hipMemcpyAsync(h->ee_energy, energy, sizeof(float) * num_systems, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    h->ee_B = num_systems;
+    return ADF_OK;
+}
+
+static int32_t eq_energy_term_ready(adf_eqv2* h, int B, hipStream_t s) {
+    if (h->ee_B > 0 && h->ee_B != B) {
+        adf_set_error("eqv2: energies were set for %lld systems, the batch has %d", (long long)h->ee_B, B);
+        return ADF_EINVAL;
+    }
+    if (h->ee_ready) return ADF_OK;
+    const int64_t rows = h->ee_B > 0 ? h->ee_B : 1;
+    if (rows > h->ee_term_rows) {
+        ADF_HIP_CHECK(hipDeviceSynchronize());
+        eq_free(h->ee_term);
+        h->ee_term_rows = 0;
+        ADF_TRY(eq_alloc(&h->ee_term, (size_t)rows * h->d.C));
+        h->ee_term_rows = rows;
+    }
+    ADF_TRY(eq_launch_energy_term(h->ee_wb, h->ee_B > 0 ? h->ee_energy : nullptr, (int)rows, h->d.C, h->ee_term, s));
+    h->ee_ready = true;
     return ADF_OK;
 }
 
@@ -969,6 +1026,7 @@ static int32_t eq_forward_impl(adf_eqv2* h, const adf_batch* b, float* f1, float
         ADF_TRY(eq_launch_check_z(h, Z, N, s));
     }
     h->lastN = N;
+    if (h->ee_on) ADF_TRY(eq_energy_term_ready(h, B, s));
     const size_t xs = (size_t)N * d.S * d.C;
     const int nl = h->hp.num_layers;
     // incremental blocks: only while the static-atom promise is in force (the same batch, only flagged atoms move)
@@ -999,7 +1057,8 @@ static int32_t eq_forward_impl(adf_eqv2* h, const adf_batch* b, float* f1, float
         const bool tab = h->rad_static && h->ed_rad.table;
         if (!tab) ADF_TRY(eq_radial(h, &h->ed_rad, h->ed_src_emb, h->ed_dst_emb, Z, n0, n1, Eub, &cb, cb.rad, N, s));
         eq_prof_scope ps(h, EQ_PROF_ROTATE, s);
-        ADF_TRY(eq_launch_edge_degree(h, tab ? h->ed_rad.table : cb.rad, Z, tab ? h->hp.max_num_elements : 0, n0, n1, X, s));
+        ADF_TRY(eq_launch_edge_degree(h, tab ? h->ed_rad.table : cb.rad, Z, tab ? h->hp.max_num_elements : 0, n0, n1, X, s,
+                                      h->ee_on ? h->ee_term : nullptr, b->batch, h->ee_B > 0 ? d.C : 0, B));
     }
     if (x_blocks) ADF_HIP_CHECK(hipMemcpyAsync(x_blocks, X, xs * 4, hipMemcpyDeviceToDevice, s));
     h->last_block_rows = 0;

@@ -390,12 +390,16 @@ int32_t eq_launch_ln_silu(float* x, const float* w, const float* b, long long ro
 // input_block.py:84-138: the radial MLP gives the m = 0 coefficients (l = 0..L) of every edge in its own frame; they are
 // rotated back (row m' = 0 of D_l, with the m-truncation rescale), summed per target, divided by the average degree, and
 // added to the element embedding on l = 0.  One workgroup per target, thread = channel.
-template <int LT>
+// COND (the conditional model, equiformer_v2_denoising.py:258-264,285): the l = 0 row is (emb[z] + term[system]) + edges,
+// the reference's order of additions; term_stride 0 = one row for every system (sampling mode).  COND = false is the
+// unconditional model's code, term / batch unread.
+template <int LT, bool COND>
 __global__ void eq_edge_degree_kernel(const float* __restrict__ m0, const float* __restrict__ wig,
                                       const int32_t* __restrict__ eptr, const int32_t* __restrict__ Z,
                                       const float* __restrict__ emb, int n0, int n1, eq_dims d, float inv_avg,
                                       int max_elem, float* __restrict__ x, int32_t* flags,
-                                      const int32_t* __restrict__ e_src, int pair_ne) {
+                                      const int32_t* __restrict__ e_src, int pair_ne, const float* __restrict__ term,
+                                      const int32_t* __restrict__ batch, int term_stride, int term_rows) {
     const int n = n0 + blockIdx.x, c = threadIdx.x;
     if (n >= n1 || c >= d.C) return;
     const long long ebase = eptr[n0];
@@ -419,19 +423,58 @@ __global__ void eq_edge_degree_kernel(const float* __restrict__ m0, const float*
     const int z = Z[n];
     if (z < 0 || z >= max_elem) { if (c == 0) atomicExch(&flags[4], 1); return; }
     float* xr = x + (size_t)n * d.S * d.C;
+    if (COND) {
+        const int sys = min(max(batch[n], 0), term_rows - 1);   // term_rows: the batch's systems
+        const float e0 = emb[(size_t)z * d.C + c] + term[(size_t)sys * term_stride + c];
+        xr[c] = acc[0] * inv_avg + e0;
+#pragma unroll
+        for (int s = 1; s < (LT + 1) * (LT + 1); ++s) xr[(size_t)s * d.C + c] = acc[s] * inv_avg + 0.f;
+        return;
+    }
 #pragma unroll
     for (int s = 0; s < (LT + 1) * (LT + 1); ++s) xr[(size_t)s * d.C + c] = acc[s] * inv_avg + (s == 0 ? emb[(size_t)z * d.C + c] : 0.f);
 }
 
 int32_t eq_launch_edge_degree(const adf_eqv2* h, const float* m0, const int32_t* Z, int pair_ne, int n0, int n1, float* x,
-                              hipStream_t s) {
+                              hipStream_t s, const float* term, const int32_t* batch, int term_stride, int term_rows) {
     if (n1 <= n0) return ADF_OK;
     const int bd = (h->d.C + 63) / 64 * 64;
-#define EQ_ED(LT_) hipLaunchKernelGGL(eq_edge_degree_kernel<LT_>, dim3(n1 - n0), dim3(bd), 0, s, m0, h->wig, h->eptr, Z, \
+#define EQ_ED(LT_) hipLaunchKernelGGL((eq_edge_degree_kernel<LT_, false>), dim3(n1 - n0), dim3(bd), 0, s, m0, h->wig, h->eptr, Z, \
                                       h->sphere_emb, n0, n1, h->d, 1.0f / h->hp.avg_degree, h->hp.max_num_elements, x, h->flags, \
-                                      h->e_src, pair_ne)
-    EQ_FOR_L(h->d.L, EQ_ED)
+                                      h->e_src, pair_ne, nullptr, nullptr, 0, 1)
+#define EQ_EDC(LT_) hipLaunchKernelGGL((eq_edge_degree_kernel<LT_, true>), dim3(n1 - n0), dim3(bd), 0, s, m0, h->wig, h->eptr, Z, \
+                                       h->sphere_emb, n0, n1, h->d, 1.0f / h->hp.avg_degree, h->hp.max_num_elements, x, h->flags, \
+                                       h->e_src, pair_ne, term, batch, term_stride, term_rows)
+    if (term) {
+        if (!batch || term_rows < 1) { adf_set_error("eqv2: the energy term needs the batch's node -> system map"); return ADF_EINVAL; }
+        EQ_FOR_L(h->d.L, EQ_EDC)
+    } else {
+        EQ_FOR_L(h->d.L, EQ_ED)
+    }
+#undef EQ_EDC
 #undef EQ_ED
+    ADF_HIP_CHECK(hipGetLastError());
+    return ADF_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ energy term
+// energy_embedding(node_wise_y.half()) of the conditional model (equiformer_v2_denoising.py:258-264): nn.Linear(1, C) in
+// fp16 - term[b, c] = fp16(fp16(e_b) * fp16(W_c) + fp16(b_c)).  The product of two fp16 values is exact in fp32, so the
+// one rounding after the bias is the layer's.  energy == null: e = 0 (sampling mode), rows = 1.  wb = [W (C) | b (C)].
+__global__ void eq_energy_term_kernel(const float* __restrict__ wb, const float* __restrict__ energy, int rows, int C,
+                                      float* __restrict__ term) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= rows * C) return;
+    const int r = i / C, c = i - r * C;
+    const float e = energy ? (float)(_Float16)energy[r] : 0.f;
+    const float w = (float)(_Float16)wb[c], b = (float)(_Float16)wb[C + c];
+    term[i] = (float)(_Float16)__fadd_rn(__fmul_rn(e, w), b);
+}
+
+int32_t eq_launch_energy_term(const float* wb, const float* energy, int rows, int C, float* term, hipStream_t s) {
+    if (rows <= 0) return ADF_OK;
+    const int n = rows * C;
+    hipLaunchKernelGGL(eq_energy_term_kernel, dim3((n + 255) / 256), dim3(256), 0, s, wb, energy, rows, C, term);
     ADF_HIP_CHECK(hipGetLastError());
     return ADF_OK;
 }

@@ -174,6 +174,8 @@ class Denoiser:
             prep = eng.prepare(batch)
             if prep.tags is None:
                 raise ValueError("batch.tags is required (tag 2 marks the adsorbate)")
+            if hasattr(eng, "bind_condition"):  # conditional EquiformerV2: batch.energy, once for the whole loop
+                eng.bind_condition(batch, prep.num_systems)
             B, N = prep.num_systems, prep.num_atoms
             T = int(params["num_steps"])
             ode = params.get("ode", True)

@@ -13,6 +13,12 @@ Supported configuration = what the repository ships (configs/denoising/eqv2_so3.
 ``use_attn_renorm=True``, ``use_gate_act=False``, ``use_grid_mlp=True``, ``use_sep_s2_act=True``,
 ``use_atom_edge_embedding=True``, ``share_atom_edge_embedding=False``, ``use_m_share_rad=False``, Gaussian distance
 expansion, ``grid_resolution`` given.  Anything else raises ``ValueError`` at construction.
+
+``energy_encoding="scalar"`` (configs/denoising/eqv2_conditional.yml) builds the conditional model: ``energy_embedding =
+nn.Linear(1, C)`` adds, per atom, a term of its system's energy to the l = 0 row of the node embedding
+(equiformer_v2_denoising.py:258-264) - zero energy when ``sampling``, else ``data.energy``.  The reference feeds that
+layer ``node_wise_y.half()``, so it runs in fp16 (its authors use --amp): the library evaluates
+``fp16(fp16(e) * fp16(W) + fp16(b))``; every other layer stays fp32.
 """
 from __future__ import annotations
 
@@ -219,9 +225,7 @@ class EquiformerV2S_OC20_DenoisingPos(nn.Module):
         if not (use_pbc and otf_graph and regress_forces and enforce_max_neighbors_strictly):
             bad.append("use_pbc = otf_graph = regress_forces = enforce_max_neighbors_strictly = True")
         if not FOR_denoising: bad.append("FOR_denoising=True (two force blocks)")
-        if energy_encoding is not None:
-            bad.append("energy_encoding=None (the reference's conditional EquiformerV2 only runs under CUDA autocast, "
-                       "equiformer_v2_denoising.py:263)")
+        if energy_encoding not in (None, "scalar"): bad.append("energy_encoding in {None, 'scalar'}")
         if weight_init not in ("normal", "uniform"): bad.append("weight_init in {'normal', 'uniform'}")
         if bad:
             raise ValueError("the HIP EquiformerV2 path implements the shipped configuration only; needs " + "; ".join(bad))
@@ -237,6 +241,7 @@ class EquiformerV2S_OC20_DenoisingPos(nn.Module):
         self.weight_init = weight_init
         self.avg_num_nodes, self.avg_degree = _AVG_NUM_NODES, _AVG_DEGREE
         self.so3_denoising, self.FOR_denoising, self.sampling = so3_denoising, FOR_denoising, sampling
+        self.energy_encoding = energy_encoding
         self.enforce_max_neighbors_strictly = enforce_max_neighbors_strictly
         lmax, mmax = self.lmax_list[0], self.mmax_list[0]
         normal = weight_init == "normal"
@@ -255,6 +260,10 @@ class EquiformerV2S_OC20_DenoisingPos(nn.Module):
         self.force_block = SO2EquivariantGraphAttention(sphere_channels, attn_hidden_channels, num_heads,
                                                         attn_alpha_channels, attn_value_channels, 1, lmax, mmax,
                                                         max_num_elements, ecl, normal)
+        if energy_encoding == "scalar":
+            # the conditional model (equiformer_v2_denoising.py:130-133), created between force_block and force_block2 as
+            # in the reference; its initialisation (zero bias) follows equiformer_v2_oc20.py:572-578
+            self.energy_embedding = _linear(1, sphere_channels, True, normal)
         self.force_block2 = SO2EquivariantGraphAttention(sphere_channels, attn_hidden_channels, num_heads,
                                                          attn_alpha_channels, attn_value_channels, 1, lmax, mmax,
                                                          max_num_elements, ecl, normal)
@@ -347,7 +356,8 @@ class EquiformerV2S_OC20_DenoisingPos(nn.Module):
         return key + (fp,)
 
     def forward(self, data):
-        """data: pos [N,3] f32, atomic_numbers [N], batch [N], natoms [B], cell [B,3,3] -> (forces [N,3], forces2 [N,3]):
-        the l = 1 coefficients (m = -1, 0, 1) of the two force blocks (equiformer_v2_denoising.py:307-318)."""
+        """data: pos [N,3] f32, atomic_numbers [N], batch [N], natoms [B], cell [B,3,3] (+ energy [B] for the conditional
+        model with ``sampling=False``) -> (forces [N,3], forces2 [N,3]): the l = 1 coefficients (m = -1, 0, 1) of the two
+        force blocks (equiformer_v2_denoising.py:307-318)."""
         eng = self.engine(data.pos.device)
         return eng.forward(data)

@@ -79,6 +79,8 @@ class EqV2Engine:
         self._weights_keepalive: List[torch.Tensor] = []
         self._moving_keepalive = None
         self._edges_keepalive = None
+        self._energy_keepalive = None
+        self._energy_mode = None   # what adf_eqv2_set_system_energy last received: None (never), "zeros", "given"
         import os
 
         self.exact_f32 = os.environ.get("ADF_GEMM") == "f32"
@@ -98,6 +100,48 @@ class EqV2Engine:
         ptrs = (C.c_void_p * len(out))(*[w.data_ptr() for w in out])
         with torch.cuda.device(self.device):
             _lib.check(self.lib.adf_eqv2_set_weights(self.handle, len(out), ptrs, self._stream()))
+        ee = getattr(self.model, "energy_embedding", None)
+        if ee is not None:  # the conditional model: nn.Linear(1, C), evaluated in fp16 by the library
+            wb = [t.detach().to(torch.float32).reshape(-1).contiguous() for t in (ee.weight, ee.bias)]
+            for t, n in zip(wb, ("energy_embedding.weight", "energy_embedding.bias")):
+                _require_gpu(t, f"parameter {n}")
+            self._weights_keepalive += wb
+            with torch.cuda.device(self.device):
+                _lib.check(self.lib.adf_eqv2_set_energy_embedding(self.handle, wb[0].data_ptr(), wb[1].data_ptr(),
+                                                                  self._stream()))
+
+    # ------------------------------------------------------------------ conditional model
+    def set_system_energy(self, energy: Optional[torch.Tensor]) -> None:
+        """Per-system energies [B] of the conditional model (adf_eqv2_set_system_energy); ``None``: zeros (sampling
+        mode).  Drops the incremental blocks' kept state."""
+        if energy is None:
+            self._energy_keepalive = None
+            _lib.check(self.lib.adf_eqv2_set_system_energy(self.handle, None, 0, self._stream()))
+            self._energy_mode = "zeros"
+            return
+        e = energy.to(self.device, torch.float32).reshape(-1).contiguous()
+        self._energy_keepalive = e
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.adf_eqv2_set_system_energy(self.handle, e.data_ptr(), int(e.numel()), self._stream()))
+        self._energy_mode = "given"
+
+    def bind_condition(self, data, num_systems: int) -> None:
+        """What the conditional model reads from a batch (equiformer_v2_denoising.py:258-264): nothing when
+        ``sampling`` (zero energies), else ``data.energy`` per system.  No-op for the unconditional model."""
+        if getattr(self.model, "energy_embedding", None) is None:
+            return
+        if self.model.sampling:
+            if self._energy_mode != "zeros":
+                self.set_system_energy(None)
+            return
+        energy = getattr(data, "energy", None)
+        if energy is None:
+            raise ValueError("the conditional EquiformerV2 (energy_encoding='scalar') with sampling=False reads "
+                             "data.energy (one value per system); the batch has none")
+        energy = torch.as_tensor(energy).reshape(-1)
+        if int(energy.numel()) != int(num_systems):
+            raise ValueError(f"data.energy has {int(energy.numel())} values for {int(num_systems)} systems")
+        self.set_system_energy(energy)
 
     # ------------------------------------------------------------------ batches
     def _stream(self) -> C.c_void_p:
@@ -180,6 +224,7 @@ class EqV2Engine:
 
     def forward(self, data, return_blocks: bool = False):
         prep = self.prepare(data)
+        self.bind_condition(data, prep.num_systems)
         pos = data.pos.to(torch.float32).contiguous()
         f1 = torch.empty(prep.num_atoms, 3, dtype=torch.float32, device=self.device)
         f2 = torch.empty_like(f1)

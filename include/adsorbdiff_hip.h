@@ -455,6 +455,18 @@ int32_t adf_eqv2_set_weights(adf_eqv2_t h, int32_t n_weights, const void* const*
 /* 0 = f16x3 split products on the f16 matrix cores where the shapes allow (default), 1 = exact f32 everywhere. */
 int32_t adf_eqv2_set_arithmetic(adf_eqv2_t h, int32_t exact_f32);
 
+/* The conditional model (energy_encoding "scalar", equiformer_v2_denoising.py:130-133,258-264): energy_embedding =
+ * nn.Linear(1, C), DEVICE float32 w [C] (weight [C,1]) and b [C], copied.  Every forward then adds to the l = 0 row of
+ * the node embedding, before the edge-degree embedding, the term fp16(fp16(e) * fp16(w) + fp16(b)) of the atom's
+ * system energy e - the reference's layer run in fp16 (node_wise_y.half(), as under its --amp).  w = b = NULL: the
+ * unconditional model (default); one of them NULL: ADF_EINVAL. */
+int32_t adf_eqv2_set_energy_embedding(adf_eqv2_t h, const float* w, const float* b, void* stream);
+/* The per-system energies e of the conditional model: DEVICE float32 [num_systems], copied; a forward on a batch of
+ * another system count returns ADF_EINVAL.  energy = NULL: e = 0 for every system (the reference's sampling mode;
+ * the default).  energy != NULL with num_systems < 1: ADF_EINVAL.  Either call drops the incremental blocks' kept
+ * state; the term table is built once by the next forward (one tiny launch), not per step of adf_eqv2_sample. */
+int32_t adf_eqv2_set_system_energy(adf_eqv2_t h, const float* energy, int32_t num_systems, void* stream);
+
 /* Use this edge list (source, target, vector target -> source image; target non-decreasing; DEVICE arrays, copied)
  * instead of building one, until adf_eqv2_set_edges(h, 0, ...) — parity tests against reference runs whose pick among
  * exactly tied K-th neighbours is implementation-defined. */
