@@ -625,8 +625,10 @@ __global__ void adf_scatter_rows3_kernel(const float* __restrict__ src, const in
     if (i < 3 * n) dst[(size_t)idx[i / 3] * 3 + i % 3] = src[i];
 }
 
+// head1_only (internal: the translation-only samplers read head 1 alone): f2 may be NULL and no out_forces2 product runs;
+// f1 is bit-identical to the two-head forward's
 static int32_t forward_impl(adf_painn_t h, const adf_batch* b, const int32_t* out_idx, int32_t n_out, float* f1,
-                            float* f2, void* stream);
+                            float* f2, void* stream, bool head1_only = false);
 
 extern "C" int32_t adf_painn_forward(adf_painn_t h, const adf_batch* b, float* f1, float* f2, void* stream) {
     return forward_impl(h, b, nullptr, 0, f1, f2, stream);
@@ -731,7 +733,7 @@ static int32_t inc_harvest(adf_painn* h, int slot, bool wait, bool peek = false)
 
 // One forward on the kept per-layer state.  The graph of this step is built; prev_* hold the previous build's CSR.
 static int32_t forward_incremental(adf_painn* h, int N, const int32_t* Z, const int32_t* out_idx, int32_t n_out,
-                                   float* f1, float* f2, bool first, hipStream_t s) {
+                                   float* f1, float* f2, bool first, int heads, hipStream_t s) {
     const int L = h->hp.num_layers, H = h->hp.hidden_channels;
     const size_t cap = (size_t)h->inc_capN, row = (size_t)5 * H;
     if (out_idx && n_out == 0) return ADF_OK;  // nothing wanted; the state stays invalid (this build was not applied)
@@ -798,7 +800,7 @@ static int32_t forward_incremental(adf_painn* h, int N, const int32_t* Z, const 
     adf_prof_begin(h, ADF_PROF_HEADS, s);
     if (!out_idx) {
         ADF_TRY(adf_head_forward(h, 0, N, h->incX[L], h->incV[L], f1, s));
-        if (h->hp.num_heads == 2) ADF_TRY(adf_head_forward(h, 1, N, h->incX[L], h->incV[L], f2, s));
+        if (heads == 2) ADF_TRY(adf_head_forward(h, 1, N, h->incX[L], h->incV[L], f2, s));
     } else {
         if (n_out > h->capS) {
             const int64_t c = (int64_t)n_out + n_out / 4 + 64;
@@ -813,7 +815,7 @@ static int32_t forward_incremental(adf_painn* h, int N, const int32_t* Z, const 
         }
         ADF_TRY(adf_inc_gather_rows(h->incX[L], out_idx, n_out, H, h->sub_x, s));
         ADF_TRY(adf_inc_gather_rows(h->incV[L], out_idx, n_out, 3 * H, h->sub_vec, s));
-        for (int hd = 0; hd < h->hp.num_heads; ++hd) {
+        for (int hd = 0; hd < heads; ++hd) {
             ADF_TRY(adf_head_forward(h, hd, n_out, h->sub_x, h->sub_vec, h->sub_f, s));
             hipLaunchKernelGGL(adf_scatter_rows3_kernel, dim3((3 * n_out + 255) / 256), dim3(256), 0, s, h->sub_f, out_idx,
                                n_out, hd == 0 ? f1 : f2);
@@ -826,10 +828,11 @@ static int32_t forward_incremental(adf_painn* h, int N, const int32_t* Z, const 
 }
 
 static int32_t forward_impl(adf_painn_t h, const adf_batch* b, const int32_t* out_idx, int32_t n_out, float* f1,
-                            float* f2, void* stream) {
+                            float* f2, void* stream, bool head1_only) {
     ADF_TRY(check_batch(h, b));
     if (!h->weights_set) { adf_set_error("weights not set"); return ADF_EINVAL; }
-    if (!b->atomic_numbers || !f1 || (h->hp.num_heads == 2 && !f2)) { adf_set_error("null argument"); return ADF_EINVAL; }
+    const int heads = head1_only ? 1 : h->hp.num_heads;
+    if (!b->atomic_numbers || !f1 || (heads == 2 && !f2)) { adf_set_error("null argument"); return ADF_EINVAL; }
     hipStream_t s = (hipStream_t)stream;
     const int N = b->num_atoms;
     ADF_TRY(ensure_capacity(h, N, b->num_systems));
@@ -839,7 +842,7 @@ static int32_t forward_impl(adf_painn_t h, const adf_batch* b, const int32_t* ou
     adf_prof_end(h, s);
     if (inc) {
         h->inc_serial = h->build_serial;
-        return forward_incremental(h, N, b->atomic_numbers, out_idx, n_out, f1, f2, inc == 2, s);
+        return forward_incremental(h, N, b->atomic_numbers, out_idx, n_out, f1, f2, inc == 2, heads, s);
     }
     ADF_TRY(zero_pad_rows(h, N, s));
     ADF_TRY(adf_nodewise_embed(h, b->atomic_numbers, N, h->x, s));  // vec = 0 is implicit in layer 0
@@ -872,7 +875,7 @@ static int32_t forward_impl(adf_painn_t h, const adf_batch* b, const int32_t* ou
         }
         adf_prof_begin(h, ADF_PROF_HEADS, s);
         ADF_TRY(adf_head_forward(h, 0, N, h->x, vin, f1, s));
-        if (h->hp.num_heads == 2) ADF_TRY(adf_head_forward(h, 1, N, h->x, vin, f2, s));
+        if (heads == 2) ADF_TRY(adf_head_forward(h, 1, N, h->x, vin, f2, s));
         adf_prof_end(h, s);
         return ADF_OK;
     }
@@ -903,7 +906,7 @@ static int32_t forward_impl(adf_painn_t h, const adf_batch* b, const int32_t* ou
                           L == 1 ? rec0 : nullptr, L == 1 && rec0_ready));
     ADF_TRY(update_layer(h, L - 1, n_out, h->sub_x, h->sub_vec, s));
     adf_prof_begin(h, ADF_PROF_HEADS, s);
-    for (int hd = 0; hd < h->hp.num_heads; ++hd) {
+    for (int hd = 0; hd < heads; ++hd) {
         ADF_TRY(adf_head_forward(h, hd, n_out, h->sub_x, h->sub_vec, h->sub_f, s));
         hipLaunchKernelGGL(adf_scatter_rows3_kernel, dim3((3 * n_out + 255) / 256), dim3(256), 0, s, h->sub_f, out_idx,
                            n_out, hd == 0 ? f1 : f2);
@@ -1073,6 +1076,65 @@ extern "C" int32_t adf_sample_traj(adf_painn_t h, const adf_batch* b, float* pos
     if (!sink) { adf_set_error("sample_traj: null sink"); return ADF_EINVAL; }
     return sample_impl(h, b, pos, tags, fixed, coefs_dev, num_steps, z_tr_all, z_rot_all, early_stop_count, poll_every, state,
                        out_idx, n_out, f1, f2, sink, frame_every, stream);
+}
+
+// Translation-only samplers (reverse_sde_sampling / langevin_dynamics, denoising_torch.py:96-196, 369-458)
+extern "C" int32_t adf_tr_step(adf_painn_t h, const adf_batch* b, float* pos, const int32_t* tags, const float* f1,
+                               const adf_tr_coef* coef, const adf_tr_coef* coefs_dev, int32_t num_steps, const float* z,
+                               int32_t early_stop_count, int32_t* state, float* dcom, void* stream) {
+    ADF_TRY(check_batch(h, b));
+    if (!pos || !tags || !f1 || (!coef && !coefs_dev) || !state) { adf_set_error("tr_step: null argument"); return ADF_EINVAL; }
+    if (!coef && num_steps <= 0) { adf_set_error("tr_step: num_steps must be positive"); return ADF_EINVAL; }
+    ADF_TRY(ensure_capacity(h, b->num_atoms, b->num_systems));
+    adf_prof_begin(h, ADF_PROF_STEPPER, (hipStream_t)stream);
+    const int32_t st = adf_stepper_tr_step(h->sys, b, pos, tags, f1, coef, coefs_dev, num_steps, z, early_stop_count, state,
+                                           dcom, (hipStream_t)stream);
+    adf_prof_end(h, (hipStream_t)stream);
+    return st;
+}
+
+static int32_t tr_sample_impl(adf_painn_t h, const adf_batch* b, float* pos, const int32_t* tags,
+                              const adf_tr_coef* coefs_dev, int32_t num_steps, const float* z_all, int32_t early_stop_count,
+                              int32_t poll_every, int32_t* state, const int32_t* out_idx, int32_t n_out, float* f1,
+                              adf_frames* sink, int32_t frame_every, void* stream) {
+    ADF_TRY(check_batch(h, b));
+    if (num_steps <= 0 || !f1 || !state || !coefs_dev || !pos || !tags || (out_idx && n_out < 0)) {
+        adf_set_error("tr_sample: bad argument");
+        return ADF_EINVAL;
+    }
+    if (sink && frame_every <= 0) { adf_set_error("tr_sample: frame_every must be positive"); return ADF_EINVAL; }
+    hipStream_t s = (hipStream_t)stream;
+    const size_t zs = (size_t)b->num_systems * 3;
+    for (int t = 0; t < num_steps; ++t) {
+        ADF_TRY(forward_impl(h, b, out_idx, out_idx ? n_out : 0, f1, nullptr, stream, true));
+        ADF_TRY(adf_tr_step(h, b, pos, tags, f1, nullptr, coefs_dev, num_steps, z_all ? z_all + t * zs : nullptr,
+                            early_stop_count, state, nullptr, stream));
+        if (sink && ((t + 1) % frame_every == 0 || t + 1 == num_steps)) ADF_TRY(adf_frames_push_impl(sink, pos, s));
+        if (early_stop_count > 0 && poll_every > 0 && (t % poll_every) == poll_every - 1 && t + 1 < num_steps) {
+            int32_t frozen = 0;
+            ADF_HIP_CHECK(hipMemcpyAsync(&frozen, state + 1, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+            ADF_HIP_CHECK(hipStreamSynchronize(s));
+            if (frozen) break;
+        }
+    }
+    return ADF_OK;
+}
+
+extern "C" int32_t adf_tr_sample(adf_painn_t h, const adf_batch* b, float* pos, const int32_t* tags,
+                                 const adf_tr_coef* coefs_dev, int32_t num_steps, const float* z_all,
+                                 int32_t early_stop_count, int32_t poll_every, int32_t* state, const int32_t* out_idx,
+                                 int32_t n_out, float* f1, void* stream) {
+    return tr_sample_impl(h, b, pos, tags, coefs_dev, num_steps, z_all, early_stop_count, poll_every, state, out_idx, n_out,
+                          f1, nullptr, 0, stream);
+}
+
+extern "C" int32_t adf_tr_sample_traj(adf_painn_t h, const adf_batch* b, float* pos, const int32_t* tags,
+                                      const adf_tr_coef* coefs_dev, int32_t num_steps, const float* z_all,
+                                      int32_t early_stop_count, int32_t poll_every, int32_t* state, const int32_t* out_idx,
+                                      int32_t n_out, float* f1, adf_frames_t sink, int32_t frame_every, void* stream) {
+    if (!sink) { adf_set_error("tr_sample_traj: null sink"); return ADF_EINVAL; }
+    return tr_sample_impl(h, b, pos, tags, coefs_dev, num_steps, z_all, early_stop_count, poll_every, state, out_idx, n_out,
+                          f1, sink, frame_every, stream);
 }
 
 extern "C" int32_t adf_get_counters(adf_painn_t h, adf_counters* out, void* stream) {

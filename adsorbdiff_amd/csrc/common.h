@@ -274,3 +274,8 @@ int32_t adf_stepper_step(float* sys, const adf_batch* b, float* pos, const int32
                          const float* f1, const float* f2, const adf_step_coef* coef, const adf_step_coef* coefs_dev,
                          int num_steps, const float* z_tr, const float* z_rot, int32_t early_stop_count,
                          int32_t* state, float* dcom, float* drot, hipStream_t s);
+// translation-only samplers (reverse_sde_sampling / langevin_dynamics): head-1 mean, dcom = coef * score (+ noise * z),
+// wrap, pos += dcom on the adsorbate; same state[] protocol as adf_stepper_step
+int32_t adf_stepper_tr_step(float* sys, const adf_batch* b, float* pos, const int32_t* tags, const float* f1,
+                            const adf_tr_coef* coef, const adf_tr_coef* coefs_dev, int num_steps, const float* z,
+                            int32_t early_stop_count, int32_t* state, float* dcom, hipStream_t s);

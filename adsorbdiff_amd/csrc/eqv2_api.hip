@@ -1237,6 +1237,65 @@ extern "C" int32_t adf_eqv2_sample_traj(adf_eqv2_t h, const adf_batch* b, float*
                           state, out_idx, n_out, f1, f2, sink, frame_every, stream);
 }
 
+// Translation-only samplers (reverse_sde_sampling / langevin_dynamics, denoising_torch.py:96-196, 369-458): force_block
+// alone is evaluated (f2 = NULL skips force_block2 in eq_forward_impl; f1 is bit-identical to the two-block forward's)
+extern "C" int32_t adf_eqv2_tr_step(adf_eqv2_t h, const adf_batch* b, float* pos, const int32_t* tags, const float* f1,
+                                    const adf_tr_coef* coef, const adf_tr_coef* coefs_dev, int32_t num_steps, const float* z,
+                                    int32_t early_stop_count, int32_t* state, float* dcom, void* stream) {
+    ADF_TRY(eq_check_batch(h, b));
+    if (!pos || !tags || !f1 || (!coef && !coefs_dev) || !state) { adf_set_error("eqv2_tr_step: null argument"); return ADF_EINVAL; }
+    if (!coef && num_steps <= 0) { adf_set_error("eqv2_tr_step: num_steps must be positive"); return ADF_EINVAL; }
+    ADF_TRY(eq_ensure_capacity(h, b->num_atoms, b->num_systems, h->ext_graph ? h->E_ext : 0));
+    eq_prof_scope ps(h, EQ_PROF_STEPPER, (hipStream_t)stream);
+    return adf_stepper_tr_step(h->sys, b, pos, tags, f1, coef, coefs_dev, num_steps, z, early_stop_count, state, dcom,
+                               (hipStream_t)stream);
+}
+
+static int32_t eq_tr_sample_impl(adf_eqv2_t h, const adf_batch* b, float* pos, const int32_t* tags,
+                                 const adf_tr_coef* coefs_dev, int32_t num_steps, const float* z_all,
+                                 int32_t early_stop_count, int32_t poll_every, int32_t* state, const int32_t* out_idx,
+                                 int32_t n_out, float* f1, adf_frames* sink, int32_t frame_every, void* stream) {
+    ADF_TRY(eq_check_batch(h, b));
+    if (num_steps <= 0 || !f1 || !state || !coefs_dev || !pos || !tags || (out_idx && n_out < 0)) {
+        adf_set_error("eqv2_tr_sample: bad argument");
+        return ADF_EINVAL;
+    }
+    if (sink && frame_every <= 0) { adf_set_error("eqv2_tr_sample: frame_every must be positive"); return ADF_EINVAL; }
+    hipStream_t s = (hipStream_t)stream;
+    const size_t zs = (size_t)b->num_systems * 3;
+    for (int t = 0; t < num_steps; ++t) {
+        ADF_TRY(eq_forward_impl(h, b, f1, nullptr, nullptr, s, out_idx, n_out));
+        ADF_TRY(adf_eqv2_tr_step(h, b, pos, tags, f1, nullptr, coefs_dev, num_steps, z_all ? z_all + t * zs : nullptr,
+                                 early_stop_count, state, nullptr, stream));
+        if (sink && ((t + 1) % frame_every == 0 || t + 1 == num_steps)) ADF_TRY(adf_frames_push_impl(sink, pos, s));
+        if (early_stop_count > 0 && poll_every > 0 && (t % poll_every) == poll_every - 1 && t + 1 < num_steps) {
+            int32_t frozen = 0;
+            ADF_HIP_CHECK(hipMemcpyAsync(&frozen, state + 1, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+            ADF_HIP_CHECK(hipStreamSynchronize(s));
+            if (frozen) break;
+        }
+    }
+    return ADF_OK;
+}
+
+extern "C" int32_t adf_eqv2_tr_sample(adf_eqv2_t h, const adf_batch* b, float* pos, const int32_t* tags,
+                                      const adf_tr_coef* coefs_dev, int32_t num_steps, const float* z_all,
+                                      int32_t early_stop_count, int32_t poll_every, int32_t* state, const int32_t* out_idx,
+                                      int32_t n_out, float* f1, void* stream) {
+    return eq_tr_sample_impl(h, b, pos, tags, coefs_dev, num_steps, z_all, early_stop_count, poll_every, state, out_idx,
+                             n_out, f1, nullptr, 0, stream);
+}
+
+extern "C" int32_t adf_eqv2_tr_sample_traj(adf_eqv2_t h, const adf_batch* b, float* pos, const int32_t* tags,
+                                           const adf_tr_coef* coefs_dev, int32_t num_steps, const float* z_all,
+                                           int32_t early_stop_count, int32_t poll_every, int32_t* state,
+                                           const int32_t* out_idx, int32_t n_out, float* f1, adf_frames_t sink,
+                                           int32_t frame_every, void* stream) {
+    if (!sink) { adf_set_error("eqv2_tr_sample_traj: null sink"); return ADF_EINVAL; }
+    return eq_tr_sample_impl(h, b, pos, tags, coefs_dev, num_steps, z_all, early_stop_count, poll_every, state, out_idx,
+                             n_out, f1, sink, frame_every, stream);
+}
+
 // Stand-alone C = act(A . W^T + b) through the dense-product kernels of this path (unit tests, micro-benchmarks).
 // mode 0: exact f32 (any shape); 1: f16x3 with per-row lifts, fp32 A staged and split in the kernel; 2: f16x3 on
 // pre-split fp16 hi / lo rows (eq_gemm16p_kernel).  `repeat` > 1 re-runs the product kernel alone (timing).

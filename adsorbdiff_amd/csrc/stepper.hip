@@ -217,6 +217,102 @@ int32_t adf_stepper_step(float* sys, const adf_batch* b, float* pos, const int32
     return ADF_OK;
 }
 
+// ------------------------------------------------------------------------------------------ translation-only samplers
+// Reference: denoising_torch.py
+//   :96-196   reverse_sde_sampling  (probability-flow ODE: dcom = 0.5 g^2 dt * score)
+//   :369-458  langevin_dynamics     (dcom = step_size * score + sqrt(2 step_size) * z, per noise level x inner step)
+// Both take the per-system mean of head 1 over the tag-2 atoms (:460-467; no fixed-atom zeroing, that is head 2's),
+// zero the z of the increment, wrap the COM exactly as adf_step_reduce_kernel does, and then add dcom to the adsorbate
+// positions (set_positions, :52-56: `pos += update.float()`), not the rot sampler's ((pos - c) R^T + t) + c.
+struct TrParams {
+    const float* cell;
+    const int32_t* atom_offset;
+    const int32_t* tags;
+    float* pos;
+    const float* f1;
+    const float* z;      // [B][3] standard normals (Langevin) or NULL (ODE)
+    float* sys;          // [B][16]: com(3) dcom(3)
+    int32_t* state;
+    float* dcom_out;
+    adf_tr_coef c;
+    const adf_tr_coef* coefs_dev;  // optional schedule table on the device, indexed by state[4]
+    int num_steps;
+};
+
+__global__ __launch_bounds__(64) void adf_tr_reduce_kernel(TrParams p) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int a0 = p.atom_offset[b], a1 = p.atom_offset[b + 1];
+    float s[7];
+#pragma unroll
+    for (int i = 0; i < 7; ++i) s[i] = 0.f;
+    for (int a = a0 + lane; a < a1; a += 64)
+        if (p.tags[a] == 2) {
+            s[0] += p.pos[3 * a]; s[1] += p.pos[3 * a + 1]; s[2] += p.pos[3 * a + 2];
+            s[3] += p.f1[3 * a]; s[4] += p.f1[3 * a + 1]; s[5] += p.f1[3 * a + 2];
+            s[6] += 1.f;
+        }
+#pragma unroll
+    for (int i = 0; i < 7; ++i) s[i] = wsum(s[i]);
+    if (lane != 0) return;
+    const float cnt = fmaxf(s[6], 1.0f);
+    adf_tr_coef c = p.c;
+    if (p.coefs_dev) c = p.coefs_dev[min(p.state[4], p.num_steps - 1)];
+    float com[3], dcom[3];
+    for (int k = 0; k < 3; ++k) {
+        com[k] = s[k] / cnt;
+        float d = __fmul_rn(c.coef, s[3 + k] / cnt);
+        // Langevin: noise = randn * sqrt(2 step_size) is its own f32 tensor, then added (:417-421)
+        if (p.z) d = __fadd_rn(d, __fmul_rn(c.noise, p.z[3 * b + k]));
+        dcom[k] = d;
+    }
+    dcom[2] = 0.f;
+    const float* cl = p.cell + 9 * b;
+    float tgt[3] = {__fadd_rn(com[0], dcom[0]), __fadd_rn(com[1], dcom[1]), __fadd_rn(com[2], dcom[2])};
+    float fr[3];
+    solve3(cl, tgt, fr);
+    for (int k = 0; k < 3; ++k) fr[k] = pymod1(pymod1(fr[k]));
+    bool conv = true;
+    for (int j = 0; j < 3; ++j) {
+        const float w = cl[3 * j] * fr[0] + cl[3 * j + 1] * fr[1] + cl[3 * j + 2] * fr[2];
+        dcom[j] = w - com[j];
+        conv = conv && (fabsf(dcom[j]) <= 1.0e-3f);
+    }
+    float* o = p.sys + 16 * b;
+    for (int k = 0; k < 3; ++k) { o[k] = com[k]; o[3 + k] = dcom[k]; }
+    if (!conv) atomicAnd(&p.state[2], 0);
+    if (p.dcom_out) for (int k = 0; k < 3; ++k) p.dcom_out[3 * b + k] = dcom[k];
+}
+
+__global__ __launch_bounds__(64) void adf_tr_apply_kernel(TrParams p) {
+    if (p.state[1]) return;  // the reference's `break`
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int a0 = p.atom_offset[b], a1 = p.atom_offset[b + 1];
+    const float* o = p.sys + 16 * b;
+    const float tx = o[3], ty = o[4], tz = o[5];
+    for (int a = a0 + lane; a < a1; a += 64)
+        if (p.tags[a] == 2) {
+            p.pos[3 * a] = __fadd_rn(p.pos[3 * a], tx);
+            p.pos[3 * a + 1] = __fadd_rn(p.pos[3 * a + 1], ty);
+            p.pos[3 * a + 2] = __fadd_rn(p.pos[3 * a + 2], tz);
+        }
+}
+
+int32_t adf_stepper_tr_step(float* sys, const adf_batch* b, float* pos, const int32_t* tags, const float* f1,
+                            const adf_tr_coef* coef, const adf_tr_coef* coefs_dev, int num_steps, const float* z,
+                            int32_t early_stop_count, int32_t* state, float* dcom, hipStream_t s) {
+    TrParams p;
+    p.cell = b->cell; p.atom_offset = b->atom_offset; p.tags = tags; p.pos = pos; p.f1 = f1; p.z = z; p.sys = sys;
+    p.state = state; p.dcom_out = dcom;
+    if (coef) p.c = *coef; else p.c = adf_tr_coef{};
+    p.coefs_dev = coef ? nullptr : coefs_dev; p.num_steps = num_steps;
+    const int B = b->num_systems;
+    hipLaunchKernelGGL(adf_tr_reduce_kernel, dim3(B), dim3(64), 0, s, p);
+    hipLaunchKernelGGL(adf_step_decide_kernel, dim3(1), dim3(64), 0, s, state, early_stop_count);
+    hipLaunchKernelGGL(adf_tr_apply_kernel, dim3(B), dim3(64), 0, s, p);
+    ADF_HIP_CHECK(hipGetLastError());
+    return ADF_OK;
+}
+
 // Hand-off rule of the reference's final-frame -> LMDB converter (scripts/create_lmdbs/pred_traj_to_lmdb.py:81-90): if the
 // lowest adsorbate atom (tag 2) is less than `min_gap` above the highest surface atom (tag 1), the whole adsorbate is
 // lifted by |diff| + min_gap.  One wave per system, in place; lifted[b] (optional) = applied shift.

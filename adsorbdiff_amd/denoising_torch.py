@@ -34,6 +34,12 @@ Extensions (all optional, defaults reproduce the reference):
   * ``denoising_pos_params["placement_noise"]`` (default None): ``[B,3]`` uniforms for the initial placement instead
     of ``torch.rand(B,3)`` from the CPU generator (:215) — a sharded run that indexes one global table by system id
     samples exactly what the single-process run samples.
+  * ``denoising_pos_params["sampler"]`` (default ``"sde_rot"``): what ``run()`` calls - ``"sde_rot"``
+    ``reverse_sde_sampling_rot`` (the reference's ``run``), ``"sde"`` ``reverse_sde_sampling``, ``"langevin"``
+    ``langevin_dynamics``; any other value raises ``ValueError``.
+  * ``denoising_pos_params["langevin_noise"]`` (default None): ``[num_steps * n_step_each, B, 3]`` standard normals for
+    ``langevin_dynamics`` instead of the device generator's ``randn_like`` per inner step (a sharded run slices one global
+    table by system id, as with ``placement_noise``).
   * ``traj_dir=None`` is allowed (the reference crashes in ``write``); with a ``traj_dir`` the
     frames are kept on the device during the loop and written once at the end.
 """
@@ -79,6 +85,45 @@ def schedule_coefs(params: dict) -> List[_lib.StepCoef]:
             c.noise_tr = float(tr_g * sqrt_dt)
             c.noise_rot = float((rot_g * sqrt_dt).to(torch.float32))
         out.append(c)
+    return out
+
+
+def ode_tr_coefs(params: dict) -> List[_lib.TrCoef]:
+    """Per-step scalars of ``reverse_sde_sampling`` (probability-flow ODE, reference :101-107, 139-150): coef =
+    0.5 * g_tr^2 * dt with the reference's 0-dim f32 tensor arithmetic - the ``coef_tr`` of ``schedule_coefs`` with
+    ``ode``, without reading the rotation keys."""
+    lo, hi = params["ads_std_low"], params["ads_std_high"]
+    T = int(params["num_steps"])
+    sched = torch.tensor(np.linspace(1, 0, T + 1)[:-1], dtype=torch.float32)
+    out = []
+    for t_idx in range(T):
+        sigma = lo ** (1 - sched[t_idx]) * hi ** sched[t_idx]
+        tr_g = sigma * (2 * np.log(hi / lo)) ** 0.5
+        dt = sched[t_idx] - sched[t_idx + 1] if t_idx < T - 1 else sched[t_idx]
+        c = _lib.TrCoef()
+        c.coef = float(0.5 * tr_g**2 * dt)
+        c.noise = 0.0
+        out.append(c)
+    return out
+
+
+def langevin_coefs(params: dict) -> List[_lib.TrCoef]:
+    """Per-inner-step scalars of ``langevin_dynamics`` (reference :376-421): for each noise level sigma of
+    f32(exp(linspace(log hi, log lo, num_steps))), ``n_step_each`` rows of (step_size, sqrt(2 * step_size)) with
+    step_size = step_lr * (sigma / sigma_min)^2, all f32 as there.  ``n_step_each`` / ``step_lr`` missing: KeyError."""
+    lo, hi = params["ads_std_low"], params["ads_std_high"]
+    T = int(params["num_steps"])
+    n_each = int(params["n_step_each"])
+    step_lr = params["step_lr"]
+    sigmas = torch.tensor(np.exp(np.linspace(np.log(hi), np.log(lo), T)), dtype=torch.float32)
+    out = []
+    for sigma in sigmas:
+        step_size = step_lr * (sigma / sigmas[-1]) ** 2
+        noise = torch.sqrt(step_size * 2)
+        for _ in range(n_each):
+            c = _lib.TrCoef()
+            c.coef, c.noise = float(step_size), float(noise)
+            out.append(c)
     return out
 
 
@@ -138,8 +183,18 @@ class Denoiser:
             raise NotImplementedError("the HIP sampling path requires otf_graph=True")
 
     # ------------------------------------------------------------------ public
+    SAMPLERS = ("sde_rot", "sde", "langevin")
+
     def run(self):
-        self.reverse_sde_sampling_rot()
+        sampler = self.denoising_pos_params.get("sampler", "sde_rot")
+        if sampler not in self.SAMPLERS:
+            raise ValueError(f"denoising_pos_params['sampler'] = {sampler!r}: expected one of {self.SAMPLERS}")
+        if sampler == "sde":
+            self.reverse_sde_sampling()
+        elif sampler == "langevin":
+            self.langevin_dynamics()
+        else:
+            self.reverse_sde_sampling_rot()
         return self.batch
 
     # ------------------------------------------------------------------ loop
@@ -327,6 +382,163 @@ class Denoiser:
                 self.wait_for_trajectories()   # like the reference: the files exist when run() returns
             B_ = B
             batch.y = torch.zeros(B_, device=dev)
+            batch.force = torch.zeros(N, 3, device=dev)
+        finally:
+            try:
+                self._engine().set_moving_atoms(None, None)
+            except Exception:
+                pass
+            if ema:
+                ema.restore()
+
+    # ------------------------------------------------------------------ translation-only samplers
+    def reverse_sde_sampling(self):
+        """The reference's translation-only probability-flow ODE (denoising_torch.py:96-196): no noise term whatever
+        ``ode`` says, the cumulative early stop of ``reverse_sde_sampling_rot`` (``early_stop`` switch as there), and
+        ``pos += dcom`` on the adsorbate.  Reads head 1 only, so a single-head PaiNN works too (the reference unpacks two
+        outputs there and fails for one)."""
+        params = self.denoising_pos_params
+        if "ads_std_low" not in params:
+            return
+        coefs = ode_tr_coefs(params)
+        self._tr_sampling(coefs, False, None, 10 if params.get("early_stop", True) else 0)
+
+    def langevin_dynamics(self):
+        """The reference's annealed Langevin dynamics (denoising_torch.py:369-458): ``num_steps`` noise levels x
+        ``n_step_each`` inner steps of dcom = step_size * score + sqrt(2 step_size) * z, no early stop, one trajectory
+        frame per inner step.  The score is head 1 (``positions``) for one- and two-head models alike (the reference
+        hands a two-head model's tuple to ``_get_ads_output`` and raises TypeError).  z: ``langevin_noise`` if given,
+        else drawn on the device generator, one ``normal_()`` per inner step as the reference's ``randn_like``."""
+        params = self.denoising_pos_params
+        if "ads_std_low" not in params:
+            return
+        coefs = langevin_coefs(params)
+        self._tr_sampling(coefs, True, params.get("langevin_noise"), 0)
+
+    def _tr_sampling(self, coefs, langevin: bool, noise_table, early: int) -> None:
+        """Shared frame of the translation-only samplers (the frame of ``reverse_sde_sampling_rot``: eval + EMA, initial
+        placement, static-atom cache, fused loop or per-step path, exact-f32 retry, trajectories)."""
+        params = self.denoising_pos_params
+        trainer = self.model.model
+        dev = torch.device(self.device)
+        trainer._unwrapped_model.eval()
+        ema = getattr(trainer, "ema", None)
+        if ema:
+            ema.store()
+            ema.copy_to()
+        try:
+            eng = self._engine()
+            batch = self.batch.to(dev)
+            if batch.pos.dtype != torch.float32 or not batch.pos.is_contiguous():
+                batch.pos = batch.pos.to(torch.float32).contiguous()
+            pos = batch.pos
+            prep = eng.prepare(batch)
+            if prep.tags is None:
+                raise ValueError("batch.tags is required (tag 2 marks the adsorbate)")
+            if hasattr(eng, "bind_condition"):
+                eng.bind_condition(batch, prep.num_systems)
+            B, N = prep.num_systems, prep.num_atoms
+            T = len(coefs)
+            z_all = None
+            if langevin:
+                if noise_table is None:  # device generator, one randn_like([B,3]) per inner step (reference :417)
+                    z_all = torch.empty(T, B, 3, dtype=torch.float32, device=dev)
+                    for t_idx in range(T):
+                        z_all[t_idx].normal_()
+                else:  # extension: caller-supplied standard normals
+                    z_all = torch.as_tensor(noise_table, dtype=torch.float32)
+                    if tuple(z_all.shape) != (T, B, 3):
+                        raise ValueError(f"langevin_noise has shape {tuple(z_all.shape)}, expected {(T, B, 3)}")
+                    z_all = z_all.to(dev).contiguous()
+            noise = params.get("placement_noise")
+            if noise is None:
+                noise = torch.rand(B, 3)
+            else:
+                noise = torch.as_tensor(noise, dtype=torch.float32).reshape(B, 3).cpu()
+            eng.init_placement(prep, pos, noise.to(dev))
+            if params.get("static_atom_cache", True):
+                eng.set_moving_atoms(prep, prep.tags == 2)
+            eng.set_incremental(bool(params.get("incremental_layers", True)))
+            coefs_dev = torch.tensor([[c.coef, c.noise] for c in coefs], dtype=torch.float32, device=dev)
+            two_heads = getattr(eng, "num_heads", 2) == 2   # EquiformerV2: always both force blocks
+            pos0 = pos.clone()
+
+            def attempt():
+                f1 = torch.zeros(N, 3, dtype=torch.float32, device=dev)
+                state = torch.tensor([0, 0, 1, 0, 0, 0, 0, 0], dtype=torch.int32, device=dev)
+                frames = [] if self.traj_dir else None
+                sink = writer = None
+                check_every = 1 if B <= 8 else 5
+                step_hook = params.get("step_hook")   # callable(t) after every step: per-step path
+                fused_loop = step_hook is None
+                ads_only = params.get("scores_on_adsorbate_only")
+                if ads_only is None:
+                    ads_only = fused_loop
+                out_idx = torch.nonzero(prep.tags == 2).reshape(-1).to(torch.int32).contiguous() if ads_only else None
+                if fused_loop:
+                    if frames is not None:
+                        from .trajectory import FrameSink, TrajectoryWriter
+
+                        frames = None
+                        sink = FrameSink(dev.index if dev.index is not None else torch.cuda.current_device(), N,
+                                         slots=int(params.get("trajectory_ring_slots", 8)))
+                        writer = TrajectoryWriter(sink, self.traj_dir, self._traj_meta(batch), T if self.save_full else 1)
+                        writer.start()
+                    try:
+                        eng.tr_sample(prep, pos, f1, coefs_dev, T, state, z_all, early_stop_count=early,
+                                      poll_every=check_every if early else 0, out_idx=out_idx,
+                                      sink=sink if (sink is not None and self.save_full) else None, frame_every=1)
+                        if sink is not None and not self.save_full:
+                            with torch.cuda.device(dev):
+                                _lib.check(eng.lib.adf_frames_push(sink.handle, pos.data_ptr(), eng._stream()))
+                        eng.check_flags()
+                    except BaseException:
+                        if writer is not None:
+                            writer.abort()
+                            sink.abort()
+                            writer.join()
+                            sink.close()
+                            if writer.error is not None:
+                                raise writer.error
+                        raise
+                    if writer is not None:
+                        applied = int(state[3].item())
+                        writer.finish(max(applied, 1) if self.save_full else 1)
+                        self._pending = (writer, sink)
+                    return state, frames
+                # per-step path: the full forward (both heads of a two-head model), then the same step kernels
+                f2 = torch.zeros(N, 3, dtype=torch.float32, device=dev) if two_heads else None
+                for t_idx in range(T):
+                    eng.forward_prepared(prep, pos, f1, f2, out_idx)
+                    eng.tr_step(prep, pos, f1, state, coefs_dev=coefs_dev, num_steps=T,
+                                z=z_all[t_idx] if z_all is not None else None, early_stop_count=early)
+                    if frames is not None and (self.save_full or t_idx == T - 1):
+                        frames.append(pos.clone())
+                    step_hook(t_idx)
+                    if early and (t_idx % check_every == check_every - 1):
+                        if int(state[1].item()):
+                            break
+                if frames is not None and not frames:
+                    frames.append(pos.clone())
+                eng.check_flags()
+                return state, frames
+
+            try:
+                state, frames = attempt()
+            except _lib.NumericRangeError:
+                if not eng.use_exact_f32():
+                    raise
+                pos.copy_(pos0)
+                state, frames = attempt()
+            st = state.tolist()
+            self.steps_applied = st[3]
+            self.cvg_count = st[0]
+            if frames is not None:
+                frames = frames[: max(self.steps_applied, 1)] if self.save_full else frames[-1:]
+                self._write_trajectories(batch, frames)
+            if getattr(self, "_pending", None) is not None and not params.get("trajectory_async", False):
+                self.wait_for_trajectories()
+            batch.y = torch.zeros(B, device=dev)
             batch.force = torch.zeros(N, 3, device=dev)
         finally:
             try:

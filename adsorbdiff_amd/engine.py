@@ -100,6 +100,7 @@ class PaiNNEngine:
             envelope_exponent=int(model.radial_basis.envelope.p), num_heads=2 if model.so3_denoising else 1,
             cutoff=float(model.cutoff),
         )
+        self.num_heads = hp.num_heads
         self.handle = C.c_void_p()
         with torch.cuda.device(self.device):
             _lib.check(self.lib.adf_painn_create(C.byref(hp), C.byref(self.handle)))
@@ -343,6 +344,35 @@ class PaiNNEngine:
                 _lib.check(self.lib.adf_sample(*args, self._stream()))
             else:
                 _lib.check(self.lib.adf_sample_traj(*args, sink.handle, int(frame_every), self._stream()))
+
+    def tr_step(self, prep: PreparedBatch, pos, f1, state, coef: Optional[_lib.TrCoef] = None,
+                coefs_dev: Optional[torch.Tensor] = None, num_steps: int = 0, z=None, early_stop_count: int = 10,
+                dcom=None) -> None:
+        """One step of the translation-only samplers (``adf_tr_step``): head-1 mean over the adsorbate, dcom =
+        coef * score (+ noise * z), COM wrap, pos += dcom.  Scalars from ``coef`` or from the device table
+        ``coefs_dev`` [num_steps, 2] indexed by state[4]."""
+        desc = prep.desc(pos)
+        opt = lambda t: t.data_ptr() if t is not None else None
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.adf_tr_step(
+                self.handle, C.byref(desc), pos.data_ptr(), prep.tags.data_ptr(), f1.data_ptr(),
+                C.byref(coef) if coef is not None else None, opt(coefs_dev), int(num_steps), opt(z), early_stop_count,
+                state.data_ptr(), opt(dcom), self._stream()))
+
+    def tr_sample(self, prep: PreparedBatch, pos, f1, coefs_dev: torch.Tensor, num_steps: int, state, z_all=None,
+                  early_stop_count: int = 10, poll_every: int = 0, out_idx=None, sink=None, frame_every: int = 1) -> None:
+        """The whole translation-only loop in one library call (``adf_tr_sample[_traj]``); the forward inside
+        evaluates head 1 only."""
+        desc = prep.desc(pos)
+        opt = lambda t: t.data_ptr() if t is not None else None
+        args = [self.handle, C.byref(desc), pos.data_ptr(), prep.tags.data_ptr(), coefs_dev.data_ptr(), int(num_steps),
+                opt(z_all), early_stop_count, poll_every, state.data_ptr(), opt(out_idx),
+                int(out_idx.numel()) if out_idx is not None else 0, f1.data_ptr()]
+        with torch.cuda.device(self.device):
+            if sink is None:
+                _lib.check(self.lib.adf_tr_sample(*args, self._stream()))
+            else:
+                _lib.check(self.lib.adf_tr_sample_traj(*args, sink.handle, int(frame_every), self._stream()))
 
     def counters(self) -> _lib.Counters:
         c = _lib.Counters()

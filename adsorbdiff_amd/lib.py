@@ -24,6 +24,7 @@ EXPORTS = (
     "adf_check_flags", "adf_painn_set_arithmetic", "adf_painn_set_incremental", "adf_painn_set_fused_mlp",
     "adf_graph_export", "adf_painn_forward", "adf_painn_forward_subset", "adf_linear_forward", "adf_painn_message_layer", "adf_painn_update_layer",
     "adf_sde_init_placement", "adf_sde_step", "adf_sde_step_scheduled", "adf_sample", "adf_sample_traj",
+    "adf_tr_step", "adf_tr_sample", "adf_tr_sample_traj",
     "adf_frames_create", "adf_frames_destroy", "adf_frames_push", "adf_frames_wait", "adf_frames_release", "adf_frames_pushed", "adf_frames_abort",
     "adf_get_counters", "adf_profile_enable", "adf_profile_read", "adf_measure_peaks",
     "adf_lift_adsorbates", "adf_comm_unique_id", "adf_comm_create", "adf_comm_destroy", "adf_allgather_sites",
@@ -31,7 +32,7 @@ EXPORTS = (
     "adf_eqv2_create", "adf_eqv2_destroy", "adf_eqv2_set_constants", "adf_eqv2_set_weights", "adf_eqv2_set_arithmetic",
     "adf_eqv2_set_energy_embedding", "adf_eqv2_set_system_energy",
     "adf_eqv2_set_edges", "adf_eqv2_set_moving", "adf_eqv2_set_incremental", "adf_eqv2_forward", "adf_eqv2_forward_subset", "adf_eqv2_check_flags", "adf_eqv2_init_placement",
-    "adf_eqv2_sde_step", "adf_eqv2_sample", "adf_eqv2_sample_traj", "adf_eqv2_linear_forward", "adf_eqv2_get_counters", "adf_eqv2_profile_enable", "adf_eqv2_profile_read",
+    "adf_eqv2_sde_step", "adf_eqv2_sample", "adf_eqv2_sample_traj", "adf_eqv2_tr_step", "adf_eqv2_tr_sample", "adf_eqv2_tr_sample_traj", "adf_eqv2_linear_forward", "adf_eqv2_get_counters", "adf_eqv2_profile_enable", "adf_eqv2_profile_read",
     "adf_last_error", "adf_version",
 )
 
@@ -72,6 +73,11 @@ class StepCoef(C.Structure):
         ("coef_tr", C.c_float), ("rot_pre", C.c_float), ("rot_dt", C.c_float), ("rot_g2", C.c_float),
         ("noise_tr", C.c_float), ("noise_rot", C.c_float),
     ]
+
+
+class TrCoef(C.Structure):
+    """adf_tr_coef: per-step scalars of the translation-only samplers (dcom = coef * score + noise * z)."""
+    _fields_ = [("coef", C.c_float), ("noise", C.c_float)]
 
 
 class Counters(C.Structure):
@@ -129,6 +135,12 @@ def load():
         "adf_sde_init_placement": [vp, C.POINTER(BatchDesc), vp, vp, vp, vp],
         "adf_sde_step": [vp, C.POINTER(BatchDesc), vp, vp, vp, vp, vp, C.POINTER(StepCoef), vp, vp, i32, vp, vp, vp, vp],
         "adf_sde_step_scheduled": [vp, C.POINTER(BatchDesc), vp, vp, vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp],
+        "adf_tr_step": [vp, C.POINTER(BatchDesc), vp, vp, vp, C.POINTER(TrCoef), vp, i32, vp, i32, vp, vp, vp],
+        "adf_tr_sample": [vp, C.POINTER(BatchDesc), vp, vp, vp, i32, vp, i32, i32, vp, vp, i32, vp, vp],
+        "adf_tr_sample_traj": [vp, C.POINTER(BatchDesc), vp, vp, vp, i32, vp, i32, i32, vp, vp, i32, vp, vp, i32, vp],
+        "adf_eqv2_tr_step": [vp, C.POINTER(BatchDesc), vp, vp, vp, C.POINTER(TrCoef), vp, i32, vp, i32, vp, vp, vp],
+        "adf_eqv2_tr_sample": [vp, C.POINTER(BatchDesc), vp, vp, vp, i32, vp, i32, i32, vp, vp, i32, vp, vp],
+        "adf_eqv2_tr_sample_traj": [vp, C.POINTER(BatchDesc), vp, vp, vp, i32, vp, i32, i32, vp, vp, i32, vp, vp, i32, vp],
         "adf_get_counters": [vp, C.POINTER(Counters), vp],
         "adf_profile_enable": [vp, i32],
         "adf_profile_read": [vp, C.POINTER(C.c_float), C.POINTER(i64), C.POINTER(i64), vp],

@@ -250,6 +250,35 @@ int32_t adf_sample(adf_painn_t h, const adf_batch* b, float* pos, const int32_t*
                    int32_t early_stop_count, int32_t poll_every, int32_t* state, const int32_t* out_idx,
                    int32_t n_out, float* f1, float* f2, void* stream);
 
+/* ---- translation-only samplers: Denoiser.reverse_sde_sampling (denoising_torch.py:96-196, probability-flow ODE) and
+ * Denoiser.langevin_dynamics (:369-458, annealed Langevin).  Per step:
+ *   score = mean of head 1 (f1) over the tag-2 atoms of each system (_get_ads_output, :460-467)
+ *   dcom  = coef * score (+ noise * z)   with dcom_z := 0, then the COM wrap of adf_sde_step (:150-166, :421-435)
+ *   pos  += dcom on the tag-2 atoms (set_positions, :52-56); slab atoms are never written.
+ * ODE: coef = 0.5*g_tr^2*dt (adf_step_coef.coef_tr with ode), noise unused, z = NULL.
+ * Langevin: coef = step_size = step_lr*(sigma/sigma_min)^2, noise = sqrt(2*step_size), z = [B,3] standard normals;
+ * the table runs over num_steps * n_step_each inner steps.  Both scalars are f32 values computed by the host with the
+ * reference's own tensor arithmetic. */
+typedef struct {
+    float coef;
+    float noise;
+} adf_tr_coef;
+
+/* One translation step after a forward: either `coef` (host) or the DEVICE table coefs_dev[num_steps] indexed by
+ * state[4], as adf_sde_step / adf_sde_step_scheduled.  state: the int32[8] protocol of adf_sde_step (early stop:
+ * cumulative count of steps where every |dcom| <= 1e-3, reverse_sde_sampling :168-176; pass 0 for Langevin, which has
+ * none).  f1 is the only model output read.  dcom: optional [B,3] output (the wrapped increment). */
+int32_t adf_tr_step(adf_painn_t h, const adf_batch* b, float* pos, const int32_t* tags, const float* f1,
+                    const adf_tr_coef* coef, const adf_tr_coef* coefs_dev, int32_t num_steps, const float* z,
+                    int32_t early_stop_count, int32_t* state, float* dcom, void* stream);
+/* The whole loop after the initial placement in one call: num_steps x (forward + adf_tr_step), with the poll_every,
+ * out_idx / n_out contracts of adf_sample.  The forward evaluates head 1 only (no out_forces2 products: neither sampler
+ * reads head 2; its head-1 rows are bit-identical to adf_painn_forward's).  z_all: [num_steps][B][3] or NULL.  f1: [N,3]
+ * work array.  adf_tr_sample_traj pushes a frame after every frame_every-th step (adf_sample_traj). */
+int32_t adf_tr_sample(adf_painn_t h, const adf_batch* b, float* pos, const int32_t* tags, const adf_tr_coef* coefs_dev,
+                      int32_t num_steps, const float* z_all, int32_t early_stop_count, int32_t poll_every,
+                      int32_t* state, const int32_t* out_idx, int32_t n_out, float* f1, void* stream);
+
 typedef struct {
     int64_t num_edges;
     int64_t num_atoms;
@@ -301,6 +330,10 @@ int32_t adf_sample_traj(adf_painn_t h, const adf_batch* b, float* pos, const int
                         const adf_step_coef* coefs_dev, int32_t num_steps, const float* z_tr_all, const float* z_rot_all,
                         int32_t early_stop_count, int32_t poll_every, int32_t* state, const int32_t* out_idx,
                         int32_t n_out, float* f1, float* f2, adf_frames_t sink, int32_t frame_every, void* stream);
+int32_t adf_tr_sample_traj(adf_painn_t h, const adf_batch* b, float* pos, const int32_t* tags,
+                           const adf_tr_coef* coefs_dev, int32_t num_steps, const float* z_all, int32_t early_stop_count,
+                           int32_t poll_every, int32_t* state, const int32_t* out_idx, int32_t n_out, float* f1,
+                           adf_frames_t sink, int32_t frame_every, void* stream);
 
 /* Hand-off to the relaxation stage: the lift rule of scripts/create_lmdbs/pred_traj_to_lmdb.py:81-90 applied to the
  * sampled final frames on the device (in place).  lifted: optional [B] output = shift applied per system. */
@@ -515,6 +548,20 @@ int32_t adf_eqv2_sample_traj(adf_eqv2_t h, const adf_batch* b, float* pos, const
                              const adf_step_coef* coefs_dev, int32_t num_steps, const float* z_tr_all, const float* z_rot_all,
                              int32_t early_stop_count, int32_t poll_every, int32_t* state, const int32_t* out_idx, int32_t n_out,
                              float* f1, float* f2, adf_frames_t sink, int32_t frame_every, void* stream);
+
+/* Translation-only samplers on an EquiformerV2 handle: same contracts as adf_tr_step / adf_tr_sample[_traj]; the fused
+ * loop runs force_block only (no force_block2, a whole SO(2) attention block, equiformer_v2_denoising.py:307-318). */
+int32_t adf_eqv2_tr_step(adf_eqv2_t h, const adf_batch* b, float* pos, const int32_t* tags, const float* f1,
+                         const adf_tr_coef* coef, const adf_tr_coef* coefs_dev, int32_t num_steps, const float* z,
+                         int32_t early_stop_count, int32_t* state, float* dcom, void* stream);
+int32_t adf_eqv2_tr_sample(adf_eqv2_t h, const adf_batch* b, float* pos, const int32_t* tags,
+                           const adf_tr_coef* coefs_dev, int32_t num_steps, const float* z_all, int32_t early_stop_count,
+                           int32_t poll_every, int32_t* state, const int32_t* out_idx, int32_t n_out, float* f1,
+                           void* stream);
+int32_t adf_eqv2_tr_sample_traj(adf_eqv2_t h, const adf_batch* b, float* pos, const int32_t* tags,
+                                const adf_tr_coef* coefs_dev, int32_t num_steps, const float* z_all,
+                                int32_t early_stop_count, int32_t poll_every, int32_t* state, const int32_t* out_idx,
+                                int32_t n_out, float* f1, adf_frames_t sink, int32_t frame_every, void* stream);
 
 /* Stand-alone torch.nn.functional.linear (+ optional SiLU, act = 2) through this path's dense-product kernels (unit tests
  * and micro-benchmarks of so2_ops.py:12-79,158-238 / so3.py:694-745 shapes).  A [M,K], W [N,K], bias [N] or NULL, C [M,N],
