@@ -100,8 +100,8 @@ extern "C" int32_t adf_painn_create(const adf_painn_hparams* hp, adf_painn_t* ou
         adf_set_error("max_neighbors=%d must be in [1,%d]", hp->max_neighbors, ADF_MAX_K);
         return ADF_EINVAL;
     }
-    if (hp->num_layers < 1 || hp->num_layers > 16 || hp->num_heads < 1 || hp->num_heads > 2) {
-        adf_set_error("num_layers must be in [1,16], num_heads in [1,2]");
+    if (hp->num_layers < 1 || hp->num_layers > 16 || hp->num_heads < 0 || hp->num_heads > 2) {
+        adf_set_error("num_layers must be in [1,16], num_heads in [0,2]");
         return ADF_EINVAL;
     }
     adf_painn* h = new (std::nothrow) adf_painn();
@@ -117,6 +117,7 @@ extern "C" int32_t adf_painn_create(const adf_painn_hparams* hp, adf_painn_t* ou
         return ADF_EHIP;
     }
     h->num_cus = prop.multiProcessorCount;
+    h->dist_floor = 1.0e-3f;
     {   // incremental layers: on unless ADF_INCREMENTAL=0 (adf_painn_set_incremental overrides)
         const char* e = getenv("ADF_INCREMENTAL");
         h->inc_on = !(e && e[0] == '0');
@@ -220,6 +221,7 @@ extern "C" int32_t adf_painn_destroy(adf_painn_t h) {
     if (h->w16_scales) (void)hipFree(h->w16_scales);
     if (h->w16_bias_perm) (void)hipFree(h->w16_bias_perm);
     if (h->w16_scratch) (void)hipFree(h->w16_scratch);
+    if (h->oe0_buf) (void)hipFree(h->oe0_buf);
     if (h->prof_ev) { for (hipEvent_t e : *h->prof_ev) (void)hipEventDestroy(e); delete h->prof_ev; }
     delete h->prof_cat;
     delete h;
@@ -799,8 +801,9 @@ static int32_t forward_incremental(adf_painn* h, int N, const int32_t* Z, const 
     }
     adf_prof_begin(h, ADF_PROF_HEADS, s);
     if (!out_idx) {
-        ADF_TRY(adf_head_forward(h, 0, N, h->incX[L], h->incV[L], f1, s));
+        if (heads >= 1) ADF_TRY(adf_head_forward(h, 0, N, h->incX[L], h->incV[L], f1, s));
         if (heads == 2) ADF_TRY(adf_head_forward(h, 1, N, h->incX[L], h->incV[L], f2, s));
+        h->x_last = h->incX[L];
     } else {
         if (n_out > h->capS) {
             const int64_t c = (int64_t)n_out + n_out / 4 + 64;
@@ -832,7 +835,9 @@ static int32_t forward_impl(adf_painn_t h, const adf_batch* b, const int32_t* ou
     ADF_TRY(check_batch(h, b));
     if (!h->weights_set) { adf_set_error("weights not set"); return ADF_EINVAL; }
     const int heads = head1_only ? 1 : h->hp.num_heads;
-    if (!b->atomic_numbers || !f1 || (heads == 2 && !f2)) { adf_set_error("null argument"); return ADF_EINVAL; }
+    if (heads > h->hp.num_heads) { adf_set_error("the model has no force head"); return ADF_EINVAL; }
+    if (!b->atomic_numbers || (heads >= 1 && !f1) || (heads == 2 && !f2)) { adf_set_error("null argument"); return ADF_EINVAL; }
+    h->x_last = nullptr;
     hipStream_t s = (hipStream_t)stream;
     const int N = b->num_atoms;
     ADF_TRY(ensure_capacity(h, N, b->num_systems));
@@ -874,9 +879,10 @@ static int32_t forward_impl(adf_painn_t h, const adf_batch* b, const int32_t* ou
             float* t = vin; vin = vout; vout = t;
         }
         adf_prof_begin(h, ADF_PROF_HEADS, s);
-        ADF_TRY(adf_head_forward(h, 0, N, h->x, vin, f1, s));
+        if (heads >= 1) ADF_TRY(adf_head_forward(h, 0, N, h->x, vin, f1, s));
         if (heads == 2) ADF_TRY(adf_head_forward(h, 1, N, h->x, vin, f2, s));
         adf_prof_end(h, s);
+        h->x_last = h->x;
         return ADF_OK;
     }
     // Outputs wanted on a subset only.  Every layer but the last is needed in full (the listed atoms' messages
@@ -911,6 +917,84 @@ static int32_t forward_impl(adf_painn_t h, const adf_batch* b, const int32_t* ou
         hipLaunchKernelGGL(adf_scatter_rows3_kernel, dim3((3 * n_out + 255) / 256), dim3(256), 0, s, h->sub_f, out_idx,
                            n_out, hd == 0 ? f1 : f2);
     }
+    ADF_HIP_CHECK(hipGetLastError());
+    adf_prof_end(h, s);
+    return ADF_OK;
+}
+
+// ---- S2EF energy head (painn.py:412-414): per_atom = out_energy.2(ScaledSiLU(out_energy.0(x))), energy = per-system sum
+extern "C" int32_t adf_painn_set_energy_head(adf_painn_t h, int32_t n_weights, const void* const* w, void* stream) {
+    if (!h || !w) { adf_set_error("null argument"); return ADF_EINVAL; }
+    if (n_weights != 4) { adf_set_error("set_energy_head: expected 4 tensors (out_energy.0.weight/bias, out_energy.2.weight/bias), got %d", n_weights); return ADF_EINVAL; }
+    for (int i = 0; i < 4; ++i)
+        if (!w[i]) { adf_set_error("energy-head tensor %d is null", i); return ADF_EINVAL; }
+    const int H = h->hp.hidden_channels, H2 = H / 2;
+    const size_t n = (size_t)H2 * H;
+    if (!h->oe0_buf) ADF_TRY(dev_alloc(&h->oe0_buf, n * 4 + 64));
+    h->oe0_w = reinterpret_cast<const float*>(w[0]);
+    h->oe0_b = reinterpret_cast<const float*>(w[1]);
+    h->oe2_w = reinterpret_cast<const float*>(w[2]);
+    h->oe2_b = reinterpret_cast<const float*>(w[3]);
+    adf_w16& e = h->oe0_16;
+    e = adf_w16{};
+    e.hi = h->oe0_buf; e.lo = h->oe0_buf + n * 2; e.inv_scale = reinterpret_cast<float*>(h->oe0_buf + n * 4);
+    ADF_TRY(adf_split_weight(h->oe0_w, (long long)n, &e, reinterpret_cast<unsigned int*>(h->oe0_buf + n * 4 + 16),
+                             (hipStream_t)stream));
+    h->energy_set = true;
+    return ADF_OK;
+}
+
+// Edge distances at or below `floor` are replaced by it before the unit vectors are formed (the denoiser's 1e-3 by default;
+// the S2EF PaiNN uses 1e-6).  Takes effect with the next graph build.
+extern "C" int32_t adf_painn_set_distance_floor(adf_painn_t h, float floor) {
+    if (!h || !(floor > 0.f)) { adf_set_error("set_distance_floor: null handle or non-positive floor"); return ADF_EINVAL; }
+    if (floor != h->dist_floor) {
+        h->dist_floor = floor;
+        h->cache_valid = false;
+        h->rec0_valid = false;
+        h->inc_valid = false;
+    }
+    return ADF_OK;
+}
+
+// One workgroup per system: the per-atom energies y[a] . w + b (one wave per atom, lanes over channels, fixed butterfly),
+// accumulated over the system's atoms in a fixed order (wave w takes atoms w, w + 4, ...; then waves 0..3).  A system's
+// energy therefore depends on its own rows only: bit-identical whatever batch it sits in.  No atomics.
+__global__ __launch_bounds__(256) void adf_energy_sum_kernel(const float* __restrict__ y, int H2, const float* __restrict__ w,
+                                                             const float* __restrict__ bias, const int32_t* __restrict__ atom_offset,
+                                                             float* __restrict__ energy) {
+    __shared__ float part[4];
+    const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int a0 = atom_offset[b], a1 = atom_offset[b + 1];
+    const float b0 = bias[0];
+    float acc = 0.f;
+    for (int a = a0 + wave; a < a1; a += 4) {
+        const float* row = y + (size_t)a * H2;
+        float d = 0.f;
+        for (int c = lane; c < H2; c += 64) d = fmaf(row[c], w[c], d);
+        for (int o = 32; o > 0; o >>= 1) d = __fadd_rn(d, __shfl_xor(d, o, 64));
+        acc = __fadd_rn(acc, __fadd_rn(d, b0));
+    }
+    if (lane == 0) part[wave] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) energy[b] = __fadd_rn(__fadd_rn(part[0], part[1]), __fadd_rn(part[2], part[3]));
+}
+
+// energy [B] (and forces [N,3] unless the model has no force head: forces may be NULL then)
+extern "C" int32_t adf_painn_forward_energy(adf_painn_t h, const adf_batch* b, float* energy, float* forces, void* stream) {
+    ADF_TRY(check_batch(h, b));
+    if (!h->energy_set) { adf_set_error("forward_energy: energy head not set (adf_painn_set_energy_head)"); return ADF_EINVAL; }
+    if (!energy || (h->hp.num_heads >= 1 && !forces)) { adf_set_error("forward_energy: null output"); return ADF_EINVAL; }
+    if (h->hp.num_heads > 1) { adf_set_error("forward_energy: the S2EF model has one force head"); return ADF_EINVAL; }
+    hipStream_t s = (hipStream_t)stream;
+    ADF_TRY(forward_impl(h, b, nullptr, 0, forces, nullptr, stream));
+    if (!h->x_last) { adf_set_error("internal: no node features after the forward"); return ADF_EINVAL; }
+    const int N = b->num_atoms, H = h->hp.hidden_channels, H2 = H / 2;
+    adf_prof_begin(h, ADF_PROF_HEADS, s);
+    // h->y is free once the force head has run ([capN, H] >= [N, H/2])
+    ADF_TRY(adf_linear(h, h->x_last, H, h->oe0_w, &h->oe0_16, h->oe0_b, h->y, H2, N, H2, H, 1, s));
+    hipLaunchKernelGGL(adf_energy_sum_kernel, dim3(b->num_systems), dim3(256), 0, s, h->y, H2, h->oe2_w, h->oe2_b,
+                       b->atom_offset, energy);
     ADF_HIP_CHECK(hipGetLastError());
     adf_prof_end(h, s);
     return ADF_OK;

@@ -193,6 +193,13 @@ struct adf_painn {
     float *sub_x, *sub_vec, *sub_f;  // compact rows of adf_painn_forward_subset: [capS,H], [capS,3,H], [capS,3]
     int64_t capS;
     float* sys;          // [B*16] per-system scratch of the stepper
+    // ---- S2EF energy head out_energy = Linear(H, H/2), ScaledSiLU, Linear(H/2, 1) (adf_painn_set_energy_head)
+    const float *oe0_w, *oe0_b, *oe2_w, *oe2_b;
+    adf_w16 oe0_16;
+    unsigned char* oe0_buf;   // hi / lo planes + inverse scale + split scratch of out_energy.0.weight
+    bool energy_set;
+    const float* x_last;      // node features entering the heads of the last full forward (h->x or the kept incX[L])
+    float dist_floor;         // edge distances at or below it are set to it (adf_painn_set_distance_floor, default 1e-3)
     // last graph
     int64_t lastN, lastB;
     int32_t last_reps[3];

@@ -96,6 +96,7 @@ int32_t eq_launch_edges_from_topk(adf_eqv2* h, const adf_batch* b, hipStream_t s
     p.pos = b->pos; p.cell = b->cell; p.batch = b->batch; p.atom_offset = b->atom_offset;
     p.r0 = b->reps[0]; p.r1 = b->reps[1]; p.r2 = b->reps[2];
     p.rc2 = h->hp.max_radius * h->hp.max_radius;
+    p.dist_floor = 1.0e-3f;  // not read by the EquiformerV2 edge kernels
     p.K = K; p.N = N;
     p.nbr_cnt = h->nbr_cnt; p.nbr_src = h->nbr_src; p.nbr_shift = h->nbr_shift;
     p.img_cnt = h->img_cnt; p.flags = h->flags;

@@ -9,6 +9,7 @@ struct GraphParams {
     const int32_t* atom_offset;
     int r0, r1, r2;
     float rc2;
+    float dist_floor;  // edge distances at or below it are set to it (painn_denoising.py:366-367: 1e-3; painn.py:334-335: 1e-6)
     int K;
     int N;
     int32_t* nbr_cnt;

@@ -279,7 +279,7 @@ __global__ void adf_fill_kernel(GraphParams p, const int32_t* nptr, int32_t* cur
     const float vz = __fadd_rn(__fsub_rn(p.pos[3 * j + 2], p.pos[3 * i + 2]), oz);
     float d = sqrtf(fmaf(vz, vz, fmaf(vy, vy, vx * vx)));
     // utils.py:536-540 drops d == 0 edges: unreachable after the d^2 > 1e-4 filter, so not handled
-    if (fabsf(d) <= 1.0e-3f) d = 1.0e-3f;  // painn_denoising.py:366-367
+    if (fabsf(d) <= p.dist_floor) d = p.dist_floor;  // painn_denoising.py:366-367 / painn.py:334-335
     const float ux = vx / d, uy = vy / d, uz = vz / d;
     // edge j -> i, stored in the segment of its target i
     long long slot = (long long)nptr[i] + atomicAdd(&cursor[i], 1);
@@ -431,7 +431,7 @@ __device__ __forceinline__ float4 csr_edge_geom(const GraphParams& p, const floa
     const float vy = __fadd_rn(__fsub_rn(spos[3 * jl + 1], spos[3 * il + 1]), oy);
     const float vz = __fadd_rn(__fsub_rn(spos[3 * jl + 2], spos[3 * il + 2]), oz);
     float d = sqrtf(fmaf(vz, vz, fmaf(vy, vy, vx * vx)));
-    if (fabsf(d) <= 1.0e-3f) d = 1.0e-3f;
+    if (fabsf(d) <= p.dist_floor) d = p.dist_floor;
     return make_float4(vx / d, vy / d, vz / d, d);
 }
 
@@ -549,6 +549,7 @@ int32_t adf_graph_build_impl(adf_painn* h, const adf_batch* b, hipStream_t s) {
     p.pos = b->pos; p.cell = b->cell; p.batch = b->batch; p.atom_offset = b->atom_offset;
     p.r0 = b->reps[0]; p.r1 = b->reps[1]; p.r2 = b->reps[2];
     p.rc2 = h->hp.cutoff * h->hp.cutoff;
+    p.dist_floor = h->dist_floor;
     p.K = K; p.N = N;
     p.nbr_cnt = h->nbr_cnt; p.nbr_src = h->nbr_src; p.nbr_shift = h->nbr_shift;
     p.img_cnt = h->img_cnt;

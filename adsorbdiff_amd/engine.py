@@ -97,7 +97,8 @@ class PaiNNEngine:
         hp = _lib.Hparams(
             hidden_channels=model.hidden_channels, num_layers=model.num_layers, num_rbf=model.num_rbf,
             num_elements=model.num_elements, max_neighbors=model.max_neighbors,
-            envelope_exponent=int(model.radial_basis.envelope.p), num_heads=2 if model.so3_denoising else 1,
+            envelope_exponent=int(model.radial_basis.envelope.p),
+            num_heads=getattr(model, "num_force_heads", 2 if model.so3_denoising else 1),
             cutoff=float(model.cutoff),
         )
         self.num_heads = hp.num_heads
@@ -109,6 +110,9 @@ class PaiNNEngine:
 
         self.exact_f32 = os.environ.get("ADF_GEMM") == "f32"
         self._last_graph_N = 0
+        floor = getattr(model, "distance_floor", None)   # the S2EF PaiNN: 1e-6 (painn.py:334-335); default 1e-3
+        if floor is not None:
+            _lib.check(self.lib.adf_painn_set_distance_floor(self.handle, float(floor)))
         self.bind_weights()
 
     # ------------------------------------------------------------------ weights
@@ -125,7 +129,7 @@ class PaiNNEngine:
                 u + "vec_proj.weight", u + "xvec_proj.0.weight", u + "xvec_proj.0.bias",
                 u + "xvec_proj.2.weight", u + "xvec_proj.2.bias",
             ]
-        heads = ["out_forces"] + (["out_forces2"] if m.so3_denoising else [])
+        heads = ["out_forces", "out_forces2"][:self.num_heads]
         for hname in heads:
             for b in range(2):
                 q = f"{hname}.output_network.{b}."
@@ -148,6 +152,15 @@ class PaiNNEngine:
         sf = (C.c_float * len(scales))(*scales)
         with torch.cuda.device(self.device):
             _lib.check(self.lib.adf_painn_set_weights(self.handle, len(ws), ptrs, sf, self._stream()))
+        if getattr(self.model, "energy_head", False):   # S2EF PaiNN: out_energy (adf_painn_set_energy_head)
+            oe = self.model.out_energy
+            es = [t.detach().to(torch.float32).contiguous() for t in (oe[0].weight, oe[0].bias, oe[2].weight, oe[2].bias)]
+            for t in es:
+                _require_gpu(t, "out_energy parameter")
+            self._weights_keepalive = ws + es
+            eptrs = (C.c_void_p * 4)(*[t.data_ptr() for t in es])
+            with torch.cuda.device(self.device):
+                _lib.check(self.lib.adf_painn_set_energy_head(self.handle, 4, eptrs, self._stream()))
 
     # ------------------------------------------------------------------ batches
     def _stream(self) -> C.c_void_p:
@@ -225,6 +238,33 @@ class PaiNNEngine:
             self.forward_prepared(prep, pos, f1, f2)
             self.check_flags()
         return f1, f2
+
+    def forward_energy_prepared(self, prep: PreparedBatch, pos: torch.Tensor, energy: torch.Tensor,
+                                forces: Optional[torch.Tensor]) -> None:
+        """Enqueue one S2EF forward (``adf_painn_forward_energy``): energy [B], forces [N,3] (None without a force
+        head); no host synchronisation."""
+        desc = prep.desc(pos)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.adf_painn_forward_energy(
+                self.handle, C.byref(desc), energy.data_ptr(), forces.data_ptr() if forces is not None else None,
+                self._stream()))
+
+    def forward_energy(self, data):
+        """S2EF forward of the model's energy head and (if it has one) its force head -> (energy [B], forces [N,3] | None).
+        Same error protocol as ``forward``."""
+        prep = self.prepare(data)
+        pos = data.pos.to(torch.float32).contiguous()
+        energy = torch.empty(prep.num_systems, dtype=torch.float32, device=self.device)
+        forces = torch.empty(prep.num_atoms, 3, dtype=torch.float32, device=self.device) if self.num_heads else None
+        self.forward_energy_prepared(prep, pos, energy, forces)
+        try:
+            self.check_flags()
+        except _lib.NumericRangeError:
+            if not self.use_exact_f32():
+                raise
+            self.forward_energy_prepared(prep, pos, energy, forces)
+            self.check_flags()
+        return energy, forces
 
     def use_exact_f32(self) -> bool:
         """Switch the handle to exact-f32 arithmetic (after a NumericRangeError in the default f16x3 mode: an

@@ -25,6 +25,9 @@ EXPORTS = (
     "adf_graph_export", "adf_painn_forward", "adf_painn_forward_subset", "adf_linear_forward", "adf_painn_message_layer", "adf_painn_update_layer",
     "adf_sde_init_placement", "adf_sde_step", "adf_sde_step_scheduled", "adf_sample", "adf_sample_traj",
     "adf_tr_step", "adf_tr_sample", "adf_tr_sample_traj",
+    "adf_painn_set_energy_head", "adf_painn_set_distance_floor", "adf_painn_forward_energy",
+    "adf_lbfgs_create", "adf_lbfgs_destroy", "adf_lbfgs_reset", "adf_lbfgs_converge", "adf_lbfgs_step",
+    "adf_lbfgs_get_mask", "adf_lbfgs_last_step_max",
     "adf_frames_create", "adf_frames_destroy", "adf_frames_push", "adf_frames_wait", "adf_frames_release", "adf_frames_pushed", "adf_frames_abort",
     "adf_get_counters", "adf_profile_enable", "adf_profile_read", "adf_measure_peaks",
     "adf_lift_adsorbates", "adf_comm_unique_id", "adf_comm_create", "adf_comm_destroy", "adf_allgather_sites",
@@ -141,6 +144,16 @@ def load():
         "adf_eqv2_tr_step": [vp, C.POINTER(BatchDesc), vp, vp, vp, C.POINTER(TrCoef), vp, i32, vp, i32, vp, vp, vp],
         "adf_eqv2_tr_sample": [vp, C.POINTER(BatchDesc), vp, vp, vp, i32, vp, i32, i32, vp, vp, i32, vp, vp],
         "adf_eqv2_tr_sample_traj": [vp, C.POINTER(BatchDesc), vp, vp, vp, i32, vp, i32, i32, vp, vp, i32, vp, vp, i32, vp],
+        "adf_painn_set_energy_head": [vp, i32, C.POINTER(vp), vp],
+        "adf_painn_set_distance_floor": [vp, C.c_float],
+        "adf_painn_forward_energy": [vp, C.POINTER(BatchDesc), vp, vp, vp],
+        "adf_lbfgs_create": [i64, i32, i32, C.c_double, C.c_double, C.c_double, i32, C.POINTER(vp)],
+        "adf_lbfgs_destroy": [vp],
+        "adf_lbfgs_reset": [vp, vp],
+        "adf_lbfgs_converge": [vp, vp, vp, C.c_double, vp, vp, vp],
+        "adf_lbfgs_step": [vp, vp, vp, vp, i64, vp],
+        "adf_lbfgs_get_mask": [vp, vp, vp],
+        "adf_lbfgs_last_step_max": [vp, vp, vp],
         "adf_get_counters": [vp, C.POINTER(Counters), vp],
         "adf_profile_enable": [vp, i32],
         "adf_profile_read": [vp, C.POINTER(C.c_float), C.POINTER(i64), C.POINTER(i64), vp],

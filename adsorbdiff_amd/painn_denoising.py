@@ -151,7 +151,91 @@ class PaiNNOutput(nn.Module):
             layer.reset_parameters()
 
 
-class PaiNN(nn.Module):
+class PaiNNHost(nn.Module):
+    """What the host mirrors of the PaiNN family share (this denoiser and the S2EF model of ``painn.py``): the
+    device-side engine bound to the module's weights and the reference's small introspection methods.  A subclass sets
+    the hyper-parameter attributes the engine reads (``hidden_channels``, ``num_layers``, ``num_rbf``, ``num_elements``,
+    ``max_neighbors``, ``cutoff``, ``so3_denoising``, ``radial_basis``) and ``_engine = _engine_key = None``."""
+
+    # ------------------------------------------------------------------ API
+    @property
+    def num_params(self) -> int:
+        return sum(p.numel() for p in self.parameters())
+
+    def no_weight_decay(self) -> list:
+        """Reference: adsorbdiff/models/base.py:128-135."""
+        return [
+            name
+            for name, _ in self.named_parameters()
+            if "embedding" in name or "frequencies" in name or "bias" in name
+        ]
+
+    def __repr__(self) -> str:
+        return (
+            f"{self.__class__.__name__}(hidden_channels={self.hidden_channels}, "
+            f"num_layers={self.num_layers}, num_rbf={self.num_rbf}, "
+            f"max_neighbors={self.max_neighbors}, cutoff={self.cutoff})"
+        )
+
+    def scale_factors(self):
+        """Effective per-layer multipliers (1.0 where a ScaleFactor is unfitted,
+        reference: scale_factor.py:166-167)."""
+        out = []
+        for i in range(self.num_layers):
+            sf = getattr(self, "upd_out_scalar_scale_%d" % i)
+            out.append(float(sf.scale_factor) if sf.fitted else 1.0)
+        return out
+
+    def engine(self, device=None, refresh=True):
+        """The device-side engine (C-ABI handle + workspaces) bound to this module's weights.
+
+        ``refresh=False`` (the training step, every optimizer step): return the existing engine without fingerprinting
+        86 MB of weights and re-packing the sampling images - the training operators read the parameters through the
+        pointers they are handed, the handle only serves the graph, the embedding table (bound by pointer to the
+        parameter's own storage, updated in place by the optimizer) and the radial-basis constants.  The packed images
+        are marked stale, so the next refreshing call (a sampling forward) re-binds them."""
+        from .engine import PaiNNEngine
+
+        if device is None:
+            device = self.atom_emb.embeddings.weight.device
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if self._engine is not None and self._engine.device != device:
+            self._engine.close()
+            self._engine = None
+        if not refresh and self._engine is not None:
+            self._engine_key = None
+            return self._engine
+        version = self._weights_version(device)
+        if self._engine is None:
+            self._engine = PaiNNEngine(self, device)
+            self._engine_key = version
+        elif self._engine_key != version:
+            # parameters were swapped or modified in place (EMA copy_to/restore, load_state_dict, optimizer step)
+            self._engine.bind_weights()
+            self._engine_key = version
+        return self._engine
+
+    def _weights_version(self, device=None):
+        """Key of the packed weight images held by the engine.  (data_ptr, _version) catches swapped tensors and
+        autograd-visible in-place writes; the content fingerprint catches writes through ``param.data`` — what the
+        reference's EMA ``copy_to``/``restore`` do (modules/exponential_moving_average.py:113,147), which leave
+        ``_version`` untouched.  The fingerprint is the wrapping int64 sum of every tensor's bit pattern (two
+        kernels over 86 MB, one host read); engine() is called per forward(data) / per sampling run, never per step."""
+        tensors = list(self.parameters()) + list(self.buffers())
+        key = tuple((t.data_ptr(), t._version) for t in tensors)
+        flat = [t.detach().reshape(-1) for t in tensors
+                if t.is_cuda and t.dtype == torch.float32 and t.numel() > 0]
+        if not flat:
+            return key
+        with torch.no_grad():
+            bits = torch.cat(flat).view(torch.int32)
+            fp = int(bits.sum(dtype=torch.int64).item()) ^ int((bits[::7].sum(dtype=torch.int64) * 31).item())
+        return key + (fp,)
+
+
+class PaiNN(PaiNNHost):
     """See module docstring.  ``num_atoms, bond_feat_dim, num_targets`` are accepted
     and ignored exactly like the reference (models/base.py:22-28)."""
 
@@ -232,83 +316,6 @@ class PaiNN(nn.Module):
 
         self._engine = None  # created lazily on first forward (device-resident packed weights)
         self._engine_key = None
-
-    # ------------------------------------------------------------------ API
-    @property
-    def num_params(self) -> int:
-        return sum(p.numel() for p in self.parameters())
-
-    def no_weight_decay(self) -> list:
-        """Reference: adsorbdiff/models/base.py:128-135."""
-        return [
-            name
-            for name, _ in self.named_parameters()
-            if "embedding" in name or "frequencies" in name or "bias" in name
-        ]
-
-    def __repr__(self) -> str:
-        return (
-            f"{self.__class__.__name__}(hidden_channels={self.hidden_channels}, "
-            f"num_layers={self.num_layers}, num_rbf={self.num_rbf}, "
-            f"max_neighbors={self.max_neighbors}, cutoff={self.cutoff})"
-        )
-
-    def scale_factors(self):
-        """Effective per-layer multipliers (1.0 where a ScaleFactor is unfitted,
-        reference: scale_factor.py:166-167)."""
-        out = []
-        for i in range(self.num_layers):
-            sf = getattr(self, "upd_out_scalar_scale_%d" % i)
-            out.append(float(sf.scale_factor) if sf.fitted else 1.0)
-        return out
-
-    def engine(self, device=None, refresh=True):
-        """The device-side engine (C-ABI handle + workspaces) bound to this module's weights.
-
-        ``refresh=False`` (the training step, every optimizer step): return the existing engine without fingerprinting
-        86 MB of weights and re-packing the sampling images - the training operators read the parameters through the
-        pointers they are handed, the handle only serves the graph, the embedding table (bound by pointer to the
-        parameter's own storage, updated in place by the optimizer) and the radial-basis constants.  The packed images
-        are marked stale, so the next refreshing call (a sampling forward) re-binds them."""
-        from .engine import PaiNNEngine
-
-        if device is None:
-            device = self.atom_emb.embeddings.weight.device
-        device = torch.device(device)
-        if device.type == "cuda" and device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        if self._engine is not None and self._engine.device != device:
-            self._engine.close()
-            self._engine = None
-        if not refresh and self._engine is not None:
-            self._engine_key = None
-            return self._engine
-        version = self._weights_version(device)
-        if self._engine is None:
-            self._engine = PaiNNEngine(self, device)
-            self._engine_key = version
-        elif self._engine_key != version:
-            # parameters were swapped or modified in place (EMA copy_to/restore, load_state_dict, optimizer step)
-            self._engine.bind_weights()
-            self._engine_key = version
-        return self._engine
-
-    def _weights_version(self, device=None):
-        """Key of the packed weight images held by the engine.  (data_ptr, _version) catches swapped tensors and
-        autograd-visible in-place writes; the content fingerprint catches writes through ``param.data`` — what the
-        reference's EMA ``copy_to``/``restore`` do (modules/exponential_moving_average.py:113,147), which leave
-        ``_version`` untouched.  The fingerprint is the wrapping int64 sum of every tensor's bit pattern (two
-        kernels over 86 MB, one host read); engine() is called per forward(data) / per sampling run, never per step."""
-        tensors = list(self.parameters()) + list(self.buffers())
-        key = tuple((t.data_ptr(), t._version) for t in tensors)
-        flat = [t.detach().reshape(-1) for t in tensors
-                if t.is_cuda and t.dtype == torch.float32 and t.numel() > 0]
-        if not flat:
-            return key
-        with torch.no_grad():
-            bits = torch.cat(flat).view(torch.int32)
-            fp = int(bits.sum(dtype=torch.int64).item()) ^ int((bits[::7].sum(dtype=torch.int64) * 31).item())
-        return key + (fp,)
 
     def forward(self, data):
         """data: pos[N,3] f32, atomic_numbers[N], batch[N] i64, natoms[B] i64, cell[B,3,3] f32

@@ -197,3 +197,94 @@ class DenoisingTrainer:
                 )
             )
         return out
+
+
+class Normalizer:
+    """Reference: modules/normalizer.py:13-60 (mean / std of a target; ``denorm`` = x * std + mean)."""
+
+    def __init__(self, mean=0.0, std=1.0, device="cpu") -> None:
+        self.mean = torch.as_tensor(mean).to(device)
+        self.std = torch.as_tensor(std).to(device)
+
+    def to(self, device) -> None:
+        self.mean = self.mean.to(device)
+        self.std = self.std.to(device)
+
+    def norm(self, x):
+        return torch.div(torch.sub(x, self.mean), self.std)
+
+    def denorm(self, x):
+        """the model's normalised output in target units"""
+        return torch.add(torch.mul(x, self.std), self.mean)
+
+    def state_dict(self):
+        return {"mean": self.mean, "std": self.std}
+
+    def load_state_dict(self, state_dict) -> None:
+        self.mean = state_dict["mean"].to(self.mean.device)
+        self.std = state_dict["std"].to(self.mean.device)
+
+
+# old checkpoint keys of the normalizers -> output targets (base_trainer.py:518-530)
+_NORMALIZER_KEYS = {"target": "energy", "grad_target": "forces"}
+
+
+class ForcesTrainer:
+    """The part of the reference's S2EF trainer (trainers/ocp_trainer.py:405-460, base_trainer.py:353-362) that
+    ``ml_relax`` / ``TorchCalc`` touch: ``predict(batch, per_image=False)`` -> ``{"energy", "forces"}`` with the EMA weights
+    swapped in for the forward and the normalizers' ``denorm`` applied, ``_unwrapped_model``, ``normalizers``.
+    ``normalizers``: ``{"energy" | "target": {"mean", "stdev"}, ...}`` as in the
+    dataset config (``transforms.normalizer``), or ready ``Normalizer`` objects."""
+
+    def __init__(self, model, device="cuda:0", normalizers: Optional[dict] = None, ema=None, config: Optional[dict] = None):
+        self.device = torch.device(device)
+        self.model = model.to(self.device)
+        self.ema = ema
+        self.scaler = None
+        self.config = dict(config or {})
+        self.normalizers = {}
+        for key, val in (normalizers or {}).items():
+            target = _NORMALIZER_KEYS.get(key, key)
+            if isinstance(val, Normalizer):
+                self.normalizers[target] = val
+            else:
+                self.normalizers[target] = Normalizer(val.get("mean", 0), val.get("stdev", val.get("std", 1)), self.device)
+
+    @property
+    def _unwrapped_model(self):
+        module = self.model
+        while hasattr(module, "module"):
+            module = module.module
+        return module
+
+    def load_normalizers(self, state: dict) -> None:
+        """Checkpoint ``normalizers`` entry (base_trainer.py:518-530): ``target`` -> energy, ``grad_target`` -> forces;
+        keys without a configured normalizer are ignored, as in the reference."""
+        for key, sd in state.items():
+            target = _NORMALIZER_KEYS.get(key, key)
+            if target in self.normalizers:
+                self.normalizers[target].load_state_dict(sd)
+
+    @torch.no_grad()
+    def predict(self, data_loader, per_image: bool = False, results_file=None, disable_tqdm: bool = False):
+        if per_image:
+            raise NotImplementedError("per_image=True (result-file writer) is outside the relaxation path")
+        ensure_fitted(self._unwrapped_model, warn=True)
+        self.model.eval()
+        if self.ema is not None:
+            self.ema.store()
+            self.ema.copy_to()
+        try:
+            out = self.model(data_loader.to(self.device) if hasattr(data_loader, "to") else data_loader)
+            predictions = {}
+            for key in ("energy", "forces"):
+                if key not in out:
+                    continue
+                pred = out[key]
+                if self.normalizers.get(key, False):
+                    pred = self.normalizers[key].denorm(pred)
+                predictions[key] = pred.detach()
+        finally:
+            if self.ema is not None:
+                self.ema.restore()
+        return predictions

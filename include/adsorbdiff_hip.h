@@ -50,7 +50,7 @@ typedef struct {
     int32_t num_elements;      /* rows of the atom embedding table               */
     int32_t max_neighbors;     /* K of the strict top-K neighbour cap, <= 128    */
     int32_t envelope_exponent; /* p of the polynomial envelope                   */
-    int32_t num_heads;         /* 2 when so3_denoising else 1                    */
+    int32_t num_heads;         /* 2 when so3_denoising else 1; 0: no force head (S2EF energy only) */
     float cutoff;              /* Angstrom                                       */
 } adf_painn_hparams;
 
@@ -590,6 +590,52 @@ typedef struct {
 int32_t adf_eqv2_get_counters(adf_eqv2_t h, adf_eqv2_counters* out, void* stream);
 int32_t adf_eqv2_profile_enable(adf_eqv2_t h, int32_t on);
 int32_t adf_eqv2_profile_read(adf_eqv2_t h, float* ms, int64_t* count, void* stream);
+
+/* ---- S2EF PaiNN (models/painn/painn.py:52-432): the denoiser's handle with one force head (num_heads = 1, or 0 for
+ * regress_forces=False) plus the energy head out_energy = Linear(H, H/2), ScaledSiLU, Linear(H/2, 1), summed per system.
+ * adf_painn_set_weights keeps its table; the energy head is bound separately, in this order:
+ *   0 out_energy.0.weight [H/2, H]  1 out_energy.0.bias [H/2]  2 out_energy.2.weight [1, H/2]  3 out_energy.2.bias [1]
+ * The tensors are read by pointer on every forward (bind again after they move); the first one is also split into the
+ * fp16 hi/lo image of the f16x3 arithmetic here, so bind again after changing it. */
+int32_t adf_painn_set_energy_head(adf_painn_t h, int32_t n_weights, const void* const* w, void* stream);
+
+/* Floor of the edge distances (edges at or below it get it): 1e-3 by default (painn_denoising.py:366-367, so the
+ * denoiser's graphs are unchanged), 1e-6 for the S2EF model (painn.py:334-335).  The radius graph drops pairs closer
+ * than 0.01 A before (d^2 > 1e-4, utils/utils.py:536-540), so neither floor is reached by an edge of a valid graph. */
+int32_t adf_painn_set_distance_floor(adf_painn_t h, float floor);
+
+/* S2EF forward: energy [B] and forces [N,3] (forces may be NULL when num_heads == 0).  The per-system sum runs in a fixed
+ * order (one workgroup per system, no atomics): a system's energy is bit-identical whatever batch it sits in. */
+int32_t adf_painn_forward_energy(adf_painn_t h, const adf_batch* b, float* energy, float* forces, void* stream);
+
+/* ---- Batched L-BFGS of ml_relax (relaxation/optimizers/lbfgs_torch.py:22-213), model-agnostic.  All state lives on the
+ * device in fp64: s / y rings [memory, 3N], rho, alpha, r0, f0, q / z.  Dot products run over the whole flattened batch
+ * (as in the reference: the systems of one batch are coupled) with fixed-order reductions and no atomics, so a relaxation
+ * is bit-reproducible run to run.  ADF_EOOM when the history does not fit (ml_relax then splits the batch). */
+typedef struct adf_lbfgs* adf_lbfgs_t;
+int32_t adf_lbfgs_create(int64_t num_atoms, int32_t num_systems, int32_t memory, double maxstep, double damping,
+                         double alpha, int32_t early_stop_batch, adf_lbfgs_t* out);
+int32_t adf_lbfgs_destroy(adf_lbfgs_t h);
+/* a new run on the same batch shape: the history is forgotten and r0, f0 and the update mask are zeroed (enqueued on
+ * `stream`), as in a fresh handle */
+int32_t adf_lbfgs_reset(adf_lbfgs_t h, void* stream);
+/* check_convergence (:70-88): max_force[b] = max over system b of |f_atom| in fp64 (max_force f64 [B], may be NULL);
+ * the update mask of system b is max_force[b] >= fmax and is kept for the next step; *all_converged (device int32, may
+ * be NULL) = no mask set.  forces: f32 [N,3] with the constraint already applied. */
+int32_t adf_lbfgs_converge(adf_lbfgs_t h, const int32_t* atom_offset, const float* forces, double fmax,
+                           double* max_force, int32_t* all_converged, void* stream);
+/* LBFGS.step (:134-189), for iteration = 0, 1, 2, ... in order from a fresh or reset handle (anything else: ADF_EINVAL):
+ * history append (iteration > 0, deque of maxlen memory), the batch-global two-loop recursion over
+ * loopmax = min(memory, iteration) entries, determine_step, the skip of a step whose max |dr| over the batch is below 1e-7
+ * (decided on the device; r0 / f0 then stay) and pos += f32(dr) where the last converge's mask is set (everywhere with
+ * early_stop_batch).  pos: f32 [N,3] in / out.  Enqueues 3 + 2 loopmax launches, no host synchronisation. */
+int32_t adf_lbfgs_step(adf_lbfgs_t h, const int32_t* atom_offset, float* pos, const float* forces, int64_t iteration,
+                       void* stream);
+/* the update mask of the last converge, int32 [B] device */
+int32_t adf_lbfgs_get_mask(adf_lbfgs_t h, int32_t* out, void* stream);
+/* max |dr| over the batch of the last step (below 1e-7: the step was skipped), device f64 scalar.  Maxima here propagate
+ * NaN as the reference's reductions do: a NaN force clears its system's mask and does not make the step skip. */
+int32_t adf_lbfgs_last_step_max(adf_lbfgs_t h, double* out, void* stream);
 
 const char* adf_last_error(void);
 const char* adf_version(void);

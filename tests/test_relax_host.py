@@ -1,0 +1,159 @@
+"""CPU tests of the S2EF PaiNN mirror (adsorbdiff_amd.painn), the ml_relax driver and the ForcesTrainer
+(tools/make_golden_relax.py fixture (a) holds the reference's key list, shapes and per-tensor sums under a seed)."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+from adsorbdiff_amd import lib as L
+from adsorbdiff_amd import ml_relaxation as MR
+from adsorbdiff_amd.data import Batch
+from adsorbdiff_amd.exponential_moving_average import ExponentialMovingAverage
+from adsorbdiff_amd.painn import PaiNN
+from adsorbdiff_amd.synthetic import make_batch
+from adsorbdiff_amd.trainer import ForcesTrainer, Normalizer
+from tests.helpers import load_npz
+
+HP_SMALL = dict(hidden_channels=128, num_layers=2, num_rbf=128, cutoff=6.0, max_neighbors=20)
+SCALES_SMALL = {"upd_out_scalar_scale_0": 1.05, "upd_out_scalar_scale_1": 0.9}
+
+
+def test_state_dict_keys_shapes_and_seeded_weights_match_reference():
+    fx = load_npz("relax_painn.npz")
+    torch.manual_seed(int(fx["small_seed"]))
+    m = PaiNN(None, 50, 1, scale_file=dict(SCALES_SMALL), **HP_SMALL)
+    sd = m.state_dict()
+    assert [k.encode() for k in sd] == list(fx["small_keys"])
+    shapes = [list(v.shape) + [0] * (2 - v.dim()) for v in sd.values()]
+    assert shapes == fx["small_shapes"].tolist()
+    sums = np.array([float(v.double().sum()) for v in sd.values()])
+    assert np.array_equal(sums, fx["small_sums"])   # the reference's weights under the same seed
+    assert "atom_radii" not in sd and not any(k.startswith("out_forces2.") for k in sd)
+    assert m.upd_out_scalar_scale_0.fitted
+
+
+def test_full_width_keys_match_reference():
+    fx = load_npz("relax_painn.npz")
+    m = PaiNN(None, 50, 1, hidden_channels=512, num_layers=6, num_rbf=128, cutoff=12.0, max_neighbors=50)
+    assert [k.encode() for k in m.state_dict()] == list(fx["full_keys"])
+    assert [list(v.shape) + [0] * (2 - v.dim()) for v in m.state_dict().values()] == fx["full_shapes"].tolist()
+
+
+def test_s2ef_model_is_not_a_denoiser():
+    from adsorbdiff_amd import painn_denoising
+
+    m = PaiNN(None, 50, 1, hidden_channels=128, num_layers=1)
+    assert not isinstance(m, painn_denoising.PaiNN) and isinstance(m, painn_denoising.PaiNNHost)
+    assert m.num_params == sum(p.numel() for p in m.parameters())
+
+
+def test_energy_only_model_has_no_force_head():
+    m = PaiNN(None, 50, 1, hidden_channels=128, num_layers=1, regress_forces=False)
+    assert m.num_force_heads == 0 and not hasattr(m, "out_forces")
+    assert not any(k.startswith("out_forces") for k in m.state_dict())
+
+
+@pytest.mark.parametrize("kw", [dict(direct_forces=False), dict(use_pbc=False), dict(otf_graph=False)])
+def test_unsupported_configurations_raise(kw):
+    with pytest.raises(ValueError):
+        PaiNN(None, 50, 1, hidden_channels=128, num_layers=1, **kw)
+
+
+def test_forward_has_no_cpu_fallback():
+    m = PaiNN(None, 50, 1, hidden_channels=128, num_layers=1)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        m(make_batch(1, n_slab=16, n_ads=2, seed=1))
+
+
+def test_lbfgs_create_rejects_bad_arguments():
+    lib = L.load()
+    h = ctypes.c_void_p()
+    assert lib.adf_lbfgs_create(10, 1, 0, 0.04, 1.0, 70.0, 0, ctypes.byref(h)) == L.ADF_EINVAL
+    assert lib.adf_lbfgs_create(0, 1, 5, 0.04, 1.0, 70.0, 0, ctypes.byref(h)) == L.ADF_EINVAL
+    assert lib.adf_lbfgs_create(10, 1, 5, 0.04, 1.0, 0.0, 0, ctypes.byref(h)) == L.ADF_EINVAL
+    assert not h.value
+
+
+def test_ml_relax_split_order(monkeypatch):
+    """RuntimeError on a batch of more than 2 systems: halves, second half first (the reference's appendleft order)."""
+    seen = []
+
+    class StubLBFGS:
+        def __init__(self, batch, calc, **kw):
+            self.batch, self.kw = batch, kw
+
+        def run(self, fmax, steps):
+            seen.append(list(self.batch.sid))
+            if len(self.batch.sid) > 2:
+                raise RuntimeError("HIP out of memory")
+            self.batch.y = torch.zeros(len(self.batch.sid))
+            return self.batch
+
+    monkeypatch.setattr(MR, "LBFGS", StubLBFGS)
+    b = make_batch(7, n_slab=4, n_ads=1, seed=3)
+    out = MR.ml_relax(b, model=None, steps=5, fmax=0.05, relax_opt={"memory": 50}, save_full_traj=False, device="cpu")
+    assert seen == [list("0123456"), list("3456"), list("56"), list("34"), list("012"), list("12"), list("0")]
+    assert out.sid == list("5634120")
+
+
+def test_ml_relax_defaults_and_single_system_error(monkeypatch):
+    got = {}
+
+    class StubLBFGS:
+        def __init__(self, batch, calc, **kw):
+            got.update(kw)
+
+        def run(self, fmax, steps):
+            raise RuntimeError("boom")
+
+    monkeypatch.setattr(MR, "LBFGS", StubLBFGS)
+    with pytest.raises(RuntimeError, match="boom"):
+        MR.ml_relax(make_batch(1, n_slab=4, n_ads=1, seed=3), None, 5, 0.05, {"memory": 7}, True)
+    assert (got["maxstep"], got["damping"], got["alpha"], got["memory"]) == (0.04, 1.0, 70.0, 7)
+
+
+def test_ml_relax_constructor_error_is_not_split(monkeypatch):
+    """Only run() is guarded, as in the reference: an error while building the optimizer propagates unsplit."""
+    calls = []
+
+    class StubLBFGS:
+        def __init__(self, batch, calc, **kw):
+            calls.append(len(batch.sid))
+            raise RuntimeError("bad setup")
+
+    monkeypatch.setattr(MR, "LBFGS", StubLBFGS)
+    with pytest.raises(RuntimeError, match="bad setup"):
+        MR.ml_relax(make_batch(4, n_slab=4, n_ads=1, seed=3), None, 5, 0.05, {"memory": 7}, True)
+    assert calls == [4]
+
+
+class _Lin(torch.nn.Module):
+    def __init__(self):
+        super().__init__()
+        self.w = torch.nn.Parameter(torch.tensor(2.0))
+        self.otf_graph = True
+
+    def forward(self, data):
+        return {"energy": self.w * data.natoms.float(), "forces": self.w * data.pos}
+
+
+def test_forces_trainer_normalizers_and_ema_swap():
+    m = _Lin()
+    ema = ExponentialMovingAverage(m.parameters(), 0.5)
+    with torch.no_grad():
+        m.w.fill_(4.0)            # live weight 4, EMA shadow still 2
+    tr = ForcesTrainer(m, device="cpu", ema=ema,
+                       normalizers={"target": {"mean": 1.0, "stdev": 3.0}, "grad_target": {"mean": 0.0, "stdev": 0.5}})
+    assert set(tr.normalizers) == {"energy", "forces"}
+    b = Batch()
+    b.pos, b.natoms = torch.ones(3, 3), torch.tensor([3])
+    p = tr.predict(b, per_image=False, disable_tqdm=True)
+    assert torch.equal(p["energy"], torch.tensor([2.0 * 3 * 3.0 + 1.0]))    # shadow weight, denormalised
+    assert torch.equal(p["forces"], torch.full((3, 3), 2.0 * 0.5))
+    assert float(m.w.detach()) == 4.0                                             # restored after the forward
+    assert tr._unwrapped_model is m
+    tr.load_normalizers({"target": {"mean": torch.tensor(5.0), "std": torch.tensor(1.0)}, "other": {}})
+    assert float(tr.normalizers["energy"].mean) == 5.0 and float(tr.normalizers["energy"].std) == 1.0
+    n = Normalizer(2.0, 4.0)
+    assert float(n.denorm(n.norm(torch.tensor(7.0)))) == 7.0

@@ -1,0 +1,178 @@
+"""Timing of ml_relax at the relaxation shape: 1000 systems x 200 atoms, the OC20 PaiNN width (H=512, 6 layers, 128 rbf,
+cutoff 12, K=50; seeded weights) and the L-BFGS settings of configs/relaxation/gemnet_oc/gemnet_relax.yml:28-32
+(maxstep 0.04, memory 50, damping 1.0, alpha 70).  Prints one JSON line:
+
+  forward_ms          one S2EF forward (energy + forces, adf_painn_forward_energy incl. its error-flag check)
+  lbfgs_step_ms       one adf_lbfgs_step alone with a full history (50 entries: 1 + 2 x 50 + 2 launches)
+  lbfgs_converge_ms   one adf_lbfgs_converge (per-system max force and update mask, 1 launch without the flag)
+  torch_step_ms       the same step in eager torch ops on the same GPU (TorchOpsLBFGS below)
+  iterations_per_s    LBFGS.run iterations per second (forward + convergence check + step)
+
+    python tools/time_relax.py [--systems 1000] [--atoms 200] [--reps 20]
+"""
+from __future__ import annotations
+
+import argparse
+import ctypes as C
+import json
+import sys
+import time
+from pathlib import Path
+
+import torch
+
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+
+from adsorbdiff_amd import lib as _lib  # noqa: E402
+from adsorbdiff_amd.lbfgs_torch import LBFGS, TorchCalc  # noqa: E402
+from adsorbdiff_amd.painn import PaiNN  # noqa: E402
+from adsorbdiff_amd.scaling import PAINN_NB6_SCALE_FACTORS  # noqa: E402
+from adsorbdiff_amd.synthetic import make_batch  # noqa: E402
+from adsorbdiff_amd.trainer import ForcesTrainer  # noqa: E402
+
+DEV = "cuda:0"
+OPT = dict(maxstep=0.04, memory=50, damping=1.0, alpha=70.0)
+
+
+def timed(fn, reps):
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / reps
+
+
+class TorchOpsLBFGS:
+    """Baseline: the batched L-BFGS step restated with torch tensor ops on the GPU, one op per algorithmic step as an
+    eager implementation issues them - what adf_lbfgs_step replaces.  History: python lists trimmed to `memory`
+    entries, oldest first; curvature pairs (ds, dg) with weights w = 1 / <dg, ds>; the direction comes from the two-loop
+    recursion with the scalar initial inverse Hessian h0 = 1 / alpha; each system's direction is rescaled so that its
+    longest atomic displacement is at most `max_len`, then damped; a step whose largest component is below 1e-7 is dropped
+    (a device-to-host read, as in an eager loop), else it is added to the masked atoms in f32."""
+
+    def __init__(self, atom_sys, n_sys, memory, max_len, damping, alpha):
+        self.atom_sys, self.n_sys, self.memory = atom_sys, n_sys, memory
+        self.max_len, self.damping, self.h0 = max_len, damping, 1.0 / alpha
+        self.ds, self.dg, self.w = [], [], []
+        self.prev_x = self.prev_g = None
+
+    def _remember(self, x, grad):
+        ds = torch.sub(x, self.prev_x).reshape(-1)
+        dg = torch.sub(grad, self.prev_g).reshape(-1)
+        for lst, v in ((self.ds, ds), (self.dg, dg), (self.w, torch.dot(dg, ds).reciprocal())):
+            lst.append(v)
+            if len(lst) > self.memory:
+                lst.pop(0)
+
+    def direction(self, grad, n_hist):
+        v = grad.reshape(-1).clone()
+        a = grad.new_empty(n_hist)
+        for j in reversed(range(n_hist)):
+            a[j] = self.w[j] * torch.dot(self.ds[j], v)
+            v -= a[j] * self.dg[j]
+        v = self.h0 * v
+        for j in range(n_hist):
+            b = self.w[j] * torch.dot(self.dg[j], v)
+            v += self.ds[j] * (a[j] - b)
+        return -v.reshape(-1, 3)
+
+    def scaled(self, d):
+        atom_len = torch.linalg.vector_norm(d, dim=1)
+        longest = torch.zeros(self.n_sys, dtype=d.dtype, device=d.device).scatter_reduce_(
+            0, self.atom_sys, atom_len, "amax", include_self=False).index_select(0, self.atom_sys)
+        factor = torch.minimum(longest, torch.full_like(longest, self.max_len)) * torch.reciprocal(longest + 1e-7)
+        return d * factor.unsqueeze(1) * self.damping
+
+    def step(self, pos, forces64, it, atom_mask):
+        x = pos.to(torch.float64)
+        grad = -forces64                         # the gradient of the energy
+        if it > 0:
+            self._remember(x, grad)
+        move = self.scaled(self.direction(grad, min(self.memory, it)))
+        if float(move.abs().max()) < 1e-7:
+            return
+        pos.add_(move.masked_fill(~atom_mask.unsqueeze(1), 0.0).to(torch.float32))
+        self.prev_x, self.prev_g = x, grad
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--systems", type=int, default=1000)
+    ap.add_argument("--atoms", type=int, default=200)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--run-steps", type=int, default=8)
+    a = ap.parse_args()
+    torch.manual_seed(0)
+    model = PaiNN(None, 50, 1, hidden_channels=512, num_layers=6, num_rbf=128, cutoff=12.0, max_neighbors=50,
+                  scale_file=dict(PAINN_NB6_SCALE_FACTORS)).to(DEV).eval()
+    b = make_batch(a.systems, n_slab=a.atoms - 4, n_ads=4, seed=1000).to(DEV)
+    N, B = int(b.pos.shape[0]), a.systems
+    out = {"systems": B, "atoms": N, **OPT}
+
+    with torch.no_grad():
+        model(b)   # engine, workspaces
+        out["forward_ms"] = timed(lambda: model(b), a.reps)
+
+    # one adf_lbfgs_step with a full history (synthetic forces; the arithmetic does not depend on their values)
+    lib = _lib.load()
+    g = torch.Generator(device=DEV).manual_seed(1)
+    fs = [torch.randn(N, 3, device=DEV, generator=g) * 0.1 for _ in range(4)]
+    off = torch.zeros(B + 1, dtype=torch.int32, device=DEV)
+    off[1:] = torch.cumsum(b.natoms.to(DEV), 0).to(torch.int32)
+    h = C.c_void_p()
+    _lib.check(lib.adf_lbfgs_create(N, B, OPT["memory"], OPT["maxstep"], OPT["damping"], OPT["alpha"], 0, C.byref(h)))
+    pos = b.pos.clone().float().contiguous()
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    mf = torch.empty(B, dtype=torch.float64, device=DEV)
+    it = [0]
+
+    def dev_converge():
+        _lib.check(lib.adf_lbfgs_converge(h, off.data_ptr(), fs[it[0] % 4].data_ptr(), 1e-9, mf.data_ptr(), None, stream))
+
+    def dev_step():
+        _lib.check(lib.adf_lbfgs_step(h, off.data_ptr(), pos.data_ptr(), fs[it[0] % 4].data_ptr(), it[0], stream))
+        it[0] += 1
+
+    for _ in range(OPT["memory"] + 1):
+        dev_converge()
+        dev_step()
+    dev_converge()   # the update mask of the timed steps (every system moves: fmax 1e-9)
+    out["lbfgs_step_ms"] = timed(dev_step, a.reps)
+    out["lbfgs_converge_ms"] = timed(dev_converge, a.reps)
+    torch.cuda.synchronize()
+    lib.adf_lbfgs_destroy(h)
+
+    # the same step in eager torch ops, full history
+    base = TorchOpsLBFGS(b.batch.to(DEV), B, OPT["memory"], OPT["maxstep"], OPT["damping"], OPT["alpha"])
+    pos_t = b.pos.clone().float()
+    mask = torch.ones(N, dtype=torch.bool, device=DEV)
+    itt = [0]
+
+    def torch_step():
+        base.step(pos_t, fs[itt[0] % 4].double(), itt[0], mask)
+        itt[0] += 1
+
+    for _ in range(OPT["memory"] + 1):
+        torch_step()
+    out["torch_step_ms"] = timed(torch_step, a.reps)
+    del base
+
+    # LBFGS.run iterations per second (fmax tiny: no system converges)
+    tr = ForcesTrainer(model, device=DEV)
+    b2 = make_batch(a.systems, n_slab=a.atoms - 4, n_ads=4, seed=1000).to(DEV)
+    opt = LBFGS(b2, TorchCalc(tr), device=DEV, **OPT)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    opt.run(fmax=1e-9, steps=a.run_steps)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    out["run_iterations"] = opt.iterations
+    out["iterations_per_s"] = opt.iterations / dt
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
