@@ -1071,33 +1071,35 @@ extern "C" int32_t adf_check_flags(adf_painn_t h, void* stream) {
     return read_flags(h, (hipStream_t)stream);
 }
 
+// ---- the stepper entries and the fused sampling loop (stepper.hip) on a PaiNN handle
+static int32_t model_check(void* h, const adf_batch* b) { return check_batch((adf_painn*)h, b); }
+static int32_t model_grow(void* h, const adf_batch* b, float** sys) {
+    adf_painn* p = (adf_painn*)h;
+    ADF_TRY(ensure_capacity(p, b->num_atoms, b->num_systems));
+    *sys = p->sys;
+    return ADF_OK;
+}
+static int32_t model_forward(void* h, const adf_batch* b, const int32_t* out_idx, int32_t n_out, float* f1, float* f2,
+                             hipStream_t s) {
+    return forward_impl((adf_painn*)h, b, out_idx, out_idx ? n_out : 0, f1, f2, s, !f2);
+}
+static void model_prof(void* h, bool begin, hipStream_t s) {
+    if (begin) adf_prof_begin((adf_painn*)h, ADF_PROF_STEPPER, s);
+    else adf_prof_end((adf_painn*)h, s);
+}
+static adf_model model(adf_painn_t h) { return {h, model_check, model_grow, model_forward, model_prof}; }
+
 extern "C" int32_t adf_sde_init_placement(adf_painn_t h, const adf_batch* b, float* pos, const int32_t* tags,
                                           const float* noise, void* stream) {
-    ADF_TRY(check_batch(h, b));
-    if (!pos || !tags || !noise) { adf_set_error("null argument"); return ADF_EINVAL; }
-    return adf_stepper_init(b, pos, tags, noise, (hipStream_t)stream);
-}
-
-static int32_t sde_step_common(adf_painn_t h, const adf_batch* b, float* pos, const int32_t* tags,
-                               const int32_t* fixed, const float* f1, const float* f2, const adf_step_coef* coef,
-                               const adf_step_coef* coefs_dev, int32_t num_steps, const float* z_tr, const float* z_rot,
-                               int32_t early_stop_count, int32_t* state, float* dcom, float* drot, void* stream) {
-    ADF_TRY(check_batch(h, b));
-    if (!pos || !tags || !f1 || !f2 || (!coef && !coefs_dev) || !state) { adf_set_error("null argument"); return ADF_EINVAL; }
-    ADF_TRY(ensure_capacity(h, b->num_atoms, b->num_systems));
-    adf_prof_begin(h, ADF_PROF_STEPPER, (hipStream_t)stream);
-    const int32_t st = adf_stepper_step(h->sys, b, pos, tags, fixed, f1, f2, coef, coefs_dev, num_steps, z_tr, z_rot,
-                                        early_stop_count, state, dcom, drot, (hipStream_t)stream);
-    adf_prof_end(h, (hipStream_t)stream);
-    return st;
+    return adf_model_init_placement(model(h), b, pos, tags, noise, (hipStream_t)stream);
 }
 
 extern "C" int32_t adf_sde_step(adf_painn_t h, const adf_batch* b, float* pos, const int32_t* tags,
                                 const int32_t* fixed, const float* f1, const float* f2, const adf_step_coef* coef,
                                 const float* z_tr, const float* z_rot, int32_t early_stop_count, int32_t* state,
                                 float* dcom, float* drot, void* stream) {
-    return sde_step_common(h, b, pos, tags, fixed, f1, f2, coef, nullptr, 0, z_tr, z_rot, early_stop_count, state, dcom,
-                           drot, stream);
+    return adf_model_sde_step(model(h), b, pos, tags, fixed, f1, f2, coef, nullptr, 0, z_tr, z_rot, early_stop_count, state,
+                              dcom, drot, (hipStream_t)stream);
 }
 
 extern "C" int32_t adf_sde_step_scheduled(adf_painn_t h, const adf_batch* b, float* pos, const int32_t* tags,
@@ -1105,51 +1107,16 @@ extern "C" int32_t adf_sde_step_scheduled(adf_painn_t h, const adf_batch* b, flo
                                           const adf_step_coef* coefs_dev, int32_t num_steps, const float* z_tr,
                                           const float* z_rot, int32_t early_stop_count, int32_t* state, float* dcom,
                                           float* drot, void* stream) {
-    if (num_steps <= 0) { adf_set_error("num_steps must be positive"); return ADF_EINVAL; }
-    return sde_step_common(h, b, pos, tags, fixed, f1, f2, nullptr, coefs_dev, num_steps, z_tr, z_rot, early_stop_count,
-                           state, dcom, drot, stream);
-}
-
-// The whole reverse loop (denoising_torch.py:235-356) in one call: num_steps x (graph build + forward + step), all
-// on `stream`.  Host round trips: with poll_every > 0 the frozen flag is read back every poll_every steps and the loop
-// ends early, exactly like the reference's `break`; with incremental layers on, each forward reads its list lengths.
-struct adf_frames;
-int32_t adf_frames_push_impl(adf_frames* f, const float* src, hipStream_t s);
-
-static int32_t sample_impl(adf_painn_t h, const adf_batch* b, float* pos, const int32_t* tags, const int32_t* fixed,
-                           const adf_step_coef* coefs_dev, int32_t num_steps, const float* z_tr_all,
-                           const float* z_rot_all, int32_t early_stop_count, int32_t poll_every, int32_t* state,
-                           const int32_t* out_idx, int32_t n_out, float* f1, float* f2, adf_frames* sink,
-                           int32_t frame_every, void* stream) {
-    ADF_TRY(check_batch(h, b));
-    if (num_steps <= 0 || !f1 || !f2 || !state || !coefs_dev || !pos || !tags) { adf_set_error("sample: bad argument"); return ADF_EINVAL; }
-    if ((z_tr_all == nullptr) != (z_rot_all == nullptr)) { adf_set_error("sample: need both noise tables or none"); return ADF_EINVAL; }
-    if (sink && frame_every <= 0) { adf_set_error("sample: frame_every must be positive"); return ADF_EINVAL; }
-    hipStream_t s = (hipStream_t)stream;
-    const size_t zs = (size_t)b->num_systems * 3;
-    for (int t = 0; t < num_steps; ++t) {
-        ADF_TRY(forward_impl(h, b, out_idx, out_idx ? n_out : 0, f1, f2, stream));
-        ADF_TRY(sde_step_common(h, b, pos, tags, fixed, f1, f2, nullptr, coefs_dev, num_steps,
-                                z_tr_all ? z_tr_all + t * zs : nullptr, z_rot_all ? z_rot_all + t * zs : nullptr,
-                                early_stop_count, state, nullptr, nullptr, stream));
-        // trajectory frame of this step: snapshot on this stream, copy-out on the sink's stream (frames.hip)
-        if (sink && ((t + 1) % frame_every == 0 || t + 1 == num_steps)) ADF_TRY(adf_frames_push_impl(sink, pos, s));
-        if (early_stop_count > 0 && poll_every > 0 && (t % poll_every) == poll_every - 1 && t + 1 < num_steps) {
-            int32_t frozen = 0;
-            ADF_HIP_CHECK(hipMemcpyAsync(&frozen, state + 1, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-            ADF_HIP_CHECK(hipStreamSynchronize(s));
-            if (frozen) break;
-        }
-    }
-    return ADF_OK;
+    return adf_model_sde_step(model(h), b, pos, tags, fixed, f1, f2, nullptr, coefs_dev, num_steps, z_tr, z_rot,
+                              early_stop_count, state, dcom, drot, (hipStream_t)stream);
 }
 
 extern "C" int32_t adf_sample(adf_painn_t h, const adf_batch* b, float* pos, const int32_t* tags, const int32_t* fixed,
                               const adf_step_coef* coefs_dev, int32_t num_steps, const float* z_tr_all,
                               const float* z_rot_all, int32_t early_stop_count, int32_t poll_every, int32_t* state,
                               const int32_t* out_idx, int32_t n_out, float* f1, float* f2, void* stream) {
-    return sample_impl(h, b, pos, tags, fixed, coefs_dev, num_steps, z_tr_all, z_rot_all, early_stop_count, poll_every, state,
-                       out_idx, n_out, f1, f2, nullptr, 0, stream);
+    return adf_model_sample(model(h), b, pos, tags, fixed, coefs_dev, num_steps, z_tr_all, z_rot_all, early_stop_count,
+                            poll_every, state, out_idx, n_out, f1, f2, nullptr, 0, (hipStream_t)stream);
 }
 
 extern "C" int32_t adf_sample_traj(adf_painn_t h, const adf_batch* b, float* pos, const int32_t* tags, const int32_t* fixed,
@@ -1158,58 +1125,24 @@ extern "C" int32_t adf_sample_traj(adf_painn_t h, const adf_batch* b, float* pos
                                    const int32_t* out_idx, int32_t n_out, float* f1, float* f2, adf_frames_t sink,
                                    int32_t frame_every, void* stream) {
     if (!sink) { adf_set_error("sample_traj: null sink"); return ADF_EINVAL; }
-    return sample_impl(h, b, pos, tags, fixed, coefs_dev, num_steps, z_tr_all, z_rot_all, early_stop_count, poll_every, state,
-                       out_idx, n_out, f1, f2, sink, frame_every, stream);
+    return adf_model_sample(model(h), b, pos, tags, fixed, coefs_dev, num_steps, z_tr_all, z_rot_all, early_stop_count,
+                            poll_every, state, out_idx, n_out, f1, f2, sink, frame_every, (hipStream_t)stream);
 }
 
 // Translation-only samplers (reverse_sde_sampling / langevin_dynamics, denoising_torch.py:96-196, 369-458)
 extern "C" int32_t adf_tr_step(adf_painn_t h, const adf_batch* b, float* pos, const int32_t* tags, const float* f1,
                                const adf_tr_coef* coef, const adf_tr_coef* coefs_dev, int32_t num_steps, const float* z,
                                int32_t early_stop_count, int32_t* state, float* dcom, void* stream) {
-    ADF_TRY(check_batch(h, b));
-    if (!pos || !tags || !f1 || (!coef && !coefs_dev) || !state) { adf_set_error("tr_step: null argument"); return ADF_EINVAL; }
-    if (!coef && num_steps <= 0) { adf_set_error("tr_step: num_steps must be positive"); return ADF_EINVAL; }
-    ADF_TRY(ensure_capacity(h, b->num_atoms, b->num_systems));
-    adf_prof_begin(h, ADF_PROF_STEPPER, (hipStream_t)stream);
-    const int32_t st = adf_stepper_tr_step(h->sys, b, pos, tags, f1, coef, coefs_dev, num_steps, z, early_stop_count, state,
-                                           dcom, (hipStream_t)stream);
-    adf_prof_end(h, (hipStream_t)stream);
-    return st;
-}
-
-static int32_t tr_sample_impl(adf_painn_t h, const adf_batch* b, float* pos, const int32_t* tags,
-                              const adf_tr_coef* coefs_dev, int32_t num_steps, const float* z_all, int32_t early_stop_count,
-                              int32_t poll_every, int32_t* state, const int32_t* out_idx, int32_t n_out, float* f1,
-                              adf_frames* sink, int32_t frame_every, void* stream) {
-    ADF_TRY(check_batch(h, b));
-    if (num_steps <= 0 || !f1 || !state || !coefs_dev || !pos || !tags || (out_idx && n_out < 0)) {
-        adf_set_error("tr_sample: bad argument");
-        return ADF_EINVAL;
-    }
-    if (sink && frame_every <= 0) { adf_set_error("tr_sample: frame_every must be positive"); return ADF_EINVAL; }
-    hipStream_t s = (hipStream_t)stream;
-    const size_t zs = (size_t)b->num_systems * 3;
-    for (int t = 0; t < num_steps; ++t) {
-        ADF_TRY(forward_impl(h, b, out_idx, out_idx ? n_out : 0, f1, nullptr, stream, true));
-        ADF_TRY(adf_tr_step(h, b, pos, tags, f1, nullptr, coefs_dev, num_steps, z_all ? z_all + t * zs : nullptr,
-                            early_stop_count, state, nullptr, stream));
-        if (sink && ((t + 1) % frame_every == 0 || t + 1 == num_steps)) ADF_TRY(adf_frames_push_impl(sink, pos, s));
-        if (early_stop_count > 0 && poll_every > 0 && (t % poll_every) == poll_every - 1 && t + 1 < num_steps) {
-            int32_t frozen = 0;
-            ADF_HIP_CHECK(hipMemcpyAsync(&frozen, state + 1, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-            ADF_HIP_CHECK(hipStreamSynchronize(s));
-            if (frozen) break;
-        }
-    }
-    return ADF_OK;
+    return adf_model_tr_step(model(h), b, pos, tags, f1, coef, coefs_dev, num_steps, z, early_stop_count, state, dcom,
+                             (hipStream_t)stream);
 }
 
 extern "C" int32_t adf_tr_sample(adf_painn_t h, const adf_batch* b, float* pos, const int32_t* tags,
                                  const adf_tr_coef* coefs_dev, int32_t num_steps, const float* z_all,
                                  int32_t early_stop_count, int32_t poll_every, int32_t* state, const int32_t* out_idx,
                                  int32_t n_out, float* f1, void* stream) {
-    return tr_sample_impl(h, b, pos, tags, coefs_dev, num_steps, z_all, early_stop_count, poll_every, state, out_idx, n_out,
-                          f1, nullptr, 0, stream);
+    return adf_model_tr_sample(model(h), b, pos, tags, coefs_dev, num_steps, z_all, early_stop_count, poll_every, state,
+                               out_idx, n_out, f1, nullptr, 0, (hipStream_t)stream);
 }
 
 extern "C" int32_t adf_tr_sample_traj(adf_painn_t h, const adf_batch* b, float* pos, const int32_t* tags,
@@ -1217,8 +1150,8 @@ extern "C" int32_t adf_tr_sample_traj(adf_painn_t h, const adf_batch* b, float* 
                                       int32_t early_stop_count, int32_t poll_every, int32_t* state, const int32_t* out_idx,
                                       int32_t n_out, float* f1, adf_frames_t sink, int32_t frame_every, void* stream) {
     if (!sink) { adf_set_error("tr_sample_traj: null sink"); return ADF_EINVAL; }
-    return tr_sample_impl(h, b, pos, tags, coefs_dev, num_steps, z_all, early_stop_count, poll_every, state, out_idx, n_out,
-                          f1, sink, frame_every, stream);
+    return adf_model_tr_sample(model(h), b, pos, tags, coefs_dev, num_steps, z_all, early_stop_count, poll_every, state,
+                               out_idx, n_out, f1, sink, frame_every, (hipStream_t)stream);
 }
 
 extern "C" int32_t adf_get_counters(adf_painn_t h, adf_counters* out, void* stream) {

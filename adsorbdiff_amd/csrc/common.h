@@ -286,3 +286,35 @@ int32_t adf_stepper_step(float* sys, const adf_batch* b, float* pos, const int32
 int32_t adf_stepper_tr_step(float* sys, const adf_batch* b, float* pos, const int32_t* tags, const float* f1,
                             const adf_tr_coef* coef, const adf_tr_coef* coefs_dev, int num_steps, const float* z,
                             int32_t early_stop_count, int32_t* state, float* dcom, hipStream_t s);
+
+// ---- the stepper entries and the fused sampling loop of both score models (stepper.hip).  The model side: api.hip
+// (PaiNN) and eqv2_api.hip (EquiformerV2) fill one in for a handle.
+struct adf_model {
+    void* h;
+    int32_t (*check)(void* h, const adf_batch* b);               // the handle's batch check
+    int32_t (*grow)(void* h, const adf_batch* b, float** sys);   // grow-only workspaces; *sys = per-system scratch [16 B]
+    // forward of all atoms (out_idx null) or of the out_idx rows; f2 null: head 1 alone (translation samplers)
+    int32_t (*forward)(void* h, const adf_batch* b, const int32_t* out_idx, int32_t n_out, float* f1, float* f2,
+                       hipStream_t s);
+    void (*prof)(void* h, bool begin, hipStream_t s);            // time the step under the model's stepper category
+};
+int32_t adf_frames_push_impl(adf_frames* f, const float* src, hipStream_t s);
+// the entries of include/adsorbdiff_hip.h on the handle of `m` (same arguments and contracts)
+int32_t adf_model_init_placement(const adf_model& m, const adf_batch* b, float* pos, const int32_t* tags,
+                                 const float* noise, hipStream_t s);
+int32_t adf_model_sde_step(const adf_model& m, const adf_batch* b, float* pos, const int32_t* tags, const int32_t* fixed,
+                           const float* f1, const float* f2, const adf_step_coef* coef, const adf_step_coef* coefs_dev,
+                           int32_t num_steps, const float* z_tr, const float* z_rot, int32_t early_stop_count,
+                           int32_t* state, float* dcom, float* drot, hipStream_t s);
+int32_t adf_model_tr_step(const adf_model& m, const adf_batch* b, float* pos, const int32_t* tags, const float* f1,
+                          const adf_tr_coef* coef, const adf_tr_coef* coefs_dev, int32_t num_steps, const float* z,
+                          int32_t early_stop_count, int32_t* state, float* dcom, hipStream_t s);
+// sink null: adf_[eqv2_]sample, else adf_[eqv2_]sample_traj
+int32_t adf_model_sample(const adf_model& m, const adf_batch* b, float* pos, const int32_t* tags, const int32_t* fixed,
+                         const adf_step_coef* coefs_dev, int32_t num_steps, const float* z_tr_all, const float* z_rot_all,
+                         int32_t early_stop_count, int32_t poll_every, int32_t* state, const int32_t* out_idx,
+                         int32_t n_out, float* f1, float* f2, adf_frames* sink, int32_t frame_every, hipStream_t s);
+int32_t adf_model_tr_sample(const adf_model& m, const adf_batch* b, float* pos, const int32_t* tags,
+                            const adf_tr_coef* coefs_dev, int32_t num_steps, const float* z_all, int32_t early_stop_count,
+                            int32_t poll_every, int32_t* state, const int32_t* out_idx, int32_t n_out, float* f1,
+                            adf_frames* sink, int32_t frame_every, hipStream_t s);

@@ -1166,65 +1166,42 @@ extern "C" int32_t adf_eqv2_check_flags(adf_eqv2_t h, void* stream) {
 }
 
 // ---------------------------------------------------------------------------------------------- stepper on this handle
+static int32_t eq_model_check(void* h, const adf_batch* b) { return eq_check_batch((adf_eqv2*)h, b); }
+static int32_t eq_model_grow(void* h, const adf_batch* b, float** sys) {
+    adf_eqv2* q = (adf_eqv2*)h;
+    ADF_TRY(eq_ensure_capacity(q, b->num_atoms, b->num_systems, q->ext_graph ? q->E_ext : 0));
+    *sys = q->sys;
+    return ADF_OK;
+}
+static int32_t eq_model_forward(void* h, const adf_batch* b, const int32_t* out_idx, int32_t n_out, float* f1, float* f2,
+                                hipStream_t s) {
+    return eq_forward_impl((adf_eqv2*)h, b, f1, f2, nullptr, s, out_idx, n_out);
+}
+static void eq_model_prof(void* h, bool begin, hipStream_t s) {
+    if (begin) eq_prof_begin((adf_eqv2*)h, EQ_PROF_STEPPER, s);
+    else eq_prof_end((adf_eqv2*)h, s);
+}
+static adf_model eq_model(adf_eqv2_t h) { return {h, eq_model_check, eq_model_grow, eq_model_forward, eq_model_prof}; }
+
 extern "C" int32_t adf_eqv2_init_placement(adf_eqv2_t h, const adf_batch* b, float* pos, const int32_t* tags,
                                            const float* noise, void* stream) {
-    ADF_TRY(eq_check_batch(h, b));
-    if (!pos || !tags || !noise) { adf_set_error("null argument"); return ADF_EINVAL; }
-    return adf_stepper_init(b, pos, tags, noise, (hipStream_t)stream);
+    return adf_model_init_placement(eq_model(h), b, pos, tags, noise, (hipStream_t)stream);
 }
 
 extern "C" int32_t adf_eqv2_sde_step(adf_eqv2_t h, const adf_batch* b, float* pos, const int32_t* tags, const int32_t* fixed,
                                      const float* f1, const float* f2, const adf_step_coef* coef,
                                      const adf_step_coef* coefs_dev, int32_t num_steps, const float* z_tr, const float* z_rot,
                                      int32_t early_stop_count, int32_t* state, float* dcom, float* drot, void* stream) {
-    ADF_TRY(eq_check_batch(h, b));
-    if (!pos || !tags || !f1 || !f2 || (!coef && !coefs_dev) || !state) { adf_set_error("null argument"); return ADF_EINVAL; }
-    if (!coef && num_steps <= 0) { adf_set_error("num_steps must be positive"); return ADF_EINVAL; }
-    ADF_TRY(eq_ensure_capacity(h, b->num_atoms, b->num_systems, h->ext_graph ? h->E_ext : 0));
-    eq_prof_scope ps(h, EQ_PROF_STEPPER, (hipStream_t)stream);
-    return adf_stepper_step(h->sys, b, pos, tags, fixed, f1, f2, coef, coef ? nullptr : coefs_dev, num_steps, z_tr, z_rot,
-                            early_stop_count, state, dcom, drot, (hipStream_t)stream);
-}
-
-struct adf_frames;
-int32_t adf_frames_push_impl(adf_frames* f, const float* src, hipStream_t s);
-
-static int32_t eq_sample_impl(adf_eqv2_t h, const adf_batch* b, float* pos, const int32_t* tags, const int32_t* fixed,
-                              const adf_step_coef* coefs_dev, int32_t num_steps, const float* z_tr_all,
-                              const float* z_rot_all, int32_t early_stop_count, int32_t poll_every, int32_t* state,
-                              const int32_t* out_idx, int32_t n_out, float* f1, float* f2, adf_frames* sink,
-                              int32_t frame_every, void* stream) {
-    ADF_TRY(eq_check_batch(h, b));
-    if (num_steps <= 0 || !f1 || !f2 || !state || !coefs_dev || !pos || !tags || (out_idx && n_out < 0)) {
-        adf_set_error("eqv2_sample: bad argument");
-        return ADF_EINVAL;
-    }
-    if ((z_tr_all == nullptr) != (z_rot_all == nullptr)) { adf_set_error("eqv2_sample: need both noise tables or none"); return ADF_EINVAL; }
-    if (sink && frame_every <= 0) { adf_set_error("eqv2_sample: frame_every must be positive"); return ADF_EINVAL; }
-    hipStream_t s = (hipStream_t)stream;
-    const size_t zs = (size_t)b->num_systems * 3;
-    for (int t = 0; t < num_steps; ++t) {
-        ADF_TRY(eq_forward_impl(h, b, f1, f2, nullptr, s, out_idx, n_out));
-        ADF_TRY(adf_eqv2_sde_step(h, b, pos, tags, fixed, f1, f2, nullptr, coefs_dev, num_steps,
-                                  z_tr_all ? z_tr_all + t * zs : nullptr, z_rot_all ? z_rot_all + t * zs : nullptr,
-                                  early_stop_count, state, nullptr, nullptr, stream));
-        if (sink && ((t + 1) % frame_every == 0 || t + 1 == num_steps)) ADF_TRY(adf_frames_push_impl(sink, pos, s));
-        if (early_stop_count > 0 && poll_every > 0 && (t % poll_every) == poll_every - 1 && t + 1 < num_steps) {
-            int32_t frozen = 0;
-            ADF_HIP_CHECK(hipMemcpyAsync(&frozen, state + 1, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-            ADF_HIP_CHECK(hipStreamSynchronize(s));
-            if (frozen) break;
-        }
-    }
-    return ADF_OK;
+    return adf_model_sde_step(eq_model(h), b, pos, tags, fixed, f1, f2, coef, coefs_dev, num_steps, z_tr, z_rot,
+                              early_stop_count, state, dcom, drot, (hipStream_t)stream);
 }
 
 extern "C" int32_t adf_eqv2_sample(adf_eqv2_t h, const adf_batch* b, float* pos, const int32_t* tags, const int32_t* fixed,
                                    const adf_step_coef* coefs_dev, int32_t num_steps, const float* z_tr_all,
                                    const float* z_rot_all, int32_t early_stop_count, int32_t poll_every, int32_t* state,
                                    const int32_t* out_idx, int32_t n_out, float* f1, float* f2, void* stream) {
-    return eq_sample_impl(h, b, pos, tags, fixed, coefs_dev, num_steps, z_tr_all, z_rot_all, early_stop_count, poll_every,
-                          state, out_idx, n_out, f1, f2, nullptr, 0, stream);
+    return adf_model_sample(eq_model(h), b, pos, tags, fixed, coefs_dev, num_steps, z_tr_all, z_rot_all, early_stop_count,
+                            poll_every, state, out_idx, n_out, f1, f2, nullptr, 0, (hipStream_t)stream);
 }
 
 extern "C" int32_t adf_eqv2_sample_traj(adf_eqv2_t h, const adf_batch* b, float* pos, const int32_t* tags,
@@ -1233,8 +1210,8 @@ extern "C" int32_t adf_eqv2_sample_traj(adf_eqv2_t h, const adf_batch* b, float*
                                         int32_t poll_every, int32_t* state, const int32_t* out_idx, int32_t n_out, float* f1,
                                         float* f2, adf_frames_t sink, int32_t frame_every, void* stream) {
     if (!sink) { adf_set_error("eqv2_sample_traj: null sink"); return ADF_EINVAL; }
-    return eq_sample_impl(h, b, pos, tags, fixed, coefs_dev, num_steps, z_tr_all, z_rot_all, early_stop_count, poll_every,
-                          state, out_idx, n_out, f1, f2, sink, frame_every, stream);
+    return adf_model_sample(eq_model(h), b, pos, tags, fixed, coefs_dev, num_steps, z_tr_all, z_rot_all, early_stop_count,
+                            poll_every, state, out_idx, n_out, f1, f2, sink, frame_every, (hipStream_t)stream);
 }
 
 // Translation-only samplers (reverse_sde_sampling / langevin_dynamics, denoising_torch.py:96-196, 369-458): force_block
@@ -1242,48 +1219,16 @@ extern "C" int32_t adf_eqv2_sample_traj(adf_eqv2_t h, const adf_batch* b, float*
 extern "C" int32_t adf_eqv2_tr_step(adf_eqv2_t h, const adf_batch* b, float* pos, const int32_t* tags, const float* f1,
                                     const adf_tr_coef* coef, const adf_tr_coef* coefs_dev, int32_t num_steps, const float* z,
                                     int32_t early_stop_count, int32_t* state, float* dcom, void* stream) {
-    ADF_TRY(eq_check_batch(h, b));
-    if (!pos || !tags || !f1 || (!coef && !coefs_dev) || !state) { adf_set_error("eqv2_tr_step: null argument"); return ADF_EINVAL; }
-    if (!coef && num_steps <= 0) { adf_set_error("eqv2_tr_step: num_steps must be positive"); return ADF_EINVAL; }
-    ADF_TRY(eq_ensure_capacity(h, b->num_atoms, b->num_systems, h->ext_graph ? h->E_ext : 0));
-    eq_prof_scope ps(h, EQ_PROF_STEPPER, (hipStream_t)stream);
-    return adf_stepper_tr_step(h->sys, b, pos, tags, f1, coef, coefs_dev, num_steps, z, early_stop_count, state, dcom,
-                               (hipStream_t)stream);
-}
-
-static int32_t eq_tr_sample_impl(adf_eqv2_t h, const adf_batch* b, float* pos, const int32_t* tags,
-                                 const adf_tr_coef* coefs_dev, int32_t num_steps, const float* z_all,
-                                 int32_t early_stop_count, int32_t poll_every, int32_t* state, const int32_t* out_idx,
-                                 int32_t n_out, float* f1, adf_frames* sink, int32_t frame_every, void* stream) {
-    ADF_TRY(eq_check_batch(h, b));
-    if (num_steps <= 0 || !f1 || !state || !coefs_dev || !pos || !tags || (out_idx && n_out < 0)) {
-        adf_set_error("eqv2_tr_sample: bad argument");
-        return ADF_EINVAL;
-    }
-    if (sink && frame_every <= 0) { adf_set_error("eqv2_tr_sample: frame_every must be positive"); return ADF_EINVAL; }
-    hipStream_t s = (hipStream_t)stream;
-    const size_t zs = (size_t)b->num_systems * 3;
-    for (int t = 0; t < num_steps; ++t) {
-        ADF_TRY(eq_forward_impl(h, b, f1, nullptr, nullptr, s, out_idx, n_out));
-        ADF_TRY(adf_eqv2_tr_step(h, b, pos, tags, f1, nullptr, coefs_dev, num_steps, z_all ? z_all + t * zs : nullptr,
-                                 early_stop_count, state, nullptr, stream));
-        if (sink && ((t + 1) % frame_every == 0 || t + 1 == num_steps)) ADF_TRY(adf_frames_push_impl(sink, pos, s));
-        if (early_stop_count > 0 && poll_every > 0 && (t % poll_every) == poll_every - 1 && t + 1 < num_steps) {
-            int32_t frozen = 0;
-            ADF_HIP_CHECK(hipMemcpyAsync(&frozen, state + 1, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-            ADF_HIP_CHECK(hipStreamSynchronize(s));
-            if (frozen) break;
-        }
-    }
-    return ADF_OK;
+    return adf_model_tr_step(eq_model(h), b, pos, tags, f1, coef, coefs_dev, num_steps, z, early_stop_count, state, dcom,
+                             (hipStream_t)stream);
 }
 
 extern "C" int32_t adf_eqv2_tr_sample(adf_eqv2_t h, const adf_batch* b, float* pos, const int32_t* tags,
                                       const adf_tr_coef* coefs_dev, int32_t num_steps, const float* z_all,
                                       int32_t early_stop_count, int32_t poll_every, int32_t* state, const int32_t* out_idx,
                                       int32_t n_out, float* f1, void* stream) {
-    return eq_tr_sample_impl(h, b, pos, tags, coefs_dev, num_steps, z_all, early_stop_count, poll_every, state, out_idx,
-                             n_out, f1, nullptr, 0, stream);
+    return adf_model_tr_sample(eq_model(h), b, pos, tags, coefs_dev, num_steps, z_all, early_stop_count, poll_every, state,
+                               out_idx, n_out, f1, nullptr, 0, (hipStream_t)stream);
 }
 
 extern "C" int32_t adf_eqv2_tr_sample_traj(adf_eqv2_t h, const adf_batch* b, float* pos, const int32_t* tags,
@@ -1292,8 +1237,8 @@ extern "C" int32_t adf_eqv2_tr_sample_traj(adf_eqv2_t h, const adf_batch* b, flo
                                            const int32_t* out_idx, int32_t n_out, float* f1, adf_frames_t sink,
                                            int32_t frame_every, void* stream) {
     if (!sink) { adf_set_error("eqv2_tr_sample_traj: null sink"); return ADF_EINVAL; }
-    return eq_tr_sample_impl(h, b, pos, tags, coefs_dev, num_steps, z_all, early_stop_count, poll_every, state, out_idx,
-                             n_out, f1, sink, frame_every, stream);
+    return adf_model_tr_sample(eq_model(h), b, pos, tags, coefs_dev, num_steps, z_all, early_stop_count, poll_every, state,
+                               out_idx, n_out, f1, sink, frame_every, (hipStream_t)stream);
 }
 
 // Stand-alone C = act(A . W^T + b) through the dense-product kernels of this path (unit tests, micro-benchmarks).

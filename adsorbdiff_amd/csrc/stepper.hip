@@ -313,6 +313,100 @@ int32_t adf_stepper_tr_step(float* sys, const adf_batch* b, float* pos, const in
     return ADF_OK;
 }
 
+// ------------------------------------------------------------------------------- the entries on a model's handle
+int32_t adf_model_init_placement(const adf_model& m, const adf_batch* b, float* pos, const int32_t* tags,
+                                 const float* noise, hipStream_t s) {
+    ADF_TRY(m.check(m.h, b));
+    if (!pos || !tags || !noise) { adf_set_error("null argument"); return ADF_EINVAL; }
+    return adf_stepper_init(b, pos, tags, noise, s);
+}
+
+int32_t adf_model_sde_step(const adf_model& m, const adf_batch* b, float* pos, const int32_t* tags, const int32_t* fixed,
+                           const float* f1, const float* f2, const adf_step_coef* coef, const adf_step_coef* coefs_dev,
+                           int32_t num_steps, const float* z_tr, const float* z_rot, int32_t early_stop_count,
+                           int32_t* state, float* dcom, float* drot, hipStream_t s) {
+    ADF_TRY(m.check(m.h, b));
+    if (!pos || !tags || !f1 || !f2 || (!coef && !coefs_dev) || !state) { adf_set_error("null argument"); return ADF_EINVAL; }
+    if (!coef && num_steps <= 0) { adf_set_error("num_steps must be positive"); return ADF_EINVAL; }
+    float* sys = nullptr;
+    ADF_TRY(m.grow(m.h, b, &sys));
+    m.prof(m.h, true, s);
+    const int32_t st = adf_stepper_step(sys, b, pos, tags, fixed, f1, f2, coef, coef ? nullptr : coefs_dev, num_steps, z_tr,
+                                        z_rot, early_stop_count, state, dcom, drot, s);
+    m.prof(m.h, false, s);
+    return st;
+}
+
+int32_t adf_model_tr_step(const adf_model& m, const adf_batch* b, float* pos, const int32_t* tags, const float* f1,
+                          const adf_tr_coef* coef, const adf_tr_coef* coefs_dev, int32_t num_steps, const float* z,
+                          int32_t early_stop_count, int32_t* state, float* dcom, hipStream_t s) {
+    ADF_TRY(m.check(m.h, b));
+    if (!pos || !tags || !f1 || (!coef && !coefs_dev) || !state) { adf_set_error("tr_step: null argument"); return ADF_EINVAL; }
+    if (!coef && num_steps <= 0) { adf_set_error("tr_step: num_steps must be positive"); return ADF_EINVAL; }
+    float* sys = nullptr;
+    ADF_TRY(m.grow(m.h, b, &sys));
+    m.prof(m.h, true, s);
+    const int32_t st = adf_stepper_tr_step(sys, b, pos, tags, f1, coef, coefs_dev, num_steps, z, early_stop_count, state,
+                                           dcom, s);
+    m.prof(m.h, false, s);
+    return st;
+}
+
+// The whole reverse loop of every sampler on either model (denoising_torch.py:235-356, :96-196, :369-458) in one call:
+// num_steps x (forward + step), all on `s`.  `step(z)` is the sampler's step on its noise tables' slices at offset z.
+// Host round trips: with poll_every > 0 the frozen flag is read back every poll_every steps and the loop ends early,
+// exactly like the reference's `break`.
+template <class Step>
+static int32_t sample_loop(const adf_model& m, const adf_batch* b, float* pos, const int32_t* tags, const void* coefs_dev,
+                           int32_t num_steps, int32_t early_stop_count, int32_t poll_every, int32_t* state,
+                           const int32_t* out_idx, int32_t n_out, float* f1, float* f2, adf_frames* sink,
+                           int32_t frame_every, hipStream_t s, Step step) {
+    ADF_TRY(m.check(m.h, b));
+    if (num_steps <= 0 || !f1 || !state || !coefs_dev || !pos || !tags || (out_idx && n_out < 0)) {
+        adf_set_error("sample: bad argument");
+        return ADF_EINVAL;
+    }
+    if (sink && frame_every <= 0) { adf_set_error("sample: frame_every must be positive"); return ADF_EINVAL; }
+    for (int t = 0; t < num_steps; ++t) {
+        ADF_TRY(m.forward(m.h, b, out_idx, n_out, f1, f2, s));
+        ADF_TRY(step((size_t)t * b->num_systems * 3));
+        // trajectory frame of this step: snapshot on this stream, copy-out on the sink's stream (frames.hip)
+        if (sink && ((t + 1) % frame_every == 0 || t + 1 == num_steps)) ADF_TRY(adf_frames_push_impl(sink, pos, s));
+        if (early_stop_count > 0 && poll_every > 0 && (t % poll_every) == poll_every - 1 && t + 1 < num_steps) {
+            int32_t frozen = 0;
+            ADF_HIP_CHECK(hipMemcpyAsync(&frozen, state + 1, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+            ADF_HIP_CHECK(hipStreamSynchronize(s));
+            if (frozen) break;
+        }
+    }
+    return ADF_OK;
+}
+
+int32_t adf_model_sample(const adf_model& m, const adf_batch* b, float* pos, const int32_t* tags, const int32_t* fixed,
+                         const adf_step_coef* coefs_dev, int32_t num_steps, const float* z_tr_all, const float* z_rot_all,
+                         int32_t early_stop_count, int32_t poll_every, int32_t* state, const int32_t* out_idx,
+                         int32_t n_out, float* f1, float* f2, adf_frames* sink, int32_t frame_every, hipStream_t s) {
+    if (!f2) { adf_set_error("sample: f2 is null"); return ADF_EINVAL; }
+    if ((z_tr_all == nullptr) != (z_rot_all == nullptr)) { adf_set_error("sample: need both noise tables or none"); return ADF_EINVAL; }
+    return sample_loop(m, b, pos, tags, coefs_dev, num_steps, early_stop_count, poll_every, state, out_idx, n_out, f1, f2,
+                       sink, frame_every, s, [&](size_t z) {
+                           return adf_model_sde_step(m, b, pos, tags, fixed, f1, f2, nullptr, coefs_dev, num_steps,
+                                                     z_tr_all ? z_tr_all + z : nullptr, z_rot_all ? z_rot_all + z : nullptr,
+                                                     early_stop_count, state, nullptr, nullptr, s);
+                       });
+}
+
+int32_t adf_model_tr_sample(const adf_model& m, const adf_batch* b, float* pos, const int32_t* tags,
+                            const adf_tr_coef* coefs_dev, int32_t num_steps, const float* z_all, int32_t early_stop_count,
+                            int32_t poll_every, int32_t* state, const int32_t* out_idx, int32_t n_out, float* f1,
+                            adf_frames* sink, int32_t frame_every, hipStream_t s) {
+    return sample_loop(m, b, pos, tags, coefs_dev, num_steps, early_stop_count, poll_every, state, out_idx, n_out, f1,
+                       nullptr, sink, frame_every, s, [&](size_t z) {
+                           return adf_model_tr_step(m, b, pos, tags, f1, nullptr, coefs_dev, num_steps,
+                                                    z_all ? z_all + z : nullptr, early_stop_count, state, nullptr, s);
+                       });
+}
+
 // Hand-off rule of the reference's final-frame -> LMDB converter (scripts/create_lmdbs/pred_traj_to_lmdb.py:81-90): if the
 // lowest adsorbate atom (tag 2) is less than `min_gap` above the highest surface atom (tag 1), the whole adsorbate is
 // lifted by |diff| + min_gap.  One wave per system, in place; lifted[b] (optional) = applied shift.

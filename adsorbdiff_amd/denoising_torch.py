@@ -211,125 +211,46 @@ class Denoiser:
         params = self.denoising_pos_params
         if "ads_std_low" not in params:
             return
-        trainer = self.model.model
-        dev = torch.device(self.device)
-        # what predict_denoising does around every model call in the reference
-        # (sde_denoising_trainer.py:577-580,638-639), done once around the loop here
-        trainer._unwrapped_model.eval()
-        ema = getattr(trainer, "ema", None)
-        if ema:
-            ema.store()
-            ema.copy_to()
-        try:
-            eng = self._engine()
-            batch = self.batch.to(dev)  # in place, like the reference's batch.to(self.device)
-            if batch.pos.dtype != torch.float32 or not batch.pos.is_contiguous():
-                batch.pos = batch.pos.to(torch.float32).contiguous()
-            pos = batch.pos
-            prep = eng.prepare(batch)
-            if prep.tags is None:
-                raise ValueError("batch.tags is required (tag 2 marks the adsorbate)")
-            if hasattr(eng, "bind_condition"):  # conditional EquiformerV2: batch.energy, once for the whole loop
-                eng.bind_condition(batch, prep.num_systems)
-            B, N = prep.num_systems, prep.num_atoms
-            T = int(params["num_steps"])
-            ode = params.get("ode", True)
-            coefs = schedule_coefs(params)
-            early = 10 if params.get("early_stop", True) else 0
+        T = int(params["num_steps"])
+        ode = params.get("ode", True)
+        coefs = schedule_coefs(params)
+        early = 10 if params.get("early_stop", True) else 0
+        use_graph = bool(params.get("use_graph", False))
 
-            # initial placement: uniform noise from the CPU global generator (reference :215)
-            noise = params.get("placement_noise")
-            if noise is None:
-                noise = torch.rand(B, 3)
-            else:  # extension: caller-supplied uniforms (sharded runs key them by global system id)
-                noise = torch.as_tensor(noise, dtype=torch.float32).reshape(B, 3).cpu()
-            eng.init_placement(prep, pos, noise.to(dev))
-            # from here on only the adsorbate (tag 2) moves: the graph builder may cache the slab-slab part and the
-            # forward the layer-0 records (loop-invariant; results are bit-identical either way)
-            if params.get("static_atom_cache", True):
-                eng.set_moving_atoms(prep, prep.tags == 2)
-            # (a captured step replays fixed buffers: the previous-graph / current-graph swap the comparison rests on, and
-            # the late read-back of the list lengths that picks between the list and the all-rows form, do not replay)
-            eng.set_incremental(bool(params.get("incremental_layers", True)) and not params.get("use_graph", False))
+        def begin(eng, prep, pos):
+            B, N, dev = prep.num_systems, prep.num_atoms, pos.device
+            # schedule table on the device: every step is then the same launch sequence and can be replayed
+            # from one captured hipGraph (`use_graph`, opt-in: measured no gain on MI355X at B=1 — the step is
+            # bound by the dependent chain of ~140 small kernels on the device, not by launch overhead)
+            coefs_dev = torch.tensor(
+                [[c.coef_tr, c.rot_pre, c.rot_dt, c.rot_g2, c.noise_tr, c.noise_rot] for c in coefs],
+                dtype=torch.float32, device=dev)
 
-            pos0 = pos.clone()  # a run that leaves the f16x3 range is repeated in exact f32 from here
-
-            def attempt():
-                f1 = torch.zeros(N, 3, dtype=torch.float32, device=dev)
+            def fused(f1, state, out_idx, poll_every, sink):
                 f2 = torch.zeros(N, 3, dtype=torch.float32, device=dev)
-                out_idx = None
-                state = torch.tensor([0, 0, 1, 0, 0, 0, 0, 0], dtype=torch.int32, device=dev)
-                frames = [] if self.traj_dir else None
-                sink = writer = None
-                check_every = 1 if B <= 8 else 5
-                z_tr = z_rot = None
+                zt = zr = None
+                if not ode:  # device generator, drawn in the reference's order (:274-289): z_tr then z_rot, per step
+                    zt = torch.empty(T, B, 3, dtype=torch.float32, device=dev)
+                    zr = torch.empty(T, B, 3, dtype=torch.float32, device=dev)
+                    for t_idx in range(T):
+                        zt[t_idx].normal_()
+                        zr[t_idx].normal_()
+                eng.sample(prep, pos, f1, f2, coefs_dev, T, state, zt, zr, early_stop_count=early, poll_every=poll_every,
+                           out_idx=out_idx, sink=sink, frame_every=1)
+
+            def per_step(f1, state, out_idx):
+                f2 = torch.zeros(N, 3, dtype=torch.float32, device=dev)
+                z_tr = z_rot = graph = None
                 if not ode:
                     z_tr = torch.empty(B, 3, dtype=torch.float32, device=dev)
                     z_rot = torch.empty(B, 3, dtype=torch.float32, device=dev)
-                # schedule table on the device: every step is then the same launch sequence and can be replayed
-                # from one captured hipGraph (`use_graph`, opt-in: measured no gain on MI355X at B=1 — the step is
-                # bound by the dependent chain of ~140 small kernels on the device, not by launch overhead)
-                coefs_dev = torch.tensor(
-                    [[c.coef_tr, c.rot_pre, c.rot_dt, c.rot_g2, c.noise_tr, c.noise_rot] for c in coefs],
-                    dtype=torch.float32, device=dev)
-                use_graph = bool(params.get("use_graph", False))
-                graph = None
 
                 def one_step():
                     eng.forward_prepared(prep, pos, f1, f2, out_idx)
                     eng.sde_step_scheduled(prep, pos, f1, f2, coefs_dev, T, state, z_tr, z_rot, early_stop_count=early)
 
-                # Nothing to hand to the host between steps (no per-step frames, no host noise hook, no graph replay):
-                # the whole loop is one library call (adf_sample), polling the early-stop flag every `check_every` steps.
-                step_hook = params.get("step_hook")  # extension: callable(t) after every applied step (diagnostics)
-                fused_loop = (not use_graph) and self.noise_fn is None and step_hook is None
-                ads_only = params.get("scores_on_adsorbate_only")
-                if ads_only is None:
-                    ads_only = fused_loop   # unobservable there: no per-atom output leaves adf_sample
-                if ads_only:
-                    out_idx = torch.nonzero(prep.tags == 2).reshape(-1).to(torch.int32).contiguous()
-                if fused_loop and frames is not None:
-                    # trajectory frames leave the device from inside the fused loop (csrc/frames.hip) and a host thread
-                    # writes them while the next steps compute (trajectory.py); frames = None: nothing is kept here
-                    from .trajectory import FrameSink, TrajectoryWriter
-
-                    frames = None
-                    sink = FrameSink(dev.index if dev.index is not None else torch.cuda.current_device(), N,
-                                     slots=int(params.get("trajectory_ring_slots", 8)))
-                    writer = TrajectoryWriter(sink, self.traj_dir, self._traj_meta(batch), T if self.save_full else 1)
-                    writer.start()
-                if fused_loop:
-                    zt = zr = None
-                    if not ode:  # device generator, drawn in the reference's order (:274-289): z_tr then z_rot, per step
-                        zt = torch.empty(T, B, 3, dtype=torch.float32, device=dev)
-                        zr = torch.empty(T, B, 3, dtype=torch.float32, device=dev)
-                        for t_idx in range(T):
-                            zt[t_idx].normal_()
-                            zr[t_idx].normal_()
-                    try:
-                        eng.sample(prep, pos, f1, f2, coefs_dev, T, state, zt, zr, early_stop_count=early,
-                                   poll_every=check_every if early else 0, out_idx=out_idx,
-                                   sink=sink if (sink is not None and self.save_full) else None, frame_every=1)
-                        if sink is not None and not self.save_full:   # final frame only (reference :474-477 with save_full False)
-                            with torch.cuda.device(dev):
-                                _lib.check(eng.lib.adf_frames_push(sink.handle, pos.data_ptr(), eng._stream()))
-                        eng.check_flags()
-                    except BaseException:
-                        if writer is not None:   # a failed attempt (e.g. the f16x3 range was left): drop its frames,
-                            writer.abort()       # publish no file (temporary files deleted), wake a blocked push
-                            sink.abort()
-                            writer.join()
-                            sink.close()
-                            if writer.error is not None:
-                                # the writer died first (disk full, ...): the push error ('ring was aborted') is only
-                                # its echo - surface the real cause
-                                raise writer.error
-                        raise
-                    if writer is not None:
-                        applied = int(state[3].item())
-                        writer.finish(max(applied, 1) if self.save_full else 1)
-                        self._pending = (writer, sink)
-                for t_idx in range(0 if fused_loop else T):  # per-step path
+                def step(t_idx):
+                    nonlocal graph
                     if not ode:
                         if self.noise_fn is not None:
                             a, b_ = self.noise_fn(t_idx, B)
@@ -340,56 +261,28 @@ class Denoiser:
                             z_rot.normal_()
                     if graph is not None:
                         graph.replay()
-                    else:
-                        one_step()
-                        if use_graph and t_idx == 0 and T > 2:
-                            # step 0 ran eagerly (workspaces are now allocated); capture the identical step once
-                            torch.cuda.synchronize(dev)
-                            graph = torch.cuda.CUDAGraph()
-                            snapshot = (pos.clone(), state.clone())
-                            with torch.cuda.graph(graph):
-                                one_step()
-                            # the capture itself does not execute; restore nothing, but make sure state is intact
-                            assert torch.equal(state, snapshot[1])
-                    if frames is not None and (self.save_full or t_idx == T - 1):
-                        frames.append(pos.clone())
-                    if step_hook is not None:
-                        step_hook(t_idx)
-                    if early and (t_idx % check_every == check_every - 1):
-                        if int(state[1].item()):
-                            break
-                if frames is not None and not frames:
-                    frames.append(pos.clone())
-                eng.check_flags()
-                return state, frames
+                        return
+                    one_step()
+                    if use_graph and t_idx == 0 and T > 2:
+                        # step 0 ran eagerly (workspaces are now allocated); capture the identical step once
+                        torch.cuda.synchronize(dev)
+                        graph = torch.cuda.CUDAGraph()
+                        snapshot = (pos.clone(), state.clone())
+                        with torch.cuda.graph(graph):
+                            one_step()
+                        # the capture itself does not execute; restore nothing, but make sure state is intact
+                        assert torch.equal(state, snapshot[1])
 
-            frames = None
-            try:
-                state, frames = attempt()
-            except _lib.NumericRangeError:
-                if not eng.use_exact_f32():
-                    raise
-                pos.copy_(pos0)
-                state, frames = attempt()
-            st = state.tolist()
-            self.steps_applied = st[3]
-            self.cvg_count = st[0]
-            if frames is not None:
-                # frames recorded after the break are identical copies; keep the applied ones
-                frames = frames[: max(self.steps_applied, 1)] if self.save_full else frames[-1:]
-                self._write_trajectories(batch, frames)
-            if getattr(self, "_pending", None) is not None and not params.get("trajectory_async", False):
-                self.wait_for_trajectories()   # like the reference: the files exist when run() returns
-            B_ = B
-            batch.y = torch.zeros(B_, device=dev)
-            batch.force = torch.zeros(N, 3, device=dev)
-        finally:
-            try:
-                self._engine().set_moving_atoms(None, None)
-            except Exception:
-                pass
-            if ema:
-                ema.restore()
+                return step
+
+            return fused, per_step
+
+        # The fused loop needs nothing handed to the host between steps: no host noise hook, no graph replay, no step
+        # hook.  A captured step replays fixed buffers: the previous-graph / current-graph swap the incremental layers'
+        # comparison rests on, and the late read-back of the list lengths that picks between the list and the all-rows
+        # form, do not replay.
+        self._sample(T, early, begin, fused=not use_graph and self.noise_fn is None and params.get("step_hook") is None,
+                     incremental=not use_graph)
 
     # ------------------------------------------------------------------ translation-only samplers
     def reverse_sde_sampling(self):
@@ -416,29 +309,13 @@ class Denoiser:
         self._tr_sampling(coefs, True, params.get("langevin_noise"), 0)
 
     def _tr_sampling(self, coefs, langevin: bool, noise_table, early: int) -> None:
-        """Shared frame of the translation-only samplers (the frame of ``reverse_sde_sampling_rot``: eval + EMA, initial
-        placement, static-atom cache, fused loop or per-step path, exact-f32 retry, trajectories)."""
-        params = self.denoising_pos_params
-        trainer = self.model.model
-        dev = torch.device(self.device)
-        trainer._unwrapped_model.eval()
-        ema = getattr(trainer, "ema", None)
-        if ema:
-            ema.store()
-            ema.copy_to()
-        try:
-            eng = self._engine()
-            batch = self.batch.to(dev)
-            if batch.pos.dtype != torch.float32 or not batch.pos.is_contiguous():
-                batch.pos = batch.pos.to(torch.float32).contiguous()
-            pos = batch.pos
-            prep = eng.prepare(batch)
-            if prep.tags is None:
-                raise ValueError("batch.tags is required (tag 2 marks the adsorbate)")
-            if hasattr(eng, "bind_condition"):
-                eng.bind_condition(batch, prep.num_systems)
-            B, N = prep.num_systems, prep.num_atoms
-            T = len(coefs)
+        """The translation-only samplers' parts of ``_sample``: the fused loop evaluates head 1 only, the per-step path
+        the full forward (both heads of a two-head model) and then the same step kernels.  Langevin's noise table is
+        drawn once, before the placement: an exact-f32 retry reuses it."""
+        T = len(coefs)
+
+        def begin(eng, prep, pos):
+            B, N, dev = prep.num_systems, prep.num_atoms, pos.device
             z_all = None
             if langevin:
                 if noise_table is None:  # device generator, one randn_like([B,3]) per inner step (reference :417)
@@ -450,71 +327,93 @@ class Denoiser:
                     if tuple(z_all.shape) != (T, B, 3):
                         raise ValueError(f"langevin_noise has shape {tuple(z_all.shape)}, expected {(T, B, 3)}")
                     z_all = z_all.to(dev).contiguous()
+            coefs_dev = torch.tensor([[c.coef, c.noise] for c in coefs], dtype=torch.float32, device=dev)
+
+            def fused(f1, state, out_idx, poll_every, sink):
+                eng.tr_sample(prep, pos, f1, coefs_dev, T, state, z_all, early_stop_count=early, poll_every=poll_every,
+                              out_idx=out_idx, sink=sink, frame_every=1)
+
+            def per_step(f1, state, out_idx):
+                f2 = torch.zeros(N, 3, dtype=torch.float32, device=dev) if eng.num_heads == 2 else None
+
+                def step(t_idx):
+                    eng.forward_prepared(prep, pos, f1, f2, out_idx)
+                    eng.tr_step(prep, pos, f1, state, coefs_dev=coefs_dev, num_steps=T,
+                                z=z_all[t_idx] if z_all is not None else None, early_stop_count=early)
+
+                return step
+
+            return fused, per_step
+
+        self._sample(T, early, begin, fused=self.denoising_pos_params.get("step_hook") is None, incremental=True)
+
+    # ------------------------------------------------------------------ the frame of every sampler
+    def _sample(self, T: int, early: int, begin, fused: bool, incremental: bool) -> None:
+        """Eval mode and the EMA weights, the batch on the device, the initial placement, the static-atom cache, one
+        attempt of ``T`` steps - repeated in exact f32 from the placed positions if it left the f16x3 range - and the
+        trajectories.  The sampler's parts come from ``begin(eng, prep, pos)``, called before the placement:
+        ``fused(f1, state, out_idx, poll_every, sink)`` runs its whole loop in one library call (taken when ``fused``),
+        ``per_step(f1, state, out_idx)`` returns the host-driven ``step(t)``.  ``incremental``: the sampler allows the
+        incremental layers."""
+        params = self.denoising_pos_params
+        trainer = self.model.model
+        dev = torch.device(self.device)
+        # what predict_denoising does around every model call in the reference
+        # (sde_denoising_trainer.py:577-580,638-639), done once around the loop here
+        trainer._unwrapped_model.eval()
+        ema = getattr(trainer, "ema", None)
+        if ema:
+            ema.store()
+            ema.copy_to()
+        try:
+            eng = self._engine()
+            batch = self.batch.to(dev)  # in place, like the reference's batch.to(self.device)
+            if batch.pos.dtype != torch.float32 or not batch.pos.is_contiguous():
+                batch.pos = batch.pos.to(torch.float32).contiguous()
+            pos = batch.pos
+            prep = eng.prepare(batch)
+            if prep.tags is None:
+                raise ValueError("batch.tags is required (tag 2 marks the adsorbate)")
+            eng.bind_condition(batch, prep.num_systems)  # conditional EquiformerV2: batch.energy, once for the whole loop
+            B, N = prep.num_systems, prep.num_atoms
+            fused_run, per_step = begin(eng, prep, pos)
+
+            # initial placement: uniform noise from the CPU global generator (reference :215)
             noise = params.get("placement_noise")
             if noise is None:
                 noise = torch.rand(B, 3)
-            else:
+            else:  # extension: caller-supplied uniforms (sharded runs key them by global system id)
                 noise = torch.as_tensor(noise, dtype=torch.float32).reshape(B, 3).cpu()
             eng.init_placement(prep, pos, noise.to(dev))
+            # from here on only the adsorbate (tag 2) moves: the graph builder may cache the slab-slab part and the
+            # forward the layer-0 records (loop-invariant; results are bit-identical either way)
             if params.get("static_atom_cache", True):
                 eng.set_moving_atoms(prep, prep.tags == 2)
-            eng.set_incremental(bool(params.get("incremental_layers", True)))
-            coefs_dev = torch.tensor([[c.coef, c.noise] for c in coefs], dtype=torch.float32, device=dev)
-            two_heads = getattr(eng, "num_heads", 2) == 2   # EquiformerV2: always both force blocks
-            pos0 = pos.clone()
+            eng.set_incremental(bool(params.get("incremental_layers", True)) and incremental)
+
+            step_hook = params.get("step_hook")  # extension: callable(t) after every applied step (diagnostics)
+            check_every = 1 if B <= 8 else 5
+            ads_only = params.get("scores_on_adsorbate_only")
+            if ads_only is None:
+                ads_only = fused   # unobservable there: no per-atom output leaves the library
+            pos0 = pos.clone()  # a run that leaves the f16x3 range is repeated in exact f32 from here
 
             def attempt():
                 f1 = torch.zeros(N, 3, dtype=torch.float32, device=dev)
                 state = torch.tensor([0, 0, 1, 0, 0, 0, 0, 0], dtype=torch.int32, device=dev)
-                frames = [] if self.traj_dir else None
-                sink = writer = None
-                check_every = 1 if B <= 8 else 5
-                step_hook = params.get("step_hook")   # callable(t) after every step: per-step path
-                fused_loop = step_hook is None
-                ads_only = params.get("scores_on_adsorbate_only")
-                if ads_only is None:
-                    ads_only = fused_loop
                 out_idx = torch.nonzero(prep.tags == 2).reshape(-1).to(torch.int32).contiguous() if ads_only else None
-                if fused_loop:
-                    if frames is not None:
-                        from .trajectory import FrameSink, TrajectoryWriter
-
-                        frames = None
-                        sink = FrameSink(dev.index if dev.index is not None else torch.cuda.current_device(), N,
-                                         slots=int(params.get("trajectory_ring_slots", 8)))
-                        writer = TrajectoryWriter(sink, self.traj_dir, self._traj_meta(batch), T if self.save_full else 1)
-                        writer.start()
-                    try:
-                        eng.tr_sample(prep, pos, f1, coefs_dev, T, state, z_all, early_stop_count=early,
-                                      poll_every=check_every if early else 0, out_idx=out_idx,
-                                      sink=sink if (sink is not None and self.save_full) else None, frame_every=1)
-                        if sink is not None and not self.save_full:
-                            with torch.cuda.device(dev):
-                                _lib.check(eng.lib.adf_frames_push(sink.handle, pos.data_ptr(), eng._stream()))
-                        eng.check_flags()
-                    except BaseException:
-                        if writer is not None:
-                            writer.abort()
-                            sink.abort()
-                            writer.join()
-                            sink.close()
-                            if writer.error is not None:
-                                raise writer.error
-                        raise
-                    if writer is not None:
-                        applied = int(state[3].item())
-                        writer.finish(max(applied, 1) if self.save_full else 1)
-                        self._pending = (writer, sink)
-                    return state, frames
-                # per-step path: the full forward (both heads of a two-head model), then the same step kernels
-                f2 = torch.zeros(N, 3, dtype=torch.float32, device=dev) if two_heads else None
+                if fused:
+                    self._run_fused(eng, batch, pos, state, T,
+                                    lambda sink: fused_run(f1, state, out_idx, check_every if early else 0, sink))
+                    return state, None
+                frames = [] if self.traj_dir else None
+                step = per_step(f1, state, out_idx)
                 for t_idx in range(T):
-                    eng.forward_prepared(prep, pos, f1, f2, out_idx)
-                    eng.tr_step(prep, pos, f1, state, coefs_dev=coefs_dev, num_steps=T,
-                                z=z_all[t_idx] if z_all is not None else None, early_stop_count=early)
+                    step(t_idx)
                     if frames is not None and (self.save_full or t_idx == T - 1):
                         frames.append(pos.clone())
-                    step_hook(t_idx)
+                    if step_hook is not None:
+                        step_hook(t_idx)
                     if early and (t_idx % check_every == check_every - 1):
                         if int(state[1].item()):
                             break
@@ -534,10 +433,11 @@ class Denoiser:
             self.steps_applied = st[3]
             self.cvg_count = st[0]
             if frames is not None:
+                # frames recorded after the break are identical copies; keep the applied ones
                 frames = frames[: max(self.steps_applied, 1)] if self.save_full else frames[-1:]
                 self._write_trajectories(batch, frames)
-            if getattr(self, "_pending", None) is not None and not params.get("trajectory_async", False):
-                self.wait_for_trajectories()
+            if self._pending is not None and not params.get("trajectory_async", False):
+                self.wait_for_trajectories()   # like the reference: the files exist when run() returns
             batch.y = torch.zeros(B, device=dev)
             batch.force = torch.zeros(N, 3, device=dev)
         finally:
@@ -547,6 +447,38 @@ class Denoiser:
                 pass
             if ema:
                 ema.restore()
+
+    def _run_fused(self, eng, batch, pos, state, T: int, run) -> None:
+        """``run(sink)``: a sampler's whole loop in one library call.  With a ``traj_dir`` the trajectory frames leave the
+        device from inside that loop (csrc/frames.hip) and a host thread writes them while the next steps compute
+        (trajectory.py)."""
+        sink = writer = None
+        if self.traj_dir:
+            from .trajectory import FrameSink, TrajectoryWriter
+
+            sink = FrameSink(pos.device.index, pos.shape[0],
+                             slots=int(self.denoising_pos_params.get("trajectory_ring_slots", 8)))
+            writer = TrajectoryWriter(sink, self.traj_dir, self._traj_meta(batch), T if self.save_full else 1)
+            writer.start()
+        try:
+            run(sink if self.save_full else None)
+            if sink is not None and not self.save_full:   # final frame only (reference :474-477 with save_full False)
+                sink.push(pos, torch.cuda.current_stream(pos.device))
+            eng.check_flags()
+        except BaseException:
+            if writer is not None:   # a failed attempt (e.g. the f16x3 range was left): drop its frames,
+                writer.abort()       # publish no file (temporary files deleted), wake a blocked push
+                sink.abort()
+                writer.join()
+                sink.close()
+                if writer.error is not None:
+                    # the writer died first (disk full, ...): the push error ('ring was aborted') is only
+                    # its echo - surface the real cause
+                    raise writer.error
+            raise
+        if writer is not None:
+            writer.finish(max(int(state[3].item()), 1) if self.save_full else 1)
+            self._pending = (writer, sink)
 
     # ------------------------------------------------------------------ trajectory sink
     _pending = None

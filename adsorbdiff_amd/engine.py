@@ -1,6 +1,6 @@
-"""Device-side engine of the PaiNN denoiser: owns the C-ABI handle, binds the module's
-parameters, converts a (PyG-like) batch into the ``adf_batch`` descriptor and enqueues
-forward / stepper calls on torch's current HIP stream.
+"""Device-side engines of the score models: ``Engine`` converts a (PyG-like) batch into the ``adf_batch``
+descriptor and enqueues the stepper and sampling-loop calls of either model on torch's current HIP stream;
+``PaiNNEngine`` owns the PaiNN C-ABI handle, binds the module's parameters and runs its forward.
 
 PyTorch is plumbing here (device memory, streams); all arithmetic is in
 libadsorbdiff_hip.so.  Nothing in this file computes a model output on the host.
@@ -8,6 +8,8 @@ libadsorbdiff_hip.so.  Nothing in this file computes a model output on the host.
 from __future__ import annotations
 
 import ctypes as C
+import logging
+import os
 from dataclasses import dataclass
 from typing import List, Optional, Sequence
 
@@ -87,13 +89,193 @@ def _require_gpu(t: torch.Tensor, what: str) -> None:
         )
 
 
-class PaiNNEngine:
+def _ptr(t: Optional[torch.Tensor]):
+    return t.data_ptr() if t is not None else None
+
+
+def _numel(t: Optional[torch.Tensor]) -> int:
+    return int(t.numel()) if t is not None else 0
+
+
+class Engine:
+    """What both score models' engines share: the stepper entries, the fused sampling loops, the static-atom promise,
+    the flags and arithmetic switches and the handle's lifetime.  A subclass creates the handle, binds the weights,
+    runs the forward and names its C entries in ``SYMBOLS`` (role -> symbol)."""
+
+    SYMBOLS: dict = {}
+
     def __init__(self, model, device) -> None:
         self.lib = _lib.load()
         self.device = torch.device(device)
         if self.device.type != "cuda":
-            raise RuntimeError(f"PaiNNEngine needs a ROCm device, got {self.device} (no CPU fallback)")
+            raise RuntimeError(f"{type(self).__name__} needs a ROCm device, got {self.device} (no CPU fallback)")
         self.model = model
+        self.exact_f32 = os.environ.get("ADF_GEMM") == "f32"
+        self._weights_keepalive: List[torch.Tensor] = []
+        self._moving_keepalive = None
+
+    def _c(self, role: str):
+        return getattr(self.lib, self.SYMBOLS[role])
+
+    def _stream(self) -> C.c_void_p:
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    # ------------------------------------------------------------------ batches
+    def prepare(self, data) -> PreparedBatch:
+        _require_gpu(data.pos, "data.pos")
+        dev = self.device
+        natoms = data.natoms.to(dev, torch.int64).reshape(-1)
+        B = int(natoms.shape[0])
+        N = int(data.pos.shape[0])
+        off = torch.zeros(B + 1, dtype=torch.int32, device=dev)
+        off[1:] = torch.cumsum(natoms, 0).to(torch.int32)
+        cell = data.cell.to(dev, torch.float32).reshape(B, 3, 3).contiguous()
+        reps = cell_repeats(cell, float(self.model.cutoff), batch_pbc(data))
+        prep = PreparedBatch(
+            num_systems=B, num_atoms=N, cell=cell,
+            atomic_numbers=data.atomic_numbers.to(dev).long().to(torch.int32).contiguous(),
+            batch=data.batch.to(dev, torch.int32).contiguous(),
+            atom_offset=off, reps=reps,
+        )
+        if hasattr(data, "tags") and data.tags is not None:
+            prep.tags = data.tags.to(dev, torch.int32).contiguous()
+        if hasattr(data, "fixed") and data.fixed is not None:
+            prep.fixed = data.fixed.to(dev, torch.int32).contiguous()
+        return prep
+
+    def bind_condition(self, data, num_systems: int) -> None:
+        """What a conditional model reads from the batch besides the atoms; nothing for the others."""
+
+    def set_moving_atoms(self, prep: Optional[PreparedBatch], moving_mask: Optional[torch.Tensor]) -> None:
+        """Declare which atoms may move between the next graph builds of ``prep`` (None switches the
+        static-atom cache off).  The arrays are kept alive on the engine until the next call."""
+        if moving_mask is None or prep is None:
+            self._moving_keepalive = None
+            _lib.check(self._c("set_moving")(self.handle, None, None, None))
+            return
+        mask = moving_mask.to(self.device, torch.int32).contiguous()
+        idx = torch.nonzero(mask).reshape(-1).to(torch.int32).contiguous()
+        per_sys = torch.bincount(prep.batch[idx.long()].long(), minlength=prep.num_systems)
+        off = torch.zeros(prep.num_systems + 1, dtype=torch.int32, device=self.device)
+        off[1:] = torch.cumsum(per_sys, 0).to(torch.int32)
+        self._moving_keepalive = (mask, idx, off)
+        _lib.check(self._c("set_moving")(self.handle, mask.data_ptr(), idx.data_ptr(), off.data_ptr()))
+
+    # ------------------------------------------------------------------ switches
+    def check_flags(self) -> None:
+        with torch.cuda.device(self.device):
+            _lib.check(self._c("check_flags")(self.handle, self._stream()))
+
+    def use_exact_f32(self) -> bool:
+        """Switch the handle to exact-f32 arithmetic (after a NumericRangeError in the default f16x3 mode: an
+        activation left the fp16 range).  Returns False if it already was exact."""
+        if self.exact_f32:
+            return False
+        logging.warning("adsorbdiff_amd: non-finite output in f16x3 arithmetic; re-running in exact f32 "
+                        "(this engine stays in exact f32)")
+        _lib.check(self._c("set_arithmetic")(self.handle, 1))
+        self.exact_f32 = True
+        return True
+
+    def set_incremental(self, on: bool = True) -> None:
+        """Incremental layers / blocks: keep the node state of every layer across the forwards of a static-atom
+        promise and recompute only rows whose inputs changed.  Bit-identical outputs."""
+        _lib.check(self._c("set_incremental")(self.handle, 1 if on else 0))
+
+    # ------------------------------------------------------------------ stepper
+    def init_placement(self, prep: PreparedBatch, pos: torch.Tensor, noise: torch.Tensor) -> None:
+        desc = prep.desc(pos)
+        with torch.cuda.device(self.device):
+            _lib.check(self._c("init_placement")(
+                self.handle, C.byref(desc), pos.data_ptr(), prep.tags.data_ptr(), noise.data_ptr(), self._stream()))
+
+    def sde_step(self, prep: PreparedBatch, pos, f1, f2, coef: _lib.StepCoef, state, z_tr=None, z_rot=None,
+                 early_stop_count: int = 10, dcom=None, drot=None) -> None:
+        self._sde_step(prep, pos, f1, f2, coef, None, 0, state, z_tr, z_rot, early_stop_count, dcom, drot)
+
+    def sde_step_scheduled(self, prep: PreparedBatch, pos, f1, f2, coefs_dev: torch.Tensor, num_steps: int, state,
+                           z_tr=None, z_rot=None, early_stop_count: int = 10) -> None:
+        """Step whose schedule scalars come from a device table indexed by state[4] (graph-capturable)."""
+        self._sde_step(prep, pos, f1, f2, None, coefs_dev, num_steps, state, z_tr, z_rot, early_stop_count, None, None)
+
+    def _sde_entry(self, coef, coefs_dev, num_steps):
+        """The step entry and its schedule arguments: one entry that takes either form."""
+        return self._c("sde_step"), (C.byref(coef) if coef is not None else None, _ptr(coefs_dev), num_steps)
+
+    def _sde_step(self, prep, pos, f1, f2, coef, coefs_dev, num_steps, state, z_tr, z_rot, early_stop_count, dcom, drot):
+        desc = prep.desc(pos)
+        entry, schedule = self._sde_entry(coef, coefs_dev, num_steps)
+        with torch.cuda.device(self.device):
+            _lib.check(entry(self.handle, C.byref(desc), pos.data_ptr(), prep.tags.data_ptr(), _ptr(prep.fixed),
+                             f1.data_ptr(), f2.data_ptr(), *schedule, _ptr(z_tr), _ptr(z_rot), early_stop_count,
+                             state.data_ptr(), _ptr(dcom), _ptr(drot), self._stream()))
+
+    def sample(self, prep: PreparedBatch, pos, f1, f2, coefs_dev: torch.Tensor, num_steps: int, state,
+               z_tr_all=None, z_rot_all=None, early_stop_count: int = 10, poll_every: int = 0,
+               out_idx: Optional[torch.Tensor] = None, sink=None, frame_every: int = 1) -> None:
+        """The whole reverse loop in one library call (``adf_sample``; with ``sink`` — a ``trajectory.FrameSink`` —
+        ``adf_sample_traj``: a frame of the positions leaves the device after every ``frame_every``-th step)."""
+        self._loop("sample", prep, pos, [_ptr(prep.fixed), coefs_dev.data_ptr(), num_steps, _ptr(z_tr_all),
+                                         _ptr(z_rot_all), early_stop_count, poll_every, state.data_ptr(), _ptr(out_idx),
+                                         _numel(out_idx), f1.data_ptr(), f2.data_ptr()], sink, frame_every)
+
+    def tr_step(self, prep: PreparedBatch, pos, f1, state, coef: Optional[_lib.TrCoef] = None,
+                coefs_dev: Optional[torch.Tensor] = None, num_steps: int = 0, z=None, early_stop_count: int = 10,
+                dcom=None) -> None:
+        """One step of the translation-only samplers (``adf_tr_step``): head-1 mean over the adsorbate, dcom =
+        coef * score (+ noise * z), COM wrap, pos += dcom.  Scalars from ``coef`` or from the device table
+        ``coefs_dev`` [num_steps, 2] indexed by state[4]."""
+        desc = prep.desc(pos)
+        with torch.cuda.device(self.device):
+            _lib.check(self._c("tr_step")(
+                self.handle, C.byref(desc), pos.data_ptr(), prep.tags.data_ptr(), f1.data_ptr(),
+                C.byref(coef) if coef is not None else None, _ptr(coefs_dev), int(num_steps), _ptr(z), early_stop_count,
+                state.data_ptr(), _ptr(dcom), self._stream()))
+
+    def tr_sample(self, prep: PreparedBatch, pos, f1, coefs_dev: torch.Tensor, num_steps: int, state, z_all=None,
+                  early_stop_count: int = 10, poll_every: int = 0, out_idx=None, sink=None, frame_every: int = 1) -> None:
+        """The whole translation-only loop in one library call (``adf_tr_sample[_traj]``); the forward inside
+        evaluates head 1 only."""
+        self._loop("tr_sample", prep, pos, [coefs_dev.data_ptr(), int(num_steps), _ptr(z_all), early_stop_count,
+                                            poll_every, state.data_ptr(), _ptr(out_idx), _numel(out_idx), f1.data_ptr()],
+                   sink, frame_every)
+
+    def _loop(self, role: str, prep: PreparedBatch, pos, args: list, sink, frame_every: int) -> None:
+        desc = prep.desc(pos)
+        head = [self.handle, C.byref(desc), pos.data_ptr(), prep.tags.data_ptr()]
+        with torch.cuda.device(self.device):
+            if sink is None:
+                _lib.check(self._c(role)(*head, *args, self._stream()))
+            else:
+                _lib.check(self._c(role + "_traj")(*head, *args, sink.handle, int(frame_every), self._stream()))
+
+    # ------------------------------------------------------------------ lifetime
+    def profile_enable(self, on: bool = True) -> None:
+        _lib.check(self._c("profile_enable")(self.handle, 1 if on else 0))
+
+    def close(self) -> None:
+        if getattr(self, "handle", None) is not None and self.handle:
+            with torch.cuda.device(self.device):
+                torch.cuda.synchronize(self.device)
+                self._c("destroy")(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class PaiNNEngine(Engine):
+    SYMBOLS = dict(set_moving="adf_graph_set_moving", check_flags="adf_check_flags",
+                   set_arithmetic="adf_painn_set_arithmetic", set_incremental="adf_painn_set_incremental",
+                   init_placement="adf_sde_init_placement", sample="adf_sample", sample_traj="adf_sample_traj",
+                   tr_step="adf_tr_step", tr_sample="adf_tr_sample", tr_sample_traj="adf_tr_sample_traj",
+                   profile_enable="adf_profile_enable", destroy="adf_painn_destroy")
+
+    def __init__(self, model, device) -> None:
+        super().__init__(model, device)
         hp = _lib.Hparams(
             hidden_channels=model.hidden_channels, num_layers=model.num_layers, num_rbf=model.num_rbf,
             num_elements=model.num_elements, max_neighbors=model.max_neighbors,
@@ -105,10 +287,6 @@ class PaiNNEngine:
         self.handle = C.c_void_p()
         with torch.cuda.device(self.device):
             _lib.check(self.lib.adf_painn_create(C.byref(hp), C.byref(self.handle)))
-        self._weights_keepalive: List[torch.Tensor] = []
-        import os
-
-        self.exact_f32 = os.environ.get("ADF_GEMM") == "f32"
         self._last_graph_N = 0
         floor = getattr(model, "distance_floor", None)   # the S2EF PaiNN: 1e-6 (painn.py:334-335); default 1e-3
         if floor is not None:
@@ -162,47 +340,6 @@ class PaiNNEngine:
             with torch.cuda.device(self.device):
                 _lib.check(self.lib.adf_painn_set_energy_head(self.handle, 4, eptrs, self._stream()))
 
-    # ------------------------------------------------------------------ batches
-    def _stream(self) -> C.c_void_p:
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def prepare(self, data) -> PreparedBatch:
-        _require_gpu(data.pos, "data.pos")
-        dev = self.device
-        natoms = data.natoms.to(dev, torch.int64).reshape(-1)
-        B = int(natoms.shape[0])
-        N = int(data.pos.shape[0])
-        off = torch.zeros(B + 1, dtype=torch.int32, device=dev)
-        off[1:] = torch.cumsum(natoms, 0).to(torch.int32)
-        cell = data.cell.to(dev, torch.float32).reshape(B, 3, 3).contiguous()
-        reps = cell_repeats(cell, float(self.model.cutoff), batch_pbc(data))
-        prep = PreparedBatch(
-            num_systems=B, num_atoms=N, cell=cell,
-            atomic_numbers=data.atomic_numbers.to(dev).long().to(torch.int32).contiguous(),
-            batch=data.batch.to(dev, torch.int32).contiguous(),
-            atom_offset=off, reps=reps,
-        )
-        if hasattr(data, "tags") and data.tags is not None:
-            prep.tags = data.tags.to(dev, torch.int32).contiguous()
-        if hasattr(data, "fixed") and data.fixed is not None:
-            prep.fixed = data.fixed.to(dev, torch.int32).contiguous()
-        return prep
-
-    def set_moving_atoms(self, prep: Optional[PreparedBatch], moving_mask: Optional[torch.Tensor]) -> None:
-        """Declare which atoms may move between the next graph builds of ``prep`` (None switches the
-        static-atom cache off).  The arrays are kept alive on the engine until the next call."""
-        if moving_mask is None or prep is None:
-            self._moving_keepalive = None
-            _lib.check(self.lib.adf_graph_set_moving(self.handle, None, None, None))
-            return
-        mask = moving_mask.to(self.device, torch.int32).contiguous()
-        idx = torch.nonzero(mask).reshape(-1).to(torch.int32).contiguous()
-        per_sys = torch.bincount(prep.batch[idx.long()].long(), minlength=prep.num_systems)
-        off = torch.zeros(prep.num_systems + 1, dtype=torch.int32, device=self.device)
-        off[1:] = torch.cumsum(per_sys, 0).to(torch.int32)
-        self._moving_keepalive = (mask, idx, off)
-        _lib.check(self.lib.adf_graph_set_moving(self.handle, mask.data_ptr(), idx.data_ptr(), off.data_ptr()))
-
     # ------------------------------------------------------------------ calls
     def forward_prepared(self, prep: PreparedBatch, pos: torch.Tensor, f1: torch.Tensor, f2: Optional[torch.Tensor],
                          out_idx: Optional[torch.Tensor] = None) -> None:
@@ -219,10 +356,6 @@ class PaiNNEngine:
                 _lib.check(self.lib.adf_painn_forward_subset(
                     self.handle, C.byref(desc), out_idx.data_ptr(), int(out_idx.numel()), f1.data_ptr(),
                     f2.data_ptr() if f2 is not None else None, self._stream()))
-
-    def check_flags(self) -> None:
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.adf_check_flags(self.handle, self._stream()))
 
     def forward(self, data):
         prep = self.prepare(data)
@@ -265,24 +398,6 @@ class PaiNNEngine:
             self.forward_energy_prepared(prep, pos, energy, forces)
             self.check_flags()
         return energy, forces
-
-    def use_exact_f32(self) -> bool:
-        """Switch the handle to exact-f32 arithmetic (after a NumericRangeError in the default f16x3 mode: an
-        activation left the fp16 range).  Returns False if it already was exact."""
-        if self.exact_f32:
-            return False
-        import logging
-
-        logging.warning("adsorbdiff_amd: non-finite output in f16x3 arithmetic; re-running in exact f32 "
-                        "(this engine stays in exact f32)")
-        _lib.check(self.lib.adf_painn_set_arithmetic(self.handle, 1))
-        self.exact_f32 = True
-        return True
-
-    def set_incremental(self, on: bool = True) -> None:
-        """Incremental layers (adf_painn_set_incremental): keep per-layer node state across the forwards of a
-        static-atom promise and recompute only rows whose inputs changed.  Bit-identical outputs; default on."""
-        _lib.check(self.lib.adf_painn_set_incremental(self.handle, 1 if on else 0))
 
     def set_fused_mlp(self, mode: int = 2) -> None:
         """Form of the x_proj / xvec_proj pairs (adf_painn_set_fused_mlp): 0 two kernels per pair, 1 the fused two-layer
@@ -337,82 +452,11 @@ class PaiNNEngine:
                 self.handle, layer, x.shape[0], x.data_ptr(), vec.data_ptr(), self._stream()))
         return x, vec
 
-    def init_placement(self, prep: PreparedBatch, pos: torch.Tensor, noise: torch.Tensor) -> None:
-        desc = prep.desc(pos)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.adf_sde_init_placement(
-                self.handle, C.byref(desc), pos.data_ptr(), prep.tags.data_ptr(), noise.data_ptr(), self._stream()))
-
-    def sde_step(self, prep: PreparedBatch, pos, f1, f2, coef: _lib.StepCoef, state, z_tr=None, z_rot=None,
-                 early_stop_count: int = 10, dcom=None, drot=None) -> None:
-        desc = prep.desc(pos)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.adf_sde_step(
-                self.handle, C.byref(desc), pos.data_ptr(), prep.tags.data_ptr(),
-                prep.fixed.data_ptr() if prep.fixed is not None else None, f1.data_ptr(), f2.data_ptr(),
-                C.byref(coef), z_tr.data_ptr() if z_tr is not None else None,
-                z_rot.data_ptr() if z_rot is not None else None, early_stop_count, state.data_ptr(),
-                dcom.data_ptr() if dcom is not None else None, drot.data_ptr() if drot is not None else None,
-                self._stream()))
-
-    def sde_step_scheduled(self, prep: PreparedBatch, pos, f1, f2, coefs_dev: torch.Tensor, num_steps: int, state,
-                           z_tr=None, z_rot=None, early_stop_count: int = 10) -> None:
-        """Step whose schedule scalars come from a device table indexed by state[4] (graph-capturable)."""
-        desc = prep.desc(pos)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.adf_sde_step_scheduled(
-                self.handle, C.byref(desc), pos.data_ptr(), prep.tags.data_ptr(),
-                prep.fixed.data_ptr() if prep.fixed is not None else None, f1.data_ptr(), f2.data_ptr(),
-                coefs_dev.data_ptr(), num_steps, z_tr.data_ptr() if z_tr is not None else None,
-                z_rot.data_ptr() if z_rot is not None else None, early_stop_count, state.data_ptr(), None, None,
-                self._stream()))
-
-    def sample(self, prep: PreparedBatch, pos, f1, f2, coefs_dev: torch.Tensor, num_steps: int, state,
-               z_tr_all=None, z_rot_all=None, early_stop_count: int = 10, poll_every: int = 0,
-               out_idx: Optional[torch.Tensor] = None, sink=None, frame_every: int = 1) -> None:
-        """The whole reverse loop in one library call (``adf_sample``; with ``sink`` — a ``trajectory.FrameSink`` —
-        ``adf_sample_traj``: a frame of the positions leaves the device after every ``frame_every``-th step)."""
-        desc = prep.desc(pos)
-        args = [self.handle, C.byref(desc), pos.data_ptr(), prep.tags.data_ptr(),
-                prep.fixed.data_ptr() if prep.fixed is not None else None, coefs_dev.data_ptr(), num_steps,
-                z_tr_all.data_ptr() if z_tr_all is not None else None,
-                z_rot_all.data_ptr() if z_rot_all is not None else None, early_stop_count, poll_every,
-                state.data_ptr(), out_idx.data_ptr() if out_idx is not None else None,
-                int(out_idx.numel()) if out_idx is not None else 0, f1.data_ptr(), f2.data_ptr()]
-        with torch.cuda.device(self.device):
-            if sink is None:
-                _lib.check(self.lib.adf_sample(*args, self._stream()))
-            else:
-                _lib.check(self.lib.adf_sample_traj(*args, sink.handle, int(frame_every), self._stream()))
-
-    def tr_step(self, prep: PreparedBatch, pos, f1, state, coef: Optional[_lib.TrCoef] = None,
-                coefs_dev: Optional[torch.Tensor] = None, num_steps: int = 0, z=None, early_stop_count: int = 10,
-                dcom=None) -> None:
-        """One step of the translation-only samplers (``adf_tr_step``): head-1 mean over the adsorbate, dcom =
-        coef * score (+ noise * z), COM wrap, pos += dcom.  Scalars from ``coef`` or from the device table
-        ``coefs_dev`` [num_steps, 2] indexed by state[4]."""
-        desc = prep.desc(pos)
-        opt = lambda t: t.data_ptr() if t is not None else None
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.adf_tr_step(
-                self.handle, C.byref(desc), pos.data_ptr(), prep.tags.data_ptr(), f1.data_ptr(),
-                C.byref(coef) if coef is not None else None, opt(coefs_dev), int(num_steps), opt(z), early_stop_count,
-                state.data_ptr(), opt(dcom), self._stream()))
-
-    def tr_sample(self, prep: PreparedBatch, pos, f1, coefs_dev: torch.Tensor, num_steps: int, state, z_all=None,
-                  early_stop_count: int = 10, poll_every: int = 0, out_idx=None, sink=None, frame_every: int = 1) -> None:
-        """The whole translation-only loop in one library call (``adf_tr_sample[_traj]``); the forward inside
-        evaluates head 1 only."""
-        desc = prep.desc(pos)
-        opt = lambda t: t.data_ptr() if t is not None else None
-        args = [self.handle, C.byref(desc), pos.data_ptr(), prep.tags.data_ptr(), coefs_dev.data_ptr(), int(num_steps),
-                opt(z_all), early_stop_count, poll_every, state.data_ptr(), opt(out_idx),
-                int(out_idx.numel()) if out_idx is not None else 0, f1.data_ptr()]
-        with torch.cuda.device(self.device):
-            if sink is None:
-                _lib.check(self.lib.adf_tr_sample(*args, self._stream()))
-            else:
-                _lib.check(self.lib.adf_tr_sample_traj(*args, sink.handle, int(frame_every), self._stream()))
+    def _sde_entry(self, coef, coefs_dev, num_steps):
+        """Two step entries here: adf_sde_step (host scalars) and adf_sde_step_scheduled (device table)."""
+        if coef is not None:
+            return self.lib.adf_sde_step, (C.byref(coef),)
+        return self.lib.adf_sde_step_scheduled, (coefs_dev.data_ptr(), num_steps)
 
     def counters(self) -> _lib.Counters:
         c = _lib.Counters()
@@ -421,9 +465,6 @@ class PaiNNEngine:
         return c
 
     PROFILE_CATEGORIES = ("graph", "message", "node_dense", "heads", "stepper")
-
-    def profile_enable(self, on: bool = True) -> None:
-        _lib.check(self.lib.adf_profile_enable(self.handle, 1 if on else 0))
 
     def profile_read(self):
         """{category: (total_ms, groups)} since the last read (HIP events on the launch stream)."""
@@ -442,16 +483,3 @@ class PaiNNEngine:
         with torch.cuda.device(self.device):
             _lib.check(self.lib.adf_measure_peaks(out, self._stream()))
         return {"hbm_copy_gbps": float(out[0]), "mfma_f16_tflops": float(out[1]), "mfma_f32_tflops": float(out[2])}
-
-    def close(self) -> None:
-        if getattr(self, "handle", None) is not None and self.handle:
-            with torch.cuda.device(self.device):
-                torch.cuda.synchronize(self.device)
-                self.lib.adf_painn_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -1,6 +1,6 @@
 """Device-side engine of the EquiformerV2 denoiser: owns the ``adf_eqv2`` handle, hands over the constant SO(3) tables
-(so3_math.py) and the module's parameters, and enqueues forward / stepper calls on torch's current HIP stream.  Same
-interface as ``PaiNNEngine`` towards ``Denoiser`` (denoising_torch.py).  PyTorch is plumbing here; nothing in this file
+(so3_math.py) and the module's parameters, and enqueues forward calls on torch's current HIP stream; the stepper and
+sampling calls are ``engine.Engine``'s, shared with ``PaiNNEngine``.  PyTorch is plumbing here; nothing in this file
 computes a model output on the host.
 """
 from __future__ import annotations
@@ -13,7 +13,7 @@ import torch
 
 from . import lib as _lib
 from . import so3_math
-from .engine import PreparedBatch, _require_gpu, batch_pbc, cell_repeats
+from .engine import Engine, PreparedBatch, _require_gpu
 
 
 def attn_weight_names(prefix: str, mmax: int) -> List[str]:
@@ -50,15 +50,18 @@ def weight_names(num_layers: int, mmax: int) -> List[str]:
     return names
 
 
-class EqV2Engine:
+class EqV2Engine(Engine):
     PROFILE_CATEGORIES = ("graph", "radial", "rotate", "so2_conv", "s2_act", "attn_weights", "node", "ffn_grid", "stepper")
+    SYMBOLS = dict(set_moving="adf_eqv2_set_moving", check_flags="adf_eqv2_check_flags",
+                   set_arithmetic="adf_eqv2_set_arithmetic", set_incremental="adf_eqv2_set_incremental",
+                   init_placement="adf_eqv2_init_placement", sde_step="adf_eqv2_sde_step", sample="adf_eqv2_sample",
+                   sample_traj="adf_eqv2_sample_traj", tr_step="adf_eqv2_tr_step", tr_sample="adf_eqv2_tr_sample",
+                   tr_sample_traj="adf_eqv2_tr_sample_traj", profile_enable="adf_eqv2_profile_enable",
+                   destroy="adf_eqv2_destroy")
+    num_heads = 2   # force_block and force_block2
 
     def __init__(self, model, device) -> None:
-        self.lib = _lib.load()
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError(f"EqV2Engine needs a ROCm device, got {self.device} (no CPU fallback)")
-        self.model = model
+        super().__init__(model, device)
         self.lmax, self.mmax = int(model.lmax_list[0]), int(model.mmax_list[0])
         hp = _lib.EqV2Hparams(
             lmax=self.lmax, mmax=self.mmax, num_layers=model.num_layers, sphere_channels=model.sphere_channels,
@@ -76,14 +79,9 @@ class EqV2Engine:
             ptr = lambda a: a.ctypes.data_as(C.c_void_p)
             _lib.check(self.lib.adf_eqv2_set_constants(self.handle, ptr(t["jd"]), ptr(t["to_red"]), ptr(t["from_red"]),
                                                        ptr(t["to_full"]), ptr(t["from_full"])))
-        self._weights_keepalive: List[torch.Tensor] = []
-        self._moving_keepalive = None
         self._edges_keepalive = None
         self._energy_keepalive = None
         self._energy_mode = None   # what adf_eqv2_set_system_energy last received: None (never), "zeros", "given"
-        import os
-
-        self.exact_f32 = os.environ.get("ADF_GEMM") == "f32"
         self.bind_weights()
 
     # ------------------------------------------------------------------ weights
@@ -143,44 +141,6 @@ class EqV2Engine:
             raise ValueError(f"data.energy has {int(energy.numel())} values for {int(num_systems)} systems")
         self.set_system_energy(energy)
 
-    # ------------------------------------------------------------------ batches
-    def _stream(self) -> C.c_void_p:
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def prepare(self, data) -> PreparedBatch:
-        _require_gpu(data.pos, "data.pos")
-        dev = self.device
-        natoms = data.natoms.to(dev, torch.int64).reshape(-1)
-        B = int(natoms.shape[0])
-        N = int(data.pos.shape[0])
-        off = torch.zeros(B + 1, dtype=torch.int32, device=dev)
-        off[1:] = torch.cumsum(natoms, 0).to(torch.int32)
-        cell = data.cell.to(dev, torch.float32).reshape(B, 3, 3).contiguous()
-        reps = cell_repeats(cell, float(self.model.cutoff), batch_pbc(data))
-        prep = PreparedBatch(
-            num_systems=B, num_atoms=N, cell=cell,
-            atomic_numbers=data.atomic_numbers.to(dev).long().to(torch.int32).contiguous(),
-            batch=data.batch.to(dev, torch.int32).contiguous(), atom_offset=off, reps=reps,
-        )
-        if hasattr(data, "tags") and data.tags is not None:
-            prep.tags = data.tags.to(dev, torch.int32).contiguous()
-        if hasattr(data, "fixed") and data.fixed is not None:
-            prep.fixed = data.fixed.to(dev, torch.int32).contiguous()
-        return prep
-
-    def set_moving_atoms(self, prep: Optional[PreparedBatch], moving_mask: Optional[torch.Tensor]) -> None:
-        if moving_mask is None or prep is None:
-            self._moving_keepalive = None
-            _lib.check(self.lib.adf_eqv2_set_moving(self.handle, None, None, None))
-            return
-        mask = moving_mask.to(self.device, torch.int32).contiguous()
-        idx = torch.nonzero(mask).reshape(-1).to(torch.int32).contiguous()
-        per_sys = torch.bincount(prep.batch[idx.long()].long(), minlength=prep.num_systems)
-        off = torch.zeros(prep.num_systems + 1, dtype=torch.int32, device=self.device)
-        off[1:] = torch.cumsum(per_sys, 0).to(torch.int32)
-        self._moving_keepalive = (mask, idx, off)
-        _lib.check(self.lib.adf_eqv2_set_moving(self.handle, mask.data_ptr(), idx.data_ptr(), off.data_ptr()))
-
     def set_edges(self, edge_index: Optional[torch.Tensor], edge_vec: Optional[torch.Tensor]) -> None:
         """Run the next forwards on this edge list ([2,E] (source, target) sorted by target, vectors [E,3]) instead of
         building one; ``None`` switches back.  For parity runs against reference outputs whose choice among exactly tied
@@ -218,10 +178,6 @@ class EqV2Engine:
                 self.handle, C.byref(desc), f1.data_ptr(), f2.data_ptr() if f2 is not None else None,
                 x_blocks.data_ptr() if x_blocks is not None else None, self._stream()))
 
-    def check_flags(self) -> None:
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.adf_eqv2_check_flags(self.handle, self._stream()))
-
     def forward(self, data, return_blocks: bool = False):
         prep = self.prepare(data)
         self.bind_condition(data, prep.num_systems)
@@ -237,99 +193,15 @@ class EqV2Engine:
         self.check_flags()
         return (f1, f2, xb) if return_blocks else (f1, f2)
 
-    def use_exact_f32(self) -> bool:
-        if self.exact_f32:
-            return False
-        _lib.check(self.lib.adf_eqv2_set_arithmetic(self.handle, 1))
-        self.exact_f32 = True
-        return True
-
     def set_arithmetic(self, exact_f32: bool) -> None:
         _lib.check(self.lib.adf_eqv2_set_arithmetic(self.handle, 1 if exact_f32 else 0))
         self.exact_f32 = bool(exact_f32)
-
-    def set_incremental(self, on: bool = True) -> None:
-        """Incremental blocks (adf_eqv2_set_incremental): keep every block's output across the forwards of a
-        static-atom run and recompute only the rows whose inputs changed (bit-identical results)."""
-        _lib.check(self.lib.adf_eqv2_set_incremental(self.handle, 1 if on else 0))
-
-    def init_placement(self, prep: PreparedBatch, pos: torch.Tensor, noise: torch.Tensor) -> None:
-        desc = prep.desc(pos)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.adf_eqv2_init_placement(
-                self.handle, C.byref(desc), pos.data_ptr(), prep.tags.data_ptr(), noise.data_ptr(), self._stream()))
-
-    def sde_step(self, prep: PreparedBatch, pos, f1, f2, coef: _lib.StepCoef, state, z_tr=None, z_rot=None,
-                 early_stop_count: int = 10, dcom=None, drot=None) -> None:
-        desc = prep.desc(pos)
-        opt = lambda t: t.data_ptr() if t is not None else None
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.adf_eqv2_sde_step(
-                self.handle, C.byref(desc), pos.data_ptr(), prep.tags.data_ptr(), opt(prep.fixed), f1.data_ptr(),
-                f2.data_ptr(), C.byref(coef), None, 0, opt(z_tr), opt(z_rot), early_stop_count, state.data_ptr(),
-                opt(dcom), opt(drot), self._stream()))
-
-    def sde_step_scheduled(self, prep: PreparedBatch, pos, f1, f2, coefs_dev: torch.Tensor, num_steps: int, state,
-                           z_tr=None, z_rot=None, early_stop_count: int = 10) -> None:
-        desc = prep.desc(pos)
-        opt = lambda t: t.data_ptr() if t is not None else None
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.adf_eqv2_sde_step(
-                self.handle, C.byref(desc), pos.data_ptr(), prep.tags.data_ptr(), opt(prep.fixed), f1.data_ptr(),
-                f2.data_ptr(), None, coefs_dev.data_ptr(), num_steps, opt(z_tr), opt(z_rot), early_stop_count,
-                state.data_ptr(), None, None, self._stream()))
-
-    def sample(self, prep: PreparedBatch, pos, f1, f2, coefs_dev: torch.Tensor, num_steps: int, state,
-               z_tr_all=None, z_rot_all=None, early_stop_count: int = 10, poll_every: int = 0, out_idx=None, sink=None,
-               frame_every: int = 1) -> None:
-        desc = prep.desc(pos)
-        opt = lambda t: t.data_ptr() if t is not None else None
-        args = [self.handle, C.byref(desc), pos.data_ptr(), prep.tags.data_ptr(), opt(prep.fixed), coefs_dev.data_ptr(),
-                num_steps, opt(z_tr_all), opt(z_rot_all), early_stop_count, poll_every, state.data_ptr(), opt(out_idx),
-                int(out_idx.numel()) if out_idx is not None else 0, f1.data_ptr(), f2.data_ptr()]
-        with torch.cuda.device(self.device):
-            if sink is None:
-                _lib.check(self.lib.adf_eqv2_sample(*args, self._stream()))
-            else:
-                _lib.check(self.lib.adf_eqv2_sample_traj(*args, sink.handle, int(frame_every), self._stream()))
-
-    def tr_step(self, prep: PreparedBatch, pos, f1, state, coef: Optional[_lib.TrCoef] = None,
-                coefs_dev: Optional[torch.Tensor] = None, num_steps: int = 0, z=None, early_stop_count: int = 10,
-                dcom=None) -> None:
-        """One step of the translation-only samplers (``adf_eqv2_tr_step``): head-1 mean over the adsorbate, dcom =
-        coef * score (+ noise * z), COM wrap, pos += dcom.  Scalars from ``coef`` or from the device table
-        ``coefs_dev`` [num_steps, 2] indexed by state[4]."""
-        desc = prep.desc(pos)
-        opt = lambda t: t.data_ptr() if t is not None else None
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.adf_eqv2_tr_step(
-                self.handle, C.byref(desc), pos.data_ptr(), prep.tags.data_ptr(), f1.data_ptr(),
-                C.byref(coef) if coef is not None else None, opt(coefs_dev), int(num_steps), opt(z), early_stop_count,
-                state.data_ptr(), opt(dcom), self._stream()))
-
-    def tr_sample(self, prep: PreparedBatch, pos, f1, coefs_dev: torch.Tensor, num_steps: int, state, z_all=None,
-                  early_stop_count: int = 10, poll_every: int = 0, out_idx=None, sink=None, frame_every: int = 1) -> None:
-        """The whole translation-only loop in one library call (``adf_eqv2_tr_sample[_traj]``); the forward inside
-        evaluates head 1 only."""
-        desc = prep.desc(pos)
-        opt = lambda t: t.data_ptr() if t is not None else None
-        args = [self.handle, C.byref(desc), pos.data_ptr(), prep.tags.data_ptr(), coefs_dev.data_ptr(), int(num_steps),
-                opt(z_all), early_stop_count, poll_every, state.data_ptr(), opt(out_idx),
-                int(out_idx.numel()) if out_idx is not None else 0, f1.data_ptr()]
-        with torch.cuda.device(self.device):
-            if sink is None:
-                _lib.check(self.lib.adf_eqv2_tr_sample(*args, self._stream()))
-            else:
-                _lib.check(self.lib.adf_eqv2_tr_sample_traj(*args, sink.handle, int(frame_every), self._stream()))
 
     def counters(self) -> _lib.EqV2Counters:
         c = _lib.EqV2Counters()
         with torch.cuda.device(self.device):
             _lib.check(self.lib.adf_eqv2_get_counters(self.handle, C.byref(c), self._stream()))
         return c
-
-    def profile_enable(self, on: bool = True) -> None:
-        _lib.check(self.lib.adf_eqv2_profile_enable(self.handle, 1 if on else 0))
 
     def profile_read(self):
         n = len(self.PROFILE_CATEGORIES)
@@ -338,16 +210,3 @@ class EqV2Engine:
         with torch.cuda.device(self.device):
             _lib.check(self.lib.adf_eqv2_profile_read(self.handle, ms, cnt, self._stream()))
         return {k: (float(ms[i]), int(cnt[i])) for i, k in enumerate(self.PROFILE_CATEGORIES)}
-
-    def close(self) -> None:
-        if getattr(self, "handle", None) is not None and self.handle:
-            with torch.cuda.device(self.device):
-                torch.cuda.synchronize(self.device)
-                self.lib.adf_eqv2_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

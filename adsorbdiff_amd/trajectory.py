@@ -40,6 +40,13 @@ class FrameSink:
         _lib.check(self.lib.adf_frames_create(int(device_index), 3 * self.num_atoms, self.slots, C.byref(h)))
         self.handle = h
 
+    def push(self, src, stream) -> None:
+        """Snapshot ``src`` (the [N,3] float32 positions on the device) on the torch ``stream`` as the next frame."""
+        import torch
+
+        with torch.cuda.device(stream.device):
+            _lib.check(self.lib.adf_frames_push(self.handle, src.data_ptr(), C.c_void_p(stream.cuda_stream)))
+
     def wait(self, index: int, timeout_ms: int = 100) -> Optional[np.ndarray]:
         """Frame ``index`` as a [N,3] view of the pinned ring (valid until ``release``), or None on time-out."""
         ptr = C.POINTER(C.c_float)()

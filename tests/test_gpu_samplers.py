@@ -1,10 +1,13 @@
 """GPU tests of the translation-only samplers Denoiser.reverse_sde_sampling / langevin_dynamics (csrc/stepper.hip
 adf_tr_* kernels, adf_tr_sample / adf_eqv2_tr_sample fused loops) against the reference's own runs recorded by
 tools/make_golden_samplers.py.  Tolerances are those of test_gpu_parity.py::test_stepper_each_step_vs_reference_fixture."""
+import ctypes
+
 import numpy as np
 import pytest
 import torch
 
+from adsorbdiff_amd import lib as L
 from adsorbdiff_amd.data import Batch
 from adsorbdiff_amd.denoising_torch import Denoiser, DiffTorchCalc, langevin_coefs, ode_tr_coefs
 from adsorbdiff_amd.painn_denoising import PaiNN
@@ -74,6 +77,14 @@ def test_translation_step_each_step_vs_reference_fixture(name):
     np.testing.assert_allclose(pos.cpu().numpy(), log[0].numpy(), rtol=0, atol=2e-6)
     f1 = torch.empty(N, 3, device=DEV)
     f2 = torch.empty(N, 3, device=DEV) if int(fx["heads"]) == 2 else None
+    # the fused loops' shared argument check rejects a negative subset size before any launch (here adf_sample)
+    desc, state = prep.desc(pos), torch.tensor([0, 0, 1, 0, 0, 0, 0, 0], dtype=torch.int32, device=DEV)
+    out_idx, placed = torch.nonzero(b.tags == 2).reshape(-1).to(torch.int32).contiguous(), pos.clone()
+    assert eng.lib.adf_sample(eng.handle, ctypes.byref(desc), pos.data_ptr(), prep.tags.data_ptr(), None,
+                              torch.zeros(1, 6, device=DEV).data_ptr(), 1, None, None, 0, 0, state.data_ptr(),
+                              out_idx.data_ptr(), -1, f1.data_ptr(), f1.data_ptr(), None) == L.ADF_EINVAL
+    torch.cuda.synchronize()
+    assert torch.equal(pos, placed) and state.tolist() == [0, 0, 1, 0, 0, 0, 0, 0]
     tags = torch.from_numpy(fx["tags"])
     ads = b.tags == 2
     cnt = torch.zeros(B, device=DEV).index_add_(0, b.batch[ads], torch.ones(int(ads.sum()), device=DEV))[:, None]
