@@ -1,5 +1,6 @@
 // Internal declarations of the EquiformerV2 denoiser path (BASELINE config 4).
-// Reference: adsorbdiff/models/equiformer_v2/equiformer_v2_denoising.py:185-318 and the modules it calls.
+// Reference: adsorbdiff/models/equiformer_v2/equiformer_v2_denoising.py:185-318 and the modules it calls; the S2EF force
+// field of equiformer_v2_oc20.py:415-562 runs on the same handle (adf_eqv2::s2ef).
 #pragma once
 #include "common.h"
 
@@ -21,6 +22,7 @@ struct eq_radial {      // RadialFunction: Linear, LayerNorm, SiLU, Linear, Laye
     const float *ln1_w, *ln1_b, *ln4_w, *ln4_b;
     float* w0t;         // library-owned transpose of l0.w: [in, out]
     float* table;       // [NE*NE, l6.out] radial weights per element pair (static-radial mode), else null
+    float* pair0;       // [NE*NE, EC] b0 + W_s semb[Z_s] + W_t temb[Z_t] of the first layer (S2EF model), else null
 };
 struct eq_norm {        // EquivariantLayerNormArraySphericalHarmonics (layer_norm.py:129-250)
     const float *affine, *l0_w, *l0_b;
@@ -88,6 +90,16 @@ struct adf_eqv2 {
     eq_block blk[EQ_MAX_LAYERS];
     eq_norm final_norm;
     eq_attn force[2];
+    // S2EF model (adf_eqv2_set_weights_s2ef / adf_eqv2_set_energy_head): no atomic radii (the Gaussian basis is live on
+    // every edge), one force block, energy head on the l = 0 row of the final-normed embedding
+    bool s2ef;
+    float* pair0_arena; size_t pair0_floats;   // the radial functions' first-layer element-pair tables (eq_radial::pair0)
+    bool eh_set;
+    eq_lin eh_scalar;                  // energy_block.scalar_mlp.0 [F, C]
+    const float *eh_w2, *eh_b2;        // row 0 of energy_block.so3_linear_2.weight[0] [F], its bias [1]
+    const float* eh_lin_ref;           // energy_lin_ref [max_num_elements] or null
+    float eh_avg_num_nodes;
+    unsigned char* eh_w16; size_t eh_w16_bytes; float* eh_scale;   // fp16 hi/lo image of eh_scalar
     // conditional model (adf_eqv2_set_energy_embedding / adf_eqv2_set_system_energy): energy_embedding = nn.Linear(1, C)
     bool ee_on, ee_ready;      // a layer is bound / ee_term matches the bound layer and energies
     float* ee_wb;              // [2C] copy of W, b (fp32; rounded to fp16 by the term kernel)
@@ -160,6 +172,15 @@ int32_t eq_launch_norm(const adf_eqv2* h, const eq_norm* nm, const float* x, flo
 int32_t eq_launch_radial_pre(const adf_eqv2* h, const eq_radial* r, const float* src_emb, const float* dst_emb,
                              const int32_t* Z, int n0, int n1, float* out, int N, hipStream_t s);
 int32_t eq_launch_ln_silu(float* x, const float* w, const float* b, long long rows, int width, hipStream_t s);
+// first radial layer with a live Gaussian basis (S2EF model): pair0 row + Gaussian window, LayerNorm, SiLU -> out [Eub, EC];
+// rows past the chunk's last edge are zeroed
+int32_t eq_launch_radial_live(const adf_eqv2* h, const eq_radial* r, const int32_t* Z, int n0, int n1, float* out,
+                              hipStream_t s);
+int32_t eq_launch_radial_live_raw(const float* e_vec, const int32_t* e_src, const int32_t* e_dst, const int32_t* eptr,
+                                  const int32_t* Z, const eq_radial* r, int n0, int n1, long long Eub, int EC, int NB, int NE,
+                                  float rc, float* out, int32_t* flags, hipStream_t s);
+// per-system energies from the hidden layer of the energy head (hid [N, F]); fixed summation order
+int32_t eq_launch_energy_sum(const adf_eqv2* h, const float* hid, const adf_batch* b, float* energy, hipStream_t s);
 // pair_ne > 0: m0 / rad are tables with one row per element pair (Z_src * pair_ne + Z_tgt) instead of one row per edge
 // term != null (conditional model): term[batch[n] * term_stride + c] joins the element embedding on l = 0
 int32_t eq_launch_edge_degree(const adf_eqv2* h, const float* m0, const int32_t* Z, int pair_ne, int n0, int n1, float* x,

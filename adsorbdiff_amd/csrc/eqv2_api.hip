@@ -2,6 +2,9 @@
 // "EquiformerV2 denoiser").  Reference: models/equiformer_v2/equiformer_v2_denoising.py:185-318 (forward),
 // transformer_block.py:226-372 (SO2EquivariantGraphAttention.forward), :473-531 (FeedForwardNetwork.forward),
 // :650-728 (TransBlockV2.forward), input_block.py:84-138 (EdgeDegreeEmbedding.forward).
+// The same handle runs the S2EF force field (equiformer_v2_oc20.py:415-562; adf_eqv2_set_weights_s2ef,
+// adf_eqv2_set_energy_head, adf_eqv2_forward_energy): no atomic radii (live distance basis, every radial function per
+// edge with the fused first layer of eqv2_kernels.hip), one force block, the energy head.
 #include <hipcub/hipcub.hpp>
 #include <math.h>
 #include <stdlib.h>
@@ -174,6 +177,7 @@ extern "C" int32_t adf_eqv2_destroy(adf_eqv2_t h) {
     { unsigned char* t = (unsigned char*)h->gtab_from; eq_free(t); h->gtab_from = nullptr; }
     eq_free(h->jd); eq_free(h->to_red); eq_free(h->from_red); eq_free(h->to_full); eq_free(h->from_full);
     eq_free(h->w16_arena); eq_free(h->wfrag_arena); eq_free(h->w16_scales); eq_free(h->w16_scratch); eq_free(h->wt_arena); eq_free(h->rtab_arena); eq_free(h->fold_arena);
+    eq_free(h->pair0_arena); eq_free(h->eh_w16); eq_free(h->eh_scale);
     if (h->prof_ev) { for (hipEvent_t e : *h->prof_ev) (void)hipEventDestroy(e); delete h->prof_ev; }
     delete h->prof_cat;
     delete h;
@@ -317,9 +321,9 @@ static void bind_attn(eq_wcursor& c, eq_attn* a, const eq_dims& d, int out_chann
         a->proj_l[l] = mk_lin(a->proj_w ? a->proj_w + (size_t)l * out_channels * d.HV : nullptr, l == 0 ? a->proj_b : nullptr, out_channels, d.HV);
 }
 
-static int eq_expected_weights(const eq_dims& d, int layers) {
+static int eq_expected_weights(const eq_dims& d, int layers, bool s2ef) {
     const int attn = 21 + 2 * d.M;
-    return 14 + layers * (3 + attn + 3 + 9) + 3 + 2 * attn;
+    return (s2ef ? 13 : 14) + layers * (3 + attn + 3 + 9) + 3 + (s2ef ? 1 : 2) * attn;
 }
 
 // fp16 hi/lo images (per-matrix power-of-two scale, gemm16.hip) of every weight a dense product reads
@@ -341,7 +345,8 @@ static void eq_collect_lins(adf_eqv2* h, std::vector<eq_lin*>& v) {
         if (h->folded)
             for (int l = 0; l <= d.L; ++l) { v.push_back(&b.ffn.l1f[l]); if (l) v.push_back(&b.ffn.l2f[l]); }
     }
-    attn(&h->force[0], false); attn(&h->force[1], false);
+    attn(&h->force[0], false);
+    if (!h->s2ef) attn(&h->force[1], false);
 }
 
 static int32_t eq_split_weights(adf_eqv2* h, hipStream_t s) {
@@ -454,6 +459,27 @@ static int32_t eq_radial_static(adf_eqv2* h, eq_radial** rads, int nrad, hipStre
     return ADF_OK;
 }
 
+// S2EF model: the element-embedding part of every first radial layer, b0 + W_s semb[Z_s] + W_t temb[Z_t], per element pair
+// (row Z_s * NE + Z_t, [NE^2, EC] per radial function); the Gaussian part is added per edge (eq_radial_live_kernel)
+static int32_t eq_radial_pair_tables(adf_eqv2* h, eq_radial** rads, const float** semb, const float** temb, int nrad,
+                                     hipStream_t s) {
+    const size_t per = (size_t)h->hp.max_num_elements * h->hp.max_num_elements * h->d.EC;
+    if (h->pair0_floats < per * nrad) {
+        ADF_HIP_CHECK(hipDeviceSynchronize());
+        eq_free(h->pair0_arena);
+        h->pair0_floats = 0;
+        ADF_TRY(eq_alloc(&h->pair0_arena, per * nrad));
+        h->pair0_floats = per * nrad;
+    }
+    for (int i = 0; i < nrad; ++i) {
+        rads[i]->table = nullptr;
+        rads[i]->pair0 = h->pair0_arena + per * i;
+        ADF_TRY(eq_launch_radial_pre_pairs(h, rads[i], semb[i], temb[i], rads[i]->pair0, s));
+    }
+    h->rad_static = false;
+    return ADF_OK;
+}
+
 // Folded feed-forward weights (eq_ffn): l1f[l] = g0 . l1[l] (+ bias g0 . b on l = 0), l2f[l] = l2[l] . g4 for l >= 1.
 static int32_t eq_fold_ffn(adf_eqv2* h, hipStream_t s) {
     const eq_dims& d = h->d;
@@ -490,16 +516,18 @@ static int32_t eq_fold_ffn(adf_eqv2* h, hipStream_t s) {
     return ADF_OK;
 }
 
-extern "C" int32_t adf_eqv2_set_weights(adf_eqv2_t h, int32_t n_weights, const void* const* weights, void* stream) {
+static int32_t eq_set_weights(adf_eqv2_t h, int32_t n_weights, const void* const* weights, void* stream, bool s2ef) {
     if (!h || !weights) { adf_set_error("eqv2_set_weights: null argument"); return ADF_EINVAL; }
     const eq_dims& d = h->d;
-    const int want = eq_expected_weights(d, h->hp.num_layers);
+    const int want = eq_expected_weights(d, h->hp.num_layers, s2ef);
     if (n_weights != want) { adf_set_error("eqv2_set_weights: expected %d tensors, got %d", want, n_weights); return ADF_EINVAL; }
     for (int i = 0; i < n_weights; ++i)
         if (!weights[i]) { adf_set_error("eqv2_set_weights: tensor %d is null", i); return ADF_EINVAL; }
     hipStream_t s = (hipStream_t)stream;
     eq_wcursor c{weights, n_weights, 0};
-    h->atom_radii = c.next();
+    h->s2ef = s2ef;
+    h->weights_set = false;
+    h->atom_radii = s2ef ? nullptr : c.next();
     h->sphere_emb = c.next();
     h->ed_src_emb = c.next(); h->ed_dst_emb = c.next();
     bind_radial(c, &h->ed_rad, d.NB + 2 * d.EC, d.EC, (d.L + 1) * d.C);
@@ -521,9 +549,9 @@ extern "C" int32_t adf_eqv2_set_weights(adf_eqv2_t h, int32_t n_weights, const v
     }
     bind_norm(c, &h->final_norm);
     bind_attn(c, &h->force[0], d, 1);
-    bind_attn(c, &h->force[1], d, 1);
+    if (!s2ef) bind_attn(c, &h->force[1], d, 1);
     // transposed first radial layers (one arena)
-    const int nrad = 1 + h->hp.num_layers + 2;
+    const int nrad = 1 + h->hp.num_layers + (s2ef ? 1 : 2);
     const size_t per = (size_t)(d.NB + 2 * d.EC) * d.EC;
     if (h->wt_bytes < per * nrad * 4) {
         eq_free(h->wt_arena);
@@ -531,10 +559,12 @@ extern "C" int32_t adf_eqv2_set_weights(adf_eqv2_t h, int32_t n_weights, const v
         h->wt_bytes = per * nrad * 4;
     }
     eq_radial* rads[EQ_MAX_LAYERS + 3];
+    const float *semb[EQ_MAX_LAYERS + 3], *temb[EQ_MAX_LAYERS + 3];
     int k = 0;
-    rads[k++] = &h->ed_rad;
-    for (int i = 0; i < h->hp.num_layers; ++i) rads[k++] = &h->blk[i].ga.rad;
-    rads[k++] = &h->force[0].rad; rads[k++] = &h->force[1].rad;
+    semb[k] = h->ed_src_emb; temb[k] = h->ed_dst_emb; rads[k++] = &h->ed_rad;
+    for (int i = 0; i < h->hp.num_layers; ++i) { semb[k] = h->blk[i].ga.src_emb; temb[k] = h->blk[i].ga.dst_emb; rads[k++] = &h->blk[i].ga.rad; }
+    for (int i = 0; i < (s2ef ? 1 : 2); ++i) { semb[k] = h->force[i].src_emb; temb[k] = h->force[i].dst_emb; rads[k++] = &h->force[i].rad; }
+    for (int i = 0; i < k; ++i) rads[i]->pair0 = nullptr;
     for (int i = 0; i < k; ++i) {
         rads[i]->w0t = h->wt_arena + per * i;
         ADF_TRY(eq_launch_transpose(rads[i]->l0.w, rads[i]->w0t, d.EC, d.NB + 2 * d.EC, s));
@@ -543,9 +573,55 @@ extern "C" int32_t adf_eqv2_set_weights(adf_eqv2_t h, int32_t n_weights, const v
     ADF_TRY(eq_split_weights(h, s));
     if (h->folded)
         for (int i = 0; i < h->hp.num_layers; ++i) h->blk[i].ffn.l2f[0] = h->blk[i].ffn.l2[0];  // l = 0 comes from the gate
-    ADF_TRY(eq_radial_static(h, rads, k, s));
+    if (s2ef) ADF_TRY(eq_radial_pair_tables(h, rads, semb, temb, k, s));
+    else ADF_TRY(eq_radial_static(h, rads, k, s));
     h->weights_set = true;
     h->inc_valid = false;
+    return ADF_OK;
+}
+
+extern "C" int32_t adf_eqv2_set_weights(adf_eqv2_t h, int32_t n_weights, const void* const* weights, void* stream) {
+    return eq_set_weights(h, n_weights, weights, stream, false);
+}
+
+extern "C" int32_t adf_eqv2_set_weights_s2ef(adf_eqv2_t h, int32_t n_weights, const void* const* weights, void* stream) {
+    return eq_set_weights(h, n_weights, weights, stream, true);
+}
+
+extern "C" int32_t adf_eqv2_set_energy_head(adf_eqv2_t h, int32_t n_weights, const void* const* w, float avg_num_nodes,
+                                            const float* energy_lin_ref, void* stream) {
+    if (!h || !w) { adf_set_error("eqv2_set_energy_head: null argument"); return ADF_EINVAL; }
+    if (n_weights != 4) {
+        adf_set_error("eqv2_set_energy_head: expected 4 tensors (energy_block.scalar_mlp.0.weight / bias, row 0 of "
+                      "energy_block.so3_linear_2.weight[0], energy_block.so3_linear_2.bias), got %d", n_weights);
+        return ADF_EINVAL;
+    }
+    for (int i = 0; i < 4; ++i) if (!w[i]) { adf_set_error("eqv2_set_energy_head: tensor %d is null", i); return ADF_EINVAL; }
+    if (!(avg_num_nodes > 0.f)) { adf_set_error("eqv2_set_energy_head: avg_num_nodes must be positive"); return ADF_EINVAL; }
+    const eq_dims& d = h->d;
+    hipStream_t s = (hipStream_t)stream;
+    h->eh_set = false;
+    h->eh_scalar = mk_lin(static_cast<const float*>(w[0]), static_cast<const float*>(w[1]), d.F, d.C);
+    h->eh_w2 = static_cast<const float*>(w[2]); h->eh_b2 = static_cast<const float*>(w[3]);
+    h->eh_lin_ref = energy_lin_ref; h->eh_avg_num_nodes = avg_num_nodes;
+    eq_lin* l = &h->eh_scalar;
+    if (l->in % 32 == 0 && (l->out & 3) == 0) {   // its fp16 hi/lo image, as eq_split_weights makes them
+        const size_t n = (size_t)l->out * l->in;
+        if (h->eh_w16_bytes < n * 4 + 64) {
+            ADF_HIP_CHECK(hipDeviceSynchronize());
+            eq_free(h->eh_w16);
+            h->eh_w16_bytes = 0;
+            ADF_TRY(eq_alloc(&h->eh_w16, n * 4 + 64));
+            h->eh_w16_bytes = n * 4 + 64;
+        }
+        if (!h->eh_scale) ADF_TRY(eq_alloc(&h->eh_scale, 1));
+        if (!h->w16_scratch) ADF_TRY(eq_alloc(&h->w16_scratch, 4));
+        l->w16.hi = h->eh_w16; l->w16.lo = h->eh_w16 + n * 2; l->w16.inv_scale = h->eh_scale; l->w16.bias_perm = nullptr;
+        l->w16.frag = nullptr;
+        ADF_TRY(adf_split_weight(l->w, (long long)n, &l->w16, h->w16_scratch, s));
+        l->has16 = true;
+    }
+    h->eh_set = true;
     return ADF_OK;
 }
 
@@ -829,8 +905,12 @@ static int32_t eq_radial(adf_eqv2* h, const eq_radial* r, const float* semb, con
                          int n1, long long Eub, eq_chunk_bufs* b, float* out, int N, hipStream_t s) {
     const eq_dims& d = h->d;
     eq_prof_scope ps(h, EQ_PROF_RADIAL, s);
-    ADF_TRY(eq_launch_radial_pre(h, r, semb, temb, Z, n0, n1, b->radh, N, s));
-    ADF_TRY(eq_launch_ln_silu(b->radh, r->ln1_w, r->ln1_b, Eub, d.EC, s));
+    if (h->s2ef) {   // live distance basis: pair table + Gaussian window + LayerNorm + SiLU in one kernel
+        ADF_TRY(eq_launch_radial_live(h, r, Z, n0, n1, b->radh, s));
+    } else {
+        ADF_TRY(eq_launch_radial_pre(h, r, semb, temb, Z, n0, n1, b->radh, N, s));
+        ADF_TRY(eq_launch_ln_silu(b->radh, r->ln1_w, r->ln1_b, Eub, d.EC, s));
+    }
     ADF_TRY(eq_gemm(h, b->radh, d.EC, nullptr, &r->l3, true, b->radh2, d.EC, nullptr, Eub, 0, false, s));
     ADF_TRY(eq_launch_ln_silu(b->radh2, r->ln4_w, r->ln4_b, Eub, d.EC, s));
     ADF_TRY(eq_gemm(h, b->radh2, d.EC, nullptr, &r->l6, true, out, r->l6.out, nullptr, Eub, 0, false, s));
@@ -1006,8 +1086,9 @@ static int32_t eq_block_nodes(adf_eqv2* h, const eq_block& bk, float* X, int n, 
 // out_idx != null: the two force blocks (all that reads the last embedding) run for the listed target atoms only, on a
 // compacted copy of their incoming edges; rows out_idx[*] of f1 / f2 are written, bit-identical to the full forward's
 // (every row of every product, the softmax of a target and its aggregation depend on that target's edges alone).
+// energy != null (S2EF model): the energy head on the final-normed embedding, [B]
 static int32_t eq_forward_impl(adf_eqv2* h, const adf_batch* b, float* f1, float* f2, float* x_blocks, hipStream_t s,
-                               const int32_t* out_idx = nullptr, int32_t n_out = 0) {
+                               const int32_t* out_idx = nullptr, int32_t n_out = 0, float* energy = nullptr) {
     const eq_dims& d = h->d;
     const int N = b->num_atoms, B = b->num_systems;
     ADF_TRY(eq_ensure_capacity(h, N, B, h->ext_graph ? h->E_ext : 0));
@@ -1104,6 +1185,12 @@ static int32_t eq_forward_impl(adf_eqv2* h, const adf_batch* b, float* f1, float
         h->inc_rows += h->last_block_rows; h->inc_rows_full += (int64_t)nl * N;
     }
     { eq_prof_scope ps(h, EQ_PROF_NODE, s); ADF_TRY(eq_launch_norm(h, &h->final_norm, X, h->y, N, s)); }
+    if (energy) {   // hid = SiLU(scalar_mlp.0(l = 0 row)) (row stride S C), then the per-system sums (eq_energy_sum_kernel)
+        eq_prof_scope ps(h, EQ_PROF_NODE, s);
+        ADF_TRY(eq_gemm(h, h->y, d.S * d.C, nullptr, &h->eh_scalar, true, h->gate, d.F, nullptr, N, 2, false, s));
+        ADF_TRY(eq_launch_energy_sum(h, h->gate, b, energy, s));
+    }
+    const int nf = h->s2ef ? 1 : 2;   // force blocks
     h->last_subset = out_idx ? n_out : -1;
     if (out_idx) {
         if (n_out <= 0) return ADF_OK;
@@ -1113,7 +1200,7 @@ static int32_t eq_forward_impl(adf_eqv2* h, const adf_batch* b, float* f1, float
         // the attention kernels read the graph through the handle: point it at the compact arrays for the force blocks
         const eq_graph_view full = eq_graph_use_subset(h);
         int32_t st = ADF_OK;
-        for (int k = 0; k < 2 && st == ADF_OK; ++k) {
+        for (int k = 0; k < nf && st == ADF_OK; ++k) {
             float* f = k == 0 ? f1 : f2;
             if (!f) continue;
             st = eq_attention(h, &h->force[k], h->y, Z, n_out, h->agg, true, s);
@@ -1124,7 +1211,7 @@ static int32_t eq_forward_impl(adf_eqv2* h, const adf_batch* b, float* f1, float
         eq_graph_restore(h, full);
         return st;
     }
-    for (int k = 0; k < 2; ++k) {
+    for (int k = 0; k < nf; ++k) {
         float* f = k == 0 ? f1 : f2;
         if (!f) continue;
         ADF_TRY(eq_attention(h, &h->force[k], h->y, Z, N, h->agg, true, s));
@@ -1137,7 +1224,19 @@ static int32_t eq_forward_impl(adf_eqv2* h, const adf_batch* b, float* f1, float
 extern "C" int32_t adf_eqv2_forward(adf_eqv2_t h, const adf_batch* b, float* f1, float* f2, float* x_blocks, void* stream) {
     ADF_TRY(eq_check_batch(h, b));
     if (!f1) { adf_set_error("eqv2_forward: f1 is null"); return ADF_EINVAL; }
+    if (h->s2ef && f2) { adf_set_error("eqv2_forward: the S2EF model has one force block (f2 must be NULL)"); return ADF_EINVAL; }
     return eq_forward_impl(h, b, f1, f2, x_blocks, (hipStream_t)stream);
+}
+
+extern "C" int32_t adf_eqv2_forward_energy(adf_eqv2_t h, const adf_batch* b, float* energy, float* forces, float* x_blocks,
+                                           void* stream) {
+    ADF_TRY(eq_check_batch(h, b));
+    if (!h->s2ef || !h->eh_set) {
+        adf_set_error("eqv2_forward_energy: bind the S2EF model first (adf_eqv2_set_weights_s2ef, adf_eqv2_set_energy_head)");
+        return ADF_EINVAL;
+    }
+    if (!energy) { adf_set_error("eqv2_forward_energy: energy is null"); return ADF_EINVAL; }
+    return eq_forward_impl(h, b, forces, nullptr, x_blocks, (hipStream_t)stream, nullptr, 0, energy);
 }
 
 extern "C" int32_t adf_eqv2_forward_subset(adf_eqv2_t h, const adf_batch* b, const int32_t* out_idx, int32_t n_out, float* f1,
@@ -1276,6 +1375,29 @@ extern "C" int32_t adf_eqv2_linear_forward(const float* A, const float* W, const
     }
     (void)hipStreamSynchronize(s);
     eq_free(buf);
+    return st;
+}
+
+// The S2EF model's first radial layer + LayerNorm + SiLU (eq_radial_live_kernel) of radial function `which` (0: the
+// edge-degree embedding, 1..num_layers: the blocks, num_layers + 1: the force block) on a caller's edge list (unit tests).
+extern "C" int32_t adf_eqv2_radial_first_layer(adf_eqv2_t h, int32_t which, int64_t num_edges, const int32_t* src,
+                                               const int32_t* dst, const float* vec, const int32_t* Z, float* out,
+                                               void* stream) {
+    if (!h || !src || !dst || !vec || !Z || !out || num_edges <= 0) { adf_set_error("eqv2_radial_first_layer: bad argument"); return ADF_EINVAL; }
+    if (!h->s2ef || !h->weights_set) { adf_set_error("eqv2_radial_first_layer: bind the S2EF model first"); return ADF_EINVAL; }
+    const int nl = h->hp.num_layers;
+    if (which < 0 || which > nl + 1 || num_edges > 0x7fffffff) { adf_set_error("eqv2_radial_first_layer: no such radial function"); return ADF_EINVAL; }
+    const struct eq_radial* r = which == 0 ? &h->ed_rad : (which <= nl ? &h->blk[which - 1].ga.rad : &h->force[0].rad);
+    hipStream_t s = (hipStream_t)stream;
+    int32_t* ep = nullptr;
+    ADF_TRY(eq_alloc(&ep, 2));
+    const int32_t hp2[2] = {0, (int32_t)num_edges};
+    int32_t st = ADF_OK;
+    if (hipMemcpyAsync(ep, hp2, sizeof(hp2), hipMemcpyHostToDevice, s) != hipSuccess) st = ADF_EHIP;
+    if (st == ADF_OK) st = eq_launch_radial_live_raw(vec, src, dst, ep, Z, r, 0, 1, num_edges, h->d.EC, h->d.NB,
+                                                     h->hp.max_num_elements, h->hp.max_radius, out, h->flags, s);
+    (void)hipStreamSynchronize(s);
+    eq_free(ep);
     return st;
 }
 

@@ -118,13 +118,15 @@ int32_t eq_launch_edges_from_topk(adf_eqv2* h, const adf_batch* b, hipStream_t s
 }
 
 // atomic numbers must index the embedding tables [0, max_num_elements) and the radius table [0, 100]
-__global__ void eq_check_z_kernel(const int32_t* __restrict__ Z, int N, int max_elem, int32_t* flags) {
+// (zmax: 100 for the denoiser; the S2EF model reads no radius table)
+__global__ void eq_check_z_kernel(const int32_t* __restrict__ Z, int N, int max_elem, int zmax, int32_t* flags) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < N && (Z[i] < 0 || Z[i] >= max_elem || Z[i] > 100)) atomicExch(&flags[4], 1);
+    if (i < N && (Z[i] < 0 || Z[i] >= max_elem || Z[i] > zmax)) atomicExch(&flags[4], 1);
 }
 
 int32_t eq_launch_check_z(const adf_eqv2* h, const int32_t* Z, int N, hipStream_t s) {
-    hipLaunchKernelGGL(eq_check_z_kernel, dim3((N + 255) / 256), dim3(256), 0, s, Z, N, h->hp.max_num_elements, h->flags);
+    hipLaunchKernelGGL(eq_check_z_kernel, dim3((N + 255) / 256), dim3(256), 0, s, Z, N, h->hp.max_num_elements,
+                       h->s2ef ? 0x7fffffff : 100, h->flags);
     ADF_HIP_CHECK(hipGetLastError());
     return ADF_OK;
 }
@@ -331,7 +333,8 @@ __global__ void eq_radial_pre_pairs_kernel(const float* __restrict__ radii, cons
     const int pair = blockIdx.x, j = threadIdx.x;
     const int zs = pair / NE, zt = pair - zs * NE;
     if (j >= EC) return;
-    const float rr = (zs <= 100 ? radii[zs] : 0.f) + (zt <= 100 ? radii[zt] : 0.f);
+    // (radii == null: the S2EF model, whose first layer adds the Gaussian part per edge, eq_radial_live_kernel)
+    const float rr = radii ? (zs <= 100 ? radii[zs] : 0.f) + (zt <= 100 ? radii[zt] : 0.f) : 0.f;
     float acc = b0[j];
     if (!(rr == rr)) acc = rr;
     const float* se = semb + (size_t)zs * EC;
@@ -383,6 +386,159 @@ __global__ __launch_bounds__(256) void eq_ln_silu_kernel(float* __restrict__ x, 
 int32_t eq_launch_ln_silu(float* x, const float* w, const float* b, long long rows, int width, hipStream_t s) {
     if (rows <= 0) return ADF_OK;
     hipLaunchKernelGGL(eq_ln_silu_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, x, w, b, rows, width);
+    ADF_HIP_CHECK(hipGetLastError());
+    return ADF_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ S2EF model: live basis
+// First radial layer + LayerNorm + SiLU of the S2EF model (equiformer_v2_oc20.py:478, no atomic radii: the Gaussian basis
+// of the plain distance is live on every edge).  x = pair0[Z_s, Z_t] (= b0 + W_s semb[Z_s] + W_t temb[Z_t], tabulated at
+// weight binding by eq_radial_pre_pairs_kernel) + sum over the window of basis functions that do not underflow
+// (|d - mu_k| < tmax = 2 delta sqrt(208): at most 58 of them, whatever NB and the cutoff); out = SiLU(LayerNorm(x)),
+// written once.  One wave per edge, EQ_RL_EPW consecutive edges per wave, four waves per workgroup; lane = channel
+// (NCH channels per lane, 64 apart), so a row of w0t [NB + 2 EC, EC] is read as NCH coalesced 256-byte segments; lane q
+// evaluates the q-th Gaussian of the window once and the wave reads it by shuffle.  Rows past the chunk's last edge are
+// zeroed (the two dense layers that follow run on the chunk's edge bound).  The centres mu_k are torch.linspace(0, rc, NB)'s
+// fp32 values (step k from the start in the lower half, rc - step (NB - 1 - k) in the upper half) and coeff is the
+// reference's -0.5 / (2 (mu_1 - mu_0))^2 rounded to fp32 (equiformer_v2_oc20.py:54-62): the basis is sharply peaked
+// (d exp / d d up to 30 per Angstrom), so a centre that is one ulp off moves a basis value by 1e-5 relative.
+#define EQ_RL_EPW 4
+template <int NCH>
+__global__ __launch_bounds__(256) void eq_radial_live_kernel(const float* __restrict__ e_vec, const int32_t* __restrict__ e_src,
+                                                             const int32_t* __restrict__ e_dst, const int32_t* __restrict__ eptr,
+                                                             const int32_t* __restrict__ Z, const float* __restrict__ w0t,
+                                                             const float* __restrict__ pair0, const float* __restrict__ ln_w,
+                                                             const float* __restrict__ ln_b, int n0, int n1, int EC, int NB,
+                                                             int NE, float rc, float delta, float coeff, long long Eub,
+                                                             float* __restrict__ out, int32_t* flags) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const long long e0 = eptr[n0], e1 = eptr[n1];
+    const float tmax = sqrtf(104.0f / -coeff);
+    for (int i = 0; i < EQ_RL_EPW; ++i) {
+        const long long slot = ((long long)blockIdx.x * 4 + wave) * EQ_RL_EPW + i;
+        if (slot >= Eub) return;
+        float* orow = out + (size_t)slot * EC;
+        const long long e = e0 + slot;
+        int zs = 0, zt = 0;
+        bool live = e < e1;
+        if (live) {
+            zs = Z[e_src[e]]; zt = Z[e_dst[e]];
+            if (zs < 0 || zs >= NE || zt < 0 || zt >= NE) {
+                if (lane == 0) atomicExch(&flags[4], 1);
+                live = false;
+            }
+        }
+        if (!live) {
+#pragma unroll
+            for (int q = 0; q < NCH; ++q) if (lane + 64 * q < EC) orow[lane + 64 * q] = 0.f;
+            continue;
+        }
+        const float vx = e_vec[3 * e], vy = e_vec[3 * e + 1], vz = e_vec[3 * e + 2];
+        const float dist = sqrtf(vx * vx + vy * vy + vz * vz);
+        int k0 = (int)ceilf((dist - tmax) / delta), k1 = (int)floorf((dist + tmax) / delta);
+        k0 = max(k0, 0); k1 = min(k1, NB - 1);
+        k1 = min(k1, k0 + 63);   // (the window holds at most 58 functions)
+        float gl = 0.f;
+        if (k0 + lane <= k1) {
+            const int k = k0 + lane;
+            const float mu = k < NB / 2 ? delta * (float)k : rc - delta * (float)(NB - 1 - k);
+            const float t = dist - mu;
+            gl = expf(coeff * (t * t));
+        }
+        const float* pr = pair0 + ((size_t)zs * NE + zt) * EC;
+        float acc[NCH];
+#pragma unroll
+        for (int q = 0; q < NCH; ++q) acc[q] = lane + 64 * q < EC ? pr[lane + 64 * q] : 0.f;
+#pragma unroll 4
+        for (int k = k0; k <= k1; ++k) {
+            const float g = __shfl(gl, k - k0);
+            const float* wr = w0t + (size_t)k * EC + lane;
+#pragma unroll
+            for (int q = 0; q < NCH; ++q) if (lane + 64 * q < EC) acc[q] += g * wr[64 * q];
+        }
+        float sum = 0.f;
+#pragma unroll
+        for (int q = 0; q < NCH; ++q) sum += acc[q];   // (lanes past EC hold zeros)
+        const float mean = eq_wave_sum(sum) / EC;
+        float var = 0.f;
+#pragma unroll
+        for (int q = 0; q < NCH; ++q) if (lane + 64 * q < EC) { const float t = acc[q] - mean; var += t * t; }
+        const float rstd = rsqrtf(eq_wave_sum(var) / EC + 1e-5f);
+#pragma unroll
+        for (int q = 0; q < NCH; ++q) {
+            const int c = lane + 64 * q;
+            if (c < EC) orow[c] = eq_silu((acc[q] - mean) * rstd * ln_w[c] + ln_b[c]);
+        }
+    }
+}
+
+int32_t eq_launch_radial_live_raw(const float* e_vec, const int32_t* e_src, const int32_t* e_dst, const int32_t* eptr,
+                                  const int32_t* Z, const eq_radial* r, int n0, int n1, long long Eub, int EC, int NB, int NE,
+                                  float rc, float* out, int32_t* flags, hipStream_t s) {
+    if (Eub <= 0) return ADF_OK;
+    if (!r->pair0 || !r->w0t) { adf_set_error("eqv2: the first radial layer's pair table is not bound"); return ADF_EINVAL; }
+    const dim3 grid((unsigned)((Eub + 4 * EQ_RL_EPW - 1) / (4 * EQ_RL_EPW))), block(256);
+    const int nch = (EC + 63) / 64;
+    const float delta = rc / (float)(NB - 1);   // mu_1 - mu_0 of torch.linspace in fp32
+    const float coeff = (float)(-0.5 / (((double)(2.0f * delta)) * ((double)(2.0f * delta))));
+#define EQ_RL_LAUNCH(NCH_)                                                                                               \
+    hipLaunchKernelGGL(eq_radial_live_kernel<NCH_>, grid, block, 0, s, e_vec, e_src, e_dst, eptr, Z, r->w0t, r->pair0,   \
+                       r->ln1_w, r->ln1_b, n0, n1, EC, NB, NE, rc, delta, coeff, Eub, out, flags)
+    if (nch <= 1) EQ_RL_LAUNCH(1);
+    else if (nch <= 2) EQ_RL_LAUNCH(2);
+    else if (nch <= 4) EQ_RL_LAUNCH(4);
+    else if (nch <= 8) EQ_RL_LAUNCH(8);
+    else if (nch <= 16) EQ_RL_LAUNCH(16);
+    else { adf_set_error("eqv2: edge_channels > 1024"); return ADF_EINVAL; }
+#undef EQ_RL_LAUNCH
+    ADF_HIP_CHECK(hipGetLastError());
+    return ADF_OK;
+}
+
+int32_t eq_launch_radial_live(const adf_eqv2* h, const eq_radial* r, const int32_t* Z, int n0, int n1, float* out,
+                              hipStream_t s) {
+    return eq_launch_radial_live_raw(h->e_vec, h->e_src, h->e_dst, h->eptr, Z, r, n0, n1, eq_edge_bound(h, n1 - n0), h->d.EC,
+                                     h->d.NB, h->hp.max_num_elements, h->hp.max_radius, out, h->flags, s);
+}
+
+// Energy head, second layer and the per-system sum (equiformer_v2_oc20.py:517-548).  With use_grid_mlp and use_sep_s2_act
+// only the gating scalars reach the l = 0 output of energy_block (transformer_block.py:473-530): per atom
+// e_i = w2 . hid_i + b2 with hid = SiLU(scalar_mlp.0(x[:, 0, :])) (a dense product, eq_forward_impl).  One workgroup per
+// system, no atomics: a wave per atom (lanes over the hidden units, butterfly sum), then ONE thread adds the atoms in
+// index order, divides by avg_num_nodes and adds energy_lin_ref[Z] atom by atom, as index_add_ does on the reference's
+// CPU path - a system's energy depends on its own rows only.
+__global__ __launch_bounds__(256) void eq_energy_sum_kernel(const float* __restrict__ hid, const float* __restrict__ w2,
+                                                            const float* __restrict__ b2, const int32_t* __restrict__ atom_offset,
+                                                            const int32_t* __restrict__ Z, const float* __restrict__ lin_ref,
+                                                            int NE, int F, float avg_num_nodes, float* __restrict__ energy) {
+    __shared__ float se[4];
+    const int b = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int a0 = atom_offset[b], a1 = atom_offset[b + 1];
+    float tot = 0.f;
+    for (int base = a0; base < a1; base += 4) {
+        const int i = base + wave;
+        if (i < a1) {
+            const float* hr = hid + (size_t)i * F;
+            float p = 0.f;
+            for (int j = lane; j < F; j += 64) p += w2[j] * hr[j];
+            p = eq_wave_sum(p) + b2[0];
+            if (lane == 0) se[wave] = p;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0)
+            for (int w = 0; w < 4 && base + w < a1; ++w) tot += se[w];
+        __syncthreads();
+    }
+    if (threadIdx.x != 0) return;
+    float E = tot / avg_num_nodes;
+    if (lin_ref)
+        for (int i = a0; i < a1; ++i) { const int z = Z[i]; if (z >= 0 && z < NE) E += lin_ref[z]; }
+    energy[b] = E;
+}
+
+int32_t eq_launch_energy_sum(const adf_eqv2* h, const float* hid, const adf_batch* b, float* energy, hipStream_t s) {
+    hipLaunchKernelGGL(eq_energy_sum_kernel, dim3(b->num_systems), dim3(256), 0, s, hid, h->eh_w2, h->eh_b2, b->atom_offset,
+                       b->atomic_numbers, h->eh_lin_ref, h->hp.max_num_elements, h->d.F, h->eh_avg_num_nodes, energy);
     ADF_HIP_CHECK(hipGetLastError());
     return ADF_OK;
 }

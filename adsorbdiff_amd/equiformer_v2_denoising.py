@@ -43,6 +43,27 @@ _ATOMIC_RADII_PM = [
 ]
 
 
+# Construction mode of the parameter containers below.  False (the denoiser mirror): every container initialises its
+# weights as it is built.  True (``reference_construction``, used by the S2EF mirror of equiformer_v2_oc20.py): a
+# container draws exactly what the reference's constructor of the same name draws and nothing more, and the model runs
+# the reference's two re-initialisation passes (equiformer_v2_oc20.py:411-412) afterwards - so the global generator is
+# consumed as in the reference and ``torch.manual_seed(s); Model(...)`` gives the reference's weights.
+_REFERENCE_CONSTRUCTION = False
+
+
+class reference_construction:
+    """Context manager: build the containers with the reference's constructor-time draws only (see above)."""
+
+    def __enter__(self):
+        global _REFERENCE_CONSTRUCTION
+        self._prev, _REFERENCE_CONSTRUCTION = _REFERENCE_CONSTRUCTION, True
+
+    def __exit__(self, *exc):
+        global _REFERENCE_CONSTRUCTION
+        _REFERENCE_CONSTRUCTION = self._prev
+        return False
+
+
 class SiLU(nn.Module):
     """Parameter-free placeholder so that Sequential indices match the reference."""
 
@@ -62,9 +83,10 @@ class RadialFunction(nn.Module):
             if i == 0:
                 continue
             lin = nn.Linear(c_in, channels_list[i], bias=True)
-            std = 1 / math.sqrt(c_in)
-            nn.init.uniform_(lin.weight, -std, std)
-            nn.init.constant_(lin.bias, 0)
+            if not _REFERENCE_CONSTRUCTION:
+                std = 1 / math.sqrt(c_in)
+                nn.init.uniform_(lin.weight, -std, std)
+                nn.init.constant_(lin.bias, 0)
             mods.append(lin)
             c_in = channels_list[i]
             if i == len(channels_list) - 1:
@@ -80,9 +102,11 @@ class SO3_LinearV2(nn.Module):
     def __init__(self, in_features: int, out_features: int, lmax: int, normal: bool) -> None:
         super().__init__()
         self.in_features, self.out_features, self.lmax = in_features, out_features, lmax
-        self.weight = nn.Parameter(torch.empty(lmax + 1, out_features, in_features))
+        # (the reference's constructor draws randn, then uniform: so3.py:708-712)
+        self.weight = nn.Parameter(torch.randn(lmax + 1, out_features, in_features) if _REFERENCE_CONSTRUCTION
+                                   else torch.empty(lmax + 1, out_features, in_features))
         bound = 1 / math.sqrt(in_features)
-        if normal:
+        if normal and not _REFERENCE_CONSTRUCTION:
             nn.init.normal_(self.weight, 0, bound)
         else:
             nn.init.uniform_(self.weight, -bound, bound)
@@ -91,6 +115,10 @@ class SO3_LinearV2(nn.Module):
 
 def _linear(c_in: int, c_out: int, bias: bool, normal: bool, scale: float = 1.0) -> nn.Linear:
     lin = nn.Linear(c_in, c_out, bias=bias)
+    if _REFERENCE_CONSTRUCTION:   # the default draws (and so2_ops.py's 1/sqrt2); the model's passes follow
+        if scale != 1.0:
+            lin.weight.data.mul_(scale)
+        return lin
     if normal:
         nn.init.normal_(lin.weight, 0, 1 / math.sqrt(c_in))
     elif scale != 1.0:
@@ -138,9 +166,10 @@ class SO2EquivariantGraphAttention(nn.Module):
     def __init__(self, sphere_channels, hidden_channels, num_heads, alpha_channels, value_channels, output_channels, lmax,
                  mmax, max_num_elements, edge_channels_list, normal: bool) -> None:
         super().__init__()
-        self.alpha_dot = nn.Parameter(torch.empty(num_heads, alpha_channels))
         std = 1.0 / math.sqrt(alpha_channels)
-        nn.init.uniform_(self.alpha_dot, -std, std)
+        if not _REFERENCE_CONSTRUCTION:
+            self.alpha_dot = nn.Parameter(torch.empty(num_heads, alpha_channels))
+            nn.init.uniform_(self.alpha_dot, -std, std)
         self.source_embedding = nn.Embedding(max_num_elements, edge_channels_list[-1])
         self.target_embedding = nn.Embedding(max_num_elements, edge_channels_list[-1])
         nn.init.uniform_(self.source_embedding.weight.data, -0.001, 0.001)
@@ -150,6 +179,9 @@ class SO2EquivariantGraphAttention(nn.Module):
         self.so2_conv_1 = SO2_Convolution(2 * sphere_channels, hidden_channels, lmax, mmax, normal,
                                           extra_m0=num_heads * alpha_channels + hidden_channels, rad_channels=rad)
         self.alpha_norm = nn.LayerNorm(alpha_channels)
+        if _REFERENCE_CONSTRUCTION:   # the reference draws it here: randn, then uniform (transformer_block.py:178-183)
+            self.alpha_dot = nn.Parameter(torch.randn(num_heads, alpha_channels))
+            nn.init.uniform_(self.alpha_dot, -std, std)
         self.so2_conv_2 = SO2_Convolution(hidden_channels, num_heads * value_channels, lmax, mmax, normal)
         self.proj = SO3_LinearV2(num_heads * value_channels, output_channels, lmax, normal)
 
@@ -193,10 +225,121 @@ class EdgeDegreeEmbedding(nn.Module):
         self.rad_func = RadialFunction(rad + [(lmax + 1) * sphere_channels])
 
 
-class EquiformerV2S_OC20_DenoisingPos(nn.Module):
-    """See module docstring.  ``num_atoms, bond_feat_dim, num_targets`` are accepted and ignored like the reference."""
+def unsupported_configuration(lmax_list, mmax_list, norm_type, attn_activation, ffn_activation, use_s2_act_attn,
+                              use_attn_renorm, use_gate_act, use_grid_mlp, use_sep_s2_act, use_atom_edge_embedding,
+                              share_atom_edge_embedding, use_m_share_rad, distance_function, grid_resolution, weight_init) -> list:
+    """What of the architecture switches lies outside the shipped configuration (module docstring), as a list of needs."""
+    bad = []
+    if len(lmax_list) != 1 or len(mmax_list) != 1: bad.append("one resolution (len(lmax_list) == 1)")
+    if norm_type != "layer_norm_sh": bad.append("norm_type='layer_norm_sh'")
+    if attn_activation != "silu" or ffn_activation != "silu": bad.append("attn_activation = ffn_activation = 'silu'")
+    if use_s2_act_attn or not use_attn_renorm or use_gate_act or not use_grid_mlp or not use_sep_s2_act:
+        bad.append("use_s2_act_attn=False, use_attn_renorm=True, use_gate_act=False, use_grid_mlp=True, use_sep_s2_act=True")
+    if not use_atom_edge_embedding or share_atom_edge_embedding or use_m_share_rad:
+        bad.append("use_atom_edge_embedding=True, share_atom_edge_embedding=False, use_m_share_rad=False")
+    if distance_function != "gaussian": bad.append("distance_function='gaussian'")
+    if grid_resolution is None: bad.append("an explicit grid_resolution")
+    if weight_init not in ("normal", "uniform"): bad.append("weight_init in {'normal', 'uniform'}")
+    return bad
+
+
+class EqV2Host(nn.Module):
+    """What the host mirrors of the EquiformerV2 family share (this denoiser and the S2EF model of
+    ``equiformer_v2_oc20.py``): the reference's introspection methods, the constant-buffer rule of ``load_state_dict``
+    and the device-side engine bound to the module's weights.  A subclass sets the hyper-parameter attributes the engine
+    reads and ``_engine = _engine_key = None``."""
 
     NUM_GAUSSIANS = 600  # equiformer_v2_oc20.py:251-262: fixed, whatever ``num_distance_basis`` says
+    _OPTIONAL_KEYS = ()  # parameters a checkpoint may omit (constant tables)
+
+    # ------------------------------------------------------------------ API
+    @property
+    def num_params(self) -> int:
+        return sum(p.numel() for p in self.parameters())
+
+    def no_weight_decay(self) -> set:
+        """Reference: equiformer_v2_oc20.py:597-621: biases and norm weights of Linear / SO3_LinearV2 / LayerNorm / the
+        equivariant norm."""
+        out = []
+        for mname, mod in self.named_modules():
+            if isinstance(mod, (nn.Linear, SO3_LinearV2, nn.LayerNorm, EquivariantLayerNormArraySphericalHarmonics)):
+                for pname, _ in mod.named_parameters(recurse=False):
+                    if isinstance(mod, (nn.Linear, SO3_LinearV2)) and "weight" in pname:
+                        continue
+                    out.append(mname + "." + pname)
+        return set(out)
+
+    # constant buffers of the reference's modules (functions of the hyper-parameters only; rebuilt by the engine):
+    # S2 grid matrices (so3.py:566-599), CoefficientMapping tables (so3.py:22-115), SO3_LinearV2.expand_index
+    # (so3.py:694-745), the equivariant norm's balance_degree_weight (layer_norm.py), GaussianSmearing.offset
+    _CONST_BUFFER_SUFFIXES = ("to_grid_mat", "from_grid_mat", "expand_index", "balance_degree_weight",
+                              "distance_expansion.offset", "l_harmonic", "m_harmonic", "m_complex", "res_size", "m_size",
+                              "to_m")
+
+    def load_state_dict(self, state_dict, strict: bool = True):
+        """Reference checkpoints also carry constant buffers (S2 grid matrices, index tables, Gaussian offsets): they are
+        functions of the hyper-parameters and are rebuilt here, so exactly THOSE keys are ignored.  Under ``strict`` any
+        other unexpected key (a checkpoint of another configuration: more blocks, ``energy_embedding.*`` ...), any missing
+        parameter and any shape mismatch raises, like ``nn.Module.load_state_dict``.  ``atom_radii`` (a frozen Parameter
+        in the reference, equiformer_v2_denoising.py:165-169) is loaded when present and may be absent: it is a constant
+        table."""
+        own = self.state_dict()
+        const = {k for k in state_dict if k not in own and k.endswith(self._CONST_BUFFER_SUFFIXES)}
+        unexpected = sorted(k for k in state_dict if k not in own and k not in const)
+        missing = sorted(k for k in own if k not in state_dict and k not in self._OPTIONAL_KEYS)
+        mismatched = sorted(k for k in own if k in state_dict and tuple(state_dict[k].shape) != tuple(own[k].shape))
+        if strict and (unexpected or missing or mismatched):
+            def head(v):
+                return f"{v[:6]}{'...' if len(v) > 6 else ''}"
+            raise RuntimeError(f"Error(s) in loading state_dict for {self.__class__.__name__}: "
+                               + (f"unexpected keys {head(unexpected)}; " if unexpected else "")
+                               + (f"missing keys {head(missing)}; " if missing else "")
+                               + (f"size mismatch for {head(mismatched)}" if mismatched else ""))
+        kept = {k: v for k, v in state_dict.items() if k in own and k not in mismatched}
+        res = super().load_state_dict(kept, strict=False)
+        from torch.nn.modules.module import _IncompatibleKeys
+
+        return _IncompatibleKeys([k for k in res.missing_keys if k not in self._OPTIONAL_KEYS] + mismatched, unexpected)
+
+    def engine(self, device=None):
+        from .eqv2_engine import EqV2Engine
+
+        if device is None:
+            device = self.sphere_embedding.weight.device
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if self._engine is not None and self._engine.device != device:
+            self._engine.close()
+            self._engine = None
+        version = self._weights_version()
+        if self._engine is None:
+            self._engine = EqV2Engine(self, device)
+            self._engine_key = version
+        elif self._engine_key != version:
+            self._engine.bind_weights()
+            self._engine_key = version
+        return self._engine
+
+    def _weights_version(self):
+        """Key of the weight images the engine derives (transposed first radial layers, fp16 hi/lo splits):
+        (data_ptr, _version) per tensor plus a content fingerprint that also catches writes through ``param.data`` —
+        what the reference's EMA copy_to / restore do (modules/exponential_moving_average.py:113,147)."""
+        tensors = list(self.parameters())
+        key = tuple((t.data_ptr(), t._version) for t in tensors)
+        flat = [t.detach().reshape(-1) for t in tensors if t.is_cuda and t.dtype == torch.float32 and t.numel() > 0]
+        if not flat:
+            return key
+        with torch.no_grad():
+            bits = torch.cat(flat).view(torch.int32)
+            fp = int(bits.sum(dtype=torch.int64).item()) ^ int((bits[::7].sum(dtype=torch.int64) * 31).item())
+        return key + (fp,)
+
+
+class EquiformerV2S_OC20_DenoisingPos(EqV2Host):
+    """See module docstring.  ``num_atoms, bond_feat_dim, num_targets`` are accepted and ignored like the reference."""
+
+    _OPTIONAL_KEYS = ("atom_radii",)   # a frozen Parameter in the reference (equiformer_v2_denoising.py:165-169): a constant
 
     def __init__(
         self,
@@ -212,21 +355,14 @@ class EquiformerV2S_OC20_DenoisingPos(nn.Module):
         energy_encoding=None, sampling=False,
     ) -> None:
         super().__init__()
-        bad = []
-        if len(lmax_list) != 1 or len(mmax_list) != 1: bad.append("one resolution (len(lmax_list) == 1)")
-        if norm_type != "layer_norm_sh": bad.append("norm_type='layer_norm_sh'")
-        if attn_activation != "silu" or ffn_activation != "silu": bad.append("attn_activation = ffn_activation = 'silu'")
-        if use_s2_act_attn or not use_attn_renorm or use_gate_act or not use_grid_mlp or not use_sep_s2_act:
-            bad.append("use_s2_act_attn=False, use_attn_renorm=True, use_gate_act=False, use_grid_mlp=True, use_sep_s2_act=True")
-        if not use_atom_edge_embedding or share_atom_edge_embedding or use_m_share_rad:
-            bad.append("use_atom_edge_embedding=True, share_atom_edge_embedding=False, use_m_share_rad=False")
-        if distance_function != "gaussian": bad.append("distance_function='gaussian'")
-        if grid_resolution is None: bad.append("an explicit grid_resolution")
+        bad = unsupported_configuration(lmax_list, mmax_list, norm_type, attn_activation, ffn_activation, use_s2_act_attn,
+                                        use_attn_renorm, use_gate_act, use_grid_mlp, use_sep_s2_act, use_atom_edge_embedding,
+                                        share_atom_edge_embedding, use_m_share_rad, distance_function, grid_resolution,
+                                        weight_init)
         if not (use_pbc and otf_graph and regress_forces and enforce_max_neighbors_strictly):
             bad.append("use_pbc = otf_graph = regress_forces = enforce_max_neighbors_strictly = True")
         if not FOR_denoising: bad.append("FOR_denoising=True (two force blocks)")
         if energy_encoding not in (None, "scalar"): bad.append("energy_encoding in {None, 'scalar'}")
-        if weight_init not in ("normal", "uniform"): bad.append("weight_init in {'normal', 'uniform'}")
         if bad:
             raise ValueError("the HIP EquiformerV2 path implements the shipped configuration only; needs " + "; ".join(bad))
         self.use_pbc, self.regress_forces, self.otf_graph = use_pbc, regress_forces, otf_graph
@@ -271,89 +407,6 @@ class EquiformerV2S_OC20_DenoisingPos(nn.Module):
         self.atom_radii = nn.Parameter(radii, requires_grad=False)  # in pm, like the reference (:165-169)
         self._engine = None
         self._engine_key = None
-
-    # ------------------------------------------------------------------ API
-    @property
-    def num_params(self) -> int:
-        return sum(p.numel() for p in self.parameters())
-
-    def no_weight_decay(self) -> set:
-        """Reference: equiformer_v2_oc20.py:597-621: biases and norm weights of Linear / SO3_LinearV2 / LayerNorm / the
-        equivariant norm."""
-        out = []
-        for mname, mod in self.named_modules():
-            if isinstance(mod, (nn.Linear, SO3_LinearV2, nn.LayerNorm, EquivariantLayerNormArraySphericalHarmonics)):
-                for pname, _ in mod.named_parameters(recurse=False):
-                    if isinstance(mod, (nn.Linear, SO3_LinearV2)) and "weight" in pname:
-                        continue
-                    out.append(mname + "." + pname)
-        return set(out)
-
-    # constant buffers of the reference's modules (functions of the hyper-parameters only; rebuilt by the engine):
-    # S2 grid matrices (so3.py:566-599), CoefficientMapping tables (so3.py:22-115), SO3_LinearV2.expand_index
-    # (so3.py:694-745), the equivariant norm's balance_degree_weight (layer_norm.py), GaussianSmearing.offset
-    _CONST_BUFFER_SUFFIXES = ("to_grid_mat", "from_grid_mat", "expand_index", "balance_degree_weight",
-                              "distance_expansion.offset", "l_harmonic", "m_harmonic", "m_complex", "res_size", "m_size",
-                              "to_m")
-
-    def load_state_dict(self, state_dict, strict: bool = True):
-        """Reference checkpoints also carry constant buffers (S2 grid matrices, index tables, Gaussian offsets): they are
-        functions of the hyper-parameters and are rebuilt here, so exactly THOSE keys are ignored.  Under ``strict`` any
-        other unexpected key (a checkpoint of another configuration: more blocks, ``energy_embedding.*`` ...), any missing
-        parameter and any shape mismatch raises, like ``nn.Module.load_state_dict``.  ``atom_radii`` (a frozen Parameter
-        in the reference, equiformer_v2_denoising.py:165-169) is loaded when present and may be absent: it is a constant
-        table."""
-        own = self.state_dict()
-        const = {k for k in state_dict if k not in own and k.endswith(self._CONST_BUFFER_SUFFIXES)}
-        unexpected = sorted(k for k in state_dict if k not in own and k not in const)
-        missing = sorted(k for k in own if k not in state_dict and k != "atom_radii")
-        mismatched = sorted(k for k in own if k in state_dict and tuple(state_dict[k].shape) != tuple(own[k].shape))
-        if strict and (unexpected or missing or mismatched):
-            def head(v):
-                return f"{v[:6]}{'...' if len(v) > 6 else ''}"
-            raise RuntimeError("Error(s) in loading state_dict for EquiformerV2S_OC20_DenoisingPos: "
-                               + (f"unexpected keys {head(unexpected)}; " if unexpected else "")
-                               + (f"missing keys {head(missing)}; " if missing else "")
-                               + (f"size mismatch for {head(mismatched)}" if mismatched else ""))
-        kept = {k: v for k, v in state_dict.items() if k in own and k not in mismatched}
-        res = super().load_state_dict(kept, strict=False)
-        from torch.nn.modules.module import _IncompatibleKeys
-
-        return _IncompatibleKeys([k for k in res.missing_keys if k != "atom_radii"] + mismatched, unexpected)
-
-    def engine(self, device=None):
-        from .eqv2_engine import EqV2Engine
-
-        if device is None:
-            device = self.sphere_embedding.weight.device
-        device = torch.device(device)
-        if device.type == "cuda" and device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        if self._engine is not None and self._engine.device != device:
-            self._engine.close()
-            self._engine = None
-        version = self._weights_version()
-        if self._engine is None:
-            self._engine = EqV2Engine(self, device)
-            self._engine_key = version
-        elif self._engine_key != version:
-            self._engine.bind_weights()
-            self._engine_key = version
-        return self._engine
-
-    def _weights_version(self):
-        """Key of the weight images the engine derives (transposed first radial layers, fp16 hi/lo splits):
-        (data_ptr, _version) per tensor plus a content fingerprint that also catches writes through ``param.data`` —
-        what the reference's EMA copy_to / restore do (modules/exponential_moving_average.py:113,147)."""
-        tensors = list(self.parameters())
-        key = tuple((t.data_ptr(), t._version) for t in tensors)
-        flat = [t.detach().reshape(-1) for t in tensors if t.is_cuda and t.dtype == torch.float32 and t.numel() > 0]
-        if not flat:
-            return key
-        with torch.no_grad():
-            bits = torch.cat(flat).view(torch.int32)
-            fp = int(bits.sum(dtype=torch.int64).item()) ^ int((bits[::7].sum(dtype=torch.int64) * 31).item())
-        return key + (fp,)
 
     def forward(self, data):
         """data: pos [N,3] f32, atomic_numbers [N], batch [N], natoms [B], cell [B,3,3] (+ energy [B] for the conditional

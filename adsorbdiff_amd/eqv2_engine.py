@@ -1,4 +1,5 @@
-"""Device-side engine of the EquiformerV2 denoiser: owns the ``adf_eqv2`` handle, hands over the constant SO(3) tables
+"""Device-side engine of the EquiformerV2 denoiser and of the S2EF force field built from the same blocks
+(``equiformer_v2_oc20.EquiformerV2_OC20``: ``forward_energy``): owns the ``adf_eqv2`` handle, hands over the constant SO(3) tables
 (so3_math.py) and the module's parameters, and enqueues forward calls on torch's current HIP stream; the stepper and
 sampling calls are ``engine.Engine``'s, shared with ``PaiNNEngine``.  PyTorch is plumbing here; nothing in this file
 computes a model output on the host.
@@ -50,6 +51,17 @@ def weight_names(num_layers: int, mmax: int) -> List[str]:
     return names
 
 
+def s2ef_weight_names(num_layers: int, mmax: int) -> List[str]:
+    """The table order of ``adf_eqv2_set_weights_s2ef``: the denoiser's table without ``atom_radii`` and without
+    ``force_block2``."""
+    return [n for n in weight_names(num_layers, mmax)[1:] if not n.startswith("force_block2.")]
+
+
+# energy_block entries the energy reaches (adf_eqv2_set_energy_head); row 0 of so3_linear_2.weight[0] is sliced out
+ENERGY_HEAD_NAMES = ["energy_block.scalar_mlp.0.weight", "energy_block.scalar_mlp.0.bias",
+                     "energy_block.so3_linear_2.weight", "energy_block.so3_linear_2.bias"]
+
+
 class EqV2Engine(Engine):
     PROFILE_CATEGORIES = ("graph", "radial", "rotate", "so2_conv", "s2_act", "attn_weights", "node", "ffn_grid", "stepper")
     SYMBOLS = dict(set_moving="adf_eqv2_set_moving", check_flags="adf_eqv2_check_flags",
@@ -62,6 +74,9 @@ class EqV2Engine(Engine):
 
     def __init__(self, model, device) -> None:
         super().__init__(model, device)
+        self.s2ef = bool(getattr(model, "s2ef", False))
+        if self.s2ef:
+            self.num_heads = 1 if model.regress_forces else 0
         self.lmax, self.mmax = int(model.lmax_list[0]), int(model.mmax_list[0])
         hp = _lib.EqV2Hparams(
             lmax=self.lmax, mmax=self.mmax, num_layers=model.num_layers, sphere_channels=model.sphere_channels,
@@ -85,15 +100,40 @@ class EqV2Engine(Engine):
         self.bind_weights()
 
     # ------------------------------------------------------------------ weights
+    def _tensor(self, sd, n: str) -> torch.Tensor:
+        t = sd[n].detach()
+        _require_gpu(t, f"parameter {n}")
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            t = t.to(torch.float32).contiguous()
+        return t
+
+    def _bind_s2ef(self) -> None:
+        """The S2EF model: its table (no radii, one force block) and the energy head."""
+        m = self.model
+        sd = dict(m.named_parameters())
+        names = s2ef_weight_names(m.num_layers, self.mmax)
+        if not m.regress_forces:   # no force block: the first block's tensors as placeholders; forces = NULL reads none
+            if m.num_layers < 1:
+                raise ValueError("an energy-only EquiformerV2 needs at least one block")
+            names = [n.replace("force_block.", "blocks.0.ga.") for n in names]
+        out = [self._tensor(sd, n) for n in names]
+        ptrs = (C.c_void_p * len(out))(*[w.data_ptr() for w in out])
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.adf_eqv2_set_weights_s2ef(self.handle, len(out), ptrs, self._stream()))
+        head = [self._tensor(sd, n) for n in ENERGY_HEAD_NAMES]
+        head[2] = head[2][0, 0].contiguous()   # so3_linear_2.weight [L+1, 1, F]: the l = 0 row
+        ref = self._tensor(sd, "energy_lin_ref") if m.use_energy_lin_ref else None
+        self._weights_keepalive = out + head + ([ref] if ref is not None else [])
+        hptrs = (C.c_void_p * 4)(*[w.data_ptr() for w in head])
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.adf_eqv2_set_energy_head(self.handle, 4, hptrs, float(m.avg_num_nodes),
+                                                         ref.data_ptr() if ref is not None else None, self._stream()))
+
     def bind_weights(self) -> None:
+        if self.s2ef:
+            return self._bind_s2ef()
         sd = dict(self.model.named_parameters())
-        out = []
-        for n in weight_names(self.model.num_layers, self.mmax):
-            t = sd[n].detach()
-            _require_gpu(t, f"parameter {n}")
-            if t.dtype != torch.float32 or not t.is_contiguous():
-                t = t.to(torch.float32).contiguous()
-            out.append(t)
+        out = [self._tensor(sd, n) for n in weight_names(self.model.num_layers, self.mmax)]
         self._weights_keepalive = out
         ptrs = (C.c_void_p * len(out))(*[w.data_ptr() for w in out])
         with torch.cuda.device(self.device):
@@ -178,7 +218,35 @@ class EqV2Engine(Engine):
                 self.handle, C.byref(desc), f1.data_ptr(), f2.data_ptr() if f2 is not None else None,
                 x_blocks.data_ptr() if x_blocks is not None else None, self._stream()))
 
+    def forward_energy_prepared(self, prep: PreparedBatch, pos: torch.Tensor, energy: torch.Tensor,
+                                forces: Optional[torch.Tensor], x_blocks: Optional[torch.Tensor] = None) -> None:
+        """Enqueue one S2EF forward (``adf_eqv2_forward_energy``): energy [B], forces [N,3] (None: the force block is not
+        evaluated); no host synchronisation."""
+        desc = prep.desc(pos)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.adf_eqv2_forward_energy(
+                self.handle, C.byref(desc), energy.data_ptr(), forces.data_ptr() if forces is not None else None,
+                x_blocks.data_ptr() if x_blocks is not None else None, self._stream()))
+
+    def forward_energy(self, data, return_blocks: bool = False):
+        """S2EF forward -> (energy [B], forces [N,3] | None) (+ the block embeddings with ``return_blocks``)."""
+        if not self.s2ef:
+            raise RuntimeError("forward_energy: this engine is bound to the denoiser (no energy head)")
+        prep = self.prepare(data)
+        pos = data.pos.to(torch.float32).contiguous()
+        energy = torch.empty(prep.num_systems, dtype=torch.float32, device=self.device)
+        forces = torch.empty(prep.num_atoms, 3, dtype=torch.float32, device=self.device) if self.num_heads else None
+        xb = None
+        if return_blocks:
+            xb = torch.empty(self.model.num_layers + 1, prep.num_atoms, (self.lmax + 1) ** 2, self.model.sphere_channels,
+                             dtype=torch.float32, device=self.device)
+        self.forward_energy_prepared(prep, pos, energy, forces, xb)
+        self.check_flags()
+        return (energy, forces, xb) if return_blocks else (energy, forces)
+
     def forward(self, data, return_blocks: bool = False):
+        if self.s2ef:
+            raise RuntimeError("forward: the S2EF model has one force block and an energy head; use forward_energy")
         prep = self.prepare(data)
         self.bind_condition(data, prep.num_systems)
         pos = data.pos.to(torch.float32).contiguous()

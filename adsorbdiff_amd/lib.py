@@ -34,6 +34,7 @@ EXPORTS = (
     "adf_op_linear_fwd", "adf_op_linear_bwd_scratch", "adf_op_linear_bwd", "adf_op_ssilu_fwd", "adf_op_ssilu_bwd", "adf_op_layernorm_fwd", "adf_op_layernorm_bwd", "adf_op_embed_fwd", "adf_op_embed_bwd", "adf_op_rbf", "adf_op_message_fwd", "adf_op_message_fwd_fused", "adf_op_message_bwd", "adf_op_message_bwd_fused", "adf_op_message_bwd_fused_supported", "adf_op_message_bwd_perm", "adf_op_edge_owner", "adf_op_rbf_image_bytes", "adf_op_rbf_image", "adf_op_rbf_wgrad_fused_scratch", "adf_op_rbf_wgrad_fused", "adf_op_vdot_fwd", "adf_op_vdot_bwd", "adf_op_update_out_fwd", "adf_op_update_out_bwd", "adf_op_vnorm_fwd", "adf_op_vnorm_bwd", "adf_op_gate_fwd", "adf_op_gate_bwd", "adf_op_copy_rows", "adf_op_score_loss", "adf_op_sqnorm_accumulate", "adf_op_adamw_step",
     "adf_eqv2_create", "adf_eqv2_destroy", "adf_eqv2_set_constants", "adf_eqv2_set_weights", "adf_eqv2_set_arithmetic",
     "adf_eqv2_set_energy_embedding", "adf_eqv2_set_system_energy",
+    "adf_eqv2_set_weights_s2ef", "adf_eqv2_set_energy_head", "adf_eqv2_forward_energy", "adf_eqv2_radial_first_layer",
     "adf_eqv2_set_edges", "adf_eqv2_set_moving", "adf_eqv2_set_incremental", "adf_eqv2_forward", "adf_eqv2_forward_subset", "adf_eqv2_check_flags", "adf_eqv2_init_placement",
     "adf_eqv2_sde_step", "adf_eqv2_sample", "adf_eqv2_sample_traj", "adf_eqv2_tr_step", "adf_eqv2_tr_sample", "adf_eqv2_tr_sample_traj", "adf_eqv2_linear_forward", "adf_eqv2_get_counters", "adf_eqv2_profile_enable", "adf_eqv2_profile_read",
     "adf_last_error", "adf_version",
@@ -198,6 +199,10 @@ def load():
         "adf_eqv2_set_constants": [vp, vp, vp, vp, vp, vp],
         "adf_eqv2_set_weights": [vp, i32, C.POINTER(vp), vp],
         "adf_eqv2_set_arithmetic": [vp, i32],
+        "adf_eqv2_set_weights_s2ef": [vp, i32, C.POINTER(vp), vp],
+        "adf_eqv2_set_energy_head": [vp, i32, C.POINTER(vp), C.c_float, vp, vp],
+        "adf_eqv2_forward_energy": [vp, C.POINTER(BatchDesc), vp, vp, vp, vp],
+        "adf_eqv2_radial_first_layer": [vp, i32, i64, vp, vp, vp, vp, vp, vp],
         "adf_eqv2_set_energy_embedding": [vp, vp, vp, vp],
         "adf_eqv2_set_system_energy": [vp, vp, i32, vp],
         "adf_eqv2_set_edges": [vp, i64, vp, vp, vp, i32, vp],

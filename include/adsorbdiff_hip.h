@@ -591,6 +591,41 @@ int32_t adf_eqv2_get_counters(adf_eqv2_t h, adf_eqv2_counters* out, void* stream
 int32_t adf_eqv2_profile_enable(adf_eqv2_t h, int32_t on);
 int32_t adf_eqv2_profile_read(adf_eqv2_t h, float* ms, int64_t* count, void* stream);
 
+/* ---- EquiformerV2 S2EF force field (models/equiformer_v2/equiformer_v2_oc20.py:415-562, class EquiformerV2_OC20): the
+ * denoiser's handle and forward with (1) no atomic radii - edge distances enter the Gaussian basis as they are, so the
+ * basis is live on every edge and no radial function is tabulated per element pair; (2) one force block; (3) an energy
+ * head.  Atomic numbers are valid in [0, max_num_elements).
+ *
+ * adf_eqv2_set_weights_s2ef binds the S2EF table: the table of adf_eqv2_set_weights WITHOUT entry 0 (atom_radii) and
+ * WITHOUT the trailing force_block2 (ATTN) entries; everything else in the same order.  It also tabulates, per radial
+ * function, the element-embedding part of the first layer, b0 + W_s semb[Z_s] + W_t temb[Z_t], per element pair
+ * ([max_num_elements^2, edge_channels]); every forward then evaluates per edge only the window of Gaussians that do not
+ * underflow (at most 58 of the 600), fused with the LayerNorm + SiLU that follows.  adf_eqv2_set_weights on the same
+ * handle switches back to the denoiser. */
+int32_t adf_eqv2_set_weights_s2ef(adf_eqv2_t h, int32_t n_weights, const void* const* weights, void* stream);
+
+/* The energy head.  With use_grid_mlp and use_sep_s2_act only the gating scalars reach the l = 0 output of energy_block
+ * (transformer_block.py:473-530), so per atom e = w2 . SiLU(W1 x[:, 0, :] + b1) + b2.  DEVICE float32 tensors, read by
+ * pointer on every forward (the first is also split into its fp16 hi/lo image here: bind again after changing it):
+ *   0 energy_block.scalar_mlp.0.weight [F, C]  1 energy_block.scalar_mlp.0.bias [F]
+ *   2 row 0 of energy_block.so3_linear_2.weight[0] [F]  3 energy_block.so3_linear_2.bias [1]
+ * energy_lin_ref: [max_num_elements] device table added per atom (use_energy_lin_ref), or NULL. */
+int32_t adf_eqv2_set_energy_head(adf_eqv2_t h, int32_t n_weights, const void* const* w, float avg_num_nodes,
+                                 const float* energy_lin_ref, void* stream);
+
+/* S2EF forward: energy [B] = (sum_i e_i) / avg_num_nodes (+ energy_lin_ref[Z_i] atom by atom), forces [N,3] = the l = 1
+ * coefficients of force_block (NULL: the force block is not evaluated), x_blocks as adf_eqv2_forward (may be NULL).  The
+ * per-system sum runs in a fixed order (one workgroup per system, no atomics): a system's energy is bit-identical
+ * whatever batch it sits in.  adf_eqv2_forward on an S2EF handle needs f2 = NULL. */
+int32_t adf_eqv2_forward_energy(adf_eqv2_t h, const adf_batch* b, float* energy, float* forces, float* x_blocks,
+                                void* stream);
+
+/* Unit-test hook: the S2EF model's first radial layer + LayerNorm + SiLU of radial function `which` (0 edge-degree
+ * embedding, 1..num_layers the blocks, num_layers + 1 the force block) on a caller's edges: src / dst [E] index Z,
+ * vec [E,3], out [E, edge_channels]; device pointers.  Synchronises. */
+int32_t adf_eqv2_radial_first_layer(adf_eqv2_t h, int32_t which, int64_t num_edges, const int32_t* src, const int32_t* dst,
+                                    const float* vec, const int32_t* Z, float* out, void* stream);
+
 /* ---- S2EF PaiNN (models/painn/painn.py:52-432): the denoiser's handle with one force head (num_heads = 1, or 0 for
  * regress_forces=False) plus the energy head out_energy = Linear(H, H/2), ScaledSiLU, Linear(H/2, 1), summed per system.
  * adf_painn_set_weights keeps its table; the energy head is bound separately, in this order:
