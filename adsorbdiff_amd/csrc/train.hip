@@ -608,7 +608,11 @@ extern "C" int32_t adf_op_ssilu_bwd(const float* h, const float* dy, float* dh, 
     return ADF_OK;
 }
 
-// LayerNorm (eps 1e-5, biased variance), one wave per row; stats[row] = (mean, rstd)
+// LayerNorm (eps 1e-5, biased variance), one wave per row; stats[row] = (mean, rstd).
+// Corrected two-pass moments: the float32 mean m0 of a row that sits far from zero (mean 1e4, unit spread) is off by up to
+// an ulp of the MEAN, which is 1e-3 of the spread; the deviations x - m0 are exact there, so their own mean cm is that
+// residual: the variance is mean(d^2) - cm^2 and xhat = (d - cm) rstd.  The backward forms the same residual from the stored
+// mean, so a row's xhat does not depend on how well one float holds its mean.
 __global__ __launch_bounds__(256) void tr_ln_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                          const float* __restrict__ b, float* __restrict__ y,
                                                          float2* __restrict__ stats, int N, int H) {
@@ -617,12 +621,13 @@ __global__ __launch_bounds__(256) void tr_ln_fwd_kernel(const float* __restrict_
     const float* xr = x + (size_t)row * H;
     float s = 0.f;
     for (int c = lane; c < H; c += 64) s += xr[c];
-    const float mean = tr_wsum(s) / (float)H;
-    float q = 0.f;
-    for (int c = lane; c < H; c += 64) { const float d = xr[c] - mean; q += d * d; }
-    const float rstd = 1.0f / sqrtf(tr_wsum(q) / (float)H + 1e-5f);
-    for (int c = lane; c < H; c += 64) y[(size_t)row * H + c] = (xr[c] - mean) * rstd * w[c] + b[c];
-    if (lane == 0) stats[row] = make_float2(mean, rstd);
+    const float m0 = tr_wsum(s) / (float)H;
+    float q = 0.f, r = 0.f;
+    for (int c = lane; c < H; c += 64) { const float d = xr[c] - m0; q += d * d; r += d; }
+    const float cm = tr_wsum(r) / (float)H;
+    const float rstd = 1.0f / sqrtf(fmaxf(tr_wsum(q) / (float)H - cm * cm, 0.f) + 1e-5f);
+    for (int c = lane; c < H; c += 64) y[(size_t)row * H + c] = ((xr[c] - m0) - cm) * rstd * w[c] + b[c];
+    if (lane == 0) stats[row] = make_float2(m0 + cm, rstd);
 }
 // dx += rstd * (g - mean(g) - xhat * mean(g * xhat)), g = dy * w;  per-row partial sums of dw, db go to part[blocks][2H]
 __global__ __launch_bounds__(256) void tr_ln_bwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
@@ -638,17 +643,20 @@ __global__ __launch_bounds__(256) void tr_ln_bwd_kernel(const float* __restrict_
         const float2 st = stats[row];
         const float* xr = x + (size_t)row * H;
         const float* gr = dy + (size_t)row * H;
-        float s1 = 0.f, s2 = 0.f;
+        // one pass for the three row sums: with d = x - mean, sum(g xhat) = rstd (sum(g d) - cm sum(g)), cm = mean(d)
+        float s1 = 0.f, s2 = 0.f, r = 0.f;
         for (int c = lane; c < H; c += 64) {
-            const float xh = (xr[c] - st.x) * st.y, g = gr[c] * w[c];
-            s1 += g; s2 += g * xh;
+            const float d = xr[c] - st.x, g = gr[c] * w[c];
+            s1 += g; s2 += g * d; r += d;
+        }
+        const float cm = tr_wsum(r) / (float)H;
+        s1 = tr_wsum(s1) / (float)H;
+        s2 = (tr_wsum(s2) / (float)H - cm * s1) * st.y;
+        for (int c = lane; c < H; c += 64) {
+            const float xh = ((xr[c] - st.x) - cm) * st.y, g = gr[c] * w[c];
+            dx[(size_t)row * H + c] += st.y * (g - s1 - xh * s2);
             mine[c] += gr[c] * xh;   // dw
             mine[H + c] += gr[c];    // db
-        }
-        s1 = tr_wsum(s1) / (float)H; s2 = tr_wsum(s2) / (float)H;
-        for (int c = lane; c < H; c += 64) {
-            const float xh = (xr[c] - st.x) * st.y, g = gr[c] * w[c];
-            dx[(size_t)row * H + c] += st.y * (g - s1 - xh * s2);
         }
     }
     __syncthreads();

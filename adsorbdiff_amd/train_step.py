@@ -94,6 +94,14 @@ class PaiNNTrainStep:
         # nothing per edge and the weight-gradient kernel forms d(rbfh) again while it stages its product);
         # ADF_TRAIN_RBF_WGRAD=materialised: the round-4 path (d(rbfh) written by the backward, read by adf_op_linear_bwd)
         self.rbf_wgrad_fused = os.environ.get("ADF_TRAIN_RBF_WGRAD", "fused") != "materialised"
+        # basis sizes the step's kernels take, checked here and not in the middle of a step: the fused message kernels
+        # stage the basis in blocks of 8, and without them the projection rbfh = rbf W^T is a product over num_rbf, which
+        # csrc/gemm.hip takes in blocks of 32 (the handle itself accepts any even num_rbf <= 128)
+        R = int(model.num_rbf)
+        if R % 32 != 0 and (R % 8 != 0 or not self.fused_message_backward):
+            raise NotImplementedError(
+                f"the training step needs num_rbf to be a multiple of 32 (a multiple of 8 with the fused message "
+                f"backward), got {R}")
 
     # ------------------------------------------------------------------ helpers
     def _params(self) -> Dict[str, torch.nn.Parameter]:

@@ -174,7 +174,7 @@ def radial_basis(d: torch.Tensor, cutoff: float, num_rbf: int = 128, p: int = 5)
     a, b, c = -(pf + 1) * (pf + 2) / 2, pf * (pf + 2), -pf * (pf + 1) / 2
     env = 1 + a * x**pf + b * x ** (pf + 1) + c * x ** (pf + 2)
     env = torch.where(x < 1, env, torch.zeros_like(x))
-    mu = torch.linspace(0.0, 1.0, num_rbf)
+    mu = torch.linspace(0.0, 1.0, num_rbf, dtype=d.dtype)
     coeff = -0.5 / (1.0 / (num_rbf - 1)) ** 2
     return env[:, None] * torch.exp(coeff * torch.pow(x[:, None] - mu[None, :], 2))
 
@@ -260,7 +260,7 @@ def painn_forward(
     edge_index, _, dist, unit_vec = graph
     rbf = radial_basis(dist, cutoff, num_rbf)
     x = sd["atom_emb.embeddings.weight"][z - 1]
-    vec = torch.zeros(x.shape[0], 3, H)
+    vec = torch.zeros(x.shape[0], 3, H, dtype=x.dtype)
     if scale_factors is None:
         scale_factors = [float(sd.get("upd_out_scalar_scale_%d.scale_factor" % i, 0.0)) or 1.0 for i in range(num_layers)]
     if capture is not None:

@@ -331,3 +331,112 @@ def test_linear_backward_weight_gradient_kernels_vs_torch(mode):
     assert res.returncode == 0, res.stderr[-2000:]
     worst = float(res.stdout.strip().split("WORST")[-1])
     assert worst < 1e-5, worst
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The whole step at adversarial shapes against the float64 oracle (tests/helpers_train.py: torch.autograd through
+# oracle/painn_oracle.py in float64 on the graph the engine exports).  The fixtures above share one shape of batch
+# (equal systems, H in {128, 512}, R = 128, >= 2 layers); the table reaches ragged batches, B = 1, a 1-atom and a 70-atom
+# adsorbate, self-image edges, an empty CSR segment, a hub above 256 incoming edges, both graph paths in one backward,
+# H = 192 / R = 96 / R = 32 and a single layer.
+_FORMS = {
+    "default": {},
+    "rbf_wgrad_materialised": {"ADF_TRAIN_RBF_WGRAD": "materialised"},
+    "msg_bwd_plain": {"ADF_TRAIN_MSG_BWD": "plain"},
+}
+
+
+def _config_names():
+    from tests import helpers_train as HT
+
+    return list(HT.CONFIGS)
+
+
+@pytest.mark.parametrize("form", list(_FORMS))
+@pytest.mark.parametrize("name", _config_names())
+def test_step_at_adversarial_shapes_vs_float64_oracle(name, form, monkeypatch):
+    """Loss, its terms and both heads' outputs within 1e-5 of float64, every parameter's gradient within 1e-4 relative
+    (the parity budget of the fixture tests), out_energy.* without a gradient, embedding rows of absent elements exactly
+    zero, a second accumulating call doubles every gradient to 1e-6; in the three backward forms."""
+    from tests import helpers_train as HT
+
+    for k in ("ADF_TRAIN_RBF_WGRAD", "ADF_TRAIN_MSG_BWD", "ADF_TRAIN_MSG"):
+        monkeypatch.delenv(k, raising=False)
+    for k, v in _FORMS[form].items():
+        monkeypatch.setenv(k, v)
+    figs = HT.measure_configuration(name, DEV)
+    print(HT.describe(figs, form))
+    HT.assert_configuration(figs, form)
+
+
+_EXACT_F32_SCRIPT = r"""
+import json, sys, torch
+sys.path.insert(0, {root!r})
+from tests import helpers_train as HT
+for name in HT.CONFIGS:
+    figs = HT.measure_configuration(name, "cuda:0")
+    print("FIGS " + json.dumps(figs), flush=True)
+"""
+
+
+def test_step_at_adversarial_shapes_with_the_exact_f32_products():
+    """The same table once under ADF_TRAIN_GEMM=f32 and ADF_WGRAD=f32 (the exact-f32 products and weight-gradient kernel;
+    both switches are read once per process, hence the child, which prints its figures for this process to assert)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from pathlib import Path
+
+    from tests import helpers_train as HT
+
+    root = str(Path(__file__).resolve().parent.parent)
+    env = dict(os.environ, ADF_TRAIN_GEMM="f32", ADF_WGRAD="f32")
+    for k in ("ADF_TRAIN_RBF_WGRAD", "ADF_TRAIN_MSG_BWD", "ADF_TRAIN_MSG"):
+        env.pop(k, None)
+    res = subprocess.run([sys.executable, "-c", _EXACT_F32_SCRIPT.format(root=root)], env=env, capture_output=True, text=True,
+                         timeout=900)
+    assert res.returncode == 0, res.stderr[-3000:]
+    seen = []
+    for line in res.stdout.splitlines():
+        if line.startswith("FIGS "):
+            figs = json.loads(line[5:])
+            print(HT.describe(figs, "exact f32 products"))
+            HT.assert_configuration(figs, "exact f32 products")
+            seen.append(figs["name"])
+    assert seen == list(HT.CONFIGS)
+
+
+@pytest.mark.parametrize("form", list(_FORMS))
+@pytest.mark.parametrize("num_rbf", [24, 30, 36])
+def test_basis_sizes_outside_the_fused_kernels_reach_parity_or_are_refused_cleanly(num_rbf, form, monkeypatch):
+    """The handle accepts any even num_rbf <= 128, the fused message kernels stage the basis in blocks of 8 and
+    csrc/gemm.hip refuses a product over K not divisible by 32.  The contract: the step either reaches parity, or raises
+    before anything is written into a param.grad - never wrong numbers, never half-accumulated gradients."""
+    from tests import helpers_train as HT
+
+    for k in ("ADF_TRAIN_RBF_WGRAD", "ADF_TRAIN_MSG_BWD", "ADF_TRAIN_MSG"):
+        monkeypatch.delenv(k, raising=False)
+    for k, v in _FORMS[form].items():
+        monkeypatch.setenv(k, v)
+    name = "basis_%d" % num_rbf
+    HT.CONFIGS.setdefault(name, dict(HT.CONFIGS["ragged"], R=num_rbf))
+    try:
+        m, bd, targets, ref, tables = HT.device_case(name, DEV)   # (the engine is created here: api.hip accepts the size)
+        for p in m.parameters():
+            p.grad = None
+        try:
+            step = PaiNNTrainStep(m, DEV, igso3=tables)
+            step.zero_grad()
+            step.loss_and_grad(bd, targets)
+        except (NotImplementedError, RuntimeError) as exc:
+            torch.cuda.synchronize()
+            for k, p in m.named_parameters():
+                assert p.grad is None or float(p.grad.abs().max()) == 0.0, (k, "gradient written before the refusal")
+            print(f"num_rbf = {num_rbf} [{form}]: refused cleanly ({type(exc).__name__}: {exc})")
+            return
+        figs = HT.measure_configuration(name, DEV)
+        print(HT.describe(figs, form))
+        HT.assert_configuration(figs, form)
+    finally:
+        HT.CONFIGS.pop(name, None)
