@@ -222,6 +222,7 @@ extern "C" int32_t adf_painn_destroy(adf_painn_t h) {
     if (h->w16_bias_perm) (void)hipFree(h->w16_bias_perm);
     if (h->w16_scratch) (void)hipFree(h->w16_scratch);
     if (h->oe0_buf) (void)hipFree(h->oe0_buf);
+    adf_grad_free(h);
     if (h->prof_ev) { for (hipEvent_t e : *h->prof_ev) (void)hipEventDestroy(e); delete h->prof_ev; }
     delete h->prof_cat;
     delete h;
@@ -313,6 +314,7 @@ extern "C" int32_t adf_painn_set_weights(adf_painn_t h, int32_t n_weights, const
     h->weights_set = true;
     h->rec0_valid = false;
     h->inc_valid = false;
+    adf_grad_invalidate(h);
     return ADF_OK;
 }
 
@@ -396,6 +398,7 @@ static int32_t read_flags(adf_painn* h, hipStream_t s) {
     if (f[2]) { adf_set_error("edge buffer overflow"); return ADF_EOVERFLOW; }
     if (f[3]) { adf_set_error("an atom has more than %d incoming edges", ADF_MAX_INDEG); return ADF_EOVERFLOW; }
     if (f[1]) { adf_set_error("An image has no neighbors"); return ADF_ENONEIGHBOR; }
+    if (f[6]) { adf_set_error("energy gradient: an edge row has no reverse row in its partner's segment (asymmetric graph)"); return ADF_EINVAL; }
     if (f[5]) {
         adf_set_error("non-finite model output%s", h->gemm_f32 ? " (exact-f32 arithmetic: the inputs or weights are not finite)"
                       : " in f16x3 arithmetic: an activation left the fp16 range or the inputs are not finite; "
@@ -941,6 +944,7 @@ extern "C" int32_t adf_painn_set_energy_head(adf_painn_t h, int32_t n_weights, c
     ADF_TRY(adf_split_weight(h->oe0_w, (long long)n, &e, reinterpret_cast<unsigned int*>(h->oe0_buf + n * 4 + 16),
                              (hipStream_t)stream));
     h->energy_set = true;
+    adf_grad_invalidate(h);
     return ADF_OK;
 }
 
@@ -980,6 +984,13 @@ __global__ __launch_bounds__(256) void adf_energy_sum_kernel(const float* __rest
     if (threadIdx.x == 0) energy[b] = __fadd_rn(__fadd_rn(part[0], part[1]), __fadd_rn(part[2], part[3]));
 }
 
+int32_t adf_energy_sum(const float* y, int H2, const float* w, const float* bias, const int32_t* atom_offset, float* energy,
+                       int num_systems, hipStream_t s) {
+    hipLaunchKernelGGL(adf_energy_sum_kernel, dim3(num_systems), dim3(256), 0, s, y, H2, w, bias, atom_offset, energy);
+    ADF_HIP_CHECK(hipGetLastError());
+    return ADF_OK;
+}
+
 // energy [B] (and forces [N,3] unless the model has no force head: forces may be NULL then)
 extern "C" int32_t adf_painn_forward_energy(adf_painn_t h, const adf_batch* b, float* energy, float* forces, void* stream) {
     ADF_TRY(check_batch(h, b));
@@ -993,9 +1004,7 @@ extern "C" int32_t adf_painn_forward_energy(adf_painn_t h, const adf_batch* b, f
     adf_prof_begin(h, ADF_PROF_HEADS, s);
     // h->y is free once the force head has run ([capN, H] >= [N, H/2])
     ADF_TRY(adf_linear(h, h->x_last, H, h->oe0_w, &h->oe0_16, h->oe0_b, h->y, H2, N, H2, H, 1, s));
-    hipLaunchKernelGGL(adf_energy_sum_kernel, dim3(b->num_systems), dim3(256), 0, s, h->y, H2, h->oe2_w, h->oe2_b,
-                       b->atom_offset, energy);
-    ADF_HIP_CHECK(hipGetLastError());
+    ADF_TRY(adf_energy_sum(h->y, H2, h->oe2_w, h->oe2_b, b->atom_offset, energy, b->num_systems, s));
     adf_prof_end(h, s);
     return ADF_OK;
 }

@@ -147,7 +147,8 @@ struct adf_painn {
     float4* e_geom;      // [capE] (ux,uy,uz,d): unit vector target->source, distance
     // device int32[8], STICKY (only adf_check_flags / adf_graph_build(num_edges) / adf_graph_set_moving clear them):
     // {0 candidate overflow, 1 empty image, 2 edge overflow, 3 in-degree beyond the sorter, 4 atomic number out of
-    //  range, 5 non-finite or fp16-range-exceeding activation (gemm16.hip), 6-7 unused}
+    //  range, 5 non-finite or fp16-range-exceeding activation (gemm16.hip), 6 an edge row without its reverse row
+    //  (energy_grad.hip), 7 unused}
     int32_t* flags;
     float *x, *vecA, *vecB, *y, *xh, *vv, *cat, *dot;  // node buffers
     float* rec;          // [(N+1)][H/32][160] gather records of the message kernel (message.hip)
@@ -200,6 +201,7 @@ struct adf_painn {
     bool energy_set;
     const float* x_last;      // node features entering the heads of the last full forward (h->x or the kept incX[L])
     float dist_floor;         // edge distances at or below it are set to it (adf_painn_set_distance_floor, default 1e-3)
+    void* grad;               // energy_grad.hip: transposed weight images and workspaces of adf_painn_forward_energy_gradient
     // last graph
     int64_t lastN, lastB;
     int32_t last_reps[3];
@@ -249,6 +251,16 @@ int32_t adf_launch_mlp16(const float* A1, const float* A2, int lda, const float*
                          const float* bias0, const void* W2f, const adf_w16* W2, int M, int H, int epi, const adf_epi* ep,
                          hipStream_t s);
 int32_t adf_graph_build_impl(adf_painn* h, const adf_batch* b, hipStream_t s);
+// api.hip: energy[b] = sum over the system's atoms of (y[a] . w + bias), fixed order (adf_energy_sum_kernel)
+int32_t adf_energy_sum(const float* y, int H2, const float* w, const float* bias, const int32_t* atom_offset, float* energy,
+                       int num_systems, hipStream_t s);
+// energy_grad.hip: state of adf_painn_forward_energy_gradient (invalidate: the bound weights changed)
+void adf_grad_invalidate(adf_painn* h);
+void adf_grad_free(adf_painn* h);
+// message_geo.hip: per-edge-row (dE/dd, dE/du) of a message block, see the kernel comment
+bool adf_message_geo_supported(const adf_painn* h);
+int32_t adf_message_geo(adf_painn* h, int layer, const float* xh, const float* vec, bool vec_is_zero, float4* part,
+                        long long ecap, bool accumulate, hipStream_t s);
 // incremental.hip
 size_t adf_inc_temp_bytes(int64_t n);
 int32_t adf_inc_compare(adf_painn* h, int N, hipStream_t s);  // inc_c0 from (nptr, e_src, e_geom) vs prev_*

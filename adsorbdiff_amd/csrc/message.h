@@ -35,5 +35,5 @@ struct MsgParams {
     int env_pi;
     unsigned long long* kcount;  // optional: sum over 32-row blocks of contracted k length x 32-column blocks run (profiling)
 };
-
-
+// message_bwd.hip: gradient records of (d(x1), d(vec1)) into h->rec; dx (optional) = d(x1) / sqrt2
+int32_t adf_pack_grad_records(adf_painn* h, const float* gx1, const float* gv1, float* dx, hipStream_t s);

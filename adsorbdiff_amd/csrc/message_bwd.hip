@@ -378,6 +378,20 @@ __global__ void adf_pack_grad_records_kernel(const float* __restrict__ gx1, cons
     }
 }
 
+// h->rec <- the gradient records of (gx1, gv1) for the graph's N atoms, row N zeroed (padded edge rows gather it); dx as above.
+// Shared with the edge-geometry kernel (message_geo.hip), which gathers the same records.
+int32_t adf_pack_grad_records(adf_painn* h, const float* gx1, const float* gv1, float* dx, hipStream_t s) {
+    const int N = (int)h->lastN, H = h->hp.hidden_channels;
+    const size_t row = (size_t)(H / 32) * 160;
+    ADF_HIP_CHECK(hipMemsetAsync(h->rec + (size_t)N * row, 0, sizeof(float) * row, s));   // padded edge rows gather record N
+    long long blocks = ((long long)N * H + 255) / 256;
+    if (blocks > 256 * 16) blocks = 256 * 16;
+    hipLaunchKernelGGL(adf_pack_grad_records_kernel, dim3((unsigned)blocks), dim3(256), 0, s, gx1, gv1, h->rec, dx, N, H,
+                       0.70710678118654752f, 1.0f / sqrtf((float)H));
+    ADF_HIP_CHECK(hipGetLastError());
+    return ADF_OK;
+}
+
 static size_t msgb_lds_bytes() {
     return (size_t)2 * MSG_COLS * MSG_LDK * 2 + sizeof(float) * (MSG_COLS + 128 + MSG_WAVES * 32 * 8) + 16;
 }
@@ -427,14 +441,7 @@ extern "C" int32_t adf_op_message_bwd_fused(adf_painn_t h, int32_t layer, const 
             ADF_HIP_CHECK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)msgb_lds_bytes()));
         attr_set = true;
     }
-    const size_t row = (size_t)(H / 32) * 160;
-    ADF_HIP_CHECK(hipMemsetAsync(h->rec + (size_t)N * row, 0, sizeof(float) * row, s));   // padded edge rows gather record N
-    {
-        long long blocks = ((long long)N * H + 255) / 256;
-        if (blocks > 256 * 16) blocks = 256 * 16;
-        hipLaunchKernelGGL(adf_pack_grad_records_kernel, dim3((unsigned)blocks), dim3(256), 0, s, gx1, gv1, h->rec, dx, N, H,
-                           0.70710678118654752f, 1.0f / sqrtf((float)H));
-    }
+    ADF_TRY(adf_pack_grad_records(h, gx1, gv1, dx, s));
     MsgBwdParams pb;
     MsgParams& p = pb.m;
     memset(&pb, 0, sizeof(pb));

@@ -399,6 +399,39 @@ class PaiNNEngine(Engine):
             self.check_flags()
         return energy, forces
 
+    def forward_energy_gradient_prepared(self, prep: PreparedBatch, pos: torch.Tensor, energy: torch.Tensor,
+                                         forces: torch.Tensor) -> None:
+        """Enqueue one evaluation of the energy [B] and of forces [N,3] = -dE/dpos, the gradient of that energy with the
+        edge set held fixed (``adf_painn_forward_energy_gradient``: what ``torch.autograd.grad(energy.sum(), pos)`` gives
+        on the reference); no host synchronisation.  Works without a force head."""
+        desc = prep.desc(pos)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.adf_painn_forward_energy_gradient(
+                self.handle, C.byref(desc), energy.data_ptr(), forces.data_ptr(), self._stream()))
+
+    def forward_energy_gradient(self, data):
+        """-> (energy [B], forces [N,3] = -dE/dpos).  Same error protocol as ``forward_energy``: a non-finite value in
+        f16x3 arithmetic re-runs in exact f32, out of memory is a ``RuntimeError`` (``ml_relax`` then halves the batch)."""
+        prep = self.prepare(data)
+        pos = data.pos.to(torch.float32).contiguous()
+        energy = torch.empty(prep.num_systems, dtype=torch.float32, device=self.device)
+        forces = torch.empty(prep.num_atoms, 3, dtype=torch.float32, device=self.device)
+        self.forward_energy_gradient_prepared(prep, pos, energy, forces)
+        try:
+            self.check_flags()
+        except _lib.NumericRangeError:
+            if not self.use_exact_f32():
+                raise
+            self.forward_energy_gradient_prepared(prep, pos, energy, forces)
+            self.check_flags()
+        return energy, forces
+
+    def energy_gradient_workspace_bytes(self, num_atoms: int) -> int:
+        """Device memory the library holds for ``forward_energy_gradient`` on a batch of ``num_atoms`` atoms."""
+        n = C.c_int64(0)
+        _lib.check(self.lib.adf_painn_energy_gradient_workspace(self.handle, int(num_atoms), C.byref(n)))
+        return int(n.value)
+
     def set_fused_mlp(self, mode: int = 2) -> None:
         """Form of the x_proj / xvec_proj pairs (adf_painn_set_fused_mlp): 0 two kernels per pair, 1 the fused two-layer
         kernel (csrc/mlp16.hip), 2 by size (default).  Bit-identical results."""

@@ -26,6 +26,7 @@ EXPORTS = (
     "adf_sde_init_placement", "adf_sde_step", "adf_sde_step_scheduled", "adf_sample", "adf_sample_traj",
     "adf_tr_step", "adf_tr_sample", "adf_tr_sample_traj",
     "adf_painn_set_energy_head", "adf_painn_set_distance_floor", "adf_painn_forward_energy",
+    "adf_painn_forward_energy_gradient", "adf_painn_energy_gradient_workspace",
     "adf_lbfgs_create", "adf_lbfgs_destroy", "adf_lbfgs_reset", "adf_lbfgs_converge", "adf_lbfgs_step",
     "adf_lbfgs_get_mask", "adf_lbfgs_last_step_max",
     "adf_frames_create", "adf_frames_destroy", "adf_frames_push", "adf_frames_wait", "adf_frames_release", "adf_frames_pushed", "adf_frames_abort",
@@ -148,6 +149,8 @@ def load():
         "adf_painn_set_energy_head": [vp, i32, C.POINTER(vp), vp],
         "adf_painn_set_distance_floor": [vp, C.c_float],
         "adf_painn_forward_energy": [vp, C.POINTER(BatchDesc), vp, vp, vp],
+        "adf_painn_forward_energy_gradient": [vp, C.POINTER(BatchDesc), vp, vp, vp],
+        "adf_painn_energy_gradient_workspace": [vp, i64, C.POINTER(i64)],
         "adf_lbfgs_create": [i64, i32, i32, C.c_double, C.c_double, C.c_double, i32, C.POINTER(vp)],
         "adf_lbfgs_destroy": [vp],
         "adf_lbfgs_reset": [vp, vp],

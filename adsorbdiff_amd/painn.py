@@ -10,6 +10,13 @@ summed per system (painn.py:412-414) next to one direct-force ``PaiNNOutput`` he
 runs in the HIP library through the denoiser's engine (``engine.PaiNNEngine``, shared through ``PaiNNHost``, the common
 base of both mirrors; this class is not a denoiser) with one force head plus the energy head
 (``adf_painn_forward_energy``).  There is no eager / CPU fallback.
+
+Forces come in two ways, chosen by ``force_mode``: ``"direct"`` (default) returns the force head's output as before;
+``"energy_gradient"`` returns ``-dE/dpos`` of the energy the same call reports (``adf_painn_forward_energy_gradient``; what
+``torch.autograd.grad(out["energy"].sum(), pos)`` gives on the reference with the edge set held fixed).  The second works
+without a force head (``regress_forces=False``).  It is not the reference's ``direct_forces=False`` branch
+(painn.py:421-429), which differentiates the sum of the last node embedding instead of the energy: the constructor keeps
+rejecting that.
 """
 from __future__ import annotations
 
@@ -28,6 +35,7 @@ class PaiNN(_pd.PaiNNHost):
 
     distance_floor = 1.0e-6   # painn.py:334-335 (the denoiser: 1e-3)
     energy_head = True        # PaiNNEngine binds out_energy and offers forward_energy
+    FORCE_MODES = ("direct", "energy_gradient")
 
     def __init__(
         self,
@@ -91,11 +99,26 @@ class PaiNN(_pd.PaiNNHost):
 
         self._engine = None
         self._engine_key = None
+        self._force_mode = "direct"
+
+    @property
+    def force_mode(self) -> str:
+        """``"direct"``: forces from the force head; ``"energy_gradient"``: forces = -dE/dpos of the reported energy."""
+        return self._force_mode
+
+    @force_mode.setter
+    def force_mode(self, mode: str) -> None:
+        if mode not in self.FORCE_MODES:
+            raise ValueError(f"force_mode must be one of {self.FORCE_MODES}, got {mode!r}")
+        self._force_mode = mode
 
     def forward(self, data):
         """data: pos[N,3] f32, atomic_numbers[N], batch[N], natoms[B], cell[B,3,3]
-        -> {"energy": [B], "forces": [N,3]} ({"energy"} only with regress_forces=False)."""
+        -> {"energy": [B], "forces": [N,3]} ({"energy"} only with regress_forces=False in the direct mode)."""
         eng = self.engine(data.pos.device)
+        if self._force_mode == "energy_gradient":
+            energy, forces = eng.forward_energy_gradient(data)
+            return {"energy": energy, "forces": forces}
         energy, forces = eng.forward_energy(data)
         out = {"energy": energy}
         if self.regress_forces:

@@ -277,11 +277,17 @@ class ForcesTrainer:
         try:
             out = self.model(data_loader.to(self.device) if hasattr(data_loader, "to") else data_loader)
             predictions = {}
+            # forces that are the gradient of the model's energy stay the gradient of the energy returned here: scaled by the
+            # energy normaliser's std (no mean), and the forces normaliser is not applied
+            gradient_forces = getattr(self._unwrapped_model, "force_mode", "direct") == "energy_gradient"
             for key in ("energy", "forces"):
                 if key not in out:
                     continue
                 pred = out[key]
-                if self.normalizers.get(key, False):
+                if key == "forces" and gradient_forces:
+                    if self.normalizers.get("energy", False):
+                        pred = torch.mul(pred, self.normalizers["energy"].std)
+                elif self.normalizers.get(key, False):
                     pred = self.normalizers[key].denorm(pred)
                 predictions[key] = pred.detach()
         finally:

@@ -643,6 +643,25 @@ int32_t adf_painn_set_distance_floor(adf_painn_t h, float floor);
  * order (one workgroup per system, no atomics): a system's energy is bit-identical whatever batch it sits in. */
 int32_t adf_painn_forward_energy(adf_painn_t h, const adf_batch* b, float* energy, float* forces, void* stream);
 
+/* Forces as the gradient of the energy: energy [B] and forces [N,3] = -dE/dpos with E = sum of the per-system energies and the
+ * edge set held fixed.  Replaces, for the S2EF PaiNN,
+ *     pos.requires_grad_(True); out = model(data); forces = -torch.autograd.grad(out["energy"].sum(), pos)[0]
+ * on the reference module (models/painn/painn.py:318-340, 380-414).  It is NOT the reference's direct_forces=False branch
+ * (painn.py:421-429), which differentiates the sum of the last node embedding x instead of the energy.  Works with
+ * num_heads == 0 (a model without a force head); the force head, if any, is not evaluated.  One call does the whole
+ * evaluation on `stream` without host synchronisation once the workspaces have grown: graph build, a forward that keeps
+ * 21 H floats per atom and layer, the data-gradient backward (no weight-gradient product; the transposed weight images are
+ * built once per adf_painn_set_weights / adf_painn_set_energy_head), the edge-geometry gradient of every message block and
+ * its reduction onto the atoms.  No float atomics: the result is run-to-run identical and a system's energy and forces do
+ * not depend on the batch it sits in.  The energy comes from the same per-system sum as adf_painn_forward_energy's but from
+ * an unfused ScaledSiLU, so the two may differ in the last bits.  Errors as adf_painn_forward_energy; ADF_EOOM when the
+ * workspace cannot be allocated (split the batch).  Flags: adf_check_flags. */
+int32_t adf_painn_forward_energy_gradient(adf_painn_t h, const adf_batch* b, float* energy, float* forces, void* stream);
+
+/* Bytes of library-owned device memory adf_painn_forward_energy_gradient holds for a batch of num_atoms atoms: activations,
+ * per-edge partial gradients (sized for either arithmetic), reverse-edge index and the images of the transposed weights. */
+int32_t adf_painn_energy_gradient_workspace(adf_painn_t h, int64_t num_atoms, int64_t* bytes);
+
 /* ---- Batched L-BFGS of ml_relax (relaxation/optimizers/lbfgs_torch.py:22-213), model-agnostic.  All state lives on the
  * device in fp64: s / y rings [memory, 3N], rho, alpha, r0, f0, q / z.  Dot products run over the whole flattened batch
  * (as in the reference: the systems of one batch are coupled) with fixed-order reductions and no atomics, so a relaxation

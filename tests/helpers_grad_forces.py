@@ -1,0 +1,122 @@
+"""Float64 oracle of the S2EF PaiNN's energy and of its gradient forces F = -dE/dpos (edge set held fixed), and the table
+of ragged configurations the GPU test (tests/test_gpu_grad_forces.py) runs beyond the fixtures.
+
+Built from the pieces of oracle/painn_oracle.py (``message_layer``, ``update_layer``, ``ssilu``, its ``radial_basis``
+restated here with the model's bound centres: plain
+PyTorch, pinned to the reference function by function) with the energy head added, and torch.autograd in float64.  The edge
+list is given (the engine's exported graph, or a fixture's reference graph): distances and unit vectors are re-derived from a
+float64 ``pos`` leaf, v = pos[src] - pos[dst] + offset with the per-edge periodic offset held constant, so ties in the K-th
+neighbour cannot enter.  tests/test_grad_forces_host.py checks this oracle against the reference's own float64 autograd
+(tests/golden/grad_forces.npz), so it is itself pinned to the reference."""
+import math
+
+import torch
+
+from adsorbdiff_amd.data import Batch
+from adsorbdiff_amd.painn import PaiNN
+from adsorbdiff_amd.synthetic import make_system
+from oracle import painn_oracle as O
+
+F = torch.nn.functional
+
+# name -> H, L, R, cutoff, K, systems (slab + adsorbate atoms); what each one reaches is in the comment
+CONFIGS = {
+    # unequal systems, a 1-atom adsorbate, self-image edges; atoms with fewer than 32 edge rows
+    "ragged": dict(H=128, L=2, R=128, cutoff=6.0, K=20, systems=((36, 4), (7, 1), (61, 3), (20, 2))),
+    # the only layer is the vec == 0 variant of the kernels
+    "one_layer": dict(H=128, L=1, R=128, cutoff=6.0, K=20, systems=((36, 4), (9, 2))),
+    # six layers, a narrower basis (zero-padded staging of the kernels' rbf_proj image)
+    "six_layers_r64": dict(H=128, L=6, R=64, cutoff=6.0, K=20, systems=((36, 4), (7, 1))),
+    # atoms with more than 64 edge rows (three and more 32-row blocks per atom), three channel slices
+    "many_rows": dict(H=192, L=2, R=128, cutoff=12.0, K=80, systems=((60, 4), (12, 1))),
+}
+SCALE_FACTORS = (1.05, 0.9, 1.1, 0.95, 1.02, 0.97)
+
+
+def make_config_batch(name):
+    cfg = CONFIGS[name]
+    g = torch.Generator().manual_seed(5151)
+    return Batch.from_data_list([make_system(g, n_slab, n_ads, sid=str(i)) for i, (n_slab, n_ads) in enumerate(cfg["systems"])])
+
+
+def make_config_model(name):
+    """The mirror S2EF PaiNN of a configuration on the CPU: seeded initialisers, biases and LayerNorm parameters moved off
+    their constants so that every term of the gradient is exercised."""
+    cfg = CONFIGS[name]
+    torch.manual_seed(9)
+    scales = {f"upd_out_scalar_scale_{i}": SCALE_FACTORS[i] for i in range(cfg["L"])}
+    m = PaiNN(None, 50, 1, hidden_channels=cfg["H"], num_layers=cfg["L"], num_rbf=cfg["R"], cutoff=cfg["cutoff"],
+              max_neighbors=cfg["K"], scale_file=scales).eval()
+    g = torch.Generator().manual_seed(10)
+    with torch.no_grad():
+        for n_, p_ in m.named_parameters():
+            if n_.endswith(".bias") or "x_layernorm.weight" in n_:
+                p_.add_(0.1 * torch.randn(p_.shape, generator=g))
+    return m
+
+
+def edge_offsets(pos, cell, batch, edge_src, edge_dst, edge_vec):
+    """Periodic offset of every edge: the edge vector minus the position difference, snapped to the lattice (integer
+    shifts), so that it is an exact constant of the differentiation; see ``shift_offsets``."""
+    pos, vec = pos.double(), edge_vec.double()
+    off = vec - (pos[edge_src] - pos[edge_dst])
+    c = cell.double()[batch[edge_dst]]
+    shifts = torch.linalg.solve(c.transpose(1, 2), off.unsqueeze(-1)).squeeze(-1).round()
+    return shift_offsets(shifts, cell, batch, edge_dst)
+
+
+def shift_offsets(shifts, cell, batch, edge_dst):
+    """shift @ cell in FLOAT32, then cast: the reference forms the offsets in float32 whatever the model's dtype
+    (utils/utils.py:526-529, ``cell_offsets.float() ... cell.float()``), and so does the engine's graph."""
+    return torch.bmm(shifts.float().unsqueeze(1), cell.float()[batch[edge_dst]]).squeeze(1).double()
+
+
+def radial_basis(d, cutoff, offset, p=5):
+    """oracle/painn_oracle.py::radial_basis with the model's bound Gaussian centres (the float32 buffer
+    ``radial_basis.rbf.offset``, as the engine and the reference's .double() both read it) instead of an exact linspace."""
+    x = d * (1 / cutoff)
+    pf = float(p)
+    a, b, c = -(pf + 1) * (pf + 2) / 2, pf * (pf + 2), -pf * (pf + 1) / 2
+    env = 1 + a * x**pf + b * x ** (pf + 1) + c * x ** (pf + 2)
+    env = torch.where(x < 1, env, torch.zeros_like(x))
+    coeff = -0.5 / (1.0 / (offset.numel() - 1)) ** 2
+    return env[:, None] * torch.exp(coeff * torch.pow(x[:, None] - offset[None, :], 2))
+
+
+def energy_forces(sd, pos, atomic_numbers, batch, num_systems, edge_src, edge_dst, offsets, *, hidden_channels, num_layers,
+                  num_rbf, cutoff, scale_factors, distance_floor=1.0e-6, **_):
+    """(energy [B], forces [N,3] = -d(energy.sum())/d(pos)) in float64.  ``sd``: state_dict of the S2EF PaiNN; messages
+    flow edge_src -> edge_dst; v = pos[src] - pos[dst] + offset (models/painn/painn.py:318-340, 380-414)."""
+    H = hidden_channels
+    sd = {k: v.double() for k, v in sd.items() if torch.is_floating_point(v)}
+    src, dst = edge_src.long(), edge_dst.long()
+    pos = pos.detach().double().clone().requires_grad_(True)
+    v = pos[src] - pos[dst] + offsets.double()
+    d = v.norm(dim=-1)
+    d = torch.where(d <= distance_floor, torch.full_like(d, distance_floor), d)
+    u = v / d[:, None]
+    rbf = radial_basis(d, cutoff, sd["radial_basis.rbf.offset"])
+    x = sd["atom_emb.embeddings.weight"][atomic_numbers.long() - 1]
+    vec = torch.zeros(x.shape[0], 3, H, dtype=torch.float64)
+    edge_index = torch.stack([src, dst])
+    for i in range(num_layers):
+        dx, dvec = O.message_layer(sd, "message_layers.%d." % i, x, vec, edge_index, rbf, u, H)
+        x = (x + dx) * (1 / math.sqrt(2.0))
+        vec = vec + dvec
+        dx, dvec = O.update_layer(sd, "update_layers.%d." % i, x, vec, H)
+        x = (x + dx) * float(scale_factors[i])
+        vec = vec + dvec
+    per_atom = F.linear(O.ssilu(F.linear(x, sd["out_energy.0.weight"], sd["out_energy.0.bias"])),
+                        sd["out_energy.2.weight"], sd["out_energy.2.bias"]).squeeze(1)
+    energy = torch.zeros(num_systems, dtype=torch.float64).index_add_(0, batch.long(), per_atom)
+    (g,) = torch.autograd.grad(energy.sum(), pos)
+    return energy.detach(), -g
+
+
+def engine_graph(model, data):
+    """(edge_src, edge_dst, edge_vec) of the engine's graph of ``data`` (on the device), on the CPU: source / neighbour,
+    target / segment owner, and the vector target -> source."""
+    eng = model.engine(data.pos.device)
+    eng.build_graph(data)
+    _, _, _, es, ed, dist, unit = eng.export_graph()
+    return es.cpu().long(), ed.cpu().long(), (unit * dist[:, None]).cpu()
