@@ -254,6 +254,13 @@ int32_t adf_graph_build_impl(adf_painn* h, const adf_batch* b, hipStream_t s);
 // api.hip: energy[b] = sum over the system's atoms of (y[a] . w + bias), fixed order (adf_energy_sum_kernel)
 int32_t adf_energy_sum(const float* y, int H2, const float* w, const float* bias, const int32_t* atom_offset, float* energy,
                        int num_systems, hipStream_t s);
+// ScaledSiLU f(x) = x sigmoid(x) / 0.6 and f'(x) w, as the energy head's backward evaluates them: the seed of the energy
+// gradient (energy_grad.hip) and adf_op_energy_head_bwd (s2ef_train.hip) share the one expression
+__device__ __forceinline__ float adf_ssilu(float x) { return x / (1.0f + expf(-x)) * 1.6666666666666667f; }
+__device__ __forceinline__ float adf_dssilu_times(float x, float w) {
+    const float sg = 1.0f / (1.0f + expf(-x));
+    return sg * (1.0f + x * (1.0f - sg)) * 1.6666666666666667f * w;
+}
 // energy_grad.hip: state of adf_painn_forward_energy_gradient (invalidate: the bound weights changed)
 void adf_grad_invalidate(adf_painn* h);
 void adf_grad_free(adf_painn* h);

@@ -108,9 +108,7 @@ __global__ void eg_seed_kernel(const float* __restrict__ he0, const float* __res
                                long long N, int H2) {
     for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < N * H2; t += (long long)gridDim.x * blockDim.x) {
         const int c = (int)(t % H2);
-        const float x = he0[t];
-        const float sg = 1.0f / (1.0f + expf(-x));
-        dhe[t] = sg * (1.0f + x * (1.0f - sg)) * 1.6666666666666667f * w2[c];
+        dhe[t] = adf_dssilu_times(he0[t], w2[c]);   // (shared with adf_op_energy_head_bwd, the dE != 1 case with weight gradients)
     }
 }
 

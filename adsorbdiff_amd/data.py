@@ -13,7 +13,7 @@ from typing import Iterable, List
 
 import torch
 
-_TENSOR_NODE_KEYS = ("pos", "atomic_numbers", "tags", "fixed", "force")
+_TENSOR_NODE_KEYS = ("pos", "atomic_numbers", "tags", "fixed", "force", "forces")
 _TENSOR_GRAPH_KEYS = ("cell", "natoms", "y", "energy", "pbc")
 
 

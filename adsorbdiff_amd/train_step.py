@@ -70,19 +70,26 @@ class _Ops:
         return dA
 
 
-class PaiNNTrainStep:
-    """loss + gradients of the score-matching objective for a mirror ``PaiNN`` module on a ROCm device."""
+class _StepContext:
+    """What one loss_and_grad call shares between the trunk, the heads and the loss."""
 
-    def __init__(self, model, device="cuda:0", igso3: Optional[Igso3Tables] = None) -> None:
+    __slots__ = ("P", "G", "eng", "h", "prep", "E", "N", "B", "scales", "fused_bwd")
+
+
+class _PaiNNStepBase:
+    """The part of a training step both PaiNN mirrors share: graph, embedding, radial basis and the message / update layers
+    forward with saved activations, the gated output head forward and backward, and the layers / rbf weight gradient /
+    embedding backward.  A subclass adds its heads and its objective."""
+
+    # parameters the objective never reads: the reference's autograd leaves their .grad at None (DDP runs with
+    # find_unused_parameters, base_trainer.py:442-447) and torch.optim.AdamW then skips them - no weight decay either
+    UNUSED_PREFIXES: tuple = ()
+
+    def __init__(self, model, device) -> None:
         self.model = model
         self.dev = torch.device(device)
         if self.dev.type != "cuda":
-            raise RuntimeError("PaiNNTrainStep needs a ROCm device (the HIP path has no CPU fallback)")
-        if not model.so3_denoising:
-            raise NotImplementedError("the training step is written for so3_denoising=True (two heads)")
-        self.ops = _Ops(self.dev)
-        self.lib = self.ops.lib
-        self.igso3 = igso3 or Igso3Tables.shared()
+            raise RuntimeError(f"{type(self).__name__} needs a ROCm device (the HIP path has no CPU fallback)")
         # forward of the message block through the sampler's fused kernel (ADF_TRAIN_MSG=plain: the rbfh-reading kernel)
         self.fused_message_forward = os.environ.get("ADF_TRAIN_MSG", "fused") != "plain"
         # backward of the message block with rbfh regenerated inside the kernel (message_bwd.hip) instead of kept from the
@@ -102,59 +109,61 @@ class PaiNNTrainStep:
             raise NotImplementedError(
                 f"the training step needs num_rbf to be a multiple of 32 (a multiple of 8 with the fused message "
                 f"backward), got {R}")
+        self.ops = _Ops(self.dev)
+        self.lib = self.ops.lib
 
     # ------------------------------------------------------------------ helpers
     def _params(self) -> Dict[str, torch.nn.Parameter]:
         return dict(self.model.named_parameters())
 
-    # parameters the score path never reads: the reference's autograd leaves their .grad at None (DDP runs with
-    # find_unused_parameters, base_trainer.py:442-447) and torch.optim.AdamW then skips them - no weight decay either
-    UNUSED_PREFIXES = ("out_energy.",)
-
     def zero_grad(self) -> None:
         for name, p in self.model.named_parameters():
             if not p.requires_grad:
                 continue
-            if name.startswith(self.UNUSED_PREFIXES):
+            if self.UNUSED_PREFIXES and name.startswith(self.UNUSED_PREFIXES):
                 p.grad = None
             elif p.grad is None:
                 p.grad = torch.zeros_like(p)
             else:
                 p.grad.zero_()
 
-    # ------------------------------------------------------------------ the step
-    def loss_and_grad(self, batch, targets: dict, grads_ready=None) -> torch.Tensor:
-        """``batch``: noised batch on the device (pos, atomic_numbers, tags, batch, natoms, cell); ``targets``: tr_sigma
-        [B,1], rot_sigma [B,1], tr_score [B,3], rot_score [B,3] (what tr_so3_schedule attaches to the batch).
-        Accumulates into ``param.grad`` (call zero_grad first, like optimizer.zero_grad) and returns the device tensor
-        (loss, translation term, rotation term).  ``grads_ready(names)`` (optional) is called as soon as the gradients of a
-        group of parameters are final: both heads, then each layer from the last to the first, then the embedding."""
-        m, ops, lib = self.model, self.ops, self.lib
-        P = self._params()
-        H, L, R = m.hidden_channels, m.num_layers, m.num_rbf
-        eng = m.engine(self.dev, refresh=False)
-        h = eng.handle
-        prep = eng.prepare(batch)
-        E = eng.build_graph(batch, prep)
-        N, B = prep.num_atoms, prep.num_systems
-        if prep.tags is None:
-            raise ValueError("batch.tags is required (tag 2 marks the adsorbate)")
-        s = ops.s
-        G = {k: p.grad for k, p in P.items() if p.requires_grad and not k.startswith(self.UNUSED_PREFIXES)}
-        for k, g in G.items():
+    def _begin(self, batch) -> _StepContext:
+        """Graph of ``batch`` on the model's engine, the parameters and their gradient buffers."""
+        c = _StepContext()
+        c.P = self._params()
+        c.eng = self.model.engine(self.dev, refresh=False)
+        c.h = c.eng.handle
+        c.prep = c.eng.prepare(batch)
+        c.E = c.eng.build_graph(batch, c.prep)
+        c.N, c.B = c.prep.num_atoms, c.prep.num_systems
+        return c
+
+    def _bind_gradients(self, c: _StepContext) -> None:
+        m, lib = self.model, self.lib
+        H = m.hidden_channels
+        c.G = {k: p.grad for k, p in c.P.items()
+               if p.requires_grad and not (self.UNUSED_PREFIXES and k.startswith(self.UNUSED_PREFIXES))}
+        for k, g in c.G.items():
             if g is None:
                 raise RuntimeError("call zero_grad() before loss_and_grad()")
-        scales = m.scale_factors()
-        fused_bwd = self.fused_message_backward and bool(lib.adf_op_message_bwd_fused_supported(h))
-        if fused_bwd and self._bwd_perm is None:
+        c.scales = m.scale_factors()
+        c.fused_bwd = self.fused_message_backward and bool(lib.adf_op_message_bwd_fused_supported(c.h))
+        if c.fused_bwd and self._bwd_perm is None:
             perm = (C.c_int32 * (3 * H))()
-            _lib.check(lib.adf_op_message_bwd_perm(h, perm, 3 * H))
+            _lib.check(lib.adf_op_message_bwd_perm(c.h, perm, 3 * H))
             self._bwd_perm = torch.tensor(list(perm), dtype=torch.long, device=self.dev)
 
-        # ---------------- forward with saved activations
+    # ------------------------------------------------------------------ trunk forward
+    def _trunk_forward(self, c: _StepContext):
+        """Embedding, radial basis and the layers with saved activations -> (x, vec, saved, rbf)."""
+        m, ops, lib = self.model, self.ops, self.lib
+        P, h, prep, E, N = c.P, c.h, c.prep, c.E, c.N
+        H, L, R = m.hidden_channels, m.num_layers, m.num_rbf
+        scales, fused_bwd = c.scales, c.fused_bwd
+        s = ops.s
         x = ops.new(N, H)
         _lib.check(lib.adf_op_embed_fwd(h, prep.atomic_numbers.data_ptr(), N, x.data_ptr(), s()))
-        eng.check_flags()
+        c.eng.check_flags()
         rbf = ops.new(E, R)
         _lib.check(lib.adf_op_rbf(h, rbf.data_ptr(), s()))
         vec = None
@@ -197,81 +206,81 @@ class PaiNNTrainStep:
                                                  x2.data_ptr(), vec2.data_ptr(), N, H, s()))
             saved.append(a)
             x, vec = x2, vec2
+        return x, vec, saved, rbf
 
-        heads = []
-        outs = []
-        for hname in ("out_forces", "out_forces2"):
-            hs = {}
-            xin, vin, Cin = x, vec, H
-            for blk, Cout in ((0, H // 2), (1, 1)):
-                q = f"{hname}.output_network.{blk}."
-                b = {"xin": xin, "vin": vin, "Cin": Cin, "Cout": Cout}
-                b["t1"] = ops.linear(vin, P[q + "vec1_proj.weight"], None, 3 * N, Cin, Cin)
-                b["cat"] = ops.new(N, 2 * Cin)
-                _lib.check(lib.adf_op_copy_rows(xin.data_ptr(), Cin, b["cat"].data_ptr(), 2 * Cin, N, Cin, 0, s()))
-                _lib.check(lib.adf_op_vnorm_fwd(b["t1"].data_ptr(), b["cat"].data_ptr() + 4 * Cin, 2 * Cin, N, Cin, s()))
-                b["t2"] = ops.linear(vin, P[q + "vec2_proj.weight"], None, 3 * N, Cout, Cin)
-                b["g0"] = ops.linear(b["cat"], P[q + "update_net.0.weight"], P[q + "update_net.0.bias"], N, Cin, 2 * Cin)
-                b["ga"] = ops.new(N, Cin)
-                _lib.check(lib.adf_op_ssilu_fwd(b["g0"].data_ptr(), b["ga"].data_ptr(), N * Cin, s()))
-                b["o"] = ops.linear(b["ga"], P[q + "update_net.2.weight"], P[q + "update_net.2.bias"], N, 2 * Cout, Cin)
-                b["xs"], b["vout"] = ops.new(N, Cout), ops.new(N, 3, Cout)
-                _lib.check(lib.adf_op_gate_fwd(b["o"].data_ptr(), b["t2"].data_ptr(), b["xs"].data_ptr(), Cout,
-                                               b["vout"].data_ptr(), N, Cout, s()))
-                hs[blk] = b
-                xin, vin, Cin = b["xs"], b["vout"], Cout
-            heads.append(hs)
-            outs.append(vin.reshape(N, 3))
-        f1, f2 = outs
+    # ------------------------------------------------------------------ gated output head
+    def _head_forward(self, c: _StepContext, hname: str, x, vec):
+        """One ``PaiNNOutput`` head (two gated equivariant blocks) -> (saved blocks, output [N, 3])."""
+        ops, lib = self.ops, self.lib
+        P, N = c.P, c.N
+        H = self.model.hidden_channels
+        s = ops.s
+        hs = {}
+        xin, vin, Cin = x, vec, H
+        for blk, Cout in ((0, H // 2), (1, 1)):
+            q = f"{hname}.output_network.{blk}."
+            b = {"xin": xin, "vin": vin, "Cin": Cin, "Cout": Cout}
+            b["t1"] = ops.linear(vin, P[q + "vec1_proj.weight"], None, 3 * N, Cin, Cin)
+            b["cat"] = ops.new(N, 2 * Cin)
+            _lib.check(lib.adf_op_copy_rows(xin.data_ptr(), Cin, b["cat"].data_ptr(), 2 * Cin, N, Cin, 0, s()))
+            _lib.check(lib.adf_op_vnorm_fwd(b["t1"].data_ptr(), b["cat"].data_ptr() + 4 * Cin, 2 * Cin, N, Cin, s()))
+            b["t2"] = ops.linear(vin, P[q + "vec2_proj.weight"], None, 3 * N, Cout, Cin)
+            b["g0"] = ops.linear(b["cat"], P[q + "update_net.0.weight"], P[q + "update_net.0.bias"], N, Cin, 2 * Cin)
+            b["ga"] = ops.new(N, Cin)
+            _lib.check(lib.adf_op_ssilu_fwd(b["g0"].data_ptr(), b["ga"].data_ptr(), N * Cin, s()))
+            b["o"] = ops.linear(b["ga"], P[q + "update_net.2.weight"], P[q + "update_net.2.bias"], N, 2 * Cout, Cin)
+            b["xs"], b["vout"] = ops.new(N, Cout), ops.new(N, 3, Cout)
+            _lib.check(lib.adf_op_gate_fwd(b["o"].data_ptr(), b["t2"].data_ptr(), b["xs"].data_ptr(), Cout,
+                                           b["vout"].data_ptr(), N, Cout, s()))
+            hs[blk] = b
+            xin, vin, Cin = b["xs"], b["vout"], Cout
+        return hs, vin.reshape(N, 3)
 
-        # ---------------- loss and its gradient with respect to the two heads' outputs
-        t = {k: targets[k].to(self.dev, torch.float32).contiguous() for k in ("tr_sigma", "rot_sigma", "tr_score", "rot_score")}
-        rot_norm = self.igso3.score_norm(t["rot_sigma"].reshape(-1).cpu()).to(self.dev).contiguous()
-        loss = ops.new(3)
-        df1, df2 = ops.new(N, 3), ops.new(N, 3)
-        _lib.check(lib.adf_op_score_loss(f1.data_ptr(), f2.data_ptr(), prep.tags.data_ptr(), prep.atom_offset.data_ptr(),
-                                         t["tr_sigma"].data_ptr(), t["rot_sigma"].data_ptr(), t["tr_score"].data_ptr(),
-                                         t["rot_score"].data_ptr(), rot_norm.data_ptr(), loss.data_ptr(), df1.data_ptr(),
-                                         df2.data_ptr(), B, ops.scratch(2 * B + 16).data_ptr(), s()))
+    def _head_backward(self, c: _StepContext, hname: str, hs, dout, dx, dvec) -> None:
+        """Backward of one head from ``dout`` [N, 3]: its parameters' gradients, and its inputs' accumulated into dx / dvec."""
+        ops, lib = self.ops, self.lib
+        P, G, N = c.P, c.G, c.N
+        H = self.model.hidden_channels
+        s = ops.s
+        dxs, dv = None, dout.reshape(N, 3, 1)
+        for blk in (1, 0):
+            b = hs[blk]
+            q = f"{hname}.output_network.{blk}."
+            Cin, Cout = b["Cin"], b["Cout"]
+            d_o, dt2 = ops.new(N, 2 * Cout), ops.new(N, 3, Cout)
+            _lib.check(lib.adf_op_gate_bwd(b["o"].data_ptr(), b["t2"].data_ptr(), dxs.data_ptr() if dxs is not None else None,
+                                           Cout, dv.data_ptr(), d_o.data_ptr(), dt2.data_ptr(), N, Cout, s()))
+            dga = ops.linear_bwd(b["ga"], P[q + "update_net.2.weight"], d_o, N, 2 * Cout, Cin,
+                                 G[q + "update_net.2.weight"], G[q + "update_net.2.bias"])
+            dg0 = ops.new(N, Cin)
+            _lib.check(lib.adf_op_ssilu_bwd(b["g0"].data_ptr(), dga.data_ptr(), dg0.data_ptr(), N * Cin, s()))
+            dcat = ops.linear_bwd(b["cat"], P[q + "update_net.0.weight"], dg0, N, Cin, 2 * Cin,
+                                  G[q + "update_net.0.weight"], G[q + "update_net.0.bias"])
+            dt1 = ops.new(N, 3, Cin)
+            _lib.check(lib.adf_op_vnorm_bwd(b["t1"].data_ptr(), b["cat"].data_ptr() + 4 * Cin, 2 * Cin,
+                                            dcat.data_ptr() + 4 * Cin, 2 * Cin, dt1.data_ptr(), N, Cin, s()))
+            # gradient of this block's inputs: x from the left half of dcat, v from the two projections
+            if blk == 1:
+                dxs_in, dv_in = ops.new(N, Cin), ops.new(N, 3, Cin)
+                tgt_x, ldx, tgt_v, acc = dxs_in, Cin, dv_in, False
+            else:
+                tgt_x, ldx, tgt_v, acc = dx, H, dvec, True
+            _lib.check(lib.adf_op_copy_rows(dcat.data_ptr(), 2 * Cin, tgt_x.data_ptr(), ldx, N, Cin, 1 if acc else 0, s()))
+            ops.linear_bwd(b["vin"], P[q + "vec1_proj.weight"], dt1, 3 * N, Cin, Cin, G[q + "vec1_proj.weight"], None,
+                           dA=tgt_v, acc_dA=acc)
+            ops.linear_bwd(b["vin"], P[q + "vec2_proj.weight"], dt2, 3 * N, Cout, Cin, G[q + "vec2_proj.weight"], None,
+                           dA=tgt_v, acc_dA=True)
+            if blk == 1:
+                dxs, dv = dxs_in, dv_in
 
-        # ---------------- backward: heads
-        dx = torch.zeros(N, H, device=self.dev)
-        dvec = torch.zeros(N, 3, H, device=self.dev)
-        for hname, hs, dout in (("out_forces", heads[0], df1), ("out_forces2", heads[1], df2)):
-            dxs, dv = None, dout.reshape(N, 3, 1)
-            for blk in (1, 0):
-                b = hs[blk]
-                q = f"{hname}.output_network.{blk}."
-                Cin, Cout = b["Cin"], b["Cout"]
-                d_o, dt2 = ops.new(N, 2 * Cout), ops.new(N, 3, Cout)
-                _lib.check(lib.adf_op_gate_bwd(b["o"].data_ptr(), b["t2"].data_ptr(), dxs.data_ptr() if dxs is not None else None,
-                                               Cout, dv.data_ptr(), d_o.data_ptr(), dt2.data_ptr(), N, Cout, s()))
-                dga = ops.linear_bwd(b["ga"], P[q + "update_net.2.weight"], d_o, N, 2 * Cout, Cin,
-                                     G[q + "update_net.2.weight"], G[q + "update_net.2.bias"])
-                dg0 = ops.new(N, Cin)
-                _lib.check(lib.adf_op_ssilu_bwd(b["g0"].data_ptr(), dga.data_ptr(), dg0.data_ptr(), N * Cin, s()))
-                dcat = ops.linear_bwd(b["cat"], P[q + "update_net.0.weight"], dg0, N, Cin, 2 * Cin,
-                                      G[q + "update_net.0.weight"], G[q + "update_net.0.bias"])
-                dt1 = ops.new(N, 3, Cin)
-                _lib.check(lib.adf_op_vnorm_bwd(b["t1"].data_ptr(), b["cat"].data_ptr() + 4 * Cin, 2 * Cin,
-                                                dcat.data_ptr() + 4 * Cin, 2 * Cin, dt1.data_ptr(), N, Cin, s()))
-                # gradient of this block's inputs: x from the left half of dcat, v from the two projections
-                if blk == 1:
-                    dxs_in, dv_in = ops.new(N, Cin), ops.new(N, 3, Cin)
-                    tgt_x, ldx, tgt_v, acc = dxs_in, Cin, dv_in, False
-                else:
-                    tgt_x, ldx, tgt_v, acc = dx, H, dvec, True
-                _lib.check(lib.adf_op_copy_rows(dcat.data_ptr(), 2 * Cin, tgt_x.data_ptr(), ldx, N, Cin, 1 if acc else 0, s()))
-                ops.linear_bwd(b["vin"], P[q + "vec1_proj.weight"], dt1, 3 * N, Cin, Cin, G[q + "vec1_proj.weight"], None,
-                               dA=tgt_v, acc_dA=acc)
-                ops.linear_bwd(b["vin"], P[q + "vec2_proj.weight"], dt2, 3 * N, Cout, Cin, G[q + "vec2_proj.weight"], None,
-                               dA=tgt_v, acc_dA=True)
-                if blk == 1:
-                    dxs, dv = dxs_in, dv_in
-
-        if grads_ready is not None:
-            grads_ready(["out_forces.", "out_forces2."])
-        # ---------------- backward: layers, last to first
+    # ------------------------------------------------------------------ trunk backward
+    def _trunk_backward(self, c: _StepContext, dx, dvec, saved, rbf, grads_ready=None) -> None:
+        """Layers from the last to the first, the rbf weight gradient and the embedding, from d(x), d(vec) of the last layer."""
+        m, ops, lib = self.model, self.ops, self.lib
+        P, G, h, prep, E, N = c.P, c.G, c.h, c.prep, c.E, c.N
+        H, L, R = m.hidden_channels, m.num_layers, m.num_rbf
+        scales, fused_bwd = c.scales, c.fused_bwd
+        s = ops.s
         edge_owner = rbf_image = None
         for l in range(L - 1, -1, -1):
             a = saved[l]
@@ -357,7 +366,179 @@ class PaiNNTrainStep:
                                         G["atom_emb.embeddings.weight"].data_ptr(), N, H, s()))
         if grads_ready is not None:
             grads_ready(["atom_emb."])
+
+
+class PaiNNTrainStep(_PaiNNStepBase):
+    """loss + gradients of the score-matching objective for a mirror ``PaiNN`` module on a ROCm device."""
+
+    # the score path never reads the energy head
+    UNUSED_PREFIXES = ("out_energy.",)
+
+    def __init__(self, model, device="cuda:0", igso3: Optional[Igso3Tables] = None) -> None:
+        if not model.so3_denoising:
+            raise NotImplementedError("the training step is written for so3_denoising=True (two heads)")
+        super().__init__(model, device)
+        self.igso3 = igso3 or Igso3Tables.shared()
+
+    # ------------------------------------------------------------------ the step
+    def loss_and_grad(self, batch, targets: dict, grads_ready=None) -> torch.Tensor:
+        """``batch``: noised batch on the device (pos, atomic_numbers, tags, batch, natoms, cell); ``targets``: tr_sigma
+        [B,1], rot_sigma [B,1], tr_score [B,3], rot_score [B,3] (what tr_so3_schedule attaches to the batch).
+        Accumulates into ``param.grad`` (call zero_grad first, like optimizer.zero_grad) and returns the device tensor
+        (loss, translation term, rotation term).  ``grads_ready(names)`` (optional) is called as soon as the gradients of a
+        group of parameters are final: both heads, then each layer from the last to the first, then the embedding."""
+        m, ops, lib = self.model, self.ops, self.lib
+        H = m.hidden_channels
+        c = self._begin(batch)
+        prep, N, B = c.prep, c.N, c.B
+        if prep.tags is None:
+            raise ValueError("batch.tags is required (tag 2 marks the adsorbate)")
+        s = ops.s
+        self._bind_gradients(c)
+
+        # ---------------- forward with saved activations
+        x, vec, saved, rbf = self._trunk_forward(c)
+        heads = []
+        outs = []
+        for hname in ("out_forces", "out_forces2"):
+            hs, out = self._head_forward(c, hname, x, vec)
+            heads.append(hs)
+            outs.append(out)
+        f1, f2 = outs
+
+        # ---------------- loss and its gradient with respect to the two heads' outputs
+        t = {k: targets[k].to(self.dev, torch.float32).contiguous() for k in ("tr_sigma", "rot_sigma", "tr_score", "rot_score")}
+        rot_norm = self.igso3.score_norm(t["rot_sigma"].reshape(-1).cpu()).to(self.dev).contiguous()
+        loss = ops.new(3)
+        df1, df2 = ops.new(N, 3), ops.new(N, 3)
+        _lib.check(lib.adf_op_score_loss(f1.data_ptr(), f2.data_ptr(), prep.tags.data_ptr(), prep.atom_offset.data_ptr(),
+                                         t["tr_sigma"].data_ptr(), t["rot_sigma"].data_ptr(), t["tr_score"].data_ptr(),
+                                         t["rot_score"].data_ptr(), rot_norm.data_ptr(), loss.data_ptr(), df1.data_ptr(),
+                                         df2.data_ptr(), B, ops.scratch(2 * B + 16).data_ptr(), s()))
+
+        # ---------------- backward: heads
+        dx = torch.zeros(N, H, device=self.dev)
+        dvec = torch.zeros(N, 3, H, device=self.dev)
+        for hname, hs, dout in (("out_forces", heads[0], df1), ("out_forces2", heads[1], df2)):
+            self._head_backward(c, hname, hs, dout, dx, dvec)
+        if grads_ready is not None:
+            grads_ready(["out_forces.", "out_forces2."])
+        # ---------------- backward: layers, last to first, then the embedding
+        self._trunk_backward(c, dx, dvec, saved, rbf, grads_ready)
         self.last_outputs = (f1, f2)
+        return loss
+
+
+class PaiNNS2EFTrainStep(_PaiNNStepBase):
+    """loss + gradients of the S2EF objective for a mirror ``adsorbdiff_amd.painn.PaiNN`` (the force field ``ml_relax``
+    relaxes with) on a ROCm device: what ``OCPTrainer._compute_loss`` + ``loss.backward()`` do for it
+    (trainers/ocp_trainer.py:308-356, modules/loss.py:48-102) with energy loss "mae" and force loss "l2mae"; the model's
+    outputs are normalised predictions, the targets ``batch.energy [B]``, ``batch.forces [N,3]`` are normalised with
+    ``normalizers`` (absent: mean 0, std 1).  Defaults: utils/utils.py:1227,1257 and base_trainer.py:382-390.  Shares the
+    trunk with ``PaiNNTrainStep``; the heads are one gated force head (none with ``regress_forces=False``: the loss is the
+    energy term alone) and the energy head, whose backward is ``adf_op_energy_head_bwd`` + ``adf_op_linear_bwd``.  Every
+    parameter of this model is used: none is left at ``grad = None``.  The engine supplies the 1e-6 distance floor."""
+
+    def __init__(self, model, device="cuda:0", normalizers: Optional[dict] = None, energy_coefficient: float = 1,
+                 force_coefficient: float = 30, train_on_free_atoms: bool = True) -> None:
+        from .painn import PaiNN as S2EFPaiNN
+
+        if not isinstance(model, S2EFPaiNN):
+            raise NotImplementedError(
+                f"PaiNNS2EFTrainStep trains adsorbdiff_amd.painn.PaiNN (energy + force heads), got {type(model).__name__}; "
+                "the denoiser's step is PaiNNTrainStep")
+        if model.force_mode == "energy_gradient":
+            raise NotImplementedError(
+                "training with force_mode='energy_gradient' needs a second-order backward, which is not offered: "
+                "train with force_mode='direct'")
+        super().__init__(model, device)
+        self.energy_coefficient, self.force_coefficient = float(energy_coefficient), float(force_coefficient)
+        self.train_on_free_atoms = bool(train_on_free_atoms)
+        self.norm = {}
+        for key in ("energy", "forces"):
+            nz = (normalizers or {}).get(key)
+            if nz is None or nz is False:
+                self.norm[key] = (0.0, 1.0)
+            elif isinstance(nz, dict):
+                self.norm[key] = (float(nz.get("mean", 0.0)), float(nz.get("stdev", nz.get("std", 1.0))))
+            else:
+                self.norm[key] = (float(nz.mean), float(nz.std))
+        self.metrics = None
+        self.last_outputs = None
+
+    def loss_and_grad(self, batch, grads_ready=None, counts: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``batch``: pos, atomic_numbers, batch, natoms, cell and the targets energy [B], forces [N,3], fixed [N] on the
+        device.  Accumulates into ``param.grad`` (call zero_grad first) and returns the device tensor (loss, energy term,
+        force term); ``metrics`` then holds the device tensor (energy MAE, force MAE per component over the free atoms) in
+        target units.  ``counts``: device int64 ``[B_glob, M_glob, W]`` of a multi-rank step (None: this batch's own
+        counts, W = 1).  ``grads_ready(names)``: ``out_energy.`` together with ``out_forces.``, then each layer from the
+        last to the first, then the embedding."""
+        m, ops, lib = self.model, self.ops, self.lib
+        H = m.hidden_channels
+        H2 = H // 2
+        c = self._begin(batch)
+        prep, N, B, P = c.prep, c.N, c.B, c.P
+        forces_on = bool(m.regress_forces)
+        for key in ("energy",) + (("forces",) if forces_on else ()):
+            if getattr(batch, key, None) is None:
+                raise ValueError(f"batch.{key} is required (the S2EF target)")
+        if self.train_on_free_atoms and forces_on and prep.fixed is None:
+            raise ValueError("batch.fixed is required with train_on_free_atoms")
+        if counts is not None and (counts.dtype != torch.int64 or counts.numel() != 3 or not counts.is_cuda):
+            raise ValueError("counts: a device int64 tensor [B_glob, M_glob, W]")
+        s = ops.s
+        self._bind_gradients(c)
+        G = c.G
+
+        # ---------------- forward with saved activations
+        x, vec, saved, rbf = self._trunk_forward(c)
+        hs = f_pred = None
+        if forces_on:
+            hs, f_pred = self._head_forward(c, "out_forces", x, vec)
+        he0 = ops.linear(x, P["out_energy.0.weight"], P["out_energy.0.bias"], N, H2, H)
+        hea = ops.new(N, H2)
+        _lib.check(lib.adf_op_ssilu_fwd(he0.data_ptr(), hea.data_ptr(), N * H2, s()))
+        e_pred = ops.new(B)
+        _lib.check(lib.adf_op_energy_sum(hea.data_ptr(), H2, P["out_energy.2.weight"].data_ptr(),
+                                         P["out_energy.2.bias"].data_ptr(), prep.atom_offset.data_ptr(), e_pred.data_ptr(), B,
+                                         s()))
+
+        # ---------------- loss and its gradient with respect to the predictions
+        e_tgt = batch.energy.to(self.dev, torch.float32).reshape(-1).contiguous()
+        f_tgt = batch.forces.to(self.dev, torch.float32).reshape(N, 3).contiguous() if forces_on else None
+        if e_tgt.numel() != B:
+            raise ValueError(f"batch.energy has {e_tgt.numel()} entries for {B} systems")
+        loss, metrics = ops.new(3), ops.new(2)
+        dE = ops.new(B)
+        dF = ops.new(N, 3) if forces_on else None
+        (mean_e, std_e), (mean_f, std_f) = self.norm["energy"], self.norm["forces"]
+        _lib.check(lib.adf_op_s2ef_loss(
+            e_pred.data_ptr(), f_pred.data_ptr() if forces_on else None, e_tgt.data_ptr(),
+            f_tgt.data_ptr() if forces_on else None, prep.fixed.data_ptr() if prep.fixed is not None else None,
+            prep.atom_offset.data_ptr(), B, 1 if self.train_on_free_atoms else 0, C.c_float(mean_e), C.c_float(std_e),
+            C.c_float(mean_f), C.c_float(std_f), C.c_float(self.energy_coefficient), C.c_float(self.force_coefficient),
+            counts.data_ptr() if counts is not None else None, loss.data_ptr(), dE.data_ptr(),
+            dF.data_ptr() if forces_on else None, metrics.data_ptr(),
+            ops.scratch(int(lib.adf_op_s2ef_loss_scratch(B))).data_ptr(), s()))
+
+        # ---------------- backward: the force head, then the energy head on top of it
+        dx = torch.zeros(N, H, device=self.dev)
+        dvec = torch.zeros(N, 3, H, device=self.dev)
+        if forces_on:
+            self._head_backward(c, "out_forces", hs, dF, dx, dvec)
+        dhe0 = ops.new(N, H2)
+        _lib.check(lib.adf_op_energy_head_bwd(
+            he0.data_ptr(), P["out_energy.2.weight"].data_ptr(), dE.data_ptr(), prep.batch.data_ptr(), dhe0.data_ptr(),
+            G["out_energy.2.weight"].data_ptr(), G["out_energy.2.bias"].data_ptr(), 1, N, H2,
+            ops.scratch(int(lib.adf_op_energy_head_bwd_scratch(N, H2))).data_ptr(), s()))
+        ops.linear_bwd(x, P["out_energy.0.weight"], dhe0, N, H2, H, G["out_energy.0.weight"], G["out_energy.0.bias"],
+                       dA=dx, acc_dA=True)
+        if grads_ready is not None:
+            grads_ready(["out_energy.", "out_forces."])
+        # ---------------- backward: layers, last to first, then the embedding
+        self._trunk_backward(c, dx, dvec, saved, rbf, grads_ready)
+        self.metrics = metrics
+        self.last_outputs = (e_pred, f_pred)
         return loss
 
 

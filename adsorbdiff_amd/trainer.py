@@ -8,7 +8,8 @@ denoising_torch.py:38,491-500): ``predict_denoising(batch, per_image=False)``,
 base_trainer.py:787-820): noising, forward, loss, backward, gradient all-reduce, clipping, AdamW, EMA — all device
 arithmetic in HIP kernels (adsorbdiff_amd/train_step.py).  Datasets, LR schedules, logging, evaluation and checkpoint
 *writing* stay out of scope; ``load_checkpoint`` reads the reference's checkpoint layout
-(base_trainer.py:456-533) so trained weights can be sampled with.
+(base_trainer.py:456-533) so trained weights can be sampled with.  ``ForcesTrainer.train_step`` is the same body for the
+S2EF force field (trainers/ocp_trainer.py:115-246, loss :308-356).
 """
 from __future__ import annotations
 
@@ -264,6 +265,81 @@ class ForcesTrainer:
             target = _NORMALIZER_KEYS.get(key, key)
             if target in self.normalizers:
                 self.normalizers[target].load_state_dict(sd)
+
+    # ---------------------------------------------------------------- training
+    def setup_training(self, lr: float, weight_decay: float = 0.001, clip_grad_norm: float = 10.0, ema_decay: float = 0.999,
+                       energy_coefficient: float = 1, force_coefficient: float = 30, loss_energy: str = "mae",
+                       loss_force: str = "l2mae", train_on_free_atoms: bool = True) -> None:
+        """Optimizer / EMA / objective of ``train_step``.  AdamW with weight decay except ``no_weight_decay()`` names;
+        clip 10 and EMA 0.999 as configs/relaxation/gemnet_oc/gemnet_relax.yml:107-108; coefficients and
+        ``train_on_free_atoms`` as the reference's defaults (utils/utils.py:1227,1257, base_trainer.py:382-390; the shipped
+        YAMLs pass force_coefficient 100).  The targets are normalised with this trainer's ``normalizers``.  Only the loss
+        names the shipped configs use are offered (energy "mae", forces "l2mae"); any other name is refused here."""
+        from .exponential_moving_average import ExponentialMovingAverage
+        from .train_step import FusedAdamW, PaiNNS2EFTrainStep
+
+        if loss_energy != "mae" or loss_force != "l2mae":
+            raise NotImplementedError(
+                f"the S2EF step offers energy loss 'mae' with force loss 'l2mae', got {loss_energy!r} / {loss_force!r} "
+                "(mse, atomwisel2 and torch module names are not offered)")
+        self.train_engine = PaiNNS2EFTrainStep(self._unwrapped_model, self.device, normalizers=self.normalizers,
+                                               energy_coefficient=energy_coefficient, force_coefficient=force_coefficient,
+                                               train_on_free_atoms=train_on_free_atoms)
+        # a falsy ema_decay trains without an EMA: one that was loaded or set up earlier is dropped, not updated on
+        self.ema = ExponentialMovingAverage(self._unwrapped_model.parameters(), ema_decay) if ema_decay else None
+        self.optimizer = FusedAdamW(self._unwrapped_model, lr=lr, weight_decay=weight_decay, max_grad_norm=clip_grad_norm,
+                                    ema=self.ema)
+        self.step = 0
+
+    def train_step(self, batch) -> dict:
+        """One optimisation step on ``batch`` (targets ``energy``, ``forces``, ``fixed``): the per-batch body of
+        ``OCPTrainer.train`` (trainers/ocp_trainer.py:115-246; update: base_trainer.py:787-820).  Multi-GPU: one process
+        per GPU, each with its own batch; the system and loss-atom counts are summed over the ranks before the loss (the
+        divisors of DDPLoss, modules/loss.py:88-99) and the gradients averaged with the bucketed all-reduce of the
+        denoiser's trainer.  A non-finite loss skips the update on every rank (the reference zeroes non-finite predictions
+        instead, loss.py:77-81); the OCP loop has no "loss too high" stop, so ``stop`` is always False."""
+        import torch.distributed as dist
+
+        from .train_step import GradientReducer
+
+        eng = self.train_engine
+        self.model.train()
+        batch = batch.to(self.device)
+        eng.zero_grad()
+        world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+        counts = None
+        if world > 1:
+            # one all-reduce of (systems, loss atoms, 1): the sum of the ones is the world size; no host read
+            n_sys = int(batch.natoms.numel())
+            fixed = getattr(batch, "fixed", None)
+            if eng.train_on_free_atoms and fixed is not None:
+                n_loss = (fixed == 0).sum().to(torch.int64)
+            else:
+                n_loss = torch.tensor(int(batch.pos.shape[0]), dtype=torch.int64, device=self.device)
+            counts = torch.stack([torch.tensor(n_sys, dtype=torch.int64, device=self.device), n_loss.reshape(()),
+                                  torch.tensor(1, dtype=torch.int64, device=self.device)])
+            if dist.get_backend() == "gloo" and counts.is_cuda:   # test configuration: several ranks on one GPU
+                host = counts.cpu()
+                dist.all_reduce(host, op=dist.ReduceOp.SUM)
+                counts = host.to(self.device)
+            else:
+                dist.all_reduce(counts, op=dist.ReduceOp.SUM)
+        reducer = GradientReducer(self._unwrapped_model, world)
+        loss = eng.loss_and_grad(batch, grads_ready=reducer.ready if world > 1 else None, counts=counts)
+        # all ranks must take the same branch: one flag, MAX-reduced, read back once (the step's single device-to-host
+        # read); the fused optimizer additionally turns an update with a non-finite gradient norm into a no-op
+        flag = (~torch.isfinite(loss.detach())).any().reshape(1).to(torch.int32)
+        if world > 1:
+            flag = flag if dist.get_backend() != "gloo" else flag.cpu()
+            dist.all_reduce(flag, op=dist.ReduceOp.MAX)
+        reducer.finish()
+        if bool(flag.item()):
+            logging.warning("non-finite loss detected, skipping step")
+            eng.zero_grad()
+            return {"loss": loss, "grad_norm": None, "skipped": True, "stop": False, "metrics": eng.metrics}
+        grad_norm = self.optimizer.step()
+        self.step += 1
+        return {"loss": loss, "grad_norm": grad_norm, "skipped": False, "stop": False, "metrics": eng.metrics}
 
     @torch.no_grad()
     def predict(self, data_loader, per_image: bool = False, results_file=None, disable_tqdm: bool = False):

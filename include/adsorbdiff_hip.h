@@ -436,6 +436,41 @@ int32_t adf_op_copy_rows(const float* src, int32_t lds_, float* dst, int32_t ldd
 int32_t adf_op_score_loss(const float* f1, const float* f2, const int32_t* tags, const int32_t* atom_offset,
                           const float* tr_sigma, const float* rot_sigma, const float* tr_score, const float* rot_score,
                           const float* rot_norm, float* loss, float* df1, float* df2, int32_t B, float* scratch, void* stream);
+/* S2EF objective of the force field: OCPTrainer._compute_loss (trainers/ocp_trainer.py:308-356) with DDPLoss
+ * (modules/loss.py:48-102) over nn.L1Loss for the energy ("mae") and L2MAELoss for the forces ("l2mae")
+ * (utils/utils.py:1219-1260, 1319-1331); E_pred [B] / F_pred [N,3] are normalised predictions, E_tgt / F_tgt in target units:
+ *     loss[1] = c_E W / B_glob  sum_b |E_pred[b] - (E_tgt[b] - mean_E) / std_E|
+ *     loss[2] = c_F W / M_glob  sum_{i in S} ||F_pred[i] - (F_tgt[i] - mean_F) / std_F||_2,   loss[0] = loss[1] + loss[2]
+ * S: the atoms with fixed == 0 when free_only (base_trainer.py:382-390), else all atoms; fixed == NULL: no atom is fixed.
+ * counts: device {B_glob, M_glob, W} (int64; the all-reduced counts of a multi-rank step) or NULL: this call's own counts
+ * and W = 1.  F_pred == NULL (a model without a force head): the energy term alone, dF untouched.  dE [B], dF [N,3]: the
+ * gradient with respect to the predictions; zero at a zero residual (torch's subgradient of abs / norm) and outside S.
+ * M_glob == 0 (no atom in S on any rank, or a supplied zero): the force term is 0 * W / 0 = NaN, as the reference's
+ * loss * world_size / num_samples is, so loss[0] and loss[2] are NaN (a trainer skips such a step) and dF is NaN or zero.
+ * metrics [2]: energy MAE and force MAE per component over the atoms with fixed == 0, both in target units
+ * (_compute_metrics after denorm, ocp_trainer.py:358-402).  One wave per system, the systems combined in ascending order,
+ * no float atomics: run-to-run identical, and a system's dE / dF rows depend on its own rows and the two divisors only.
+ * scratch: adf_op_s2ef_loss_scratch(B) floats. */
+int32_t adf_op_s2ef_loss(const float* E_pred, const float* F_pred, const float* E_tgt, const float* F_tgt,
+                         const int32_t* fixed, const int32_t* atom_offset, int32_t B, int32_t free_only, float mean_E,
+                         float std_E, float mean_F, float std_F, float c_E, float c_F, const int64_t* counts, float* loss,
+                         float* dE, float* dF, float* metrics, float* scratch, void* stream);
+int64_t adf_op_s2ef_loss_scratch(int32_t B);
+/* energy[b] = sum over the system's atoms of (y[a] . w + bias), y [N, H2] the activated hidden layer of out_energy
+ * (models/painn/painn.py:412-414): the fixed-order per-system sum of adf_painn_forward_energy. */
+int32_t adf_op_energy_sum(const float* y, int32_t H2, const float* w, const float* bias, const int32_t* atom_offset,
+                          float* energy, int32_t B, void* stream);
+/* Backward of out_energy.2 (H2 -> 1), the per-system sum and the ScaledSiLU before it (painn.py:412-414) in one pass over
+ * the stored pre-activation he0 [N, H2]:
+ *     dhe0[n,c] = dE[sys(n)] w2[c] SSiLU'(he0[n,c]),   dW2[c] (+)= sum_n dE[sys(n)] SSiLU(he0[n,c]),   db2 (+)= sum_n dE[sys(n)]
+ * atom_sys [N]: the atoms' system index.  dE == NULL: dE = 1 (the values adf_painn_forward_energy_gradient's own seed kernel
+ * writes, from the same expression; that call does not go through this entry).  dW2 == db2 ==
+ * NULL: data gradient only.  A workgroup owns 64 rows x 64 columns and writes one partial row; a second launch adds the
+ * partial rows in a fixed order (16 contiguous groups of chunks, each ascending, then the groups): no float atomics.  scratch: adf_op_energy_head_bwd_scratch(N, H2) floats. */
+int32_t adf_op_energy_head_bwd(const float* he0, const float* w2, const float* dE, const int32_t* atom_sys, float* dhe0,
+                               float* dW2, float* db2, int32_t accumulate, int64_t N, int32_t H2, float* scratch,
+                               void* stream);
+int64_t adf_op_energy_head_bwd_scratch(int64_t N, int32_t H2);
 int32_t adf_op_sqnorm_accumulate(const float* g, int64_t n, float* out, void* stream);
 int32_t adf_op_adamw_step(float* p, const float* g, float* m, float* v, float* ema, int64_t n, const float* sqnorm,
                           float max_norm, float lr, float beta1, float beta2, float eps, float weight_decay, int32_t step,
