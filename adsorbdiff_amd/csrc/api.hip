@@ -158,6 +158,8 @@ extern "C" int32_t adf_painn_create(const adf_painn_hparams* hp, adf_painn_t* ou
         h->lift_on = !(el && strcmp(el, "0") == 0);
         const char* e2 = getenv("ADF_MSG");
         h->msg_f32 = e2 ? strcmp(e2, "f32") == 0 : h->gemm_f32;
+        const char* er = getenv("ADF_ROW_MAXIMA");   // row maxima from the producers (common.h: adf_painn::rmx)
+        h->rmx = (er && atoi(er) == 0) ? 0 : 1;
     }
     if (st == ADF_OK) st = dev_alloc(&h->kcount, 8);
     if (st == ADF_OK && hipMemset(h->kcount, 0, 8 * sizeof(unsigned long long)) != hipSuccess) st = ADF_EHIP;
@@ -185,7 +187,7 @@ static void inc_free(adf_painn* h) {
 static void free_workspaces(adf_painn* h) {
     void* ptrs[] = {h->nbr_cnt, h->nbr_src, h->nbr_shift, h->deg, h->nptr, h->cursor, h->img_cnt, h->sys_slow, h->scan_tmp,
                     h->e_src, h->e_geom, h->x, h->vecA, h->vecB, h->y, h->xh, h->vv, h->cat, h->dot, h->sys, h->rec, h->lift.buf, h->mag_a, h->mag_b, h->mag_v3,
-                    h->cache_d2, h->cache_cid, h->cache_cnt, h->prev_nptr, h->prev_src, h->prev_geom};
+                    h->rmx_part, h->cache_d2, h->cache_cid, h->cache_cnt, h->prev_nptr, h->prev_src, h->prev_geom};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     h->prev_nptr = h->prev_src = nullptr; h->prev_geom = nullptr; h->inc_valid = false;
@@ -194,6 +196,8 @@ static void free_workspaces(adf_painn* h) {
     h->e_geom = nullptr;
     h->x = h->vecA = h->vecB = h->y = h->xh = h->vv = h->cat = h->dot = h->sys = h->rec = nullptr;
     h->lift.buf = h->mag_a = h->mag_b = h->mag_v3 = nullptr; h->lift.cap = 0; h->mag_v3_valid = false;
+    h->rmx_part = h->xpart = h->catpart = h->vpart = nullptr; h->part_stride = 0;
+    h->part_x = h->part_vec = nullptr; h->dbg_msg_rows = h->dbg_cat_rows = h->dbg_comb_rows = 0; h->dbg_mag = nullptr;
     h->cache_d2 = nullptr; h->cache_cid = nullptr; h->cache_cnt = nullptr; h->cache_valid = false;
     h->capN = h->capB = h->capE = 0;
 }
@@ -370,9 +374,16 @@ static int32_t ensure_capacity(adf_painn* h, int64_t N, int64_t B) {
     ALLOC(mag_a, capN);
     ALLOC(mag_b, capN);
     ALLOC(mag_v3, capN * 3);
+    const int64_t ps = (capN + 31) / 32 * 32, ns = H / ADF_SLICE_CH;
+    if (h->rmx) ALLOC(rmx_part, (4 * ns + H / 32 + 4) * ps);
 #undef ALLOC
     h->lift.cap = st == ADF_OK ? capN * 3 : 0;
     if (st != ADF_OK) { free_workspaces(h); return st; }
+    if (h->rmx) {   // xpart and catpart side by side: the [x | |v2|] rows' maxima are one run of parts
+        h->part_stride = ps;
+        h->xpart = h->rmx_part; h->catpart = h->xpart + ns * ps; h->vpart = h->catpart + (H / 32) * ps;
+        h->dbg_mag = h->vpart + 3 * ns * ps;
+    }
     h->capN = capN; h->capB = capB; h->capE = capE;
     return ADF_OK;
 }
@@ -547,16 +558,30 @@ static int32_t message_layer(adf_painn* h, int l, int N, const float* x, const f
                              int n_targets = 0, float* rec = nullptr, bool records_ready = false) {
     if (!records_ready) ADF_TRY(make_records(h, l, N, x, vec, vec_is_zero, rec, nullptr, s));
     adf_prof_begin(h, ADF_PROF_MESSAGE, s);
+    // the f16x3 kernel also leaves the partial maxima of its output rows for update_layer's products (MsgParams::xpart)
+    const int items = tlist ? n_targets : N;
+    const bool emit = h->rmx && h->lift_on && !h->gemm_f32 && !h->msg_f32 && items > 0 && items <= h->part_stride;
+    h->part_x = h->part_vec = nullptr;
     const int32_t st = adf_message_impl(h, l, N, x, h->xh, vec, x_out, vec_out, vec_is_zero, s, tlist, n_targets, rec,
-                                        tlist ? h->rows_dev : nullptr);
+                                        tlist ? h->rows_dev : nullptr, emit ? h->xpart : nullptr, h->vpart, h->part_stride);
+    if (st == ADF_OK && emit) {
+        h->part_x = x_out; h->part_vec = vec_out; h->part_n = items; h->part_dev = tlist ? h->rows_dev : nullptr;
+        h->dbg_msg_rows = items;
+    }
     adf_prof_end(h, s);
     return st;
 }
 
-static int32_t update_layer(adf_painn* h, int l, int N, float* x, float* vec, hipStream_t s) {
+// from_message: (x, vec) are the rows the last message_layer call wrote, untouched since.  (Rows the caller owns - the
+// public per-layer entry - may have been rewritten between the two calls: never trusted, their maxima are measured.)
+static int32_t update_layer(adf_painn* h, int l, int N, float* x, float* vec, hipStream_t s, bool from_message = true) {
     const int H = h->hp.hidden_channels;
     const adf_layer_weights& w = h->layer[l];
     adf_prof_begin(h, ADF_PROF_NODE, s);
+    // are the partial maxima of exactly these rows current?  They are consumed here: the rows are rewritten in place below.
+    const bool parts = from_message && h->rmx && h->lift_on && !h->gemm_f32 && N > 0 && h->part_x == x && h->part_vec == vec &&
+                       h->part_n == N && h->part_dev == h->rows_dev;
+    h->part_x = h->part_vec = nullptr;
     if (h->gemm_f32) {
         ADF_TRY(adf_launch_gemm(vec, H, w.vp_w, H, nullptr, h->vv, 2 * H, 3 * N, 2 * H, H, 0, s));
         ADF_TRY(adf_nodewise_update_prep(h->vv, x, h->cat, h->dot, N, H, s));
@@ -566,16 +591,40 @@ static int32_t update_layer(adf_painn* h, int l, int N, float* x, float* vec, hi
         adf_epi ep = {};
         ep.v1 = h->vv; ep.dotw = h->dot; ep.cat = h->cat; ep.H = H; ep.m_dev = h->rows_dev;
         const adf_lift* lf = h->lift_on ? &h->lift : nullptr;
-        // vec rows and the [x | |v2|] rows are measured by a pass of their own; xvec_proj.0 hands its output rows' on.
-        // (Measured alternative: the message kernel emitting the magnitudes of its vec_out rows - DPP maxima per
-        // half-wave, 4 atomicMax per target and channel slice: measuring passes -11 ms, message kernel +9 ms per 10 full
-        // steps of 1000 systems: a wash, not kept.)
+        // The magnitudes of the vec rows and of the [x | |v2|] rows come from the rows' producers: the message kernel and
+        // vec_proj's epilogue each leave the maximum over the columns they own in a slot of their own (plain stores, nothing
+        // to zero) and adf_rowmax_combine_kernel takes the maximum over a row's 8 resp. 24 slots - 6 + 19 MB per layer of
+        // 200k rows where the two measuring passes (adf_rowmag_kernel) read 1.23 + 0.82 GB.  A maximum is exact, so the lifts
+        // and with them every bit of the results are the same.  ADF_ROW_MAXIMA=0, and rows that did not come from the
+        // message kernel (from_message), keep the passes.  xvec_proj.0 hands its output rows' magnitudes on as before.
+        // (Earlier form of the same fusion, measured and dropped: 4 atomicMax per target and channel slice from the message
+        // kernel into a zeroed array - measuring passes -11 ms, message kernel +9 ms per 10 full steps of 1000 systems: a
+        // wash.  Float atomics execute at the memory side and stay in the wave's in-order vmcnt in front of every younger
+        // gather; the plain stores here do not.)
+        // The heads keep their five passes per step: their vec / x rows come out of the kept per-layer tables, which mix
+        // rows computed in different steps, so no launch of this step holds a whole table's maxima.
+        if (parts) {
+            ADF_TRY(adf_launch_rowmax_combine(h->vpart, 3 * h->part_stride, H / ADF_SLICE_CH, 3ll * N, h->lift.buf, s, h->rows_dev, 3));
+            ep.rmag = h->lift.buf;
+            if (h->dbg_capture) ADF_HIP_CHECK(hipMemcpyAsync(h->dbg_mag, h->lift.buf, sizeof(float) * 3 * (size_t)N, hipMemcpyDeviceToDevice, s));
+        }
+        // vec_proj stores its |v2| slots only where somebody reads them: the combine below, or the test hook (dbg_capture)
+        if (parts || (h->dbg_capture && h->rmx && lf && N <= h->part_stride)) {
+            ep.catpart = h->catpart; ep.part_stride = h->part_stride; h->dbg_cat_rows = N;
+        }
         ADF_TRY(adf_launch_gemm16_fused(vec, H, &w.vp_16, N, H, H, 3, &ep, s, lf));
+        if (parts) {   // [x | |v2|]: xpart and catpart lie side by side
+            ADF_TRY(adf_launch_rowmax_combine(h->xpart, h->part_stride, H / ADF_SLICE_CH + H / 32, N, h->lift.buf, s, h->rows_dev, 1));
+            if (h->dbg_capture) {
+                ADF_HIP_CHECK(hipMemcpyAsync(h->dbg_mag + 3 * h->part_stride, h->lift.buf, sizeof(float) * (size_t)N, hipMemcpyDeviceToDevice, s));
+                h->dbg_comb_rows = N;
+            }
+        }
         if (use_fused_mlp(h, N)) {   // xvec_proj.0 -> xvec_proj.2 -> gating in one kernel (mlp16.hip), same bits
             const float* rm = nullptr;
             if (lf) {
                 if (N > lf->cap) { adf_set_error("mlp16: lift scratch holds %lld rows, need %d", lf->cap, N); return ADF_EINVAL; }
-                ADF_TRY(adf_launch_rowmag(x, H, H, h->cat, H, N, lf->buf, s, h->rows_dev, 1));
+                if (!parts) ADF_TRY(adf_launch_rowmag(x, H, H, h->cat, H, N, lf->buf, s, h->rows_dev, 1));
                 rm = lf->buf;
             }
             adf_epi e2 = {};
@@ -585,7 +634,7 @@ static int32_t update_layer(adf_painn* h, int l, int N, float* x, float* vec, hi
             adf_prof_end(h, s);
             return stf;
         }
-        ADF_TRY(adf_launch_gemm16(x, H, &w.xv0_16, w.xv0_b, h->y, H, N, H, 2 * H, 1, s, h->cat, H, lf, nullptr,
+        ADF_TRY(adf_launch_gemm16(x, H, &w.xv0_16, w.xv0_b, h->y, H, N, H, 2 * H, 1, s, h->cat, H, lf, parts ? h->lift.buf : nullptr,
                                   h->lift_on ? h->mag_b : nullptr, h->rows_dev));
     }
     int32_t st;
@@ -621,7 +670,36 @@ extern "C" int32_t adf_painn_update_layer(adf_painn_t h, int32_t layer, int32_t 
         return ADF_EINVAL;
     }
     ADF_TRY(ensure_capacity(h, N, 1));
-    return update_layer(h, layer, N, x, vec, (hipStream_t)stream);
+    return update_layer(h, layer, N, x, vec, (hipStream_t)stream, false);
+}
+
+// Test hook: the row maxima as the producers of the last launch left them, combined over their slots.  which = 0: max|x_out|
+// [rows] and 1: max|vec_out| [3 rows] of the last message launch; 2: max |v2| [rows] of the last vec_proj launch; 3: the
+// |v2| rows themselves [rows, H].  4: capture on (capacity != 0) / off, nothing returned: vec_proj emits its slots on the public
+// per-layer entry too and update_layer keeps what it combined; 5 / 6: the magnitudes of the vec rows [3 rows] / of the
+// [x | |v2|] rows [rows] exactly as the last update_layer that took them from the slots handed them to its products.
+// *rows receives the row count; out (device, may be null to query rows) holds `capacity` floats.
+extern "C" int32_t adf_painn_debug_row_maxima(adf_painn_t h, int32_t which, float* out, int64_t capacity, int32_t* rows,
+                                              void* stream) {
+    if (!h || which < 0 || which > 6) { adf_set_error("debug_row_maxima: null handle or which outside 0..6"); return ADF_EINVAL; }
+    if (which == 4) { h->dbg_capture = capacity != 0; h->dbg_comb_rows = 0; return ADF_OK; }
+    const int H = h->hp.hidden_channels, ns = H / ADF_SLICE_CH;
+    const int n = which <= 1 ? h->dbg_msg_rows : which <= 3 ? h->dbg_cat_rows : h->dbg_comb_rows;
+    if (!h->rmx_part || n <= 0) { adf_set_error("debug_row_maxima: no launch has emitted row maxima (ADF_ROW_MAXIMA=0?)"); return ADF_EINVAL; }
+    if (rows) *rows = n;
+    if (!out) return ADF_OK;
+    const int64_t need = (which == 1 || which == 5) ? 3ll * n : which == 3 ? (int64_t)n * H : n;
+    if (capacity < need) { adf_set_error("debug_row_maxima: out holds %lld floats, need %lld", (long long)capacity, (long long)need); return ADF_EINVAL; }
+    hipStream_t s = (hipStream_t)stream;
+    if (which == 0) return adf_launch_rowmax_combine(h->xpart, h->part_stride, ns, n, out, s);
+    if (which == 1) return adf_launch_rowmax_combine(h->vpart, 3 * h->part_stride, ns, 3ll * n, out, s);
+    if (which == 2) return adf_launch_rowmax_combine(h->catpart, h->part_stride, H / 32, n, out, s);
+    if (which >= 5) {
+        ADF_HIP_CHECK(hipMemcpyAsync(out, h->dbg_mag + (which == 5 ? 0 : 3 * h->part_stride), sizeof(float) * (size_t)need, hipMemcpyDeviceToDevice, s));
+        return ADF_OK;
+    }
+    ADF_HIP_CHECK(hipMemcpyAsync(out, h->cat, sizeof(float) * (size_t)n * H, hipMemcpyDeviceToDevice, s));
+    return ADF_OK;
 }
 
 __global__ void adf_scatter_rows3_kernel(const float* __restrict__ src, const int32_t* __restrict__ idx, int n,

@@ -74,6 +74,10 @@ struct adf_epi {
     const float* gate;       // EPI 0 (heads): multiply output row r, column c by gate[(r / 3) * gate_ld + c]  (null: no gate)
     int gate_ld;
     long long rec_rows;      // mlp16.hip EPI 1: rows of the record table the (mapped) rows are written into (0 = the launch's rows)
+    // Partial row maxima (see adf_painn::rmx): a producer writes, with plain stores, the maximum over the columns it owns
+    // into a slot of its own, [part][part_stride]; adf_launch_rowmax_combine takes the maximum over the parts.
+    float* catpart;          // EPI 3: max |v2| of row n over the 32 channels of group g -> catpart[g * part_stride + n]
+    long long part_stride;
 };
 // scratch for the row magnitudes a launcher measures itself (adf_launch_rowmag) when the caller has none to hand over
 struct adf_lift {
@@ -122,6 +126,24 @@ struct adf_painn {
     float *mag_a, *mag_b;  // [capN] magnitudes handed from a producer (LayerNorm, a product's epilogue) to the next product
     float* mag_v3;         // [3 capN] magnitudes of the vec rows entering the heads (measured once, used by both heads)
     bool mag_v3_valid;
+    // Row maxima from the producers (ADF_ROW_MAXIMA, read at creation, default 1): the message kernel and vec_proj's
+    // epilogue emit partial maxima of the rows they write and the layers' measuring passes go.  No atomics, no memsets:
+    // every slot has one writer and every row's slots are all written.
+    int rmx;
+    float* rmx_part;       // [H/64 + H/32 + 3 H/64][part_stride]: xpart | catpart | vpart, then dbg_mag [4][part_stride]
+    float *xpart, *catpart, *vpart;   // xpart[slice][row], catpart[group][row], vpart[slice][3 row + axis]
+    int64_t part_stride;   // capN rounded up to 32 rows: a 128-B line of a slot array has one writing workgroup
+    // the rows whose xpart / vpart slots are current: written by the last message launch and not touched since
+    const float *part_x, *part_vec;
+    int part_n;
+    const int32_t* part_dev;
+    int dbg_msg_rows, dbg_cat_rows;   // adf_painn_debug_row_maxima: rows of the last emitting message / vec_proj launch
+    // adf_painn_debug_row_maxima(which = 4) switches capture on: vec_proj then emits its slots on the public per-layer entry too
+    // (nobody reads them there but the hook), and update_layer keeps a copy of the magnitudes it combined for its two
+    // products: dbg_mag[0 .. 3 rows) of the vec rows, dbg_mag[3 part_stride ..] of the [x | |v2|] rows
+    bool dbg_capture;
+    float* dbg_mag;
+    int dbg_comb_rows;
 
     // ---- grow-only workspaces
     int64_t capN, capB, capE;
@@ -231,6 +253,9 @@ int32_t adf_launch_gemm16(const float* A, int lda, const adf_w16* W, const float
 // m_dev / m_mul: rows = min(M, *m_dev * m_mul) when the count lives on the device (m_mul = 3: [N,3,K] vector rows)
 int32_t adf_launch_rowmag(const float* A, int lda, int K1, const float* A2, int K2, long long M, float* mag, hipStream_t s,
                           const int32_t* m_dev = nullptr, int m_mul = 1);
+// mag[r] = max over p < nparts of part[p * stride + r], r < M (partial row maxima written by the rows' producers)
+int32_t adf_launch_rowmax_combine(const float* part, long long stride, int nparts, long long M, float* mag, hipStream_t s,
+                                  const int32_t* m_dev = nullptr, int m_mul = 1);
 int32_t adf_split_weight(const float* w, long long n, adf_w16* out, unsigned int* scratch_bits, hipStream_t s,
                          int perm_H = 0, int K = 0, const float* bias = nullptr, int parts = 3);
 int32_t adf_launch_gemm16_vecnorm(const float* A, int lda, const adf_w16* W, float* nrm, int M, int N, int K,
@@ -256,6 +281,31 @@ int32_t adf_energy_sum(const float* y, int H2, const float* w, const float* bias
                        int num_systems, hipStream_t s);
 // ScaledSiLU f(x) = x sigmoid(x) / 0.6 and f'(x) w, as the energy head's backward evaluates them: the seed of the energy
 // gradient (energy_grad.hip) and adf_op_energy_head_bwd (s2ef_train.hip) share the one expression
+// max over the 16 lanes of a DPP row (non-negative values), left in every lane: four v_max_f32 with row rotations
+__device__ __forceinline__ float adf_row16_max(float v) {
+#define ADF_ROR(n_) __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x120 + (n_), 0xf, 0xf, false))
+    v = fmaxf(v, ADF_ROR(8));
+    v = fmaxf(v, ADF_ROR(4));
+    v = fmaxf(v, ADF_ROR(2));
+    v = fmaxf(v, ADF_ROR(1));
+#undef ADF_ROR
+    return v;
+}
+// max over the 32 lanes of a half-wave (non-negative values), left in lanes 16-31 of the half: adf_row16_max, then lane 15
+// of DPP rows 0 / 2 is broadcast into rows 1 / 3 (row_bcast:15, row mask 0xa; rows 0 / 2 receive 0)
+__device__ __forceinline__ float adf_half32_max_hi(float v) {
+    v = adf_row16_max(v);
+    return fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x142, 0xa, 0xf, false)));
+}
+// max over aligned groups of 8 lanes (non-negative values), left in every lane: two quad permutes, then row_half_mirror
+__device__ __forceinline__ float adf_lane8_max(float v) {
+#define ADF_DPP(c_) __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), (c_), 0xf, 0xf, false))
+    v = fmaxf(v, ADF_DPP(0xb1));    // quad_perm [1,0,3,2]
+    v = fmaxf(v, ADF_DPP(0x4e));    // quad_perm [2,3,0,1]
+    v = fmaxf(v, ADF_DPP(0x141));   // row_half_mirror: lane i <-> 7 - i
+#undef ADF_DPP
+    return v;
+}
 __device__ __forceinline__ float adf_ssilu(float x) { return x / (1.0f + expf(-x)) * 1.6666666666666667f; }
 __device__ __forceinline__ float adf_dssilu_times(float x, float w) {
     const float sg = 1.0f / (1.0f + expf(-x));
@@ -281,7 +331,8 @@ size_t adf_scan_temp_bytes(int64_t n);
 int32_t adf_message_impl(adf_painn* h, int layer, int N, const float* x, const float* xh, const float* vec,
                          float* x_out, float* vec_out, bool vec_is_zero, hipStream_t s,
                          const int32_t* tlist = nullptr, int n_targets = 0, const float* rec = nullptr,
-                         const int32_t* n_targets_dev = nullptr);  // n_targets_dev: the list length lives on the device
+                         const int32_t* n_targets_dev = nullptr,   // n_targets_dev: the list length lives on the device
+                         float* xpart = nullptr, float* vpart = nullptr, long long part_stride = 0);  // MsgParams::xpart
 int32_t adf_pack_rbf(adf_painn* h, hipStream_t s);
 int32_t adf_pack_rbf_layer(adf_painn* h, int l, hipStream_t s);
 int32_t adf_pack_records(adf_painn* h, int N, const float* xh, const float* vec, bool vec_is_zero, hipStream_t s,

@@ -31,6 +31,12 @@ typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 #define EPI_ABL 0   // timing experiments only (wrong results): bit 0 = EPI 1 without its epilogue, bit 1 = EPI 2 without,
                     // bit 2 = EPI 1/2 without their global loads, bit 3 = without their global stores
 #endif
+#ifndef EPI2_POLICY
+#define EPI2_POLICY 0   // cache policy of EPI 2's one-touch epilogue streams: bit 0 = the x / vec outputs stored sc1 (write-through:
+                        // the line is dropped from the XCD's L2 instead of kept), bit 1 = the v1 / dot / vec / x inputs loaded
+                        // non-temporally.  Same sites; each measured alone against 0: node products inside the run-to-run spread,
+                        // EPI 2's L2 hit rate 0.65 -> 0.56 / 0.57 (profiles/NOTES.md, row maxima section): left off
+#endif
 #ifndef G16_ABL
 #define G16_ABL 0   // timing experiments only (wrong results; harness builds): 1 = vec_proj epilogue without its global stores,
                     // 2 = A tile staged without the fp32 -> hi/lo conversion, 4 = A rows all read from row 0 (cache-hot),
@@ -60,17 +66,6 @@ __device__ __forceinline__ float adf_pow2_lift(float mx) {
 __device__ __forceinline__ float ssilu16(float x) {
     float s = x / (1.0f + expf(-x));
     return s * 1.6666666666666667f;
-}
-
-// max over the 16 lanes of a DPP row (non-negative values), left in every lane: four v_max_f32 with row rotations
-__device__ __forceinline__ float adf_row16_max(float v) {
-#define ADF_ROR(n_) __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x120 + (n_), 0xf, 0xf, false))
-    v = fmaxf(v, ADF_ROR(8));
-    v = fmaxf(v, ADF_ROR(4));
-    v = fmaxf(v, ADF_ROR(2));
-    v = fmaxf(v, ADF_ROR(1));
-#undef ADF_ROR
-    return v;
 }
 
 // Workgroup = 4 waves as 2(M) x 2(N); wave tile = (32*MI) rows x (32*NJ) columns of MFMA 32x32 blocks.
@@ -507,13 +502,21 @@ __global__ __launch_bounds__(128 * NWN, (MI == 4 || NWN == 4 ? 1 : 2)) void adf_
         for (int it = 0; it < 4; ++it) {
             const int lr = it * 8 + (lane >> 3), c4 = lane & 7;
             const int n = a0 + lr, c = 32 * g + 4 * c4;
+            const float4 dv_ = *reinterpret_cast<const float4*>(T + lr * TLD3 + 4 * c4);
+            const float4 nv_ = *reinterpret_cast<const float4*>(T + lr * TLD3 + 32 + 4 * c4);
             if (n < M) {
-                const float4 dv_ = *reinterpret_cast<const float4*>(T + lr * TLD3 + 4 * c4);
-                const float4 nv_ = *reinterpret_cast<const float4*>(T + lr * TLD3 + 32 + 4 * c4);
                 if (G16_ABL & 1) { asm volatile("" :: "v"(dv_.x), "v"(nv_.w)); } else {
                 *reinterpret_cast<float4*>(ep.dotw + (size_t)n * H + c) = dv_;
                 *reinterpret_cast<float4*>(ep.cat + (size_t)n * H + c) = nv_;
                 }
+            }
+            if (ep.catpart) {
+                // max |v2| of row n over this wave's 32 channels, for the row lifts of the product that reads [x | |v2|]: the
+                // 8 lanes that hold the row reduce by DPP and one of them stores the slot of (group g, row n) - a plain store,
+                // no other writer.  Outside the row guard: every lane takes part in the permutes (rows beyond M hold the
+                // clamped last row's values and are not stored).
+                const float mg = adf_lane8_max(fmaxf(fmaxf(fmaxf(0.f, fabsf(nv_.x)), fabsf(nv_.y)), fmaxf(fabsf(nv_.z), fabsf(nv_.w))));
+                if (c4 == 0 && n < M) ep.catpart[(size_t)g * ep.part_stride + n] = mg;
             }
         }
     } else if constexpr (EPI == 4) {
@@ -625,14 +628,22 @@ __global__ __launch_bounds__(128 * NWN, (MI == 4 || NWN == 4 ? 1 : 2)) void adf_
                 for (int it = 0; it < 4; ++it) {
                     const int n = min(m0 + wm + 32 * i + it * 8 + (lane >> 3), M - 1);
                     const size_t xo = (size_t)n * H + c;
-                    d[it] = *reinterpret_cast<const float4*>(ep.dot + xo);
-                    xv[it] = *reinterpret_cast<const float4*>(ep.x + xo);
+#if EPI2_POLICY & 2
+                    typedef float f32x4_t __attribute__((ext_vector_type(4)));
+                    auto ntld = [](const float* p_) { const f32x4_t v = __builtin_nontemporal_load(reinterpret_cast<const f32x4_t*>(p_));
+                                                      return make_float4(v.x, v.y, v.z, v.w); };
+#define EPI2_LD(p_) ntld(p_)
+#else
+#define EPI2_LD(p_) (*reinterpret_cast<const float4*>(p_))
+#endif
+                    d[it] = EPI2_LD(ep.dot + xo);
+                    xv[it] = EPI2_LD(ep.x + xo);
                     const float* vr = ep.vec + (size_t)n * 3 * H + c;
                     const float* v1p = ep.vv + (size_t)n * 3 * H + c;  // v1 [N,3,H] written by EPI 3
 #pragma unroll
                     for (int ax = 0; ax < 3; ++ax) {
-                        w1[it][ax] = *reinterpret_cast<const float4*>(v1p + ax * H);
-                        tv[it][ax] = *reinterpret_cast<const float4*>(vr + ax * H);
+                        w1[it][ax] = EPI2_LD(v1p + ax * H);
+                        tv[it][ax] = EPI2_LD(vr + ax * H);
                     }
                 }
 #pragma unroll
@@ -648,17 +659,28 @@ __global__ __launch_bounds__(128 * NWN, (MI == 4 || NWN == 4 ? 1 : 2)) void adf_
                     xo4.y = (xo4.y + (p0.y + p1.y * d[it].y) * k2) * sc;
                     xo4.z = (xo4.z + (p0.z + p1.z * d[it].z) * k2) * sc;
                     xo4.w = (xo4.w + (p0.w + p1.w * d[it].w) * k2) * sc;
+#undef EPI2_LD
+#if EPI2_POLICY & 1
+                    // buffer stores with aux = sc1; descriptors over the whole x / vec arrays (wave-uniform, < 4 GB: check_a_span)
+                    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+                    const auto rx = __builtin_amdgcn_make_buffer_rsrc(ep.x, 0, (int)((unsigned int)M * (unsigned int)H * 4u), 0x00020000);
+                    const auto rv = __builtin_amdgcn_make_buffer_rsrc(ep.vec, 0, (int)((unsigned int)M * 3u * (unsigned int)H * 4u), 0x00020000);
+#define EPI2_ST(r_, p_, base_, v_) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v_), r_, (int)(((p_) - (base_)) * 4), 0, 16)
+#else
+#define EPI2_ST(r_, p_, base_, v_) (*reinterpret_cast<float4*>(p_) = (v_))
+#endif
                     if (n < M) {
-                        *reinterpret_cast<float4*>(ep.x + (size_t)n * H + c) = xo4;
+                        EPI2_ST(rx, ep.x + (size_t)n * H + c, ep.x, xo4);
                         float* vr = ep.vec + (size_t)n * 3 * H + c;
 #pragma unroll
                         for (int ax = 0; ax < 3; ++ax) {
                             float4 t = tv[it][ax];
                             const float4 v1 = w1[it][ax];
                             t.x += p2.x * v1.x; t.y += p2.y * v1.y; t.z += p2.z * v1.z; t.w += p2.w * v1.w;
-                            *reinterpret_cast<float4*>(vr + ax * H) = t;
+                            EPI2_ST(rv, vr + ax * H, ep.vec, t);
                         }
                     }
+#undef EPI2_ST
                 }
             }
             __builtin_amdgcn_wave_barrier();  // T is rewritten for the next 32-row block
@@ -692,6 +714,27 @@ __global__ __launch_bounds__(256) void adf_rowmag_kernel(const float* __restrict
     if (lane == 0) mag[r] = mx;
 }
 
+// mag[r] = max over the parts of part[p * stride + r]: the slots the producers of the rows wrote (message.hip's target
+// finish, EPI 3's epilogue).  8 to 24 dwords read per row where adf_rowmag_kernel reads the 2 to 4 KB of the row itself.
+__global__ __launch_bounds__(256) void adf_rowmax_combine_kernel(const float* __restrict__ part, long long stride, int nparts,
+                                                                 long long M, float* __restrict__ mag,
+                                                                 const int32_t* __restrict__ m_dev, int m_mul) {
+    const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (r >= M || (m_dev && r >= (long long)*m_dev * m_mul)) return;
+    float mx = 0.f;
+    for (int p = 0; p < nparts; ++p) mx = fmaxf(mx, part[(size_t)p * stride + r]);
+    mag[r] = mx;
+}
+
+int32_t adf_launch_rowmax_combine(const float* part, long long stride, int nparts, long long M, float* mag, hipStream_t s,
+                                  const int32_t* m_dev, int m_mul) {
+    if (M <= 0) return ADF_OK;
+    hipLaunchKernelGGL(adf_rowmax_combine_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, part, stride, nparts, M,
+                       mag, m_dev, m_mul);
+    ADF_HIP_CHECK(hipGetLastError());
+    return ADF_OK;
+}
+
 int32_t adf_launch_rowmag(const float* A, int lda, int K1, const float* A2, int K2, long long M, float* mag, hipStream_t s,
                           const int32_t* m_dev, int m_mul) {
     if (M <= 0) return ADF_OK;
@@ -707,6 +750,13 @@ int32_t adf_launch_rowmag(const float* A, int lda, int K1, const float* A2, int 
 // (Round 6: ONE pass over the vec rows and the x rows of a layer + norm(v2)'s row maxima raised from vec_proj's epilogue by
 // atomicMax, instead of the two passes (vec; [x | norm(v2)]): identical sites, node products 1672 / 1676 ms per pass with and
 // 1673 / 1677 without - the epilogue's atomics cost what the second pass did.)
+// (What replaced both layer passes: the rows' producers - the message kernel's target finish, EPI 3's epilogue - write the
+// maximum over the columns they own into a slot of their own with plain stores, and adf_rowmax_combine_kernel takes the
+// maximum over a row's slots; api.hip update_layer hands the result in as `premag`.  No atomics, no memset.  Identical sites;
+// five alternating runs each at 1000 systems: node products 1674 -> 1588 ms per pass, message kernel 1918 -> 1942, 245.3 ->
+// 249.3 sites/s (spread of the parent's runs 0.7).  The same scheme for EPI 0's out_mag - one slot per column tile through LDS,
+// the consumer's prologue taking the maximum of the two - instead of atomicMax behind a memset: node products + 4 to 6 ms per
+// pass, not kept: profiles/NOTES.md.)
 // (Round 6, again: the eight-wave vec_proj kernel measuring its own 192 rows in a prologue - one wave per row, eight rows in
 // flight - instead of the adf_rowmag pass over `vec`: identical sites, node products 1647 -> 2014 ms per pass.  At one workgroup
 // per CU nothing overlaps the prologue's three dependent HBM round trips.)

@@ -34,6 +34,13 @@ struct MsgParams {
     float dmu2, dmusq, cstep;  // UNI: 2*dmu', dmu'^2, exp2(-2 dmu'^2) with dmu' = scaled spacing of the centres
     int env_pi;
     unsigned long long* kcount;  // optional: sum over 32-row blocks of contracted k length x 32-column blocks run (profiling)
+    // optional (adf_message_kernel only; null = none): partial row maxima of the output rows, over this slice's 64 channels:
+    // xpart[slice * part_stride + orow] = max |x_out|, vpart[slice * 3 part_stride + 3 orow + axis] = max |vec_out[axis]|.
+    // Plain stores, one writer per slot, every target writes its four: the arrays need no zeroing.  Slice-major: a cache
+    // line of them is only ever written by one XCD (slice = XCD, a workgroup's targets are runs of 32 consecutive rows).
+    float* xpart;
+    float* vpart;
+    long long part_stride;
 };
 // message_bwd.hip: gradient records of (d(x1), d(vec1)) into h->rec; dx (optional) = d(x1) / sqrt2
 int32_t adf_pack_grad_records(adf_painn* h, const float* gx1, const float* gv1, float* dx, hipStream_t s);

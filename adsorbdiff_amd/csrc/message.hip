@@ -480,16 +480,34 @@ __global__ __launch_bounds__(FWD_THREADS, MSG_WAVES_PER_SIMD) void adf_message_k
                 // lane q owns channels c0+q and c0+32+q; half-wave 0 writes x and vec_x, half-wave 1 vec_y, vec_z
                 const size_t xo = (size_t)orow * H + c0 + q;
                 const size_t vo = (size_t)orow * 3 * H + c0 + q;
+                float o0, o1, o2, o3;
                 if (hi == 0) {
-                    p.x_out[xo] = (res0 + sx0) * inv_sqrt2;
-                    p.x_out[xo + 32] = (res1 + sx1) * inv_sqrt2;
-                    p.vec_out[vo] = res2 + sa0;
-                    p.vec_out[vo + 32] = res3 + sa1;
+                    o0 = (res0 + sx0) * inv_sqrt2; o1 = (res1 + sx1) * inv_sqrt2;
+                    o2 = res2 + sa0; o3 = res3 + sa1;
+                    p.x_out[xo] = o0;
+                    p.x_out[xo + 32] = o1;
+                    p.vec_out[vo] = o2;
+                    p.vec_out[vo + 32] = o3;
                 } else {
-                    p.vec_out[vo + H] = res0 + sb0;
-                    p.vec_out[vo + H + 32] = res1 + sb1;
-                    p.vec_out[vo + 2 * H] = res2 + sc0;
-                    p.vec_out[vo + 2 * H + 32] = res3 + sc1;
+                    o0 = res0 + sb0; o1 = res1 + sb1;
+                    o2 = res2 + sc0; o3 = res3 + sc1;
+                    p.vec_out[vo + H] = o0;
+                    p.vec_out[vo + H + 32] = o1;
+                    p.vec_out[vo + 2 * H] = o2;
+                    p.vec_out[vo + 2 * H + 32] = o3;
+                }
+                if (p.xpart) {
+                    // This slice's share of the rows' magnitudes for the f16x3 products that read them (gemm16.hip row lifts;
+                    // same fmaxf(0, |.|) form as adf_rowmag_kernel): half-wave 0 holds max|x|, max|vec_x| over its 32 lanes'
+                    // 64 channels, half-wave 1 max|vec_y|, max|vec_z|.  DPP only, four plain dword stores per target; a target
+                    // without in-edges passes here like any other, so every slot of every row is written.
+                    const float mA = adf_half32_max_hi(fmaxf(fmaxf(0.f, fabsf(o0)), fabsf(o1)));
+                    const float mB = adf_half32_max_hi(fmaxf(fmaxf(0.f, fabsf(o2)), fabsf(o3)));
+                    if (q == 16) {
+                        float* vp = p.vpart + (size_t)slice * 3 * p.part_stride + (size_t)orow * 3;
+                        if (hi == 0) { p.xpart[(size_t)slice * p.part_stride + orow] = mA; vp[0] = mB; }
+                        else { vp[1] = mA; vp[2] = mB; }
+                    }
                 }
                 sx0 = sx1 = sa0 = sa1 = sb0 = sb1 = sc0 = sc1 = 0.f;
                 ra0 = ra1 = rb0 = rb1 = rc0 = rc1 = 0.f;
@@ -655,7 +673,8 @@ int32_t adf_pack_rbf(adf_painn* h, hipStream_t s) {
 
 int32_t adf_message_impl(adf_painn* h, int layer, int N, const float* x, const float* xh, const float* vec,
                          float* x_out, float* vec_out, bool vec_is_zero, hipStream_t s, const int32_t* tlist,
-                         int n_targets, const float* rec, const int32_t* n_targets_dev) {
+                         int n_targets, const float* rec, const int32_t* n_targets_dev, float* xpart, float* vpart,
+                         long long part_stride) {
     const int H = h->hp.hidden_channels, R = h->hp.num_rbf;
     if ((unsigned long long)(N + 1) * 5ull * H * sizeof(float) >= (1ull << 32)) {
         adf_set_error("message kernel uses 32-bit byte offsets into the node tables: N=%d is too large, split the batch", N);
@@ -685,6 +704,7 @@ int32_t adf_message_impl(adf_painn* h, int layer, int N, const float* x, const f
     p.env_b = (float)(pe * (pe + 2));
     p.env_c = (float)(-pe * (pe + 1) / 2);
     p.kcount = h->prof_on ? h->kcount : nullptr;
+    p.xpart = xpart; p.vpart = xpart ? vpart : nullptr; p.part_stride = part_stride;
     int workers = h->num_cus / p.nslices;
     if (workers < 1) workers = 1;
     if (workers > p.G) workers = p.G;

@@ -23,6 +23,7 @@ EXPORTS = (
     "adf_painn_create", "adf_painn_destroy", "adf_painn_set_weights", "adf_graph_build", "adf_graph_set_moving",
     "adf_check_flags", "adf_painn_set_arithmetic", "adf_painn_set_incremental", "adf_painn_set_fused_mlp",
     "adf_graph_export", "adf_painn_forward", "adf_painn_forward_subset", "adf_linear_forward", "adf_painn_message_layer", "adf_painn_update_layer",
+    "adf_painn_debug_row_maxima",
     "adf_sde_init_placement", "adf_sde_step", "adf_sde_step_scheduled", "adf_sample", "adf_sample_traj",
     "adf_tr_step", "adf_tr_sample", "adf_tr_sample_traj",
     "adf_painn_set_energy_head", "adf_painn_set_distance_floor", "adf_painn_forward_energy",
@@ -137,6 +138,7 @@ def load():
         "adf_painn_message_layer": [vp, i32, i32, vp, vp, vp, vp, vp],
         "adf_linear_forward": [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
         "adf_painn_update_layer": [vp, i32, i32, vp, vp, vp],
+        "adf_painn_debug_row_maxima": [vp, i32, vp, C.c_int64, C.POINTER(i32), vp],
         "adf_sde_init_placement": [vp, C.POINTER(BatchDesc), vp, vp, vp, vp],
         "adf_sde_step": [vp, C.POINTER(BatchDesc), vp, vp, vp, vp, vp, C.POINTER(StepCoef), vp, vp, i32, vp, vp, vp, vp],
         "adf_sde_step_scheduled": [vp, C.POINTER(BatchDesc), vp, vp, vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp],

@@ -182,6 +182,18 @@ int32_t adf_painn_message_layer(adf_painn_t h, int32_t layer, int32_t num_atoms,
 /* PaiNNUpdate.forward + residual + ScaleFactor (painn_denoising.py:447-451,601-623), in place. */
 int32_t adf_painn_update_layer(adf_painn_t h, int32_t layer, int32_t num_atoms, float* x, float* vec,
                                void* stream);
+/* Test hook for the row maxima that the f16x3 path takes from the kernels that write the rows (ADF_ROW_MAXIMA, on by
+ * default) instead of measuring passes: the maxima of the last launch, combined over the producers' slots.
+ * which = 0: max|x_out| per row [rows] and 1: max|vec_out| per row and component [3 rows] of the last message launch;
+ * 2: max of every |v2| row [rows] of the last vec_proj launch (adf_painn_update_layer); 3: the |v2| rows themselves
+ * [rows, H].  which = 4 switches capture on (capacity != 0) or off and returns nothing: while it is on, vec_proj leaves its
+ * slots on the per-layer entry above too (otherwise only where the library reads them) and the library keeps a copy of the
+ * magnitudes it combined from the slots; which = 5 / 6 return that copy: the magnitudes of the vec rows [3 rows] / of the
+ * [x | |v2|] rows [rows] as the last layer of the last forward handed them to its products.
+ * *rows (optional) receives the row count; out: device floats, `capacity` of them (NULL: only query rows).
+ * ADF_EINVAL when no launch has emitted maxima. */
+int32_t adf_painn_debug_row_maxima(adf_painn_t h, int32_t which, float* out, int64_t capacity, int32_t* rows,
+                                   void* stream);
 
 /* Stand-alone torch.nn.functional.linear (+ optional ScaledSiLU) on device pointers, A[M,K]
  * W[N,K] bias[N] C[M,N] contiguous; K % 32 == 0.  mode 0: exact-f32 MFMA (gemm.hip); mode 1:
