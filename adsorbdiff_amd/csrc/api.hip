@@ -20,6 +20,42 @@ void adf_set_error(const char* fmt, ...) {
 extern "C" const char* adf_last_error(void) { return g_err; }
 extern "C" const char* adf_version(void) { return "adsorbdiff_hip 0.5.0 (gfx950)"; }
 
+// ---- the kernel-selection switches (adf_tune): the one place that reads them
+adf_tune adf_tune_from_env() {
+    auto off_is_0 = [](const char* name) { const char* e = getenv(name); return (e && atoi(e) == 0) ? 0 : 1; };
+    auto is_f32 = [](const char* name) { const char* e = getenv(name); return e && strcmp(e, "f32") == 0; };
+    adf_tune t = {};
+    const char* mi = getenv("ADF_GEMM16_MI");
+    t.gemm16_mi = (mi && atoi(mi) == 4) ? 4 : 2;
+    t.gemm_w8_plain = off_is_0("ADF_GEMM_W8_PLAIN");
+    t.gemm_w8 = off_is_0("ADF_GEMM_W8");
+    t.gemm_wreg = off_is_0("ADF_GEMM_WREG");
+    const char* wf = getenv("ADF_GEMM_WR_FUSED");
+    t.gemm_wr_fused = wf ? atoi(wf) : 2;
+    if (t.gemm_wr_fused != 0 && t.gemm_wr_fused != 4) t.gemm_wr_fused = 2;
+    t.head_gate_fused = off_is_0("ADF_HEAD_GATE_FUSED");
+    t.lift_emit = off_is_0("ADF_LIFT_EMIT");
+    t.graph_sys_csr = off_is_0("ADF_GRAPH_SYS_CSR");
+    t.train_gemm16 = is_f32("ADF_TRAIN_GEMM") ? 0 : 1;
+    t.wgrad_f32 = is_f32("ADF_WGRAD") ? 1 : 0;
+    const char* pw = getenv("ADF_EQV2_PW_MI");
+    t.eqv2_pw_mi = (pw && atoi(pw) == 3) ? 3 : 4;
+    const char* gt = getenv("ADF_EQV2_GEMM_TILE");
+    t.eqv2_gemm_tile256 = (gt && atoi(gt) == 128) ? 0 : 1;
+    t.eqv2_rotin_generic = getenv("ADF_EQV2_ROTIN_GENERIC") != nullptr;
+    t.eqv2_rotout_generic = getenv("ADF_EQV2_ROTOUT_GENERIC") != nullptr;
+    return t;
+}
+const adf_tune& adf_tune_process() {
+    static const adf_tune t = adf_tune_from_env();   // read once per process; the initialisation is thread-safe
+    return t;
+}
+int adf_current_num_cus() {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
+    return n;
+}
+
 // ---- HIP-event profiling: pairs of events on the launch stream around kernel groups
 void adf_prof_begin(adf_painn* h, int cat, hipStream_t s) {
     if (!h->prof_on) return;
@@ -147,11 +183,6 @@ extern "C" int32_t adf_painn_create(const adf_painn_hparams* hp, adf_painn_t* ou
         if (st == ADF_OK) st = dev_alloc(&h->w16_bias_perm, (size_t)L * 2 * 3 * H);
         if (st == ADF_OK) st = dev_alloc(&h->w16_scratch, 1);
         if (st == ADF_OK) st = dev_alloc(&h->wfrag_arena, h->w16_bytes);
-        {   // form of the x_proj / xvec_proj pairs: the two-kernel form unless asked otherwise (mlp16.hip: measured slower)
-            const char* ef = getenv("ADF_FUSED_MLP");
-            h->fused_mlp = ef ? atoi(ef) : 0;
-            if (h->fused_mlp < 0 || h->fused_mlp > 2) h->fused_mlp = 0;
-        }
         const char* e = getenv("ADF_GEMM");
         h->gemm_f32 = e && strcmp(e, "f32") == 0;
         const char* el = getenv("ADF_LIFT");
@@ -160,6 +191,7 @@ extern "C" int32_t adf_painn_create(const adf_painn_hparams* hp, adf_painn_t* ou
         h->msg_f32 = e2 ? strcmp(e2, "f32") == 0 : h->gemm_f32;
         const char* er = getenv("ADF_ROW_MAXIMA");   // row maxima from the producers (common.h: adf_painn::rmx)
         h->rmx = (er && atoi(er) == 0) ? 0 : 1;
+        h->tune = adf_tune_from_env();
     }
     if (st == ADF_OK) st = dev_alloc(&h->kcount, 8);
     if (st == ADF_OK && hipMemset(h->kcount, 0, 8 * sizeof(unsigned long long)) != hipSuccess) st = ADF_EHIP;
@@ -502,15 +534,6 @@ static int32_t zero_pad_rows(adf_painn* h, int N, hipStream_t s) {
 
 // Gather records of layer l for the n rows (x, vec): xh = x_proj(LayerNorm(x)) (painn_denoising.py:531), packed with
 // vec for the message kernel.  row_map != null: row r of (x, vec) is atom row_map[r] of the record table.
-// The fused two-layer kernel (mlp16.hip) or the two-kernel form of the x_proj / xvec_proj pairs?  Same bits either way.
-// By size (mode 2): a 64-row tile per CU wants at least two rounds of tiles on the chip; below that the 128 x 192 tiles of
-// the two-kernel form spread a small batch over more CUs (B = 1: 200 rows are 4 fused tiles against 16 workgroups).
-static bool use_fused_mlp(const adf_painn* h, int rows) {
-    if (h->hp.hidden_channels != 512 || h->gemm_f32 || h->fused_mlp == 0) return false;
-    if (h->fused_mlp == 1) return true;
-    return rows >= 2 * 64 * h->num_cus;
-}
-
 static int32_t make_records(adf_painn* h, int l, int n, const float* x, const float* vec, bool vec_is_zero, float* rec,
                             const int32_t* row_map, hipStream_t s) {
     const int H = h->hp.hidden_channels;
@@ -518,21 +541,9 @@ static int32_t make_records(adf_painn* h, int l, int n, const float* x, const fl
     if (n <= 0) return ADF_OK;
     adf_prof_begin(h, ADF_PROF_NODE, s);
     const bool lift = h->lift_on && !h->gemm_f32;
-    static int emit = -1;
-    if (emit < 0) { const char* e = getenv("ADF_LIFT_EMIT"); emit = (e && atoi(e) == 0) ? 0 : 1; }
-    const bool em = lift && emit;
+    const bool em = lift && h->tune.lift_emit;
     // row magnitudes travel with the rows: LayerNorm -> x_proj.0 -> (its epilogue) -> x_proj.2
     ADF_TRY(adf_nodewise_layernorm(x, w.ln_w, w.ln_b, h->y, n, H, s, em ? h->mag_a : nullptr, h->rows_dev));
-    if (use_fused_mlp(h, n) && (em || !lift)) {   // x_proj.0 -> x_proj.2 -> records in one kernel (mlp16.hip), same bits
-        adf_epi ep = {};
-        ep.vec_in = vec; ep.rec = rec ? rec : h->rec; ep.H = H; ep.vec_is_zero = vec_is_zero ? 1 : 0;
-        ep.row_map = row_map; ep.m_dev = h->rows_dev; ep.lift_y = lift ? 1 : 0;
-        ep.rec_rows = row_map ? (long long)h->inc_capN : (long long)n;   // mapped rows index the whole kept table
-        ADF_TRY(adf_launch_mlp16(h->y, nullptr, H, em ? h->mag_a : nullptr, w.xp0_16.frag, &w.xp0_16, w.xp0_b, w.xp2_16.frag, &w.xp2_16, n,
-                                 H, 1, &ep, s));
-        adf_prof_end(h, s);
-        return ADF_OK;
-    }
     ADF_TRY(adf_linear(h, h->y, H, w.xp0_w, &w.xp0_16, w.xp0_b, h->cat, H, n, H, H, 1, s, em ? h->mag_a : nullptr,
                        em ? h->mag_b : nullptr));
     if (h->gemm_f32) {
@@ -545,7 +556,7 @@ static int32_t make_records(adf_painn* h, int l, int n, const float* x, const fl
         ep.row_map = row_map;
         ep.rmag = em ? h->mag_b : nullptr;
         ep.m_dev = h->rows_dev;
-        ADF_TRY(adf_launch_gemm16_fused(h->cat, H, &w.xp2_16, n, H, H, 1, &ep, s, lift ? &h->lift : nullptr));
+        ADF_TRY(adf_launch_gemm16_fused(h->cat, H, &w.xp2_16, n, H, H, 1, &ep, s, h->tune, lift ? &h->lift : nullptr));
     }
     adf_prof_end(h, s);
     return ADF_OK;
@@ -612,7 +623,7 @@ static int32_t update_layer(adf_painn* h, int l, int N, float* x, float* vec, hi
         if (parts || (h->dbg_capture && h->rmx && lf && N <= h->part_stride)) {
             ep.catpart = h->catpart; ep.part_stride = h->part_stride; h->dbg_cat_rows = N;
         }
-        ADF_TRY(adf_launch_gemm16_fused(vec, H, &w.vp_16, N, H, H, 3, &ep, s, lf));
+        ADF_TRY(adf_launch_gemm16_fused(vec, H, &w.vp_16, N, H, H, 3, &ep, s, h->tune, lf));
         if (parts) {   // [x | |v2|]: xpart and catpart lie side by side
             ADF_TRY(adf_launch_rowmax_combine(h->xpart, h->part_stride, H / ADF_SLICE_CH + H / 32, N, h->lift.buf, s, h->rows_dev, 1));
             if (h->dbg_capture) {
@@ -620,22 +631,11 @@ static int32_t update_layer(adf_painn* h, int l, int N, float* x, float* vec, hi
                 h->dbg_comb_rows = N;
             }
         }
-        if (use_fused_mlp(h, N)) {   // xvec_proj.0 -> xvec_proj.2 -> gating in one kernel (mlp16.hip), same bits
-            const float* rm = nullptr;
-            if (lf) {
-                if (N > lf->cap) { adf_set_error("mlp16: lift scratch holds %lld rows, need %d", lf->cap, N); return ADF_EINVAL; }
-                if (!parts) ADF_TRY(adf_launch_rowmag(x, H, H, h->cat, H, N, lf->buf, s, h->rows_dev, 1));
-                rm = lf->buf;
-            }
-            adf_epi e2 = {};
-            e2.x = x; e2.vec = vec; e2.dot = h->dot; e2.vv = h->vv; e2.scale = h->scale[l]; e2.H = H;
-            e2.m_dev = h->rows_dev; e2.lift_y = h->lift_on ? 1 : 0;
-            const int32_t stf = adf_launch_mlp16(x, h->cat, H, rm, w.xv0_16.frag, &w.xv0_16, w.xv0_b, w.xv2_16.frag, &w.xv2_16, N, H, 2, &e2, s);
-            adf_prof_end(h, s);
-            return stf;
-        }
-        ADF_TRY(adf_launch_gemm16(x, H, &w.xv0_16, w.xv0_b, h->y, H, N, H, 2 * H, 1, s, h->cat, H, lf, parts ? h->lift.buf : nullptr,
-                                  h->lift_on ? h->mag_b : nullptr, h->rows_dev));
+        adf_epi e0 = {};   // xvec_proj.0 on [x | |v2|]; its output rows' magnitudes go on to xvec_proj.2
+        e0.A2 = h->cat; e0.K1 = H; e0.m_dev = h->rows_dev;
+        e0.rmag = parts ? h->lift.buf : nullptr;
+        e0.out_mag = h->lift_on ? reinterpret_cast<unsigned int*>(h->mag_b) : nullptr;
+        ADF_TRY(adf_launch_gemm16(x, H, &w.xv0_16, w.xv0_b, h->y, H, N, H, 2 * H, 1, &e0, s, lf, h->tune, h->num_cus));
     }
     int32_t st;
     if (h->gemm_f32) {
@@ -646,7 +646,7 @@ static int32_t update_layer(adf_painn* h, int l, int N, float* x, float* vec, hi
         ep.x = x; ep.vec = vec; ep.dot = h->dot; ep.vv = h->vv; ep.scale = h->scale[l]; ep.H = H;
         ep.rmag = h->lift_on ? h->mag_b : nullptr;
         ep.m_dev = h->rows_dev;
-        st = adf_launch_gemm16_fused(h->y, H, &w.xv2_16, N, H, H, 2, &ep, s);
+        st = adf_launch_gemm16_fused(h->y, H, &w.xv2_16, N, H, H, 2, &ep, s, h->tune);
     }
     adf_prof_end(h, s);
     return st;
@@ -671,6 +671,13 @@ extern "C" int32_t adf_painn_update_layer(adf_painn_t h, int32_t layer, int32_t 
     }
     ADF_TRY(ensure_capacity(h, N, 1));
     return update_layer(h, layer, N, x, vec, (hipStream_t)stream, false);
+}
+
+// Test hook: the kernel selection the handle holds (read from the environment by adf_painn_create)
+extern "C" int32_t adf_painn_get_tune(adf_painn_t h, adf_tune* out) {
+    if (!h || !out) { adf_set_error("get_tune: null handle or output"); return ADF_EINVAL; }
+    *out = h->tune;
+    return ADF_OK;
 }
 
 // Test hook: the row maxima as the producers of the last launch left them, combined over their slots.  which = 0: max|x_out|
@@ -1105,7 +1112,8 @@ extern "C" int32_t adf_linear_forward(const float* A, const float* W, const floa
     const bool lift = !(el && strcmp(el, "0") == 0);
     if (st == ADF_OK && lift) st = dev_alloc(&mags, (size_t)M);
     adf_lift lf = {mags, M};
-    if (st == ADF_OK) st = adf_launch_gemm16(A, K, &w16, bias, C, N, M, N, K, act_ssilu, s, nullptr, 0, lift ? &lf : nullptr);
+    if (st == ADF_OK) st = adf_launch_gemm16(A, K, &w16, bias, C, N, M, N, K, act_ssilu, nullptr, s, lift ? &lf : nullptr,
+                                             adf_tune_process(), adf_current_num_cus());
     (void)hipStreamSynchronize(s);
     (void)hipFree(buf);
     if (mags) (void)hipFree(mags);
@@ -1126,12 +1134,6 @@ extern "C" int32_t adf_painn_set_arithmetic(adf_painn_t h, int32_t exact_f32) {
 // Incremental layers (see incremental.hip): 1 = keep per-layer node state across the forwards of a static-atom promise
 // and recompute only rows whose inputs changed (default; bit-identical outputs), 0 = every forward computes every row.
 // Resets the row counters reported by adf_get_counters.
-extern "C" int32_t adf_painn_set_fused_mlp(adf_painn_t h, int32_t mode) {
-    if (!h || mode < 0 || mode > 2) { adf_set_error("set_fused_mlp: mode must be 0 (never), 1 (always) or 2 (by size)"); return ADF_EINVAL; }
-    h->fused_mlp = mode;
-    return ADF_OK;
-}
-
 extern "C" int32_t adf_painn_set_incremental(adf_painn_t h, int32_t on) {
     if (!h) { adf_set_error("null handle"); return ADF_EINVAL; }
     if ((on != 0) != h->inc_on) {

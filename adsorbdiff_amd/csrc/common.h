@@ -41,7 +41,7 @@ struct adf_w16 {
     void* lo;
     float* inv_scale;  // device scalar: 1 / (power-of-two scale applied before the split)
     float* bias_perm;  // row-permuted bias of the fused 3H-wide layers (else null)
-    void* frag;        // fragment-ordered image of hi / lo (adf_pack_frag, mlp16.hip): the B operands of v_mfma_f32_32x32x16_f16
+    void* frag;        // fragment-ordered image of hi / lo (adf_pack_frag, gemm16.hip): the B operands of v_mfma_f32_32x32x16_f16
                        // as the lanes load them, for the kernels that stream weights straight into registers (null: none)
 };
 // operands of the fused GEMM epilogues (gemm16.hip)
@@ -70,10 +70,8 @@ struct adf_epi {
     // min(M, *m_dev); the launch is sized for M.  null = M.
     const int32_t* m_dev;
     int accumulate;          // EPI 0: C += A W^T (+ bias) instead of C = (the training step's accumulated data gradients)
-    int lift_y;              // mlp16.hip: lift the intermediate rows by their own power of two (= the engine's lift_on)
     const float* gate;       // EPI 0 (heads): multiply output row r, column c by gate[(r / 3) * gate_ld + c]  (null: no gate)
     int gate_ld;
-    long long rec_rows;      // mlp16.hip EPI 1: rows of the record table the (mapped) rows are written into (0 = the launch's rows)
     // Partial row maxima (see adf_painn::rmx): a producer writes, with plain stores, the maximum over the columns it owns
     // into a slot of its own, [part][part_stride]; adf_launch_rowmax_combine takes the maximum over the parts.
     float* catpart;          // EPI 3: max |v2| of row n over the 32 channels of group g -> catpart[g * part_stride + n]
@@ -117,9 +115,9 @@ struct adf_painn {
     float* w16_bias_perm;  // [L][2][3H] row-permuted biases of x_proj.2 / xvec_proj.2
     unsigned int* w16_scratch;
     unsigned char* wfrag_arena;   // fragment images of every split weight (adf_w16::frag), same size as w16_arena
-    int fused_mlp;                // 0 never (default), 1 always, 2 by size: adf_painn_set_fused_mlp / ADF_FUSED_MLP
     bool gemm_f32;
     bool msg_f32;
+    adf_tune tune;       // kernel-selection switches, read from the environment at creation (adf_tune_from_env)
     // per-row power-of-two lifts of the f16x3 products' A operands (default on; ADF_LIFT=0 = the unlifted split of rounds 1-2)
     bool lift_on;
     adf_lift lift;       // [3 capN] magnitudes a launcher measures itself
@@ -243,13 +241,19 @@ void adf_prof_end(adf_painn* h, hipStream_t s);
 // ---- kernels' host launchers (each enqueues on `s`, returns ADF_*)
 int32_t adf_launch_gemm(const float* A, int lda, const float* W, int ldw, const float* bias, float* C, int ldc,
                         int M, int N, int K, int act_ssilu, hipStream_t s);
-// lf: measure the A rows' magnitudes into lf->buf first (row lifts, see adf_epi::rmag); premag: they are already known
-// (written by the producer of A: LayerNorm, a previous product's out_mag); out_mag: emit the output rows' magnitudes
+// The kernel-selection switches (include/adsorbdiff_hip.h: adf_tune) as the environment sets them now.  Handles keep a
+// copy made at creation; callers without a handle (adf_linear_forward, the adf_op_* / tr_* operators of train.hip) share
+// adf_tune_process(): one copy read at its first use, and adf_current_num_cus(): the CU count of the current device.
+adf_tune adf_tune_from_env();
+const adf_tune& adf_tune_process();
+int adf_current_num_cus();
+// C = act(A W^T + bias) with EPI 0's operands in *ep (null: the plain product): A2 / K1, rmag (the A rows' magnitudes are
+// already known: written by the producer of A - LayerNorm, a previous product's out_mag), out_mag (emit the output rows'
+// magnitudes; zeroed here), m_dev, accumulate, gate / gate_ld.  lf: measure the A rows' magnitudes into lf->buf first (row
+// lifts, see adf_epi::rmag) unless ep->rmag has them.  num_cus: of the device the launch goes to (tile choice).
 int32_t adf_launch_gemm16(const float* A, int lda, const adf_w16* W, const float* bias, float* C, int ldc, int M,
-                          int N, int K, int act_ssilu, hipStream_t s, const float* A2 = nullptr, int K1 = 0,
-                          const adf_lift* lf = nullptr, const float* premag = nullptr, float* out_mag = nullptr,
-                          const int32_t* m_dev = nullptr, int accumulate = 0,   // m_dev: see adf_epi::m_dev
-                          const float* gate = nullptr, int gate_ld = 0);        // gate: see adf_epi::gate
+                          int N, int K, int act_ssilu, const adf_epi* ep, hipStream_t s, const adf_lift* lf,
+                          const adf_tune& tune, int num_cus);
 // m_dev / m_mul: rows = min(M, *m_dev * m_mul) when the count lives on the device (m_mul = 3: [N,3,K] vector rows)
 int32_t adf_launch_rowmag(const float* A, int lda, int K1, const float* A2, int K2, long long M, float* mag, hipStream_t s,
                           const int32_t* m_dev = nullptr, int m_mul = 1);
@@ -259,22 +263,23 @@ int32_t adf_launch_rowmax_combine(const float* part, long long stride, int npart
 int32_t adf_split_weight(const float* w, long long n, adf_w16* out, unsigned int* scratch_bits, hipStream_t s,
                          int perm_H = 0, int K = 0, const float* bias = nullptr, int parts = 3);
 int32_t adf_launch_gemm16_vecnorm(const float* A, int lda, const adf_w16* W, float* nrm, int M, int N, int K,
-                                  hipStream_t s, const adf_lift* lf = nullptr, const float* premag = nullptr);
+                                  hipStream_t s, const adf_tune& tune, const adf_lift* lf = nullptr,
+                                  const float* premag = nullptr);
 int32_t adf_launch_gemm16_fused(const float* A, int lda, const adf_w16* W, int M, int H, int K, int epi,
-                                const adf_epi* ep, hipStream_t s, const adf_lift* lf = nullptr);
+                                const adf_epi* ep, hipStream_t s, const adf_tune& tune, const adf_lift* lf = nullptr);
 // C = act(A . W^T + b): f16x3 split MFMA by default, exact-f32 MFMA when h->gemm_f32 (ADF_GEMM=f32)
 static inline int32_t adf_linear(const adf_painn* h, const float* A, int lda, const float* W, const adf_w16* W16,
                                  const float* bias, float* C, int ldc, int M, int N, int K, int act, hipStream_t s,
                                  const float* premag = nullptr, float* out_mag = nullptr) {
     if (h->gemm_f32) return adf_launch_gemm(A, lda, W, K, bias, C, ldc, M, N, K, act, s);
-    return adf_launch_gemm16(A, lda, W16, bias, C, ldc, M, N, K, act, s, nullptr, 0, h->lift_on ? &h->lift : nullptr,
-                             h->lift_on ? premag : nullptr, h->lift_on ? out_mag : nullptr, h->rows_dev);
+    adf_epi ep = {};
+    ep.m_dev = h->rows_dev;
+    if (h->lift_on) { ep.rmag = premag; ep.out_mag = reinterpret_cast<unsigned int*>(out_mag); }
+    return adf_launch_gemm16(A, lda, W16, bias, C, ldc, M, N, K, act, &ep, s, h->lift_on ? &h->lift : nullptr, h->tune,
+                             h->num_cus);
 }
-// mlp16.hip: fragment image of a split weight [N, K]; the fused two-layer product (see the kernel comment)
+// gemm16.hip: fragment image of a split weight [N, K]
 int32_t adf_pack_frag(const adf_w16* w, int N, int K, void* out, hipStream_t s);
-int32_t adf_launch_mlp16(const float* A1, const float* A2, int lda, const float* rmag, const void* W0f, const adf_w16* W0,
-                         const float* bias0, const void* W2f, const adf_w16* W2, int M, int H, int epi, const adf_epi* ep,
-                         hipStream_t s);
 int32_t adf_graph_build_impl(adf_painn* h, const adf_batch* b, hipStream_t s);
 // api.hip: energy[b] = sum over the system's atoms of (y[a] . w + bias), fixed order (adf_energy_sum_kernel)
 int32_t adf_energy_sum(const float* y, int H2, const float* w, const float* bias, const int32_t* atom_offset, float* energy,

@@ -347,8 +347,10 @@ static int32_t eg_lin(adf_painn* h, const float* A, int lda, const EgW& w, const
         ADF_HIP_CHECK(hipGetLastError());
         return ADF_OK;
     }
-    return adf_launch_gemm16(A, lda, &w.w16, bias, C, ldc, (int)M, N, K, 0, s, nullptr, 0, h->lift_on ? &h->lift : nullptr,
-                             nullptr, nullptr, nullptr, accumulate);
+    adf_epi ep = {};
+    ep.accumulate = accumulate;
+    return adf_launch_gemm16(A, lda, &w.w16, bias, C, ldc, (int)M, N, K, 0, &ep, s, h->lift_on ? &h->lift : nullptr, h->tune,
+                             h->num_cus);
 }
 
 // ------------------------------------------------------------------------------------------------ workspace

@@ -110,6 +110,7 @@ struct adf_eqv2 {
     unsigned char* wfrag_arena;   // fragment images (adf_w16::frag) of the split weights, for eq_launch_gemm16pw
     bool conv1_wr;                // first convolution with the weights streamed as fragments (ADF_EQV2_CONV1_WR, default on)
     bool alpha_generic;           // attention logits by the one-head-at-a-time kernel for every width (ADF_EQV2_ALPHA_GENERIC=1)
+    adf_tune tune;                // kernel-selection switches read at creation (common.h: adf_tune_from_env)
     bool conv2_wr;                // plain products on whole 256-column tiles through gemm16.hip's streamed-fragment kernel (ADF_EQV2_CONV2_WR)
     float* wt_arena; size_t wt_bytes;   // transposed first radial layers
     float* rtab_arena; size_t rtab_floats; bool rad_static;   // per-element-pair radial tables (see eq_radial_static)
@@ -199,7 +200,7 @@ int32_t eq_launch_gemm16p(const void* Ahi, const void* Alo, const float* mag, co
 // the same product with the weights streamed from their fragment image (W->frag); eq_gemm16pw_ok: shapes it takes
 bool eq_gemm16pw_ok(const adf_w16* W, int N, int K);
 int32_t eq_launch_gemm16pw(const void* Ahi, const void* Alo, const float* mag, const adf_w16* W, const float* bias, float* Cm,
-                           int ldc, long long M, int N, int K, int act, hipStream_t s);
+                           int ldc, long long M, int N, int K, int act, hipStream_t s, const adf_tune& tune);
 // rsp (optional): per-order arrays that receive the power-of-two lifts of the output rows (matrix-core version only;
 // *rs_written tells whether they were filled)
 int32_t eq_launch_s2act(const adf_eqv2* h, const float* y0, float* const* ym, int extra, int gate_off, int n0, int n1,

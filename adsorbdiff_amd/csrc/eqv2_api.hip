@@ -21,7 +21,7 @@ bool eq_gemm16_ok(const float* A, const eq_rowmap* am, const float* Cm, const eq
 int32_t eq_launch_rowscale(const float* A, const eq_rowmap* am, long long M, int K, float* rs, hipStream_t s);
 int32_t eq_launch_gemm16(const float* A, const eq_rowmap* am, const float* rscale, const adf_w16* W, const float* bias,
                          float* Cm, const eq_rowmap* cm, long long M, int N, int K, int act, bool accumulate,
-                         hipStream_t s, float* out_mag, int rs_div = 1);
+                         hipStream_t s, const adf_tune& tune, float* out_mag, int rs_div = 1);
 
 template <typename T>
 static int32_t eq_alloc(T** p, size_t count) {
@@ -130,6 +130,7 @@ extern "C" int32_t adf_eqv2_create(const adf_eqv2_hparams* hp, adf_eqv2_t* out) 
     { const char* e6 = getenv("ADF_EQV2_ALPHA_GENERIC"); h->alpha_generic = e6 && atoi(e6) != 0; }
     { const char* e4 = getenv("ADF_EQV2_FOLD"); h->fold_on = !(e4 && atoi(e4) == 0); }
     { const char* e5 = getenv("ADF_EQV2_COMPACT"); h->no_compact = e5 && atoi(e5) == 0; }
+    h->tune = adf_tune_from_env();
     h->prof_ev = new std::vector<hipEvent_t>();
     h->prof_cat = new std::vector<int>();
     int32_t st = eq_alloc(&h->flags, EQ_NFLAGS);
@@ -854,11 +855,15 @@ int32_t eq_gemm(const adf_eqv2* h, const float* A, int lda, const eq_rowmap* ama
         // launches only (node-level products measured no better there)
         if (h->conv2_wr && !amap && !cmap && !accumulate && act == 0 && !out_mag && (!rs_pre || rs_div == 1) && W->w16.frag &&
             W->out % 256 == 0 && (W->in / 32) % 2 == 0 && lda == W->in && M >= 65536 && M * (long long)lda * 4 < (1ll << 32) && M < (1ll << 31))
-            return adf_launch_gemm16(A, lda, &W->w16, use_bias ? W->b : nullptr, Cm, ldc, (int)M, W->out, W->in, 0, s, nullptr, 0,
-                                     nullptr, rs_pre ? rs_pre : h->rs, nullptr, nullptr, 0, nullptr, 0);
+        {
+            adf_epi ep = {};
+            ep.rmag = rs_pre ? rs_pre : h->rs;
+            return adf_launch_gemm16(A, lda, &W->w16, use_bias ? W->b : nullptr, Cm, ldc, (int)M, W->out, W->in, 0, &ep, s, nullptr,
+                                     h->tune, h->num_cus);
+        }
         if (out_mag) ADF_HIP_CHECK(hipMemsetAsync(out_mag, 0, sizeof(float) * (size_t)M, s));
         return eq_launch_gemm16(A, am, rs_pre ? rs_pre : h->rs, &W->w16, use_bias ? W->b : nullptr, Cm, cm, M, W->out, W->in,
-                                act, accumulate, s, out_mag, rs_pre ? rs_div : 1);
+                                act, accumulate, s, h->tune, out_mag, rs_pre ? rs_div : 1);
     }
     // exact-f32 product: no lifts needed downstream either (out_mag stays untouched; callers only pass it on when the
     // matrix-core path runs, see eq_uses_mfma)
@@ -948,7 +953,7 @@ static int32_t eq_attention(adf_eqv2* h, const eq_attn* at, const float* y, cons
                     const _Float16* hi = reinterpret_cast<const _Float16*>(b.m[m]);
                     if (h->conv1_wr && eq_gemm16pw_ok(&W->w16, W->out, W->in))
                         ADF_TRY(eq_launch_gemm16pw(hi, hi + (size_t)rows * W->in, b.rsb[m], &W->w16, m == 0 ? W->b : nullptr,
-                                                   b.y[m], W->out, rows, W->out, W->in, 0, s));
+                                                   b.y[m], W->out, rows, W->out, W->in, 0, s, h->tune));
                     else
                         ADF_TRY(eq_launch_gemm16p(hi, hi + (size_t)rows * W->in, b.rsb[m], &W->w16, m == 0 ? W->b : nullptr, b.y[m],
                                                   W->out, rows, W->out, W->in, 0, s));
@@ -1369,9 +1374,9 @@ extern "C" int32_t adf_eqv2_linear_forward(const float* A, const float* W, const
         st = adf_pack_frag(&w16, N, K, w16.frag, s);
     }
     for (int r = 0; r < (repeat > 0 ? repeat : 1) && st == ADF_OK; ++r) {
-        if (mode == 3) st = eq_launch_gemm16pw(split, split + ma * 2, mag, &w16, bias, Cm, N, M, N, K, act, s);
+        if (mode == 3) st = eq_launch_gemm16pw(split, split + ma * 2, mag, &w16, bias, Cm, N, M, N, K, act, s, adf_tune_process());
         else if (mode == 2) st = eq_launch_gemm16p(split, split + ma * 2, mag, &w16, bias, Cm, N, M, N, K, act, s);
-        else st = eq_launch_gemm16(A, &am, mag, &w16, bias, Cm, &cm, M, N, K, act, false, s, nullptr);
+        else st = eq_launch_gemm16(A, &am, mag, &w16, bias, Cm, &cm, M, N, K, act, false, s, adf_tune_process(), nullptr);
     }
     (void)hipStreamSynchronize(s);
     eq_free(buf);

@@ -613,7 +613,7 @@ int32_t eq_launch_gemm16p(const void* Ahi, const void* Alo, const float* mag, co
 
 // The same product with the WEIGHTS STREAMED AS MFMA FRAGMENTS (round 6; the form gemm16.hip's node products took this
 // round): every wave loads the B operands of its own two column blocks straight from the fragment-ordered image
-// (adf_pack_frag, mlp16.hip) into a ring of four register sets, two k-steps ahead; LDS holds only the A tile (two buffers,
+// (adf_pack_frag, gemm16.hip) into a ring of four register sets, two k-steps ahead; LDS holds only the A tile (two buffers,
 // hi + lo, 64-byte rows with the chunk XOR-swizzle of the kernel above), one barrier per K tile, the next tile's rows are
 // requested two tiles ahead in two register sets and copied into the other buffer between the products of the second
 // k-step.  Per K tile a CU's LDS moves (TM / 256) x (128 KB of fragment reads + 32 KB of writes) instead of 196 + 64 KB.
@@ -829,11 +829,10 @@ static int32_t eq_gemm16pw_go(const void* Ahi, const void* Alo, const float* mag
 bool eq_gemm16pw_ok(const adf_w16* W, int N, int K) { return W->frag && N % 32 == 0 && K % 64 == 0 && N >= 128; }
 
 int32_t eq_launch_gemm16pw(const void* Ahi, const void* Alo, const float* mag, const adf_w16* W, const float* bias, float* Cm,
-                           int ldc, long long M, int N, int K, int act, hipStream_t s) {
+                           int ldc, long long M, int N, int K, int act, hipStream_t s, const adf_tune& tune) {
     if (M <= 0 || N <= 0) return ADF_OK;
     if (!eq_gemm16pw_ok(W, N, K)) { adf_set_error("eq_gemm16pw: shape or fragment image"); return ADF_EINVAL; }
-    static int mi = -1;   // rows per tile: 256 (default; 1.5 % faster than 192 on config 4's shapes), ADF_EQV2_PW_MI=3: 192
-    if (mi < 0) { const char* e = getenv("ADF_EQV2_PW_MI"); mi = (e && atoi(e) == 3) ? 3 : 4; }
+    const int mi = tune.eqv2_pw_mi;   // rows per tile: 256 (default; 1.5 % faster than 192 on config 4's shapes), ADF_EQV2_PW_MI=3: 192
     // whole 256-column tiles on eight waves; a remainder of at most 128 columns on the four-wave form
     const int rem = N % 256;
     // 256-row tiles: a last tile of at most 128 columns runs the kernel's half layout; 192-row tiles (ADF_EQV2_PW_MI=3): the
@@ -881,11 +880,9 @@ bool eq_gemm16_ok(const float* A, const eq_rowmap* am, const float* Cm, const eq
 
 int32_t eq_launch_gemm16(const float* A, const eq_rowmap* am, const float* rscale, const adf_w16* W, const float* bias,
                          float* Cm, const eq_rowmap* cm, long long M, int N, int K, int act, bool accumulate,
-                         hipStream_t s, float* out_mag, int rs_div) {
+                         hipStream_t s, const adf_tune& tune, float* out_mag, int rs_div) {
     if (M <= 0 || N <= 0) return ADF_OK;
-    static int big = -1;
-    if (big < 0) { const char* e = getenv("ADF_EQV2_GEMM_TILE"); big = (e && atoi(e) == 128) ? 0 : 1; }
-    if (big && N >= 256 && M >= 8192) {
+    if (tune.eqv2_gemm_tile256 && N >= 256 && M >= 8192) {
         const int tiles_n = (N + 255) / 256;
         const long long tiles_m8 = ((M + 255) / 256 + 7) / 8 * 8;
         const long long nb = tiles_m8 * tiles_n;

@@ -82,7 +82,7 @@ __device__ __forceinline__ float ssilu16(float x) {
 //   g*64 + part*32 + q  <->  row part*H + 32g + q).  dot = sum_xyz v1*v2 / sqrt(H) and |v2| ([N,H] each) are formed
 //   on the accumulators: v2 (1.2 GB per layer at N = 200k) never goes to HBM and the separate reduction pass is gone.
 //   WR (round 6; every product of the PaiNN sampler): the weights are NOT staged through LDS - every wave loads the MFMA B
-//   fragments of its own columns straight from a fragment-ordered image (adf_pack_frag, mlp16.hip; `Whi` then points at that
+//   fragments of its own columns straight from a fragment-ordered image (adf_pack_frag below; `Whi` then points at that
 //   image) into a ring of register sets, two k-steps ahead; LDS holds two A buffers, there is one barrier per K tile, and the
 //   lift / split of the next A tile is dealt between the MFMAs of the current one (see the main loop).  Same products in the
 //   same order as the LDS-staged form (kept below, WR = false): same bits.
@@ -224,7 +224,7 @@ __global__ __launch_bounds__(128 * NWN, (MI == 4 || NWN == 4 ? 1 : 2)) void adf_
     if constexpr (WR) {
         // The B fragments of a k-step are requested one or two k-steps ahead (G16_WDEEP), in front of the products of the k-step
         // before (sched_barrier(0) between the request group and the product group: left alone, hipcc sinks the requests to
-        // their first use and every k-step waits out an L2 round trip - mlp16.hip's first build).
+        // their first use and every k-step waits out an L2 round trip - the retired mlp16.hip's first build).
         auto kstep = [&](int boff, int ks, const half8 (&cur)[NJ][2]) {
             if (G16_ABL & 8) { asm volatile("" :: "v"(cur[0][0]), "v"(cur[0][1]), "v"(cur[NJ - 1][0]), "v"(cur[NJ - 1][1])); return; }
 #pragma unroll
@@ -819,6 +819,29 @@ int32_t adf_split_weight(const float* w, long long n, adf_w16* out, unsigned int
     return ADF_OK;
 }
 
+// Fragment-ordered weight image: for 32-column block cb, k-step s (16 k) and plane (0 = hi, 1 = lo) the 64 lanes' B operands
+// of v_mfma_f32_32x32x16_f16 lie in one contiguous KB: lane l holds W[32 cb + (l & 31)][16 s + 8 (l >> 5) .. + 7].
+__global__ void adf_pack_frag_kernel(const _Float16* __restrict__ hi, const _Float16* __restrict__ lo, half8* __restrict__ out,
+                                     int N, int K) {
+    const int nks = K / 16;
+    const long long total = (long long)(N / 32) * nks * 2 * 64;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int lane = (int)(i & 63), plane = (int)((i >> 6) & 1);
+        const long long cs = i >> 7;
+        const int s = (int)(cs % nks), cb = (int)(cs / nks);
+        const _Float16* src = (plane ? lo : hi) + (size_t)(32 * cb + (lane & 31)) * K + 16 * s + 8 * (lane >> 5);
+        out[i] = *reinterpret_cast<const half8*>(src);
+    }
+}
+
+int32_t adf_pack_frag(const adf_w16* w, int N, int K, void* out, hipStream_t s) {
+    if (N % 32 || K % 16) { adf_set_error("pack_frag: N %% 32 or K %% 16"); return ADF_EINVAL; }
+    hipLaunchKernelGGL(adf_pack_frag_kernel, dim3(256), dim3(256), 0, s, (const _Float16*)w->hi, (const _Float16*)w->lo,
+                       (half8*)out, N, K);
+    ADF_HIP_CHECK(hipGetLastError());
+    return ADF_OK;
+}
+
 // the kernels address A with 32-bit byte offsets
 static int32_t check_a_span(long long rows, int lda) {
     if (rows * (long long)lda * 4 >= (1ll << 32)) {
@@ -829,46 +852,43 @@ static int32_t check_a_span(long long rows, int lda) {
 }
 
 int32_t adf_launch_gemm16(const float* A, int lda, const adf_w16* W, const float* bias, float* C, int ldc, int M,
-                          int N, int K, int act_ssilu, hipStream_t s, const float* A2, int K1, const adf_lift* lf,
-                          const float* premag, float* out_mag, const int32_t* m_dev, int accumulate, const float* gate,
-                          int gate_ld) {
+                          int N, int K, int act_ssilu, const adf_epi* ep_in, hipStream_t s, const adf_lift* lf,
+                          const adf_tune& tune, int num_cus) {
     if (M <= 0) return ADF_OK;
-    if (K % HK != 0 || (lda & 3) || (A2 && (K1 <= 0 || K1 % HK != 0 || K1 >= K))) {
-        adf_set_error("gemm16: K=%d (K1=%d) must be multiples of %d and lda a multiple of 4", K, K1, HK);
+    adf_epi ep = {};
+    if (ep_in) ep = *ep_in;
+    if (!ep.A2) ep.K1 = 0;
+    if (K % HK != 0 || (lda & 3) || (ep.A2 && (ep.K1 <= 0 || ep.K1 % HK != 0 || ep.K1 >= K))) {
+        adf_set_error("gemm16: K=%d (K1=%d) must be multiples of %d and lda a multiple of 4", K, ep.K1, HK);
         return ADF_EINVAL;
     }
     ADF_TRY(check_a_span(M, lda));
-    static int mi = 0;
-    if (!mi) { const char* e = getenv("ADF_GEMM16_MI"); mi = e ? atoi(e) : 2; if (mi != 4) mi = 2; }
+    const int mi = tune.gemm16_mi;
     const int TM = 64 * mi, TN = 256;
     const int tiles_n = (N + TN - 1) / TN;
     const int tiles_m = (M + TM - 1) / TM;
     const int tiles_m8 = (tiles_m + 7) / 8 * 8;
     dim3 grid((unsigned)(tiles_m8 * tiles_n));
-    adf_epi ep = {};
-    ep.A2 = A2; ep.K1 = A2 ? K1 : 0; ep.m_dev = m_dev; ep.accumulate = accumulate;
-    ep.gate = gate; ep.gate_ld = gate_ld;
-    if (gate && ((N | ldc) & 3)) { adf_set_error("gemm16: the gate epilogue needs N and ldc multiples of 4"); return ADF_EINVAL; }
-    ADF_TRY(lift_mags(A, lda, A2 ? K1 : K, A2, A2 ? K - K1 : 0, M, lf, premag, &ep.rmag, s, m_dev, 1));
-    if (out_mag) {
-        ADF_HIP_CHECK(hipMemsetAsync(out_mag, 0, sizeof(float) * (size_t)M, s));
-        ep.out_mag = reinterpret_cast<unsigned int*>(out_mag);
+    // the gate is applied by the float4 store branch alone: it must be the branch every tile of this launch takes
+    if (ep.gate && (((N | ldc | ep.gate_ld) & 3) || (((uintptr_t)C | (uintptr_t)ep.gate) & 15))) {
+        adf_set_error("gemm16: the gate epilogue needs N, ldc and gate_ld multiples of 4 and 16-byte aligned C and gate");
+        return ADF_EINVAL;
     }
+    ADF_TRY(lift_mags(A, lda, ep.A2 ? ep.K1 : K, ep.A2, ep.A2 ? K - ep.K1 : 0, M, lf, ep.rmag, &ep.rmag, s, ep.m_dev, 1));
+    if (ep.out_mag) ADF_HIP_CHECK(hipMemsetAsync(ep.out_mag, 0, sizeof(float) * (size_t)M, s));
     // Round 6: weights streamed as fragments, eight waves per workgroup, 192 x 256 tile, software-pipelined staging (see the
     // kernel comment: WR, NWN = 4).  Needs the fragment image, N a multiple of 256 and an even number of K tiles.
-    static int w8 = -1;     // ADF_GEMM_W8_PLAIN=0: the 128 x 256 tile with LDS-staged weights of rounds 1-5
-    if (w8 < 0) { const char* e = getenv("ADF_GEMM_W8_PLAIN"); w8 = (e && atoi(e) == 0) ? 0 : 1; }
+    // (adf_tune::gemm_w8_plain = 0: the 128 x 256 tile with LDS-staged weights of rounds 1-5)
     // (the same pipeline with four waves - 192 x 128 tile, two workgroups per CU - measured 1.3 % slower on the node products
     // and 2.3 % on the heads; a 128 x 256 four-wave tile spills 36-46 registers)
     // One such workgroup per CU: with few, long tiles the last round matters.  A launch of fewer than four rounds whose last
     // round would fill under 30 % of the chip (25 000 rows: 131 x 2 = 262 workgroups on 256 CUs) keeps the 128 x 256 tile,
     // two workgroups per CU (392 on 512 slots).
-    static int ncu = 0;
-    if (!ncu) { int dev = 0; if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256; }
+    const int ncu = num_cus > 0 ? num_cus : 256;
     const long long wg8 = (long long)((M + 191) / 192) * (N / 256 > 0 ? N / 256 : 1);
     const bool ragged = wg8 < 4ll * ncu && wg8 % ncu != 0 && wg8 % ncu < (3 * ncu) / 10 && wg8 > ncu;
     // (256-row tiles, MI = 4 - every weight fragment reused by 128 rows - measured: no gain, 1672-1676 against 1670-1673 ms)
-    if (w8 == 1 && W->frag && N % 256 == 0 && (K / HK) % 2 == 0 && mi == 2 && !ragged) {
+    if (tune.gemm_w8_plain && W->frag && N % 256 == 0 && (K / HK) % 2 == 0 && mi == 2 && !ragged) {
         const int tn8 = N / 256, tmw8 = ((M + 191) / 192 + 7) / 8 * 8;
         dim3 g8((unsigned)(tmw8 * tn8));
         if (act_ssilu)
@@ -893,7 +913,7 @@ int32_t adf_launch_gemm16(const float* A, int lda, const adf_w16* W, const float
 
 // ||W v||_xyz of a [M,3,K] vector field -> nrm [M, N]  (EPI 4; N % 4 == 0)
 int32_t adf_launch_gemm16_vecnorm(const float* A, int lda, const adf_w16* W, float* nrm, int M, int N, int K,
-                                  hipStream_t s, const adf_lift* lf, const float* premag) {
+                                  hipStream_t s, const adf_tune& tune, const adf_lift* lf, const float* premag) {
     if (M <= 0) return ADF_OK;
     if (K % HK != 0 || (lda & 3) || (N & 3)) { adf_set_error("gemm16_vecnorm: bad shape"); return ADF_EINVAL; }
     ADF_TRY(check_a_span(3ll * M, lda));
@@ -901,9 +921,7 @@ int32_t adf_launch_gemm16_vecnorm(const float* A, int lda, const adf_w16* W, flo
     ep.cat = nrm;
     ADF_TRY(lift_mags(A, lda, K, nullptr, 0, 3ll * M, lf, premag, &ep.rmag, s));
     const int tn = (N + 127) / 128, tm8 = ((M + 63) / 64 + 7) / 8 * 8;
-    static int w8 = -1;
-    if (w8 < 0) { const char* e = getenv("ADF_GEMM_W8"); w8 = (e && atoi(e) == 0) ? 0 : 1; }
-    if (w8 && W->frag && N % 256 == 0 && (K / HK) % 2 == 0) {   // weights streamed as fragments, eight waves (see the kernel comment)
+    if (tune.gemm_w8 && W->frag && N % 256 == 0 && (K / HK) % 2 == 0) {   // weights streamed as fragments, eight waves (see the kernel comment)
         hipLaunchKernelGGL((adf_gemm_f16x3_kernel<0, 3, 2, 4, true, 4>), dim3((unsigned)(tm8 * (N / 256))), dim3(512), 0, s, A, lda,
                            (const _Float16*)W->frag, (const _Float16*)nullptr, W->inv_scale, (const float*)nullptr,
                            (float*)nullptr, 0, M, N, K, N / 256, ep);
@@ -919,7 +937,7 @@ int32_t adf_launch_gemm16_vecnorm(const float* A, int lda, const adf_w16* W, flo
 
 // 3H-wide layer with row-permuted weights and a fused consumer epilogue (EPI 1 or 2, see kernel comment)
 int32_t adf_launch_gemm16_fused(const float* A, int lda, const adf_w16* W, int M, int H, int K, int epi,
-                                const adf_epi* ep_in, hipStream_t s, const adf_lift* lf) {
+                                const adf_epi* ep_in, hipStream_t s, const adf_tune& tune, const adf_lift* lf) {
     adf_epi epv = *ep_in;
     const adf_epi* ep = &epv;
     if (M <= 0) return ADF_OK;
@@ -937,12 +955,10 @@ int32_t adf_launch_gemm16_fused(const float* A, int lda, const adf_w16* W, int M
     dim3 grid((unsigned)(tiles_m8 * tiles_n));
     if (epi == 3) {  // vec_proj: A = vec [N,3,H], weights [2H, K] permuted in (v1, v2) pairs; M = atoms
         const int tn = 2 * H / 128, tm8 = ((M + 63) / 64 + 7) / 8 * 8;
-        static int wreg = -1;   // ADF_GEMM_WREG=0: weights staged through LDS as in rounds 1-5
-        if (wreg < 0) { const char* e = getenv("ADF_GEMM_WREG"); wreg = (e && atoi(e) == 0) ? 0 : 1; }
-        static int w8 = -1;     // ADF_GEMM_W8=0: four waves per workgroup (128 columns) instead of eight (256)
-        if (w8 < 0) { const char* e = getenv("ADF_GEMM_W8"); w8 = (e && atoi(e) == 0) ? 0 : 1; }
-        // (four waves, two workgroups per CU, same pipeline: node products 1748 ms per pass against 1679)
-        if (wreg && W->frag && w8 == 1 && (2 * H) % 256 == 0 && (K / HK) % 2 == 0)
+        // adf_tune::gemm_wreg = 0: weights staged through LDS as in rounds 1-5; gemm_w8 = 0: four waves per workgroup (128
+        // columns) instead of eight (256) (four waves, two workgroups per CU, same pipeline: node products 1748 ms per pass
+        // against 1679)
+        if (tune.gemm_wreg && W->frag && tune.gemm_w8 && (2 * H) % 256 == 0 && (K / HK) % 2 == 0)
             hipLaunchKernelGGL((adf_gemm_f16x3_kernel<0, 3, 2, 3, true, 4>), dim3((unsigned)(tm8 * (2 * H / 256))), dim3(512), 0, s,
                                A, lda, (const _Float16*)W->frag, (const _Float16*)nullptr, W->inv_scale, (const float*)nullptr,
                                (float*)nullptr, 0, M, 2 * H, K, 2 * H / 256, *ep);
@@ -953,8 +969,7 @@ int32_t adf_launch_gemm16_fused(const float* A, int lda, const adf_w16* W, int M
         ADF_HIP_CHECK(hipGetLastError());
         return ADF_OK;
     }
-    static int wf = -1;   // ADF_GEMM_WR_FUSED: 0 = LDS-staged weights (rounds 1-5), 2 / 4 = streamed fragments with 4 / 8 waves
-    if (wf < 0) { const char* e = getenv("ADF_GEMM_WR_FUSED"); wf = e ? atoi(e) : 2; }
+    const int wf = tune.gemm_wr_fused;   // 0 = LDS-staged weights (rounds 1-5), 2 / 4 = streamed fragments with 4 / 8 waves
     // (measured: 4 waves 1656 ms of node products per pass, LDS-staged weights 1702, 8 waves 1741 - the record / gating
     // epilogues are HBM-heavy and want the CU's second workgroup beside them)
     if (wf && W->frag && (K / HK) % 2 == 0 && (wf == 2 || N % 384 == 0)) {

@@ -572,10 +572,8 @@ int32_t adf_graph_build_impl(adf_painn* h, const adf_batch* b, hipStream_t s) {
     const long long slots = (long long)N * K;
     const unsigned nb = (unsigned)((slots + 255) / 256);
     // count / fill / sort: per system out of LDS (above); systems that do not fit go through the global-memory kernels
-    static int sys_csr = -1;
-    if (sys_csr < 0) { const char* e = getenv("ADF_GRAPH_SYS_CSR"); sys_csr = (e && atoi(e) == 0) ? 0 : 1; }
     const int32_t* only = nullptr;
-    if (sys_csr) {
+    if (h->tune.graph_sys_csr) {
         hipLaunchKernelGGL(adf_count_sys_kernel, dim3(B), dim3(256), 0, s, p, h->deg, h->sys_slow);
         only = h->sys_slow;
     }

@@ -293,22 +293,28 @@ int32_t adf_head_forward(adf_painn* h, int head, int N, const float* x, const fl
         ADF_TRY(adf_linear(h, vec, H, b0.vec1_w, &b0.vec1_16, nullptr, t1, H, 3 * N, H, H, 0, s));
         hipLaunchKernelGGL(adf_head_norm_cat_kernel, dim3(ew_grid((long long)N * H / 4)), dim3(256), 0, s, x, t1, h->cat, N, H);
     } else {  // ||vec1_proj(vec)|| straight from the accumulators into cat [N,H]
-        ADF_TRY(adf_launch_gemm16_vecnorm(vec, H, &b0.vec1_16, h->cat, N, H, H, s, lf, vmag));
+        ADF_TRY(adf_launch_gemm16_vecnorm(vec, H, &b0.vec1_16, h->cat, N, H, H, s, h->tune, lf, vmag));
     }
     // f16x3 path (round 6): vec2_proj runs AFTER the update net and multiplies its rows by the gate half of `o` in its own
     // epilogue (same single fp32 multiplication per element as adf_head_gate_kernel: same bits); t2 never reaches HBM
-    static int fuse_gate = -1;
-    if (fuse_gate < 0) { const char* e = getenv("ADF_HEAD_GATE_FUSED"); fuse_gate = (e && atoi(e) == 0) ? 0 : 1; }
-    const bool fg = fuse_gate && !h->gemm_f32 && (H2 & 3) == 0;
+    const bool fg = h->tune.head_gate_fused && !h->gemm_f32 && (H2 & 3) == 0;
     if (!fg) ADF_TRY(adf_linear(h, vec, H, b0.vec2_w, &b0.vec2_16, nullptr, t2, H2, 3 * N, H2, H, 0, s, vmag));
     if (h->gemm_f32) ADF_TRY(adf_linear(h, h->cat, 2 * H, b0.un0_w, &b0.un0_16, b0.un0_b, h->y, H, N, H, 2 * H, 1, s));
-    else ADF_TRY(adf_launch_gemm16(x, H, &b0.un0_16, b0.un0_b, h->y, H, N, H, 2 * H, 1, s, h->cat, H,  // [x | norm]
-                                   h->lift_on ? &h->lift : nullptr, nullptr, h->lift_on ? h->mag_b : nullptr));
+    else {
+        adf_epi e0 = {};
+        e0.A2 = h->cat; e0.K1 = H;   // [x | norm]
+        e0.out_mag = h->lift_on ? reinterpret_cast<unsigned int*>(h->mag_b) : nullptr;
+        ADF_TRY(adf_launch_gemm16(x, H, &b0.un0_16, b0.un0_b, h->y, H, N, H, 2 * H, 1, &e0, s, h->lift_on ? &h->lift : nullptr,
+                                  h->tune, h->num_cus));
+    }
     ADF_TRY(adf_linear(h, h->y, H, b0.un2_w, &b0.un2_16, b0.un2_b, o, H, N, H, H, 0, s, (h->lift_on && !h->gemm_f32) ? h->mag_b : nullptr));
     if (fg) {
         // (its epilogue also emits the magnitudes of the gated rows v1: block 1's vector-norm product needs no measuring pass)
-        ADF_TRY(adf_launch_gemm16(vec, H, &b0.vec2_16, nullptr, v1, H2, 3 * N, H2, H, 0, s, nullptr, 0, lf, vmag,
-                                  lift ? h->lift.buf : nullptr, nullptr, 0, o + H2, H));
+        adf_epi eg = {};
+        eg.rmag = vmag;
+        eg.out_mag = lift ? reinterpret_cast<unsigned int*>(h->lift.buf) : nullptr;
+        eg.gate = o + H2; eg.gate_ld = H;
+        ADF_TRY(adf_launch_gemm16(vec, H, &b0.vec2_16, nullptr, v1, H2, 3 * N, H2, H, 0, &eg, s, lf, h->tune, h->num_cus));
         hipLaunchKernelGGL(adf_head_xact_kernel, dim3(ew_grid((long long)N * H2 / 4)), dim3(256), 0, s, o, x1, N, H2);
     } else
     hipLaunchKernelGGL(adf_head_gate_kernel, dim3(ew_grid((long long)N * H2 / 4)), dim3(256), 0, s, o, t2, x1, v1, N, H2);
@@ -318,9 +324,12 @@ int32_t adf_head_forward(adf_painn* h, int head, int N, const float* x, const fl
         hipLaunchKernelGGL(adf_head_norm_cat_kernel, dim3(ew_grid((long long)N * H2 / 4)), dim3(256), 0, s, x1, t1b, cat1, N, H2);
         ADF_TRY(adf_linear(h, cat1, H, b1.un0_w, &b1.un0_16, b1.un0_b, h->y, H2, N, H2, H, 1, s));
     } else {
-        ADF_TRY(adf_launch_gemm16_vecnorm(v1, H2, &b1.vec1_16, cat1, N, H2, H2, s, h->lift_on ? &h->lift : nullptr,
+        ADF_TRY(adf_launch_gemm16_vecnorm(v1, H2, &b1.vec1_16, cat1, N, H2, H2, s, h->tune, h->lift_on ? &h->lift : nullptr,
                                           (fg && lift) ? h->lift.buf : nullptr));
-        ADF_TRY(adf_launch_gemm16(x1, H2, &b1.un0_16, b1.un0_b, h->y, H2, N, H2, H, 1, s, cat1, H2, h->lift_on ? &h->lift : nullptr));
+        adf_epi e1 = {};
+        e1.A2 = cat1; e1.K1 = H2;   // [x1 | norm]
+        ADF_TRY(adf_launch_gemm16(x1, H2, &b1.un0_16, b1.un0_b, h->y, H2, N, H2, H, 1, &e1, s, h->lift_on ? &h->lift : nullptr,
+                                  h->tune, h->num_cus));
     }
     hipLaunchKernelGGL(adf_head_final_kernel, dim3((N + 3) / 4), dim3(256), 0, s, h->y, v1, b1.vec2_w, b1.un2_w,
                        b1.un2_b, out, N, H2, h->flags);

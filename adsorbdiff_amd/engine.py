@@ -432,10 +432,12 @@ class PaiNNEngine(Engine):
         _lib.check(self.lib.adf_painn_energy_gradient_workspace(self.handle, int(num_atoms), C.byref(n)))
         return int(n.value)
 
-    def set_fused_mlp(self, mode: int = 2) -> None:
-        """Form of the x_proj / xvec_proj pairs (adf_painn_set_fused_mlp): 0 two kernels per pair, 1 the fused two-layer
-        kernel (csrc/mlp16.hip), 2 by size (default).  Bit-identical results."""
-        _lib.check(self.lib.adf_painn_set_fused_mlp(self.handle, int(mode)))
+    def get_tune(self) -> dict:
+        """The kernel-selection switches this engine's handle read from the environment when it was created
+        (adf_painn_get_tune): field name -> value.  The variants give the same bits, so only this shows the selection."""
+        t = _lib.Tune()
+        _lib.check(self.lib.adf_painn_get_tune(self.handle, C.byref(t)))
+        return {name: int(getattr(t, name)) for name, _ in _lib.Tune._fields_}
 
     def build_graph(self, data, prep=None):
         """Graph only; returns the number of symmetrised edges.  ``prep``: an already prepared batch of ``data``."""

@@ -21,7 +21,7 @@ class NumericRangeError(ArithmeticError):
 
 EXPORTS = (
     "adf_painn_create", "adf_painn_destroy", "adf_painn_set_weights", "adf_graph_build", "adf_graph_set_moving",
-    "adf_check_flags", "adf_painn_set_arithmetic", "adf_painn_set_incremental", "adf_painn_set_fused_mlp",
+    "adf_check_flags", "adf_painn_set_arithmetic", "adf_painn_set_incremental", "adf_painn_get_tune",
     "adf_graph_export", "adf_painn_forward", "adf_painn_forward_subset", "adf_linear_forward", "adf_painn_message_layer", "adf_painn_update_layer",
     "adf_painn_debug_row_maxima",
     "adf_sde_init_placement", "adf_sde_step", "adf_sde_step_scheduled", "adf_sample", "adf_sample_traj",
@@ -65,6 +65,14 @@ class EqV2Counters(C.Structure):
     _fields_ = [("num_edges", C.c_int64), ("num_atoms", C.c_int64), ("dense_flops", C.c_int64), ("conv_flops", C.c_int64),
                 ("inc_rows", C.c_int64), ("inc_rows_full", C.c_int64), ("forwards_total", C.c_int64),
                 ("conv_flops_total", C.c_int64)]
+
+
+class Tune(C.Structure):
+    """adf_tune: the kernel-selection switches a handle holds (include/adsorbdiff_hip.h)."""
+    _fields_ = [(name, C.c_int32) for name in (
+        "gemm16_mi", "gemm_w8_plain", "gemm_w8", "gemm_wreg", "gemm_wr_fused", "head_gate_fused", "lift_emit",
+        "graph_sys_csr", "train_gemm16", "wgrad_f32",
+        "eqv2_pw_mi", "eqv2_gemm_tile256", "eqv2_rotin_generic", "eqv2_rotout_generic")]
 
 
 class BatchDesc(C.Structure):
@@ -131,7 +139,7 @@ def load():
         "adf_check_flags": [vp, vp],
         "adf_painn_set_arithmetic": [vp, i32],
         "adf_painn_set_incremental": [vp, i32],
-        "adf_painn_set_fused_mlp": [vp, i32],
+        "adf_painn_get_tune": [vp, C.POINTER(Tune)],
         "adf_graph_export": [vp, vp, vp, vp, i64, vp, vp, vp, vp, C.POINTER(i64), vp],
         "adf_painn_forward": [vp, C.POINTER(BatchDesc), vp, vp, vp],
         "adf_painn_forward_subset": [vp, C.POINTER(BatchDesc), vp, i32, vp, vp, vp],

@@ -139,13 +139,29 @@ int32_t adf_painn_set_arithmetic(adf_painn_t h, int32_t exact_f32);
  * Calling this (with either value) drops the kept state and zeroes the counters adf_get_counters reports. */
 int32_t adf_painn_set_incremental(adf_painn_t h, int32_t on);
 
-/* Form of the two node MLP pairs of a layer (x_proj: painn_denoising.py:531; xvec_proj: :614-623) at hidden width 512 in the
- * f16x3 arithmetic: mode 0 (default) = two kernels per pair (product + ScaledSiLU, then product + fused epilogue;
- * csrc/gemm16.hip), 1 = one kernel per pair with the [rows, 512] intermediate kept in LDS and the weights streamed as MFMA
- * fragments (csrc/mlp16.hip; round 6: bit-identical results, measured 5-10 % slower per pair on MI355X - its epilogues'
- * HBM traffic does not overlap its matrix phases at one workgroup per CU, profiles/NOTES.md), 2 = mode 1 from 2 x 64 rows per
- * CU on.  ADF_FUSED_MLP sets the initial mode. */
-int32_t adf_painn_set_fused_mlp(adf_painn_t h, int32_t mode);
+/* Kernel-selection switches.  Each chooses between kernels that compute the same thing (same K order per output element:
+ * same bits); the non-default values select earlier variants kept for measurements.  adf_painn_create reads them from the
+ * environment once and the handle keeps its own copy, so handles created under different environments coexist in one
+ * process.  The stateless entries (adf_linear_forward, adf_op_*) share one copy read at their first use. */
+typedef struct adf_tune {
+    int32_t gemm16_mi;        /* ADF_GEMM16_MI: 4 = 256-row tiles of the LDS-staged product, anything else 2 (default) */
+    int32_t gemm_w8_plain;    /* ADF_GEMM_W8_PLAIN: 0 = plain products keep the 128 x 256 LDS-staged tile, else 1 (default) */
+    int32_t gemm_w8;          /* ADF_GEMM_W8: 0 = vec_proj / vector-norm products with four waves, else 1 (eight, default) */
+    int32_t gemm_wreg;        /* ADF_GEMM_WREG: 0 = vec_proj stages its weights through LDS, else 1 (default) */
+    int32_t gemm_wr_fused;    /* ADF_GEMM_WR_FUSED: 0 = LDS-staged weights, 4 = streamed with eight waves, anything else 2 (default) */
+    int32_t head_gate_fused;  /* ADF_HEAD_GATE_FUSED: 0 = the heads' gate in a kernel of its own, else 1 (default) */
+    int32_t lift_emit;        /* ADF_LIFT_EMIT: 0 = x_proj's row magnitudes are measured, else 1 (handed on by the producers) */
+    int32_t graph_sys_csr;    /* ADF_GRAPH_SYS_CSR: 0 = global-memory count / fill / sort only, else 1 (default) */
+    int32_t train_gemm16;     /* ADF_TRAIN_GEMM: "f32" = 0, the training products in exact f32, else 1 (stateless entries only) */
+    int32_t wgrad_f32;        /* ADF_WGRAD: "f32" = 1, weight gradients in exact f32, else 0 (stateless entries only) */
+    /* EquiformerV2 (adf_eqv2_create keeps the same copy) */
+    int32_t eqv2_pw_mi;          /* ADF_EQV2_PW_MI: 3 = 192-row tiles of the streamed-weights product, anything else 4 (256) */
+    int32_t eqv2_gemm_tile256;   /* ADF_EQV2_GEMM_TILE: 128 = 0, the 128-row tile for every shape, else 1 (256 rows from 8192 on) */
+    int32_t eqv2_rotin_generic;  /* ADF_EQV2_ROTIN_GENERIC set (any value): 1, the run-time-mmax rotate-in kernel, else 0 */
+    int32_t eqv2_rotout_generic; /* ADF_EQV2_ROTOUT_GENERIC set (any value): 1, the run-time-mmax rotate-out kernel, else 0 */
+} adf_tune;
+/* Test hook: the selection the handle holds (the variants give the same bits, so outputs cannot show it). */
+int32_t adf_painn_get_tune(adf_painn_t h, adf_tune* out);
 
 /* Read the device-side error flags of the last graph build (candidate overflow,
  * empty image).  Synchronises the stream.  adf_painn_forward does not check

@@ -1,9 +1,8 @@
 // stand-alone timing harness of the vec_proj product (adf_gemm_f16x3_kernel<0,3,2,3,...>) with the G16_ABL ablation bits of
 // gemm16.hip: hipcc --offload-arch=gfx950 -O3 -std=c++17 -fno-slp-vectorize -DG16_ABL=<bits> -o g16 gemm16_vecproj_harness.hip
-// (ADF_GEMM_WREG=0 / ADF_GEMM_W8=0 select the earlier forms at run time)
+// usage: g16 [rows [gemm_wreg [gemm_w8]]]  (adf_tune fields; 0 selects the earlier forms)
 #include <stdarg.h>
 #include "../../adsorbdiff_amd/csrc/gemm16.hip"
-#include "../../adsorbdiff_amd/csrc/mlp16.hip"
 void adf_set_error(const char* fmt, ...) { va_list a; va_start(a, fmt); vfprintf(stderr, fmt, a); va_end(a); fprintf(stderr, "\n"); }
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e_)); return 1; } } while (0)
 __global__ void fillf(float* p, size_t n, float a, unsigned seed) {
@@ -14,6 +13,8 @@ __global__ void fillf(float* p, size_t n, float a, unsigned seed) {
 }
 int main(int argc, char** argv) {
     const int N = argc > 1 ? atoi(argv[1]) : 200000, H = 512;
+    adf_tune tune = {};
+    tune.gemm_wreg = argc > 2 ? atoi(argv[2]) : 1; tune.gemm_w8 = argc > 3 ? atoi(argv[3]) : 1;
     float *vec, *w, *v1, *dot, *cat, *mag, *isc;
     _Float16 *hi, *lo; void* frag; unsigned int* scratch;
     CK(hipMalloc(&vec, (size_t)N * 3 * H * 4)); CK(hipMalloc(&w, (size_t)2 * H * H * 4)); CK(hipMalloc(&v1, (size_t)N * 3 * H * 4));
@@ -31,11 +32,11 @@ int main(int argc, char** argv) {
         ep.v1 = v1; ep.dotw = dot; ep.cat = cat; ep.H = H; W.frag = wr ? frag : nullptr;
         if (adf_launch_rowmag(vec, H, H, nullptr, 0, 3ll * N, mag, 0) != ADF_OK) return 2;
         ep.rmag = mag;
-        for (int it = 0; it < 2; ++it) if (adf_launch_gemm16_fused(vec, H, &W, N, H, H, 3, &ep, 0, nullptr) != ADF_OK) return 2;
+        for (int it = 0; it < 2; ++it) if (adf_launch_gemm16_fused(vec, H, &W, N, H, H, 3, &ep, 0, tune, nullptr) != ADF_OK) return 2;
         CK(hipDeviceSynchronize());
         CK(hipEventRecord(e0, 0));
         const int reps = 5;
-        for (int it = 0; it < reps; ++it) adf_launch_gemm16_fused(vec, H, &W, N, H, H, 3, &ep, 0, nullptr);
+        for (int it = 0; it < reps; ++it) adf_launch_gemm16_fused(vec, H, &W, N, H, H, 3, &ep, 0, tune, nullptr);
         CK(hipEventRecord(e1, 0)); CK(hipEventSynchronize(e1));
         float ms; CK(hipEventElapsedTime(&ms, e0, e1));
         const double flops = (double)N * 3 * 1024.0 * 512 * 6;

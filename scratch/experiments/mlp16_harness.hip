@@ -1,6 +1,6 @@
 // stand-alone timing harness of adf_mlp16_kernel (synthetic operands): hipcc -DML_ABL=x ... mlp_harness.hip
 #include <stdarg.h>
-#include "../../adsorbdiff_amd/csrc/mlp16.hip"
+#include "mlp16.hip"  // (with common.h on the include path: -I adsorbdiff_amd/csrc)
 void adf_set_error(const char* fmt, ...) { va_list a; va_start(a, fmt); vfprintf(stderr, fmt, a); va_end(a); fprintf(stderr, "\n"); }
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e_)); return 1; } } while (0)
 __global__ void fill(float* p, size_t n, float a, unsigned seed) {
