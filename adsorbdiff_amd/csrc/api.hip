@@ -56,31 +56,9 @@ int adf_current_num_cus() {
     return n;
 }
 
-// ---- HIP-event profiling: pairs of events on the launch stream around kernel groups
-void adf_prof_begin(adf_painn* h, int cat, hipStream_t s) {
-    if (!h->prof_on) return;
-    if (h->prof_used + 2 > h->prof_ev->size()) {
-        for (int i = 0; i < 512; ++i) {
-            hipEvent_t e;
-            if (hipEventCreate(&e) != hipSuccess) return;
-            h->prof_ev->push_back(e);
-        }
-    }
-    h->prof_cat->push_back(cat);
-    (void)hipEventRecord((*h->prof_ev)[h->prof_used], s);
-    h->prof_used += 1;
-}
-void adf_prof_end(adf_painn* h, hipStream_t s) {
-    if (!h->prof_on || (h->prof_used & 1) == 0) return;
-    (void)hipEventRecord((*h->prof_ev)[h->prof_used], s);
-    h->prof_used += 1;
-}
-
 extern "C" int32_t adf_profile_enable(adf_painn_t h, int32_t on) {
     if (!h) { adf_set_error("null handle"); return ADF_EINVAL; }
-    h->prof_on = on != 0;
-    h->prof_used = 0;
-    h->prof_cat->clear();
+    h->prof.enable(on != 0);
     ADF_HIP_CHECK(hipMemset(h->kcount, 0, 8 * sizeof(unsigned long long)));
     return ADF_OK;
 }
@@ -94,32 +72,7 @@ extern "C" int32_t adf_profile_read(adf_painn_t h, float* ms, int64_t* count, in
         ADF_HIP_CHECK(hipMemset(h->kcount, 0, sizeof(k)));
         *message_ksteps = (int64_t)k[0];
     }
-    for (int c = 0; c < ADF_PROF_NCAT; ++c) { ms[c] = 0.f; count[c] = 0; }
-    const size_t pairs = h->prof_used / 2;
-    for (size_t i = 0; i < pairs; ++i) {
-        float t = 0.f;
-        ADF_HIP_CHECK(hipEventElapsedTime(&t, (*h->prof_ev)[2 * i], (*h->prof_ev)[2 * i + 1]));
-        const int c = (*h->prof_cat)[i];
-        ms[c] += t;
-        count[c] += 1;
-    }
-    h->prof_used = 0;
-    h->prof_cat->clear();
-    return ADF_OK;
-}
-
-template <typename T>
-static int32_t dev_alloc(T** p, size_t count) {
-    if (*p) { (void)hipFree(*p); *p = nullptr; }
-    if (count == 0) return ADF_OK;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T));
-    if (e != hipSuccess) {
-        *p = nullptr;
-        (void)hipGetLastError();
-        adf_set_error("hipMalloc of %zu bytes failed: %s", count * sizeof(T), hipGetErrorString(e));
-        return ADF_EOOM;
-    }
-    return ADF_OK;
+    return h->prof.read(ms, count, ADF_PROF_NCAT);
 }
 
 extern "C" int32_t adf_painn_create(const adf_painn_hparams* hp, adf_painn_t* out) {
@@ -142,10 +95,7 @@ extern "C" int32_t adf_painn_create(const adf_painn_hparams* hp, adf_painn_t* ou
     }
     adf_painn* h = new (std::nothrow) adf_painn();
     if (!h) { adf_set_error("host allocation failed"); return ADF_EOOM; }
-    memset(h, 0, sizeof(*h));
     h->hp = *hp;
-    h->prof_ev = new std::vector<hipEvent_t>();
-    h->prof_cat = new std::vector<int>();
     hipDeviceProp_t prop;
     if (hipGetDevice(&h->device) != hipSuccess || hipGetDeviceProperties(&prop, h->device) != hipSuccess) {
         adf_set_error("no usable HIP device: %s", hipGetErrorString(hipGetLastError()));
@@ -161,16 +111,13 @@ extern "C" int32_t adf_painn_create(const adf_painn_hparams* hp, adf_painn_t* ou
         h->inc_sync = e2 && e2[0] == '1';
     }
     const int H = hp->hidden_channels, R = hp->num_rbf, L = hp->num_layers;
-    int32_t st = dev_alloc(&h->rbf_pack, (size_t)L * (H / ADF_SLICE_CH) * R * 192);
-    if (st == ADF_OK) st = dev_alloc(&h->rbf_bias_pack, (size_t)L * (H / ADF_SLICE_CH) * 192);
-    {
-        uint16_t* p16 = nullptr;
-        if (st == ADF_OK) st = dev_alloc(&p16, (size_t)L * (H / ADF_SLICE_CH) * R * 192 * 2);
-        h->rbf_pack16 = p16;
-    }
-    if (st == ADF_OK) st = dev_alloc(&h->rbf_bias_pack16, (size_t)L * (H / ADF_SLICE_CH) * 192);
-    if (st == ADF_OK) st = dev_alloc(&h->rbf_scales, 16);
-    if (st == ADF_OK) st = dev_alloc(&h->flags, ADF_NFLAGS);
+    adf_pool& m = h->m_life;
+    int32_t st = m.alloc(&h->rbf_pack, (size_t)L * (H / ADF_SLICE_CH) * R * 192);
+    if (st == ADF_OK) st = m.alloc(&h->rbf_bias_pack, (size_t)L * (H / ADF_SLICE_CH) * 192);
+    if (st == ADF_OK) st = m.alloc(&h->rbf_pack16, (size_t)L * (H / ADF_SLICE_CH) * R * 192 * 2 * sizeof(uint16_t));
+    if (st == ADF_OK) st = m.alloc(&h->rbf_bias_pack16, (size_t)L * (H / ADF_SLICE_CH) * 192);
+    if (st == ADF_OK) st = m.alloc(&h->rbf_scales, 16);
+    if (st == ADF_OK) st = m.alloc(&h->flags, ADF_NFLAGS);
     if (st == ADF_OK && hipMemset(h->flags, 0, sizeof(int32_t) * ADF_NFLAGS) != hipSuccess) st = ADF_EHIP;
     {   // fp16 hi/lo arena: per layer 9 H^2 + 2 (H*2H) ... computed exactly below
         const size_t HH = (size_t)H * H;
@@ -178,11 +125,11 @@ extern "C" int32_t adf_painn_create(const adf_painn_hparams* hp, adf_painn_t* ou
         const size_t per_head = HH + HH / 2 + 2 * HH + HH + HH / 4 + HH / 2;              // b0: vec1 vec2 un0 un2 ; b1: vec1 un0
         const size_t elems = (size_t)L * per_layer + (size_t)hp->num_heads * per_head;
         h->w16_bytes = elems * 2 * sizeof(uint16_t) + 4096;
-        if (st == ADF_OK) st = dev_alloc(&h->w16_arena, h->w16_bytes);
-        if (st == ADF_OK) st = dev_alloc(&h->w16_scales, 256);
-        if (st == ADF_OK) st = dev_alloc(&h->w16_bias_perm, (size_t)L * 2 * 3 * H);
-        if (st == ADF_OK) st = dev_alloc(&h->w16_scratch, 1);
-        if (st == ADF_OK) st = dev_alloc(&h->wfrag_arena, h->w16_bytes);
+        if (st == ADF_OK) st = m.alloc(&h->w16_arena, h->w16_bytes);
+        if (st == ADF_OK) st = m.alloc(&h->w16_scales, 256);
+        if (st == ADF_OK) st = m.alloc(&h->w16_bias_perm, (size_t)L * 2 * 3 * H);
+        if (st == ADF_OK) st = m.alloc(&h->w16_scratch, 1);
+        if (st == ADF_OK) st = m.alloc(&h->wfrag_arena, h->w16_bytes);
         const char* e = getenv("ADF_GEMM");
         h->gemm_f32 = e && strcmp(e, "f32") == 0;
         const char* el = getenv("ADF_LIFT");
@@ -193,75 +140,38 @@ extern "C" int32_t adf_painn_create(const adf_painn_hparams* hp, adf_painn_t* ou
         h->rmx = (er && atoi(er) == 0) ? 0 : 1;
         h->tune = adf_tune_from_env();
     }
-    if (st == ADF_OK) st = dev_alloc(&h->kcount, 8);
+    if (st == ADF_OK) st = m.alloc(&h->kcount, 8);
     if (st == ADF_OK && hipMemset(h->kcount, 0, 8 * sizeof(unsigned long long)) != hipSuccess) st = ADF_EHIP;
     if (st != ADF_OK) { adf_painn_destroy(h); return st; }
     *out = h;
     return ADF_OK;
 }
 
+// The owners null the fields they filled; what is reset here is the state that is not memory.
 static void inc_free(adf_painn* h) {
-    for (int l = 0; l <= ADF_MAX_LAYERS; ++l) {
-        if (h->incX[l]) (void)hipFree(h->incX[l]);
-        if (h->incV[l]) (void)hipFree(h->incV[l]);
-        if (l < ADF_MAX_LAYERS && h->incR[l]) (void)hipFree(h->incR[l]);
-        h->incX[l] = h->incV[l] = nullptr;
-        if (l < ADF_MAX_LAYERS) h->incR[l] = nullptr;
-    }
-    void* ptrs[] = {h->inc_c0, h->inc_chg, h->inc_pend, h->inc_need, h->inc_tf, h->inc_list, h->inc_cnt, h->inc_tmp};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    h->inc_c0 = h->inc_chg = h->inc_pend = h->inc_need = h->inc_tf = nullptr;
-    h->inc_list = h->inc_cnt = nullptr; h->inc_tmp = nullptr; h->inc_tmp_bytes = 0;
+    h->m_inc.release();
+    h->inc_tmp_bytes = 0;
     h->inc_capN = 0; h->inc_valid = false;
 }
 
 static void free_workspaces(adf_painn* h) {
-    void* ptrs[] = {h->nbr_cnt, h->nbr_src, h->nbr_shift, h->deg, h->nptr, h->cursor, h->img_cnt, h->sys_slow, h->scan_tmp,
-                    h->e_src, h->e_geom, h->x, h->vecA, h->vecB, h->y, h->xh, h->vv, h->cat, h->dot, h->sys, h->rec, h->lift.buf, h->mag_a, h->mag_b, h->mag_v3,
-                    h->rmx_part, h->cache_d2, h->cache_cid, h->cache_cnt, h->prev_nptr, h->prev_src, h->prev_geom};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    h->prev_nptr = h->prev_src = nullptr; h->prev_geom = nullptr; h->inc_valid = false;
-    h->nbr_cnt = h->nbr_src = h->nbr_shift = h->deg = h->nptr = h->cursor = h->img_cnt = h->sys_slow = h->e_src = nullptr;
-    h->scan_tmp = nullptr; h->scan_tmp_bytes = 0;
-    h->e_geom = nullptr;
-    h->x = h->vecA = h->vecB = h->y = h->xh = h->vv = h->cat = h->dot = h->sys = h->rec = nullptr;
-    h->lift.buf = h->mag_a = h->mag_b = h->mag_v3 = nullptr; h->lift.cap = 0; h->mag_v3_valid = false;
-    h->rmx_part = h->xpart = h->catpart = h->vpart = nullptr; h->part_stride = 0;
+    h->m_ws.release();
+    h->inc_valid = false;
+    h->scan_tmp_bytes = 0;
+    h->lift.cap = 0; h->mag_v3_valid = false;
+    h->xpart = h->catpart = h->vpart = nullptr; h->part_stride = 0;
     h->part_x = h->part_vec = nullptr; h->dbg_msg_rows = h->dbg_cat_rows = h->dbg_comb_rows = 0; h->dbg_mag = nullptr;
-    h->cache_d2 = nullptr; h->cache_cid = nullptr; h->cache_cnt = nullptr; h->cache_valid = false;
+    h->cache_valid = false;
     h->capN = h->capB = h->capE = 0;
 }
 
 extern "C" int32_t adf_painn_destroy(adf_painn_t h) {
     if (!h) return ADF_OK;
-    free_workspaces(h);
-    if (h->rbf_pack) (void)hipFree(h->rbf_pack);
-    if (h->rbf_bias_pack) (void)hipFree(h->rbf_bias_pack);
-    if (h->rec0) (void)hipFree(h->rec0);
-    inc_free(h);
     if (h->inc_cnt_host) (void)hipHostFree(h->inc_cnt_host);
     for (int i = 0; i < 2; ++i)
         if (h->inc_ev[i]) (void)hipEventDestroy((hipEvent_t)h->inc_ev[i]);
-    if (h->sub_x) (void)hipFree(h->sub_x);
-    if (h->sub_vec) (void)hipFree(h->sub_vec);
-    if (h->sub_f) (void)hipFree(h->sub_f);
-    if (h->rbf_pack16) (void)hipFree(h->rbf_pack16);
-    if (h->rbf_bias_pack16) (void)hipFree(h->rbf_bias_pack16);
-    if (h->rbf_scales) (void)hipFree(h->rbf_scales);
-    if (h->flags) (void)hipFree(h->flags);
-    if (h->kcount) (void)hipFree(h->kcount);
-    if (h->w16_arena) (void)hipFree(h->w16_arena);
-    if (h->wfrag_arena) (void)hipFree(h->wfrag_arena);
-    if (h->w16_scales) (void)hipFree(h->w16_scales);
-    if (h->w16_bias_perm) (void)hipFree(h->w16_bias_perm);
-    if (h->w16_scratch) (void)hipFree(h->w16_scratch);
-    if (h->oe0_buf) (void)hipFree(h->oe0_buf);
     adf_grad_free(h);
-    if (h->prof_ev) { for (hipEvent_t e : *h->prof_ev) (void)hipEventDestroy(e); delete h->prof_ev; }
-    delete h->prof_cat;
-    delete h;
+    delete h;   // the owners free the device buffers, the profiler its events
     return ADF_OK;
 }
 
@@ -367,7 +277,7 @@ static int32_t ensure_capacity(adf_painn* h, int64_t N, int64_t B) {
     // self image with a negative shift) and is then doubled: E <= 2*N*K.
     const int64_t capE = 2 * capN * K;
     int32_t st = ADF_OK;
-#define ALLOC(field, count) if (st == ADF_OK) st = dev_alloc(&h->field, (size_t)(count))
+#define ALLOC(field, count) if (st == ADF_OK) st = h->m_ws.alloc(&h->field, (size_t)(count))
     ALLOC(nbr_cnt, capN);
     ALLOC(nbr_src, capN * K);
     ALLOC(nbr_shift, capN * K);
@@ -388,9 +298,7 @@ static int32_t ensure_capacity(adf_painn* h, int64_t N, int64_t B) {
     }
     if (st == ADF_OK) {
         h->scan_tmp_bytes = adf_scan_temp_bytes(capN + 1);
-        unsigned char* tmp = nullptr;
-        st = dev_alloc(&tmp, h->scan_tmp_bytes + 16);
-        h->scan_tmp = tmp;
+        st = h->m_ws.alloc(&h->scan_tmp, h->scan_tmp_bytes + 16);
     }
     ALLOC(x, capN * H);
     ALLOC(vecA, capN * 3 * H);
@@ -715,19 +623,18 @@ __global__ void adf_scatter_rows3_kernel(const float* __restrict__ src, const in
     if (i < 3 * n) dst[(size_t)idx[i / 3] * 3 + i % 3] = src[i];
 }
 
-// head1_only (internal: the translation-only samplers read head 1 alone): f2 may be NULL and no out_forces2 product runs;
-// f1 is bit-identical to the two-head forward's
-static int32_t forward_impl(adf_painn_t h, const adf_batch* b, const int32_t* out_idx, int32_t n_out, float* f1,
-                            float* f2, void* stream, bool head1_only = false);
-
-extern "C" int32_t adf_painn_forward(adf_painn_t h, const adf_batch* b, float* f1, float* f2, void* stream) {
-    return forward_impl(h, b, nullptr, 0, f1, f2, stream);
-}
-
-extern "C" int32_t adf_painn_forward_subset(adf_painn_t h, const adf_batch* b, const int32_t* out_idx, int32_t n_out,
-                                            float* f1, float* f2, void* stream) {
-    if (!out_idx || n_out < 0) { adf_set_error("forward_subset: null index list"); return ADF_EINVAL; }
-    return forward_impl(h, b, out_idx, n_out, f1, f2, stream);
+// compact rows of a subset forward: sub_x / sub_vec / sub_f for n_out rows
+static int32_t ensure_subset(adf_painn* h, int32_t n_out) {
+    if (n_out <= h->capS) return ADF_OK;
+    const int64_t cap = (int64_t)n_out + n_out / 4 + 64;
+    const size_t H = h->hp.hidden_channels;
+    h->m_sub.release();
+    h->capS = 0;
+    ADF_TRY(h->m_sub.alloc(&h->sub_x, (size_t)cap * H));
+    ADF_TRY(h->m_sub.alloc(&h->sub_vec, (size_t)cap * 3 * H));
+    ADF_TRY(h->m_sub.alloc(&h->sub_f, (size_t)cap * 3));
+    h->capS = cap;
+    return ADF_OK;
 }
 
 // Incremental layers usable for this forward?  0 = no; 1 = yes and the kept state is current; 2 = yes, but every row has
@@ -745,22 +652,20 @@ static int inc_prepare(adf_painn* h, int N) {
         const size_t cap = (size_t)N;
         int32_t st = ADF_OK;
         for (int l = 0; l <= L && st == ADF_OK; ++l) {
-            st = dev_alloc(&h->incX[l], cap * H);
-            if (st == ADF_OK && l >= 1) st = dev_alloc(&h->incV[l], cap * 3 * H);
-            if (st == ADF_OK && l < L) st = dev_alloc(&h->incR[l], (cap + 1) * 5 * H);
+            st = h->m_inc.alloc(&h->incX[l], cap * H);
+            if (st == ADF_OK && l >= 1) st = h->m_inc.alloc(&h->incV[l], cap * 3 * H);
+            if (st == ADF_OK && l < L) st = h->m_inc.alloc(&h->incR[l], (cap + 1) * 5 * H);
         }
-        if (st == ADF_OK) st = dev_alloc(&h->inc_c0, cap);
-        if (st == ADF_OK) st = dev_alloc(&h->inc_chg, 2 * cap);
-        if (st == ADF_OK) st = dev_alloc(&h->inc_pend, cap * L);
-        if (st == ADF_OK) st = dev_alloc(&h->inc_need, cap * L);
-        if (st == ADF_OK) st = dev_alloc(&h->inc_tf, cap * L);
-        if (st == ADF_OK) st = dev_alloc(&h->inc_list, cap * L);
-        if (st == ADF_OK) st = dev_alloc(&h->inc_cnt, (size_t)2 * ADF_MAX_LAYERS + 1);
+        if (st == ADF_OK) st = h->m_inc.alloc(&h->inc_c0, cap);
+        if (st == ADF_OK) st = h->m_inc.alloc(&h->inc_chg, 2 * cap);
+        if (st == ADF_OK) st = h->m_inc.alloc(&h->inc_pend, cap * L);
+        if (st == ADF_OK) st = h->m_inc.alloc(&h->inc_need, cap * L);
+        if (st == ADF_OK) st = h->m_inc.alloc(&h->inc_tf, cap * L);
+        if (st == ADF_OK) st = h->m_inc.alloc(&h->inc_list, cap * L);
+        if (st == ADF_OK) st = h->m_inc.alloc(&h->inc_cnt, (size_t)2 * ADF_MAX_LAYERS + 1);
         if (st == ADF_OK) {
             h->inc_tmp_bytes = adf_inc_temp_bytes((int64_t)cap);
-            unsigned char* tmp = nullptr;
-            st = dev_alloc(&tmp, h->inc_tmp_bytes + 16);
-            h->inc_tmp = tmp;
+            st = h->m_inc.alloc(&h->inc_tmp, h->inc_tmp_bytes + 16);
         }
         if (st == ADF_OK && !h->inc_cnt_host &&
             hipHostMalloc(reinterpret_cast<void**>(&h->inc_cnt_host), sizeof(int32_t) * 2 * (2 * ADF_MAX_LAYERS + 1)) != hipSuccess)
@@ -786,9 +691,6 @@ static int inc_prepare(adf_painn* h, int N) {
     h->inc_valid = false;
     return state;
 }
-
-__global__ void adf_scatter_rows3_kernel(const float* __restrict__ src, const int32_t* __restrict__ idx, int n,
-                                         float* __restrict__ dst);
 
 // Counts of an earlier forward that have reached the pinned buffer: remember them (they steer the next forwards' choice
 // between the list and the all-rows form of a layer) and book that forward's statistics.  wait: block until they are there.
@@ -893,17 +795,7 @@ static int32_t forward_incremental(adf_painn* h, int N, const int32_t* Z, const 
         if (heads == 2) ADF_TRY(adf_head_forward(h, 1, N, h->incX[L], h->incV[L], f2, s));
         h->x_last = h->incX[L];
     } else {
-        if (n_out > h->capS) {
-            const int64_t c = (int64_t)n_out + n_out / 4 + 64;
-            if (h->sub_x) (void)hipFree(h->sub_x);
-            if (h->sub_vec) (void)hipFree(h->sub_vec);
-            if (h->sub_f) (void)hipFree(h->sub_f);
-            h->sub_x = h->sub_vec = h->sub_f = nullptr; h->capS = 0;
-            ADF_TRY(dev_alloc(&h->sub_x, (size_t)c * H));
-            ADF_TRY(dev_alloc(&h->sub_vec, (size_t)c * 3 * H));
-            ADF_TRY(dev_alloc(&h->sub_f, (size_t)c * 3));
-            h->capS = c;
-        }
+        ADF_TRY(ensure_subset(h, n_out));
         ADF_TRY(adf_inc_gather_rows(h->incX[L], out_idx, n_out, H, h->sub_x, s));
         ADF_TRY(adf_inc_gather_rows(h->incV[L], out_idx, n_out, 3 * H, h->sub_vec, s));
         for (int hd = 0; hd < heads; ++hd) {
@@ -918,8 +810,10 @@ static int32_t forward_incremental(adf_painn* h, int N, const int32_t* Z, const 
     return ADF_OK;
 }
 
+// head1_only (internal: the translation-only samplers read head 1 alone): f2 may be NULL and no out_forces2 product runs;
+// f1 is bit-identical to the two-head forward's
 static int32_t forward_impl(adf_painn_t h, const adf_batch* b, const int32_t* out_idx, int32_t n_out, float* f1,
-                            float* f2, void* stream, bool head1_only) {
+                            float* f2, void* stream, bool head1_only = false) {
     ADF_TRY(check_batch(h, b));
     if (!h->weights_set) { adf_set_error("weights not set"); return ADF_EINVAL; }
     const int heads = head1_only ? 1 : h->hp.num_heads;
@@ -948,9 +842,8 @@ static int32_t forward_impl(adf_painn_t h, const adf_batch* b, const int32_t* ou
     if (h->moving) {
         const size_t row = (size_t)5 * H;
         if ((int64_t)N + 1 > h->rec0_cap) {
-            if (h->rec0) { (void)hipFree(h->rec0); h->rec0 = nullptr; }
             h->rec0_cap = 0; h->rec0_valid = false;
-            ADF_TRY(dev_alloc(&h->rec0, ((size_t)N + 1) * row));
+            ADF_TRY(h->m_rec0.alloc(&h->rec0, ((size_t)N + 1) * row));
             h->rec0_cap = (int64_t)N + 1;
         }
         rec0 = h->rec0;
@@ -978,17 +871,7 @@ static int32_t forward_impl(adf_painn_t h, const adf_batch* b, const int32_t* ou
     // update and the heads run on compact rows.  Per-row arithmetic is unchanged, so the listed rows of f1 / f2
     // are bit-identical to adf_painn_forward's.
     if (n_out == 0) return ADF_OK;
-    if (n_out > h->capS) {
-        const int64_t cap = (int64_t)n_out + n_out / 4 + 64;
-        if (h->sub_x) (void)hipFree(h->sub_x);
-        if (h->sub_vec) (void)hipFree(h->sub_vec);
-        if (h->sub_f) (void)hipFree(h->sub_f);
-        h->sub_x = h->sub_vec = h->sub_f = nullptr; h->capS = 0;
-        ADF_TRY(dev_alloc(&h->sub_x, (size_t)cap * H));
-        ADF_TRY(dev_alloc(&h->sub_vec, (size_t)cap * 3 * H));
-        ADF_TRY(dev_alloc(&h->sub_f, (size_t)cap * 3));
-        h->capS = cap;
-    }
+    ADF_TRY(ensure_subset(h, n_out));
     for (int l = 0; l + 1 < L; ++l) {
         if (l == 0) ADF_TRY(message_layer(h, 0, N, h->x, vin, h->x, vout, true, s, nullptr, 0, rec0, rec0_ready));
         else
@@ -1010,6 +893,16 @@ static int32_t forward_impl(adf_painn_t h, const adf_batch* b, const int32_t* ou
     return ADF_OK;
 }
 
+extern "C" int32_t adf_painn_forward(adf_painn_t h, const adf_batch* b, float* f1, float* f2, void* stream) {
+    return forward_impl(h, b, nullptr, 0, f1, f2, stream);
+}
+
+extern "C" int32_t adf_painn_forward_subset(adf_painn_t h, const adf_batch* b, const int32_t* out_idx, int32_t n_out,
+                                            float* f1, float* f2, void* stream) {
+    if (!out_idx || n_out < 0) { adf_set_error("forward_subset: null index list"); return ADF_EINVAL; }
+    return forward_impl(h, b, out_idx, n_out, f1, f2, stream);
+}
+
 // ---- S2EF energy head (painn.py:412-414): per_atom = out_energy.2(ScaledSiLU(out_energy.0(x))), energy = per-system sum
 extern "C" int32_t adf_painn_set_energy_head(adf_painn_t h, int32_t n_weights, const void* const* w, void* stream) {
     if (!h || !w) { adf_set_error("null argument"); return ADF_EINVAL; }
@@ -1018,7 +911,7 @@ extern "C" int32_t adf_painn_set_energy_head(adf_painn_t h, int32_t n_weights, c
         if (!w[i]) { adf_set_error("energy-head tensor %d is null", i); return ADF_EINVAL; }
     const int H = h->hp.hidden_channels, H2 = H / 2;
     const size_t n = (size_t)H2 * H;
-    if (!h->oe0_buf) ADF_TRY(dev_alloc(&h->oe0_buf, n * 4 + 64));
+    if (!h->oe0_buf) ADF_TRY(h->m_life.alloc(&h->oe0_buf, n * 4 + 64));
     h->oe0_w = reinterpret_cast<const float*>(w[0]);
     h->oe0_b = reinterpret_cast<const float*>(w[1]);
     h->oe2_w = reinterpret_cast<const float*>(w[2]);
@@ -1100,9 +993,10 @@ extern "C" int32_t adf_linear_forward(const float* A, const float* W, const floa
     hipStream_t s = (hipStream_t)stream;
     if (!A || !W || !C || M <= 0 || N <= 0 || K <= 0) { adf_set_error("bad argument"); return ADF_EINVAL; }
     if (mode == 0) return adf_launch_gemm(A, K, W, K, bias, C, N, M, N, K, act_ssilu, s);
+    adf_pool tmp;   // frees buf / mags on every return
     unsigned char* buf = nullptr;
     const size_t n = (size_t)N * K;
-    ADF_TRY(dev_alloc(&buf, n * 4 + 64));
+    ADF_TRY(tmp.alloc(&buf, n * 4 + 64));
     adf_w16 w16 = {};
     w16.hi = buf; w16.lo = buf + n * 2; w16.inv_scale = reinterpret_cast<float*>(buf + n * 4);
     unsigned int* scratch = reinterpret_cast<unsigned int*>(buf + n * 4 + 16);
@@ -1110,13 +1004,11 @@ extern "C" int32_t adf_linear_forward(const float* A, const float* W, const floa
     float* mags = nullptr;
     const char* el = getenv("ADF_LIFT");
     const bool lift = !(el && strcmp(el, "0") == 0);
-    if (st == ADF_OK && lift) st = dev_alloc(&mags, (size_t)M);
+    if (st == ADF_OK && lift) st = tmp.alloc(&mags, (size_t)M);
     adf_lift lf = {mags, M};
     if (st == ADF_OK) st = adf_launch_gemm16(A, K, &w16, bias, C, N, M, N, K, act_ssilu, nullptr, s, lift ? &lf : nullptr,
                                              adf_tune_process(), adf_current_num_cus());
     (void)hipStreamSynchronize(s);
-    (void)hipFree(buf);
-    if (mags) (void)hipFree(mags);
     return st;
 }
 
@@ -1141,9 +1033,9 @@ extern "C" int32_t adf_painn_set_incremental(adf_painn_t h, int32_t on) {
         h->inc_on = on != 0;
         if (!h->inc_on) inc_free(h);
         if (h->inc_on && h->capN > 0 && !h->prev_nptr) {  // workspaces exist without the previous-CSR buffers
-            int32_t st = dev_alloc(&h->prev_nptr, (size_t)h->capN + 1);
-            if (st == ADF_OK) st = dev_alloc(&h->prev_src, (size_t)h->capE);
-            if (st == ADF_OK) st = dev_alloc(&h->prev_geom, (size_t)h->capE);
+            int32_t st = h->m_ws.alloc(&h->prev_nptr, (size_t)h->capN + 1);
+            if (st == ADF_OK) st = h->m_ws.alloc(&h->prev_src, (size_t)h->capE);
+            if (st == ADF_OK) st = h->m_ws.alloc(&h->prev_geom, (size_t)h->capE);
             if (st != ADF_OK) { h->inc_on = false; return st; }
         }
     }

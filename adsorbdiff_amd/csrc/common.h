@@ -35,6 +35,95 @@ void adf_set_error(const char* fmt, ...);
         if (_s != ADF_OK) return _s;      \
     } while (0)
 
+// ---- device memory: the one owner type.  A pool fills pointer fields (of a handle, or locals of the function that holds
+// the pool) and remembers their ADDRESSES, so it frees whatever a field holds at release time (fields that are swapped
+// among themselves stay correct) and nulls the field itself.  Handles are heap objects: their fields do not move.
+// It never synchronises: the caller does where enqueued work may still use the buffers.
+struct adf_pool {
+    std::vector<void**> slots;
+    adf_pool() = default;
+    adf_pool(const adf_pool&) = delete;
+    adf_pool& operator=(const adf_pool&) = delete;
+    ~adf_pool() { release(); }
+    // *field = new buffer of `bytes` bytes (0 is rounded up: a filled field is never null).  A field this pool filled
+    // before is re-allocated: its old buffer is freed first.  On failure *field is null.
+    int32_t alloc(void** field, size_t bytes) {
+        bool known = false;
+        for (void** s : slots) known = known || s == field;
+        if (known) { if (*field) (void)hipFree(*field); } else slots.push_back(field);
+        *field = nullptr;
+        if (bytes == 0) bytes = 16;
+        const hipError_t e = hipMalloc(field, bytes);
+        if (e == hipSuccess) return ADF_OK;
+        *field = nullptr;
+        (void)hipGetLastError();
+        adf_set_error("device allocation of %zu bytes failed: %s", bytes, hipGetErrorString(e));
+        return ADF_EOOM;
+    }
+    template <typename T>
+    int32_t alloc(T** field, size_t count) { return alloc(reinterpret_cast<void**>(field), count * sizeof(T)); }
+    void release() {
+        for (void** s : slots) {
+            if (*s) (void)hipFree(*s);
+            *s = nullptr;
+        }
+        slots.clear();
+    }
+};
+
+// ---- HIP-event profiling (bench.py roofline): pairs of events on the launch stream around kernel groups, a category per pair
+struct adf_prof {
+    bool on = false;
+    bool open = false;                // a begin has recorded its event and waits for its end
+    std::vector<hipEvent_t> ev;       // pool of events, used pairwise
+    std::vector<int> cat;             // category of every recorded pair
+    size_t used = 0;                  // events of the finished pairs
+    adf_prof() = default;
+    adf_prof(const adf_prof&) = delete;
+    adf_prof& operator=(const adf_prof&) = delete;
+    ~adf_prof() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
+    // no events to be had: this begin and its end do nothing
+    void begin(int c, hipStream_t s) {
+        open = false;
+        if (!on) return;
+        if (used + 2 > ev.size())
+            for (int i = 0; i < 512; ++i) {
+                hipEvent_t e;
+                if (hipEventCreate(&e) != hipSuccess) { (void)hipGetLastError(); break; }
+                ev.push_back(e);
+            }
+        if (used + 2 > ev.size()) return;
+        cat.resize(used / 2);         // (drops a pair that an error return left without its end)
+        cat.push_back(c);
+        (void)hipEventRecord(ev[used], s);
+        open = true;
+    }
+    void end(hipStream_t s) {
+        if (!on || !open) return;
+        (void)hipEventRecord(ev[used + 1], s);
+        used += 2;
+        open = false;
+    }
+    void enable(bool o) { on = o; open = false; used = 0; cat.clear(); }
+    // per category: summed milliseconds and number of pairs since the last read (the stream must be idle); then empty
+    int32_t read(float* ms, int64_t* count, int ncat) {
+        for (int c = 0; c < ncat; ++c) { ms[c] = 0.f; count[c] = 0; }
+        for (size_t i = 0; i < used; i += 2) {
+            float t = 0.f;
+            ADF_HIP_CHECK(hipEventElapsedTime(&t, ev[i], ev[i + 1]));
+            ms[cat[i / 2]] += t;
+            count[cat[i / 2]] += 1;
+        }
+        enable(on);
+        return ADF_OK;
+    }
+    struct scope {
+        adf_prof& p; hipStream_t s;
+        scope(adf_prof& p_, int c, hipStream_t s_) : p(p_), s(s_) { p.begin(c, s); }
+        ~scope() { p.end(s); }
+    };
+};
+
 // fp16 hi/lo split of one nn.Linear weight (gemm16.hip), library-owned
 struct adf_w16 {
     void* hi;
@@ -227,16 +316,19 @@ struct adf_painn {
     int32_t last_reps[3];
     int num_cus;
     // ---- optional HIP-event profiling of the forward (bench.py roofline); see api.hip
-    bool prof_on;
-    std::vector<hipEvent_t>* prof_ev;     // pool of events, used pairwise
-    std::vector<int>* prof_cat;           // category of every recorded pair
-    size_t prof_used;                     // events handed out
+    adf_prof prof;
     unsigned long long* kcount;           // device counter: executed k-steps of the message kernel
+    // ---- owners of the device buffers above, one per set that lives and dies together
+    adf_pool m_life;   // creation to destruction: rbf_pack*, flags, kcount, the w16_* and wfrag arenas, oe0_buf
+    adf_pool m_ws;     // the workspaces sized by capN / capB / capE, prev_* and rmx_part included
+    adf_pool m_inc;    // incremental layers: incX / incV / incR, inc_*
+    adf_pool m_sub;    // sub_x / sub_vec / sub_f
+    adf_pool m_rec0;   // rec0
 };
 
 enum { ADF_PROF_GRAPH = 0, ADF_PROF_MESSAGE = 1, ADF_PROF_NODE = 2, ADF_PROF_HEADS = 3, ADF_PROF_STEPPER = 4 };
-void adf_prof_begin(adf_painn* h, int cat, hipStream_t s);
-void adf_prof_end(adf_painn* h, hipStream_t s);
+static inline void adf_prof_begin(adf_painn* h, int cat, hipStream_t s) { h->prof.begin(cat, s); }
+static inline void adf_prof_end(adf_painn* h, hipStream_t s) { h->prof.end(s); }
 
 // ---- kernels' host launchers (each enqueues on `s`, returns ADF_*)
 int32_t adf_launch_gemm(const float* A, int lda, const float* W, int ldw, const float* bias, float* C, int ldc,

@@ -43,13 +43,14 @@ struct adf_grad {
     int32_t* rev;
     long long ecap;
     int part_slices;
+    adf_pool m_w;    // warena, wscales
+    adf_pool m_ws;   // act, part, rev
 };
 
 static adf_grad* eg_state(adf_painn* h) {
     if (!h->grad) {
         adf_grad* g = new (std::nothrow) adf_grad();
         if (!g) return nullptr;
-        memset(g, 0, sizeof(*g));
         h->grad = g;
     }
     return reinterpret_cast<adf_grad*>(h->grad);
@@ -60,25 +61,9 @@ void adf_grad_invalidate(adf_painn* h) {
 }
 
 void adf_grad_free(adf_painn* h) {
-    if (!h || !h->grad) return;
-    adf_grad* g = reinterpret_cast<adf_grad*>(h->grad);
-    void* ptrs[] = {g->warena, g->wscales, g->act, g->part, g->rev};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    delete g;
+    if (!h) return;
+    delete reinterpret_cast<adf_grad*>(h->grad);
     h->grad = nullptr;
-}
-
-static int32_t eg_malloc(void** p, size_t bytes, const char* what) {
-    *p = nullptr;
-    hipError_t e = hipMalloc(p, bytes);
-    if (e != hipSuccess) {
-        *p = nullptr;
-        (void)hipGetLastError();
-        adf_set_error("energy gradient: hipMalloc of %zu bytes (%s) failed: %s", bytes, what, hipGetErrorString(e));
-        return ADF_EOOM;
-    }
-    return ADF_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ small kernels
@@ -289,9 +274,8 @@ static int32_t eg_build_weights(adf_painn* h, adf_grad* g, hipStream_t s) {
     const Shape shp[EG_NW] = {{H, H}, {3 * H, H}, {2 * H, H}, {H, 2 * H}, {3 * H, H}};
     auto al = eg_al;
     const size_t bytes = eg_weight_bytes(h);
-    if (g->warena) { (void)hipFree(g->warena); g->warena = nullptr; }
-    if (!g->wscales) ADF_TRY(eg_malloc(reinterpret_cast<void**>(&g->wscales), sizeof(float) * (2 * EG_NW * ADF_MAX_LAYERS + 8), "weight scales"));
-    ADF_TRY(eg_malloc(reinterpret_cast<void**>(&g->warena), bytes, "transposed weight images"));
+    if (!g->wscales) ADF_TRY(g->m_w.alloc(&g->wscales, (size_t)2 * EG_NW * ADF_MAX_LAYERS + 8));
+    ADF_TRY(g->m_w.alloc(&g->warena, bytes));
     unsigned char* cur = g->warena;
     int nscale = 0;
     auto image = [&](const float* w, long long n, long long k, EgW* out) -> int32_t {   // split + fragment image of w [n, k]
@@ -417,14 +401,12 @@ extern "C" int32_t adf_painn_forward_energy_gradient(adf_painn_t h, const adf_ba
     eg_layout(N, H, L, nullptr, &w);
     if (w.total > g->act_floats || ecap > g->ecap || nslices > g->part_slices) {
         ADF_HIP_CHECK(hipDeviceSynchronize());   // enqueued work may still use the buffers
-        void* old[] = {g->act, g->part, g->rev};
-        for (void* p : old)
-            if (p) (void)hipFree(p);
-        g->act = nullptr; g->part = nullptr; g->rev = nullptr; g->act_floats = 0; g->ecap = 0; g->part_slices = 0;
+        g->m_ws.release();
+        g->act_floats = 0; g->ecap = 0; g->part_slices = 0;
         const int sl = H / ADF_SLICE_CH;   // room for either arithmetic
-        ADF_TRY(eg_malloc(reinterpret_cast<void**>(&g->act), w.total * sizeof(float), "activations"));
-        ADF_TRY(eg_malloc(reinterpret_cast<void**>(&g->part), (size_t)ecap * sl * sizeof(float4), "per-edge partial gradients"));
-        ADF_TRY(eg_malloc(reinterpret_cast<void**>(&g->rev), (size_t)ecap * sizeof(int32_t), "reverse-edge index"));
+        ADF_TRY(g->m_ws.alloc(&g->act, w.total));
+        ADF_TRY(g->m_ws.alloc(&g->part, (size_t)ecap * sl));
+        ADF_TRY(g->m_ws.alloc(&g->rev, (size_t)ecap));
         g->act_floats = w.total; g->ecap = ecap; g->part_slices = sl;
     }
     eg_layout(N, H, L, g->act, &w);
@@ -448,10 +430,10 @@ extern "C" int32_t adf_painn_forward_energy_gradient(adf_painn_t h, const adf_ba
         ADF_TRY(adf_pack_records(h, N, a.xh, a.vec, vz, s));
         {   // profiling of a gradient evaluation times and counts the geometry kernel alone: the forward message kernel
             // must not add its k-steps to the handle's one counter
-            const bool prof = h->prof_on;
-            h->prof_on = false;
+            const bool prof = h->prof.on;
+            h->prof.on = false;
             const int32_t st = adf_message_impl(h, l, N, a.x, a.xh, a.vec, x1, vec1, vz, s);
-            h->prof_on = prof;
+            h->prof.on = prof;
             ADF_TRY(st);
         }
         ADF_TRY(eg_lin(h, vec1, H, g->fw[l][EG_VP], nullptr, a.vv, 2 * H, 3ll * N, 2 * H, H, s));

@@ -155,10 +155,16 @@ struct adf_eqv2 {
     int64_t last_block_rows;           // block rows the last forward computed (all blocks: layers x N)
     int64_t prof_block_rows, prof_forwards;   // the same summed over the forwards since adf_eqv2_profile_enable(1)
     // HIP-event timing per kernel group (bench.py roofline)
-    bool prof_on;
-    std::vector<hipEvent_t>* prof_ev;
-    std::vector<int>* prof_cat;
-    size_t prof_used;
+    adf_prof prof;
+    // ---- owners of the device buffers above, one per set that lives and dies together
+    adf_pool m_life;    // creation to destruction: flags, d_dev
+    adf_pool m_const;   // adf_eqv2_set_constants: jd, to_* / from_*, s2tab, gtab_*
+    adf_pool m_w;       // images of the bound weights: w16_*, wfrag_arena, wt_arena, rtab_arena, fold_arena, pair0_arena, eh_*
+    adf_pool m_ws;      // the workspaces sized by capN / capB / capE
+    adf_pool m_inc;     // incremental blocks: inc_*
+    adf_pool m_sub;     // sub_*
+    adf_pool m_xe;      // xe_*
+    adf_pool m_ee;      // ee_*
 };
 
 enum { EQ_PROF_GRAPH = 0, EQ_PROF_RADIAL, EQ_PROF_ROTATE, EQ_PROF_CONV, EQ_PROF_S2ACT, EQ_PROF_ATTN, EQ_PROF_NODE,

@@ -23,47 +23,7 @@ int32_t eq_launch_gemm16(const float* A, const eq_rowmap* am, const float* rscal
                          float* Cm, const eq_rowmap* cm, long long M, int N, int K, int act, bool accumulate,
                          hipStream_t s, const adf_tune& tune, float* out_mag, int rs_div = 1);
 
-template <typename T>
-static int32_t eq_alloc(T** p, size_t count) {
-    *p = nullptr;
-    if (count == 0) count = 1;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T));
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        adf_set_error("eqv2: device allocation of %zu bytes failed: %s", count * sizeof(T), hipGetErrorString(e));
-        return ADF_EOOM;
-    }
-    return ADF_OK;
-}
-template <typename T>
-static void eq_free(T*& p) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-}
-
-// ---------------------------------------------------------------------------------------------- profiling
-static void eq_prof_begin(adf_eqv2* h, int cat, hipStream_t s) {
-    if (!h->prof_on) return;
-    if (h->prof_used + 2 > h->prof_ev->size()) {
-        for (int i = 0; i < 2; ++i) {
-            hipEvent_t e;
-            if (hipEventCreate(&e) != hipSuccess) return;
-            h->prof_ev->push_back(e);
-        }
-    }
-    h->prof_cat->push_back(cat);
-    (void)hipEventRecord((*h->prof_ev)[h->prof_used], s);
-}
-static void eq_prof_end(adf_eqv2* h, hipStream_t s) {
-    if (!h->prof_on || h->prof_used + 2 > h->prof_ev->size()) return;
-    (void)hipEventRecord((*h->prof_ev)[h->prof_used + 1], s);
-    h->prof_used += 2;
-}
-struct eq_prof_scope {
-    adf_eqv2* h; hipStream_t s;
-    eq_prof_scope(adf_eqv2* h_, int cat, hipStream_t s_) : h(h_), s(s_) { eq_prof_begin(h, cat, s); }
-    ~eq_prof_scope() { eq_prof_end(h, s); }
-};
+using eq_prof_scope = adf_prof::scope;   // eq_prof_scope ps(h->prof, category, stream)
 
 // ---------------------------------------------------------------------------------------------- create / destroy
 static void eq_fill_dims(adf_eqv2* h) {
@@ -111,13 +71,15 @@ extern "C" int32_t adf_eqv2_create(const adf_eqv2_hparams* hp, adf_eqv2_t* out) 
     }
     adf_eqv2* h = new (std::nothrow) adf_eqv2();
     if (!h) { adf_set_error("eqv2_create: host allocation failed"); return ADF_EOOM; }
-    memset(static_cast<void*>(h), 0, sizeof(*h));
     h->hp = *hp;
     eq_fill_dims(h);
     if ((2 * h->d.M + 1) * (2 * h->d.L + 1) > 13 * 13 || h->d.Sr > 49) { delete h; adf_set_error("eqv2_create: lmax / mmax too large"); return ADF_EINVAL; }
-    ADF_HIP_CHECK(hipGetDevice(&h->device));
     hipDeviceProp_t prop;
-    ADF_HIP_CHECK(hipGetDeviceProperties(&prop, h->device));
+    if (hipGetDevice(&h->device) != hipSuccess || hipGetDeviceProperties(&prop, h->device) != hipSuccess) {
+        adf_set_error("no usable HIP device: %s", hipGetErrorString(hipGetLastError()));
+        delete h;
+        return ADF_EHIP;
+    }
     h->num_cus = prop.multiProcessorCount;
     const char* env = getenv("ADF_GEMM");
     h->exact_f32 = env && !strcmp(env, "f32");
@@ -131,10 +93,8 @@ extern "C" int32_t adf_eqv2_create(const adf_eqv2_hparams* hp, adf_eqv2_t* out) 
     { const char* e4 = getenv("ADF_EQV2_FOLD"); h->fold_on = !(e4 && atoi(e4) == 0); }
     { const char* e5 = getenv("ADF_EQV2_COMPACT"); h->no_compact = e5 && atoi(e5) == 0; }
     h->tune = adf_tune_from_env();
-    h->prof_ev = new std::vector<hipEvent_t>();
-    h->prof_cat = new std::vector<int>();
-    int32_t st = eq_alloc(&h->flags, EQ_NFLAGS);
-    if (st == ADF_OK) st = eq_alloc(&h->d_dev, 1);
+    int32_t st = h->m_life.alloc(&h->flags, EQ_NFLAGS);
+    if (st == ADF_OK) st = h->m_life.alloc(&h->d_dev, 1);
     if (st == ADF_OK && hipMemcpy(h->d_dev, &h->d, sizeof(eq_dims), hipMemcpyHostToDevice) != hipSuccess) st = ADF_EHIP;
     if (st == ADF_OK) { hipError_t e = hipMemset(h->flags, 0, sizeof(int32_t) * EQ_NFLAGS); if (e != hipSuccess) st = ADF_EHIP; }
     if (st != ADF_OK) { adf_eqv2_destroy(h); return st; }
@@ -142,25 +102,18 @@ extern "C" int32_t adf_eqv2_create(const adf_eqv2_hparams* hp, adf_eqv2_t* out) 
     return ADF_OK;
 }
 
+// The owners null the fields they filled; what is reset here is the state that is not memory.
 static void eq_inc_free(adf_eqv2* h) {
-    for (int i = 0; i <= EQ_MAX_LAYERS; ++i) eq_free(h->inc_x[i]);
-    eq_free(h->inc_xg); eq_free(h->inc_peptr); eq_free(h->inc_psrc); eq_free(h->inc_pvec); eq_free(h->inc_dirty);
-    eq_free(h->inc_idx); eq_free(h->inc_cnt);
-    if (h->inc_sel_tmp) { (void)hipFree(h->inc_sel_tmp); h->inc_sel_tmp = nullptr; }
+    h->m_inc.release();
     h->inc_capN = h->inc_capE = 0; h->inc_nl = 0; h->inc_sel_bytes = 0;
     h->inc_valid = false;
 }
 
 static void eq_free_workspaces(adf_eqv2* h) {
     eq_inc_free(h);
-    eq_free(h->nbr_cnt); eq_free(h->nbr_src); eq_free(h->nbr_shift); eq_free(h->img_cnt); eq_free(h->eptr);
-    eq_free(h->e_src); eq_free(h->e_dst); eq_free(h->e_vec); eq_free(h->wig);
-    eq_free(h->sub_eptr); eq_free(h->sub_src); eq_free(h->sub_dst); eq_free(h->sub_vec); eq_free(h->sub_wig); eq_free(h->sub_f);
+    h->m_sub.release();
     h->sub_cap = 0;
-    if (h->scan_tmp) { (void)hipFree(h->scan_tmp); h->scan_tmp = nullptr; }
-    eq_free(h->cache_d2); eq_free(h->cache_cid); eq_free(h->cache_cnt);
-    eq_free(h->x); eq_free(h->y); eq_free(h->agg); eq_free(h->gate); eq_free(h->h1); eq_free(h->h2);
-    eq_free(h->arena); eq_free(h->garena); eq_free(h->sys); eq_free(h->rs);
+    h->m_ws.release();
     h->rs_cap = 0;
     h->capN = h->capB = h->capE = 0;
     h->arena_floats = h->garena_floats = 0;
@@ -169,19 +122,7 @@ static void eq_free_workspaces(adf_eqv2* h) {
 extern "C" int32_t adf_eqv2_destroy(adf_eqv2_t h) {
     if (!h) return ADF_OK;
     (void)hipDeviceSynchronize();
-    eq_free_workspaces(h);
-    eq_free(h->flags); eq_free(h->d_dev);
-    eq_free(h->ee_wb); eq_free(h->ee_energy); eq_free(h->ee_term);
-    eq_free(h->xe_src); eq_free(h->xe_dst); eq_free(h->xe_vec);
-    { unsigned char* t = (unsigned char*)h->s2tab; eq_free(t); h->s2tab = nullptr; }
-    { unsigned char* t = (unsigned char*)h->gtab_to; eq_free(t); h->gtab_to = nullptr; }
-    { unsigned char* t = (unsigned char*)h->gtab_from; eq_free(t); h->gtab_from = nullptr; }
-    eq_free(h->jd); eq_free(h->to_red); eq_free(h->from_red); eq_free(h->to_full); eq_free(h->from_full);
-    eq_free(h->w16_arena); eq_free(h->wfrag_arena); eq_free(h->w16_scales); eq_free(h->w16_scratch); eq_free(h->wt_arena); eq_free(h->rtab_arena); eq_free(h->fold_arena);
-    eq_free(h->pair0_arena); eq_free(h->eh_w16); eq_free(h->eh_scale);
-    if (h->prof_ev) { for (hipEvent_t e : *h->prof_ev) (void)hipEventDestroy(e); delete h->prof_ev; }
-    delete h->prof_cat;
-    delete h;
+    delete h;   // the owners free the device buffers, the profiler its events
     return ADF_OK;
 }
 
@@ -190,12 +131,11 @@ extern "C" int32_t adf_eqv2_set_constants(adf_eqv2_t h, const float* jd, const f
     if (!h || !jd || !to_red || !from_red || !to_full || !from_full) { adf_set_error("eqv2_set_constants: null argument"); return ADF_EINVAL; }
     const eq_dims& d = h->d;
     const size_t nj = d.j_off[d.L + 1], nr = (size_t)d.G * d.Sr, nf = (size_t)d.G * d.S;
-    eq_free(h->jd); eq_free(h->to_red); eq_free(h->from_red); eq_free(h->to_full); eq_free(h->from_full);
-    { unsigned char* t = (unsigned char*)h->s2tab; eq_free(t); h->s2tab = nullptr; }
-    { unsigned char* t = (unsigned char*)h->gtab_to; eq_free(t); h->gtab_to = nullptr; }
-    { unsigned char* t = (unsigned char*)h->gtab_from; eq_free(t); h->gtab_from = nullptr; }
-    ADF_TRY(eq_alloc(&h->jd, nj)); ADF_TRY(eq_alloc(&h->to_red, nr)); ADF_TRY(eq_alloc(&h->from_red, nr));
-    ADF_TRY(eq_alloc(&h->to_full, nf)); ADF_TRY(eq_alloc(&h->from_full, nf));
+    adf_pool& m = h->m_const;
+    m.release();
+    h->consts_set = false;
+    ADF_TRY(m.alloc(&h->jd, nj)); ADF_TRY(m.alloc(&h->to_red, nr)); ADF_TRY(m.alloc(&h->from_red, nr));
+    ADF_TRY(m.alloc(&h->to_full, nf)); ADF_TRY(m.alloc(&h->from_full, nf));
     ADF_HIP_CHECK(hipMemcpy(h->jd, jd, nj * 4, hipMemcpyHostToDevice));
     ADF_HIP_CHECK(hipMemcpy(h->to_red, to_red, nr * 4, hipMemcpyHostToDevice));
     ADF_HIP_CHECK(hipMemcpy(h->from_red, from_red, nr * 4, hipMemcpyHostToDevice));
@@ -240,10 +180,9 @@ extern "C" int32_t adf_eqv2_set_constants(adf_eqv2_t h, const float* jd, const f
                         img[((nh8 + base + lane) * 8) + j] = fh;
                         img[((nh8 + base + 64 + lane) * 8) + j] = (_Float16)(fv - (float)fh);
                     }
-        unsigned char* dev = nullptr;
-        ADF_TRY(eq_alloc(&dev, img.size() * 2));
-        ADF_HIP_CHECK(hipMemcpy(dev, img.data(), img.size() * 2, hipMemcpyHostToDevice));
-        h->s2tab = dev; h->s2_npb = npb; h->s2_inv_sT = 1.0f / sT; h->s2_inv_sF = 1.0f / sF;
+        ADF_TRY(m.alloc(&h->s2tab, img.size() * 2));
+        ADF_HIP_CHECK(hipMemcpy(h->s2tab, img.data(), img.size() * 2, hipMemcpyHostToDevice));
+        h->s2_npb = npb; h->s2_inv_sT = 1.0f / sT; h->s2_inv_sF = 1.0f / sF;
         h->s2_gain_shift = ldexpf(1.0f, -ge);
     }
     // and of to_full / from_full for the feed-forward grid transforms
@@ -276,11 +215,10 @@ extern "C" int32_t adf_eqv2_set_constants(adf_eqv2_t h, const float* jd, const f
                         fi[(base + 64 + lane) * 8 + j] = (_Float16)(v - (float)hh);
                     }
             }
-        unsigned char *dt = nullptr, *df = nullptr;
-        ADF_TRY(eq_alloc(&dt, ti.size() * 2)); ADF_TRY(eq_alloc(&df, fi.size() * 2));
-        ADF_HIP_CHECK(hipMemcpy(dt, ti.data(), ti.size() * 2, hipMemcpyHostToDevice));
-        ADF_HIP_CHECK(hipMemcpy(df, fi.data(), fi.size() * 2, hipMemcpyHostToDevice));
-        h->gtab_to = dt; h->gtab_from = df; h->g_npb = npb; h->g_nkst = nkst; h->g_inv_sT = 1.0f / sT; h->g_inv_sF = 1.0f / sF;
+        ADF_TRY(m.alloc(&h->gtab_to, ti.size() * 2)); ADF_TRY(m.alloc(&h->gtab_from, fi.size() * 2));
+        ADF_HIP_CHECK(hipMemcpy(h->gtab_to, ti.data(), ti.size() * 2, hipMemcpyHostToDevice));
+        ADF_HIP_CHECK(hipMemcpy(h->gtab_from, fi.data(), fi.size() * 2, hipMemcpyHostToDevice));
+        h->g_npb = npb; h->g_nkst = nkst; h->g_inv_sT = 1.0f / sT; h->g_inv_sF = 1.0f / sF;
     }
     h->consts_set = true;
     return ADF_OK;
@@ -362,14 +300,13 @@ static int32_t eq_split_weights(adf_eqv2* h, hipStream_t s) {
     }
     if (h->w16_bytes < halves * 2 + 64) {
         ADF_HIP_CHECK(hipDeviceSynchronize());
-        eq_free(h->w16_arena); eq_free(h->wfrag_arena);
-        ADF_TRY(eq_alloc(&h->w16_arena, halves * 2 + 64));
-        ADF_TRY(eq_alloc(&h->wfrag_arena, halves * 2 + 64));
+        h->w16_bytes = 0;
+        ADF_TRY(h->m_w.alloc(&h->w16_arena, halves * 2 + 64));
+        ADF_TRY(h->m_w.alloc(&h->wfrag_arena, halves * 2 + 64));
         h->w16_bytes = halves * 2 + 64;
     }
-    eq_free(h->w16_scales);
-    ADF_TRY(eq_alloc(&h->w16_scales, nmat + 1));
-    if (!h->w16_scratch) ADF_TRY(eq_alloc(&h->w16_scratch, 4));
+    ADF_TRY(h->m_w.alloc(&h->w16_scales, nmat + 1));
+    if (!h->w16_scratch) ADF_TRY(h->m_w.alloc(&h->w16_scratch, 4));
     unsigned char* p = h->w16_arena;
     unsigned char* pf = h->wfrag_arena;
     size_t k = 0;
@@ -418,18 +355,15 @@ static int32_t eq_radial_static(adf_eqv2* h, eq_radial** rads, int nrad, hipStre
     for (int i = 0; i < nrad; ++i) total += (size_t)NE * NE * rads[i]->l6.out;
     if (h->rtab_floats < total) {
         ADF_HIP_CHECK(hipDeviceSynchronize());
-        eq_free(h->rtab_arena);
-        if (eq_alloc(&h->rtab_arena, total) != ADF_OK) { h->rtab_floats = 0; return ADF_OK; }  // no room: per-edge mode
+        if (h->m_w.alloc(&h->rtab_arena, total) != ADF_OK) { h->rtab_floats = 0; return ADF_OK; }  // no room: per-edge mode
         h->rtab_floats = total;
     }
+    adf_pool tmp;   // frees the scratch rows on every return
     float *t1 = nullptr, *t2 = nullptr, *rs = nullptr;
     const long long rows = (long long)NE * NE;
-    if (eq_alloc(&t1, (size_t)rows * d.EC) != ADF_OK || eq_alloc(&t2, (size_t)rows * d.EC) != ADF_OK ||
-        eq_alloc(&rs, (size_t)rows) != ADF_OK) {  // no room for the scratch rows: per-edge mode
-        eq_free(t1); eq_free(t2); eq_free(rs);
-        (void)hipGetLastError();
+    if (tmp.alloc(&t1, (size_t)rows * d.EC) != ADF_OK || tmp.alloc(&t2, (size_t)rows * d.EC) != ADF_OK ||
+        tmp.alloc(&rs, (size_t)rows) != ADF_OK)   // no room for the scratch rows: per-edge mode
         return ADF_OK;
-    }
     float* keep_rs = h->rs; const int64_t keep_cap = h->rs_cap;
     h->rs = rs; h->rs_cap = rows;
     // The tables are built ONCE per weight binding and are then read by both arithmetics (adf_eqv2_set_arithmetic only flips
@@ -454,7 +388,6 @@ static int32_t eq_radial_static(adf_eqv2* h, eq_radial** rads, int nrad, hipStre
     (void)hipStreamSynchronize(s);
     h->exact_f32 = keep_exact;
     h->rs = keep_rs; h->rs_cap = keep_cap;
-    eq_free(t1); eq_free(t2); eq_free(rs);
     if (st != ADF_OK) { for (int i = 0; i < nrad; ++i) rads[i]->table = nullptr; return st; }
     h->rad_static = true;
     return ADF_OK;
@@ -467,9 +400,8 @@ static int32_t eq_radial_pair_tables(adf_eqv2* h, eq_radial** rads, const float*
     const size_t per = (size_t)h->hp.max_num_elements * h->hp.max_num_elements * h->d.EC;
     if (h->pair0_floats < per * nrad) {
         ADF_HIP_CHECK(hipDeviceSynchronize());
-        eq_free(h->pair0_arena);
         h->pair0_floats = 0;
-        ADF_TRY(eq_alloc(&h->pair0_arena, per * nrad));
+        ADF_TRY(h->m_w.alloc(&h->pair0_arena, per * nrad));
         h->pair0_floats = per * nrad;
     }
     for (int i = 0; i < nrad; ++i) {
@@ -490,9 +422,8 @@ static int32_t eq_fold_ffn(adf_eqv2* h, hipStream_t s) {
     const size_t total = per * h->hp.num_layers;
     if (h->fold_floats < total) {
         ADF_HIP_CHECK(hipDeviceSynchronize());
-        eq_free(h->fold_arena);
         h->fold_floats = 0;
-        ADF_TRY(eq_alloc(&h->fold_arena, total));
+        ADF_TRY(h->m_w.alloc(&h->fold_arena, total));
         h->fold_floats = total;
     }
     float* p = h->fold_arena;
@@ -555,8 +486,8 @@ static int32_t eq_set_weights(adf_eqv2_t h, int32_t n_weights, const void* const
     const int nrad = 1 + h->hp.num_layers + (s2ef ? 1 : 2);
     const size_t per = (size_t)(d.NB + 2 * d.EC) * d.EC;
     if (h->wt_bytes < per * nrad * 4) {
-        eq_free(h->wt_arena);
-        ADF_TRY(eq_alloc(&h->wt_arena, per * nrad));
+        h->wt_bytes = 0;
+        ADF_TRY(h->m_w.alloc(&h->wt_arena, per * nrad));
         h->wt_bytes = per * nrad * 4;
     }
     eq_radial* rads[EQ_MAX_LAYERS + 3];
@@ -610,13 +541,12 @@ extern "C" int32_t adf_eqv2_set_energy_head(adf_eqv2_t h, int32_t n_weights, con
         const size_t n = (size_t)l->out * l->in;
         if (h->eh_w16_bytes < n * 4 + 64) {
             ADF_HIP_CHECK(hipDeviceSynchronize());
-            eq_free(h->eh_w16);
             h->eh_w16_bytes = 0;
-            ADF_TRY(eq_alloc(&h->eh_w16, n * 4 + 64));
+            ADF_TRY(h->m_w.alloc(&h->eh_w16, n * 4 + 64));
             h->eh_w16_bytes = n * 4 + 64;
         }
-        if (!h->eh_scale) ADF_TRY(eq_alloc(&h->eh_scale, 1));
-        if (!h->w16_scratch) ADF_TRY(eq_alloc(&h->w16_scratch, 4));
+        if (!h->eh_scale) ADF_TRY(h->m_w.alloc(&h->eh_scale, 1));
+        if (!h->w16_scratch) ADF_TRY(h->m_w.alloc(&h->w16_scratch, 4));
         l->w16.hi = h->eh_w16; l->w16.lo = h->eh_w16 + n * 2; l->w16.inv_scale = h->eh_scale; l->w16.bias_perm = nullptr;
         l->w16.frag = nullptr;
         ADF_TRY(adf_split_weight(l->w, (long long)n, &l->w16, h->w16_scratch, s));
@@ -644,7 +574,7 @@ extern "C" int32_t adf_eqv2_set_energy_embedding(adf_eqv2_t h, const float* w, c
     h->ee_ready = false;
     if (!w) { h->ee_on = false; return ADF_OK; }
     const int C = h->d.C;
-    if (!h->ee_wb) ADF_TRY(eq_alloc(&h->ee_wb, 2 * (size_t)C));
+    if (!h->ee_wb) ADF_TRY(h->m_ee.alloc(&h->ee_wb, 2 * (size_t)C));
     hipStream_t s = (hipStream_t)stream;
     ADF_HIP_CHECK(hipMemcpyAsync(h->ee_wb, w, sizeof(float) * C, hipMemcpyDeviceToDevice, s));
     ADF_HIP_CHECK(hipMemcpyAsync(h->ee_wb + C, b, sizeof(float) * C, hipMemcpyDeviceToDevice, s));
@@ -660,9 +590,8 @@ extern "C" int32_t adf_eqv2_set_system_energy(adf_eqv2_t h, const float* energy,
     if (!energy) { h->ee_B = 0; return ADF_OK; }
     if (num_systems > h->ee_cap) {
         ADF_HIP_CHECK(hipDeviceSynchronize());
-        eq_free(h->ee_energy);
         h->ee_cap = 0;
-        ADF_TRY(eq_alloc(&h->ee_energy, (size_t)num_systems));
+        ADF_TRY(h->m_ee.alloc(&h->ee_energy, (size_t)num_systems));
         h->ee_cap = num_systems;
     }
     ADF_HIP_CHECK(hipMemcpyAsync(h->ee_energy, energy, sizeof(float) * num_systems, hipMemcpyDeviceToDevice, (hipStream_t)stream));
@@ -679,9 +608,8 @@ static int32_t eq_energy_term_ready(adf_eqv2* h, int B, hipStream_t s) {
     const int64_t rows = h->ee_B > 0 ? h->ee_B : 1;
     if (rows > h->ee_term_rows) {
         ADF_HIP_CHECK(hipDeviceSynchronize());
-        eq_free(h->ee_term);
         h->ee_term_rows = 0;
-        ADF_TRY(eq_alloc(&h->ee_term, (size_t)rows * h->d.C));
+        ADF_TRY(h->m_ee.alloc(&h->ee_term, (size_t)rows * h->d.C));
         h->ee_term_rows = rows;
     }
     ADF_TRY(eq_launch_energy_term(h->ee_wb, h->ee_B > 0 ? h->ee_energy : nullptr, (int)rows, h->d.C, h->ee_term, s));
@@ -709,26 +637,26 @@ static int32_t eq_ensure_capacity(adf_eqv2* h, int64_t N, int64_t B, int64_t Ene
         if (Eneed > cE) cE = Eneed;
         if (h->capE > cE) cE = h->capE;
         eq_free_workspaces(h);
-        ADF_TRY(eq_alloc(&h->nbr_cnt, (size_t)cN + 1));
+        ADF_TRY(h->m_ws.alloc(&h->nbr_cnt, (size_t)cN + 1));
         ADF_HIP_CHECK(hipMemset(h->nbr_cnt, 0, sizeof(int32_t) * ((size_t)cN + 1)));
-        ADF_TRY(eq_alloc(&h->nbr_src, (size_t)cN * K)); ADF_TRY(eq_alloc(&h->nbr_shift, (size_t)cN * K));
-        ADF_TRY(eq_alloc(&h->img_cnt, (size_t)cB)); ADF_TRY(eq_alloc(&h->eptr, (size_t)cN + 2));
-        ADF_TRY(eq_alloc(&h->e_src, (size_t)cE)); ADF_TRY(eq_alloc(&h->e_dst, (size_t)cE));
-        ADF_TRY(eq_alloc(&h->e_vec, (size_t)cE * 3)); ADF_TRY(eq_alloc(&h->wig, (size_t)cE * d.DR));
+        ADF_TRY(h->m_ws.alloc(&h->nbr_src, (size_t)cN * K)); ADF_TRY(h->m_ws.alloc(&h->nbr_shift, (size_t)cN * K));
+        ADF_TRY(h->m_ws.alloc(&h->img_cnt, (size_t)cB)); ADF_TRY(h->m_ws.alloc(&h->eptr, (size_t)cN + 2));
+        ADF_TRY(h->m_ws.alloc(&h->e_src, (size_t)cE)); ADF_TRY(h->m_ws.alloc(&h->e_dst, (size_t)cE));
+        ADF_TRY(h->m_ws.alloc(&h->e_vec, (size_t)cE * 3)); ADF_TRY(h->m_ws.alloc(&h->wig, (size_t)cE * d.DR));
         size_t bytes = 0;
         (void)hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, (int32_t*)nullptr, (int32_t*)nullptr, (int)(cN + 1));
         h->scan_tmp_bytes = bytes;
-        ADF_HIP_CHECK(hipMalloc(&h->scan_tmp, bytes ? bytes : 16));
-        ADF_TRY(eq_alloc(&h->cache_d2, (size_t)cN * K)); ADF_TRY(eq_alloc(&h->cache_cid, (size_t)cN * K));
-        ADF_TRY(eq_alloc(&h->cache_cnt, (size_t)cN));
+        ADF_TRY(h->m_ws.alloc(&h->scan_tmp, bytes));
+        ADF_TRY(h->m_ws.alloc(&h->cache_d2, (size_t)cN * K)); ADF_TRY(h->m_ws.alloc(&h->cache_cid, (size_t)cN * K));
+        ADF_TRY(h->m_ws.alloc(&h->cache_cnt, (size_t)cN));
         h->cache_valid = false;
         const size_t ns = (size_t)cN * d.S;
         const size_t wmax = (size_t)(d.C > d.F ? d.C : d.F);
-        ADF_TRY(eq_alloc(&h->x, ns * d.C)); ADF_TRY(eq_alloc(&h->y, ns * d.C));
-        ADF_TRY(eq_alloc(&h->agg, ns * (d.HV > (int)wmax ? d.HV : wmax)));
-        ADF_TRY(eq_alloc(&h->gate, (size_t)cN * d.F));
-        ADF_TRY(eq_alloc(&h->h1, ns * d.F)); ADF_TRY(eq_alloc(&h->h2, ns * d.F));
-        ADF_TRY(eq_alloc(&h->sys, (size_t)cB * 16));
+        ADF_TRY(h->m_ws.alloc(&h->x, ns * d.C)); ADF_TRY(h->m_ws.alloc(&h->y, ns * d.C));
+        ADF_TRY(h->m_ws.alloc(&h->agg, ns * (d.HV > (int)wmax ? d.HV : wmax)));
+        ADF_TRY(h->m_ws.alloc(&h->gate, (size_t)cN * d.F));
+        ADF_TRY(h->m_ws.alloc(&h->h1, ns * d.F)); ADF_TRY(h->m_ws.alloc(&h->h2, ns * d.F));
+        ADF_TRY(h->m_ws.alloc(&h->sys, (size_t)cB * 16));
         // chunk size: bounded edge-arena (ADF_EQV2_CHUNK_EDGES, default 2^19 edges)
         int64_t chunk_edges = 1 << 19;
         if (const char* e = getenv("ADF_EQV2_CHUNK_EDGES")) { const long long v = atoll(e); if (v > 0) chunk_edges = v; }
@@ -739,13 +667,13 @@ static int32_t eq_ensure_capacity(adf_eqv2* h, int64_t N, int64_t B, int64_t Ene
         if (cn > cN) cn = cN;
         h->chunk_nodes = cn;
         h->arena_floats = eq_arena_floats_per_edge(d) * (size_t)(cn * kk);
-        ADF_TRY(eq_alloc(&h->arena, h->arena_floats));
+        ADF_TRY(h->m_ws.alloc(&h->arena, h->arena_floats));
         h->garena_floats = 2 * (size_t)cn * d.G * d.F;
-        ADF_TRY(eq_alloc(&h->garena, h->garena_floats));
+        ADF_TRY(h->m_ws.alloc(&h->garena, h->garena_floats));
         int64_t rc = 2 * cn * kk;
         if (3 * cn * d.G > rc) rc = 3 * cn * d.G;
         if (cN * (2 * d.L + 1) > rc) rc = cN * (2 * d.L + 1);
-        ADF_TRY(eq_alloc(&h->rs, (size_t)rc));
+        ADF_TRY(h->m_ws.alloc(&h->rs, (size_t)rc));
         h->rs_cap = rc;
         h->capN = cN; h->capB = cB; h->capE = cE;
     }
@@ -762,9 +690,10 @@ extern "C" int32_t adf_eqv2_set_edges(adf_eqv2_t h, int64_t num_edges, const int
     // private copy; the forward moves it into the (possibly re-allocated) graph workspaces
     if (num_edges > h->xe_cap) {
         ADF_HIP_CHECK(hipDeviceSynchronize());
-        eq_free(h->xe_src); eq_free(h->xe_dst); eq_free(h->xe_vec);
-        ADF_TRY(eq_alloc(&h->xe_src, (size_t)num_edges)); ADF_TRY(eq_alloc(&h->xe_dst, (size_t)num_edges));
-        ADF_TRY(eq_alloc(&h->xe_vec, (size_t)num_edges * 3));
+        h->m_xe.release();
+        h->xe_cap = 0;
+        ADF_TRY(h->m_xe.alloc(&h->xe_src, (size_t)num_edges)); ADF_TRY(h->m_xe.alloc(&h->xe_dst, (size_t)num_edges));
+        ADF_TRY(h->m_xe.alloc(&h->xe_vec, (size_t)num_edges * 3));
         h->xe_cap = num_edges;
     }
     ADF_HIP_CHECK(hipMemcpyAsync(h->xe_src, src, sizeof(int32_t) * num_edges, hipMemcpyDeviceToDevice, s));
@@ -802,17 +731,17 @@ static bool eq_inc_ensure(adf_eqv2* h) {
     eq_inc_free(h);
     const size_t row = (size_t)d.S * d.C, cN = (size_t)h->capN;
     int32_t st = ADF_OK;
-    for (int i = 0; i <= nl && st == ADF_OK; ++i) st = eq_alloc(&h->inc_x[i], cN * row);
-    if (st == ADF_OK) st = eq_alloc(&h->inc_xg, cN * row);
-    if (st == ADF_OK) st = eq_alloc(&h->inc_peptr, cN + 2);
-    if (st == ADF_OK) st = eq_alloc(&h->inc_psrc, (size_t)h->capE);
-    if (st == ADF_OK) st = eq_alloc(&h->inc_pvec, (size_t)h->capE * 3);
-    if (st == ADF_OK) st = eq_alloc(&h->inc_dirty, 2 * cN);
-    if (st == ADF_OK) st = eq_alloc(&h->inc_idx, (size_t)nl * cN);
-    if (st == ADF_OK) st = eq_alloc(&h->inc_cnt, (size_t)nl + 1);
+    for (int i = 0; i <= nl && st == ADF_OK; ++i) st = h->m_inc.alloc(&h->inc_x[i], cN * row);
+    if (st == ADF_OK) st = h->m_inc.alloc(&h->inc_xg, cN * row);
+    if (st == ADF_OK) st = h->m_inc.alloc(&h->inc_peptr, cN + 2);
+    if (st == ADF_OK) st = h->m_inc.alloc(&h->inc_psrc, (size_t)h->capE);
+    if (st == ADF_OK) st = h->m_inc.alloc(&h->inc_pvec, (size_t)h->capE * 3);
+    if (st == ADF_OK) st = h->m_inc.alloc(&h->inc_dirty, 2 * cN);
+    if (st == ADF_OK) st = h->m_inc.alloc(&h->inc_idx, (size_t)nl * cN);
+    if (st == ADF_OK) st = h->m_inc.alloc(&h->inc_cnt, (size_t)nl + 1);
     if (st == ADF_OK) {
         h->inc_sel_bytes = eq_inc_select_bytes((int)cN);
-        if (hipMalloc(&h->inc_sel_tmp, h->inc_sel_bytes ? h->inc_sel_bytes : 16) != hipSuccess) st = ADF_EOOM;
+        st = h->m_inc.alloc(&h->inc_sel_tmp, h->inc_sel_bytes);
     }
     if (st != ADF_OK) {
         (void)hipGetLastError();
@@ -909,7 +838,7 @@ static void eq_carve(const adf_eqv2* h, long long Eub, eq_chunk_bufs* b) {
 static int32_t eq_radial(adf_eqv2* h, const eq_radial* r, const float* semb, const float* temb, const int32_t* Z, int n0,
                          int n1, long long Eub, eq_chunk_bufs* b, float* out, int N, hipStream_t s) {
     const eq_dims& d = h->d;
-    eq_prof_scope ps(h, EQ_PROF_RADIAL, s);
+    eq_prof_scope ps(h->prof, EQ_PROF_RADIAL, s);
     if (h->s2ef) {   // live distance basis: pair table + Gaussian window + LayerNorm + SiLU in one kernel
         ADF_TRY(eq_launch_radial_live(h, r, Z, n0, n1, b->radh, s));
     } else {
@@ -940,12 +869,12 @@ static int32_t eq_attention(adf_eqv2* h, const eq_attn* at, const float* y, cons
         bool pre = lifts && h->presplit && at->c1_m0.has16 && at->c1_m0.in % 32 == 0 && (at->c1_m0.out & 3) == 0;
         for (int m = 1; m <= d.M; ++m) pre = pre && at->c1_m[m - 1].has16 && at->c1_m[m - 1].in % 32 == 0 && (at->c1_m[m - 1].out & 3) == 0;
         {
-            eq_prof_scope ps(h, EQ_PROF_ROTATE, s);
+            eq_prof_scope ps(h->prof, EQ_PROF_ROTATE, s);
             ADF_TRY(eq_launch_rotate_in(h, y, tab ? at->rad.table : b.rad, Z, tab ? h->hp.max_num_elements : 0, n0, n1, b.m,
                                         lifts ? b.rsb : nullptr, pre, s));
         }
         {
-            eq_prof_scope ps(h, EQ_PROF_CONV, s);
+            eq_prof_scope ps(h->prof, EQ_PROF_CONV, s);
             if (pre) {
                 for (int m = 0; m <= d.M; ++m) {
                     const eq_lin* W = m == 0 ? &at->c1_m0 : &at->c1_m[m - 1];
@@ -966,14 +895,14 @@ static int32_t eq_attention(adf_eqv2* h, const eq_attn* at, const float* y, cons
                                     nullptr, 2 * Eub, 0, false, s, lifts ? b.rsb[m] : nullptr));
             }
         }
-        { eq_prof_scope ps(h, EQ_PROF_ATTN, s); ADF_TRY(eq_launch_alpha(h, at, b.y[0], at->c1_m0.out, n0, n1, b.alpha, s)); }
+        { eq_prof_scope ps(h->prof, EQ_PROF_ATTN, s); ADF_TRY(eq_launch_alpha(h, at, b.y[0], at->c1_m0.out, n0, n1, b.alpha, s)); }
         bool rs_ok = false;
-        { eq_prof_scope ps(h, EQ_PROF_S2ACT, s); ADF_TRY(eq_launch_s2act(h, b.y[0], b.y, extra, d.NH * d.A, n0, n1, b.mb, h->s2_emit_mag ? b.rsb : nullptr, &rs_ok, s)); }
+        { eq_prof_scope ps(h->prof, EQ_PROF_S2ACT, s); ADF_TRY(eq_launch_s2act(h, b.y[0], b.y, extra, d.NH * d.A, n0, n1, b.mb, h->s2_emit_mag ? b.rsb : nullptr, &rs_ok, s)); }
         // a force block reads only the l = 1 rows of the rotated-back message: its second convolution keeps only the
         // output columns that reach them (order 0: l = 1; order 1: real and imaginary part of l = 1; order 2: none)
         const bool compact = only_l1 && d.M >= 1 && d.L >= 1 && !h->no_compact;
         if (compact) {
-            eq_prof_scope ps(h, EQ_PROF_CONV, s);
+            eq_prof_scope ps(h->prof, EQ_PROF_CONV, s);
             const eq_lin w0 = eq_lin_rows(at->c2_m0, d.HV, d.HV);
             const eq_lin wr = eq_lin_rows(at->c2_m[0], 0, d.HV), wi = eq_lin_rows(at->c2_m[0], d.L * d.HV, d.HV);
             ADF_TRY(eq_gemm(h, b.mb[0], w0.in, nullptr, &w0, true, b.z[0], d.HV, nullptr, Eub, 0, false, s, rs_ok ? b.rsb[0] : nullptr));
@@ -983,14 +912,14 @@ static int32_t eq_attention(adf_eqv2* h, const eq_attn* at, const float* y, cons
             ADF_TRY(eq_gemm(h, b.mb[1], wr.in, nullptr, &wr, false, b.z[1], 2 * d.HV, nullptr, 2 * Eub, 0, false, s, rs1));
             ADF_TRY(eq_gemm(h, b.mb[1], wi.in, nullptr, &wi, false, b.z[1] + d.HV, 2 * d.HV, nullptr, 2 * Eub, 0, false, s, rs1));
         } else {
-            eq_prof_scope ps(h, EQ_PROF_CONV, s);
+            eq_prof_scope ps(h->prof, EQ_PROF_CONV, s);
             ADF_TRY(eq_gemm(h, b.mb[0], at->c2_m0.in, nullptr, &at->c2_m0, true, b.z[0], at->c2_m0.out, nullptr, Eub, 0, false, s,
                             rs_ok ? b.rsb[0] : nullptr));
             for (int m = 1; m <= d.M; ++m)
                 ADF_TRY(eq_gemm(h, b.mb[m], at->c2_m[m - 1].in, nullptr, &at->c2_m[m - 1], false, b.z[m], at->c2_m[m - 1].out,
                                 nullptr, 2 * Eub, 0, false, s, rs_ok ? b.rsb[m] : nullptr));
         }
-        { eq_prof_scope ps(h, EQ_PROF_ROTATE, s); ADF_TRY(eq_launch_rotate_out(h, b.z, b.alpha, n0, n1, agg, only_l1, s, compact)); }
+        { eq_prof_scope ps(h->prof, EQ_PROF_ROTATE, s); ADF_TRY(eq_launch_rotate_out(h, b.z, b.alpha, n0, n1, agg, only_l1, s, compact)); }
     }
     return ADF_OK;
 }
@@ -1022,14 +951,14 @@ static int32_t eq_check_batch(const adf_eqv2* h, const adf_batch* b) {
 static int32_t eq_ensure_subset(adf_eqv2* h, int64_t n_out) {
     if (n_out <= h->sub_cap) return ADF_OK;
     ADF_HIP_CHECK(hipDeviceSynchronize());
-    eq_free(h->sub_eptr); eq_free(h->sub_src); eq_free(h->sub_dst); eq_free(h->sub_vec); eq_free(h->sub_wig); eq_free(h->sub_f);
+    h->m_sub.release();
     h->sub_cap = 0;
     const int64_t cap = n_out + n_out / 4 + 64;
     const int64_t kk = h->arena_kk > 0 ? h->arena_kk : h->hp.max_neighbors;
-    ADF_TRY(eq_alloc(&h->sub_eptr, (size_t)2 * (cap + 2)));  // CSR, then the counts it is scanned from
-    ADF_TRY(eq_alloc(&h->sub_src, (size_t)cap * kk)); ADF_TRY(eq_alloc(&h->sub_dst, (size_t)cap * kk));
-    ADF_TRY(eq_alloc(&h->sub_vec, (size_t)cap * kk * 3)); ADF_TRY(eq_alloc(&h->sub_wig, (size_t)cap * kk * h->d.DR));
-    ADF_TRY(eq_alloc(&h->sub_f, (size_t)cap * 3));
+    ADF_TRY(h->m_sub.alloc(&h->sub_eptr, (size_t)2 * (cap + 2)));  // CSR, then the counts it is scanned from
+    ADF_TRY(h->m_sub.alloc(&h->sub_src, (size_t)cap * kk)); ADF_TRY(h->m_sub.alloc(&h->sub_dst, (size_t)cap * kk));
+    ADF_TRY(h->m_sub.alloc(&h->sub_vec, (size_t)cap * kk * 3)); ADF_TRY(h->m_sub.alloc(&h->sub_wig, (size_t)cap * kk * h->d.DR));
+    ADF_TRY(h->m_sub.alloc(&h->sub_f, (size_t)cap * 3));
     h->sub_cap = cap;
     return ADF_OK;
 }
@@ -1049,9 +978,9 @@ static void eq_graph_restore(adf_eqv2* h, const eq_graph_view& v) {
 // X += proj(agg); X += ffn(norm_2(X))   (transformer_block.py:650-700, 375-531)
 static int32_t eq_block_nodes(adf_eqv2* h, const eq_block& bk, float* X, int n, hipStream_t s) {
     const eq_dims& d = h->d;
-    { eq_prof_scope ps(h, EQ_PROF_NODE, s); ADF_TRY(eq_so3_linear(h, bk.ga.proj_l, h->agg, d.HV, X, d.C, n, true, s)); }
-    { eq_prof_scope ps(h, EQ_PROF_NODE, s); ADF_TRY(eq_launch_norm(h, &bk.n2, X, h->y, n, s)); }
-    eq_prof_scope ps(h, EQ_PROF_FFN, s);
+    { eq_prof_scope ps(h->prof, EQ_PROF_NODE, s); ADF_TRY(eq_so3_linear(h, bk.ga.proj_l, h->agg, d.HV, X, d.C, n, true, s)); }
+    { eq_prof_scope ps(h->prof, EQ_PROF_NODE, s); ADF_TRY(eq_launch_norm(h, &bk.n2, X, h->y, n, s)); }
+    eq_prof_scope ps(h->prof, EQ_PROF_FFN, s);
     const eq_ffn& f = bk.ffn;
     // scalar gate from the l = 0 row of every node (row stride S*C)
     ADF_TRY(eq_gemm(h, h->y, d.S * d.C, nullptr, &f.scalar, true, h->gate, d.F, nullptr, n, 2, false, s));
@@ -1099,7 +1028,7 @@ static int32_t eq_forward_impl(adf_eqv2* h, const adf_batch* b, float* f1, float
     ADF_TRY(eq_ensure_capacity(h, N, B, h->ext_graph ? h->E_ext : 0));
     const int32_t* Z = b->atomic_numbers;
     {
-        eq_prof_scope ps(h, EQ_PROF_GRAPH, s);
+        eq_prof_scope ps(h->prof, EQ_PROF_GRAPH, s);
         if (h->ext_graph) {
             ADF_HIP_CHECK(hipMemcpyAsync(h->e_src, h->xe_src, sizeof(int32_t) * h->E_ext, hipMemcpyDeviceToDevice, s));
             ADF_HIP_CHECK(hipMemcpyAsync(h->e_dst, h->xe_dst, sizeof(int32_t) * h->E_ext, hipMemcpyDeviceToDevice, s));
@@ -1120,7 +1049,7 @@ static int32_t eq_forward_impl(adf_eqv2* h, const adf_batch* b, float* f1, float
     bool lists = false;
     int32_t cnt[EQ_MAX_LAYERS];
     if (inc) {
-        eq_prof_scope ps(h, EQ_PROF_GRAPH, s);
+        eq_prof_scope ps(h->prof, EQ_PROF_GRAPH, s);
         if (h->inc_valid && h->inc_N == N) {
             ADF_TRY(eq_launch_inc_lists(h, N, nl, s));
             // the list lengths size the launches of this forward: one read-back (the forward is ~10^5 times longer)
@@ -1142,7 +1071,7 @@ static int32_t eq_forward_impl(adf_eqv2* h, const adf_batch* b, float* f1, float
         eq_carve(h, Eub, &cb);
         const bool tab = h->rad_static && h->ed_rad.table;
         if (!tab) ADF_TRY(eq_radial(h, &h->ed_rad, h->ed_src_emb, h->ed_dst_emb, Z, n0, n1, Eub, &cb, cb.rad, N, s));
-        eq_prof_scope ps(h, EQ_PROF_ROTATE, s);
+        eq_prof_scope ps(h->prof, EQ_PROF_ROTATE, s);
         ADF_TRY(eq_launch_edge_degree(h, tab ? h->ed_rad.table : cb.rad, Z, tab ? h->hp.max_num_elements : 0, n0, n1, X, s,
                                       h->ee_on ? h->ee_term : nullptr, b->batch, h->ee_B > 0 ? d.C : 0, B));
     }
@@ -1163,21 +1092,21 @@ static int32_t eq_forward_impl(adf_eqv2* h, const adf_batch* b, float* f1, float
             if (listed && n > 0) {
                 const int32_t* idx = h->inc_idx + (size_t)i * h->inc_capN;
                 // x = x + ga(norm_1(x)) + ffn(norm_2(.)) on the listed rows: sources are read from every row of the block below
-                { eq_prof_scope ps(h, EQ_PROF_NODE, s); ADF_TRY(eq_launch_norm(h, &bk.n1, X, h->y, N, s)); }
-                { eq_prof_scope ps(h, EQ_PROF_GRAPH, s); ADF_TRY(eq_launch_subset_graph(h, idx, n, s)); }
+                { eq_prof_scope ps(h->prof, EQ_PROF_NODE, s); ADF_TRY(eq_launch_norm(h, &bk.n1, X, h->y, N, s)); }
+                { eq_prof_scope ps(h->prof, EQ_PROF_GRAPH, s); ADF_TRY(eq_launch_subset_graph(h, idx, n, s)); }
                 const eq_graph_view full = eq_graph_use_subset(h);
                 int32_t st = eq_attention(h, &bk.ga, h->y, Z, n, h->agg, false, s);
                 eq_graph_restore(h, full);
                 ADF_TRY(st);
-                { eq_prof_scope ps(h, EQ_PROF_NODE, s); ADF_TRY(eq_launch_gather_rows(X, idx, n, d.S * d.C, h->inc_xg, s)); }
+                { eq_prof_scope ps(h->prof, EQ_PROF_NODE, s); ADF_TRY(eq_launch_gather_rows(X, idx, n, d.S * d.C, h->inc_xg, s)); }
                 ADF_TRY(eq_block_nodes(h, bk, h->inc_xg, n, s));
-                { eq_prof_scope ps(h, EQ_PROF_NODE, s); ADF_TRY(eq_launch_scatter_rows(h->inc_xg, idx, n, d.S * d.C, Xout, s)); }
+                { eq_prof_scope ps(h->prof, EQ_PROF_NODE, s); ADF_TRY(eq_launch_scatter_rows(h->inc_xg, idx, n, d.S * d.C, Xout, s)); }
             }
             X = Xout;
         }
         if (!listed) {
             // x = x + ga(norm_1(x))   (transformer_block.py:650-700; drop path / dropout are identity in eval mode)
-            { eq_prof_scope ps(h, EQ_PROF_NODE, s); ADF_TRY(eq_launch_norm(h, &bk.n1, X, h->y, N, s)); }
+            { eq_prof_scope ps(h->prof, EQ_PROF_NODE, s); ADF_TRY(eq_launch_norm(h, &bk.n1, X, h->y, N, s)); }
             ADF_TRY(eq_attention(h, &bk.ga, h->y, Z, N, h->agg, false, s));
             ADF_TRY(eq_block_nodes(h, bk, X, N, s));
         }
@@ -1189,9 +1118,9 @@ static int32_t eq_forward_impl(adf_eqv2* h, const adf_batch* b, float* f1, float
         h->inc_valid = true; h->inc_N = N;
         h->inc_rows += h->last_block_rows; h->inc_rows_full += (int64_t)nl * N;
     }
-    { eq_prof_scope ps(h, EQ_PROF_NODE, s); ADF_TRY(eq_launch_norm(h, &h->final_norm, X, h->y, N, s)); }
+    { eq_prof_scope ps(h->prof, EQ_PROF_NODE, s); ADF_TRY(eq_launch_norm(h, &h->final_norm, X, h->y, N, s)); }
     if (energy) {   // hid = SiLU(scalar_mlp.0(l = 0 row)) (row stride S C), then the per-system sums (eq_energy_sum_kernel)
-        eq_prof_scope ps(h, EQ_PROF_NODE, s);
+        eq_prof_scope ps(h->prof, EQ_PROF_NODE, s);
         ADF_TRY(eq_gemm(h, h->y, d.S * d.C, nullptr, &h->eh_scalar, true, h->gate, d.F, nullptr, N, 2, false, s));
         ADF_TRY(eq_launch_energy_sum(h, h->gate, b, energy, s));
     }
@@ -1201,7 +1130,7 @@ static int32_t eq_forward_impl(adf_eqv2* h, const adf_batch* b, float* f1, float
         if (n_out <= 0) return ADF_OK;
         if (n_out > N) { adf_set_error("eqv2_forward_subset: more indices than atoms"); return ADF_EINVAL; }
         ADF_TRY(eq_ensure_subset(h, n_out));
-        { eq_prof_scope ps(h, EQ_PROF_GRAPH, s); ADF_TRY(eq_launch_subset_graph(h, out_idx, n_out, s)); }
+        { eq_prof_scope ps(h->prof, EQ_PROF_GRAPH, s); ADF_TRY(eq_launch_subset_graph(h, out_idx, n_out, s)); }
         // the attention kernels read the graph through the handle: point it at the compact arrays for the force blocks
         const eq_graph_view full = eq_graph_use_subset(h);
         int32_t st = ADF_OK;
@@ -1209,7 +1138,7 @@ static int32_t eq_forward_impl(adf_eqv2* h, const adf_batch* b, float* f1, float
             float* f = k == 0 ? f1 : f2;
             if (!f) continue;
             st = eq_attention(h, &h->force[k], h->y, Z, n_out, h->agg, true, s);
-            eq_prof_scope ps(h, EQ_PROF_NODE, s);
+            eq_prof_scope ps(h->prof, EQ_PROF_NODE, s);
             if (st == ADF_OK) st = eq_launch_force_out(h, &h->force[k], h->agg, n_out, h->sub_f, s);
             if (st == ADF_OK) st = eq_launch_scatter_rows3(h->sub_f, out_idx, n_out, f, s);
         }
@@ -1220,7 +1149,7 @@ static int32_t eq_forward_impl(adf_eqv2* h, const adf_batch* b, float* f1, float
         float* f = k == 0 ? f1 : f2;
         if (!f) continue;
         ADF_TRY(eq_attention(h, &h->force[k], h->y, Z, N, h->agg, true, s));
-        eq_prof_scope ps(h, EQ_PROF_NODE, s);
+        eq_prof_scope ps(h->prof, EQ_PROF_NODE, s);
         ADF_TRY(eq_launch_force_out(h, &h->force[k], h->agg, N, f, s));
     }
     return ADF_OK;
@@ -1282,8 +1211,8 @@ static int32_t eq_model_forward(void* h, const adf_batch* b, const int32_t* out_
     return eq_forward_impl((adf_eqv2*)h, b, f1, f2, nullptr, s, out_idx, n_out);
 }
 static void eq_model_prof(void* h, bool begin, hipStream_t s) {
-    if (begin) eq_prof_begin((adf_eqv2*)h, EQ_PROF_STEPPER, s);
-    else eq_prof_end((adf_eqv2*)h, s);
+    if (begin) ((adf_eqv2*)h)->prof.begin(EQ_PROF_STEPPER, s);
+    else ((adf_eqv2*)h)->prof.end(s);
 }
 static adf_model eq_model(adf_eqv2_t h) { return {h, eq_model_check, eq_model_grow, eq_model_forward, eq_model_prof}; }
 
@@ -1357,10 +1286,11 @@ extern "C" int32_t adf_eqv2_linear_forward(const float* A, const float* W, const
     if (mode == 0) return eq_gemm_f32(A, K, nullptr, W, bias, Cm, N, nullptr, M, N, K, act, false, s);
     const eq_rowmap am = {K, 1, 0}, cm = {N, 1, 0};
     if (!eq_gemm16_ok(A, &am, Cm, &cm, N, K)) { adf_set_error("shape not taken by the f16x3 kernels"); return ADF_EINVAL; }
+    adf_pool tmp;   // frees buf on every return
     unsigned char* buf = nullptr;
     const size_t n = (size_t)N * K, ma = (size_t)M * K;
     if (mode == 3 && (N % 32 || K % 64 || N < 128)) { adf_set_error("mode 3 needs N %% 32 == 0, N >= 128 and K %% 64 == 0"); return ADF_EINVAL; }
-    ADF_TRY(eq_alloc(&buf, n * 4 + 64 + (size_t)M * 4 + 64 + (mode >= 2 ? ma * 4 : 0) + 64 + (mode == 3 ? n * 4 : 0)));
+    ADF_TRY(tmp.alloc(&buf, n * 4 + 64 + (size_t)M * 4 + 64 + (mode >= 2 ? ma * 4 : 0) + 64 + (mode == 3 ? n * 4 : 0)));
     adf_w16 w16 = {};
     w16.hi = buf; w16.lo = buf + n * 2; w16.inv_scale = reinterpret_cast<float*>(buf + n * 4); w16.bias_perm = nullptr;
     unsigned int* scratch = reinterpret_cast<unsigned int*>(buf + n * 4 + 16);
@@ -1379,7 +1309,6 @@ extern "C" int32_t adf_eqv2_linear_forward(const float* A, const float* W, const
         else st = eq_launch_gemm16(A, &am, mag, &w16, bias, Cm, &cm, M, N, K, act, false, s, adf_tune_process(), nullptr);
     }
     (void)hipStreamSynchronize(s);
-    eq_free(buf);
     return st;
 }
 
@@ -1394,15 +1323,15 @@ extern "C" int32_t adf_eqv2_radial_first_layer(adf_eqv2_t h, int32_t which, int6
     if (which < 0 || which > nl + 1 || num_edges > 0x7fffffff) { adf_set_error("eqv2_radial_first_layer: no such radial function"); return ADF_EINVAL; }
     const struct eq_radial* r = which == 0 ? &h->ed_rad : (which <= nl ? &h->blk[which - 1].ga.rad : &h->force[0].rad);
     hipStream_t s = (hipStream_t)stream;
+    adf_pool tmp;   // frees ep on every return
     int32_t* ep = nullptr;
-    ADF_TRY(eq_alloc(&ep, 2));
+    ADF_TRY(tmp.alloc(&ep, 2));
     const int32_t hp2[2] = {0, (int32_t)num_edges};
     int32_t st = ADF_OK;
     if (hipMemcpyAsync(ep, hp2, sizeof(hp2), hipMemcpyHostToDevice, s) != hipSuccess) st = ADF_EHIP;
     if (st == ADF_OK) st = eq_launch_radial_live_raw(vec, src, dst, ep, Z, r, 0, 1, num_edges, h->d.EC, h->d.NB,
                                                      h->hp.max_num_elements, h->hp.max_radius, out, h->flags, s);
     (void)hipStreamSynchronize(s);
-    eq_free(ep);
     return st;
 }
 
@@ -1449,9 +1378,7 @@ extern "C" int32_t adf_eqv2_get_counters(adf_eqv2_t h, adf_eqv2_counters* out, v
 
 extern "C" int32_t adf_eqv2_profile_enable(adf_eqv2_t h, int32_t on) {
     if (!h) { adf_set_error("null handle"); return ADF_EINVAL; }
-    h->prof_on = on != 0;
-    h->prof_used = 0;
-    h->prof_cat->clear();
+    h->prof.enable(on != 0);
     if (on) h->prof_block_rows = h->prof_forwards = 0;
     return ADF_OK;
 }
@@ -1459,15 +1386,5 @@ extern "C" int32_t adf_eqv2_profile_enable(adf_eqv2_t h, int32_t on) {
 extern "C" int32_t adf_eqv2_profile_read(adf_eqv2_t h, float* ms, int64_t* count, void* stream) {
     if (!h || !ms || !count) { adf_set_error("null argument"); return ADF_EINVAL; }
     ADF_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
-    for (int i = 0; i < EQ_PROF_NCAT; ++i) { ms[i] = 0.f; count[i] = 0; }
-    for (size_t i = 0; i + 1 < h->prof_used; i += 2) {
-        float t = 0.f;
-        if (hipEventElapsedTime(&t, (*h->prof_ev)[i], (*h->prof_ev)[i + 1]) == hipSuccess) {
-            const int c = (*h->prof_cat)[i / 2];
-            ms[c] += t; count[c] += 1;
-        }
-    }
-    h->prof_used = 0;
-    h->prof_cat->clear();
-    return ADF_OK;
+    return h->prof.read(ms, count, EQ_PROF_NCAT);
 }

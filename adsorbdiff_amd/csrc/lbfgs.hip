@@ -36,25 +36,10 @@ struct adf_lbfgs {
     double* sys_absmax;  // [B] max |dr| of the system
     int32_t* mask;       // [B] update mask of the last adf_lbfgs_converge
     int64_t total;       // entries appended since create / reset
+    adf_pool mem;        // owns every device buffer above
 };
 
-static int32_t lb_alloc(void** p, size_t bytes) {
-    hipError_t e = hipMalloc(p, bytes);
-    if (e != hipSuccess) {
-        *p = nullptr;
-        (void)hipGetLastError();
-        adf_set_error("hipMalloc of %zu bytes failed: %s", bytes, hipGetErrorString(e));
-        return ADF_EOOM;
-    }
-    return ADF_OK;
-}
-
 extern "C" int32_t adf_lbfgs_destroy(adf_lbfgs_t h) {
-    if (!h) return ADF_OK;
-    void* ptrs[] = {h->s, h->y, h->rho, h->alpha, h->r0, h->f0, h->q, h->dr, h->part_a, h->part_b, h->part_rho,
-                    h->sys_absmax, h->mask};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
     delete h;
     return ADF_OK;
 }
@@ -73,7 +58,6 @@ extern "C" int32_t adf_lbfgs_create(int64_t num_atoms, int32_t num_systems, int3
     }
     adf_lbfgs* h = new (std::nothrow) adf_lbfgs();
     if (!h) { adf_set_error("host allocation failed"); return ADF_EOOM; }
-    memset(h, 0, sizeof(*h));
     h->N = num_atoms; h->n = 3 * num_atoms; h->B = num_systems; h->M = memory;
     h->maxstep = maxstep; h->damping = damping; h->H0 = 1.0 / alpha; h->early_stop_batch = early_stop_batch != 0;
     // about 4 entries per thread, at most LB_MAX_G workgroups
@@ -82,20 +66,20 @@ extern "C" int32_t adf_lbfgs_create(int64_t num_atoms, int32_t num_systems, int3
     h->chunk = (h->n + h->G - 1) / h->G;
     const size_t n = (size_t)h->n, M = (size_t)memory;
     int32_t st = ADF_OK;
-#define LB_ALLOC(field, bytes) if (st == ADF_OK) st = lb_alloc(reinterpret_cast<void**>(&h->field), (bytes))
-    LB_ALLOC(s, M * n * sizeof(double));
-    LB_ALLOC(y, M * n * sizeof(double));
-    LB_ALLOC(rho, M * sizeof(double));
-    LB_ALLOC(alpha, M * sizeof(double));
-    LB_ALLOC(r0, n * sizeof(double));
-    LB_ALLOC(f0, n * sizeof(double));
-    LB_ALLOC(q, n * sizeof(double));
-    LB_ALLOC(dr, n * sizeof(double));
-    LB_ALLOC(part_a, LB_MAX_G * sizeof(double));
-    LB_ALLOC(part_b, LB_MAX_G * sizeof(double));
-    LB_ALLOC(part_rho, LB_MAX_G * sizeof(double));
-    LB_ALLOC(sys_absmax, (size_t)num_systems * sizeof(double));
-    LB_ALLOC(mask, (size_t)num_systems * sizeof(int32_t));
+#define LB_ALLOC(field, count) if (st == ADF_OK) st = h->mem.alloc(&h->field, (count))
+    LB_ALLOC(s, M * n);
+    LB_ALLOC(y, M * n);
+    LB_ALLOC(rho, M);
+    LB_ALLOC(alpha, M);
+    LB_ALLOC(r0, n);
+    LB_ALLOC(f0, n);
+    LB_ALLOC(q, n);
+    LB_ALLOC(dr, n);
+    LB_ALLOC(part_a, LB_MAX_G);
+    LB_ALLOC(part_b, LB_MAX_G);
+    LB_ALLOC(part_rho, LB_MAX_G);
+    LB_ALLOC(sys_absmax, (size_t)num_systems);
+    LB_ALLOC(mask, (size_t)num_systems);
 #undef LB_ALLOC
     if (st == ADF_OK && hipMemset(h->r0, 0, n * sizeof(double)) != hipSuccess) st = ADF_EHIP;
     if (st == ADF_OK && hipMemset(h->f0, 0, n * sizeof(double)) != hipSuccess) st = ADF_EHIP;

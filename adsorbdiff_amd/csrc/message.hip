@@ -703,7 +703,7 @@ int32_t adf_message_impl(adf_painn* h, int layer, int N, const float* x, const f
     p.env_a = (float)(-(pe + 1) * (pe + 2) / 2);
     p.env_b = (float)(pe * (pe + 2));
     p.env_c = (float)(-pe * (pe + 1) / 2);
-    p.kcount = h->prof_on ? h->kcount : nullptr;
+    p.kcount = h->prof.on ? h->kcount : nullptr;
     p.xpart = xpart; p.vpart = xpart ? vpart : nullptr; p.part_stride = part_stride;
     int workers = h->num_cus / p.nslices;
     if (workers < 1) workers = 1;

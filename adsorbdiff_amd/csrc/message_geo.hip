@@ -378,7 +378,7 @@ int32_t adf_message_geo(adf_painn* h, int layer, const float* xh, const float* v
         p.dmu2 = (float)(2.0 * d); p.dmusq = (float)(d * d); p.cstep = (float)exp2(-2.0 * d * d);
     }
     pg.dcoef = (float)(2.0 * 0.69314718055994531 * sarg);
-    p.kcount = h->prof_on ? h->kcount : nullptr;
+    p.kcount = h->prof.on ? h->kcount : nullptr;
     pg.xh = xh; pg.vec = vec; pg.part = part; pg.ecap = ecap; pg.accumulate = accumulate ? 1 : 0;
     int workers = h->num_cus / p.nslices;
     if (workers < 1) workers = 1;
