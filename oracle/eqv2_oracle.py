@@ -65,9 +65,9 @@ def order_major_perm(L: int, M: int) -> torch.Tensor:
     return torch.tensor(out)
 
 
-def truncation_rescale(L: int, M: int) -> torch.Tensor:
+def truncation_rescale(L: int, M: int, dtype=torch.float32) -> torch.Tensor:
     """sqrt((2l+1)/(2M+1)) for the reduced coefficients of degree l > M, 1 otherwise (so3.py:160-186, 572-613)."""
-    return torch.tensor([math.sqrt((2 * l + 1) / (2 * M + 1)) if l > M else 1.0 for l, _ in lm_list(L, M)])
+    return torch.tensor([math.sqrt((2 * l + 1) / (2 * M + 1)) if l > M else 1.0 for l, _ in lm_list(L, M)], dtype=dtype)
 
 
 # --------------------------------------------------------------------------------------------------- geometry
@@ -87,7 +87,8 @@ _SAMPLES: Dict[int, Tuple[torch.Tensor, torch.Tensor]] = {}
 
 
 def wigner_from_rotation(L: int, R: torch.Tensor) -> torch.Tensor:
-    """Block-diagonal [E, S, S] with D_l(R): Y_l(R x) = D_l(R) Y_l(x), solved on a fixed generic point set in fp64."""
+    """Block-diagonal [E, S, S] with D_l(R): Y_l(R x) = D_l(R) Y_l(x), solved on a fixed generic point set in fp64 and
+    returned in R's dtype (a float64 R keeps the solve as it is)."""
     if L not in _SAMPLES:
         g = torch.Generator().manual_seed(1234)
         pts = torch.randn(4 * (L + 1) ** 2, 3, generator=g, dtype=torch.float64)
@@ -102,7 +103,7 @@ def wigner_from_rotation(L: int, R: torch.Tensor) -> torch.Tensor:
     mask = torch.zeros(S, S, dtype=torch.bool)
     for l in range(L + 1):
         mask[l * l:(l + 1) ** 2, l * l:(l + 1) ** 2] = True
-    return (D * mask).float()
+    return (D * mask).to(R.dtype)
 
 
 # --------------------------------------------------------------------------------------------------- small layers
@@ -133,7 +134,7 @@ def norm_sh(sd, pre: str, x: torch.Tensor, L: int, eps: float = 1e-5) -> torch.T
     if L == 0:
         return out0
     deg = torch.tensor([l for l, _ in lm_list(L, L)][1:])
-    w = (1.0 / (2.0 * deg + 1.0) / L).to(x.dtype)                       # every degree weighs the same
+    w = 1.0 / (2.0 * deg.to(x.dtype) + 1.0) / L                         # every degree weighs the same
     ms = torch.einsum("nsc,s->nc", x[:, 1:] ** 2, w).mean(dim=1)         # [N]
     scale = (ms + eps).pow(-0.5)[:, None, None] * sd[pre + "affine_weight"][deg - 1][None]
     return torch.cat([out0, x[:, 1:] * scale], dim=1)
@@ -143,13 +144,19 @@ class Grids:
     """to-grid / from-grid matrices [beta, alpha, coefficient] of the stand-in S2 grid with the reference's
     m-truncation rescale (so3.py:566-613)."""
 
-    def __init__(self, L: int, M: int, res: int) -> None:
-        to, fr = E3.ToS2Grid(L, (res, res), normalization="component"), E3.FromS2Grid((res, res), L, normalization="component")
+    def __init__(self, L: int, M: int, res: int, dtype=torch.float32) -> None:
+        prev = torch.get_default_dtype()
+        torch.set_default_dtype(dtype)   # the stand-in builds its tables in the default dtype
+        try:
+            to, fr = (E3.ToS2Grid(L, (res, res), normalization="component"),
+                      E3.FromS2Grid((res, res), L, normalization="component"))
+        finally:
+            torch.set_default_dtype(prev)
         full_to = torch.einsum("mbi,am->bai", to.shb, to.sha)
         full_fr = torch.einsum("am,mbi->bai", fr.sha, fr.shb)
         self.to_full, self.from_full = full_to, full_fr
         deg = torch.tensor([l for l, _ in lm_list(L, L)])
-        scale = torch.where(deg > M, torch.sqrt((2.0 * deg + 1.0) / (2 * M + 1)), torch.ones_like(deg, dtype=torch.float32))
+        scale = torch.where(deg > M, torch.sqrt((2.0 * deg.to(dtype) + 1.0) / (2 * M + 1)), torch.ones_like(deg, dtype=dtype))
         rm = reduced_mask(L, M)
         self.to_red = (full_to * scale)[:, :, rm] if M != L else full_to
         self.from_red = (full_fr * scale)[:, :, rm] if M != L else full_fr
@@ -225,7 +232,7 @@ def attention_block(sd, pre, x, Z, basis, src, dst, D, hp, grids: Grids, out_cha
     a = torch.einsum("ehk,hk->eh", smooth_leaky_relu(a), sd[pre + "alpha_dot"])
     a = segment_softmax(a, dst, N)
     msg = (msg.reshape(msg.shape[0], -1, H, V) * a[:, None, :, None]).reshape(msg.shape[0], -1, H * V)
-    back = D.transpose(1, 2)[:, :, rm] * truncation_rescale(L, M)[None, None, :]
+    back = D.transpose(1, 2)[:, :, rm] * truncation_rescale(L, M, D.dtype)[None, None, :]
     msg = torch.bmm(back, msg)                                        # [E, S, H V]
     agg = torch.zeros(N, msg.shape[1], msg.shape[2], dtype=msg.dtype).index_add_(0, dst, msg)
     return so3_linear(sd, pre + "proj.", agg, L)
@@ -245,36 +252,45 @@ def feed_forward(sd, pre, x, hp, grids: Grids) -> torch.Tensor:
 
 
 def eqv2_forward(sd: Dict[str, torch.Tensor], hp: dict, pos, atomic_numbers, cell, natoms,
-                 atom_radii: Optional[torch.Tensor] = None, graph: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+                 atom_radii: Optional[torch.Tensor] = None, graph: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+                 dtype: torch.dtype = torch.float32, return_blocks: bool = False):
     """(f1 [N,3], f2 [N,3]) of EquiformerV2S_OC20_DenoisingPos.forward with FOR_denoising (equiformer_v2_denoising.py:
     184-318).  hp: lmax, mmax, num_layers, sphere_channels, attn_hidden_channels, num_heads, attn_alpha_channels,
     attn_value_channels, ffn_hidden_channels, grid_resolution, max_radius, max_neighbors.  atom_radii: [101] in the
     reference's units (pm); None = the basis is taken as exactly zero, which is what any finite tabulated radius gives.
     graph = (edge_index [2,E] (source, target), edge_vec [E,3]): use this edge list instead of building one — in small
     cells the +a / -a images of an atom tie exactly at the K-th place and the reference's pick is implementation-defined
-    (exact ties), so fixtures carry the reference's list."""
+    (exact ties), so fixtures carry the reference's list.
+    dtype = torch.float64: the same forward in double precision (weights, radii, positions / edge vectors cast once here;
+    the edge list itself is chosen on the inputs as given), the reference the GPU tests measure float32 evaluations
+    against.  return_blocks: also x_blocks [num_layers + 1, N, S, C], the node embedding after the edge-degree embedding
+    and after every block."""
     L, M, C = hp["lmax"], hp["mmax"], hp["sphere_channels"]
     Z = atomic_numbers.long()
     N = Z.shape[0]
+    if dtype != torch.float32:
+        sd = {k: (t.to(dtype) if t.is_floating_point() else t) for k, t in sd.items()}
+        atom_radii = None if atom_radii is None else atom_radii.to(dtype)
     if graph is None:
         ei, sh, nb = radius_graph_pbc(pos, cell, natoms, hp["max_radius"], hp["max_neighbors"])
-        ei, d, v, _ = pbc_distances(pos, ei, cell, sh, nb)
+        ei, d, v, _ = pbc_distances(pos if dtype == torch.float32 else pos.to(dtype), ei, cell, sh, nb)
     else:
         ei, v = graph
+        v = v if dtype == torch.float32 else v.to(dtype)
         d = v.norm(dim=1)
     src, dst = ei[0], ei[1]
     nbasis = 600
     if atom_radii is None:
-        basis = torch.zeros(d.shape[0], nbasis)
+        basis = torch.zeros(d.shape[0], nbasis, dtype=dtype)
     else:
-        offs = torch.linspace(0.0, hp["max_radius"], nbasis)
+        offs = torch.linspace(0.0, hp["max_radius"], nbasis, dtype=dtype)
         coeff = -0.5 / (2.0 * (offs[1] - offs[0]).item()) ** 2
         dd = d - atom_radii[Z[src]] - atom_radii[Z[dst]]
         basis = torch.exp(coeff * (dd[:, None] - offs[None, :]) ** 2)
     D = wigner_from_rotation(L, edge_frames(v))
-    g_red, S = Grids(L, M, hp["grid_resolution"]), (L + 1) ** 2
+    g_red, S = Grids(L, M, hp["grid_resolution"], dtype), (L + 1) ** 2
     # node embedding: element embedding on l = 0 + edge-degree embedding (input_block.py:84-138)
-    x = torch.zeros(N, S, C)
+    x = torch.zeros(N, S, C, dtype=dtype)
     x[:, 0] = sd["sphere_embedding.weight"][Z]
     pre = "edge_degree_embedding."
     scal = torch.cat([basis, sd[pre + "source_embedding.weight"][Z[src]], sd[pre + "target_embedding.weight"][Z[dst]]], dim=1)
@@ -282,13 +298,15 @@ def eqv2_forward(sd: Dict[str, torch.Tensor], hp: dict, pos, atomic_numbers, cel
     red = lm_list(L, M)
     cols = torch.tensor([red.index((l, 0)) for l in range(L + 1)])
     rm = reduced_mask(L, M)
-    back = (D.transpose(1, 2)[:, :, rm] * truncation_rescale(L, M)[None, None, :])[:, :, cols]   # [E, S, L+1]
-    x = x + torch.zeros(N, S, C).index_add_(0, dst, torch.bmm(back, m0)) / AVG_DEGREE
+    back = (D.transpose(1, 2)[:, :, rm] * truncation_rescale(L, M, dtype)[None, None, :])[:, :, cols]   # [E, S, L+1]
+    x = x + torch.zeros(N, S, C, dtype=dtype).index_add_(0, dst, torch.bmm(back, m0)) / AVG_DEGREE
+    blocks = [x]
     for i in range(hp["num_layers"]):
         p = f"blocks.{i}."
         x = x + attention_block(sd, p + "ga.", norm_sh(sd, p + "norm_1.", x, L), Z, basis, src, dst, D, hp, g_red, C)
         x = x + feed_forward(sd, p + "ffn.", norm_sh(sd, p + "norm_2.", x, L), hp, g_red)
+        blocks.append(x)
     x = norm_sh(sd, "norm.", x, L)
     f1 = attention_block(sd, "force_block.", x, Z, basis, src, dst, D, hp, g_red, 1)[:, 1:4, 0]
     f2 = attention_block(sd, "force_block2.", x, Z, basis, src, dst, D, hp, g_red, 1)[:, 1:4, 0]
-    return f1, f2
+    return (f1, f2, torch.stack(blocks)) if return_blocks else (f1, f2)
