@@ -13,6 +13,13 @@
 // history entry finishes the previous dot, applies the axpy of that entry and emits the partials of the next dot.
 // Arithmetic that the reference performs as separate tensor ops (q - alpha * y, z + s * (alpha - beta), ...) uses explicitly
 // rounded operations, so the compiler cannot contract it into FMAs.
+//
+// Per-system mode (adf_lbfgs_set_per_system).  Every system keeps its own step counter, its slice of the rings and its own
+// rho / alpha [memory]; one workgroup per system walks a whole step in ONE launch (lb_per_system_kernel).  Thread t owns
+// elements t, t + LB_THREADS, ... of its system's q / z; a dot product is the per-thread strided sum followed by the fixed
+// LDS tree, so its summation order is a function of the system's atom count alone and a system's relaxation has the same
+// bits alone, in any batch and on any shard.  The ring slot of a logical entry follows from the system's own counter and
+// is computed on the device.
 #include <string.h>
 
 #include <new>
@@ -36,6 +43,10 @@ struct adf_lbfgs {
     double* sys_absmax;  // [B] max |dr| of the system
     int32_t* mask;       // [B] update mask of the last adf_lbfgs_converge
     int64_t total;       // entries appended since create / reset
+    int64_t calls;       // adf_lbfgs_step calls since create / reset
+    int per_system;      // every system keeps its own history and decisions (lb_per_system_kernel)
+    double *rho_ps, *alpha_ps;  // [B, M], per-system mode
+    int32_t* steps;             // [B] steps a system attempted (its own iteration number), per-system mode
     adf_pool mem;        // owns every device buffer above
 };
 
@@ -97,7 +108,38 @@ extern "C" int32_t adf_lbfgs_reset(adf_lbfgs_t h, void* stream) {
     ADF_HIP_CHECK(hipMemsetAsync(h->r0, 0, n * sizeof(double), s));
     ADF_HIP_CHECK(hipMemsetAsync(h->f0, 0, n * sizeof(double), s));
     ADF_HIP_CHECK(hipMemsetAsync(h->mask, 0, (size_t)h->B * sizeof(int32_t), s));
+    if (h->steps) {
+        ADF_HIP_CHECK(hipMemsetAsync(h->steps, 0, (size_t)h->B * sizeof(int32_t), s));
+        ADF_HIP_CHECK(hipMemsetAsync(h->sys_absmax, 0, (size_t)h->B * sizeof(double), s));
+    }
     h->total = 0;
+    h->calls = 0;
+    return ADF_OK;
+}
+
+// Per-system mode on / off, on a handle that has not stepped since create / reset.
+extern "C" int32_t adf_lbfgs_set_per_system(adf_lbfgs_t h, int32_t on) {
+    if (!h) { adf_set_error("null handle"); return ADF_EINVAL; }
+    if (h->calls != 0) {
+        adf_set_error("lbfgs_set_per_system: the handle has stepped %lld times (fresh or reset handles only)",
+                      (long long)h->calls);
+        return ADF_EINVAL;
+    }
+    if (on && h->early_stop_batch) {
+        adf_set_error("lbfgs_set_per_system: early_stop_batch moves converged systems while others run, so a system alone "
+                      "and in a batch would differ; the two cannot be combined");
+        return ADF_EINVAL;
+    }
+    if (on && !h->steps) {
+        const size_t B = (size_t)h->B, M = (size_t)h->M;
+        int32_t st = h->mem.alloc(&h->rho_ps, B * M);
+        if (st == ADF_OK) st = h->mem.alloc(&h->alpha_ps, B * M);
+        if (st == ADF_OK) st = h->mem.alloc(&h->steps, B);
+        if (st == ADF_OK && hipMemset(h->steps, 0, B * sizeof(int32_t)) != hipSuccess) st = ADF_EHIP;
+        if (st == ADF_OK && hipMemset(h->sys_absmax, 0, B * sizeof(double)) != hipSuccess) st = ADF_EHIP;
+        if (st != ADF_OK) return st;
+    }
+    h->per_system = on != 0;
     return ADF_OK;
 }
 
@@ -287,6 +329,122 @@ __global__ __launch_bounds__(LB_THREADS) void lb_apply_kernel(const int32_t* __r
     }
 }
 
+// One whole step of the per-system mode; workgroup b walks system b (elements lo .. lo + nb of the flattened batch).
+//   mask clear: nothing is touched (last_absmax[b] = -1: no step attempted).
+//   mask set, t = steps[b]: (1) t > 0: s = r - r0, y = -(f - f0) into ring slot (t - 1) % M, rho = 1 / dot(y, s);
+//   (2) two loops over L = min(M, t) entries, logical entry i in slot (t - L + i) % M; (3) determine_step; (4) the skip of
+//   a step whose max |dr| over THIS system is below 1e-7 (NaN does not skip); (5) pos += f32(dr), r0 = r, f0 = f unless
+//   skipped; steps[b] = t + 1 either way.
+// Thread t reads and writes only its own elements t, t + LB_THREADS, ... of q / z up to determine_step, which reads whole
+// atoms after a barrier.  alpha is written by thread 0 and read by every thread after the barriers of the next reduction.
+__global__ __launch_bounds__(LB_THREADS) void lb_per_system_kernel(const int32_t* __restrict__ atom_offset,
+                                                                   const int32_t* __restrict__ mask, int32_t* steps,
+                                                                   float* pos, const float* __restrict__ f, double* r0,
+                                                                   double* f0, double* s, double* y, double* rho,
+                                                                   double* alpha, double* q, int64_t n, int M, double H0,
+                                                                   double maxstep, double damping, double* last_absmax) {
+    __shared__ double red[LB_THREADS];
+    const int b = blockIdx.x;
+    const int tid = threadIdx.x;
+    if (mask[b] == 0) {
+        if (tid == 0) last_absmax[b] = -1.0;
+        return;
+    }
+    const int a0 = atom_offset[b], a1 = atom_offset[b + 1];
+    const int64_t lo = 3 * (int64_t)a0;
+    const int nb = 3 * (a1 - a0);
+    const int t = steps[b];
+    const int L = t < M ? t : M;
+    pos += lo; f += lo; r0 += lo; f0 += lo; q += lo;
+    s += lo; y += lo;
+    rho += (size_t)b * M;
+    alpha += (size_t)b * M;
+    // ring slot of logical deque entry i (0 = oldest kept) and the offset of that entry in the rings
+    auto slot = [&](int i) -> int { return (t - L + i) % M; };
+    auto entry = [&](int i) -> size_t { return (size_t)slot(i) * (size_t)n; };
+
+    // (1) history append and rho; q = -f, with the partial of dot(s[L-1], q), or z = H0 q without a history
+    double rho_new = 0.0, acc = 0.0;
+    if (t > 0) {
+        double* s_new = s + entry(L - 1);
+        double* y_new = y + entry(L - 1);
+        double acc_rho = 0.0;
+        for (int i = tid; i < nb; i += LB_THREADS) {
+            const double fd = (double)f[i];
+            const double qv = -fd;
+            const double sv = __dsub_rn((double)pos[i], r0[i]);
+            const double yv = -__dsub_rn(fd, f0[i]);
+            s_new[i] = sv;
+            y_new[i] = yv;
+            acc_rho = __dadd_rn(acc_rho, __dmul_rn(yv, sv));
+            acc = __dadd_rn(acc, __dmul_rn(sv, qv));
+            q[i] = qv;
+        }
+        rho_new = __ddiv_rn(1.0, lb_block_sum(acc_rho, red));
+        if (tid == 0) rho[slot(L - 1)] = rho_new;
+    } else {
+        for (int i = tid; i < nb; i += LB_THREADS) q[i] = __dmul_rn(H0, -(double)f[i]);
+    }
+
+    // (2) first loop, descending: alpha_i = rho_i dot(s_i, q); q -= alpha_i y_i; the last entry leaves z = H0 q
+    for (int i = L - 1; i >= 0; --i) {
+        const double rho_i = i == L - 1 ? rho_new : rho[slot(i)];
+        const double a = __dmul_rn(rho_i, lb_block_sum(acc, red));
+        if (tid == 0) alpha[i] = a;
+        const double* y_i = y + entry(i);
+        const double* next = i > 0 ? s + entry(i - 1) : y + entry(0);
+        acc = 0.0;
+        for (int j = tid; j < nb; j += LB_THREADS) {
+            double qv = __dsub_rn(q[j], __dmul_rn(a, y_i[j]));
+            if (i == 0) qv = __dmul_rn(H0, qv);
+            q[j] = qv;
+            acc = __dadd_rn(acc, __dmul_rn(next[j], qv));
+        }
+    }
+    // second loop, ascending: beta = rho_i dot(y_i, z); z += s_i (alpha_i - beta)
+    for (int i = 0; i < L; ++i) {
+        const double rho_i = i == L - 1 ? rho_new : rho[slot(i)];
+        const double beta = __dmul_rn(rho_i, lb_block_sum(acc, red));
+        const double c = __dsub_rn(alpha[i], beta);
+        const double* s_i = s + entry(i);
+        const double* next = i + 1 < L ? y + entry(i + 1) : nullptr;
+        acc = 0.0;
+        for (int j = tid; j < nb; j += LB_THREADS) {
+            const double zv = __dadd_rn(q[j], __dmul_rn(s_i[j], c));
+            q[j] = zv;
+            if (next) acc = __dadd_rn(acc, __dmul_rn(next[j], zv));
+        }
+    }
+    __syncthreads();   // z is complete: determine_step reads whole atoms
+
+    // (3) determine_step
+    double m = 0.0;
+    for (int a = tid; a < a1 - a0; a += LB_THREADS) {
+        const double px = -q[3 * a], py = -q[3 * a + 1], pz = -q[3 * a + 2];
+        const double l = __dsqrt_rn(__dadd_rn(__dadd_rn(__dmul_rn(px, px), __dmul_rn(py, py)), __dmul_rn(pz, pz)));
+        m = lb_max(m, l);
+    }
+    const double longest = lb_block_max(m, red);
+    const double scale = __dmul_rn(__ddiv_rn(1.0, __dadd_rn(longest, 1e-7)), fmin(longest, maxstep));
+    double am = 0.0;
+    for (int i = tid; i < nb; i += LB_THREADS) am = lb_max(am, fabs(__dmul_rn(__dmul_rn(-q[i], scale), damping)));
+    // (4) the system's own skip decision
+    const double absmax = lb_block_max(am, red);
+    // (5) masked update
+    if (!(absmax < 1e-7)) {
+        for (int i = tid; i < nb; i += LB_THREADS) {
+            const float p = pos[i];
+            r0[i] = (double)p;
+            f0[i] = (double)f[i];
+            pos[i] = __fadd_rn(p, (float)__dmul_rn(__dmul_rn(-q[i], scale), damping));
+        }
+    }
+    if (tid == 0) {
+        steps[b] = t + 1;
+        last_absmax[b] = absmax;
+    }
+}
+
 // check_convergence: max over the system's atoms of sqrt(fx^2 + fy^2 + fz^2) in f64; mask = max >= fmax
 __global__ __launch_bounds__(LB_THREADS) void lb_converge_kernel(const int32_t* __restrict__ atom_offset, const float* __restrict__ f,
                                                                  double fmax_, double* __restrict__ max_force,
@@ -346,6 +504,14 @@ extern "C" int32_t adf_lbfgs_step(adf_lbfgs_t h, const int32_t* atom_offset, flo
     const int len = (int)(total < M ? total : M);
     const int L = (int)(iteration < M ? iteration : M);
     h->total = total;
+    h->calls += 1;
+    if (h->per_system) {
+        hipLaunchKernelGGL(lb_per_system_kernel, dim3(h->B), dim3(LB_THREADS), 0, s, atom_offset, h->mask, h->steps, pos,
+                           forces, h->r0, h->f0, h->s, h->y, h->rho_ps, h->alpha_ps, h->q, (int64_t)h->n, M, h->H0,
+                           h->maxstep, h->damping, h->sys_absmax);
+        ADF_HIP_CHECK(hipGetLastError());
+        return ADF_OK;
+    }
     // ring slot of logical deque entry i (0 = oldest kept)
     auto slot = [&](int i) -> int { return (int)((total - len + i) % M); };
     double* s_new = append ? h->s + (size_t)slot(len - 1) * n : nullptr;
@@ -387,7 +553,21 @@ extern "C" int32_t adf_lbfgs_get_mask(adf_lbfgs_t h, int32_t* out, void* stream)
     return ADF_OK;
 }
 
-// max |dr| over the batch of the last adf_lbfgs_step (< 1e-7: the step was skipped); device scalar out
+// Per-system mode: the steps every system has attempted and the max |dr| of its last attempt (-1: the last
+// adf_lbfgs_step did not attempt one); either output may be null.
+extern "C" int32_t adf_lbfgs_get_step_state(adf_lbfgs_t h, int32_t* steps_taken, double* last_absmax, void* stream) {
+    if (!h) { adf_set_error("null handle"); return ADF_EINVAL; }
+    if (!h->per_system) { adf_set_error("lbfgs_get_step_state: the handle is not in per-system mode"); return ADF_EINVAL; }
+    hipStream_t s = (hipStream_t)stream;
+    if (steps_taken)
+        ADF_HIP_CHECK(hipMemcpyAsync(steps_taken, h->steps, sizeof(int32_t) * h->B, hipMemcpyDeviceToDevice, s));
+    if (last_absmax)
+        ADF_HIP_CHECK(hipMemcpyAsync(last_absmax, h->sys_absmax, sizeof(double) * h->B, hipMemcpyDeviceToDevice, s));
+    return ADF_OK;
+}
+
+// max |dr| over the batch of the last adf_lbfgs_step (< 1e-7: the step was skipped); device scalar out.  Per-system mode:
+// over the systems that attempted a step (the others hold -1, below the 0 the maximum starts from).
 __global__ void lb_last_absmax_kernel(const double* __restrict__ sys_absmax, int B, double* out) {
     __shared__ double red[LB_THREADS];
     double m = 0.0;

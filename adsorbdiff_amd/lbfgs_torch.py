@@ -9,9 +9,16 @@ reductions, ``determine_step``, the skip of a near-zero step and the masked posi
 int32 from the device per iteration (the all-converged flag), plus the [B] max forces when INFO logging is on.
 
 The optimizer is model-agnostic: any ``TorchCalc`` whose trainer's ``predict`` returns forces on the ROCm device works
-(the S2EF PaiNN of ``adsorbdiff_amd.painn`` through ``trainer.ForcesTrainer``, or any torch model).  As in the reference,
-the systems of one batch are coupled through the global dot products: a relaxation split over several batches or devices
-does not reproduce the single run.
+(the S2EF PaiNN of ``adsorbdiff_amd.painn`` through ``trainer.ForcesTrainer``, or any torch model).
+
+Two modes.  The default is the reference's recursion: the systems of one batch are coupled through dot products over the
+whole flattened batch (one ``rho``, one ``alpha``, one skip decision), so a relaxation split over several batches or
+devices does not reproduce the single run.  With ``per_system=True`` every system keeps its own history, step counter
+and decisions (``adf_lbfgs_set_per_system``): a system takes exactly the steps the reference's ``LBFGS`` would take if it
+were alone in its batch, and the summation order of its dot products depends on its atom count alone.  Given a force
+model whose rows do not depend on the other systems of the batch, a per-system relaxation is then bit-identical alone, in
+any batch, after ``ml_relax``'s out-of-memory split and on any shard (``ml_relaxation.ml_relax_sharded``).
+``early_stop_batch`` cannot be combined with it.
 
 Trajectories (``traj_dir``): ``<sid>.npz`` per system with ``positions`` [F, n, 3], ``energy`` [F], ``forces`` [F, n, 3]
 (the constrained fp64 forces the optimizer saw) plus ``numbers``, ``tags``, ``fixed`` and ``cell``; frames follow the
@@ -47,7 +54,11 @@ class LBFGS:
         traj_dir: Optional[Path] = None,
         traj_names=None,
         early_stop_batch: bool = False,
+        per_system: bool = False,
     ) -> None:
+        if per_system and early_stop_batch:
+            raise ValueError("per_system cannot be combined with early_stop_batch: it moves converged systems while others "
+                             "run, so a system alone and in a batch would differ")
         if traj_dir is not None and not traj_names:
             raise AssertionError("traj_dir needs traj_names: one trajectory file per system")
         unwrapped = getattr(model.model, "_unwrapped_model", None)
@@ -59,7 +70,7 @@ class LBFGS:
         self.H0 = 1.0 / alpha
         self.force_consistent = force_consistent
         self.device = torch.device(device)
-        self.save_full, self.early_stop_batch = save_full_traj, early_stop_batch
+        self.save_full, self.early_stop_batch, self.per_system = save_full_traj, early_stop_batch, bool(per_system)
         self.traj_dir = None if traj_dir is None else Path(traj_dir)
         self.traj_names = traj_names
         logging.info("iteration, then the max |force| of every system (eV/A)")
@@ -91,6 +102,8 @@ class LBFGS:
                                                  float(self.damping), float(self.alpha), 1 if self.early_stop_batch else 0,
                                                  C.byref(h)))
         self.handle = h
+        if self.per_system:
+            self.set_per_system(True)
         self._max_force = torch.empty(self.num_systems, dtype=torch.float64, device=self.device)
         self._all_conv = torch.empty(1, dtype=torch.int32, device=self.device)
         self._all_conv_host = torch.empty(1, dtype=torch.int32, pin_memory=True)
@@ -188,11 +201,27 @@ class LBFGS:
                                                f32.data_ptr(), int(iteration), self._stream()))
 
     def last_step_max(self) -> torch.Tensor:
-        """max |dr| over the batch of the last step, device f64 scalar (below 1e-7: the step was skipped)."""
+        """max |dr| over the batch of the last step, device f64 scalar (below 1e-7: the step was skipped); per-system mode:
+        over the systems that attempted a step."""
         out = torch.empty((), dtype=torch.float64, device=self.device)
         with torch.cuda.device(self.device):
             _lib.check(self.lib.adf_lbfgs_last_step_max(self.handle, out.data_ptr(), self._stream()))
         return out
+
+    def set_per_system(self, on: bool) -> None:
+        """Switch the handle's mode (``adf_lbfgs_set_per_system``); ValueError after a step or with early_stop_batch."""
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.adf_lbfgs_set_per_system(self.handle, 1 if on else 0))
+        self.per_system = bool(on)
+
+    def step_state(self):
+        """Per-system mode: (steps_taken int32 [B], last_absmax f64 [B]) on the device - the steps every system has
+        attempted and the largest |dr| of its last attempt (below 1e-7: skipped; -1: its mask was clear in the last step)."""
+        steps = torch.empty(self.num_systems, dtype=torch.int32, device=self.device)
+        absmax = torch.empty(self.num_systems, dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.adf_lbfgs_get_step_state(self.handle, steps.data_ptr(), absmax.data_ptr(), self._stream()))
+        return steps, absmax
 
     def reset(self) -> None:
         """Forget the history (``adf_lbfgs_reset``): the next step must have iteration 0."""

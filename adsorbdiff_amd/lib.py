@@ -29,7 +29,7 @@ EXPORTS = (
     "adf_painn_set_energy_head", "adf_painn_set_distance_floor", "adf_painn_forward_energy",
     "adf_painn_forward_energy_gradient", "adf_painn_energy_gradient_workspace",
     "adf_lbfgs_create", "adf_lbfgs_destroy", "adf_lbfgs_reset", "adf_lbfgs_converge", "adf_lbfgs_step",
-    "adf_lbfgs_get_mask", "adf_lbfgs_last_step_max",
+    "adf_lbfgs_get_mask", "adf_lbfgs_last_step_max", "adf_lbfgs_set_per_system", "adf_lbfgs_get_step_state",
     "adf_frames_create", "adf_frames_destroy", "adf_frames_push", "adf_frames_wait", "adf_frames_release", "adf_frames_pushed", "adf_frames_abort",
     "adf_get_counters", "adf_profile_enable", "adf_profile_read", "adf_measure_peaks",
     "adf_lift_adsorbates", "adf_comm_unique_id", "adf_comm_create", "adf_comm_destroy", "adf_allgather_sites",
@@ -168,6 +168,8 @@ def load():
         "adf_lbfgs_step": [vp, vp, vp, vp, i64, vp],
         "adf_lbfgs_get_mask": [vp, vp, vp],
         "adf_lbfgs_last_step_max": [vp, vp, vp],
+        "adf_lbfgs_set_per_system": [vp, i32],
+        "adf_lbfgs_get_step_state": [vp, vp, vp, vp],
         "adf_get_counters": [vp, C.POINTER(Counters), vp],
         "adf_profile_enable": [vp, i32],
         "adf_profile_read": [vp, C.POINTER(C.c_float), C.POINTER(i64), C.POINTER(i64), vp],

@@ -24,12 +24,17 @@ from .denoising_torch import Denoiser, DiffTorchCalc
 from .lbfgs_torch import LBFGS, TorchCalc
 
 
-def _sample_or_split(batch, make_denoiser, construct_in_try: bool = True) -> Iterator:
+def _sample_or_split(batch, make_denoiser, construct_in_try: bool = True, order=None, ids=None) -> Iterator:
     """Yield sampled (sub-)batches of ``batch``; halve and retry on RuntimeError.  ``construct_in_try=False``: only
-    ``run()`` is guarded, an error of the constructor propagates (``ml_relax``, reference ml_relaxation.py:56-79)."""
+    ``run()`` is guarded, an error of the constructor propagates (``ml_relax``, reference ml_relaxation.py:56-79).
+    ``order`` (a list) receives the input index of every yielded system, in the order they are yielded."""
+    if order is not None and ids is None:
+        ids = list(range(int(batch.natoms.shape[0])))
     runner = None if construct_in_try else make_denoiser(batch)
     try:
         yield (runner if runner is not None else make_denoiser(batch)).run()
+        if order is not None:
+            order.extend(ids)
         return
     except RuntimeError:
         systems = batch.to_data_list()
@@ -39,8 +44,9 @@ def _sample_or_split(batch, make_denoiser, construct_in_try: bool = True) -> Ite
             torch.cuda.empty_cache()
     logging.info(f"Failed to relax batch with size: {len(systems)}, splitting into two...")
     half = len(systems) // 2
-    for part in (systems[half:], systems[:half]):
-        yield from _sample_or_split(data_list_collater(part), make_denoiser, construct_in_try)
+    for part in (slice(half, None), slice(None, half)):
+        yield from _sample_or_split(data_list_collater(systems[part]), make_denoiser, construct_in_try, order,
+                                    None if order is None else ids[part])
 
 
 def ml_diffuse(
@@ -74,22 +80,65 @@ def ml_relax(
     device: str = "cuda:0",
     transform=None,
     early_stop_batch: bool = False,
+    _order=None,
 ):
     """Relax every system of ``batch`` with the device L-BFGS driven by ``model.predict`` (a trainer such as
     ``trainer.ForcesTrainer``).  ``relax_opt``: ``memory`` (required), ``maxstep`` (0.04), ``damping`` (1.0), ``alpha`` (70.0),
-    ``traj_dir`` (None).  Same split-on-RuntimeError order as ``ml_diffuse``; returns one re-collated ``Batch``."""
-    opts = {"maxstep": 0.04, "damping": 1.0, "alpha": 70.0, "traj_dir": None}
+    ``traj_dir`` (None), ``per_system`` (False: the reference's coupled recursion; True: every system keeps its own history
+    and decisions, so the split below and a shard reproduce the unsplit run).  Same split-on-RuntimeError order as
+    ``ml_diffuse``; returns one re-collated ``Batch``."""
+    opts = {"maxstep": 0.04, "damping": 1.0, "alpha": 70.0, "traj_dir": None, "per_system": False}
     opts.update(relax_opt)
     sink = None if opts["traj_dir"] is None else Path(opts["traj_dir"])
+
+    # the keyword goes out only when set: LBFGS stand-ins with the reference's signature keep working
+    per_system = {"per_system": True} if opts["per_system"] else {}
 
     class _Relaxer:
         def __init__(self, b):
             self.optimizer = LBFGS(b, TorchCalc(model, transform), maxstep=opts["maxstep"], memory=opts["memory"],
                                    damping=opts["damping"], alpha=opts["alpha"], device=device,
                                    save_full_traj=save_full_traj, traj_dir=sink, traj_names=b.sid,
-                                   early_stop_batch=early_stop_batch)
+                                   early_stop_batch=early_stop_batch, **per_system)
 
         def run(self):
             return self.optimizer.run(fmax=fmax, steps=steps)
 
-    return Batch.from_data_list(list(_sample_or_split(batch, _Relaxer, construct_in_try=False)))
+    return Batch.from_data_list(list(_sample_or_split(batch, _Relaxer, construct_in_try=False, order=_order)))
+
+
+def ml_relax_sharded(
+    batch,
+    model,
+    steps: int,
+    fmax: float,
+    relax_opt,
+    save_full_traj,
+    rank: int,
+    world: int,
+    via: str = "torch",
+    device: str = "cuda:0",
+    transform=None,
+):
+    """``ml_relax`` dealt over ``world`` ranks: this rank relaxes its share of ``batch`` (``sampler.shard_batch``, by atom
+    count) and ONE all-gather (``sampler.gather_relaxed``) brings every system's relaxed positions, energy and forces to
+    every rank.  Returns the whole batch in global system order with ``pos``, ``y`` and ``force`` filled in.  Needs
+    ``relax_opt["per_system"]``: only then does a system relax the same way in a shard as in the whole batch."""
+    from . import sampler
+
+    if not dict(relax_opt).get("per_system", False):
+        raise ValueError("ml_relax_sharded needs relax_opt['per_system'] = True: the default L-BFGS couples the systems of "
+                         "a batch through batch-wide dot products, so a shard would not reproduce the single run")
+    mine, ids = sampler.shard_batch(batch, rank, world)
+    local = None
+    if ids:
+        order = []
+        local = ml_relax(mine, model, steps, fmax, relax_opt, save_full_traj, device=device, transform=transform,
+                         _order=order)
+        ids = [ids[i] for i in order]   # ml_relax returns its out-of-memory halves in the reference's order
+    pos, y, force = sampler.gather_relaxed(local, ids, batch.natoms.tolist(), world, via=via)
+    out = batch.clone()
+    out.pos = pos.to(batch.pos.device)
+    out.y = y.to(batch.pos.device)
+    out.force = force.to(batch.pos.device)
+    return out

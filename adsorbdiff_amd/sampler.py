@@ -6,6 +6,10 @@ end (RCCL over xGMI on the GPU box, gloo in the CPU tests).  This replaces the r
 per-rank ``.npz`` files + barrier + rank-0 merge (adsorbdiff/trainers/sde_denoising_trainer.py:
 862-909); the greedy partition mirrors its load balancing by atom count
 (adsorbdiff/datasets/data_parallel.py:32-48).
+
+A relaxation in the per-system L-BFGS mode shards the same way (``ml_relaxation.ml_relax_sharded``); its one exchange
+carries every system's relaxed positions, energy and forces (``pack_relaxed`` / ``merge_packed_relaxed`` /
+``gather_relaxed``).
 """
 from __future__ import annotations
 
@@ -206,3 +210,90 @@ def merge_packed_sites(everything: torch.Tensor, Amax: int, ordered: bool = True
     if not ordered:
         return sites                                                   # rank-major
     return sites[torch.argsort(gid[keep].to(torch.int64))]
+
+
+# ---- the exchange of a sharded relaxation (ml_relaxation.ml_relax_sharded): same conventions as gather_sites
+def relaxed_bounds(natoms: Sequence[int], world: int):
+    """(B_max, n_max) of a relaxation dealt by ``shard_batch``: the largest number of systems on a rank and the largest
+    system.  Derived locally from the global atom counts (the partition is deterministic): no shape exchange."""
+    parts = balanced_partition(list(natoms), world)
+    return max(len(p) for p in parts), max(max(int(n) for n in natoms), 1)
+
+
+def pack_relaxed(local, system_ids, bounds, device=None) -> torch.Tensor:
+    """One rank's message: ``[B_max, 2 + 6 n_max]`` INT32 words per system - the global id as it is (-1 = padding row), then
+    float32 bit patterns: the energy ``y``, the positions (3 n_max) and the forces (3 n_max), NaN-padded.  ``local``: the
+    relaxed shard (``pos``, ``y``, ``force``, ``natoms``), or None for a rank that was dealt nothing (an all-padding message
+    on ``device``)."""
+    Bmax, nmax = int(bounds[0]), int(bounds[1])
+    ids = torch.as_tensor(list(system_ids), dtype=torch.int32)
+    dev = local.pos.device if local is not None else (device if device is not None else torch.device("cpu"))
+    nan_bits = int(torch.tensor([float("nan")], dtype=torch.float32).view(torch.int32)[0])
+    packed = torch.full((Bmax, 2 + 6 * nmax), nan_bits, dtype=torch.int32, device=dev)
+    packed[:, 0] = -1
+    if local is None:
+        if ids.numel():
+            raise ValueError("pack_relaxed: system ids without a batch")
+        return packed
+    natoms = local.natoms.reshape(-1)
+    B = int(natoms.shape[0])
+    if ids.numel() != B:
+        raise ValueError("every rank must pass one id per local system")
+    if B > Bmax or int(natoms.max()) > nmax:
+        raise ValueError(f"pack_relaxed: {B} systems of up to {int(natoms.max())} atoms exceed the bounds {(Bmax, nmax)}")
+    sys_of = local.batch.to(dev, torch.int64)
+    start = (torch.cumsum(natoms, 0) - natoms).to(dev)
+    within = torch.arange(sys_of.shape[0], device=dev) - start[sys_of]
+    col = (3 * within).reshape(-1, 1) + torch.arange(3, device=dev)
+    row = sys_of.reshape(-1, 1).expand(-1, 3)
+    packed[:B, 0] = ids.to(dev)
+    packed[:B, 1] = local.y.detach().reshape(-1).to(dev, torch.float32).contiguous().view(torch.int32)
+    packed[row, 2 + col] = local.pos.detach().to(torch.float32).contiguous().view(torch.int32)
+    packed[row, 2 + 3 * nmax + col] = local.force.detach().to(dev, torch.float32).contiguous().view(torch.int32)
+    return packed
+
+
+def merge_packed_relaxed(everything: torch.Tensor, natoms: Sequence[int]):
+    """All ranks' messages ``[world, B_max, 2 + 6 n_max]`` -> (pos [N, 3], y [B], force [N, 3]) as float32 in global system
+    order; ``natoms``: the atom counts of the global batch."""
+    world, Bmax, W = everything.shape
+    nmax = (W - 2) // 6
+    rows = everything.reshape(world * Bmax, W)
+    gid = rows[:, 0].to(torch.int64)
+    rows = rows[gid >= 0][torch.argsort(gid[gid >= 0])]
+    counts = torch.as_tensor(list(natoms), dtype=torch.int64, device=rows.device)
+    if rows.shape[0] != counts.shape[0] or not torch.equal(rows[:, 0].to(torch.int64), torch.arange(counts.shape[0], device=rows.device)):
+        raise ValueError("merge_packed_relaxed: the messages do not hold every system of the batch exactly once")
+    keep = (torch.arange(nmax, device=rows.device).reshape(1, -1) < counts.reshape(-1, 1)).reshape(-1)
+    y = rows[:, 1].contiguous().view(torch.float32)
+    pos = rows[:, 2 : 2 + 3 * nmax].contiguous().view(torch.float32).reshape(-1, 3)[keep]
+    force = rows[:, 2 + 3 * nmax :].contiguous().view(torch.float32).reshape(-1, 3)[keep]
+    return pos, y, force
+
+
+def gather_relaxed(local, system_ids, natoms: Sequence[int], world: int, via: str = "torch", device=None):
+    """All ranks' relaxed systems: (pos [N, 3], y [B], force [N, 3]) of the GLOBAL batch (atom counts ``natoms``) in global
+    system order, on every rank.  ONE all-gather of ``[B_max, 2 + 6 n_max]`` int32 words per rank (``pack_relaxed``); the
+    shape comes from ``relaxed_bounds``.  A rank that was dealt nothing passes ``local=None`` and ``system_ids=[]``: its
+    all-padding message lies on ``device``, or where this group's collective runs (``_exchange_device``).
+
+    via="torch": ``torch.distributed.all_gather`` (backend nccl = RCCL over xGMI; gloo in the CPU tests);
+    via="rccl":  the library's C-ABI entry ``adf_allgather_sites`` (one GPU per rank)."""
+    bounds = relaxed_bounds(natoms, world)
+    if local is None and device is None and world > 1:
+        device = _exchange_device(via)
+    packed = pack_relaxed(local, system_ids, bounds, device)
+    if world <= 1:
+        return merge_packed_relaxed(packed.unsqueeze(0), natoms)
+    import torch.distributed as dist
+
+    if via != "rccl" and dist.get_backend() == "gloo" and packed.is_cuda:   # test configuration
+        packed = packed.cpu()
+    packed = packed.contiguous()
+    if via == "rccl":
+        everything = RcclGather.get(packed.device).all_gather(packed)
+    else:
+        outs = [torch.empty_like(packed) for _ in range(world)]
+        dist.all_gather(outs, packed)                                       # the one exchange
+        everything = torch.stack(outs)
+    return merge_packed_relaxed(everything, natoms)

@@ -745,7 +745,8 @@ int32_t adf_lbfgs_converge(adf_lbfgs_t h, const int32_t* atom_offset, const floa
  * history append (iteration > 0, deque of maxlen memory), the batch-global two-loop recursion over
  * loopmax = min(memory, iteration) entries, determine_step, the skip of a step whose max |dr| over the batch is below 1e-7
  * (decided on the device; r0 / f0 then stay) and pos += f32(dr) where the last converge's mask is set (everywhere with
- * early_stop_batch).  pos: f32 [N,3] in / out.  Enqueues 3 + 2 loopmax launches, no host synchronisation. */
+ * early_stop_batch).  pos: f32 [N,3] in / out.  Enqueues 3 + 2 loopmax launches, no host synchronisation.  In per-system
+ * mode (adf_lbfgs_set_per_system) the step is the one described there, in one launch. */
 int32_t adf_lbfgs_step(adf_lbfgs_t h, const int32_t* atom_offset, float* pos, const float* forces, int64_t iteration,
                        void* stream);
 /* the update mask of the last converge, int32 [B] device */
@@ -753,6 +754,26 @@ int32_t adf_lbfgs_get_mask(adf_lbfgs_t h, int32_t* out, void* stream);
 /* max |dr| over the batch of the last step (below 1e-7: the step was skipped), device f64 scalar.  Maxima here propagate
  * NaN as the reference's reductions do: a NaN force clears its system's mask and does not make the step skip. */
 int32_t adf_lbfgs_last_step_max(adf_lbfgs_t h, double* out, void* stream);
+/* Per-system mode (on != 0) or the coupled recursion above (0, the default).  Valid on a handle that has not stepped since
+ * create / reset (ADF_EINVAL afterwards) and not together with early_stop_batch (ADF_EINVAL: it moves converged systems
+ * while others run, so a system alone and in a batch would differ by design); allocates rho / alpha [B, memory] and the
+ * step counters.  In this mode every system b keeps its own step counter t_b (0 at create / reset), its slice of the
+ * rings, its own rho and alpha, and adf_lbfgs_step does, in ONE launch with one workgroup per system:
+ *   mask of the last converge clear: nothing - no history append, r0 / f0 / pos untouched, t_b unchanged;
+ *   mask set, t = t_b: if t > 0 append s = r - r0, y = -(f - f0), rho = 1 / dot(y, s) (deque of maxlen memory); the
+ *   two-loop recursion over loopmax = min(memory, t) entries with every dot product over this system's 3 n_b entries
+ *   only; determine_step; the step is skipped when the largest |dr| of THIS system is below 1e-7 (the maximum propagates
+ *   NaN, so a NaN does not skip; pos, r0 and f0 then stay); otherwise pos += f32(dr), r0 = r, f0 = f; t_b += 1 either way.
+ * That is the step LBFGS.step (:134-189) takes for iteration t_b when the system is alone in its batch.  The summation
+ * order of a dot product depends on the system's atom count alone (a 256-strided sum per thread, then a fixed tree), so a
+ * system's relaxation has the same bits alone, in any batch and on any shard.  adf_lbfgs_step keeps its iteration check
+ * (0, 1, 2, ... from a fresh or reset handle), adf_lbfgs_reset zeroes the counters too, and adf_lbfgs_last_step_max is the
+ * NaN-propagating maximum over the systems that attempted a step (0 when none did). */
+int32_t adf_lbfgs_set_per_system(adf_lbfgs_t h, int32_t on);
+/* Per-system mode only (ADF_EINVAL otherwise): steps_taken[b] = t_b (int32 [B], device) and last_absmax[b] = the largest
+ * |dr| of system b in the last adf_lbfgs_step (f64 [B], device; below 1e-7: that system skipped; -1: its mask was clear
+ * and it attempted nothing).  Either output may be NULL. */
+int32_t adf_lbfgs_get_step_state(adf_lbfgs_t h, int32_t* steps_taken, double* last_absmax, void* stream);
 
 const char* adf_last_error(void);
 const char* adf_version(void);
