@@ -20,6 +20,9 @@
 // LDS tree, so its summation order is a function of the system's atom count alone and a system's relaxation has the same
 // bits alone, in any batch and on any shard.  The ring slot of a logical entry follows from the system's own counter and
 // is computed on the device.
+//
+// The active set (adf_lbfgs_active_build): the list of the systems whose update mask is set, for a relaxation that leaves
+// the converged ones out of the model forward; csrc/active.hip gathers and scatters over it.
 #include <string.h>
 
 #include <new>
@@ -47,6 +50,9 @@ struct adf_lbfgs {
     int per_system;      // every system keeps its own history and decisions (lb_per_system_kernel)
     double *rho_ps, *alpha_ps;  // [B, M], per-system mode
     int32_t* steps;             // [B] steps a system attempted (its own iteration number), per-system mode
+    int32_t* prev_mask;         // [B] the mask the last adf_lbfgs_active_build saw (allocated by the first build)
+    int converged;              // adf_lbfgs_converge has run since create / reset
+    int built;                  // adf_lbfgs_active_build has run since create / reset
     adf_pool mem;        // owns every device buffer above
 };
 
@@ -114,6 +120,8 @@ extern "C" int32_t adf_lbfgs_reset(adf_lbfgs_t h, void* stream) {
     }
     h->total = 0;
     h->calls = 0;
+    h->converged = 0;
+    h->built = 0;
     return ADF_OK;
 }
 
@@ -483,6 +491,91 @@ extern "C" int32_t adf_lbfgs_converge(adf_lbfgs_t h, const int32_t* atom_offset,
     if (all_converged)
         hipLaunchKernelGGL(lb_all_converged_kernel, dim3(1), dim3(LB_THREADS), 0, s, h->mask, h->B, all_converged);
     ADF_HIP_CHECK(hipGetLastError());
+    h->converged = 1;
+    return ADF_OK;
+}
+
+// The active set of the last converge's mask, one workgroup.  The B systems are walked in chunks of LB_THREADS; inside a
+// chunk an inclusive integer scan in LDS (count of set masks, sum of their atom counts) gives every set system its place
+// k in the list and the first compact row of its atoms, and the totals of the chunks before it are carried in registers
+// (the same value in every thread).  Integer sums in a fixed order, no atomics.  changed: any mask that differs from the
+// one the previous build saw (the list is a function of the mask), or `first`.
+__global__ __launch_bounds__(LB_THREADS) void lb_active_build_kernel(const int32_t* __restrict__ mask,
+                                                                     int32_t* __restrict__ prev_mask,
+                                                                     const int32_t* __restrict__ atom_offset, int B,
+                                                                     int first, int32_t* __restrict__ act_sys,
+                                                                     int32_t* __restrict__ act_offset,
+                                                                     int32_t* __restrict__ info) {
+    __shared__ int32_t sc[LB_THREADS], sa[LB_THREADS];
+    const int t = threadIdx.x;
+    int carry_c = 0, carry_a = 0, diff = first;
+    for (int base = 0; base < B; base += LB_THREADS) {
+        const int i = base + t;
+        int flag = 0, n = 0;
+        if (i < B) {
+            flag = mask[i] != 0;
+            if (flag) n = atom_offset[i + 1] - atom_offset[i];
+            diff |= flag != (prev_mask[i] != 0);
+            prev_mask[i] = flag;
+        }
+        sc[t] = flag;
+        sa[t] = n;
+        __syncthreads();
+        for (int d = 1; d < LB_THREADS; d <<= 1) {
+            const int vc = t >= d ? sc[t - d] : 0, va = t >= d ? sa[t - d] : 0;
+            __syncthreads();
+            sc[t] += vc;
+            sa[t] += va;
+            __syncthreads();
+        }
+        if (flag) {
+            const int k = carry_c + sc[t] - 1;
+            act_sys[k] = i;
+            act_offset[k] = carry_a + sa[t] - n;
+        }
+        carry_c += sc[LB_THREADS - 1];
+        carry_a += sa[LB_THREADS - 1];
+        __syncthreads();   // the totals are read before the next chunk overwrites them
+    }
+    sc[t] = diff;
+    __syncthreads();
+    for (int w = LB_THREADS / 2; w > 0; w >>= 1) {
+        if (t < w) sc[t] |= sc[t + w];
+        __syncthreads();
+    }
+    for (int k = carry_c + t; k <= B; k += LB_THREADS) {
+        if (k < B) act_sys[k] = -1;
+        act_offset[k] = carry_a;
+    }
+    if (t == 0) {
+        info[0] = carry_c;
+        info[1] = carry_a;
+        info[2] = sc[0] != 0;
+        info[3] = 0;
+    }
+}
+
+extern "C" int32_t adf_lbfgs_active_build(adf_lbfgs_t h, const int32_t* atom_offset, int32_t* act_sys, int32_t* act_offset,
+                                          int32_t* info, void* stream) {
+    if (!h || !atom_offset || !act_sys || !act_offset || !info) {
+        adf_set_error("lbfgs_active_build: null argument");
+        return ADF_EINVAL;
+    }
+    if (!h->converged) {
+        adf_set_error("lbfgs_active_build: no adf_lbfgs_converge since create / reset (the list is built from its mask)");
+        return ADF_EINVAL;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    if (!h->prev_mask) {
+        const int32_t st = h->mem.alloc(&h->prev_mask, (size_t)h->B);
+        if (st != ADF_OK) return st;
+    }
+    // the first build after create / reset compares with nothing: an all-clear previous mask and changed forced to 1
+    if (!h->built) ADF_HIP_CHECK(hipMemsetAsync(h->prev_mask, 0, (size_t)h->B * sizeof(int32_t), s));
+    hipLaunchKernelGGL(lb_active_build_kernel, dim3(1), dim3(LB_THREADS), 0, s, h->mask, h->prev_mask, atom_offset, h->B,
+                       h->built ? 0 : 1, act_sys, act_offset, info);
+    ADF_HIP_CHECK(hipGetLastError());
+    h->built = 1;
     return ADF_OK;
 }
 

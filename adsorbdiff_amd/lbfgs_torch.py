@@ -7,6 +7,7 @@ every iteration, no step on the last one).  The optimizer state and arithmetic l
 (``csrc/lbfgs.hip``, ``adf_lbfgs_*``): fp64 history rings, the batch-global two-loop recursion with fixed-order
 reductions, ``determine_step``, the skip of a near-zero step and the masked position update.  The optimizer reads one
 int32 from the device per iteration (the all-converged flag), plus the [B] max forces when INFO logging is on.
+With ``set_drop_converged`` that word is replaced by the active list (below).
 
 The optimizer is model-agnostic: any ``TorchCalc`` whose trainer's ``predict`` returns forces on the ROCm device works
 (the S2EF PaiNN of ``adsorbdiff_amd.painn`` through ``trainer.ForcesTrainer``, or any torch model).
@@ -19,6 +20,19 @@ were alone in its batch, and the summation order of its dot products depends on 
 model whose rows do not depend on the other systems of the batch, a per-system relaxation is then bit-identical alone, in
 any batch, after ``ml_relax``'s out-of-memory split and on any shard (``ml_relaxation.ml_relax_sharded``).
 ``early_stop_batch`` cannot be combined with it.
+
+Dropping converged systems (``LBFGS.set_drop_converged(True)``, off by default; both modes).  A system whose update mask
+is clear is not moved any more, so a new forward would hand back the energy and force rows of its last one - PROVIDED a
+system's rows do not depend on the batch it sits in and the forward is deterministic run to run.  Both hold for the force
+fields of this package and are tested.  The optimizer then keeps full-size energies, raw forces and constrained forces,
+evaluates the whole batch once (iteration 0) and from then on only the systems whose mask was set at the last check: the
+active list comes from ``adf_lbfgs_active_build``, the model sees a compact batch (``adf_active_gather``) and its outputs
+go back to the full arrays (``adf_active_scatter``).  The final forward is skipped: the kept arrays are what it would
+return.  Every output of ``run`` then has the bits of the run without the option.  A model without those two properties
+(rows that depend on the batch composition, or sums in a run-dependent order) still gets a relaxation - one where every
+system is relaxed until its own convergence - but a different one from the run without the option, not the same bits.  Per
+iteration the option costs 3 launches (build, gather, scatter; the gather also copies the step-invariant fields when the
+list changed) and replaces the host read of the all-converged word by ONE read of the list (4 + B words).
 
 Trajectories (``traj_dir``): ``<sid>.npz`` per system with ``positions`` [F, n, 3], ``energy`` [F], ``forces`` [F, n, 3]
 (the constrained fp64 forces the optimizer saw) plus ``numbers``, ``tags``, ``fixed`` and ``cell``; frames follow the
@@ -36,9 +50,17 @@ import numpy as np
 import torch
 
 from . import lib as _lib
+from .data import _TENSOR_GRAPH_KEYS, _TENSOR_NODE_KEYS, Batch
 
 
 class LBFGS:
+    """The batched device L-BFGS (module docstring).  ``set_drop_converged(True)`` leaves the systems whose update mask is
+    clear out of the model forward and skips the final forward.  That rests on two properties of the force model: a
+    system's energy and force rows do not depend on the batch it is evaluated in, and the forward is deterministic; the
+    kept rows of a system that is no longer moved are then the bits a new forward would return, and ``run`` returns the
+    bits of the run without the option.  A model without those properties gets a different relaxation, not a
+    wrong-by-construction one: every system is still relaxed until its own convergence."""
+
     # the reference's constructor signature; force_consistent is accepted and unused, as there
     def __init__(
         self,
@@ -77,6 +99,11 @@ class LBFGS:
         self.lib = _lib.load()
         self.handle = None
         self.max_force_log = []   # device f64 [B] per iteration (the update masks are max_force >= fmax)
+        self.drop_converged = False   # set_drop_converged: leave systems whose mask is clear out of the forward
+        self.forward_log = []     # (systems, atoms) of every model call of the last run
+        self.time_compaction = False  # record device events around build / gather / scatter (compaction_ms)
+        self._events = []
+        self._dropping = False    # inside _run_dropping: the active list stands in for the all-converged word
 
     # ------------------------------------------------------------------ device state
     def _stream(self) -> C.c_void_p:
@@ -144,12 +171,21 @@ class LBFGS:
         with torch.cuda.device(self.device):
             _lib.check(self.lib.adf_lbfgs_converge(self.handle, self.atom_offset.data_ptr(), f32.data_ptr(),
                                                    float(self.fmax), self._max_force.data_ptr(),
-                                                   self._all_conv.data_ptr(), self._stream()))
+                                                   None if self._dropping else self._all_conv.data_ptr(), self._stream()))
         max_forces_ = self._max_force.clone()
         self.max_force_log.append(max_forces_)
         if logging.getLogger().isEnabledFor(logging.INFO):
             logging.info("%d %s", iteration, " ".join("%.3f" % v for v in max_forces_.tolist()))
         return max_forces_[self.atom_batch].ge(self.fmax), energy, f32
+
+    def set_drop_converged(self, on: bool) -> None:
+        """Leave the systems whose update mask is clear out of the model forward (module docstring).  Rests on two
+        properties of the force model: a system's rows do not depend on the batch it is evaluated in, and the forward is
+        deterministic.  ValueError with ``early_stop_batch``, which keeps moving converged systems."""
+        if on and self.early_stop_batch:
+            raise ValueError("drop_converged cannot be combined with early_stop_batch: it moves converged systems while "
+                             "others run, so their forces keep changing")
+        self.drop_converged = bool(on)
 
     def _all_converged(self) -> bool:
         self._all_conv_host.copy_(self._all_conv, non_blocking=True)
@@ -169,9 +205,15 @@ class LBFGS:
         # every iteration checks convergence; the trajectory gets the first, the last and (save_full_traj) every
         # unconverged iteration; no step after convergence or on the last iteration
         self.iterations = 0
+        self.forward_log = []
+        self._events = []
+        if self.drop_converged and steps > 0:
+            return self._run_dropping(steps)
+        shape = (self.num_systems, self.num_atoms)
         try:
             for it in range(steps):
                 mask, energy, forces = self.check_convergence(it)
+                self.forward_log.append(shape)
                 self.iterations = it + 1
                 done = self._all_converged()
                 last = it + 1 == steps
@@ -186,7 +228,163 @@ class LBFGS:
         if self.frames is not None:
             self._write_files()
         self.batch.y, self.batch.force = self.get_energy_and_forces(apply_constraint=False)
+        self.forward_log.append(shape)
         return self.batch
+
+    # ------------------------------------------------------------------ dropping converged systems
+    def _timed(self, fn) -> None:
+        if not self.time_compaction:
+            return fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        self._events.append((e0, e1))
+
+    def compaction_ms(self) -> float:
+        """Device time of the build, gather and scatter launches of the last run (``time_compaction`` set before it)."""
+        torch.cuda.current_stream(self.device).synchronize()
+        return float(sum(a.elapsed_time(b) for a, b in self._events))
+
+    def _setup_dropping(self) -> None:
+        """The active list's device words, the table of fields a compact batch carries and their compact twins, allocated
+        once at full capacity."""
+        b, dev, B, N = self.batch, self.device, self.num_systems, self.num_atoms
+        # one array, so that ONE copy brings info and the list to the host: info [4] | act_sys [B] | act_offset [B + 1]
+        self._act = torch.empty(4 + B + B + 1, dtype=torch.int32, device=dev)
+        self._info, self._act_sys, self._act_off = self._act[:4], self._act[4:4 + B], self._act[4 + B:]
+        self._act_host = torch.empty(4 + B, dtype=torch.int32, pin_memory=True)
+        self._fixed_i32 = (b.fixed.to(dev) == 1).reshape(-1).to(torch.int32).contiguous()   # TorchCalc's constraint rows
+        self._fields = {}    # key -> (source, compact twin, per_system); what the kernel copies
+        self._indexed = {}   # key -> source: rows that are no multiple of 4 bytes (bool flags), by index_select on a change
+        for keys, per_system in ((_TENSOR_NODE_KEYS, False), (_TENSOR_GRAPH_KEYS, True)):
+            for k in keys:
+                v = getattr(b, k, None) if k in b else None
+                if k in ("force", "forces", "y", "natoms") or not torch.is_tensor(v):
+                    continue
+                if k == "pos":
+                    v = b.pos    # gathered every iteration from the tensor the step moves
+                else:
+                    v = v.to(dev).contiguous()
+                rows = B if per_system else N
+                if v.shape[0] != rows:
+                    raise ValueError(f"drop_converged: batch.{k} has {v.shape[0]} rows, expected {rows}")
+                row_bytes = v.element_size() * int(v[0].numel()) if rows else 0
+                if row_bytes % 4 or v.data_ptr() % 4:
+                    self._indexed[k] = v
+                else:
+                    self._fields[k] = (v, torch.empty_like(v), per_system, row_bytes)
+        if "pos" not in self._fields:
+            raise ValueError("drop_converged: batch.pos must be a 4-byte aligned f32 [N, 3] tensor")
+        self._c_batch = torch.empty(N, dtype=torch.int64, device=dev)
+        self._c_natoms = torch.empty(B, dtype=torch.int64, device=dev)
+        self._compact = None
+
+    def _list_args(self):
+        return (self.atom_offset.data_ptr(), self._act_sys.data_ptr(), self._act_off.data_ptr(), self._info.data_ptr(),
+                self.num_systems, self.num_atoms)
+
+    def _gather(self, everything: bool) -> None:
+        """ONE launch: ``pos`` of the active systems, and with ``everything`` the step-invariant fields, ``batch`` and
+        ``natoms`` too."""
+        names = list(self._fields) if everything else ["pos"]
+        table = (_lib.ActiveField * len(names))()
+        for j, k in enumerate(names):
+            src, dst, per_system, row_bytes = self._fields[k]
+            table[j].src, table[j].dst, table[j].row_bytes, table[j].per_system = (src.data_ptr(), dst.data_ptr(), row_bytes,
+                                                                                   1 if per_system else 0)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.adf_active_gather(*self._list_args(), table, len(names),
+                                                  self._c_batch.data_ptr() if everything else None,
+                                                  self._c_natoms.data_ptr() if everything else None, self._stream()))
+
+    def _compact_batch(self, b_act: int, n_act: int, ids, changed: bool):
+        """The compact ``Batch`` of the active systems (views of the compact twins, sliced to the current counts)."""
+        self._timed(lambda: self._gather(changed or self._compact is None))
+        if changed or self._compact is None:
+            c = Batch()
+            for k, (_, dst, per_system, _) in self._fields.items():
+                setattr(c, k, dst[:b_act] if per_system else dst[:n_act])
+            if self._indexed:     # one torch index per such field, on a changed list only
+                rows, atoms = self._act_sys[:b_act].long(), self._atom_mask.nonzero().reshape(-1)
+                for k, src in self._indexed.items():
+                    setattr(c, k, src.index_select(0, rows if k in _TENSOR_GRAPH_KEYS else atoms))
+            c.batch, c.natoms = self._c_batch[:n_act], self._c_natoms[:b_act]
+            sid = getattr(self.batch, "sid", None)
+            if sid is not None:
+                c.sid = [sid[i] for i in ids]
+            self._compact = c
+        return self._compact
+
+    def _scatter(self, energy_c, forces_c) -> None:
+        f = forces_c.detach()
+        if f.dtype != torch.float32:
+            raise TypeError(f"drop_converged keeps the forces as the model returns them and scatters f32 rows; got {f.dtype}")
+        f = f.contiguous()
+        e = energy_c.detach().contiguous()
+        if e.dtype != self._energy.dtype or e.shape[1:] != self._energy.shape[1:]:
+            raise TypeError(f"drop_converged: the model's energy changed from {self._energy.dtype} {tuple(self._energy.shape[1:])} "
+                            f"to {e.dtype} {tuple(e.shape[1:])} per system")
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.adf_active_scatter(*self._list_args(), f.data_ptr(), e.data_ptr(), self._energy_row_bytes,
+                                                   self._fixed_i32.data_ptr(), self._raw.data_ptr(), self._con.data_ptr(),
+                                                   self._energy.data_ptr(), self._stream()))
+
+    def _run_dropping(self, steps: int):
+        """``run`` with ``drop_converged``: iteration 0 evaluates the whole batch, iteration it >= 1 the systems whose mask
+        was set at it - 1; no final forward.  One host read per iteration: info and the active list."""
+        B, N = self.num_systems, self.num_atoms
+        self._setup_dropping()
+        self._dropping = True
+        try:
+            for it in range(steps):
+                if it == 0:
+                    energy, raw = self.get_energy_and_forces(apply_constraint=False)
+                    self.forward_log.append((B, N))
+                    if raw.dtype != torch.float32:
+                        raise TypeError(f"drop_converged keeps the forces as the model returns them and scatters f32 rows; "
+                                        f"got {raw.dtype}")
+                    self._energy = energy.detach().clone().contiguous()
+                    self._energy_row_bytes = self._energy.element_size() * int(self._energy[0].numel())
+                    self._raw = raw.detach().clone().contiguous()
+                    self._con = self._raw.masked_fill((self._fixed_i32 != 0).reshape(-1, 1), 0)
+                else:
+                    if b_act == B:
+                        energy, raw = self.get_energy_and_forces(apply_constraint=False)   # the full batch as it is
+                    else:
+                        compact = self._compact_batch(b_act, n_act, ids, changed)
+                        energy, raw = self.model.get_energy_and_forces(compact, False)
+                    self.forward_log.append((b_act, n_act))
+                    self._timed(lambda: self._scatter(energy, raw))
+                mask, _, forces = self.check_convergence(it, forces=self._con, energy=self._energy)
+                self._atom_mask = mask
+                self.iterations = it + 1
+                self._timed(self._build_active)
+                self._act_host.copy_(self._act[:4 + B], non_blocking=True)
+                torch.cuda.current_stream(self.device).synchronize()
+                head = self._act_host[:3].tolist()
+                b_act, n_act, changed = head[0], head[1], bool(head[2])
+                ids = self._act_host[4:4 + b_act].tolist()
+                done = b_act == 0
+                last = it + 1 == steps
+                if self.frames is not None and (self.save_full or done or last or it == 0):
+                    self.write(self._energy, forces, mask)
+                if done:
+                    break
+                if not last:
+                    self.step(it, forces, mask)
+        finally:
+            self._dropping = False
+            self.close()
+        if self.frames is not None:
+            self._write_files()
+        self.batch.y, self.batch.force = self._energy, self._raw
+        return self.batch
+
+    def _build_active(self) -> None:
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.adf_lbfgs_active_build(self.handle, self.atom_offset.data_ptr(), self._act_sys.data_ptr(),
+                                                       self._act_off.data_ptr(), self._info.data_ptr(), self._stream()))
 
     def step(self, iteration: int, forces: Optional[torch.Tensor], update_mask: Optional[torch.Tensor] = None) -> None:
         """Reference :134-189 (``adf_lbfgs_step``).  The update mask is the one of the last ``check_convergence`` (kept on

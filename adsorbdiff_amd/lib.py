@@ -30,6 +30,7 @@ EXPORTS = (
     "adf_painn_forward_energy_gradient", "adf_painn_energy_gradient_workspace",
     "adf_lbfgs_create", "adf_lbfgs_destroy", "adf_lbfgs_reset", "adf_lbfgs_converge", "adf_lbfgs_step",
     "adf_lbfgs_get_mask", "adf_lbfgs_last_step_max", "adf_lbfgs_set_per_system", "adf_lbfgs_get_step_state",
+    "adf_lbfgs_active_build", "adf_active_gather", "adf_active_scatter",
     "adf_frames_create", "adf_frames_destroy", "adf_frames_push", "adf_frames_wait", "adf_frames_release", "adf_frames_pushed", "adf_frames_abort",
     "adf_get_counters", "adf_profile_enable", "adf_profile_read", "adf_measure_peaks",
     "adf_lift_adsorbates", "adf_comm_unique_id", "adf_comm_create", "adf_comm_destroy", "adf_allgather_sites",
@@ -80,6 +81,11 @@ class BatchDesc(C.Structure):
         ("num_systems", C.c_int32), ("num_atoms", C.c_int32), ("pos", C.c_void_p), ("cell", C.c_void_p),
         ("atomic_numbers", C.c_void_p), ("batch", C.c_void_p), ("atom_offset", C.c_void_p), ("reps", C.c_int32 * 3),
     ]
+
+
+class ActiveField(C.Structure):
+    """adf_active_field: one array of adf_active_gather (rows per atom, or per system)."""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("row_bytes", C.c_int32), ("per_system", C.c_int32)]
 
 
 class StepCoef(C.Structure):
@@ -170,6 +176,9 @@ def load():
         "adf_lbfgs_last_step_max": [vp, vp, vp],
         "adf_lbfgs_set_per_system": [vp, i32],
         "adf_lbfgs_get_step_state": [vp, vp, vp, vp],
+        "adf_lbfgs_active_build": [vp, vp, vp, vp, vp, vp],
+        "adf_active_gather": [vp, vp, vp, vp, i32, i64, C.POINTER(ActiveField), i32, vp, vp, vp],
+        "adf_active_scatter": [vp, vp, vp, vp, i32, i64, vp, vp, i32, vp, vp, vp, vp, vp],
         "adf_get_counters": [vp, C.POINTER(Counters), vp],
         "adf_profile_enable": [vp, i32],
         "adf_profile_read": [vp, C.POINTER(C.c_float), C.POINTER(i64), C.POINTER(i64), vp],

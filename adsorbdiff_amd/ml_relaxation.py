@@ -85,9 +85,12 @@ def ml_relax(
     """Relax every system of ``batch`` with the device L-BFGS driven by ``model.predict`` (a trainer such as
     ``trainer.ForcesTrainer``).  ``relax_opt``: ``memory`` (required), ``maxstep`` (0.04), ``damping`` (1.0), ``alpha`` (70.0),
     ``traj_dir`` (None), ``per_system`` (False: the reference's coupled recursion; True: every system keeps its own history
-    and decisions, so the split below and a shard reproduce the unsplit run).  Same split-on-RuntimeError order as
-    ``ml_diffuse``; returns one re-collated ``Batch``."""
-    opts = {"maxstep": 0.04, "damping": 1.0, "alpha": 70.0, "traj_dir": None, "per_system": False}
+    and decisions, so the split below and a shard reproduce the unsplit run), ``drop_converged`` (False; True: a system whose
+    update mask is clear is left out of the model forward from then on and the final forward is skipped,
+    ``LBFGS.set_drop_converged`` - the same bits for a force model whose rows do not depend on the batch and whose forward
+    is deterministic; not with ``early_stop_batch``).  Same split-on-RuntimeError order as ``ml_diffuse``; returns one
+    re-collated ``Batch``."""
+    opts = {"maxstep": 0.04, "damping": 1.0, "alpha": 70.0, "traj_dir": None, "per_system": False, "drop_converged": False}
     opts.update(relax_opt)
     sink = None if opts["traj_dir"] is None else Path(opts["traj_dir"])
 
@@ -100,6 +103,9 @@ def ml_relax(
                                    damping=opts["damping"], alpha=opts["alpha"], device=device,
                                    save_full_traj=save_full_traj, traj_dir=sink, traj_names=b.sid,
                                    early_stop_batch=early_stop_batch, **per_system)
+            # called only when set, for the same reason
+            if opts["drop_converged"]:
+                self.optimizer.set_drop_converged(True)
 
         def run(self):
             return self.optimizer.run(fmax=fmax, steps=steps)
@@ -123,7 +129,8 @@ def ml_relax_sharded(
     """``ml_relax`` dealt over ``world`` ranks: this rank relaxes its share of ``batch`` (``sampler.shard_batch``, by atom
     count) and ONE all-gather (``sampler.gather_relaxed``) brings every system's relaxed positions, energy and forces to
     every rank.  Returns the whole batch in global system order with ``pos``, ``y`` and ``force`` filled in.  Needs
-    ``relax_opt["per_system"]``: only then does a system relax the same way in a shard as in the whole batch."""
+    ``relax_opt["per_system"]``: only then does a system relax the same way in a shard as in the whole batch.  ``relax_opt``
+    goes to ``ml_relax`` unchanged, so ``drop_converged`` works on every shard as it does there."""
     from . import sampler
 
     if not dict(relax_opt).get("per_system", False):

@@ -775,6 +775,51 @@ int32_t adf_lbfgs_set_per_system(adf_lbfgs_t h, int32_t on);
  * and it attempted nothing).  Either output may be NULL. */
 int32_t adf_lbfgs_get_step_state(adf_lbfgs_t h, int32_t* steps_taken, double* last_absmax, void* stream);
 
+/* ---- The active set: the systems whose update mask is set, so that a relaxation can leave the converged ones out of the
+ * model forward (LBFGS.set_drop_converged).  That mode rests on two properties of the force model, not on anything in
+ * these entries: a system's energy and force rows do not depend on the batch it is evaluated in, and the forward is
+ * deterministic run to run; then the rows kept from a system's last forward are the bits a new forward would return.  A
+ * model without them gets a different relaxation, not a wrong-by-construction one: every system is still relaxed until its
+ * own convergence.  All arrays are on the device; B is the handle's system count.
+ *
+ * adf_lbfgs_active_build, from the mask the last adf_lbfgs_converge left in the handle (ADF_EINVAL before any converge
+ * since create / reset, and for a NULL argument): act_sys [B] = the ids of the systems whose mask is set, ascending,
+ * padded with -1; act_offset [B + 1] = the exclusive prefix sum of those systems' atom counts, entries past B_act equal
+ * N_act; info [4] = {B_act, N_act, changed, 0}.  changed = 1 when the list differs from the one the previous build on this
+ * handle wrote; the first build after create / reset always reports 1 (the handle keeps the previous mask, adf_lbfgs_reset
+ * forgets it).  One launch of one workgroup: an integer scan that walks B in chunks of the workgroup size with a carried
+ * prefix, in a fixed order, no atomics. */
+int32_t adf_lbfgs_active_build(adf_lbfgs_t h, const int32_t* atom_offset, int32_t* act_sys, int32_t* act_offset,
+                               int32_t* info, void* stream);
+/* One array of a gather: rows of row_bytes bytes (a positive multiple of 4; src and dst 4-byte aligned), one row per atom
+ * (per_system = 0) or per system (per_system != 0). */
+typedef struct adf_active_field {
+    const void* src;
+    void* dst;
+    int32_t row_bytes;
+    int32_t per_system;
+} adf_active_field;
+#define ADF_ACTIVE_MAX_FIELDS 16
+/* Gather, no handle.  For the k-th active system s = act_sys[k] (k < info[0], read on the device; the grid is sized by
+ * num_systems and workgroups past B_act exit): rows [atom_offset[s], atom_offset[s+1]) of every per-atom field go to rows
+ * [act_offset[k], act_offset[k+1]) of its dst, row s of every per-system field goes to row k.  batch_out (int64, one per
+ * compact atom, value k) and natoms_out (int64, one per compact system) are written when not NULL.  ONE launch copies all
+ * fields (at most ADF_ACTIVE_MAX_FIELDS) as contiguous dword ranges.  num_atoms is the atom count of the full batch (it
+ * sizes the grid only).  ADF_EINVAL: a NULL list or field pointer, a row_bytes that is not a positive multiple of 4, a
+ * misaligned pointer, more fields than the maximum, nothing to write. */
+int32_t adf_active_gather(const int32_t* atom_offset, const int32_t* act_sys, const int32_t* act_offset,
+                          const int32_t* info, int32_t num_systems, int64_t num_atoms, const adf_active_field* fields,
+                          int32_t num_fields, int64_t* batch_out, int64_t* natoms_out, void* stream);
+/* Scatter, the inverse for the outputs of a compact forward.  forces_c f32 [N_act, 3] go to the rows of the active systems
+ * in forces_raw and in forces_con (both f32 [N, 3]); a row of forces_con is +0 where fixed (int32 [N]) != 0 and the raw row
+ * otherwise.  energy_c [B_act] rows of energy_row_bytes bytes (a positive multiple of 4) go to rows act_sys[k] of energy.
+ * Rows of systems outside the list are not written.  One launch, plain vector stores.  energy_c / energy may both be NULL
+ * (forces only). */
+int32_t adf_active_scatter(const int32_t* atom_offset, const int32_t* act_sys, const int32_t* act_offset,
+                           const int32_t* info, int32_t num_systems, int64_t num_atoms, const float* forces_c,
+                           const void* energy_c, int32_t energy_row_bytes, const int32_t* fixed, float* forces_raw,
+                           float* forces_con, void* energy, void* stream);
+
 const char* adf_last_error(void);
 const char* adf_version(void);
 

@@ -16,7 +16,17 @@ With --per-system, in the same process (the default-mode figures above stay as t
   iterations_to_convergence     LBFGS.run iterations in both modes on the harmonic fixture (relax_harmonic.npz) and on the
                                 relax_run.npz batch with the small seeded S2EF PaiNN, --converge-steps at the most
 
+With --drop-converged, INSTEAD of the figures above (one process, the same model and shape): LBFGS.run with
+set_drop_converged off and on, alternating, --drop-repeats each, under a convergence SCHEDULE - a calculator wrapper zeroes
+the force rows of system b from a seeded iteration c_b on, so that its mask clears there.  This is a schedule, not physics:
+it fixes which systems are dropped when, and the forward that is timed is the real one.  Two legs: "overhead" (c_b =
+--drop-steps for every system: nothing drops early) and "staggered" (c_b uniform over 1 .. --drop-steps).  One JSON line per
+run (wall_ms, iterations, system_forwards, atom_forwards from LBFGS.forward_log, compaction_ms_per_iteration = the device
+time of build + gather + scatter) and one summary line per leg (on / off time ratio, evaluated-atom share, the spread of
+the off setting); --out writes the same lines as a JSON array.
+
     python tools/time_relax.py [--systems 1000] [--atoms 200] [--reps 20] [--per-system]
+    python tools/time_relax.py --drop-converged [--drop-steps 20] [--drop-repeats 2] [--out profiles/relax_drop_converged.json]
 """
 from __future__ import annotations
 
@@ -193,6 +203,82 @@ def iterations_to_convergence(max_steps):
     return res
 
 
+class ScheduledCalc(TorchCalc):
+    """TorchCalc whose forces of system b are zero from call number c_b on (looked up by ``sid``, so it works on the compact
+    batches of drop_converged too).  A schedule of convergence, not physics."""
+
+    def __init__(self, trainer, sids, cutoff):
+        super().__init__(trainer)
+        self.row = {s: i for i, s in enumerate(sids)}
+        self.cutoff = torch.as_tensor(cutoff, dtype=torch.int64, device=DEV)
+        self.calls = 0
+
+    def get_energy_and_forces(self, atoms, apply_constraint=True):
+        energy, forces = super().get_energy_and_forces(atoms, apply_constraint)
+        rows = torch.tensor([self.row[s] for s in atoms.sid], dtype=torch.int64).to(DEV)
+        done = self.cutoff[rows] <= self.calls
+        self.calls += 1
+        return energy, forces.masked_fill(done[atoms.batch].reshape(-1, 1), 0)
+
+
+def drop_converged_legs(model, a):
+    """The two legs of --drop-converged; returns the JSON-able lines."""
+    tr = ForcesTrainer(model, device=DEV)
+    cpu_batch = make_batch(a.systems, n_slab=a.atoms - 4, n_ads=4, seed=1000)
+    B, steps = a.systems, a.drop_steps
+    g = torch.Generator().manual_seed(7)
+    legs = {"overhead": [steps] * B, "staggered": torch.randint(1, steps + 1, (B,), generator=g).tolist()}
+    lines = []
+
+    def run(cutoff, drop, n_steps):
+        b = cpu_batch.clone().to(DEV)
+        opt = LBFGS(b, ScheduledCalc(tr, b.sid, cutoff), device=DEV, **OPT)
+        opt.set_drop_converged(drop)
+        opt.time_compaction = drop
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        opt.run(fmax=1e-9, steps=n_steps)
+        torch.cuda.synchronize()
+        ms = (time.perf_counter() - t0) * 1e3
+        return opt, b, ms
+
+    settings = {"both": (False, True), "off": (False,), "on": (True,)}[a.drop_only]
+    if a.drop_leg != "both":
+        legs = {a.drop_leg: legs[a.drop_leg]}
+    if not a.drop_no_warmup:
+        for drop in settings:       # workspaces, allocator: not timed
+            run(legs[next(iter(legs))], drop, 3)
+    for leg, cutoff in legs.items():
+        res = {False: [], True: []}
+        for rep in range(a.drop_repeats):
+            for drop in settings:
+                opt, b, ms = run(cutoff, drop, steps)
+                line = {"leg": leg, "setting": "on" if drop else "off", "repeat": rep, "schedule": "seeded, not physics",
+                        "systems": B, "atoms": int(b.pos.shape[0]), "steps": steps, "wall_ms": ms,
+                        "iterations": opt.iterations, "model_calls": len(opt.forward_log),
+                        "system_forwards": sum(s for s, _ in opt.forward_log),
+                        "atom_forwards": sum(n for _, n in opt.forward_log)}
+                if drop:
+                    line["compaction_ms_per_iteration"] = opt.compaction_ms() / max(1, opt.iterations)
+                res[drop].append((line, b.pos.clone(), torch.stack(opt.max_force_log)))
+                lines.append(line)
+                print(json.dumps(line), flush=True)
+        if len(settings) < 2:       # one setting alone (a kernel-trace run of its own): no comparison to print
+            continue
+        off = [r[0]["wall_ms"] for r in res[False]]
+        on = [r[0]["wall_ms"] for r in res[True]]
+        summary = {"leg": leg, "summary": True,
+                   "off_ms_mean": sum(off) / len(off), "on_ms_mean": sum(on) / len(on),
+                   "off_spread_ms": max(off) - min(off), "on_spread_ms": max(on) - min(on),
+                   "on_over_off": (sum(on) / len(on)) / (sum(off) / len(off)),
+                   "evaluated_atom_share": res[True][0][0]["atom_forwards"] / res[False][0][0]["atom_forwards"],
+                   "same_positions_and_max_forces": bool(torch.equal(res[True][0][1], res[False][0][1])
+                                                         and torch.equal(res[True][0][2], res[False][0][2]))}
+        lines.append(summary)
+        print(json.dumps(summary), flush=True)
+    return lines
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--systems", type=int, default=1000)
@@ -201,10 +287,24 @@ def main() -> None:
     ap.add_argument("--run-steps", type=int, default=8)
     ap.add_argument("--per-system", action="store_true", help="also time the per-system mode and count iterations in both")
     ap.add_argument("--converge-steps", type=int, default=200)
+    ap.add_argument("--drop-converged", action="store_true", help="time LBFGS.run with set_drop_converged off and on")
+    ap.add_argument("--drop-steps", type=int, default=20)
+    ap.add_argument("--drop-repeats", type=int, default=2)
+    ap.add_argument("--drop-only", choices=("both", "off", "on"), default="both",
+                    help="one setting alone, for a profiler run of its own (no summary line)")
+    ap.add_argument("--drop-leg", choices=("both", "overhead", "staggered"), default="both")
+    ap.add_argument("--drop-no-warmup", action="store_true", help="skip the untimed warm-up runs (kernel traces)")
+    ap.add_argument("--out", type=Path, default=None, help="--drop-converged: also write the lines as a JSON array")
     a = ap.parse_args()
     torch.manual_seed(0)
     model = PaiNN(None, 50, 1, hidden_channels=512, num_layers=6, num_rbf=128, cutoff=12.0, max_neighbors=50,
                   scale_file=dict(PAINN_NB6_SCALE_FACTORS)).to(DEV).eval()
+    if a.drop_converged:
+        lines = drop_converged_legs(model, a)
+        if a.out is not None:
+            a.out.parent.mkdir(parents=True, exist_ok=True)
+            a.out.write_text(json.dumps(lines, indent=1) + "\n")
+        return
     b = make_batch(a.systems, n_slab=a.atoms - 4, n_ads=4, seed=1000).to(DEV)
     N, B = int(b.pos.shape[0]), a.systems
     out = {"systems": B, "atoms": N, **OPT}
