@@ -19,6 +19,7 @@ from typing import Iterator
 
 import torch
 
+from . import flag_anomaly as _anomaly
 from .data import Batch, data_list_collater
 from .denoising_torch import Denoiser, DiffTorchCalc
 from .lbfgs_torch import LBFGS, TorchCalc
@@ -88,9 +89,12 @@ def ml_relax(
     and decisions, so the split below and a shard reproduce the unsplit run), ``drop_converged`` (False; True: a system whose
     update mask is clear is left out of the model forward from then on and the final forward is skipped,
     ``LBFGS.set_drop_converged`` - the same bits for a force model whose rows do not depend on the batch and whose forward
-    is deterministic; not with ``early_stop_batch``).  Same split-on-RuntimeError order as ``ml_diffuse``; returns one
-    re-collated ``Batch``."""
-    opts = {"maxstep": 0.04, "damping": 1.0, "alpha": 70.0, "traj_dir": None, "per_system": False, "drop_converged": False}
+    is deterministic; not with ``early_stop_batch``), ``flag_anomalies`` (False; True: the returned batch carries ``anomaly``
+    [B,4] bool, ``flag_anomaly.flag_anomalies`` of the positions given here against the relaxed ones, computed once on the
+    collated result; ``anomaly_radii``: its radius table, default ``ase.data.covalent_radii``).  Same split-on-RuntimeError
+    order as ``ml_diffuse``; returns one re-collated ``Batch``."""
+    opts = {"maxstep": 0.04, "damping": 1.0, "alpha": 70.0, "traj_dir": None, "per_system": False, "drop_converged": False,
+            "flag_anomalies": False, "anomaly_radii": None}
     opts.update(relax_opt)
     sink = None if opts["traj_dir"] is None else Path(opts["traj_dir"])
 
@@ -110,7 +114,24 @@ def ml_relax(
         def run(self):
             return self.optimizer.run(fmax=fmax, steps=steps)
 
-    return Batch.from_data_list(list(_sample_or_split(batch, _Relaxer, construct_in_try=False, order=_order)))
+    if not opts["flag_anomalies"]:
+        return Batch.from_data_list(list(_sample_or_split(batch, _Relaxer, construct_in_try=False, order=_order)))
+    # the optimizer moves batch.pos in place: keep the positions this call was given
+    initial = batch.clone()
+    order = [] if _order is None else _order
+    first = len(order)
+    out = Batch.from_data_list(list(_sample_or_split(batch, _Relaxer, construct_in_try=False, order=order)))
+    out.anomaly = _flag_relaxed(initial, order[first:], out, opts["anomaly_radii"])
+    return out
+
+
+def _flag_relaxed(initial, order, relaxed, radii):
+    """Anomaly flags of ``relaxed`` against ``initial``, whose systems are brought into the returned order first (the
+    out-of-memory split reorders them; ``order[k]`` is the input index of returned system ``k``)."""
+    if order != list(range(len(order))):
+        systems = initial.to_data_list()
+        initial = Batch.from_data_list([systems[i] for i in order])
+    return _anomaly.flag_anomalies(initial.to(relaxed.pos.device), relaxed.pos, radii=radii)
 
 
 def ml_relax_sharded(
@@ -130,17 +151,21 @@ def ml_relax_sharded(
     count) and ONE all-gather (``sampler.gather_relaxed``) brings every system's relaxed positions, energy and forces to
     every rank.  Returns the whole batch in global system order with ``pos``, ``y`` and ``force`` filled in.  Needs
     ``relax_opt["per_system"]``: only then does a system relax the same way in a shard as in the whole batch.  ``relax_opt``
-    goes to ``ml_relax`` unchanged, so ``drop_converged`` works on every shard as it does there."""
+    goes to ``ml_relax`` unchanged, so ``drop_converged`` works on every shard as it does there - but for ``flag_anomalies``:
+    the flags are computed after the gather, on the whole batch, on every rank."""
     from . import sampler
 
     if not dict(relax_opt).get("per_system", False):
         raise ValueError("ml_relax_sharded needs relax_opt['per_system'] = True: the default L-BFGS couples the systems of "
                          "a batch through batch-wide dot products, so a shard would not reproduce the single run")
+    want_flags = bool(dict(relax_opt).get("flag_anomalies", False))
+    initial = batch.clone() if want_flags else None     # a shard may share storage with batch.pos
+    shard_opt = dict(relax_opt, flag_anomalies=False) if want_flags else relax_opt
     mine, ids = sampler.shard_batch(batch, rank, world)
     local = None
     if ids:
         order = []
-        local = ml_relax(mine, model, steps, fmax, relax_opt, save_full_traj, device=device, transform=transform,
+        local = ml_relax(mine, model, steps, fmax, shard_opt, save_full_traj, device=device, transform=transform,
                          _order=order)
         ids = [ids[i] for i in order]   # ml_relax returns its out-of-memory halves in the reference's order
     pos, y, force = sampler.gather_relaxed(local, ids, batch.natoms.tolist(), world, via=via)
@@ -148,4 +173,6 @@ def ml_relax_sharded(
     out.pos = pos.to(batch.pos.device)
     out.y = y.to(batch.pos.device)
     out.force = force.to(batch.pos.device)
+    if want_flags:
+        out.anomaly = _anomaly.flag_anomalies(initial.to(out.pos.device), out.pos, radii=dict(relax_opt).get("anomaly_radii"))
     return out

@@ -368,6 +368,37 @@ int32_t adf_tr_sample_traj(adf_painn_t h, const adf_batch* b, float* pos, const 
 int32_t adf_lift_adsorbates(float* pos, const int32_t* tags, const int32_t* atom_offset, int32_t B, float min_gap,
                             float* lifted, void* stream);
 
+/* Relaxation anomalies (replaces DetectTrajAnomaly, adsorbdiff/placement/flag_anomaly.py:6-154, evaluated per structure on
+ * the host with five ASE NeighborList builds) for a whole batch of relaxations, first frame against last frame.
+ *   dmin(i,j)   = min over lattice vectors T of |p_j + T - p_i|, T over all integer combinations along the periodic
+ *                 directions, T = 0 excluded when i == j (an atom can bind its own image: the diagonal counts);
+ *   conn_m(i,j) = dmin(i,j) < m * (R_i + R_j) + 2 * skin   (strict), R = radii[atomic number];
+ *   adsorbate = tag 2, slab = tag != 2, frozen = tag 0; slab_ref = pos_slab_ref, or the initial positions when NULL.
+ *   flags[b] = { dissociated:     conn_1 over the adsorbate atoms differs between initial and final in any entry,
+ *                desorbed:        no (adsorbate, slab) pair has conn_desorption_mult in the final positions (a system
+ *                                 without adsorbate atoms is desorbed),
+ *                surface_changed: a slab pair with conn_1(final) and not conn_surface_mult(slab_ref), or with
+ *                                 conn_1(slab_ref) and not conn_surface_mult(final),
+ *                intercalated:    an (adsorbate, frozen) pair with conn_1 in the final positions }  - scripts/eval.py's order.
+ * b->pos: the initial positions; pos_final [N,3]; pos_slab_ref [N,3] aligned with the batch (rows of tag 2 are ignored);
+ * radii: device table [num_radii]; flags: [B,4] int32, 0 or 1.  Positions need not be wrapped into the cell: every
+ * displacement is reduced to its nearest image first.  b->reps: images tried per direction after that reduction, sized by
+ * the caller for the largest threshold of the batch (engine.cell_repeats; anomaly.hip states why that suffices); a
+ * direction with reps 0 is not periodic.  An atomic number outside [0, num_radii) returns ADF_EINVAL, reported like
+ * adf_graph_build reports one outside its table: the call synchronises `stream` to read the error word.  The flags are
+ * ORs of per-pair evidence, combined with integer atomics: bit-reproducible. */
+int32_t adf_flag_anomalies(const adf_batch* b, const float* pos_final, const float* pos_slab_ref, const int32_t* tags,
+                           const float* radii, int32_t num_radii, float skin, float surface_mult, float desorption_mult,
+                           int32_t* flags, void* stream);
+
+/* Rank the relaxed sites (scripts/eval.py:566-579: the minimum relaxed energy per system among the sites without an
+ * anomaly).  Sites of group g are energy[group_offset[g] .. group_offset[g+1]).  A site is valid when its four flags
+ * (flags [S,4], NULL: no filter) are 0 and its energy is not NaN.  best[g]: index into `energy` of the valid site of
+ * least energy, ties to the lowest index, -1 without a valid site; best_energy[g] (may be NULL): its energy, +inf
+ * without one; n_valid[g] (may be NULL): valid sites.  One launch, fixed reduction order, no atomics. */
+int32_t adf_select_best_sites(const float* energy, const int32_t* flags, const int32_t* group_offset, int32_t num_groups,
+                              int32_t* best, float* best_energy, int32_t* n_valid, void* stream);
+
 /* Multi-GPU exchange of the sharded sampler: systems are independent, every rank samples its shard
  * with no data-path collective, and ONE all-gather of the sampled adsorbate sites ends a pass.  Replaces the reference's
  * per-rank .npz + barrier + rank-0 merge (trainers/sde_denoising_trainer.py:862-909).  RCCL is loaded lazily (dlopen).
