@@ -35,6 +35,7 @@ EXPORTS = (
     "adf_get_counters", "adf_profile_enable", "adf_profile_read", "adf_measure_peaks",
     "adf_lift_adsorbates", "adf_flag_anomalies", "adf_select_best_sites", "adf_comm_unique_id", "adf_comm_create", "adf_comm_destroy", "adf_allgather_sites",
     "adf_op_linear_fwd", "adf_op_linear_bwd_scratch", "adf_op_linear_bwd", "adf_op_ssilu_fwd", "adf_op_ssilu_bwd", "adf_op_layernorm_fwd", "adf_op_layernorm_bwd", "adf_op_embed_fwd", "adf_op_embed_bwd", "adf_op_rbf", "adf_op_message_fwd", "adf_op_message_fwd_fused", "adf_op_message_bwd", "adf_op_message_bwd_fused", "adf_op_message_bwd_fused_supported", "adf_op_message_bwd_perm", "adf_op_edge_owner", "adf_op_rbf_image_bytes", "adf_op_rbf_image", "adf_op_rbf_wgrad_fused_scratch", "adf_op_rbf_wgrad_fused", "adf_op_vdot_fwd", "adf_op_vdot_bwd", "adf_op_update_out_fwd", "adf_op_update_out_bwd", "adf_op_vnorm_fwd", "adf_op_vnorm_bwd", "adf_op_gate_fwd", "adf_op_gate_bwd", "adf_op_copy_rows", "adf_op_score_loss", "adf_op_s2ef_loss", "adf_op_s2ef_loss_scratch", "adf_op_energy_sum", "adf_op_energy_head_bwd", "adf_op_energy_head_bwd_scratch", "adf_op_sqnorm_accumulate", "adf_op_adamw_step",
+    "adf_eval_scratch", "adf_eval_s2ef", "adf_eval_is2rs", "adf_eval_is2re", "adf_eval_add",
     "adf_eqv2_create", "adf_eqv2_destroy", "adf_eqv2_set_constants", "adf_eqv2_set_weights", "adf_eqv2_set_arithmetic",
     "adf_eqv2_set_energy_embedding", "adf_eqv2_set_system_energy",
     "adf_eqv2_set_weights_s2ef", "adf_eqv2_set_energy_head", "adf_eqv2_forward_energy", "adf_eqv2_radial_first_layer",
@@ -224,6 +225,10 @@ def load():
         "adf_op_energy_head_bwd": [vp, vp, vp, vp, vp, vp, vp, i32, i64, i32, vp, vp],
         "adf_op_sqnorm_accumulate": [vp, i64, vp, vp],
         "adf_op_adamw_step": [vp, vp, vp, vp, vp, i64, vp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, i32, C.c_float, vp],
+        "adf_eval_s2ef": [vp, vp, vp, vp, vp, vp, i32, i32, i32, C.c_float, C.c_float, C.c_float, C.c_float, vp, vp, vp, vp],
+        "adf_eval_is2rs": [vp, vp, vp, vp, vp, i32, i32, vp, i32, vp, vp, vp, vp],
+        "adf_eval_is2re": [vp, vp, i32, vp, vp, vp],
+        "adf_eval_add": [vp, i32, vp, vp, vp],
         "adf_eqv2_create": [C.POINTER(EqV2Hparams), C.POINTER(vp)],
         "adf_eqv2_destroy": [vp],
         "adf_eqv2_set_constants": [vp, vp, vp, vp, vp, vp],
@@ -272,6 +277,8 @@ def load():
     lib.adf_op_s2ef_loss_scratch.restype = i64
     lib.adf_op_energy_head_bwd_scratch.argtypes = [i64, i32]
     lib.adf_op_energy_head_bwd_scratch.restype = i64
+    lib.adf_eval_scratch.argtypes = [i32]
+    lib.adf_eval_scratch.restype = i64
     lib.adf_frames_pushed.argtypes = [vp]
     lib.adf_frames_pushed.restype = i64
     _LIB = lib

@@ -154,6 +154,72 @@ class DenoisingTrainer:
         self.step += 1
         return {"loss": loss, "grad_norm": grad_norm, "skipped": False, "stop": False}
 
+    # ---------------------------------------------------------------- evaluation
+    @torch.no_grad()
+    def validate(self, batches: Optional[Iterable] = None, noised: bool = False, split: str = "val",
+                 disable_tqdm: bool = True) -> dict:
+        """The reference's ``validate`` (sde_denoising_trainer.py:286-368): per batch ``pos_relaxed`` for the positions,
+        ``tr_so3_schedule`` (unless ``noised``: the batch already carries its noise and scores), the inference forward and the
+        score loss without a backward.  This trainer evaluates under the task "ocp", which has no metrics, so the result is
+        ``{"loss": {"metric", "total", "numel"}}``: the mean over the batches, summed over the ranks.  The losses are added
+        up on the device; the pass ends with one all-reduce and one read (per batch, the look-up of the rotation score's
+        norm reads ``rot_sigma`` on the host, as in ``train_step``).  ``batches``: default ``val_loader`` / ``test_loader``
+        by ``split``; ``disable_tqdm`` is accepted for the reference's signature, there is no progress bar."""
+        import ctypes as C
+
+        from . import lib as _lib
+        from .evaluator import DeviceMetrics, Evaluator, atom_offsets
+        from .noising import tr_so3_schedule
+        from .so3_tables import Igso3Tables
+
+        if not self.config["model_attributes"].get("so3_denoising", False):
+            raise NotImplementedError("validate offers the translation + rotation score loss (so3_denoising=True)")
+        ensure_fitted(self._unwrapped_model, warn=True)
+        engine = getattr(self, "train_engine", None)
+        tables = engine.igso3 if engine is not None else Igso3Tables.shared()
+        params = getattr(self, "denoising_pos_params", None) or self.config["optim"].get("denoising_pos_params")
+        if batches is None:
+            batches = getattr(self, "val_loader" if split == "val" else "test_loader")
+        evaluator = Evaluator(task="ocp")   # no metrics: `loss` only
+        lib = _lib.load()
+        dm = DeviceMetrics(self.device)
+        self.model.eval()
+        if self.ema:
+            self.ema.store()
+            self.ema.copy_to()
+        try:
+            for batch in batches:
+                batch = batch.to(self.device)
+                if hasattr(batch, "pos_relaxed"):
+                    batch.pos = batch.pos_relaxed
+                if not noised:
+                    batch = tr_so3_schedule(batch, params, tables)
+                out = self._forward_denoising(batch)
+                if getattr(batch, "tags", None) is None:
+                    raise ValueError("batch.tags is required (tag 2 marks the adsorbate)")
+                tags = batch.tags.to(self.device, torch.int32).contiguous()
+                atom_offset = atom_offsets(batch.natoms, self.device)
+                B, N = int(batch.natoms.numel()), int(batch.pos.shape[0])
+                t = {k: getattr(batch, k).to(self.device, torch.float32).contiguous()
+                     for k in ("tr_sigma", "rot_sigma", "tr_score", "rot_score")}
+                rot_norm = tables.score_norm(t["rot_sigma"].reshape(-1).cpu()).to(self.device).contiguous()
+                f1, f2 = out["positions"].contiguous(), out["positions_free"].contiguous()
+                loss = torch.empty(3, device=self.device)
+                grads = torch.empty(2, N, 3, device=self.device)   # the loss entry writes its gradients: not used here
+                scratch = torch.empty(2 * B + 16, device=self.device)
+                with torch.cuda.device(self.device):
+                    _lib.check(lib.adf_op_score_loss(
+                        f1.data_ptr(), f2.data_ptr(), tags.data_ptr(), atom_offset.data_ptr(),
+                        t["tr_sigma"].data_ptr(), t["rot_sigma"].data_ptr(), t["tr_score"].data_ptr(),
+                        t["rot_score"].data_ptr(), rot_norm.data_ptr(), loss.data_ptr(), grads[0].data_ptr(),
+                        grads[1].data_ptr(), B, scratch.data_ptr(),
+                        C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+                dm.add_value("loss", loss[:1])
+        finally:
+            if self.ema:
+                self.ema.restore()
+        return dm.all_reduce().result(evaluator.metric_names() + ["loss"])
+
     # ---------------------------------------------------------------- checkpoint ingest
     def load_checkpoint(self, checkpoint_path: str) -> None:
         """Reads ``state_dict`` (with 0-2 ``module.`` prefixes) from a reference checkpoint
@@ -340,6 +406,123 @@ class ForcesTrainer:
         grad_norm = self.optimizer.step()
         self.step += 1
         return {"loss": loss, "grad_norm": grad_norm, "skipped": False, "stop": False, "metrics": eng.metrics}
+
+    # ---------------------------------------------------------------- evaluation
+    def _objective(self) -> dict:
+        """The S2EF objective's settings: ``setup_training``'s, or its defaults where it was not called."""
+        eng = getattr(self, "train_engine", None)
+        if eng is not None:
+            return dict(norm=dict(eng.norm), energy_coefficient=eng.energy_coefficient, force_coefficient=eng.force_coefficient,
+                        train_on_free_atoms=eng.train_on_free_atoms)
+        norm = {}
+        for key in ("energy", "forces"):
+            nz = self.normalizers.get(key)
+            norm[key] = (float(nz.mean), float(nz.std)) if nz else (0.0, 1.0)
+        return dict(norm=norm, energy_coefficient=1.0, force_coefficient=30.0, train_on_free_atoms=True)
+
+    def _rank_counts(self, num_systems: int, num_atoms: int, fixed, free_only: bool):
+        """Device int64 (systems, loss atoms, 1) summed over the ranks - the divisors of DDPLoss, as ``train_step`` forms
+        them - or None for one rank."""
+        import torch.distributed as dist
+
+        if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() <= 1:
+            return None
+        if free_only and fixed is not None:
+            n_loss = (fixed == 0).sum().to(torch.int64)
+        else:
+            n_loss = torch.tensor(num_atoms, dtype=torch.int64, device=self.device)
+        counts = torch.stack([torch.tensor(num_systems, dtype=torch.int64, device=self.device), n_loss.reshape(()),
+                              torch.tensor(1, dtype=torch.int64, device=self.device)])
+        if dist.get_backend() == "gloo" and counts.is_cuda:   # test configuration: several ranks on one GPU
+            host = counts.cpu()
+            dist.all_reduce(host, op=dist.ReduceOp.SUM)
+            return host.to(self.device)
+        dist.all_reduce(counts, op=dist.ReduceOp.SUM)
+        return counts
+
+    @torch.no_grad()
+    def validate(self, batches: Optional[Iterable] = None, split: str = "val", disable_tqdm: bool = True) -> dict:
+        """``BaseTrainer.validate`` for the S2EF task (trainers/base_trainer.py:712-785 with
+        ``OCPTrainer._compute_metrics``, ocp_trainer.py:358-402): per batch the inference forward ``predict`` uses (EMA
+        weights swapped in, restored at the end), the objective of ``train_step`` without its backward, and the eight
+        metrics of ``Evaluator.task_metrics["s2ef"]`` over the free atoms, all added up on the device; the pass ends with one
+        all-reduce over the ranks and one read.  Returns ``{name: {"metric", "total", "numel"}}`` for the eight names and
+        ``loss`` (the mean of the batches' losses).  With ``force_mode == "energy_gradient"`` the forces are denormalised as
+        ``predict`` denormalises them (energy std, no mean).  A system without a free atom counts a force maximum of 0
+        (the reference raises).  ``batches``: default ``val_loader`` / ``test_loader`` by ``split``."""
+        import ctypes as C
+
+        from . import lib as _lib
+        from .evaluator import DeviceMetrics, Evaluator, atom_offsets
+
+        ensure_fitted(self._unwrapped_model, warn=True)
+        model = self._unwrapped_model
+        obj = self._objective()
+        (mean_e, std_e), (mean_f, std_f) = obj["norm"]["energy"], obj["norm"]["forces"]
+        norm_f_eval = (0.0, std_e) if getattr(model, "force_mode", "direct") == "energy_gradient" else (mean_f, std_f)
+        if batches is None:
+            batches = getattr(self, "val_loader" if split == "val" else "test_loader")
+        evaluator = Evaluator(task="s2ef")
+        lib = _lib.load()
+        dm = DeviceMetrics(self.device)
+        self.model.eval()
+        if self.ema is not None:
+            self.ema.store()
+            self.ema.copy_to()
+        try:
+            for batch in batches:
+                batch = batch.to(self.device)
+                out = self.model(batch)
+                if "forces" not in out:
+                    raise NotImplementedError("the s2ef metrics need forces (regress_forces or force_mode='energy_gradient')")
+                atom_offset = atom_offsets(batch.natoms, self.device)
+                fixed = batch.fixed.to(self.device, torch.int32).contiguous() if getattr(batch, "fixed", None) is not None else None
+                B, N = int(batch.natoms.numel()), int(batch.pos.shape[0])
+                e_pred, f_pred = out["energy"].reshape(B).contiguous(), out["forces"].reshape(N, 3).contiguous()
+                e_tgt = batch.energy.to(self.device, torch.float32).reshape(-1).contiguous()
+                f_tgt = batch.forces.to(self.device, torch.float32).reshape(N, 3).contiguous()
+                if e_tgt.numel() != B:
+                    raise ValueError(f"batch.energy has {e_tgt.numel()} entries for {B} systems")
+                free_only = obj["train_on_free_atoms"]
+                if free_only and fixed is None:
+                    raise ValueError("batch.fixed is required with train_on_free_atoms")
+                counts = self._rank_counts(B, N, fixed, free_only)
+                loss, unused = torch.empty(3, device=self.device), torch.empty(2, device=self.device)
+                grads = torch.empty(B + 3 * N, device=self.device)   # the loss entry writes dE, dF: not used here
+                scratch = torch.empty(int(lib.adf_op_s2ef_loss_scratch(B)), device=self.device)
+                with torch.cuda.device(self.device):
+                    _lib.check(lib.adf_op_s2ef_loss(
+                        e_pred.data_ptr(), f_pred.data_ptr(), e_tgt.data_ptr(), f_tgt.data_ptr(),
+                        fixed.data_ptr() if fixed is not None else None, atom_offset.data_ptr(), B,
+                        1 if free_only else 0, C.c_float(mean_e), C.c_float(std_e), C.c_float(mean_f), C.c_float(std_f),
+                        C.c_float(obj["energy_coefficient"]), C.c_float(obj["force_coefficient"]),
+                        counts.data_ptr() if counts is not None else None, loss.data_ptr(), grads.data_ptr(),
+                        grads[B:].data_ptr(), unused.data_ptr(), scratch.data_ptr(),
+                        C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+                dm.add_s2ef(e_pred, f_pred, e_tgt, f_tgt, atom_offset, fixed=fixed, free_only=True,
+                            norm_energy=(mean_e, std_e), norm_forces=norm_f_eval)
+                dm.add_value("loss", loss[:1])
+        finally:
+            if self.ema is not None:
+                self.ema.restore()
+        return dm.all_reduce().result(evaluator.metric_names() + ["loss"])
+
+    @torch.no_grad()
+    def evaluate_relaxed(self, relaxed_batch, metrics: Optional[tuple] = None) -> tuple:
+        """The ``split == "val"`` block of ``OCPTrainer.run_relaxations`` (ocp_trainer.py:607-642) for what ``ml_relax`` /
+        ``ml_relax_sharded`` return, once the DFT targets ``pos_relaxed`` and ``y_relaxed`` are attached: ``pos`` against
+        ``pos_relaxed`` over the free atoms (is2rs) and ``y`` against ``y_relaxed`` (is2re), added into two ``DeviceMetrics``.
+        ``metrics``: the pair a previous call returned (None: two fresh ones); returns ``(is2rs, is2re)``.  Nothing is read
+        back: ``result(Evaluator(task).metric_names())`` of each, after an ``all_reduce()`` when several ranks relaxed."""
+        from .evaluator import DeviceMetrics, atom_offsets
+
+        is2rs, is2re = metrics if metrics is not None else (DeviceMetrics(self.device), DeviceMetrics(self.device))
+        b = relaxed_batch.to(self.device)
+        fixed = b.fixed.to(self.device, torch.int32).contiguous() if getattr(b, "fixed", None) is not None else None
+        B = int(b.natoms.numel())
+        is2rs.add_is2rs(b.pos, b.pos_relaxed, b.cell.reshape(B, 3, 3), atom_offsets(b.natoms, self.device), fixed=fixed)
+        is2re.add_is2re(b.y.reshape(-1), b.y_relaxed.reshape(-1))
+        return is2rs, is2re
 
     @torch.no_grad()
     def predict(self, data_loader, per_image: bool = False, results_file=None, disable_tqdm: bool = False):

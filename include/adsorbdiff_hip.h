@@ -535,6 +535,61 @@ int32_t adf_op_adamw_step(float* p, const float* g, float* m, float* v, float* e
                           float max_norm, float lr, float beta1, float beta2, float eps, float weight_decay, int32_t step,
                           float ema_decay, void* stream);
 
+/* ---- Evaluation metrics (csrc/evaluate.hip): modules/evaluator.py for the tasks "s2ef", "is2rs", "is2re", and the
+ * per-batch loss of BaseTrainer.validate (trainers/base_trainer.py:712-785), accumulated on the device.
+ * Accumulator: caller-owned device memory, double total[ADF_EVAL_SLOTS] and int64_t numel[ADF_EVAL_SLOTS], indexed by the
+ * enum below (the reference's {"total", "numel"} of a metric; "metric" = total / numel is the reader's).  Every entry
+ * ADDS into it and the caller zeroes it, so a pass over many batches needs no device-to-host read.  One accumulator per
+ * Evaluator: "s2ef" and "is2re" both write ADF_EVAL_ENERGY_MAE.
+ * One wave per system writes the system's partial sums in a fixed lane order, one thread adds the systems in ascending order
+ * and adds into the accumulator; no float atomics, run-to-run bit-identical.  Every per-element term is formed in float32
+ * with separately rounded operations, as the reference's float32 tensors form it; every sum is carried in float64.
+ * scratch: adf_eval_scratch(B) doubles. */
+enum {
+    ADF_EVAL_ENERGY_MAE = 0,
+    ADF_EVAL_FORCESX_MAE = 1,
+    ADF_EVAL_FORCESY_MAE = 2,
+    ADF_EVAL_FORCESZ_MAE = 3,
+    ADF_EVAL_FORCES_MAE = 4,
+    ADF_EVAL_FORCES_COSINE_SIMILARITY = 5,
+    ADF_EVAL_FORCES_MAGNITUDE_ERROR = 6,
+    ADF_EVAL_ENERGY_FORCES_WITHIN_THRESHOLD = 7,
+    ADF_EVAL_POSITIONS_AVERAGE_DISTANCE_WITHIN_THRESHOLD = 8,
+    ADF_EVAL_POSITIONS_MAE = 9,
+    ADF_EVAL_POSITIONS_MSE = 10,
+    ADF_EVAL_ENERGY_MSE = 11,
+    ADF_EVAL_ENERGY_WITHIN_THRESHOLD = 12,
+    ADF_EVAL_LOSS = 13,
+    ADF_EVAL_SLOTS = 14
+};
+int64_t adf_eval_scratch(int32_t B);
+/* Evaluator.task_metrics["s2ef"] as OCPTrainer._compute_metrics feeds it (trainers/ocp_trainer.py:358-402): E_pred [B] /
+ * F_pred [N,3] are normalised predictions and are denormalised here (x * std + mean), E_tgt / F_tgt are in target units; the
+ * force metrics run over the atoms with fixed == 0 when free_only (fixed == NULL: no atom is fixed), else over all atoms.
+ * With M atoms in scope: energy_mae (numel B), forcesx/y/z_mae (M), forces_mae (3M), forces_cosine_similarity (M; per-atom
+ * torch.cosine_similarity with eps 1e-8, 0 for an all-zero row), forces_magnitude_error (M; | ||p|| - ||t|| |) and
+ * energy_forces_within_threshold (B; total = systems with |dE| < 0.02 and every in-scope |dF component| < 0.03).
+ * Departure: a system with no atom in scope makes the reference raise (.max() of an empty slice); here its force maximum
+ * counts as 0.  N: rows of F_pred / F_tgt / fixed; atom_offset is clamped to it. */
+int32_t adf_eval_s2ef(const float* E_pred, const float* F_pred, const float* E_tgt, const float* F_tgt,
+                      const int32_t* fixed, const int32_t* atom_offset, int32_t B, int32_t N, int32_t free_only,
+                      float mean_E, float std_E, float mean_F, float std_F, double* total, int64_t* numel, double* scratch,
+                      void* stream);
+/* Evaluator.task_metrics["is2rs"] over the atoms with fixed == 0 (the split == "val" block of run_relaxations,
+ * trainers/ocp_trainer.py:607-642): positions_mae and positions_mse of the plain difference (numel 3M, no minimum image, as
+ * the reference) and average_distance_within_threshold: per system the mean over its free atoms of the minimum-image
+ * distance (evaluator.py min_diff: fractional = d . inv(cell), % 1.0 twice, > 0.5 -> -1, back through cell [B,3,3], rows =
+ * lattice vectors, all three directions periodic), total = thresholds [T] (device, float64: numpy.arange(0.01, 0.5, 0.001)
+ * built on the host) that the mean lies strictly below, numel = B * T.  A system without free atoms has a NaN mean and
+ * counts for none.  N: rows of pos_pred / pos_tgt / fixed; atom_offset is clamped to it. */
+int32_t adf_eval_is2rs(const float* pos_pred, const float* pos_tgt, const float* cell, const int32_t* fixed,
+                       const int32_t* atom_offset, int32_t B, int32_t N, const double* thresholds, int32_t T,
+                       double* total, int64_t* numel, double* scratch, void* stream);
+/* Evaluator.task_metrics["is2re"]: energy_mae, energy_mse and energy_within_threshold (|dE| < 0.02), numel B each. */
+int32_t adf_eval_is2re(const float* E_pred, const float* E_tgt, int32_t B, double* total, int64_t* numel, void* stream);
+/* Evaluator.update with a plain number: total[slot] += value[0] (a device float), numel[slot] += 1. */
+int32_t adf_eval_add(const float* value, int32_t slot, double* total, int64_t* numel, void* stream);
+
 /* ---- EquiformerV2 denoiser (BASELINE config 4).  Replaces
  * EquiformerV2S_OC20_DenoisingPos.forward(data) (models/equiformer_v2/equiformer_v2_denoising.py:185-318) for the
  * configuration the repository ships (configs/denoising/eqv2_so3.yml): one resolution, layer_norm_sh, SiLU attention
