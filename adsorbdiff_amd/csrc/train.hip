@@ -1118,6 +1118,54 @@ extern "C" int32_t adf_op_score_loss(const float* f1, const float* f2, const int
     return ADF_OK;
 }
 
+// DenoisingTrainer._compute_loss without so3_denoising (sde_denoising_trainer.py:675-701): the translation term alone, one
+// wave per system.  loss_part[b] = this system's share of L_tr; df1 [N,3] written (zero off the adsorbate).
+__global__ __launch_bounds__(64) void tr_loss_tr_kernel(const float* __restrict__ f1, const int32_t* __restrict__ tags,
+                                                        const int32_t* __restrict__ atom_offset,
+                                                        const float* __restrict__ tr_sigma, const float* __restrict__ tr_score,
+                                                        float* __restrict__ loss_part, float* __restrict__ df1, int B) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int a0 = atom_offset[b], a1 = atom_offset[b + 1];
+    float s[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int a = a0 + lane; a < a1; a += 64)
+        if (tags[a] == 2) {
+            for (int k = 0; k < 3; ++k) s[k] += f1[3 * a + k];
+            s[3] += 1.f;
+        }
+    for (int i = 0; i < 4; ++i) s[i] = tr_wsum(s[i]);
+    const float cnt = fmaxf(s[3], 1.f), st = tr_sigma[b];
+    const float inv = 1.0f / (3.0f * (float)B);
+    float lt = 0.f, g1[3];
+    for (int k = 0; k < 3; ++k) {
+        const float p = k < 2 ? s[k] / cnt / st : 0.f;
+        const float d = p - tr_score[3 * b + k];
+        lt += d * d * st * st;
+        g1[k] = k < 2 ? 2.f * d * st * st * inv / (st * cnt) : 0.f;
+    }
+    if (lane == 0) loss_part[b] = lt * inv;
+    for (int a = a0 + lane; a < a1; a += 64) {
+        const bool ads = tags[a] == 2;
+        for (int k = 0; k < 3; ++k) df1[3 * a + k] = ads ? g1[k] : 0.f;
+    }
+}
+__global__ void tr_loss_tr_sum_kernel(const float* __restrict__ part, float* __restrict__ loss, int B) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        float lt = 0.f;
+        for (int b = 0; b < B; ++b) lt += part[b];
+        loss[0] = lt; loss[1] = lt; loss[2] = 0.f;
+    }
+}
+// loss [3] = (total, translation term, 0); scratch: B floats
+extern "C" int32_t adf_op_score_loss_tr(const float* f1, const int32_t* tags, const int32_t* atom_offset,
+                                        const float* tr_sigma, const float* tr_score, float* loss, float* df1, int32_t B,
+                                        float* scratch, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(tr_loss_tr_kernel, dim3(B), dim3(64), 0, s, f1, tags, atom_offset, tr_sigma, tr_score, scratch, df1, B);
+    hipLaunchKernelGGL(tr_loss_tr_sum_kernel, dim3(1), dim3(64), 0, s, scratch, loss, B);
+    TR_CHECK_LAUNCH();
+    return ADF_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ optimizer
 // One fused pass per parameter tensor: global-norm clip factor (from a device scalar), AdamW (torch.optim.AdamW
 // semantics: decoupled weight decay, bias-corrected moments) and the EMA shadow update (base_trainer.py:803-820,

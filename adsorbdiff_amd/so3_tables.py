@@ -142,7 +142,23 @@ class Igso3Tables:
             nrm[b] = np.sqrt(xb.dot(xb))                                   # np.linalg.norm of a vector
             u[b] = ub
             j[b] = np.searchsorted(self.cdf[idx[b]], ub, side="right") - 1  # last k with cdf[k] <= u
-        rows = np.arange(B)
+        return self._vecs_and_scores(idx, x, nrm, u, j)
+
+    def vecs_and_scores_from_draws(self, eps: np.ndarray, x: np.ndarray, u: np.ndarray):
+        """``sample_and_score_vecs`` with the draws supplied: ``x`` [B,3] the normals of the axis, ``u`` [B] the uniforms of
+        the CDF look-up.  Consumes no random stream; the same arithmetic, so the same bits from the same draws."""
+        eps = np.asarray(eps, dtype=np.float64).reshape(-1)
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, 3)
+        u = np.asarray(u, dtype=np.float64).reshape(-1)
+        idx = self.eps_index(eps)
+        nrm = np.array([np.sqrt(xb.dot(xb)) for xb in x])
+        j = np.array([np.searchsorted(self.cdf[idx[b]], u[b], side="right") - 1 for b in range(eps.shape[0])],
+                     dtype=np.int64)
+        return self._vecs_and_scores(idx, x, nrm, u, j)
+
+    def _vecs_and_scores(self, idx, x, nrm, u, j):
+        """The look-ups of all systems at once: omega by the inverse CDF (j: last k with cdf[k] <= u), the vector, its score."""
+        n = self.omegas.shape[0]
         jc = np.clip(j, 0, n - 2)
         cdf0, cdf1 = self.cdf[idx, jc], self.cdf[idx, jc + 1]
         omega = self._lerp(u, cdf0, cdf1, self.omegas[jc], self.omegas[jc + 1])
@@ -153,8 +169,23 @@ class Igso3Tables:
         kc = np.clip(k, 0, n - 2)
         sc = self._lerp(om, self.omegas[kc], self.omegas[kc + 1], self.score[idx, kc], self.score[idx, kc + 1])
         sc = np.where(k < 0, self.score[idx, 0], np.where(om >= self.omegas[n - 1], self.score[idx, n - 1], sc))
-        del rows
         return vec, sc[:, None] * vec / om[:, None]
+
+    def on_device(self, device) -> dict:
+        """The tables as float64 device tensors for csrc/noising.hip (``omegas``, ``exp_score_norm`` and, where this object
+        holds them, ``cdf`` and ``score``): uploaded once per object and device."""
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        cache = self.__dict__.setdefault("_device_tables", {})
+        if device not in cache:
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(device)  # noqa: E731
+            t = {"omegas": up(self.omegas), "exp_score_norm": up(self.exp_score_norm)}
+            for k in ("cdf", "score"):
+                if getattr(self, k) is not None:
+                    t[k] = up(getattr(self, k))
+            cache[device] = t
+        return cache[device]
 
     def score_norm(self, eps: torch.Tensor) -> torch.Tensor:
         return torch.from_numpy(self.exp_score_norm[self.eps_index(eps.detach().cpu().numpy())]).float()

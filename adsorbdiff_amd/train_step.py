@@ -375,18 +375,21 @@ class PaiNNTrainStep(_PaiNNStepBase):
     UNUSED_PREFIXES = ("out_energy.",)
 
     def __init__(self, model, device="cuda:0", igso3: Optional[Igso3Tables] = None) -> None:
-        if not model.so3_denoising:
-            raise NotImplementedError("the training step is written for so3_denoising=True (two heads)")
         super().__init__(model, device)
-        self.igso3 = igso3 or Igso3Tables.shared()
+        # one head (so3_denoising=False): the translation term alone; the rotation tables are neither needed nor loaded
+        self.two_heads = bool(model.so3_denoising)
+        self.igso3 = (igso3 or Igso3Tables.shared()) if self.two_heads else igso3
 
     # ------------------------------------------------------------------ the step
     def loss_and_grad(self, batch, targets: dict, grads_ready=None) -> torch.Tensor:
         """``batch``: noised batch on the device (pos, atomic_numbers, tags, batch, natoms, cell); ``targets``: tr_sigma
-        [B,1], rot_sigma [B,1], tr_score [B,3], rot_score [B,3] (what tr_so3_schedule attaches to the batch).
-        Accumulates into ``param.grad`` (call zero_grad first, like optimizer.zero_grad) and returns the device tensor
-        (loss, translation term, rotation term).  ``grads_ready(names)`` (optional) is called as soon as the gradients of a
-        group of parameters are final: both heads, then each layer from the last to the first, then the embedding."""
+        [B,1], rot_sigma [B,1], tr_score [B,3], rot_score [B,3] (what tr_so3_schedule attaches to the batch) and, optionally,
+        rot_norm [B] (the expected score norm of every rot_sigma, as the device noising returns it; absent: looked up on
+        the device).  A one-head model (``so3_denoising=False``) takes tr_sigma and tr_score only (what
+        ads_COM_gaussian_schedule attaches).  Accumulates into ``param.grad`` (call zero_grad first, like
+        optimizer.zero_grad) and returns the device tensor (loss, translation term, rotation term; 0 for one head).
+        ``grads_ready(names)`` (optional) is called as soon as the gradients of a group of parameters are final: the
+        head(s), then each layer from the last to the first, then the embedding."""
         m, ops, lib = self.model, self.ops, self.lib
         H = m.hidden_channels
         c = self._begin(batch)
@@ -395,37 +398,49 @@ class PaiNNTrainStep(_PaiNNStepBase):
             raise ValueError("batch.tags is required (tag 2 marks the adsorbate)")
         s = ops.s
         self._bind_gradients(c)
+        hnames = ("out_forces", "out_forces2") if self.two_heads else ("out_forces",)
 
         # ---------------- forward with saved activations
         x, vec, saved, rbf = self._trunk_forward(c)
         heads = []
         outs = []
-        for hname in ("out_forces", "out_forces2"):
+        for hname in hnames:
             hs, out = self._head_forward(c, hname, x, vec)
             heads.append(hs)
             outs.append(out)
-        f1, f2 = outs
 
-        # ---------------- loss and its gradient with respect to the two heads' outputs
-        t = {k: targets[k].to(self.dev, torch.float32).contiguous() for k in ("tr_sigma", "rot_sigma", "tr_score", "rot_score")}
-        rot_norm = self.igso3.score_norm(t["rot_sigma"].reshape(-1).cpu()).to(self.dev).contiguous()
+        # ---------------- loss and its gradient with respect to the heads' outputs
+        keys = ("tr_sigma", "rot_sigma", "tr_score", "rot_score") if self.two_heads else ("tr_sigma", "tr_score")
+        t = {k: targets[k].to(self.dev, torch.float32).contiguous() for k in keys}
         loss = ops.new(3)
-        df1, df2 = ops.new(N, 3), ops.new(N, 3)
-        _lib.check(lib.adf_op_score_loss(f1.data_ptr(), f2.data_ptr(), prep.tags.data_ptr(), prep.atom_offset.data_ptr(),
-                                         t["tr_sigma"].data_ptr(), t["rot_sigma"].data_ptr(), t["tr_score"].data_ptr(),
-                                         t["rot_score"].data_ptr(), rot_norm.data_ptr(), loss.data_ptr(), df1.data_ptr(),
-                                         df2.data_ptr(), B, ops.scratch(2 * B + 16).data_ptr(), s()))
+        douts = [ops.new(N, 3) for _ in hnames]
+        if self.two_heads:
+            rot_norm = targets.get("rot_norm")
+            if rot_norm is None:
+                from .noising import device_score_norm
+
+                rot_norm = device_score_norm(t["rot_sigma"], self.igso3, self.dev)
+            rot_norm = rot_norm.to(self.dev, torch.float32).reshape(-1).contiguous()
+            _lib.check(lib.adf_op_score_loss(outs[0].data_ptr(), outs[1].data_ptr(), prep.tags.data_ptr(),
+                                             prep.atom_offset.data_ptr(), t["tr_sigma"].data_ptr(), t["rot_sigma"].data_ptr(),
+                                             t["tr_score"].data_ptr(), t["rot_score"].data_ptr(), rot_norm.data_ptr(),
+                                             loss.data_ptr(), douts[0].data_ptr(), douts[1].data_ptr(), B,
+                                             ops.scratch(2 * B + 16).data_ptr(), s()))
+        else:
+            _lib.check(lib.adf_op_score_loss_tr(outs[0].data_ptr(), prep.tags.data_ptr(), prep.atom_offset.data_ptr(),
+                                                t["tr_sigma"].data_ptr(), t["tr_score"].data_ptr(), loss.data_ptr(),
+                                                douts[0].data_ptr(), B, ops.scratch(B + 16).data_ptr(), s()))
 
         # ---------------- backward: heads
         dx = torch.zeros(N, H, device=self.dev)
         dvec = torch.zeros(N, 3, H, device=self.dev)
-        for hname, hs, dout in (("out_forces", heads[0], df1), ("out_forces2", heads[1], df2)):
+        for hname, hs, dout in zip(hnames, heads, douts):
             self._head_backward(c, hname, hs, dout, dx, dvec)
         if grads_ready is not None:
-            grads_ready(["out_forces.", "out_forces2."])
+            grads_ready([h + "." for h in hnames])
         # ---------------- backward: layers, last to first, then the embedding
         self._trunk_backward(c, dx, dvec, saved, rbf, grads_ready)
-        self.last_outputs = (f1, f2)
+        self.last_outputs = tuple(outs)
         return loss
 
 

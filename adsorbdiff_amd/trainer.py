@@ -83,26 +83,64 @@ class DenoisingTrainer:
 
     # ---------------------------------------------------------------- training
     def setup_training(self, denoising_pos_params: dict, lr: float = 1e-3, weight_decay: float = 0.001,
-                       clip_grad_norm: float = 100.0, ema_decay: float = 0.999, tables=None) -> None:
+                       clip_grad_norm: float = 100.0, ema_decay: float = 0.999, tables=None,
+                       noise_on_device: bool = False, noise_seed: int = 0) -> None:
         """Optimizer / EMA / noising parameters; defaults = configs/denoising/painn_so3.yml:56-83 (AdamW, weight decay
-        1e-3 except no_weight_decay() names, clip 100, EMA 0.999)."""
+        1e-3 except no_weight_decay() names, clip 100, EMA 0.999).  ``noise_on_device``: ``train_step`` and ``validate``
+        noise through ``noising.DeviceNoiser`` (counter-based draws keyed by ``noise_seed``, the step number and
+        ``noising.noise_keys(batch)``: no host round trip, and a system's noise does not depend on its batch or rank);
+        off (default): the reference's stream order on the host."""
         from .exponential_moving_average import ExponentialMovingAverage
         from .train_step import FusedAdamW, PaiNNTrainStep
 
         self.denoising_pos_params = dict(denoising_pos_params)
         self.train_engine = PaiNNTrainStep(self._unwrapped_model, self.device, igso3=tables)
+        self.noiser = None
+        if noise_on_device:
+            from .noising import DeviceNoiser
+
+            self.noiser = DeviceNoiser(self.denoising_pos_params, self.train_engine.igso3, self.device, seed=noise_seed)
+        self.noise_step = 0
         if ema_decay:
             self.ema = ExponentialMovingAverage(self._unwrapped_model.parameters(), ema_decay)
         self.optimizer = FusedAdamW(self._unwrapped_model, lr=lr, weight_decay=weight_decay, max_grad_norm=clip_grad_norm,
                                     ema=self.ema)
         self.step = 0
 
-    def train_step(self, batch, noised: bool = False) -> dict:
+    def _noise(self, batch, params, tables, noise_step=None, draws=None):
+        """The schedule ``config["model_attributes"]["so3_denoising"]`` selects, as the reference's loop does
+        (sde_denoising_trainer.py:416-421): on the device where ``setup_training`` asked for it, else the host mirrors.
+        The device noising numbers its calls with ``self.noise_step`` (``noise_step`` overrides; ``draws`` replaces the
+        generator)."""
+        from .noising import ads_COM_gaussian_schedule, tr_so3_schedule
+
+        so3 = self.config["model_attributes"].get("so3_denoising", False)
+        noiser = getattr(self, "noiser", None)
+        if noiser is None:
+            if draws is not None or noise_step is not None:
+                raise ValueError("draws= / noise_step= need setup_training(noise_on_device=True)")
+            return tr_so3_schedule(batch, params, tables) if so3 else ads_COM_gaussian_schedule(batch, params)
+        if noise_step is None and draws is None:   # supplied rows or a supplied number leave the counter alone
+            noise_step = self.noise_step
+            self.noise_step += 1
+        return (noiser.tr_so3 if so3 else noiser.com)(batch, step=noise_step, draws=draws)
+
+    def _score_targets(self, batch) -> dict:
+        keys = ("tr_sigma", "rot_sigma", "tr_score", "rot_score") \
+            if self.config["model_attributes"].get("so3_denoising", False) else ("tr_sigma", "tr_score")
+        targets = {k: getattr(batch, k) for k in keys}
+        if "rot_sigma" in targets and getattr(batch, "rot_norm", None) is not None:
+            targets["rot_norm"] = batch.rot_norm   # from the device noising: the loss needs no look-up of its own
+        return targets
+
+    def train_step(self, batch, noised: bool = False, noise_step: Optional[int] = None, draws=None) -> dict:
         """One optimisation step on ``batch`` (clean positions unless ``noised``).  Multi-GPU: one process per GPU, each
-        with its own batch; gradients are averaged with a bucketed all-reduce (RCCL over xGMI under backend nccl)."""
+        with its own batch; gradients are averaged with a bucketed all-reduce (RCCL over xGMI under backend nccl).
+        The noising and the loss follow the model: two heads, ``tr_so3_schedule`` and both score terms; one head
+        (``so3_denoising=False``), ``ads_COM_gaussian_schedule`` and the translation term.  ``noise_step`` / ``draws``:
+        with ``noise_on_device``, the step number of the draws (default: this trainer's counter) or the rows themselves."""
         import torch.distributed as dist
 
-        from .noising import tr_so3_schedule
         from .train_step import GradientReducer
 
         self.model.train()
@@ -110,8 +148,8 @@ class DenoisingTrainer:
         if hasattr(batch, "pos_relaxed"):
             batch.pos = batch.pos_relaxed
         if not noised:
-            batch = tr_so3_schedule(batch, self.denoising_pos_params, self.train_engine.igso3)
-        targets = {k: getattr(batch, k) for k in ("tr_sigma", "rot_sigma", "tr_score", "rot_score")}
+            batch = self._noise(batch, self.denoising_pos_params, self.train_engine.igso3, noise_step, draws)
+        targets = self._score_targets(batch)
         self.train_engine.zero_grad()
         world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         # the buckets' all-reduces are issued from inside the backward (heads, then layer by layer) and overlap with it
@@ -157,26 +195,28 @@ class DenoisingTrainer:
     # ---------------------------------------------------------------- evaluation
     @torch.no_grad()
     def validate(self, batches: Optional[Iterable] = None, noised: bool = False, split: str = "val",
-                 disable_tqdm: bool = True) -> dict:
+                 disable_tqdm: bool = True, noise_step: Optional[int] = None) -> dict:
         """The reference's ``validate`` (sde_denoising_trainer.py:286-368): per batch ``pos_relaxed`` for the positions,
         ``tr_so3_schedule`` (unless ``noised``: the batch already carries its noise and scores), the inference forward and the
         score loss without a backward.  This trainer evaluates under the task "ocp", which has no metrics, so the result is
         ``{"loss": {"metric", "total", "numel"}}``: the mean over the batches, summed over the ranks.  The losses are added
-        up on the device; the pass ends with one all-reduce and one read (per batch, the look-up of the rotation score's
-        norm reads ``rot_sigma`` on the host, as in ``train_step``).  ``batches``: default ``val_loader`` / ``test_loader``
-        by ``split``; ``disable_tqdm`` is accepted for the reference's signature, there is no progress bar."""
+        up on the device; the pass ends with one all-reduce and one read (the rotation score's norm is looked up on the
+        device).  A one-head model (``so3_denoising=False``) is noised by ``ads_COM_gaussian_schedule`` and scored by the
+        translation term alone.  With ``setup_training(noise_on_device=True)`` the batches are noised on the device, batch i
+        with step number ``noise_step + i`` (default: the trainer's counter, which advances).  ``batches``: default
+        ``val_loader`` / ``test_loader`` by ``split``; ``disable_tqdm`` is accepted for the reference's signature, there is
+        no progress bar."""
         import ctypes as C
 
         from . import lib as _lib
         from .evaluator import DeviceMetrics, Evaluator, atom_offsets
-        from .noising import tr_so3_schedule
+        from .noising import device_score_norm
         from .so3_tables import Igso3Tables
 
-        if not self.config["model_attributes"].get("so3_denoising", False):
-            raise NotImplementedError("validate offers the translation + rotation score loss (so3_denoising=True)")
+        so3 = bool(self.config["model_attributes"].get("so3_denoising", False))
         ensure_fitted(self._unwrapped_model, warn=True)
         engine = getattr(self, "train_engine", None)
-        tables = engine.igso3 if engine is not None else Igso3Tables.shared()
+        tables = engine.igso3 if engine is not None else (Igso3Tables.shared() if so3 else None)
         params = getattr(self, "denoising_pos_params", None) or self.config["optim"].get("denoising_pos_params")
         if batches is None:
             batches = getattr(self, "val_loader" if split == "val" else "test_loader")
@@ -188,32 +228,39 @@ class DenoisingTrainer:
             self.ema.store()
             self.ema.copy_to()
         try:
-            for batch in batches:
+            for i, batch in enumerate(batches):
                 batch = batch.to(self.device)
                 if hasattr(batch, "pos_relaxed"):
                     batch.pos = batch.pos_relaxed
                 if not noised:
-                    batch = tr_so3_schedule(batch, params, tables)
+                    batch = self._noise(batch, params, tables, None if noise_step is None else noise_step + i)
                 out = self._forward_denoising(batch)
                 if getattr(batch, "tags", None) is None:
                     raise ValueError("batch.tags is required (tag 2 marks the adsorbate)")
                 tags = batch.tags.to(self.device, torch.int32).contiguous()
                 atom_offset = atom_offsets(batch.natoms, self.device)
                 B, N = int(batch.natoms.numel()), int(batch.pos.shape[0])
-                t = {k: getattr(batch, k).to(self.device, torch.float32).contiguous()
-                     for k in ("tr_sigma", "rot_sigma", "tr_score", "rot_score")}
-                rot_norm = tables.score_norm(t["rot_sigma"].reshape(-1).cpu()).to(self.device).contiguous()
-                f1, f2 = out["positions"].contiguous(), out["positions_free"].contiguous()
+                t = {k: v.to(self.device, torch.float32).contiguous() for k, v in self._score_targets(batch).items()}
+                f1 = out["positions"].contiguous()
                 loss = torch.empty(3, device=self.device)
                 grads = torch.empty(2, N, 3, device=self.device)   # the loss entry writes its gradients: not used here
                 scratch = torch.empty(2 * B + 16, device=self.device)
-                with torch.cuda.device(self.device):
-                    _lib.check(lib.adf_op_score_loss(
-                        f1.data_ptr(), f2.data_ptr(), tags.data_ptr(), atom_offset.data_ptr(),
-                        t["tr_sigma"].data_ptr(), t["rot_sigma"].data_ptr(), t["tr_score"].data_ptr(),
-                        t["rot_score"].data_ptr(), rot_norm.data_ptr(), loss.data_ptr(), grads[0].data_ptr(),
-                        grads[1].data_ptr(), B, scratch.data_ptr(),
-                        C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+                stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+                if so3:
+                    rot_norm = t["rot_norm"].reshape(-1) if "rot_norm" in t else \
+                        device_score_norm(t["rot_sigma"], tables, self.device)
+                    f2 = out["positions_free"].contiguous()
+                    with torch.cuda.device(self.device):
+                        _lib.check(lib.adf_op_score_loss(
+                            f1.data_ptr(), f2.data_ptr(), tags.data_ptr(), atom_offset.data_ptr(),
+                            t["tr_sigma"].data_ptr(), t["rot_sigma"].data_ptr(), t["tr_score"].data_ptr(),
+                            t["rot_score"].data_ptr(), rot_norm.data_ptr(), loss.data_ptr(), grads[0].data_ptr(),
+                            grads[1].data_ptr(), B, scratch.data_ptr(), stream))
+                else:
+                    with torch.cuda.device(self.device):
+                        _lib.check(lib.adf_op_score_loss_tr(
+                            f1.data_ptr(), tags.data_ptr(), atom_offset.data_ptr(), t["tr_sigma"].data_ptr(),
+                            t["tr_score"].data_ptr(), loss.data_ptr(), grads[0].data_ptr(), B, scratch.data_ptr(), stream))
                 dm.add_value("loss", loss[:1])
         finally:
             if self.ema:

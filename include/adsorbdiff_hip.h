@@ -495,6 +495,43 @@ int32_t adf_op_copy_rows(const float* src, int32_t lds_, float* dst, int32_t ldd
 int32_t adf_op_score_loss(const float* f1, const float* f2, const int32_t* tags, const int32_t* atom_offset,
                           const float* tr_sigma, const float* rot_sigma, const float* tr_score, const float* rot_score,
                           const float* rot_norm, float* loss, float* df1, float* df2, int32_t B, float* scratch, void* stream);
+/* The same objective without so3_denoising (sde_denoising_trainer.py:675-701, the one-head model the translation-only
+ * samplers run): L = mean_{b,k} (mean_ads(f1) / sigma - s)^2 sigma^2 with the z component of the prediction zeroed;
+ * loss [3] = (L, L, 0); df1 [N,3] is written for all rows (zero off the adsorbate).  One wave per system, sums in a fixed
+ * order; scratch: B floats. */
+int32_t adf_op_score_loss_tr(const float* f1, const int32_t* tags, const int32_t* atom_offset, const float* tr_sigma,
+                             const float* tr_score, float* loss, float* df1, int32_t B, float* scratch, void* stream);
+
+/* ---- Forward noising of a training batch on the device (csrc/noising.hip; adsorbdiff_amd/noising.py DeviceNoiser).
+ * Counter-based draws: row b of out (double [B,8]) depends on (seed, step, keys[b]) alone.  Philox4x32-10 with key
+ * (seed lo, seed hi) and counters (key lo, key hi, step, j), j = 0, 1; a word w becomes u = (w + 0.5) 2^-32; the words of
+ * j = 0 are (u_t, u_om, a0, a1), of j = 1 (a2, a3, a4, a5); Box-Muller in double on (a0,a1), (a2,a3), (a4,a5):
+ * r = sqrt(-2 ln a_2p), n_2p = r cos(2 pi a_2p+1), n_2p+1 = r sin(2 pi a_2p+1).  Row = (u_t, n0..n5, u_om): n0..2 the COM
+ * noise, n3..5 the rotation axis before normalisation. */
+int32_t adf_noise_draws(int64_t seed, int32_t step, const int64_t* keys, int32_t B, double* out, void* stream);
+/* tr_so3_schedule (sde_denoising_trainer.py:67-135 with pbc_correction :45-64 and rot_utils.py:18-98, 226-253) given one row
+ * of draws per system: t = float(u_t), both sigmas in float32, the COM noise wrapped to its minimum image (fractional
+ * solve in double), rot_update = axis / |axis| * omega(u_om) and its score by the table look-ups of rot_utils.py in
+ * double (nearest eps row, np.interp), the quaternion rotation about the adsorbate's centre, the COM shift and the +1 A
+ * lift.  The adsorbate is every atom of tag 2 in [atom_offset[b], atom_offset[b+1]).  pos_out [N,3] is a copy of pos with
+ * the adsorbate rows replaced (pos_out != pos); tr_sigma, rot_sigma, rot_norm [B]; tr_score, rot_score, noise_vec [B,3];
+ * rot_norm is exp_score_norm of the system's eps row (rot_utils.py:256-264), what the loss divides by.  Tables: device
+ * double, omegas [n_omega], cdf and score [n_eps, n_omega], exp_score_norm [n_eps].  One wave per system, no atomics. */
+int32_t adf_noise_tr_so3(const float* pos, const float* cell, const int32_t* tags, const int32_t* atom_offset, int32_t B,
+                         int32_t N, const double* draws, float ads_std_low, float ads_std_high, float rot_std_low,
+                         float rot_std_high, const double* omegas, const double* cdf, const double* score,
+                         const double* exp_score_norm, int32_t n_eps, int32_t n_omega, float* pos_out, float* tr_sigma,
+                         float* rot_sigma, float* tr_score, float* rot_score, float* noise_vec, float* rot_norm,
+                         void* stream);
+/* ads_COM_gaussian_schedule (sde_denoising_trainer.py:138-177) from (u_t, n0, n1) of the same rows: the noised centre is
+ * wrapped into the cell as the samplers wrap it (float32 solve with cell, modulo 1 twice, back with cell . f; the COLUMNS
+ * of cell act as lattice vectors), lifted by 1 A, and every adsorbate atom is set to it. */
+int32_t adf_noise_com(const float* pos, const float* cell, const int32_t* tags, const int32_t* atom_offset, int32_t B,
+                      int32_t N, const double* draws, float ads_std_low, float ads_std_high, float* pos_out,
+                      float* tr_sigma, float* tr_score, float* noise_vec, void* stream);
+/* rot_utils.score_norm (rot_utils.py:256-264) alone: out[b] = table[eps_index(rot_sigma[b])], table = exp_score_norm
+ * [n_eps] on the device; for batches that arrive already noised. */
+int32_t adf_igso3_score_norm(const float* rot_sigma, const double* table, int32_t n_eps, int32_t B, float* out, void* stream);
 /* S2EF objective of the force field: OCPTrainer._compute_loss (trainers/ocp_trainer.py:308-356) with DDPLoss
  * (modules/loss.py:48-102) over nn.L1Loss for the energy ("mae") and L2MAELoss for the forces ("l2mae")
  * (utils/utils.py:1219-1260, 1319-1331); E_pred [B] / F_pred [N,3] are normalised predictions, E_tgt / F_tgt in target units:
