@@ -44,6 +44,8 @@ adf_tune adf_tune_from_env() {
     t.eqv2_gemm_tile256 = (gt && atoi(gt) == 128) ? 0 : 1;
     t.eqv2_rotin_generic = getenv("ADF_EQV2_ROTIN_GENERIC") != nullptr;
     t.eqv2_rotout_generic = getenv("ADF_EQV2_ROTOUT_GENERIC") != nullptr;
+    const char* r4 = getenv("ADF_GEMM_ROWS4");
+    t.gemm_rows4 = r4 ? (atoi(r4) & 3) : 3;   // both bits on: each measured faster alone and together (profiles/NOTES.md)
     return t;
 }
 const adf_tune& adf_tune_process() {

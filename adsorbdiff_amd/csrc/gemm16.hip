@@ -19,6 +19,10 @@
 // Global loads are 16 B per lane, prefetched one K-tile ahead in registers; XCD-aware tile map as in
 // gemm.hip (all N-tiles of an M-panel on one XCD's L2).  Every epilogue transposes the accumulators through the
 // idle staging LDS so that global accesses are 16 B per lane, and issues all its loads before its first store.
+// That tile is the LDS-staged form (rounds 1-5), still what shapes without a fragment image run.  The sampler's products stream
+// their weights as register fragments (WR, kernel comment) and run as four waves laid out 1(M) x 4(N), two workgroups per CU:
+// 96 x 256 tiles (plain, vec_proj, vector-norm products) and 64 x 384 tiles (x_proj.2 / xvec_proj.2 with their fused
+// epilogues); adf_tune::gemm_rows4 = 0 selects the eight-wave 192 x 256 resp. four-wave 2(M) x 2(N) 128 x 192 tiles before them.
 #include <stdlib.h>
 
 #include "common.h"
@@ -44,6 +48,11 @@ typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 #endif
 #ifndef G16_WDEEP
 #define G16_WDEEP 1   // WR kernels request their weight fragments two k-steps ahead (four register sets); 0: one k-step (node products 1699 -> 1681 ms per pass with 1)
+#endif
+#ifndef G16_START_DELAY
+#define G16_START_DELAY 0   // timing experiment (same results): the four-wave 1(M) x 4(N) workgroups that take the second residency
+                            // slot of their CU in the first round (256 CUs: blockIdx >> 3 in [32, 64)) start this many
+                            // s_sleep(127) (~8k cycles each) late, so that the CU's two workgroups are not in the same phase
 #endif
 #define HK 32
 // Row strides (floats) of the epilogues' transposition buffers.  Unpadded on purpose: with the lane groups of
@@ -90,15 +99,25 @@ __device__ __forceinline__ float ssilu16(float x) {
 //   columns 128 NJ - the A tile (staged, lifted and split once per workgroup) then serves twice the columns: half the L2 reads
 //   and half the conversions of the A panel (vec_proj: the panel was re-staged by 8 column tiles; staging + epilogue alone
 //   took 1.14 of the kernel's 2.2 ms in the stand-alone harness).
-template <int ACT, int MI, int NJ, int EPI, bool WR = false, int NWN = 2>
-__global__ __launch_bounds__(128 * NWN, (MI == 4 || NWN == 4 ? 1 : 2)) void adf_gemm_f16x3_kernel(
+//   NWM (WR only): waves along M.  2 (default): the layouts above.  1 with NWN = 4: 4 waves as 1(M) x 4(N), 256 threads, tile
+//   32 MI rows x 128 NJ columns (96 x 256: EPI 0 / 3 / 4, 32 atoms x 3 components for EPI 3 / 4; 64 x 384: EPI 1 / 2), two
+//   workgroups per CU.  Every wave runs the instruction stream it runs in the eight-wave form (same accumulators, same A
+//   float4s per thread and K tile, same fragment ring) and the A tile still serves all the columns; the barrier spans four
+//   waves, and the prologue / epilogue of one workgroup can run beside the K loop of the CU's other one.  A weight fragment
+//   is then requested once per 32 MI rows instead of once per 64 MI.  Measured against the forms above (kernel trace of the
+//   benchmark, average per launch): vec_proj 1717 -> 1615 us, plain products with ScaledSiLU 524 -> 486, without 549 -> 483, the
+//   vector-norm product 646 -> 604; xvec_proj.2 1202 -> 1196, x_proj.2 1322 -> 1321 (profiles/NOTES.md, "96 x 256 four-wave
+//   tiles").  Same bits.
+template <int ACT, int MI, int NJ, int EPI, bool WR = false, int NWN = 2, int NWM = 2>
+__global__ __launch_bounds__(64 * NWM * NWN, (MI == 4 || NWM * NWN == 8 ? 1 : 2)) void adf_gemm_f16x3_kernel(
     const float* __restrict__ A, int lda, const _Float16* __restrict__ Whi, const _Float16* __restrict__ Wlo,
     const float* __restrict__ inv_scale, const float* __restrict__ bias, float* __restrict__ C, int ldc, int Mh, int N,
     int K, int tiles_n, adf_epi ep) {
     const int M = ep.m_dev ? min(Mh, (int)*ep.m_dev) : Mh;  // rows: the host's bound, or fewer by a device-side count
     static_assert(NWN == 2 || WR, "eight waves only with the register-streamed weights");
-    constexpr int NT = 128 * NWN;        // threads
-    constexpr int TM = 64 * MI;          // rows per workgroup
+    static_assert(NWM == 2 || (NWM == 1 && WR), "one wave along M only with the register-streamed weights");
+    constexpr int NT = 64 * NWM * NWN;   // threads
+    constexpr int TM = 32 * MI * NWM;    // rows per workgroup
     constexpr int TN = 32 * NJ * NWN;    // columns per workgroup
     constexpr int NA = TM * 8 / NT;      // float4 A loads per thread
     static_assert(TM * 8 % NT == 0, "A staging: whole float4s per thread");
@@ -124,6 +143,12 @@ __global__ __launch_bounds__(128 * NWN, (MI == 4 || NWN == 4 ? 1 : 2)) void adf_
     const int m0 = tile_m * (EPI >= 3 ? TM / 3 : TM);  // EPI 3, 4: M counts atoms, a tile holds TM/3 of them
     const int n0 = tile_n * TN;
     if (m0 >= M) return;
+#if G16_START_DELAY
+    if constexpr (NWM == 1) {
+        if (qd >= 32 && qd < 64)
+            for (int i = 0; i < G16_START_DELAY; ++i) __builtin_amdgcn_s_sleep(127);
+    }
+#endif
 
     // A staging: NA float4 per thread (8 lanes per 128-B row segment, 32 rows per pass).  Addresses are a
     // wave-uniform base + a 32-bit byte offset per lane (the launchers check rows*lda*4 < 2^32), which also lets
@@ -888,7 +913,24 @@ int32_t adf_launch_gemm16(const float* A, int lda, const adf_w16* W, const float
     const long long wg8 = (long long)((M + 191) / 192) * (N / 256 > 0 ? N / 256 : 1);
     const bool ragged = wg8 < 4ll * ncu && wg8 % ncu != 0 && wg8 % ncu < (3 * ncu) / 10 && wg8 > ncu;
     // (256-row tiles, MI = 4 - every weight fragment reused by 128 rows - measured: no gain, 1672-1676 against 1670-1673 ms)
-    if (tune.gemm_w8_plain && W->frag && N % 256 == 0 && (K / HK) % 2 == 0 && mi == 2 && !ragged) {
+    // adf_tune::gemm_rows4 bit 0: the same products as 96 x 256 tiles of four waves, two workgroups per CU (kernel comment:
+    // NWM = 1).  Twice the slots, tiles half as long: the same rule over 2 x ncu slots (25 000 rows: N = 512 gives 261 x 2 = 522
+    // workgroups on 512 slots, a last round of 10 - the 128 x 256 tile as before; N = 256 gives 261, one round - the new tile).
+    const long long wg4 = (long long)((M + 95) / 96) * (N / 256 > 0 ? N / 256 : 1), slots4 = 2ll * ncu;
+    const bool ragged4 = wg4 < 4 * slots4 && wg4 % slots4 != 0 && wg4 % slots4 < (3 * slots4) / 10 && wg4 > slots4;
+    if ((tune.gemm_rows4 & 1) && tune.gemm_w8_plain && W->frag && N % 256 == 0 && (K / HK) % 2 == 0 && mi == 2 && !ragged4) {
+        const int tn4 = N / 256, tmw4 = ((M + 95) / 96 + 7) / 8 * 8;
+        dim3 g4((unsigned)(tmw4 * tn4));
+        if (act_ssilu)
+            hipLaunchKernelGGL((adf_gemm_f16x3_kernel<1, 3, 2, 0, true, 4, 1>), g4, dim3(256), 0, s, A, lda, (const _Float16*)W->frag,
+                               (const _Float16*)nullptr, W->inv_scale, bias, C, ldc, M, N, K, tn4, ep);
+        else
+            hipLaunchKernelGGL((adf_gemm_f16x3_kernel<0, 3, 2, 0, true, 4, 1>), g4, dim3(256), 0, s, A, lda, (const _Float16*)W->frag,
+                               (const _Float16*)nullptr, W->inv_scale, bias, C, ldc, M, N, K, tn4, ep);
+        ADF_HIP_CHECK(hipGetLastError());
+        return ADF_OK;
+    }
+    if (!(tune.gemm_rows4 & 1) && tune.gemm_w8_plain && W->frag && N % 256 == 0 && (K / HK) % 2 == 0 && mi == 2 && !ragged) {
         const int tn8 = N / 256, tmw8 = ((M + 191) / 192 + 7) / 8 * 8;
         dim3 g8((unsigned)(tmw8 * tn8));
         if (act_ssilu)
@@ -921,6 +963,14 @@ int32_t adf_launch_gemm16_vecnorm(const float* A, int lda, const adf_w16* W, flo
     ep.cat = nrm;
     ADF_TRY(lift_mags(A, lda, K, nullptr, 0, 3ll * M, lf, premag, &ep.rmag, s));
     const int tn = (N + 127) / 128, tm8 = ((M + 63) / 64 + 7) / 8 * 8;
+    if ((tune.gemm_rows4 & 1) && tune.gemm_w8 && W->frag && N % 256 == 0 && (K / HK) % 2 == 0) {   // four waves, 32 atoms x 256 columns
+        const int tm4 = ((M + 31) / 32 + 7) / 8 * 8;
+        hipLaunchKernelGGL((adf_gemm_f16x3_kernel<0, 3, 2, 4, true, 4, 1>), dim3((unsigned)(tm4 * (N / 256))), dim3(256), 0, s, A, lda,
+                           (const _Float16*)W->frag, (const _Float16*)nullptr, W->inv_scale, (const float*)nullptr,
+                           (float*)nullptr, 0, M, N, K, N / 256, ep);
+        ADF_HIP_CHECK(hipGetLastError());
+        return ADF_OK;
+    }
     if (tune.gemm_w8 && W->frag && N % 256 == 0 && (K / HK) % 2 == 0) {   // weights streamed as fragments, eight waves (see the kernel comment)
         hipLaunchKernelGGL((adf_gemm_f16x3_kernel<0, 3, 2, 4, true, 4>), dim3((unsigned)(tm8 * (N / 256))), dim3(512), 0, s, A, lda,
                            (const _Float16*)W->frag, (const _Float16*)nullptr, W->inv_scale, (const float*)nullptr,
@@ -958,7 +1008,12 @@ int32_t adf_launch_gemm16_fused(const float* A, int lda, const adf_w16* W, int M
         // adf_tune::gemm_wreg = 0: weights staged through LDS as in rounds 1-5; gemm_w8 = 0: four waves per workgroup (128
         // columns) instead of eight (256) (four waves, two workgroups per CU, same pipeline: node products 1748 ms per pass
         // against 1679)
-        if (tune.gemm_wreg && W->frag && tune.gemm_w8 && (2 * H) % 256 == 0 && (K / HK) % 2 == 0)
+        // gemm_rows4 bit 0: the eight-wave form's tile halved along M - four waves, 32 atoms x 256 columns, two workgroups per CU
+        if ((tune.gemm_rows4 & 1) && tune.gemm_wreg && W->frag && tune.gemm_w8 && (2 * H) % 256 == 0 && (K / HK) % 2 == 0)
+            hipLaunchKernelGGL((adf_gemm_f16x3_kernel<0, 3, 2, 3, true, 4, 1>), dim3((unsigned)(((M + 31) / 32 + 7) / 8 * 8 * (2 * H / 256))),
+                               dim3(256), 0, s, A, lda, (const _Float16*)W->frag, (const _Float16*)nullptr, W->inv_scale,
+                               (const float*)nullptr, (float*)nullptr, 0, M, 2 * H, K, 2 * H / 256, *ep);
+        else if (tune.gemm_wreg && W->frag && tune.gemm_w8 && (2 * H) % 256 == 0 && (K / HK) % 2 == 0)
             hipLaunchKernelGGL((adf_gemm_f16x3_kernel<0, 3, 2, 3, true, 4>), dim3((unsigned)(tm8 * (2 * H / 256))), dim3(512), 0, s,
                                A, lda, (const _Float16*)W->frag, (const _Float16*)nullptr, W->inv_scale, (const float*)nullptr,
                                (float*)nullptr, 0, M, 2 * H, K, 2 * H / 256, *ep);
@@ -972,6 +1027,19 @@ int32_t adf_launch_gemm16_fused(const float* A, int lda, const adf_w16* W, int M
     const int wf = tune.gemm_wr_fused;   // 0 = LDS-staged weights (rounds 1-5), 2 / 4 = streamed fragments with 4 / 8 waves
     // (measured: 4 waves 1656 ms of node products per pass, LDS-staged weights 1702, 8 waves 1741 - the record / gating
     // epilogues are HBM-heavy and want the CU's second workgroup beside them)
+    // gemm_rows4 bit 1 (with the default wf = 2 only): four waves as 1(M) x 4(N), 64 x 384 tile - the per-wave stream of wf = 4
+    // at two workgroups per CU; a row panel is read and converted by N / 384 column tiles instead of N / 192
+    if ((tune.gemm_rows4 & 2) && wf == 2 && W->frag && (K / HK) % 2 == 0 && N % 384 == 0) {
+        dim3 g4((unsigned)(((M + 63) / 64 + 7) / 8 * 8 * (N / 384)));
+        if (epi == 1)
+            hipLaunchKernelGGL((adf_gemm_f16x3_kernel<0, 2, 3, 1, true, 4, 1>), g4, dim3(256), 0, s, A, lda, (const _Float16*)W->frag,
+                               (const _Float16*)nullptr, W->inv_scale, W->bias_perm, (float*)nullptr, 0, M, N, K, N / 384, *ep);
+        else
+            hipLaunchKernelGGL((adf_gemm_f16x3_kernel<0, 2, 3, 2, true, 4, 1>), g4, dim3(256), 0, s, A, lda, (const _Float16*)W->frag,
+                               (const _Float16*)nullptr, W->inv_scale, W->bias_perm, (float*)nullptr, 0, M, N, K, N / 384, *ep);
+        ADF_HIP_CHECK(hipGetLastError());
+        return ADF_OK;
+    }
     if (wf && W->frag && (K / HK) % 2 == 0 && (wf == 2 || N % 384 == 0)) {
         const int tnw = wf == 4 ? N / 384 : tiles_n;
         dim3 gw((unsigned)(tiles_m8 * tnw));

@@ -75,7 +75,8 @@ class Tune(C.Structure):
     _fields_ = [(name, C.c_int32) for name in (
         "gemm16_mi", "gemm_w8_plain", "gemm_w8", "gemm_wreg", "gemm_wr_fused", "head_gate_fused", "lift_emit",
         "graph_sys_csr", "train_gemm16", "wgrad_f32",
-        "eqv2_pw_mi", "eqv2_gemm_tile256", "eqv2_rotin_generic", "eqv2_rotout_generic")]
+        "eqv2_pw_mi", "eqv2_gemm_tile256", "eqv2_rotin_generic", "eqv2_rotout_generic",
+        "gemm_rows4")]
 
 
 class BatchDesc(C.Structure):

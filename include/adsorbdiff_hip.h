@@ -159,6 +159,10 @@ typedef struct adf_tune {
     int32_t eqv2_gemm_tile256;   /* ADF_EQV2_GEMM_TILE: 128 = 0, the 128-row tile for every shape, else 1 (256 rows from 8192 on) */
     int32_t eqv2_rotin_generic;  /* ADF_EQV2_ROTIN_GENERIC set (any value): 1, the run-time-mmax rotate-in kernel, else 0 */
     int32_t eqv2_rotout_generic; /* ADF_EQV2_ROTOUT_GENERIC set (any value): 1, the run-time-mmax rotate-out kernel, else 0 */
+    /* PaiNN again (appended: the fields above keep their offsets) */
+    int32_t gemm_rows4;       /* ADF_GEMM_ROWS4: streamed-weights products as four waves 1(M) x 4(N), two workgroups per CU. Bit 0 =
+                               * plain / vec_proj / vector-norm products (96 x 256 tile), bit 1 = the fused x_proj.2 / xvec_proj.2
+                               * products (64 x 384, with gemm_wr_fused = 2 only); 0 = the eight- / four-wave forms above; default 3 */
 } adf_tune;
 /* Test hook: the selection the handle holds (the variants give the same bits, so outputs cannot show it). */
 int32_t adf_painn_get_tune(adf_painn_t h, adf_tune* out);

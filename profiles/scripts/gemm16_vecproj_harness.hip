@@ -1,6 +1,7 @@
 // stand-alone timing harness of the vec_proj product (adf_gemm_f16x3_kernel<0,3,2,3,...>) with the G16_ABL ablation bits of
 // gemm16.hip: hipcc --offload-arch=gfx950 -O3 -std=c++17 -fno-slp-vectorize -DG16_ABL=<bits> -o g16 gemm16_vecproj_harness.hip
-// usage: g16 [rows [gemm_wreg [gemm_w8]]]  (adf_tune fields; 0 selects the earlier forms)
+// usage: g16 [rows [gemm_wreg [gemm_w8 [gemm_rows4]]]]  (adf_tune fields; 0 selects the earlier forms, gemm_rows4 = 1 the
+// four-wave 96 x 256 tile; -DG16_START_DELAY=<n> staggers its first round)
 #include <stdarg.h>
 #include "../../adsorbdiff_amd/csrc/gemm16.hip"
 void adf_set_error(const char* fmt, ...) { va_list a; va_start(a, fmt); vfprintf(stderr, fmt, a); va_end(a); fprintf(stderr, "\n"); }
@@ -15,6 +16,7 @@ int main(int argc, char** argv) {
     const int N = argc > 1 ? atoi(argv[1]) : 200000, H = 512;
     adf_tune tune = {};
     tune.gemm_wreg = argc > 2 ? atoi(argv[2]) : 1; tune.gemm_w8 = argc > 3 ? atoi(argv[3]) : 1;
+    tune.gemm_rows4 = argc > 4 ? atoi(argv[4]) : 0;
     float *vec, *w, *v1, *dot, *cat, *mag, *isc;
     _Float16 *hi, *lo; void* frag; unsigned int* scratch;
     CK(hipMalloc(&vec, (size_t)N * 3 * H * 4)); CK(hipMalloc(&w, (size_t)2 * H * H * 4)); CK(hipMalloc(&v1, (size_t)N * 3 * H * 4));
@@ -40,7 +42,7 @@ int main(int argc, char** argv) {
         CK(hipEventRecord(e1, 0)); CK(hipEventSynchronize(e1));
         float ms; CK(hipEventElapsedTime(&ms, e0, e1));
         const double flops = (double)N * 3 * 1024.0 * 512 * 6;
-        printf("G16_ABL=%d WR=%d N=%d: %.3f ms per launch, %.0f TFLOP/s issued\n", G16_ABL, wr, N, ms / reps, flops / (ms / reps * 1e-3) / 1e12);
+        printf("G16_ABL=%d rows4=%d WR=%d N=%d: %.3f ms per launch, %.0f TFLOP/s issued\n", G16_ABL, tune.gemm_rows4, wr, N, ms / reps, flops / (ms / reps * 1e-3) / 1e12);
     }
     return 0;
 }
