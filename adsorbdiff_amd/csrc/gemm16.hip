@@ -18,7 +18,8 @@
 // halves (row stride 80 B: the 16 lanes of a ds_read_b128 lane group land on 16 distinct 16-B bank quads).
 // Global loads are 16 B per lane, prefetched one K-tile ahead in registers; XCD-aware tile map as in
 // gemm.hip (all N-tiles of an M-panel on one XCD's L2).  Every epilogue transposes the accumulators through the
-// idle staging LDS so that global accesses are 16 B per lane, and issues all its loads before its first store.
+// idle staging LDS so that global accesses are 16 B per lane, and issues all its loads before its first store.  The record
+// epilogue (EPI 1) also stores whole 128-B lines: the eight lanes of a row exchange their float4s through 4 KB of LDS per wave.
 // That tile is the LDS-staged form (rounds 1-5), still what shapes without a fragment image run.  The sampler's products stream
 // their weights as register fragments (WR, kernel comment) and run as four waves laid out 1(M) x 4(N), two workgroups per CU:
 // 96 x 256 tiles (plain, vec_proj, vector-norm products) and 64 x 384 tiles (x_proj.2 / xvec_proj.2 with their fused
@@ -123,7 +124,9 @@ __global__ __launch_bounds__(64 * NWM * NWN, (MI == 4 || NWM * NWN == 8 ? 1 : 2)
     static_assert(TM * 8 % NT == 0, "A staging: whole float4s per thread");
     // (WR: no W tiles; two A buffers, reused as the epilogues' scratch of NT / 64 waves x 3200 floats)
     constexpr int LDS_WR = 4 * TM * HLD > NT / 64 * 6400 ? 4 * TM * HLD : NT / 64 * 6400;   // two A buffers (hi + lo) | the scratch
-    __shared__ __attribute__((aligned(16))) _Float16 lds[WR ? LDS_WR : (2 * TM + 2 * TN) * HLD];
+    constexpr int LDS_MAIN = WR ? LDS_WR : (2 * TM + 2 * TN) * HLD;
+    constexpr int LDS_REC = EPI == 1 ? NT / 64 * 2048 : 0;   // EPI 1: 4 KB per wave behind the scratch, the record exchange (epilogue)
+    __shared__ __attribute__((aligned(16))) _Float16 lds[LDS_MAIN + LDS_REC];
     __shared__ float rinv[TM];  // 1 / lift of every staged A row
     _Float16* Ahi = lds;
     _Float16* Alo = Ahi + TM * HLD;
@@ -628,22 +631,36 @@ __global__ __launch_bounds__(64 * NWM * NWN, (MI == 4 || NWM * NWN == 8 ? 1 : 2)
                     const float4 p0 = *reinterpret_cast<const float4*>(T + lr * TLD3 + 4 * c4);
                     const float4 p1 = *reinterpret_cast<const float4*>(T + lr * TLD3 + 32 + 4 * c4);
                     const float4 p2 = *reinterpret_cast<const float4*>(T + lr * TLD3 + 64 + 4 * c4);
-                    if ((EPI_ABL & 8) && n >= 0) { if (ep.H < 0) ep.rec[0] = p0.x + p1.x + p2.x + v0[it].x + v1[it].y + v2[it].z; }
+                    // half-record of (atom n, group g): [32 x (P0, P1, P2, xa)] then [32 x xc].  A lane forms the (P0, P1, P2, xa) of
+                    // its four channels, 64 consecutive bytes of the row's 512.  Stored from there, each of the four store
+                    // instructions puts 16 B into every 64-B segment of the eight rows: 64 partial writes to L2 per instruction
+                    // and every line written four times over.  So the eight lanes of a row exchange them through LDS (float4
+                    // lane * 4 + k  ->  row * 32 + 8 k + lane % 8): store k of a row is then one whole 128-B line.
+                    float4 o[4];
+                    if (!ep.vec_is_zero) {
+                        o[0] = make_float4(v0[it].x * p1.x, v1[it].x * p1.x, v2[it].x * p1.x, p0.x);
+                        o[1] = make_float4(v0[it].y * p1.y, v1[it].y * p1.y, v2[it].y * p1.y, p0.y);
+                        o[2] = make_float4(v0[it].z * p1.z, v1[it].z * p1.z, v2[it].z * p1.z, p0.z);
+                        o[3] = make_float4(v0[it].w * p1.w, v1[it].w * p1.w, v2[it].w * p1.w, p0.w);
+                    } else {
+                        o[0] = make_float4(0.f, 0.f, 0.f, p0.x);
+                        o[1] = make_float4(0.f, 0.f, 0.f, p0.y);
+                        o[2] = make_float4(0.f, 0.f, 0.f, p0.z);
+                        o[3] = make_float4(0.f, 0.f, 0.f, p0.w);
+                    }
+                    float4* X = reinterpret_cast<float4*>(lds + LDS_MAIN) + wave * 256;   // [8 rows][32] float4 of this wave
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) X[lane * 4 + k] = o[k];
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) o[k] = X[(lane >> 3) * 32 + 8 * k + c4];
+                    __builtin_amdgcn_wave_barrier();  // X is rewritten by the next item
+                    if ((EPI_ABL & 8) && n >= 0) { if (ep.H < 0) ep.rec[0] = p2.x + o[0].x + o[1].y + o[2].z + o[3].w; }
                     else if (n < M) {
-                        // half-record of (atom n, group g): [32 x (P0, P1, P2, xa)] then [32 x xc]
                         float* rec = ep.rec + ((size_t)(ep.row_map ? ep.row_map[n] : n) * (H / 32) + g) * 160;
-                        float4* ra_ = reinterpret_cast<float4*>(rec + 16 * c4);
-                        if (!ep.vec_is_zero) {
-                            ra_[0] = make_float4(v0[it].x * p1.x, v1[it].x * p1.x, v2[it].x * p1.x, p0.x);
-                            ra_[1] = make_float4(v0[it].y * p1.y, v1[it].y * p1.y, v2[it].y * p1.y, p0.y);
-                            ra_[2] = make_float4(v0[it].z * p1.z, v1[it].z * p1.z, v2[it].z * p1.z, p0.z);
-                            ra_[3] = make_float4(v0[it].w * p1.w, v1[it].w * p1.w, v2[it].w * p1.w, p0.w);
-                        } else {
-                            ra_[0] = make_float4(0.f, 0.f, 0.f, p0.x);
-                            ra_[1] = make_float4(0.f, 0.f, 0.f, p0.y);
-                            ra_[2] = make_float4(0.f, 0.f, 0.f, p0.z);
-                            ra_[3] = make_float4(0.f, 0.f, 0.f, p0.w);
-                        }
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) *reinterpret_cast<float4*>(rec + 32 * k + 4 * c4) = o[k];
                         *reinterpret_cast<float4*>(rec + 128 + 4 * c4) = p2;
                     }
                 }
@@ -1029,6 +1046,10 @@ int32_t adf_launch_gemm16_fused(const float* A, int lda, const adf_w16* W, int M
     // epilogues are HBM-heavy and want the CU's second workgroup beside them)
     // gemm_rows4 bit 1 (with the default wf = 2 only): four waves as 1(M) x 4(N), 64 x 384 tile - the per-wave stream of wf = 4
     // at two workgroups per CU; a row panel is read and converted by N / 384 column tiles instead of N / 192
+    // (Measured and dropped: 32 x 384 tiles, MI = 1 - 48 accumulators, a fragment ring of two sets, 145 / 156 VGPRs, three
+    // workgroups per CU.  Same sites; x_proj.2 1339 -> 1615 us per launch, xvec_proj.2 1194 -> 1473, node products + 77 ms per pass
+    // each.  Every weight fragment is then requested once per 32 rows: 76 M more L2 requests of 128 B per launch, 9.8 GB, and
+    // 0.28 ms more - the L2s' full rate.  These two kernels pay for their L2 requests; profiles/NOTES.md, "32 x 384 tiles".)
     if ((tune.gemm_rows4 & 2) && wf == 2 && W->frag && (K / HK) % 2 == 0 && N % 384 == 0) {
         dim3 g4((unsigned)(((M + 63) / 64 + 7) / 8 * 8 * (N / 384)));
         if (epi == 1)
