@@ -66,6 +66,28 @@ extern "C" int32_t adf_noise_draws(int64_t seed, int32_t step, const int64_t* ke
     return ADF_OK;
 }
 
+// The placement stage's rows (placement.hip): eight plain uniforms per (key, index), from the counters
+// (key lo, key hi, index, 2) and (key lo, key hi, index, 3): the last counter word keeps them apart from the rows above.
+__global__ void nz_place_draws_kernel(uint32_t seed_lo, uint32_t seed_hi, const int64_t* __restrict__ keys,
+                                      const int32_t* __restrict__ index, int n, double* __restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t key = (uint64_t)keys[i];
+    const uint32_t idx = (uint32_t)index[i];
+    uint32_t w[8];
+    nz_philox4x32_10((uint32_t)key, (uint32_t)(key >> 32), idx, 2u, seed_lo, seed_hi, w);
+    nz_philox4x32_10((uint32_t)key, (uint32_t)(key >> 32), idx, 3u, seed_lo, seed_hi, w + 4);
+    for (int k = 0; k < 8; ++k) out[8 * (size_t)i + k] = nz_unit(w[k]);
+}
+extern "C" int32_t adf_place_draws(int64_t seed, const int64_t* keys, const int32_t* index, int32_t n, double* out,
+                                   void* stream) {
+    if (!keys || !index || !out || n <= 0) { adf_set_error("place_draws: bad argument"); return ADF_EINVAL; }
+    hipLaunchKernelGGL(nz_place_draws_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream,
+                       (uint32_t)(uint64_t)seed, (uint32_t)((uint64_t)seed >> 32), keys, index, n, out);
+    NZ_CHECK_LAUNCH();
+    return ADF_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ table look-ups
 // Igso3Tables.eps_index: nearest row of the log-spaced eps grid, clipped (np.around rounds halves to even, as rint does)
 __device__ __forceinline__ int nz_eps_index(double eps, int n_eps) {

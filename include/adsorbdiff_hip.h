@@ -403,6 +403,66 @@ int32_t adf_flag_anomalies(const adf_batch* b, const float* pos_final, const flo
 int32_t adf_select_best_sites(const float* energy, const int32_t* flags, const int32_t* group_offset, int32_t num_groups,
                               int32_t* best, float* best_energy, int32_t* n_valid, void* stream);
 
+/* ---- Adsorbate placement (csrc/placement.hip; adsorbdiff_amd/placement.py): the reference's
+ * AdsorbateSlabConfig, placement/adsorbate_slab_config.py:99-439, 460-575 with adsorbate.py:122-169, modes "random"
+ * [mode 0] and "random_site_heuristic_placement" [mode 1], for a whole batch of slabs.  This is a written contract, a
+ * reading of those lines and of the ASE calls they make [Atoms.rotate, Atoms.wrap, get_center_of_mass]; ASE was not run
+ * against it: parity with ASE is unpinned.  Inputs and outputs are float32 unless stated, all arithmetic is float64, no
+ * float atomics, every output is bit-reproducible.
+ *
+ * Draw rows [double, 8 per row, uniforms in the open unit interval]: (r1, r2, selection key, u0, u1, u2, binding pick,
+ * spare).  adf_place_draws fills row i from (seed, keys[i], index[i]) alone: Philox4x32-10 as adf_noise_draws, counters
+ * (key lo, key hi, index, j), j = 2 for the first four words and j = 3 for the last four, u = (w + 0.5) 2^-32. */
+int32_t adf_place_draws(int64_t seed, const int64_t* keys, const int32_t* index, int32_t n, double* out, void* stream);
+/* P placements in one launch.  Placement p belongs to slab slab_of[p] of `slabs` [pos, cell, atomic_numbers, atom_offset;
+ * reps unused], sits on site[p] [P,3] and reads u0, u1, u2 of draws row p [P,8].  Adsorbates are CSR over the slabs:
+ * atoms ads_offset[b] .. ads_offset[b+1] of ads_pos / ads_Z.  radii [num_radii] and masses [num_masses] are indexed by
+ * atomic number; pbc [B,3] int32: the periodic directions of each slab.  Per placement:
+ *   Rotation.  A one-atom adsorbate is not rotated and reports zeros.  Otherwise zrot = 360 u0 degrees, phi = 2 pi u2,
+ *     z = -1 + 2 u1 [mode 0] or cos[pi/9] + (1 - cos[pi/9]) u1 [mode 1], rotvec = (sqrt(1 - z^2) cos phi,
+ *     sqrt(1 - z^2) sin phi, z).  First the counter-clockwise rotation by zrot about +z, then the Rodrigues rotation that
+ *     takes +z to rotvec: axis z_hat x rotvec normalised, cos = z, sin = |z_hat x rotvec|; below 1e-7 the axis is
+ *     x_hat x rotvec normalised [ASE's fallback as we read it].  Both about the centre C: the mass-weighted centre
+ *     [masses of ads_Z] in mode 0, atom binding_idx[p] in mode 1.
+ *   Translation so that C sits on the site.  Normal n = cell[0] x cell[1] normalised, its sign not fixed.
+ *   Height.  Every slab atom is moved by (cell centre - site), cell centre = 0.5 (a + b + c), and wrapped into the cell along
+ *     the periodic directions by ASE's rule, fractional f -> (f + 1e-7) mod 1 - 1e-7; the adsorbate is moved by the same
+ *     vector.  Only this one image of each slab atom is looked at, as in the reference.  For each pair (adsorbate atom a,
+ *     slab atom s of any tag): w = s - a, h = w . n, q = |w - h n|, D = radii[Z_a] + radii[Z_s] + interstitial_gap.  The
+ *     pair counts when q <= D, with x_pair = h + sqrt(D^2 - q^2).  scaled_normal = max x_pair; without a counted pair it is
+ *     0 and n_combos = 0 [the reference's "scary edge case": the adsorbate stays on the site].
+ *     A deliberate reading: the reference solves each pair with fsolve started at 3 (R_a + R_s), which reaches the upper
+ *     root whenever the slab atom lies less than that far above the adsorbate atom along n; this contract takes the
+ *     upper root always.
+ * Outputs: rows out_row[p] .. out_row[p] + n_a of out_pos [out_rows,3] receive rotated + translation + scaled_normal n,
+ * in the slab's original frame [the caller points out_pos at the collated batch: out_row[p] is where the adsorbate of
+ * system p begins]; scaled_normal double [P]; n_combos int32 [P]; rot_meta double [P,4] = (zrot, rotvec).
+ * mode 1 needs binding_idx [P]; interstitial_gap must lie in [0, 5).  An atomic number outside either table, a
+ * binding_idx outside its adsorbate or an offset out of range returns ADF_EINVAL, reported like adf_flag_anomalies
+ * reports one: the call synchronises `stream` to read the error word. */
+int32_t adf_place_adsorbates(const adf_batch* slabs, const int32_t* slab_of, const float* site, const double* draws,
+                             const int32_t* ads_offset, const float* ads_pos, const int32_t* ads_Z, const float* radii,
+                             int32_t num_radii, const float* masses, int32_t num_masses, float interstitial_gap,
+                             int32_t mode, const int32_t* binding_idx, const int32_t* pbc, int32_t P,
+                             const int32_t* out_row, int64_t out_rows, float* out_pos, double* scaled_normal,
+                             int32_t* n_combos, double* rot_meta, void* stream);
+/* Candidate sites [get_binding_sites, :144-164].  Slab b has triangles tri_offset[b] .. tri_offset[b+1] of tri [T,3,3]
+ * and candidates cand_offset[b] .. cand_offset[b+1], per_tri[b] = ceil(2 num_sites / T_b) per triangle in triangle order
+ * [equal counts per triangle, not area-uniform: the reference's scheme]; cand_slab[c] is the slab of candidate c.
+ * Candidate c reads r1, r2 of draws row c: (1 - sqrt(r1)) v0 + sqrt(r1) (1 - r2) v1 + sqrt(r1) r2 v2.  keep[c] = 1 when
+ * its fractional coordinates along a and b lie in [-1e-7, 1 - 1e-7), that is when ASE's wrap with pbc = (T, T, F) leaves
+ * it where it is [the reference's isclose of unwrapped and wrapped]. */
+int32_t adf_place_site_candidates(const float* tri, const int32_t* tri_offset, const int32_t* per_tri,
+                                  const int32_t* cand_offset, const int32_t* cand_slab, const float* cell,
+                                  const double* draws, int32_t B, int32_t num_candidates, float* cand, int32_t* keep,
+                                  void* stream);
+/* get_interstitial_distances / there_is_overlap [:511-575] per system of any adsorbate + slab batch: the system is
+ * translated so that the mass centre of the adsorbate [tag 2] is on the cell centre, every atom is wrapped as above, and
+ * out[b] = min over (surface atom s of tag 1, adsorbate atom a) of |p_a - p_s| - R_a - R_s [float32; +inf for a system
+ * without such a pair].  Errors as adf_place_adsorbates. */
+int32_t adf_interstitial_distances(const adf_batch* b, const int32_t* tags, const float* radii, int32_t num_radii,
+                                   const float* masses, int32_t num_masses, const int32_t* pbc, float* out, void* stream);
+
 /* Multi-GPU exchange of the sharded sampler: systems are independent, every rank samples its shard
  * with no data-path collective, and ONE all-gather of the sampled adsorbate sites ends a pass.  Replaces the reference's
  * per-rank .npz + barrier + rank-0 merge (trainers/sde_denoising_trainer.py:862-909).  RCCL is loaded lazily (dlopen).
