@@ -34,6 +34,7 @@ EXPORTS = (
     "adf_frames_create", "adf_frames_destroy", "adf_frames_push", "adf_frames_wait", "adf_frames_release", "adf_frames_pushed", "adf_frames_abort",
     "adf_get_counters", "adf_profile_enable", "adf_profile_read", "adf_measure_peaks",
     "adf_lift_adsorbates", "adf_flag_anomalies", "adf_select_best_sites",
+    "adf_site_pair_distances", "adf_unique_sites", "adf_select_top_sites",
     "adf_place_draws", "adf_place_adsorbates", "adf_place_site_candidates", "adf_interstitial_distances", "adf_comm_unique_id", "adf_comm_create", "adf_comm_destroy", "adf_allgather_sites",
     "adf_op_linear_fwd", "adf_op_linear_bwd_scratch", "adf_op_linear_bwd", "adf_op_ssilu_fwd", "adf_op_ssilu_bwd", "adf_op_layernorm_fwd", "adf_op_layernorm_bwd", "adf_op_embed_fwd", "adf_op_embed_bwd", "adf_op_rbf", "adf_op_message_fwd", "adf_op_message_fwd_fused", "adf_op_message_bwd", "adf_op_message_bwd_fused", "adf_op_message_bwd_fused_supported", "adf_op_message_bwd_perm", "adf_op_edge_owner", "adf_op_rbf_image_bytes", "adf_op_rbf_image", "adf_op_rbf_wgrad_fused_scratch", "adf_op_rbf_wgrad_fused", "adf_op_vdot_fwd", "adf_op_vdot_bwd", "adf_op_update_out_fwd", "adf_op_update_out_bwd", "adf_op_vnorm_fwd", "adf_op_vnorm_bwd", "adf_op_gate_fwd", "adf_op_gate_bwd", "adf_op_copy_rows", "adf_op_score_loss", "adf_op_score_loss_tr", "adf_op_s2ef_loss", "adf_op_s2ef_loss_scratch", "adf_op_energy_sum", "adf_op_energy_head_bwd", "adf_op_energy_head_bwd_scratch", "adf_op_sqnorm_accumulate", "adf_op_adamw_step",
     "adf_noise_draws", "adf_noise_tr_so3", "adf_noise_com", "adf_igso3_score_norm",
@@ -190,6 +191,9 @@ def load():
         "adf_lift_adsorbates": [vp, vp, vp, i32, C.c_float, vp, vp],
         "adf_flag_anomalies": [C.POINTER(BatchDesc), vp, vp, vp, vp, i32, C.c_float, C.c_float, C.c_float, vp, vp],
         "adf_select_best_sites": [vp, vp, vp, i32, vp, vp, vp, vp],
+        "adf_site_pair_distances": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i64, i32, i32, vp, vp],
+        "adf_unique_sites": [vp, vp, vp, i32, i32, i64, vp, vp, C.c_float, C.c_float, vp, vp, vp],
+        "adf_select_top_sites": [vp, vp, vp, vp, i32, i32, vp, vp, vp],
         "adf_place_draws": [i64, vp, vp, i32, vp, vp],
         "adf_place_adsorbates": [C.POINTER(BatchDesc), vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, C.c_float, i32, vp, vp, i32,
                                  vp, i64, vp, vp, vp, vp, vp],

@@ -1,4 +1,5 @@
-"""``ml_diffuse`` — driver of the diffusion sampler; ``ml_relax`` — driver of the L-BFGS relaxation.
+"""``ml_diffuse`` — driver of the diffusion sampler; ``ml_relax`` — driver of the L-BFGS relaxation; ``ml_relax_unique`` —
+``ml_relax`` of one representative per cluster of duplicate sites (an extension).
 
 Drop-ins for ``adsorbdiff.relaxation.ml_relaxation.ml_diffuse`` / ``ml_relax`` (reference:
 adsorbdiff/relaxation/ml_relaxation.py:98-168 / :23-95).  Written from their contract, not their text:
@@ -175,4 +176,63 @@ def ml_relax_sharded(
     out.force = force.to(batch.pos.device)
     if want_flags:
         out.anomaly = _anomaly.flag_anomalies(initial.to(out.pos.device), out.pos, radii=dict(relax_opt).get("anomaly_radii"))
+    return out
+
+
+def ml_relax_unique(
+    batch,
+    model,
+    steps: int,
+    fmax: float,
+    relax_opt,
+    save_full_traj,
+    group=None,
+    tol: float = 0.05,
+    rank=None,
+    world=None,
+    **kw,
+):
+    """``ml_relax`` of one representative per cluster of duplicate sites (``site_select.unique_sites`` on the positions given
+    here, no energies yet; ``group`` defaults to ``batch.site_group``; ``include_slab`` / ``permutation_invariant`` go to it,
+    every other keyword to ``ml_relax``, or to ``ml_relax_sharded`` when ``rank`` and ``world`` are given).  Returns the whole
+    batch in input order - the out-of-memory split's reordering is undone: a duplicate carries its representative's relaxed
+    ``pos``, ``y`` and ``force`` (and, with ``relax_opt["flag_anomalies"]``, its ``anomaly`` row); ``site_rep`` [S] holds every
+    site's representative.  The sites of a cluster are the same atoms within ``tol``, so a duplicate's own relaxation would
+    start from the same basin; how many relaxations that saves is a property of the input."""
+    from . import site_select
+
+    select = {k: kw.pop(k) for k in ("include_slab", "permutation_invariant") if k in kw}
+    if (rank is None) != (world is None):
+        raise ValueError("ml_relax_unique: rank and world go together")
+    rep, is_rep, _ = site_select.unique_sites(batch, group=group, tol=tol, **select)
+    dev = batch.pos.device
+    chosen = is_rep.nonzero().reshape(-1).tolist()
+    systems = batch.to_data_list()
+    sub = Batch.from_data_list([systems[i] for i in chosen])     # a copy: the optimizer moves positions in place
+    if rank is None:
+        order = []
+        relaxed = ml_relax(sub, model, steps, fmax, relax_opt, save_full_traj, _order=order, **kw)
+    else:
+        relaxed = ml_relax_sharded(sub, model, steps, fmax, relax_opt, save_full_traj, rank=rank, world=world, **kw)
+        order = list(range(len(chosen)))
+    # slot[i]: where input site i sits in `relaxed` (representatives only)
+    S = int(batch.natoms.shape[0])
+    slot = torch.full((S,), -1, dtype=torch.long)
+    slot[torch.tensor([chosen[i] for i in order], dtype=torch.long)] = torch.arange(len(order))
+    src = slot.to(dev)[rep]
+    r_dev = relaxed.pos.device
+    r_natoms = relaxed.natoms.to(r_dev).long()
+    r_start = torch.cumsum(r_natoms, 0) - r_natoms
+    natoms = batch.natoms.to(r_dev).long()
+    N = int(batch.pos.shape[0])
+    start = torch.cumsum(natoms, 0) - natoms
+    src_r = src.to(r_dev)
+    rows = torch.arange(N, device=r_dev) + torch.repeat_interleave(r_start[src_r] - start, natoms, output_size=N)
+    out = batch.clone()
+    out.pos = relaxed.pos[rows].to(dev)
+    out.y = relaxed.y.reshape(-1)[src_r].to(dev)
+    out.force = relaxed.force[rows].to(dev)
+    if hasattr(relaxed, "anomaly"):
+        out.anomaly = relaxed.anomaly[src_r.to(relaxed.anomaly.device)].to(dev)
+    out.site_rep = rep
     return out

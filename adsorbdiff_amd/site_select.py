@@ -1,0 +1,176 @@
+"""Duplicate sites on the device (csrc/unique.hip): ``site_distances`` - the pairwise distance of the sites
+of every slab; ``unique_sites`` - a deterministic greedy clustering on top of it; ``top_sites`` - the k valid (and, given
+the clustering, distinct) sites of least energy per slab.  An extension: the reference has no counterpart; its
+``scripts/run_vasp_dft/write_vasp_inputs_nsite.py`` takes the best N relaxed sites per slab on the host, where N copies of
+one minimum are N sites.
+
+The displacement of two positions follows the IS2RS metric (``scripts/eval.py:765-777``, ``min_diff``): fractional
+coordinates in the first site's cell, ``% 1`` twice, minus 1 above 0.5.  In a strongly skewed cell that is the reference's
+convention and not the shortest lattice image.  The contract is written out in include/adsorbdiff_hip.h.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from typing import Optional
+
+import torch
+
+from . import lib as _lib
+from .flag_anomaly import regroup
+
+
+def _stream(dev):
+    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def to_caller_order(index: torch.Tensor, perm: torch.Tensor) -> torch.Tensor:
+    """Indices into the regrouped order -> indices into the caller's order; negative entries (none) are kept."""
+    index = index.long()
+    return torch.where(index >= 0, perm[index.clamp(min=0)], index)
+
+
+def to_group_order(index: torch.Tensor, perm: torch.Tensor) -> torch.Tensor:
+    """``index[s]`` (caller's order, pointing at the caller's order) -> the same array in the regrouped order, pointing at
+    the regrouped order; negative entries are kept."""
+    index = index.long()
+    inverse = torch.empty_like(perm)
+    inverse[perm] = torch.arange(perm.numel(), device=perm.device)
+    moved = index[perm]
+    return torch.where(moved >= 0, inverse[moved.clamp(min=0)], moved)
+
+
+def _groups(batch, group, S: int, dev):
+    if group is None:
+        group = getattr(batch, "site_group", None)
+        if group is None:
+            raise ValueError("no group ids: pass group=, or a batch that carries site_group (place_adsorbates)")
+    group = torch.as_tensor(group).reshape(-1)
+    if int(group.numel()) != S:
+        raise ValueError(f"{S} sites, {int(group.numel())} group ids")
+    return group.to(dev)
+
+
+class _Matrices:
+    """The distance matrices of a batch in the regrouped order, with what the clustering needs next to them."""
+
+    def __init__(self, batch, group, include_slab: bool, permutation_invariant: bool):
+        pos = batch.pos
+        S = int(batch.natoms.shape[0])
+        group = _groups(batch, group, S, pos.device)
+        if not pos.is_cuda:
+            raise RuntimeError("site_distances runs on a ROCm device (no CPU fallback)")
+        if S == 0:
+            raise ValueError("site_distances: no site")
+        lib = _lib.load()
+        dev = pos.device
+        self.S, self.dev = S, dev
+        self.perm, self.offsets, self.ids = regroup(group)
+        self.G = int(self.ids.numel())
+        N = int(pos.shape[0])
+        natoms = batch.natoms.to(dev, torch.int64).reshape(-1)
+        start = torch.cumsum(natoms, 0) - natoms
+        # the atoms in the regrouped order of their sites
+        moved = natoms[self.perm]
+        new_off = torch.zeros(S + 1, dtype=torch.int64, device=dev)
+        new_off[1:] = torch.cumsum(moved, 0)
+        rows = torch.arange(N, device=dev) + torch.repeat_interleave(start[self.perm] - new_off[:-1], moved, output_size=N)
+        p = pos.detach().to(torch.float32)[rows].contiguous()
+        tags = batch.tags.to(dev)[rows].to(torch.int32).contiguous()
+        Z = batch.atomic_numbers.to(dev).long()[rows].to(torch.int32).contiguous()
+        cell = batch.cell.to(dev, torch.float32).reshape(S, 9)[self.perm].contiguous()
+        self.counts = (self.offsets[1:] - self.offsets[:-1]).long()
+        self.pair_offset = torch.zeros(self.G + 1, dtype=torch.int64, device=dev)
+        self.pair_offset[1:] = torch.cumsum(self.counts * self.counts, 0)
+        self.sizes = self.counts.tolist()                       # the one read-back: the output's size
+        self.total = sum(n * n for n in self.sizes)
+        self.dist = torch.empty(self.total, dtype=torch.float32, device=dev)
+        atom_offset = new_off.to(torch.int32)
+        with torch.cuda.device(dev):
+            _lib.check(lib.adf_site_pair_distances(p.data_ptr(), cell.data_ptr(), tags.data_ptr(), Z.data_ptr(),
+                                                   atom_offset.data_ptr(), self.offsets.data_ptr(),
+                                                   self.pair_offset.data_ptr(), N, S, self.G, self.total,
+                                                   int(bool(include_slab)), int(bool(permutation_invariant)),
+                                                   self.dist.data_ptr(), _stream(dev)))
+
+    def matrices(self):
+        out, at = [], 0
+        for n in self.sizes:
+            out.append(self.dist[at:at + n * n].view(n, n))
+            at += n * n
+        return out
+
+
+def site_distances(batch, group=None, include_slab: bool = True, permutation_invariant: bool = True):
+    """One [n,n] float32 matrix per distinct id of ``group`` (default ``batch.site_group``), ascending ids, rows and columns in
+    the caller's order of the group's sites: ``d = max(d_ads, d_slab)``, symmetric, zero diagonal, ``+inf`` between sites that
+    differ in atom count, tags or atomic numbers.  ``include_slab=False``: the adsorbate alone.  ``permutation_invariant``:
+    the adsorbate through the symmetric per-element Hausdorff distance (a flipped N2 is the same site) instead of atom by
+    atom."""
+    return _Matrices(batch, group, include_slab, permutation_invariant).matrices()
+
+
+def unique_sites(batch, group=None, tol: float = 0.05, energy=None, energy_tol: Optional[float] = None, flags=None,
+                 include_slab: bool = True, permutation_invariant: bool = True):
+    """(rep [S] long, is_rep [S] bool, n_unique [G] long).  Per group the valid sites (no flag set, energy not NaN) are
+    visited by (energy, the caller's order) - without ``energy`` in the caller's order - and each joins the first
+    representative within ``tol`` of it (and within ``energy_tol`` in energy, when given), or becomes one.  ``rep[s]`` is the
+    representative of site s in the caller's indexing, s itself for a representative, -1 for an invalid site."""
+    S = int(batch.natoms.shape[0])
+    if energy is not None and int(energy.numel()) != S:
+        raise ValueError(f"{S} sites, {int(energy.numel())} energies")
+    if flags is not None and tuple(flags.shape) != (S, 4):
+        raise ValueError(f"flags has shape {tuple(flags.shape)}, expected ({S}, 4)")
+    tol = float(tol)
+    if not (math.isfinite(tol) and tol >= 0):
+        raise ValueError(f"tol = {tol}: must be finite and not negative")
+    m = _Matrices(batch, group, include_slab, permutation_invariant)
+    lib, dev = _lib.load(), m.dev
+    e = None if energy is None else energy.detach().reshape(-1).to(dev, torch.float32)[m.perm].contiguous()
+    f = None if flags is None else flags.to(dev)[m.perm].to(torch.int32).contiguous()
+    rep = torch.empty(S, dtype=torch.int32, device=dev)
+    n_unique = torch.empty(m.G, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.adf_unique_sites(m.dist.data_ptr(), m.offsets.data_ptr(), m.pair_offset.data_ptr(), S, m.G, m.total,
+                                        None if e is None else e.data_ptr(), None if f is None else f.data_ptr(),
+                                        C.c_float(tol), C.c_float(-1.0 if energy_tol is None else float(energy_tol)),
+                                        rep.data_ptr(), n_unique.data_ptr(), _stream(dev)))
+    out = torch.empty(S, dtype=torch.long, device=dev)
+    out[m.perm] = to_caller_order(rep, m.perm)
+    return out, out == torch.arange(S, device=dev), n_unique.long()
+
+
+def top_sites(energy: torch.Tensor, flags: Optional[torch.Tensor], group, k: int, rep=None):
+    """(top [G,k] long, top_energy [G,k]) per distinct id of ``group`` (ascending): the k valid sites of least energy, ascending,
+    ties to the site that comes first in the caller's order; with ``rep`` (``unique_sites``) only representatives.  ``top``
+    indexes the caller's arrays; a group with fewer such sites has -1 and +inf in the remaining columns.  Column 0 without
+    ``rep`` is ``best_sites``."""
+    energy = energy.detach().reshape(-1)
+    S = int(energy.numel())
+    group = torch.as_tensor(group).reshape(-1)
+    if int(group.numel()) != S:
+        raise ValueError(f"{S} energies, {int(group.numel())} group ids")
+    if flags is not None and tuple(flags.shape) != (S, 4):
+        raise ValueError(f"flags has shape {tuple(flags.shape)}, expected ({S}, 4)")
+    if rep is not None and int(torch.as_tensor(rep).numel()) != S:
+        raise ValueError(f"{S} energies, {int(torch.as_tensor(rep).numel())} representatives")
+    if int(k) < 1:
+        raise ValueError(f"k = {k}: at least one site per group")
+    if S == 0:
+        raise ValueError("top_sites: no site")
+    if not energy.is_cuda:
+        raise RuntimeError("top_sites runs on a ROCm device (no CPU fallback)")
+    lib = _lib.load()
+    dev = energy.device
+    perm, offsets, ids = regroup(group.to(dev))
+    e = energy.to(torch.float32)[perm].contiguous()
+    f = None if flags is None else flags.to(dev)[perm].to(torch.int32).contiguous()
+    r = None if rep is None else to_group_order(torch.as_tensor(rep).to(dev).reshape(-1), perm).to(torch.int32).contiguous()
+    G, k = int(ids.numel()), int(k)
+    top = torch.empty(G, k, dtype=torch.int32, device=dev)
+    top_e = torch.empty(G, k, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.adf_select_top_sites(e.data_ptr(), None if f is None else f.data_ptr(),
+                                            None if r is None else r.data_ptr(), offsets.data_ptr(), G, k, top.data_ptr(),
+                                            top_e.data_ptr(), _stream(dev)))
+    return to_caller_order(top, perm), top_e

@@ -403,6 +403,49 @@ int32_t adf_flag_anomalies(const adf_batch* b, const float* pos_final, const flo
 int32_t adf_select_best_sites(const float* energy, const int32_t* flags, const int32_t* group_offset, int32_t num_groups,
                               int32_t* best, float* best_energy, int32_t* n_valid, void* stream);
 
+/* ---- Duplicate sites (csrc/unique.hip; adsorbdiff_amd/site_select.py).  An extension: the reference has no
+ * counterpart (scripts/run_vasp_dft/write_vasp_inputs_nsite.py takes the best N sites per slab on the host).  Every array
+ * is a device array, outputs are written with plain stores, there are no float atomics, nothing is read back and every
+ * result is bit-reproducible.  Sites are systems of a batch: atoms atom_offset[s] .. atom_offset[s+1] of pos / tags /
+ * atomic_numbers, cell [S,9] with rows = lattice vectors.  Sites of group g are group_offset[g] .. group_offset[g+1]: the
+ * caller has brought them into contiguous groups.
+ *
+ * adf_site_pair_distances.  Group g with n sites owns out[pair_offset[g] .. pair_offset[g] + n n): a full symmetric
+ * [n,n] matrix with a zero diagonal (a group whose matrix does not fit into out_len elements is left unwritten).
+ *   d(a,b) = max(d_ads, d_slab).  The displacement of two positions is the IS2RS metric's (adf_eval_is2rs;
+ *   scripts/eval.py:765-777 min_diff): fractional = (q - p) . inverse(cell of site a, a the earlier site of the pair), a
+ *   float32 explicit inverse; % 1 twice; minus 1 where > 0.5; times the cell; its Euclidean norm.  In a strongly skewed
+ *   cell this is the reference's convention and not the shortest lattice image.
+ *   d_slab: the largest displacement over the atoms of tag != 2, atom k of a against atom k of b; 0 when include_slab == 0.
+ *   d_ads, permutation_invariant == 0: the same over the atoms of tag 2.
+ *   d_ads, permutation_invariant == 1: the symmetric per-element Hausdorff distance of the two adsorbates: the largest,
+ *     over the adsorbate atoms of a, of the least displacement to an adsorbate atom of b of the same atomic number, and
+ *     the same with a and b exchanged; the larger of the two.  A flipped N2 is at distance 0 from itself; the value equals
+ *     the ordered one whenever that is below half the shortest same-element separation.
+ *   An adsorbate without atoms has d_ads = 0.  d = +inf when the two sites differ in atom count or anywhere in the ordered
+ *   tags or atomic numbers (so also in adsorbate size).  A non-finite coordinate gives NaN, which is within no tolerance.
+ *   One wave per pair i < j, lanes over atoms, mirrored to (j, i). */
+int32_t adf_site_pair_distances(const float* pos, const float* cell, const int32_t* tags, const int32_t* atomic_numbers,
+                                const int32_t* atom_offset, const int32_t* group_offset, const int64_t* pair_offset,
+                                int32_t num_atoms, int32_t num_sites, int32_t num_groups, int64_t out_len,
+                                int32_t include_slab, int32_t permutation_invariant, float* out, void* stream);
+/* Greedy clustering of each group on the matrices of adf_site_pair_distances (dist, dist_len elements).  A site is valid
+ * when its four flags (flags [S,4], NULL: no filter) are 0 and its energy (energy [S], NULL: none) is not NaN.  An invalid
+ * site gets rep = -1; it is never a representative and nothing is merged into it.  Valid sites are visited in the order
+ * (energy ascending, position in the group); without energies in the order of position.  A visited site s joins the first
+ * representative r, in visiting order, with dist(s,r) <= tol and, when energy_tol >= 0 and energies are given,
+ * |E_s - E_r| <= energy_tol (the difference is taken in double); rep[s] = r, an index into the site arrays.  Without
+ * such a representative s becomes one: rep[s] = s.  n_unique[g]: representatives of the group.  tol must be finite and
+ * >= 0.  One workgroup per group, the sort inside it; a group may hold any number of sites. */
+int32_t adf_unique_sites(const float* dist, const int32_t* group_offset, const int64_t* pair_offset, int32_t num_sites,
+                         int32_t num_groups, int64_t dist_len, const float* energy, const int32_t* flags, float tol,
+                         float energy_tol, int32_t* rep, int32_t* n_unique, void* stream);
+/* The k valid sites of least energy per group, ascending, ties to the lower index (validity as adf_select_best_sites);
+ * with rep (may be NULL) only representatives, rep[s] == s.  top [G,k]: indices into `energy`, -1 where the group has
+ * fewer; top_energy [G,k]: their energies, +inf there.  Column 0 with rep == NULL is adf_select_best_sites' answer. */
+int32_t adf_select_top_sites(const float* energy, const int32_t* flags, const int32_t* rep, const int32_t* group_offset,
+                             int32_t num_groups, int32_t k, int32_t* top, float* top_energy, void* stream);
+
 /* ---- Adsorbate placement (csrc/placement.hip; adsorbdiff_amd/placement.py): the reference's
  * AdsorbateSlabConfig, placement/adsorbate_slab_config.py:99-439, 460-575 with adsorbate.py:122-169, modes "random"
  * [mode 0] and "random_site_heuristic_placement" [mode 1], for a whole batch of slabs.  This is a written contract, a
