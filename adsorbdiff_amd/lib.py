@@ -5,7 +5,9 @@ no fallback: if the library is missing or a call fails, an exception is
 raised — ``RuntimeError`` for out-of-memory / HIP errors (so that
 ``ml_diffuse``'s split-and-retry contract works, reference
 relaxation/ml_relaxation.py:146-165) and ``ValueError`` for an image without
-neighbours (reference painn_denoising.py:370-375).
+neighbours (reference painn_denoising.py:370-375) and for a structure beyond a
+fixed capacity of the graph builder (``ADF_EOVERFLOW``: splitting the batch does
+not help).
 """
 from __future__ import annotations
 
@@ -310,6 +312,10 @@ def check(status: int) -> None:
     msg = load().adf_last_error().decode("utf-8", "replace")
     if status == ADF_ENONEIGHBOR:
         raise ValueError(msg)
+    if status == ADF_EOVERFLOW:
+        # a property of one structure (candidates around a centre, incoming edges of an atom): halving the batch, which is
+        # what ``ml_diffuse`` / ``ml_relax`` answer a RuntimeError with, cannot cure it
+        raise ValueError(f"adsorbdiff_hip: capacity exceeded: {msg}")
     if status == ADF_EOOM:
         raise RuntimeError(f"HIP out of memory: {msg}")
     if status == ADF_ENUMERIC:
