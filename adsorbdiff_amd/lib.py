@@ -39,6 +39,7 @@ EXPORTS = (
     "adf_site_pair_distances", "adf_unique_sites", "adf_select_top_sites",
     "adf_place_draws", "adf_place_adsorbates", "adf_place_site_candidates", "adf_interstitial_distances", "adf_comm_unique_id", "adf_comm_create", "adf_comm_destroy", "adf_allgather_sites",
     "adf_op_linear_fwd", "adf_op_linear_bwd_scratch", "adf_op_linear_bwd", "adf_op_ssilu_fwd", "adf_op_ssilu_bwd", "adf_op_layernorm_fwd", "adf_op_layernorm_bwd", "adf_op_embed_fwd", "adf_op_embed_bwd", "adf_op_rbf", "adf_op_message_fwd", "adf_op_message_fwd_fused", "adf_op_message_bwd", "adf_op_message_bwd_fused", "adf_op_message_bwd_fused_supported", "adf_op_message_bwd_perm", "adf_op_edge_owner", "adf_op_rbf_image_bytes", "adf_op_rbf_image", "adf_op_rbf_wgrad_fused_scratch", "adf_op_rbf_wgrad_fused", "adf_op_vdot_fwd", "adf_op_vdot_bwd", "adf_op_update_out_fwd", "adf_op_update_out_bwd", "adf_op_vnorm_fwd", "adf_op_vnorm_bwd", "adf_op_gate_fwd", "adf_op_gate_bwd", "adf_op_copy_rows", "adf_op_score_loss", "adf_op_score_loss_tr", "adf_op_s2ef_loss", "adf_op_s2ef_loss_scratch", "adf_op_energy_sum", "adf_op_energy_head_bwd", "adf_op_energy_head_bwd_scratch", "adf_op_sqnorm_accumulate", "adf_op_adamw_step",
+    "adf_op_optimizer_chunk", "adf_op_grad_sqnorm_multi", "adf_op_adamw_multi", "adf_op_embed_bwd_ordered", "adf_op_embed_bwd_ordered_scratch",
     "adf_noise_draws", "adf_noise_tr_so3", "adf_noise_com", "adf_igso3_score_norm",
     "adf_eval_scratch", "adf_eval_s2ef", "adf_eval_is2rs", "adf_eval_is2re", "adf_eval_add",
     "adf_eqv2_create", "adf_eqv2_destroy", "adf_eqv2_set_constants", "adf_eqv2_set_weights", "adf_eqv2_set_arithmetic",
@@ -245,6 +246,9 @@ def load():
         "adf_op_energy_head_bwd": [vp, vp, vp, vp, vp, vp, vp, i32, i64, i32, vp, vp],
         "adf_op_sqnorm_accumulate": [vp, i64, vp, vp],
         "adf_op_adamw_step": [vp, vp, vp, vp, vp, i64, vp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, i32, C.c_float, vp],
+        "adf_op_grad_sqnorm_multi": [vp, vp, i32, vp, vp, C.c_float, C.c_double, C.c_double, C.c_float, i64, vp],
+        "adf_op_adamw_multi": [vp, vp, i32, vp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, vp],
+        "adf_op_embed_bwd_ordered": [vp, vp, vp, i32, i32, i32, vp, vp],
         "adf_eval_s2ef": [vp, vp, vp, vp, vp, vp, i32, i32, i32, C.c_float, C.c_float, C.c_float, C.c_float, vp, vp, vp, vp],
         "adf_eval_is2rs": [vp, vp, vp, vp, vp, i32, i32, vp, i32, vp, vp, vp, vp],
         "adf_eval_is2re": [vp, vp, i32, vp, vp, vp],
@@ -297,6 +301,10 @@ def load():
     lib.adf_op_s2ef_loss_scratch.restype = i64
     lib.adf_op_energy_head_bwd_scratch.argtypes = [i64, i32]
     lib.adf_op_energy_head_bwd_scratch.restype = i64
+    lib.adf_op_optimizer_chunk.argtypes = []
+    lib.adf_op_optimizer_chunk.restype = i64
+    lib.adf_op_embed_bwd_ordered_scratch.argtypes = [i64, i32, i32]
+    lib.adf_op_embed_bwd_ordered_scratch.restype = i64
     lib.adf_eval_scratch.argtypes = [i32]
     lib.adf_eval_scratch.restype = i64
     lib.adf_frames_pushed.argtypes = [vp]

@@ -19,6 +19,7 @@ gradients), message forward AND backward through fused kernels that regenerate t
 """
 from __future__ import annotations
 
+import copy
 import os
 
 import ctypes as C
@@ -111,6 +112,9 @@ class _PaiNNStepBase:
                 f"backward), got {R}")
         self.ops = _Ops(self.dev)
         self.lib = self.ops.lib
+        # the embedding gradient summed in a fixed order (csrc/optimizer.hip: adf_op_embed_bwd_ordered) instead of with
+        # float atomics: with it every gradient of the step is bit-reproducible (setup_training(reproducible=True))
+        self.ordered_embedding_backward = False
 
     # ------------------------------------------------------------------ helpers
     def _params(self) -> Dict[str, torch.nn.Parameter]:
@@ -362,8 +366,14 @@ class _PaiNNStepBase:
             dx, dvec = dx_in, dvec_in
             if grads_ready is not None:
                 grads_ready([mp, up])
-        _lib.check(lib.adf_op_embed_bwd(dx.data_ptr(), prep.atomic_numbers.data_ptr(),
-                                        G["atom_emb.embeddings.weight"].data_ptr(), N, H, s()))
+        demb = G["atom_emb.embeddings.weight"]
+        if self.ordered_embedding_backward:
+            rows = int(demb.shape[0])
+            sc = ops.scratch(int(lib.adf_op_embed_bwd_ordered_scratch(N, H, rows)))
+            _lib.check(lib.adf_op_embed_bwd_ordered(dx.data_ptr(), prep.atomic_numbers.data_ptr(), demb.data_ptr(), N, H, rows,
+                                                    sc.data_ptr(), s()))
+        else:
+            _lib.check(lib.adf_op_embed_bwd(dx.data_ptr(), prep.atomic_numbers.data_ptr(), demb.data_ptr(), N, H, s()))
         if grads_ready is not None:
             grads_ready(["atom_emb."])
 
@@ -609,6 +619,217 @@ class FusedAdamW:
                 stream))
             i += 1
         return self.sqnorm.sqrt()
+
+
+# ------------------------------------------------------------------------------------------------ reproducible optimizer
+def reference_param_groups(model, weight_decay: float) -> list:
+    """The parameter groups of the reference's ``load_optimizer`` (base_trainer.py:556-609).  ``weight_decay > 0``: group 0
+    holds the trainable parameters whose name ends with one of ``model.no_weight_decay()`` (weight decay 0), group 1 the
+    other trainable ones, each in ``named_parameters()`` order; ``weight_decay == 0``: one group of ``model.parameters()``."""
+    if weight_decay > 0:
+        skip = tuple(model.no_weight_decay()) if hasattr(model, "no_weight_decay") else ()
+        no_decay, decay = [], []
+        for name, p in model.named_parameters():
+            if not p.requires_grad:
+                continue
+            (no_decay if any(name.endswith(s) for s in skip) else decay).append(p)
+        return [{"params": no_decay, "weight_decay": 0}, {"params": decay, "weight_decay": weight_decay}]
+    return [{"params": list(model.parameters())}]
+
+
+def adamw_state_to_flat(state_dict: dict):
+    """``torch.optim.AdamW.state_dict()`` -> ``(step, {index: (exp_avg, exp_avg_sq)}, param_groups)``: the one step counter
+    the multi-tensor optimizer keeps (0 for an empty state) and the moments by parameter index.  Per-parameter ``step``
+    values that differ raise ``ValueError``: there is one counter."""
+    steps = sorted({float(e["step"]) for e in state_dict["state"].values()})
+    if len(steps) > 1:
+        raise ValueError(f"the per-parameter step counts differ ({steps}); MultiTensorAdamW keeps one counter")
+    step = int(steps[0]) if steps else 0
+    if steps and float(step) != steps[0]:
+        raise ValueError(f"step count {steps[0]} is not an integer")
+    moments = {int(i): (e["exp_avg"], e["exp_avg_sq"]) for i, e in state_dict["state"].items()}
+    return step, moments, [dict(g) for g in state_dict["param_groups"]]
+
+
+def flat_to_adamw_state(step: int, moments: dict, param_groups: list) -> dict:
+    """The inverse of ``adamw_state_to_flat``: torch's AdamW layout, ``step`` as the float32 CPU scalar torch keeps."""
+    state = {int(i): {"step": torch.tensor(float(step), dtype=torch.float32), "exp_avg": m, "exp_avg_sq": v}
+             for i, (m, v) in moments.items()}
+    return {"state": state, "param_groups": [dict(g) for g in param_groups]}
+
+
+class MultiTensorAdamW(torch.optim.Optimizer):
+    """AdamW + global-norm clipping + EMA over every parameter tensor in three launches (csrc/optimizer.hip): the squared
+    gradient norm in a fixed order (``adf_op_grad_sqnorm_multi``: one partial per chunk of ``chunk`` elements, added in index
+    order in double) and ``tr_adamw_kernel``'s arithmetic over all chunks (``adf_op_adamw_multi``).  The step counter, the bias
+    corrections, the clip factor and the EMA decay of the step live in a device state block; a step with a non-finite norm
+    changes nothing but the block's ``skipped`` count.  ``step()`` reads nothing back.
+
+    A ``torch.optim.Optimizer``: ``param_groups`` as the reference builds them (``reference_param_groups``), so torch's
+    schedulers accept it, and ``state_dict()`` / ``load_state_dict()`` speak ``torch.optim.AdamW``'s layout.  ``step()`` takes
+    the learning rate from ``param_groups[0]["lr"]`` and passes it to the kernel as an argument."""
+
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm: Optional[float] = None,
+                 ema=None) -> None:
+        # torch's own defaults for this version, so that a state written here loads into torch.optim.AdamW and runs
+        defaults = dict(torch.optim.AdamW([torch.nn.Parameter(torch.zeros(1))]).defaults)
+        defaults.update(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay)
+        super().__init__(reference_param_groups(model, weight_decay), defaults)
+        self.lib = _lib.load()
+        self.model = model
+        self.max_grad_norm = max_grad_norm
+        self.ema = ema
+        self.chunk = int(self.lib.adf_op_optimizer_chunk())
+        self.params = [p for g in self.param_groups for p in g["params"]]
+        if not self.params:
+            raise ValueError("MultiTensorAdamW: the model has no parameters")
+        self.dev = self.params[0].device
+        if self.dev.type != "cuda":
+            raise RuntimeError("MultiTensorAdamW needs a ROCm device (the HIP path has no CPU fallback)")
+        for p in self.params:
+            if p.dtype != torch.float32 or not p.is_contiguous() or p.device != self.dev:
+                raise ValueError("MultiTensorAdamW: parameters must be contiguous float32 tensors on one device")
+        self.exp_avg = [torch.zeros_like(p, memory_format=torch.contiguous_format) for p in self.params]
+        self.exp_avg_sq = [torch.zeros_like(p, memory_format=torch.contiguous_format) for p in self.params]
+        self.had_grad = [False] * len(self.params)
+        # chunk table: fixed for the life of the optimizer (every tensor, with or without a gradient)
+        chunks = []
+        for t, p in enumerate(self.params):
+            chunks += [(t, o) for o in range(0, p.numel(), self.chunk)]
+        self._chunks = np.asarray(chunks, dtype=np.int64).reshape(-1, 2)
+        self.nchunks = int(self._chunks.shape[0])
+        T = len(self.params)
+        self._tables = torch.zeros(8 * T + 2 * self.nchunks, dtype=torch.int64, device=self.dev)
+        self._partials = torch.zeros(self.nchunks, dtype=torch.float32, device=self.dev)
+        # state block: int64 applied, skipped; int32 apply; float clip, bc1, bc2, ema_decay, sqnorm
+        self._state = torch.zeros(5, dtype=torch.int64, device=self.dev)
+        self._sqnorm = self._state.view(torch.float32)[9:10]
+        self._signature = None
+        self._applied_sync = 0     # the device counter as last read or written by the host
+        self.resync_ema()
+
+    # ------------------------------------------------------------------ tables
+    def _shadow_of(self) -> dict:
+        if self.ema is None:
+            return {}
+        trainable = [p for p in self.model.parameters() if p.requires_grad]
+        return {id(p): s for p, s in zip(trainable, self.ema.shadow_params)}
+
+    def _refresh_tables(self) -> None:
+        """Rebuilds and uploads the tables (one asynchronous copy) when a pointer or a gradient's presence changed."""
+        shadows = self._shadow_of()
+        rows = []
+        for i, p in enumerate(self.params):
+            g = p.grad if p.requires_grad else None
+            s = shadows.get(id(p))
+            rows.append((p.data_ptr(), g.data_ptr() if g is not None else 0, self.exp_avg[i].data_ptr(),
+                         self.exp_avg_sq[i].data_ptr(), s.data_ptr() if s is not None else 0))
+        signature = tuple(rows)
+        if signature == self._signature:
+            return
+        decay = {id(p): 1 if g.get("weight_decay", 0) else 0 for g in self.param_groups for p in g["params"]}
+        host = torch.empty(self._tables.numel(), dtype=torch.int64).pin_memory()
+        tab = host.numpy()
+        T = len(self.params)
+        for i, (p, row) in enumerate(zip(self.params, rows)):
+            g = p.grad if p.requires_grad else None
+            if g is not None:
+                if g.dtype != torch.float32 or not g.is_contiguous() or g.shape != p.shape or g.device != p.device:
+                    raise ValueError("MultiTensorAdamW: gradients must be contiguous float32 tensors of their parameter's shape")
+                self.had_grad[i] = True
+            s = shadows.get(id(p))
+            if s is not None and (s.dtype != torch.float32 or not s.is_contiguous() or s.shape != p.shape
+                                  or s.device != p.device):
+                raise ValueError("MultiTensorAdamW: EMA shadows must be contiguous float32 tensors of their parameter's shape")
+            tab[8 * i: 8 * i + 8] = (*row, p.numel(), decay[id(p)], 0)
+        tab[8 * T:] = self._chunks.reshape(-1)
+        self._tables.copy_(host, non_blocking=True)
+        self._signature = signature
+
+    def _weight_decay(self) -> float:
+        values = {float(g.get("weight_decay", 0)) for g in self.param_groups} - {0.0}
+        if len(values) > 1:
+            raise ValueError(f"MultiTensorAdamW takes one non-zero weight decay, the groups hold {sorted(values)}")
+        return values.pop() if values else 0.0
+
+    # ------------------------------------------------------------------ the step
+    @torch.no_grad()
+    def step(self, closure=None) -> torch.Tensor:
+        """Applies the update from ``param.grad``; returns the (pre-clip) global gradient norm as a device tensor."""
+        if closure is not None:
+            raise NotImplementedError("MultiTensorAdamW.step takes no closure")
+        g0 = self.param_groups[0]
+        beta1, beta2 = g0["betas"]
+        with torch.cuda.device(self.dev):
+            self._refresh_tables()
+            stream = C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
+            tensors = self._tables.data_ptr()
+            chunks = tensors + 8 * 8 * len(self.params)
+            _lib.check(self.lib.adf_op_grad_sqnorm_multi(
+                tensors, chunks, self.nchunks, self._partials.data_ptr(), self._state.data_ptr(),
+                C.c_float(self.max_grad_norm or 0.0), C.c_double(beta1), C.c_double(beta2),
+                C.c_float(self.ema.decay if self.ema is not None else 0.0), self._ema_n0, stream))
+            _lib.check(self.lib.adf_op_adamw_multi(
+                tensors, chunks, self.nchunks, self._state.data_ptr(), C.c_float(g0["lr"]), C.c_float(beta1),
+                C.c_float(beta2), C.c_float(g0["eps"]), C.c_float(self._weight_decay()), stream))
+        return self._sqnorm.sqrt()
+
+    # ------------------------------------------------------------------ counters and state
+    def counters(self) -> dict:
+        """``{"applied", "skipped"}`` read from the device (a synchronising read: not for the step loop)."""
+        applied, skipped = (int(v) for v in self._state[:2].tolist())
+        return {"applied": applied, "skipped": skipped}
+
+    def resync_ema(self) -> None:
+        """Call after ``ema.load_state_dict`` / a new ``ema.num_updates``: the device forms the EMA decay of a step from
+        ``num_updates`` at the last synchronisation plus the updates applied since."""
+        n = getattr(self.ema, "num_updates", None) if self.ema is not None else None
+        self._ema_n0 = -1 if n is None else int(n) - self._applied_sync
+        self._signature = None   # the shadow tensors may be new ones
+
+    def _sync_counter(self) -> int:
+        applied = self.counters()["applied"]
+        if self.ema is not None and self.ema.num_updates is not None:
+            self.ema.num_updates = self._ema_n0 + applied
+        self._applied_sync = applied
+        return applied
+
+    def state_dict(self) -> dict:
+        """``torch.optim.AdamW``'s layout; ``step`` is the device counter, read here and only here, and
+        ``ema.num_updates`` is refreshed from it.  A parameter that never had a gradient has no entry."""
+        applied = self._sync_counter()
+        moments = {i: (self.exp_avg[i], self.exp_avg_sq[i]) for i in range(len(self.params)) if self.had_grad[i]}
+        groups, start = [], 0
+        for g in self.param_groups:
+            packed = {k: v for k, v in g.items() if k != "params"}
+            packed["params"] = list(range(start, start + len(g["params"])))
+            start += len(g["params"])
+            groups.append(packed)
+        return flat_to_adamw_state(applied, moments, groups)
+
+    def load_state_dict(self, state_dict: dict) -> None:
+        step, moments, groups = adamw_state_to_flat(state_dict)
+        if len(groups) != len(self.param_groups) or any(len(a["params"]) != len(b["params"])
+                                                        for a, b in zip(groups, self.param_groups)):
+            raise ValueError("loaded state dict has different parameter groups")
+        for i, (m, v) in moments.items():
+            if not 0 <= i < len(self.params) or m.shape != self.params[i].shape or v.shape != self.params[i].shape:
+                raise ValueError(f"loaded state of parameter {i} does not fit")
+        with torch.no_grad():
+            for i in range(len(self.params)):
+                if i in moments:
+                    self.exp_avg[i].copy_(moments[i][0])
+                    self.exp_avg_sq[i].copy_(moments[i][1])
+                else:
+                    self.exp_avg[i].zero_()
+                    self.exp_avg_sq[i].zero_()
+                self.had_grad[i] = i in moments
+        for mine, theirs in zip(self.param_groups, groups):
+            mine.update({k: copy.deepcopy(v) for k, v in theirs.items() if k != "params"})
+        self._state.zero_()
+        self._state[0] = step
+        self._applied_sync = step
+        self.resync_ema()
 
 
 class GradientReducer:

@@ -6,9 +6,9 @@ denoising_torch.py:38,491-500): ``predict_denoising(batch, per_image=False)``,
 
 ``train_step`` is the per-batch body of the reference's training loop (sde_denoising_trainer.py:410-441 +
 base_trainer.py:787-820): noising, forward, loss, backward, gradient all-reduce, clipping, AdamW, EMA — all device
-arithmetic in HIP kernels (adsorbdiff_amd/train_step.py).  Datasets, LR schedules, logging, evaluation and checkpoint
-*writing* stay out of scope; ``load_checkpoint`` reads the reference's checkpoint layout
-(base_trainer.py:456-533) so trained weights can be sampled with.  ``ForcesTrainer.train_step`` is the same body for the
+arithmetic in HIP kernels (adsorbdiff_amd/train_step.py).  ``train``, ``save``, ``load_checkpoint`` and ``update_best`` come
+from ``train_loop.TrainLoopMixin`` (the reference's epoch loop, checkpoint layout of base_trainer.py:456-533, 625-704, LR
+schedules of ``lr_scheduler``); datasets and data loaders stay out of scope.  ``ForcesTrainer.train_step`` is the same body for the
 S2EF force field (trainers/ocp_trainer.py:115-246, loss :308-356).
 """
 from __future__ import annotations
@@ -22,6 +22,7 @@ import torch
 from .ml_relaxation import ml_diffuse
 from .painn_denoising import PaiNN
 from .scaling import ensure_fitted
+from .train_loop import TrainLoopMixin
 
 
 def check_traj_files(batch, traj_dir) -> bool:
@@ -33,7 +34,9 @@ def check_traj_files(batch, traj_dir) -> bool:
     return all((traj_dir / f"{sid}.traj").exists() or (traj_dir / f"{sid}.npz").exists() for sid in batch.sid)
 
 
-class DenoisingTrainer:
+class DenoisingTrainer(TrainLoopMixin):
+    name = "ocp"   # the task validate() evaluates under: no metrics but `loss`
+
     def __init__(self, model: PaiNN, device="cuda:0", config: Optional[dict] = None, ema=None, relax_loader=None):
         self.device = torch.device(device)
         self.model = model.to(self.device)
@@ -84,17 +87,21 @@ class DenoisingTrainer:
     # ---------------------------------------------------------------- training
     def setup_training(self, denoising_pos_params: dict, lr: float = 1e-3, weight_decay: float = 0.001,
                        clip_grad_norm: float = 100.0, ema_decay: float = 0.999, tables=None,
-                       noise_on_device: bool = False, noise_seed: int = 0) -> None:
+                       noise_on_device: bool = False, noise_seed: int = 0, reproducible: bool = False) -> None:
         """Optimizer / EMA / noising parameters; defaults = configs/denoising/painn_so3.yml:56-83 (AdamW, weight decay
         1e-3 except no_weight_decay() names, clip 100, EMA 0.999).  ``noise_on_device``: ``train_step`` and ``validate``
         noise through ``noising.DeviceNoiser`` (counter-based draws keyed by ``noise_seed``, the step number and
         ``noising.noise_keys(batch)``: no host round trip, and a system's noise does not depend on its batch or rank);
-        off (default): the reference's stream order on the host."""
+        off (default): the reference's stream order on the host.  ``reproducible``: ``MultiTensorAdamW`` (ordered gradient
+        norm, device step counter, torch's state layout and schedulers) in place of ``FusedAdamW``, and the embedding
+        gradient summed in a fixed order: with ``noise_on_device`` a run resumed from a checkpoint retraces the
+        uninterrupted one to the bit."""
         from .exponential_moving_average import ExponentialMovingAverage
-        from .train_step import FusedAdamW, PaiNNTrainStep
+        from .train_step import FusedAdamW, MultiTensorAdamW, PaiNNTrainStep
 
         self.denoising_pos_params = dict(denoising_pos_params)
         self.train_engine = PaiNNTrainStep(self._unwrapped_model, self.device, igso3=tables)
+        self.train_engine.ordered_embedding_backward = bool(reproducible)
         self.noiser = None
         if noise_on_device:
             from .noising import DeviceNoiser
@@ -103,8 +110,9 @@ class DenoisingTrainer:
         self.noise_step = 0
         if ema_decay:
             self.ema = ExponentialMovingAverage(self._unwrapped_model.parameters(), ema_decay)
-        self.optimizer = FusedAdamW(self._unwrapped_model, lr=lr, weight_decay=weight_decay, max_grad_norm=clip_grad_norm,
-                                    ema=self.ema)
+        self.optimizer = (MultiTensorAdamW if reproducible else FusedAdamW)(
+            self._unwrapped_model, lr=lr, weight_decay=weight_decay, max_grad_norm=clip_grad_norm, ema=self.ema)
+        self.scheduler = None
         self.step = 0
 
     def _noise(self, batch, params, tables, noise_step=None, draws=None):
@@ -267,29 +275,6 @@ class DenoisingTrainer:
                 self.ema.restore()
         return dm.all_reduce().result(evaluator.metric_names() + ["loss"])
 
-    # ---------------------------------------------------------------- checkpoint ingest
-    def load_checkpoint(self, checkpoint_path: str) -> None:
-        """Reads ``state_dict`` (with 0-2 ``module.`` prefixes) from a reference checkpoint
-        (base_trainer.py:456-533).  ``ema`` shadow parameters, if present, are applied directly."""
-        ckpt = torch.load(checkpoint_path, map_location="cpu")
-        sd = ckpt.get("state_dict", ckpt)
-        clean = {}
-        for k, v in sd.items():
-            while k.startswith("module."):
-                k = k[len("module."):]
-            clean[k] = v
-        missing, unexpected = self._unwrapped_model.load_state_dict(clean, strict=False)
-        for k in missing:
-            logging.warning(f"checkpoint is missing key {k}")
-        for k in unexpected:
-            logging.warning(f"checkpoint has unexpected key {k}")
-        ema = ckpt.get("ema")
-        if ema and "shadow_params" in ema:
-            params = [p for p in self._unwrapped_model.parameters() if p.requires_grad]
-            with torch.no_grad():
-                for p, s in zip(params, ema["shadow_params"]):
-                    p.copy_(s.to(p.device))
-
     # ---------------------------------------------------------------- sampling entry
     def run_relaxations(self, batches: Optional[Iterable] = None):
         """``--mode run-relaxations`` (reference :750-813): for every batch of the relax loader not
@@ -343,12 +328,14 @@ class Normalizer:
 _NORMALIZER_KEYS = {"target": "energy", "grad_target": "forces"}
 
 
-class ForcesTrainer:
+class ForcesTrainer(TrainLoopMixin):
     """The part of the reference's S2EF trainer (trainers/ocp_trainer.py:405-460, base_trainer.py:353-362) that
     ``ml_relax`` / ``TorchCalc`` touch: ``predict(batch, per_image=False)`` -> ``{"energy", "forces"}`` with the EMA weights
     swapped in for the forward and the normalizers' ``denorm`` applied, ``_unwrapped_model``, ``normalizers``.
     ``normalizers``: ``{"energy" | "target": {"mean", "stdev"}, ...}`` as in the
     dataset config (``transforms.normalizer``), or ready ``Normalizer`` objects."""
+
+    name = "s2ef"   # the task validate() evaluates under
 
     def __init__(self, model, device="cuda:0", normalizers: Optional[dict] = None, ema=None, config: Optional[dict] = None):
         self.device = torch.device(device)
@@ -382,14 +369,15 @@ class ForcesTrainer:
     # ---------------------------------------------------------------- training
     def setup_training(self, lr: float, weight_decay: float = 0.001, clip_grad_norm: float = 10.0, ema_decay: float = 0.999,
                        energy_coefficient: float = 1, force_coefficient: float = 30, loss_energy: str = "mae",
-                       loss_force: str = "l2mae", train_on_free_atoms: bool = True) -> None:
+                       loss_force: str = "l2mae", train_on_free_atoms: bool = True, reproducible: bool = False) -> None:
         """Optimizer / EMA / objective of ``train_step``.  AdamW with weight decay except ``no_weight_decay()`` names;
         clip 10 and EMA 0.999 as configs/relaxation/gemnet_oc/gemnet_relax.yml:107-108; coefficients and
         ``train_on_free_atoms`` as the reference's defaults (utils/utils.py:1227,1257, base_trainer.py:382-390; the shipped
         YAMLs pass force_coefficient 100).  The targets are normalised with this trainer's ``normalizers``.  Only the loss
-        names the shipped configs use are offered (energy "mae", forces "l2mae"); any other name is refused here."""
+        names the shipped configs use are offered (energy "mae", forces "l2mae"); any other name is refused here.
+        ``reproducible``: as ``DenoisingTrainer.setup_training``."""
         from .exponential_moving_average import ExponentialMovingAverage
-        from .train_step import FusedAdamW, PaiNNS2EFTrainStep
+        from .train_step import FusedAdamW, MultiTensorAdamW, PaiNNS2EFTrainStep
 
         if loss_energy != "mae" or loss_force != "l2mae":
             raise NotImplementedError(
@@ -398,10 +386,12 @@ class ForcesTrainer:
         self.train_engine = PaiNNS2EFTrainStep(self._unwrapped_model, self.device, normalizers=self.normalizers,
                                                energy_coefficient=energy_coefficient, force_coefficient=force_coefficient,
                                                train_on_free_atoms=train_on_free_atoms)
+        self.train_engine.ordered_embedding_backward = bool(reproducible)
         # a falsy ema_decay trains without an EMA: one that was loaded or set up earlier is dropped, not updated on
         self.ema = ExponentialMovingAverage(self._unwrapped_model.parameters(), ema_decay) if ema_decay else None
-        self.optimizer = FusedAdamW(self._unwrapped_model, lr=lr, weight_decay=weight_decay, max_grad_norm=clip_grad_norm,
-                                    ema=self.ema)
+        self.optimizer = (MultiTensorAdamW if reproducible else FusedAdamW)(
+            self._unwrapped_model, lr=lr, weight_decay=weight_decay, max_grad_norm=clip_grad_norm, ema=self.ema)
+        self.scheduler = None
         self.step = 0
 
     def train_step(self, batch) -> dict:

@@ -679,6 +679,32 @@ int32_t adf_op_adamw_step(float* p, const float* g, float* m, float* v, float* e
                           float max_norm, float lr, float beta1, float beta2, float eps, float weight_decay, int32_t step,
                           float ema_decay, void* stream);
 
+/* ---- Reproducible optimizer step and embedding backward (csrc/optimizer.hip): no float atomics, every sum
+ * in an order that depends on the data and on the chunk length L alone.
+ * Tables (device memory, written by the host as int64 words): one row of 8 words per tensor
+ *   { p, g, m, v, ema (pointers; g or ema may be 0), numel, weight-decay flag, 0 }
+ * and one row of 2 words per chunk { tensor, offset }: every tensor is cut into chunks of L elements, the last one short.
+ * State block (40 bytes): int64 applied, int64 skipped, int32 apply, float clip, bc1, bc2, ema_decay, sqnorm.
+ * The chunk length L: */
+int64_t adf_op_optimizer_chunk(void);
+/* Squared gradient norm over all chunks (partials: nchunks floats, one ordinary store each; then one workgroup adds them in
+ * index order in double) and the step's decision: apply = isfinite(sqnorm); if set, applied += 1, bc_k = 1 - beta_k^applied
+ * in double, clip = min(1, max_norm / (sqrt(sqnorm) + 1e-6)) (max_norm <= 0: 1), ema_decay = min(ema_decay,
+ * (1 + n) / (10 + n)) with n = ema_updates0 + applied (ema_updates0 < 0: ema_decay as given); else skipped += 1. */
+int32_t adf_op_grad_sqnorm_multi(const void* tensors, const void* chunks, int32_t nchunks, float* partials, void* state,
+                                 float max_norm, double beta1, double beta2, float ema_decay, int64_t ema_updates0,
+                                 void* stream);
+/* AdamW + clip + EMA over all chunks in one launch, reading apply / clip / bc1 / bc2 / ema_decay from the state block; the
+ * element arithmetic is the one behind the per-tensor step above.  Tensors without a gradient are skipped. */
+int32_t adf_op_adamw_multi(const void* tensors, const void* chunks, int32_t nchunks, const void* state, float lr, float beta1,
+                           float beta2, float eps, float weight_decay, void* stream);
+/* demb[Z[n]-1, :] += dx[n, :] (demb: [rows, H]) in segments of 64 atoms: per segment one partial row per element present
+ * (atoms in index order), then per element the segments in index order.  Rows of absent elements are not written; Z outside
+ * 1..rows contributes nothing.  scratch: the number of floats the _scratch entry returns. */
+int32_t adf_op_embed_bwd_ordered(const float* dx, const int32_t* Z, float* demb, int32_t N, int32_t H, int32_t rows,
+                                 float* scratch, void* stream);
+int64_t adf_op_embed_bwd_ordered_scratch(int64_t N, int32_t H, int32_t rows);
+
 /* ---- Evaluation metrics (csrc/evaluate.hip): modules/evaluator.py for the tasks "s2ef", "is2rs", "is2re", and the
  * per-batch loss of BaseTrainer.validate (trainers/base_trainer.py:712-785), accumulated on the device.
  * Accumulator: caller-owned device memory, double total[ADF_EVAL_SLOTS] and int64_t numel[ADF_EVAL_SLOTS], indexed by the
