@@ -1070,7 +1070,14 @@ static void model_prof(void* h, bool begin, hipStream_t s) {
     if (begin) adf_prof_begin((adf_painn*)h, ADF_PROF_STEPPER, s);
     else adf_prof_end((adf_painn*)h, s);
 }
-static adf_model model(adf_painn_t h) { return {h, model_check, model_grow, model_forward, model_prof}; }
+static adf_model model(adf_painn_t h) {
+    return {h, model_check, model_grow, model_forward, model_prof, h ? h->ps_state : nullptr, h ? h->ps_B : 0};
+}
+
+extern "C" int32_t adf_painn_set_per_system_stop(adf_painn_t h, int32_t* sys_state, int32_t B) {
+    if (!h) { adf_set_error("null handle"); return ADF_EINVAL; }
+    return adf_model_set_per_system_stop(&h->ps_state, &h->ps_B, sys_state, B);
+}
 
 extern "C" int32_t adf_sde_init_placement(adf_painn_t h, const adf_batch* b, float* pos, const int32_t* tags,
                                           const float* noise, void* stream) {

@@ -303,6 +303,7 @@ struct adf_painn {
     float *sub_x, *sub_vec, *sub_f;  // compact rows of adf_painn_forward_subset: [capS,H], [capS,3,H], [capS,3]
     int64_t capS;
     float* sys;          // [B*16] per-system scratch of the stepper
+    int32_t* ps_state = nullptr; int32_t ps_B = 0;   // per-system early stop (adf_painn_set_per_system_stop): caller's [B,4]
     // ---- S2EF energy head out_energy = Linear(H, H/2), ScaledSiLU, Linear(H/2, 1) (adf_painn_set_energy_head)
     const float *oe0_w, *oe0_b, *oe2_w, *oe2_b;
     adf_w16 oe0_16;
@@ -447,12 +448,13 @@ int32_t adf_stepper_init(const adf_batch* b, float* pos, const int32_t* tags, co
 int32_t adf_stepper_step(float* sys, const adf_batch* b, float* pos, const int32_t* tags, const int32_t* fixed,
                          const float* f1, const float* f2, const adf_step_coef* coef, const adf_step_coef* coefs_dev,
                          int num_steps, const float* z_tr, const float* z_rot, int32_t early_stop_count,
-                         int32_t* state, float* dcom, float* drot, hipStream_t s);
+                         int32_t* state, float* dcom, float* drot, hipStream_t s, int32_t* sys_state = nullptr);
 // translation-only samplers (reverse_sde_sampling / langevin_dynamics): head-1 mean, dcom = coef * score (+ noise * z),
 // wrap, pos += dcom on the adsorbate; same state[] protocol as adf_stepper_step
 int32_t adf_stepper_tr_step(float* sys, const adf_batch* b, float* pos, const int32_t* tags, const float* f1,
                             const adf_tr_coef* coef, const adf_tr_coef* coefs_dev, int num_steps, const float* z,
-                            int32_t early_stop_count, int32_t* state, float* dcom, hipStream_t s);
+                            int32_t early_stop_count, int32_t* state, float* dcom, hipStream_t s,
+                            int32_t* sys_state = nullptr);   // sys_state: the per-system rule (stepper.hip)
 
 // ---- the stepper entries and the fused sampling loop of both score models (stepper.hip).  The model side: api.hip
 // (PaiNN) and eqv2_api.hip (EquiformerV2) fill one in for a handle.
@@ -464,7 +466,12 @@ struct adf_model {
     int32_t (*forward)(void* h, const adf_batch* b, const int32_t* out_idx, int32_t n_out, float* f1, float* f2,
                        hipStream_t s);
     void (*prof)(void* h, bool begin, hipStream_t s);            // time the step under the model's stepper category
+    // per-system early stop (adf_*_set_per_system_stop): the caller's [sys_B, 4] int32 table, null = the coupled rule
+    int32_t* sys_state;
+    int32_t sys_B;
 };
+// the switch itself: validates and stores into the handle's two fields
+int32_t adf_model_set_per_system_stop(int32_t** slot, int32_t* slot_B, int32_t* sys_state, int32_t B);
 int32_t adf_frames_push_impl(adf_frames* f, const float* src, hipStream_t s);
 // the entries of include/adsorbdiff_hip.h on the handle of `m` (same arguments and contracts)
 int32_t adf_model_init_placement(const adf_model& m, const adf_batch* b, float* pos, const int32_t* tags,

@@ -136,6 +136,7 @@ struct adf_eqv2 {
     float* arena; size_t arena_floats;
     float* garena; size_t garena_floats;   // grid MLP buffers of a node chunk
     float* sys;
+    int32_t* ps_state = nullptr; int32_t ps_B = 0;   // per-system early stop (adf_eqv2_set_per_system_stop): caller's [B,4]
     void* s2tab; int s2_npb; float s2_inv_sT, s2_inv_sF, s2_gain_shift;  // fragment-order fp16 hi/lo images of to_red / from_red
     void *gtab_to, *gtab_from; int g_npb, g_nkst; float g_inv_sT, g_inv_sF;  // likewise for to_full / from_full
     float* rs; int64_t rs_cap;   // per-row magnitudes max|a| of the A operand of an f16x3 product (-> power-of-two lift)

@@ -1214,7 +1214,14 @@ static void eq_model_prof(void* h, bool begin, hipStream_t s) {
     if (begin) ((adf_eqv2*)h)->prof.begin(EQ_PROF_STEPPER, s);
     else ((adf_eqv2*)h)->prof.end(s);
 }
-static adf_model eq_model(adf_eqv2_t h) { return {h, eq_model_check, eq_model_grow, eq_model_forward, eq_model_prof}; }
+static adf_model eq_model(adf_eqv2_t h) {
+    return {h, eq_model_check, eq_model_grow, eq_model_forward, eq_model_prof, h ? h->ps_state : nullptr, h ? h->ps_B : 0};
+}
+
+extern "C" int32_t adf_eqv2_set_per_system_stop(adf_eqv2_t h, int32_t* sys_state, int32_t B) {
+    if (!h) { adf_set_error("null handle"); return ADF_EINVAL; }
+    return adf_model_set_per_system_stop(&h->ps_state, &h->ps_B, sys_state, B);
+}
 
 extern "C" int32_t adf_eqv2_init_placement(adf_eqv2_t h, const adf_batch* b, float* pos, const int32_t* tags,
                                            const float* noise, void* stream) {

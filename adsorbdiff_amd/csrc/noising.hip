@@ -88,6 +88,73 @@ extern "C" int32_t adf_place_draws(int64_t seed, const int64_t* keys, const int3
     return ADF_OK;
 }
 
+// The sampler's rows (denoising_torch.py: noise_seed): counters (key lo, key hi, t, 4 + 2 site + j), j in {0, 1} - the last
+// counter word keeps them apart from the rows above (words 0 to 3) and from each other across the sites of one slab.
+// Step row t in [0, T): six normals by the Box-Muller of nz_draws_kernel on (w0,w1), (w2,w3), (w4,w5), cast to float32:
+// z_a[t,b] = (n0, n1, n2), z_b[t,b] = (n3, n4, n5).  Placement row: t = 0xFFFFFFFF, j = 0, place[b,k] = (w_k >> 8) * 2^-24,
+// in [0, 1) and exact in float32 as torch.rand is (nz_unit would round to 1.0f for the largest words).
+// One thread per (row, system); row T is the placement row.
+__global__ void nz_sampler_draws_kernel(uint32_t seed_lo, uint32_t seed_hi, const int64_t* __restrict__ keys,
+                                        const int32_t* __restrict__ site, int B, int T, float* __restrict__ place,
+                                        float* __restrict__ z_a, float* __restrict__ z_b) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long long)(T + 1) * B) return;
+    const int t = (int)(i / B), b = (int)(i % B);
+    const uint64_t key = (uint64_t)keys[b];
+    const uint32_t last = 4u + 2u * (uint32_t)(site ? site[b] : 0);
+    uint32_t w[8];
+    if (t == T) {
+        if (!place) return;
+        nz_philox4x32_10((uint32_t)key, (uint32_t)(key >> 32), 0xFFFFFFFFu, last, seed_lo, seed_hi, w);
+        for (int k = 0; k < 3; ++k) place[3 * (size_t)b + k] = (float)(w[k] >> 8) * 5.9604644775390625e-08f;   // 2^-24
+        return;
+    }
+    if (!z_a && !z_b) return;
+    nz_philox4x32_10((uint32_t)key, (uint32_t)(key >> 32), (uint32_t)t, last, seed_lo, seed_hi, w);
+    nz_philox4x32_10((uint32_t)key, (uint32_t)(key >> 32), (uint32_t)t, last + 1u, seed_lo, seed_hi, w + 4);
+    double n[6];
+    for (int p = 0; p < 3; ++p) {
+        const double r = sqrt(-2.0 * log(nz_unit(w[2 * p]))), ph = 2.0 * 3.141592653589793 * nz_unit(w[2 * p + 1]);
+        n[2 * p] = r * cos(ph);
+        n[2 * p + 1] = r * sin(ph);
+    }
+    const size_t row = 3 * ((size_t)t * B + b);
+    if (z_a) for (int k = 0; k < 3; ++k) z_a[row + k] = (float)n[k];
+    if (z_b) for (int k = 0; k < 3; ++k) z_b[row + k] = (float)n[3 + k];
+}
+// a site outside [0, 2^30) is ADF_EINVAL: the table lives on the device, so one flag is read back before the draws
+__global__ void nz_site_range_kernel(const int32_t* __restrict__ site, int B, int32_t* __restrict__ bad) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < B && (site[b] < 0 || site[b] >= (1 << 30))) *bad = 1;
+}
+extern "C" int32_t adf_sampler_draws(int64_t seed, const int64_t* keys, const int32_t* site, int32_t B, int32_t T, float* place,
+                                     float* z_a, float* z_b, void* stream) {
+    if (!keys || B <= 0 || T < 0 || (!place && !z_a && !z_b) || ((z_a || z_b) && T == 0)) {
+        adf_set_error("sampler_draws: bad argument");
+        return ADF_EINVAL;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    if (site) {
+        int32_t* bad = nullptr;
+        int32_t host_bad = 0;
+        ADF_HIP_CHECK(hipMalloc(&bad, sizeof(int32_t)));
+        hipError_t e = hipMemsetAsync(bad, 0, sizeof(int32_t), s);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(nz_site_range_kernel, dim3((B + 255) / 256), dim3(256), 0, s, site, B, bad);
+            e = hipMemcpyAsync(&host_bad, bad, sizeof(int32_t), hipMemcpyDeviceToHost, s);
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        (void)hipFree(bad);
+        ADF_HIP_CHECK(e);
+        if (host_bad) { adf_set_error("sampler_draws: site outside [0, 2^30)"); return ADF_EINVAL; }
+    }
+    const long long n = (long long)(T + 1) * B;
+    hipLaunchKernelGGL(nz_sampler_draws_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (uint32_t)(uint64_t)seed,
+                       (uint32_t)((uint64_t)seed >> 32), keys, site, B, T, place, z_a, z_b);
+    NZ_CHECK_LAUNCH();
+    return ADF_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ table look-ups
 // Igso3Tables.eps_index: nearest row of the log-spaced eps grid, clipped (np.around rounds halves to even, as rint does)
 __device__ __forceinline__ int nz_eps_index(double eps, int n_eps) {

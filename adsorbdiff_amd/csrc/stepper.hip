@@ -91,11 +91,10 @@ __global__ __launch_bounds__(64) void adf_init_placement_kernel(const float* cel
         }
 }
 
-// phase 1: per-system scores -> (dcom, drot), wrapped; per-system convergence AND-ed into state[2]
-__global__ __launch_bounds__(64) void adf_step_reduce_kernel(StepParams p) {
-    const int b = blockIdx.x, lane = threadIdx.x;
-    const int a0 = p.atom_offset[b], a1 = p.atom_offset[b + 1];
-    float s[10];
+// ---- the per-system arithmetic of one step, shared by the coupled kernels (reduce / apply) and the per-system kernel:
+// the two paths must give the same bits, so there is one text of it.
+// sums over the tag-2 atoms of [a0, a1): pos(3) f1(3) f2*keep(3) count; every lane returns the same totals
+__device__ __forceinline__ void step_sums(const StepParams& p, int a0, int a1, int lane, float* s) {
 #pragma unroll
     for (int i = 0; i < 10; ++i) s[i] = 0.f;
     for (int a = a0 + lane; a < a1; a += 64)
@@ -108,12 +107,30 @@ __global__ __launch_bounds__(64) void adf_step_reduce_kernel(StepParams p) {
         }
 #pragma unroll
     for (int i = 0; i < 10; ++i) s[i] = wsum(s[i]);
-    if (lane != 0) return;
+}
+
+// the wrap of the COM into the cell: com + dcom -> solve / mod / cell.f; dcom becomes the wrapped increment.
+// Returns the convergence predicate allclose(dcom, 0, 1e-3, 1e-3) of this system.
+__device__ __forceinline__ bool step_wrap(const float* cl, const float* tgt, const float* com, float* dcom) {
+    float fr[3];
+    solve3(cl, tgt, fr);
+    for (int k = 0; k < 3; ++k) fr[k] = pymod1(pymod1(fr[k]));
+    bool conv = true;
+    for (int j = 0; j < 3; ++j) {
+        const float w = cl[3 * j] * fr[0] + cl[3 * j + 1] * fr[1] + cl[3 * j + 2] * fr[2];
+        dcom[j] = w - com[j];
+        conv = conv && (fabsf(dcom[j]) <= 1.0e-3f);
+    }
+    return conv;
+}
+
+// sums -> com, wrapped dcom, drot of system b; returns its convergence predicate
+__device__ __forceinline__ bool step_increment(const StepParams& p, int b, const float* s, float* com, float* dcom,
+                                               float* drot) {
     const float cnt = fmaxf(s[9], 1.0f);
     // schedule scalars: by value, or (graph replay: identical launch every step) from the device table
     adf_step_coef c = p.c;
     if (p.coefs_dev) c = p.coefs_dev[min(p.state[4], p.num_steps - 1)];
-    float com[3], dcom[3], drot[3];
     for (int k = 0; k < 3; ++k) {
         com[k] = s[k] / cnt;
         const float str = s[3 + k] / cnt;
@@ -126,17 +143,45 @@ __global__ __launch_bounds__(64) void adf_step_reduce_kernel(StepParams p) {
         drot[k] = r;
     }
     dcom[2] = 0.f;
-    const float* cl = p.cell + 9 * b;
-    float tgt[3] = {com[0] + dcom[0], com[1] + dcom[1], com[2] + dcom[2]};
-    float fr[3];
-    solve3(cl, tgt, fr);
-    for (int k = 0; k < 3; ++k) fr[k] = pymod1(pymod1(fr[k]));
-    bool conv = true;
-    for (int j = 0; j < 3; ++j) {
-        const float w = cl[3 * j] * fr[0] + cl[3 * j + 1] * fr[1] + cl[3 * j + 2] * fr[2];
-        dcom[j] = w - com[j];
-        conv = conv && (fabsf(dcom[j]) <= 1.0e-3f);
-    }
+    const float tgt[3] = {com[0] + dcom[0], com[1] + dcom[1], com[2] + dcom[2]};
+    return step_wrap(p.cell + 9 * b, tgt, com, dcom);
+}
+
+// rigid update of the adsorbate of [a0, a1): rotation by the axis-angle (ax, ay, az) about (cx, cy, cz), then translation
+__device__ __forceinline__ void step_rigid_update(float* pos, const int32_t* tags, int a0, int a1, int lane, float cx,
+                                                  float cy, float cz, float tx, float ty, float tz, float ax, float ay,
+                                                  float az) {
+    // axis-angle -> quaternion (rot_utils.py:50-81)
+    const float ang = sqrtf(ax * ax + ay * ay + az * az);
+    const float half = 0.5f * ang;
+    float k;
+    if (fabsf(ang) < 1e-6f) k = 0.5f - (ang * ang) / 48.0f;
+    else k = sinf(half) / ang;
+    const float qr = cosf(half), qi = ax * k, qj = ay * k, qk = az * k;
+    // quaternion -> matrix (rot_utils.py:18-47)
+    const float two_s = 2.0f / (qr * qr + qi * qi + qj * qj + qk * qk);
+    const float R00 = 1 - two_s * (qj * qj + qk * qk), R01 = two_s * (qi * qj - qk * qr), R02 = two_s * (qi * qk + qj * qr);
+    const float R10 = two_s * (qi * qj + qk * qr), R11 = 1 - two_s * (qi * qi + qk * qk), R12 = two_s * (qj * qk - qi * qr);
+    const float R20 = two_s * (qi * qk - qj * qr), R21 = two_s * (qj * qk + qi * qr), R22 = 1 - two_s * (qi * qi + qj * qj);
+    for (int a = a0 + lane; a < a1; a += 64)
+        if (tags[a] == 2) {
+            const float rx = pos[3 * a] - cx, ry = pos[3 * a + 1] - cy, rz = pos[3 * a + 2] - cz;
+            // (rel @ R^T) + dcom + com   (denoising_torch.py:331-336)
+            pos[3 * a] = ((rx * R00 + ry * R01 + rz * R02) + tx) + cx;
+            pos[3 * a + 1] = ((rx * R10 + ry * R11 + rz * R12) + ty) + cy;
+            pos[3 * a + 2] = ((rx * R20 + ry * R21 + rz * R22) + tz) + cz;
+        }
+}
+
+// phase 1: per-system scores -> (dcom, drot), wrapped; per-system convergence AND-ed into state[2]
+__global__ __launch_bounds__(64) void adf_step_reduce_kernel(StepParams p) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int a0 = p.atom_offset[b], a1 = p.atom_offset[b + 1];
+    float s[10];
+    step_sums(p, a0, a1, lane, s);
+    if (lane != 0) return;
+    float com[3], dcom[3], drot[3];
+    const bool conv = step_increment(p, b, s, com, dcom, drot);
     float* o = p.sys + 16 * b;
     for (int k = 0; k < 3; ++k) { o[k] = com[k]; o[3 + k] = dcom[k]; o[6 + k] = drot[k]; }
     if (!conv) atomicAnd(&p.state[2], 0);
@@ -167,29 +212,68 @@ __global__ __launch_bounds__(64) void adf_step_apply_kernel(StepParams p) {
     const int b = blockIdx.x, lane = threadIdx.x;
     const int a0 = p.atom_offset[b], a1 = p.atom_offset[b + 1];
     const float* o = p.sys + 16 * b;
-    const float cx = o[0], cy = o[1], cz = o[2];
-    const float tx = o[3], ty = o[4], tz = o[5];
-    const float ax = o[6], ay = o[7], az = o[8];
-    // axis-angle -> quaternion (rot_utils.py:50-81)
-    const float ang = sqrtf(ax * ax + ay * ay + az * az);
-    const float half = 0.5f * ang;
-    float k;
-    if (fabsf(ang) < 1e-6f) k = 0.5f - (ang * ang) / 48.0f;
-    else k = sinf(half) / ang;
-    const float qr = cosf(half), qi = ax * k, qj = ay * k, qk = az * k;
-    // quaternion -> matrix (rot_utils.py:18-47)
-    const float two_s = 2.0f / (qr * qr + qi * qi + qj * qj + qk * qk);
-    const float R00 = 1 - two_s * (qj * qj + qk * qk), R01 = two_s * (qi * qj - qk * qr), R02 = two_s * (qi * qk + qj * qr);
-    const float R10 = two_s * (qi * qj + qk * qr), R11 = 1 - two_s * (qi * qi + qk * qk), R12 = two_s * (qj * qk - qi * qr);
-    const float R20 = two_s * (qi * qk - qj * qr), R21 = two_s * (qj * qk + qi * qr), R22 = 1 - two_s * (qi * qi + qj * qj);
-    for (int a = a0 + lane; a < a1; a += 64)
-        if (p.tags[a] == 2) {
-            const float rx = p.pos[3 * a] - cx, ry = p.pos[3 * a + 1] - cy, rz = p.pos[3 * a + 2] - cz;
-            // (rel @ R^T) + dcom + com   (denoising_torch.py:331-336)
-            p.pos[3 * a] = ((rx * R00 + ry * R01 + rz * R02) + tx) + cx;
-            p.pos[3 * a + 1] = ((rx * R10 + ry * R11 + rz * R12) + ty) + cy;
-            p.pos[3 * a + 2] = ((rx * R20 + ry * R21 + rz * R22) + tz) + cz;
+    step_rigid_update(p.pos, p.tags, a0, a1, lane, o[0], o[1], o[2], o[3], o[4], o[5], o[6], o[7], o[8]);
+}
+
+// ---- per-system early stop (adf_*_set_per_system_stop): the decision is local to a system, so scores, wrap, decision and
+// the rigid update are ONE kernel, one wave per system.  sys_state[b] = {cvg_count, frozen, steps_applied, stop_step}.
+// The rule is the reference's loop (:312-320) for that system alone: a frozen system is not read and not written; a system
+// whose cumulative count reaches early_stop_count at step t freezes BEFORE this step's update (the `break`).
+// Global state: [0] frozen systems (atomicAdd), [3] max steps applied (atomicMax), [4] steps issued - read here by every
+// workgroup as the schedule index and as t, so it is the finish kernel after this one that bumps it and sets [1].
+// Returns true when this step's update is to be applied; lane 0 has then done all of the system's bookkeeping.
+__device__ __forceinline__ bool system_decide(int32_t* st, int32_t* state, int cvg, bool conv, int early_stop_count,
+                                              int lane) {
+    bool freeze = false;
+    if (conv) {
+        cvg += 1;
+        freeze = early_stop_count > 0 && cvg == early_stop_count;
+    }
+    if (lane == 0) {
+        st[0] = cvg;
+        if (freeze) {
+            st[1] = 1;
+            st[3] = state[4];
+            atomicAdd(&state[0], 1);
+        } else {
+            const int applied = st[2] + 1;
+            st[2] = applied;
+            atomicMax(&state[3], applied);
         }
+    }
+    return !freeze;
+}
+
+__global__ __launch_bounds__(64) void adf_step_system_kernel(StepParams p, int32_t* sys_state) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    int32_t* st = sys_state + 4 * b;
+    const int cvg = st[0], frozen = st[1];
+    if (frozen) {
+        if (lane < 3) {
+            if (p.dcom_out) p.dcom_out[3 * b + lane] = 0.f;
+            if (p.drot_out) p.drot_out[3 * b + lane] = 0.f;
+        }
+        return;
+    }
+    const int a0 = p.atom_offset[b], a1 = p.atom_offset[b + 1];
+    float s[10];
+    step_sums(p, a0, a1, lane, s);
+    float com[3], dcom[3], drot[3];   // every lane alike: the totals are in all of them
+    const bool conv = step_increment(p, b, s, com, dcom, drot);
+    if (lane < 3) {
+        if (p.dcom_out) p.dcom_out[3 * b + lane] = dcom[lane];
+        if (p.drot_out) p.drot_out[3 * b + lane] = drot[lane];
+    }
+    if (system_decide(st, p.state, cvg, conv, p.early_stop_count, lane))
+        step_rigid_update(p.pos, p.tags, a0, a1, lane, com[0], com[1], com[2], dcom[0], dcom[1], dcom[2], drot[0], drot[1],
+                          drot[2]);
+}
+
+__global__ void adf_step_system_finish_kernel(int32_t* state, int B) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        state[1] = state[0] >= B ? 1 : 0;
+        state[4] += 1;
+    }
 }
 
 int32_t adf_stepper_init(const adf_batch* b, float* pos, const int32_t* tags, const float* noise,
@@ -203,13 +287,19 @@ int32_t adf_stepper_init(const adf_batch* b, float* pos, const int32_t* tags, co
 int32_t adf_stepper_step(float* sys, const adf_batch* b, float* pos, const int32_t* tags, const int32_t* fixed,
                          const float* f1, const float* f2, const adf_step_coef* coef, const adf_step_coef* coefs_dev,
                          int num_steps, const float* z_tr, const float* z_rot, int32_t early_stop_count,
-                         int32_t* state, float* dcom, float* drot, hipStream_t s) {
+                         int32_t* state, float* dcom, float* drot, hipStream_t s, int32_t* sys_state) {
     StepParams p;
     p.cell = b->cell; p.atom_offset = b->atom_offset; p.tags = tags; p.fixed = fixed; p.pos = pos;
     p.f1 = f1; p.f2 = f2; p.z_tr = z_tr; p.z_rot = z_rot; p.sys = sys; p.state = state;
     p.dcom_out = dcom; p.drot_out = drot; p.B = b->num_systems; p.early_stop_count = early_stop_count;
     if (coef) p.c = *coef; else p.c = adf_step_coef{};
     p.coefs_dev = coefs_dev; p.num_steps = num_steps;
+    if (sys_state) {   // two launches where the coupled rule needs three
+        hipLaunchKernelGGL(adf_step_system_kernel, dim3(p.B), dim3(64), 0, s, p, sys_state);
+        hipLaunchKernelGGL(adf_step_system_finish_kernel, dim3(1), dim3(64), 0, s, state, p.B);
+        ADF_HIP_CHECK(hipGetLastError());
+        return ADF_OK;
+    }
     hipLaunchKernelGGL(adf_step_reduce_kernel, dim3(p.B), dim3(64), 0, s, p);
     hipLaunchKernelGGL(adf_step_decide_kernel, dim3(1), dim3(64), 0, s, state, early_stop_count);
     hipLaunchKernelGGL(adf_step_apply_kernel, dim3(p.B), dim3(64), 0, s, p);
@@ -239,10 +329,8 @@ struct TrParams {
     int num_steps;
 };
 
-__global__ __launch_bounds__(64) void adf_tr_reduce_kernel(TrParams p) {
-    const int b = blockIdx.x, lane = threadIdx.x;
-    const int a0 = p.atom_offset[b], a1 = p.atom_offset[b + 1];
-    float s[7];
+// sums over the tag-2 atoms of [a0, a1): pos(3) f1(3) count; every lane returns the same totals
+__device__ __forceinline__ void tr_sums(const TrParams& p, int a0, int a1, int lane, float* s) {
 #pragma unroll
     for (int i = 0; i < 7; ++i) s[i] = 0.f;
     for (int a = a0 + lane; a < a1; a += 64)
@@ -253,11 +341,13 @@ __global__ __launch_bounds__(64) void adf_tr_reduce_kernel(TrParams p) {
         }
 #pragma unroll
     for (int i = 0; i < 7; ++i) s[i] = wsum(s[i]);
-    if (lane != 0) return;
+}
+
+// sums -> com and the wrapped dcom of system b; returns its convergence predicate
+__device__ __forceinline__ bool tr_increment(const TrParams& p, int b, const float* s, float* com, float* dcom) {
     const float cnt = fmaxf(s[6], 1.0f);
     adf_tr_coef c = p.c;
     if (p.coefs_dev) c = p.coefs_dev[min(p.state[4], p.num_steps - 1)];
-    float com[3], dcom[3];
     for (int k = 0; k < 3; ++k) {
         com[k] = s[k] / cnt;
         float d = __fmul_rn(c.coef, s[3 + k] / cnt);
@@ -266,17 +356,29 @@ __global__ __launch_bounds__(64) void adf_tr_reduce_kernel(TrParams p) {
         dcom[k] = d;
     }
     dcom[2] = 0.f;
-    const float* cl = p.cell + 9 * b;
-    float tgt[3] = {__fadd_rn(com[0], dcom[0]), __fadd_rn(com[1], dcom[1]), __fadd_rn(com[2], dcom[2])};
-    float fr[3];
-    solve3(cl, tgt, fr);
-    for (int k = 0; k < 3; ++k) fr[k] = pymod1(pymod1(fr[k]));
-    bool conv = true;
-    for (int j = 0; j < 3; ++j) {
-        const float w = cl[3 * j] * fr[0] + cl[3 * j + 1] * fr[1] + cl[3 * j + 2] * fr[2];
-        dcom[j] = w - com[j];
-        conv = conv && (fabsf(dcom[j]) <= 1.0e-3f);
-    }
+    const float tgt[3] = {__fadd_rn(com[0], dcom[0]), __fadd_rn(com[1], dcom[1]), __fadd_rn(com[2], dcom[2])};
+    return step_wrap(p.cell + 9 * b, tgt, com, dcom);
+}
+
+// pos += dcom on the adsorbate of [a0, a1)
+__device__ __forceinline__ void tr_update(float* pos, const int32_t* tags, int a0, int a1, int lane, float tx, float ty,
+                                          float tz) {
+    for (int a = a0 + lane; a < a1; a += 64)
+        if (tags[a] == 2) {
+            pos[3 * a] = __fadd_rn(pos[3 * a], tx);
+            pos[3 * a + 1] = __fadd_rn(pos[3 * a + 1], ty);
+            pos[3 * a + 2] = __fadd_rn(pos[3 * a + 2], tz);
+        }
+}
+
+__global__ __launch_bounds__(64) void adf_tr_reduce_kernel(TrParams p) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int a0 = p.atom_offset[b], a1 = p.atom_offset[b + 1];
+    float s[7];
+    tr_sums(p, a0, a1, lane, s);
+    if (lane != 0) return;
+    float com[3], dcom[3];
+    const bool conv = tr_increment(p, b, s, com, dcom);
     float* o = p.sys + 16 * b;
     for (int k = 0; k < 3; ++k) { o[k] = com[k]; o[3 + k] = dcom[k]; }
     if (!conv) atomicAnd(&p.state[2], 0);
@@ -288,24 +390,43 @@ __global__ __launch_bounds__(64) void adf_tr_apply_kernel(TrParams p) {
     const int b = blockIdx.x, lane = threadIdx.x;
     const int a0 = p.atom_offset[b], a1 = p.atom_offset[b + 1];
     const float* o = p.sys + 16 * b;
-    const float tx = o[3], ty = o[4], tz = o[5];
-    for (int a = a0 + lane; a < a1; a += 64)
-        if (p.tags[a] == 2) {
-            p.pos[3 * a] = __fadd_rn(p.pos[3 * a], tx);
-            p.pos[3 * a + 1] = __fadd_rn(p.pos[3 * a + 1], ty);
-            p.pos[3 * a + 2] = __fadd_rn(p.pos[3 * a + 2], tz);
-        }
+    tr_update(p.pos, p.tags, a0, a1, lane, o[3], o[4], o[5]);
+}
+
+// the per-system rule (adf_step_system_kernel) for the translation-only samplers
+__global__ __launch_bounds__(64) void adf_tr_system_kernel(TrParams p, int32_t* sys_state, int early_stop_count) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    int32_t* st = sys_state + 4 * b;
+    const int cvg = st[0], frozen = st[1];
+    if (frozen) {
+        if (lane < 3 && p.dcom_out) p.dcom_out[3 * b + lane] = 0.f;
+        return;
+    }
+    const int a0 = p.atom_offset[b], a1 = p.atom_offset[b + 1];
+    float s[7];
+    tr_sums(p, a0, a1, lane, s);
+    float com[3], dcom[3];
+    const bool conv = tr_increment(p, b, s, com, dcom);
+    if (lane < 3 && p.dcom_out) p.dcom_out[3 * b + lane] = dcom[lane];
+    if (system_decide(st, p.state, cvg, conv, early_stop_count, lane))
+        tr_update(p.pos, p.tags, a0, a1, lane, dcom[0], dcom[1], dcom[2]);
 }
 
 int32_t adf_stepper_tr_step(float* sys, const adf_batch* b, float* pos, const int32_t* tags, const float* f1,
                             const adf_tr_coef* coef, const adf_tr_coef* coefs_dev, int num_steps, const float* z,
-                            int32_t early_stop_count, int32_t* state, float* dcom, hipStream_t s) {
+                            int32_t early_stop_count, int32_t* state, float* dcom, hipStream_t s, int32_t* sys_state) {
     TrParams p;
     p.cell = b->cell; p.atom_offset = b->atom_offset; p.tags = tags; p.pos = pos; p.f1 = f1; p.z = z; p.sys = sys;
     p.state = state; p.dcom_out = dcom;
     if (coef) p.c = *coef; else p.c = adf_tr_coef{};
     p.coefs_dev = coef ? nullptr : coefs_dev; p.num_steps = num_steps;
     const int B = b->num_systems;
+    if (sys_state) {
+        hipLaunchKernelGGL(adf_tr_system_kernel, dim3(B), dim3(64), 0, s, p, sys_state, early_stop_count);
+        hipLaunchKernelGGL(adf_step_system_finish_kernel, dim3(1), dim3(64), 0, s, state, B);
+        ADF_HIP_CHECK(hipGetLastError());
+        return ADF_OK;
+    }
     hipLaunchKernelGGL(adf_tr_reduce_kernel, dim3(B), dim3(64), 0, s, p);
     hipLaunchKernelGGL(adf_step_decide_kernel, dim3(1), dim3(64), 0, s, state, early_stop_count);
     hipLaunchKernelGGL(adf_tr_apply_kernel, dim3(B), dim3(64), 0, s, p);
@@ -314,6 +435,20 @@ int32_t adf_stepper_tr_step(float* sys, const adf_batch* b, float* pos, const in
 }
 
 // ------------------------------------------------------------------------------- the entries on a model's handle
+int32_t adf_model_set_per_system_stop(int32_t** slot, int32_t* slot_B, int32_t* sys_state, int32_t B) {
+    if (sys_state && B <= 0) { adf_set_error("set_per_system_stop: B must be positive"); return ADF_EINVAL; }
+    *slot = sys_state;
+    *slot_B = sys_state ? B : 0;
+    return ADF_OK;
+}
+static int32_t check_per_system(const adf_model& m, const adf_batch* b) {
+    if (m.sys_state && m.sys_B != b->num_systems) {
+        adf_set_error("per-system stop is set for %d systems, the batch has %d", (int)m.sys_B, (int)b->num_systems);
+        return ADF_EINVAL;
+    }
+    return ADF_OK;
+}
+
 int32_t adf_model_init_placement(const adf_model& m, const adf_batch* b, float* pos, const int32_t* tags,
                                  const float* noise, hipStream_t s) {
     ADF_TRY(m.check(m.h, b));
@@ -328,11 +463,12 @@ int32_t adf_model_sde_step(const adf_model& m, const adf_batch* b, float* pos, c
     ADF_TRY(m.check(m.h, b));
     if (!pos || !tags || !f1 || !f2 || (!coef && !coefs_dev) || !state) { adf_set_error("null argument"); return ADF_EINVAL; }
     if (!coef && num_steps <= 0) { adf_set_error("num_steps must be positive"); return ADF_EINVAL; }
+    ADF_TRY(check_per_system(m, b));
     float* sys = nullptr;
     ADF_TRY(m.grow(m.h, b, &sys));
     m.prof(m.h, true, s);
     const int32_t st = adf_stepper_step(sys, b, pos, tags, fixed, f1, f2, coef, coef ? nullptr : coefs_dev, num_steps, z_tr,
-                                        z_rot, early_stop_count, state, dcom, drot, s);
+                                        z_rot, early_stop_count, state, dcom, drot, s, m.sys_state);
     m.prof(m.h, false, s);
     return st;
 }
@@ -343,11 +479,12 @@ int32_t adf_model_tr_step(const adf_model& m, const adf_batch* b, float* pos, co
     ADF_TRY(m.check(m.h, b));
     if (!pos || !tags || !f1 || (!coef && !coefs_dev) || !state) { adf_set_error("tr_step: null argument"); return ADF_EINVAL; }
     if (!coef && num_steps <= 0) { adf_set_error("tr_step: num_steps must be positive"); return ADF_EINVAL; }
+    ADF_TRY(check_per_system(m, b));
     float* sys = nullptr;
     ADF_TRY(m.grow(m.h, b, &sys));
     m.prof(m.h, true, s);
     const int32_t st = adf_stepper_tr_step(sys, b, pos, tags, f1, coef, coefs_dev, num_steps, z, early_stop_count, state,
-                                           dcom, s);
+                                           dcom, s, m.sys_state);
     m.prof(m.h, false, s);
     return st;
 }
@@ -367,6 +504,7 @@ static int32_t sample_loop(const adf_model& m, const adf_batch* b, float* pos, c
         return ADF_EINVAL;
     }
     if (sink && frame_every <= 0) { adf_set_error("sample: frame_every must be positive"); return ADF_EINVAL; }
+    ADF_TRY(check_per_system(m, b));
     for (int t = 0; t < num_steps; ++t) {
         ADF_TRY(m.forward(m.h, b, out_idx, n_out, f1, f2, s));
         ADF_TRY(step((size_t)t * b->num_systems * 3));

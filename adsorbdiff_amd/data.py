@@ -14,7 +14,7 @@ from typing import Iterable, List
 import torch
 
 _TENSOR_NODE_KEYS = ("pos", "atomic_numbers", "tags", "fixed", "force", "forces")
-_TENSOR_GRAPH_KEYS = ("cell", "natoms", "y", "energy", "pbc")
+_TENSOR_GRAPH_KEYS = ("cell", "natoms", "y", "energy", "pbc", "noise_key", "site_index", "sample_steps", "sample_stopped")
 
 
 class Data:

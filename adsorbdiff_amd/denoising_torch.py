@@ -40,6 +40,29 @@ Extensions (all optional, defaults reproduce the reference):
   * ``denoising_pos_params["langevin_noise"]`` (default None): ``[num_steps * n_step_each, B, 3]`` standard normals for
     ``langevin_dynamics`` instead of the device generator's ``randn_like`` per inner step (a sharded run slices one global
     table by system id, as with ``placement_noise``).
+  * ``denoising_pos_params["per_system"]`` (default False): every system follows the reference's loop as if it were sampled
+    alone (``adf_*_set_per_system_stop``, csrc/stepper.hip): its own cumulative count of converged steps, its own stop - a
+    stopped system is neither read nor written again - instead of ONE ``allclose`` over the whole batch (:312-320), which in
+    a large batch almost never fires.  A system then gets the same bits alone, in any batch, in any order, after
+    ``ml_diffuse``'s split and on any shard (given noise that is keyed the same way: ``noise_seed``, or ODE with
+    ``placement_noise``).  After ``run()``: ``batch.sample_steps`` (int64 [B], steps applied), ``batch.sample_stopped`` (bool
+    [B]), ``Denoiser.stop_step`` ([B], the step at which the system stopped, -1 = ran to the end), ``Denoiser.steps_applied``
+    = the largest; ``Denoiser.cvg_count`` is the number of stopped systems.  With a ``traj_dir``, ``<sid>.npz`` holds the
+    system's own ``max(sample_steps[b], 1)`` frames (the batch file keeps every frame).  Fused and per-step path, all three
+    samplers (Langevin has no stop: only the attributes appear); with ``use_graph``: ``ValueError``.  What stays a decision
+    of the whole batch is the exact-f32 retry: one system leaving the f16x3 range re-runs all of them in exact f32.
+  * ``denoising_pos_params["noise_seed"]`` (default None): the placement uniforms and the step normals (``ode=False``,
+    Langevin) come from the counter-based ``adf_sampler_draws`` keyed by ``(noise_seed, noising.noise_keys(batch)[b],
+    batch.site_index[b] or 0)`` instead of ``torch.rand`` / ``normal_()`` streams over the batch.  An explicit
+    ``placement_noise``, ``langevin_noise`` or ``noise_fn`` still wins for its part.  Two systems of one batch with the same
+    ``(key, site_index)`` would be sampled identically: ``ValueError``.  Keys that fell back to the batch index: one
+    warning, the run is not batch-invariant.  Independent of ``per_system``.
+  * ``denoising_pos_params["image_repeats"]`` (default None): a floor ``[ra, rb, rc]`` for the number of periodic images the
+    graph search tries per lattice direction.  That number is the largest need over the batch (reference
+    utils/utils.py:634-662), the one input a system's graph takes from its batch-mates: an adsorbate atom outside the cell
+    can gain a neighbour when a mate with a smaller cell raises the count.  ``ml_diffuse`` (in per-system mode) and
+    ``ml_diffuse_sharded`` pin it to the need of the batch they are given, so their halves and shards build the graphs of
+    the unsplit run; pass ``engine.image_repeats(global_batch, cutoff)`` to compare runs of other batches bit for bit.
   * ``traj_dir=None`` is allowed (the reference crashes in ``write``); with a ``traj_dir`` the
     frames are kept on the device during the loop and written once at the end.
 """
@@ -127,6 +150,25 @@ def langevin_coefs(params: dict) -> List[_lib.TrCoef]:
     return out
 
 
+def per_system_stop_steps(conv, count: int = 10):
+    """The per-system stop rule on the host: ``conv`` [T,B] bool (step t left every wrapped abs(dcom) of system b <= 1e-3) ->
+    ``(steps_applied [B], stop_step [B])`` int64.  A system's cumulative count of converged steps reaching ``count`` at step t
+    stops it BEFORE that step's update (the reference's ``break``, :312-320, for that system alone): ``stop_step = t``,
+    ``steps_applied`` = the updates before it; a system that never gets there has ``stop_step = -1`` and T updates.
+    ``count <= 0``: nothing stops.  The oracle of ``adf_*_set_per_system_stop``."""
+    conv = torch.as_tensor(conv).to(torch.bool)
+    if conv.dim() != 2:
+        raise ValueError(f"per_system_stop_steps: [T,B] expected, got {list(conv.shape)}")
+    T, B = conv.shape
+    cum = torch.cumsum(conv.to(torch.int64), 0)
+    hit = (cum == int(count)) & conv if count > 0 else torch.zeros_like(conv)
+    any_hit = hit.any(0)
+    first = torch.argmax(hit.to(torch.int64), 0)
+    stop_step = torch.where(any_hit, first, torch.full_like(first, -1))
+    steps = torch.where(any_hit, first, torch.full_like(first, T))
+    return steps, stop_step
+
+
 class DiffTorchCalc:
     """Adapter between the stepper and a trainer-like object
     (reference: denoising_torch.py:486-511)."""
@@ -176,11 +218,47 @@ class Denoiser:
         self.denoising_pos_params = denoising_pos_params
         self.noise_fn = noise_fn
         self.steps_applied = 0
+        self.stop_step = None
+        self.per_system = bool(denoising_pos_params.get("per_system", False))
+        if self.per_system and denoising_pos_params.get("use_graph", False):
+            raise ValueError("denoising_pos_params: per_system with use_graph - the per-system rule ends the loop by a read "
+                             "of the frozen count, which a replayed graph does not make")
+        self.noise_seed = denoising_pos_params.get("noise_seed")
+        self._noise_keys = self._noise_site = None
+        if self.noise_seed is not None:
+            self._init_noise_keys()
         assert not self.traj_dir or (
             traj_dir and len(traj_names)
         ), "Trajectory names should be specified to save trajectories"
         if not self.otf_graph:
             raise NotImplementedError("the HIP sampling path requires otf_graph=True")
+
+    def _init_noise_keys(self) -> None:
+        """Keys and site indices of ``noise_seed``: checked here, before anything runs."""
+        from .noising import noise_key_source, noise_keys
+
+        batch = self.batch
+        B = int(batch.natoms.shape[0])
+        keys = noise_keys(batch).detach().cpu().reshape(-1)
+        if noise_key_source(batch) == "index":
+            logging.warning("adsorbdiff_amd: noise_seed without batch.noise_key or batch.sid: the keys are the positions in "
+                            "the batch, so this run is NOT batch-invariant")
+        site = getattr(batch, "site_index", None)
+        site = torch.zeros(B, dtype=torch.int32) if site is None else torch.as_tensor(site).detach().cpu().reshape(-1).to(torch.int32)
+        if site.numel() != B:
+            raise ValueError(f"batch.site_index: [{B}] expected, got [{site.numel()}]")
+        if site.numel() and (int(site.min()) < 0 or int(site.max()) >= (1 << 30)):
+            raise ValueError("batch.site_index outside [0, 2^30)")
+        pairs = set(zip(keys.tolist(), site.tolist()))
+        if len(pairs) != B:
+            raise ValueError("noise_seed: two systems of the batch share (noise key, site_index) and would be sampled "
+                             "identically; give them distinct batch.noise_key / sid or batch.site_index")
+        self._noise_keys, self._noise_site = keys, site
+
+    def _keyed_draws(self, dev, T: int, place: bool = False, z_a: bool = False, z_b: bool = False):
+        from .engine import sampler_draws
+
+        return sampler_draws(int(self.noise_seed), self._noise_keys, self._noise_site, T, dev, place=place, z_a=z_a, z_b=z_b)
 
     # ------------------------------------------------------------------ public
     SAMPLERS = ("sde_rot", "sde", "langevin")
@@ -229,7 +307,9 @@ class Denoiser:
             def fused(f1, state, out_idx, poll_every, sink):
                 f2 = torch.zeros(N, 3, dtype=torch.float32, device=dev)
                 zt = zr = None
-                if not ode:  # device generator, drawn in the reference's order (:274-289): z_tr then z_rot, per step
+                if not ode and self.noise_seed is not None:   # keyed per system: z_tr = z_a, z_rot = z_b
+                    _, zt, zr = self._keyed_draws(dev, T, z_a=True, z_b=True)
+                elif not ode:  # device generator, drawn in the reference's order (:274-289): z_tr then z_rot, per step
                     zt = torch.empty(T, B, 3, dtype=torch.float32, device=dev)
                     zr = torch.empty(T, B, 3, dtype=torch.float32, device=dev)
                     for t_idx in range(T):
@@ -240,10 +320,12 @@ class Denoiser:
 
             def per_step(f1, state, out_idx):
                 f2 = torch.zeros(N, 3, dtype=torch.float32, device=dev)
-                z_tr = z_rot = graph = None
+                z_tr = z_rot = graph = keyed = None
                 if not ode:
                     z_tr = torch.empty(B, 3, dtype=torch.float32, device=dev)
                     z_rot = torch.empty(B, 3, dtype=torch.float32, device=dev)
+                    if self.noise_fn is None and self.noise_seed is not None:
+                        keyed = self._keyed_draws(dev, T, z_a=True, z_b=True)[1:]
 
                 def one_step():
                     eng.forward_prepared(prep, pos, f1, f2, out_idx)
@@ -256,6 +338,9 @@ class Denoiser:
                             a, b_ = self.noise_fn(t_idx, B)
                             z_tr.copy_(a.to(dev, torch.float32))
                             z_rot.copy_(b_.to(dev, torch.float32))
+                        elif keyed is not None:
+                            z_tr.copy_(keyed[0][t_idx])
+                            z_rot.copy_(keyed[1][t_idx])
                         else:  # device generator, like the reference (:274-289)
                             z_tr.normal_()
                             z_rot.normal_()
@@ -318,7 +403,9 @@ class Denoiser:
             B, N, dev = prep.num_systems, prep.num_atoms, pos.device
             z_all = None
             if langevin:
-                if noise_table is None:  # device generator, one randn_like([B,3]) per inner step (reference :417)
+                if noise_table is None and self.noise_seed is not None:   # keyed per system, t = the inner-step index
+                    z_all = self._keyed_draws(dev, T, z_a=True)[1]
+                elif noise_table is None:  # device generator, one randn_like([B,3]) per inner step (reference :417)
                     z_all = torch.empty(T, B, 3, dtype=torch.float32, device=dev)
                     for t_idx in range(T):
                         z_all[t_idx].normal_()
@@ -371,7 +458,7 @@ class Denoiser:
             if batch.pos.dtype != torch.float32 or not batch.pos.is_contiguous():
                 batch.pos = batch.pos.to(torch.float32).contiguous()
             pos = batch.pos
-            prep = eng.prepare(batch)
+            prep = eng.prepare(batch, params.get("image_repeats"))
             if prep.tags is None:
                 raise ValueError("batch.tags is required (tag 2 marks the adsorbate)")
             eng.bind_condition(batch, prep.num_systems)  # conditional EquiformerV2: batch.energy, once for the whole loop
@@ -380,7 +467,9 @@ class Denoiser:
 
             # initial placement: uniform noise from the CPU global generator (reference :215)
             noise = params.get("placement_noise")
-            if noise is None:
+            if noise is None and self.noise_seed is not None:   # extension: keyed per system
+                noise = self._keyed_draws(dev, 0, place=True)[0]
+            elif noise is None:
                 noise = torch.rand(B, 3)
             else:  # extension: caller-supplied uniforms (sharded runs key them by global system id)
                 noise = torch.as_tensor(noise, dtype=torch.float32).reshape(B, 3).cpu()
@@ -401,11 +490,15 @@ class Denoiser:
             def attempt():
                 f1 = torch.zeros(N, 3, dtype=torch.float32, device=dev)
                 state = torch.tensor([0, 0, 1, 0, 0, 0, 0, 0], dtype=torch.int32, device=dev)
+                sys_state = None
+                if self.per_system:
+                    sys_state = torch.tensor([[0, 0, 0, -1]] * B, dtype=torch.int32, device=dev)
+                    eng.set_per_system_stop(sys_state)
                 out_idx = torch.nonzero(prep.tags == 2).reshape(-1).to(torch.int32).contiguous() if ads_only else None
                 if fused:
                     self._run_fused(eng, batch, pos, state, T,
-                                    lambda sink: fused_run(f1, state, out_idx, check_every if early else 0, sink))
-                    return state, None
+                                    lambda sink: fused_run(f1, state, out_idx, check_every if early else 0, sink), sys_state)
+                    return state, None, sys_state
                 frames = [] if self.traj_dir else None
                 step = per_step(f1, state, out_idx)
                 for t_idx in range(T):
@@ -420,35 +513,46 @@ class Denoiser:
                 if frames is not None and not frames:
                     frames.append(pos.clone())
                 eng.check_flags()
-                return state, frames
+                return state, frames, sys_state
 
             try:
-                state, frames = attempt()
-            except _lib.NumericRangeError:
+                state, frames, sys_state = attempt()
+            except _lib.NumericRangeError:   # a decision of the whole batch, in per-system mode too
                 if not eng.use_exact_f32():
                     raise
                 pos.copy_(pos0)
-                state, frames = attempt()
+                state, frames, sys_state = attempt()
             st = state.tolist()
             self.steps_applied = st[3]
             self.cvg_count = st[0]
+            counts = None
+            if sys_state is not None:
+                batch.sample_steps = sys_state[:, 2].to(torch.int64)
+                batch.sample_stopped = sys_state[:, 1] != 0
+                self.stop_step = sys_state[:, 3].to(torch.int64)
+                counts = [max(int(n), 1) for n in batch.sample_steps.tolist()]
             if frames is not None:
                 # frames recorded after the break are identical copies; keep the applied ones
                 frames = frames[: max(self.steps_applied, 1)] if self.save_full else frames[-1:]
-                self._write_trajectories(batch, frames)
+                self._write_trajectories(batch, frames, counts if self.save_full else None)
             if self._pending is not None and not params.get("trajectory_async", False):
                 self.wait_for_trajectories()   # like the reference: the files exist when run() returns
             batch.y = torch.zeros(B, device=dev)
             batch.force = torch.zeros(N, 3, device=dev)
         finally:
             try:
-                self._engine().set_moving_atoms(None, None)
+                eng = self._engine()
+                try:
+                    eng.set_moving_atoms(None, None)
+                finally:
+                    if self.per_system:
+                        eng.set_per_system_stop(None)
             except Exception:
                 pass
             if ema:
                 ema.restore()
 
-    def _run_fused(self, eng, batch, pos, state, T: int, run) -> None:
+    def _run_fused(self, eng, batch, pos, state, T: int, run, sys_state=None) -> None:
         """``run(sink)``: a sampler's whole loop in one library call.  With a ``traj_dir`` the trajectory frames leave the
         device from inside that loop (csrc/frames.hip) and a host thread writes them while the next steps compute
         (trajectory.py)."""
@@ -477,6 +581,8 @@ class Denoiser:
                     raise writer.error
             raise
         if writer is not None:
+            if sys_state is not None and self.save_full:   # per-system mode: a system's file holds its own applied frames
+                writer.set_frame_counts([max(int(n), 1) for n in sys_state[:, 2].tolist()])
             writer.finish(max(int(state[3].item()), 1) if self.save_full else 1)
             self._pending = (writer, sink)
 
@@ -499,11 +605,11 @@ class Denoiser:
                     fixed=batch.fixed.cpu().numpy() if hasattr(batch, "fixed") else np.zeros_like(tags),
                     cell=batch.cell.cpu().numpy(), natoms=batch.natoms.cpu().numpy(), names=list(self.traj_names))
 
-    def _write_trajectories(self, batch, frames) -> None:
+    def _write_trajectories(self, batch, frames, counts=None) -> None:
         """One file per system, written once after the loop under a temporary name and then renamed (the reference's
         ``.traj_tmp`` -> ``.traj`` protocol, :66-82).  With ``ase`` importable: genuine ASE trajectories ``<name>.traj``;
         without it the same content (positions per frame, numbers, cell, tags, fixed) goes to ``<name>.npz`` - a file
-        named ``.traj`` always is one."""
+        named ``.traj`` always is one.  ``counts`` (per-system mode): system b's file holds its first ``counts[b]`` frames."""
         traj_dir = Path(self.traj_dir)
         traj_dir.mkdir(exist_ok=True, parents=True)
         stack = torch.stack(frames).cpu().numpy()  # [F,N,3]
@@ -524,16 +630,17 @@ class Denoiser:
         start = 0
         for b, (n, name) in enumerate(zip(natoms, self.traj_names)):
             sl = slice(start, start + n)
+            nf = stack.shape[0] if counts is None else min(int(counts[b]), stack.shape[0])
             tmp = traj_dir / (f"{name}.traj_tmp" if have_ase else f"{name}.npz_tmp")
             if have_ase:  # pragma: no cover
                 with Trajectory(tmp, mode="w") as traj:
-                    for f in range(stack.shape[0]):
+                    for f in range(nf):
                         traj.write(Atoms(numbers=Z[sl].astype(int), positions=stack[f, sl], tags=tags[sl],
                                          cell=cell[b], constraint=FixAtoms(mask=fixed[sl].astype(bool)),
                                          pbc=[True, True, True]))
             else:
                 with open(tmp, "wb") as fh:
-                    np.savez(fh, positions=stack[:, sl], numbers=Z[sl], tags=tags[sl], fixed=fixed[sl], cell=cell[b])
+                    np.savez(fh, positions=stack[:nf, sl], numbers=Z[sl], tags=tags[sl], fixed=fixed[sl], cell=cell[b])
             tmp.rename(tmp.with_suffix(".traj" if have_ase else ".npz"))
             start += n
 

@@ -81,6 +81,14 @@ class PreparedBatch:
         return d
 
 
+def image_repeats(batch, cutoff: float) -> List[int]:
+    """``cell_repeats`` of a whole batch: the number of periodic images the graph search tries per lattice direction.  It is
+    the largest need over the batch (as in the reference), so it is the one thing a system's graph takes from its
+    batch-mates: an adsorbate atom that has left the cell can gain a neighbour when a mate with a smaller cell raises the
+    count.  Pinning it (``denoising_pos_params["image_repeats"]``) removes that."""
+    return cell_repeats(batch.cell, float(cutoff), batch_pbc(batch))
+
+
 def _require_gpu(t: torch.Tensor, what: str) -> None:
     if not t.is_cuda:
         raise RuntimeError(
@@ -95,6 +103,27 @@ def _ptr(t: Optional[torch.Tensor]):
 
 def _numel(t: Optional[torch.Tensor]) -> int:
     return int(t.numel()) if t is not None else 0
+
+
+def sampler_draws(seed: int, keys: torch.Tensor, site: Optional[torch.Tensor], num_steps: int, device, place: bool = True,
+                  z_a: bool = False, z_b: bool = False):
+    """The sampler's keyed draws (``adf_sampler_draws``) -> (place [B,3] | None, z_a [T,B,3] | None, z_b | None), float32 on
+    ``device``.  A system's rows depend on ``(seed, keys[b], site[b])`` alone."""
+    dev = torch.device(device)
+    keys = torch.as_tensor(keys, dtype=torch.int64).reshape(-1).to(dev).contiguous()
+    B, T = int(keys.shape[0]), int(num_steps)
+    if site is not None:
+        site = torch.as_tensor(site).reshape(-1).to(dev, torch.int32).contiguous()
+        if site.shape[0] != B:
+            raise ValueError(f"sampler_draws: {B} keys, {site.shape[0]} site indices")
+    out = [torch.empty(shape, dtype=torch.float32, device=dev) if want else None
+           for want, shape in ((place, (B, 3)), (z_a, (T, B, 3)), (z_b, (T, B, 3)))]
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    seed = seed - (1 << 64) if seed >= (1 << 63) else seed
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().adf_sampler_draws(seed, keys.data_ptr(), _ptr(site), B, T, *[_ptr(t) for t in out],
+                                                 C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    return tuple(out)
 
 
 class Engine:
@@ -113,6 +142,7 @@ class Engine:
         self.exact_f32 = os.environ.get("ADF_GEMM") == "f32"
         self._weights_keepalive: List[torch.Tensor] = []
         self._moving_keepalive = None
+        self._sys_state_keepalive = None
 
     def _c(self, role: str):
         return getattr(self.lib, self.SYMBOLS[role])
@@ -121,7 +151,9 @@ class Engine:
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     # ------------------------------------------------------------------ batches
-    def prepare(self, data) -> PreparedBatch:
+    def prepare(self, data, image_repeats: Optional[Sequence[int]] = None) -> PreparedBatch:
+        """``image_repeats``: a floor for the periodic images per direction (never fewer than this batch needs; a
+        non-periodic direction stays at 0)."""
         _require_gpu(data.pos, "data.pos")
         dev = self.device
         natoms = data.natoms.to(dev, torch.int64).reshape(-1)
@@ -131,6 +163,10 @@ class Engine:
         off[1:] = torch.cumsum(natoms, 0).to(torch.int32)
         cell = data.cell.to(dev, torch.float32).reshape(B, 3, 3).contiguous()
         reps = cell_repeats(cell, float(self.model.cutoff), batch_pbc(data))
+        if image_repeats is not None:
+            if len(image_repeats) != 3:
+                raise ValueError(f"image_repeats: three counts expected, got {list(image_repeats)}")
+            reps = [max(int(r), int(f)) if r > 0 else 0 for r, f in zip(reps, image_repeats)]
         prep = PreparedBatch(
             num_systems=B, num_atoms=N, cell=cell,
             atomic_numbers=data.atomic_numbers.to(dev).long().to(torch.int32).contiguous(),
@@ -181,6 +217,20 @@ class Engine:
         """Incremental layers / blocks: keep the node state of every layer across the forwards of a static-atom
         promise and recompute only rows whose inputs changed.  Bit-identical outputs."""
         _lib.check(self._c("set_incremental")(self.handle, 1 if on else 0))
+
+    def set_per_system_stop(self, sys_state: Optional[torch.Tensor]) -> None:
+        """Per-system early stop of the step entries and fused loops of this handle (``adf_*_set_per_system_stop``):
+        ``sys_state`` int32 ``[B,4]`` on the device, rows ``{cvg_count, frozen, steps_applied, stop_step}`` initialised to
+        ``{0, 0, 0, -1}``; None switches the mode off.  The tensor is kept alive on the engine until the next call."""
+        if sys_state is None:
+            self._sys_state_keepalive = None
+            _lib.check(self._c("set_per_system_stop")(self.handle, None, 0))
+            return
+        if (sys_state.dtype != torch.int32 or sys_state.dim() != 2 or sys_state.shape[1] != 4 or not sys_state.is_contiguous()
+                or sys_state.device != self.device):
+            raise ValueError("set_per_system_stop: contiguous int32 [B,4] on the engine's device expected")
+        self._sys_state_keepalive = sys_state
+        _lib.check(self._c("set_per_system_stop")(self.handle, sys_state.data_ptr(), int(sys_state.shape[0])))
 
     # ------------------------------------------------------------------ stepper
     def init_placement(self, prep: PreparedBatch, pos: torch.Tensor, noise: torch.Tensor) -> None:
@@ -272,6 +322,7 @@ class PaiNNEngine(Engine):
                    set_arithmetic="adf_painn_set_arithmetic", set_incremental="adf_painn_set_incremental",
                    init_placement="adf_sde_init_placement", sample="adf_sample", sample_traj="adf_sample_traj",
                    tr_step="adf_tr_step", tr_sample="adf_tr_sample", tr_sample_traj="adf_tr_sample_traj",
+                   set_per_system_stop="adf_painn_set_per_system_stop",
                    profile_enable="adf_profile_enable", destroy="adf_painn_destroy")
 
     def __init__(self, model, device) -> None:

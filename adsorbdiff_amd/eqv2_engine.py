@@ -69,7 +69,7 @@ class EqV2Engine(Engine):
                    init_placement="adf_eqv2_init_placement", sde_step="adf_eqv2_sde_step", sample="adf_eqv2_sample",
                    sample_traj="adf_eqv2_sample_traj", tr_step="adf_eqv2_tr_step", tr_sample="adf_eqv2_tr_sample",
                    tr_sample_traj="adf_eqv2_tr_sample_traj", profile_enable="adf_eqv2_profile_enable",
-                   destroy="adf_eqv2_destroy")
+                   set_per_system_stop="adf_eqv2_set_per_system_stop", destroy="adf_eqv2_destroy")
     num_heads = 2   # force_block and force_block2
 
     def __init__(self, model, device) -> None:

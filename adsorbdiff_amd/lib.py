@@ -28,6 +28,7 @@ EXPORTS = (
     "adf_painn_debug_row_maxima",
     "adf_sde_init_placement", "adf_sde_step", "adf_sde_step_scheduled", "adf_sample", "adf_sample_traj",
     "adf_tr_step", "adf_tr_sample", "adf_tr_sample_traj",
+    "adf_painn_set_per_system_stop", "adf_eqv2_set_per_system_stop", "adf_sampler_draws",
     "adf_painn_set_energy_head", "adf_painn_set_distance_floor", "adf_painn_forward_energy",
     "adf_painn_forward_energy_gradient", "adf_painn_energy_gradient_workspace",
     "adf_lbfgs_create", "adf_lbfgs_destroy", "adf_lbfgs_reset", "adf_lbfgs_converge", "adf_lbfgs_step",
@@ -236,6 +237,9 @@ def load():
         "adf_op_score_loss": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp],
         "adf_op_score_loss_tr": [vp, vp, vp, vp, vp, vp, vp, i32, vp, vp],
         "adf_noise_draws": [i64, i32, vp, i32, vp, vp],
+        "adf_sampler_draws": [i64, vp, vp, i32, i32, vp, vp, vp, vp],
+        "adf_painn_set_per_system_stop": [vp, vp, i32],
+        "adf_eqv2_set_per_system_stop": [vp, vp, i32],
         "adf_noise_tr_so3": [vp, vp, vp, vp, i32, i32, vp, C.c_float, C.c_float, C.c_float, C.c_float, vp, vp, vp, vp, i32, i32,
                              vp, vp, vp, vp, vp, vp, vp, vp],
         "adf_noise_com": [vp, vp, vp, vp, i32, i32, vp, C.c_float, C.c_float, vp, vp, vp, vp, vp],

@@ -51,6 +51,17 @@ def _sample_or_split(batch, make_denoiser, construct_in_try: bool = True, order=
                                     None if order is None else ids[part])
 
 
+def _pin_image_repeats(batch, model, params: dict, always: bool = False) -> dict:
+    """In per-system mode (or ``always``): ``params`` with ``image_repeats`` set to what ``batch`` as a whole needs, unless
+    the caller pinned it.  The halves of an out-of-memory split and the shards then search the periodic images the unsplit
+    run searches (``engine.image_repeats``: the count is a maximum over the batch)."""
+    if not (always or params.get("per_system", False)) or params.get("image_repeats") is not None:
+        return params
+    from .engine import image_repeats
+
+    return dict(params, image_repeats=image_repeats(batch, model._unwrapped_model.cutoff))
+
+
 def ml_diffuse(
     batch,
     model,
@@ -62,14 +73,113 @@ def ml_diffuse(
     early_stop_batch: bool = False,
     logger=None,
 ):
+    """What a system carries (``noise_key``, ``site_index``; after a per-system run ``sample_steps``, ``sample_stopped``)
+    travels with it through the out-of-memory split."""
+    return Batch.from_data_list(list(_diffuse_parts(batch, model, denoising_pos_params, traj_dir, save_full_traj, device,
+                                                    transform, early_stop_batch, logger, None)))
+
+
+def _diffuse_parts(batch, model, denoising_pos_params, traj_dir, save_full_traj, device, transform, early_stop_batch, logger,
+                   order):
+    """The sampled (sub-)batches of ``ml_diffuse``; ``order`` (a list) receives the input index of every yielded system."""
     sink = Path(traj_dir) if traj_dir is not None else None
+    denoising_pos_params = _pin_image_repeats(batch, model, denoising_pos_params)
 
     def make_denoiser(b):
         return Denoiser(b, DiffTorchCalc(model, transform), denoising_pos_params=denoising_pos_params,
                         device=device, save_full_traj=save_full_traj, traj_dir=sink, traj_names=b.sid,
                         early_stop_batch=early_stop_batch, logger=logger)
 
-    return Batch.from_data_list(list(_sample_or_split(batch, make_denoiser)))
+    return _sample_or_split(batch, make_denoiser, order=order)
+
+
+def ml_diffuse_sharded(
+    batch,
+    model,
+    denoising_pos_params: dict,
+    traj_dir,
+    save_full_traj,
+    device: str = "cuda:0",
+    rank: int = 0,
+    world: int = 1,
+    via: str = "torch",
+    transform=None,
+):
+    """``ml_diffuse`` dealt over ``world`` ranks, the twin of ``ml_relax_sharded``: this rank samples its share of ``batch``
+    (``sampler.shard_batch``) and ONE all-gather (``sampler.gather_sites``) brings every system's sampled adsorbate to every
+    rank.  Returns the whole batch in global system order with the adsorbate rows filled in; ``sample_steps`` (per-system
+    mode) is -1 for the systems sampled on another rank - it is not gathered.  A shard reproduces the single run only if
+    nothing couples a system to its batch-mates, so this needs
+
+    * ``per_system=True`` or ``early_stop=False`` (the default early stop is one decision over the batch), and
+    * a shard-invariant noise source: ``noise_seed``, or an ODE run (``ode`` not False, sampler not ``"langevin"``) with a
+      global ``[B,3]`` ``placement_noise``, which is sliced by system id here;
+
+    otherwise ``ValueError`` names what is missing."""
+    from . import sampler
+
+    params = dict(denoising_pos_params)
+    if not params.get("per_system", False) and params.get("early_stop", True) and params.get("sampler", "sde_rot") != "langevin":
+        raise ValueError("ml_diffuse_sharded needs denoising_pos_params['per_system'] = True or ['early_stop'] = False: the "
+                         "default early stop is one decision over all systems of a batch, so a shard would not reproduce "
+                         "the single run")
+    B = int(batch.natoms.shape[0])
+    table = params.get("placement_noise")
+    if params.get("noise_seed") is None:
+        stochastic = params.get("sampler", "sde_rot") == "langevin" or (
+            params.get("sampler", "sde_rot") == "sde_rot" and not params.get("ode", True))
+        if stochastic or table is None:
+            raise ValueError("ml_diffuse_sharded needs a shard-invariant noise source: denoising_pos_params['noise_seed'], "
+                             "or an ODE sampler with a global [B,3] 'placement_noise' (the default draws are streams over "
+                             "the batch)")
+    if table is not None:
+        table = torch.as_tensor(table, dtype=torch.float32).reshape(-1, 3)
+        if table.shape[0] != B:
+            raise ValueError(f"placement_noise has {table.shape[0]} rows, the batch has {B} systems")
+    params = _pin_image_repeats(batch, model, params, always=True)   # of the GLOBAL batch: every shard searches the same images
+    mine, ids = sampler.shard_batch(batch, rank, world)
+    local = None
+    if ids:
+        if table is not None:
+            params["placement_noise"] = table[torch.as_tensor(ids, dtype=torch.long)]
+        order = []
+        if table is not None:   # a table indexed by position cannot follow the out-of-memory split: sample unsplit
+            local = Batch.from_data_list([Denoiser(mine, DiffTorchCalc(model, transform), denoising_pos_params=params,
+                                                   device=device, save_full_traj=save_full_traj,
+                                                   traj_dir=Path(traj_dir) if traj_dir is not None else None,
+                                                   traj_names=mine.sid).run()])
+            order = list(range(len(ids)))
+        else:
+            local = Batch.from_data_list(list(_diffuse_parts(mine, model, params, traj_dir, save_full_traj, device, transform,
+                                                             False, None, order)))
+        ids = [ids[i] for i in order]
+    sites = sampler.gather_sites(local, world, via=via, system_ids=ids, bounds=sampler.shard_bounds(batch, world))
+    if world <= 1:   # no exchange: the local sites, brought into global order here
+        sites = sites[torch.argsort(torch.as_tensor(ids, dtype=torch.long)).to(sites.device)]
+    return assemble_sharded(batch, sites, local, ids)
+
+
+def assemble_sharded(batch, sites, local, ids):
+    """The result of ``ml_diffuse_sharded`` on one rank: ``batch`` with every system's adsorbate rows taken from ``sites``
+    ([B, A_max, 3] in global system order, what ``gather_sites`` returns) and, if this rank's shard ``local`` (systems
+    ``ids``, in its order; None for a rank that was dealt nothing) ran in per-system mode, ``sample_steps`` /
+    ``sample_stopped`` filled in for its own systems: -1 / False for the systems sampled elsewhere."""
+    B = int(batch.natoms.shape[0])
+    out = batch.clone()
+    dev = out.pos.device
+    m = out.tags == 2
+    idx_b = out.batch[m]
+    counts = torch.bincount(idx_b, minlength=B)
+    within = torch.arange(idx_b.shape[0], device=dev) - (torch.cumsum(counts, 0) - counts)[idx_b]
+    out.pos = out.pos.clone()
+    out.pos[m] = sites.to(dev, out.pos.dtype)[idx_b, within]
+    if local is not None and hasattr(local, "sample_steps"):
+        gid = torch.as_tensor(ids, dtype=torch.long, device=dev)
+        out.sample_steps = torch.full((B,), -1, dtype=torch.int64, device=dev)
+        out.sample_steps[gid] = local.sample_steps.to(dev)
+        out.sample_stopped = torch.zeros(B, dtype=torch.bool, device=dev)
+        out.sample_stopped[gid] = local.sample_stopped.to(dev)
+    return out
 
 
 def ml_relax(

@@ -151,22 +151,31 @@ def ads_COM_gaussian_schedule(batch, denoise_pos_params: dict):
 
 
 # ---------------------------------------------------------------------------------------------------- keyed draws
+def noise_key_source(batch) -> str:
+    """Where ``noise_keys`` takes a batch's keys from: ``"noise_key"``, ``"sid"`` or ``"index"`` (the position in the batch:
+    the only source that does not identify a system wherever it appears)."""
+    B = int(batch.natoms.shape[0])
+    if getattr(batch, "noise_key", None) is not None:
+        return "noise_key"
+    sid = getattr(batch, "sid", None)
+    return "sid" if sid is not None and len(sid) == B else "index"
+
+
 def noise_keys(batch) -> torch.Tensor:
     """int64 [B] keys of the systems for the counter-based draws, by preference: ``batch.noise_key`` (int64 [B]); the first
     8 bytes (little endian) of ``blake2b(str(sid))`` per system where ``batch.sid`` is present; the system's index in the
     batch otherwise.  The first two identify a system wherever it appears; the index fallback does NOT: with it the noise
     of a system still depends on its position in the batch."""
     B = int(batch.natoms.shape[0])
-    key = getattr(batch, "noise_key", None)
-    if key is not None:
-        key = torch.as_tensor(key).reshape(-1)
+    source = noise_key_source(batch)
+    if source == "noise_key":
+        key = torch.as_tensor(batch.noise_key).reshape(-1)
         if key.dtype != torch.int64 or key.numel() != B:
             raise ValueError(f"batch.noise_key: int64 [{B}] expected, got {key.dtype} [{key.numel()}]")
         return key
-    sid = getattr(batch, "sid", None)
-    if sid is not None and len(sid) == B:
+    if source == "sid":
         return torch.tensor([int.from_bytes(hashlib.blake2b(str(s).encode("utf-8")).digest()[:8], "little", signed=True)
-                             for s in sid], dtype=torch.int64)
+                             for s in batch.sid], dtype=torch.int64)
     return torch.arange(B, dtype=torch.int64)
 
 

@@ -293,7 +293,8 @@ class AdsorbatePlacer:
         """Place ``adsorbates`` on ``sites``: a collated ``Batch`` of all placements, slab-major, then site, then
         augmentation.  ``adsorbates``: one ``(Z, pos)`` for all slabs or one per slab; ``sites``: what ``sites()`` returned,
         or per slab an [n,3] array, or ``(pos [S,3], slab [S])`` tensors; ``binding_indices`` (heuristic placement): one
-        list of atom indices, or one per slab; ``draws``: [P,8] rows, one per placement."""
+        list of atom indices, or one per slab; ``draws``: [P,8] rows, one per placement.  The batch carries ``site_group``
+        (the slab of every placement) and ``site_index`` (int32 [P]: its number within that slab)."""
         if mode not in MODES:
             raise ValueError(f"mode {mode!r}: one of {sorted(MODES)} (\"heuristic\" site finding is not provided; pass "
                              "sites= found elsewhere with mode=\"random_site_heuristic_placement\")")
@@ -405,6 +406,11 @@ class AdsorbatePlacer:
         if sid is not None and len(sid) == B:
             out.sid = [sid[b] for b, c in enumerate(st.counts) for _ in range(c * n_aug)]
         out.site_group = slab_of
+        # the placement's number within its slab: what its own draws are keyed by, and what the sampler's keyed noise
+        # (denoising_pos_params["noise_seed"]) tells the replicas of one slab apart by - they share a sid
+        out.site_index = local.to(torch.int32)
+        if getattr(slab_batch, "noise_key", None) is not None:
+            out.noise_key = noise_keys(slab_batch).to(dev)[slab_of]
         out.site = site
         out.xyz_angles = meta
         out.scaled_normal = sn

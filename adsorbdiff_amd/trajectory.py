@@ -78,6 +78,7 @@ class TrajectoryWriter(threading.Thread):
 
     ``source``: anything with ``wait(index, timeout_ms) -> ndarray[N,3] | None`` and ``release(index)`` (a ``FrameSink``,
     or a fake in the CPU tests).  ``meta``: numbers [N], tags [N], fixed [N], cell [B,3,3], natoms [B], names [B].
+    ``set_frame_counts(counts)`` (optional) limits every system's own file to its first ``counts[b]`` frames;
     ``finish(n_frames)`` tells the writer how many of the pushed frames count (the early stop of the sampler ends a run
     before ``max_frames``; frames pushed after the stop are dropped); ``join()`` then returns once every file exists."""
 
@@ -91,10 +92,17 @@ class TrajectoryWriter(threading.Thread):
         self.error: Optional[BaseException] = None
         self._aborted = False
         self._n_final: Optional[int] = None
+        self._counts = None
         self._lock = threading.Lock()
         self.frames_written = 0
         names = [str(n) for n in meta["names"]]
         self.batch_stem = self.traj_dir / f"batch_{names[0]}"
+
+    def set_frame_counts(self, counts) -> None:
+        """Per-system frame counts (the sampler's per-system mode; call before ``finish``): ``<sid>.npz`` of system b holds
+        its first ``counts[b]`` frames - the frames after its own stop are copies.  The batch file keeps every frame."""
+        with self._lock:
+            self._counts = [int(c) for c in counts]
 
     def finish(self, n_frames: int) -> None:
         with self._lock:
@@ -185,11 +193,16 @@ class TrajectoryWriter(threading.Thread):
         numbers, tags, fixed = (np.asarray(self.meta[k]) for k in ("numbers", "tags", "fixed"))
         cell = np.asarray(self.meta["cell"]).reshape(-1, 3, 3)
         start = 0
+        with self._lock:
+            counts = self._counts
+        if counts is not None and (self.keep_last_only or len(counts) != len(natoms)):
+            counts = None
         for b, (na, name) in enumerate(zip(natoms, names)):
             sl = slice(start, start + na)
+            nf = frames.shape[0] if counts is None else max(min(counts[b], frames.shape[0]), 1)
             tmp = self.traj_dir / f"{name}.npz_tmp"
             with open(tmp, "wb") as fh:
-                np.savez(fh, positions=frames[:, sl], numbers=numbers[sl], tags=tags[sl], fixed=fixed[sl], cell=cell[b])
+                np.savez(fh, positions=frames[:nf, sl], numbers=numbers[sl], tags=tags[sl], fixed=fixed[sl], cell=cell[b])
             tmp.rename(self.traj_dir / f"{name}.npz")
             start += na
         # the batch file: trimmed to the frames that count, final name last (a reader never sees a half-written one)

@@ -322,6 +322,20 @@ typedef struct {
 } adf_counters;
 int32_t adf_get_counters(adf_painn_t h, adf_counters* out, void* stream);
 
+/* ---- Per-system early stop (opt-in; csrc/stepper.hip).  sys_state: [B,4] int32 DEVICE memory owned by the caller, row b =
+ * {cvg_count, frozen, steps_applied, stop_step}, initialised to {0, 0, 0, -1}; NULL switches the mode off.  While it is set,
+ * adf_sde_step[_scheduled], adf_tr_step, adf_sample[_traj] and adf_tr_sample[_traj] on this handle apply the reference's
+ * loop (denoising_torch.py:312-320) to every system on its own, as if it were sampled alone:
+ *   frozen: nothing is read of f1 / f2 and nothing written to its pos rows; its dcom / drot output rows are 0;
+ *   else dcom / drot as always; if its wrapped |dcom| <= 1e-3: cvg_count += 1, and when cvg_count == early_stop_count
+ *   the system freezes with stop_step = state[4], this step's update NOT applied (the reference's break);
+ *   a system that did not freeze gets the update and steps_applied += 1.  early_stop_count == 0: nothing freezes.
+ * The arithmetic is the coupled path's own (shared device functions): at B = 1 both give the same bits.
+ * state[] in this mode: [0] frozen systems, [1] 1 iff all B are frozen (what the fused loops poll), [3] max steps_applied,
+ * [4] steps issued.  One kernel per step (one wave per system) plus a one-thread launch that advances state[4].
+ * A call whose batch does not have B systems returns ADF_EINVAL. */
+int32_t adf_painn_set_per_system_stop(adf_painn_t h, int32_t* sys_state, int32_t B);
+
 /* Optional HIP-event timing of the kernel groups of adf_painn_forward / adf_sde_step, recorded
  * on the launch stream.  Categories: 0 graph build, 1 message kernel (one launch per layer),
  * 2 node-side dense blocks (LayerNorm + GEMMs + update), 3 output heads, 4 stepper.
@@ -616,6 +630,16 @@ int32_t adf_op_score_loss_tr(const float* f1, const int32_t* tags, const int32_t
  * r = sqrt(-2 ln a_2p), n_2p = r cos(2 pi a_2p+1), n_2p+1 = r sin(2 pi a_2p+1).  Row = (u_t, n0..n5, u_om): n0..2 the COM
  * noise, n3..5 the rotation axis before normalisation. */
 int32_t adf_noise_draws(int64_t seed, int32_t step, const int64_t* keys, int32_t B, double* out, void* stream);
+/* The sampler's draws, keyed like the rows above: a system's rows depend on (seed, keys[b], site[b]) alone, so it is
+ * sampled the same alone, in any batch, in any order and on any shard.  Philox4x32-10, key (seed lo, seed hi), counters
+ * (key lo, key hi, t, 4 + 2 site + j), j = 0, 1 (last words 0..3 belong to adf_noise_draws and adf_place_draws).  site: the
+ * number of the placement within its slab (NULL = 0), outside [0, 2^30) is ADF_EINVAL (read back once, synchronises).
+ * Step row t in [0, T): words w0..w7 of j = 0, 1; Box-Muller in double on (w0,w1), (w2,w3), (w4,w5) as adf_noise_draws;
+ * z_a[t,b] = float(n0, n1, n2), z_b[t,b] = float(n3, n4, n5).  Placement row: t = 0xFFFFFFFF, j = 0,
+ * place[b,k] = (w_k >> 8) 2^-24, k = 0..2: in [0, 1), exact in float32.  Any of place [B,3], z_a, z_b [T,B,3] may be NULL.
+ * Use: adf_sample with noise: z_tr_all = z_a, z_rot_all = z_b; Langevin: z_all = z_a. */
+int32_t adf_sampler_draws(int64_t seed, const int64_t* keys, const int32_t* site, int32_t B, int32_t T, float* place,
+                          float* z_a, float* z_b, void* stream);
 /* tr_so3_schedule (sde_denoising_trainer.py:67-135 with pbc_correction :45-64 and rot_utils.py:18-98, 226-253) given one row
  * of draws per system: t = float(u_t), both sigmas in float32, the COM noise wrapped to its minimum image (fractional
  * solve in double), rot_update = axis / |axis| * omega(u_om) and its score by the table look-ups of rot_utils.py in
@@ -881,6 +905,9 @@ int32_t adf_eqv2_tr_sample_traj(adf_eqv2_t h, const adf_batch* b, float* pos, co
                                 const adf_tr_coef* coefs_dev, int32_t num_steps, const float* z_all,
                                 int32_t early_stop_count, int32_t poll_every, int32_t* state, const int32_t* out_idx,
                                 int32_t n_out, float* f1, adf_frames_t sink, int32_t frame_every, void* stream);
+
+/* adf_painn_set_per_system_stop on an EquiformerV2 handle: adf_eqv2_sde_step, adf_eqv2_tr_step and the fused loops. */
+int32_t adf_eqv2_set_per_system_stop(adf_eqv2_t h, int32_t* sys_state, int32_t B);
 
 /* Stand-alone torch.nn.functional.linear (+ optional SiLU, act = 2) through this path's dense-product kernels (unit tests
  * and micro-benchmarks of so2_ops.py:12-79,158-238 / so3.py:694-745 shapes).  A [M,K], W [N,K], bias [N] or NULL, C [M,N],
