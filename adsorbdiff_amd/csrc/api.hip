@@ -25,27 +25,16 @@ adf_tune adf_tune_from_env() {
     auto off_is_0 = [](const char* name) { const char* e = getenv(name); return (e && atoi(e) == 0) ? 0 : 1; };
     auto is_f32 = [](const char* name) { const char* e = getenv(name); return e && strcmp(e, "f32") == 0; };
     adf_tune t = {};
-    const char* mi = getenv("ADF_GEMM16_MI");
-    t.gemm16_mi = (mi && atoi(mi) == 4) ? 4 : 2;
-    t.gemm_w8_plain = off_is_0("ADF_GEMM_W8_PLAIN");
-    t.gemm_w8 = off_is_0("ADF_GEMM_W8");
-    t.gemm_wreg = off_is_0("ADF_GEMM_WREG");
-    const char* wf = getenv("ADF_GEMM_WR_FUSED");
-    t.gemm_wr_fused = wf ? atoi(wf) : 2;
-    if (t.gemm_wr_fused != 0 && t.gemm_wr_fused != 4) t.gemm_wr_fused = 2;
+    t.gemm_stream = off_is_0("ADF_GEMM_STREAM");
     t.head_gate_fused = off_is_0("ADF_HEAD_GATE_FUSED");
     t.lift_emit = off_is_0("ADF_LIFT_EMIT");
     t.graph_sys_csr = off_is_0("ADF_GRAPH_SYS_CSR");
     t.train_gemm16 = is_f32("ADF_TRAIN_GEMM") ? 0 : 1;
     t.wgrad_f32 = is_f32("ADF_WGRAD") ? 1 : 0;
-    const char* pw = getenv("ADF_EQV2_PW_MI");
-    t.eqv2_pw_mi = (pw && atoi(pw) == 3) ? 3 : 4;
     const char* gt = getenv("ADF_EQV2_GEMM_TILE");
     t.eqv2_gemm_tile256 = (gt && atoi(gt) == 128) ? 0 : 1;
     t.eqv2_rotin_generic = getenv("ADF_EQV2_ROTIN_GENERIC") != nullptr;
     t.eqv2_rotout_generic = getenv("ADF_EQV2_ROTOUT_GENERIC") != nullptr;
-    const char* r4 = getenv("ADF_GEMM_ROWS4");
-    t.gemm_rows4 = r4 ? (atoi(r4) & 3) : 3;   // both bits on: each measured faster alone and together (profiles/NOTES.md)
     return t;
 }
 const adf_tune& adf_tune_process() {

@@ -207,7 +207,7 @@ int32_t eq_launch_gemm16p(const void* Ahi, const void* Alo, const float* mag, co
 // the same product with the weights streamed from their fragment image (W->frag); eq_gemm16pw_ok: shapes it takes
 bool eq_gemm16pw_ok(const adf_w16* W, int N, int K);
 int32_t eq_launch_gemm16pw(const void* Ahi, const void* Alo, const float* mag, const adf_w16* W, const float* bias, float* Cm,
-                           int ldc, long long M, int N, int K, int act, hipStream_t s, const adf_tune& tune);
+                           int ldc, long long M, int N, int K, int act, hipStream_t s);
 // rsp (optional): per-order arrays that receive the power-of-two lifts of the output rows (matrix-core version only;
 // *rs_written tells whether they were filled)
 int32_t eq_launch_s2act(const adf_eqv2* h, const float* y0, float* const* ym, int extra, int gate_off, int n0, int n1,

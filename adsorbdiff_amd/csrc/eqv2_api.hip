@@ -779,9 +779,9 @@ int32_t eq_gemm(const adf_eqv2* h, const float* A, int lda, const eq_rowmap* ama
         // per-row power-of-two lift of A (eqv2_gemm16.hip; rs_pre: already written by the producer of A), then the product
         if (!rs_pre) ADF_TRY(eq_launch_rowscale(A, am, M, W->in, h->rs, s));
         // Plain dense rows on both sides, whole 256-column tiles, an even number of K tiles: the sampler's streamed-fragment
-        // product kernel of gemm16.hip (eight waves, 192 x 256 tile, software-pipelined conversion; same lifts, same products
-        // in the same order: same bits) - the second SO(2) convolution's orders m >= 1 (N = 1536 / 1280 at config 4); edge-level
-        // launches only (node-level products measured no better there)
+        // product kernel of gemm16.hip (four waves, 96 x 256 tile, two workgroups per CU, software-pipelined conversion; same
+        // lifts, same products in the same order: same bits) - the second SO(2) convolution's orders m >= 1 (N = 1536 / 1280 at
+        // config 4); edge-level launches only (node-level products measured no better there)
         if (h->conv2_wr && !amap && !cmap && !accumulate && act == 0 && !out_mag && (!rs_pre || rs_div == 1) && W->w16.frag &&
             W->out % 256 == 0 && (W->in / 32) % 2 == 0 && lda == W->in && M >= 65536 && M * (long long)lda * 4 < (1ll << 32) && M < (1ll << 31))
         {
@@ -882,7 +882,7 @@ static int32_t eq_attention(adf_eqv2* h, const eq_attn* at, const float* y, cons
                     const _Float16* hi = reinterpret_cast<const _Float16*>(b.m[m]);
                     if (h->conv1_wr && eq_gemm16pw_ok(&W->w16, W->out, W->in))
                         ADF_TRY(eq_launch_gemm16pw(hi, hi + (size_t)rows * W->in, b.rsb[m], &W->w16, m == 0 ? W->b : nullptr,
-                                                   b.y[m], W->out, rows, W->out, W->in, 0, s, h->tune));
+                                                   b.y[m], W->out, rows, W->out, W->in, 0, s));
                     else
                         ADF_TRY(eq_launch_gemm16p(hi, hi + (size_t)rows * W->in, b.rsb[m], &W->w16, m == 0 ? W->b : nullptr, b.y[m],
                                                   W->out, rows, W->out, W->in, 0, s));
@@ -1311,7 +1311,7 @@ extern "C" int32_t adf_eqv2_linear_forward(const float* A, const float* W, const
         st = adf_pack_frag(&w16, N, K, w16.frag, s);
     }
     for (int r = 0; r < (repeat > 0 ? repeat : 1) && st == ADF_OK; ++r) {
-        if (mode == 3) st = eq_launch_gemm16pw(split, split + ma * 2, mag, &w16, bias, Cm, N, M, N, K, act, s, adf_tune_process());
+        if (mode == 3) st = eq_launch_gemm16pw(split, split + ma * 2, mag, &w16, bias, Cm, N, M, N, K, act, s);
         else if (mode == 2) st = eq_launch_gemm16p(split, split + ma * 2, mag, &w16, bias, Cm, N, M, N, K, act, s);
         else st = eq_launch_gemm16(A, &am, mag, &w16, bias, Cm, &cm, M, N, K, act, false, s, adf_tune_process(), nullptr);
     }

@@ -618,12 +618,10 @@ int32_t eq_launch_gemm16p(const void* Ahi, const void* Alo, const float* mag, co
 // requested two tiles ahead in two register sets and copied into the other buffer between the products of the second
 // k-step.  Per K tile a CU's LDS moves (TM / 256) x (128 KB of fragment reads + 32 KB of writes) instead of 196 + 64 KB.
 // Same products in the same order as eq_gemm16p_kernel: same bits.
-//   NWN = 4: 8 waves as 2 (M) x 4 (N), tile (64 MI) x 256, one workgroup per CU.
-//   NWN = 2: 4 waves as 2 x 2, tile (64 MI) x 128, two workgroups per CU: the remainder columns of an N that is not a
-//   multiple of 256 (order 2 of config 4: 640 = 2 x 256 + 128) without idle column waves.
-// Columns [col0, col0 + tiles_n * TN) of C; needs K / 32 even and N % 32 == 0 (launcher).
+// Eight waves, 256 x 256 tile, one workgroup per CU.  Columns [col0, col0 + tiles_n * TN) of C; needs K / 32 even and
+// N % 32 == 0 (launcher).
 // TMI: tile rows / 64; NWN: waves / 2 (tile columns 64 NWN); the 2 NWN waves sit as (2 NWN / WCOLS) x WCOLS, each on MI row blocks
-// x 2 column blocks: MI = TMI, WCOLS = NWN is the full tile; MI = 2, WCOLS = 2 on eight waves the 256 x 128 HALF tile (below)
+// x 2 column blocks: MI = TMI, WCOLS = NWN is the full tile, 2 (M) x 4 (N) waves; MI = 2, WCOLS = 2 the 256 x 128 HALF tile (below)
 template <int ACT, int TMI, int NWN, int MI, int WCOLS>
 __device__ __forceinline__ void eq_gemm16pw_tile(
     const _Float16* __restrict__ Ahi, const _Float16* __restrict__ Alo, const float* __restrict__ mag,
@@ -788,65 +786,42 @@ __device__ __forceinline__ void eq_gemm16pw_tile(
 // 256-row A tile - shared through L2 with the workgroups of the full column tiles beside it - on eight waves as 4 (M) x 2 (N), two row
 // blocks each: no idle column waves and no second pass over the operand rows (a separate four-wave launch for those columns re-read
 // all of A: 3.4 GB for a fifth of the columns, MfmaUtil 32 % beside 56 %).
-template <int ACT, int MI, int NWN>
-__global__ __launch_bounds__(128 * NWN, NWN == 4 ? 1 : 2) void eq_gemm16pw_kernel(
+template <int ACT>
+__global__ __launch_bounds__(512, 1) void eq_gemm16pw_kernel(
     const _Float16* __restrict__ Ahi, const _Float16* __restrict__ Alo, const float* __restrict__ mag,
     const half8* __restrict__ Wf, const float* __restrict__ inv_scale, const float* __restrict__ bias, float* __restrict__ Cm,
     int ldc, long long M, int N, int K, int tiles_n, int col0) {
     extern __shared__ __attribute__((aligned(16))) _Float16 ldsw[];
-    __shared__ float rinv[64 * MI];
-    if constexpr (NWN == 4 && MI == 4) {
+    __shared__ float rinv[256];
+    {   // (a scope of its own: hipcc lays the two tiles out differently when n0 lives to the end of the kernel)
         const int n0 = col0 + (int)((blockIdx.x >> 3) % tiles_n) * 256;
         if (N - n0 <= 128) {
             eq_gemm16pw_tile<ACT, 4, 4, 2, 2>(Ahi, Alo, mag, Wf, inv_scale, bias, Cm, ldc, M, N, K, tiles_n, col0, ldsw, rinv);
             return;
         }
     }
-    eq_gemm16pw_tile<ACT, MI, NWN, MI, NWN>(Ahi, Alo, mag, Wf, inv_scale, bias, Cm, ldc, M, N, K, tiles_n, col0, ldsw, rinv);
-}
-
-template <int ACT, int MI, int NWN>
-static int32_t eq_gemm16pw_go(const void* Ahi, const void* Alo, const float* mag, const adf_w16* W, const float* bias, float* Cm,
-                              int ldc, long long M, int N, int K, int col0, int ncols, hipStream_t s) {
-    constexpr int TM = 64 * MI, TN = 64 * NWN;
-    const int tiles_n = (ncols + TN - 1) / TN;
-    const long long tiles_m8 = ((M + TM - 1) / TM + 7) / 8 * 8;
-    const long long nb = tiles_m8 * tiles_n;
-    if (nb > 0x7fffffffLL) { adf_set_error("eq_gemm16pw: grid too large"); return ADF_EINVAL; }
-    // two A buffers; the epilogue's per-wave transposition scratch (2 NWN waves x 8 KB) lives in the same bytes
-    size_t dyn = (size_t)2 * 2 * TM * 32 * sizeof(_Float16);
-    const size_t scratch = (size_t)2 * NWN * 32 * GTLD * sizeof(float);
-    if (dyn < scratch) dyn = scratch;
-    auto kern = &eq_gemm16pw_kernel<ACT, MI, NWN>;
-    ADF_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
-    hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(128 * NWN), dyn, s, (const _Float16*)Ahi, (const _Float16*)Alo, mag,
-                       (const half8*)W->frag, W->inv_scale, bias, Cm, ldc, M, N, K, tiles_n, col0);
-    ADF_HIP_CHECK(hipGetLastError());
-    return ADF_OK;
+    eq_gemm16pw_tile<ACT, 4, 4, 4, 4>(Ahi, Alo, mag, Wf, inv_scale, bias, Cm, ldc, M, N, K, tiles_n, col0, ldsw, rinv);
 }
 
 // whether eq_launch_gemm16pw takes the shape (the weight needs its fragment image)
 bool eq_gemm16pw_ok(const adf_w16* W, int N, int K) { return W->frag && N % 32 == 0 && K % 64 == 0 && N >= 128; }
 
 int32_t eq_launch_gemm16pw(const void* Ahi, const void* Alo, const float* mag, const adf_w16* W, const float* bias, float* Cm,
-                           int ldc, long long M, int N, int K, int act, hipStream_t s, const adf_tune& tune) {
+                           int ldc, long long M, int N, int K, int act, hipStream_t s) {
     if (M <= 0 || N <= 0) return ADF_OK;
     if (!eq_gemm16pw_ok(W, N, K)) { adf_set_error("eq_gemm16pw: shape or fragment image"); return ADF_EINVAL; }
-    const int mi = tune.eqv2_pw_mi;   // rows per tile: 256 (default; 1.5 % faster than 192 on config 4's shapes), ADF_EQV2_PW_MI=3: 192
-    // whole 256-column tiles on eight waves; a remainder of at most 128 columns on the four-wave form
-    const int rem = N % 256;
-    // 256-row tiles: a last tile of at most 128 columns runs the kernel's half layout; 192-row tiles (ADF_EQV2_PW_MI=3): the
-    // four-wave remainder launch
-    const int wide = (mi == 3 && rem > 0 && rem <= 128) ? N - rem : N;
-#define EQ_PW(ACT_, MI_, NWN_, C0_, NC_) eq_gemm16pw_go<ACT_, MI_, NWN_>(Ahi, Alo, mag, W, bias, Cm, ldc, M, N, K, C0_, NC_, s)
-    if (wide > 0) {
-        if (act == 2) { if (mi == 4) ADF_TRY(EQ_PW(2, 4, 4, 0, wide)); else ADF_TRY(EQ_PW(2, 3, 4, 0, wide)); }
-        else { if (mi == 4) ADF_TRY(EQ_PW(0, 4, 4, 0, wide)); else ADF_TRY(EQ_PW(0, 3, 4, 0, wide)); }
-    }
-    if (wide < N) {
-        if (act == 2) ADF_TRY(EQ_PW(2, 3, 2, wide, N - wide)); else ADF_TRY(EQ_PW(0, 3, 2, wide, N - wide));
-    }
-#undef EQ_PW
+    const int tiles_n = (N + 255) / 256;
+    const long long tiles_m8 = ((M + 255) / 256 + 7) / 8 * 8;
+    const long long nb = tiles_m8 * tiles_n;
+    if (nb > 0x7fffffffLL) { adf_set_error("eq_gemm16pw: grid too large"); return ADF_EINVAL; }
+    // two A buffers of 256 rows (hi + lo, 64 B each); the epilogue's per-wave transposition scratch (8 waves x 8 KB) lives in the same bytes
+    const size_t dyn = (size_t)2 * 2 * 256 * 32 * sizeof(_Float16);
+    static_assert(2 * 2 * 256 * 32 * sizeof(_Float16) >= 8 * 32 * GTLD * sizeof(float), "the scratch fits the A buffers");
+    auto kern = act == 2 ? &eq_gemm16pw_kernel<2> : &eq_gemm16pw_kernel<0>;
+    ADF_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
+    hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(512), dyn, s, (const _Float16*)Ahi, (const _Float16*)Alo, mag,
+                       (const half8*)W->frag, W->inv_scale, bias, Cm, ldc, M, N, K, tiles_n, 0);
+    ADF_HIP_CHECK(hipGetLastError());
     return ADF_OK;
 }
 

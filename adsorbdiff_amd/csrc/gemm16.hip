@@ -13,17 +13,18 @@
 // while they are staged into LDS.  The exact-f32 kernel (gemm.hip) stays selectable
 // (ADF_GEMM=f32) and is what this kernel is tested against.
 //
-// Tiling (default): 128(M) x 256(N) x 32(K) per 256-thread workgroup, 4 waves as 2(M) x 2(N), each wave 64 x 128 =
-// 2 x 4 MFMA 32x32 accumulators, two workgroups per CU.  LDS holds A_hi, A_lo [128][32+8] and W_hi, W_lo [256][32+8]
-// halves (row stride 80 B: the 16 lanes of a ds_read_b128 lane group land on 16 distinct 16-B bank quads).
-// Global loads are 16 B per lane, prefetched one K-tile ahead in registers; XCD-aware tile map as in
-// gemm.hip (all N-tiles of an M-panel on one XCD's L2).  Every epilogue transposes the accumulators through the
-// idle staging LDS so that global accesses are 16 B per lane, and issues all its loads before its first store.  The record
-// epilogue (EPI 1) also stores whole 128-B lines: the eight lanes of a row exchange their float4s through 4 KB of LDS per wave.
-// That tile is the LDS-staged form (rounds 1-5), still what shapes without a fragment image run.  The sampler's products stream
-// their weights as register fragments (WR, kernel comment) and run as four waves laid out 1(M) x 4(N), two workgroups per CU:
-// 96 x 256 tiles (plain, vec_proj, vector-norm products) and 64 x 384 tiles (x_proj.2 / xvec_proj.2 with their fused
-// epilogues); adf_tune::gemm_rows4 = 0 selects the eight-wave 192 x 256 resp. four-wave 2(M) x 2(N) 128 x 192 tiles before them.
+// Two tile forms, each a 256-thread workgroup at two workgroups per CU (g16_tile_of below is the geometry table):
+//   LDS-staged, 4 waves as 2(M) x 2(N): A_hi, A_lo [TM][32+8] and W_hi, W_lo [TN][32+8] halves per 32-deep K tile in LDS (row
+//     stride 80 B: the 16 lanes of a ds_read_b128 lane group land on 16 distinct 16-B bank quads), global loads of 16 B per
+//     lane prefetched one K tile ahead in registers.  Runs any shape, and is the reference form the bit-identity tests compare
+//     the other one against (adf_tune::gemm_stream = 0 selects it everywhere).
+//   streamed, 4 waves as 1(M) x 4(N): the weights are not staged - every wave loads the MFMA B fragments of its own columns
+//     from a fragment-ordered image (adf_pack_frag) into a ring of register sets; LDS holds two A buffers and there is one
+//     barrier per K tile.  Needs the image, whole column tiles and an even number of K tiles; the default where those hold.
+// Both use the XCD-aware tile map of gemm.hip (all N-tiles of an M-panel on one XCD's L2).  Every epilogue transposes the
+// accumulators through the idle staging LDS so that global accesses are 16 B per lane, and issues all its loads before its
+// first store.  The record epilogue (EPI 1) also stores whole 128-B lines: the eight lanes of a row exchange their float4s
+// through 4 KB of LDS per wave.  Same products in the same order in both forms: same bits.
 #include <stdlib.h>
 
 #include "common.h"
@@ -36,24 +37,10 @@ typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 #define EPI_ABL 0   // timing experiments only (wrong results): bit 0 = EPI 1 without its epilogue, bit 1 = EPI 2 without,
                     // bit 2 = EPI 1/2 without their global loads, bit 3 = without their global stores
 #endif
-#ifndef EPI2_POLICY
-#define EPI2_POLICY 0   // cache policy of EPI 2's one-touch epilogue streams: bit 0 = the x / vec outputs stored sc1 (write-through:
-                        // the line is dropped from the XCD's L2 instead of kept), bit 1 = the v1 / dot / vec / x inputs loaded
-                        // non-temporally.  Same sites; each measured alone against 0: node products inside the run-to-run spread,
-                        // EPI 2's L2 hit rate 0.65 -> 0.56 / 0.57 (profiles/NOTES.md, row maxima section): left off
-#endif
 #ifndef G16_ABL
 #define G16_ABL 0   // timing experiments only (wrong results; harness builds): 1 = vec_proj epilogue without its global stores,
                     // 2 = A tile staged without the fp32 -> hi/lo conversion, 4 = A rows all read from row 0 (cache-hot),
                     // 8 = no products (staging + epilogue only)
-#endif
-#ifndef G16_WDEEP
-#define G16_WDEEP 1   // WR kernels request their weight fragments two k-steps ahead (four register sets); 0: one k-step (node products 1699 -> 1681 ms per pass with 1)
-#endif
-#ifndef G16_START_DELAY
-#define G16_START_DELAY 0   // timing experiment (same results): the four-wave 1(M) x 4(N) workgroups that take the second residency
-                            // slot of their CU in the first round (256 CUs: blockIdx >> 3 in [32, 64)) start this many
-                            // s_sleep(127) (~8k cycles each) late, so that the CU's two workgroups are not in the same phase
 #endif
 #define HK 32
 // Row strides (floats) of the epilogues' transposition buffers.  Unpadded on purpose: with the lane groups of
@@ -78,53 +65,57 @@ __device__ __forceinline__ float ssilu16(float x) {
     return s * 1.6666666666666667f;
 }
 
-// Workgroup = 4 waves as 2(M) x 2(N); wave tile = (32*MI) rows x (32*NJ) columns of MFMA 32x32 blocks.
-//   MI=2,NJ=4 (default): 128 x 256 tile, 2 workgroups per CU.
-//   NJ=3 with EPI != 0: the three column blocks of a wave are the three H-wide parts of a 3H-wide
-//   linear layer for the SAME 32 channels (weights row-permuted at set_weights:
-//   column g*96 + part*32 + q  <->  original row part*H + 32g + q), so the consumer's elementwise
-//   work runs on the accumulators and the 3H-wide intermediate never goes to HBM:
+// Tile geometry of a form (STREAM: weights streamed as register fragments; else staged through LDS) and an epilogue: the
+// one place it is written down, read by the kernel and by the launch helper.  A workgroup is 4 waves, NWM along M and NWN
+// along N; a wave's tile is 32 MI rows x 32 NJ columns of MFMA 32x32 blocks.
+//                          EPI 0            EPI 1 / 2        EPI 3 / 4 (M counts atoms: 3 rows each)
+//   LDS-staged, 2 x 2      128 x 256        128 x 192        64 atoms x 128
+//   streamed,   1 x 4       96 x 256         64 x 384        32 atoms x 256
+struct g16_tile {
+    int NWN;         // waves along N (4 / NWN along M)
+    int MI, NJ;      // MFMA blocks of a wave along M and N
+    int NT;          // threads
+    int TM, TN;      // staged A rows and columns per workgroup
+    int ROWS;        // rows of M per workgroup
+};
+constexpr g16_tile g16_tile_of(int epi, bool stream) {
+    const int nwm = stream ? 1 : 2, nwn = stream ? 4 : 2;
+    const int mi = epi >= 3 ? 3 : (epi ? 2 : (stream ? 3 : 2));
+    const int nj = epi >= 3 ? 2 : (epi ? 3 : (stream ? 2 : 4));
+    const int tm = 32 * mi * nwm;
+    return {nwn, mi, nj, 64 * nwm * nwn, tm, 32 * nj * nwn, epi >= 3 ? tm / 3 : tm};
+}
+
+// One kernel for every f16x3 node product: <ScaledSiLU, epilogue, form>.
+//   EPI 0: C = act(A W^T + bias), with the optional operands of adf_epi (second K source, gate, accumulate, row maxima).
+//   EPI 1 / 2 (NJ = 3): the three column blocks of a wave are the three H-wide parts of a 3H-wide linear layer for the SAME
+//   32 channels (weights row-permuted at set_weights: column g*96 + part*32 + q  <->  original row part*H + 32g + q), so the
+//   consumer's elementwise work runs on the accumulators and the 3H-wide intermediate never goes to HBM:
 //     EPI 1  x_proj.2 -> gather records of the message kernel ((P0,P1,P2,xa) + xc, P_i = vec_i * xb; message.hip)
 //     EPI 2  xvec_proj.2 -> PaiNNUpdate gating + residuals + ScaleFactor (painn_denoising.py:614-623,449-451)
-//   MI=3, NJ=2 with EPI 3: vec_proj of PaiNNUpdate (painn_denoising.py:602-611).  The A rows of vec [N,3,H] are
-//   staged component-major (LDS row = component*32 + atom), so accumulator block i of a wave is component i of
-//   its 32 atoms; the two column blocks are v1 and v2 of the same 32 channels (weights row-permuted: column
-//   g*64 + part*32 + q  <->  row part*H + 32g + q).  dot = sum_xyz v1*v2 / sqrt(H) and |v2| ([N,H] each) are formed
-//   on the accumulators: v2 (1.2 GB per layer at N = 200k) never goes to HBM and the separate reduction pass is gone.
-//   WR (round 6; every product of the PaiNN sampler): the weights are NOT staged through LDS - every wave loads the MFMA B
-//   fragments of its own columns straight from a fragment-ordered image (adf_pack_frag below; `Whi` then points at that
-//   image) into a ring of register sets, two k-steps ahead; LDS holds two A buffers, there is one barrier per K tile, and the
-//   lift / split of the next A tile is dealt between the MFMAs of the current one (see the main loop).  Same products in the
-//   same order as the LDS-staged form (kept below, WR = false): same bits.
-//   NWN (WR only): waves along N.  2 (default): 4 waves, tile columns 64 NJ.  4: 8 waves as 2(M) x 4(N), 512 threads, tile
-//   columns 128 NJ - the A tile (staged, lifted and split once per workgroup) then serves twice the columns: half the L2 reads
-//   and half the conversions of the A panel (vec_proj: the panel was re-staged by 8 column tiles; staging + epilogue alone
-//   took 1.14 of the kernel's 2.2 ms in the stand-alone harness).
-//   NWM (WR only): waves along M.  2 (default): the layouts above.  1 with NWN = 4: 4 waves as 1(M) x 4(N), 256 threads, tile
-//   32 MI rows x 128 NJ columns (96 x 256: EPI 0 / 3 / 4, 32 atoms x 3 components for EPI 3 / 4; 64 x 384: EPI 1 / 2), two
-//   workgroups per CU.  Every wave runs the instruction stream it runs in the eight-wave form (same accumulators, same A
-//   float4s per thread and K tile, same fragment ring) and the A tile still serves all the columns; the barrier spans four
-//   waves, and the prologue / epilogue of one workgroup can run beside the K loop of the CU's other one.  A weight fragment
-//   is then requested once per 32 MI rows instead of once per 64 MI.  Measured against the forms above (kernel trace of the
-//   benchmark, average per launch): vec_proj 1717 -> 1615 us, plain products with ScaledSiLU 524 -> 486, without 549 -> 483, the
-//   vector-norm product 646 -> 604; xvec_proj.2 1202 -> 1196, x_proj.2 1322 -> 1321 (profiles/NOTES.md, "96 x 256 four-wave
-//   tiles").  Same bits.
-template <int ACT, int MI, int NJ, int EPI, bool WR = false, int NWN = 2, int NWM = 2>
-__global__ __launch_bounds__(64 * NWM * NWN, (MI == 4 || NWM * NWN == 8 ? 1 : 2)) void adf_gemm_f16x3_kernel(
+//   EPI 3 (MI = 3, NJ = 2): vec_proj of PaiNNUpdate (painn_denoising.py:602-611).  The A rows of vec [N,3,H] are staged
+//   component-major (LDS row = component*32 + atom), so accumulator block i of a wave is component i of its 32 atoms; the two
+//   column blocks are v1 and v2 of the same 32 channels (weights row-permuted: column g*64 + part*32 + q  <->  row
+//   part*H + 32g + q).  dot = sum_xyz v1*v2 / sqrt(H) and |v2| ([N,H] each) are formed on the accumulators: v2 never goes to HBM.
+//   EPI 4: the same staging; only ||W v||_xyz is stored (see its epilogue).
+//   STREAM: `Whi` points at the fragment image and `Wlo` is unused.  The B fragments are requested two k-steps ahead (four
+//   register sets), LDS holds two A buffers, there is one barrier per K tile, and the lift / split of the next A tile is dealt
+//   between the MFMAs of the current one (see the main loop).  The A tile serves all the workgroup's columns, and the prologue
+//   / epilogue of one workgroup runs beside the K loop of the CU's other one.  Same products in the same order as the
+//   LDS-staged form: same bits.
+template <int ACT, int EPI, bool STREAM>
+__global__ __launch_bounds__(g16_tile_of(EPI, STREAM).NT, 2) void adf_gemm_f16x3_kernel(
     const float* __restrict__ A, int lda, const _Float16* __restrict__ Whi, const _Float16* __restrict__ Wlo,
     const float* __restrict__ inv_scale, const float* __restrict__ bias, float* __restrict__ C, int ldc, int Mh, int N,
     int K, int tiles_n, adf_epi ep) {
+    constexpr g16_tile geo = g16_tile_of(EPI, STREAM);
+    constexpr int MI = geo.MI, NJ = geo.NJ, NWN = geo.NWN, NT = geo.NT, TM = geo.TM, TN = geo.TN;
     const int M = ep.m_dev ? min(Mh, (int)*ep.m_dev) : Mh;  // rows: the host's bound, or fewer by a device-side count
-    static_assert(NWN == 2 || WR, "eight waves only with the register-streamed weights");
-    static_assert(NWM == 2 || (NWM == 1 && WR), "one wave along M only with the register-streamed weights");
-    constexpr int NT = 64 * NWM * NWN;   // threads
-    constexpr int TM = 32 * MI * NWM;    // rows per workgroup
-    constexpr int TN = 32 * NJ * NWN;    // columns per workgroup
     constexpr int NA = TM * 8 / NT;      // float4 A loads per thread
     static_assert(TM * 8 % NT == 0, "A staging: whole float4s per thread");
-    // (WR: no W tiles; two A buffers, reused as the epilogues' scratch of NT / 64 waves x 3200 floats)
-    constexpr int LDS_WR = 4 * TM * HLD > NT / 64 * 6400 ? 4 * TM * HLD : NT / 64 * 6400;   // two A buffers (hi + lo) | the scratch
-    constexpr int LDS_MAIN = WR ? LDS_WR : (2 * TM + 2 * TN) * HLD;
+    // (streamed: no W tiles; two A buffers, reused as the epilogues' scratch of NT / 64 waves x 3200 floats)
+    constexpr int LDS_STREAM = 4 * TM * HLD > NT / 64 * 6400 ? 4 * TM * HLD : NT / 64 * 6400;   // two A buffers (hi + lo) | the scratch
+    constexpr int LDS_MAIN = STREAM ? LDS_STREAM : (2 * TM + 2 * TN) * HLD;
     constexpr int LDS_REC = EPI == 1 ? NT / 64 * 2048 : 0;   // EPI 1: 4 KB per wave behind the scratch, the record exchange (epilogue)
     __shared__ __attribute__((aligned(16))) _Float16 lds[LDS_MAIN + LDS_REC];
     __shared__ float rinv[TM];  // 1 / lift of every staged A row
@@ -143,15 +134,9 @@ __global__ __launch_bounds__(64 * NWM * NWN, (MI == 4 || NWM * NWN == 8 ? 1 : 2)
     const int qd = id >> 3;
     const int tile_m = (qd / tiles_n) * 8 + xcd;
     const int tile_n = qd % tiles_n;
-    const int m0 = tile_m * (EPI >= 3 ? TM / 3 : TM);  // EPI 3, 4: M counts atoms, a tile holds TM/3 of them
+    const int m0 = tile_m * geo.ROWS;  // EPI 3, 4: M counts atoms, a tile holds TM/3 of them
     const int n0 = tile_n * TN;
     if (m0 >= M) return;
-#if G16_START_DELAY
-    if constexpr (NWM == 1) {
-        if (qd >= 32 && qd < 64)
-            for (int i = 0; i < G16_START_DELAY; ++i) __builtin_amdgcn_s_sleep(127);
-    }
-#endif
 
     // A staging: NA float4 per thread (8 lanes per 128-B row segment, 32 rows per pass).  Addresses are a
     // wave-uniform base + a 32-bit byte offset per lane (the launchers check rows*lda*4 < 2^32), which also lets
@@ -195,14 +180,14 @@ __global__ __launch_bounds__(64 * NWM * NWN, (MI == 4 || NWM * NWN == 8 ? 1 : 2)
     half8 rwh[NJ], rwl[NJ];
 #pragma unroll
     for (int i = 0; i < NA; ++i) ra[i] = *reinterpret_cast<const float4*>(A1b + a_goff[i]);
-    if constexpr (!WR) {
+    if constexpr (!STREAM) {
 #pragma unroll
         for (int i = 0; i < NJ; ++i) {
             rwh[i] = *reinterpret_cast<const half8*>(Whi + w_src[i]);
             rwl[i] = *reinterpret_cast<const half8*>(Wlo + w_src[i]);
         }
     }
-    // WR: B fragments of one 16-deep k-step for this wave's NJ column blocks: [column block][hi | lo]; two register sets
+    // streamed: B fragments of one 16-deep k-step for this wave's NJ column blocks: [column block][hi | lo]; four register sets
     half8 wfa[NJ][2], wfb[NJ][2];
     const half8* const wfr = reinterpret_cast<const half8*>(Whi) + (size_t)((n0 + wn) / 32) * (K / 16) * 128 + lane;
     auto load_wf = [&](int s_, half8 (&wf)[NJ][2]) {
@@ -213,7 +198,7 @@ __global__ __launch_bounds__(64 * NWM * NWN, (MI == 4 || NWM * NWN == 8 ? 1 : 2)
             wf[j][1] = wfr[base + 64];
         }
     };
-    if constexpr (WR) load_wf(0, wfa);
+    if constexpr (STREAM) load_wf(0, wfa);
 
     f32x16 acc[MI][NJ];
 #pragma unroll
@@ -249,9 +234,9 @@ __global__ __launch_bounds__(64 * NWM * NWN, (MI == 4 || NWM * NWN == 8 ? 1 : 2)
 #pragma unroll
         for (int i = 0; i < NA; ++i) ra[i] = *reinterpret_cast<const float4*>(ab + ((G16_ABL & 4) ? (a_goff[i] & 127u) : a_goff[i]));
     };
-    if constexpr (WR) {
-        // The B fragments of a k-step are requested one or two k-steps ahead (G16_WDEEP), in front of the products of the k-step
-        // before (sched_barrier(0) between the request group and the product group: left alone, hipcc sinks the requests to
+    if constexpr (STREAM) {
+        // The B fragments of a k-step are requested two k-steps ahead, in front of the products of the k-step before
+        // (sched_barrier(0) between the request group and the product group: left alone, hipcc sinks the requests to
         // their first use and every k-step waits out an L2 round trip - the retired mlp16.hip's first build).
         auto kstep = [&](int boff, int ks, const half8 (&cur)[NJ][2]) {
             if (G16_ABL & 8) { asm volatile("" :: "v"(cur[0][0]), "v"(cur[0][1]), "v"(cur[NJ - 1][0]), "v"(cur[NJ - 1][1])); return; }
@@ -272,8 +257,8 @@ __global__ __launch_bounds__(64 * NWM * NWN, (MI == 4 || NWM * NWN == 8 ? 1 : 2)
         {
             // Software-pipelined staging: two A buffers, one barrier per K tile, and the conversion of tile kt + 1 is dealt
             // BETWEEN the products of tile kt's second k-step (sched_group_barrier: 1 MFMA, 4 VALU), where the matrix pipe hides
-            // it; its rows were requested two tiles ahead (two register sets).  With eight waves (the only workgroup of its
-            // CU) nothing else could fill the staging time; with four it adds to the overlap between the CU's two workgroups.
+            // it; its rows were requested two tiles ahead (two register sets).  That adds to the overlap between the CU's
+            // two workgroups.
             constexpr int BUF = 2 * TM * HLD;
             float4 rb[NA];
             auto request_b = [&](int kt1) {
@@ -300,7 +285,6 @@ __global__ __launch_bounds__(64 * NWM * NWN, (MI == 4 || NWM * NWN == 8 ? 1 : 2)
                 }
             };
             // tile kt: products on buffer `cur` with the registers `nxt_regs` (tile kt + 1) converted into the other buffer
-#if G16_WDEEP
             // weight fragments TWO k-steps ahead: four register sets, a tile uses (w0, w1) and requests the next tile's into (w2, w3)
             half8 wfc[NJ][2], wfd[NJ][2];
             load_wf(1, wfb);
@@ -313,18 +297,7 @@ __global__ __launch_bounds__(64 * NWM * NWN, (MI == 4 || NWM * NWN == 8 ? 1 : 2)
                 load_wf(min(2 * kt + 3, 2 * nk - 1), w3);
                 __builtin_amdgcn_sched_barrier(0);
                 kstep(cur, 1, w1);
-                stage_from(nxt_regs, BUF - cur);
-#else
-            auto tile = [&](int kt, int cur, const float4 (&nxt_regs)[NA]) {
-                load_wf(2 * kt + 1, wfb);
-                __builtin_amdgcn_sched_barrier(0);
-                kstep(cur, 0, wfa);
-                __builtin_amdgcn_sched_barrier(0);
-                load_wf(min(2 * kt + 2, 2 * nk - 1), wfa);
-                __builtin_amdgcn_sched_barrier(0);
-                kstep(cur, 1, wfb);
                 stage_from(nxt_regs, BUF - cur);   // (behind the last tile: a copy nobody reads)
-#endif
                 __builtin_amdgcn_sched_group_barrier(0x100, 2 * MI, 0);
 #pragma unroll
                 for (int u = 0; u < 3 * MI * NJ; ++u) {
@@ -334,26 +307,16 @@ __global__ __launch_bounds__(64 * NWM * NWN, (MI == 4 || NWM * NWN == 8 ? 1 : 2)
                 }
                 __builtin_amdgcn_sched_barrier(0);
             };
-            // (Measured and dropped: FOUR A buffers and one barrier per PAIR of K tiles for the eight-wave kernels - identical
-            // sites, node products 1662 -> 1714 ms per pass, heads 420 -> 442: the second tile staged in the prologue costs every
-            // workgroup another exposed HBM round trip, the barriers were not what the tiles were waiting for.)
             __syncthreads();   // (rinv)
             stage_a(0);                       // tile 0 (requested in the prologue)
             request_a(min(1, nk - 1));        // tile 1 -> ra
             request_b(min(2, nk - 1));        // tile 2 -> rb
             __syncthreads();
             for (int kt = 0; kt < nk; kt += 2) {   // (nk is even: checked by the launcher)
-#if G16_WDEEP
                 tile(kt, 0, ra, wfa, wfb, wfc, wfd);
                 request_a(min(kt + 3, nk - 1));
                 __syncthreads();
                 tile(kt + 1, BUF, rb, wfc, wfd, wfa, wfb);
-#else
-                tile(kt, 0, ra);
-                request_a(min(kt + 3, nk - 1));
-                __syncthreads();
-                tile(kt + 1, BUF, rb);
-#endif
                 request_b(min(kt + 4, nk - 1));
                 __syncthreads();
             }
@@ -670,22 +633,14 @@ __global__ __launch_bounds__(64 * NWM * NWN, (MI == 4 || NWM * NWN == 8 ? 1 : 2)
                 for (int it = 0; it < 4; ++it) {
                     const int n = min(m0 + wm + 32 * i + it * 8 + (lane >> 3), M - 1);
                     const size_t xo = (size_t)n * H + c;
-#if EPI2_POLICY & 2
-                    typedef float f32x4_t __attribute__((ext_vector_type(4)));
-                    auto ntld = [](const float* p_) { const f32x4_t v = __builtin_nontemporal_load(reinterpret_cast<const f32x4_t*>(p_));
-                                                      return make_float4(v.x, v.y, v.z, v.w); };
-#define EPI2_LD(p_) ntld(p_)
-#else
-#define EPI2_LD(p_) (*reinterpret_cast<const float4*>(p_))
-#endif
-                    d[it] = EPI2_LD(ep.dot + xo);
-                    xv[it] = EPI2_LD(ep.x + xo);
+                    d[it] = *reinterpret_cast<const float4*>(ep.dot + xo);
+                    xv[it] = *reinterpret_cast<const float4*>(ep.x + xo);
                     const float* vr = ep.vec + (size_t)n * 3 * H + c;
                     const float* v1p = ep.vv + (size_t)n * 3 * H + c;  // v1 [N,3,H] written by EPI 3
 #pragma unroll
                     for (int ax = 0; ax < 3; ++ax) {
-                        w1[it][ax] = EPI2_LD(v1p + ax * H);
-                        tv[it][ax] = EPI2_LD(vr + ax * H);
+                        w1[it][ax] = *reinterpret_cast<const float4*>(v1p + ax * H);
+                        tv[it][ax] = *reinterpret_cast<const float4*>(vr + ax * H);
                     }
                 }
 #pragma unroll
@@ -701,28 +656,17 @@ __global__ __launch_bounds__(64 * NWM * NWN, (MI == 4 || NWM * NWN == 8 ? 1 : 2)
                     xo4.y = (xo4.y + (p0.y + p1.y * d[it].y) * k2) * sc;
                     xo4.z = (xo4.z + (p0.z + p1.z * d[it].z) * k2) * sc;
                     xo4.w = (xo4.w + (p0.w + p1.w * d[it].w) * k2) * sc;
-#undef EPI2_LD
-#if EPI2_POLICY & 1
-                    // buffer stores with aux = sc1; descriptors over the whole x / vec arrays (wave-uniform, < 4 GB: check_a_span)
-                    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-                    const auto rx = __builtin_amdgcn_make_buffer_rsrc(ep.x, 0, (int)((unsigned int)M * (unsigned int)H * 4u), 0x00020000);
-                    const auto rv = __builtin_amdgcn_make_buffer_rsrc(ep.vec, 0, (int)((unsigned int)M * 3u * (unsigned int)H * 4u), 0x00020000);
-#define EPI2_ST(r_, p_, base_, v_) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v_), r_, (int)(((p_) - (base_)) * 4), 0, 16)
-#else
-#define EPI2_ST(r_, p_, base_, v_) (*reinterpret_cast<float4*>(p_) = (v_))
-#endif
                     if (n < M) {
-                        EPI2_ST(rx, ep.x + (size_t)n * H + c, ep.x, xo4);
+                        *reinterpret_cast<float4*>(ep.x + (size_t)n * H + c) = xo4;
                         float* vr = ep.vec + (size_t)n * 3 * H + c;
 #pragma unroll
                         for (int ax = 0; ax < 3; ++ax) {
                             float4 t = tv[it][ax];
                             const float4 v1 = w1[it][ax];
                             t.x += p2.x * v1.x; t.y += p2.y * v1.y; t.z += p2.z * v1.z; t.w += p2.w * v1.w;
-                            EPI2_ST(rv, vr + ax * H, ep.vec, t);
+                            *reinterpret_cast<float4*>(vr + ax * H) = t;
                         }
                     }
-#undef EPI2_ST
                 }
             }
             __builtin_amdgcn_wave_barrier();  // T is rewritten for the next 32-row block
@@ -893,6 +837,32 @@ static int32_t check_a_span(long long rows, int lda) {
     return ADF_OK;
 }
 
+// The streamed form runs a product when the switch allows it, the weight has a fragment image, the columns are whole
+// streamed tiles and the K tiles come in pairs (its main loop takes two per round).  Everything else runs LDS-staged.
+static bool can_stream(const adf_tune& tune, const adf_w16* W, int epi, int N, int K) {
+    return tune.gemm_stream && W->frag && N % g16_tile_of(epi, true).TN == 0 && (K / HK) % 2 == 0;
+}
+
+// Launch the (act, epi) kernel of one form over M rows (atoms for EPI 3 / 4) x N columns.  The grid comes from the geometry
+// table, with the row tiles rounded up to the 8 XCDs of the kernel's tile map.
+static int32_t launch_f16x3(bool stream, int act, int epi, const float* A, int lda, const adf_w16* W, const float* bias, float* C,
+                            int ldc, int M, int N, int K, const adf_epi& ep, hipStream_t s) {
+    using kern_t = decltype(&adf_gemm_f16x3_kernel<0, 0, false>);
+#define G16_FORM(STREAM_)                                                                                              \
+    { adf_gemm_f16x3_kernel<0, 0, STREAM_>, adf_gemm_f16x3_kernel<1, 0, STREAM_>, adf_gemm_f16x3_kernel<0, 1, STREAM_>, \
+      adf_gemm_f16x3_kernel<0, 2, STREAM_>, adf_gemm_f16x3_kernel<0, 3, STREAM_>, adf_gemm_f16x3_kernel<0, 4, STREAM_> }
+    static const kern_t kernels[2][6] = {G16_FORM(false), G16_FORM(true)};   // [form][EPI 0, EPI 0 + ScaledSiLU, EPI 1 .. 4]
+#undef G16_FORM
+    const g16_tile t = g16_tile_of(epi, stream);
+    const int tiles_n = (N + t.TN - 1) / t.TN;
+    const int tiles_m8 = ((M + t.ROWS - 1) / t.ROWS + 7) / 8 * 8;
+    hipLaunchKernelGGL(kernels[stream][epi ? epi + 1 : (act ? 1 : 0)], dim3((unsigned)(tiles_m8 * tiles_n)), dim3(t.NT), 0, s, A, lda,
+                       (const _Float16*)(stream ? W->frag : W->hi), (const _Float16*)(stream ? nullptr : W->lo), W->inv_scale,
+                       bias, C, ldc, M, N, K, tiles_n, ep);
+    ADF_HIP_CHECK(hipGetLastError());
+    return ADF_OK;
+}
+
 int32_t adf_launch_gemm16(const float* A, int lda, const adf_w16* W, const float* bias, float* C, int ldc, int M,
                           int N, int K, int act_ssilu, const adf_epi* ep_in, hipStream_t s, const adf_lift* lf,
                           const adf_tune& tune, int num_cus) {
@@ -905,12 +875,6 @@ int32_t adf_launch_gemm16(const float* A, int lda, const adf_w16* W, const float
         return ADF_EINVAL;
     }
     ADF_TRY(check_a_span(M, lda));
-    const int mi = tune.gemm16_mi;
-    const int TM = 64 * mi, TN = 256;
-    const int tiles_n = (N + TN - 1) / TN;
-    const int tiles_m = (M + TM - 1) / TM;
-    const int tiles_m8 = (tiles_m + 7) / 8 * 8;
-    dim3 grid((unsigned)(tiles_m8 * tiles_n));
     // the gate is applied by the float4 store branch alone: it must be the branch every tile of this launch takes
     if (ep.gate && (((N | ldc | ep.gate_ld) & 3) || (((uintptr_t)C | (uintptr_t)ep.gate) & 15))) {
         adf_set_error("gemm16: the gate epilogue needs N, ldc and gate_ld multiples of 4 and 16-byte aligned C and gate");
@@ -918,56 +882,15 @@ int32_t adf_launch_gemm16(const float* A, int lda, const adf_w16* W, const float
     }
     ADF_TRY(lift_mags(A, lda, ep.A2 ? ep.K1 : K, ep.A2, ep.A2 ? K - ep.K1 : 0, M, lf, ep.rmag, &ep.rmag, s, ep.m_dev, 1));
     if (ep.out_mag) ADF_HIP_CHECK(hipMemsetAsync(ep.out_mag, 0, sizeof(float) * (size_t)M, s));
-    // Round 6: weights streamed as fragments, eight waves per workgroup, 192 x 256 tile, software-pipelined staging (see the
-    // kernel comment: WR, NWN = 4).  Needs the fragment image, N a multiple of 256 and an even number of K tiles.
-    // (adf_tune::gemm_w8_plain = 0: the 128 x 256 tile with LDS-staged weights of rounds 1-5)
-    // (the same pipeline with four waves - 192 x 128 tile, two workgroups per CU - measured 1.3 % slower on the node products
-    // and 2.3 % on the heads; a 128 x 256 four-wave tile spills 36-46 registers)
-    // One such workgroup per CU: with few, long tiles the last round matters.  A launch of fewer than four rounds whose last
-    // round would fill under 30 % of the chip (25 000 rows: 131 x 2 = 262 workgroups on 256 CUs) keeps the 128 x 256 tile,
-    // two workgroups per CU (392 on 512 slots).
-    const int ncu = num_cus > 0 ? num_cus : 256;
-    const long long wg8 = (long long)((M + 191) / 192) * (N / 256 > 0 ? N / 256 : 1);
-    const bool ragged = wg8 < 4ll * ncu && wg8 % ncu != 0 && wg8 % ncu < (3 * ncu) / 10 && wg8 > ncu;
-    // (256-row tiles, MI = 4 - every weight fragment reused by 128 rows - measured: no gain, 1672-1676 against 1670-1673 ms)
-    // adf_tune::gemm_rows4 bit 0: the same products as 96 x 256 tiles of four waves, two workgroups per CU (kernel comment:
-    // NWM = 1).  Twice the slots, tiles half as long: the same rule over 2 x ncu slots (25 000 rows: N = 512 gives 261 x 2 = 522
-    // workgroups on 512 slots, a last round of 10 - the 128 x 256 tile as before; N = 256 gives 261, one round - the new tile).
-    const long long wg4 = (long long)((M + 95) / 96) * (N / 256 > 0 ? N / 256 : 1), slots4 = 2ll * ncu;
-    const bool ragged4 = wg4 < 4 * slots4 && wg4 % slots4 != 0 && wg4 % slots4 < (3 * slots4) / 10 && wg4 > slots4;
-    if ((tune.gemm_rows4 & 1) && tune.gemm_w8_plain && W->frag && N % 256 == 0 && (K / HK) % 2 == 0 && mi == 2 && !ragged4) {
-        const int tn4 = N / 256, tmw4 = ((M + 95) / 96 + 7) / 8 * 8;
-        dim3 g4((unsigned)(tmw4 * tn4));
-        if (act_ssilu)
-            hipLaunchKernelGGL((adf_gemm_f16x3_kernel<1, 3, 2, 0, true, 4, 1>), g4, dim3(256), 0, s, A, lda, (const _Float16*)W->frag,
-                               (const _Float16*)nullptr, W->inv_scale, bias, C, ldc, M, N, K, tn4, ep);
-        else
-            hipLaunchKernelGGL((adf_gemm_f16x3_kernel<0, 3, 2, 0, true, 4, 1>), g4, dim3(256), 0, s, A, lda, (const _Float16*)W->frag,
-                               (const _Float16*)nullptr, W->inv_scale, bias, C, ldc, M, N, K, tn4, ep);
-        ADF_HIP_CHECK(hipGetLastError());
-        return ADF_OK;
-    }
-    if (!(tune.gemm_rows4 & 1) && tune.gemm_w8_plain && W->frag && N % 256 == 0 && (K / HK) % 2 == 0 && mi == 2 && !ragged) {
-        const int tn8 = N / 256, tmw8 = ((M + 191) / 192 + 7) / 8 * 8;
-        dim3 g8((unsigned)(tmw8 * tn8));
-        if (act_ssilu)
-            hipLaunchKernelGGL((adf_gemm_f16x3_kernel<1, 3, 2, 0, true, 4>), g8, dim3(512), 0, s, A, lda, (const _Float16*)W->frag,
-                               (const _Float16*)nullptr, W->inv_scale, bias, C, ldc, M, N, K, tn8, ep);
-        else
-            hipLaunchKernelGGL((adf_gemm_f16x3_kernel<0, 3, 2, 0, true, 4>), g8, dim3(512), 0, s, A, lda, (const _Float16*)W->frag,
-                               (const _Float16*)nullptr, W->inv_scale, bias, C, ldc, M, N, K, tn8, ep);
-        ADF_HIP_CHECK(hipGetLastError());
-        return ADF_OK;
-    }
-#define LAUNCH16(ACT_, MI_)                                                                                  \
-    hipLaunchKernelGGL((adf_gemm_f16x3_kernel<ACT_, MI_, 4, 0>), grid, dim3(256), 0, s, A, lda,              \
-                       (const _Float16*)W->hi, (const _Float16*)W->lo, W->inv_scale, bias, C, ldc, M, N, K, \
-                       tiles_n, ep)
-    if (mi == 4) { if (act_ssilu) LAUNCH16(1, 4); else LAUNCH16(0, 4); }
-    else { if (act_ssilu) LAUNCH16(1, 2); else LAUNCH16(0, 2); }
-#undef LAUNCH16
-    ADF_HIP_CHECK(hipGetLastError());
-    return ADF_OK;
+    // With few, long tiles the last round matters.  A streamed launch of more than one and fewer than four rounds over the
+    // chip's 2 x num_cus slots whose last round would fill under 30 % of them runs LDS-staged, whose 128-row tiles leave
+    // fewer workgroups (25 000 rows x 512 columns: 261 x 2 = 522 streamed workgroups on 512 slots, a last round of 10,
+    // against 392 LDS-staged ones in one round).
+    const g16_tile ts = g16_tile_of(0, true);
+    const long long wg = (long long)((M + ts.ROWS - 1) / ts.ROWS) * (N / ts.TN > 0 ? N / ts.TN : 1);
+    const long long slots = 2ll * (num_cus > 0 ? num_cus : 256);
+    const bool ragged4 = wg < 4 * slots && wg % slots != 0 && wg % slots < (3 * slots) / 10 && wg > slots;
+    return launch_f16x3(can_stream(tune, W, 0, N, K) && !ragged4, act_ssilu, 0, A, lda, W, bias, C, ldc, M, N, K, ep, s);
 }
 
 // ||W v||_xyz of a [M,3,K] vector field -> nrm [M, N]  (EPI 4; N % 4 == 0)
@@ -979,107 +902,22 @@ int32_t adf_launch_gemm16_vecnorm(const float* A, int lda, const adf_w16* W, flo
     adf_epi ep = {};
     ep.cat = nrm;
     ADF_TRY(lift_mags(A, lda, K, nullptr, 0, 3ll * M, lf, premag, &ep.rmag, s));
-    const int tn = (N + 127) / 128, tm8 = ((M + 63) / 64 + 7) / 8 * 8;
-    if ((tune.gemm_rows4 & 1) && tune.gemm_w8 && W->frag && N % 256 == 0 && (K / HK) % 2 == 0) {   // four waves, 32 atoms x 256 columns
-        const int tm4 = ((M + 31) / 32 + 7) / 8 * 8;
-        hipLaunchKernelGGL((adf_gemm_f16x3_kernel<0, 3, 2, 4, true, 4, 1>), dim3((unsigned)(tm4 * (N / 256))), dim3(256), 0, s, A, lda,
-                           (const _Float16*)W->frag, (const _Float16*)nullptr, W->inv_scale, (const float*)nullptr,
-                           (float*)nullptr, 0, M, N, K, N / 256, ep);
-        ADF_HIP_CHECK(hipGetLastError());
-        return ADF_OK;
-    }
-    if (tune.gemm_w8 && W->frag && N % 256 == 0 && (K / HK) % 2 == 0) {   // weights streamed as fragments, eight waves (see the kernel comment)
-        hipLaunchKernelGGL((adf_gemm_f16x3_kernel<0, 3, 2, 4, true, 4>), dim3((unsigned)(tm8 * (N / 256))), dim3(512), 0, s, A, lda,
-                           (const _Float16*)W->frag, (const _Float16*)nullptr, W->inv_scale, (const float*)nullptr,
-                           (float*)nullptr, 0, M, N, K, N / 256, ep);
-        ADF_HIP_CHECK(hipGetLastError());
-        return ADF_OK;
-    }
-    hipLaunchKernelGGL((adf_gemm_f16x3_kernel<0, 3, 2, 4>), dim3((unsigned)(tm8 * tn)), dim3(256), 0, s, A, lda,
-                       (const _Float16*)W->hi, (const _Float16*)W->lo, W->inv_scale, (const float*)nullptr,
-                       (float*)nullptr, 0, M, N, K, tn, ep);
-    ADF_HIP_CHECK(hipGetLastError());
-    return ADF_OK;
+    return launch_f16x3(can_stream(tune, W, 4, N, K), 0, 4, A, lda, W, nullptr, nullptr, 0, M, N, K, ep, s);
 }
 
-// 3H-wide layer with row-permuted weights and a fused consumer epilogue (EPI 1 or 2, see kernel comment)
+// Layer with row-permuted weights and a fused consumer epilogue (see the kernel comment): EPI 1 / 2, 3H wide, or EPI 3,
+// vec_proj: A = vec [N,3,H], weights [2H, K] permuted in (v1, v2) pairs, M = atoms
 int32_t adf_launch_gemm16_fused(const float* A, int lda, const adf_w16* W, int M, int H, int K, int epi,
                                 const adf_epi* ep_in, hipStream_t s, const adf_tune& tune, const adf_lift* lf) {
-    adf_epi epv = *ep_in;
-    const adf_epi* ep = &epv;
+    adf_epi ep = *ep_in;
     if (M <= 0) return ADF_OK;
     if (K % HK != 0 || (lda & 3) || H % 64 != 0 || (epi != 3 && !W->bias_perm)) {
         adf_set_error("gemm16_fused: bad shape");
         return ADF_EINVAL;
     }
-    ADF_TRY(check_a_span(epi == 3 ? 3ll * M : (long long)M, lda));
-    ADF_TRY(lift_mags(A, lda, K, nullptr, 0, epi == 3 ? 3ll * M : (long long)M, lf, ep_in->rmag, &epv.rmag, s, ep_in->m_dev,
-                      epi == 3 ? 3 : 1));
-    const int N = 3 * H, TM = 128, TN = 192;
-    const int tiles_n = N / TN;  // H % 64 == 0
-    const int tiles_m = (M + TM - 1) / TM;
-    const int tiles_m8 = (tiles_m + 7) / 8 * 8;
-    dim3 grid((unsigned)(tiles_m8 * tiles_n));
-    if (epi == 3) {  // vec_proj: A = vec [N,3,H], weights [2H, K] permuted in (v1, v2) pairs; M = atoms
-        const int tn = 2 * H / 128, tm8 = ((M + 63) / 64 + 7) / 8 * 8;
-        // adf_tune::gemm_wreg = 0: weights staged through LDS as in rounds 1-5; gemm_w8 = 0: four waves per workgroup (128
-        // columns) instead of eight (256) (four waves, two workgroups per CU, same pipeline: node products 1748 ms per pass
-        // against 1679)
-        // gemm_rows4 bit 0: the eight-wave form's tile halved along M - four waves, 32 atoms x 256 columns, two workgroups per CU
-        if ((tune.gemm_rows4 & 1) && tune.gemm_wreg && W->frag && tune.gemm_w8 && (2 * H) % 256 == 0 && (K / HK) % 2 == 0)
-            hipLaunchKernelGGL((adf_gemm_f16x3_kernel<0, 3, 2, 3, true, 4, 1>), dim3((unsigned)(((M + 31) / 32 + 7) / 8 * 8 * (2 * H / 256))),
-                               dim3(256), 0, s, A, lda, (const _Float16*)W->frag, (const _Float16*)nullptr, W->inv_scale,
-                               (const float*)nullptr, (float*)nullptr, 0, M, 2 * H, K, 2 * H / 256, *ep);
-        else if (tune.gemm_wreg && W->frag && tune.gemm_w8 && (2 * H) % 256 == 0 && (K / HK) % 2 == 0)
-            hipLaunchKernelGGL((adf_gemm_f16x3_kernel<0, 3, 2, 3, true, 4>), dim3((unsigned)(tm8 * (2 * H / 256))), dim3(512), 0, s,
-                               A, lda, (const _Float16*)W->frag, (const _Float16*)nullptr, W->inv_scale, (const float*)nullptr,
-                               (float*)nullptr, 0, M, 2 * H, K, 2 * H / 256, *ep);
-        else
-        hipLaunchKernelGGL((adf_gemm_f16x3_kernel<0, 3, 2, 3>), dim3((unsigned)(tm8 * tn)), dim3(256), 0, s, A, lda,
-                           (const _Float16*)W->hi, (const _Float16*)W->lo, W->inv_scale, (const float*)nullptr,
-                           (float*)nullptr, 0, M, 2 * H, K, tn, *ep);
-        ADF_HIP_CHECK(hipGetLastError());
-        return ADF_OK;
-    }
-    const int wf = tune.gemm_wr_fused;   // 0 = LDS-staged weights (rounds 1-5), 2 / 4 = streamed fragments with 4 / 8 waves
-    // (measured: 4 waves 1656 ms of node products per pass, LDS-staged weights 1702, 8 waves 1741 - the record / gating
-    // epilogues are HBM-heavy and want the CU's second workgroup beside them)
-    // gemm_rows4 bit 1 (with the default wf = 2 only): four waves as 1(M) x 4(N), 64 x 384 tile - the per-wave stream of wf = 4
-    // at two workgroups per CU; a row panel is read and converted by N / 384 column tiles instead of N / 192
-    // (Measured and dropped: 32 x 384 tiles, MI = 1 - 48 accumulators, a fragment ring of two sets, 145 / 156 VGPRs, three
-    // workgroups per CU.  Same sites; x_proj.2 1339 -> 1615 us per launch, xvec_proj.2 1194 -> 1473, node products + 77 ms per pass
-    // each.  Every weight fragment is then requested once per 32 rows: 76 M more L2 requests of 128 B per launch, 9.8 GB, and
-    // 0.28 ms more - the L2s' full rate.  These two kernels pay for their L2 requests; profiles/NOTES.md, "32 x 384 tiles".)
-    if ((tune.gemm_rows4 & 2) && wf == 2 && W->frag && (K / HK) % 2 == 0 && N % 384 == 0) {
-        dim3 g4((unsigned)(((M + 63) / 64 + 7) / 8 * 8 * (N / 384)));
-        if (epi == 1)
-            hipLaunchKernelGGL((adf_gemm_f16x3_kernel<0, 2, 3, 1, true, 4, 1>), g4, dim3(256), 0, s, A, lda, (const _Float16*)W->frag,
-                               (const _Float16*)nullptr, W->inv_scale, W->bias_perm, (float*)nullptr, 0, M, N, K, N / 384, *ep);
-        else
-            hipLaunchKernelGGL((adf_gemm_f16x3_kernel<0, 2, 3, 2, true, 4, 1>), g4, dim3(256), 0, s, A, lda, (const _Float16*)W->frag,
-                               (const _Float16*)nullptr, W->inv_scale, W->bias_perm, (float*)nullptr, 0, M, N, K, N / 384, *ep);
-        ADF_HIP_CHECK(hipGetLastError());
-        return ADF_OK;
-    }
-    if (wf && W->frag && (K / HK) % 2 == 0 && (wf == 2 || N % 384 == 0)) {
-        const int tnw = wf == 4 ? N / 384 : tiles_n;
-        dim3 gw((unsigned)(tiles_m8 * tnw));
-#define LAUNCHWF(EPI_, NWN_)                                                                                                  \
-        hipLaunchKernelGGL((adf_gemm_f16x3_kernel<0, 2, 3, EPI_, true, NWN_>), gw, dim3(128 * NWN_), 0, s, A, lda,            \
-                           (const _Float16*)W->frag, (const _Float16*)nullptr, W->inv_scale, W->bias_perm, (float*)nullptr, 0, \
-                           M, N, K, tnw, *ep)
-        if (epi == 1) { if (wf == 4) LAUNCHWF(1, 4); else LAUNCHWF(1, 2); }
-        else { if (wf == 4) LAUNCHWF(2, 4); else LAUNCHWF(2, 2); }
-#undef LAUNCHWF
-        ADF_HIP_CHECK(hipGetLastError());
-        return ADF_OK;
-    }
-    if (epi == 1)
-        hipLaunchKernelGGL((adf_gemm_f16x3_kernel<0, 2, 3, 1>), grid, dim3(256), 0, s, A, lda, (const _Float16*)W->hi,
-                           (const _Float16*)W->lo, W->inv_scale, W->bias_perm, (float*)nullptr, 0, M, N, K, tiles_n, *ep);
-    else
-        hipLaunchKernelGGL((adf_gemm_f16x3_kernel<0, 2, 3, 2>), grid, dim3(256), 0, s, A, lda, (const _Float16*)W->hi,
-                           (const _Float16*)W->lo, W->inv_scale, W->bias_perm, (float*)nullptr, 0, M, N, K, tiles_n, *ep);
-    ADF_HIP_CHECK(hipGetLastError());
-    return ADF_OK;
+    const int rows_per = epi == 3 ? 3 : 1;
+    ADF_TRY(check_a_span((long long)rows_per * M, lda));
+    ADF_TRY(lift_mags(A, lda, K, nullptr, 0, (long long)rows_per * M, lf, ep_in->rmag, &ep.rmag, s, ep_in->m_dev, rows_per));
+    const int N = (epi == 3 ? 2 : 3) * H;   // (H % 64 == 0: whole LDS-staged column tiles)
+    return launch_f16x3(can_stream(tune, W, epi, N, K), 0, epi, A, lda, W, epi == 3 ? nullptr : W->bias_perm, nullptr, 0, M, N, K, ep, s);
 }

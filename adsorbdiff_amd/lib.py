@@ -79,10 +79,8 @@ class EqV2Counters(C.Structure):
 class Tune(C.Structure):
     """adf_tune: the kernel-selection switches a handle holds (include/adsorbdiff_hip.h)."""
     _fields_ = [(name, C.c_int32) for name in (
-        "gemm16_mi", "gemm_w8_plain", "gemm_w8", "gemm_wreg", "gemm_wr_fused", "head_gate_fused", "lift_emit",
-        "graph_sys_csr", "train_gemm16", "wgrad_f32",
-        "eqv2_pw_mi", "eqv2_gemm_tile256", "eqv2_rotin_generic", "eqv2_rotout_generic",
-        "gemm_rows4")]
+        "gemm_stream", "head_gate_fused", "lift_emit", "graph_sys_csr", "train_gemm16", "wgrad_f32",
+        "eqv2_gemm_tile256", "eqv2_rotin_generic", "eqv2_rotout_generic")]
 
 
 class BatchDesc(C.Structure):

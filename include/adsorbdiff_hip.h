@@ -140,29 +140,22 @@ int32_t adf_painn_set_arithmetic(adf_painn_t h, int32_t exact_f32);
 int32_t adf_painn_set_incremental(adf_painn_t h, int32_t on);
 
 /* Kernel-selection switches.  Each chooses between kernels that compute the same thing (same K order per output element:
- * same bits); the non-default values select earlier variants kept for measurements.  adf_painn_create reads them from the
+ * same bits); the non-default values select the independent form a test compares the default against, or a path that some
+ * inputs run anyway.  adf_painn_create reads them from the
  * environment once and the handle keeps its own copy, so handles created under different environments coexist in one
  * process.  The stateless entries (adf_linear_forward, adf_op_*) share one copy read at their first use. */
 typedef struct adf_tune {
-    int32_t gemm16_mi;        /* ADF_GEMM16_MI: 4 = 256-row tiles of the LDS-staged product, anything else 2 (default) */
-    int32_t gemm_w8_plain;    /* ADF_GEMM_W8_PLAIN: 0 = plain products keep the 128 x 256 LDS-staged tile, else 1 (default) */
-    int32_t gemm_w8;          /* ADF_GEMM_W8: 0 = vec_proj / vector-norm products with four waves, else 1 (eight, default) */
-    int32_t gemm_wreg;        /* ADF_GEMM_WREG: 0 = vec_proj stages its weights through LDS, else 1 (default) */
-    int32_t gemm_wr_fused;    /* ADF_GEMM_WR_FUSED: 0 = LDS-staged weights, 4 = streamed with eight waves, anything else 2 (default) */
-    int32_t head_gate_fused;  /* ADF_HEAD_GATE_FUSED: 0 = the heads' gate in a kernel of its own, else 1 (default) */
+    int32_t gemm_stream;      /* ADF_GEMM_STREAM: test hook.  0 = every f16x3 node product runs the LDS-staged form, the reference the
+                               * bit-identity tests compare against; else 1 (default): the streamed form wherever a shape allows it */
+    int32_t head_gate_fused; /* ADF_HEAD_GATE_FUSED: 0 = the heads' gate in a kernel of its own, else 1 (default) */
     int32_t lift_emit;        /* ADF_LIFT_EMIT: 0 = x_proj's row magnitudes are measured, else 1 (handed on by the producers) */
     int32_t graph_sys_csr;    /* ADF_GRAPH_SYS_CSR: 0 = global-memory count / fill / sort only, else 1 (default) */
     int32_t train_gemm16;     /* ADF_TRAIN_GEMM: "f32" = 0, the training products in exact f32, else 1 (stateless entries only) */
     int32_t wgrad_f32;        /* ADF_WGRAD: "f32" = 1, weight gradients in exact f32, else 0 (stateless entries only) */
     /* EquiformerV2 (adf_eqv2_create keeps the same copy) */
-    int32_t eqv2_pw_mi;          /* ADF_EQV2_PW_MI: 3 = 192-row tiles of the streamed-weights product, anything else 4 (256) */
     int32_t eqv2_gemm_tile256;   /* ADF_EQV2_GEMM_TILE: 128 = 0, the 128-row tile for every shape, else 1 (256 rows from 8192 on) */
     int32_t eqv2_rotin_generic;  /* ADF_EQV2_ROTIN_GENERIC set (any value): 1, the run-time-mmax rotate-in kernel, else 0 */
     int32_t eqv2_rotout_generic; /* ADF_EQV2_ROTOUT_GENERIC set (any value): 1, the run-time-mmax rotate-out kernel, else 0 */
-    /* PaiNN again (appended: the fields above keep their offsets) */
-    int32_t gemm_rows4;       /* ADF_GEMM_ROWS4: streamed-weights products as four waves 1(M) x 4(N), two workgroups per CU. Bit 0 =
-                               * plain / vec_proj / vector-norm products (96 x 256 tile), bit 1 = the fused x_proj.2 / xvec_proj.2
-                               * products (64 x 384, with gemm_wr_fused = 2 only); 0 = the eight- / four-wave forms above; default 3 */
 } adf_tune;
 /* Test hook: the selection the handle holds (the variants give the same bits, so outputs cannot show it). */
 int32_t adf_painn_get_tune(adf_painn_t h, adf_tune* out);

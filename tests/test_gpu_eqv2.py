@@ -250,23 +250,23 @@ def test_eqv2_attention_logits_four_heads_per_wave_equal_the_one_head_kernel(mon
 _TUNE_REF = {}
 
 
-@pytest.mark.parametrize("var,value", [("ADF_EQV2_PW_MI", "3"), ("ADF_EQV2_GEMM_TILE", "128"), ("ADF_EQV2_ROTIN_GENERIC", "1"),
+@pytest.mark.parametrize("var,value", [("ADF_EQV2_GEMM_TILE", "128"), ("ADF_EQV2_ROTIN_GENERIC", "1"),
                                        ("ADF_EQV2_ROTOUT_GENERIC", "1")])
 def test_eqv2_kernel_selection_switches_are_read_per_engine(monkeypatch, var, value):
-    """The four launcher switches that were process-wide statics are fields of the handle now: a fresh engine created under the
+    """The three launcher switches that were process-wide statics are fields of the handle now: a fresh engine created under the
     variable, in the process in which the default engine has already run, takes the other kernel and gives the default
     engine's outputs and node embeddings after every block, within the 2e-6 this file grants two evaluation orders of the
     same fp32 arithmetic.  The shapes (lmax 6, mmax 2, 32 sphere / 64 hidden channels, 3 x 200 atoms = 12 000 edges) reach all
-    four launchers: the first convolution's products are 448+ / 768 / 640 wide with K = 448 / 384 / 320 (eq_launch_gemm16pw;
-    640 = two 256-column tiles + a 128-column remainder, the part ADF_EQV2_PW_MI=3 launches apart); the second convolution's
+    the launchers: the first convolution's products are 448+ / 768 / 640 wide with K = 448 / 384 / 320 (eq_launch_gemm16pw;
+    640 = two 256-column tiles + a 128-column remainder, the kernel's half layout); the second convolution's
     orders m >= 1 have 24 000 rows and 256+ columns (eq_launch_gemm16 takes its 256-row tile from 8192 rows on;
     ADF_EQV2_GEMM_TILE=128: never); mmax = 2 is the compile-time fast path of both rotations that the GENERIC variables
     leave."""
     m = make_model(6, 2, C=32, hidden=64, heads=2, alpha=16, value=16, ffn=32, ec=32, layers=2, cutoff=12.0).to(DEV)
     b = safe_batch(3, 196, seed=17).to(DEV)
-    for v in ("ADF_EQV2_PW_MI", "ADF_EQV2_GEMM_TILE", "ADF_EQV2_ROTIN_GENERIC", "ADF_EQV2_ROTOUT_GENERIC"):
+    for v in ("ADF_EQV2_GEMM_TILE", "ADF_EQV2_ROTIN_GENERIC", "ADF_EQV2_ROTOUT_GENERIC"):
         monkeypatch.delenv(v, raising=False)
-    if not _TUNE_REF:   # the default engine's outputs, computed once for the four cases
+    if not _TUNE_REF:   # the default engine's outputs, computed once for the three cases
         f1, f2, xb = m.engine().forward(b, return_blocks=True)
         _TUNE_REF.update(f1=f1.clone(), f2=f2.clone(), xb=xb.clone())
         m._engine.close()

@@ -1,12 +1,13 @@
-"""ADF_GEMM_ROWS4: the streamed-weights node products as four waves laid out 1(M) x 4(N), two workgroups per CU - 96 x 256
-tiles for the plain, vec_proj and vector-norm products (bit 0; 32 atoms x 3 components for the latter two), 64 x 384 tiles for
-the fused x_proj.2 / xvec_proj.2 products (bit 1) - against the eight- / four-wave forms of ADF_GEMM_ROWS4=0.  The new tiles
-keep the products of every output element, their order along K, the lifts and the epilogues' arithmetic, so nothing here has a
-tolerance: every comparison is torch.equal between two engines of one model in one process, each created under its own
-environment (the switch is read when the handle is created, tests/test_gpu_tune.py).
+"""The two forms of the f16x3 node products (csrc/gemm16.hip): the default, weights streamed as fragments by four waves laid
+out 1(M) x 4(N) - 96 x 256 tiles for the plain, vec_proj and vector-norm products (32 atoms x 3 components for the latter
+two), 64 x 384 tiles for the fused x_proj.2 / xvec_proj.2 products - against the LDS-staged 2(M) x 2(N) reference form that
+ADF_GEMM_STREAM=0 runs everywhere.  Both forms keep the products of every output element, their order along K, the lifts and
+the epilogues' arithmetic, so nothing here has a tolerance: every comparison is torch.equal between two engines of one model
+in one process, each created under its own environment (the switch is read when the handle is created,
+tests/test_gpu_tune.py).
 
 Model: H = 256, 2 layers, R = 128 - every layer product is a multiple of 256 (resp. 384) wide with an even number of K tiles
-and takes the new shape; the heads' products are 128 wide there and keep the LDS-staged kernel, so one case runs H = 512,
+and streams by default; the heads' products are 128 wide there and run LDS-staged either way, so one case runs H = 512,
 1 layer, where they are 256 wide.  Atom counts: 31 (one ragged tile), 32 (exactly one), 33 (a full tile + a one-atom tile), 97
 (fused products: one 64-row tile + a ragged one; plain: a full 96-row tile + one row), 210 (the shape of test_gpu_tune.py),
 290 (ten 32-atom tiles: the XCD tile map's second group of eight runs with six padding tiles that return at m0 >= M)."""
@@ -32,7 +33,11 @@ ATOMS = (31, 32, 33, 97, 210, 290)
 @contextlib.contextmanager
 def _env(**kv):
     old = {k: os.environ.get(k) for k in kv}
-    os.environ.update(kv)
+    for k, v in kv.items():   # (None: the variable is absent)
+        if v is None:
+            os.environ.pop(k, None)
+        else:
+            os.environ[k] = v
     try:
         yield
     finally:
@@ -53,20 +58,20 @@ def _batch(n):
 
 
 def _pair(hp, seed, **extra_env):
-    """Two engines of one model: ADF_GEMM_ROWS4 = 0 and = 3."""
+    """Two engines of one model: ADF_GEMM_STREAM = 0 (LDS-staged everywhere) and the default."""
     torch.manual_seed(seed)
     sd = {k: v.clone() for k, v in PaiNN(None, 50, 1, scale_file=SCALES, so3_denoising=True, **hp).state_dict().items()}
     models = []
-    for rows4 in ("0", "3"):
-        with _env(ADF_GEMM_ROWS4=rows4, **extra_env):
+    for stream in (0, 1):
+        with _env(ADF_GEMM_STREAM=None if stream else "0", **extra_env):
             m = PaiNN(None, 50, 1, scale_file=SCALES, so3_denoising=True, **hp)
             m.load_state_dict(sd)
             m = m.to(DEV).eval()
-            assert m.engine().get_tune()["gemm_rows4"] == int(rows4)
+            assert m.engine().get_tune()["gemm_stream"] == stream
         models.append(m)
-    # every other switch is what it is without the variable: the older forms are what the first engine runs
+    # every other switch is what it is without the variable
     ta, tb = (m.engine().get_tune() for m in models)
-    assert {k: v for k, v in ta.items() if k != "gemm_rows4"} == {k: v for k, v in tb.items() if k != "gemm_rows4"}
+    assert {k: v for k, v in ta.items() if k != "gemm_stream"} == {k: v for k, v in tb.items() if k != "gemm_stream"}
     return models
 
 
@@ -148,8 +153,8 @@ def test_sampler_with_listed_rows_is_bit_identical():
         out = den.run()
         assert den.steps_applied == 3
         c = m.engine().counters()
-        print("rows4 %d: rows %d of %d in %d launches" % (m.engine().get_tune()["gemm_rows4"], c.inc_rows, c.inc_rows_full,
-                                                           c.inc_msg_launches))
+        print("stream %d: rows %d of %d in %d launches" % (m.engine().get_tune()["gemm_stream"], c.inc_rows, c.inc_rows_full,
+                                                            c.inc_msg_launches))
         assert 0 < c.inc_rows < c.inc_rows_full, "no layer took the listed-rows form"
         sites.append(out.pos.clone())
     assert bool(torch.isfinite(sites[0]).all())

@@ -10,8 +10,8 @@ forward to, and every single row's difference by 1e-4 of the largest row norm, t
 puts a row off by the order of its own magnitude.
 
 Model: H = 256, 2 layers, R = 128 (layer 0 takes the vec_is_zero branch, layer 1 the full one).  Atom counts as for the tile
-tests: 31 (one ragged 32-row block), 33 and 65 (a block / a 64-row tile + one row), 290 (padding tiles).  The three forms
-(ADF_GEMM_WR_FUSED = 0 LDS-staged weights, 2 default, 4 eight waves) must still give the same bits."""
+tests: 31 (one ragged 32-row block), 33 and 65 (a block / a 64-row tile + one row), 290 (padding tiles).  The two forms
+(ADF_GEMM_STREAM = 0 LDS-staged weights, and the default) must still give the same bits."""
 import contextlib
 import os
 
@@ -54,12 +54,11 @@ def _batch(n):
 
 @pytest.fixture(scope="module")
 def models():
-    """One model as four engines: exact f32, and the f16x3 path with x_proj.2 in each of its three forms."""
+    """One model as three engines: exact f32, and the f16x3 path with x_proj.2 in each of its two forms."""
     torch.manual_seed(41)
     sd = {k: v.clone() for k, v in PaiNN(None, 50, 1, scale_file=SCALES, so3_denoising=True, **HP).state_dict().items()}
     out = {}
-    for name, env in (("f32", dict(ADF_GEMM="f32")), ("wf0", dict(ADF_GEMM_WR_FUSED="0")), ("wf2", dict(ADF_GEMM_WR_FUSED="2")),
-                      ("wf4", dict(ADF_GEMM_WR_FUSED="4"))):
+    for name, env in (("f32", dict(ADF_GEMM="f32")), ("lds", dict(ADF_GEMM_STREAM="0")), ("default", dict())):
         with _env(**env):
             m = PaiNN(None, 50, 1, scale_file=SCALES, so3_denoising=True, **HP)
             m.load_state_dict(sd)
@@ -67,7 +66,7 @@ def models():
             eng = m.engine()
             assert eng.exact_f32 == (name == "f32")
             if name != "f32":
-                assert eng.get_tune()["gemm_wr_fused"] == int(name[2])
+                assert eng.get_tune()["gemm_stream"] == (name == "default")
         out[name] = m
     return out
 
@@ -90,12 +89,12 @@ def test_message_layers_match_exact_f32_row_by_row(models, n):
     x0 = m.atom_emb.embeddings.weight.detach()[b.atomic_numbers.long() - 1].contiguous()
     vec0 = torch.randn(n, 3, HP["hidden_channels"], generator=torch.Generator().manual_seed(n)).to(DEV)
     ref = _message_rows(m, b, x0, vec0)
-    got = {k: _message_rows(models[k], b, x0, vec0) for k in ("wf0", "wf2", "wf4")}
-    for k, (r, a) in enumerate(zip(ref, got["wf2"])):
+    got = {k: _message_rows(models[k], b, x0, vec0) for k in ("lds", "default")}
+    for k, (r, a) in enumerate(zip(ref, got["default"])):
         assert bool(torch.isfinite(r).all()) and float(r.abs().max()) > 0, (n, k)
         e = rel_err(a, r)
         rown = (a.double() - r.double()).reshape(n, -1).norm(dim=1)
         worst = float(rown.max() / r.double().reshape(n, -1).norm(dim=1).max())
         print("n %d tensor %d: rel err %.2e, worst row %.2e" % (n, k, e, worst))
         assert e < 2e-5 and worst < 1e-4, (n, k)
-        assert torch.equal(a, got["wf0"][k]) and torch.equal(a, got["wf4"][k]), (n, k)
+        assert torch.equal(a, got["lds"][k]), (n, k)

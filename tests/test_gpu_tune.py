@@ -13,23 +13,20 @@ from tests.helpers import rel_err
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
-DEFAULTS = dict(gemm16_mi=2, gemm_w8_plain=1, gemm_w8=1, gemm_wreg=1, gemm_wr_fused=2, head_gate_fused=1, lift_emit=1,
-                graph_sys_csr=1)
+DEFAULTS = dict(gemm_stream=1, head_gate_fused=1, lift_emit=1, graph_sys_csr=1)
 # every PaiNN switch at its non-default value: environment variable, field, value
-SWITCHED = (("ADF_GEMM16_MI", "gemm16_mi", 4), ("ADF_GEMM_W8_PLAIN", "gemm_w8_plain", 0), ("ADF_GEMM_W8", "gemm_w8", 0),
-            ("ADF_GEMM_WREG", "gemm_wreg", 0), ("ADF_GEMM_WR_FUSED", "gemm_wr_fused", 0),
-            ("ADF_HEAD_GATE_FUSED", "head_gate_fused", 0), ("ADF_LIFT_EMIT", "lift_emit", 0),
-            ("ADF_GRAPH_SYS_CSR", "graph_sys_csr", 0))
+SWITCHED = (("ADF_GEMM_STREAM", "gemm_stream", 0), ("ADF_HEAD_GATE_FUSED", "head_gate_fused", 0),
+            ("ADF_LIFT_EMIT", "lift_emit", 0), ("ADF_GRAPH_SYS_CSR", "graph_sys_csr", 0))
 
 
 def test_selection_switches_belong_to_the_handle(monkeypatch):
     """Three engines of one model in one process: A under the default environment, B with every PaiNN switch at its
     non-default value, C after the variables are gone again.  Each handle holds the selection of the environment it was created
-    in (adf_painn_get_tune), whatever ran before it in the process.  210 rows: one full 192-row tile of the eight-wave kernels
+    in (adf_painn_get_tune), whatever ran before it in the process.  210 rows: two full 96-row tiles of the streamed kernels
     + 18 rows, two 128-row tiles of the LDS-staged ones (the second ragged).  At H = 256 the layer products are multiples of
     256 wide with an even number of K tiles - streamed fragments by default, LDS-staged weights when switched; the heads'
     128-wide products take the LDS-staged kernel either way.
-    B equals A bit for bit: the variants keep the products of every output element and their order along K (tile shapes and
+    B equals A bit for bit: the two forms keep the products of every output element and their order along K (tile shapes and
     the way the weights reach the registers differ), a row maximum is exact whether a producer emits it or a pass measures it,
     the separate gate kernel does the same single fp32 multiplication as the gate epilogue, and both CSR builds sort the same
     edges by the same key.  (The one-process-per-environment comparison on the parent library that was to confirm this
@@ -70,16 +67,6 @@ def test_selection_switches_belong_to_the_handle(monkeypatch):
     print("B against A: rel err", rel_err(b1.cpu(), a1.cpu()), rel_err(b2.cpu(), a2.cpu()))
     assert torch.equal(a1, b1) and torch.equal(a2, b2)
     del mb, mc
-
-
-def test_wr_fused_stray_value_is_the_default(monkeypatch):
-    """ADF_GEMM_WR_FUSED takes 0, 2 or 4; anything else is 2."""
-    m = PaiNN(None, 50, 1, hidden_channels=128, num_layers=1, num_rbf=128, max_neighbors=20, cutoff=6.0, so3_denoising=True).to(DEV)
-    for value, want in (("3", 2), ("4", 4), ("0", 0), ("-1", 2)):
-        monkeypatch.setenv("ADF_GEMM_WR_FUSED", value)
-        assert m.engine().get_tune()["gemm_wr_fused"] == want
-        m._engine.close()
-        m._engine = None
 
 
 def test_plain_product_into_an_output_that_is_not_16_byte_aligned():
