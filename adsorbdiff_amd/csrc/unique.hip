@@ -53,18 +53,43 @@ __device__ __forceinline__ float uq_wave_max(float v) {
     return v;
 }
 
+// R x + tau of a symmetry operation (T: R row-major, then tau), formed in double and rounded to float32 once
+__device__ __forceinline__ void uq_apply(const double (&T)[12], float& x, float& y, float& z) {
+    const double dx = x, dy = y, dz = z;
+    x = (float)(T[0] * dx + T[1] * dy + T[2] * dz + T[9]);
+    y = (float)(T[3] * dx + T[4] * dy + T[5] * dz + T[10]);
+    z = (float)(T[6] * dx + T[7] * dy + T[8] * dz + T[11]);
+}
+
 // max over the adsorbate atoms of site X of the least displacement to an adsorbate atom of site Y of the same element;
-// flip: the displacement is taken from Y's atom to X's (so that both directions evaluate the same vectors b - a)
+// flip: the displacement is taken from Y's atom to X's (so that both directions evaluate the same vectors b - a).
+// XF (the symmetry-aware entry): 1 - the atoms of X go through T first, 2 - the atoms of Y do; 0 - T is not read.
+__device__ const double UQ_NO_OP[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};   // never read (XF = 0)
+
+// the cell of site s (rows = lattice vectors) and its float32 explicit inverse
+__device__ __forceinline__ void uq_cell(const float* __restrict__ cell, int s, float (&c)[9], float (&inv)[9]) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) c[k] = cell[9 * (size_t)s + k];
+    const float m00 = c[4] * c[8] - c[5] * c[7], m01 = c[5] * c[6] - c[3] * c[8], m02 = c[3] * c[7] - c[4] * c[6];
+    const float r = 1.0f / (c[0] * m00 + c[1] * m01 + c[2] * m02);
+    inv[0] = m00 * r; inv[1] = (c[2] * c[7] - c[1] * c[8]) * r; inv[2] = (c[1] * c[5] - c[2] * c[4]) * r;
+    inv[3] = m01 * r; inv[4] = (c[0] * c[8] - c[2] * c[6]) * r; inv[5] = (c[2] * c[3] - c[0] * c[5]) * r;
+    inv[6] = m02 * r; inv[7] = (c[1] * c[6] - c[0] * c[7]) * r; inv[8] = (c[0] * c[4] - c[1] * c[3]) * r;
+}
+
+template <int XF>
 __device__ __forceinline__ float uq_one_sided(const float* __restrict__ pos, const int32_t* __restrict__ tags,
                                               const int32_t* __restrict__ Z, int x0, int y0, int n, bool flip,
-                                              const float (&c)[9], const float (&inv)[9], int lane, bool& nan) {
+                                              const float (&c)[9], const float (&inv)[9], int lane, bool& nan,
+                                              const double (&T)[12]) {
     float worst = 0.f;
     for (int k0 = 0; k0 < n; k0 += 64) {
         const int k = k0 + lane;
         const bool mine = k < n && tags[x0 + min(k, n - 1)] == 2;
         if (__ballot(mine) == 0ull) continue;           // a round of slab atoms
         const int ax = x0 + min(k, n - 1);
-        const float px = pos[3 * (size_t)ax], py = pos[3 * (size_t)ax + 1], pz = pos[3 * (size_t)ax + 2];
+        float px = pos[3 * (size_t)ax], py = pos[3 * (size_t)ax + 1], pz = pos[3 * (size_t)ax + 2];
+        if (XF == 1) uq_apply(T, px, py, pz);
         const int zx = Z[ax];
         float least = INFINITY;
         for (int m0 = 0; m0 < n; m0 += 64) {
@@ -72,7 +97,8 @@ __device__ __forceinline__ float uq_one_sided(const float* __restrict__ pos, con
             const int ay = y0 + min(m, n - 1);
             unsigned long long ads = __ballot(m < n && tags[ay] == 2);
             if (ads == 0ull) continue;
-            const float qx = pos[3 * (size_t)ay], qy = pos[3 * (size_t)ay + 1], qz = pos[3 * (size_t)ay + 2];
+            float qx = pos[3 * (size_t)ay], qy = pos[3 * (size_t)ay + 1], qz = pos[3 * (size_t)ay + 2];
+            if (XF == 2) uq_apply(T, qx, qy, qz);
             const int zy = Z[ay];
             while (ads != 0ull) {
                 const int l = __ffsll((long long)ads) - 1;
@@ -116,15 +142,7 @@ __global__ __launch_bounds__(UQ_THREADS) void uq_pair_kernel(
         bool differ = na != b1 - b0, nan = false;
         if (!differ && na > 0) {
             float c[9], inv[9];
-#pragma unroll
-            for (int k = 0; k < 9; ++k) c[k] = cell[9 * (size_t)sa + k];
-            {
-                const float m00 = c[4] * c[8] - c[5] * c[7], m01 = c[5] * c[6] - c[3] * c[8], m02 = c[3] * c[7] - c[4] * c[6];
-                const float r = 1.0f / (c[0] * m00 + c[1] * m01 + c[2] * m02);
-                inv[0] = m00 * r; inv[1] = (c[2] * c[7] - c[1] * c[8]) * r; inv[2] = (c[1] * c[5] - c[2] * c[4]) * r;
-                inv[3] = m01 * r; inv[4] = (c[0] * c[8] - c[2] * c[6]) * r; inv[5] = (c[2] * c[3] - c[0] * c[5]) * r;
-                inv[6] = m02 * r; inv[7] = (c[1] * c[6] - c[0] * c[7]) * r; inv[8] = (c[0] * c[4] - c[1] * c[3]) * r;
-            }
+            uq_cell(cell, sa, c, inv);
             // the ordered part: slab atoms, and the adsorbate atoms when the adsorbate is compared in order
             bool any_ads = false;
             for (int k = lane; k < na; k += 64) {
@@ -140,8 +158,8 @@ __global__ __launch_bounds__(UQ_THREADS) void uq_pair_kernel(
             }
             differ = __ballot(differ) != 0ull;
             if (!differ && permutation_invariant && __ballot(any_ads) != 0ull) {
-                d = fmaxf(d, uq_one_sided(pos, tags, Z, a0, b0, na, false, c, inv, lane, nan));
-                d = fmaxf(d, uq_one_sided(pos, tags, Z, b0, a0, na, true, c, inv, lane, nan));
+                d = fmaxf(d, uq_one_sided<0>(pos, tags, Z, a0, b0, na, false, c, inv, lane, nan, UQ_NO_OP));
+                d = fmaxf(d, uq_one_sided<0>(pos, tags, Z, b0, a0, na, true, c, inv, lane, nan, UQ_NO_OP));
             }
             d = uq_wave_max(d);
             nan = __ballot(nan) != 0ull;
@@ -153,6 +171,12 @@ __global__ __launch_bounds__(UQ_THREADS) void uq_pair_kernel(
             out[po + (long long)j * n + i] = d;
         }
     }
+}
+
+static int uq_pair_slots(int32_t num_sites, int32_t num_groups) {
+    const long long avg = (num_sites + num_groups - 1) / num_groups;
+    const long long blocks = (avg * avg + (UQ_THREADS / 64) - 1) / (UQ_THREADS / 64);
+    return (int)(blocks > 4096 ? 4096 : blocks < 1 ? 1 : blocks);
 }
 
 extern "C" int32_t adf_site_pair_distances(const float* pos, const float* cell, const int32_t* tags,
@@ -171,12 +195,161 @@ extern "C" int32_t adf_site_pair_distances(const float* pos, const float* cell, 
     }
     // waves per group: one per matrix entry of the average group (the lower triangle's leave at once), so that the common
     // group has a wave per pair; a larger group strides over its pairs, a smaller one leaves its spare waves at once
-    const long long avg = (num_sites + num_groups - 1) / num_groups;
-    const long long blocks = (avg * avg + (UQ_THREADS / 64) - 1) / (UQ_THREADS / 64);
-    const int slots = (int)(blocks > 4096 ? 4096 : blocks < 1 ? 1 : blocks);
+    const int slots = uq_pair_slots(num_sites, num_groups);
     hipLaunchKernelGGL(uq_pair_kernel, dim3(num_groups, slots), dim3(UQ_THREADS), 0, (hipStream_t)stream, pos, cell, tags,
                        atomic_numbers, atom_offset, group_offset, pair_offset, num_atoms, num_sites, (long long)out_len,
                        include_slab, permutation_invariant, out);
+    ADF_HIP_CHECK(hipGetLastError());
+    return ADF_OK;
+}
+
+// ---- the symmetry-aware distance: d_sym(i, j) = min over the operations g of the group's slab of
+// d(g . site i, site j), i the earlier site.  One wave per pair, the operations one after the other; per operation the
+// adsorbate part first, and the slab part only while the operation can still win.  Operation 0 of every group is the
+// identity and is not applied, so a group with that one operation evaluates the expressions of uq_pair_kernel.
+__device__ __forceinline__ int uq_wave_min_int(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
+    return v;
+}
+
+__global__ __launch_bounds__(UQ_THREADS) void uq_pair_sym_kernel(
+    const float* __restrict__ pos, const float* __restrict__ cell, const int32_t* __restrict__ tags,
+    const int32_t* __restrict__ Z, const int32_t* __restrict__ atom_offset, const int32_t* __restrict__ group_offset,
+    const int64_t* __restrict__ pair_offset, const int32_t* __restrict__ op_offset, const double* __restrict__ rot,
+    const double* __restrict__ trans, const int32_t* __restrict__ perm, const int64_t* __restrict__ perm_offset,
+    int num_atoms, int num_sites, long long out_len, int num_ops, long long perm_len, int include_slab,
+    int permutation_invariant, float* __restrict__ out, int32_t* __restrict__ best_op) {
+    const int g = blockIdx.x, lane = threadIdx.x & 63;
+    const int s0 = min(max(group_offset[g], 0), num_sites), s1 = min(max(group_offset[g + 1], s0), num_sites);
+    const long long n = s1 - s0;
+    const long long po = pair_offset[g];
+    if (n <= 0 || po < 0 || po + n * n > out_len) return;
+    // the group's operations: [o0, o0 + nops), each with a permutation of nb slab atoms
+    const int o0 = op_offset[g];
+    int nops = op_offset[g + 1] - o0;
+    const long long pp = perm_offset[g];
+    long long nb = -1;
+    if (o0 >= 0 && nops > 0 && o0 + (long long)nops <= num_ops && pp >= 0 && perm_offset[g + 1] <= perm_len &&
+        perm_offset[g + 1] >= pp && (perm_offset[g + 1] - pp) % nops == 0)
+        nb = (perm_offset[g + 1] - pp) / nops;
+    const long long wave0 = (long long)blockIdx.y * (UQ_THREADS / 64) + (threadIdx.x >> 6);
+    const long long stride = (long long)gridDim.y * (UQ_THREADS / 64);
+    for (long long p = wave0; p < n * n; p += stride) {
+        const int i = (int)(p / n), j = (int)(p - (long long)i * n);
+        if (i > j) continue;
+        if (i == j) {
+            if (lane == 0) { out[po + p] = 0.f; best_op[po + p] = 0; }
+            continue;
+        }
+        const int sa = s0 + i, sb = s0 + j;
+        const int a0 = min(max(atom_offset[sa], 0), num_atoms), a1 = min(max(atom_offset[sa + 1], a0), num_atoms);
+        const int b0 = min(max(atom_offset[sb], 0), num_atoms), b1 = min(max(atom_offset[sb + 1], b0), num_atoms);
+        const int na = a1 - a0;
+        float best = INFINITY;
+        int bop = 0;
+        bool differ = na != b1 - b0, nan = false;
+        if (!differ && na > 0) {
+            float c[9], inv[9];
+            uq_cell(cell, sa, c, inv);
+            // the layout: equal tags and elements, the adsorbate one contiguous block [q0, q0 + nads)
+            int q0 = INT_MAX, q1 = -1, cnt = 0;
+            for (int k = lane; k < na; k += 64) {
+                const int ta = tags[a0 + k];
+                if (ta != tags[b0 + k] || Z[a0 + k] != Z[b0 + k]) differ = true;
+                if (ta == 2) { q0 = min(q0, k); q1 = max(q1, k); ++cnt; }
+            }
+            differ = __ballot(differ) != 0ull;
+            q0 = uq_wave_min_int(q0);
+            q1 = -uq_wave_min_int(-q1);
+            int nads = cnt;
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) nads += __shfl_xor(nads, o, 64);
+            if (nads == 0) q0 = na;
+            const int nslab = na - nads;
+            if ((nads > 0 && q1 - q0 + 1 != nads) || nslab != nb) differ = true;
+            for (int op = 0; op < nops && !differ; ++op) {
+                double T[12];
+#pragma unroll
+                for (int k = 0; k < 9; ++k) T[k] = rot[9 * (size_t)(o0 + op) + k];
+#pragma unroll
+                for (int k = 0; k < 3; ++k) T[9 + k] = trans[3 * (size_t)(o0 + op) + k];
+                float d = 0.f;
+                bool bad = false;
+                if (nads > 0 && permutation_invariant) {
+                    if (op == 0) {
+                        d = fmaxf(d, uq_one_sided<0>(pos, tags, Z, a0, b0, na, false, c, inv, lane, bad, T));
+                        d = fmaxf(d, uq_one_sided<0>(pos, tags, Z, b0, a0, na, true, c, inv, lane, bad, T));
+                    } else {
+                        d = fmaxf(d, uq_one_sided<1>(pos, tags, Z, a0, b0, na, false, c, inv, lane, bad, T));
+                        d = fmaxf(d, uq_one_sided<2>(pos, tags, Z, b0, a0, na, true, c, inv, lane, bad, T));
+                    }
+                } else if (nads > 0) {
+                    for (int k = q0 + lane; k < q0 + nads; k += 64) {
+                        const size_t ra = 3 * (size_t)(a0 + k), rb = 3 * (size_t)(b0 + k);
+                        float x = pos[ra], y = pos[ra + 1], z = pos[ra + 2];
+                        if (op != 0) uq_apply(T, x, y, z);
+                        const float v = uq_disp(pos[rb] - x, pos[rb + 1] - y, pos[rb + 2] - z, c, inv);
+                        if (v != v) bad = true;
+                        d = fmaxf(d, v);
+                    }
+                }
+                d = uq_wave_max(d);
+                if (__ballot(bad) != 0ull) { nan = true; continue; }
+                if (!(d < best)) continue;                  // the slab part can only raise d: this operation cannot win
+                if (include_slab) {
+                    const int32_t* pm = perm + pp + (long long)op * nb;
+                    for (int r = lane; r < nslab; r += 64) {
+                        const int t = op == 0 ? r : pm[r];
+                        if (t < 0 || t >= nslab) { bad = true; continue; }
+                        const size_t ra = 3 * (size_t)(a0 + (r < q0 ? r : r + nads)), rb = 3 * (size_t)(b0 + (t < q0 ? t : t + nads));
+                        float x = pos[ra], y = pos[ra + 1], z = pos[ra + 2];
+                        if (op != 0) uq_apply(T, x, y, z);
+                        const float v = uq_disp(pos[rb] - x, pos[rb + 1] - y, pos[rb + 2] - z, c, inv);
+                        if (v != v) bad = true;
+                        d = fmaxf(d, v);
+                    }
+                    d = uq_wave_max(d);
+                    if (__ballot(bad) != 0ull) { nan = true; continue; }
+                }
+                if (d < best) { best = d; bop = op; }
+            }
+        } else if (!differ) {
+            best = nb == 0 ? 0.f : INFINITY;               // two sites without atoms
+        }
+        if (nan) { best = NAN; bop = 0; }                   // a non-finite coordinate: the pair is within no tolerance
+        if (differ) { best = INFINITY; bop = 0; }
+        if (lane == 0) {
+            out[po + p] = best;
+            out[po + (long long)j * n + i] = best;
+            best_op[po + p] = bop;
+            best_op[po + (long long)j * n + i] = bop;
+        }
+    }
+}
+
+extern "C" int32_t adf_site_pair_distances_sym(const float* pos, const float* cell, const int32_t* tags,
+                                               const int32_t* atomic_numbers, const int32_t* atom_offset,
+                                               const int32_t* group_offset, const int64_t* pair_offset, int32_t num_atoms,
+                                               int32_t num_sites, int32_t num_groups, int64_t out_len, int32_t include_slab,
+                                               int32_t permutation_invariant, const int32_t* op_offset, const double* rot,
+                                               const double* trans, const int32_t* perm, const int64_t* perm_offset,
+                                               int32_t num_ops, int64_t perm_len, float* out, int32_t* best_op, void* stream) {
+    if (!pos || !cell || !tags || !atomic_numbers || !atom_offset || !group_offset || !pair_offset || !op_offset || !rot ||
+        !trans || !perm || !perm_offset || !out || !best_op) {
+        adf_set_error("site_pair_distances_sym: null argument");
+        return ADF_EINVAL;
+    }
+    if (num_atoms < 0 || num_sites <= 0 || num_groups <= 0 || num_groups > num_sites || out_len < num_sites || num_ops <= 0 ||
+        perm_len < 0) {
+        adf_set_error("site_pair_distances_sym: %d atoms, %d sites, %d groups, %lld output elements, %d operations, %lld "
+                      "permutation entries", num_atoms, num_sites, num_groups, (long long)out_len, num_ops, (long long)perm_len);
+        return ADF_EINVAL;
+    }
+    hipLaunchKernelGGL(uq_pair_sym_kernel, dim3(num_groups, uq_pair_slots(num_sites, num_groups)), dim3(UQ_THREADS), 0,
+                       (hipStream_t)stream, pos, cell, tags, atomic_numbers, atom_offset, group_offset, pair_offset, op_offset,
+                       rot, trans, perm, perm_offset, num_atoms, num_sites, (long long)out_len, num_ops, (long long)perm_len,
+                       include_slab, permutation_invariant, out, best_op);
     ADF_HIP_CHECK(hipGetLastError());
     return ADF_OK;
 }

@@ -300,6 +300,7 @@ def ml_relax_unique(
     tol: float = 0.05,
     rank=None,
     world=None,
+    symmetry=None,
     **kw,
 ):
     """``ml_relax`` of one representative per cluster of duplicate sites (``site_select.unique_sites`` on the positions given
@@ -308,13 +309,27 @@ def ml_relax_unique(
     batch in input order - the out-of-memory split's reordering is undone: a duplicate carries its representative's relaxed
     ``pos``, ``y`` and ``force`` (and, with ``relax_opt["flag_anomalies"]``, its ``anomaly`` row); ``site_rep`` [S] holds every
     site's representative.  The sites of a cluster are the same atoms within ``tol``, so a duplicate's own relaxation would
-    start from the same basin; how many relaxations that saves is a property of the input."""
+    start from the same basin; how many relaxations that saves is a property of the input.
+
+    ``symmetry`` (``slab_symmetry.find_symmetry`` of the bare slabs; its slab b is group id b): sites that are images of each
+    other under an operation of their slab are one cluster too.  A duplicate s merged into r under operation
+    g = (R, tau, perm) gets ``y`` and the ``anomaly`` row of r unchanged and r's relaxed ``pos`` and ``force`` carried through g
+    (``slab_symmetry.carry``), in the direction the distance recorded: where s comes before r in its group (g takes s onto r)
+    slab atom i of s is ``R^-1 (x_r[perm[i]] - tau)`` and adsorbate atom m ``R^-1 (x_r[m] - tau)``; otherwise slab atom
+    ``perm[i]`` of s is ``R x_r[i] + tau`` and adsorbate atom m ``R x_r[m] + tau``; forces go through ``R`` / ``R^-1`` without
+    ``tau``; positions are not wrapped back into the cell.  Adsorbate rows keep r's atom order: with the permutation-invariant
+    (Hausdorff) adsorbate rule the result is r's relaxed site up to a relabelling of same-element adsorbate atoms.
+    Operation 0 is the plain copy, bit for bit.  The batch also carries ``site_op`` [S] and ``site_op_inverse`` [S]."""
     from . import site_select
 
     select = {k: kw.pop(k) for k in ("include_slab", "permutation_invariant") if k in kw}
     if (rank is None) != (world is None):
         raise ValueError("ml_relax_unique: rank and world go together")
-    rep, is_rep, _ = site_select.unique_sites(batch, group=group, tol=tol, **select)
+    if symmetry is None:
+        rep, is_rep, _ = site_select.unique_sites(batch, group=group, tol=tol, **select)
+    else:
+        rep, is_rep, _, site_op, site_op_inverse = site_select.unique_sites(batch, group=group, tol=tol, symmetry=symmetry,
+                                                                            return_op=True, **select)
     dev = batch.pos.device
     chosen = is_rep.nonzero().reshape(-1).tolist()
     systems = batch.to_data_list()
@@ -345,4 +360,11 @@ def ml_relax_unique(
     if hasattr(relaxed, "anomaly"):
         out.anomaly = relaxed.anomaly[src_r.to(relaxed.anomaly.device)].to(dev)
     out.site_rep = rep
+    if symmetry is not None:
+        from . import slab_symmetry
+
+        slab = torch.as_tensor(batch.site_group if group is None else group).reshape(-1).to(dev)
+        out.pos, out.force = slab_symmetry.carry(symmetry, slab, site_op, site_op_inverse, batch.tags, batch.natoms, out.pos,
+                                                 out.force)
+        out.site_op, out.site_op_inverse = site_op, site_op_inverse
     return out

@@ -54,7 +54,7 @@ def _groups(batch, group, S: int, dev):
 class _Matrices:
     """The distance matrices of a batch in the regrouped order, with what the clustering needs next to them."""
 
-    def __init__(self, batch, group, include_slab: bool, permutation_invariant: bool):
+    def __init__(self, batch, group, include_slab: bool, permutation_invariant: bool, symmetry=None):
         pos = batch.pos
         S = int(batch.natoms.shape[0])
         group = _groups(batch, group, S, pos.device)
@@ -86,6 +86,21 @@ class _Matrices:
         self.total = sum(n * n for n in self.sizes)
         self.dist = torch.empty(self.total, dtype=torch.float32, device=dev)
         atom_offset = new_off.to(torch.int32)
+        self.best_op = None
+        if symmetry is not None:
+            # slab b of the symmetry is group id b: the operations of the groups present, group by group (the ids come to
+            # the host for it: a second small read-back)
+            op_off, rot, trans, sperm, perm_off, K, P = symmetry.for_groups(self.ids.tolist())
+            self.best_op = torch.empty(self.total, dtype=torch.int32, device=dev)
+            with torch.cuda.device(dev):
+                _lib.check(lib.adf_site_pair_distances_sym(p.data_ptr(), cell.data_ptr(), tags.data_ptr(), Z.data_ptr(),
+                                                           atom_offset.data_ptr(), self.offsets.data_ptr(),
+                                                           self.pair_offset.data_ptr(), N, S, self.G, self.total,
+                                                           int(bool(include_slab)), int(bool(permutation_invariant)),
+                                                           op_off.data_ptr(), rot.data_ptr(), trans.data_ptr(),
+                                                           sperm.data_ptr(), perm_off.data_ptr(), K, P,
+                                                           self.dist.data_ptr(), self.best_op.data_ptr(), _stream(dev)))
+            return
         with torch.cuda.device(dev):
             _lib.check(lib.adf_site_pair_distances(p.data_ptr(), cell.data_ptr(), tags.data_ptr(), Z.data_ptr(),
                                                    atom_offset.data_ptr(), self.offsets.data_ptr(),
@@ -93,29 +108,45 @@ class _Matrices:
                                                    int(bool(include_slab)), int(bool(permutation_invariant)),
                                                    self.dist.data_ptr(), _stream(dev)))
 
-    def matrices(self):
+    def matrices(self, flat=None):
+        flat = self.dist if flat is None else flat
         out, at = [], 0
         for n in self.sizes:
-            out.append(self.dist[at:at + n * n].view(n, n))
+            out.append(flat[at:at + n * n].view(n, n))
             at += n * n
         return out
 
 
-def site_distances(batch, group=None, include_slab: bool = True, permutation_invariant: bool = True):
+def site_distances(batch, group=None, include_slab: bool = True, permutation_invariant: bool = True, symmetry=None,
+                   return_op: bool = False):
     """One [n,n] float32 matrix per distinct id of ``group`` (default ``batch.site_group``), ascending ids, rows and columns in
     the caller's order of the group's sites: ``d = max(d_ads, d_slab)``, symmetric, zero diagonal, ``+inf`` between sites that
     differ in atom count, tags or atomic numbers.  ``include_slab=False``: the adsorbate alone.  ``permutation_invariant``:
     the adsorbate through the symmetric per-element Hausdorff distance (a flipped N2 is the same site) instead of atom by
-    atom."""
-    return _Matrices(batch, group, include_slab, permutation_invariant).matrices()
+    atom.  ``symmetry`` (``slab_symmetry.find_symmetry``; its slab b is group id b): the least distance over the slab's
+    operations applied to the earlier site of a pair; ``return_op``: also one [n,n] int32 matrix per group
+    with the minimising operation's index within its slab, the direction always "earlier site onto later site"."""
+    m = _Matrices(batch, group, include_slab, permutation_invariant, symmetry)
+    if not return_op:
+        return m.matrices()
+    if m.best_op is None:
+        raise ValueError("return_op needs symmetry=")
+    return m.matrices(), m.matrices(m.best_op)
 
 
 def unique_sites(batch, group=None, tol: float = 0.05, energy=None, energy_tol: Optional[float] = None, flags=None,
-                 include_slab: bool = True, permutation_invariant: bool = True):
+                 include_slab: bool = True, permutation_invariant: bool = True, symmetry=None, return_op: bool = False):
     """(rep [S] long, is_rep [S] bool, n_unique [G] long).  Per group the valid sites (no flag set, energy not NaN) are
     visited by (energy, the caller's order) - without ``energy`` in the caller's order - and each joins the first
     representative within ``tol`` of it (and within ``energy_tol`` in energy, when given), or becomes one.  ``rep[s]`` is the
-    representative of site s in the caller's indexing, s itself for a representative, -1 for an invalid site."""
+    representative of site s in the caller's indexing, s itself for a representative, -1 for an invalid site.
+
+    ``symmetry`` (``slab_symmetry.find_symmetry``; its slab b is group id b): the distance is the least over the slab's
+    operations, so sites that are images of each other under a symmetry of their slab fall into one cluster.
+    ``return_op`` (with ``symmetry``): also ``site_op`` [S] long - the operation of its slab under which site s was merged into
+    ``rep[s]``, 0 for a representative or an invalid site - and ``site_op_inverse`` [S] bool: the operation takes the earlier
+    site of a pair onto the later one, so it takes s onto its representative where s comes first (True) and the
+    representative onto s otherwise."""
     S = int(batch.natoms.shape[0])
     if energy is not None and int(energy.numel()) != S:
         raise ValueError(f"{S} sites, {int(energy.numel())} energies")
@@ -124,7 +155,9 @@ def unique_sites(batch, group=None, tol: float = 0.05, energy=None, energy_tol: 
     tol = float(tol)
     if not (math.isfinite(tol) and tol >= 0):
         raise ValueError(f"tol = {tol}: must be finite and not negative")
-    m = _Matrices(batch, group, include_slab, permutation_invariant)
+    if return_op and symmetry is None:
+        raise ValueError("return_op needs symmetry=")
+    m = _Matrices(batch, group, include_slab, permutation_invariant, symmetry)
     lib, dev = _lib.load(), m.dev
     e = None if energy is None else energy.detach().reshape(-1).to(dev, torch.float32)[m.perm].contiguous()
     f = None if flags is None else flags.to(dev)[m.perm].to(torch.int32).contiguous()
@@ -137,7 +170,21 @@ def unique_sites(batch, group=None, tol: float = 0.05, energy=None, energy_tol: 
                                         rep.data_ptr(), n_unique.data_ptr(), _stream(dev)))
     out = torch.empty(S, dtype=torch.long, device=dev)
     out[m.perm] = to_caller_order(rep, m.perm)
-    return out, out == torch.arange(S, device=dev), n_unique.long()
+    if not return_op:
+        return out, out == torch.arange(S, device=dev), n_unique.long()
+    # in the regrouped order: site s of group g sits at row s - offsets[g] of the group's matrix, its representative likewise
+    at = torch.arange(S, device=dev)
+    g = torch.repeat_interleave(torch.arange(m.G, device=dev), m.counts, output_size=S)
+    first, n = m.offsets.long()[g], m.counts[g]
+    r = rep.long()
+    merged = (r >= 0) & (r != at)
+    cell_at = m.pair_offset[g] + (at - first) * n + (r.clamp(min=0) - first)
+    op = torch.where(merged, m.best_op.long()[cell_at.clamp(0, max(m.total - 1, 0))], torch.zeros_like(at))
+    site_op = torch.empty(S, dtype=torch.long, device=dev)
+    site_op[m.perm] = op
+    inverse = torch.empty(S, dtype=torch.bool, device=dev)
+    inverse[m.perm] = merged & (at < r)
+    return out, out == torch.arange(S, device=dev), n_unique.long(), site_op, inverse
 
 
 def top_sites(energy: torch.Tensor, flags: Optional[torch.Tensor], group, k: int, rep=None):

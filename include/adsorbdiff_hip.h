@@ -453,6 +453,69 @@ int32_t adf_unique_sites(const float* dist, const int32_t* group_offset, const i
 int32_t adf_select_top_sites(const float* energy, const int32_t* flags, const int32_t* rep, const int32_t* group_offset,
                              int32_t num_groups, int32_t k, int32_t* top, float* top_energy, void* stream);
 
+/* ---- Slab symmetry (csrc/symmetry.hip, csrc/unique.hip; adsorbdiff_amd/slab_symmetry.py).  An extension: the
+ * reference has no counterpart (it leaves symmetry reduction to pymatgen's site finder, placement/adsorbate_slab_config.py:
+ * 113-116); neither pymatgen nor spglib was run against this contract, it stands alone and is checked against
+ * crystallography.  Slabs are bare: atoms atom_offset[b] .. atom_offset[b+1] of pos [N,3] float32 / atomic_numbers, cell
+ * [B,9] float32 with rows = lattice vectors; rows 0 and 1 span the surface plane.  All arithmetic is double, outputs are
+ * written with plain stores, there are no float atomics and two calls give the same bits.
+ *
+ * Operation: x -> R x + tau with the permutation perm it induces on the slab's atoms.  R n = n for the surface normal
+ * n = cell[0] x cell[1] / |.| (rotations about n, mirrors containing n; nothing that turns the slab over), R maps the
+ * in-plane lattice onto itself, tau lies in the plane.
+ *   Point operations.  (1) Lagrange-reduce the in-plane basis A = [a b]: A_r = A U, U integer unimodular.  (2) Enumerate the
+ *   2 x 2 integer matrices W_r with entries in {-1, 0, 1} and determinant +-1 (proper_only: +1).  (3) Accept W_r when the
+ *   lengths of the images of a_r, b_r and a_r + b_r (the columns of A_r W_r and their sum) each differ from the originals
+ *   by at most symprec.  (4) W = U W_r U^-1, integer.  (5) R = M [W 0; 0 1] M^-1, M = [a b n] as columns: the lattice goes
+ *   exactly onto itself even where the float32 cell is symmetric only to rounding.  At most 12 per slab.
+ *   Translations.  i0: the first atom of the rarest atomic number (ties to the smaller number).  For every atom j of that
+ *   element the candidate is tau_j = x_j - R x_i0.
+ *   Acceptance.  (W, j) is an operation when every atom i has an atom k of its atomic number with
+ *   |reduce(R x_i + tau - x_k)| <= symprec and no k is taken twice; perm[i] = that k (the nearest, ties to the lower
+ *   index).  reduce: the two in-plane fractional components through M^-1 minus their nearest integer (ties to even), the
+ *   component along n as it is (no wrap along the normal), then the Euclidean norm of M times that.  Below half the
+ *   shortest in-plane lattice height, area / max(|a|, |b|), that is the true nearest image in any cell; a symprec at or
+ *   above it (or a cell whose first two rows span no finite area) is refused: ADF_EINVAL.  No convention quirk as in
+ *   adf_site_pair_distances.
+ *   Order.  Operation 0 is the identity, stored as R = I, tau = 0, perm = iota exactly; then the other accepted candidates
+ *   in ascending (W00, W01, W10, W11, j).  A slab without atoms has no operation.
+ *
+ * adf_slab_symmetry_search verifies every candidate (slab, 12 point slots, atom j) - one flag word each in `scratch`, slots
+ * without a point operation and atoms of another element are rejected - and counts: n_ops [2B] on the device, the counts
+ * followed by the slabs' atom counts n_b, copied into n_ops_host [2B] (host memory) before it returns: the one read-back,
+ * after which the caller sizes the outputs.
+ * `scratch`: adf_slab_symmetry_scratch(num_atoms, num_slabs) bytes of device memory, handed on unchanged to
+ * adf_slab_symmetry_emit with the same atom_offset / symprec.  That writes, for op_offset [B+1] = exclusive sum of n_ops
+ * and perm_offset [B+1] (int64) = exclusive sum of n_ops[b] n_b: rot [K,9] and trans [K,3] double, W [K,4] int32 and perm
+ * (perm_len int32; operation k of slab b owns perm[perm_offset[b] + k n_b ..+ n_b)). */
+int64_t adf_slab_symmetry_scratch(int32_t num_atoms, int32_t num_slabs);
+int32_t adf_slab_symmetry_search(const float* pos, const float* cell, const int32_t* atomic_numbers,
+                                 const int32_t* atom_offset, int32_t num_atoms, int32_t num_slabs, double symprec,
+                                 int32_t proper_only, void* scratch, int32_t* n_ops, int32_t* n_ops_host, void* stream);
+int32_t adf_slab_symmetry_emit(const int32_t* atom_offset, int32_t num_atoms, int32_t num_slabs, double symprec,
+                               const void* scratch, const int32_t* op_offset, const int64_t* perm_offset, int32_t num_ops,
+                               int64_t perm_len, double* rot, double* trans, int32_t* W, int32_t* perm, void* stream);
+/* adf_site_pair_distances up to a symmetry of the slab.  The arguments of adf_site_pair_distances, and per group g the
+ * operations op_offset[g] .. op_offset[g+1] of rot / trans (num_ops of them) with their permutations at perm_offset[g]
+ * (as adf_slab_symmetry_emit writes them; n_b = the group's entries / its operations).  For i < j
+ *   d_sym(i,j) = min over the group's operations g of d(g . site_i, site_j),
+ * d exactly adf_site_pair_distances' max(d_ads, d_slab) in its min_diff convention with the cell of the earlier site i.
+ * g . site_i: every position is R x + tau, formed in double and rounded to float32 once; the k-th atom of tag != 2 of
+ * site i is compared with the perm[k]-th atom of tag != 2 of site j; the adsorbate goes through the ordered or the
+ * per-element Hausdorff rule.  Operation 0 of a group is the identity and is not applied, so a group with that one
+ * operation gets the bits of adf_site_pair_distances.  The value goes to (i,j) and (j,i); best_op (int32, laid out as out)
+ * gets the index within the group of the minimising operation at both, ties to the lowest index - its direction is always
+ * "earlier site onto later site"; 0 on the diagonal and where d is +inf or NaN.  d = +inf also when the number of tag != 2
+ * atoms of the sites differs from n_b, when a group has no operation, and when the atoms of tag 2 of a site are not one
+ * contiguous block (place_adsorbates writes them after the slab).  Per operation d_ads is evaluated first and the slab part
+ * is skipped when d_ads >= the best d so far: such an operation cannot win (an exact saving). */
+int32_t adf_site_pair_distances_sym(const float* pos, const float* cell, const int32_t* tags, const int32_t* atomic_numbers,
+                                    const int32_t* atom_offset, const int32_t* group_offset, const int64_t* pair_offset,
+                                    int32_t num_atoms, int32_t num_sites, int32_t num_groups, int64_t out_len,
+                                    int32_t include_slab, int32_t permutation_invariant, const int32_t* op_offset,
+                                    const double* rot, const double* trans, const int32_t* perm, const int64_t* perm_offset,
+                                    int32_t num_ops, int64_t perm_len, float* out, int32_t* best_op, void* stream);
+
 /* ---- Adsorbate placement (csrc/placement.hip; adsorbdiff_amd/placement.py): the reference's
  * AdsorbateSlabConfig, placement/adsorbate_slab_config.py:99-439, 460-575 with adsorbate.py:122-169, modes "random"
  * [mode 0] and "random_site_heuristic_placement" [mode 1], for a whole batch of slabs.  This is a written contract, a
