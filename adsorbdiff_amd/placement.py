@@ -11,8 +11,15 @@ in one launch (``adf_place_adsorbates``) and returns the collated batch that ``D
 
 The rule is the contract written in include/adsorbdiff_hip.h: a reading of the reference's lines and of the ASE calls
 they make.  ASE is not a dependency and was not run against it: parity with ASE is unpinned, ``radii`` and ``masses`` are
-parameters.  ``mode="heuristic"`` site finding (pymatgen's ``AdsorbateSiteFinder``) is not here; explicit ``sites=`` are
-accepted, so sites found elsewhere can still be placed.
+parameters.
+
+The reference's third mode, ``"heuristic"`` (:113-116, 185-194: the ontop, bridge and hollow sites of pymatgen's
+``AdsorbateSiteFinder``, all of them, each with heuristic placement), is ``heuristic_sites`` / ``place_adsorbates_heuristic``
+/ ``AdsorbateSlabConfig.heuristic`` (csrc/sites.hip): the candidates and their reduction - near-duplicates,
+then sites equivalent under the slab's symmetry (``slab_symmetry.find_symmetry``) - run on the device for the whole batch.
+It is a written contract; pymatgen was not run against it.  ``place``, ``place_adsorbates`` and
+``AdsorbateSlabConfig(...)`` keep refusing the string ``mode="heuristic"`` (``ValueError``): that mode takes no ``num_sites``
+and draws no site, so it has entry points of its own.  ``reduce_sites`` runs the same reduction on any ``Sites``.
 
 Draws are counter based (``adf_place_draws``): a row of eight uniforms ``(r1, r2, selection key, u0, u1, u2, binding
 pick, spare)`` depends on ``(seed, noising.noise_keys(slab_batch)[b], index)`` alone, where ``index`` is the candidate's
@@ -32,9 +39,11 @@ import torch
 from . import lib as _lib
 from .data import Batch
 from .noising import noise_keys
+from .slab_symmetry import SlabSymmetry, find_symmetry
 
 MODES = {"random": 0, "random_site_heuristic_placement": 1}
 DRAW_COLUMNS = ("r1", "r2", "select", "u0", "u1", "u2", "binding", "spare")
+SITE_KINDS = ("ontop", "bridge", "hollow")     # SurfaceSites.kind: 0, 1, 2
 
 
 def default_radii() -> np.ndarray:
@@ -155,6 +164,141 @@ class Sites(NamedTuple):
     cand_slab: Optional[torch.Tensor] = None
 
 
+class SurfaceSites(NamedTuple):
+    """Heuristic sites (``heuristic_sites``), slab-major, then ontop, bridge, hollow, then candidate order.  As ``Sites``:
+    ``pos`` float32 [S,3], ``slab`` int64 [S], the host lists ``counts`` and ``slab_natoms``.  Per site: ``kind`` int32 [S]
+    (the index into ``SITE_KINDS``), ``multiplicity`` int32 [S] (its orbit size in the cell: the distinct candidates
+    equivalent to it, itself included) and ``candidate`` int64 [S] (its row of the raw tables).  The raw tables, kind-major
+    within a slab: ``candidates`` float32 [C,3], ``valid`` bool [C] (False: the hollow of an obtuse triangle), ``rep``
+    int32 [C] (the row of the site a candidate fell to, -1 where invalid), ``first`` int32 [C] (the same after the
+    near-duplicate pass alone) and ``seg_offset`` int32 [3B+1] (segment 3 b + kind owns rows ``seg_offset[3 b + kind] ..``).
+    Everything but the two lists is on the device."""
+    pos: torch.Tensor
+    slab: torch.Tensor
+    counts: list
+    slab_natoms: list
+    kind: torch.Tensor
+    multiplicity: torch.Tensor
+    candidate: torch.Tensor
+    candidates: torch.Tensor
+    valid: torch.Tensor
+    rep: torch.Tensor
+    first: torch.Tensor
+    seg_offset: torch.Tensor
+
+
+class ReducedSites(NamedTuple):
+    """``reduce_sites``: the kept ``sites`` (a ``Sites``, in the order they came in), ``rep`` int64 [S_in] (per site that
+    went in, the index among those of the kept site it fell to) and ``multiplicity`` int32 [S_out] per kept site."""
+    sites: Sites
+    rep: torch.Tensor
+    multiplicity: torch.Tensor
+
+
+def _resolve_symmetry(symmetry, slab_batch, B: int):
+    if symmetry is None or isinstance(symmetry, SlabSymmetry):
+        if symmetry is not None and symmetry.num_slabs != B:
+            raise ValueError(f"symmetry of {symmetry.num_slabs} slabs for a batch of {B}")
+        return symmetry
+    if isinstance(symmetry, str) and symmetry == "auto":
+        return "auto"
+    raise ValueError(f"symmetry = {symmetry!r}: \"auto\", None or a SlabSymmetry")
+
+
+def _check_tol(tol) -> float:
+    tol = float(tol)
+    if not (0.0 <= tol < math.inf):
+        raise ValueError(f"tol = {tol}: finite and not negative expected")
+    return tol
+
+
+def _reduce(lib, dev, slab_batch, B, cand, valid, seg_off, seg_slab, G, symmetry, tol):
+    """adf_reduce_sites on a candidate table: (first, rep, multiplicity, counts [G,2]) on the device."""
+    if isinstance(symmetry, str):
+        symmetry = find_symmetry(slab_batch)
+    C_rows = int(cand.shape[0])
+    cell = slab_batch.cell.to(dev, torch.float32).reshape(B, 9).contiguous()
+    first = torch.full((C_rows,), -1, dtype=torch.int32, device=dev)
+    rep = torch.full((C_rows,), -1, dtype=torch.int32, device=dev)
+    mult = torch.zeros(C_rows, dtype=torch.int32, device=dev)
+    counts = torch.zeros(G, 2, dtype=torch.int32, device=dev)
+    if symmetry is None:
+        op_off = rot = trans = None
+        K = 0
+    else:
+        op_off = symmetry.op_offset.to(dev, torch.int32).contiguous()
+        rot = symmetry.rot.to(dev, torch.float64).contiguous()
+        trans = symmetry.trans.to(dev, torch.float64).contiguous()
+        K = int(rot.shape[0])
+    ptr = lambda t: None if t is None else t.data_ptr()
+    with torch.cuda.device(dev):
+        _lib.check(lib.adf_reduce_sites(cand.data_ptr(), ptr(valid), seg_off.data_ptr(), ptr(seg_slab), cell.data_ptr(),
+                                        C_rows, G, B, ptr(op_off), ptr(rot), ptr(trans), K, C.c_double(tol),
+                                        first.data_ptr(), rep.data_ptr(), mult.data_ptr(), counts.data_ptr(), _stream(dev)))
+    return first, rep, mult, counts
+
+
+@torch.no_grad()
+def heuristic_sites(slab_batch, triangles=None, symmetry="auto", tol: float = 0.05, positions=SITE_KINDS) -> SurfaceSites:
+    """The ontop, bridge and hollow sites of every slab, reduced to one per class of equivalent sites (the
+    contract is in include/adsorbdiff_hip.h).  ``triangles``: per slab a ``[T,3,3]`` array (None: ``surface_triangles``).
+    ``symmetry``: ``"auto"`` - ``slab_symmetry.find_symmetry(slab_batch)``; a ``SlabSymmetry`` - used as given; None - only
+    near-duplicates (closer than ``tol``, in A, modulo the in-plane lattice) are merged.  ``positions``: the kinds to
+    return (the raw tables always hold all three).  All sites are returned: there is no shuffle and no ``num_sites``, as in the reference's mode ``"heuristic"``.
+    Two launches; beyond what ``surface_triangles`` and ``find_symmetry`` do, one host read (the per-slab counts) and no
+    loop over slabs or sites."""
+    positions = (positions,) if isinstance(positions, str) else tuple(positions)
+    if not positions or len(set(positions)) != len(positions) or any(p not in SITE_KINDS for p in positions):
+        raise ValueError(f"positions = {positions!r}: a non-empty selection of {SITE_KINDS} expected")
+    tol = _check_tol(tol)
+    B = int(slab_batch.natoms.numel())
+    symmetry = _resolve_symmetry(symmetry, slab_batch, B)
+    if getattr(slab_batch, "tags", None) is None:
+        raise ValueError("slab_batch.tags is required (tag 1 marks the surface)")
+    if triangles is None:
+        triangles = surface_triangles(slab_batch)
+    triangles = [np.asarray(t, dtype=np.float64).reshape(-1, 3, 3) for t in triangles]
+    if len(triangles) != B:
+        raise ValueError(f"{len(triangles)} triangle tables for {B} slabs")
+    if not slab_batch.pos.is_cuda:
+        raise RuntimeError("heuristic_sites runs on a ROCm device (the HIP path has no CPU fallback)")
+    lib = _lib.load()
+    dev = slab_batch.pos.device
+    T = [int(t.shape[0]) for t in triangles]
+    Ttot = sum(T)
+    pos = slab_batch.pos.detach().to(torch.float32).contiguous()
+    N = int(pos.shape[0])
+    tags = _i32(slab_batch.tags, dev)
+    natoms = slab_batch.natoms.to(dev, torch.int64).reshape(-1)
+    atom_off = _offsets(natoms)
+    cell = slab_batch.cell.to(dev, torch.float32).reshape(B, 9).contiguous()
+    tri = torch.from_numpy(np.concatenate(triangles).astype(np.float32) if Ttot else np.zeros((1, 3, 3), np.float32))
+    tri = tri.to(dev).contiguous()
+    tri_off = torch.tensor(np.concatenate([[0], np.cumsum(T)]), dtype=torch.int32, device=dev)
+    rows = max(N + 4 * Ttot, 1)                                   # an upper bound: the tag-1 counts stay on the device
+    seg_off = torch.zeros(3 * B + 1, dtype=torch.int32, device=dev)
+    cand = torch.zeros(rows, 3, dtype=torch.float32, device=dev)
+    valid = torch.zeros(rows, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.adf_surface_site_candidates(pos.data_ptr(), tags.data_ptr(), atom_off.data_ptr(), cell.data_ptr(),
+                                                   tri.data_ptr(), tri_off.data_ptr(), N, Ttot, B, rows, seg_off.data_ptr(),
+                                                   cand.data_ptr(), valid.data_ptr(), _stream(dev)))
+    seg_slab = torch.repeat_interleave(torch.arange(B, dtype=torch.int32, device=dev), 3, output_size=3 * B).contiguous()
+    first, rep, mult, seg_counts = _reduce(lib, dev, slab_batch, B, cand, valid, seg_off, seg_slab, 3 * B, symmetry, tol)
+    wanted = torch.tensor([k in positions for k in SITE_KINDS], device=dev)
+    per_slab = (seg_counts[:, 1].long().view(B, 3) * wanted.long()).sum(1)
+    so = seg_off.long()
+    counts, slab_natoms, n_cand = torch.stack([per_slab, natoms, so[3::3] - so[0:-1:3]]).tolist()   # the one host read
+    S, Ctot = int(sum(counts)), int(sum(n_cand))
+    row = torch.arange(rows, device=dev)
+    seg = torch.searchsorted(so[1:].contiguous(), row, right=True).clamp(max=3 * B - 1)
+    chosen = (rep.long() == row) & wanted[seg % 3]
+    order = torch.sort((~chosen).long(), stable=True).indices[:S]   # the chosen rows, ascending
+    return SurfaceSites(cand[order].contiguous(), (seg[order] // 3).contiguous(), counts, slab_natoms,
+                        (seg[order] % 3).to(torch.int32), mult[order].contiguous(), order, cand[:Ctot], valid[:Ctot] != 0,
+                        rep[:Ctot], first[:Ctot], seg_off)
+
+
 # ------------------------------------------------------------------------------------------------ the placer
 class AdsorbatePlacer:
     """Sites and placements for batches of slabs on one device.  ``radii`` / ``masses``: tables indexed by atomic number
@@ -256,7 +400,7 @@ class AdsorbatePlacer:
 
     def _as_sites(self, slab_batch, sites) -> Sites:
         B = int(slab_batch.natoms.numel())
-        if isinstance(sites, Sites):
+        if isinstance(sites, (Sites, SurfaceSites)):
             return sites
         natoms = slab_batch.natoms.reshape(-1).tolist()
         if isinstance(sites, (list, tuple)) and len(sites) == 2 and torch.is_tensor(sites[1]) and sites[1].dim() == 1 \
@@ -286,6 +430,35 @@ class AdsorbatePlacer:
         slab = torch.repeat_interleave(torch.arange(B), torch.tensor(counts)).to(self.dev)
         return Sites(pos, slab, counts, natoms)
 
+    # ---- heuristic sites and the reduction of any sites
+    def heuristic_sites(self, slab_batch, triangles=None, symmetry="auto", tol: float = 0.05, positions=SITE_KINDS) -> SurfaceSites:
+        """The module's ``heuristic_sites`` (which needs no radii or masses)."""
+        return heuristic_sites(slab_batch, triangles, symmetry, tol, positions)
+
+    @torch.no_grad()
+    def reduce_sites(self, slab_batch, sites, symmetry="auto", tol: float = 0.05) -> ReducedSites:
+        """The reduction of ``heuristic_sites`` on any sites - those of ``sites()``, or whatever ``place(sites=)`` takes -
+        all of one kind: per slab, in the order given, a site is kept unless a kept one before it lies within ``tol`` of it,
+        first as it is, then under the slab's operations (``symmetry`` as in ``heuristic_sites``).  One host read."""
+        tol = _check_tol(tol)
+        B = int(slab_batch.natoms.numel())
+        symmetry = _resolve_symmetry(symmetry, slab_batch, B)
+        st = self._as_sites(slab_batch, sites)
+        S = int(st.pos.shape[0])
+        if S == 0:
+            raise ValueError("reduce_sites: no site")
+        dev = self.dev
+        cand = st.pos.to(dev, torch.float32).contiguous()
+        seg_off = torch.tensor(np.concatenate([[0], np.cumsum(st.counts)]), dtype=torch.int32, device=dev)
+        _, rep, mult, seg_counts = _reduce(self.lib, dev, slab_batch, B, cand, None, seg_off, None, B, symmetry, tol)
+        counts = seg_counts[:, 1].tolist()                          # the one host read
+        kept = rep.long() == torch.arange(S, device=dev)
+        order = torch.sort((~kept).long(), stable=True).indices[:sum(counts)]
+        new_index = torch.cumsum(kept.long(), 0) - 1
+        slab = st.slab.to(dev)
+        return ReducedSites(Sites(cand[order].contiguous(), slab[order].contiguous(), counts, list(st.slab_natoms)),
+                            new_index[rep.long()], mult[order].contiguous())
+
     # ---- placements
     @torch.no_grad()
     def place(self, slab_batch, adsorbates, sites, num_augmentations_per_site: int = 1, interstitial_gap: float = 0.1,
@@ -294,10 +467,13 @@ class AdsorbatePlacer:
         augmentation.  ``adsorbates``: one ``(Z, pos)`` for all slabs or one per slab; ``sites``: what ``sites()`` returned,
         or per slab an [n,3] array, or ``(pos [S,3], slab [S])`` tensors; ``binding_indices`` (heuristic placement): one
         list of atom indices, or one per slab; ``draws``: [P,8] rows, one per placement.  The batch carries ``site_group``
-        (the slab of every placement) and ``site_index`` (int32 [P]: its number within that slab)."""
+        (the slab of every placement) and ``site_index`` (int32 [P]: its number within that slab); with the ``SurfaceSites``
+        of ``heuristic_sites`` also ``site_kind`` and ``site_multiplicity`` (int32 [P]).  ``mode="heuristic"`` is refused
+        here: that is ``place_adsorbates_heuristic``."""
         if mode not in MODES:
-            raise ValueError(f"mode {mode!r}: one of {sorted(MODES)} (\"heuristic\" site finding is not provided; pass "
-                             "sites= found elsewhere with mode=\"random_site_heuristic_placement\")")
+            raise ValueError(f"mode {mode!r}: one of {sorted(MODES)} (the reference's mode \"heuristic\" is "
+                             "place_adsorbates_heuristic / AdsorbateSlabConfig.heuristic, or sites=heuristic_sites(...) "
+                             "with mode=\"random_site_heuristic_placement\")")
         gap = float(interstitial_gap)
         if not (0.0 <= gap < 5.0):
             raise ValueError(f"interstitial_gap = {gap}: 0 <= gap < 5 expected")
@@ -417,6 +593,9 @@ class AdsorbatePlacer:
         out.n_combos = nc
         if bind is not None:
             out.binding_idx = bind
+        if isinstance(st, SurfaceSites):
+            out.site_kind = torch.repeat_interleave(st.kind, n_aug, output_size=P)
+            out.site_multiplicity = torch.repeat_interleave(st.multiplicity, n_aug, output_size=P)
         return out
 
 
@@ -433,6 +612,23 @@ def place_adsorbates(slab_batch, adsorbates, num_sites: int, num_augmentations_p
     if sites is None:
         sites = placer.sites(slab_batch, num_sites, triangles=triangles)
     return placer.place(slab_batch, adsorbates, sites, num_augmentations_per_site, interstitial_gap, mode, binding_indices)
+
+
+def place_adsorbates_heuristic(slab_batch, adsorbates, binding_indices, num_augmentations_per_site: int = 1,
+                               interstitial_gap: float = 0.1, radii=None, masses=None, triangles=None, symmetry="auto",
+                               tol: float = 0.05, positions=SITE_KINDS, seed: int = 0, device=None,
+                               placer: AdsorbatePlacer = None) -> Batch:
+    """The reference's mode ``"heuristic"`` (:113-116, 185-194, 208, 223) for a batch: ``heuristic_sites`` - every ontop,
+    bridge and hollow site, one per class of equivalent sites - and on each of them ``place`` with
+    ``mode="random_site_heuristic_placement"``, the rule the reference applies there.  The batch also carries ``site_kind``
+    and ``site_multiplicity`` per placement.  (``place_adsorbates(mode="heuristic")`` stays a ``ValueError``.)"""
+    if not (0.0 <= float(interstitial_gap) < 5.0):
+        raise ValueError(f"interstitial_gap = {interstitial_gap}: 0 <= gap < 5 expected")
+    if placer is None:
+        placer = AdsorbatePlacer(radii, masses, device=slab_batch.pos.device if device is None else device, seed=seed)
+    sites = placer.heuristic_sites(slab_batch, triangles, symmetry, tol, positions)
+    return placer.place(slab_batch, adsorbates, sites, num_augmentations_per_site, interstitial_gap,
+                        "random_site_heuristic_placement", binding_indices)
 
 
 # ------------------------------------------------------------------------------------------------ overlap
@@ -509,15 +705,37 @@ class AdsorbateSlabConfig:
         self.interstitial_gap, self.mode = interstitial_gap, mode
         placer = AdsorbatePlacer(radii, masses, device=device, seed=seed)
         sb = _atoms_batch(slab.atoms, placer.dev)
-        a = adsorbate.atoms
-        ads = (np.asarray(a.numbers), np.asarray(_get(a, "positions"), dtype=np.float64).reshape(-1, 3))
         if sites is None:
             st = placer.sites(sb, num_sites, triangles=None if triangles is None else [triangles])
         else:
             st = [np.asarray(sites, dtype=np.float64).reshape(-1, 3)]
-        binding = None if mode == "random" else list(getattr(adsorbate, "binding_indices"))
-        self.batch = placer.place(sb, ads, st, num_augmentations_per_site, interstitial_gap, mode, binding)
-        self.sites = (st.pos if isinstance(st, Sites) else torch.as_tensor(st[0])).detach().cpu().double().numpy()
+        self._place(placer, sb, st, mode)
+
+    @classmethod
+    def heuristic(cls, slab, adsorbate, num_augmentations_per_site: int = 1, interstitial_gap: float = 0.1, radii=None,
+                  masses=None, triangles=None, symmetry="auto", tol: float = 0.05, positions=SITE_KINDS, device="cuda:0",
+                  seed: int = 0):
+        """The reference's ``mode="heuristic"`` for one structure: every site of ``heuristic_sites``, heuristic placement on
+        each.  Also exposes ``surface_sites`` (the ``SurfaceSites``).  The constructor keeps refusing that mode string."""
+        if not (0.0 <= float(interstitial_gap) < 5.0):
+            raise ValueError(f"interstitial_gap = {interstitial_gap}: 0 <= gap < 5 expected")
+        self = cls.__new__(cls)
+        self.slab, self.adsorbate = slab, adsorbate
+        self.num_sites, self.num_augmentations_per_site = None, num_augmentations_per_site
+        self.interstitial_gap, self.mode = interstitial_gap, "heuristic"
+        placer = AdsorbatePlacer(radii, masses, device=device, seed=seed)
+        sb = _atoms_batch(slab.atoms, placer.dev)
+        st = placer.heuristic_sites(sb, None if triangles is None else [triangles], symmetry, tol, positions)
+        self.surface_sites = st
+        self._place(placer, sb, st, "random_site_heuristic_placement")
+        return self
+
+    def _place(self, placer, sb, st, mode):
+        a = self.adsorbate.atoms
+        ads = (np.asarray(a.numbers), np.asarray(_get(a, "positions"), dtype=np.float64).reshape(-1, 3))
+        binding = None if mode == "random" else list(getattr(self.adsorbate, "binding_indices"))
+        self.batch = placer.place(sb, ads, st, self.num_augmentations_per_site, self.interstitial_gap, mode, binding)
+        self.sites = (st.pos if isinstance(st, (Sites, SurfaceSites)) else torch.as_tensor(st[0])).detach().cpu().double().numpy()
         site = self.batch.site.detach().cpu().double().numpy()
         meta = self.batch.xyz_angles.detach().cpu().numpy()
         self.metadata_list = [{"site": site[p], "xyz_angles": [float(meta[p, 0]), meta[p, 1:4].copy()]}

@@ -576,6 +576,62 @@ int32_t adf_place_site_candidates(const float* tri, const int32_t* tri_offset, c
 int32_t adf_interstitial_distances(const adf_batch* b, const int32_t* tags, const float* radii, int32_t num_radii,
                                    const float* masses, int32_t num_masses, const int32_t* pbc, float* out, void* stream);
 
+/* ---- Heuristic adsorption sites (csrc/sites.hip; adsorbdiff_amd/placement.py: heuristic_sites, reduce_sites; DESIGN.md
+ * 4k): the site list of the reference's mode "heuristic" [placement/adsorbate_slab_config.py:113-116, 185-194], which it
+ * takes from pymatgen's AdsorbateSiteFinder.  pymatgen was not run against this: it is a written contract, parity with
+ * pymatgen is unpinned, and it is checked against crystallographic known answers and a float64 oracle.  Inputs are float32,
+ * all arithmetic is float64, there are no float atomics and two calls give the same bits.
+ *
+ * Frame of slab b: M = [a b n] as columns, a = cell[b][0], b = cell[b][1], n = a x b / |a x b| [sign as it comes]; a cell
+ * whose first two rows span no finite area is refused.
+ *   put inside:  f = M^-1 x, f_k -> (f_k + 1e-7) - floor(f_k + 1e-7) - 1e-7 for k = 0, 1 [the wrap rule of
+ *     adf_place_adsorbates], the component along n kept, x = M f.  [With cell[2] parallel to n this is that rule on the
+ *     cell's own fractional coordinates; with a tilted cell[2] it may pick another lattice image.]
+ *   d(x, y) = |reduce(x - y)|, reduce as in the slab symmetry section: the two in-plane components of M^-1 (x - y) minus
+ *     their nearest integer [ties to even], the normal component as it is, the norm of M times that.  In a strongly skewed
+ *     cell this is not the shortest image [the caveat of adf_site_pair_distances and adf_slab_symmetry_search]: two
+ *     sites closer than tol through another image are then both kept.
+ *
+ * adf_surface_site_candidates.  Slab b has atoms atom_offset[b] .. atom_offset[b+1] of pos [N,3] / tags [N] and triangles
+ * tri_offset[b] .. tri_offset[b+1] of tri [T,3,3] [as adf_place_site_candidates takes them].  Its candidates, kind-major:
+ *   ontop   n_top[b] of them: its atoms of tag 1, in atom order;
+ *   bridge  3 T_b: per triangle, in table order, the midpoints 0.5 (v1 + v2), 0.5 (v0 + v2), 0.5 (v0 + v1) - every edge
+ *           listed by the corner opposite to it;
+ *   hollow  T_b: per triangle (v0 + v1 + v2) / 3.  The slot is INVALID [valid = 0; it stays in the layout] when the
+ *           triangle is "obtuse": at some corner the cosine between the two normalised edge vectors leaving it is not
+ *           >= 1e-5 [pymatgen's no_obtuse_hollow as we read it].  A right triangle therefore counts as obtuse - the
+ *           four-fold hollow of fcc(100) appears as the bridge site of the diagonal, a quirk that is kept - and so does a
+ *           triangle with an edge of no length [its cosine is NaN].
+ * Every candidate is put inside and stored as float32.  seg_offset [3 B + 1] is WRITTEN here, on the device, from the tag-1
+ * counts and the triangle counts: segment 3 b + kind holds rows seg_offset[3 b + kind] .. seg_offset[3 b + kind + 1] of
+ * cand [capacity,3] / valid [capacity]; seg_offset[3 B] = sum_b n_top[b] + 4 T.  capacity: rows of the two tables,
+ * N + 4 T always suffices [rows past seg_offset[3 B] are not written].  Offsets that are not ascending or leave their
+ * arrays, and tables too small, return ADF_EINVAL: no candidate is written, seg_offset holds nothing of use, nothing is
+ * read or written past an array, and the call synchronises `stream` to read the error word [as adf_place_adsorbates does]. */
+int32_t adf_surface_site_candidates(const float* pos, const int32_t* tags, const int32_t* atom_offset, const float* cell,
+                                    const float* tri, const int32_t* tri_offset, int32_t num_atoms, int32_t num_triangles,
+                                    int32_t num_slabs, int32_t capacity, int32_t* seg_offset, float* cand, int32_t* valid,
+                                    void* stream);
+/* The reduction of any candidate table.  Segment g = rows seg_offset[g] .. seg_offset[g+1] of cand [C,3] belongs to slab
+ * seg_slab[g] [NULL: slab g] of cell [B,9]; valid [C] may be NULL [all valid].  Per segment, greedy in candidate order: a
+ * valid candidate c is kept if and only if no kept r < c of its segment has dist(c, r) <= tol.  Two passes:
+ *   first   dist = d [the identity alone]: near-duplicates, the copies that tiling produces included.  first[c] = the
+ *           index [into cand] of the kept candidate c fell to - the first kept one within tol -, c itself when kept;
+ *   second  over the survivors of the first, dist(c, r) = d_sym(c, r) = min over the operations k of the slab of
+ *           d(R_k x_c + tau_k, x_r), evaluated in exactly this form [the operation acts on the later candidate], the
+ *           operations op_offset[b] .. op_offset[b+1] of rot [K,9] / trans [K,3] as adf_slab_symmetry_emit writes them.
+ *           op_offset NULL: the identity alone, and the second pass keeps what the first kept.
+ * rep[c]: the kept candidate of the second pass that first[c] fell to; first[c] = rep[c] = -1 for an invalid slot.
+ * multiplicity[r], for a survivor of the second pass: the survivors of the first pass that fell to it, itself included -
+ * its orbit size in the cell; 0 for every other row.  counts [G,2]: kept after the first pass, kept after both; 0 for an
+ * empty segment or one with invalid slots only.  tol [A] must be finite and >= 0.  One workgroup per segment; candidates,
+ * kept sites and operations may each be of any number.  A segment whose offsets are not ascending or leave [0, C], whose
+ * slab is outside [0, B) or whose operations leave [0, K) is neither read nor written: ADF_EINVAL, reported as above. */
+int32_t adf_reduce_sites(const float* cand, const int32_t* valid, const int32_t* seg_offset, const int32_t* seg_slab,
+                         const float* cell, int32_t num_candidates, int32_t num_segments, int32_t num_slabs,
+                         const int32_t* op_offset, const double* rot, const double* trans, int32_t num_ops, double tol,
+                         int32_t* first, int32_t* rep, int32_t* multiplicity, int32_t* counts, void* stream);
+
 /* Multi-GPU exchange of the sharded sampler: systems are independent, every rank samples its shard
  * with no data-path collective, and ONE all-gather of the sampled adsorbate sites ends a pass.  Replaces the reference's
  * per-rank .npz + barrier + rank-0 merge (trainers/sde_denoising_trainer.py:862-909).  RCCL is loaded lazily (dlopen).
