@@ -21,6 +21,10 @@ It is a written contract; pymatgen was not run against it.  ``place``, ``place_a
 ``AdsorbateSlabConfig(...)`` keep refusing the string ``mode="heuristic"`` (``ValueError``): that mode takes no ``num_sites``
 and draws no site, so it has entry points of its own.  ``reduce_sites`` runs the same reduction on any ``Sites``.
 
+All of them start from the triangles of the tiled surface atoms: ``surface_triangles`` makes them on the host with
+``scipy.spatial.Delaunay``, ``surface_triangles_device`` (csrc/triangulate.hip) on the device for the whole
+batch, and every ``triangles=`` takes ``"device"`` or the ``SurfaceTriangles`` it returns besides host tables.
+
 Draws are counter based (``adf_place_draws``): a row of eight uniforms ``(r1, r2, selection key, u0, u1, u2, binding
 pick, spare)`` depends on ``(seed, noising.noise_keys(slab_batch)[b], index)`` alone, where ``index`` is the candidate's
 position among its slab's candidates (``sites``) or ``site * num_augmentations_per_site + augmentation`` within its slab
@@ -107,7 +111,7 @@ def _offsets(counts: torch.Tensor) -> torch.Tensor:
     return off
 
 
-# ------------------------------------------------------------------------------------------------ surface triangles (host)
+# ------------------------------------------------------------------------------------------------ surface triangles (host: scipy)
 def tiling_vectors(cell: np.ndarray) -> np.ndarray:
     """The two lattice vectors ``custom_tile_atoms`` (:479-508) tiles with: the first two rows of the cell that pass its
     test ``round(v[0], 3) != 0 or round(v[1], 3 != 0)`` - as written there, the second ``round`` has one decimal."""
@@ -126,7 +130,7 @@ def surface_triangles(slab_batch) -> List[np.ndarray]:
         from scipy.spatial import Delaunay
     except ImportError as e:
         raise ImportError("surface_triangles needs scipy (scipy.spatial.Delaunay), which is not installed; pass the "
-                          "triangle tables yourself (triangles=...)") from e
+                          "triangle tables yourself (triangles=...) or have them made on the device (triangles=\"device\")") from e
     pos = slab_batch.pos.detach().cpu().double().numpy()
     tags = slab_batch.tags.detach().cpu().numpy()
     cells = slab_batch.cell.detach().cpu().double().numpy().reshape(-1, 3, 3)
@@ -149,6 +153,80 @@ def surface_triangles(slab_batch) -> List[np.ndarray]:
             raise ValueError(f"surface_triangles: slab {b} has no surface triangle ({len(surf)} atoms of tag 1)")
         out.append(tiled[simplices])
     return out
+
+
+# ------------------------------------------------------------------------------------------------ surface triangles (device)
+class SurfaceTriangles(NamedTuple):
+    """``surface_triangles_device``: ``tri`` float32 [T,3,3] (the vertices), ``tri_offset`` int32 [B+1] (slab b owns rows
+    ``tri_offset[b] .. tri_offset[b+1]``) and ``index`` int32 [T,3] (the tiled indices ``tile * n_top + ordinal``, the
+    least first, counter-clockwise, the rows of a slab ascending) on the device; ``counts``: triangles per slab, a host
+    list."""
+    tri: torch.Tensor
+    tri_offset: torch.Tensor
+    index: torch.Tensor
+    counts: list
+
+    def to_list(self) -> List[np.ndarray]:
+        """The host form ``surface_triangles`` returns: per slab a float64 ``[T,3,3]`` array."""
+        tri = self.tri.detach().cpu().double().numpy()
+        bounds = np.concatenate([[0], np.cumsum(self.counts)]).astype(np.int64)
+        return [tri[bounds[b]:bounds[b + 1]].copy() for b in range(len(self.counts))]
+
+
+@torch.no_grad()
+def surface_triangles_device(slab_batch, circle_tol: float = 1e-4) -> SurfaceTriangles:
+    """``surface_triangles`` on the device for the whole batch (``adf_surface_triangles``; the contract is
+    in include/adsorbdiff_hip.h): the same tiling, the Delaunay triangles of the tiled x, y with a vertex in the central
+    tile, as a set what scipy returns wherever the triangulation is unique.  Points within ``circle_tol`` (A) of a
+    triangle's circumcircle count as co-circular; such a polygon is split as a fan from its vertex of least x (then y).
+    No scipy, no loop over slabs; one host read (the per-slab counts)."""
+    circle_tol = float(circle_tol)
+    if not (0.0 <= circle_tol < math.inf):
+        raise ValueError(f"circle_tol = {circle_tol}: finite and not negative expected")
+    if getattr(slab_batch, "tags", None) is None:
+        raise ValueError("slab_batch.tags is required (tag 1 marks the surface)")
+    if not slab_batch.pos.is_cuda:
+        raise RuntimeError("surface_triangles_device runs on a ROCm device (the HIP path has no CPU fallback)")
+    lib = _lib.load()
+    dev = slab_batch.pos.device
+    B = int(slab_batch.natoms.numel())
+    pos = slab_batch.pos.detach().to(torch.float32).contiguous()
+    N = int(pos.shape[0])
+    tags = _i32(slab_batch.tags, dev)
+    atom_off = _offsets(slab_batch.natoms.to(dev, torch.int64).reshape(-1))
+    cell = slab_batch.cell.to(dev, torch.float32).reshape(B, 9).contiguous()
+    rows = max(18 * N, 1)                                          # always enough: fewer than 2 * 9 n_top triangles per slab
+    tri = torch.empty(rows, 3, 3, dtype=torch.float32, device=dev)
+    index = torch.empty(rows, 3, dtype=torch.int32, device=dev)
+    tri_off = torch.zeros(B + 1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.adf_surface_triangles(pos.data_ptr(), tags.data_ptr(), atom_off.data_ptr(), cell.data_ptr(), N, B,
+                                             C.c_double(circle_tol), rows, tri_off.data_ptr(), tri.data_ptr(),
+                                             index.data_ptr(), _stream(dev)))
+    bounds = tri_off.tolist()                                      # the one host read
+    return SurfaceTriangles(tri[:bounds[-1]], tri_off, index[:bounds[-1]], [b1 - b0 for b0, b1 in zip(bounds, bounds[1:])])
+
+
+def _triangle_tables(slab_batch, triangles, B: int, dev):
+    """What every entry point does with ``triangles=``: (tables, tri_offset, the per-slab counts as a host list).
+    ``"device"`` (``surface_triangles_device``) or a ``SurfaceTriangles``: tri float32 [T,3,3] and tri_offset int32 [B+1]
+    on ``dev``, as they are - no host copy, no upload.  None (``surface_triangles``: scipy, on the host) or per slab a
+    ``[T,3,3]`` array: the float64 host tables and tri_offset None - the caller packs and uploads them."""
+    if isinstance(triangles, str):
+        if triangles != "device":
+            raise ValueError(f"triangles = {triangles!r}: None, \"device\", a SurfaceTriangles or one [T,3,3] array per slab")
+        triangles = surface_triangles_device(slab_batch)
+    if isinstance(triangles, SurfaceTriangles):
+        if len(triangles.counts) != B or int(triangles.tri_offset.numel()) != B + 1:
+            raise ValueError(f"SurfaceTriangles of {len(triangles.counts)} slabs for a batch of {B}")
+        return (triangles.tri.to(dev, torch.float32).contiguous(), triangles.tri_offset.to(dev, torch.int32).contiguous(),
+                [int(c) for c in triangles.counts])
+    if triangles is None:
+        triangles = surface_triangles(slab_batch)
+    triangles = [np.asarray(t, dtype=np.float64).reshape(-1, 3, 3) for t in triangles]
+    if len(triangles) != B:
+        raise ValueError(f"{len(triangles)} triangle tables for {B} slabs")
+    return triangles, None, [int(t.shape[0]) for t in triangles]
 
 
 class Sites(NamedTuple):
@@ -241,7 +319,8 @@ def _reduce(lib, dev, slab_batch, B, cand, valid, seg_off, seg_slab, G, symmetry
 @torch.no_grad()
 def heuristic_sites(slab_batch, triangles=None, symmetry="auto", tol: float = 0.05, positions=SITE_KINDS) -> SurfaceSites:
     """The ontop, bridge and hollow sites of every slab, reduced to one per class of equivalent sites (the
-    contract is in include/adsorbdiff_hip.h).  ``triangles``: per slab a ``[T,3,3]`` array (None: ``surface_triangles``).
+    contract is in include/adsorbdiff_hip.h).  ``triangles``: per slab a ``[T,3,3]`` array (None: ``surface_triangles``, on
+    the host with scipy; ``"device"``: ``surface_triangles_device``; a ``SurfaceTriangles``: used as it is, on the device).
     ``symmetry``: ``"auto"`` - ``slab_symmetry.find_symmetry(slab_batch)``; a ``SlabSymmetry`` - used as given; None - only
     near-duplicates (closer than ``tol``, in A, modulo the in-plane lattice) are merged.  ``positions``: the kinds to
     return (the raw tables always hold all three).  All sites are returned: there is no shuffle and no ``num_sites``, as in the reference's mode ``"heuristic"``.
@@ -255,16 +334,11 @@ def heuristic_sites(slab_batch, triangles=None, symmetry="auto", tol: float = 0.
     symmetry = _resolve_symmetry(symmetry, slab_batch, B)
     if getattr(slab_batch, "tags", None) is None:
         raise ValueError("slab_batch.tags is required (tag 1 marks the surface)")
-    if triangles is None:
-        triangles = surface_triangles(slab_batch)
-    triangles = [np.asarray(t, dtype=np.float64).reshape(-1, 3, 3) for t in triangles]
-    if len(triangles) != B:
-        raise ValueError(f"{len(triangles)} triangle tables for {B} slabs")
+    triangles, tri_off, T = _triangle_tables(slab_batch, triangles, B, slab_batch.pos.device)
     if not slab_batch.pos.is_cuda:
         raise RuntimeError("heuristic_sites runs on a ROCm device (the HIP path has no CPU fallback)")
     lib = _lib.load()
     dev = slab_batch.pos.device
-    T = [int(t.shape[0]) for t in triangles]
     Ttot = sum(T)
     pos = slab_batch.pos.detach().to(torch.float32).contiguous()
     N = int(pos.shape[0])
@@ -272,9 +346,12 @@ def heuristic_sites(slab_batch, triangles=None, symmetry="auto", tol: float = 0.
     natoms = slab_batch.natoms.to(dev, torch.int64).reshape(-1)
     atom_off = _offsets(natoms)
     cell = slab_batch.cell.to(dev, torch.float32).reshape(B, 9).contiguous()
-    tri = torch.from_numpy(np.concatenate(triangles).astype(np.float32) if Ttot else np.zeros((1, 3, 3), np.float32))
-    tri = tri.to(dev).contiguous()
-    tri_off = torch.tensor(np.concatenate([[0], np.cumsum(T)]), dtype=torch.int32, device=dev)
+    if tri_off is None:                                           # host tables: packed and uploaded
+        tri = torch.from_numpy(np.concatenate(triangles).astype(np.float32) if Ttot else np.zeros((1, 3, 3), np.float32))
+        tri = tri.to(dev).contiguous()
+        tri_off = torch.tensor(np.concatenate([[0], np.cumsum(T)]), dtype=torch.int32, device=dev)
+    else:                                                         # the device's tables, as they are
+        tri = triangles if Ttot else torch.zeros(1, 3, 3, dtype=torch.float32, device=dev)
     rows = max(N + 4 * Ttot, 1)                                   # an upper bound: the tag-1 counts stay on the device
     seg_off = torch.zeros(3 * B + 1, dtype=torch.int32, device=dev)
     cand = torch.zeros(rows, 3, dtype=torch.float32, device=dev)
@@ -345,7 +422,8 @@ class AdsorbatePlacer:
     @torch.no_grad()
     def sites(self, slab_batch, num_sites: int, triangles=None, draws=None) -> Sites:
         """Up to ``num_sites`` sites per slab (fewer where fewer candidates fall into the central cell, as in the
-        reference).  ``triangles``: per slab a ``[T,3,3]`` array (None: ``surface_triangles``); ``draws``: [C,8] rows for the
+        reference).  ``triangles``: per slab a ``[T,3,3]`` array (None: ``surface_triangles``; ``"device"`` or a
+        ``SurfaceTriangles``: ``surface_triangles_device``'s tables, used on the device as they are); ``draws``: [C,8] rows for the
         C = sum_b T_b ceil(2 num_sites / T_b) candidates in slab-major, triangle-major order.  The kept candidates of a slab
         are ordered by ascending selection key (ties: candidate index) and the first ``num_sites`` are taken; this
         replaces the reference's ``np.random.shuffle``.  One host read: the per-slab counts."""
@@ -354,19 +432,17 @@ class AdsorbatePlacer:
             raise ValueError(f"num_sites = {num_sites}")
         dev = self.dev
         B = int(slab_batch.natoms.numel())
-        if triangles is None:
-            triangles = surface_triangles(slab_batch)
-        triangles = [np.asarray(t, dtype=np.float64).reshape(-1, 3, 3) for t in triangles]
-        if len(triangles) != B:
-            raise ValueError(f"{len(triangles)} triangle tables for {B} slabs")
-        T = [int(t.shape[0]) for t in triangles]
+        triangles, tri_off, T = _triangle_tables(slab_batch, triangles, B, dev)
         if min(T) == 0:
             raise ValueError(f"slab {T.index(0)} has no triangle")
         per = [int(math.ceil(2.0 * num_sites / t)) for t in T]
         n_cand = [t * p for t, p in zip(T, per)]
         Ctot = sum(n_cand)
-        tri = torch.from_numpy(np.concatenate(triangles).astype(np.float32)).to(dev).contiguous()
-        tri_off = torch.tensor(np.concatenate([[0], np.cumsum(T)]), dtype=torch.int32, device=dev)
+        if tri_off is None:                                       # host tables: packed and uploaded
+            tri = torch.from_numpy(np.concatenate(triangles).astype(np.float32)).to(dev).contiguous()
+            tri_off = torch.tensor(np.concatenate([[0], np.cumsum(T)]), dtype=torch.int32, device=dev)
+        else:                                                     # the device's tables, as they are
+            tri = triangles
         per_t = torch.tensor(per, dtype=torch.int32, device=dev)
         cand_counts = torch.tensor(n_cand, dtype=torch.int64, device=dev)
         cand_off = _offsets(cand_counts)
@@ -686,12 +762,19 @@ def _atoms_batch(atoms, dev) -> Batch:
     return b
 
 
+def _one_slab_triangles(triangles):
+    """``triangles=`` of the one-structure interface: None, ``"device"`` and a ``SurfaceTriangles`` pass, a ``[T,3,3]``
+    array becomes the list of one table."""
+    return triangles if triangles is None or isinstance(triangles, (str, SurfaceTriangles)) else [triangles]
+
+
 class AdsorbateSlabConfig:
     """The reference's interface (:22-97) on the batched call, with its keyword names.  ``slab.atoms`` and
     ``adsorbate.atoms`` are duck-typed (``positions`` / ``get_positions()``, ``cell``, ``numbers``, ``tags`` /
     ``get_tags()``, ``pbc``); ``adsorbate.binding_indices`` is read in the heuristic-placement mode.  Exposes ``sites``
     ([S,3] numpy), ``batch`` (the collated placements) and ``metadata_list`` (``{"site", "xyz_angles": [zrot, rotvec]}``
-    per placement).  ASE ``atoms_list`` objects are not built (ASE is not a dependency)."""
+    per placement).  ``triangles``: one ``[T,3,3]`` table, ``"device"`` or a ``SurfaceTriangles`` (None: scipy on the
+    host).  ASE ``atoms_list`` objects are not built (ASE is not a dependency)."""
 
     def __init__(self, slab, adsorbate, num_sites: int = 1, num_augmentations_per_site: int = 1,
                  interstitial_gap: float = 0.1, mode: str = "random", sites=None, radii=None, masses=None,
@@ -706,7 +789,7 @@ class AdsorbateSlabConfig:
         placer = AdsorbatePlacer(radii, masses, device=device, seed=seed)
         sb = _atoms_batch(slab.atoms, placer.dev)
         if sites is None:
-            st = placer.sites(sb, num_sites, triangles=None if triangles is None else [triangles])
+            st = placer.sites(sb, num_sites, triangles=_one_slab_triangles(triangles))
         else:
             st = [np.asarray(sites, dtype=np.float64).reshape(-1, 3)]
         self._place(placer, sb, st, mode)
@@ -725,7 +808,7 @@ class AdsorbateSlabConfig:
         self.interstitial_gap, self.mode = interstitial_gap, "heuristic"
         placer = AdsorbatePlacer(radii, masses, device=device, seed=seed)
         sb = _atoms_batch(slab.atoms, placer.dev)
-        st = placer.heuristic_sites(sb, None if triangles is None else [triangles], symmetry, tol, positions)
+        st = placer.heuristic_sites(sb, _one_slab_triangles(triangles), symmetry, tol, positions)
         self.surface_sites = st
         self._place(placer, sb, st, "random_site_heuristic_placement")
         return self

@@ -632,6 +632,44 @@ int32_t adf_reduce_sites(const float* cand, const int32_t* valid, const int32_t*
                          const int32_t* op_offset, const double* rot, const double* trans, int32_t num_ops, double tol,
                          int32_t* first, int32_t* rep, int32_t* multiplicity, int32_t* counts, void* stream);
 
+/* ---- Surface triangles (csrc/triangulate.hip; adsorbdiff_amd/placement.py: surface_triangles_device): the
+ * triangle tables that adf_place_site_candidates and adf_surface_site_candidates take, made on the device for a whole
+ * batch - the reference's tiling and pruning [placement/adsorbate_slab_config.py:117-142, 479-508], which it and
+ * placement.surface_triangles leave to scipy.spatial.Delaunay on the host.  For points in general position the Delaunay
+ * triangulation is unique: there the table equals scipy's as a set, and that is pinned [tests/golden/surface_triangles.npz].
+ * Inputs are float32, all arithmetic is float64, there are no float atomics, two calls give the same bits, and a slab's
+ * rows depend neither on its batch-mates nor on its place in the batch.
+ *
+ * Slab b has atoms atom_offset[b] .. atom_offset[b+1] of pos [N,3] / tags [N] and the cell cell[b] [9, rows a, b, c].
+ *   Tiling.  v0, v1: the first two rows v of the cell with |v_x| >= 0.0005 or |v_y| >= 0.05 [custom_tile_atoms' test
+ *     round(v[0], 3) != 0 or round(v[1], 1) != 0 - placement.tiling_vectors - which it equals wherever the two components
+ *     are not within 1e-6 of 0.0005 / 0.05].  The n_top atoms of tag 1, in atom order, are copied to 9 tiles in the order
+ *     of surface_triangles: tile 0 is (0, 0), tiles 1 .. 8 are (i, j) for i in (-1, 0, 1), j in (-1, 0, 1) without (0, 0).
+ *     Tiled point tile * n_top + ordinal is (p + i v0) + j v1 in float64 [the products are exact]; rounded once to float32
+ *     it is a row of tri, equal bit for bit to the host path's .astype(float32).
+ *   Triangles.  Of the Delaunay triangulation of the x, y of all 9 n_top points [the float64 values], those with at least
+ *     one vertex in tile 0.  A triangle is (a, b, c), a its least tiled index, a -> b -> c counter-clockwise in x, y; a
+ *     slab's rows are sorted ascending by (a, b, c).
+ *   Co-circular points.  A point whose distance to a triangle's circumcentre differs from the radius by at most circle_tol
+ *     [A] lies on the circle.  The points on one empty circle form one convex polygon, which is split as a fan from its
+ *     canonical vertex: the one of least x, values of x within circle_tol of the least counting as equal and the least y
+ *     [then the least index] deciding among those.  Every vertex of the polygon arrives at the same fan: the rectangles of
+ *     an fcc(100) or fcc(110) surface are all split along parallel diagonals.  [With more than one point strictly inside
+ *     the band circle_tol / 10 .. 10 circle_tol of a circle the rule may be applied differently from two sides; 1e-4 A is
+ *     ten float32 roundings of a coordinate above, and far below any interatomic distance.]
+ * Outputs, written on the device: tri_offset [B+1] - slab b owns rows tri_offset[b] .. tri_offset[b+1] -, tri
+ * [capacity,3,3] the vertices and tri_index [capacity,3] their tiled indices.  capacity >= 18 N always suffices [a planar
+ * triangulation of n points has fewer than 2 n triangles, n = 9 n_top]; rows past tri_offset[B] are not written.
+ * ADF_EINVAL - reported as adf_surface_site_candidates reports one: the call synchronises `stream` to read an error word -
+ * for a slab without an atom of tag 1, a cell with fewer than two such rows, tiled points that are all collinear [or
+ * coincide, or whose tiling vectors are parallel in x, y so that the tiles do not surround tile 0], atom offsets that are
+ * not ascending or leave [0, N], more triangles than capacity, and a circle_tol that is negative or not finite.  On an error
+ * tri and tri_index are not written, tri_offset holds zeros, and nothing is read or written past an array.  n_top may be
+ * any number; n_top = 1 gives the triangulation of the lattice itself. */
+int32_t adf_surface_triangles(const float* pos, const int32_t* tags, const int32_t* atom_offset, const float* cell,
+                              int32_t num_atoms, int32_t num_slabs, double circle_tol, int32_t capacity,
+                              int32_t* tri_offset, float* tri, int32_t* tri_index, void* stream);
+
 /* Multi-GPU exchange of the sharded sampler: systems are independent, every rank samples its shard
  * with no data-path collective, and ONE all-gather of the sampled adsorbate sites ends a pass.  Replaces the reference's
  * per-rank .npz + barrier + rank-0 merge (trainers/sde_denoising_trainer.py:862-909).  RCCL is loaded lazily (dlopen).
