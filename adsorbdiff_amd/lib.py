@@ -39,7 +39,7 @@ EXPORTS = (
     "adf_lift_adsorbates", "adf_flag_anomalies", "adf_select_best_sites",
     "adf_site_pair_distances", "adf_unique_sites", "adf_select_top_sites",
     "adf_slab_symmetry_scratch", "adf_slab_symmetry_search", "adf_slab_symmetry_emit", "adf_site_pair_distances_sym",
-    "adf_place_draws", "adf_place_adsorbates", "adf_place_site_candidates", "adf_interstitial_distances", "adf_surface_site_candidates", "adf_reduce_sites", "adf_surface_triangles", "adf_comm_unique_id", "adf_comm_create", "adf_comm_destroy", "adf_allgather_sites",
+    "adf_place_draws", "adf_place_adsorbates", "adf_place_site_candidates", "adf_interstitial_distances", "adf_surface_site_candidates", "adf_reduce_sites", "adf_surface_triangles", "adf_voronoi_coordination", "adf_bulk_coordination_min", "adf_tag_surface_atoms", "adf_comm_unique_id", "adf_comm_create", "adf_comm_destroy", "adf_allgather_sites",
     "adf_op_linear_fwd", "adf_op_linear_bwd_scratch", "adf_op_linear_bwd", "adf_op_ssilu_fwd", "adf_op_ssilu_bwd", "adf_op_layernorm_fwd", "adf_op_layernorm_bwd", "adf_op_embed_fwd", "adf_op_embed_bwd", "adf_op_rbf", "adf_op_message_fwd", "adf_op_message_fwd_fused", "adf_op_message_bwd", "adf_op_message_bwd_fused", "adf_op_message_bwd_fused_supported", "adf_op_message_bwd_perm", "adf_op_edge_owner", "adf_op_rbf_image_bytes", "adf_op_rbf_image", "adf_op_rbf_wgrad_fused_scratch", "adf_op_rbf_wgrad_fused", "adf_op_vdot_fwd", "adf_op_vdot_bwd", "adf_op_update_out_fwd", "adf_op_update_out_bwd", "adf_op_vnorm_fwd", "adf_op_vnorm_bwd", "adf_op_gate_fwd", "adf_op_gate_bwd", "adf_op_copy_rows", "adf_op_score_loss", "adf_op_score_loss_tr", "adf_op_s2ef_loss", "adf_op_s2ef_loss_scratch", "adf_op_energy_sum", "adf_op_energy_head_bwd", "adf_op_energy_head_bwd_scratch", "adf_op_sqnorm_accumulate", "adf_op_adamw_step",
     "adf_op_optimizer_chunk", "adf_op_grad_sqnorm_multi", "adf_op_adamw_multi", "adf_op_embed_bwd_ordered", "adf_op_embed_bwd_ordered_scratch",
     "adf_noise_draws", "adf_noise_tr_so3", "adf_noise_com", "adf_igso3_score_norm",
@@ -209,6 +209,10 @@ def load():
         "adf_surface_site_candidates": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp],
         "adf_reduce_sites": [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, i32, C.c_double, vp, vp, vp, vp, vp],
         "adf_surface_triangles": [vp, vp, vp, vp, i32, i32, C.c_double, i32, vp, vp, vp, vp],
+        "adf_voronoi_coordination": [vp, vp, vp, vp, i32, i32, vp, C.c_double, C.c_double, C.c_double, vp, vp, vp, vp, vp],
+        "adf_bulk_coordination_min": [vp, vp, vp, vp, i32, i32, vp, vp],
+        "adf_tag_surface_atoms": [vp, vp, vp, vp, vp, i32, i32, vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
+                                  vp, vp, vp, vp],
         "adf_comm_unique_id": [vp],
         "adf_comm_create": [vp, i32, i32, C.POINTER(vp)],
         "adf_comm_destroy": [vp],

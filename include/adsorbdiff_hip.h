@@ -670,6 +670,77 @@ int32_t adf_surface_triangles(const float* pos, const int32_t* tags, const int32
                               int32_t num_atoms, int32_t num_slabs, double circle_tol, int32_t capacity,
                               int32_t* tri_offset, float* tri, int32_t* tri_index, void* stream);
 
+/* ---- Surface tags (csrc/voronoi.hip; adsorbdiff_amd/surface_tags.py): the tags that every entry point above
+ * starts from - 1 for a surface atom, 0 for the rest -, made on the device for a whole batch: the reference's
+ * tag_surface_atoms [placement/slab.py:284-482: find_surface_atoms_by_height, find_surface_atoms_with_voronoi_given_height,
+ * calculate_coordination_of_bulk_atoms], whose coordination numbers are pymatgen's VoronoiNN(tol=0.1).get_cn(use_weights=
+ * True), a qhull call per atom.  pymatgen was not run against it; the geometry is pinned to qhull [scipy.spatial.Voronoi on
+ * the same points, tests/golden/voronoi_cn.npz].  Inputs are float32, ALL arithmetic is float64, there are no float atomics,
+ * two calls give the same bits, and a system's rows depend neither on its batch-mates nor on its place in the batch.
+ *
+ * adf_voronoi_coordination.  System b has atoms atom_offset[b] .. atom_offset[b+1] of pos [N,3], the cell cell[b] [9, rows
+ * a, b, c] and is periodic along row k where pbc[b][k] != 0.  select [N]: the atoms to evaluate [!= 0], NULL: all.
+ *   Images.  With V = a . (b x c), the plane spacing along row k is |V| / |product of the other two rows|, and the repeats
+ *     along a periodic row are r_k = ceil(cutoff / spacing_k) of that system alone [0 along a row that is not periodic].
+ *     Image (i_a, i_b, i_c), |i_k| <= r_k, has the index ((i_a + r_a) (2 r_b + 1) + (i_b + r_b)) (2 r_c + 1) + (i_c + r_c)
+ *     and the shift (i_a a + i_b b) + i_c c.  The points of atom i are d = (p_j + shift) - p_i over every atom j of its
+ *     system and every image, with 1e-16 < |d|^2 and |d| <= cutoff [13.0 A is pymatgen's; the first excludes the atom
+ *     itself].  They are the CANDIDATES, ordered by (|d|^2, atom index j, image index).
+ *   Facet j.  On the bisector plane of (i, j) - the points x with x . d_j = |d_j|^2 / 2 - start from the square of half-width
+ *     1e4 A about d_j / 2 with sides along u = normalised(n x e), v = n x u [n = d_j / |d_j|, e = x when |n_x| < 0.9, else
+ *     y], and clip it in candidate order by every other candidate k [Sutherland-Hodgman; a vertex with
+ *     s = x . d_k - |d_k|^2 / 2 <= 0 is kept, an edge whose ends differ in that gets the point at t = s_a / (s_a - s_b)].
+ *     What is left, if it has three vertices or more, is the facet; omega_j is the solid angle it subtends at the atom, the
+ *     absolute value of the sum over the fan (v_0, v_m, v_m+1) of Van Oosterom and Strackee's
+ *     2 atan2(a . (b x c), |a||b||c| + (a . b)|c| + (a . c)|b| + (b . c)|a|); omega_j = 0 without a facet.
+ *   Outputs per evaluated atom.  omega_max = max_j omega_j; w_j = omega_j / omega_max; nn = the number of j with
+ *     w_j > weight_tol; cn = the sum of those w_j in candidate order [get_cn(use_weights=True) with tol = weight_tol].
+ *   Open cells.  flags bit 0 is set when a vertex of a facet lies farther than `far` [100 A] from the atom - a cell its
+ *     candidates do not close, pymatgen's "pathological" RuntimeError - and for an atom without a candidate.  Then cn and
+ *     omega_max are NaN and nn is 0.
+ *   Security radius.  A candidate farther than twice the largest vertex distance R of the cell built so far cannot cut it,
+ *     and a clip that does not cut leaves the vertices as they are, bit for bit.  The kernel builds the cell from the K
+ *     nearest candidates [K = 64, doubled while candidate K exists and is not farther than 2 R]: the outputs are those of
+ *     clipping by all candidates.
+ *   Capacities, never silently exceeded: 1024 candidates per atom, 32 vertices per facet while it is clipped, 2^24 (atom,
+ *     image) pairs looked at per atom.  ADF_EOVERFLOW otherwise; the message names the first such atom.
+ * ADF_EINVAL: atom offsets that are not ascending or leave [0, N]; a system with a periodic row whose cell is singular or
+ * not finite; cutoff, weight_tol or far that are not finite or not positive.  Errors are reported as
+ * adf_surface_site_candidates reports them: the call synchronises `stream` to read an error word.  On an error no output is
+ * written and nothing is read or written past an array.  Rows of atoms that are not selected are never written. */
+int32_t adf_voronoi_coordination(const float* pos, const float* cell, const int32_t* pbc, const int32_t* atom_offset,
+                                 int32_t num_atoms, int32_t num_systems, const int32_t* select, double cutoff,
+                                 double weight_tol, double far, double* cn, double* omega_max, int32_t* nn, int32_t* flags,
+                                 void* stream);
+/* table [B,119]: per system and atomic number the least cn over that element's atoms, in atom order, +inf where the system
+ * has none [calculate_coordination_of_bulk_atoms, reduced to the minimum that the comparison uses; every atom is
+ * evaluated, not one per symmetry class].  cn / flags [N] as adf_voronoi_coordination wrote them for all atoms.  ADF_EINVAL:
+ * a flagged atom [a bulk is periodic in three directions and its cells close], a cn that is NaN, an atomic number outside
+ * [0, 118], offsets as above; the table is then not written.  Fixed order, no atomics. */
+int32_t adf_bulk_coordination_min(const double* cn, const int32_t* flags, const int32_t* atomic_numbers,
+                                  const int32_t* atom_offset, int32_t num_atoms, int32_t num_systems, double* table,
+                                  void* stream);
+/* adf_tag_surface_atoms.  Every atom of system b is a slab atom [tags of the caller are not read].  Per system, in order:
+ *   1. f_i = p_i . (a x b) / (c . (a x b)): the fractional coordinate along row c; where that row is periodic f -> f - floor(f),
+ *      twice [ASE's get_scaled_positions].
+ *   2. Height rule [slab.py:350-382]: tag 1 iff not (f_i < max_i f - height / |c|); height = 2.0 A there.
+ *   3. Coordination rule [slab.py:385-437], only with bulk_cn_min [B,119; adf_bulk_coordination_min of the slabs' bulks,
+ *      one row per slab]: f_com = sum(m_i f_i) / sum(m_i) in atom order, m = masses[Z_i] [119 doubles]; every atom of tag 0
+ *      with not (f_i < f_com) is evaluated as adf_voronoi_coordination evaluates it and becomes tag 1 when its cell is open
+ *      or cn < bulk_cn_min[b][Z_i] - cn_tol.
+ * Two deviations from the reference.  It takes the centre-of-mass test on pymatgen's unwrapped fractional coordinates:
+ * here the one wrapped f serves both rules [they differ only for atoms outside the cell along c].  It compares
+ * round(cn, 5) < min: with float32 positions a fully coordinated fcc atom comes out at 11.999995, on that knife; here the
+ * comparison is cn < min - cn_tol, cn_tol = 1e-3 by default [>= 0].
+ * Outputs: tags [N] 0 / 1; cn [N] and flags [N] of the evaluated atoms, NaN and 0 for the others.  ADF_EINVAL besides
+ * adf_voronoi_coordination's: a singular or non-finite cell [any system], height or cn_tol negative or not finite, a mass
+ * sum that is not positive, an atomic number outside [0, 118], and - with bulk_cn_min - an atom whose element is absent
+ * [+inf or NaN] from its slab's row.  ADF_EOVERFLOW as above.  On an error no output is written. */
+int32_t adf_tag_surface_atoms(const float* pos, const float* cell, const int32_t* pbc, const int32_t* atomic_numbers,
+                              const int32_t* atom_offset, int32_t num_atoms, int32_t num_systems, const double* masses,
+                              const double* bulk_cn_min, double height, double cutoff, double weight_tol, double far,
+                              double cn_tol, int32_t* tags, double* cn, int32_t* flags, void* stream);
+
 /* Multi-GPU exchange of the sharded sampler: systems are independent, every rank samples its shard
  * with no data-path collective, and ONE all-gather of the sampled adsorbate sites ends a pass.  Replaces the reference's
  * per-rank .npz + barrier + rank-0 merge (trainers/sde_denoising_trainer.py:862-909).  RCCL is loaded lazily (dlopen).
