@@ -127,6 +127,11 @@ extern "C" int32_t adf_painn_create(const adf_painn_hparams* hp, adf_painn_t* ou
         h->lift_on = !(el && strcmp(el, "0") == 0);
         const char* e2 = getenv("ADF_MSG");
         h->msg_f32 = e2 ? strcmp(e2, "f32") == 0 : h->gemm_f32;
+        // The f16 message kernel stages its rbf_proj image in 16-byte pieces of 8 basis functions per column: a basis that
+        // is no multiple of 8 runs the exact-f32 message kernel (even R, contracted two deep) whatever the arithmetic of
+        // the node products.  message_bwd.hip / message_geo.hip carry the same predicate.
+        h->msg_f32_only = hp->num_rbf % 8 != 0;
+        h->msg_f32 = h->msg_f32 || h->msg_f32_only;
         const char* er = getenv("ADF_ROW_MAXIMA");   // row maxima from the producers (common.h: adf_painn::rmx)
         h->rmx = (er && atoi(er) == 0) ? 0 : 1;
         h->tune = adf_tune_from_env();
@@ -1008,7 +1013,7 @@ extern "C" int32_t adf_linear_forward(const float* A, const float* W, const floa
 extern "C" int32_t adf_painn_set_arithmetic(adf_painn_t h, int32_t exact_f32) {
     if (!h) { adf_set_error("null handle"); return ADF_EINVAL; }
     h->gemm_f32 = exact_f32 != 0;
-    h->msg_f32 = exact_f32 != 0;
+    h->msg_f32 = exact_f32 != 0 || h->msg_f32_only;
     h->rec0_valid = false;
     h->inc_valid = false;
     return ADF_OK;

@@ -206,6 +206,7 @@ struct adf_painn {
     unsigned char* wfrag_arena;   // fragment images of every split weight (adf_w16::frag), same size as w16_arena
     bool gemm_f32;
     bool msg_f32;
+    bool msg_f32_only;   // num_rbf % 8 != 0: the message block always runs its exact-f32 kernel (adf_painn_create)
     adf_tune tune;       // kernel-selection switches, read from the environment at creation (adf_tune_from_env)
     // per-row power-of-two lifts of the f16x3 products' A operands (default on; ADF_LIFT=0 = the unlifted split of rounds 1-2)
     bool lift_on;

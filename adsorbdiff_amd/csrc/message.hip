@@ -359,7 +359,14 @@ __global__ __launch_bounds__(FWD_THREADS, MSG_WAVES_PER_SIMD) void adf_message_k
                             const float dm = xsq - mus[j];
                             // a in [0,1] is lifted by 2^8 before the split so that a_lo is a normal fp16 number
                             // for every term that matters (the matrix core flushes fp16 subnormals)
-                            const float a = env256 * __builtin_amdgcn_exp2f(-(dm * dm));
+                            float a = env256 * __builtin_amdgcn_exp2f(-(dm * dm));
+                            // The product must be ONE f32 value before it is split.  Left to itself hipcc forms the h that a_lo
+                            // is taken against from the unrounded product (v_fma_mixlo_f16) and the h that goes to the matrix
+                            // core from the rounded one (v_cvt_pk_f16_f32): wherever the f32 rounding crosses an fp16 midpoint
+                            // (one term in 2^13) the two differ by an fp16 ulp and a_hi + a_lo is off by 5e-4 of the term -
+                            // 1e-4 of a whole output row when it is an edge's leading term (tests/test_gpu_painn_range.py,
+                            // direct128).  The empty asm makes `a` opaque, so both uses see the same conversion.
+                            asm volatile("" : "+v"(a));
                             const _Float16 h = (_Float16)a;
                             ah[j] = h;
                             al[j] = (_Float16)(a - (float)h);

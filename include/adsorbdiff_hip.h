@@ -79,7 +79,11 @@ typedef struct {
 #define ADF_WEIGHTS_PER_LAYER 13
 #define ADF_WEIGHTS_PER_HEAD 12
 
-/* Replaces constructing the model (painn_denoising.py:57-148). */
+/* Replaces constructing the model (painn_denoising.py:57-148).  Accepted: hidden_channels a multiple of 64 in
+ * [128, 1024], num_rbf even in [2, 128], max_neighbors in [1, 128], num_layers in [1, 16], num_heads in [0, 2], any
+ * envelope exponent; anything else is ADF_EINVAL.  A num_rbf that is no multiple of 8 does not fit the 16-byte pieces
+ * of the f16 message kernel's rbf_proj image: such a handle runs the message block in its exact-f32 kernel in either
+ * arithmetic (adf_painn_set_arithmetic then only switches the node products). */
 int32_t adf_painn_create(const adf_painn_hparams* hp, adf_painn_t* out);
 int32_t adf_painn_destroy(adf_painn_t h);
 

@@ -248,9 +248,11 @@ def painn_forward(
     so3_denoising: bool = True,
     graph=None,
     capture: Optional[dict] = None,
+    envelope_exponent: int = 5,
 ):
     """PaiNN.forward for the denoiser (painn_denoising.py:402-481).  ``sd`` is a reference
-    ``state_dict``.  ``tag_based_Z`` is a no-op in the reference (operator precedence,
+    ``state_dict``.  ``envelope_exponent``: p of the polynomial envelope (radial_basis.py:18-43; 5 in every shipped
+    configuration).  ``tag_based_Z`` is a no-op in the reference (operator precedence,
     :160-166) and is therefore absent here.  ``scale_factors[i]`` multiplies x after update
     layer i (:451); pass 1.0 for unfitted factors."""
     H = hidden_channels
@@ -258,7 +260,7 @@ def painn_forward(
     if graph is None:
         graph = generate_graph_values(pos, cell, natoms, cutoff, max_neighbors)
     edge_index, _, dist, unit_vec = graph
-    rbf = radial_basis(dist, cutoff, num_rbf)
+    rbf = radial_basis(dist, cutoff, num_rbf, envelope_exponent)
     x = sd["atom_emb.embeddings.weight"][z - 1]
     vec = torch.zeros(x.shape[0], 3, H, dtype=x.dtype)
     if scale_factors is None:

@@ -84,20 +84,21 @@ def radial_basis(d, cutoff, offset, p=5):
 
 
 def energy_forces(sd, pos, atomic_numbers, batch, num_systems, edge_src, edge_dst, offsets, *, hidden_channels, num_layers,
-                  num_rbf, cutoff, scale_factors, distance_floor=1.0e-6, **_):
-    """(energy [B], forces [N,3] = -d(energy.sum())/d(pos)) in float64.  ``sd``: state_dict of the S2EF PaiNN; messages
-    flow edge_src -> edge_dst; v = pos[src] - pos[dst] + offset (models/painn/painn.py:318-340, 380-414)."""
+                  num_rbf, cutoff, scale_factors, distance_floor=1.0e-6, envelope_exponent=5, dtype=torch.float64, **_):
+    """(energy [B], forces [N,3] = -d(energy.sum())/d(pos)) in ``dtype`` (float64: the oracle; float32: what the same
+    evaluation leaves in single precision).  ``sd``: state_dict of the S2EF PaiNN; messages flow edge_src -> edge_dst;
+    v = pos[src] - pos[dst] + offset (models/painn/painn.py:318-340, 380-414); ``envelope_exponent``: p of the envelope."""
     H = hidden_channels
-    sd = {k: v.double() for k, v in sd.items() if torch.is_floating_point(v)}
+    sd = {k: v.to(dtype) for k, v in sd.items() if torch.is_floating_point(v)}
     src, dst = edge_src.long(), edge_dst.long()
-    pos = pos.detach().double().clone().requires_grad_(True)
-    v = pos[src] - pos[dst] + offsets.double()
+    pos = pos.detach().to(dtype).clone().requires_grad_(True)
+    v = pos[src] - pos[dst] + offsets.to(dtype)
     d = v.norm(dim=-1)
     d = torch.where(d <= distance_floor, torch.full_like(d, distance_floor), d)
     u = v / d[:, None]
-    rbf = radial_basis(d, cutoff, sd["radial_basis.rbf.offset"])
+    rbf = radial_basis(d, cutoff, sd["radial_basis.rbf.offset"], envelope_exponent)
     x = sd["atom_emb.embeddings.weight"][atomic_numbers.long() - 1]
-    vec = torch.zeros(x.shape[0], 3, H, dtype=torch.float64)
+    vec = torch.zeros(x.shape[0], 3, H, dtype=dtype)
     edge_index = torch.stack([src, dst])
     for i in range(num_layers):
         dx, dvec = O.message_layer(sd, "message_layers.%d." % i, x, vec, edge_index, rbf, u, H)
@@ -108,7 +109,7 @@ def energy_forces(sd, pos, atomic_numbers, batch, num_systems, edge_src, edge_ds
         vec = vec + dvec
     per_atom = F.linear(O.ssilu(F.linear(x, sd["out_energy.0.weight"], sd["out_energy.0.bias"])),
                         sd["out_energy.2.weight"], sd["out_energy.2.bias"]).squeeze(1)
-    energy = torch.zeros(num_systems, dtype=torch.float64).index_add_(0, batch.long(), per_atom)
+    energy = torch.zeros(num_systems, dtype=dtype).index_add_(0, batch.long(), per_atom)
     (g,) = torch.autograd.grad(energy.sum(), pos)
     return energy.detach(), -g
 
