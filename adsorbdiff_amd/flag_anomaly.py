@@ -19,6 +19,7 @@ import torch
 
 from . import lib as _lib
 from .engine import batch_pbc, cell_repeats
+from .hostargs import desc, geometry, stream
 
 FLAG_NAMES = ("dissociated", "desorbed", "surface_changed", "intercalated")   # scripts/eval.py's order
 
@@ -57,23 +58,13 @@ def flag_anomalies(init_batch, final, final_slab_pos=None, radii=None, skin: flo
     ``final``: a batch, or an [N,3] tensor, aligned with ``init_batch``; ``final_slab_pos``: [N_slab,3] over the tag != 2
     atoms in batch order (the relaxed clean slab), default the initial positions."""
     table = default_radii() if radii is None else radii   # before the device check: a missing ase is reported first
-    pos0 = init_batch.pos
-    if not pos0.is_cuda:
-        raise RuntimeError("flag_anomalies runs on a ROCm device (no CPU fallback)")
+    g = geometry(init_batch, "flag_anomalies", Z=True, tags=True)
     lib = _lib.load()
-    dev = pos0.device
+    dev, B, pos0, Z, tags = g.dev, g.B, g.pos, g.Z, g.tags
     pos_final = final if torch.is_tensor(final) else final.pos
-    pos0 = pos0.detach().to(torch.float32).contiguous()
     pos_final = pos_final.detach().to(dev, torch.float32).contiguous()
     if pos_final.shape != pos0.shape:
         raise ValueError(f"final positions {tuple(pos_final.shape)} are not aligned with the batch {tuple(pos0.shape)}")
-    natoms = init_batch.natoms.to(dev, torch.int64).reshape(-1)
-    B, N = int(natoms.shape[0]), int(pos0.shape[0])
-    off = torch.zeros(B + 1, dtype=torch.int32, device=dev)
-    off[1:] = torch.cumsum(natoms, 0).to(torch.int32)
-    cell = init_batch.cell.to(dev, torch.float32).reshape(B, 3, 3).contiguous()
-    Z = init_batch.atomic_numbers.to(dev).long().to(torch.int32).contiguous()
-    tags = init_batch.tags.to(dev, torch.int32).contiguous()
     radii_t = _radii_tensor(table, dev)
     ref = None
     if final_slab_pos is not None:
@@ -83,17 +74,15 @@ def flag_anomalies(init_batch, final, final_slab_pos=None, radii=None, skin: flo
     r_max = float(radii_t[Z.long().clamp(0, radii_t.numel() - 1)].max())
     mult = max(1.0, float(surface_change_cutoff_multiplier), float(desorption_cutoff_multiplier))
     reach = mult * 2.0 * r_max + 2.0 * float(skin)
-    reps = cell_repeats(cell, max(reach, 0.0) + 0.01, batch_pbc(init_batch))
-    d = _lib.BatchDesc()
-    d.num_systems, d.num_atoms = B, N
-    d.pos, d.cell, d.atomic_numbers, d.batch, d.atom_offset = pos0.data_ptr(), cell.data_ptr(), Z.data_ptr(), None, off.data_ptr()
+    reps = cell_repeats(g.cell, max(reach, 0.0) + 0.01, batch_pbc(init_batch))
+    d = desc(pos0, g.cell, Z, g.atom_offset, B, g.N)
     d.reps[0], d.reps[1], d.reps[2] = reps
     flags = torch.empty(B, 4, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
         _lib.check(lib.adf_flag_anomalies(C.byref(d), pos_final.data_ptr(), None if ref is None else ref.data_ptr(),
                                           tags.data_ptr(), radii_t.data_ptr(), int(radii_t.numel()), C.c_float(skin),
                                           C.c_float(surface_change_cutoff_multiplier), C.c_float(desorption_cutoff_multiplier),
-                                          flags.data_ptr(), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+                                          flags.data_ptr(), stream(dev)))
     return flags != 0
 
 
@@ -191,8 +180,7 @@ def best_sites(energy: torch.Tensor, flags: Optional[torch.Tensor], group):
     n_valid = torch.empty(G, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
         _lib.check(lib.adf_select_best_sites(e.data_ptr(), None if f is None else f.data_ptr(), offsets.data_ptr(), G,
-                                             best.data_ptr(), best_e.data_ptr(), n_valid.data_ptr(),
-                                             C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+                                             best.data_ptr(), best_e.data_ptr(), n_valid.data_ptr(), stream(dev)))
     best = best.long()
     best = torch.where(best >= 0, perm[best.clamp(min=0)], best)   # sorted order -> the caller's order
     return best, best_e, n_valid.long()

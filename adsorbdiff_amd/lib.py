@@ -1,6 +1,10 @@
 """ctypes binding of libadsorbdiff_hip.so (the C ABI in include/adsorbdiff_hip.h).
 
-This is the stub a reference maintainer would add.  There is
+This is the stub a reference maintainer would add.  The header
+is the one description of the ABI: ``EXPORTS`` and every function's ``argtypes`` /
+``restype`` are parsed from its prototypes (``parse_header``), so a new entry point
+is declared there and nowhere else; only the struct mirrors and the status codes
+are repeated here, and tests/test_host_logic.py compares them with the header.  There is
 no fallback: if the library is missing or a call fails, an exception is
 raised — ``RuntimeError`` for out-of-memory / HIP errors (so that
 ``ml_diffuse``'s split-and-retry contract works, reference
@@ -12,6 +16,7 @@ not help).
 from __future__ import annotations
 
 import ctypes as C
+import re
 from pathlib import Path
 
 ADF_OK, ADF_EINVAL, ADF_EOOM, ADF_ENONEIGHBOR, ADF_EHIP, ADF_EOVERFLOW, ADF_ENUMERIC = 0, 1, 2, 3, 4, 5, 6
@@ -20,37 +25,6 @@ ADF_OK, ADF_EINVAL, ADF_EOOM, ADF_ENONEIGHBOR, ADF_EHIP, ADF_EOVERFLOW, ADF_ENUM
 class NumericRangeError(ArithmeticError):
     """Non-finite model output (ADF_ENUMERIC).  Not a RuntimeError on purpose: ``ml_diffuse`` must not answer it by
     splitting the batch; the engine answers it by re-running in exact f32."""
-
-EXPORTS = (
-    "adf_painn_create", "adf_painn_destroy", "adf_painn_set_weights", "adf_graph_build", "adf_graph_set_moving",
-    "adf_check_flags", "adf_painn_set_arithmetic", "adf_painn_set_incremental", "adf_painn_get_tune",
-    "adf_graph_export", "adf_painn_forward", "adf_painn_forward_subset", "adf_linear_forward", "adf_painn_message_layer", "adf_painn_update_layer",
-    "adf_painn_debug_row_maxima",
-    "adf_sde_init_placement", "adf_sde_step", "adf_sde_step_scheduled", "adf_sample", "adf_sample_traj",
-    "adf_tr_step", "adf_tr_sample", "adf_tr_sample_traj",
-    "adf_painn_set_per_system_stop", "adf_eqv2_set_per_system_stop", "adf_sampler_draws",
-    "adf_painn_set_energy_head", "adf_painn_set_distance_floor", "adf_painn_forward_energy",
-    "adf_painn_forward_energy_gradient", "adf_painn_energy_gradient_workspace",
-    "adf_lbfgs_create", "adf_lbfgs_destroy", "adf_lbfgs_reset", "adf_lbfgs_converge", "adf_lbfgs_step",
-    "adf_lbfgs_get_mask", "adf_lbfgs_last_step_max", "adf_lbfgs_set_per_system", "adf_lbfgs_get_step_state",
-    "adf_lbfgs_active_build", "adf_active_gather", "adf_active_scatter",
-    "adf_frames_create", "adf_frames_destroy", "adf_frames_push", "adf_frames_wait", "adf_frames_release", "adf_frames_pushed", "adf_frames_abort",
-    "adf_get_counters", "adf_profile_enable", "adf_profile_read", "adf_measure_peaks",
-    "adf_lift_adsorbates", "adf_flag_anomalies", "adf_select_best_sites",
-    "adf_site_pair_distances", "adf_unique_sites", "adf_select_top_sites",
-    "adf_slab_symmetry_scratch", "adf_slab_symmetry_search", "adf_slab_symmetry_emit", "adf_site_pair_distances_sym",
-    "adf_place_draws", "adf_place_adsorbates", "adf_place_site_candidates", "adf_interstitial_distances", "adf_surface_site_candidates", "adf_reduce_sites", "adf_surface_triangles", "adf_voronoi_coordination", "adf_bulk_coordination_min", "adf_tag_surface_atoms", "adf_comm_unique_id", "adf_comm_create", "adf_comm_destroy", "adf_allgather_sites",
-    "adf_op_linear_fwd", "adf_op_linear_bwd_scratch", "adf_op_linear_bwd", "adf_op_ssilu_fwd", "adf_op_ssilu_bwd", "adf_op_layernorm_fwd", "adf_op_layernorm_bwd", "adf_op_embed_fwd", "adf_op_embed_bwd", "adf_op_rbf", "adf_op_message_fwd", "adf_op_message_fwd_fused", "adf_op_message_bwd", "adf_op_message_bwd_fused", "adf_op_message_bwd_fused_supported", "adf_op_message_bwd_perm", "adf_op_edge_owner", "adf_op_rbf_image_bytes", "adf_op_rbf_image", "adf_op_rbf_wgrad_fused_scratch", "adf_op_rbf_wgrad_fused", "adf_op_vdot_fwd", "adf_op_vdot_bwd", "adf_op_update_out_fwd", "adf_op_update_out_bwd", "adf_op_vnorm_fwd", "adf_op_vnorm_bwd", "adf_op_gate_fwd", "adf_op_gate_bwd", "adf_op_copy_rows", "adf_op_score_loss", "adf_op_score_loss_tr", "adf_op_s2ef_loss", "adf_op_s2ef_loss_scratch", "adf_op_energy_sum", "adf_op_energy_head_bwd", "adf_op_energy_head_bwd_scratch", "adf_op_sqnorm_accumulate", "adf_op_adamw_step",
-    "adf_op_optimizer_chunk", "adf_op_grad_sqnorm_multi", "adf_op_adamw_multi", "adf_op_embed_bwd_ordered", "adf_op_embed_bwd_ordered_scratch",
-    "adf_noise_draws", "adf_noise_tr_so3", "adf_noise_com", "adf_igso3_score_norm",
-    "adf_eval_scratch", "adf_eval_s2ef", "adf_eval_is2rs", "adf_eval_is2re", "adf_eval_add",
-    "adf_eqv2_create", "adf_eqv2_destroy", "adf_eqv2_set_constants", "adf_eqv2_set_weights", "adf_eqv2_set_arithmetic",
-    "adf_eqv2_set_energy_embedding", "adf_eqv2_set_system_energy",
-    "adf_eqv2_set_weights_s2ef", "adf_eqv2_set_energy_head", "adf_eqv2_forward_energy", "adf_eqv2_radial_first_layer",
-    "adf_eqv2_set_edges", "adf_eqv2_set_moving", "adf_eqv2_set_incremental", "adf_eqv2_forward", "adf_eqv2_forward_subset", "adf_eqv2_check_flags", "adf_eqv2_init_placement",
-    "adf_eqv2_sde_step", "adf_eqv2_sample", "adf_eqv2_sample_traj", "adf_eqv2_tr_step", "adf_eqv2_tr_sample", "adf_eqv2_tr_sample_traj", "adf_eqv2_linear_forward", "adf_eqv2_get_counters", "adf_eqv2_profile_enable", "adf_eqv2_profile_read",
-    "adf_last_error", "adf_version",
-)
 
 
 class Hparams(C.Structure):
@@ -117,6 +91,62 @@ class Counters(C.Structure):
     ]
 
 
+# ---- the header is the one description of the ABI: every prototype in it is bound from its own text
+HEADER = Path(__file__).resolve().parent.parent / "include" / "adsorbdiff_hip.h"
+
+_SCALARS = {"int32_t": C.c_int32, "int64_t": C.c_int64, "float": C.c_float, "double": C.c_double}
+_RETURNS = {"int32_t": C.c_int32, "int64_t": C.c_int64, "const char*": C.c_char_p}
+# the structs that are always host structs handed over with byref(); adf_step_coef / adf_tr_coef are also device tables
+# passed as data_ptr(), so a pointer to one is a plain address
+_BYREF = {"adf_batch": BatchDesc, "adf_painn_hparams": Hparams, "adf_eqv2_hparams": EqV2Hparams, "adf_tune": Tune,
+          "adf_counters": Counters, "adf_eqv2_counters": EqV2Counters, "adf_active_field": ActiveField}
+
+
+def parse_header(text: str) -> dict:
+    """``{name: (restype, argtypes)}`` for every function the header text declares, in its order.  Whatever is no
+    comment, preprocessor line, enum, struct or handle typedef has to be a prototype in the vocabulary above: anything else
+    raises ``ValueError`` naming the function and the type, so that an entry is bound correctly or not at all."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
+    structs = set(re.findall(r"typedef\s+struct\s*\w*\s*\{[^}]*\}\s*(\w+)\s*;", text))
+    text = re.sub(r"(typedef\s+struct|enum)\s*\w*\s*\{[^}]*\}\s*\w*\s*;", " ", text)
+    handles = set(re.findall(r"typedef\s+struct\s+\w+\s*\*\s*(adf_\w+_t)\s*;", text))
+    text = re.sub(r"typedef\s+struct\s+\w+\s*\*\s*adf_\w+_t\s*;|extern\s+\"C\"\s*\{|\}", " ", text)
+    pointees = set(_SCALARS) | structs | handles | {"void", "char", "uint8_t"}
+
+    def argtype(fn: str, param: str):
+        tokens = [t for t in re.findall(r"\w+|\*|\S", param) if t != "const"]
+        base, stars, name = tokens[:1], tokens[1:-1], tokens[-1:]
+        if len(tokens) < 2 or any(t != "*" for t in stars) or not re.fullmatch(r"[A-Za-z_]\w*", name[0]) or name[0] in pointees:
+            raise ValueError(f"{fn}: parameter {param.strip()!r} is not `type name`")
+        base = base[0]
+        if stars:
+            if base not in pointees:
+                raise ValueError(f"{fn}: parameter {param.strip()!r} points to the unknown type {base!r}")
+            return C.POINTER(_BYREF[base]) if base in _BYREF and len(stars) == 1 else C.c_void_p
+        if base in handles:
+            return C.c_void_p
+        if base not in _SCALARS:
+            raise ValueError(f"{fn}: parameter {param.strip()!r} has the unknown type {base!r}")
+        return _SCALARS[base]
+
+    out = {}
+    for stmt in filter(None, (s.strip() for s in text.split(";"))):
+        m = re.fullmatch(r"(.*?)\b(adf_[a-z_0-9]+)\s*\((.*)\)", stmt, flags=re.S)
+        if m is None:
+            raise ValueError(f"not a prototype, an enum, a struct or a handle typedef: {' '.join(stmt.split())!r}")
+        ret, fn, params = re.sub(r"\s*\*\s*", "*", " ".join(m.group(1).split())), m.group(2), m.group(3).strip()
+        if ret not in _RETURNS:
+            raise ValueError(f"{fn}: unknown return type {ret!r}")
+        if fn in out:
+            raise ValueError(f"{fn}: declared twice")
+        out[fn] = (_RETURNS[ret], [] if params == "void" else [argtype(fn, p) for p in params.split(",")])
+    return out
+
+
+SIGNATURES = parse_header(HEADER.read_text())
+EXPORTS = tuple(SIGNATURES)
+
 _LIB = None
 
 
@@ -130,7 +160,7 @@ def lib_path() -> Path:
 
 
 def load():
-    """Load the shared library (once).  Raises if it has not been built."""
+    """Load the shared library (once) and bind every function of the header.  Raises if it has not been built."""
     global _LIB
     if _LIB is not None:
         return _LIB
@@ -141,190 +171,9 @@ def load():
             "(the HIP path has no CPU fallback)"
         )
     lib = C.CDLL(str(path))
-    vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
-    lib.adf_last_error.restype = C.c_char_p
-    lib.adf_version.restype = C.c_char_p
-    sigs = {
-        "adf_painn_create": [C.POINTER(Hparams), C.POINTER(vp)],
-        "adf_painn_destroy": [vp],
-        "adf_painn_set_weights": [vp, i32, C.POINTER(vp), C.POINTER(C.c_float), vp],
-        "adf_graph_build": [vp, C.POINTER(BatchDesc), vp, C.POINTER(i64)],
-        "adf_graph_set_moving": [vp, vp, vp, vp],
-        "adf_check_flags": [vp, vp],
-        "adf_painn_set_arithmetic": [vp, i32],
-        "adf_painn_set_incremental": [vp, i32],
-        "adf_painn_get_tune": [vp, C.POINTER(Tune)],
-        "adf_graph_export": [vp, vp, vp, vp, i64, vp, vp, vp, vp, C.POINTER(i64), vp],
-        "adf_painn_forward": [vp, C.POINTER(BatchDesc), vp, vp, vp],
-        "adf_painn_forward_subset": [vp, C.POINTER(BatchDesc), vp, i32, vp, vp, vp],
-        "adf_painn_message_layer": [vp, i32, i32, vp, vp, vp, vp, vp],
-        "adf_linear_forward": [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
-        "adf_painn_update_layer": [vp, i32, i32, vp, vp, vp],
-        "adf_painn_debug_row_maxima": [vp, i32, vp, C.c_int64, C.POINTER(i32), vp],
-        "adf_sde_init_placement": [vp, C.POINTER(BatchDesc), vp, vp, vp, vp],
-        "adf_sde_step": [vp, C.POINTER(BatchDesc), vp, vp, vp, vp, vp, C.POINTER(StepCoef), vp, vp, i32, vp, vp, vp, vp],
-        "adf_sde_step_scheduled": [vp, C.POINTER(BatchDesc), vp, vp, vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp],
-        "adf_tr_step": [vp, C.POINTER(BatchDesc), vp, vp, vp, C.POINTER(TrCoef), vp, i32, vp, i32, vp, vp, vp],
-        "adf_tr_sample": [vp, C.POINTER(BatchDesc), vp, vp, vp, i32, vp, i32, i32, vp, vp, i32, vp, vp],
-        "adf_tr_sample_traj": [vp, C.POINTER(BatchDesc), vp, vp, vp, i32, vp, i32, i32, vp, vp, i32, vp, vp, i32, vp],
-        "adf_eqv2_tr_step": [vp, C.POINTER(BatchDesc), vp, vp, vp, C.POINTER(TrCoef), vp, i32, vp, i32, vp, vp, vp],
-        "adf_eqv2_tr_sample": [vp, C.POINTER(BatchDesc), vp, vp, vp, i32, vp, i32, i32, vp, vp, i32, vp, vp],
-        "adf_eqv2_tr_sample_traj": [vp, C.POINTER(BatchDesc), vp, vp, vp, i32, vp, i32, i32, vp, vp, i32, vp, vp, i32, vp],
-        "adf_painn_set_energy_head": [vp, i32, C.POINTER(vp), vp],
-        "adf_painn_set_distance_floor": [vp, C.c_float],
-        "adf_painn_forward_energy": [vp, C.POINTER(BatchDesc), vp, vp, vp],
-        "adf_painn_forward_energy_gradient": [vp, C.POINTER(BatchDesc), vp, vp, vp],
-        "adf_painn_energy_gradient_workspace": [vp, i64, C.POINTER(i64)],
-        "adf_lbfgs_create": [i64, i32, i32, C.c_double, C.c_double, C.c_double, i32, C.POINTER(vp)],
-        "adf_lbfgs_destroy": [vp],
-        "adf_lbfgs_reset": [vp, vp],
-        "adf_lbfgs_converge": [vp, vp, vp, C.c_double, vp, vp, vp],
-        "adf_lbfgs_step": [vp, vp, vp, vp, i64, vp],
-        "adf_lbfgs_get_mask": [vp, vp, vp],
-        "adf_lbfgs_last_step_max": [vp, vp, vp],
-        "adf_lbfgs_set_per_system": [vp, i32],
-        "adf_lbfgs_get_step_state": [vp, vp, vp, vp],
-        "adf_lbfgs_active_build": [vp, vp, vp, vp, vp, vp],
-        "adf_active_gather": [vp, vp, vp, vp, i32, i64, C.POINTER(ActiveField), i32, vp, vp, vp],
-        "adf_active_scatter": [vp, vp, vp, vp, i32, i64, vp, vp, i32, vp, vp, vp, vp, vp],
-        "adf_get_counters": [vp, C.POINTER(Counters), vp],
-        "adf_profile_enable": [vp, i32],
-        "adf_profile_read": [vp, C.POINTER(C.c_float), C.POINTER(i64), C.POINTER(i64), vp],
-        "adf_measure_peaks": [C.POINTER(C.c_float), vp],
-        "adf_lift_adsorbates": [vp, vp, vp, i32, C.c_float, vp, vp],
-        "adf_flag_anomalies": [C.POINTER(BatchDesc), vp, vp, vp, vp, i32, C.c_float, C.c_float, C.c_float, vp, vp],
-        "adf_select_best_sites": [vp, vp, vp, i32, vp, vp, vp, vp],
-        "adf_site_pair_distances": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i64, i32, i32, vp, vp],
-        "adf_unique_sites": [vp, vp, vp, i32, i32, i64, vp, vp, C.c_float, C.c_float, vp, vp, vp],
-        "adf_select_top_sites": [vp, vp, vp, vp, i32, i32, vp, vp, vp],
-        "adf_slab_symmetry_search": [vp, vp, vp, vp, i32, i32, C.c_double, i32, vp, vp, vp, vp],
-        "adf_slab_symmetry_emit": [vp, i32, i32, C.c_double, vp, vp, vp, i32, i64, vp, vp, vp, vp, vp],
-        "adf_site_pair_distances_sym": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i64, i32, i32, vp, vp, vp, vp, vp, i32, i64,
-                                        vp, vp, vp],
-        "adf_place_draws": [i64, vp, vp, i32, vp, vp],
-        "adf_place_adsorbates": [C.POINTER(BatchDesc), vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, C.c_float, i32, vp, vp, i32,
-                                 vp, i64, vp, vp, vp, vp, vp],
-        "adf_place_site_candidates": [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp],
-        "adf_interstitial_distances": [C.POINTER(BatchDesc), vp, vp, i32, vp, i32, vp, vp, vp],
-        "adf_surface_site_candidates": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp],
-        "adf_reduce_sites": [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, i32, C.c_double, vp, vp, vp, vp, vp],
-        "adf_surface_triangles": [vp, vp, vp, vp, i32, i32, C.c_double, i32, vp, vp, vp, vp],
-        "adf_voronoi_coordination": [vp, vp, vp, vp, i32, i32, vp, C.c_double, C.c_double, C.c_double, vp, vp, vp, vp, vp],
-        "adf_bulk_coordination_min": [vp, vp, vp, vp, i32, i32, vp, vp],
-        "adf_tag_surface_atoms": [vp, vp, vp, vp, vp, i32, i32, vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
-                                  vp, vp, vp, vp],
-        "adf_comm_unique_id": [vp],
-        "adf_comm_create": [vp, i32, i32, C.POINTER(vp)],
-        "adf_comm_destroy": [vp],
-        "adf_allgather_sites": [vp, vp, i64, vp, vp],
-        "adf_op_linear_fwd": [vp, i32, vp, vp, vp, i32, i64, i32, i32, vp],
-        "adf_op_linear_bwd": [vp, i32, vp, vp, i32, vp, i32, i32, vp, vp, i32, i64, i32, i32, vp, vp],
-        "adf_op_ssilu_fwd": [vp, vp, i64, vp],
-        "adf_op_ssilu_bwd": [vp, vp, vp, i64, vp],
-        "adf_op_layernorm_fwd": [vp, vp, vp, vp, vp, i32, i32, vp],
-        "adf_op_layernorm_bwd": [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp],
-        "adf_op_embed_fwd": [vp, vp, i32, vp, vp],
-        "adf_op_embed_bwd": [vp, vp, vp, i32, i32, vp],
-        "adf_op_rbf": [vp, vp, vp],
-        "adf_op_message_fwd": [vp, vp, vp, vp, vp, vp, vp, i32, vp],
-        "adf_op_message_fwd_fused": [vp, i32, vp, vp, vp, vp, vp, i32, vp],
-        "adf_op_message_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp],
-        "adf_op_message_bwd_fused": [vp, i32, vp, vp, vp, vp, vp, vp, C.c_int64, vp, vp, i32, vp, vp],
-        "adf_op_edge_owner": [vp, vp, C.c_int64, vp],
-        "adf_op_rbf_image": [vp, vp, C.c_int64, vp, vp],
-        "adf_op_rbf_wgrad_fused": [vp, vp, vp, vp, vp, C.c_int64, vp, vp, i32, vp],
-        "adf_op_message_bwd_fused_supported": [vp],
-        "adf_op_message_bwd_perm": [vp, vp, i32],
-        "adf_op_vdot_fwd": [vp, vp, vp, i32, i64, i32, C.c_float, vp],
-        "adf_op_vdot_bwd": [vp, vp, i32, vp, vp, i32, vp, vp, i64, i32, vp],
-        "adf_op_update_out_fwd": [vp, vp, vp, vp, vp, C.c_float, vp, vp, i64, i32, vp],
-        "adf_op_update_out_bwd": [vp, vp, vp, C.c_float, vp, vp, vp, vp, vp, vp, vp, i64, i32, vp],
-        "adf_op_vnorm_fwd": [vp, vp, i32, i64, i32, vp],
-        "adf_op_vnorm_bwd": [vp, vp, i32, vp, i32, vp, i64, i32, vp],
-        "adf_op_gate_fwd": [vp, vp, vp, i32, vp, i64, i32, vp],
-        "adf_op_gate_bwd": [vp, vp, vp, i32, vp, vp, vp, i64, i32, vp],
-        "adf_op_copy_rows": [vp, i32, vp, i32, i64, i32, i32, vp],
-        "adf_op_score_loss": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp],
-        "adf_op_score_loss_tr": [vp, vp, vp, vp, vp, vp, vp, i32, vp, vp],
-        "adf_noise_draws": [i64, i32, vp, i32, vp, vp],
-        "adf_sampler_draws": [i64, vp, vp, i32, i32, vp, vp, vp, vp],
-        "adf_painn_set_per_system_stop": [vp, vp, i32],
-        "adf_eqv2_set_per_system_stop": [vp, vp, i32],
-        "adf_noise_tr_so3": [vp, vp, vp, vp, i32, i32, vp, C.c_float, C.c_float, C.c_float, C.c_float, vp, vp, vp, vp, i32, i32,
-                             vp, vp, vp, vp, vp, vp, vp, vp],
-        "adf_noise_com": [vp, vp, vp, vp, i32, i32, vp, C.c_float, C.c_float, vp, vp, vp, vp, vp],
-        "adf_igso3_score_norm": [vp, vp, i32, i32, vp, vp],
-        "adf_op_s2ef_loss": [vp, vp, vp, vp, vp, vp, i32, i32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
-                             vp, vp, vp, vp, vp, vp, vp],
-        "adf_op_energy_sum": [vp, i32, vp, vp, vp, vp, i32, vp],
-        "adf_op_energy_head_bwd": [vp, vp, vp, vp, vp, vp, vp, i32, i64, i32, vp, vp],
-        "adf_op_sqnorm_accumulate": [vp, i64, vp, vp],
-        "adf_op_adamw_step": [vp, vp, vp, vp, vp, i64, vp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, i32, C.c_float, vp],
-        "adf_op_grad_sqnorm_multi": [vp, vp, i32, vp, vp, C.c_float, C.c_double, C.c_double, C.c_float, i64, vp],
-        "adf_op_adamw_multi": [vp, vp, i32, vp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, vp],
-        "adf_op_embed_bwd_ordered": [vp, vp, vp, i32, i32, i32, vp, vp],
-        "adf_eval_s2ef": [vp, vp, vp, vp, vp, vp, i32, i32, i32, C.c_float, C.c_float, C.c_float, C.c_float, vp, vp, vp, vp],
-        "adf_eval_is2rs": [vp, vp, vp, vp, vp, i32, i32, vp, i32, vp, vp, vp, vp],
-        "adf_eval_is2re": [vp, vp, i32, vp, vp, vp],
-        "adf_eval_add": [vp, i32, vp, vp, vp],
-        "adf_eqv2_create": [C.POINTER(EqV2Hparams), C.POINTER(vp)],
-        "adf_eqv2_destroy": [vp],
-        "adf_eqv2_set_constants": [vp, vp, vp, vp, vp, vp],
-        "adf_eqv2_set_weights": [vp, i32, C.POINTER(vp), vp],
-        "adf_eqv2_set_arithmetic": [vp, i32],
-        "adf_eqv2_set_weights_s2ef": [vp, i32, C.POINTER(vp), vp],
-        "adf_eqv2_set_energy_head": [vp, i32, C.POINTER(vp), C.c_float, vp, vp],
-        "adf_eqv2_forward_energy": [vp, C.POINTER(BatchDesc), vp, vp, vp, vp],
-        "adf_eqv2_radial_first_layer": [vp, i32, i64, vp, vp, vp, vp, vp, vp],
-        "adf_eqv2_set_energy_embedding": [vp, vp, vp, vp],
-        "adf_eqv2_set_system_energy": [vp, vp, i32, vp],
-        "adf_eqv2_set_edges": [vp, i64, vp, vp, vp, i32, vp],
-        "adf_eqv2_set_moving": [vp, vp, vp, vp],
-        "adf_eqv2_set_incremental": [vp, i32],
-        "adf_eqv2_forward": [vp, C.POINTER(BatchDesc), vp, vp, vp, vp],
-        "adf_eqv2_forward_subset": [vp, C.POINTER(BatchDesc), vp, i32, vp, vp, vp],
-        "adf_eqv2_check_flags": [vp, vp],
-        "adf_eqv2_init_placement": [vp, C.POINTER(BatchDesc), vp, vp, vp, vp],
-        "adf_eqv2_sde_step": [vp, C.POINTER(BatchDesc), vp, vp, vp, vp, vp, C.POINTER(StepCoef), vp, i32, vp, vp, i32, vp, vp, vp, vp],
-        "adf_eqv2_sample": [vp, C.POINTER(BatchDesc), vp, vp, vp, vp, i32, vp, vp, i32, i32, vp, vp, i32, vp, vp, vp],
-        "adf_eqv2_get_counters": [vp, C.POINTER(EqV2Counters), vp],
-        "adf_eqv2_linear_forward": [vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, vp],
-        "adf_eqv2_profile_enable": [vp, i32],
-        "adf_eqv2_profile_read": [vp, C.POINTER(C.c_float), C.POINTER(i64), vp],
-        "adf_sample": [vp, C.POINTER(BatchDesc), vp, vp, vp, vp, i32, vp, vp, i32, i32, vp, vp, i32, vp, vp, vp],
-        "adf_sample_traj": [vp, C.POINTER(BatchDesc), vp, vp, vp, vp, i32, vp, vp, i32, i32, vp, vp, i32, vp, vp, vp, i32, vp],
-        "adf_eqv2_sample_traj": [vp, C.POINTER(BatchDesc), vp, vp, vp, vp, i32, vp, vp, i32, i32, vp, vp, i32, vp, vp, vp, i32, vp],
-        "adf_frames_create": [i32, i64, i32, C.POINTER(vp)],
-        "adf_frames_destroy": [vp],
-        "adf_frames_push": [vp, vp, vp],
-        "adf_frames_wait": [vp, i64, i32, C.POINTER(C.POINTER(C.c_float))],
-        "adf_frames_release": [vp, i64],
-        "adf_frames_abort": [vp],
-    }
-    for name, argtypes in sigs.items():
+    for name, (restype, argtypes) in SIGNATURES.items():
         fn = getattr(lib, name)
-        fn.argtypes = argtypes
-        fn.restype = i32
-    lib.adf_op_linear_bwd_scratch.argtypes = [i64, i32, i32]
-    lib.adf_op_linear_bwd_scratch.restype = i64
-    lib.adf_op_rbf_image_bytes.argtypes = [i64]
-    lib.adf_op_rbf_image_bytes.restype = i64
-    lib.adf_op_rbf_wgrad_fused_scratch.argtypes = [vp]
-    lib.adf_op_rbf_wgrad_fused_scratch.restype = i64
-    lib.adf_op_s2ef_loss_scratch.argtypes = [i32]
-    lib.adf_op_s2ef_loss_scratch.restype = i64
-    lib.adf_op_energy_head_bwd_scratch.argtypes = [i64, i32]
-    lib.adf_op_energy_head_bwd_scratch.restype = i64
-    lib.adf_op_optimizer_chunk.argtypes = []
-    lib.adf_op_optimizer_chunk.restype = i64
-    lib.adf_op_embed_bwd_ordered_scratch.argtypes = [i64, i32, i32]
-    lib.adf_op_embed_bwd_ordered_scratch.restype = i64
-    lib.adf_slab_symmetry_scratch.argtypes = [i32, i32]
-    lib.adf_slab_symmetry_scratch.restype = i64
-    lib.adf_eval_scratch.argtypes = [i32]
-    lib.adf_eval_scratch.restype = i64
-    lib.adf_frames_pushed.argtypes = [vp]
-    lib.adf_frames_pushed.restype = i64
+        fn.restype, fn.argtypes = restype, argtypes
     _LIB = lib
     return lib
 

@@ -42,6 +42,7 @@ import torch
 
 from . import lib as _lib
 from .data import Batch
+from .hostargs import desc, geometry, i32, offsets, pbc_rows, stream
 from .noising import noise_keys
 from .slab_symmetry import SlabSymmetry, find_symmetry
 
@@ -75,40 +76,6 @@ def _table(values, device, what) -> torch.Tensor:
     if t.numel() == 0:
         raise ValueError(f"placement: empty {what} table")
     return t
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
-def _i32(t, dev) -> torch.Tensor:
-    return torch.as_tensor(t).to(dev).long().to(torch.int32).contiguous()
-
-
-def _pbc_rows(batch, B: int, dev) -> torch.Tensor:
-    """int32 [B,3]: ``batch.pbc`` per system, all periodic without one (the project's default, engine.batch_pbc)."""
-    pbc = getattr(batch, "pbc", None)
-    if pbc is None:
-        return torch.ones(B, 3, dtype=torch.int32, device=dev)
-    pbc = torch.atleast_2d(torch.as_tensor(pbc)).to(dev)
-    if pbc.shape[0] == 1 and B > 1:
-        pbc = pbc.expand(B, 3)
-    if tuple(pbc.shape) != (B, 3):
-        raise ValueError(f"batch.pbc: [{B}, 3] expected, got {list(pbc.shape)}")
-    return (pbc != 0).to(torch.int32).contiguous()
-
-
-def _desc(pos, cell, Z, off, B, N):
-    d = _lib.BatchDesc()
-    d.num_systems, d.num_atoms = B, N
-    d.pos, d.cell, d.atomic_numbers, d.batch, d.atom_offset = pos.data_ptr(), cell.data_ptr(), Z.data_ptr(), None, off.data_ptr()
-    return d
-
-
-def _offsets(counts: torch.Tensor) -> torch.Tensor:
-    off = torch.zeros(int(counts.numel()) + 1, dtype=torch.int32, device=counts.device)
-    off[1:] = torch.cumsum(counts.long(), 0).to(torch.int32)
-    return off
 
 
 # ------------------------------------------------------------------------------------------------ surface triangles (host: scipy)
@@ -185,24 +152,17 @@ def surface_triangles_device(slab_batch, circle_tol: float = 1e-4) -> SurfaceTri
         raise ValueError(f"circle_tol = {circle_tol}: finite and not negative expected")
     if getattr(slab_batch, "tags", None) is None:
         raise ValueError("slab_batch.tags is required (tag 1 marks the surface)")
-    if not slab_batch.pos.is_cuda:
-        raise RuntimeError("surface_triangles_device runs on a ROCm device (the HIP path has no CPU fallback)")
+    g = geometry(slab_batch, "surface_triangles_device", tags=True)
     lib = _lib.load()
-    dev = slab_batch.pos.device
-    B = int(slab_batch.natoms.numel())
-    pos = slab_batch.pos.detach().to(torch.float32).contiguous()
-    N = int(pos.shape[0])
-    tags = _i32(slab_batch.tags, dev)
-    atom_off = _offsets(slab_batch.natoms.to(dev, torch.int64).reshape(-1))
-    cell = slab_batch.cell.to(dev, torch.float32).reshape(B, 9).contiguous()
+    dev, B, N = g.dev, g.B, g.N
     rows = max(18 * N, 1)                                          # always enough: fewer than 2 * 9 n_top triangles per slab
     tri = torch.empty(rows, 3, 3, dtype=torch.float32, device=dev)
     index = torch.empty(rows, 3, dtype=torch.int32, device=dev)
     tri_off = torch.zeros(B + 1, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        _lib.check(lib.adf_surface_triangles(pos.data_ptr(), tags.data_ptr(), atom_off.data_ptr(), cell.data_ptr(), N, B,
-                                             C.c_double(circle_tol), rows, tri_off.data_ptr(), tri.data_ptr(),
-                                             index.data_ptr(), _stream(dev)))
+        _lib.check(lib.adf_surface_triangles(g.pos.data_ptr(), g.tags.data_ptr(), g.atom_offset.data_ptr(), g.cell.data_ptr(),
+                                             N, B, C.c_double(circle_tol), rows, tri_off.data_ptr(), tri.data_ptr(),
+                                             index.data_ptr(), stream(dev)))
     bounds = tri_off.tolist()                                      # the one host read
     return SurfaceTriangles(tri[:bounds[-1]], tri_off, index[:bounds[-1]], [b1 - b0 for b0, b1 in zip(bounds, bounds[1:])])
 
@@ -312,7 +272,7 @@ def _reduce(lib, dev, slab_batch, B, cand, valid, seg_off, seg_slab, G, symmetry
     with torch.cuda.device(dev):
         _lib.check(lib.adf_reduce_sites(cand.data_ptr(), ptr(valid), seg_off.data_ptr(), ptr(seg_slab), cell.data_ptr(),
                                         C_rows, G, B, ptr(op_off), ptr(rot), ptr(trans), K, C.c_double(tol),
-                                        first.data_ptr(), rep.data_ptr(), mult.data_ptr(), counts.data_ptr(), _stream(dev)))
+                                        first.data_ptr(), rep.data_ptr(), mult.data_ptr(), counts.data_ptr(), stream(dev)))
     return first, rep, mult, counts
 
 
@@ -335,17 +295,10 @@ def heuristic_sites(slab_batch, triangles=None, symmetry="auto", tol: float = 0.
     if getattr(slab_batch, "tags", None) is None:
         raise ValueError("slab_batch.tags is required (tag 1 marks the surface)")
     triangles, tri_off, T = _triangle_tables(slab_batch, triangles, B, slab_batch.pos.device)
-    if not slab_batch.pos.is_cuda:
-        raise RuntimeError("heuristic_sites runs on a ROCm device (the HIP path has no CPU fallback)")
+    g = geometry(slab_batch, "heuristic_sites", tags=True)
     lib = _lib.load()
-    dev = slab_batch.pos.device
+    dev, N, natoms = g.dev, g.N, g.natoms
     Ttot = sum(T)
-    pos = slab_batch.pos.detach().to(torch.float32).contiguous()
-    N = int(pos.shape[0])
-    tags = _i32(slab_batch.tags, dev)
-    natoms = slab_batch.natoms.to(dev, torch.int64).reshape(-1)
-    atom_off = _offsets(natoms)
-    cell = slab_batch.cell.to(dev, torch.float32).reshape(B, 9).contiguous()
     if tri_off is None:                                           # host tables: packed and uploaded
         tri = torch.from_numpy(np.concatenate(triangles).astype(np.float32) if Ttot else np.zeros((1, 3, 3), np.float32))
         tri = tri.to(dev).contiguous()
@@ -357,9 +310,9 @@ def heuristic_sites(slab_batch, triangles=None, symmetry="auto", tol: float = 0.
     cand = torch.zeros(rows, 3, dtype=torch.float32, device=dev)
     valid = torch.zeros(rows, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        _lib.check(lib.adf_surface_site_candidates(pos.data_ptr(), tags.data_ptr(), atom_off.data_ptr(), cell.data_ptr(),
-                                                   tri.data_ptr(), tri_off.data_ptr(), N, Ttot, B, rows, seg_off.data_ptr(),
-                                                   cand.data_ptr(), valid.data_ptr(), _stream(dev)))
+        _lib.check(lib.adf_surface_site_candidates(g.pos.data_ptr(), g.tags.data_ptr(), g.atom_offset.data_ptr(),
+                                                   g.cell.data_ptr(), tri.data_ptr(), tri_off.data_ptr(), N, Ttot, B, rows,
+                                                   seg_off.data_ptr(), cand.data_ptr(), valid.data_ptr(), stream(dev)))
     seg_slab = torch.repeat_interleave(torch.arange(B, dtype=torch.int32, device=dev), 3, output_size=3 * B).contiguous()
     first, rep, mult, seg_counts = _reduce(lib, dev, slab_batch, B, cand, valid, seg_off, seg_slab, 3 * B, symmetry, tol)
     wanted = torch.tensor([k in positions for k in SITE_KINDS], device=dev)
@@ -399,7 +352,7 @@ class AdsorbatePlacer:
         if keys.dtype != torch.int64:
             raise ValueError(f"keys: int64 expected, got {keys.dtype}")
         keys = keys.to(self.dev).contiguous()
-        index = _i32(index, self.dev).reshape(-1)
+        index = i32(index, self.dev).reshape(-1)
         n = int(keys.numel())
         if int(index.numel()) != n:
             raise ValueError(f"{n} keys, {int(index.numel())} indices")
@@ -407,7 +360,7 @@ class AdsorbatePlacer:
         seed = self.seed & 0xFFFFFFFFFFFFFFFF
         seed = seed - (1 << 64) if seed >= (1 << 63) else seed
         with torch.cuda.device(self.dev):
-            _lib.check(self.lib.adf_place_draws(seed, keys.data_ptr(), index.data_ptr(), n, out.data_ptr(), _stream(self.dev)))
+            _lib.check(self.lib.adf_place_draws(seed, keys.data_ptr(), index.data_ptr(), n, out.data_ptr(), stream(self.dev)))
         return out
 
     def _draw_table(self, draws, n: int) -> torch.Tensor:
@@ -445,7 +398,7 @@ class AdsorbatePlacer:
             tri = triangles
         per_t = torch.tensor(per, dtype=torch.int32, device=dev)
         cand_counts = torch.tensor(n_cand, dtype=torch.int64, device=dev)
-        cand_off = _offsets(cand_counts)
+        cand_off = offsets(cand_counts)
         cand_slab = torch.repeat_interleave(torch.arange(B, device=dev), cand_counts, output_size=Ctot)
         local = torch.arange(Ctot, device=dev) - cand_off.long()[cand_slab]
         if draws is None:
@@ -459,7 +412,7 @@ class AdsorbatePlacer:
             _lib.check(self.lib.adf_place_site_candidates(tri.data_ptr(), tri_off.data_ptr(), per_t.data_ptr(),
                                                           cand_off.data_ptr(), slab32.data_ptr(), cell.data_ptr(),
                                                           draws.data_ptr(), B, Ctot, cand.data_ptr(), keep.data_ptr(),
-                                                          _stream(dev)))
+                                                          stream(dev)))
         keep = keep != 0
         # order: slab, kept first, selection key, candidate index (two stable sorts)
         by_key = torch.sort(draws[:, 2], stable=True).indices
@@ -580,11 +533,11 @@ class AdsorbatePlacer:
         adsZ32 = adsZ_t.to(torch.int32).contiguous()
         adsP_t = torch.from_numpy(np.concatenate(ads_P).astype(np.float32)).to(dev).contiguous()
         n_ads_t = torch.tensor(n_ads, dtype=torch.int64, device=dev)
-        ads_off = _offsets(n_ads_t)
+        ads_off = offsets(n_ads_t)
         # placements
         slab_of = torch.repeat_interleave(st.slab, n_aug, output_size=P)
         site = torch.repeat_interleave(st.pos, n_aug, dim=0, output_size=P).contiguous()
-        site_off = _offsets(torch.tensor(st.counts, dtype=torch.int64, device=dev)).long() * n_aug
+        site_off = offsets(torch.tensor(st.counts, dtype=torch.int64, device=dev)).long() * n_aug
         local = torch.arange(P, device=dev) - site_off[slab_of]
         if draws is None:
             draws = self.draws(noise_keys(slab_batch).to(dev)[slab_of], local)
@@ -601,17 +554,17 @@ class AdsorbatePlacer:
             n_b = torch.tensor([len(x) for x in binding_indices], dtype=torch.int64, device=dev)
             flat = torch.tensor([int(i) for x in binding_indices for i in x], dtype=torch.int32, device=dev)
             pick = torch.minimum((draws[:, 6] * n_b[slab_of].double()).floor().long(), n_b[slab_of] - 1)
-            bind = flat[_offsets(n_b).long()[slab_of] + pick].contiguous()
+            bind = flat[offsets(n_b).long()[slab_of] + pick].contiguous()
         # the collated output: slab rows gathered, adsorbate rows written by the kernel
         n_slab_t = torch.tensor(st.slab_natoms, dtype=torch.int64, device=dev)
         natoms_p = (n_slab_t + n_ads_t)[slab_of]
         N = sum(c * n_aug * (ns + na) for c, ns, na in zip(st.counts, st.slab_natoms, n_ads))
-        off_p = _offsets(natoms_p).long()
+        off_p = offsets(natoms_p).long()
         batch_idx = torch.repeat_interleave(torch.arange(P, device=dev), natoms_p, output_size=N)
         loc = torch.arange(N, device=dev) - off_p[batch_idx]
         sys_slab = slab_of[batch_idx]
         is_slab = loc < n_slab_t[sys_slab]
-        slab_off = _offsets(n_slab_t)
+        slab_off = offsets(n_slab_t)
         src = torch.where(is_slab, slab_off.long()[sys_slab] + loc, torch.zeros_like(loc))
         asrc = torch.where(is_slab, torch.zeros_like(loc), ads_off.long()[sys_slab] + loc - n_slab_t[sys_slab])
         slab_pos = slab_batch.pos.detach().to(dev, torch.float32).contiguous()
@@ -622,9 +575,9 @@ class AdsorbatePlacer:
         pos = slab_pos[src].contiguous() if Nslab else torch.zeros(N, 3, dtype=torch.float32, device=dev)
         out_row = (off_p[:P] + n_slab_t[slab_of]).to(torch.int32).contiguous()
         cell = slab_batch.cell.to(dev, torch.float32).reshape(B, 9).contiguous()
-        slabZ32 = slab_Z.long().to(torch.int32).contiguous()
-        d = _desc(slab_pos, cell, slabZ32, slab_off, B, Nslab)
-        pbc = _pbc_rows(slab_batch, B, dev)
+        slabZ32 = i32(slab_Z, dev)
+        d = desc(slab_pos, cell, slabZ32, slab_off, B, Nslab)
+        pbc = pbc_rows(slab_batch, B, dev)
         slab32 = slab_of.to(torch.int32).contiguous()
         sn = torch.empty(P, dtype=torch.float64, device=dev)
         nc = torch.empty(P, dtype=torch.int32, device=dev)
@@ -635,7 +588,7 @@ class AdsorbatePlacer:
                 adsZ32.data_ptr(), self.radii.data_ptr(), int(self.radii.numel()), self.masses.data_ptr(),
                 int(self.masses.numel()), C.c_float(gap), MODES[mode], None if bind is None else bind.data_ptr(),
                 pbc.data_ptr(), P, out_row.data_ptr(), N, pos.data_ptr(), sn.data_ptr(), nc.data_ptr(), meta.data_ptr(),
-                _stream(dev)))
+                stream(dev)))
         out = Batch()
         out.pos = pos
         out.atomic_numbers = torch.where(is_slab, slab_Z[src].long(), adsZ_t[asrc]).to(slab_Z.dtype) if Nslab \
@@ -714,24 +667,15 @@ def interstitial_distances(batch, radii=None, masses=None) -> torch.Tensor:
     atom of tag 2), ``+inf`` without such a pair (``get_interstitial_distances``, :511-559, reduced to its minimum)."""
     radii = default_radii() if radii is None else radii
     masses = default_masses() if masses is None else masses
-    if not batch.pos.is_cuda:
-        raise RuntimeError("interstitial_distances runs on a ROCm device (no CPU fallback)")
+    g = geometry(batch, "interstitial_distances", Z=True, tags=True, pbc=True)
     lib = _lib.load()
-    dev = batch.pos.device
-    pos = batch.pos.detach().to(torch.float32).contiguous()
-    natoms = batch.natoms.to(dev, torch.int64).reshape(-1)
-    B, N = int(natoms.numel()), int(pos.shape[0])
-    off = _offsets(natoms)
-    cell = batch.cell.to(dev, torch.float32).reshape(B, 9).contiguous()
-    Z = _i32(batch.atomic_numbers, dev)
-    tags = _i32(batch.tags, dev)
+    dev = g.dev
     r, m = _table(radii, dev, "radius"), _table(masses, dev, "mass")
-    pbc = _pbc_rows(batch, B, dev)
-    d = _desc(pos, cell, Z, off, B, N)
-    out = torch.empty(B, dtype=torch.float32, device=dev)
+    d = desc(g.pos, g.cell, g.Z, g.atom_offset, g.B, g.N)
+    out = torch.empty(g.B, dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        _lib.check(lib.adf_interstitial_distances(C.byref(d), tags.data_ptr(), r.data_ptr(), int(r.numel()), m.data_ptr(),
-                                                  int(m.numel()), pbc.data_ptr(), out.data_ptr(), _stream(dev)))
+        _lib.check(lib.adf_interstitial_distances(C.byref(d), g.tags.data_ptr(), r.data_ptr(), int(r.numel()), m.data_ptr(),
+                                                  int(m.numel()), g.pbc.data_ptr(), out.data_ptr(), stream(dev)))
     return out
 
 

@@ -18,10 +18,7 @@ import torch
 
 from . import lib as _lib
 from .flag_anomaly import regroup
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+from .hostargs import geometry, stream
 
 
 def to_caller_order(index: torch.Tensor, perm: torch.Tensor) -> torch.Tensor:
@@ -55,30 +52,22 @@ class _Matrices:
     """The distance matrices of a batch in the regrouped order, with what the clustering needs next to them."""
 
     def __init__(self, batch, group, include_slab: bool, permutation_invariant: bool, symmetry=None):
-        pos = batch.pos
         S = int(batch.natoms.shape[0])
-        group = _groups(batch, group, S, pos.device)
-        if not pos.is_cuda:
-            raise RuntimeError("site_distances runs on a ROCm device (no CPU fallback)")
-        if S == 0:
-            raise ValueError("site_distances: no site")
+        group = _groups(batch, group, S, batch.pos.device)
+        g = geometry(batch, "site_distances", Z=True, tags=True)
         lib = _lib.load()
-        dev = pos.device
+        dev, N, natoms = g.dev, g.N, g.natoms
         self.S, self.dev = S, dev
         self.perm, self.offsets, self.ids = regroup(group)
         self.G = int(self.ids.numel())
-        N = int(pos.shape[0])
-        natoms = batch.natoms.to(dev, torch.int64).reshape(-1)
-        start = torch.cumsum(natoms, 0) - natoms
+        start = g.atom_offset.long()[:-1]
         # the atoms in the regrouped order of their sites
         moved = natoms[self.perm]
         new_off = torch.zeros(S + 1, dtype=torch.int64, device=dev)
         new_off[1:] = torch.cumsum(moved, 0)
         rows = torch.arange(N, device=dev) + torch.repeat_interleave(start[self.perm] - new_off[:-1], moved, output_size=N)
-        p = pos.detach().to(torch.float32)[rows].contiguous()
-        tags = batch.tags.to(dev)[rows].to(torch.int32).contiguous()
-        Z = batch.atomic_numbers.to(dev).long()[rows].to(torch.int32).contiguous()
-        cell = batch.cell.to(dev, torch.float32).reshape(S, 9)[self.perm].contiguous()
+        p, tags, Z = g.pos[rows].contiguous(), g.tags[rows].contiguous(), g.Z[rows].contiguous()
+        cell = g.cell[self.perm].contiguous()
         self.counts = (self.offsets[1:] - self.offsets[:-1]).long()
         self.pair_offset = torch.zeros(self.G + 1, dtype=torch.int64, device=dev)
         self.pair_offset[1:] = torch.cumsum(self.counts * self.counts, 0)
@@ -99,14 +88,14 @@ class _Matrices:
                                                            int(bool(include_slab)), int(bool(permutation_invariant)),
                                                            op_off.data_ptr(), rot.data_ptr(), trans.data_ptr(),
                                                            sperm.data_ptr(), perm_off.data_ptr(), K, P,
-                                                           self.dist.data_ptr(), self.best_op.data_ptr(), _stream(dev)))
+                                                           self.dist.data_ptr(), self.best_op.data_ptr(), stream(dev)))
             return
         with torch.cuda.device(dev):
             _lib.check(lib.adf_site_pair_distances(p.data_ptr(), cell.data_ptr(), tags.data_ptr(), Z.data_ptr(),
                                                    atom_offset.data_ptr(), self.offsets.data_ptr(),
                                                    self.pair_offset.data_ptr(), N, S, self.G, self.total,
                                                    int(bool(include_slab)), int(bool(permutation_invariant)),
-                                                   self.dist.data_ptr(), _stream(dev)))
+                                                   self.dist.data_ptr(), stream(dev)))
 
     def matrices(self, flat=None):
         flat = self.dist if flat is None else flat
@@ -167,7 +156,7 @@ def unique_sites(batch, group=None, tol: float = 0.05, energy=None, energy_tol: 
         _lib.check(lib.adf_unique_sites(m.dist.data_ptr(), m.offsets.data_ptr(), m.pair_offset.data_ptr(), S, m.G, m.total,
                                         None if e is None else e.data_ptr(), None if f is None else f.data_ptr(),
                                         C.c_float(tol), C.c_float(-1.0 if energy_tol is None else float(energy_tol)),
-                                        rep.data_ptr(), n_unique.data_ptr(), _stream(dev)))
+                                        rep.data_ptr(), n_unique.data_ptr(), stream(dev)))
     out = torch.empty(S, dtype=torch.long, device=dev)
     out[m.perm] = to_caller_order(rep, m.perm)
     if not return_op:
@@ -219,5 +208,5 @@ def top_sites(energy: torch.Tensor, flags: Optional[torch.Tensor], group, k: int
     with torch.cuda.device(dev):
         _lib.check(lib.adf_select_top_sites(e.data_ptr(), None if f is None else f.data_ptr(),
                                             None if r is None else r.data_ptr(), offsets.data_ptr(), G, k, top.data_ptr(),
-                                            top_e.data_ptr(), _stream(dev)))
+                                            top_e.data_ptr(), stream(dev)))
     return to_caller_order(top, perm), top_e

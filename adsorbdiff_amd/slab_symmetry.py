@@ -17,10 +17,7 @@ from typing import List
 import torch
 
 from . import lib as _lib
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+from .hostargs import geometry, stream
 
 
 @dataclass
@@ -97,28 +94,19 @@ def find_symmetry(slab_batch, symprec: float = 0.01, proper_only: bool = False) 
     far a lattice vector's length and an atom's image may be off; it must stay below half the shortest in-plane lattice
     height (``ValueError`` otherwise).  ``proper_only``: rotations only, no mirrors.  Two launches and one read-back (the
     counts, which size the outputs) between them; no loop over slabs."""
-    pos = slab_batch.pos
-    if not pos.is_cuda:
-        raise RuntimeError("find_symmetry runs on a ROCm device (no CPU fallback)")
-    dev = pos.device
-    natoms = slab_batch.natoms.to(dev, torch.int64).reshape(-1)
-    B, N = int(natoms.shape[0]), int(pos.shape[0])
-    if B == 0 or N == 0:
+    g = geometry(slab_batch, "find_symmetry", Z=True)
+    dev, B, N, atom_offset = g.dev, g.B, g.N, g.atom_offset
+    if N == 0:
         raise ValueError("find_symmetry: no slab")
     symprec = float(symprec)
     lib = _lib.load()
-    p = pos.detach().to(torch.float32).contiguous()
-    cell = slab_batch.cell.to(dev, torch.float32).reshape(B, 9).contiguous()
-    Z = slab_batch.atomic_numbers.to(dev).to(torch.int32).contiguous()
-    atom_offset = torch.zeros(B + 1, dtype=torch.int32, device=dev)
-    atom_offset[1:] = torch.cumsum(natoms, 0)
     scratch = torch.empty(int(lib.adf_slab_symmetry_scratch(N, B)), dtype=torch.uint8, device=dev)
     found = torch.empty(2 * B, dtype=torch.int32, device=dev)          # counts, then atom counts
     host = torch.empty(2 * B, dtype=torch.int32)
     with torch.cuda.device(dev):
-        _lib.check(lib.adf_slab_symmetry_search(p.data_ptr(), cell.data_ptr(), Z.data_ptr(), atom_offset.data_ptr(), N, B,
+        _lib.check(lib.adf_slab_symmetry_search(g.pos.data_ptr(), g.cell.data_ptr(), g.Z.data_ptr(), atom_offset.data_ptr(), N, B,
                                                 C.c_double(symprec), int(bool(proper_only)), scratch.data_ptr(),
-                                                found.data_ptr(), host.data_ptr(), _stream(dev)))
+                                                found.data_ptr(), host.data_ptr(), stream(dev)))
     counts, sizes = host[:B].tolist(), host[B:].tolist()
     K, P = sum(counts), sum(c * n for c, n in zip(counts, sizes))
     n_ops, nat = found[:B].long(), found[B:].long()
@@ -134,7 +122,7 @@ def find_symmetry(slab_batch, symprec: float = 0.01, proper_only: bool = False) 
         with torch.cuda.device(dev):
             _lib.check(lib.adf_slab_symmetry_emit(atom_offset.data_ptr(), N, B, C.c_double(symprec), scratch.data_ptr(),
                                                   op_offset.data_ptr(), perm_offset.data_ptr(), K, P, rot.data_ptr(),
-                                                  trans.data_ptr(), W.data_ptr(), perm.data_ptr(), _stream(dev)))
+                                                  trans.data_ptr(), W.data_ptr(), perm.data_ptr(), stream(dev)))
     return SlabSymmetry(n_ops=n_ops, op_offset=op_offset, rot=rot, trans=trans, W=W, perm=perm, perm_offset=perm_offset,
                         natoms=nat, counts=counts, sizes=sizes)
 

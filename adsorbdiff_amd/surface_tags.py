@@ -26,7 +26,8 @@ import torch
 
 from . import lib as _lib
 from .data import _TENSOR_GRAPH_KEYS, Batch
-from .placement import _i32, _offsets, _pbc_rows, _stream, default_masses
+from .hostargs import geometry, i32, offsets, stream
+from .placement import default_masses
 
 NUM_ELEMENTS = 119             # rows of the tables indexed by atomic number: 0 .. 118
 
@@ -56,26 +57,14 @@ def _not_negative(name: str, v) -> float:
     return v
 
 
-def _geometry(batch, who: str):
-    if not batch.pos.is_cuda:
-        raise RuntimeError(f"{who} runs on a ROCm device (the HIP path has no CPU fallback)")
-    dev = batch.pos.device
-    pos = batch.pos.detach().to(torch.float32).contiguous()
-    natoms = batch.natoms.to(dev, torch.int64).reshape(-1)
-    B, N = int(natoms.numel()), int(pos.shape[0])
-    if B < 1:
-        raise ValueError(f"{who}: an empty batch")
-    cell = batch.cell.to(dev, torch.float32).reshape(B, 9).contiguous()
-    return dev, pos, cell, _pbc_rows(batch, B, dev), _offsets(natoms), N, B
-
-
 @torch.no_grad()
 def voronoi_coordination(batch, select=None, cutoff: float = 13.0, tol: float = 0.1, far: float = 100.0) -> VoronoiCoordination:
     """The Voronoi coordination number of every atom of ``batch`` (``select``: a mask [N] of the atoms to evaluate) among
     the periodic images of its own system within ``cutoff`` - ``VoronoiNN(tol=tol, cutoff=cutoff).get_cn(use_weights=True)``.
     ``batch.pbc`` says which directions repeat (all, without one).  One launch for the batch, a wave per atom; no host loop."""
     cutoff, tol, far = _positive("cutoff", cutoff), _positive("tol", tol), _positive("far", far)
-    dev, pos, cell, pbc, off, N, B = _geometry(batch, "voronoi_coordination")
+    g = geometry(batch, "voronoi_coordination", pbc=True)
+    dev, N = g.dev, g.N
     sel = None
     if select is not None:
         sel = torch.as_tensor(select).to(dev).reshape(-1)
@@ -88,10 +77,10 @@ def voronoi_coordination(batch, select=None, cutoff: float = 13.0, tol: float = 
     flags = torch.zeros(N, dtype=torch.int32, device=dev)
     lib = _lib.load()
     with torch.cuda.device(dev):
-        _lib.check(lib.adf_voronoi_coordination(pos.data_ptr(), cell.data_ptr(), pbc.data_ptr(), off.data_ptr(), N, B,
-                                                None if sel is None else sel.data_ptr(), C.c_double(cutoff), C.c_double(tol),
+        _lib.check(lib.adf_voronoi_coordination(g.pos.data_ptr(), g.cell.data_ptr(), g.pbc.data_ptr(), g.atom_offset.data_ptr(),
+                                                N, g.B, None if sel is None else sel.data_ptr(), C.c_double(cutoff), C.c_double(tol),
                                                 C.c_double(far), cn.data_ptr(), om.data_ptr(), nn.data_ptr(), flags.data_ptr(),
-                                                _stream(dev)))
+                                                stream(dev)))
     return VoronoiCoordination(cn, om, nn, (flags & 1) != 0)
 
 
@@ -104,13 +93,13 @@ def bulk_coordination(bulk_batch, cutoff: float = 13.0, tol: float = 0.1, far: f
     dev = vc.cn.device
     natoms = bulk_batch.natoms.to(dev, torch.int64).reshape(-1)
     B, N = int(natoms.numel()), int(vc.cn.numel())
-    Z = _i32(bulk_batch.atomic_numbers, dev)
+    Z = i32(bulk_batch.atomic_numbers, dev)
     table = torch.full((B, NUM_ELEMENTS), math.inf, dtype=torch.float64, device=dev)
     flags = vc.open.to(torch.int32).contiguous()
     lib = _lib.load()
     with torch.cuda.device(dev):
-        _lib.check(lib.adf_bulk_coordination_min(vc.cn.data_ptr(), flags.data_ptr(), Z.data_ptr(), _offsets(natoms).data_ptr(),
-                                                 N, B, table.data_ptr(), _stream(dev)))
+        _lib.check(lib.adf_bulk_coordination_min(vc.cn.data_ptr(), flags.data_ptr(), Z.data_ptr(), offsets(natoms).data_ptr(),
+                                                 N, B, table.data_ptr(), stream(dev)))
     return table
 
 
@@ -136,7 +125,8 @@ def tag_surface_atoms(slab_batch, bulk=None, height: float = 2.0, cn_tol: float 
     and ``surface_open`` (bool [N]) per atom.  Reference order of use: tag the unit slab, then ``tile_atoms``."""
     height, cn_tol = _not_negative("height", height), _not_negative("cn_tol", cn_tol)
     cutoff, tol, far = _positive("cutoff", cutoff), _positive("tol", tol), _positive("far", far)
-    dev, pos, cell, pbc, off, N, B = _geometry(slab_batch, "tag_surface_atoms")
+    g = geometry(slab_batch, "tag_surface_atoms", Z=True, pbc=True)
+    dev, N, B = g.dev, g.N, g.B
     table = None
     if bulk is not None:
         if torch.is_tensor(bulk) or isinstance(bulk, np.ndarray):
@@ -148,16 +138,16 @@ def tag_surface_atoms(slab_batch, bulk=None, height: float = 2.0, cn_tol: float 
         if tuple(table.shape) != (B, NUM_ELEMENTS):
             raise ValueError(f"bulk: a [{B}, {NUM_ELEMENTS}] table expected, got {list(table.shape)}")
     m = _mass_table(masses, dev)
-    Z = _i32(slab_batch.atomic_numbers, dev)
     tags = torch.zeros(N, dtype=torch.int32, device=dev)
     cn = torch.full((N,), math.nan, dtype=torch.float64, device=dev)
     flags = torch.zeros(N, dtype=torch.int32, device=dev)
     lib = _lib.load()
     with torch.cuda.device(dev):
-        _lib.check(lib.adf_tag_surface_atoms(pos.data_ptr(), cell.data_ptr(), pbc.data_ptr(), Z.data_ptr(), off.data_ptr(), N, B,
+        _lib.check(lib.adf_tag_surface_atoms(g.pos.data_ptr(), g.cell.data_ptr(), g.pbc.data_ptr(), g.Z.data_ptr(),
+                                             g.atom_offset.data_ptr(), N, B,
                                              m.data_ptr(), None if table is None else table.data_ptr(), C.c_double(height),
                                              C.c_double(cutoff), C.c_double(tol), C.c_double(far), C.c_double(cn_tol),
-                                             tags.data_ptr(), cn.data_ptr(), flags.data_ptr(), _stream(dev)))
+                                             tags.data_ptr(), cn.data_ptr(), flags.data_ptr(), stream(dev)))
     out = slab_batch.clone()
     out.tags = tags.to(torch.int64)
     out.fixed = (out.tags == 0).to(torch.int64)

@@ -21,15 +21,124 @@ from oracle import painn_oracle as O
 ROOT = Path(__file__).resolve().parent.parent
 
 
-def test_c_abi_exports_match_header():
-    hdr = (ROOT / "include" / "adsorbdiff_hip.h").read_text()
-    declared = set(re.findall(r"\b(adf_[a-z_0-9]+)\s*\(", hdr))
-    declared -= {"adf_painn"}  # struct tag
+# ---- the C ABI: lib.py binds what include/adsorbdiff_hip.h declares.  The tests read the header with their own few lines.
+HEADER = (ROOT / "include" / "adsorbdiff_hip.h").read_text()
+CODE = re.sub(r"/\*.*?\*/", " ", HEADER, flags=re.S)                           # no comments
+SCALARS = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "double": ctypes.c_double}
+BYREF = {"adf_batch": L.BatchDesc, "adf_painn_hparams": L.Hparams, "adf_eqv2_hparams": L.EqV2Hparams, "adf_tune": L.Tune,
+         "adf_counters": L.Counters, "adf_eqv2_counters": L.EqV2Counters, "adf_active_field": L.ActiveField}
+MIRRORS = dict(BYREF, adf_step_coef=L.StepCoef, adf_tr_coef=L.TrCoef)
+PROTOTYPES = re.findall(r"^(int32_t|int64_t|const char\*) (adf_[a-z_0-9]+)\(([^)]*)\);", CODE, flags=re.M)
+
+
+def _expected_argtype(param: str):
+    words = param.replace("const", " ").replace("*", " * ").split()[:-1]      # the type without the parameter's name
+    if "*" in words:
+        return ctypes.POINTER(BYREF[words[0]]) if words[0] in BYREF and words.count("*") == 1 else ctypes.c_void_p
+    return ctypes.c_void_p if re.fullmatch(r"adf_\w+_t", words[0]) else SCALARS[words[0]]
+
+
+def test_c_abi_every_header_prototype_is_parsed_and_exported():
+    loose = set(re.findall(r"\b(adf_[a-z_0-9]+)\s*\(", HEADER)) - {"adf_painn"}   # the old loose search; adf_painn: struct tag
+    assert {name for _, name, _ in PROTOTYPES} == loose and len(PROTOTYPES) == len(loose) == 162
+    assert set(L.parse_header(HEADER)) == loose and set(L.EXPORTS) == loose
+    assert list(L.EXPORTS) == [name for _, name, _ in PROTOTYPES]               # header order
     lib = L.load()
-    for name in sorted(declared):
+    for name in sorted(loose):
         assert hasattr(lib, name), f"{name} declared in the header but not exported"
-    assert set(L.EXPORTS) == declared
     assert b"gfx950" in lib.adf_version()
+
+
+def test_c_abi_argument_and_return_types_are_the_headers():
+    lib = L.load()
+    returns = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "const char*": ctypes.c_char_p}
+    n64 = 0
+    for ret, name, params in PROTOTYPES:
+        fn = getattr(lib, name)
+        expected = [] if params.strip() == "void" else [_expected_argtype(p) for p in params.split(",")]
+        assert list(fn.argtypes) == expected, name
+        assert fn.restype is returns[ret], name
+        n64 += ret == "int64_t"
+    assert n64 == 10 and lib.adf_frames_pushed.restype is ctypes.c_int64 and lib.adf_op_optimizer_chunk.argtypes == []
+    assert lib.adf_last_error.restype is ctypes.c_char_p and lib.adf_version.restype is ctypes.c_char_p
+    # spot checks written out by hand: a double, a float, an int64 in the middle, a host struct, a coefficient table
+    i32, i64, vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p
+    assert lib.adf_lbfgs_create.argtypes == [i64, i32, i32, ctypes.c_double, ctypes.c_double, ctypes.c_double, i32, vp]
+    assert lib.adf_lift_adsorbates.argtypes == [vp, vp, vp, i32, ctypes.c_float, vp, vp]
+    assert lib.adf_graph_build.argtypes == [vp, ctypes.POINTER(L.BatchDesc), vp, vp]
+    assert lib.adf_tr_step.argtypes == [vp, ctypes.POINTER(L.BatchDesc), vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp]
+
+
+@pytest.mark.parametrize("text, named", [
+    ("int32_t adf_new_entry(const float* x, uint16_t n, void* stream);", ("adf_new_entry", "uint16_t")),
+    ("int32_t adf_new_entry(const half* x, void* stream);", ("adf_new_entry", "half")),
+    ("uint8_t adf_new_entry(void);", ("adf_new_entry", "uint8_t")),
+    ("int32_t adf_new_entry(adf_unknown_t h);", ("adf_new_entry", "adf_unknown_t")),
+    ("int32_t adf_new_entry(float v[3]);", ("adf_new_entry", "float v[3]")),
+    ("int32_t adf_new_entry(int32_t);", ("adf_new_entry", "int32_t")),
+    ("int32_t adf_new_entry();", ("adf_new_entry",)),
+])
+def test_c_abi_parser_refuses_what_it_does_not_know(text, named):
+    with pytest.raises(ValueError) as e:
+        L.parse_header("typedef struct adf_painn* adf_painn_t;\nint32_t adf_ok(adf_painn_t h, int64_t n);\n" + text)
+    for word in named:
+        assert word in str(e.value)
+    assert list(L.parse_header("typedef struct adf_painn* adf_painn_t;\nint32_t adf_ok(adf_painn_t h, int64_t n);")) == ["adf_ok"]
+
+
+def test_c_abi_struct_mirrors_equal_the_typedefs():
+    structs = dict((name, body) for body, name in re.findall(r"typedef struct\s*\w*\s*\{([^}]*)\}\s*(\w+);", CODE))
+    assert set(structs) == set(MIRRORS) and len(MIRRORS) == 9
+    for name, mirror in MIRRORS.items():
+        fields = []
+        for decl in filter(None, (d.strip() for d in structs[name].split(";"))):
+            m = re.fullmatch(r"(?:const\s+)?(\w+)\s*(\*?)\s*(.+)", decl, flags=re.S)
+            base = ctypes.c_void_p if m.group(2) else SCALARS[m.group(1)]
+            for declarator in m.group(3).split(","):                           # int64_t inc_rows, inc_rows_full;
+                d = re.fullmatch(r"(\w+)(?:\[(\d+)\])?", declarator.strip())    # int32_t reps[3];
+                fields.append((d.group(1), base * int(d.group(2)) if d.group(2) else base))
+        assert mirror._fields_ == fields, name
+
+
+def test_c_abi_status_codes_equal_the_defines():
+    defines = dict(re.findall(r"^#define (ADF_(?:OK|E[A-Z]+)) (\d+)\b", HEADER, flags=re.M))
+    assert list(defines) == ["ADF_OK", "ADF_EINVAL", "ADF_EOOM", "ADF_ENONEIGHBOR", "ADF_EHIP", "ADF_EOVERFLOW", "ADF_ENUMERIC"]
+    for name, value in defines.items():
+        assert getattr(L, name) == int(value), name
+
+
+def test_hostargs_conversions_on_a_two_system_batch():
+    from adsorbdiff_amd import hostargs as HA
+
+    b = make_batch(2, n_slab=5, n_ads=2, seed=3)
+    cpu = torch.device("cpu")
+    natoms = b.natoms.to(cpu, torch.int64).reshape(-1)
+    off = HA.offsets(natoms)
+    assert off.dtype == torch.int32 and off.shape == (3,) and off.is_contiguous()
+    assert off.tolist() == [0] + torch.cumsum(natoms, 0).tolist() and off[-1] == b.pos.shape[0]
+    assert HA.offsets(natoms.to(torch.int32)).equal(off) and HA.offsets(natoms[:0]).tolist() == [0]
+    z_int = HA.i32(b.atomic_numbers.long(), cpu)
+    z_float = HA.i32(b.atomic_numbers.double(), cpu)
+    assert z_int.dtype == z_float.dtype == torch.int32 and z_int.is_contiguous() and z_int.shape == (b.pos.shape[0],)
+    assert torch.equal(z_int, z_float) and torch.equal(z_int.long(), b.atomic_numbers.long())
+    assert torch.equal(HA.i32(b.atomic_numbers.long().numpy()[::-1].copy(), cpu), z_int.flip(0))   # arrays, any stride
+    assert torch.equal(HA.i32(b.tags, cpu).long(), b.tags.long())
+    # pbc: all periodic without one, a [1,3] or [3] row for every system, [B,3] as it is, anything else refused
+    assert getattr(b, "pbc", None) is None
+    ones = HA.pbc_rows(b, 2, cpu)
+    assert ones.dtype == torch.int32 and ones.shape == (2, 3) and ones.is_contiguous() and bool((ones == 1).all())
+    for one_row in (torch.tensor([[True, True, False]]), torch.tensor([1, 1, 0]), np.array([[2.0, 1.0, 0.0]])):
+        b.pbc = one_row
+        rows = HA.pbc_rows(b, 2, cpu)
+        assert rows.dtype == torch.int32 and rows.is_contiguous() and rows.tolist() == [[1, 1, 0], [1, 1, 0]]
+    b.pbc = torch.tensor([[True, False, False], [False, True, True]])
+    assert HA.pbc_rows(b, 2, cpu).tolist() == [[1, 0, 0], [0, 1, 1]]
+    b.pbc = torch.ones(3, 3, dtype=torch.bool)
+    with pytest.raises(ValueError, match=r"batch\.pbc: \[2, 3\] expected, got \[3, 3\]"):
+        HA.pbc_rows(b, 2, cpu)
+    # the whole unpacking is for device batches only
+    with pytest.raises(RuntimeError, match=r"some_stage runs on a ROCm device \(the HIP path has no CPU fallback\)"):
+        HA.geometry(b, "some_stage")
 
 
 def test_no_cpu_fallback():
