@@ -40,7 +40,14 @@ FLAGS = [
     # Packed f32 VALU math is also slower beside MFMAs (MI355X_MICROARCH.md, filler prices).
     "-fno-slp-vectorize",
 ]
-EXTRA_FLAGS = {}  # per-file additions to FLAGS
+# per-file additions to FLAGS
+EXTRA_FLAGS = {
+    # The L-BFGS performs the reference's separate tensor ops (q - alpha * y, acc + y * s, ...) as separately rounded
+    # operations.  hipcc's __dadd_rn / __dmul_rn are plain + and *, and the device default (-ffp-contract=fast) fused them
+    # into v_fma_f64 once inlined; with contraction off the kernels do what they say, and the float64 statement of the
+    # step with the device's summation order reproduces z bit for bit (tests/test_gpu_relax_coupled.py).
+    "lbfgs.hip": ["-ffp-contract=off"],
+}
 OBJ_DIR = CSRC / "build"  # git-ignored
 
 

@@ -11,8 +11,11 @@
 // sum (per-thread strided sums, then a fixed LDS tree).  The next launch finishes the dot: every workgroup sums the same G
 // partials in the same fixed order, so all of them hold the same bits, and no atomics are involved anywhere.  One launch per
 // history entry finishes the previous dot, applies the axpy of that entry and emits the partials of the next dot.
-// Arithmetic that the reference performs as separate tensor ops (q - alpha * y, z + s * (alpha - beta), ...) uses explicitly
-// rounded operations, so the compiler cannot contract it into FMAs.
+// Arithmetic that the reference performs as separate tensor ops (q - alpha * y, z + s * (alpha - beta), ...) is separately
+// rounded.  The __dadd_rn / __dmul_rn spelling marks those places but does not do it: hipcc defines them as plain + and *,
+// which the device default -ffp-contract=fast fuses into FMAs once inlined.  This file is therefore compiled with
+// -ffp-contract=off (build.py, EXTRA_FLAGS); tests/test_gpu_relax_coupled.py checks z bit for bit against the float64
+// statement of the step with this file's summation order.
 //
 // Per-system mode (adf_lbfgs_set_per_system).  Every system keeps its own step counter, its slice of the rings and its own
 // rho / alpha [memory]; one workgroup per system walks a whole step in ONE launch (lb_per_system_kernel).  Thread t owns
@@ -643,6 +646,18 @@ extern "C" int32_t adf_lbfgs_step(adf_lbfgs_t h, const int32_t* atom_offset, flo
 extern "C" int32_t adf_lbfgs_get_mask(adf_lbfgs_t h, int32_t* out, void* stream) {
     if (!h || !out) { adf_set_error("null argument"); return ADF_EINVAL; }
     ADF_HIP_CHECK(hipMemcpyAsync(out, h->mask, sizeof(int32_t) * h->B, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return ADF_OK;
+}
+
+// The search direction z of the last adf_lbfgs_step ([3N] f64, device): q holds it after the second loop in both modes.
+// The rows of a system whose mask was clear in a per-system step are the ones of its own last step (undefined before it).
+extern "C" int32_t adf_lbfgs_get_direction(adf_lbfgs_t h, double* z_out, void* stream) {
+    if (!h || !z_out) { adf_set_error("null argument"); return ADF_EINVAL; }
+    if (h->calls == 0) {
+        adf_set_error("lbfgs_get_direction: no adf_lbfgs_step since create / reset (there is no direction yet)");
+        return ADF_EINVAL;
+    }
+    ADF_HIP_CHECK(hipMemcpyAsync(z_out, h->q, sizeof(double) * (size_t)h->n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return ADF_OK;
 }
 

@@ -433,6 +433,14 @@ class LBFGS:
             _lib.check(self.lib.adf_lbfgs_get_mask(self.handle, out.data_ptr(), self._stream()))
         return out
 
+    def direction(self) -> torch.Tensor:
+        """The search direction ``z`` of the last step (the two-loop recursion's result, before ``determine_step``), f64
+        [N, 3] on the device (``adf_lbfgs_get_direction``); ValueError before the first step and after ``reset``."""
+        out = torch.empty(self.num_atoms, 3, dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.adf_lbfgs_get_direction(self.handle, out.data_ptr(), self._stream()))
+        return out
+
     # ------------------------------------------------------------------ trajectories
     def write(self, energy, forces, update_mask) -> None:
         """Reference :204-212: a frame per system whose mask is set, or every system without ``save_full_traj``."""

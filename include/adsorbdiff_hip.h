@@ -1259,6 +1259,11 @@ int32_t adf_lbfgs_step(adf_lbfgs_t h, const int32_t* atom_offset, float* pos, co
                        void* stream);
 /* the update mask of the last converge, int32 [B] device */
 int32_t adf_lbfgs_get_mask(adf_lbfgs_t h, int32_t* out, void* stream);
+/* the search direction z of the last step (the two-loop recursion's result, before determine_step), f64 [3N] device; a
+ * device-to-device copy on `stream`.  Both modes; in per-system mode the rows of a system whose mask was clear are those of
+ * its own last step (undefined before it).  ADF_EINVAL on a null argument or a handle that has not stepped since create /
+ * reset. */
+int32_t adf_lbfgs_get_direction(adf_lbfgs_t h, double* z_out, void* stream);
 /* max |dr| over the batch of the last step (below 1e-7: the step was skipped), device f64 scalar.  Maxima here propagate
  * NaN as the reference's reductions do: a NaN force clears its system's mask and does not make the step skip. */
 int32_t adf_lbfgs_last_step_max(adf_lbfgs_t h, double* out, void* stream);

@@ -40,7 +40,7 @@ def _expected_argtype(param: str):
 
 def test_c_abi_every_header_prototype_is_parsed_and_exported():
     loose = set(re.findall(r"\b(adf_[a-z_0-9]+)\s*\(", HEADER)) - {"adf_painn"}   # the old loose search; adf_painn: struct tag
-    assert {name for _, name, _ in PROTOTYPES} == loose and len(PROTOTYPES) == len(loose) == 162
+    assert {name for _, name, _ in PROTOTYPES} == loose and len(PROTOTYPES) == len(loose) == 163
     assert set(L.parse_header(HEADER)) == loose and set(L.EXPORTS) == loose
     assert list(L.EXPORTS) == [name for _, name, _ in PROTOTYPES]               # header order
     lib = L.load()
@@ -64,6 +64,7 @@ def test_c_abi_argument_and_return_types_are_the_headers():
     # spot checks written out by hand: a double, a float, an int64 in the middle, a host struct, a coefficient table
     i32, i64, vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p
     assert lib.adf_lbfgs_create.argtypes == [i64, i32, i32, ctypes.c_double, ctypes.c_double, ctypes.c_double, i32, vp]
+    assert lib.adf_lbfgs_get_direction.argtypes == [vp, vp, vp] and lib.adf_lbfgs_get_direction.restype is i32
     assert lib.adf_lift_adsorbates.argtypes == [vp, vp, vp, i32, ctypes.c_float, vp, vp]
     assert lib.adf_graph_build.argtypes == [vp, ctypes.POINTER(L.BatchDesc), vp, vp]
     assert lib.adf_tr_step.argtypes == [vp, ctypes.POINTER(L.BatchDesc), vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp]

@@ -75,6 +75,16 @@ def test_lbfgs_create_rejects_bad_arguments():
     assert not h.value
 
 
+def test_lbfgs_get_direction_rejects_null_arguments():
+    """The null checks come before anything touches the device; the refusal on a handle that has not stepped needs a handle
+    and is a GPU test (tests/test_gpu_relax_coupled.py)."""
+    lib = L.load()
+    z = (ctypes.c_double * 3)()
+    assert lib.adf_lbfgs_get_direction(None, z, None) == L.ADF_EINVAL and b"null argument" in lib.adf_last_error()
+    assert lib.adf_lbfgs_get_direction(None, None, None) == L.ADF_EINVAL
+    assert list(z) == [0.0, 0.0, 0.0]
+
+
 def test_ml_relax_split_order(monkeypatch):
     """RuntimeError on a batch of more than 2 systems: halves, second half first (the reference's appendleft order)."""
     seen = []
