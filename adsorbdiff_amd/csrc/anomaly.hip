@@ -29,10 +29,14 @@
 #include <float.h>
 #include <limits.h>
 
-#include "common.h"
+#include "host_util.h"
+#include "cell3.h"
+#include "lanes.h"
 
 #define AN_THREADS 256
 #define AN_TJ 256   // atoms per staged j tile
+
+enum { AN_ERR_Z = 1 };   // the one bit of the error word
 
 struct an_params {
     const float* pos_init;
@@ -86,15 +90,7 @@ __global__ __launch_bounds__(AN_THREADS) void an_pairs_kernel(an_params p) {
     float c[9], inv[9];
 #pragma unroll
     for (int k = 0; k < 9; ++k) c[k] = p.cell[9 * (size_t)b + k];
-    {
-        const float cx0 = c[4] * c[8] - c[5] * c[7], cx1 = c[5] * c[6] - c[3] * c[8], cx2 = c[3] * c[7] - c[4] * c[6];
-        const float vol = c[0] * cx0 + c[1] * cx1 + c[2] * cx2;
-        const float iv = vol != 0.f ? 1.0f / vol : 0.f;
-        // columns of the inverse: f_k = d . inv[:,k]
-        inv[0] = cx0 * iv; inv[3] = cx1 * iv; inv[6] = cx2 * iv;
-        inv[1] = (c[2] * c[7] - c[1] * c[8]) * iv; inv[4] = (c[0] * c[8] - c[2] * c[6]) * iv; inv[7] = (c[1] * c[6] - c[0] * c[7]) * iv;
-        inv[2] = (c[1] * c[5] - c[2] * c[4]) * iv; inv[5] = (c[2] * c[3] - c[0] * c[5]) * iv; inv[8] = (c[0] * c[4] - c[1] * c[3]) * iv;
-    }
+    adf_inv3(c, inv);
     const int r0 = p.reps[0], r1 = p.reps[1], r2 = p.reps[2];
     const float w0 = r0 > 0 ? 1.f : 0.f, w1 = r1 > 0 ? 1.f : 0.f, w2 = r2 > 0 ? 1.f : 0.f;
 
@@ -103,7 +99,7 @@ __global__ __launch_bounds__(AN_THREADS) void an_pairs_kernel(an_params p) {
         const int tag = p.tags[a];
         const int z = p.Z[a];
         const bool bad = z < 0 || z >= p.num_radii;
-        if (bad && local < n) atomicOr(p.err, 1);
+        if (bad && local < n) atomicOr(p.err, AN_ERR_Z);
         const float rad = p.radii[bad ? 0 : z];
         const float* src = tag == 2 ? p.pos_init : p.pos_ref;
         f = make_float4(p.pos_final[3 * (size_t)a], p.pos_final[3 * (size_t)a + 1], p.pos_final[3 * (size_t)a + 2], rad);
@@ -181,11 +177,9 @@ extern "C" int32_t adf_flag_anomalies(const adf_batch* b, const float* pos_final
     for (int k = 0; k < 3; ++k)
         if (b->reps[k] < 0 || b->reps[k] > 16) { adf_set_error("flag_anomalies: reps[%d]=%d out of range", k, b->reps[k]); return ADF_EINVAL; }
     hipStream_t s = (hipStream_t)stream;
-    adf_pool tmp;   // the error word; freed on every return (after the synchronisation below)
-    int32_t* err = nullptr;
-    ADF_TRY(tmp.alloc(&err, 1));
+    adf_errword err;   // freed on every return (after the synchronisation in finish)
+    ADF_TRY(err.create(s));
     const int B = b->num_systems;
-    ADF_HIP_CHECK(hipMemsetAsync(err, 0, sizeof(int32_t), s));
     ADF_HIP_CHECK(hipMemsetAsync(flags, 0, sizeof(int32_t) * 4 * (size_t)B, s));
     an_params p = {};
     p.pos_init = b->pos; p.pos_final = pos_final; p.pos_ref = pos_slab_ref ? pos_slab_ref : b->pos;
@@ -193,7 +187,7 @@ extern "C" int32_t adf_flag_anomalies(const adf_batch* b, const float* pos_final
     p.radii = radii; p.num_radii = num_radii;
     for (int k = 0; k < 3; ++k) p.reps[k] = b->reps[k];
     p.skin2 = 2.0f * skin; p.surface_mult = surface_mult; p.desorption_mult = desorption_mult;
-    p.flags = flags; p.err = err;
+    p.flags = flags; p.err = err.dev;
     // row-tile slots per system: twice the average system's 64-row tiles, so that the common system has a workgroup
     // per tile; a system with more tiles strides over them, one with fewer leaves its spare workgroups at once
     const long long avg_tiles = ((long long)b->num_atoms / B + 63) / 64;
@@ -203,11 +197,9 @@ extern "C" int32_t adf_flag_anomalies(const adf_batch* b, const float* pos_final
     ADF_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(an_finish_kernel, dim3((B + 255) / 256), dim3(256), 0, s, flags, B);
     ADF_HIP_CHECK(hipGetLastError());
-    int32_t bad = 0;
-    ADF_HIP_CHECK(hipMemcpyAsync(&bad, err, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    ADF_HIP_CHECK(hipStreamSynchronize(s));
-    if (bad) { adf_set_error("atomic number outside [0, %d) (rows of the radius table)", num_radii); return ADF_EINVAL; }
-    return ADF_OK;
+    // this message has never named its entry: `who` is empty, and the format's leading %s prints nothing
+    const adf_errrow rows[] = {{AN_ERR_Z, ADF_EINVAL, "%satomic number outside [0, %d) (rows of the radius table)", num_radii}};
+    return err.finish(s, "", rows);
 }
 
 // ---- site ranking: one wave per group, lanes stride over the group's sites in index order, then a butterfly whose
@@ -229,6 +221,7 @@ __global__ __launch_bounds__(256) void an_best_sites_kernel(const float* energy,
             if (e < be || (e == be && i < bi)) { be = e; bi = i; }
         }
     }
+    // kept inline: as a call to lanes.h this butterfly reorders the kernel's instructions (tools/device_asm_diff.py)
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         const float oe = __shfl_xor(be, o);

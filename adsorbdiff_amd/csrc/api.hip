@@ -950,7 +950,7 @@ __global__ __launch_bounds__(256) void adf_energy_sum_kernel(const float* __rest
         const float* row = y + (size_t)a * H2;
         float d = 0.f;
         for (int c = lane; c < H2; c += 64) d = fmaf(row[c], w[c], d);
-        for (int o = 32; o > 0; o >>= 1) d = __fadd_rn(d, __shfl_xor(d, o, 64));
+        d = adf_wave_sum(d);
         acc = __fadd_rn(acc, __fadd_rn(d, b0));
     }
     if (lane == 0) part[wave] = acc;

@@ -1,13 +1,9 @@
 // Internal declarations shared by the HIP translation units of libadsorbdiff_hip.so.
 // gfx950 (MI355X) only: 64-wide wavefronts, f32 MFMA 32x32x2, 160 KiB LDS per CU.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <string>
-#include <vector>
-
-#include "../../include/adsorbdiff_hip.h"
+#include "base.h"
+#include "arith.h"
+#include "lanes.h"
 
 #define ADF_GROUP_NODES 32      // target nodes per message-kernel work item
 #define ADF_SLICE_CH 64         // channels per message-kernel slice (x3 parts = 192 MFMA columns)
@@ -16,113 +12,6 @@
 #define ADF_NFLAGS 8
 #define ADF_MAX_INDEG 1024
 #define ADF_MAX_LAYERS 16      // incoming edges per target the per-target sorter handles (graph.hip)
-
-void adf_set_error(const char* fmt, ...);
-
-#define ADF_HIP_CHECK(expr)                                                             \
-    do {                                                                                \
-        hipError_t _e = (expr);                                                         \
-        if (_e != hipSuccess) {                                                         \
-            adf_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e),        \
-                          __FILE__, __LINE__);                                          \
-            return (_e == hipErrorOutOfMemory) ? ADF_EOOM : ADF_EHIP;                   \
-        }                                                                               \
-    } while (0)
-
-#define ADF_TRY(expr)                     \
-    do {                                  \
-        int32_t _s = (expr);              \
-        if (_s != ADF_OK) return _s;      \
-    } while (0)
-
-// ---- device memory: the one owner type.  A pool fills pointer fields (of a handle, or locals of the function that holds
-// the pool) and remembers their ADDRESSES, so it frees whatever a field holds at release time (fields that are swapped
-// among themselves stay correct) and nulls the field itself.  Handles are heap objects: their fields do not move.
-// It never synchronises: the caller does where enqueued work may still use the buffers.
-struct adf_pool {
-    std::vector<void**> slots;
-    adf_pool() = default;
-    adf_pool(const adf_pool&) = delete;
-    adf_pool& operator=(const adf_pool&) = delete;
-    ~adf_pool() { release(); }
-    // *field = new buffer of `bytes` bytes (0 is rounded up: a filled field is never null).  A field this pool filled
-    // before is re-allocated: its old buffer is freed first.  On failure *field is null.
-    int32_t alloc(void** field, size_t bytes) {
-        bool known = false;
-        for (void** s : slots) known = known || s == field;
-        if (known) { if (*field) (void)hipFree(*field); } else slots.push_back(field);
-        *field = nullptr;
-        if (bytes == 0) bytes = 16;
-        const hipError_t e = hipMalloc(field, bytes);
-        if (e == hipSuccess) return ADF_OK;
-        *field = nullptr;
-        (void)hipGetLastError();
-        adf_set_error("device allocation of %zu bytes failed: %s", bytes, hipGetErrorString(e));
-        return ADF_EOOM;
-    }
-    template <typename T>
-    int32_t alloc(T** field, size_t count) { return alloc(reinterpret_cast<void**>(field), count * sizeof(T)); }
-    void release() {
-        for (void** s : slots) {
-            if (*s) (void)hipFree(*s);
-            *s = nullptr;
-        }
-        slots.clear();
-    }
-};
-
-// ---- HIP-event profiling (bench.py roofline): pairs of events on the launch stream around kernel groups, a category per pair
-struct adf_prof {
-    bool on = false;
-    bool open = false;                // a begin has recorded its event and waits for its end
-    std::vector<hipEvent_t> ev;       // pool of events, used pairwise
-    std::vector<int> cat;             // category of every recorded pair
-    size_t used = 0;                  // events of the finished pairs
-    adf_prof() = default;
-    adf_prof(const adf_prof&) = delete;
-    adf_prof& operator=(const adf_prof&) = delete;
-    ~adf_prof() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
-    // no events to be had: this begin and its end do nothing
-    void begin(int c, hipStream_t s) {
-        open = false;
-        if (!on) return;
-        if (used + 2 > ev.size())
-            for (int i = 0; i < 512; ++i) {
-                hipEvent_t e;
-                if (hipEventCreate(&e) != hipSuccess) { (void)hipGetLastError(); break; }
-                ev.push_back(e);
-            }
-        if (used + 2 > ev.size()) return;
-        cat.resize(used / 2);         // (drops a pair that an error return left without its end)
-        cat.push_back(c);
-        (void)hipEventRecord(ev[used], s);
-        open = true;
-    }
-    void end(hipStream_t s) {
-        if (!on || !open) return;
-        (void)hipEventRecord(ev[used + 1], s);
-        used += 2;
-        open = false;
-    }
-    void enable(bool o) { on = o; open = false; used = 0; cat.clear(); }
-    // per category: summed milliseconds and number of pairs since the last read (the stream must be idle); then empty
-    int32_t read(float* ms, int64_t* count, int ncat) {
-        for (int c = 0; c < ncat; ++c) { ms[c] = 0.f; count[c] = 0; }
-        for (size_t i = 0; i < used; i += 2) {
-            float t = 0.f;
-            ADF_HIP_CHECK(hipEventElapsedTime(&t, ev[i], ev[i + 1]));
-            ms[cat[i / 2]] += t;
-            count[cat[i / 2]] += 1;
-        }
-        enable(on);
-        return ADF_OK;
-    }
-    struct scope {
-        adf_prof& p; hipStream_t s;
-        scope(adf_prof& p_, int c, hipStream_t s_) : p(p_), s(s_) { p.begin(c, s); }
-        ~scope() { p.end(s); }
-    };
-};
 
 // fp16 hi/lo split of one nn.Linear weight (gemm16.hip), library-owned
 struct adf_w16 {
@@ -378,38 +267,6 @@ int32_t adf_graph_build_impl(adf_painn* h, const adf_batch* b, hipStream_t s);
 // api.hip: energy[b] = sum over the system's atoms of (y[a] . w + bias), fixed order (adf_energy_sum_kernel)
 int32_t adf_energy_sum(const float* y, int H2, const float* w, const float* bias, const int32_t* atom_offset, float* energy,
                        int num_systems, hipStream_t s);
-// ScaledSiLU f(x) = x sigmoid(x) / 0.6 and f'(x) w, as the energy head's backward evaluates them: the seed of the energy
-// gradient (energy_grad.hip) and adf_op_energy_head_bwd (s2ef_train.hip) share the one expression
-// max over the 16 lanes of a DPP row (non-negative values), left in every lane: four v_max_f32 with row rotations
-__device__ __forceinline__ float adf_row16_max(float v) {
-#define ADF_ROR(n_) __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x120 + (n_), 0xf, 0xf, false))
-    v = fmaxf(v, ADF_ROR(8));
-    v = fmaxf(v, ADF_ROR(4));
-    v = fmaxf(v, ADF_ROR(2));
-    v = fmaxf(v, ADF_ROR(1));
-#undef ADF_ROR
-    return v;
-}
-// max over the 32 lanes of a half-wave (non-negative values), left in lanes 16-31 of the half: adf_row16_max, then lane 15
-// of DPP rows 0 / 2 is broadcast into rows 1 / 3 (row_bcast:15, row mask 0xa; rows 0 / 2 receive 0)
-__device__ __forceinline__ float adf_half32_max_hi(float v) {
-    v = adf_row16_max(v);
-    return fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x142, 0xa, 0xf, false)));
-}
-// max over aligned groups of 8 lanes (non-negative values), left in every lane: two quad permutes, then row_half_mirror
-__device__ __forceinline__ float adf_lane8_max(float v) {
-#define ADF_DPP(c_) __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), (c_), 0xf, 0xf, false))
-    v = fmaxf(v, ADF_DPP(0xb1));    // quad_perm [1,0,3,2]
-    v = fmaxf(v, ADF_DPP(0x4e));    // quad_perm [2,3,0,1]
-    v = fmaxf(v, ADF_DPP(0x141));   // row_half_mirror: lane i <-> 7 - i
-#undef ADF_DPP
-    return v;
-}
-__device__ __forceinline__ float adf_ssilu(float x) { return x / (1.0f + expf(-x)) * 1.6666666666666667f; }
-__device__ __forceinline__ float adf_dssilu_times(float x, float w) {
-    const float sg = 1.0f / (1.0f + expf(-x));
-    return sg * (1.0f + x * (1.0f - sg)) * 1.6666666666666667f * w;
-}
 // energy_grad.hip: state of adf_painn_forward_energy_gradient (invalidate: the bound weights changed)
 void adf_grad_invalidate(adf_painn* h);
 void adf_grad_free(adf_painn* h);

@@ -102,12 +102,6 @@ __global__ void eg_add_kernel(const float* __restrict__ src, float* __restrict__
         dst[i] += src[i];
 }
 
-__device__ __forceinline__ float eg_wsum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // Exact-f32 (and unequally spaced centres) form of a message block's backward with the geometry gradient: one workgroup per
 // SOURCE atom j over its own CSR segment, as train.hip's tr_msg_bwd_kernel, but rbfh and rbfh' are formed per edge from the
 // transposed rbf_proj.weight instead of read from an [E, 3H] tensor, and nothing per edge and channel is written.
@@ -174,7 +168,7 @@ __global__ __launch_bounds__(256) void eg_msg_bwd_plain_kernel(
                 const float fc = xc * rc;
                 b0 = g0 * fc; b1 = g1 * fc; b2 = g2 * fc;
             }
-            al = eg_wsum(al); b0 = eg_wsum(b0); b1 = eg_wsum(b1); b2 = eg_wsum(b2);
+            al = adf_wave_sum(al); b0 = adf_wave_sum(b0); b1 = adf_wave_sum(b1); b2 = adf_wave_sum(b2);
             if (lane == 0) { red[wave][0] = al; red[wave][1] = b0; red[wave][2] = b1; red[wave][3] = b2; }
             __syncthreads();
             if (tid < 4) {
@@ -251,6 +245,7 @@ __global__ __launch_bounds__(256) void eg_position_kernel(const int32_t* __restr
         if (f >= 0) eg_row_gradient(part, ecap, nslices, e_geom[f], f, bx, by, bz);
         fx = __fadd_rn(fx, __fsub_rn(ax, bx)); fy = __fadd_rn(fy, __fsub_rn(ay, by)); fz = __fadd_rn(fz, __fsub_rn(az, bz));
     }
+    // kept inline: as a call to lanes.h this butterfly reorders the kernel's instructions (tools/device_asm_diff.py)
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         fx = __fadd_rn(fx, __shfl_xor(fx, o)); fy = __fadd_rn(fy, __shfl_xor(fy, o)); fz = __fadd_rn(fz, __shfl_xor(fz, o));

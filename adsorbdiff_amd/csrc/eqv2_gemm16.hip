@@ -23,18 +23,6 @@ typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 #define GLD 40  // halves per LDS row (32 + 8 pad: conflict-free ds_read_b128)
 #define GTLD 64
 
-__device__ __forceinline__ float eq16_silu(float x) { return x / (1.0f + expf(-x)); }
-
-__device__ __forceinline__ float eq16_lift(float mx) {
-    // 2^e with mx 2^e in [2^14, 2^15); 1 for mx == 0 or non-finite
-    if (!(mx > 0.f) || !(mx < 3.0e38f)) return 1.0f;
-    int e;
-    (void)frexpf(mx, &e);
-    e = 15 - e;
-    e = e > 120 ? 120 : (e < -120 ? -120 : e);
-    return ldexpf(1.0f, e);
-}
-
 // rs[r] = max_k |A[r, k]| (the product kernels turn it into the row's power-of-two lift).  Sixteen lanes per row (four rows per
 // wave, sixteen per workgroup), the row's maximum by four DPP row rotations (round 6; was one wave per row with a six-step
 // ds_bpermute butterfly: four times the workgroups and a chain of LDS-crossbar round trips per row).
@@ -55,12 +43,7 @@ __global__ __launch_bounds__(256) void eq_rowscale_kernel(const float* __restric
         const float4 v = *reinterpret_cast<const float4*>(a + k);
         mx = fmaxf(fmaxf(fmaxf(mx, fabsf(v.x)), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)));
     }
-#define EQ_ROR(n_) __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(mx), 0x120 + (n_), 0xf, 0xf, false))
-    mx = fmaxf(mx, EQ_ROR(8));
-    mx = fmaxf(mx, EQ_ROR(4));
-    mx = fmaxf(mx, EQ_ROR(2));
-    mx = fmaxf(mx, EQ_ROR(1));
-#undef EQ_ROR
+    mx = adf_row16_max(mx);
     if (j == 0 && r < M) rs[r] = mx;
 }
 
@@ -108,13 +91,13 @@ __global__ __launch_bounds__(256, 2) void eq_gemm16_kernel(const float* __restri
         long long grow = m0 + row;
         if (grow > M - 1) grow = M - 1;
         a_ptr[i] = A + (grow / am.period) * am.outer + (grow % am.period) * (long long)am.inner + kq * 4;
-        a_rs[i] = rscale ? eq16_lift(rscale[rs_div > 1 ? grow / rs_div : grow]) : 1.0f;
+        a_rs[i] = rscale ? adf_pow2_lift(rscale[rs_div > 1 ? grow / rs_div : grow]) : 1.0f;
         a_off[i] = row * GLD + kq * 4;
     }
     if (tid < TM) {
         long long grow = m0 + tid;
         if (grow > M - 1) grow = M - 1;
-        rinv[tid] = rscale ? 1.0f / eq16_lift(rscale[rs_div > 1 ? grow / rs_div : grow]) : 1.0f;
+        rinv[tid] = rscale ? 1.0f / adf_pow2_lift(rscale[rs_div > 1 ? grow / rs_div : grow]) : 1.0f;
     }
     int w_src[NJ], w_off[NJ];
 #pragma unroll
@@ -210,7 +193,7 @@ __global__ __launch_bounds__(256, 2) void eq_gemm16_kernel(const float* __restri
                 const int lr = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
                 const float sc = isc * rinv[wm + 32 * i + lr];
                 float v0 = acc[i][2 * jj][r] * sc + bv0, v1 = acc[i][2 * jj + 1][r] * sc + bv1;
-                if (ACT == 2) { v0 = eq16_silu(v0); v1 = eq16_silu(v1); }
+                if (ACT == 2) { v0 = adf_silu(v0); v1 = adf_silu(v1); }
                 T[lr * GTLD + q] = v0;
                 T[lr * GTLD + 32 + q] = v1;
                 if (out_mag) {  // magnitude of the output row (all lanes of a half-wave hold the same row)
@@ -283,13 +266,13 @@ __global__ __launch_bounds__(512, 2) void eq_gemm16_256_kernel(const float* __re
         long long grow = m0 + row;
         if (grow > M - 1) grow = M - 1;
         a_ptr[i] = A + (grow / am.period) * am.outer + (grow % am.period) * (long long)am.inner + kq * 4;
-        a_rs[i] = rscale ? eq16_lift(rscale[rs_div > 1 ? grow / rs_div : grow]) : 1.0f;
+        a_rs[i] = rscale ? adf_pow2_lift(rscale[rs_div > 1 ? grow / rs_div : grow]) : 1.0f;
         a_off[i] = row * GLD + kq * 4;
     }
     if (tid < TM) {
         long long grow = m0 + tid;
         if (grow > M - 1) grow = M - 1;
-        rinv[tid] = rscale ? 1.0f / eq16_lift(rscale[rs_div > 1 ? grow / rs_div : grow]) : 1.0f;
+        rinv[tid] = rscale ? 1.0f / adf_pow2_lift(rscale[rs_div > 1 ? grow / rs_div : grow]) : 1.0f;
     }
     int w_src[NW], w_off[NW];
 #pragma unroll
@@ -397,7 +380,7 @@ __global__ __launch_bounds__(512, 2) void eq_gemm16_256_kernel(const float* __re
             const int lr = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
             const float sc = isc * rinv[wm + 32 * i + lr];
             float v0 = acc[i][0][r] * sc + bv0, v1 = acc[i][1][r] * sc + bv1;
-            if (ACT == 2) { v0 = eq16_silu(v0); v1 = eq16_silu(v1); }
+            if (ACT == 2) { v0 = adf_silu(v0); v1 = adf_silu(v1); }
             T[lr * GTLD + q] = v0;
             T[lr * GTLD + 32 + q] = v1;
             if (out_mag) {
@@ -471,7 +454,7 @@ __global__ __launch_bounds__(512, 2) void eq_gemm16p_kernel(const _Float16* __re
     if (tid < TM) {
         long long grow = m0 + tid;
         if (grow > M - 1) grow = M - 1;
-        rinv[tid] = 1.0f / eq16_lift(mag[grow]);
+        rinv[tid] = 1.0f / adf_pow2_lift(mag[grow]);
     }
     half8 rah[2], ral[2], rwh[2], rwl[2];
     auto load_tile = [&](int k1) {
@@ -568,7 +551,7 @@ __global__ __launch_bounds__(512, 2) void eq_gemm16p_kernel(const _Float16* __re
             const int lr = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
             const float sc = isc * rinv[wm + 32 * i + lr];
             float v0 = acc[i][0][r] * sc + bv0, v1 = acc[i][1][r] * sc + bv1;
-            if (ACT == 2) { v0 = eq16_silu(v0); v1 = eq16_silu(v1); }
+            if (ACT == 2) { v0 = adf_silu(v0); v1 = adf_silu(v1); }
             T[lr * GTLD + q] = v0;
             T[lr * GTLD + 32 + q] = v1;
         }
@@ -658,7 +641,7 @@ __device__ __forceinline__ void eq_gemm16pw_tile(
     if (tid < TM) {
         long long grow = m0 + tid;
         if (grow > M - 1) grow = M - 1;
-        rinv[tid] = 1.0f / eq16_lift(mag[grow]);
+        rinv[tid] = 1.0f / adf_pow2_lift(mag[grow]);
     }
     half8 ra[NA], rb[NA];
     auto request = [&](half8 (&r)[NA], int kt1) {
@@ -762,7 +745,7 @@ __device__ __forceinline__ void eq_gemm16pw_tile(
             const int lr = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
             const float sc = isc * rinv[wm + 32 * i + lr];
             float v0 = acc[i][0][r] * sc + bv0, v1 = acc[i][1][r] * sc + bv1;
-            if (ACT == 2) { v0 = eq16_silu(v0); v1 = eq16_silu(v1); }
+            if (ACT == 2) { v0 = adf_silu(v0); v1 = adf_silu(v1); }
             T[lr * GTLD + q] = v0;
             T[lr * GTLD + 32 + q] = v1;
         }
@@ -831,7 +814,7 @@ __global__ void eq_presplit_kernel(const float* __restrict__ A, const float* __r
                                    _Float16* __restrict__ hi, _Float16* __restrict__ lo) {
     const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= M * K) return;
-    const float sv = A[t] * eq16_lift(mag[t / K]);
+    const float sv = A[t] * adf_pow2_lift(mag[t / K]);
     const _Float16 h = (_Float16)sv;
     hi[t] = h;
     lo[t] = (_Float16)(sv - (float)h);

@@ -31,26 +31,10 @@
         default: adf_set_error("eqv2: lmax %d not instantiated (1..6)", L_); return ADF_EINVAL; \
     }
 
-__device__ __forceinline__ float eq_silu(float x) { return x / (1.0f + expf(-x)); }
-
-__device__ __forceinline__ float eq_pow2_lift(float mx) {
-    // 2^e such that mx 2^e in [2^14, 2^15); 1 for mx == 0 or non-finite
-    if (!(mx > 0.f) || !(mx < 3.0e38f)) return 1.0f;
-    int e;
-    (void)frexpf(mx, &e);
-    e = 15 - e;
-    e = e > 120 ? 120 : (e < -120 ? -120 : e);
-    return ldexpf(1.0f, e);
-}
-
-__device__ __forceinline__ float eq_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-// sum over a workgroup of up to 1024 threads; every thread gets the result
+// sum over a workgroup of up to 1024 threads; every thread gets the result.  Not lanes.h's adf_block_reduce: the wave count
+// is the launch's and the combine starts from 0.f (a sum of -0.f comes out +0.f), so it compiles to other instructions
 __device__ __forceinline__ float eq_block_sum(float v, float* red) {
-    v = eq_wave_sum(v);
+    v = adf_wave_sum(v);
     const int w = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
     __syncthreads();
     if ((threadIdx.x & 63) == 0) red[w] = v;
@@ -376,11 +360,11 @@ __global__ __launch_bounds__(256) void eq_ln_silu_kernel(float* __restrict__ x, 
     float* xr = x + (size_t)r * width;
     float sum = 0.f;
     for (int c = lane; c < width; c += 64) sum += xr[c];
-    const float mean = eq_wave_sum(sum) / width;
+    const float mean = adf_wave_sum(sum) / width;
     float q = 0.f;
     for (int c = lane; c < width; c += 64) { const float t = xr[c] - mean; q += t * t; }
-    const float rstd = rsqrtf(eq_wave_sum(q) / width + 1e-5f);
-    for (int c = lane; c < width; c += 64) xr[c] = eq_silu((xr[c] - mean) * rstd * w[c] + b[c]);
+    const float rstd = rsqrtf(adf_wave_sum(q) / width + 1e-5f);
+    for (int c = lane; c < width; c += 64) xr[c] = adf_silu((xr[c] - mean) * rstd * w[c] + b[c]);
 }
 
 int32_t eq_launch_ln_silu(float* x, const float* w, const float* b, long long rows, int width, hipStream_t s) {
@@ -459,15 +443,15 @@ __global__ __launch_bounds__(256) void eq_radial_live_kernel(const float* __rest
         float sum = 0.f;
 #pragma unroll
         for (int q = 0; q < NCH; ++q) sum += acc[q];   // (lanes past EC hold zeros)
-        const float mean = eq_wave_sum(sum) / EC;
+        const float mean = adf_wave_sum(sum) / EC;
         float var = 0.f;
 #pragma unroll
         for (int q = 0; q < NCH; ++q) if (lane + 64 * q < EC) { const float t = acc[q] - mean; var += t * t; }
-        const float rstd = rsqrtf(eq_wave_sum(var) / EC + 1e-5f);
+        const float rstd = rsqrtf(adf_wave_sum(var) / EC + 1e-5f);
 #pragma unroll
         for (int q = 0; q < NCH; ++q) {
             const int c = lane + 64 * q;
-            if (c < EC) orow[c] = eq_silu((acc[q] - mean) * rstd * ln_w[c] + ln_b[c]);
+            if (c < EC) orow[c] = adf_silu((acc[q] - mean) * rstd * ln_w[c] + ln_b[c]);
         }
     }
 }
@@ -521,7 +505,7 @@ __global__ __launch_bounds__(256) void eq_energy_sum_kernel(const float* __restr
             const float* hr = hid + (size_t)i * F;
             float p = 0.f;
             for (int j = lane; j < F; j += 64) p += w2[j] * hr[j];
-            p = eq_wave_sum(p) + b2[0];
+            p = adf_wave_sum(p) + b2[0];
             if (lane == 0) se[wave] = p;
         }
         __syncthreads();
@@ -734,13 +718,7 @@ __global__ __launch_bounds__(256) void eq_rotate_in_kernel(const float* __restri
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
             if (MT == 0 && t >= 2 * d.M + 1) break;
-            float v = rmx[t];
-#define EQ_ROR(n_) __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x120 + (n_), 0xf, 0xf, false))
-            v = fmaxf(v, EQ_ROR(8));
-            v = fmaxf(v, EQ_ROR(4));
-            v = fmaxf(v, EQ_ROR(2));
-            v = fmaxf(v, EQ_ROR(1));
-#undef EQ_ROR
+            const float v = adf_row16_max(rmx[t]);
             if ((threadIdx.x & 15) == 0) atomicMax(&smax[t], __float_as_uint(v));
         }
     }
@@ -761,7 +739,7 @@ __global__ __launch_bounds__(256) void eq_rotate_in_kernel(const float* __restri
                 const int am = mp < 0 ? -mp : mp;
                 if (am > ml) continue;
                 const int nm = LT - am + 1, sg = mp < 0 ? 1 : 0;
-                const float lift = eq_pow2_lift(__uint_as_float(smax[am == 0 ? 0 : 2 * am - 1 + sg]));
+                const float lift = adf_pow2_lift(__uint_as_float(smax[am == 0 ? 0 : 2 * am - 1 + sg]));
                 const float sv = vals[l * l + l + mp] * lift;
                 const _Float16 hh = (_Float16)sv;
                 const long long row = am == 0 ? el : 2 * el + sg;
@@ -847,12 +825,12 @@ __global__ __launch_bounds__(256) void eq_s2act_kernel(const float* __restrict__
         float g = 0.f;
 #pragma unroll
         for (int r = 0; r < SRT; ++r) g += tp[r] * in[r];
-        const float sv = eq_silu(g);
+        const float sv = adf_silu(g);
         const float* fp = Fm + p * SRT;
 #pragma unroll
         for (int r = 0; r < SRT; ++r) out[r] += fp[r] * sv;
     }
-    out[0] = eq_silu(y0[(size_t)el * ld0 + gate_off + c]);
+    out[0] = adf_silu(y0[(size_t)el * ld0 + gate_off + c]);
 #pragma unroll
     for (int r = 0; r < SRT; ++r) {
         if (r < d.Sr) {
@@ -890,12 +868,7 @@ __device__ __forceinline__ void eq_stg(float* p, float v) { *(__attribute__((add
 // max of a non-negative value over the 64 lanes, left in every lane: four DPP row rotations inside each 16 lanes, then the four
 // rows' results through scalar registers (a 64-lane `__shfl_xor` butterfly is six dependent ds_bpermute round trips)
 __device__ __forceinline__ float eq_wave_max_nonneg(float v) {
-#define EQ_ROR(n_) __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x120 + (n_), 0xf, 0xf, false))
-    v = fmaxf(v, EQ_ROR(8));
-    v = fmaxf(v, EQ_ROR(4));
-    v = fmaxf(v, EQ_ROR(2));
-    v = fmaxf(v, EQ_ROR(1));
-#undef EQ_ROR
+    v = adf_row16_max(v);
     const unsigned int b = __float_as_uint(v);   // non-negative floats order like their bit patterns
     const unsigned int m01 = max((unsigned int)__builtin_amdgcn_readlane((int)b, 0), (unsigned int)__builtin_amdgcn_readlane((int)b, 16));
     const unsigned int m23 = max((unsigned int)__builtin_amdgcn_readlane((int)b, 32), (unsigned int)__builtin_amdgcn_readlane((int)b, 48));
@@ -1031,7 +1004,7 @@ __global__ __launch_bounds__(1024, 4) void eq_s2act_mfma_kernel(const float* __r
                     }
                 }
             mx = eq_wave_max_nonneg(mx);
-            lift = eq_pow2_lift(mx);
+            lift = adf_pow2_lift(mx);
 #pragma unroll
             for (int nb = 0; nb < NBK; ++nb)
 #pragma unroll
@@ -1126,7 +1099,7 @@ __global__ __launch_bounds__(1024, 4) void eq_s2act_mfma_kernel(const float* __r
             for (int nb = 0; nb < NBK; ++nb) {
                 const int c = cb + 32 * nb + cl;
                 float v = acc2[nb][r] * sc2;
-                if (r == 0 && kh == 0) v = eq_silu(gate[nb]);
+                if (r == 0 && kh == 0) v = adf_silu(gate[nb]);
                 if (o & 8u) eq_stg(dst + c, v);
                 mg = fmaxf(mg, fabsf(v));
             }
@@ -1228,10 +1201,10 @@ __global__ __launch_bounds__(256) void eq_alpha_logit_kernel(const float* __rest
         const float* v = row + hd * A;
         float sum = 0.f;
         for (int a = lane; a < A; a += 64) sum += v[a];
-        const float mean = eq_wave_sum(sum) / A;
+        const float mean = adf_wave_sum(sum) / A;
         float q = 0.f;
         for (int a = lane; a < A; a += 64) { const float u = v[a] - mean; q += u * u; }
-        const float rstd = rsqrtf(eq_wave_sum(q) / A + 1e-5f);
+        const float rstd = rsqrtf(adf_wave_sum(q) / A + 1e-5f);
         float acc = 0.f;
         for (int a = lane; a < A; a += 64) {
             const float u = (v[a] - mean) * rstd * lnw[a] + lnb[a];
@@ -1239,7 +1212,7 @@ __global__ __launch_bounds__(256) void eq_alpha_logit_kernel(const float* __rest
             const float sl = 0.6f * u + 0.4f * u * (2.0f / (1.0f + expf(-u)) - 1.0f);
             acc += sl * adot[hd * A + a];
         }
-        acc = eq_wave_sum(acc);
+        acc = adf_wave_sum(acc);
         if (lane == 0) logit[(size_t)el * NH + hd] = acc;
     }
 }
@@ -1463,7 +1436,7 @@ __global__ __launch_bounds__(256) void eq_force_out_kernel(const float* __restri
         const float w = w1[i];
         a0 += r[i] * w; a1 += r[HV + i] * w; a2 += r[2 * HV + i] * w;
     }
-    a0 = eq_wave_sum(a0); a1 = eq_wave_sum(a1); a2 = eq_wave_sum(a2);
+    a0 = adf_wave_sum(a0); a1 = adf_wave_sum(a1); a2 = adf_wave_sum(a2);
     if (lane == 0) { f[3 * n] = a0; f[3 * n + 1] = a1; f[3 * n + 2] = a2; }
 }
 
@@ -1650,7 +1623,7 @@ __global__ void eq_to_grid_kernel(const float* __restrict__ h1, const float* __r
         float a = 0.f;
 #pragma unroll
         for (int s = 0; s < S; ++s) a += T[p * S + s] * in[s];
-        gr[(size_t)p * d.F] = silu ? eq_silu(a) : a;
+        gr[(size_t)p * d.F] = silu ? adf_silu(a) : a;
     }
 }
 
@@ -1708,7 +1681,7 @@ __global__ __launch_bounds__(512, 2) void eq_to_grid_mfma_kernel(const float* __
                 mx = fmaxf(mx, fabsf(v));
             }
         mx = eq_wave_max_nonneg(mx);
-        const float lift = eq_pow2_lift(mx);
+        const float lift = adf_pow2_lift(mx);
         eqhalf8 bh[4], bl[4];
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
@@ -1741,11 +1714,12 @@ __global__ __launch_bounds__(512, 2) void eq_to_grid_mfma_kernel(const float* __
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int pp = 32 * pb + (r & 3) + 8 * (r >> 2) + 4 * kh;
-                const float v = acc[r] * sc, w = silu ? eq_silu(v) : v;
+                const float v = acc[r] * sc, w = silu ? adf_silu(v) : v;
                 if (pp < G) { gr[(size_t)pp * F] = w; omx = fmaxf(omx, fabsf(w)); }
             }
         }
         if (node_mag) {  // float bits of a non-negative value order like unsigned integers
+            // kept inline: as a call to lanes.h this butterfly reorders the kernel's instructions (tools/device_asm_diff.py)
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) omx = fmaxf(omx, __shfl_xor(omx, o));
             if (lane == 0) atomicMax(node_mag + (n - n0), __float_as_uint(omx));
@@ -1794,7 +1768,7 @@ __global__ __launch_bounds__(512, 1) void eq_from_grid_mfma_kernel(const float* 
 #pragma unroll
                 for (int j = 0; j < 8; ++j) mx = fmaxf(mx, fabsf(v[c][j]));
             mx = fmaxf(mx, __shfl_xor(mx, 32));
-            const float lift = eq_pow2_lift(mx);
+            const float lift = adf_pow2_lift(mx);
             eqf32x16 acc[2];
 #pragma unroll
             for (int sb = 0; sb < 2; ++sb)
@@ -1965,7 +1939,7 @@ __global__ __launch_bounds__(256) void eq_gemm_kernel(const float* __restrict__ 
             const int col = nb + 4 * tc + j;
             if (col >= N) continue;
             float v = acc[i][j] + (bias ? bias[col] : 0.f);
-            if (act == 2) v = eq_silu(v);
+            if (act == 2) v = adf_silu(v);
             if (accumulate) v += cp[col];
             cp[col] = v;
         }

@@ -15,7 +15,8 @@
 // The one departure: a system without a free atom.  The reference takes .max() of an empty slice there and raises; here
 // the system's force maximum counts as 0, so energy_forces_within_threshold is decided by its energy alone.  In the is2rs
 // entry such a system has a NaN mean distance (0 / 0) and lies below no threshold, as numpy's mean of an empty array.
-#include "common.h"
+#include "base.h"
+#include "lanes.h"
 
 #define EV_CHECK_LAUNCH() ADF_HIP_CHECK(hipGetLastError())
 
@@ -31,24 +32,6 @@ __device__ __forceinline__ float ev_sub(float a, float b) { return a - b; }
 __device__ __forceinline__ float ev_mul(float a, float b) { return a * b; }
 __device__ __forceinline__ float ev_div(float a, float b) { return a / b; }
 __device__ __forceinline__ double ev_dadd(double a, double b) { return a + b; }
-
-__device__ __forceinline__ double ev_wsum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = ev_dadd(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
-__device__ __forceinline__ int ev_wsum_i(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-__device__ __forceinline__ float ev_wmax(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
 
 // torch.norm(v, p=2, dim=-1) / linalg.vector_norm of a float32 row: torch's CPU reduction accumulates the squares with a
 // fused multiply-add chain (checked bit for bit on 1e5 random rows; with separately rounded adds one row in ten differs)
@@ -91,9 +74,9 @@ __global__ __launch_bounds__(64) void ev_s2ef_part_kernel(
         smag += (double)fabsf(ev_sub(np_, nt));
         cnt += 1;
     }
-    sx = ev_wsum(sx); sy = ev_wsum(sy); sz = ev_wsum(sz); scos = ev_wsum(scos); smag = ev_wsum(smag);
-    cnt = ev_wsum_i(cnt);
-    fmax = ev_wmax(fmax);
+    sx = adf_wave_sum(sx); sy = adf_wave_sum(sy); sz = adf_wave_sum(sz); scos = adf_wave_sum(scos); smag = adf_wave_sum(smag);
+    cnt = adf_wave_sum(cnt);
+    fmax = adf_wave_max(fmax);
     if (lane == 0) {
         const float ee = fabsf(ev_sub(E_tgt[b], ev_add(ev_mul(E_pred[b], std_E), mean_E)));
         double* o = part + (size_t)EV_PART * b;
@@ -159,7 +142,7 @@ __global__ __launch_bounds__(64) void ev_is2rs_part_kernel(
     float c[9], inv[9];
 #pragma unroll
     for (int k = 0; k < 9; ++k) c[k] = cell[9 * (size_t)b + k];
-    {
+    {   // (not cell3.h's adf_inv3: unguarded, assigned row by row, and compiled without contraction here)
         const float m00 = c[4] * c[8] - c[5] * c[7], m01 = c[5] * c[6] - c[3] * c[8], m02 = c[3] * c[7] - c[4] * c[6];
         const float det = c[0] * m00 + c[1] * m01 + c[2] * m02;
         const float r = 1.0f / det;
@@ -192,12 +175,12 @@ __global__ __launch_bounds__(64) void ev_is2rs_part_kernel(
         sd += (double)ev_norm3(m);
         cnt += 1;
     }
-    sa = ev_wsum(sa); sq = ev_wsum(sq); sd = ev_wsum(sd);
-    cnt = ev_wsum_i(cnt);
+    sa = adf_wave_sum(sa); sq = adf_wave_sum(sq); sd = adf_wave_sum(sd);
+    cnt = adf_wave_sum(cnt);
     const double mean = sd / (double)cnt;   // no free atom: 0 / 0 = NaN, below no threshold
     int below = 0;
     for (int i = lane; i < T; i += 64) below += mean < thresholds[i] ? 1 : 0;
-    below = ev_wsum_i(below);
+    below = adf_wave_sum(below);
     if (lane == 0) {
         double* o = part + (size_t)EV_PART * b;
         o[0] = sa; o[1] = sq; o[2] = (double)cnt; o[3] = (double)below;

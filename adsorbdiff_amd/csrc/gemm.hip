@@ -27,12 +27,6 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 #define BK 32
 #define LDT 129
 
-__device__ __forceinline__ float ssilu_f(float x) {
-    // ScaledSiLU: silu(x) * (1/0.6)   (gemnet_oc/layers/base_layers.py:65-72)
-    float s = x / (1.0f + expf(-x));
-    return s * 1.6666666666666667f;
-}
-
 template <int ACT>
 __global__ __launch_bounds__(256) void adf_gemm_kernel(const float* __restrict__ A, int lda,
                                                         const float* __restrict__ W, int ldw,
@@ -130,7 +124,7 @@ __global__ __launch_bounds__(256) void adf_gemm_kernel(const float* __restrict__
                 const int row = m0 + wm + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
                 if (row < M) {
                     float v = acc[i][j][r] + bv;
-                    if (ACT) v = ssilu_f(v);
+                    if (ACT) v = adf_ssilu(v);
                     C[(size_t)row * ldc + col] = v;
                 }
             }

@@ -50,21 +50,6 @@ typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 #define TLD2 64
 #define HLD 40  // halves per LDS row (32 + 8 pad)
 
-// 2^e with mx 2^e in [2^14, 2^15); 1 for mx == 0 or non-finite
-__device__ __forceinline__ float adf_pow2_lift(float mx) {
-    if (!(mx > 0.f) || !(mx < 3.0e38f)) return 1.0f;
-    int e;
-    (void)frexpf(mx, &e);
-    e = 15 - e;
-    e = e > 120 ? 120 : (e < -120 ? -120 : e);
-    return ldexpf(1.0f, e);
-}
-
-__device__ __forceinline__ float ssilu16(float x) {
-    float s = x / (1.0f + expf(-x));
-    return s * 1.6666666666666667f;
-}
-
 // Tile geometry of a form (STREAM: weights streamed as register fragments; else staged through LDS) and an epilogue: the
 // one place it is written down, read by the kernel and by the launch helper.  A workgroup is 4 waves, NWM along M and NWN
 // along N; a wave's tile is 32 MI rows x 32 NJ columns of MFMA 32x32 blocks.
@@ -384,7 +369,7 @@ __global__ __launch_bounds__(g16_tile_of(EPI, STREAM).NT, 2) void adf_gemm_f16x3
                         const int lr = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
                         const float sc = isc * rinv[wm + 32 * i + lr];
                         float v0 = acc[i][2 * jj][r] * sc + bv0, v1 = acc[i][2 * jj + 1][r] * sc + bv1;
-                        if (ACT) { v0 = ssilu16(v0); v1 = ssilu16(v1); }
+                        if (ACT) { v0 = adf_ssilu(v0); v1 = adf_ssilu(v1); }
                         T[lr * TLD2 + q] = v0;
                         T[lr * TLD2 + 32 + q] = v1;
                     }
@@ -430,7 +415,7 @@ __global__ __launch_bounds__(g16_tile_of(EPI, STREAM).NT, 2) void adf_gemm_f16x3
                     const int row = m0 + wm + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
                     if (row < M) {
                         float v = acc[i][j][r] * (isc * rinv[row - m0]) + bv;
-                        if (ACT) v = ssilu16(v);
+                        if (ACT) v = adf_ssilu(v);
                         if (ep.accumulate) v += C[(size_t)row * ldc + col];
                         C[(size_t)row * ldc + col] = v;
                         if (ep.out_mag) atomicMax(ep.out_mag + row, __float_as_uint(fabsf(v)));
@@ -695,6 +680,7 @@ __global__ __launch_bounds__(256) void adf_rowmag_kernel(const float* __restrict
             mx = fmaxf(fmaxf(fmaxf(mx, fabsf(v.x)), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)));
         }
     }
+    // kept inline: as a call to lanes.h this butterfly reorders the kernel's instructions (tools/device_asm_diff.py)
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
     if (lane == 0) mag[r] = mx;
@@ -762,8 +748,7 @@ __global__ void adf_absmax_kernel(const float* __restrict__ w, long long n, unsi
     float m = 0.f;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
         m = fmaxf(m, fabsf(w[i]));
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    m = adf_wave_max(m);
     if ((threadIdx.x & 63) == 0) atomicMax(out_bits, __float_as_uint(m));  // non-negative floats order like uints
 }
 

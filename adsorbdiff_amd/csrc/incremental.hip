@@ -64,6 +64,7 @@ __global__ __launch_bounds__(256) void adf_inc_flags_kernel(const int32_t* __res
         tf[i] = (unsigned char)t;
         deg = t ? e1 - e0 : 0;
     }
+    // kept inline: as a call to lanes.h this butterfly reorders the kernel's instructions (tools/device_asm_diff.py)
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) deg += __shfl_xor(deg, o);
     if ((threadIdx.x & 63) == 0 && deg) atomicAdd(edge_total, deg);

@@ -50,17 +50,6 @@
 #define MSG_EXP_NOXC 0   // timing experiments only (wrong results): 1 no xc gathers; 2 no record gathers at all
 #endif
 
-__device__ __forceinline__ float wave_min(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-
 // Geometry of THIS kernel (message_bwd.hip keeps message.h's 8 waves): FWD_WAVES waves per workgroup share the slice's weight
 // image; FWD_AHEAD = gather rows requested ahead of the row being consumed (4: 80 landing registers, 2: 40).
 #ifndef FWD_WAVES

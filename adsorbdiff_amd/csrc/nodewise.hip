@@ -7,11 +7,6 @@
 //   :647-650,688-697 PaiNNOutput / GatedEquivariantBlock
 #include "common.h"
 
-__device__ __forceinline__ float ssilu_d(float x) {
-    float s = x / (1.0f + expf(-x));
-    return s * 1.6666666666666667f;
-}
-
 // x[n,:] = emb[Z[n]-1,:]   (gemnet_oc/layers/embedding_block.py:42).  vec = 0 (painn_denoising.py:426) is
 // not materialised: the first message layer runs in its vec-is-zero mode.
 // Z outside [1, num_elements] (torch's nn.Embedding raises IndexError there): flagged, row read clamped.
@@ -47,8 +42,7 @@ __global__ __launch_bounds__(256) void adf_layernorm_kernel(const float* __restr
         vals[i] = c < h4 ? xr[c] : make_float4(0.f, 0.f, 0.f, 0.f);
         sum += (vals[i].x + vals[i].y) + (vals[i].z + vals[i].w);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+    sum = adf_wave_sum(sum);
     const float mean = sum / (float)H;
     float sq = 0.f;
 #pragma unroll
@@ -57,8 +51,7 @@ __global__ __launch_bounds__(256) void adf_layernorm_kernel(const float* __restr
             const float dx = vals[i].x - mean, dy = vals[i].y - mean, dz = vals[i].z - mean, dw = vals[i].w - mean;
             sq += (dx * dx + dy * dy) + (dz * dz + dw * dw);
         }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o);
+    sq = adf_wave_sum(sq);
     const float rstd = 1.0f / sqrtf(sq / (float)H + 1e-5f);
     float4* yr = reinterpret_cast<float4*>(y + (size_t)row * H);
     const float4* w4 = reinterpret_cast<const float4*>(w);
@@ -76,6 +69,7 @@ __global__ __launch_bounds__(256) void adf_layernorm_kernel(const float* __restr
         }
     }
     if (out_mag) {  // the row's magnitude for the f16x3 product that reads it (gemm16.hip row lifts)
+        // kept inline: as a call to lanes.h this butterfly reorders the kernel's instructions (tools/device_asm_diff.py)
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) mg = fmaxf(mg, __shfl_xor(mg, o));
         if (lane == 0) out_mag[row] = mg;
@@ -170,7 +164,7 @@ __global__ void adf_head_gate_kernel(const float* __restrict__ o, const float* _
         const float4* orow = reinterpret_cast<const float4*>(o + (size_t)n * 2 * Cout);
         const float4 xs = orow[c], g = orow[c4 + c];
         reinterpret_cast<float4*>(xout + (size_t)n * Cout)[c] =
-            make_float4(ssilu_d(xs.x), ssilu_d(xs.y), ssilu_d(xs.z), ssilu_d(xs.w));
+            make_float4(adf_ssilu(xs.x), adf_ssilu(xs.y), adf_ssilu(xs.z), adf_ssilu(xs.w));
         const float4* tb = reinterpret_cast<const float4*>(t2 + (size_t)n * 3 * Cout);
         float4* vb = reinterpret_cast<float4*>(vout + (size_t)n * 3 * Cout);
 #pragma unroll
@@ -190,7 +184,7 @@ __global__ void adf_head_xact_kernel(const float* __restrict__ o, float* __restr
         const int n = (int)(i / c4), c = (int)(i - (long long)n * c4);
         const float4 xs = reinterpret_cast<const float4*>(o + (size_t)n * 2 * Cout)[c];
         reinterpret_cast<float4*>(xout + (size_t)n * Cout)[c] =
-            make_float4(ssilu_d(xs.x), ssilu_d(xs.y), ssilu_d(xs.z), ssilu_d(xs.w));
+            make_float4(adf_ssilu(xs.x), adf_ssilu(xs.y), adf_ssilu(xs.z), adf_ssilu(xs.w));
     }
 }
 
@@ -212,6 +206,7 @@ __global__ __launch_bounds__(256) void adf_head_final_kernel(const float* __rest
         t1 += v[((size_t)n * 3 + 1) * C + c] * w2;
         t2 += v[((size_t)n * 3 + 2) * C + c] * w2;
     }
+    // kept inline: as a call to lanes.h this butterfly reorders the kernel's instructions (tools/device_asm_diff.py)
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         g += __shfl_xor(g, o); t0 += __shfl_xor(t0, o); t1 += __shfl_xor(t1, o); t2 += __shfl_xor(t2, o);

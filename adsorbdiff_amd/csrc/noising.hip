@@ -12,19 +12,14 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "common.h"
+#include "base.h"
+#include "lanes.h"
 
 #define NZ_CHECK_LAUNCH() ADF_HIP_CHECK(hipGetLastError())
 
 // eps grid of the IGSO(3) tables (rot_utils.py:9-10)
 #define NZ_MIN_EPS 0.01
 #define NZ_MAX_EPS 2.0
-
-__device__ __forceinline__ double nz_wsum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 // ------------------------------------------------------------------------------------------------ generator
 __device__ __forceinline__ void nz_philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
@@ -135,6 +130,7 @@ extern "C" int32_t adf_sampler_draws(int64_t seed, const int64_t* keys, const in
     }
     hipStream_t s = (hipStream_t)stream;
     if (site) {
+        // (not host_util.h's adf_errword: a failed allocation here reports through ADF_HIP_CHECK, and adf_pool words it otherwise)
         int32_t* bad = nullptr;
         int32_t host_bad = 0;
         ADF_HIP_CHECK(hipMalloc(&bad, sizeof(int32_t)));
@@ -206,7 +202,7 @@ __device__ __forceinline__ void nz_ads_center(const float* __restrict__ pos, con
             for (int k = 0; k < 3; ++k) s[k] += (double)pos[3 * a + k];
             s[3] += 1.0;
         }
-    for (int i = 0; i < 4; ++i) s[i] = nz_wsum(s[i]);
+    for (int i = 0; i < 4; ++i) s[i] = adf_wave_sum(s[i]);
     const double cnt = s[3] > 1.0 ? s[3] : 1.0;
     for (int k = 0; k < 3; ++k) c[k] = (float)(s[k] / cnt);
 }

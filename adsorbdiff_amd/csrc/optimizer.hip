@@ -77,6 +77,7 @@ __global__ void __launch_bounds__(OP_THREADS) op_sqnorm_stage1_kernel(const op_t
         }
     }
     // fixed shuffle tree within the wave, then the waves in wave order through LDS
+    // kept inline: as a call to lanes.h this butterfly reorders the kernel's instructions (tools/device_asm_diff.py)
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
     __shared__ float ws[OP_THREADS / 64];

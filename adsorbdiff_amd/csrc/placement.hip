@@ -14,9 +14,9 @@
 #include <float.h>
 #include <math.h>
 
-#include "common.h"
-
-#define PL_EPS 1e-7   // ASE's wrap eps: f -> (f + eps) mod 1 - eps
+#include "host_util.h"
+#include "cell3.h"
+#include "lanes.h"
 
 enum { PL_ERR_Z = 1, PL_ERR_BINDING = 2, PL_ERR_RANGE = 4 };
 
@@ -31,47 +31,25 @@ __device__ __forceinline__ void pl_load_frame(const float* __restrict__ cell, pl
 #pragma unroll
     for (int k = 0; k < 9; ++k) F.c[k] = (double)cell[k];
     const double* c = F.c;
-    const double cx0 = c[4] * c[8] - c[5] * c[7], cx1 = c[5] * c[6] - c[3] * c[8], cx2 = c[3] * c[7] - c[4] * c[6];
-    const double vol = c[0] * cx0 + c[1] * cx1 + c[2] * cx2;
-    const double iv = vol != 0.0 ? 1.0 / vol : 0.0;
-    F.inv[0] = cx0 * iv; F.inv[3] = cx1 * iv; F.inv[6] = cx2 * iv;
-    F.inv[1] = (c[2] * c[7] - c[1] * c[8]) * iv; F.inv[4] = (c[0] * c[8] - c[2] * c[6]) * iv; F.inv[7] = (c[1] * c[6] - c[0] * c[7]) * iv;
-    F.inv[2] = (c[1] * c[5] - c[2] * c[4]) * iv; F.inv[5] = (c[2] * c[3] - c[0] * c[5]) * iv; F.inv[8] = (c[0] * c[4] - c[1] * c[3]) * iv;
-    // a x b
+    adf_inv3(c, F.inv);
+    // a x b (not cell3.h's adf_cross3: the call reorders the kernels' instructions)
     const double nx = c[1] * c[5] - c[2] * c[4], ny = c[2] * c[3] - c[0] * c[5], nz = c[0] * c[4] - c[1] * c[3];
     const double nn = sqrt(nx * nx + ny * ny + nz * nz);
     F.n[0] = nx / nn; F.n[1] = ny / nn; F.n[2] = nz / nn;
 #pragma unroll
     for (int k = 0; k < 3; ++k) F.cc[k] = 0.5 * (c[k] + c[3 + k] + c[6 + k]);
 }
-__device__ __forceinline__ double pl_wrap1(double f) { return (f + PL_EPS) - floor(f + PL_EPS) - PL_EPS; }
 // ase.geometry.wrap_positions about the cell centre: fractional coordinates, the periodic ones into [-eps, 1 - eps), back
 __device__ __forceinline__ void pl_wrap(const pl_frame& F, const int32_t* __restrict__ pbc, double* p) {
     double f[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         f[k] = p[0] * F.inv[k] + p[1] * F.inv[3 + k] + p[2] * F.inv[6 + k];
-        if (pbc[k]) f[k] = pl_wrap1(f[k]);
+        if (pbc[k]) f[k] = adf_mod1_eps(f[k]);
     }
 #pragma unroll
     for (int k = 0; k < 3; ++k) p[k] = f[0] * F.c[k] + f[1] * F.c[3 + k] + f[2] * F.c[6 + k];
 }
-__device__ __forceinline__ double pl_wmax(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ double pl_wmin(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ int pl_wsum(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // ------------------------------------------------------------------------------------------------ placements
 struct pl_place_params {
     const float* slab_pos; const float* cell; const int32_t* slab_Z; const int32_t* slab_offset;
@@ -191,8 +169,8 @@ __global__ __launch_bounds__(64) void pl_place_kernel(pl_place_params q) {
     if (s1 == s0)   // no slab atom: the adsorbate's radii are still checked
         for (int a = 0; a < na; ++a) { const int za = q.ads_Z[a0 + a]; bad = bad || za < 0 || za >= q.num_radii; }
     if (__ballot(bad) != 0ull && lane == 0) atomicOr(q.err, PL_ERR_Z);
-    cnt = pl_wsum(cnt);
-    best = pl_wmax(best);
+    cnt = adf_wave_sum(cnt);
+    best = adf_wave_max(best);
     const double sn = cnt > 0 ? best : 0.0;
     if (lane == 0) {
         q.scaled_normal[p] = sn;
@@ -206,18 +184,13 @@ __global__ __launch_bounds__(64) void pl_place_kernel(pl_place_params q) {
     }
 }
 
-static int32_t pl_read_error(int32_t* err, hipStream_t s, const char* who, int32_t num_radii, int32_t num_masses) {
-    int32_t bad = 0;
-    ADF_HIP_CHECK(hipMemcpyAsync(&bad, err, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    ADF_HIP_CHECK(hipStreamSynchronize(s));
-    if (bad & PL_ERR_RANGE) { adf_set_error("%s: an offset, slab index or output row out of range", who); return ADF_EINVAL; }
-    if (bad & PL_ERR_BINDING) { adf_set_error("%s: binding_idx outside the adsorbate", who); return ADF_EINVAL; }
-    if (bad & PL_ERR_Z) {
-        adf_set_error("%s: atomic number outside [0, %d) (rows of the radius table) or [0, %d) (mass table)", who, num_radii,
-                      num_masses);
-        return ADF_EINVAL;
-    }
-    return ADF_OK;
+static int32_t pl_finish(adf_errword& err, hipStream_t s, const char* who, int32_t num_radii, int32_t num_masses) {
+    const adf_errrow rows[] = {
+        {PL_ERR_RANGE, ADF_EINVAL, "%s: an offset, slab index or output row out of range"},
+        {PL_ERR_BINDING, ADF_EINVAL, "%s: binding_idx outside the adsorbate"},
+        {PL_ERR_Z, ADF_EINVAL, "%s: atomic number outside [0, %d) (rows of the radius table) or [0, %d) (mass table)", num_radii,
+         num_masses}};
+    return err.finish(s, who, rows);
 }
 
 extern "C" int32_t adf_place_adsorbates(const adf_batch* slabs, const int32_t* slab_of, const float* site, const double* draws,
@@ -235,10 +208,8 @@ extern "C" int32_t adf_place_adsorbates(const adf_batch* slabs, const int32_t* s
     if (mode == 1 && !binding_idx) { adf_set_error("place_adsorbates: heuristic placement needs binding_idx"); return ADF_EINVAL; }
     if (!(interstitial_gap >= 0.f && interstitial_gap < 5.f)) { adf_set_error("place_adsorbates: interstitial_gap %g outside [0, 5)", (double)interstitial_gap); return ADF_EINVAL; }
     hipStream_t s = (hipStream_t)stream;
-    adf_pool tmp;   // the error word; freed on every return (after the synchronisation below)
-    int32_t* err = nullptr;
-    ADF_TRY(tmp.alloc(&err, 1));
-    ADF_HIP_CHECK(hipMemsetAsync(err, 0, sizeof(int32_t), s));
+    adf_errword err;   // freed on every return (after the synchronisation in finish)
+    ADF_TRY(err.create(s));
     pl_place_params q = {};
     q.slab_pos = slabs->pos; q.cell = slabs->cell; q.slab_Z = slabs->atomic_numbers; q.slab_offset = slabs->atom_offset;
     q.B = slabs->num_systems; q.N = slabs->num_atoms;
@@ -247,10 +218,10 @@ extern "C" int32_t adf_place_adsorbates(const adf_batch* slabs, const int32_t* s
     q.radii = radii; q.num_radii = num_radii; q.masses = masses; q.num_masses = num_masses;
     q.gap = (double)interstitial_gap; q.mode = mode; q.binding_idx = binding_idx; q.pbc = pbc;
     q.P = P; q.out_row = out_row; q.out_rows = out_rows;
-    q.out_pos = out_pos; q.scaled_normal = scaled_normal; q.n_combos = n_combos; q.rot_meta = rot_meta; q.err = err;
+    q.out_pos = out_pos; q.scaled_normal = scaled_normal; q.n_combos = n_combos; q.rot_meta = rot_meta; q.err = err.dev;
     hipLaunchKernelGGL(pl_place_kernel, dim3(P), dim3(64), 0, s, q);
     ADF_HIP_CHECK(hipGetLastError());
-    return pl_read_error(err, s, "place_adsorbates", num_radii, num_masses);
+    return pl_finish(err, s, "place_adsorbates", num_radii, num_masses);
 }
 
 // ------------------------------------------------------------------------------------------------ candidate sites
@@ -288,7 +259,7 @@ __global__ void pl_candidates_kernel(const float* __restrict__ tri, const int32_
     bool in = true;
     for (int k = 0; k < 2; ++k) {   // along a and b; c is not periodic for a site
         const double f = x[0] * F.inv[k] + x[1] * F.inv[3 + k] + x[2] * F.inv[6 + k];
-        in = in && f >= -PL_EPS && f < 1.0 - PL_EPS;
+        in = in && f >= -ADF_WRAP_EPS && f < 1.0 - ADF_WRAP_EPS;
     }
     for (int k = 0; k < 3; ++k) cand[3 * (size_t)c + k] = (float)x[k];
     keep[c] = in ? 1 : 0;
@@ -301,14 +272,12 @@ extern "C" int32_t adf_place_site_candidates(const float* tri, const int32_t* tr
     if (!tri || !tri_offset || !per_tri || !cand_offset || !cand_slab || !cell || !draws || !cand || !keep || B <= 0 ||
         num_candidates <= 0) { adf_set_error("place_site_candidates: bad argument"); return ADF_EINVAL; }
     hipStream_t s = (hipStream_t)stream;
-    adf_pool tmp;
-    int32_t* err = nullptr;
-    ADF_TRY(tmp.alloc(&err, 1));
-    ADF_HIP_CHECK(hipMemsetAsync(err, 0, sizeof(int32_t), s));
+    adf_errword err;   // freed on every return (after the synchronisation in finish)
+    ADF_TRY(err.create(s));
     hipLaunchKernelGGL(pl_candidates_kernel, dim3((num_candidates + 255) / 256), dim3(256), 0, s, tri, tri_offset, per_tri,
-                       cand_offset, cand_slab, cell, draws, B, num_candidates, cand, keep, err);
+                       cand_offset, cand_slab, cell, draws, B, num_candidates, cand, keep, err.dev);
     ADF_HIP_CHECK(hipGetLastError());
-    return pl_read_error(err, s, "place_site_candidates", 0, 0);
+    return pl_finish(err, s, "place_site_candidates", 0, 0);
 }
 
 // ------------------------------------------------------------------------------------------------ interstitial distances
@@ -366,7 +335,7 @@ __global__ __launch_bounds__(64) void pl_gap_kernel(const float* __restrict__ po
         }
     }
     if (__ballot(bad) != 0ull && lane == 0) atomicOr(err, PL_ERR_Z);
-    best = pl_wmin(best);
+    best = adf_wave_min(best);
     if (lane == 0) out[b] = (float)best;
 }
 
@@ -378,12 +347,10 @@ extern "C" int32_t adf_interstitial_distances(const adf_batch* b, const int32_t*
     if (!b->pos || !b->cell || !b->atomic_numbers || !b->atom_offset) { adf_set_error("interstitial_distances: null batch array"); return ADF_EINVAL; }
     if (num_radii <= 0 || num_masses <= 0) { adf_set_error("interstitial_distances: empty radius or mass table"); return ADF_EINVAL; }
     hipStream_t s = (hipStream_t)stream;
-    adf_pool tmp;
-    int32_t* err = nullptr;
-    ADF_TRY(tmp.alloc(&err, 1));
-    ADF_HIP_CHECK(hipMemsetAsync(err, 0, sizeof(int32_t), s));
+    adf_errword err;   // freed on every return (after the synchronisation in finish)
+    ADF_TRY(err.create(s));
     hipLaunchKernelGGL(pl_gap_kernel, dim3(b->num_systems), dim3(64), 0, s, b->pos, b->cell, b->atomic_numbers, tags,
-                       b->atom_offset, b->num_systems, b->num_atoms, radii, num_radii, masses, num_masses, pbc, out, err);
+                       b->atom_offset, b->num_systems, b->num_atoms, radii, num_radii, masses, num_masses, pbc, out, err.dev);
     ADF_HIP_CHECK(hipGetLastError());
-    return pl_read_error(err, s, "interstitial_distances", num_radii, num_masses);
+    return pl_finish(err, s, "interstitial_distances", num_radii, num_masses);
 }

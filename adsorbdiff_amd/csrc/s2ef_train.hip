@@ -24,12 +24,6 @@
 enum { S2_PART = 6 };         // per-system partials: |dE| sum, force-norm sum, |S|, energy abs error, force abs error, free atoms
 enum { EH_ROWS = 64, EH_COLS = 64 };
 
-__device__ __forceinline__ float s2_wsum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = __fadd_rn(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
 // one wave per system: partial sums of the system
 __global__ __launch_bounds__(64) void s2_loss_part_kernel(
     const float* __restrict__ E_pred, const float* __restrict__ F_pred, const float* __restrict__ E_tgt,
@@ -53,7 +47,7 @@ __global__ __launch_bounds__(64) void s2_loss_part_kernel(
         }
         if (in_s) sn += sqrtf(q);
     }
-    sn = s2_wsum(sn); cnt = s2_wsum(cnt); fae = s2_wsum(fae); nfree = s2_wsum(nfree);
+    sn = adf_wave_sum(sn); cnt = adf_wave_sum(cnt); fae = adf_wave_sum(fae); nfree = adf_wave_sum(nfree);
     if (lane == 0) {
         const float p = E_pred[b], t = E_tgt[b];
         float* o = part + (size_t)S2_PART * b;

@@ -21,11 +21,12 @@
 #include <limits.h>
 #include <math.h>
 
-#include "common.h"
+#include "host_util.h"
+#include "cell3.h"
+#include "lanes.h"
 
 #define SS_THREADS 256
 #define SS_OP_TILE 128      // operations staged in LDS at a time: 12 doubles each, 12 KiB
-#define SS_EPS 1e-7         // ASE's wrap eps (placement.hip: PL_EPS)
 #define SS_COS_MIN 1e-5     // a corner whose cosine is not at least this makes the triangle "obtuse"
 
 enum { SS_ERR_RANGE = 1, SS_ERR_CELL = 2 };
@@ -40,8 +41,8 @@ __device__ __forceinline__ void ss_load_frame(const float* __restrict__ cell, ss
     double a[3], b[3], n[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) { a[k] = (double)cell[k]; b[k] = (double)cell[3 + k]; }
-    n[0] = a[1] * b[2] - a[2] * b[1]; n[1] = a[2] * b[0] - a[0] * b[2]; n[2] = a[0] * b[1] - a[1] * b[0];
-    const double nn = sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+    adf_cross3(a, b, n);
+    const double nn = sqrt(adf_dot3(n, n));
     F.ok = nn > 0.0 && nn < INFINITY;
     const double in = F.ok ? 1.0 / nn : 0.0;
 #pragma unroll
@@ -49,10 +50,11 @@ __device__ __forceinline__ void ss_load_frame(const float* __restrict__ cell, ss
 #pragma unroll
     for (int k = 0; k < 3; ++k) { F.M[3 * k] = a[k]; F.M[3 * k + 1] = b[k]; F.M[3 * k + 2] = n[k]; }
     // rows of the inverse: b x n, n x a, a x b over det = a . (b x n)
-    const double r0[3] = {b[1] * n[2] - b[2] * n[1], b[2] * n[0] - b[0] * n[2], b[0] * n[1] - b[1] * n[0]};
-    const double r1[3] = {n[1] * a[2] - n[2] * a[1], n[2] * a[0] - n[0] * a[2], n[0] * a[1] - n[1] * a[0]};
-    const double r2[3] = {a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]};
-    const double det = a[0] * r0[0] + a[1] * r0[1] + a[2] * r0[2];
+    double r0[3], r1[3], r2[3];
+    adf_cross3(b, n, r0);
+    adf_cross3(n, a, r1);
+    adf_cross3(a, b, r2);
+    const double det = adf_dot3(a, r0);
     const double id = F.ok && det != 0.0 ? 1.0 / det : 0.0;
 #pragma unroll
     for (int k = 0; k < 3; ++k) { F.Mi[k] = r0[k] * id; F.Mi[3 + k] = r1[k] * id; F.Mi[6 + k] = r2[k] * id; }
@@ -77,26 +79,15 @@ __device__ __forceinline__ void ss_store_inside(const ss_frame& F, const double 
 #pragma unroll
     for (int k = 0; k < 3; ++k) f[k] = F.Mi[3 * k] * x[0] + F.Mi[3 * k + 1] * x[1] + F.Mi[3 * k + 2] * x[2];
 #pragma unroll
-    for (int k = 0; k < 2; ++k) f[k] = (f[k] + SS_EPS) - floor(f[k] + SS_EPS) - SS_EPS;
+    for (int k = 0; k < 2; ++k) f[k] = adf_mod1_eps(f[k]);
 #pragma unroll
     for (int k = 0; k < 3; ++k) out[k] = (float)(F.M[3 * k] * f[0] + F.M[3 * k + 1] * f[1] + F.M[3 * k + 2] * f[2]);
 }
 
-// workgroup minimum / sum of an int, left in every thread; red: SS_THREADS / 64 words of LDS
-__device__ __forceinline__ int ss_block_min(int v, int* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-    __syncthreads();                                    // the previous reads of red are done
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    v = red[0];
-#pragma unroll
-    for (int w = 1; w < SS_THREADS / 64; ++w) v = min(v, red[w]);
-    return v;
-}
+// workgroup sum of an int, left in every thread; red: SS_THREADS / 64 words of LDS.  Kept beside lanes.h's adf_block_reduce:
+// through it the combine of ss_reduce_kernel compiles to other instructions (tools/device_asm_diff.py)
 __device__ __forceinline__ int ss_block_sum(int v, int* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    v = adf_wave_sum(v);
     __syncthreads();
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
     __syncthreads();
@@ -247,18 +238,10 @@ __global__ __launch_bounds__(SS_THREADS) void ss_candidates_kernel(
     }
 }
 
-static int32_t ss_read_error(int32_t* err, hipStream_t s, const char* who) {
-    int32_t bad = 0;
-    ADF_HIP_CHECK(hipMemcpyAsync(&bad, err, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    ADF_HIP_CHECK(hipStreamSynchronize(s));
-    if (bad & SS_ERR_RANGE) {
-        adf_set_error("%s: malformed offsets (not ascending, outside their arrays, a slab or operation index out of range, or "
-                      "more candidates than the tables hold)", who);
-        return ADF_EINVAL;
-    }
-    if (bad & SS_ERR_CELL) { adf_set_error("%s: the first two rows of a cell span no finite area", who); return ADF_EINVAL; }
-    return ADF_OK;
-}
+static const adf_errrow SS_ERRORS[] = {
+    {SS_ERR_RANGE, ADF_EINVAL, "%s: malformed offsets (not ascending, outside their arrays, a slab or operation index out of range, or "
+                               "more candidates than the tables hold)"},
+    {SS_ERR_CELL, ADF_EINVAL, "%s: the first two rows of a cell span no finite area"}};
 
 extern "C" int32_t adf_surface_site_candidates(const float* pos, const int32_t* tags, const int32_t* atom_offset,
                                                const float* cell, const float* tri, const int32_t* tri_offset,
@@ -276,17 +259,15 @@ extern "C" int32_t adf_surface_site_candidates(const float* pos, const int32_t* 
         return ADF_EINVAL;
     }
     hipStream_t s = (hipStream_t)stream;
-    adf_pool tmp;   // the error word; freed on every return (after the synchronisation below)
-    int32_t* err = nullptr;
-    ADF_TRY(tmp.alloc(&err, 1));
-    ADF_HIP_CHECK(hipMemsetAsync(err, 0, sizeof(int32_t), s));
+    adf_errword err;   // freed on every return (after the synchronisation in finish)
+    ADF_TRY(err.create(s));
     hipLaunchKernelGGL(ss_offsets_kernel, dim3(1), dim3(SS_THREADS), 0, s, tags, atom_offset, tri_offset, num_atoms,
-                       num_triangles, num_slabs, capacity, seg_offset, err);
+                       num_triangles, num_slabs, capacity, seg_offset, err.dev);
     ADF_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(ss_candidates_kernel, dim3(num_slabs, 3), dim3(SS_THREADS), 0, s, pos, tags, atom_offset, cell, tri,
-                       tri_offset, seg_offset, num_atoms, num_triangles, capacity, cand, valid, err);
+                       tri_offset, seg_offset, num_atoms, num_triangles, capacity, cand, valid, err.dev);
     ADF_HIP_CHECK(hipGetLastError());
-    return ss_read_error(err, s, "surface_site_candidates");
+    return err.finish(s, "surface_site_candidates", SS_ERRORS);
 }
 
 // ------------------------------------------------------------------------------------------------ reduction
@@ -310,7 +291,7 @@ __device__ __forceinline__ int ss_rounds(const ss_reduce_params& q, const ss_fra
         int key = INT_MAX;
         for (int c = tid; c < n; c += SS_THREADS)
             if (state[s0 + c] == -2) { key = c; break; }
-        key = ss_block_min(key, red);
+        key = adf_block_min<SS_THREADS / 64>(key, red);
         if (key == INT_MAX) break;
         const int r = key;
         if (tid < 3) rx[tid] = (double)q.cand[3 * (size_t)(s0 + r) + tid];
@@ -435,17 +416,15 @@ extern "C" int32_t adf_reduce_sites(const float* cand, const int32_t* valid, con
         return ADF_EINVAL;
     }
     hipStream_t s = (hipStream_t)stream;
-    adf_pool tmp;
-    int32_t* err = nullptr;
-    ADF_TRY(tmp.alloc(&err, 1));
-    ADF_HIP_CHECK(hipMemsetAsync(err, 0, sizeof(int32_t), s));
+    adf_errword err;   // freed on every return (after the synchronisation in finish)
+    ADF_TRY(err.create(s));
     ss_reduce_params q = {};
     q.cand = cand; q.valid = valid; q.seg_offset = seg_offset; q.seg_slab = seg_slab; q.cell = cell;
     q.op_offset = op_offset; q.rot = rot; q.trans = trans;
     q.C = num_candidates; q.G = num_segments; q.B = num_slabs; q.K = op_offset ? num_ops : 0;
     q.tol = tol;
-    q.first = first; q.rep = rep; q.mult = multiplicity; q.counts = counts; q.err = err;
+    q.first = first; q.rep = rep; q.mult = multiplicity; q.counts = counts; q.err = err.dev;
     hipLaunchKernelGGL(ss_reduce_kernel, dim3(num_segments), dim3(SS_THREADS), 0, s, q);
     ADF_HIP_CHECK(hipGetLastError());
-    return ss_read_error(err, s, "reduce_sites");
+    return err.finish(s, "reduce_sites", SS_ERRORS);
 }

@@ -34,12 +34,6 @@ struct StepParams {
     int early_stop_count;
 };
 
-__device__ __forceinline__ float wsum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 __device__ __forceinline__ float pymod1(float x) {
     // torch.remainder(x, 1): result has the sign of the divisor
     float r = fmodf(x, 1.0f);
@@ -73,7 +67,7 @@ __global__ __launch_bounds__(64) void adf_init_placement_kernel(const float* cel
     float sx = 0.f, sy = 0.f, sz = 0.f, cnt = 0.f;
     for (int a = a0 + lane; a < a1; a += 64)
         if (tags[a] == 2) { sx += pos[3 * a]; sy += pos[3 * a + 1]; sz += pos[3 * a + 2]; cnt += 1.f; }
-    sx = wsum(sx); sy = wsum(sy); sz = wsum(sz); cnt = wsum(cnt);
+    sx = adf_wave_sum(sx); sy = adf_wave_sum(sy); sz = adf_wave_sum(sz); cnt = adf_wave_sum(cnt);
     const float inv = 1.0f / fmaxf(cnt, 1.0f);
     const float cx = sx * inv, cy = sy * inv, cz = sz * inv;
     const float* cl = cell + 9 * b;
@@ -106,7 +100,7 @@ __device__ __forceinline__ void step_sums(const StepParams& p, int a0, int a1, i
             s[9] += 1.f;
         }
 #pragma unroll
-    for (int i = 0; i < 10; ++i) s[i] = wsum(s[i]);
+    for (int i = 0; i < 10; ++i) s[i] = adf_wave_sum(s[i]);
 }
 
 // the wrap of the COM into the cell: com + dcom -> solve / mod / cell.f; dcom becomes the wrapped increment.
@@ -340,7 +334,7 @@ __device__ __forceinline__ void tr_sums(const TrParams& p, int a0, int a1, int l
             s[6] += 1.f;
         }
 #pragma unroll
-    for (int i = 0; i < 7; ++i) s[i] = wsum(s[i]);
+    for (int i = 0; i < 7; ++i) s[i] = adf_wave_sum(s[i]);
 }
 
 // sums -> com and the wrapped dcom of system b; returns its convergence predicate
@@ -558,6 +552,7 @@ __global__ __launch_bounds__(64) void adf_lift_kernel(float* pos, const int32_t*
         if (tags[a] == 1) zs = fmaxf(zs, z);
         if (tags[a] == 2) za = fminf(za, z);
     }
+    // kept inline: as a call to lanes.h this butterfly reorders the kernel's instructions (tools/device_asm_diff.py)
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) { zs = fmaxf(zs, __shfl_xor(zs, o)); za = fminf(za, __shfl_xor(za, o)); }
     float shift = 0.f;

@@ -22,7 +22,9 @@
 #include <limits.h>
 #include <math.h>
 
-#include "common.h"
+#include "host_util.h"
+#include "cell3.h"
+#include "lanes.h"
 
 #define SY_THREADS 256
 #define SY_WAVES (SY_THREADS / 64)
@@ -45,11 +47,6 @@ struct sy_lat {
 #define SY_IDENT(l) ((l).i[4])
 #define SY_W(l, s, k) ((l).i[8 + 4 * (s) + (k)])
 
-__device__ __forceinline__ void sy_range(const int32_t* __restrict__ atom_offset, int b, int num_atoms, int& a0, int& n) {
-    a0 = min(max(atom_offset[b], 0), num_atoms);
-    n = min(max(atom_offset[b + 1], a0), num_atoms) - a0;
-}
-
 __global__ __launch_bounds__(SY_THREADS) void sy_lattice_kernel(
     const float* __restrict__ pos, const float* __restrict__ cell, const int32_t* __restrict__ Z,
     const int32_t* __restrict__ atom_offset, int num_atoms, int num_slabs, double symprec, int proper_only,
@@ -57,7 +54,7 @@ __global__ __launch_bounds__(SY_THREADS) void sy_lattice_kernel(
     const int b = blockIdx.x * SY_WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (b >= num_slabs) return;
     int a0, n;
-    sy_range(atom_offset, b, num_atoms, a0, n);
+    adf_segment_clamp(atom_offset, b, num_atoms, a0, n);
     for (int k = lane; k < n; k += 64) {
         const size_t r = 3 * (size_t)(a0 + k);
         xz[a0 + k] = make_float4(pos[r], pos[r + 1], pos[r + 2], __int_as_float(Z[a0 + k]));
@@ -70,6 +67,7 @@ __global__ __launch_bounds__(SY_THREADS) void sy_lattice_kernel(
         for (int k = 0; k < n; ++k) cnt += Z[a0 + k] == zi ? 1 : 0;
         if (cnt < bc || (cnt == bc && (zi < bz || (zi == bz && i < bi)))) { bc = cnt; bz = zi; bi = i; }
     }
+    // kept inline: as a call to lanes.h this butterfly reorders the kernel's instructions (tools/device_asm_diff.py)
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         const int oc = __shfl_xor(bc, o, 64), oz = __shfl_xor(bz, o, 64), oi = __shfl_xor(bi, o, 64);
@@ -79,11 +77,11 @@ __global__ __launch_bounds__(SY_THREADS) void sy_lattice_kernel(
     double a[3], bv[3], nv[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) { a[k] = (double)cell[9 * (size_t)b + k]; bv[k] = (double)cell[9 * (size_t)b + 3 + k]; }
-    nv[0] = a[1] * bv[2] - a[2] * bv[1];
+    nv[0] = a[1] * bv[2] - a[2] * bv[1];   // (not cell3.h's adf_cross3: the call reorders this kernel's instructions)
     nv[1] = a[2] * bv[0] - a[0] * bv[2];
     nv[2] = a[0] * bv[1] - a[1] * bv[0];
-    const double area = sqrt(nv[0] * nv[0] + nv[1] * nv[1] + nv[2] * nv[2]);
-    const double la = sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]), lb = sqrt(bv[0] * bv[0] + bv[1] * bv[1] + bv[2] * bv[2]);
+    const double area = sqrt(adf_dot3(nv, nv));
+    const double la = sqrt(adf_dot3(a, a)), lb = sqrt(adf_dot3(bv, bv));
     // symprec below half the shortest in-plane height, a finite cell of non-zero area: else the slab is refused
     const bool ok = area > 0.0 && area < (double)FLT_MAX && symprec >= 0.0 && symprec < 0.5 * area / fmax(la, lb);
     double M[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, Mi[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
@@ -91,7 +89,7 @@ __global__ __launch_bounds__(SY_THREADS) void sy_lattice_kernel(
     if (ok) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) { nv[k] /= area; M[3 * k] = a[k]; M[3 * k + 1] = bv[k]; M[3 * k + 2] = nv[k]; }
-        {
+        {   // (not cell3.h's adf_inv3: unguarded, and assigned row by row)
             const double c00 = M[4] * M[8] - M[5] * M[7], c01 = M[5] * M[6] - M[3] * M[8], c02 = M[3] * M[7] - M[4] * M[6];
             const double r = 1.0 / (M[0] * c00 + M[1] * c01 + M[2] * c02);
             Mi[0] = c00 * r; Mi[1] = (M[2] * M[7] - M[1] * M[8]) * r; Mi[2] = (M[1] * M[5] - M[2] * M[4]) * r;
@@ -247,7 +245,7 @@ __global__ __launch_bounds__(SY_THREADS) void sy_verify_kernel(
     __shared__ int32_t sh_partner[SY_WAVES][SY_CAP];
     const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     int a0, n;
-    sy_range(atom_offset, b, num_atoms, a0, n);
+    adf_segment_clamp(atom_offset, b, num_atoms, a0, n);
     if (n == 0) return;
     const float4* src = sy_stage(lat_d, lat_i, xz, b, a0, n, L, sh);
     const bool big = n > SY_CAP;
@@ -287,7 +285,7 @@ __global__ __launch_bounds__(SY_THREADS) void sy_rank_kernel(const int32_t* __re
     const int b = blockIdx.x * SY_WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (b >= num_slabs) return;
     int a0, n;
-    sy_range(atom_offset, b, num_atoms, a0, n);
+    adf_segment_clamp(atom_offset, b, num_atoms, a0, n);
     const long long total = (long long)SY_SLOTS * n;
     int base = 0;
     for (long long c0 = 0; c0 < total; c0 += 64) {
@@ -312,7 +310,7 @@ __global__ __launch_bounds__(SY_THREADS) void sy_emit_kernel(
     __shared__ float4 sh[SY_CAP];
     const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     int a0, n;
-    sy_range(atom_offset, b, num_atoms, a0, n);
+    adf_segment_clamp(atom_offset, b, num_atoms, a0, n);
     if (n == 0) return;
     const float4* src = sy_stage(lat_d, lat_i, xz, b, a0, n, L, sh);
     const int o0 = op_offset[b], nops = op_offset[b + 1] - o0;
@@ -355,25 +353,25 @@ struct sy_scratch {
     float4* xz;
     int32_t* flags;
     int32_t* big_partner;
+    size_t bytes;
 };
 
-static size_t sy_up(size_t x) { return (x + 255) / 256 * 256; }
-
+// the layout of the caller's scratch, every region on a 256-byte boundary; a null scratch measures it (s.bytes)
 static sy_scratch sy_carve(void* scratch, int32_t num_atoms, int32_t num_slabs) {
-    unsigned char* p = (unsigned char*)scratch;
+    adf_carver c(scratch, 256);
     sy_scratch s;
-    s.lat_d = (double*)p;       p += sy_up((size_t)num_slabs * SY_LATD * sizeof(double));
-    s.lat_i = (int32_t*)p;      p += sy_up((size_t)num_slabs * SY_LATI * sizeof(int32_t));
-    s.xz = (float4*)p;          p += sy_up((size_t)num_atoms * sizeof(float4));
-    s.flags = (int32_t*)p;      p += sy_up((size_t)num_atoms * SY_SLOTS * sizeof(int32_t));
-    s.big_partner = (int32_t*)p;
+    s.lat_d = c.take<double>((size_t)num_slabs * SY_LATD);
+    s.lat_i = c.take<int32_t>((size_t)num_slabs * SY_LATI);
+    s.xz = c.take<float4>((size_t)num_atoms);
+    s.flags = c.take<int32_t>((size_t)num_atoms * SY_SLOTS);
+    s.big_partner = c.take<int32_t>((size_t)num_atoms * SY_SLOTS);
+    s.bytes = c.bytes();
     return s;
 }
 
 extern "C" int64_t adf_slab_symmetry_scratch(int32_t num_atoms, int32_t num_slabs) {
     if (num_atoms < 0 || num_slabs < 0) return 0;
-    return (int64_t)(sy_up((size_t)num_slabs * SY_LATD * sizeof(double)) + sy_up((size_t)num_slabs * SY_LATI * sizeof(int32_t)) +
-                     sy_up((size_t)num_atoms * sizeof(float4)) + 2 * sy_up((size_t)num_atoms * SY_SLOTS * sizeof(int32_t)));
+    return (int64_t)sy_carve(nullptr, num_atoms, num_slabs).bytes;
 }
 
 // blocks per slab: about four candidates per wave of the average slab; at least one block per point slot (large slabs)

@@ -28,19 +28,6 @@ static inline unsigned tr_grid(long long total, int per_block = 256) {
     return (unsigned)b;
 }
 
-__device__ __forceinline__ float tr_wsum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// ScaledSiLU and its derivative (gemnet_oc/layers/base_layers.py:65-72): f(x) = x sigmoid(x) / 0.6
-__device__ __forceinline__ float tr_ssilu(float x) { return x / (1.0f + expf(-x)) * 1.6666666666666667f; }
-__device__ __forceinline__ float tr_dssilu(float x) {
-    const float s = 1.0f / (1.0f + expf(-x));
-    return s * (1.0f + x * (1.0f - s)) * 1.6666666666666667f;
-}
-
 // ------------------------------------------------------------------------------------------------ linear layers
 // C = A W^T (+ bias): the f16x3 split GEMM of the sampling path (gemm16.hip) with the same per-row power-of-two lifts
 // (every A row is measured by adf_launch_rowmag and lifted before the split: activations of any magnitude, and the
@@ -587,12 +574,12 @@ extern "C" int32_t adf_op_linear_bwd(const float* A, int32_t lda, const float* W
 // ------------------------------------------------------------------------------------------------ elementwise
 __global__ void tr_ssilu_fwd_kernel(const float* __restrict__ h, float* __restrict__ y, long long n) {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
-        y[i] = tr_ssilu(h[i]);
+        y[i] = adf_ssilu(h[i]);
 }
 __global__ void tr_ssilu_bwd_kernel(const float* __restrict__ h, const float* __restrict__ dy, float* __restrict__ dh,
                                     long long n) {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
-        dh[i] = dy[i] * tr_dssilu(h[i]);
+        dh[i] = dy[i] * adf_dssilu(h[i]);
 }
 extern "C" int32_t adf_op_ssilu_fwd(const float* h, float* y, int64_t n, void* stream) {
     hipLaunchKernelGGL(tr_ssilu_fwd_kernel, dim3(tr_grid(n)), dim3(256), 0, (hipStream_t)stream, h, y, (long long)n);
@@ -618,11 +605,11 @@ __global__ __launch_bounds__(256) void tr_ln_fwd_kernel(const float* __restrict_
     const float* xr = x + (size_t)row * H;
     float s = 0.f;
     for (int c = lane; c < H; c += 64) s += xr[c];
-    const float m0 = tr_wsum(s) / (float)H;
+    const float m0 = adf_wave_sum(s) / (float)H;
     float q = 0.f, r = 0.f;
     for (int c = lane; c < H; c += 64) { const float d = xr[c] - m0; q += d * d; r += d; }
-    const float cm = tr_wsum(r) / (float)H;
-    const float rstd = 1.0f / sqrtf(fmaxf(tr_wsum(q) / (float)H - cm * cm, 0.f) + 1e-5f);
+    const float cm = adf_wave_sum(r) / (float)H;
+    const float rstd = 1.0f / sqrtf(fmaxf(adf_wave_sum(q) / (float)H - cm * cm, 0.f) + 1e-5f);
     for (int c = lane; c < H; c += 64) y[(size_t)row * H + c] = ((xr[c] - m0) - cm) * rstd * w[c] + b[c];
     if (lane == 0) stats[row] = make_float2(m0 + cm, rstd);
 }
@@ -646,9 +633,9 @@ __global__ __launch_bounds__(256) void tr_ln_bwd_kernel(const float* __restrict_
             const float d = xr[c] - st.x, g = gr[c] * w[c];
             s1 += g; s2 += g * d; r += d;
         }
-        const float cm = tr_wsum(r) / (float)H;
-        s1 = tr_wsum(s1) / (float)H;
-        s2 = (tr_wsum(s2) / (float)H - cm * s1) * st.y;
+        const float cm = adf_wave_sum(r) / (float)H;
+        s1 = adf_wave_sum(s1) / (float)H;
+        s2 = (adf_wave_sum(s2) / (float)H - cm * s1) * st.y;
         for (int c = lane; c < H; c += 64) {
             const float xh = ((xr[c] - st.x) - cm) * st.y, g = gr[c] * w[c];
             dx[(size_t)row * H + c] += st.y * (g - s1 - xh * s2);
@@ -989,7 +976,7 @@ __global__ void tr_gate_fwd_kernel(const float* __restrict__ o, const float* __r
         const long long n = t / C;
         const int c = (int)(t - n * C);
         const float xo = o[(size_t)n * 2 * C + c], g = o[(size_t)n * 2 * C + C + c];
-        if (xs) xs[(size_t)n * ldx + c] = tr_ssilu(xo);
+        if (xs) xs[(size_t)n * ldx + c] = adf_ssilu(xo);
         for (int k = 0; k < 3; ++k) { const size_t q = ((size_t)n * 3 + k) * C + c; vout[q] = g * t2[q]; }
     }
 }
@@ -1007,7 +994,7 @@ __global__ void tr_gate_bwd_kernel(const float* __restrict__ o, const float* __r
             dg += dvout[q] * t2[q];
             dt2[q] = dvout[q] * g;
         }
-        d_o[(size_t)n * 2 * C + c] = dxs ? dxs[(size_t)n * lddx + c] * tr_dssilu(xo) : 0.f;
+        d_o[(size_t)n * 2 * C + c] = dxs ? dxs[(size_t)n * lddx + c] * adf_dssilu(xo) : 0.f;
         d_o[(size_t)n * 2 * C + C + c] = dg;
     }
 }
@@ -1078,7 +1065,7 @@ __global__ __launch_bounds__(64) void tr_loss_kernel(const float* __restrict__ f
             for (int k = 0; k < 3; ++k) { s[k] += f1[3 * a + k]; s[3 + k] += f2[3 * a + k]; }
             s[6] += 1.f;
         }
-    for (int i = 0; i < 7; ++i) s[i] = tr_wsum(s[i]);
+    for (int i = 0; i < 7; ++i) s[i] = adf_wave_sum(s[i]);
     const float cnt = fmaxf(s[6], 1.f), st = tr_sigma[b], sr = rot_sigma[b], nr = rot_norm[b];
     const float inv = 1.0f / (3.0f * (float)B);
     float lt = 0.f, lr = 0.f, g1[3], g2[3];
@@ -1132,7 +1119,7 @@ __global__ __launch_bounds__(64) void tr_loss_tr_kernel(const float* __restrict_
             for (int k = 0; k < 3; ++k) s[k] += f1[3 * a + k];
             s[3] += 1.f;
         }
-    for (int i = 0; i < 4; ++i) s[i] = tr_wsum(s[i]);
+    for (int i = 0; i < 4; ++i) s[i] = adf_wave_sum(s[i]);
     const float cnt = fmaxf(s[3], 1.f), st = tr_sigma[b];
     const float inv = 1.0f / (3.0f * (float)B);
     float lt = 0.f, g1[3];
@@ -1174,7 +1161,7 @@ __global__ void tr_sqnorm_kernel(const float* __restrict__ g, long long n, float
     float s = 0.f;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
         s += g[i] * g[i];
-    s = tr_wsum(s);
+    s = adf_wave_sum(s);
     // one atomic per workgroup (one per wave from up to 4096 workgroups serialised on the single address: 44 us per call)
     __shared__ float ws[4];
     if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = s;

@@ -28,7 +28,9 @@
 
 #include <algorithm>
 
-#include "common.h"
+#include "host_util.h"
+#include "cell3.h"
+#include "lanes.h"
 
 #define TG_THREADS 256
 #define TG_WAVES (TG_THREADS / 64)
@@ -151,25 +153,6 @@ __global__ __launch_bounds__(TG_THREADS) void tg_tile_kernel(const float* __rest
 
 // ------------------------------------------------------------------------------------------------ the star walk
 // (key, index) of the least key over the wave, ties to the least index; left in every lane
-__device__ __forceinline__ void tg_wave_argmin(double& key, int& idx) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const double k2 = __shfl_xor(key, o, 64);
-        const int i2 = __shfl_xor(idx, o, 64);
-        if (k2 < key || (k2 == key && i2 < idx)) { key = k2; idx = i2; }
-    }
-}
-__device__ __forceinline__ double tg_wave_min(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ int tg_wave_sum(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // One triangle (i, x, y), counter-clockwise, of the star of i: owned, and counted, where i is its least index.  Emitting:
 // lane 0 notes (x, y) in row base + count of bc (rows up to `room` only: what the counting walk found).
 template <bool EMIT>
@@ -195,7 +178,7 @@ __device__ __forceinline__ int tg_star(const double2* P, int n, int i, double to
         const double ux = p.x - pi.x, uy = p.y - pi.y, d2 = ux * ux + uy * uy;
         if (d2 < key) { key = d2; j0 = q; }
     }
-    tg_wave_argmin(key, j0);
+    adf_wave_argmin(key, j0);
     if (j0 == INT_MAX || !(key > 0.0)) return -1;
     int count = 0, j = j0;
     for (int step = 0;; ++step) {
@@ -214,7 +197,7 @@ __device__ __forceinline__ int tg_star(const double2* P, int n, int i, double to
             const double t = (ux * (ux - dx) + uy * (uy - dy)) / (2.0 * cr);
             if (t < tk) { tk = t; ks = q; }
         }
-        tg_wave_argmin(tk, ks);
+        adf_wave_argmin(tk, ks);
         if (ks == INT_MAX || !(fabs(tk) < INFINITY)) return -1;
         const double cx = pi.x + 0.5 * dx - tk * dy, cy = pi.y + 0.5 * dy + tk * dx;
         const double r = sqrt(dd * (0.25 + tk * tk));
@@ -234,13 +217,13 @@ __device__ __forceinline__ int tg_star(const double2* P, int n, int i, double to
             const double c = (dx * ux + dy * uy) / sqrt(ux * ux + uy * uy);
             if (c < cmin) { cmin = c; qs = q; }
         }
-        on_count = tg_wave_sum(on_count);
-        tg_wave_argmin(cmin, qs);
+        on_count = adf_wave_sum(on_count);
+        adf_wave_argmin(cmin, qs);
         if (qs == INT_MAX) return -1;
         if (on_count <= 2) {
             tg_triangle<EMIT>(i, j, qs, count, bc, room);   // a triangle: the generic case
         } else {
-            xmin = fmin(tg_wave_min(xmin), pi.x);
+            xmin = fmin(adf_wave_min(xmin), pi.x);
             // pass C: the canonical vertex - least y among the vertices whose x is within tol of the least
             double ymin = INFINITY;
             int v = INT_MAX;
@@ -253,7 +236,7 @@ __device__ __forceinline__ int tg_star(const double2* P, int n, int i, double to
                 if (!on || !(p.x <= xmin + tol)) continue;
                 if (p.y < ymin || (p.y == ymin && q < v)) { ymin = p.y; v = q; }
             }
-            tg_wave_argmin(ymin, v);
+            adf_wave_argmin(ymin, v);
             if (v == i) {
                 // the fan is i's own: the polygon's vertices in the order of their angle from i -> j
                 int cur = j;
@@ -272,7 +255,7 @@ __device__ __forceinline__ int tg_star(const double2* P, int n, int i, double to
                         const double c = (dx * ux + dy * uy) / sqrt(ux * ux + uy * uy);
                         if (c < ccur && -c < best) { best = -c; nx = q; }
                     }
-                    tg_wave_argmin(best, nx);
+                    adf_wave_argmin(best, nx);
                     if (nx == INT_MAX) return -1;
                     tg_triangle<EMIT>(i, cur, nx, count, bc, room);
                     cur = nx;
@@ -412,59 +395,51 @@ extern "C" int32_t adf_surface_triangles(const float* pos, const int32_t* tags, 
     hipStream_t s = (hipStream_t)stream;
     const size_t N = (size_t)num_atoms, B = (size_t)num_slabs;
     const size_t rows = (size_t)std::min((long long)capacity, 18ll * num_atoms);     // more rows than that are never owned
-    // one scratch block, freed on every return (after the synchronisation below): doubles first, then the int tables
-    const size_t n_tv = 6 * B, n_pts = 2 * 9 * N, bc_at = 1 + (B + 1) + N + N + (N + 1), n_int = bc_at + 1 + 2 * rows;
+    // one scratch block, freed on every return (after the synchronisation in finish): laid out by the same code twice
+    double* tv;
+    double2* pts;
+    int32_t *err_dev, *top_off, *top_atom, *cnt, *start;
+    int2* bc;
+    auto lay = [&](adf_carver c) {
+        tv = c.take<double>(6 * B); pts = c.take<double2>(9 * N);
+        err_dev = c.take<int32_t>(1); top_off = c.take<int32_t>(B + 1); top_atom = c.take<int32_t>(N); cnt = c.take<int32_t>(N);
+        start = c.take<int32_t>(N + 1); bc = c.take<int2>(rows);
+        return c.bytes();
+    };
     adf_pool tmp;
-    double* block = nullptr;
-    ADF_TRY(tmp.alloc(&block, n_tv + n_pts + (n_int + 1) / 2));
-    double* tv = block;
-    double2* pts = reinterpret_cast<double2*>(block + n_tv);
-    int32_t* err = reinterpret_cast<int32_t*>(block + n_tv + n_pts);
-    int32_t* top_off = err + 1;
-    int32_t* top_atom = top_off + (B + 1);
-    int32_t* cnt = top_atom + N;
-    int32_t* start = cnt + N;
-    int2* bc = reinterpret_cast<int2*>(err + bc_at + (bc_at & 1));               // 8-byte aligned: n_int has the spare word
-    ADF_HIP_CHECK(hipMemsetAsync(err, 0, sizeof(int32_t), s));
+    void* block = nullptr;
+    ADF_TRY(tmp.alloc(&block, lay(adf_carver())));
+    lay(adf_carver(block));
+    adf_errword err;
+    ADF_TRY(err.adopt(err_dev, s));
     ADF_HIP_CHECK(hipMemsetAsync(tri_offset, 0, (B + 1) * sizeof(int32_t), s));
     hipLaunchKernelGGL(tg_prepare_kernel, dim3(1), dim3(TG_THREADS), 0, s, tags, atom_offset, cell, num_atoms, num_slabs,
-                       top_off, tv, err);
+                       top_off, tv, err.dev);
     ADF_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(tg_tile_kernel, dim3(num_slabs), dim3(TG_THREADS), 0, s, pos, tags, atom_offset, top_off, tv, num_atoms,
-                       top_atom, pts, err);
+                       top_atom, pts, err.dev);
     ADF_HIP_CHECK(hipGetLastError());
     tg_walk_params q = {};
     q.pos = pos; q.top_off = top_off; q.top_atom = top_atom; q.tv = tv; q.pts = pts; q.start = start;
     q.N = num_atoms; q.capacity = (int32_t)rows; q.tol = circle_tol;
     q.lds_points = (int32_t)std::min((long long)TG_LDS_POINTS, 9ll * num_atoms);
-    q.cnt = cnt; q.bc = bc; q.tri_offset = tri_offset; q.tri = tri; q.tri_index = tri_index; q.err = err;
+    q.cnt = cnt; q.bc = bc; q.tri_offset = tri_offset; q.tri = tri; q.tri_index = tri_index; q.err = err.dev;
     // workgroups per slab: a wave per star, sized by the mean slab (a slab's rows do not depend on it)
     const int parts = (int)std::min(64ll, std::max(1ll, ((long long)num_atoms / num_slabs + 31) / 32));
     const size_t lds = (size_t)q.lds_points * sizeof(double2);
     hipLaunchKernelGGL(tg_walk_kernel<false>, dim3(num_slabs, parts), dim3(TG_THREADS), lds, s, q);
     ADF_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(tg_scan_kernel, dim3(1), dim3(TG_THREADS), 0, s, cnt, top_off, num_slabs, num_atoms, (int32_t)rows, start,
-                       err);
+                       err.dev);
     ADF_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(tg_walk_kernel<true>, dim3(num_slabs, parts), dim3(TG_THREADS), lds, s, q);
     ADF_HIP_CHECK(hipGetLastError());
-    int32_t bad = 0;
-    ADF_HIP_CHECK(hipMemcpyAsync(&bad, err, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    ADF_HIP_CHECK(hipStreamSynchronize(s));
-    if (bad & TG_ERR_RANGE) { adf_set_error("surface_triangles: atom offsets not ascending or outside [0, N]"); return ADF_EINVAL; }
-    if (bad & TG_ERR_NOTOP) { adf_set_error("surface_triangles: a slab has no atom of tag 1"); return ADF_EINVAL; }
-    if (bad & TG_ERR_CELL) {
-        adf_set_error("surface_triangles: a cell has fewer than two in-plane lattice vectors (or a non-finite one)");
-        return ADF_EINVAL;
-    }
-    if (bad & TG_ERR_DEGENERATE) {
-        adf_set_error("surface_triangles: a slab cannot be triangulated (its tiled points are collinear, coincide, or its "
-                      "tiling vectors do not surround the central tile)");
-        return ADF_EINVAL;
-    }
-    if (bad & TG_ERR_CAPACITY) {
-        adf_set_error("surface_triangles: more triangles than the tables hold (%d rows; 18 * num_atoms always suffices)", capacity);
-        return ADF_EINVAL;
-    }
-    return ADF_OK;
+    const adf_errrow errors[] = {
+        {TG_ERR_RANGE, ADF_EINVAL, "%s: atom offsets not ascending or outside [0, N]"},
+        {TG_ERR_NOTOP, ADF_EINVAL, "%s: a slab has no atom of tag 1"},
+        {TG_ERR_CELL, ADF_EINVAL, "%s: a cell has fewer than two in-plane lattice vectors (or a non-finite one)"},
+        {TG_ERR_DEGENERATE, ADF_EINVAL, "%s: a slab cannot be triangulated (its tiled points are collinear, coincide, or its "
+                                        "tiling vectors do not surround the central tile)"},
+        {TG_ERR_CAPACITY, ADF_EINVAL, "%s: more triangles than the tables hold (%d rows; 18 * num_atoms always suffices)", capacity}};
+    return err.finish(s, "surface_triangles", errors);
 }

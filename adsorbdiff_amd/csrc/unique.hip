@@ -21,7 +21,9 @@
 #include <limits.h>
 #include <math.h>
 
-#include "common.h"
+#include "base.h"
+#include "cell3.h"
+#include "lanes.h"
 
 #define UQ_THREADS 256
 
@@ -47,12 +49,6 @@ __device__ __forceinline__ float uq_disp(float dx, float dy, float dz, const flo
     return sqrtf(fmaf(mz, mz, fmaf(my, my, mx * mx)));
 }
 
-__device__ __forceinline__ float uq_wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
 // R x + tau of a symmetry operation (T: R row-major, then tau), formed in double and rounded to float32 once
 __device__ __forceinline__ void uq_apply(const double (&T)[12], float& x, float& y, float& z) {
     const double dx = x, dy = y, dz = z;
@@ -70,6 +66,7 @@ __device__ const double UQ_NO_OP[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};   /
 __device__ __forceinline__ void uq_cell(const float* __restrict__ cell, int s, float (&c)[9], float (&inv)[9]) {
 #pragma unroll
     for (int k = 0; k < 9; ++k) c[k] = cell[9 * (size_t)s + k];
+    // (not cell3.h's adf_inv3: unguarded, and assigned row by row)
     const float m00 = c[4] * c[8] - c[5] * c[7], m01 = c[5] * c[6] - c[3] * c[8], m02 = c[3] * c[7] - c[4] * c[6];
     const float r = 1.0f / (c[0] * m00 + c[1] * m01 + c[2] * m02);
     inv[0] = m00 * r; inv[1] = (c[2] * c[7] - c[1] * c[8]) * r; inv[2] = (c[1] * c[5] - c[2] * c[4]) * r;
@@ -161,7 +158,7 @@ __global__ __launch_bounds__(UQ_THREADS) void uq_pair_kernel(
                 d = fmaxf(d, uq_one_sided<0>(pos, tags, Z, a0, b0, na, false, c, inv, lane, nan, UQ_NO_OP));
                 d = fmaxf(d, uq_one_sided<0>(pos, tags, Z, b0, a0, na, true, c, inv, lane, nan, UQ_NO_OP));
             }
-            d = uq_wave_max(d);
+            d = adf_wave_max(d);
             nan = __ballot(nan) != 0ull;
         }
         if (nan) d = NAN;               // a non-finite coordinate: the pair is within no tolerance
@@ -207,12 +204,6 @@ extern "C" int32_t adf_site_pair_distances(const float* pos, const float* cell, 
 // d(g . site i, site j), i the earlier site.  One wave per pair, the operations one after the other; per operation the
 // adsorbate part first, and the slab part only while the operation can still win.  Operation 0 of every group is the
 // identity and is not applied, so a group with that one operation evaluates the expressions of uq_pair_kernel.
-__device__ __forceinline__ int uq_wave_min_int(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
 __global__ __launch_bounds__(UQ_THREADS) void uq_pair_sym_kernel(
     const float* __restrict__ pos, const float* __restrict__ cell, const int32_t* __restrict__ tags,
     const int32_t* __restrict__ Z, const int32_t* __restrict__ atom_offset, const int32_t* __restrict__ group_offset,
@@ -260,9 +251,10 @@ __global__ __launch_bounds__(UQ_THREADS) void uq_pair_sym_kernel(
                 if (ta == 2) { q0 = min(q0, k); q1 = max(q1, k); ++cnt; }
             }
             differ = __ballot(differ) != 0ull;
-            q0 = uq_wave_min_int(q0);
-            q1 = -uq_wave_min_int(-q1);
+            q0 = adf_wave_min(q0);
+            q1 = -adf_wave_min(-q1);
             int nads = cnt;
+            // kept inline: as a call to lanes.h this butterfly reorders the kernel's instructions (tools/device_asm_diff.py)
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) nads += __shfl_xor(nads, o, 64);
             if (nads == 0) q0 = na;
@@ -294,7 +286,7 @@ __global__ __launch_bounds__(UQ_THREADS) void uq_pair_sym_kernel(
                         d = fmaxf(d, v);
                     }
                 }
-                d = uq_wave_max(d);
+                d = adf_wave_max(d);
                 if (__ballot(bad) != 0ull) { nan = true; continue; }
                 if (!(d < best)) continue;                  // the slab part can only raise d: this operation cannot win
                 if (include_slab) {
@@ -309,7 +301,7 @@ __global__ __launch_bounds__(UQ_THREADS) void uq_pair_sym_kernel(
                         if (v != v) bad = true;
                         d = fmaxf(d, v);
                     }
-                    d = uq_wave_max(d);
+                    d = adf_wave_max(d);
                     if (__ballot(bad) != 0ull) { nan = true; continue; }
                 }
                 if (d < best) { best = d; bop = op; }
@@ -410,6 +402,7 @@ __global__ __launch_bounds__(UQ_THREADS) void uq_cluster_kernel(
                 key = k < key ? k : key;
             }
         }
+        // kept inline: as a call to lanes.h this butterfly reorders the kernel's instructions (tools/device_asm_diff.py)
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
             const unsigned long long other = __shfl_xor(key, o, 64);
@@ -482,6 +475,7 @@ __global__ __launch_bounds__(256) void uq_top_sites_kernel(const float* __restri
             if (c > 0) ok = ok && (e > last_e || (e == last_e && i > last_i));
             if (ok && (e < be || (e == be && i < bi))) { be = e; bi = i; }
         }
+        // kept inline: as a call to lanes.h this butterfly reorders the kernel's instructions (tools/device_asm_diff.py)
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
             const float oe = __shfl_xor(be, o);

@@ -22,7 +22,9 @@
 
 #include <algorithm>
 
-#include "common.h"
+#include "host_util.h"
+#include "cell3.h"
+#include "lanes.h"
 
 #define VO_CAND 1024            // candidates of one atom held in LDS
 #define VO_VERT 32              // vertices of a facet while it is clipped
@@ -47,12 +49,6 @@ __device__ __forceinline__ vo_cell3 vo_load_cell(const float* cell, int b) {
     }
     return q;
 }
-__device__ __forceinline__ void vo_cross(const double* x, const double* y, double* o) {
-    o[0] = x[1] * y[2] - x[2] * y[1];
-    o[1] = x[2] * y[0] - x[0] * y[2];
-    o[2] = x[0] * y[1] - x[1] * y[0];
-}
-__device__ __forceinline__ double vo_dot(const double* x, const double* y) { return x[0] * y[0] + x[1] * y[1] + x[2] * y[2]; }
 __device__ __forceinline__ bool vo_finite(double v) { return fabs(v) < INFINITY; }
 
 __device__ __forceinline__ void vo_fail(int32_t* err, int bit, int atom) {
@@ -77,11 +73,11 @@ __global__ void vo_prepare_kernel(const float* __restrict__ cell, const int32_t*
         if (per[0] || per[1] || per[2] || cell_always) {
             const vo_cell3 q = vo_load_cell(cell, b);
             double bc[3], ca[3], ab[3];
-            vo_cross(q.b, q.c, bc);
-            vo_cross(q.c, q.a, ca);
-            vo_cross(q.a, q.b, ab);
-            const double vol = fabs(vo_dot(q.a, bc));
-            const double area[3] = {sqrt(vo_dot(bc, bc)), sqrt(vo_dot(ca, ca)), sqrt(vo_dot(ab, ab))};
+            adf_cross3(q.b, q.c, bc);
+            adf_cross3(q.c, q.a, ca);
+            adf_cross3(q.a, q.b, ab);
+            const double vol = fabs(adf_dot3(q.a, bc));
+            const double area[3] = {sqrt(adf_dot3(bc, bc)), sqrt(adf_dot3(ca, ca)), sqrt(adf_dot3(ab, ab))};
             if (!(vol > 0.0) || !vo_finite(vol) || !vo_finite(area[0]) || !vo_finite(area[1]) || !vo_finite(area[2])) {
                 ok = false;
                 vo_fail(err, VO_ERR_CELL, a0);
@@ -106,12 +102,6 @@ __global__ void vo_prepare_kernel(const float* __restrict__ cell, const int32_t*
 }
 
 // ------------------------------------------------------------------------------------------------ the cell of one atom
-__device__ __forceinline__ double vo_wave_max(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
 struct vo_params {
     const float* pos; const float* cell; const int32_t* atom_offset; const int32_t* select; const int32_t* reps;
     int32_t N;
@@ -212,10 +202,10 @@ __global__ __launch_bounds__(64) void vo_cell_kernel(vo_params q) {
                     const bool ex = fabs(nrm[0]) < 0.9;
                     const double e[3] = {ex ? 1.0 : 0.0, ex ? 0.0 : 1.0, 0.0};
                     double u[3], v[3];
-                    vo_cross(nrm, e, u);
-                    const double ul = sqrt(vo_dot(u, u));
+                    adf_cross3(nrm, e, u);
+                    const double ul = sqrt(adf_dot3(u, u));
                     u[0] /= ul; u[1] /= ul; u[2] /= ul;
-                    vo_cross(nrm, u, v);
+                    adf_cross3(nrm, u, v);
                     int cur = 0, cnt = 4;
                     mine[0 * 64] = make_double2(-VO_SQUARE, -VO_SQUARE);
                     mine[1 * 64] = make_double2(VO_SQUARE, -VO_SQUARE);
@@ -224,7 +214,7 @@ __global__ __launch_bounds__(64) void vo_cell_kernel(vo_params q) {
                     for (int k = 0; k < K && cnt >= 3; ++k) {
                         if (k == j) continue;
                         const double dk[3] = {cx[k], cy[k], cz[k]};
-                        const double c0 = vo_dot(o, dk) - 0.5 * key[k], cu = vo_dot(u, dk), cv = vo_dot(v, dk);
+                        const double c0 = adf_dot3(o, dk) - 0.5 * key[k], cu = adf_dot3(u, dk), cv = adf_dot3(v, dk);
                         const double2* src = mine + cur * (VO_VERT * 64);
                         bool cuts = false;
                         for (int a = 0; a < cnt; ++a) {
@@ -263,15 +253,15 @@ __global__ __launch_bounds__(64) void vo_cell_kernel(vo_params q) {
                             const double2 p = src[a * 64];
                             const double Pc[3] = {o[0] + p.x * u[0] + p.y * v[0], o[1] + p.x * u[1] + p.y * v[1],
                                                   o[2] + p.x * u[2] + p.y * v[2]};
-                            const double lc = sqrt(vo_dot(Pc, Pc));
+                            const double lc = sqrt(adf_dot3(Pc, Pc));
                             rmax = fmax(rmax, lc);
                             if (a == 0) {
                                 P0[0] = Pc[0]; P0[1] = Pc[1]; P0[2] = Pc[2]; l0 = lc;
                             } else if (a >= 2) {
                                 double bxc[3];
-                                vo_cross(Pb, Pc, bxc);
-                                const double num = vo_dot(P0, bxc);
-                                const double den = l0 * lb * lc + vo_dot(P0, Pb) * lc + vo_dot(P0, Pc) * lb + vo_dot(Pb, Pc) * l0;
+                                adf_cross3(Pb, Pc, bxc);
+                                const double num = adf_dot3(P0, bxc);
+                                const double den = l0 * lb * lc + adf_dot3(P0, Pb) * lc + adf_dot3(P0, Pc) * lb + adf_dot3(Pb, Pc) * l0;
                                 tot += 2.0 * atan2(num, den);
                             }
                             Pb[0] = Pc[0]; Pb[1] = Pc[1]; Pb[2] = Pc[2]; lb = lc;
@@ -281,7 +271,7 @@ __global__ __launch_bounds__(64) void vo_cell_kernel(vo_params q) {
                     om[j] = omega;
                 }
             }
-            R = vo_wave_max(rmax);
+            R = adf_wave_max(rmax);
             if (__any(over)) break;
             if (K == count || sqrt(key[K]) > 2.0 * R) break;
             K = min(count, 2 * K);
@@ -293,7 +283,7 @@ __global__ __launch_bounds__(64) void vo_cell_kernel(vo_params q) {
         __syncthreads();                                    // every lane's om is written
         double omax = 0.0;
         for (int j = lane; j < K; j += 64) omax = fmax(omax, om[j]);
-        omax = vo_wave_max(omax);
+        omax = adf_wave_max(omax);
         if (R > q.far || !(omax > 0.0)) {                   // open [no facet at all cannot happen: the nearest has one]
             if (lane == 0) { q.cn[i] = NAN; q.omega_max[i] = NAN; q.nn[i] = 0; q.flags[i] = 1; }
             continue;
@@ -362,14 +352,14 @@ __global__ __launch_bounds__(64) void vo_tag_prepare_kernel(vo_tag_params q) {
     const int a0 = q.atom_offset[b], a1 = q.atom_offset[b + 1];
     const vo_cell3 L = vo_load_cell(q.cell, b);
     double axb[3];
-    vo_cross(L.a, L.b, axb);
-    const double vol = vo_dot(L.c, axb), clen = sqrt(vo_dot(L.c, L.c));
+    adf_cross3(L.a, L.b, axb);
+    const double vol = adf_dot3(L.c, axb), clen = sqrt(adf_dot3(L.c, L.c));
     const bool wrap = q.pbc[3 * (size_t)b + 2] != 0;
     double fmx = -INFINITY;
     bool badz = false;
     for (int i = a0 + lane; i < a1; i += 64) {
         const double p[3] = {(double)q.pos[3 * (size_t)i], (double)q.pos[3 * (size_t)i + 1], (double)q.pos[3 * (size_t)i + 2]};
-        double f = vo_dot(p, axb) / vol;
+        double f = adf_dot3(p, axb) / vol;
         if (wrap) {
             f -= floor(f);
             f -= floor(f);
@@ -382,7 +372,7 @@ __global__ __launch_bounds__(64) void vo_tag_prepare_kernel(vo_tag_params q) {
         }
     }
     if (__any(badz)) return;
-    fmx = vo_wave_max(fmx);
+    fmx = adf_wave_max(fmx);
     __syncthreads();                                        // f of this system is written [one wave: its own stores]
     double sm = 0.0, smf = 0.0;                             // in atom order, the same in every lane
     for (int i = a0; i < a1; ++i) {
@@ -434,45 +424,18 @@ __global__ void vo_tag_commit_kernel(const int32_t* __restrict__ tag0, const int
 // ------------------------------------------------------------------------------------------------ host side
 static bool vo_positive(double v) { return v > 0.0 && v < (double)INFINITY; }
 
-static int32_t vo_report(const char* who, const int32_t bad[2]) {
-    const int atom = bad[1];
-    if (bad[0] & VO_ERR_RANGE) { adf_set_error("%s: atom offsets not ascending or outside [0, N]", who); return ADF_EINVAL; }
-    if (bad[0] & VO_ERR_CELL) {
-        adf_set_error("%s: the cell of the system of atom %d is singular or not finite", who, atom);
-        return ADF_EINVAL;
-    }
-    if (bad[0] & VO_ERR_Z) { adf_set_error("%s: atom %d has an atomic number outside [0, 118]", who, atom); return ADF_EINVAL; }
-    if (bad[0] & VO_ERR_MASS) { adf_set_error("%s: the masses of the system of atom %d do not sum to a positive number", who, atom); return ADF_EINVAL; }
-    if (bad[0] & VO_ERR_ELEMENT) {
-        adf_set_error("%s: the element of atom %d is absent from its slab's row of the bulk table", who, atom);
-        return ADF_EINVAL;
-    }
-    if (bad[0] & VO_ERR_FLAGGED) {
-        adf_set_error("%s: atom %d has an open cell or no coordination number (a bulk is periodic in three directions)", who, atom);
-        return ADF_EINVAL;
-    }
-    if (bad[0] & VO_ERR_PAIRS) {
-        adf_set_error("%s: the system of atom %d has more than %d (atom, image) pairs within the cutoff's repeats", who, atom,
-                      VO_MAX_PAIRS);
-        return ADF_EOVERFLOW;
-    }
-    if (bad[0] & VO_ERR_CAND) {
-        adf_set_error("%s: atom %d has more than %d candidates within the cutoff", who, atom, VO_CAND);
-        return ADF_EOVERFLOW;
-    }
-    if (bad[0] & VO_ERR_VERT) {
-        adf_set_error("%s: a facet of atom %d needs more than %d vertices", who, atom, VO_VERT);
-        return ADF_EOVERFLOW;
-    }
-    return ADF_OK;
-}
-
-// err[0] = 0, err[1] = INT_MAX
-static int32_t vo_reset_error(int32_t* err, hipStream_t s) {
-    ADF_HIP_CHECK(hipMemsetAsync(err, 0, sizeof(int32_t), s));
-    ADF_HIP_CHECK(hipMemsetAsync(err + 1, 0x7f, sizeof(int32_t), s));
-    return ADF_OK;
-}
+static const adf_errrow VO_ERRORS[] = {
+    {VO_ERR_RANGE, ADF_EINVAL, "%s: atom offsets not ascending or outside [0, N]"},
+    {VO_ERR_CELL, ADF_EINVAL, "%s: the cell of the system of atom %d is singular or not finite", ADF_ERR_ATOM},
+    {VO_ERR_Z, ADF_EINVAL, "%s: atom %d has an atomic number outside [0, 118]", ADF_ERR_ATOM},
+    {VO_ERR_MASS, ADF_EINVAL, "%s: the masses of the system of atom %d do not sum to a positive number", ADF_ERR_ATOM},
+    {VO_ERR_ELEMENT, ADF_EINVAL, "%s: the element of atom %d is absent from its slab's row of the bulk table", ADF_ERR_ATOM},
+    {VO_ERR_FLAGGED, ADF_EINVAL, "%s: atom %d has an open cell or no coordination number (a bulk is periodic in three directions)",
+     ADF_ERR_ATOM},
+    {VO_ERR_PAIRS, ADF_EOVERFLOW, "%s: the system of atom %d has more than %d (atom, image) pairs within the cutoff's repeats",
+     ADF_ERR_ATOM, VO_MAX_PAIRS},
+    {VO_ERR_CAND, ADF_EOVERFLOW, "%s: atom %d has more than %d candidates within the cutoff", ADF_ERR_ATOM, VO_CAND},
+    {VO_ERR_VERT, ADF_EOVERFLOW, "%s: a facet of atom %d needs more than %d vertices", ADF_ERR_ATOM, VO_VERT}};
 
 static int32_t vo_launch_cells(vo_params q, int num_atoms, int num_systems, hipStream_t s) {
     // workgroups per system: a wave per atom, sized by the mean system (a system's rows do not depend on it)
@@ -500,30 +463,34 @@ extern "C" int32_t adf_voronoi_coordination(const float* pos, const float* cell,
     }
     hipStream_t s = (hipStream_t)stream;
     const size_t N = (size_t)num_atoms, B = (size_t)num_systems;
-    adf_pool tmp;                                           // freed on every return (after the synchronisation below)
-    double* block = nullptr;
-    ADF_TRY(tmp.alloc(&block, 2 * N + (2 * N + 4 * B + 2 + 1) / 2 + 1));
-    double *r_cn = block, *r_om = block + N;
-    int32_t* r_nn = reinterpret_cast<int32_t*>(block + 2 * N);
-    int32_t *r_fl = r_nn + N, *reps = r_fl + N, *err = reps + 4 * B;
-    ADF_TRY(vo_reset_error(err, s));
+    // one scratch block, freed on every return (after the synchronisation in finish): laid out by the same code twice
+    double *r_cn, *r_om;
+    int32_t *r_nn, *r_fl, *reps, *err_dev;
+    auto lay = [&](adf_carver c) {
+        r_cn = c.take<double>(N); r_om = c.take<double>(N);
+        r_nn = c.take<int32_t>(N); r_fl = c.take<int32_t>(N); reps = c.take<int32_t>(4 * B); err_dev = c.take<int32_t>(2);
+        return c.bytes();
+    };
+    adf_pool tmp;
+    void* block = nullptr;
+    ADF_TRY(tmp.alloc(&block, lay(adf_carver())));
+    lay(adf_carver(block));
+    adf_errword err;
+    ADF_TRY(err.adopt(err_dev, s, 2));
     hipLaunchKernelGGL(vo_prepare_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, cell, pbc, atom_offset, num_atoms,
-                       num_systems, cutoff, 0, reps, err);
+                       num_systems, cutoff, 0, reps, err.dev);
     ADF_HIP_CHECK(hipGetLastError());
     vo_params q = {};
     q.pos = pos; q.cell = cell; q.atom_offset = atom_offset; q.select = select; q.reps = reps; q.N = num_atoms;
     q.cutoff = cutoff; q.weight_tol = weight_tol; q.far = far;
-    q.cn = r_cn; q.omega_max = r_om; q.nn = r_nn; q.flags = r_fl; q.err = err;
+    q.cn = r_cn; q.omega_max = r_om; q.nn = r_nn; q.flags = r_fl; q.err = err.dev;
     if (num_atoms > 0) {
         ADF_TRY(vo_launch_cells(q, num_atoms, num_systems, s));
         hipLaunchKernelGGL(vo_commit_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, select, num_atoms, r_cn, r_om,
-                           r_nn, r_fl, cn, omega_max, nn, flags, err);
+                           r_nn, r_fl, cn, omega_max, nn, flags, err.dev);
         ADF_HIP_CHECK(hipGetLastError());
     }
-    int32_t bad[2] = {0, 0};
-    ADF_HIP_CHECK(hipMemcpyAsync(bad, err, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    ADF_HIP_CHECK(hipStreamSynchronize(s));
-    return vo_report("voronoi_coordination", bad);
+    return err.finish(s, "voronoi_coordination", VO_ERRORS);
 }
 
 extern "C" int32_t adf_bulk_coordination_min(const double* cn, const int32_t* flags, const int32_t* atomic_numbers,
@@ -538,20 +505,15 @@ extern "C" int32_t adf_bulk_coordination_min(const double* cn, const int32_t* fl
         return ADF_EINVAL;
     }
     hipStream_t s = (hipStream_t)stream;
-    adf_pool tmp;
-    int32_t* err = nullptr;
-    ADF_TRY(tmp.alloc(&err, 2));
-    ADF_TRY(vo_reset_error(err, s));
+    adf_errword err;   // freed on every return (after the synchronisation in finish)
+    ADF_TRY(err.create(s, 2));
     const int most = std::max(num_atoms, num_systems);
     hipLaunchKernelGGL(vo_bulk_check_kernel, dim3((unsigned)((most + 255) / 256)), dim3(256), 0, s, cn, flags, atomic_numbers,
-                       atom_offset, num_atoms, num_systems, err);
+                       atom_offset, num_atoms, num_systems, err.dev);
     ADF_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(vo_bulk_min_kernel, dim3(num_systems), dim3(128), 0, s, cn, atomic_numbers, atom_offset, table, err);
+    hipLaunchKernelGGL(vo_bulk_min_kernel, dim3(num_systems), dim3(128), 0, s, cn, atomic_numbers, atom_offset, table, err.dev);
     ADF_HIP_CHECK(hipGetLastError());
-    int32_t bad[2] = {0, 0};
-    ADF_HIP_CHECK(hipMemcpyAsync(bad, err, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    ADF_HIP_CHECK(hipStreamSynchronize(s));
-    return vo_report("bulk_coordination_min", bad);
+    return err.finish(s, "bulk_coordination_min", VO_ERRORS);
 }
 
 extern "C" int32_t adf_tag_surface_atoms(const float* pos, const float* cell, const int32_t* pbc, const int32_t* atomic_numbers,
@@ -577,33 +539,37 @@ extern "C" int32_t adf_tag_surface_atoms(const float* pos, const float* cell, co
     }
     hipStream_t s = (hipStream_t)stream;
     const size_t N = (size_t)num_atoms, B = (size_t)num_systems;
+    double *r_cn, *r_om, *f;
+    int32_t *r_nn, *r_fl, *tag0, *sel, *reps, *err_dev;
+    auto lay = [&](adf_carver c) {
+        r_cn = c.take<double>(N); r_om = c.take<double>(N); f = c.take<double>(N);
+        r_nn = c.take<int32_t>(N); r_fl = c.take<int32_t>(N); tag0 = c.take<int32_t>(N); sel = c.take<int32_t>(N);
+        reps = c.take<int32_t>(4 * B); err_dev = c.take<int32_t>(2);
+        return c.bytes();
+    };
     adf_pool tmp;
-    double* block = nullptr;
-    ADF_TRY(tmp.alloc(&block, 3 * N + (4 * N + 4 * B + 2 + 1) / 2 + 1));
-    double *r_cn = block, *r_om = block + N, *f = block + 2 * N;
-    int32_t* r_nn = reinterpret_cast<int32_t*>(block + 3 * N);
-    int32_t *r_fl = r_nn + N, *tag0 = r_fl + N, *sel = tag0 + N, *reps = sel + N, *err = reps + 4 * B;
-    ADF_TRY(vo_reset_error(err, s));
+    void* block = nullptr;
+    ADF_TRY(tmp.alloc(&block, lay(adf_carver())));
+    lay(adf_carver(block));
+    adf_errword err;
+    ADF_TRY(err.adopt(err_dev, s, 2));
     hipLaunchKernelGGL(vo_prepare_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, cell, pbc, atom_offset, num_atoms,
-                       num_systems, cutoff, 1, reps, err);
+                       num_systems, cutoff, 1, reps, err.dev);
     ADF_HIP_CHECK(hipGetLastError());
     vo_tag_params t = {};
     t.pos = pos; t.cell = cell; t.pbc = pbc; t.Z = atomic_numbers; t.atom_offset = atom_offset; t.masses = masses;
-    t.bulk = bulk_cn_min; t.reps = reps; t.height = height; t.f = f; t.tag0 = tag0; t.sel = sel; t.err = err;
+    t.bulk = bulk_cn_min; t.reps = reps; t.height = height; t.f = f; t.tag0 = tag0; t.sel = sel; t.err = err.dev;
     hipLaunchKernelGGL(vo_tag_prepare_kernel, dim3(num_systems), dim3(64), 0, s, t);
     ADF_HIP_CHECK(hipGetLastError());
     if (bulk_cn_min && num_atoms > 0) {
         vo_params q = {};
         q.pos = pos; q.cell = cell; q.atom_offset = atom_offset; q.select = sel; q.reps = reps; q.N = num_atoms;
         q.cutoff = cutoff; q.weight_tol = weight_tol; q.far = far;
-        q.cn = r_cn; q.omega_max = r_om; q.nn = r_nn; q.flags = r_fl; q.err = err;
+        q.cn = r_cn; q.omega_max = r_om; q.nn = r_nn; q.flags = r_fl; q.err = err.dev;
         ADF_TRY(vo_launch_cells(q, num_atoms, num_systems, s));
     }
     hipLaunchKernelGGL(vo_tag_commit_kernel, dim3(num_systems), dim3(64), 0, s, tag0, sel, r_cn, r_fl, bulk_cn_min,
-                       atomic_numbers, atom_offset, num_atoms, num_systems, cn_tol, tags, cn, flags, err);
+                       atomic_numbers, atom_offset, num_atoms, num_systems, cn_tol, tags, cn, flags, err.dev);
     ADF_HIP_CHECK(hipGetLastError());
-    int32_t bad[2] = {0, 0};
-    ADF_HIP_CHECK(hipMemcpyAsync(bad, err, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    ADF_HIP_CHECK(hipStreamSynchronize(s));
-    return vo_report("tag_surface_atoms", bad);
+    return err.finish(s, "tag_surface_atoms", VO_ERRORS);
 }

@@ -312,7 +312,7 @@ def test_malformed_offsets_are_refused_not_read_past():
     cell = sb.cell.reshape(1, 9).contiguous()
     tri_off = torch.tensor([0, T], dtype=torch.int32, device=DEV)
 
-    def candidates(atom_off, rows, pos_ptr="pos"):
+    def candidates(atom_off, rows, pos_ptr="pos", cell=cell):
         a = torch.tensor(atom_off, dtype=torch.int32, device=DEV)
         seg = torch.full((4,), -7, dtype=torch.int32, device=DEV)
         cand = torch.full((N + 4 * T, 3), -7.0, device=DEV)
@@ -329,6 +329,12 @@ def test_malformed_offsets_are_refused_not_read_past():
         s, seg, cand, valid = candidates(atom_off, rows)
         assert s == L.ADF_EINVAL and b"malformed offsets" in lib.adf_last_error()
         assert bool((valid == -7).all()) and bool((cand == -7).all())                # no candidate was written
+    # a cell whose first two rows are parallel: the frame is refused before a candidate is computed in it
+    flat = cell.clone()
+    flat[0, 3:6] = 2.0 * flat[0, 0:3]
+    s, seg, cand, valid = candidates([0, N], N + 4 * T, cell=flat)
+    assert s == L.ADF_EINVAL and b"surface_site_candidates: the first two rows of a cell span no finite area" in lib.adf_last_error()
+    assert bool((valid == -7).all()) and bool((cand == -7).all())
     s, seg, cand, valid = candidates([0, N], N + 4 * T, pos_ptr=None)
     assert s == L.ADF_EINVAL and b"null argument" in lib.adf_last_error()
     assert seg == [-7] * 4 and bool((valid == -7).all())

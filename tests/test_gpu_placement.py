@@ -315,6 +315,62 @@ def test_atomic_number_outside_the_tables_is_an_error():
         PL.interstitial_distances(out, RADII, MASSES)
 
 
+def test_a_candidate_of_a_slab_outside_the_batch_is_refused():
+    """The range bit of the placement error word, through the raw entry (the wrapper builds cand_slab itself): the
+    kernel tests the slab index before it indexes any per-slab array with it, zeroes the candidate's own row and reports."""
+    from adsorbdiff_amd import lib as L
+    tri = torch.tensor([[0.0, 0.0, 5.0, 1.0, 0.0, 5.0, 0.0, 1.0, 5.0]], device=DEV)
+    i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=DEV)
+    tri_off, per_tri, cand_off, cell = i32([0, 1]), i32([2]), i32([0, 2]), torch.eye(3, device=DEV).mul(4.0).reshape(1, 9).contiguous()
+    draws = torch.full((2, 8), 0.25, dtype=torch.float64, device=DEV)
+    for slab, status in (([0, 0], L.ADF_OK), ([0, 1], L.ADF_EINVAL), ([-1, 0], L.ADF_EINVAL)):
+        cand, keep, cand_slab = torch.full((2, 3), -7.0, device=DEV), i32([-7, -7]), i32(slab)
+        got = L.load().adf_place_site_candidates(tri.data_ptr(), tri_off.data_ptr(), per_tri.data_ptr(), cand_off.data_ptr(),
+                                                 cand_slab.data_ptr(), cell.data_ptr(), draws.data_ptr(), 1, 2, cand.data_ptr(),
+                                                 keep.data_ptr(), None)
+        torch.cuda.synchronize()
+        assert got == status, (slab, L.load().adf_last_error())
+        if status != L.ADF_OK:
+            assert b"place_site_candidates: an offset, slab index or output row out of range" in L.load().adf_last_error()
+            bad = slab.index(1) if 1 in slab else slab.index(-1)
+            assert keep.tolist()[bad] == 0 and cand[bad].tolist() == [0.0, 0.0, 0.0]
+
+
+def test_a_binding_index_outside_the_adsorbate_is_refused():
+    """The binding bit of the placement error word, through the raw entry (the wrapper refuses such an index itself): one
+    slab of four atoms, one adsorbate of two, heuristic placement.  pl_place_kernel replaces the index by 0 before it
+    reads ads_pos with it, and an atomic number outside the radius table by row 0, so nothing is indexed out of range.
+    The bit outranks the atomic-number bit in the message."""
+    import ctypes as C
+
+    from adsorbdiff_amd import lib as L
+    from adsorbdiff_amd.hostargs import desc
+    i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=DEV)
+    slab_pos = torch.tensor([[0.0, 0.0, 5.0], [2.0, 0.0, 5.0], [0.0, 2.0, 5.0], [2.0, 2.0, 5.0]], device=DEV)
+    cell = torch.tensor([[4.0, 0.0, 0.0, 0.0, 4.0, 0.0, 0.0, 0.0, 20.0]], device=DEV)
+    slab_Z, slab_off = i32([29, 29, 29, 29]), i32([0, 4])
+    d = desc(slab_pos, cell, slab_Z, slab_off, 1, 4)
+    site = torch.tensor([[1.0, 1.0, 5.0]], device=DEV)
+    draws = torch.full((1, 8), 0.25, dtype=torch.float64, device=DEV)
+    ads_off, ads_pos = i32([0, 2]), torch.tensor([[0.0, 0.0, 0.0], [0.0, 0.0, 1.1]], device=DEV)
+    radii, masses = torch.ones(120, device=DEV), torch.ones(120, device=DEV)
+    slab_of, pbc, out_row = i32([0]), i32([[1, 1, 0]]), i32([0])
+    for bind, ads_Z, status in ((1, [6, 8], L.ADF_OK), (2, [6, 8], L.ADF_EINVAL), (-1, [6, 8], L.ADF_EINVAL),
+                                (2, [6, 500], L.ADF_EINVAL)):
+        b, z = i32([bind]), i32(ads_Z)
+        out = torch.full((2, 3), -7.0, device=DEV)
+        sn = torch.zeros(1, dtype=torch.float64, device=DEV)
+        nc, meta = i32([0]), torch.zeros(1, 4, dtype=torch.float64, device=DEV)
+        got = L.load().adf_place_adsorbates(C.byref(d), slab_of.data_ptr(), site.data_ptr(), draws.data_ptr(), ads_off.data_ptr(),
+                                            ads_pos.data_ptr(), z.data_ptr(), radii.data_ptr(), 120, masses.data_ptr(), 120,
+                                            C.c_float(0.1), 1, b.data_ptr(), pbc.data_ptr(), 1, out_row.data_ptr(), 2,
+                                            out.data_ptr(), sn.data_ptr(), nc.data_ptr(), meta.data_ptr(), None)
+        torch.cuda.synchronize()
+        assert got == status, (bind, ads_Z, L.load().adf_last_error())
+        if status != L.ADF_OK:
+            assert b"place_adsorbates: binding_idx outside the adsorbate" in L.load().adf_last_error(), (bind, ads_Z)
+
+
 def test_adsorbate_slab_config_interface():
     """The reference's keyword names on duck-typed objects: given sites are placed as ``place`` places them; sampled
     sites come from the triangle table."""

@@ -179,7 +179,7 @@ def raw_voronoi(cases, cutoff=H.CUTOFF, offsets=None):
     return status, N, [t.cpu() for t in (cn, om, nn, fl)]
 
 
-def raw_tags(cases, table, height=H.HEIGHT):
+def raw_tags(cases, table, height=H.HEIGHT, mass_table=None):
     sb = H.batch_of(cases, DEV)
     B, N = len(cases), int(sb.pos.shape[0])
     off = torch.zeros(B + 1, dtype=torch.int32, device=DEV)
@@ -187,7 +187,7 @@ def raw_tags(cases, table, height=H.HEIGHT):
     pos, cell = sb.pos.float().contiguous(), sb.cell.float().reshape(B, 9).contiguous()
     pbc = torch.ones(B, 3, dtype=torch.int32, device=DEV)
     Z = sb.atomic_numbers.to(torch.int32).contiguous()
-    m = torch.from_numpy(masses()).to(DEV)
+    m = torch.from_numpy(masses() if mass_table is None else mass_table).to(DEV)
     table = torch.as_tensor(table).to(DEV, torch.float64).contiguous()
     tags = torch.full((N + GUARD,), SENTINEL, dtype=torch.int32, device=DEV)
     cn = torch.full((N + GUARD,), float(SENTINEL), dtype=torch.float64, device=DEV)
@@ -230,6 +230,35 @@ def test_refused_arguments_leave_the_outputs_alone():
         ST.tag_surface_atoms(H.batch_of(slabs, DEV), bulk=missing, masses=masses())
     with pytest.raises(ValueError, match="open cell"):
         ST.bulk_coordination(H.batch_of([H.case("fcc_primitive"), H.case("alone")], DEV))
+
+
+def test_the_remaining_error_bits_name_their_atom():
+    """The bits of the Voronoi error word that the test above does not raise, each from a system of one or four atoms and
+    through the raw entries.  In every case the kernels refuse the value before anything is indexed with it: a refused
+    cell or pair count clears the system's reps[3], which vo_cell_kernel tests first; an atomic number outside the tables
+    ends vo_tag_prepare_kernel before its masses[Z] load; the commits return on a set error word."""
+    good, one = H.case("fcc4_rattled"), H.case("fcc_primitive")
+    flat = dict(one, cell=np.array([[2.0, 0.0, 0.0], [0.0, 2.0, 0.0], [2.0, 2.0, 0.0]], np.float32))
+    status, N, outs = raw_voronoi([good, flat])
+    assert status == L.ADF_EINVAL, L.load().adf_last_error()
+    assert b"voronoi_coordination: the cell of the system of atom 4 is singular or not finite" in L.load().adf_last_error()
+    assert all((t == SENTINEL).all() for t in outs)
+    tiny = dict(one, pos=np.asarray(one["pos"], np.float32) * 1e-3, cell=np.asarray(one["cell"], np.float32) * 1e-3)
+    status, N, outs = raw_voronoi([good, tiny])
+    assert status == L.ADF_EOVERFLOW, L.load().adf_last_error()
+    assert b"the system of atom 4 has more than 16777216 (atom, image) pairs within the cutoff's repeats" in L.load().adf_last_error()
+    assert all((t == SENTINEL).all() for t in outs)
+    table = np.full((1, 119), 12.0)
+    Z = np.asarray(good["Z"]).copy()
+    Z[2] = 119
+    status, N, outs = raw_tags([dict(good, Z=Z)], table)
+    assert status == L.ADF_EINVAL, L.load().adf_last_error()
+    assert b"tag_surface_atoms: atom 2 has an atomic number outside [0, 118]" in L.load().adf_last_error()
+    assert all((t == SENTINEL).all() for t in outs)
+    status, N, outs = raw_tags([good], table, mass_table=np.zeros_like(masses()))
+    assert status == L.ADF_EINVAL, L.load().adf_last_error()
+    assert b"tag_surface_atoms: the masses of the system of atom 0 do not sum to a positive number" in L.load().adf_last_error()
+    assert all((t == SENTINEL).all() for t in outs)
 
 
 # 6

@@ -140,7 +140,7 @@ def test_a_slab_gets_the_same_rows_alone_reversed_and_twice():
 
 
 # 7
-def raw_call(cases, capacity, circle_tol=H.CIRCLE_TOL, guard=4):
+def raw_call(cases, capacity, circle_tol=H.CIRCLE_TOL, guard=4, offsets=None):
     """adf_surface_triangles on tables of ``capacity`` rows followed by ``guard`` rows of a sentinel: (status, tri_offset,
     tri, index) with the guard rows included."""
     sb = H.batch_of(cases, DEV)
@@ -148,6 +148,8 @@ def raw_call(cases, capacity, circle_tol=H.CIRCLE_TOL, guard=4):
     pos, tags = sb.pos.float().contiguous(), sb.tags.to(torch.int32).contiguous()
     off = torch.zeros(B + 1, dtype=torch.int32, device=DEV)
     off[1:] = torch.cumsum(sb.natoms.reshape(-1), 0).to(torch.int32)
+    if offsets is not None:
+        off = torch.tensor(offsets, dtype=torch.int32, device=DEV)
     cell = sb.cell.float().reshape(B, 9).contiguous()
     tri = torch.full((capacity + guard, 3, 3), -77.0, dtype=torch.float32, device=DEV)
     index = torch.full((capacity + guard, 3), -77, dtype=torch.int32, device=DEV)
@@ -172,6 +174,11 @@ def collinear():
                 cell=np.array([[3.0, 0.0, 0.0], [1.5, 0.0, 0.0], [0.0, 0.0, 20.0]], np.float32))
 
 
+def one_in_plane_vector():
+    """Only the first row of the cell has an in-plane component: there is no second tiling vector."""
+    return dict(collinear(), cell=np.array([[3.0, 0.0, 0.0], [0.0, 0.0, 5.0], [0.0, 0.0, 20.0]], np.float32))
+
+
 def test_errors_leave_the_tables_alone():
     good = list(H.generic3())
     T = sum(generic_run().counts)
@@ -180,12 +187,21 @@ def test_errors_leave_the_tables_alone():
     assert (tri[T:] == -77).all() and (index[T:] == -77).all() and (off[4:] == -77).all() and (index[:T] >= 0).all()
     for cases, capacity, tol, what in (([good[0], no_top(), good[2]], 18 * 40, H.CIRCLE_TOL, b"tag 1"),
                                        ([good[0], collinear()], 18 * 40, H.CIRCLE_TOL, b"collinear"),
+                                       ([good[0], one_in_plane_vector()], 18 * 40, H.CIRCLE_TOL,
+                                        b"surface_triangles: a cell has fewer than two in-plane lattice vectors (or a non-finite one)"),
                                        (good, T - 1, H.CIRCLE_TOL, b"more triangles"),
                                        (good, T, -1e-4, b"circle_tol")):
         status, off, tri, index = raw_call(cases, capacity, tol)
         assert status == L.ADF_EINVAL and what in L.load().adf_last_error(), what
         assert (tri == -77).all() and (index == -77).all(), what     # nothing is written, the guard rows least of all
         assert (off[len(cases) + 1:] == -77).all(), what
+    # offsets that descend, or run past the atoms: refused by the first kernel, before an atom is read through them
+    n0, n1 = len(good[0]["Z"]), len(good[1]["Z"])
+    for offsets in ([0, n0 + n1, n0], [0, n0, n0 + n1 + 1], [-1, n0, n0 + n1]):
+        status, off, tri, index = raw_call(good[:2], 18 * 40, offsets=offsets)
+        assert status == L.ADF_EINVAL, offsets
+        assert b"surface_triangles: atom offsets not ascending or outside [0, N]" in L.load().adf_last_error(), offsets
+        assert (tri == -77).all() and (index == -77).all(), offsets
     with pytest.raises(ValueError, match="tag 1"):
         PL.surface_triangles_device(H.batch_of([good[0], no_top()], DEV))
     with pytest.raises(ValueError, match="collinear"):

@@ -220,3 +220,13 @@ def test_ml_relax_unique_carries_the_representative_through_the_operation(monkey
     earlier = out.pos[n:2 * n].numpy()                                   # site 1 comes before it: g . s = r
     assert np.abs(H.apply_op(dict(a, pos=earlier), ops[5])["pos"] - relaxed.numpy()).max() < 2e-5
     assert np.abs(out.force[3 * n:].numpy()[-2:] - (-relaxed.numpy()[-2:]) @ ops[9]["R"].T).max() < 1e-5
+
+
+# adf_slab_symmetry_scratch sizes caller-owned memory, so its numbers are a contract: recorded from the build that laid the
+# scratch out by hand (five regions, each rounded up to 256 bytes), before the layout moved to the shared carver
+SCRATCH_BYTES = {(0, 0): 0, (1, 1): 2048, (7, 3): 5120, (64, 1): 8448, (1000, 16): 132864, (200000, 1000): 23680000}
+
+
+@pytest.mark.parametrize("num_atoms,num_slabs", sorted(SCRATCH_BYTES))
+def test_scratch_size_is_unchanged(num_atoms, num_slabs):
+    assert L.load().adf_slab_symmetry_scratch(num_atoms, num_slabs) == SCRATCH_BYTES[(num_atoms, num_slabs)]
