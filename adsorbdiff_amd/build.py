@@ -28,7 +28,7 @@ def needs_build() -> bool:
     if not LIB.exists():
         return True
     t = LIB.stat().st_mtime
-    deps = [CSRC / s for s in SOURCES] + sorted(CSRC.glob("*.h")) + [PKG.parent / "include" / "adsorbdiff_hip.h"]
+    deps = [CSRC / s for s in SOURCES] + sorted(CSRC.glob("*.h")) + sorted((PKG.parent / "include").glob("*.h"))
     return any(d.stat().st_mtime > t for d in deps)
 
 
@@ -66,8 +66,8 @@ def build(force: bool = False, verbose: bool = False) -> Path:
 
     cc = _hipcc()
     OBJ_DIR.mkdir(exist_ok=True)
-    hdr_t = max([p.stat().st_mtime for p in CSRC.glob("*.h")] + [(PKG.parent / "include" / "adsorbdiff_hip.h").stat().st_mtime,
-                                                                  Path(__file__).stat().st_mtime])
+    hdr_t = max([p.stat().st_mtime for p in CSRC.glob("*.h")] + [p.stat().st_mtime for p in (PKG.parent / "include").glob("*.h")] +
+                [Path(__file__).stat().st_mtime])
     jobs, objs = [], []
     for s in SOURCES:
         src, obj = CSRC / s, OBJ_DIR / (s + ".o")

@@ -35,6 +35,7 @@ adf_tune adf_tune_from_env() {
     t.eqv2_gemm_tile256 = (gt && atoi(gt) == 128) ? 0 : 1;
     t.eqv2_rotin_generic = getenv("ADF_EQV2_ROTIN_GENERIC") != nullptr;
     t.eqv2_rotout_generic = getenv("ADF_EQV2_ROTOUT_GENERIC") != nullptr;
+    t.sample_split = off_is_0("ADF_SAMPLE_SPLIT");
     return t;
 }
 const adf_tune& adf_tune_process() {
@@ -51,6 +52,7 @@ extern "C" int32_t adf_profile_enable(adf_painn_t h, int32_t on) {
     if (!h) { adf_set_error("null handle"); return ADF_EINVAL; }
     h->prof.enable(on != 0);
     ADF_HIP_CHECK(hipMemset(h->kcount, 0, 8 * sizeof(unsigned long long)));
+    if (h->twin) return adf_profile_enable(h->twin, on);
     return ADF_OK;
 }
 
@@ -63,7 +65,15 @@ extern "C" int32_t adf_profile_read(adf_painn_t h, float* ms, int64_t* count, in
         ADF_HIP_CHECK(hipMemset(h->kcount, 0, sizeof(k)));
         *message_ksteps = (int64_t)k[0];
     }
-    return h->prof.read(ms, count, ADF_PROF_NCAT);
+    ADF_TRY(h->prof.read(ms, count, ADF_PROF_NCAT));
+    if (h->twin) {   // the pair's profile: sums over both handles (the join has put B's work in front of `stream`'s end)
+        float ms2[ADF_PROF_NCAT];
+        int64_t count2[ADF_PROF_NCAT], k2 = 0;
+        ADF_TRY(adf_profile_read(h->twin, ms2, count2, message_ksteps ? &k2 : nullptr, h->twin->split_stream));
+        for (int c = 0; c < ADF_PROF_NCAT; ++c) { ms[c] += ms2[c]; count[c] += count2[c]; }
+        if (message_ksteps) *message_ksteps += k2;
+    }
+    return ADF_OK;
 }
 
 extern "C" int32_t adf_painn_create(const adf_painn_hparams* hp, adf_painn_t* out) {
@@ -163,6 +173,14 @@ static void free_workspaces(adf_painn* h) {
 
 extern "C" int32_t adf_painn_destroy(adf_painn_t h) {
     if (!h) return ADF_OK;
+    if (h->twin) { adf_set_error("destroy: the handle has a live twin that reads its weight images; destroy the twin first"); return ADF_EINVAL; }
+    if (h->parent) {   // a twin: the weight images are the parent's and stay; its own stream and events go
+        h->parent->twin = nullptr;
+        h->parent->split_last = false;
+        if (h->split_stream) { (void)hipStreamSynchronize((hipStream_t)h->split_stream); (void)hipStreamDestroy((hipStream_t)h->split_stream); }
+        for (void* e : h->split_ev)
+            if (e) (void)hipEventDestroy((hipEvent_t)e);
+    }
     if (h->inc_cnt_host) (void)hipHostFree(h->inc_cnt_host);
     for (int i = 0; i < 2; ++i)
         if (h->inc_ev[i]) (void)hipEventDestroy((hipEvent_t)h->inc_ev[i]);
@@ -171,9 +189,95 @@ extern "C" int32_t adf_painn_destroy(adf_painn_t h) {
     return ADF_OK;
 }
 
+// ---- the twin of a handle (include/adsorbdiff_split.h): a second set of everything a forward writes, around the parent's
+// weight images.  The images are fields of the parent that its pools own: the twin holds plain copies of the pointers,
+// outside its own pools, so it never frees them.  bound = false: forget them (the parent is re-binding).
+static void borrow_weights(adf_painn* t, const adf_painn* p, bool bound) {
+    t->emb = p->emb; t->rbf_offset = p->rbf_offset;
+    memcpy(t->layer, p->layer, sizeof(t->layer));
+    memcpy(t->head, p->head, sizeof(t->head));
+    memcpy(t->scale, p->scale, sizeof(t->scale));
+    t->rbf_pack = p->rbf_pack; t->rbf_bias_pack = p->rbf_bias_pack; t->rbf_pack16 = p->rbf_pack16;
+    t->rbf_bias_pack16 = p->rbf_bias_pack16; t->rbf_scales = p->rbf_scales; t->rbf_uniform = p->rbf_uniform;
+    t->w16_arena = p->w16_arena; t->w16_bytes = p->w16_bytes; t->w16_scales = p->w16_scales;
+    t->w16_bias_perm = p->w16_bias_perm; t->w16_scratch = p->w16_scratch; t->wfrag_arena = p->wfrag_arena;
+    t->weights_set = bound && p->weights_set;
+    t->rec0_valid = false;
+    t->inc_valid = false;
+}
+// the parent's switches and arithmetic, as they stand now; a change drops what the twin kept under the old ones
+static void follow_settings(adf_painn* t, const adf_painn* p) {
+    if (t->gemm_f32 != p->gemm_f32 || t->msg_f32 != p->msg_f32 || t->dist_floor != p->dist_floor || t->lift_on != p->lift_on) {
+        t->cache_valid = false; t->rec0_valid = false; t->inc_valid = false;
+    }
+    t->gemm_f32 = p->gemm_f32; t->msg_f32 = p->msg_f32; t->msg_f32_only = p->msg_f32_only; t->dist_floor = p->dist_floor;
+    t->lift_on = p->lift_on; t->tune = p->tune; t->inc_sync = p->inc_sync;
+}
+
+extern "C" int32_t adf_painn_create_twin(adf_painn_t parent, adf_painn_t* out) {
+    if (!parent || !out) { adf_set_error("create_twin: null argument"); return ADF_EINVAL; }
+    if (parent->parent) { adf_set_error("create_twin: the handle is a twin itself"); return ADF_EINVAL; }
+    if (parent->twin) { adf_set_error("create_twin: the handle already has a twin"); return ADF_EINVAL; }
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev != parent->device) {
+        adf_set_error("create_twin: the parent lives on device %d, the current device is %d", parent->device, dev);
+        return ADF_EINVAL;
+    }
+    adf_painn* t = new (std::nothrow) adf_painn();
+    if (!t) { adf_set_error("host allocation failed"); return ADF_EOOM; }
+    t->hp = parent->hp; t->device = parent->device; t->num_cus = parent->num_cus;
+    t->rmx = parent->rmx; t->inc_on = parent->inc_on;
+    follow_settings(t, parent);
+    // its own: flags, the k-step counter, view B's state and the stream pair's objects.  No weight image is allocated.
+    int32_t st = t->m_life.alloc(&t->flags, ADF_NFLAGS);
+    if (st == ADF_OK && hipMemset(t->flags, 0, sizeof(int32_t) * ADF_NFLAGS) != hipSuccess) st = ADF_EHIP;
+    if (st == ADF_OK) st = t->m_life.alloc(&t->kcount, 8);
+    if (st == ADF_OK && hipMemset(t->kcount, 0, 8 * sizeof(unsigned long long)) != hipSuccess) st = ADF_EHIP;
+    if (st == ADF_OK) st = t->m_life.alloc(&t->split_state, 16);
+    if (st == ADF_OK && hipStreamCreateWithFlags(reinterpret_cast<hipStream_t*>(&t->split_stream), hipStreamNonBlocking) != hipSuccess) st = ADF_EHIP;
+    for (int i = 0; i < 2 && st == ADF_OK; ++i)
+        if (hipEventCreateWithFlags(reinterpret_cast<hipEvent_t*>(&t->split_ev[i]), hipEventDisableTiming) != hipSuccess) st = ADF_EHIP;
+    if (st != ADF_OK) {
+        if (st == ADF_EHIP) adf_set_error("create_twin: %s", hipGetErrorString(hipGetLastError()));
+        t->parent = parent;       // (so that the destroy below releases the stream and the events)
+        parent->twin = t;
+        adf_painn_destroy(t);
+        return st;
+    }
+    borrow_weights(t, parent, true);
+    t->prof.enable(parent->prof.on);
+    t->parent = parent;
+    parent->twin = t;
+    *out = t;
+    return ADF_OK;
+}
+
+extern "C" int32_t adf_painn_set_split(adf_painn_t h, int32_t on) {
+    if (!h) { adf_set_error("null handle"); return ADF_EINVAL; }
+    h->tune.sample_split = on != 0;
+    return ADF_OK;
+}
+
+extern "C" int32_t adf_split_stats(adf_painn_t h, int64_t* split_runs, int64_t* fallback_runs) {
+    if (!h) { adf_set_error("null handle"); return ADF_EINVAL; }
+    if (split_runs) *split_runs = (int64_t)h->split_runs;
+    if (fallback_runs) *fallback_runs = (int64_t)h->split_fallbacks;
+    return ADF_OK;
+}
+
+// A parent that ran view A of a split run holds a graph cache, layer-0 records and kept layer state of that view, under the
+// same static-atom promise as the whole batch: before it runs anything else they go.
+static void leave_split(adf_painn* h) {
+    if (!h || !h->split_last) return;
+    h->split_last = false;
+    h->cache_valid = false; h->rec0_valid = false; h->inc_valid = false;
+}
+
 extern "C" int32_t adf_painn_set_weights(adf_painn_t h, int32_t n_weights, const void* const* w,
                                          const float* scale_factors, void* stream) {
     if (!h || !w || !scale_factors) { adf_set_error("null argument"); return ADF_EINVAL; }
+    if (h->parent) { adf_set_error("set_weights: a twin reads its parent's weights; bind them there"); return ADF_EINVAL; }
+    if (h->twin) borrow_weights(h->twin, h, false);   // whatever happens below, the twin trusts nothing it borrowed before
     const int L = h->hp.num_layers;
     const int expect = 2 + ADF_WEIGHTS_PER_LAYER * L + ADF_WEIGHTS_PER_HEAD * h->hp.num_heads;
     if (n_weights != expect) {
@@ -257,6 +361,7 @@ extern "C" int32_t adf_painn_set_weights(adf_painn_t h, int32_t n_weights, const
     h->rec0_valid = false;
     h->inc_valid = false;
     adf_grad_invalidate(h);
+    if (h->twin) borrow_weights(h->twin, h, true);
     return ADF_OK;
 }
 
@@ -339,7 +444,13 @@ static int32_t read_flags(adf_painn* h, hipStream_t s) {
     int32_t f[ADF_NFLAGS];
     ADF_HIP_CHECK(hipMemcpyAsync(f, h->flags, sizeof(f), hipMemcpyDeviceToHost, s));
     ADF_HIP_CHECK(hipMemsetAsync(h->flags, 0, sizeof(f), s));
+    int32_t f2[ADF_NFLAGS] = {};
+    if (h->twin) {   // the pair's flags are one set: a split run has joined view B's stream into `s`
+        ADF_HIP_CHECK(hipMemcpyAsync(f2, h->twin->flags, sizeof(f2), hipMemcpyDeviceToHost, s));
+        ADF_HIP_CHECK(hipMemsetAsync(h->twin->flags, 0, sizeof(f2), s));
+    }
     ADF_HIP_CHECK(hipStreamSynchronize(s));
+    for (int i = 0; i < ADF_NFLAGS; ++i) f[i] |= f2[i];
     if (f[4]) { adf_set_error("atomic number outside [1, %d] (rows of the embedding table)", h->hp.num_elements); return ADF_EINVAL; }
     if (f[0]) { adf_set_error("a centre atom has more than %d in-cutoff candidates", ADF_MAX_CAND); return ADF_EOVERFLOW; }
     if (f[2]) { adf_set_error("edge buffer overflow"); return ADF_EOVERFLOW; }
@@ -360,6 +471,7 @@ extern "C" int32_t adf_graph_set_moving(adf_painn_t h, const int32_t* moving, co
     if (!h) { adf_set_error("null handle"); return ADF_EINVAL; }
     if (moving && (!mov_idx || !mov_off)) { adf_set_error("moving mask needs mov_idx and mov_off"); return ADF_EINVAL; }
     h->moving = moving; h->mov_idx = mov_idx; h->mov_off = mov_off;
+    ++h->moving_serial;
     ADF_HIP_CHECK(hipMemset(h->flags, 0, sizeof(int32_t) * ADF_NFLAGS));  // a new promise starts with clean flags
     h->cache_valid = false;
     h->rec0_valid = false;
@@ -369,6 +481,7 @@ extern "C" int32_t adf_graph_set_moving(adf_painn_t h, const int32_t* moving, co
 
 extern "C" int32_t adf_graph_build(adf_painn_t h, const adf_batch* b, void* stream, int64_t* num_edges) {
     ADF_TRY(check_batch(h, b));
+    leave_split(h);
     ADF_TRY(ensure_capacity(h, b->num_atoms, b->num_systems));
     hipStream_t s = (hipStream_t)stream;
     ADF_TRY(adf_graph_build_impl(h, b, s));
@@ -890,12 +1003,14 @@ static int32_t forward_impl(adf_painn_t h, const adf_batch* b, const int32_t* ou
 }
 
 extern "C" int32_t adf_painn_forward(adf_painn_t h, const adf_batch* b, float* f1, float* f2, void* stream) {
+    leave_split(h);
     return forward_impl(h, b, nullptr, 0, f1, f2, stream);
 }
 
 extern "C" int32_t adf_painn_forward_subset(adf_painn_t h, const adf_batch* b, const int32_t* out_idx, int32_t n_out,
                                             float* f1, float* f2, void* stream) {
     if (!out_idx || n_out < 0) { adf_set_error("forward_subset: null index list"); return ADF_EINVAL; }
+    leave_split(h);
     return forward_impl(h, b, out_idx, n_out, f1, f2, stream);
 }
 
@@ -972,6 +1087,7 @@ extern "C" int32_t adf_painn_forward_energy(adf_painn_t h, const adf_batch* b, f
     if (!energy || (h->hp.num_heads >= 1 && !forces)) { adf_set_error("forward_energy: null output"); return ADF_EINVAL; }
     if (h->hp.num_heads > 1) { adf_set_error("forward_energy: the S2EF model has one force head"); return ADF_EINVAL; }
     hipStream_t s = (hipStream_t)stream;
+    leave_split(h);
     ADF_TRY(forward_impl(h, b, nullptr, 0, forces, nullptr, stream));
     if (!h->x_last) { adf_set_error("internal: no node features after the forward"); return ADF_EINVAL; }
     const int N = b->num_atoms, H = h->hp.hidden_channels, H2 = H / 2;
@@ -1036,10 +1152,15 @@ extern "C" int32_t adf_painn_set_incremental(adf_painn_t h, int32_t on) {
         }
     }
     h->inc_valid = false;
+    ++h->inc_set_serial;
     (void)inc_harvest(h, h->inc_slot, true);
     (void)inc_harvest(h, h->inc_slot ^ 1, true);
     h->inc_seen_valid = false;
     h->inc_rows = h->inc_rows_full = h->inc_edges = h->inc_launches = 0;
+    if (h->twin) {   // the pair's totals are sums: both start from zero together
+        ADF_TRY(adf_painn_set_incremental(h->twin, on));
+        h->twin->seen_inc_serial = h->inc_set_serial;
+    }
     return ADF_OK;
 }
 
@@ -1099,6 +1220,7 @@ extern "C" int32_t adf_sample(adf_painn_t h, const adf_batch* b, float* pos, con
                               const adf_step_coef* coefs_dev, int32_t num_steps, const float* z_tr_all,
                               const float* z_rot_all, int32_t early_stop_count, int32_t poll_every, int32_t* state,
                               const int32_t* out_idx, int32_t n_out, float* f1, float* f2, void* stream) {
+    leave_split(h);
     return adf_model_sample(model(h), b, pos, tags, fixed, coefs_dev, num_steps, z_tr_all, z_rot_all, early_stop_count,
                             poll_every, state, out_idx, n_out, f1, f2, nullptr, 0, (hipStream_t)stream);
 }
@@ -1108,6 +1230,7 @@ extern "C" int32_t adf_sample_traj(adf_painn_t h, const adf_batch* b, float* pos
                                    const float* z_rot_all, int32_t early_stop_count, int32_t poll_every, int32_t* state,
                                    const int32_t* out_idx, int32_t n_out, float* f1, float* f2, adf_frames_t sink,
                                    int32_t frame_every, void* stream) {
+    leave_split(h);
     if (!sink) { adf_set_error("sample_traj: null sink"); return ADF_EINVAL; }
     return adf_model_sample(model(h), b, pos, tags, fixed, coefs_dev, num_steps, z_tr_all, z_rot_all, early_stop_count,
                             poll_every, state, out_idx, n_out, f1, f2, sink, frame_every, (hipStream_t)stream);
@@ -1125,6 +1248,7 @@ extern "C" int32_t adf_tr_sample(adf_painn_t h, const adf_batch* b, float* pos, 
                                  const adf_tr_coef* coefs_dev, int32_t num_steps, const float* z_all,
                                  int32_t early_stop_count, int32_t poll_every, int32_t* state, const int32_t* out_idx,
                                  int32_t n_out, float* f1, void* stream) {
+    leave_split(h);
     return adf_model_tr_sample(model(h), b, pos, tags, coefs_dev, num_steps, z_all, early_stop_count, poll_every, state,
                                out_idx, n_out, f1, nullptr, 0, (hipStream_t)stream);
 }
@@ -1133,13 +1257,87 @@ extern "C" int32_t adf_tr_sample_traj(adf_painn_t h, const adf_batch* b, float* 
                                       const adf_tr_coef* coefs_dev, int32_t num_steps, const float* z_all,
                                       int32_t early_stop_count, int32_t poll_every, int32_t* state, const int32_t* out_idx,
                                       int32_t n_out, float* f1, adf_frames_t sink, int32_t frame_every, void* stream) {
+    leave_split(h);
     if (!sink) { adf_set_error("tr_sample_traj: null sink"); return ADF_EINVAL; }
     return adf_model_tr_sample(model(h), b, pos, tags, coefs_dev, num_steps, z_all, early_stop_count, poll_every, state,
                                out_idx, n_out, f1, sink, frame_every, (hipStream_t)stream);
 }
 
-extern "C" int32_t adf_get_counters(adf_painn_t h, adf_counters* out, void* stream) {
-    if (!h || !out || h->lastN <= 0) { adf_set_error("no forward has run"); return ADF_EINVAL; }
+// ---- adf_sample on two views of the batch, two handles, two streams (include/adsorbdiff_split.h; the loop: stepper.hip)
+extern "C" int32_t adf_sample_split(adf_painn_t h, adf_painn_t t, const adf_batch* b, const adf_split_view* v, float* pos,
+                                    const int32_t* tags, const int32_t* fixed, const adf_step_coef* coefs_dev,
+                                    int32_t num_steps, const float* z_tr_all, const float* z_rot_all,
+                                    int32_t early_stop_count, int32_t poll_every, int32_t* state, const int32_t* out_idx,
+                                    int32_t n_out, float* f1, float* f2, void* stream) {
+    ADF_TRY(check_batch(h, b));
+    if (!t || t->parent != h) { adf_set_error("sample_split: the second handle is not this handle's twin"); return ADF_EINVAL; }
+    hipStream_t s = (hipStream_t)stream;
+    const bool per_system = h->ps_state != nullptr;
+    // The one-stream loop, unchanged, where two chains are not independent or not the same arithmetic: the coupled early
+    // stop makes every step wait for all systems; the exact-f32 retry is a decision of the whole batch.
+    const bool split = h->tune.sample_split && b->num_systems >= 2 && !h->gemm_f32 && !(early_stop_count > 0 && !per_system);
+    if (!split) {
+        leave_split(h);
+        ++h->split_fallbacks;
+        return adf_model_sample(model(h), b, pos, tags, fixed, coefs_dev, num_steps, z_tr_all, z_rot_all, early_stop_count,
+                                poll_every, state, out_idx, n_out, f1, f2, nullptr, 0, s);
+    }
+    const int32_t B = b->num_systems, N = b->num_atoms;
+    if (!v || v->cut <= 0 || v->cut >= B || v->atoms_a <= 0 || v->atoms_a >= N || !v->atom_offset || !v->batch) {
+        adf_set_error("sample_split: the view does not cut the batch into two non-empty sides");
+        return ADF_EINVAL;
+    }
+    if (!pos || !tags || !f1 || !f2 || !state || num_steps <= 0) { adf_set_error("sample_split: bad argument"); return ADF_EINVAL; }
+    if (out_idx && (v->n_out_a < 0 || v->n_out_b < 0 || v->n_out_a + v->n_out_b != n_out || (v->n_out_b > 0 && !v->out_idx))) {
+        adf_set_error("sample_split: the view's share of out_idx does not add up to n_out = %d", (int)n_out);
+        return ADF_EINVAL;
+    }
+    if (h->moving && (!v->mov_idx || !v->mov_off)) { adf_set_error("sample_split: a static-atom promise is in force and the view has no moving lists"); return ADF_EINVAL; }
+    if (per_system && h->ps_B != B) { adf_set_error("per-system stop is set for %d systems, the batch has %d", (int)h->ps_B, (int)B); return ADF_EINVAL; }
+    const int32_t cut = v->cut, NA = v->atoms_a;
+    // the parent: whatever it kept of another shape (the whole batch, another cut) under this promise goes
+    if (!h->split_last || h->split_cut != cut || h->split_N != N) { h->cache_valid = false; h->rec0_valid = false; h->inc_valid = false; }
+    h->split_last = true; h->split_cut = cut; h->split_N = N;
+    // the twin follows the parent: switches, arithmetic, the static-atom promise, the incremental-layer switch
+    follow_settings(t, h);
+    const int32_t* movB = h->moving ? h->moving + NA : nullptr;   // a new promise, or other lists for the same one
+    if (t->seen_moving_serial != h->moving_serial || t->moving != movB ||
+        (movB && (t->mov_idx != v->mov_idx || t->mov_off != v->mov_off))) {
+        ADF_TRY(adf_graph_set_moving(t, h->moving ? h->moving + NA : nullptr, h->moving ? v->mov_idx : nullptr,
+                                     h->moving ? v->mov_off : nullptr));
+        t->seen_moving_serial = h->moving_serial;
+    }
+    if (t->seen_inc_serial != h->inc_set_serial || t->inc_on != h->inc_on) {
+        ADF_TRY(adf_painn_set_incremental(t, h->inc_on ? 1 : 0));
+        t->seen_inc_serial = h->inc_set_serial;
+    }
+    if (!per_system && num_steps > t->split_hist_cap) {
+        ADF_HIP_CHECK(hipDeviceSynchronize());
+        t->split_hist_cap = 0;
+        ADF_TRY(t->m_life.alloc(&t->split_hist, (size_t)2 * num_steps));
+        t->split_hist_cap = num_steps;
+    }
+    adf_batch bA = *b, bB = *b;   // both views search the whole batch's lattice images (reps)
+    bA.num_systems = cut; bA.num_atoms = NA;
+    bB.num_systems = B - cut; bB.num_atoms = N - NA;
+    bB.pos = b->pos + 3 * (size_t)NA; bB.cell = b->cell + 9 * (size_t)cut;
+    bB.atomic_numbers = b->atomic_numbers ? b->atomic_numbers + NA : nullptr;
+    bB.batch = v->batch; bB.atom_offset = v->atom_offset;
+    adf_model mA = model(h), mB = model(t);
+    if (per_system) { mA.sys_B = cut; mB.sys_state = h->ps_state + 4 * (size_t)cut; mB.sys_B = B - cut; }
+    else { mB.sys_state = nullptr; mB.sys_B = 0; }
+    adf_split_side A = {&bA, pos, tags, fixed, out_idx, out_idx ? v->n_out_a : 0, f1, f2, state,
+                        per_system ? nullptr : t->split_hist, 0, s};
+    adf_split_side Bv = {&bB, pos + 3 * (size_t)NA, tags + NA, fixed ? fixed + NA : nullptr, out_idx ? v->out_idx : nullptr,
+                         out_idx ? v->n_out_b : 0, f1 + 3 * (size_t)NA, f2 + 3 * (size_t)NA, t->split_state,
+                         per_system ? nullptr : t->split_hist + t->split_hist_cap, cut, (hipStream_t)t->split_stream};
+    ++h->split_runs;
+    return adf_model_sample_split(mA, mB, A, Bv, coefs_dev, num_steps, z_tr_all, z_rot_all, B, early_stop_count, poll_every,
+                                  t->split_state + 8, (hipEvent_t)t->split_ev[0], (hipEvent_t)t->split_ev[1]);
+}
+
+// the counters of one handle
+static int32_t handle_counters(adf_painn* h, adf_counters* out, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     const int64_t N = h->lastN, H = h->hp.hidden_channels, R = h->hp.num_rbf, L = h->hp.num_layers;
     int32_t e = 0;
@@ -1159,5 +1357,22 @@ extern "C" int32_t adf_get_counters(adf_painn_t h, adf_counters* out, void* stre
     ADF_TRY(inc_harvest(h, h->inc_slot ^ 1, true));
     out->inc_rows = (int64_t)h->inc_rows; out->inc_rows_full = (int64_t)h->inc_rows_full;
     out->inc_msg_launches = (int64_t)h->inc_launches; out->inc_msg_edges = (int64_t)h->inc_edges;
+    return ADF_OK;
+}
+
+extern "C" int32_t adf_get_counters(adf_painn_t h, adf_counters* out, void* stream) {
+    if (!h || !out || h->lastN <= 0) { adf_set_error("no forward has run"); return ADF_EINVAL; }
+    ADF_TRY(handle_counters(h, out, stream));
+    if (!h->twin || h->twin->lastN <= 0) return ADF_OK;
+    // the pair: every field is a sum (all are linear in E and N) - the totals of the incremental layers always, the last
+    // graph's only when the last run was split
+    adf_counters c;
+    ADF_TRY(handle_counters(h->twin, &c, stream));
+    if (h->split_last) {
+        out->num_edges += c.num_edges; out->num_atoms += c.num_atoms;
+        out->message_bytes_per_layer += c.message_bytes_per_layer; out->dense_flops += c.dense_flops;
+    }
+    out->inc_rows += c.inc_rows; out->inc_rows_full += c.inc_rows_full;
+    out->inc_msg_launches += c.inc_msg_launches; out->inc_msg_edges += c.inc_msg_edges;
     return ADF_OK;
 }

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/adsorbdiff_hip.h"
+#include "../../include/adsorbdiff_split.h"
 
 void adf_set_error(const char* fmt, ...);
 

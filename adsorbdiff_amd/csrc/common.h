@@ -209,6 +209,18 @@ struct adf_painn {
     // ---- optional HIP-event profiling of the forward (bench.py roofline); see api.hip
     adf_prof prof;
     unsigned long long* kcount;           // device counter: executed k-steps of the message kernel
+    // ---- two half-batches on two streams (api.hip adf_sample_split, stepper.hip sample_loop_split)
+    adf_painn* twin;                      // a parent: its twin (adf_painn_create_twin), else null
+    adf_painn* parent;                    // a twin: the handle whose weight images it reads (never freed here)
+    bool split_last;                      // parent: its caches and graph belong to view A of a split run
+    int32_t split_cut; int64_t split_N;   // ... of this cut of a batch of this many atoms
+    unsigned long long split_runs, split_fallbacks;
+    unsigned long long moving_serial, inc_set_serial;     // calls of adf_graph_set_moving / adf_painn_set_incremental
+    unsigned long long seen_moving_serial, seen_inc_serial;   // twin: the parent's calls it has followed
+    void* split_stream;                   // twin: hipStream_t of view B (non-blocking)
+    void* split_ev[2];                    // twin: hipEvent_t fork, join
+    int32_t* split_state;                 // twin: device int32[16]: view B's state[8], the caller's state at the fork [8]
+    int32_t* split_hist; int64_t split_hist_cap;   // twin: device [2][cap] all-converged flag of every step of A and of B
     // ---- owners of the device buffers above, one per set that lives and dies together
     adf_pool m_life;   // creation to destruction: rbf_pack*, flags, kcount, the w16_* and wfrag arenas, oe0_buf
     adf_pool m_ws;     // the workspaces sized by capN / capB / capE, prev_* and rmx_part included
@@ -306,7 +318,8 @@ int32_t adf_stepper_init(const adf_batch* b, float* pos, const int32_t* tags, co
 int32_t adf_stepper_step(float* sys, const adf_batch* b, float* pos, const int32_t* tags, const int32_t* fixed,
                          const float* f1, const float* f2, const adf_step_coef* coef, const adf_step_coef* coefs_dev,
                          int num_steps, const float* z_tr, const float* z_rot, int32_t early_stop_count,
-                         int32_t* state, float* dcom, float* drot, hipStream_t s, int32_t* sys_state = nullptr);
+                         int32_t* state, float* dcom, float* drot, hipStream_t s, int32_t* sys_state = nullptr,
+                         int32_t* hist_t = nullptr);   // hist_t (coupled rule): receives this step's all-converged flag
 // translation-only samplers (reverse_sde_sampling / langevin_dynamics): head-1 mean, dcom = coef * score (+ noise * z),
 // wrap, pos += dcom on the adsorbate; same state[] protocol as adf_stepper_step
 int32_t adf_stepper_tr_step(float* sys, const adf_batch* b, float* pos, const int32_t* tags, const float* f1,
@@ -337,7 +350,7 @@ int32_t adf_model_init_placement(const adf_model& m, const adf_batch* b, float* 
 int32_t adf_model_sde_step(const adf_model& m, const adf_batch* b, float* pos, const int32_t* tags, const int32_t* fixed,
                            const float* f1, const float* f2, const adf_step_coef* coef, const adf_step_coef* coefs_dev,
                            int32_t num_steps, const float* z_tr, const float* z_rot, int32_t early_stop_count,
-                           int32_t* state, float* dcom, float* drot, hipStream_t s);
+                           int32_t* state, float* dcom, float* drot, hipStream_t s, int32_t* hist_t = nullptr);
 int32_t adf_model_tr_step(const adf_model& m, const adf_batch* b, float* pos, const int32_t* tags, const float* f1,
                           const adf_tr_coef* coef, const adf_tr_coef* coefs_dev, int32_t num_steps, const float* z,
                           int32_t early_stop_count, int32_t* state, float* dcom, hipStream_t s);
@@ -350,3 +363,25 @@ int32_t adf_model_tr_sample(const adf_model& m, const adf_batch* b, float* pos, 
                             const adf_tr_coef* coefs_dev, int32_t num_steps, const float* z_all, int32_t early_stop_count,
                             int32_t poll_every, int32_t* state, const int32_t* out_idx, int32_t n_out, float* f1,
                             adf_frames* sink, int32_t frame_every, hipStream_t s);
+
+// ---- two half-batches on two streams (stepper.hip).  One view of a split run: what differs between the two sides.
+// Every array is the caller's, offset to the view's first atom / system; nothing is copied.
+struct adf_split_side {
+    const adf_batch* b;        // the view's batch descriptor (whole-batch reps)
+    float* pos;
+    const int32_t* tags;
+    const int32_t* fixed;
+    const int32_t* out_idx;    // re-based to the view's first atom (null: all atoms)
+    int32_t n_out;
+    float* f1;
+    float* f2;
+    int32_t* state;            // the view's own state[8]
+    int32_t* hist;             // [num_steps] all-converged flag per step (coupled rule), else null
+    int32_t sys0;              // the view's first system in the whole batch: its rows of the noise tables
+    hipStream_t s;
+};
+// fork / join: events of the pair; state_init: the caller's state at the fork [8]
+int32_t adf_model_sample_split(const adf_model& mA, const adf_model& mB, adf_split_side A, adf_split_side B,
+                               const adf_step_coef* coefs_dev, int32_t num_steps, const float* z_tr_all,
+                               const float* z_rot_all, int32_t total_systems, int32_t early_stop_count, int32_t poll_every,
+                               int32_t* state_init, hipEvent_t fork, hipEvent_t join);

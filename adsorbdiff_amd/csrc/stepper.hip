@@ -11,6 +11,8 @@
 //             utils/rot_utils.py:18-98) + translation of each adsorbate
 // The reference does this with a Python loop over systems and a device->host sync per step; here
 // it is two tiny kernels (one wave per system) and no host round trip.
+#include <stdlib.h>
+
 #include "common.h"
 
 struct StepParams {
@@ -201,6 +203,12 @@ __global__ void adf_step_decide_kernel(int32_t* state, int early_stop_count) {
     }
 }
 
+// a split run (sample_loop_split) keeps every step's all-converged flag of each view: the whole batch's count of converged
+// steps is formed from the two histories at the join.  Runs between the reduce and the decide launch of its step.
+__global__ void adf_step_keep_flag_kernel(const int32_t* state, int32_t* hist_t) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) *hist_t = state[2];
+}
+
 __global__ __launch_bounds__(64) void adf_step_apply_kernel(StepParams p) {
     if (p.state[1]) return;  // the reference's `break`: this and all later steps leave pos untouched
     const int b = blockIdx.x, lane = threadIdx.x;
@@ -281,7 +289,7 @@ int32_t adf_stepper_init(const adf_batch* b, float* pos, const int32_t* tags, co
 int32_t adf_stepper_step(float* sys, const adf_batch* b, float* pos, const int32_t* tags, const int32_t* fixed,
                          const float* f1, const float* f2, const adf_step_coef* coef, const adf_step_coef* coefs_dev,
                          int num_steps, const float* z_tr, const float* z_rot, int32_t early_stop_count,
-                         int32_t* state, float* dcom, float* drot, hipStream_t s, int32_t* sys_state) {
+                         int32_t* state, float* dcom, float* drot, hipStream_t s, int32_t* sys_state, int32_t* hist_t) {
     StepParams p;
     p.cell = b->cell; p.atom_offset = b->atom_offset; p.tags = tags; p.fixed = fixed; p.pos = pos;
     p.f1 = f1; p.f2 = f2; p.z_tr = z_tr; p.z_rot = z_rot; p.sys = sys; p.state = state;
@@ -295,6 +303,7 @@ int32_t adf_stepper_step(float* sys, const adf_batch* b, float* pos, const int32
         return ADF_OK;
     }
     hipLaunchKernelGGL(adf_step_reduce_kernel, dim3(p.B), dim3(64), 0, s, p);
+    if (hist_t) hipLaunchKernelGGL(adf_step_keep_flag_kernel, dim3(1), dim3(64), 0, s, state, hist_t);
     hipLaunchKernelGGL(adf_step_decide_kernel, dim3(1), dim3(64), 0, s, state, early_stop_count);
     hipLaunchKernelGGL(adf_step_apply_kernel, dim3(p.B), dim3(64), 0, s, p);
     ADF_HIP_CHECK(hipGetLastError());
@@ -453,7 +462,7 @@ int32_t adf_model_init_placement(const adf_model& m, const adf_batch* b, float* 
 int32_t adf_model_sde_step(const adf_model& m, const adf_batch* b, float* pos, const int32_t* tags, const int32_t* fixed,
                            const float* f1, const float* f2, const adf_step_coef* coef, const adf_step_coef* coefs_dev,
                            int32_t num_steps, const float* z_tr, const float* z_rot, int32_t early_stop_count,
-                           int32_t* state, float* dcom, float* drot, hipStream_t s) {
+                           int32_t* state, float* dcom, float* drot, hipStream_t s, int32_t* hist_t) {
     ADF_TRY(m.check(m.h, b));
     if (!pos || !tags || !f1 || !f2 || (!coef && !coefs_dev) || !state) { adf_set_error("null argument"); return ADF_EINVAL; }
     if (!coef && num_steps <= 0) { adf_set_error("num_steps must be positive"); return ADF_EINVAL; }
@@ -462,7 +471,7 @@ int32_t adf_model_sde_step(const adf_model& m, const adf_batch* b, float* pos, c
     ADF_TRY(m.grow(m.h, b, &sys));
     m.prof(m.h, true, s);
     const int32_t st = adf_stepper_step(sys, b, pos, tags, fixed, f1, f2, coef, coef ? nullptr : coefs_dev, num_steps, z_tr,
-                                        z_rot, early_stop_count, state, dcom, drot, s, m.sys_state);
+                                        z_rot, early_stop_count, state, dcom, drot, s, m.sys_state, hist_t);
     m.prof(m.h, false, s);
     return st;
 }
@@ -537,6 +546,112 @@ int32_t adf_model_tr_sample(const adf_model& m, const adf_batch* b, float* pos, 
                            return adf_model_tr_step(m, b, pos, tags, f1, nullptr, coefs_dev, num_steps,
                                                     z_all ? z_all + z : nullptr, early_stop_count, state, nullptr, s);
                        });
+}
+
+// ---------------------------------------------------------------------------- two half-batches, two streams
+// The join of a split run, one thread: the caller's state[] as the one-stream loop on the whole batch leaves it.
+// st: view A's state (the caller's array), sb: view B's, init: the caller's state at the fork.
+//   per-system rule: [0] frozen systems and [3] max steps applied are a sum / a maximum over the views, [1] all B frozen.
+//   coupled rule (no early stop, nothing freezes): [0] counts the steps at which EVERY system had converged = the steps at
+//   which both views' flags were set; [3] steps applied and [4] steps issued are the same on both views.
+__global__ void adf_split_combine_kernel(int32_t* st, const int32_t* sb, const int32_t* init, const int32_t* hist_a,
+                                         const int32_t* hist_b, int steps, int B, int per_system) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    if (per_system) {
+        st[0] = st[0] + sb[0] - init[0];
+        st[1] = st[0] >= B ? 1 : 0;
+        st[3] = max(st[3], sb[3]);
+        return;
+    }
+    int both = 0;
+    for (int t = 0; t < steps; ++t) both += (hist_a[t] != 0 && hist_b[t] != 0) ? 1 : 0;
+    st[0] = init[0] + both;
+}
+
+// sample_loop for two views of one batch cut at a system boundary: view A on its own (the caller's) stream with the model,
+// view B on the pair's second stream with the twin.  One event forks B off A's stream at entry, one joins it before the
+// return; in between the two chains share nothing: each has its handle, its state[] and its rows of every array.  The
+// host enqueues step t of A, then step t of B, so both queues stay fed; it synchronises only where sample_loop does
+// (the poll of the per-system early stop).  The noise tables are [step][system][3] over the WHOLE batch: a view reads
+// its systems' rows of step t at t * total_systems * 3 + sys0 * 3.
+int32_t adf_model_sample_split(const adf_model& mA, const adf_model& mB, adf_split_side A, adf_split_side B,
+                               const adf_step_coef* coefs_dev, int32_t num_steps, const float* z_tr_all,
+                               const float* z_rot_all, int32_t total_systems, int32_t early_stop_count, int32_t poll_every,
+                               int32_t* state_init, hipEvent_t fork, hipEvent_t join) {
+    ADF_TRY(mA.check(mA.h, A.b));
+    ADF_TRY(mB.check(mB.h, B.b));
+    if (num_steps <= 0 || !coefs_dev || !A.state || !B.state || !state_init || !A.f1 || !A.f2 || !A.pos || !A.tags) {
+        adf_set_error("sample_split: bad argument");
+        return ADF_EINVAL;
+    }
+    if ((z_tr_all == nullptr) != (z_rot_all == nullptr)) { adf_set_error("sample_split: need both noise tables or none"); return ADF_EINVAL; }
+    ADF_TRY(check_per_system(mA, A.b));
+    ADF_TRY(check_per_system(mB, B.b));
+    const bool per_system = mA.sys_state != nullptr;
+    if (!per_system && (!A.hist || !B.hist)) { adf_set_error("sample_split: no step history"); return ADF_EINVAL; }
+    // fork: B's stream takes over from everything enqueued on A's so far; both views start from the caller's state
+    ADF_HIP_CHECK(hipMemcpyAsync(state_init, A.state, 8 * sizeof(int32_t), hipMemcpyDeviceToDevice, A.s));
+    ADF_HIP_CHECK(hipEventRecord(fork, A.s));
+    ADF_HIP_CHECK(hipStreamWaitEvent(B.s, fork, 0));
+    ADF_HIP_CHECK(hipMemcpyAsync(B.state, state_init, 8 * sizeof(int32_t), hipMemcpyDeviceToDevice, B.s));
+    const size_t z_stride = (size_t)total_systems * 3;
+    auto one = [&](const adf_model& m, const adf_split_side& v, int t) -> int32_t {
+        ADF_TRY(m.forward(m.h, v.b, v.out_idx, v.out_idx ? v.n_out : 0, v.f1, v.f2, v.s));
+        const size_t z = (size_t)t * z_stride + (size_t)v.sys0 * 3;
+        return adf_model_sde_step(m, v.b, v.pos, v.tags, v.fixed, v.f1, v.f2, nullptr, coefs_dev, num_steps,
+                                  z_tr_all ? z_tr_all + z : nullptr, z_rot_all ? z_rot_all + z : nullptr, early_stop_count,
+                                  v.state, nullptr, nullptr, v.s, per_system ? nullptr : v.hist + t);
+    };
+    int32_t st = ADF_OK;
+    int steps = 0;
+    for (int t = 0; t < num_steps && st == ADF_OK; ++t) {
+        st = one(mA, A, t);
+        if (st == ADF_OK) st = one(mB, B, t);
+        if (st != ADF_OK) break;
+        steps = t + 1;
+        if (early_stop_count > 0 && poll_every > 0 && (t % poll_every) == poll_every - 1 && t + 1 < num_steps) {
+            int32_t fa = 0, fb = 0;   // all systems frozen = both views all frozen
+            if (hipMemcpyAsync(&fa, A.state + 1, sizeof(int32_t), hipMemcpyDeviceToHost, A.s) != hipSuccess ||
+                hipMemcpyAsync(&fb, B.state + 1, sizeof(int32_t), hipMemcpyDeviceToHost, B.s) != hipSuccess ||
+                hipStreamSynchronize(A.s) != hipSuccess || hipStreamSynchronize(B.s) != hipSuccess) {
+                adf_set_error("sample_split: reading the frozen flags failed: %s", hipGetErrorString(hipGetLastError()));
+                st = ADF_EHIP;
+                break;
+            }
+            if (fa && fb) break;
+        }
+    }
+    // join - on an error too: the caller's stream must not run ahead of what B's stream still holds
+    if (hipEventRecord(join, B.s) != hipSuccess || hipStreamWaitEvent(A.s, join, 0) != hipSuccess) {
+        if (st == ADF_OK) { adf_set_error("sample_split: join failed: %s", hipGetErrorString(hipGetLastError())); st = ADF_EHIP; }
+        return st;
+    }
+    if (st != ADF_OK) return st;
+    hipLaunchKernelGGL(adf_split_combine_kernel, dim3(1), dim3(64), 0, A.s, A.state, B.state, state_init, A.hist, B.hist,
+                       steps, total_systems, per_system ? 1 : 0);
+    ADF_HIP_CHECK(hipGetLastError());
+    return ADF_OK;
+}
+
+// The cut of a split run (include/adsorbdiff_split.h): host arithmetic only.
+extern "C" int32_t adf_split_choose_cut(const int32_t* natoms, const int64_t* edges, int32_t num_systems, int32_t* cut) {
+    if (!natoms || !cut || num_systems < 0) { adf_set_error("split_choose_cut: bad argument"); return ADF_EINVAL; }
+    *cut = 0;
+    if (num_systems < 2) return ADF_OK;
+    long long total = 0, etotal = 0;
+    for (int b = 0; b < num_systems; ++b) {
+        if (natoms[b] < 0 || (edges && edges[b] < 0)) { adf_set_error("split_choose_cut: negative count at system %d", b); return ADF_EINVAL; }
+        total += natoms[b];
+        if (edges) etotal += edges[b];
+    }
+    long long best = -1, best_e = -1, a = 0, e = 0;
+    for (int c = 1; c < num_systems; ++c) {
+        a += natoms[c - 1];
+        if (edges) e += edges[c - 1];
+        const long long d = llabs(2 * a - total), de = edges ? llabs(2 * e - etotal) : 0;
+        if (best < 0 || d < best || (d == best && de < best_e)) { best = d; best_e = de; *cut = c; }
+    }
+    return ADF_OK;
 }
 
 // Hand-off rule of the reference's final-frame -> LMDB converter (scripts/create_lmdbs/pred_traj_to_lmdb.py:81-90): if the

@@ -57,6 +57,9 @@ Extensions (all optional, defaults reproduce the reference):
     ``placement_noise``, ``langevin_noise`` or ``noise_fn`` still wins for its part.  Two systems of one batch with the same
     ``(key, site_index)`` would be sampled identically: ``ValueError``.  Keys that fell back to the batch index: one
     warning, the run is not batch-invariant.  Independent of ``per_system``.
+  * ``denoising_pos_params["split_streams"]`` (default None = ``ADF_SAMPLE_SPLIT`` as the engine's handle read it: on
+    unless it is 0): the fused ``sde_rot`` loop of a PaiNN batch of two or more systems runs as two half-batches on two
+    streams (``adf_sample_split``, DESIGN.md 4 "Two half-batches, two streams"); bit-identical results.
   * ``denoising_pos_params["image_repeats"]`` (default None): a floor ``[ra, rb, rc]`` for the number of periodic images the
     graph search tries per lattice direction.  That number is the largest need over the batch (reference
     utils/utils.py:634-662), the one input a system's graph takes from its batch-mates: an adsorbate atom outside the cell
@@ -316,7 +319,7 @@ class Denoiser:
                         zt[t_idx].normal_()
                         zr[t_idx].normal_()
                 eng.sample(prep, pos, f1, f2, coefs_dev, T, state, zt, zr, early_stop_count=early, poll_every=poll_every,
-                           out_idx=out_idx, sink=sink, frame_every=1)
+                           out_idx=out_idx, sink=sink, frame_every=1, split_streams=params.get("split_streams"))
 
             def per_step(f1, state, out_idx):
                 f2 = torch.zeros(N, 3, dtype=torch.float32, device=dev)

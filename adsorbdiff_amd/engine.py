@@ -68,6 +68,7 @@ class PreparedBatch:
     reps: List[int]
     tags: Optional[torch.Tensor] = None   # [N] i32
     fixed: Optional[torch.Tensor] = None  # [N] i32
+    edge_counts: Optional[Sequence[int]] = None   # [B] host: edges per system of an earlier build (tie-break of split_cut)
 
     def desc(self, pos: torch.Tensor) -> _lib.BatchDesc:
         d = _lib.BatchDesc()
@@ -87,6 +88,22 @@ def image_repeats(batch, cutoff: float) -> List[int]:
     batch-mates: an adsorbate atom that has left the cell can gain a neighbour when a mate with a smaller cell raises the
     count.  Pinning it (``denoising_pos_params["image_repeats"]``) removes that."""
     return cell_repeats(batch.cell, float(cutoff), batch_pbc(batch))
+
+
+def split_cut(natoms: Sequence[int], edges: Optional[Sequence[int]] = None) -> int:
+    """Systems of view A when a batch with these atom counts is cut in two for ``adf_sample_split``
+    (``adf_split_choose_cut``: host arithmetic in the library, no device): the boundary where the two sides' atom counts
+    are closest, ties to the closest ``edges`` (per-system edge counts of an earlier build, optional), then the lowest.
+    0 for fewer than two systems: no split."""
+    n = (C.c_int32 * max(len(natoms), 1))(*[int(x) for x in natoms])
+    e = None
+    if edges is not None:
+        if len(edges) != len(natoms):
+            raise ValueError(f"split_cut: {len(natoms)} atom counts, {len(edges)} edge counts")
+        e = (C.c_int64 * max(len(edges), 1))(*[int(x) for x in edges])
+    cut = C.c_int32(-1)
+    _lib.check(_lib.load().adf_split_choose_cut(n, e, len(natoms), C.byref(cut)))
+    return int(cut.value)
 
 
 def _require_gpu(t: torch.Tensor, what: str) -> None:
@@ -262,9 +279,12 @@ class Engine:
 
     def sample(self, prep: PreparedBatch, pos, f1, f2, coefs_dev: torch.Tensor, num_steps: int, state,
                z_tr_all=None, z_rot_all=None, early_stop_count: int = 10, poll_every: int = 0,
-               out_idx: Optional[torch.Tensor] = None, sink=None, frame_every: int = 1) -> None:
+               out_idx: Optional[torch.Tensor] = None, sink=None, frame_every: int = 1,
+               split_streams: Optional[bool] = None) -> None:
         """The whole reverse loop in one library call (``adf_sample``; with ``sink`` — a ``trajectory.FrameSink`` —
-        ``adf_sample_traj``: a frame of the positions leaves the device after every ``frame_every``-th step)."""
+        ``adf_sample_traj``: a frame of the positions leaves the device after every ``frame_every``-th step).
+        ``split_streams``: two half-batches on two streams where the engine has that form (``PaiNNEngine.sample``);
+        ignored here."""
         self._loop("sample", prep, pos, [_ptr(prep.fixed), coefs_dev.data_ptr(), num_steps, _ptr(z_tr_all),
                                          _ptr(z_rot_all), early_stop_count, poll_every, state.data_ptr(), _ptr(out_idx),
                                          _numel(out_idx), f1.data_ptr(), f2.data_ptr()], sink, frame_every)
@@ -307,6 +327,10 @@ class Engine:
         if getattr(self, "handle", None) is not None and self.handle:
             with torch.cuda.device(self.device):
                 torch.cuda.synchronize(self.device)
+                twin = getattr(self, "_twin", None)
+                if twin is not None and twin:   # it reads this handle's weight images: it goes first
+                    self._c("destroy")(twin)
+                    self._twin = None
                 self._c("destroy")(self.handle)
             self.handle = None
 
@@ -339,6 +363,11 @@ class PaiNNEngine(Engine):
         with torch.cuda.device(self.device):
             _lib.check(self.lib.adf_painn_create(C.byref(hp), C.byref(self.handle)))
         self._last_graph_N = 0
+        self._twin = None                 # adf_painn_create_twin, made by the first split run
+        self._split_keepalive = None      # view B's re-based index arrays of the last split run
+        self._moving_gen = 0
+        self._split_moving = None         # view B's re-based moving lists of the promise in force: (key, mov_idx, mov_off)
+        self._split_default = bool(self.get_tune()["sample_split"])   # ADF_SAMPLE_SPLIT as the handle read it
         floor = getattr(model, "distance_floor", None)   # the S2EF PaiNN: 1e-6 (painn.py:334-335); default 1e-3
         if floor is not None:
             _lib.check(self.lib.adf_painn_set_distance_floor(self.handle, float(floor)))
@@ -390,6 +419,72 @@ class PaiNNEngine(Engine):
             eptrs = (C.c_void_p * 4)(*[t.data_ptr() for t in es])
             with torch.cuda.device(self.device):
                 _lib.check(self.lib.adf_painn_set_energy_head(self.handle, 4, eptrs, self._stream()))
+
+    # ------------------------------------------------------------------ two half-batches, two streams
+    def set_moving_atoms(self, prep, moving_mask) -> None:
+        self._moving_gen += 1
+        super().set_moving_atoms(prep, moving_mask)
+
+    def split_view(self, prep: PreparedBatch, out_idx: Optional[torch.Tensor]):
+        """View B of ``prep`` for ``adf_sample_split`` -> (``lib.SplitView``, the tensors it points into).  The cut comes
+        from ``adf_split_choose_cut`` on the host copy of the atom counts (ties go to ``prep.edge_counts`` where the caller
+        has set them); what counts atoms or systems from the start of the batch (atom offsets, system index, ``out_idx``,
+        the moving lists) is re-based to view B's first atom / system.  The cut and the batch's own arrays are kept on
+        ``prep``; the moving lists on the engine for as long as the static-atom promise they belong to, because the twin
+        reads them until the promise changes; ``out_idx``'s share is formed anew at every call."""
+        cached = getattr(prep, "_split_cut", None)
+        if cached is None:
+            off = prep.atom_offset.cpu()
+            cut = split_cut((off[1:] - off[:-1]).tolist(), prep.edge_counts)
+            na = int(off[cut])
+            cached = prep._split_cut = (cut, na, (prep.atom_offset[cut:] - na).contiguous(), (prep.batch[na:] - cut).contiguous())
+        cut, na, off_b, batch_b = cached
+        v = _lib.SplitView()
+        v.cut, v.atoms_a, v.atom_offset, v.batch = cut, na, off_b.data_ptr(), batch_b.data_ptr()
+        keep = [off_b, batch_b]
+        if out_idx is not None:
+            n_a = int((out_idx < na).sum().item())
+            keep.append((out_idx[n_a:] - na).contiguous())
+            v.n_out_a, v.n_out_b, v.out_idx = n_a, int(out_idx.numel()) - n_a, keep[-1].data_ptr()
+        if self._moving_keepalive is not None:
+            if self._split_moving is None or self._split_moving[0] != (self._moving_gen, cut, na):
+                _, idx, moff = self._moving_keepalive
+                m0 = int(moff[cut].item())
+                self._split_moving = ((self._moving_gen, cut, na), (idx[m0:] - na).contiguous(), (moff[cut:] - m0).contiguous())
+            v.mov_idx, v.mov_off = self._split_moving[1].data_ptr(), self._split_moving[2].data_ptr()
+        return v, keep
+
+    def split_stats(self):
+        """(runs of ``sample`` that went through the split loop, runs that ``adf_sample_split`` gave to the one-stream loop)."""
+        a, b = C.c_int64(0), C.c_int64(0)
+        _lib.check(self.lib.adf_split_stats(self.handle, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
+    def sample(self, prep: PreparedBatch, pos, f1, f2, coefs_dev: torch.Tensor, num_steps: int, state,
+               z_tr_all=None, z_rot_all=None, early_stop_count: int = 10, poll_every: int = 0,
+               out_idx: Optional[torch.Tensor] = None, sink=None, frame_every: int = 1,
+               split_streams: Optional[bool] = None) -> None:
+        """``Engine.sample``; with ``split_streams`` (default: ``ADF_SAMPLE_SPLIT`` as the handle read it) the two sides of a
+        cut at a system boundary run on two streams (``adf_sample_split``, include/adsorbdiff_split.h) - same bits.  A
+        trajectory sink and a batch of one system take the one-stream loop here; the library's own fallbacks (exact f32, the
+        coupled early stop) are counted by ``split_stats``."""
+        want = self._split_default if split_streams is None else bool(split_streams)
+        if not want or sink is not None or prep.num_systems < 2:
+            return super().sample(prep, pos, f1, f2, coefs_dev, num_steps, state, z_tr_all, z_rot_all, early_stop_count,
+                                  poll_every, out_idx, sink, frame_every)
+        with torch.cuda.device(self.device):
+            if self._twin is None:
+                twin = C.c_void_p()
+                _lib.check(self.lib.adf_painn_create_twin(self.handle, C.byref(twin)))
+                self._twin = twin
+            _lib.check(self.lib.adf_painn_set_split(self.handle, 1))
+            view, keep = self.split_view(prep, out_idx)
+            self._split_keepalive = keep
+            desc = prep.desc(pos)
+            _lib.check(self.lib.adf_sample_split(
+                self.handle, self._twin, C.byref(desc), C.byref(view), pos.data_ptr(), prep.tags.data_ptr(), _ptr(prep.fixed),
+                coefs_dev.data_ptr(), num_steps, _ptr(z_tr_all), _ptr(z_rot_all), early_stop_count, poll_every,
+                state.data_ptr(), _ptr(out_idx), _numel(out_idx), f1.data_ptr(), f2.data_ptr(), self._stream()))
 
     # ------------------------------------------------------------------ calls
     def forward_prepared(self, prep: PreparedBatch, pos: torch.Tensor, f1: torch.Tensor, f2: Optional[torch.Tensor],

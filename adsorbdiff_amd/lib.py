@@ -55,7 +55,14 @@ class Tune(C.Structure):
     """adf_tune: the kernel-selection switches a handle holds (include/adsorbdiff_hip.h)."""
     _fields_ = [(name, C.c_int32) for name in (
         "gemm_stream", "head_gate_fused", "lift_emit", "graph_sys_csr", "train_gemm16", "wgrad_f32",
-        "eqv2_gemm_tile256", "eqv2_rotin_generic", "eqv2_rotout_generic")]
+        "eqv2_gemm_tile256", "eqv2_rotin_generic", "eqv2_rotout_generic", "sample_split")]
+
+
+class SplitView(C.Structure):
+    """adf_split_view: view B of a split sampling run (include/adsorbdiff_split.h)."""
+    _fields_ = [("cut", C.c_int32), ("atoms_a", C.c_int32), ("n_out_a", C.c_int32), ("n_out_b", C.c_int32),
+                ("atom_offset", C.c_void_p), ("batch", C.c_void_p), ("out_idx", C.c_void_p), ("mov_idx", C.c_void_p),
+                ("mov_off", C.c_void_p)]
 
 
 class BatchDesc(C.Structure):
@@ -146,6 +153,10 @@ def parse_header(text: str) -> dict:
 
 SIGNATURES = parse_header(HEADER.read_text())
 EXPORTS = tuple(SIGNATURES)
+# the companion header of the split sampling loop: read behind the main header's text (it uses its types), bound the same way
+SPLIT_HEADER = HEADER.with_name("adsorbdiff_split.h")
+SPLIT_SIGNATURES = {name: sig for name, sig in parse_header(HEADER.read_text() + "\n" + SPLIT_HEADER.read_text()).items()
+                    if name not in SIGNATURES}
 
 _LIB = None
 
@@ -171,7 +182,7 @@ def load():
             "(the HIP path has no CPU fallback)"
         )
     lib = C.CDLL(str(path))
-    for name, (restype, argtypes) in SIGNATURES.items():
+    for name, (restype, argtypes) in {**SIGNATURES, **SPLIT_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     _LIB = lib

@@ -160,6 +160,9 @@ typedef struct adf_tune {
     int32_t eqv2_gemm_tile256;   /* ADF_EQV2_GEMM_TILE: 128 = 0, the 128-row tile for every shape, else 1 (256 rows from 8192 on) */
     int32_t eqv2_rotin_generic;  /* ADF_EQV2_ROTIN_GENERIC set (any value): 1, the run-time-mmax rotate-in kernel, else 0 */
     int32_t eqv2_rotout_generic; /* ADF_EQV2_ROTOUT_GENERIC set (any value): 1, the run-time-mmax rotate-out kernel, else 0 */
+    /* Two half-batches on two streams (include/adsorbdiff_split.h; same bits as the one-stream loop) */
+    int32_t sample_split;     /* ADF_SAMPLE_SPLIT: 0 = adf_sample_split runs the one-stream loop, else 1 (default): its two views
+                               * run on two streams (adf_painn_set_split overrides) */
 } adf_tune;
 /* Test hook: the selection the handle holds (the variants give the same bits, so outputs cannot show it). */
 int32_t adf_painn_get_tune(adf_painn_t h, adf_tune* out);
