@@ -1014,6 +1014,57 @@ extern "C" int32_t adf_painn_forward_subset(adf_painn_t h, const adf_batch* b, c
     return forward_impl(h, b, out_idx, n_out, f1, f2, stream);
 }
 
+// ---- the forward that the scale-factor fit observes (scale_fit.hip; modules/scaling/fit.py:204-213).  The same launches as
+// forward_impl's all-rows branch up to layer `upto`, with the column variance of x taken after every update layer.
+extern "C" int32_t adf_painn_forward_observe(adf_painn_t h, const adf_batch* b, int32_t upto, double* layer_var, float* f1,
+                                             float* f2, void* stream) {
+    ADF_TRY(check_batch(h, b));
+    if (!h->weights_set) { adf_set_error("weights not set"); return ADF_EINVAL; }
+    const int L = h->hp.num_layers, H = h->hp.hidden_channels, N = b->num_atoms;
+    if (!layer_var || !b->atomic_numbers) { adf_set_error("forward_observe: null argument"); return ADF_EINVAL; }
+    if (upto < 0 || upto >= L) { adf_set_error("forward_observe: upto=%d outside [0, %d)", upto, L); return ADF_EINVAL; }
+    if (N < 2) { adf_set_error("forward_observe: the variance over the atoms needs at least 2 of them, got %d", N); return ADF_EINVAL; }
+    const int heads = f1 ? h->hp.num_heads : 0;
+    if (f2 && !f1) { adf_set_error("forward_observe: f2 without f1"); return ADF_EINVAL; }
+    if (f1 && upto < L - 1) { adf_set_error("forward_observe: the heads need every layer (upto=%d of %d): pass f1 = f2 = NULL", upto, L); return ADF_EINVAL; }
+    if (f1 && heads == 0) { adf_set_error("the model has no force head"); return ADF_EINVAL; }
+    if (heads == 2 && !f2) { adf_set_error("forward_observe: a two-head handle needs f2 with f1"); return ADF_EINVAL; }
+    hipStream_t s = (hipStream_t)stream;
+    leave_split(h);
+    // a static-atom promise ends here: this is no forward of its sequence
+    if (h->moving) { h->moving = nullptr; h->mov_idx = nullptr; h->mov_off = nullptr; ++h->moving_serial; }
+    h->cache_valid = false; h->rec0_valid = false; h->inc_valid = false;
+    h->x_last = nullptr;
+    ADF_TRY(ensure_capacity(h, N, b->num_systems));
+    const int64_t need = adf_op_column_variance_scratch(N, H);
+    if (need > h->obs_bytes) {
+        ADF_HIP_CHECK(hipDeviceSynchronize());   // enqueued work may still use the buffer
+        h->obs_bytes = 0;
+        ADF_TRY(h->m_obs.alloc(&h->obs_scratch, (size_t)need));
+        h->obs_bytes = need;
+    }
+    adf_prof_begin(h, ADF_PROF_GRAPH, s);
+    ADF_TRY(adf_graph_build_impl(h, b, s));
+    adf_prof_end(h, s);
+    ADF_TRY(zero_pad_rows(h, N, s));
+    ADF_TRY(adf_nodewise_embed(h, b->atomic_numbers, N, h->x, s));
+    float* vin = h->vecA;
+    float* vout = h->vecB;
+    for (int l = 0; l <= upto; ++l) {
+        ADF_TRY(message_layer(h, l, N, h->x, vin, h->x, vout, l == 0, s));
+        ADF_TRY(update_layer(h, l, N, h->x, vout, s));
+        ADF_TRY(adf_op_column_variance(h->x, N, H, layer_var + l, h->obs_scratch, stream));
+        float* t = vin; vin = vout; vout = t;
+    }
+    if (heads) {
+        adf_prof_begin(h, ADF_PROF_HEADS, s);
+        ADF_TRY(adf_head_forward(h, 0, N, h->x, vin, f1, s));
+        if (heads == 2) ADF_TRY(adf_head_forward(h, 1, N, h->x, vin, f2, s));
+        adf_prof_end(h, s);
+    }
+    return ADF_OK;
+}
+
 // ---- S2EF energy head (painn.py:412-414): per_atom = out_energy.2(ScaledSiLU(out_energy.0(x))), energy = per-system sum
 extern "C" int32_t adf_painn_set_energy_head(adf_painn_t h, int32_t n_weights, const void* const* w, void* stream) {
     if (!h || !w) { adf_set_error("null argument"); return ADF_EINVAL; }

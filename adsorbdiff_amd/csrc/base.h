@@ -9,6 +9,7 @@
 
 #include "../../include/adsorbdiff_hip.h"
 #include "../../include/adsorbdiff_split.h"
+#include "../../include/adsorbdiff_scale_fit.h"
 
 void adf_set_error(const char* fmt, ...);
 

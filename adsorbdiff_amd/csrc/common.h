@@ -227,6 +227,10 @@ struct adf_painn {
     adf_pool m_inc;    // incremental layers: incX / incV / incR, inc_*
     adf_pool m_sub;    // sub_x / sub_vec / sub_f
     adf_pool m_rec0;   // rec0
+    // ---- adf_painn_forward_observe: scratch of the column-variance operator (scale_fit.hip), grown on demand
+    void* obs_scratch = nullptr;
+    int64_t obs_bytes = 0;
+    adf_pool m_obs;    // obs_scratch
 };
 
 enum { ADF_PROF_GRAPH = 0, ADF_PROF_MESSAGE = 1, ADF_PROF_NODE = 2, ADF_PROF_HEADS = 3, ADF_PROF_STEPPER = 4 };

@@ -518,6 +518,39 @@ class PaiNNEngine(Engine):
             self.check_flags()
         return f1, f2
 
+    def forward_observe(self, data, upto: Optional[int] = None, with_heads: bool = False):
+        """The full forward that also observes what a ``ScaleFactor`` fit reads (``adf_painn_forward_observe``): ->
+        ``layer_var`` float64 ``[num_layers]`` on the device, entry l = ``torch.mean(torch.var(x, dim=0))`` of the node
+        features after update layer l's scale multiply; entries after ``upto`` (default: the last layer) are NaN, their
+        layers are not run.  ``with_heads`` (``upto`` the last layer only): -> ``(layer_var, f1, f2)`` with the heads'
+        outputs as ``forward`` gives them.  Ends a static-atom promise.  Same error protocol as ``forward``."""
+        L = int(self.model.num_layers)
+        upto = L - 1 if upto is None else int(upto)
+        prep = self.prepare(data)
+        pos = data.pos.to(torch.float32).contiguous()
+        layer_var = torch.full((L,), float("nan"), dtype=torch.float64, device=self.device)
+        f1 = f2 = None
+        if with_heads:
+            f1 = torch.empty(prep.num_atoms, 3, dtype=torch.float32, device=self.device)
+            f2 = torch.empty_like(f1) if self.num_heads == 2 else None
+        self._moving_keepalive = None   # the library forgets the promise: so does its keeper
+        self._moving_gen += 1
+        desc = prep.desc(pos)
+
+        def run():
+            with torch.cuda.device(self.device):
+                _lib.check(self.lib.adf_painn_forward_observe(self.handle, C.byref(desc), upto, layer_var.data_ptr(),
+                                                              _ptr(f1), _ptr(f2), self._stream()))
+        run()
+        try:
+            self.check_flags()
+        except _lib.NumericRangeError:
+            if not self.use_exact_f32():
+                raise
+            run()
+            self.check_flags()
+        return (layer_var, f1, f2) if with_heads else layer_var
+
     def forward_energy_prepared(self, prep: PreparedBatch, pos: torch.Tensor, energy: torch.Tensor,
                                 forces: Optional[torch.Tensor]) -> None:
         """Enqueue one S2EF forward (``adf_painn_forward_energy``): energy [B], forces [N,3] (None without a force

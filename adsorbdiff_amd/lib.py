@@ -157,6 +157,10 @@ EXPORTS = tuple(SIGNATURES)
 SPLIT_HEADER = HEADER.with_name("adsorbdiff_split.h")
 SPLIT_SIGNATURES = {name: sig for name, sig in parse_header(HEADER.read_text() + "\n" + SPLIT_HEADER.read_text()).items()
                     if name not in SIGNATURES}
+# ... and of the scale-factor fit (adf_op_column_variance, adf_painn_forward_observe)
+SCALE_FIT_HEADER = HEADER.with_name("adsorbdiff_scale_fit.h")
+SCALE_FIT_SIGNATURES = {name: sig for name, sig in parse_header(HEADER.read_text() + "\n" + SCALE_FIT_HEADER.read_text()).items()
+                        if name not in SIGNATURES}
 
 _LIB = None
 
@@ -182,7 +186,7 @@ def load():
             "(the HIP path has no CPU fallback)"
         )
     lib = C.CDLL(str(path))
-    for name, (restype, argtypes) in {**SIGNATURES, **SPLIT_SIGNATURES}.items():
+    for name, (restype, argtypes) in {**SIGNATURES, **SPLIT_SIGNATURES, **SCALE_FIT_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     _LIB = lib

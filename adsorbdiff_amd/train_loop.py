@@ -114,6 +114,21 @@ class TrainLoopMixin:
             for group, lr in zip(self.optimizer.param_groups, last):
                 group["lr"] = lr
 
+    # ---------------------------------------------------------------- scale factors
+    def fit_scale_factors(self, batches: Optional[Iterable] = None, num_batches: int = 16, mode: str = "all") -> dict:
+        """Fit the model's ``ScaleFactor``s as the reference's ``modules/scaling/fit.py`` does (``scaling.fit_scale_factors``):
+        the first ``num_batches`` of ``batches`` (default ``val_loader``) as they are - not noised -, the current weights
+        (no EMA swap), one factor after the other on the device.  The factors are parameters, so ``save()`` writes them;
+        afterwards ``validate`` / ``predict`` no longer warn about unfitted factors.  -> ``{name: {"variance_in",
+        "variance_out", "n_samples", "ratio", "value"}}``."""
+        from .scaling import fit_scale_factors
+
+        if batches is None:
+            batches = getattr(self, "val_loader", None)
+            if batches is None:
+                raise ValueError("fit_scale_factors: no batches given and the trainer has no val_loader")
+        return fit_scale_factors(self._unwrapped_model, batches, num_batches=num_batches, mode=mode, device=self.device)
+
     # ---------------------------------------------------------------- checkpoints
     def checkpoint_dict(self, metrics=None, training_state: bool = True) -> dict:
         """What ``save`` writes.  ``training_state=True``: the reference's twelve keys plus ``noise_step`` (the counter of
