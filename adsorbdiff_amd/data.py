@@ -14,7 +14,8 @@ from typing import Iterable, List
 import torch
 
 _TENSOR_NODE_KEYS = ("pos", "atomic_numbers", "tags", "fixed", "force", "forces")
-_TENSOR_GRAPH_KEYS = ("cell", "natoms", "y", "energy", "pbc", "noise_key", "site_index", "sample_steps", "sample_stopped")
+_TENSOR_GRAPH_KEYS = ("cell", "natoms", "y", "energy", "pbc", "noise_key", "site_index", "sample_steps", "sample_stopped",
+                      "millers", "shift", "top", "bulk_index")    # the last four: per slab, slabs.compute_slabs
 
 
 class Data:
@@ -73,7 +74,7 @@ class Batch(Data):
                     v = getattr(d, k)
                     if k == "cell":
                         v = v.reshape(-1, 3, 3)
-                    elif k == "pbc":
+                    elif k in ("pbc", "millers"):
                         v = torch.atleast_2d(v)
                     else:
                         v = v.reshape(-1)

@@ -161,6 +161,10 @@ SPLIT_SIGNATURES = {name: sig for name, sig in parse_header(HEADER.read_text() +
 SCALE_FIT_HEADER = HEADER.with_name("adsorbdiff_scale_fit.h")
 SCALE_FIT_SIGNATURES = {name: sig for name, sig in parse_header(HEADER.read_text() + "\n" + SCALE_FIT_HEADER.read_text()).items()
                         if name not in SIGNATURES}
+# ... and of slab cutting (adf_distinct_millers_*, adf_slab_cut_*)
+SLABS_HEADER = HEADER.with_name("adsorbdiff_slabs.h")
+SLABS_SIGNATURES = {name: sig for name, sig in parse_header(HEADER.read_text() + "\n" + SLABS_HEADER.read_text()).items()
+                    if name not in SIGNATURES}
 
 _LIB = None
 
@@ -186,7 +190,7 @@ def load():
             "(the HIP path has no CPU fallback)"
         )
     lib = C.CDLL(str(path))
-    for name, (restype, argtypes) in {**SIGNATURES, **SPLIT_SIGNATURES, **SCALE_FIT_SIGNATURES}.items():
+    for name, (restype, argtypes) in {**SIGNATURES, **SPLIT_SIGNATURES, **SCALE_FIT_SIGNATURES, **SLABS_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     _LIB = lib

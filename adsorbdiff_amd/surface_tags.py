@@ -13,7 +13,7 @@ against it: parity with pymatgen is unpinned; the geometry is pinned to qhull (`
 tests/golden/voronoi_cn.npz).  Two deliberate deviations from the reference: one wrapped fractional height serves both the
 height and the centre-of-mass test, and the coordination is compared as ``cn < bulk minimum - cn_tol`` instead of
 ``round(cn, 5) < bulk minimum`` (with float32 positions a fully coordinated fcc atom comes out at 11.999995).
-Slab cutting from a Miller index (``Slab``, ``Bulk``, ``compute_slabs``) is pymatgen's ``SlabGenerator`` and stays out.
+Slab cutting from a Miller index (``Slab``, ``Bulk``, ``compute_slabs``) is adsorbdiff_amd/slabs.py.
 """
 from __future__ import annotations
 
