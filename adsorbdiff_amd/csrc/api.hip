@@ -20,28 +20,6 @@ void adf_set_error(const char* fmt, ...) {
 extern "C" const char* adf_last_error(void) { return g_err; }
 extern "C" const char* adf_version(void) { return "adsorbdiff_hip 0.5.0 (gfx950)"; }
 
-// ---- the kernel-selection switches (adf_tune): the one place that reads them
-adf_tune adf_tune_from_env() {
-    auto off_is_0 = [](const char* name) { const char* e = getenv(name); return (e && atoi(e) == 0) ? 0 : 1; };
-    auto is_f32 = [](const char* name) { const char* e = getenv(name); return e && strcmp(e, "f32") == 0; };
-    adf_tune t = {};
-    t.gemm_stream = off_is_0("ADF_GEMM_STREAM");
-    t.head_gate_fused = off_is_0("ADF_HEAD_GATE_FUSED");
-    t.lift_emit = off_is_0("ADF_LIFT_EMIT");
-    t.graph_sys_csr = off_is_0("ADF_GRAPH_SYS_CSR");
-    t.train_gemm16 = is_f32("ADF_TRAIN_GEMM") ? 0 : 1;
-    t.wgrad_f32 = is_f32("ADF_WGRAD") ? 1 : 0;
-    const char* gt = getenv("ADF_EQV2_GEMM_TILE");
-    t.eqv2_gemm_tile256 = (gt && atoi(gt) == 128) ? 0 : 1;
-    t.eqv2_rotin_generic = getenv("ADF_EQV2_ROTIN_GENERIC") != nullptr;
-    t.eqv2_rotout_generic = getenv("ADF_EQV2_ROTOUT_GENERIC") != nullptr;
-    t.sample_split = off_is_0("ADF_SAMPLE_SPLIT");
-    return t;
-}
-const adf_tune& adf_tune_process() {
-    static const adf_tune t = adf_tune_from_env();   // read once per process; the initialisation is thread-safe
-    return t;
-}
 int adf_current_num_cus() {
     int dev = 0, n = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
@@ -105,12 +83,8 @@ extern "C" int32_t adf_painn_create(const adf_painn_hparams* hp, adf_painn_t* ou
     }
     h->num_cus = prop.multiProcessorCount;
     h->dist_floor = 1.0e-3f;
-    {   // incremental layers: on unless ADF_INCREMENTAL=0 (adf_painn_set_incremental overrides)
-        const char* e = getenv("ADF_INCREMENTAL");
-        h->inc_on = !(e && e[0] == '0');
-        const char* e2 = getenv("ADF_INC_SYNC");
-        h->inc_sync = e2 && e2[0] == '1';
-    }
+    h->sw = adf_switches_from_env();
+    h->inc_on = h->sw.incremental != 0;   // incremental layers: on unless ADF_INCREMENTAL=0 (adf_painn_set_incremental overrides)
     const int H = hp->hidden_channels, R = hp->num_rbf, L = hp->num_layers;
     adf_pool& m = h->m_life;
     int32_t st = m.alloc(&h->rbf_pack, (size_t)L * (H / ADF_SLICE_CH) * R * 192);
@@ -131,20 +105,14 @@ extern "C" int32_t adf_painn_create(const adf_painn_hparams* hp, adf_painn_t* ou
         if (st == ADF_OK) st = m.alloc(&h->w16_bias_perm, (size_t)L * 2 * 3 * H);
         if (st == ADF_OK) st = m.alloc(&h->w16_scratch, 1);
         if (st == ADF_OK) st = m.alloc(&h->wfrag_arena, h->w16_bytes);
-        const char* e = getenv("ADF_GEMM");
-        h->gemm_f32 = e && strcmp(e, "f32") == 0;
-        const char* el = getenv("ADF_LIFT");
-        h->lift_on = !(el && strcmp(el, "0") == 0);
-        const char* e2 = getenv("ADF_MSG");
-        h->msg_f32 = e2 ? strcmp(e2, "f32") == 0 : h->gemm_f32;
+        h->gemm_f32 = h->sw.gemm_f32 != 0;
+        h->lift_on = h->sw.lift != 0;
+        h->msg_f32 = h->sw.msg_f32 != 0;
         // The f16 message kernel stages its rbf_proj image in 16-byte pieces of 8 basis functions per column: a basis that
         // is no multiple of 8 runs the exact-f32 message kernel (even R, contracted two deep) whatever the arithmetic of
         // the node products.  message_bwd.hip / message_geo.hip carry the same predicate.
         h->msg_f32_only = hp->num_rbf % 8 != 0;
         h->msg_f32 = h->msg_f32 || h->msg_f32_only;
-        const char* er = getenv("ADF_ROW_MAXIMA");   // row maxima from the producers (common.h: adf_painn::rmx)
-        h->rmx = (er && atoi(er) == 0) ? 0 : 1;
-        h->tune = adf_tune_from_env();
     }
     if (st == ADF_OK) st = m.alloc(&h->kcount, 8);
     if (st == ADF_OK && hipMemset(h->kcount, 0, 8 * sizeof(unsigned long long)) != hipSuccess) st = ADF_EHIP;
@@ -189,9 +157,9 @@ extern "C" int32_t adf_painn_destroy(adf_painn_t h) {
     return ADF_OK;
 }
 
-// ---- the twin of a handle (include/adsorbdiff_split.h): a second set of everything a forward writes, around the parent's
-// weight images.  The images are fields of the parent that its pools own: the twin holds plain copies of the pointers,
-// outside its own pools, so it never frees them.  bound = false: forget them (the parent is re-binding).
+// ---- the twin of a handle (adsorbdiff_hip.h, "Two half-batches, two streams"): a second set of everything a forward
+// writes, around the parent's weight images.  The images are fields of the parent that its pools own: the twin holds plain
+// copies of the pointers, outside its own pools, so it never frees them.  bound = false: forget them (the parent is re-binding).
 static void borrow_weights(adf_painn* t, const adf_painn* p, bool bound) {
     t->emb = p->emb; t->rbf_offset = p->rbf_offset;
     memcpy(t->layer, p->layer, sizeof(t->layer));
@@ -211,7 +179,7 @@ static void follow_settings(adf_painn* t, const adf_painn* p) {
         t->cache_valid = false; t->rec0_valid = false; t->inc_valid = false;
     }
     t->gemm_f32 = p->gemm_f32; t->msg_f32 = p->msg_f32; t->msg_f32_only = p->msg_f32_only; t->dist_floor = p->dist_floor;
-    t->lift_on = p->lift_on; t->tune = p->tune; t->inc_sync = p->inc_sync;
+    t->lift_on = p->lift_on; t->sw = p->sw;
 }
 
 extern "C" int32_t adf_painn_create_twin(adf_painn_t parent, adf_painn_t* out) {
@@ -226,7 +194,7 @@ extern "C" int32_t adf_painn_create_twin(adf_painn_t parent, adf_painn_t* out) {
     adf_painn* t = new (std::nothrow) adf_painn();
     if (!t) { adf_set_error("host allocation failed"); return ADF_EOOM; }
     t->hp = parent->hp; t->device = parent->device; t->num_cus = parent->num_cus;
-    t->rmx = parent->rmx; t->inc_on = parent->inc_on;
+    t->inc_on = parent->inc_on;
     follow_settings(t, parent);
     // its own: flags, the k-step counter, view B's state and the stream pair's objects.  No weight image is allocated.
     int32_t st = t->m_life.alloc(&t->flags, ADF_NFLAGS);
@@ -254,7 +222,7 @@ extern "C" int32_t adf_painn_create_twin(adf_painn_t parent, adf_painn_t* out) {
 
 extern "C" int32_t adf_painn_set_split(adf_painn_t h, int32_t on) {
     if (!h) { adf_set_error("null handle"); return ADF_EINVAL; }
-    h->tune.sample_split = on != 0;
+    h->sw.tune.sample_split = on != 0;
     return ADF_OK;
 }
 
@@ -416,11 +384,11 @@ static int32_t ensure_capacity(adf_painn* h, int64_t N, int64_t B) {
     ALLOC(mag_b, capN);
     ALLOC(mag_v3, capN * 3);
     const int64_t ps = (capN + 31) / 32 * 32, ns = H / ADF_SLICE_CH;
-    if (h->rmx) ALLOC(rmx_part, (4 * ns + H / 32 + 4) * ps);
+    if (h->sw.row_maxima) ALLOC(rmx_part, (4 * ns + H / 32 + 4) * ps);
 #undef ALLOC
     h->lift.cap = st == ADF_OK ? capN * 3 : 0;
     if (st != ADF_OK) { free_workspaces(h); return st; }
-    if (h->rmx) {   // xpart and catpart side by side: the [x | |v2|] rows' maxima are one run of parts
+    if (h->sw.row_maxima) {   // xpart and catpart side by side: the [x | |v2|] rows' maxima are one run of parts
         h->part_stride = ps;
         h->xpart = h->rmx_part; h->catpart = h->xpart + ns * ps; h->vpart = h->catpart + (H / 32) * ps;
         h->dbg_mag = h->vpart + 3 * ns * ps;
@@ -558,7 +526,7 @@ static int32_t make_records(adf_painn* h, int l, int n, const float* x, const fl
     if (n <= 0) return ADF_OK;
     adf_prof_begin(h, ADF_PROF_NODE, s);
     const bool lift = h->lift_on && !h->gemm_f32;
-    const bool em = lift && h->tune.lift_emit;
+    const bool em = lift && h->sw.tune.lift_emit;
     // row magnitudes travel with the rows: LayerNorm -> x_proj.0 -> (its epilogue) -> x_proj.2
     ADF_TRY(adf_nodewise_layernorm(x, w.ln_w, w.ln_b, h->y, n, H, s, em ? h->mag_a : nullptr, h->rows_dev));
     ADF_TRY(adf_linear(h, h->y, H, w.xp0_w, &w.xp0_16, w.xp0_b, h->cat, H, n, H, H, 1, s, em ? h->mag_a : nullptr,
@@ -573,7 +541,7 @@ static int32_t make_records(adf_painn* h, int l, int n, const float* x, const fl
         ep.row_map = row_map;
         ep.rmag = em ? h->mag_b : nullptr;
         ep.m_dev = h->rows_dev;
-        ADF_TRY(adf_launch_gemm16_fused(h->cat, H, &w.xp2_16, n, H, H, 1, &ep, s, h->tune, lift ? &h->lift : nullptr));
+        ADF_TRY(adf_launch_gemm16_fused(h->cat, H, &w.xp2_16, n, H, H, 1, &ep, s, h->sw.tune, lift ? &h->lift : nullptr));
     }
     adf_prof_end(h, s);
     return ADF_OK;
@@ -588,7 +556,7 @@ static int32_t message_layer(adf_painn* h, int l, int N, const float* x, const f
     adf_prof_begin(h, ADF_PROF_MESSAGE, s);
     // the f16x3 kernel also leaves the partial maxima of its output rows for update_layer's products (MsgParams::xpart)
     const int items = tlist ? n_targets : N;
-    const bool emit = h->rmx && h->lift_on && !h->gemm_f32 && !h->msg_f32 && items > 0 && items <= h->part_stride;
+    const bool emit = h->sw.row_maxima && h->lift_on && !h->gemm_f32 && !h->msg_f32 && items > 0 && items <= h->part_stride;
     h->part_x = h->part_vec = nullptr;
     const int32_t st = adf_message_impl(h, l, N, x, h->xh, vec, x_out, vec_out, vec_is_zero, s, tlist, n_targets, rec,
                                         tlist ? h->rows_dev : nullptr, emit ? h->xpart : nullptr, h->vpart, h->part_stride);
@@ -607,7 +575,7 @@ static int32_t update_layer(adf_painn* h, int l, int N, float* x, float* vec, hi
     const adf_layer_weights& w = h->layer[l];
     adf_prof_begin(h, ADF_PROF_NODE, s);
     // are the partial maxima of exactly these rows current?  They are consumed here: the rows are rewritten in place below.
-    const bool parts = from_message && h->rmx && h->lift_on && !h->gemm_f32 && N > 0 && h->part_x == x && h->part_vec == vec &&
+    const bool parts = from_message && h->sw.row_maxima && h->lift_on && !h->gemm_f32 && N > 0 && h->part_x == x && h->part_vec == vec &&
                        h->part_n == N && h->part_dev == h->rows_dev;
     h->part_x = h->part_vec = nullptr;
     if (h->gemm_f32) {
@@ -637,10 +605,10 @@ static int32_t update_layer(adf_painn* h, int l, int N, float* x, float* vec, hi
             if (h->dbg_capture) ADF_HIP_CHECK(hipMemcpyAsync(h->dbg_mag, h->lift.buf, sizeof(float) * 3 * (size_t)N, hipMemcpyDeviceToDevice, s));
         }
         // vec_proj stores its |v2| slots only where somebody reads them: the combine below, or the test hook (dbg_capture)
-        if (parts || (h->dbg_capture && h->rmx && lf && N <= h->part_stride)) {
+        if (parts || (h->dbg_capture && h->sw.row_maxima && lf && N <= h->part_stride)) {
             ep.catpart = h->catpart; ep.part_stride = h->part_stride; h->dbg_cat_rows = N;
         }
-        ADF_TRY(adf_launch_gemm16_fused(vec, H, &w.vp_16, N, H, H, 3, &ep, s, h->tune, lf));
+        ADF_TRY(adf_launch_gemm16_fused(vec, H, &w.vp_16, N, H, H, 3, &ep, s, h->sw.tune, lf));
         if (parts) {   // [x | |v2|]: xpart and catpart lie side by side
             ADF_TRY(adf_launch_rowmax_combine(h->xpart, h->part_stride, H / ADF_SLICE_CH + H / 32, N, h->lift.buf, s, h->rows_dev, 1));
             if (h->dbg_capture) {
@@ -652,7 +620,7 @@ static int32_t update_layer(adf_painn* h, int l, int N, float* x, float* vec, hi
         e0.A2 = h->cat; e0.K1 = H; e0.m_dev = h->rows_dev;
         e0.rmag = parts ? h->lift.buf : nullptr;
         e0.out_mag = h->lift_on ? reinterpret_cast<unsigned int*>(h->mag_b) : nullptr;
-        ADF_TRY(adf_launch_gemm16(x, H, &w.xv0_16, w.xv0_b, h->y, H, N, H, 2 * H, 1, &e0, s, lf, h->tune, h->num_cus));
+        ADF_TRY(adf_launch_gemm16(x, H, &w.xv0_16, w.xv0_b, h->y, H, N, H, 2 * H, 1, &e0, s, lf, h->sw.tune, h->num_cus));
     }
     int32_t st;
     if (h->gemm_f32) {
@@ -663,7 +631,7 @@ static int32_t update_layer(adf_painn* h, int l, int N, float* x, float* vec, hi
         ep.x = x; ep.vec = vec; ep.dot = h->dot; ep.vv = h->vv; ep.scale = h->scale[l]; ep.H = H;
         ep.rmag = h->lift_on ? h->mag_b : nullptr;
         ep.m_dev = h->rows_dev;
-        st = adf_launch_gemm16_fused(h->y, H, &w.xv2_16, N, H, H, 2, &ep, s, h->tune);
+        st = adf_launch_gemm16_fused(h->y, H, &w.xv2_16, N, H, H, 2, &ep, s, h->sw.tune);
     }
     adf_prof_end(h, s);
     return st;
@@ -693,7 +661,7 @@ extern "C" int32_t adf_painn_update_layer(adf_painn_t h, int32_t layer, int32_t 
 // Test hook: the kernel selection the handle holds (read from the environment by adf_painn_create)
 extern "C" int32_t adf_painn_get_tune(adf_painn_t h, adf_tune* out) {
     if (!h || !out) { adf_set_error("get_tune: null handle or output"); return ADF_EINVAL; }
-    *out = h->tune;
+    *out = h->sw.tune;
     return ADF_OK;
 }
 
@@ -860,7 +828,7 @@ static int32_t forward_incremental(adf_painn* h, int N, const int32_t* Z, const 
     h->inc_ev_live[slot] = true;
     h->inc_pend_N[slot] = N;
     ADF_TRY(inc_harvest(h, slot ^ 1, false));   // the previous forward's counts, if they have arrived
-    if (h->inc_sync) ADF_TRY(inc_harvest(h, slot, true, true));
+    if (h->sw.inc_sync) ADF_TRY(inc_harvest(h, slot, true, true));
     adf_prof_end(h, s);
     if (first) ADF_TRY(make_records(h, 0, N, h->incX[0], nullptr, true, h->incR[0], nullptr, s));
     for (int l = 0; l < L; ++l) {
@@ -872,7 +840,7 @@ static int32_t forward_incremental(adf_painn* h, int N, const int32_t* Z, const 
         const int n_seen = h->inc_seen_valid ? h->inc_seen[l] : N;
         const bool whole = first || !h->inc_seen_valid || h->inc_pend_Nseen != N || (long long)n_seen * 10 >= (long long)N * 9;
         h->inc_pend_whole[slot][l] = whole ? 1 : 0;
-        if (h->inc_sync && !whole && n_seen == 0) continue;  // exact count: nothing to do
+        if (h->sw.inc_sync && !whole && n_seen == 0) continue;  // exact count: nothing to do
         const float* vin = l == 0 ? h->vecA : h->incV[l];  // layer 0: vec is zero, the pointer is not read
         if (whole) {
             ADF_TRY(message_layer(h, l, N, h->incX[l], vin, h->incX[l + 1], h->incV[l + 1], l == 0, s, nullptr, 0,
@@ -884,7 +852,7 @@ static int32_t forward_incremental(adf_painn* h, int N, const int32_t* Z, const 
         }
         // listed rows: launches sized for `cap` rows, the kernels stop at the list length they read from inc_cnt[l]
         const int32_t* list = h->inc_list + cap * l;
-        const int ncap = h->inc_sync ? n_seen : N;
+        const int ncap = h->sw.inc_sync ? n_seen : N;
         h->rows_dev = h->inc_cnt + l;
         int32_t st = message_layer(h, l, N, h->incX[l], vin, h->x, h->vecB, l == 0, s, list, ncap, h->incR[l], true);
         if (st == ADF_OK) st = update_layer(h, l, ncap, h->x, h->vecB, s);
@@ -1165,12 +1133,11 @@ extern "C" int32_t adf_linear_forward(const float* A, const float* W, const floa
     unsigned int* scratch = reinterpret_cast<unsigned int*>(buf + n * 4 + 16);
     int32_t st = adf_split_weight(W, (long long)n, &w16, scratch, s);
     float* mags = nullptr;
-    const char* el = getenv("ADF_LIFT");
-    const bool lift = !(el && strcmp(el, "0") == 0);
+    const bool lift = adf_switches_from_env().lift != 0;   // ADF_LIFT as it stands at this call
     if (st == ADF_OK && lift) st = tmp.alloc(&mags, (size_t)M);
     adf_lift lf = {mags, M};
     if (st == ADF_OK) st = adf_launch_gemm16(A, K, &w16, bias, C, N, M, N, K, act_ssilu, nullptr, s, lift ? &lf : nullptr,
-                                             adf_tune_process(), adf_current_num_cus());
+                                             adf_switches_process().tune, adf_current_num_cus());
     (void)hipStreamSynchronize(s);
     return st;
 }
@@ -1314,7 +1281,7 @@ extern "C" int32_t adf_tr_sample_traj(adf_painn_t h, const adf_batch* b, float* 
                                out_idx, n_out, f1, sink, frame_every, (hipStream_t)stream);
 }
 
-// ---- adf_sample on two views of the batch, two handles, two streams (include/adsorbdiff_split.h; the loop: stepper.hip)
+// ---- adf_sample on two views of the batch, two handles, two streams (the header's section of that name; the loop: stepper.hip)
 extern "C" int32_t adf_sample_split(adf_painn_t h, adf_painn_t t, const adf_batch* b, const adf_split_view* v, float* pos,
                                     const int32_t* tags, const int32_t* fixed, const adf_step_coef* coefs_dev,
                                     int32_t num_steps, const float* z_tr_all, const float* z_rot_all,
@@ -1326,7 +1293,7 @@ extern "C" int32_t adf_sample_split(adf_painn_t h, adf_painn_t t, const adf_batc
     const bool per_system = h->ps_state != nullptr;
     // The one-stream loop, unchanged, where two chains are not independent or not the same arithmetic: the coupled early
     // stop makes every step wait for all systems; the exact-f32 retry is a decision of the whole batch.
-    const bool split = h->tune.sample_split && b->num_systems >= 2 && !h->gemm_f32 && !(early_stop_count > 0 && !per_system);
+    const bool split = h->sw.tune.sample_split && b->num_systems >= 2 && !h->gemm_f32 && !(early_stop_count > 0 && !per_system);
     if (!split) {
         leave_split(h);
         ++h->split_fallbacks;

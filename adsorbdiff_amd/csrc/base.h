@@ -8,8 +8,6 @@
 #include <vector>
 
 #include "../../include/adsorbdiff_hip.h"
-#include "../../include/adsorbdiff_split.h"
-#include "../../include/adsorbdiff_scale_fit.h"
 
 void adf_set_error(const char* fmt, ...);
 

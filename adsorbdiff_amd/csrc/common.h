@@ -2,6 +2,7 @@
 // gfx950 (MI355X) only: 64-wide wavefronts, f32 MFMA 32x32x2, 160 KiB LDS per CU.
 #pragma once
 #include "base.h"
+#include "switches.h"
 #include "arith.h"
 #include "lanes.h"
 
@@ -50,7 +51,7 @@ struct adf_epi {
     int accumulate;          // EPI 0: C += A W^T (+ bias) instead of C = (the training step's accumulated data gradients)
     const float* gate;       // EPI 0 (heads): multiply output row r, column c by gate[(r / 3) * gate_ld + c]  (null: no gate)
     int gate_ld;
-    // Partial row maxima (see adf_painn::rmx): a producer writes, with plain stores, the maximum over the columns it owns
+    // Partial row maxima (see adf_painn::rmx_part): a producer writes, with plain stores, the maximum over the columns it owns
     // into a slot of its own, [part][part_stride]; adf_launch_rowmax_combine takes the maximum over the parts.
     float* catpart;          // EPI 3: max |v2| of row n over the 32 channels of group g -> catpart[g * part_stride + n]
     long long part_stride;
@@ -96,17 +97,18 @@ struct adf_painn {
     bool gemm_f32;
     bool msg_f32;
     bool msg_f32_only;   // num_rbf % 8 != 0: the message block always runs its exact-f32 kernel (adf_painn_create)
-    adf_tune tune;       // kernel-selection switches, read from the environment at creation (adf_tune_from_env)
+    // The environment switches as adf_painn_create read them (switches.h); a twin holds its parent's.  gemm_f32, msg_f32,
+    // lift_on, inc_on start from it and change with their setters; sw.tune.sample_split with adf_painn_set_split.
+    adf_switches sw;
     // per-row power-of-two lifts of the f16x3 products' A operands (default on; ADF_LIFT=0 = the unlifted split of rounds 1-2)
     bool lift_on;
     adf_lift lift;       // [3 capN] magnitudes a launcher measures itself
     float *mag_a, *mag_b;  // [capN] magnitudes handed from a producer (LayerNorm, a product's epilogue) to the next product
     float* mag_v3;         // [3 capN] magnitudes of the vec rows entering the heads (measured once, used by both heads)
     bool mag_v3_valid;
-    // Row maxima from the producers (ADF_ROW_MAXIMA, read at creation, default 1): the message kernel and vec_proj's
+    // Row maxima from the producers (sw.row_maxima: ADF_ROW_MAXIMA, default 1): the message kernel and vec_proj's
     // epilogue emit partial maxima of the rows they write and the layers' measuring passes go.  No atomics, no memsets:
     // every slot has one writer and every row's slots are all written.
-    int rmx;
     float* rmx_part;       // [H/64 + H/32 + 3 H/64][part_stride]: xpart | catpart | vpart, then dbg_mag [4][part_stride]
     float *xpart, *catpart, *vpart;   // xpart[slice][row], catpart[group][row], vpart[slice][3 row + axis]
     int64_t part_stride;   // capN rounded up to 32 rows: a 128-B line of a slot array has one writing workgroup
@@ -175,12 +177,11 @@ struct adf_painn {
     // The list lengths never gate a launch: list-mode kernels are sized for all N rows and read their row count from
     // inc_cnt on the device (rows_dev below).  The host sees the counts one forward late, through a pinned double buffer
     // and an event it polls without waiting, and uses them only to choose between the list and the all-rows form of a
-    // layer and for the statistics.  ADF_INC_SYNC=1: read them back synchronously instead (exact launch sizes).
+    // layer and for the statistics.  ADF_INC_SYNC=1 (sw.inc_sync): read them back synchronously instead (exact launch sizes).
     int32_t* inc_cnt_host;             // pinned [2][2L+1]
     void* inc_ev[2];                   // hipEvent_t after the copy into inc_cnt_host[slot]
     bool inc_ev_live[2];
     int inc_slot;
-    bool inc_sync;
     int32_t inc_seen[2 * ADF_MAX_LAYERS + 1];  // the latest counts the host has seen
     bool inc_seen_valid;
     unsigned char inc_pend_whole[2][ADF_MAX_LAYERS];  // per slot: which layers of that forward ran in the all-rows form
@@ -240,11 +241,8 @@ static inline void adf_prof_end(adf_painn* h, hipStream_t s) { h->prof.end(s); }
 // ---- kernels' host launchers (each enqueues on `s`, returns ADF_*)
 int32_t adf_launch_gemm(const float* A, int lda, const float* W, int ldw, const float* bias, float* C, int ldc,
                         int M, int N, int K, int act_ssilu, hipStream_t s);
-// The kernel-selection switches (include/adsorbdiff_hip.h: adf_tune) as the environment sets them now.  Handles keep a
-// copy made at creation; callers without a handle (adf_linear_forward, the adf_op_* / tr_* operators of train.hip) share
-// adf_tune_process(): one copy read at its first use, and adf_current_num_cus(): the CU count of the current device.
-adf_tune adf_tune_from_env();
-const adf_tune& adf_tune_process();
+// Callers without a handle (adf_linear_forward, the adf_op_* / tr_* operators of train.hip) take the kernel selection from
+// adf_switches_process().tune (switches.h) and the CU count of the current device from adf_current_num_cus().
 int adf_current_num_cus();
 // C = act(A W^T + bias) with EPI 0's operands in *ep (null: the plain product): A2 / K1, rmag (the A rows' magnitudes are
 // already known: written by the producer of A - LayerNorm, a previous product's out_mag), out_mag (emit the output rows'
@@ -274,7 +272,7 @@ static inline int32_t adf_linear(const adf_painn* h, const float* A, int lda, co
     adf_epi ep = {};
     ep.m_dev = h->rows_dev;
     if (h->lift_on) { ep.rmag = premag; ep.out_mag = reinterpret_cast<unsigned int*>(out_mag); }
-    return adf_launch_gemm16(A, lda, W16, bias, C, ldc, M, N, K, act, &ep, s, h->lift_on ? &h->lift : nullptr, h->tune,
+    return adf_launch_gemm16(A, lda, W16, bias, C, ldc, M, N, K, act, &ep, s, h->lift_on ? &h->lift : nullptr, h->sw.tune,
                              h->num_cus);
 }
 // gemm16.hip: fragment image of a split weight [N, K]

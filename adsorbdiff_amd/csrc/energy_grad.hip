@@ -328,7 +328,7 @@ static int32_t eg_lin(adf_painn* h, const float* A, int lda, const EgW& w, const
     }
     adf_epi ep = {};
     ep.accumulate = accumulate;
-    return adf_launch_gemm16(A, lda, &w.w16, bias, C, ldc, (int)M, N, K, 0, &ep, s, h->lift_on ? &h->lift : nullptr, h->tune,
+    return adf_launch_gemm16(A, lda, &w.w16, bias, C, ldc, (int)M, N, K, 0, &ep, s, h->lift_on ? &h->lift : nullptr, h->sw.tune,
                              h->num_cus);
 }
 

@@ -76,9 +76,9 @@ struct adf_eqv2 {
     eq_dims d;
     eq_dims* d_dev;   // device copy (kernels that index its tables per lane)
     int device, num_cus;
-    bool weights_set, consts_set, exact_f32, s2_emit_mag, presplit;
-    bool no_compact;           // ADF_EQV2_COMPACT=0: force blocks evaluate every column of their second convolution
-    bool fold_on, folded;      // grid-MLP end maps folded into the SO(3) linears (eq_ffn); ADF_EQV2_FOLD=0 switches it off
+    bool weights_set, consts_set, exact_f32;   // exact_f32: from sw.gemm_f32, then adf_eqv2_set_arithmetic
+    adf_switches sw;           // the environment switches as adf_eqv2_create read them (switches.h), the eqv2_* ones and tune
+    bool folded;               // grid-MLP end maps folded into the SO(3) linears (eq_ffn); sw.eqv2_fold = 0 switches it off
     float* fold_arena; size_t fold_floats;
     // constants (device)
     float *jd, *to_red, *from_red, *to_full, *from_full;
@@ -108,10 +108,6 @@ struct adf_eqv2 {
     float* ee_term; int64_t ee_term_rows;   // [max(ee_B, 1), C] the per-system term rows
     unsigned char* w16_arena; size_t w16_bytes; float* w16_scales; unsigned int* w16_scratch;
     unsigned char* wfrag_arena;   // fragment images (adf_w16::frag) of the split weights, for eq_launch_gemm16pw
-    bool conv1_wr;                // first convolution with the weights streamed as fragments (ADF_EQV2_CONV1_WR, default on)
-    bool alpha_generic;           // attention logits by the one-head-at-a-time kernel for every width (ADF_EQV2_ALPHA_GENERIC=1)
-    adf_tune tune;                // kernel-selection switches read at creation (common.h: adf_tune_from_env)
-    bool conv2_wr;                // plain products on whole 256-column tiles through gemm16.hip's streamed-fragment kernel (ADF_EQV2_CONV2_WR)
     float* wt_arena; size_t wt_bytes;   // transposed first radial layers
     float* rtab_arena; size_t rtab_floats; bool rad_static;   // per-element-pair radial tables (see eq_radial_static)
     // graph

@@ -81,18 +81,8 @@ extern "C" int32_t adf_eqv2_create(const adf_eqv2_hparams* hp, adf_eqv2_t* out) 
         return ADF_EHIP;
     }
     h->num_cus = prop.multiProcessorCount;
-    const char* env = getenv("ADF_GEMM");
-    h->exact_f32 = env && !strcmp(env, "f32");
-    // the S2 activation can hand the magnitudes of its output rows to the second convolution (atomics in its epilogue)
-    // instead of a separate pass over them: measured slower on MI355X (+8 ms vs -3 ms per forward at 256 k edges): off
-    { const char* e2 = getenv("ADF_EQV2_S2_EMIT"); h->s2_emit_mag = e2 && atoi(e2) != 0; }
-    { const char* e3 = getenv("ADF_EQV2_PRESPLIT"); h->presplit = !(e3 && atoi(e3) == 0); }
-    { const char* e4 = getenv("ADF_EQV2_CONV1_WR"); h->conv1_wr = !(e4 && atoi(e4) == 0); }
-    { const char* e5 = getenv("ADF_EQV2_CONV2_WR"); h->conv2_wr = !(e5 && atoi(e5) == 0); }
-    { const char* e6 = getenv("ADF_EQV2_ALPHA_GENERIC"); h->alpha_generic = e6 && atoi(e6) != 0; }
-    { const char* e4 = getenv("ADF_EQV2_FOLD"); h->fold_on = !(e4 && atoi(e4) == 0); }
-    { const char* e5 = getenv("ADF_EQV2_COMPACT"); h->no_compact = e5 && atoi(e5) == 0; }
-    h->tune = adf_tune_from_env();
+    h->sw = adf_switches_from_env();
+    h->exact_f32 = h->sw.gemm_f32 != 0;
     int32_t st = h->m_life.alloc(&h->flags, EQ_NFLAGS);
     if (st == ADF_OK) st = h->m_life.alloc(&h->d_dev, 1);
     if (st == ADF_OK && hipMemcpy(h->d_dev, &h->d, sizeof(eq_dims), hipMemcpyHostToDevice) != hipSuccess) st = ADF_EHIP;
@@ -337,8 +327,7 @@ static int32_t eq_radial_static(adf_eqv2* h, eq_radial** rads, int nrad, hipStre
     const int NE = h->hp.max_num_elements;
     h->rad_static = false;
     for (int i = 0; i < nrad; ++i) rads[i]->table = nullptr;
-    const char* env = getenv("ADF_EQV2_RADIAL");
-    if (env && !strcmp(env, "edge")) return ADF_OK;
+    if (h->sw.eqv2_radial_edge) return ADF_OK;
     float radii[101];
     ADF_HIP_CHECK(hipMemcpyAsync(radii, h->atom_radii, sizeof(radii), hipMemcpyDeviceToHost, s));
     ADF_HIP_CHECK(hipStreamSynchronize(s));
@@ -417,7 +406,7 @@ static int32_t eq_radial_pair_tables(adf_eqv2* h, eq_radial** rads, const float*
 static int32_t eq_fold_ffn(adf_eqv2* h, hipStream_t s) {
     const eq_dims& d = h->d;
     h->folded = false;
-    if (!h->fold_on) return ADF_OK;
+    if (!h->sw.eqv2_fold) return ADF_OK;
     const size_t per = (size_t)(d.L + 1) * d.F * d.C + d.F + (size_t)d.L * d.C * d.F;
     const size_t total = per * h->hp.num_layers;
     if (h->fold_floats < total) {
@@ -658,8 +647,7 @@ static int32_t eq_ensure_capacity(adf_eqv2* h, int64_t N, int64_t B, int64_t Ene
         ADF_TRY(h->m_ws.alloc(&h->h1, ns * d.F)); ADF_TRY(h->m_ws.alloc(&h->h2, ns * d.F));
         ADF_TRY(h->m_ws.alloc(&h->sys, (size_t)cB * 16));
         // chunk size: bounded edge-arena (ADF_EQV2_CHUNK_EDGES, default 2^19 edges)
-        int64_t chunk_edges = 1 << 19;
-        if (const char* e = getenv("ADF_EQV2_CHUNK_EDGES")) { const long long v = atoll(e); if (v > 0) chunk_edges = v; }
+        const int64_t chunk_edges = h->sw.eqv2_chunk_edges;
         if (h->arena_kk > kk) kk = h->arena_kk;
         h->arena_kk = kk;
         int64_t cn = chunk_edges / kk;
@@ -782,17 +770,17 @@ int32_t eq_gemm(const adf_eqv2* h, const float* A, int lda, const eq_rowmap* ama
         // product kernel of gemm16.hip (four waves, 96 x 256 tile, two workgroups per CU, software-pipelined conversion; same
         // lifts, same products in the same order: same bits) - the second SO(2) convolution's orders m >= 1 (N = 1536 / 1280 at
         // config 4); edge-level launches only (node-level products measured no better there)
-        if (h->conv2_wr && !amap && !cmap && !accumulate && act == 0 && !out_mag && (!rs_pre || rs_div == 1) && W->w16.frag &&
+        if (h->sw.eqv2_conv2_wr && !amap && !cmap && !accumulate && act == 0 && !out_mag && (!rs_pre || rs_div == 1) && W->w16.frag &&
             W->out % 256 == 0 && (W->in / 32) % 2 == 0 && lda == W->in && M >= 65536 && M * (long long)lda * 4 < (1ll << 32) && M < (1ll << 31))
         {
             adf_epi ep = {};
             ep.rmag = rs_pre ? rs_pre : h->rs;
             return adf_launch_gemm16(A, lda, &W->w16, use_bias ? W->b : nullptr, Cm, ldc, (int)M, W->out, W->in, 0, &ep, s, nullptr,
-                                     h->tune, h->num_cus);
+                                     h->sw.tune, h->num_cus);
         }
         if (out_mag) ADF_HIP_CHECK(hipMemsetAsync(out_mag, 0, sizeof(float) * (size_t)M, s));
         return eq_launch_gemm16(A, am, rs_pre ? rs_pre : h->rs, &W->w16, use_bias ? W->b : nullptr, Cm, cm, M, W->out, W->in,
-                                act, accumulate, s, h->tune, out_mag, rs_pre ? rs_div : 1);
+                                act, accumulate, s, h->sw.tune, out_mag, rs_pre ? rs_div : 1);
     }
     // exact-f32 product: no lifts needed downstream either (out_mag stays untouched; callers only pass it on when the
     // matrix-core path runs, see eq_uses_mfma)
@@ -866,7 +854,7 @@ static int32_t eq_attention(adf_eqv2* h, const eq_attn* at, const float* y, cons
         const bool lifts = !h->exact_f32;
         // first convolution on pre-split operands (rotate-in writes lifted fp16 hi / lo rows, the product kernel copies
         // them): every order's weight must have its fp16 image and a contraction length that is a multiple of 32
-        bool pre = lifts && h->presplit && at->c1_m0.has16 && at->c1_m0.in % 32 == 0 && (at->c1_m0.out & 3) == 0;
+        bool pre = lifts && h->sw.eqv2_presplit && at->c1_m0.has16 && at->c1_m0.in % 32 == 0 && (at->c1_m0.out & 3) == 0;
         for (int m = 1; m <= d.M; ++m) pre = pre && at->c1_m[m - 1].has16 && at->c1_m[m - 1].in % 32 == 0 && (at->c1_m[m - 1].out & 3) == 0;
         {
             eq_prof_scope ps(h->prof, EQ_PROF_ROTATE, s);
@@ -880,7 +868,7 @@ static int32_t eq_attention(adf_eqv2* h, const eq_attn* at, const float* y, cons
                     const eq_lin* W = m == 0 ? &at->c1_m0 : &at->c1_m[m - 1];
                     const long long rows = m == 0 ? Eub : 2 * Eub;
                     const _Float16* hi = reinterpret_cast<const _Float16*>(b.m[m]);
-                    if (h->conv1_wr && eq_gemm16pw_ok(&W->w16, W->out, W->in))
+                    if (h->sw.eqv2_conv1_wr && eq_gemm16pw_ok(&W->w16, W->out, W->in))
                         ADF_TRY(eq_launch_gemm16pw(hi, hi + (size_t)rows * W->in, b.rsb[m], &W->w16, m == 0 ? W->b : nullptr,
                                                    b.y[m], W->out, rows, W->out, W->in, 0, s));
                     else
@@ -897,10 +885,10 @@ static int32_t eq_attention(adf_eqv2* h, const eq_attn* at, const float* y, cons
         }
         { eq_prof_scope ps(h->prof, EQ_PROF_ATTN, s); ADF_TRY(eq_launch_alpha(h, at, b.y[0], at->c1_m0.out, n0, n1, b.alpha, s)); }
         bool rs_ok = false;
-        { eq_prof_scope ps(h->prof, EQ_PROF_S2ACT, s); ADF_TRY(eq_launch_s2act(h, b.y[0], b.y, extra, d.NH * d.A, n0, n1, b.mb, h->s2_emit_mag ? b.rsb : nullptr, &rs_ok, s)); }
+        { eq_prof_scope ps(h->prof, EQ_PROF_S2ACT, s); ADF_TRY(eq_launch_s2act(h, b.y[0], b.y, extra, d.NH * d.A, n0, n1, b.mb, h->sw.eqv2_s2_emit ? b.rsb : nullptr, &rs_ok, s)); }
         // a force block reads only the l = 1 rows of the rotated-back message: its second convolution keeps only the
         // output columns that reach them (order 0: l = 1; order 1: real and imaginary part of l = 1; order 2: none)
-        const bool compact = only_l1 && d.M >= 1 && d.L >= 1 && !h->no_compact;
+        const bool compact = only_l1 && d.M >= 1 && d.L >= 1 && h->sw.eqv2_compact;
         if (compact) {
             eq_prof_scope ps(h->prof, EQ_PROF_CONV, s);
             const eq_lin w0 = eq_lin_rows(at->c2_m0, d.HV, d.HV);
@@ -1313,7 +1301,7 @@ extern "C" int32_t adf_eqv2_linear_forward(const float* A, const float* W, const
     for (int r = 0; r < (repeat > 0 ? repeat : 1) && st == ADF_OK; ++r) {
         if (mode == 3) st = eq_launch_gemm16pw(split, split + ma * 2, mag, &w16, bias, Cm, N, M, N, K, act, s);
         else if (mode == 2) st = eq_launch_gemm16p(split, split + ma * 2, mag, &w16, bias, Cm, N, M, N, K, act, s);
-        else st = eq_launch_gemm16(A, &am, mag, &w16, bias, Cm, &cm, M, N, K, act, false, s, adf_tune_process(), nullptr);
+        else st = eq_launch_gemm16(A, &am, mag, &w16, bias, Cm, &cm, M, N, K, act, false, s, adf_switches_process().tune, nullptr);
     }
     (void)hipStreamSynchronize(s);
     return st;
@@ -1371,7 +1359,7 @@ extern "C" int32_t adf_eqv2_get_counters(adf_eqv2_t h, adf_eqv2_counters* out, v
     out->dense_flops = 2 * macs;  // the reference's algorithm (f32-equivalent), whatever shortcuts this path takes
     // what the SO(2)-convolution kernels of the last forward executed: the force blocks keep only the l = 1 columns of their
     // second convolution and, in a subset forward, only the edges of the listed targets (estimated as E n_out / N)
-    const bool compact = d.M >= 1 && d.L >= 1 && !h->no_compact;
+    const bool compact = d.M >= 1 && d.L >= 1 && h->sw.eqv2_compact;
     const int64_t conv2f = compact ? (int64_t)(d.L + 1) * d.Hd * d.HV + 2 * ((int64_t)d.L * d.Hd) * (2 * d.HV) : conv2;
     const int64_t Ef = h->last_subset >= 0 ? E * h->last_subset / (N > 0 ? N : 1) : E;
     // incremental blocks: a block's convolutions run on the edges of its listed targets only (estimated as E rows / N)

@@ -764,7 +764,7 @@ int32_t eq_launch_rotate_in(const adf_eqv2* h, const float* y, const float* rad,
     for (int m = 0; m <= EQ_MAX_M; ++m) { mb.p[m] = m <= h->d.M ? mbuf[m] : nullptr; rs.p[m] = (rsp && m <= h->d.M) ? rsp[m] : nullptr; }
     const int bd = (2 * h->d.C + 63) / 64 * 64;
     if (bd > 256) { adf_set_error("rotate_in: more than 128 sphere channels (one thread per input channel, 256-thread workgroups; INTEGRATION.md 5)"); return ADF_EINVAL; }
-    const bool m2 = h->d.M == 2 && !h->tune.eqv2_rotin_generic;   // compile-time-M fast path (M = 2: the shipped models)
+    const bool m2 = h->d.M == 2 && !h->sw.tune.eqv2_rotin_generic;   // compile-time-M fast path (M = 2: the shipped models)
 #define EQ_RI_(LT_, MT_)                                                                                               \
     if (presplit)                                                                                                      \
         hipLaunchKernelGGL((eq_rotate_in_kernel<LT_, true, MT_>), dim3((unsigned)Eub), dim3(bd), 0, s, y, rad, h->wig, h->eptr, \
@@ -1277,7 +1277,7 @@ int32_t eq_launch_alpha(const adf_eqv2* h, const eq_attn* at, const float* y0, i
     if (n1 <= n0) return ADF_OK;
     if (h->d.NH > 16) { adf_set_error("eqv2: more than 16 heads"); return ADF_EINVAL; }
     const long long Eub = eq_edge_bound(h, n1 - n0);
-    const bool a64 = !h->alpha_generic && h->d.A == 64 && (ldy & 3) == 0 && (reinterpret_cast<uintptr_t>(y0) & 15) == 0 &&
+    const bool a64 = !h->sw.eqv2_alpha_generic && h->d.A == 64 && (ldy & 3) == 0 && (reinterpret_cast<uintptr_t>(y0) & 15) == 0 &&
                      (reinterpret_cast<uintptr_t>(at->alpha_ln_w) & 15) == 0 && (reinterpret_cast<uintptr_t>(at->alpha_ln_b) & 15) == 0 &&
                      (reinterpret_cast<uintptr_t>(at->alpha_dot) & 15) == 0;
     if (a64)
@@ -1408,7 +1408,7 @@ int32_t eq_launch_rotate_out(const adf_eqv2* h, float* const* z, const float* al
     for (int m = 0; m <= h->d.M; ++m) zm.p[m] = z[m];
     const int bd = (h->d.HV + 63) / 64 * 64;
     if (bd > 256) { adf_set_error("rotate_out: num_heads * attn_value_channels > 256 (one thread per value channel; INTEGRATION.md 5)"); return ADF_EINVAL; }
-    const bool m2 = h->d.M == 2 && !h->tune.eqv2_rotout_generic;   // the compile-time-M fast path (M = 2: the shipped models)
+    const bool m2 = h->d.M == 2 && !h->sw.tune.eqv2_rotout_generic;   // the compile-time-M fast path (M = 2: the shipped models)
 #define EQ_RO_(LT_, MT_)                                                                                               \
     if (only_l1)                                                                                                       \
         hipLaunchKernelGGL((eq_rotate_out_kernel<LT_, true, MT_>), dim3(n1 - n0), dim3(bd), 0, s, z[0], zm, alpha, h->wig, \

@@ -573,7 +573,7 @@ int32_t adf_graph_build_impl(adf_painn* h, const adf_batch* b, hipStream_t s) {
     const unsigned nb = (unsigned)((slots + 255) / 256);
     // count / fill / sort: per system out of LDS (above); systems that do not fit go through the global-memory kernels
     const int32_t* only = nullptr;
-    if (h->tune.graph_sys_csr) {
+    if (h->sw.tune.graph_sys_csr) {
         hipLaunchKernelGGL(adf_count_sys_kernel, dim3(B), dim3(256), 0, s, p, h->deg, h->sys_slow);
         only = h->sys_slow;
     }

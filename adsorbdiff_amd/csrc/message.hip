@@ -651,8 +651,7 @@ int32_t adf_pack_rbf(adf_painn* h, hipStream_t s) {
         ADF_HIP_CHECK(hipStreamSynchronize(s));
         bool uni = true;
         for (int k = 0; k < R; ++k) uni = uni && fabsf(mu[k] - (float)k / (float)(R - 1)) <= 2e-7f;
-        const char* e = getenv("ADF_MSG_RBF");
-        h->rbf_uniform = uni && !(e && strcmp(e, "direct") == 0);
+        h->rbf_uniform = uni && !h->sw.msg_rbf_direct;   // ADF_MSG_RBF=direct, as the handle read it at creation
     }
     for (int l = 0; l < h->hp.num_layers; ++l) ADF_TRY(adf_pack_rbf_layer(h, l, s));
     ADF_HIP_CHECK(hipGetLastError());

@@ -288,11 +288,11 @@ int32_t adf_head_forward(adf_painn* h, int head, int N, const float* x, const fl
         ADF_TRY(adf_linear(h, vec, H, b0.vec1_w, &b0.vec1_16, nullptr, t1, H, 3 * N, H, H, 0, s));
         hipLaunchKernelGGL(adf_head_norm_cat_kernel, dim3(ew_grid((long long)N * H / 4)), dim3(256), 0, s, x, t1, h->cat, N, H);
     } else {  // ||vec1_proj(vec)|| straight from the accumulators into cat [N,H]
-        ADF_TRY(adf_launch_gemm16_vecnorm(vec, H, &b0.vec1_16, h->cat, N, H, H, s, h->tune, lf, vmag));
+        ADF_TRY(adf_launch_gemm16_vecnorm(vec, H, &b0.vec1_16, h->cat, N, H, H, s, h->sw.tune, lf, vmag));
     }
     // f16x3 path (round 6): vec2_proj runs AFTER the update net and multiplies its rows by the gate half of `o` in its own
     // epilogue (same single fp32 multiplication per element as adf_head_gate_kernel: same bits); t2 never reaches HBM
-    const bool fg = h->tune.head_gate_fused && !h->gemm_f32 && (H2 & 3) == 0;
+    const bool fg = h->sw.tune.head_gate_fused && !h->gemm_f32 && (H2 & 3) == 0;
     if (!fg) ADF_TRY(adf_linear(h, vec, H, b0.vec2_w, &b0.vec2_16, nullptr, t2, H2, 3 * N, H2, H, 0, s, vmag));
     if (h->gemm_f32) ADF_TRY(adf_linear(h, h->cat, 2 * H, b0.un0_w, &b0.un0_16, b0.un0_b, h->y, H, N, H, 2 * H, 1, s));
     else {
@@ -300,7 +300,7 @@ int32_t adf_head_forward(adf_painn* h, int head, int N, const float* x, const fl
         e0.A2 = h->cat; e0.K1 = H;   // [x | norm]
         e0.out_mag = h->lift_on ? reinterpret_cast<unsigned int*>(h->mag_b) : nullptr;
         ADF_TRY(adf_launch_gemm16(x, H, &b0.un0_16, b0.un0_b, h->y, H, N, H, 2 * H, 1, &e0, s, h->lift_on ? &h->lift : nullptr,
-                                  h->tune, h->num_cus));
+                                  h->sw.tune, h->num_cus));
     }
     ADF_TRY(adf_linear(h, h->y, H, b0.un2_w, &b0.un2_16, b0.un2_b, o, H, N, H, H, 0, s, (h->lift_on && !h->gemm_f32) ? h->mag_b : nullptr));
     if (fg) {
@@ -309,7 +309,7 @@ int32_t adf_head_forward(adf_painn* h, int head, int N, const float* x, const fl
         eg.rmag = vmag;
         eg.out_mag = lift ? reinterpret_cast<unsigned int*>(h->lift.buf) : nullptr;
         eg.gate = o + H2; eg.gate_ld = H;
-        ADF_TRY(adf_launch_gemm16(vec, H, &b0.vec2_16, nullptr, v1, H2, 3 * N, H2, H, 0, &eg, s, lf, h->tune, h->num_cus));
+        ADF_TRY(adf_launch_gemm16(vec, H, &b0.vec2_16, nullptr, v1, H2, 3 * N, H2, H, 0, &eg, s, lf, h->sw.tune, h->num_cus));
         hipLaunchKernelGGL(adf_head_xact_kernel, dim3(ew_grid((long long)N * H2 / 4)), dim3(256), 0, s, o, x1, N, H2);
     } else
     hipLaunchKernelGGL(adf_head_gate_kernel, dim3(ew_grid((long long)N * H2 / 4)), dim3(256), 0, s, o, t2, x1, v1, N, H2);
@@ -319,12 +319,12 @@ int32_t adf_head_forward(adf_painn* h, int head, int N, const float* x, const fl
         hipLaunchKernelGGL(adf_head_norm_cat_kernel, dim3(ew_grid((long long)N * H2 / 4)), dim3(256), 0, s, x1, t1b, cat1, N, H2);
         ADF_TRY(adf_linear(h, cat1, H, b1.un0_w, &b1.un0_16, b1.un0_b, h->y, H2, N, H2, H, 1, s));
     } else {
-        ADF_TRY(adf_launch_gemm16_vecnorm(v1, H2, &b1.vec1_16, cat1, N, H2, H2, s, h->tune, h->lift_on ? &h->lift : nullptr,
+        ADF_TRY(adf_launch_gemm16_vecnorm(v1, H2, &b1.vec1_16, cat1, N, H2, H2, s, h->sw.tune, h->lift_on ? &h->lift : nullptr,
                                           (fg && lift) ? h->lift.buf : nullptr));
         adf_epi e1 = {};
         e1.A2 = cat1; e1.K1 = H2;   // [x1 | norm]
         ADF_TRY(adf_launch_gemm16(x1, H2, &b1.un0_16, b1.un0_b, h->y, H2, N, H2, H, 1, &e1, s, h->lift_on ? &h->lift : nullptr,
-                                  h->tune, h->num_cus));
+                                  h->sw.tune, h->num_cus));
     }
     hipLaunchKernelGGL(adf_head_final_kernel, dim3((N + 3) / 4), dim3(256), 0, s, h->y, v1, b1.vec2_w, b1.un2_w,
                        b1.un2_b, out, N, H2, h->flags);

@@ -1,6 +1,6 @@
 // Slab cutting: the slabs of a batch of bulk crystals along Miller indices - oriented cell, thickness,
 // terminations, primitive in-plane cell, duplicate terminations, top and bottom - and the distinct Miller indices of a bulk
-// under its point group.  The contract is in include/adsorbdiff_slabs.h.  It is the reference's compute_slabs
+// under its point group.  The contract is in include/adsorbdiff_hip.h, section "Slab cutting".  It is the reference's compute_slabs
 // (placement/slab.py:485-552: pymatgen's SlabGenerator, StructureMatcher and SpacegroupAnalyzer per Miller index) as a written
 // contract: parity with pymatgen unpinned.
 //
@@ -20,7 +20,6 @@
 #include <math.h>
 
 #include "host_util.h"
-#include "../../include/adsorbdiff_slabs.h"
 
 #define SC_THREADS 256
 #define SC_WAVES (SC_THREADS / 64)

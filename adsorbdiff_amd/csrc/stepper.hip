@@ -633,7 +633,7 @@ int32_t adf_model_sample_split(const adf_model& mA, const adf_model& mB, adf_spl
     return ADF_OK;
 }
 
-// The cut of a split run (include/adsorbdiff_split.h): host arithmetic only.
+// The cut of a split run (adsorbdiff_hip.h, "Two half-batches, two streams"): host arithmetic only.
 extern "C" int32_t adf_split_choose_cut(const int32_t* natoms, const int64_t* edges, int32_t num_systems, int32_t* cut) {
     if (!natoms || !cut || num_systems < 0) { adf_set_error("split_choose_cut: bad argument"); return ADF_EINVAL; }
     *cut = 0;

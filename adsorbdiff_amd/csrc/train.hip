@@ -34,7 +34,7 @@ static inline unsigned tr_grid(long long total, int per_block = 256) {
 // ~1e-6 gradient rows of the data-gradient products, keep both fp16 terms) and the weight split per call - in training
 // the weights change every step; the hi/lo image and the row magnitudes live in per-device scratch that consecutive
 // calls on one stream reuse in order.  ADF_TRAIN_GEMM=f32 selects the exact-f32 MFMA GEMM (gemm.hip) everywhere.
-static int tr_gemm_mode() { return adf_tune_process().train_gemm16; }
+static int tr_gemm_mode() { return adf_switches_process().tune.train_gemm16; }
 // the f16x3 path takes this product (A [M, K] with row stride lda)
 static bool tr_gemm16_ok(int lda, long long M, int K) {
     return tr_gemm_mode() == 1 && K % 32 == 0 && (lda & 3) == 0 && M * (long long)lda * 4 < (1ll << 32);
@@ -94,7 +94,7 @@ static int32_t tr_gemm(const float* A, int lda, const float* W, const float* bia
     const adf_lift lf = {mag[dev], mag_cap[dev]};
     adf_epi ep = {};
     ep.accumulate = accumulate;
-    return adf_launch_gemm16(A, lda, &w16, bias, C, ldc, (int)M, N, K, 0, &ep, s, &lf, adf_tune_process(), adf_current_num_cus());
+    return adf_launch_gemm16(A, lda, &w16, bias, C, ldc, (int)M, N, K, 0, &ep, s, &lf, adf_switches_process().tune, adf_current_num_cus());
 }
 
 __global__ void tr_transpose_kernel(const float* __restrict__ src, float* __restrict__ dst, int R, int C) {
@@ -546,7 +546,7 @@ extern "C" int32_t adf_op_linear_bwd(const float* A, int32_t lda, const float* W
         if (N % 128 == 0 && K % 128 == 0 && (lda & 3) == 0 && (ldc & 3) == 0 &&
             ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(dC)) & 15) == 0) {
             // ADF_WGRAD=f32: the exact-f32 matrix-core kernel (v_mfma_f32_32x32x2_f32); default: three-term bf16 split
-            if (adf_tune_process().wgrad_f32)
+            if (adf_switches_process().tune.wgrad_f32)
                 hipLaunchKernelGGL(tr_wgrad128_kernel, dim3((N / 128) * (K / 128), splits), dim3(256), 0, s, dC, ldc, A, lda, part,
                                    (int)M, N, K, rows, K / 128, bp);
             else

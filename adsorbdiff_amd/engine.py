@@ -465,9 +465,9 @@ class PaiNNEngine(Engine):
                out_idx: Optional[torch.Tensor] = None, sink=None, frame_every: int = 1,
                split_streams: Optional[bool] = None) -> None:
         """``Engine.sample``; with ``split_streams`` (default: ``ADF_SAMPLE_SPLIT`` as the handle read it) the two sides of a
-        cut at a system boundary run on two streams (``adf_sample_split``, include/adsorbdiff_split.h) - same bits.  A
-        trajectory sink and a batch of one system take the one-stream loop here; the library's own fallbacks (exact f32, the
-        coupled early stop) are counted by ``split_stats``."""
+        cut at a system boundary run on two streams (``adf_sample_split``; include/adsorbdiff_hip.h, section "Two
+        half-batches, two streams") - same bits.  A trajectory sink and a batch of one system take the one-stream
+        loop here; the library's own fallbacks (exact f32, the coupled early stop) are counted by ``split_stats``."""
         want = self._split_default if split_streams is None else bool(split_streams)
         if not want or sink is not None or prep.num_systems < 2:
             return super().sample(prep, pos, f1, f2, coefs_dev, num_steps, state, z_tr_all, z_rot_all, early_stop_count,

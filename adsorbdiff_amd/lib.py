@@ -59,7 +59,7 @@ class Tune(C.Structure):
 
 
 class SplitView(C.Structure):
-    """adf_split_view: view B of a split sampling run (include/adsorbdiff_split.h)."""
+    """adf_split_view: view B of a split sampling run (include/adsorbdiff_hip.h, "Two half-batches, two streams")."""
     _fields_ = [("cut", C.c_int32), ("atoms_a", C.c_int32), ("n_out_a", C.c_int32), ("n_out_b", C.c_int32),
                 ("atom_offset", C.c_void_p), ("batch", C.c_void_p), ("out_idx", C.c_void_p), ("mov_idx", C.c_void_p),
                 ("mov_off", C.c_void_p)]
@@ -104,7 +104,7 @@ HEADER = Path(__file__).resolve().parent.parent / "include" / "adsorbdiff_hip.h"
 _SCALARS = {"int32_t": C.c_int32, "int64_t": C.c_int64, "float": C.c_float, "double": C.c_double}
 _RETURNS = {"int32_t": C.c_int32, "int64_t": C.c_int64, "const char*": C.c_char_p}
 # the structs that are always host structs handed over with byref(); adf_step_coef / adf_tr_coef are also device tables
-# passed as data_ptr(), so a pointer to one is a plain address
+# passed as data_ptr(), so a pointer to one is a plain address, and so is one to adf_split_view
 _BYREF = {"adf_batch": BatchDesc, "adf_painn_hparams": Hparams, "adf_eqv2_hparams": EqV2Hparams, "adf_tune": Tune,
           "adf_counters": Counters, "adf_eqv2_counters": EqV2Counters, "adf_active_field": ActiveField}
 
@@ -153,18 +153,6 @@ def parse_header(text: str) -> dict:
 
 SIGNATURES = parse_header(HEADER.read_text())
 EXPORTS = tuple(SIGNATURES)
-# the companion header of the split sampling loop: read behind the main header's text (it uses its types), bound the same way
-SPLIT_HEADER = HEADER.with_name("adsorbdiff_split.h")
-SPLIT_SIGNATURES = {name: sig for name, sig in parse_header(HEADER.read_text() + "\n" + SPLIT_HEADER.read_text()).items()
-                    if name not in SIGNATURES}
-# ... and of the scale-factor fit (adf_op_column_variance, adf_painn_forward_observe)
-SCALE_FIT_HEADER = HEADER.with_name("adsorbdiff_scale_fit.h")
-SCALE_FIT_SIGNATURES = {name: sig for name, sig in parse_header(HEADER.read_text() + "\n" + SCALE_FIT_HEADER.read_text()).items()
-                        if name not in SIGNATURES}
-# ... and of slab cutting (adf_distinct_millers_*, adf_slab_cut_*)
-SLABS_HEADER = HEADER.with_name("adsorbdiff_slabs.h")
-SLABS_SIGNATURES = {name: sig for name, sig in parse_header(HEADER.read_text() + "\n" + SLABS_HEADER.read_text()).items()
-                    if name not in SIGNATURES}
 
 _LIB = None
 
@@ -190,7 +178,7 @@ def load():
             "(the HIP path has no CPU fallback)"
         )
     lib = C.CDLL(str(path))
-    for name, (restype, argtypes) in {**SIGNATURES, **SPLIT_SIGNATURES, **SCALE_FIT_SIGNATURES, **SLABS_SIGNATURES}.items():
+    for name, (restype, argtypes) in SIGNATURES.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     _LIB = lib

@@ -5,8 +5,8 @@ primitive in-plane cell, duplicate terminations, top and bottom - and ``distinct
 ``compute_slabs``) ``bulk -> slabs -> tags -> sites -> placement -> sampling -> relaxation -> ranked sites`` needs nothing
 outside this package.
 
-The rule is the contract written in include/adsorbdiff_slabs.h.  Neither pymatgen nor spglib is a dependency and neither
-was run against it: parity with pymatgen unpinned; the contract is pinned to an independent float64 statement
+The rule is the contract written in include/adsorbdiff_hip.h, section "Slab cutting".  Neither pymatgen nor spglib is a
+dependency and neither was run against it: parity with pymatgen unpinned; the contract is pinned to an independent float64 statement
 (tests/helpers_slabs.py), to crystallographic facts and to the invariants of a correct slab.  The bulk's cell is taken as
 given: ``standardize_bulk`` (spglib's conventional cell) stays out, and so do ``lll_reduce``, ``max_normal_search``,
 bond-aware cuts, ``symmetrize=True``, pickles (``from_precomputed_slabs_pkl``, ``save_path``) and ASE / pymatgen objects.

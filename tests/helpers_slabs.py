@@ -1,4 +1,4 @@
-"""An independent float64 numpy statement of the slab-cutting contract (include/adsorbdiff_slabs.h), by brute
+"""An independent float64 numpy statement of the slab-cutting contract (include/adsorbdiff_hip.h "Slab cutting"), by brute
 force: the in-plane basis and u3 come from a search over small integer vectors (no Euclid, no reduction), a slab's atoms
 from a block of periodic images cut by height and by the in-plane cell (no lifting of the oriented cell), equivalence from
 trying every pairing of one atom with every atom of the other slab and every periodic image.  Also the invariant checkers

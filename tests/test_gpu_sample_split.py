@@ -1,4 +1,4 @@
-"""GPU tests of "two half-batches, two streams" (include/adsorbdiff_split.h; csrc/stepper.hip sample_loop_split):
+"""GPU tests of "two half-batches, two streams" (the header's section of that name; csrc/stepper.hip sample_loop_split):
 a sampling run whose two sides of a cut run on two handles and two streams has the bits of the one-stream run.
 
 Two engines are built from one state dict (the stepper fixtures' small PaiNN: H = 128, 2 layers): `split` runs every case

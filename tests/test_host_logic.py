@@ -27,7 +27,7 @@ CODE = re.sub(r"/\*.*?\*/", " ", HEADER, flags=re.S)                           #
 SCALARS = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "double": ctypes.c_double}
 BYREF = {"adf_batch": L.BatchDesc, "adf_painn_hparams": L.Hparams, "adf_eqv2_hparams": L.EqV2Hparams, "adf_tune": L.Tune,
          "adf_counters": L.Counters, "adf_eqv2_counters": L.EqV2Counters, "adf_active_field": L.ActiveField}
-MIRRORS = dict(BYREF, adf_step_coef=L.StepCoef, adf_tr_coef=L.TrCoef)
+MIRRORS = dict(BYREF, adf_step_coef=L.StepCoef, adf_tr_coef=L.TrCoef, adf_split_view=L.SplitView)
 PROTOTYPES = re.findall(r"^(int32_t|int64_t|const char\*) (adf_[a-z_0-9]+)\(([^)]*)\);", CODE, flags=re.M)
 
 
@@ -40,9 +40,10 @@ def _expected_argtype(param: str):
 
 def test_c_abi_every_header_prototype_is_parsed_and_exported():
     loose = set(re.findall(r"\b(adf_[a-z_0-9]+)\s*\(", HEADER)) - {"adf_painn"}   # the old loose search; adf_painn: struct tag
-    assert {name for _, name, _ in PROTOTYPES} == loose and len(PROTOTYPES) == len(loose) == 163
+    assert {name for _, name, _ in PROTOTYPES} == loose and len(PROTOTYPES) == len(loose) == 177
     assert set(L.parse_header(HEADER)) == loose and set(L.EXPORTS) == loose
     assert list(L.EXPORTS) == [name for _, name, _ in PROTOTYPES]               # header order
+    assert sorted(p.name for p in (ROOT / "include").iterdir()) == ["adsorbdiff_hip.h"]   # the one header: no companions
     lib = L.load()
     for name in sorted(loose):
         assert hasattr(lib, name), f"{name} declared in the header but not exported"
@@ -59,7 +60,7 @@ def test_c_abi_argument_and_return_types_are_the_headers():
         assert list(fn.argtypes) == expected, name
         assert fn.restype is returns[ret], name
         n64 += ret == "int64_t"
-    assert n64 == 10 and lib.adf_frames_pushed.restype is ctypes.c_int64 and lib.adf_op_optimizer_chunk.argtypes == []
+    assert n64 == 13 and lib.adf_frames_pushed.restype is ctypes.c_int64 and lib.adf_op_optimizer_chunk.argtypes == []
     assert lib.adf_last_error.restype is ctypes.c_char_p and lib.adf_version.restype is ctypes.c_char_p
     # spot checks written out by hand: a double, a float, an int64 in the middle, a host struct, a coefficient table
     i32, i64, vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p
@@ -89,7 +90,7 @@ def test_c_abi_parser_refuses_what_it_does_not_know(text, named):
 
 def test_c_abi_struct_mirrors_equal_the_typedefs():
     structs = dict((name, body) for body, name in re.findall(r"typedef struct\s*\w*\s*\{([^}]*)\}\s*(\w+);", CODE))
-    assert set(structs) == set(MIRRORS) and len(MIRRORS) == 9
+    assert set(structs) == set(MIRRORS) and len(MIRRORS) == 10
     for name, mirror in MIRRORS.items():
         fields = []
         for decl in filter(None, (d.strip() for d in structs[name].split(";"))):
@@ -106,6 +107,28 @@ def test_c_abi_status_codes_equal_the_defines():
     assert list(defines) == ["ADF_OK", "ADF_EINVAL", "ADF_EOOM", "ADF_ENONEIGHBOR", "ADF_EHIP", "ADF_EOVERFLOW", "ADF_ENUMERIC"]
     for name, value in defines.items():
         assert getattr(L, name) == int(value), name
+
+
+def test_environment_switches_one_table_one_reader_and_the_documentation():
+    """Three sets of ADF_* names must agree: the rows of the table in csrc/switches.h, the switch paragraph of INTEGRATION.md
+    section 4 (less the names listed here with their reasons), and what getenv is called with under csrc/ - the table's
+    reader alone."""
+    csrc = ROOT / "adsorbdiff_amd" / "csrc"
+    table = re.findall(r'^\s*\{"(ADF_[A-Z0-9_]+)",\s*ADF_SW_(?:FLAG|PRESENT|WORD|POSINT),', (csrc / "switches.h").read_text(), flags=re.M)
+    assert len(table) == len(set(table)) == 26
+    section = re.search(r"^Environment switches \(.*?(?=^## )", (ROOT / "INTEGRATION.md").read_text(), flags=re.M | re.S).group(0)
+    documented = set(re.findall(r"\bADF_[A-Z0-9_]+\b", section))
+    elsewhere = {
+        "ADF_TRAIN_MSG": "read by adsorbdiff_amd/train_step.py: which training operators Python calls",
+        "ADF_TRAIN_MSG_BWD": "read by adsorbdiff_amd/train_step.py",
+        "ADF_TRAIN_RBF_WGRAD": "read by adsorbdiff_amd/train_step.py",
+        "ADF_LIB_PATH": "read by adsorbdiff_amd/lib.py before the library is loaded",
+        "ADF_FUSED_MLP": "retired with the kernel it selected; the paragraph says so",
+    }
+    assert set(elsewhere) <= documented
+    assert set(table) == documented - set(elsewhere)
+    calls = [(path.name, arg) for path in sorted(csrc.glob("*.h*")) for arg in re.findall(r"\bgetenv\s*\(([^)]*)\)", path.read_text())]
+    assert calls == [("switches.h", "r.name")]
 
 
 def test_hostargs_conversions_on_a_two_system_batch():

@@ -1,8 +1,11 @@
 """Host tests (no GPU) of the split sampling run's cut: adf_split_choose_cut is host arithmetic inside the library
 (csrc/stepper.hip) and engine.split_cut calls it.  The view's pointer offsets are formed inside adf_sample_split, next to
 the device calls: tests/test_gpu_sample_split.py covers them."""
+import ctypes as C
+
 import pytest
 
+from adsorbdiff_amd import lib as L
 from adsorbdiff_amd.engine import split_cut
 
 
@@ -42,3 +45,27 @@ def test_edge_counts_break_ties_only():
         split_cut([1, 2], [1])
     with pytest.raises(ValueError):
         split_cut([1, -2])
+
+
+def test_c_abi_of_the_five_split_entries():
+    # the section "Two half-batches, two streams" of include/adsorbdiff_hip.h declares these five, in this order
+    names = ["adf_painn_create_twin", "adf_painn_set_split", "adf_split_choose_cut", "adf_sample_split", "adf_split_stats"]
+    first = L.EXPORTS.index(names[0])
+    assert list(L.EXPORTS[first:first + len(names)]) == names
+    i32, vp, batch = C.c_int32, C.c_void_p, C.POINTER(L.BatchDesc)
+    assert L.SIGNATURES["adf_painn_create_twin"] == (i32, [vp, vp])
+    assert L.SIGNATURES["adf_painn_set_split"] == (i32, [vp, i32])
+    assert L.SIGNATURES["adf_split_choose_cut"] == (i32, [vp, vp, i32, vp])
+    # the batch goes by reference; the view is a plain address (the engine hands over the address of its own SplitView)
+    assert L.SIGNATURES["adf_sample_split"] == (i32, [vp, vp, batch, vp, vp, vp, vp, vp, i32, vp, vp, i32, i32, vp, vp, i32,
+                                                      vp, vp, vp])
+    assert L.SIGNATURES["adf_split_stats"] == (i32, [vp, vp, vp])
+    lib = L.load()
+    for name in names:
+        fn = getattr(lib, name)
+        assert fn.restype is L.SIGNATURES[name][0] and list(fn.argtypes) == L.SIGNATURES[name][1], name
+    # argument checks come before any device work
+    assert lib.adf_painn_create_twin(None, None) == L.ADF_EINVAL and lib.adf_painn_set_split(None, 1) == L.ADF_EINVAL
+    cut = C.c_int32(-1)
+    natoms = (C.c_int32 * 3)(31, 65, 290)
+    assert lib.adf_split_choose_cut(natoms, None, 3, C.byref(cut)) == L.ADF_OK and cut.value == 2

@@ -168,10 +168,11 @@ def test_c_abi_of_the_two_entries():
 
     from adsorbdiff_amd import lib as L
 
-    # the companion header include/adsorbdiff_scale_fit.h declares exactly these three, bound from its text
-    sig = L.SCALE_FIT_SIGNATURES
-    assert list(sig) == ["adf_op_column_variance_scratch", "adf_op_column_variance", "adf_painn_forward_observe"]
-    assert not set(sig) & set(L.EXPORTS)
+    # the section "Scale-factor fit" of include/adsorbdiff_hip.h declares exactly these three, in this order, bound from its text
+    names = ["adf_op_column_variance_scratch", "adf_op_column_variance", "adf_painn_forward_observe"]
+    at = L.EXPORTS.index(names[0])
+    assert list(L.EXPORTS[at:at + len(names)]) == names
+    sig = {name: L.SIGNATURES[name] for name in names}
     assert sig["adf_op_column_variance_scratch"] == (C.c_int64, [C.c_int64, C.c_int32])
     assert sig["adf_op_column_variance"] == (C.c_int32, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p])
     rt, at = sig["adf_painn_forward_observe"]

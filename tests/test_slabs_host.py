@@ -1,6 +1,6 @@
 """CPU tests of slab cutting (adsorbdiff_amd/slabs.py): the float64 oracle of tests/helpers_slabs.py must give
 the crystallographic facts of the case table and satisfy the invariants (a)-(g) before the device is held to it
-(tests/test_gpu_slabs.py); then the host-side argument checks, the C ABI of include/adsorbdiff_slabs.h and the per-slab keys
+(tests/test_gpu_slabs.py); then the host-side argument checks, the C ABI of the header's section "Slab cutting" and the per-slab keys
 through ``Batch`` splitting.  Parity with pymatgen unpinned."""
 import functools
 
@@ -124,11 +124,13 @@ def test_specific_millers_forms():
 
 
 def test_c_abi_of_the_slab_header():
-    assert list(L.SLABS_SIGNATURES) == ["adf_distinct_millers_scratch", "adf_distinct_millers_count", "adf_distinct_millers_fill",
-                                        "adf_slab_cut_scratch", "adf_slab_cut_count", "adf_slab_cut_fill"]
-    assert not set(L.SLABS_SIGNATURES) & set(L.EXPORTS) and "slabcut.hip" in BUILD.SOURCES
+    names = ["adf_distinct_millers_scratch", "adf_distinct_millers_count", "adf_distinct_millers_fill",
+             "adf_slab_cut_scratch", "adf_slab_cut_count", "adf_slab_cut_fill"]
+    at = L.EXPORTS.index(names[0])
+    assert list(L.EXPORTS[at:at + len(names)]) == names and "slabcut.hip" in BUILD.SOURCES
     lib = L.load()
-    for name, (restype, argtypes) in L.SLABS_SIGNATURES.items():
+    for name in names:
+        restype, argtypes = L.SIGNATURES[name]
         fn = getattr(lib, name)
         assert fn.restype is restype and list(fn.argtypes) == argtypes
     small, large = lib.adf_slab_cut_scratch(8, 2), lib.adf_slab_cut_scratch(800, 2)
