@@ -13,6 +13,7 @@
 #include <new>
 
 #include "eqv2.h"
+#include "eqv2_train.h"   // adf_eqv2_export_graph
 
 int32_t eq_gemm_f32(const float* A, int lda, const eq_rowmap* amap, const float* W, const float* bias, float* Cm, int ldc,
                     const eq_rowmap* cmap, long long M, int N, int K, int act, bool accumulate, hipStream_t s);
@@ -1009,9 +1010,9 @@ static int32_t eq_block_nodes(adf_eqv2* h, const eq_block& bk, float* X, int n, 
 // compacted copy of their incoming edges; rows out_idx[*] of f1 / f2 are written, bit-identical to the full forward's
 // (every row of every product, the softmax of a target and its aggregation depend on that target's edges alone).
 // energy != null (S2EF model): the energy head on the final-normed embedding, [B]
-static int32_t eq_forward_impl(adf_eqv2* h, const adf_batch* b, float* f1, float* f2, float* x_blocks, hipStream_t s,
-                               const int32_t* out_idx = nullptr, int32_t n_out = 0, float* energy = nullptr) {
-    const eq_dims& d = h->d;
+// The graph of a batch in the handle's workspaces: the caller's edge list (adf_eqv2_set_edges) or the top-K radius graph,
+// then the Wigner rows and the range check of the atomic numbers.  Shared by the forward and adf_eqv2_export_graph.
+static int32_t eq_build_graph(adf_eqv2* h, const adf_batch* b, hipStream_t s) {
     const int N = b->num_atoms, B = b->num_systems;
     ADF_TRY(eq_ensure_capacity(h, N, B, h->ext_graph ? h->E_ext : 0));
     const int32_t* Z = b->atomic_numbers;
@@ -1029,6 +1030,15 @@ static int32_t eq_forward_impl(adf_eqv2* h, const adf_batch* b, float* f1, float
         ADF_TRY(eq_launch_check_z(h, Z, N, s));
     }
     h->lastN = N;
+    return ADF_OK;
+}
+
+static int32_t eq_forward_impl(adf_eqv2* h, const adf_batch* b, float* f1, float* f2, float* x_blocks, hipStream_t s,
+                               const int32_t* out_idx = nullptr, int32_t n_out = 0, float* energy = nullptr) {
+    const eq_dims& d = h->d;
+    const int N = b->num_atoms, B = b->num_systems;
+    ADF_TRY(eq_build_graph(h, b, s));
+    const int32_t* Z = b->atomic_numbers;
     if (h->ee_on) ADF_TRY(eq_energy_term_ready(h, B, s));
     const size_t xs = (size_t)N * d.S * d.C;
     const int nl = h->hp.num_layers;
@@ -1328,6 +1338,31 @@ extern "C" int32_t adf_eqv2_radial_first_layer(adf_eqv2_t h, int32_t which, int6
                                                      h->hp.max_num_elements, h->hp.max_radius, out, h->flags, s);
     (void)hipStreamSynchronize(s);
     return st;
+}
+
+// ---------------------------------------------------------------------------------------------- graph hand-off (training)
+extern "C" int32_t adf_eqv2_export_graph(adf_eqv2_t h, const adf_batch* b, int64_t cap_edges, int32_t* eptr, int32_t* src,
+                                         int32_t* dst, float* vec, float* wig, int64_t* num_edges, void* stream) {
+    ADF_TRY(eq_check_batch(h, b));
+    if (!eptr || !src || !dst || !vec || !wig || !num_edges || cap_edges < 0) { adf_set_error("eqv2_export_graph: null argument"); return ADF_EINVAL; }
+    hipStream_t s = (hipStream_t)stream;
+    h->inc_valid = false;   // the workspaces now hold this batch's graph, not the kept forward's
+    ADF_TRY(eq_build_graph(h, b, s));
+    const int N = b->num_atoms;
+    int32_t E = 0;
+    ADF_HIP_CHECK(hipMemcpyAsync(&E, h->eptr + N, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    ADF_HIP_CHECK(hipStreamSynchronize(s));
+    *num_edges = E;
+    if (E < 0 || E > h->capE) { adf_set_error("eqv2_export_graph: edge capacity exceeded"); return ADF_EOVERFLOW; }
+    if (E > cap_edges) { adf_set_error("eqv2_export_graph: %d edges, the arrays hold %lld", E, (long long)cap_edges); return ADF_EOVERFLOW; }
+    ADF_HIP_CHECK(hipMemcpyAsync(eptr, h->eptr, sizeof(int32_t) * ((size_t)N + 1), hipMemcpyDeviceToDevice, s));
+    if (E > 0) {
+        ADF_HIP_CHECK(hipMemcpyAsync(src, h->e_src, sizeof(int32_t) * (size_t)E, hipMemcpyDeviceToDevice, s));
+        ADF_HIP_CHECK(hipMemcpyAsync(dst, h->e_dst, sizeof(int32_t) * (size_t)E, hipMemcpyDeviceToDevice, s));
+        ADF_HIP_CHECK(hipMemcpyAsync(vec, h->e_vec, sizeof(float) * 3 * (size_t)E, hipMemcpyDeviceToDevice, s));
+        ADF_HIP_CHECK(hipMemcpyAsync(wig, h->wig, sizeof(float) * (size_t)h->d.DR * (size_t)E, hipMemcpyDeviceToDevice, s));
+    }
+    return ADF_OK;
 }
 
 // ---------------------------------------------------------------------------------------------- counters / profile

@@ -301,7 +301,10 @@ class EqV2Host(nn.Module):
 
         return _IncompatibleKeys([k for k in res.missing_keys if k not in self._OPTIONAL_KEYS] + mismatched, unexpected)
 
-    def engine(self, device=None):
+    def engine(self, device=None, refresh: bool = True):
+        """``refresh=False`` (the training step, which reads the graph, the constant tables and the frozen ``atom_radii``
+        from the handle and nothing else): an existing engine is handed out without looking whether the weights changed;
+        the next ``refresh=True`` call binds them again."""
         from .eqv2_engine import EqV2Engine
 
         if device is None:
@@ -312,6 +315,8 @@ class EqV2Host(nn.Module):
         if self._engine is not None and self._engine.device != device:
             self._engine.close()
             self._engine = None
+        if self._engine is not None and not refresh:
+            return self._engine
         version = self._weights_version()
         if self._engine is None:
             self._engine = EqV2Engine(self, device)
@@ -379,6 +384,9 @@ class EquiformerV2S_OC20_DenoisingPos(EqV2Host):
         self.so3_denoising, self.FOR_denoising, self.sampling = so3_denoising, FOR_denoising, sampling
         self.energy_encoding = energy_encoding
         self.enforce_max_neighbors_strictly = enforce_max_neighbors_strictly
+        # stochastic regularisers: read by the training step in model.train() only (eqv2_train_step.py); the force blocks
+        # are built with alpha_drop 0 in the reference (equiformer_v2_oc20.py:376-391)
+        self.alpha_drop, self.drop_path_rate, self.proj_drop = float(alpha_drop), float(drop_path_rate), float(proj_drop)
         lmax, mmax = self.lmax_list[0], self.mmax_list[0]
         normal = weight_init == "normal"
         ecl = [self.NUM_GAUSSIANS, edge_channels, edge_channels]

@@ -95,6 +95,7 @@ class EqV2Engine(Engine):
             _lib.check(self.lib.adf_eqv2_set_constants(self.handle, ptr(t["jd"]), ptr(t["to_red"]), ptr(t["from_red"]),
                                                        ptr(t["to_full"]), ptr(t["from_full"])))
         self._edges_keepalive = None
+        self._ext_edges = 0        # edges of the list set_edges last handed over (0: the engine builds its own graph)
         self._energy_keepalive = None
         self._energy_mode = None   # what adf_eqv2_set_system_energy last received: None (never), "zeros", "given"
         self.bind_weights()
@@ -187,6 +188,7 @@ class EqV2Engine(Engine):
         K-th neighbours is implementation-defined."""
         if edge_index is None:
             _lib.check(self.lib.adf_eqv2_set_edges(self.handle, 0, None, None, None, 1, self._stream()))
+            self._ext_edges = 0
             return
         dst = edge_index[1].to(self.device, torch.int32).contiguous()
         src = edge_index[0].to(self.device, torch.int32).contiguous()
@@ -197,6 +199,32 @@ class EqV2Engine(Engine):
         with torch.cuda.device(self.device):
             _lib.check(self.lib.adf_eqv2_set_edges(self.handle, int(dst.numel()), src.data_ptr(), dst.data_ptr(),
                                                    vec.data_ptr(), maxdeg, self._stream()))
+        self._ext_edges = int(dst.numel())
+
+    def export_graph(self, data, prep: Optional[PreparedBatch] = None):
+        """The graph of ``data`` as the forward builds it (``adf_eqv2_export_graph``; the list of ``set_edges`` while one is
+        in force) -> (eptr [N+1], src [E], dst [E], vec [E,3], wig [E,DR]): edges sorted by target, int32 indices, ``wig``
+        the Wigner rows kept per edge.  The counterpart of ``PaiNNEngine.export_graph`` for the training step."""
+        if prep is None:
+            prep = self.prepare(data)
+        pos = data.pos.to(torch.float32).contiguous()
+        N, dev = prep.num_atoms, self.device
+        cap = max(self._ext_edges or N * int(self.model.max_neighbors), 1)
+        DR = sum((2 * min(l, self.mmax) + 1) * (2 * l + 1) for l in range(self.lmax + 1))
+        eptr = torch.empty(N + 1, dtype=torch.int32, device=dev)
+        src = torch.empty(cap, dtype=torch.int32, device=dev)
+        dst = torch.empty(cap, dtype=torch.int32, device=dev)
+        vec = torch.empty(cap, 3, dtype=torch.float32, device=dev)
+        wig = torch.empty(cap, DR, dtype=torch.float32, device=dev)
+        n = C.c_int64(0)
+        desc = prep.desc(pos)
+        with torch.cuda.device(dev):
+            _lib.check(self.lib.adf_eqv2_export_graph(self.handle, C.byref(desc), cap, eptr.data_ptr(), src.data_ptr(),
+                                                      dst.data_ptr(), vec.data_ptr(), wig.data_ptr(), C.byref(n),
+                                                      self._stream()))
+        self.check_flags()
+        E = int(n.value)
+        return eptr, src[:E], dst[:E], vec[:E], wig[:E]
 
     # ------------------------------------------------------------------ calls
     def forward_prepared(self, prep: PreparedBatch, pos: torch.Tensor, f1: torch.Tensor, f2: Optional[torch.Tensor],

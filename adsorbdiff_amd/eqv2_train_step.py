@@ -1,0 +1,671 @@
+"""Score-matching training step of the EquiformerV2 denoiser on the device.
+
+The counterpart of ``train_step.PaiNNTrainStep`` for ``EquiformerV2S_OC20_DenoisingPos``: the same contract
+(``zero_grad``, ``loss_and_grad(batch, targets, grads_ready)`` accumulating into ``param.grad``, ``last_outputs``), so the
+trainer, the optimizers, the EMA, the gradient reducer and the checkpoints work on it unchanged.
+
+Where the arithmetic runs:
+
+* EDGE side (E rows; everything ``oracle/eqv2_oracle.py::attention_block`` does per edge, and the edge-degree embedding):
+  hand-written HIP behind the stateless ``adf_op_eq_*`` entries (csrc/eqv2_train.hip), forward and backward, on the
+  graph ``EqV2Engine.export_graph`` hands out.  Each entry is wrapped here in a ``torch.autograd.Function`` that owns its
+  saved activations; torch only chains them.
+* NODE side (N rows: ``norm_sh``, SO(3) linears, the feed-forward network, the element embedding, the conditional
+  model's energy term): plain torch operations on the device under autograd, written so that no backward uses a float
+  atomic (no gather by index: per-degree slices, a one-hot product for the per-system term, the ordered embedding
+  backward ``adf_op_embed_bwd_ordered``).
+
+Exact f32 throughout, no float atomics: two calls on the same input give the same bits.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, List, Optional
+
+import torch
+
+from . import lib as _lib
+from . import so3_math
+from .so3_tables import Igso3Tables
+
+
+# ------------------------------------------------------------------------------------------------------- graph + entries
+class EqGraph:
+    """The engine's graph of one batch plus the source-sorted permutation the rotate-in backward sums along."""
+
+    def __init__(self, engine, data, prep) -> None:
+        self.prep = prep
+        self.eptr, self.src, self.dst, self.vec, self.wig = engine.export_graph(data, prep)
+        self.N, self.E = prep.num_atoms, int(self.src.numel())
+        self.Z = prep.atomic_numbers                                  # [N] int32
+        dev = self.src.device
+        order = torch.sort(self.src.long(), stable=True).indices       # ties keep the list order
+        self.sperm = order.to(torch.int32).contiguous()
+        self.sptr = torch.zeros(self.N + 1, dtype=torch.int32, device=dev)
+        self.sptr[1:] = torch.cumsum(torch.bincount(self.src.long(), minlength=self.N), 0).to(torch.int32)
+        # 1-based element of every edge's source / target: the row lists of adf_op_embed_bwd_ordered
+        self.zs1 = (self.Z[self.src.long()] + 1).contiguous()
+        self.zt1 = (self.Z[self.dst.long()] + 1).contiguous()
+        self.ones = None
+
+
+class EqOps:
+    """Typed wrappers over the adf_op_eq_* entries for one engine (dimensions and constant tables come from its handle)."""
+
+    def __init__(self, engine) -> None:
+        m = engine.model
+        self.engine, self.lib, self.h, self.dev = engine, engine.lib, engine.handle, engine.device
+        self.L, self.M, self.C = engine.lmax, engine.mmax, int(m.sphere_channels)
+        L, M = self.L, self.M
+        self.S = (L + 1) ** 2
+        self.Sr = sum(2 * min(l, M) + 1 for l in range(L + 1))
+        self.RW = sum(L - mm + 1 for mm in range(M + 1))
+        self.rbase = [0] * (M + 1)
+        r = L + 1
+        for mm in range(1, M + 1):
+            self.rbase[mm] = r
+            r += 2 * (L - mm + 1)
+        self.NH, self.A, self.V = int(m.num_heads), int(m.attn_alpha_channels), int(m.attn_value_channels)
+        self.Hd, self.EC, self.NB = int(m.attn_hidden_channels), int(m.edge_channels), int(m.NUM_GAUSSIANS)
+        self.NE = int(m.max_num_elements)
+        self._scratch = torch.empty(0, device=self.dev)
+
+    def s(self):
+        return C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
+
+    def new(self, *shape) -> torch.Tensor:
+        return torch.empty(*shape, dtype=torch.float32, device=self.dev)
+
+    def zeros(self, *shape) -> torch.Tensor:
+        return torch.zeros(*shape, dtype=torch.float32, device=self.dev)
+
+    def scratch(self, n: int) -> torch.Tensor:
+        if self._scratch.numel() < n:
+            self._scratch = torch.empty(int(n * 1.25) + 1024, device=self.dev)
+        return self._scratch
+
+    @staticmethod
+    def _p(t: Optional[torch.Tensor], off: int = 0):
+        return None if t is None else t.data_ptr() + 4 * off
+
+    # ---- dense rows
+    def linear(self, A, W, bias, Cm, M, N, K, a_off=0, lda=None, w_off=0, ldw=None, b_off=0, c_off=0, ldc=None, acc=False):
+        _lib.check(self.lib.adf_op_eq_linear_fwd(self._p(A, a_off), lda or K, self._p(W, w_off), ldw or K, self._p(bias, b_off),
+                                                 self._p(Cm, c_off), ldc or N, 1 if acc else 0, M, N, K, self.s()))
+        return Cm
+
+    def linear_bwd(self, A, W, dC, M, N, K, dA=None, dW=None, db=None, a_off=0, lda=None, w_off=0, ldw=None, c_off=0, ldc=None,
+                   da_off=0, ldda=None, acc_dA=False, dw_off=0, lddw=None, db_off=0):
+        _lib.check(self.lib.adf_op_eq_linear_bwd(
+            self._p(A, a_off), lda or K, self._p(W, w_off), ldw or K, self._p(dC, c_off), ldc or N, self._p(dA, da_off),
+            ldda or K, 1 if acc_dA else 0, self._p(dW, dw_off), lddw or K, self._p(db, db_off), M, N, K, self.s()))
+
+    def silu(self, x):
+        y = torch.empty_like(x)
+        _lib.check(self.lib.adf_op_eq_silu_fwd(x.data_ptr(), y.data_ptr(), x.numel(), self.s()))
+        return y
+
+    def silu_bwd(self, x, dy):
+        dx = torch.empty_like(x)
+        _lib.check(self.lib.adf_op_eq_silu_bwd(x.data_ptr(), dy.data_ptr(), dx.data_ptr(), x.numel(), self.s()))
+        return dx
+
+    def layernorm(self, x, w, b):
+        rows, H = x.shape
+        y, stats = torch.empty_like(x), self.new(rows, 2)
+        _lib.check(self.lib.adf_op_layernorm_fwd(x.data_ptr(), w.data_ptr(), b.data_ptr(), y.data_ptr(), stats.data_ptr(), rows,
+                                                 H, self.s()))
+        return y, stats
+
+    def layernorm_bwd(self, x, w, stats, dy):
+        rows, H = x.shape
+        dx, dw, db = torch.zeros_like(x), self.new(H), self.new(H)
+        _lib.check(self.lib.adf_op_layernorm_bwd(x.data_ptr(), w.data_ptr(), stats.data_ptr(), dy.data_ptr(), dx.data_ptr(),
+                                                 dw.data_ptr(), db.data_ptr(), rows, H, self.scratch(1024 * H).data_ptr(),
+                                                 self.s()))
+        return dx, dw, db
+
+    def embed_bwd(self, dx, idx1, rows):
+        """demb [rows, H] with demb[idx1[n] - 1] = sum of dx[n] in a fixed order; rows of absent indices stay exactly zero."""
+        n, H = dx.shape
+        demb = self.zeros(rows, H)
+        if n:
+            sc = self.scratch(int(self.lib.adf_op_embed_bwd_ordered_scratch(n, H, rows)))
+            _lib.check(self.lib.adf_op_embed_bwd_ordered(dx.data_ptr(), idx1.data_ptr(), demb.data_ptr(), n, H, rows,
+                                                         sc.data_ptr(), self.s()))
+        return demb
+
+    def edge_scalars(self, g: EqGraph, semb, temb):
+        out = self.new(g.E, self.NB + 2 * self.EC)
+        _lib.check(self.lib.adf_op_eq_edge_scalars(self.h, g.Z.data_ptr(), g.src.data_ptr(), g.dst.data_ptr(), g.vec.data_ptr(),
+                                                   semb.data_ptr(), temb.data_ptr(), g.E, out.data_ptr(), self.s()))
+        return out
+
+
+def _c(t: torch.Tensor) -> torch.Tensor:
+    return t if t.is_contiguous() else t.contiguous()
+
+
+# ------------------------------------------------------------------------------------------------------- edge operators
+class RadialMLP(torch.autograd.Function):
+    """Linear, LayerNorm, SiLU, Linear, LayerNorm, SiLU, Linear on the E rows [basis | semb[Z_src] | temb[Z_dst]]
+    (oracle ``radial_mlp``); ``pad``: row stride of the output (> its width: the columns behind it are zero)."""
+
+    @staticmethod
+    def forward(ctx, ops: EqOps, g: EqGraph, pad, semb, temb, W0, b0, w1, b1, W3, b3, w4, b4, W6, b6):
+        E, EC, IN, OUT = g.E, ops.EC, ops.NB + 2 * ops.EC, W6.shape[0]
+        scal = ops.edge_scalars(g, semb, temb)
+        h0 = ops.linear(scal, W0, b0, ops.new(E, EC), E, EC, IN)
+        y1, st1 = ops.layernorm(h0, w1, b1)
+        a1 = ops.silu(y1)
+        h3 = ops.linear(a1, W3, b3, ops.new(E, EC), E, EC, EC)
+        y4, st4 = ops.layernorm(h3, w4, b4)
+        a4 = ops.silu(y4)
+        ld = int(pad) if pad else OUT
+        out = ops.zeros(E, ld) if ld > OUT else ops.new(E, ld)
+        ops.linear(a4, W6, b6, out, E, OUT, EC, ldc=ld)
+        ctx.ops, ctx.g, ctx.ld = ops, g, ld
+        ctx.save_for_backward(semb, temb, W0, w1, W3, w4, W6, h0, st1, y1, a1, h3, st4, y4, a4)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        ops, g, ld = ctx.ops, ctx.g, ctx.ld
+        semb, temb, W0, w1, W3, w4, W6, h0, st1, y1, a1, h3, st4, y4, a4 = ctx.saved_tensors
+        E, EC, NB, OUT = g.E, ops.EC, ops.NB, W6.shape[0]
+        IN = NB + 2 * EC
+        dout = _c(dout)
+        dW6, db6 = torch.zeros_like(W6), ops.zeros(OUT)
+        da4 = ops.new(E, EC)
+        ops.linear_bwd(a4, W6, dout, E, OUT, EC, dA=da4, dW=dW6, db=db6, ldc=ld)
+        dh3, dw4, db4 = ops.layernorm_bwd(h3, w4, st4, ops.silu_bwd(y4, da4))
+        dW3, db3 = torch.zeros_like(W3), ops.zeros(EC)
+        da1 = ops.new(E, EC)
+        ops.linear_bwd(a1, W3, dh3, E, EC, EC, dA=da1, dW=dW3, db=db3)
+        dh0, dw1, db1 = ops.layernorm_bwd(h0, w1, st1, ops.silu_bwd(y1, da1))
+        scal = ops.edge_scalars(g, semb, temb)            # formed again, not kept: 4 (NB + 2 EC) bytes per edge
+        dW0, db0 = torch.zeros_like(W0), ops.zeros(EC)
+        ops.linear_bwd(scal, W0, dh0, E, EC, IN, dW=dW0, db=db0)
+        demb = ops.new(E, 2 * EC)                         # the embedding columns of d scal only
+        ops.linear_bwd(None, W0, dh0, E, EC, 2 * EC, dA=demb, w_off=NB, ldw=IN)
+        dsemb = ops.embed_bwd(_c(demb[:, :EC]), g.zs1, ops.NE)
+        dtemb = ops.embed_bwd(_c(demb[:, EC:]), g.zt1, ops.NE)
+        return None, None, None, dsemb, dtemb, dW0, db0, dw1, db1, dW3, db3, dw4, db4, dW6, db6
+
+
+class RotateIn(torch.autograd.Function):
+    """[x[src] | x[dst]] into the edges' frames (rows |m| <= mmax, order-major) times the radial weights."""
+
+    @staticmethod
+    def forward(ctx, ops: EqOps, g: EqGraph, x, radial):
+        x, radial = _c(x), _c(radial)
+        out = ops.new(g.E, ops.Sr, 2 * ops.C)
+        _lib.check(ops.lib.adf_op_eq_rotate_in_fwd(ops.h, x.data_ptr(), g.src.data_ptr(), g.dst.data_ptr(), g.wig.data_ptr(),
+                                                   radial.data_ptr(), g.E, out.data_ptr(), ops.s()))
+        ctx.ops, ctx.g = ops, g
+        ctx.save_for_backward(x, radial)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        ops, g = ctx.ops, ctx.g
+        x, radial = ctx.saved_tensors
+        dout = _c(dout)
+        dradial, dx = torch.empty_like(radial), torch.empty_like(x)
+        _lib.check(ops.lib.adf_op_eq_rotate_in_bwd(
+            ops.h, x.data_ptr(), g.eptr.data_ptr(), g.src.data_ptr(), g.dst.data_ptr(), g.wig.data_ptr(), radial.data_ptr(),
+            dout.data_ptr(), g.sptr.data_ptr(), g.sperm.data_ptr(), g.N, g.E, dradial.data_ptr(), dx.data_ptr(), ops.s()))
+        return None, None, dx, dradial
+
+
+def _so2_block_weight(W, h, k):
+    """[[Wr, -Wi], [Wi, Wr]] of fc.weight = [Wr; Wi]: the (+m, -m) pair mixed like a complex product as ONE map on
+    [x(+m) | x(-m)] (plus = Wr x+ - Wi x-, minus = Wi x+ + Wr x-; so2_ops.py:52-66)."""
+    Wr, Wi = W[:h], W[h:]
+    return torch.cat([torch.cat([Wr, -Wi], 1), torch.cat([Wi, Wr], 1)], 0).contiguous()
+
+
+class SO2Conv(torch.autograd.Function):
+    """SO(2) convolution on order-major coefficients x [E, S_r, cin] -> out [E, S_r, cout] and the `extra` scalar outputs
+    [E, extra] of fc_m0 (oracle ``so2_conv`` without the radial weighting, which RotateIn applies)."""
+
+    @staticmethod
+    def forward(ctx, ops: EqOps, x, extra, cout, W0, b0, *Wm):
+        x = _c(x)
+        E, Sr, cin = x.shape
+        L, M = ops.L, ops.M
+        K0 = (L + 1) * cin
+        out = ops.new(E, Sr, cout)
+        ex = ops.new(E, max(extra, 1))
+        if extra:
+            ops.linear(x, W0, b0, ex, E, extra, K0, lda=Sr * cin)
+        ops.linear(x, W0, b0, out, E, (L + 1) * cout, K0, lda=Sr * cin, w_off=extra * K0, b_off=extra, ldc=Sr * cout)
+        Wbs = []
+        for mm in range(1, M + 1):
+            nm = L - mm + 1
+            h, k = nm * cout, nm * cin
+            Wb = _so2_block_weight(Wm[mm - 1], h, k)
+            Wbs.append(Wb)
+            ops.linear(x, Wb, None, out, E, 2 * h, 2 * k, a_off=ops.rbase[mm] * cin, lda=Sr * cin, c_off=ops.rbase[mm] * cout,
+                       ldc=Sr * cout)
+        ctx.ops, ctx.extra, ctx.cout = ops, extra, cout
+        ctx.save_for_backward(x, W0, *Wbs)
+        ctx.mark_non_differentiable(*([] if extra else [ex]))
+        return out, ex
+
+    @staticmethod
+    def backward(ctx, dout, dex):
+        ops, extra, cout = ctx.ops, ctx.extra, ctx.cout
+        x, W0, *Wbs = ctx.saved_tensors
+        E, Sr, cin = x.shape
+        L, M = ops.L, ops.M
+        K0 = (L + 1) * cin
+        dout = _c(dout)
+        dx = torch.empty_like(x)
+        dW0, db0 = torch.zeros_like(W0), ops.zeros(W0.shape[0])
+        ops.linear_bwd(x, W0, dout, E, (L + 1) * cout, K0, dA=dx, dW=dW0, db=db0, lda=Sr * cin, w_off=extra * K0, ldc=Sr * cout,
+                       ldda=Sr * cin, dw_off=extra * K0, db_off=extra)
+        if extra and dex is not None:
+            dex = _c(dex)
+            ops.linear_bwd(x, W0, dex, E, extra, K0, dA=dx, dW=dW0, db=db0, lda=Sr * cin, ldda=Sr * cin, acc_dA=True)
+        dWm = []
+        for mm in range(1, M + 1):
+            nm = L - mm + 1
+            h, k = nm * cout, nm * cin
+            dWb = torch.zeros_like(Wbs[mm - 1])
+            ops.linear_bwd(x, Wbs[mm - 1], dout, E, 2 * h, 2 * k, dA=dx, dW=dWb, a_off=ops.rbase[mm] * cin, lda=Sr * cin,
+                           c_off=ops.rbase[mm] * cout, ldc=Sr * cout, da_off=ops.rbase[mm] * cin, ldda=Sr * cin)
+            dWm.append(torch.cat([dWb[:h, :k] + dWb[h:, k:], dWb[h:, :k] - dWb[:h, k:]], 0))
+        return (None, dx, None, None, dW0, db0, *dWm)
+
+
+class S2Act(torch.autograd.Function):
+    """Separable S2 activation: SiLU on the gate columns of `ex` for l = 0, point-wise SiLU on the reduced grid for the rest."""
+
+    @staticmethod
+    def forward(ctx, ops: EqOps, y, ex, gate_off):
+        y, ex = _c(y), _c(ex)
+        E, Sr, W = y.shape
+        out = torch.empty_like(y)
+        _lib.check(ops.lib.adf_op_eq_s2act_fwd(ops.h, y.data_ptr(), ops._p(ex, gate_off), ex.shape[1], W, E, out.data_ptr(),
+                                               ops.s()))
+        ctx.ops, ctx.gate_off = ops, gate_off
+        ctx.save_for_backward(y, ex)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        ops, gate_off = ctx.ops, ctx.gate_off
+        y, ex = ctx.saved_tensors
+        E, Sr, W = y.shape
+        dout = _c(dout)
+        dy, dex = torch.empty_like(y), torch.zeros_like(ex)
+        _lib.check(ops.lib.adf_op_eq_s2act_bwd(ops.h, y.data_ptr(), ops._p(ex, gate_off), ex.shape[1], dout.data_ptr(), W, E,
+                                               dy.data_ptr(), ops._p(dex, gate_off), ex.shape[1], ops.s()))
+        return None, dy, dex, None
+
+
+class AttnWeights(torch.autograd.Function):
+    """LayerNorm over a head's alpha channels, smooth leaky ReLU, dot with alpha_dot, softmax over a target's edges, dropout
+    mask -> alpha [E, heads].  `ex` [E, extra]: the alpha channels are its first heads * alpha columns."""
+
+    @staticmethod
+    def forward(ctx, ops: EqOps, g: EqGraph, ex, ln_w, ln_b, adot, mask):
+        ex = _c(ex)
+        soft, alpha = ops.new(g.E, ops.NH), ops.new(g.E, ops.NH)
+        mask = None if mask is None else _c(mask.to(torch.float32))
+        _lib.check(ops.lib.adf_op_eq_alpha_fwd(ops.h, ex.data_ptr(), ex.shape[1], ln_w.data_ptr(), ln_b.data_ptr(),
+                                               adot.data_ptr(), g.eptr.data_ptr(), ops._p(mask), g.N, g.E, soft.data_ptr(),
+                                               alpha.data_ptr(), ops.s()))
+        ctx.ops, ctx.g, ctx.mask = ops, g, mask
+        ctx.save_for_backward(ex, ln_w, ln_b, adot, soft)
+        return alpha
+
+    @staticmethod
+    def backward(ctx, dalpha):
+        ops, g, mask = ctx.ops, ctx.g, ctx.mask
+        ex, ln_w, ln_b, adot, soft = ctx.saved_tensors
+        dalpha = _c(dalpha)
+        HA = ops.NH * ops.A
+        dex = torch.zeros_like(ex)
+        dw, db, dadot = torch.zeros_like(ln_w), torch.zeros_like(ln_b), torch.zeros_like(adot)
+        need = 3 * g.E * ops.NH + (3 * ((g.E + 255) // 256) + 2) * HA
+        sc = ops.scratch(need)
+        _lib.check(ops.lib.adf_op_eq_alpha_bwd(
+            ops.h, ex.data_ptr(), ex.shape[1], ln_w.data_ptr(), ln_b.data_ptr(), adot.data_ptr(), g.eptr.data_ptr(),
+            ops._p(mask), soft.data_ptr(), dalpha.data_ptr(), g.N, g.E, dex.data_ptr(), ex.shape[1], dw.data_ptr(),
+            db.data_ptr(), dadot.data_ptr(), sc.data_ptr(), sc.numel(), ops.s()))
+        return None, None, dex, dw, db, dadot, None
+
+
+class RotateOut(torch.autograd.Function):
+    """alpha-weighted rotation back (D^T with the truncation rescale) summed over a target's edges -> [N, S, heads * V]."""
+
+    @staticmethod
+    def forward(ctx, ops: EqOps, g: EqGraph, z, alpha, NH, V, only_l):
+        z, alpha = _c(z), _c(alpha)
+        agg = ops.new(g.N, ops.S, NH * V)
+        _lib.check(ops.lib.adf_op_eq_rotate_out_fwd(ops.h, z.data_ptr(), alpha.data_ptr(), NH, V, g.eptr.data_ptr(),
+                                                    g.wig.data_ptr(), only_l, g.N, agg.data_ptr(), ops.s()))
+        ctx.ops, ctx.g, ctx.dims = ops, g, (NH, V, only_l)
+        ctx.save_for_backward(z, alpha)
+        return agg
+
+    @staticmethod
+    def backward(ctx, dagg):
+        ops, g, (NH, V, only_l) = ctx.ops, ctx.g, ctx.dims
+        z, alpha = ctx.saved_tensors
+        dagg = _c(dagg)
+        dz, dalpha = torch.empty_like(z), torch.empty_like(alpha)
+        _lib.check(ops.lib.adf_op_eq_rotate_out_bwd(ops.h, z.data_ptr(), alpha.data_ptr(), NH, V, g.dst.data_ptr(),
+                                                    g.wig.data_ptr(), dagg.data_ptr(), only_l, g.E, dz.data_ptr(),
+                                                    dalpha.data_ptr(), ops.s()))
+        return None, None, dz, dalpha, None, None, None
+
+
+class OrderedEmbedding(torch.autograd.Function):
+    """weight[Z] with the backward summed in a fixed order (``adf_op_embed_bwd_ordered``); absent rows get exactly zero."""
+
+    @staticmethod
+    def forward(ctx, ops: EqOps, weight, Z):
+        ctx.ops, ctx.rows = ops, weight.shape[0]
+        ctx.save_for_backward(Z)
+        return weight[Z.long()]
+
+    @staticmethod
+    def backward(ctx, dx):
+        (Z,) = ctx.saved_tensors
+        return None, ctx.ops.embed_bwd(_c(dx), (Z + 1).contiguous(), ctx.rows), None
+
+
+# ------------------------------------------------------------------------------------------------------- node side (torch)
+def so3_linear(weight, bias, x, L: int):
+    """One weight matrix per degree, bias on l = 0 (so3.py:694-745); per-degree slices, no gather."""
+    out = []
+    for l in range(L + 1):
+        y = x[:, l * l:(l + 1) ** 2] @ weight[l].t()
+        out.append(y + bias if l == 0 else y)
+    return torch.cat(out, 1)
+
+
+def norm_sh(affine, w0, b0, x, L: int, eps: float = 1e-5):
+    """layer_norm_sh (layer_norm.py:129-250): LayerNorm on l = 0, one degree-balanced RMS over l > 0."""
+    x0 = x[:, :1]
+    mu = x0.mean(-1, keepdim=True)
+    var = ((x0 - mu) ** 2).mean(-1, keepdim=True)
+    out = [(x0 - mu) * torch.rsqrt(var + eps) * w0 + b0]
+    ms = 0.0
+    for l in range(1, L + 1):
+        ms = ms + (x[:, l * l:(l + 1) ** 2] ** 2).sum(1) / ((2 * l + 1) * L)     # [N, C]
+    scale = torch.rsqrt(ms.mean(1) + eps)[:, None, None]
+    for l in range(1, L + 1):
+        out.append(x[:, l * l:(l + 1) ** 2] * scale * affine[l - 1][None, None, :])
+    return torch.cat(out, 1)
+
+
+# ------------------------------------------------------------------------------------------------------- the step
+def _rad_params(P, pre):
+    return [P[pre + f"net.{i}.{k}"] for i in (0, 1, 3, 4, 6) for k in ("weight", "bias")]
+
+
+def mask_generator(device, seed: int, step: int) -> torch.Generator:
+    """The device generator of a step's dropout / drop-path draws: a function of (seed, step) alone."""
+    gen = torch.Generator(device=device)
+    gen.manual_seed((int(seed) * 1000003 + int(step) * 7919 + 12345) & 0x7FFFFFFFFFFFFFFF)
+    return gen
+
+
+class EqV2TrainStep:
+    """loss + gradients of the score-matching objective for a mirror ``EquiformerV2S_OC20_DenoisingPos`` on a ROCm device."""
+
+    # no path to the loss (equiformer_v2_denoising.py:300-318): the reference's autograd leaves them at None
+    UNUSED_PREFIXES = ("energy_block.",)
+
+    def __init__(self, model, device="cuda:0", igso3: Optional[Igso3Tables] = None) -> None:
+        from .equiformer_v2_denoising import EquiformerV2S_OC20_DenoisingPos
+
+        if not isinstance(model, EquiformerV2S_OC20_DenoisingPos):
+            raise NotImplementedError(f"EqV2TrainStep trains EquiformerV2S_OC20_DenoisingPos, got {type(model).__name__} "
+                                      "(training the EquiformerV2 S2EF force field is not offered)")
+        self.model = model
+        self.dev = torch.device(device)
+        if self.dev.type != "cuda":
+            raise RuntimeError("EqV2TrainStep needs a ROCm device (the HIP path has no CPU fallback)")
+        if float(getattr(model, "proj_drop", 0.0)) != 0.0:
+            raise NotImplementedError("proj_drop != 0 is not offered by the EquiformerV2 training step")
+        self.two_heads = bool(model.so3_denoising)
+        self.igso3 = (igso3 or Igso3Tables.shared()) if self.two_heads else igso3
+        self.lib = _lib.load()
+        self.ordered_embedding_backward = True   # always: kept for the trainer, which sets it on every step object
+        self.mask_seed, self.mask_step = 0, 0
+        self.last_outputs = None
+        self.last_masks = None
+        L, M = int(model.lmax_list[0]), int(model.mmax_list[0])
+        t = so3_math.device_tables(L, M, int(model.grid_resolution))
+        self._to_full = torch.from_numpy(t["to_full"]).to(self.dev)      # [G, S]
+        self._from_full = torch.from_numpy(t["from_full"]).to(self.dev)
+        self._scratch = torch.empty(0, device=self.dev)
+
+    # ------------------------------------------------------------------ helpers
+    def _unused(self, name: str) -> bool:
+        if name.startswith(self.UNUSED_PREFIXES) or name == "atom_radii":
+            return True
+        return not self.two_heads and name.startswith("force_block2.")
+
+    def zero_grad(self) -> None:
+        for name, p in self.model.named_parameters():
+            if not p.requires_grad:
+                continue
+            if self._unused(name):
+                p.grad = None
+            elif p.grad is None:
+                p.grad = torch.zeros_like(p)
+            else:
+                p.grad.zero_()
+
+    def groups(self) -> List[List[str]]:
+        """Parameter names in the order their gradients become final: force blocks, blocks last to first, embeddings."""
+        names = [n for n, p in self.model.named_parameters() if p.requires_grad and not self._unused(n)]
+        out = [[n for n in names if n.startswith(("force_block.", "force_block2.", "norm."))]]
+        for i in range(self.model.num_layers - 1, -1, -1):
+            out.append([n for n in names if n.startswith(f"blocks.{i}.")])
+        seen = {n for grp in out for n in grp}
+        out.append([n for n in names if n not in seen])
+        return [grp for grp in out if grp]
+
+    def draw_masks(self, g: EqGraph, B: int) -> Optional[dict]:
+        """The step's dropout masks from (mask_seed, mask_step): ``alpha`` [layers][E, heads] and ``path`` [layers, 2, B] of
+        0 / 1 (1 = kept), or None when both rates are 0."""
+        m = self.model
+        pa, pp = float(getattr(m, "alpha_drop", 0.0)), float(getattr(m, "drop_path_rate", 0.0))
+        if pa == 0.0 and pp == 0.0:
+            return None
+        gen = mask_generator(self.dev, self.mask_seed, self.mask_step)
+        nl = m.num_layers
+        path = (torch.rand(nl, 2, B, device=self.dev, generator=gen) >= pp).to(torch.float32)
+        alpha = [(torch.rand(g.E, m.num_heads, device=self.dev, generator=gen) >= pa).to(torch.float32) for _ in range(nl)]
+        return {"alpha": alpha, "path": path}
+
+    # ------------------------------------------------------------------ forward pieces
+    def _attention(self, ops: EqOps, g: EqGraph, P, pre: str, x, mask, only_l: int):
+        """SO2EquivariantGraphAttention (oracle ``attention_block``) -> [N, S, out_channels]."""
+        NH, A, V, Hd = ops.NH, ops.A, ops.V, ops.Hd
+        radial = RadialMLP.apply(ops, g, 0, P[pre + "source_embedding.weight"], P[pre + "target_embedding.weight"],
+                                 *_rad_params(P, pre + "so2_conv_1.rad_func."))
+        msg = RotateIn.apply(ops, g, x, radial)
+        extra = NH * A + Hd
+        msg, ex = SO2Conv.apply(ops, msg, extra, Hd, P[pre + "so2_conv_1.fc_m0.weight"], P[pre + "so2_conv_1.fc_m0.bias"],
+                                *[P[pre + f"so2_conv_1.so2_m_conv.{k}.fc.weight"] for k in range(ops.M)])
+        msg = S2Act.apply(ops, msg, ex, NH * A)
+        msg, _ = SO2Conv.apply(ops, msg, 0, NH * V, P[pre + "so2_conv_2.fc_m0.weight"], P[pre + "so2_conv_2.fc_m0.bias"],
+                               *[P[pre + f"so2_conv_2.so2_m_conv.{k}.fc.weight"] for k in range(ops.M)])
+        alpha = AttnWeights.apply(ops, g, ex, P[pre + "alpha_norm.weight"], P[pre + "alpha_norm.bias"], P[pre + "alpha_dot"],
+                                  mask)
+        agg = RotateOut.apply(ops, g, msg, alpha, NH, V, only_l)
+        if only_l >= 0:   # the force blocks: the l = 1 rows alone reach the output
+            sl = slice(only_l * only_l, (only_l + 1) ** 2)
+            return agg[:, sl] @ P[pre + "proj.weight"][only_l].t()
+        return so3_linear(P[pre + "proj.weight"], P[pre + "proj.bias"], agg, ops.L)
+
+    def _feed_forward(self, ops: EqOps, P, pre: str, x):
+        F = torch.nn.functional
+        gate = F.silu(x[:, :1] @ P[pre + "scalar_mlp.0.weight"].t() + P[pre + "scalar_mlp.0.bias"])
+        h = so3_linear(P[pre + "so3_linear_1.weight"], P[pre + "so3_linear_1.bias"], x, ops.L)
+        gr = torch.einsum("gi,nic->ngc", self._to_full, h)
+        gr = F.silu(F.silu(gr @ P[pre + "grid_mlp.0.weight"].t()) @ P[pre + "grid_mlp.2.weight"].t()) @ P[pre + "grid_mlp.4.weight"].t()
+        h = torch.einsum("gi,ngc->nic", self._from_full, gr)
+        h = torch.cat([gate, h[:, 1:]], 1)
+        return so3_linear(P[pre + "so3_linear_2.weight"], P[pre + "so3_linear_2.bias"], h, ops.L)
+
+    def _energy_term(self, P, batch, prep):
+        """The conditional model's per-atom term (equiformer_v2_denoising.py:258-264): the layer runs in fp16 in the
+        reference and in the inference forward, so the VALUE is fp16(fp16(e) fp16(W) + fp16(b)); the gradient is the one of
+        e W + b (the rounding is passed straight through)."""
+        m = self.model
+        B, N = prep.num_systems, prep.num_atoms
+        W, b = P["energy_embedding.weight"].reshape(-1), P["energy_embedding.bias"]
+        if m.sampling:
+            e = torch.zeros(B, device=self.dev)
+        else:
+            energy = getattr(batch, "energy", None)
+            if energy is None:
+                raise ValueError("the conditional EquiformerV2 (energy_encoding='scalar') with sampling=False reads "
+                                 "data.energy (one value per system); the batch has none")
+            e = torch.as_tensor(energy).to(self.dev, torch.float32).reshape(-1)
+            if e.numel() != B:
+                raise ValueError(f"data.energy has {e.numel()} values for {B} systems")
+        t = e[:, None] * W[None, :] + b[None, :]
+        t16 = (e.half().float()[:, None] * W.detach().half().float()[None, :] + b.detach().half().float()[None, :]).half().float()
+        t = t + (t16 - t).detach()
+        onehot = torch.zeros(N, B, device=self.dev)
+        onehot[torch.arange(N, device=self.dev), prep.batch.long()] = 1.0
+        return onehot @ t       # a product, not a gather: its backward needs no float atomic
+
+    def forward(self, batch, masks=None):
+        """The training forward -> (outputs [(N,3)] per head, graph, masks in force)."""
+        m = self.model
+        eng = m.engine(self.dev, refresh=False)
+        ops = EqOps(eng)
+        prep = eng.prepare(batch)
+        g = EqGraph(eng, batch, prep)
+        P = dict(m.named_parameters())
+        N, B, L, C_ = g.N, prep.num_systems, ops.L, ops.C
+        training = bool(m.training)
+        if not training:
+            masks = None
+        elif masks is None:
+            masks = self.draw_masks(g, B)
+        pa, pp = float(getattr(m, "alpha_drop", 0.0)), float(getattr(m, "drop_path_rate", 0.0))
+        self.last_masks = masks
+        # node embedding: element embedding (+ energy term) on l = 0, plus the edge-degree embedding
+        x0 = OrderedEmbedding.apply(ops, P["sphere_embedding.weight"], g.Z)
+        if getattr(m, "energy_embedding", None) is not None:
+            x0 = x0 + self._energy_term(P, batch, prep)
+        pre = "edge_degree_embedding."
+        m0 = RadialMLP.apply(ops, g, ops.Sr * C_, P[pre + "source_embedding.weight"], P[pre + "target_embedding.weight"],
+                             *_rad_params(P, pre + "rad_func."))
+        if g.ones is None:
+            g.ones = torch.ones(g.E, 1, device=self.dev)
+        deg = RotateOut.apply(ops, g, m0.reshape(g.E, ops.Sr, C_), g.ones, 1, C_, -1) / float(m.avg_degree)
+        x = torch.cat([deg[:, :1] + x0[:, None, :], deg[:, 1:]], 1)
+        sysidx = prep.batch.long()
+        for i in range(m.num_layers):
+            p = f"blocks.{i}."
+            amask = None
+            if masks is not None and pa > 0.0:
+                amask = masks["alpha"][i].to(self.dev, torch.float32) / (1.0 - pa)
+            y = self._attention(ops, g, P, p + "ga.", norm_sh(P[p + "norm_1.affine_weight"], P[p + "norm_1.norm_l0.weight"],
+                                                              P[p + "norm_1.norm_l0.bias"], x, L), amask, -1)
+            if masks is not None and pp > 0.0:
+                y = y * (masks["path"][i, 0].to(self.dev, torch.float32) / (1.0 - pp))[sysidx][:, None, None]
+            x = x + y
+            y = self._feed_forward(ops, P, p + "ffn.", norm_sh(P[p + "norm_2.affine_weight"], P[p + "norm_2.norm_l0.weight"],
+                                                               P[p + "norm_2.norm_l0.bias"], x, L))
+            if masks is not None and pp > 0.0:
+                y = y * (masks["path"][i, 1].to(self.dev, torch.float32) / (1.0 - pp))[sysidx][:, None, None]
+            x = x + y
+        x = norm_sh(P["norm.affine_weight"], P["norm.norm_l0.weight"], P["norm.norm_l0.bias"], x, L)
+        outs = []
+        for hname in (("force_block.", "force_block2.") if self.two_heads else ("force_block.",)):
+            outs.append(self._attention(ops, g, P, hname, x, None, 1)[:, :, 0].contiguous())
+        return outs, g, prep
+
+    # ------------------------------------------------------------------ the step
+    def loss_and_grad(self, batch, targets: dict, grads_ready=None, masks=None) -> torch.Tensor:
+        """``PaiNNTrainStep.loss_and_grad``'s contract: accumulates into ``param.grad`` (call ``zero_grad`` first) and returns
+        the device tensor (loss, translation term, rotation term; 0 for one head).  ``masks``: replaces the dropout /
+        drop-path draws (``draw_masks``'s layout).  ``grads_ready(names)`` is called as soon as a group of parameters is
+        final: the force blocks (with the final norm), then the blocks from the last to the first, then the embeddings."""
+        lib = self.lib
+        for name, p in self.model.named_parameters():
+            if p.requires_grad and not self._unused(name) and p.grad is None:
+                raise RuntimeError("call zero_grad() before loss_and_grad()")
+        if getattr(batch, "tags", None) is None:
+            raise ValueError("batch.tags is required (tag 2 marks the adsorbate)")
+        try:
+            with torch.enable_grad():
+                outs, g, prep = self.forward(batch, masks)
+        except torch.OutOfMemoryError as e:   # as the rest of the library: an allocation failure is a RuntimeError
+            raise RuntimeError(f"HIP out of memory: {e}") from e
+        N, B = g.N, prep.num_systems
+        stream = C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
+        keys = ("tr_sigma", "rot_sigma", "tr_score", "rot_score") if self.two_heads else ("tr_sigma", "tr_score")
+        t = {k: targets[k].to(self.dev, torch.float32).contiguous() for k in keys}
+        loss = torch.empty(3, device=self.dev)
+        douts = [torch.empty(N, 3, device=self.dev) for _ in outs]
+        scratch = torch.empty(2 * B + 16, device=self.dev)
+        f = [o.detach() for o in outs]
+        with torch.cuda.device(self.dev):
+            if self.two_heads:
+                rot_norm = targets.get("rot_norm")
+                if rot_norm is None:
+                    from .noising import device_score_norm
+
+                    rot_norm = device_score_norm(t["rot_sigma"], self.igso3, self.dev)
+                rot_norm = rot_norm.to(self.dev, torch.float32).reshape(-1).contiguous()
+                _lib.check(lib.adf_op_score_loss(f[0].data_ptr(), f[1].data_ptr(), prep.tags.data_ptr(),
+                                                 prep.atom_offset.data_ptr(), t["tr_sigma"].data_ptr(), t["rot_sigma"].data_ptr(),
+                                                 t["tr_score"].data_ptr(), t["rot_score"].data_ptr(), rot_norm.data_ptr(),
+                                                 loss.data_ptr(), douts[0].data_ptr(), douts[1].data_ptr(), B, scratch.data_ptr(),
+                                                 stream))
+            else:
+                _lib.check(lib.adf_op_score_loss_tr(f[0].data_ptr(), prep.tags.data_ptr(), prep.atom_offset.data_ptr(),
+                                                    t["tr_sigma"].data_ptr(), t["tr_score"].data_ptr(), loss.data_ptr(),
+                                                    douts[0].data_ptr(), B, scratch.data_ptr(), stream))
+        # backward: the operators' own backwards chained by autograd; a group is announced when its last gradient landed
+        hooks = []
+        if grads_ready is not None:
+            P = dict(self.model.named_parameters())
+            groups = self.groups()
+            # a force block's output is its l = 1 rows, which proj.bias (l = 0) never reaches: its gradient is the zero
+            # tensor zero_grad left, final from the start
+            pending = [{n for n in grp if not (n.startswith("force_block") and n.endswith("proj.bias"))} for grp in groups]
+            state = {"next": 0}
+
+            def landed(name):
+                def hook(_):
+                    for s in pending:
+                        s.discard(name)
+                    while state["next"] < len(groups) and not pending[state["next"]]:
+                        grads_ready(list(groups[state["next"]]))
+                        state["next"] += 1
+                return hook
+
+            for grp in groups:
+                for name in grp:
+                    hooks.append(P[name].register_post_accumulate_grad_hook(landed(name)))
+        try:
+            torch.autograd.backward(outs, douts)
+        except torch.OutOfMemoryError as e:
+            raise RuntimeError(f"HIP out of memory: {e}") from e
+        finally:
+            for hk in hooks:
+                hk.remove()
+        if grads_ready is not None:
+            while state["next"] < len(groups):   # a group none of whose parameters the graph reached (no edges at all)
+                grads_ready(list(groups[state["next"]]))
+                state["next"] += 1
+        if self.model.training:
+            self.mask_step += 1
+        self.last_outputs = tuple(f)
+        return loss

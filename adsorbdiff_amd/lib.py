@@ -154,6 +154,12 @@ def parse_header(text: str) -> dict:
 SIGNATURES = parse_header(HEADER.read_text())
 EXPORTS = tuple(SIGNATURES)
 
+# the EquiformerV2 training operators are declared beside their translation unit (csrc/eqv2_train.h, which builds on the
+# header's types); they are bound from that text by the same parser, so they too are bound correctly or not at all
+TRAIN_HEADER = Path(__file__).resolve().parent / "csrc" / "eqv2_train.h"
+TRAIN_SIGNATURES = {name: sig for name, sig in parse_header(HEADER.read_text() + "\n" + TRAIN_HEADER.read_text()).items()
+                    if name not in SIGNATURES}
+
 _LIB = None
 
 
@@ -178,7 +184,7 @@ def load():
             "(the HIP path has no CPU fallback)"
         )
     lib = C.CDLL(str(path))
-    for name, (restype, argtypes) in SIGNATURES.items():
+    for name, (restype, argtypes) in {**SIGNATURES, **TRAIN_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     _LIB = lib

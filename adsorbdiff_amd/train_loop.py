@@ -121,8 +121,11 @@ class TrainLoopMixin:
         (no EMA swap), one factor after the other on the device.  The factors are parameters, so ``save()`` writes them;
         afterwards ``validate`` / ``predict`` no longer warn about unfitted factors.  -> ``{name: {"variance_in",
         "variance_out", "n_samples", "ratio", "value"}}``."""
-        from .scaling import fit_scale_factors
+        from .scaling import ScaleFactor, fit_scale_factors
 
+        if not any(isinstance(m, ScaleFactor) for m in self._unwrapped_model.modules()):
+            raise ValueError(f"fit_scale_factors: {type(self._unwrapped_model).__name__} has no scale factors: "
+                             "there is nothing to fit for this model")
         if batches is None:
             batches = getattr(self, "val_loader", None)
             if batches is None:

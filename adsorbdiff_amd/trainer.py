@@ -60,7 +60,9 @@ class DenoisingTrainer(TrainLoopMixin):
     def _forward_denoising(self, batch):
         """Reference: sde_denoising_trainer.py:539-553."""
         if not self.config["model_attributes"].get("so3_denoising", False):
-            return {"positions": self.model(batch.to(self.device))}
+            out = self.model(batch.to(self.device))
+            # the EquiformerV2 mirror always evaluates both force blocks; a one-head run reads the first
+            return {"positions": out[0] if isinstance(out, tuple) else out}
         out1, out2 = self.model(batch.to(self.device))
         return {"positions": out1, "positions_free": out2}
 
@@ -99,8 +101,18 @@ class DenoisingTrainer(TrainLoopMixin):
         from .exponential_moving_average import ExponentialMovingAverage
         from .train_step import FusedAdamW, MultiTensorAdamW, PaiNNTrainStep
 
+        from .equiformer_v2_denoising import EquiformerV2S_OC20_DenoisingPos
+
         self.denoising_pos_params = dict(denoising_pos_params)
-        self.train_engine = PaiNNTrainStep(self._unwrapped_model, self.device, igso3=tables)
+        if isinstance(self._unwrapped_model, EquiformerV2S_OC20_DenoisingPos):
+            # the same contract, the EquiformerV2 operators (eqv2_train_step.py); its dropout masks are keyed by
+            # (noise_seed, the trainer's step counter), so a resumed run draws the masks of the uninterrupted one
+            from .eqv2_train_step import EqV2TrainStep
+
+            self.train_engine = EqV2TrainStep(self._unwrapped_model, self.device, igso3=tables)
+            self.train_engine.mask_seed = int(noise_seed)
+        else:
+            self.train_engine = PaiNNTrainStep(self._unwrapped_model, self.device, igso3=tables)
         self.train_engine.ordered_embedding_backward = bool(reproducible)
         self.noiser = None
         if noise_on_device:
@@ -158,6 +170,8 @@ class DenoisingTrainer(TrainLoopMixin):
         if not noised:
             batch = self._noise(batch, self.denoising_pos_params, self.train_engine.igso3, noise_step, draws)
         targets = self._score_targets(batch)
+        if hasattr(self.train_engine, "mask_step"):
+            self.train_engine.mask_step = int(self.step)
         self.train_engine.zero_grad()
         world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         # the buckets' all-reduces are issued from inside the backward (heads, then layer by layer) and overlap with it
