@@ -18,6 +18,7 @@
 #include <stdlib.h>
 
 #include "eqv2.h"
+#include "eqv2_gauss.h"
 #include "graph.h"
 
 #define EQ_FOR_L(L_, MACRO) \
@@ -385,7 +386,8 @@ int32_t eq_launch_ln_silu(float* x, const float* w, const float* b, long long ro
 // zeroed (the two dense layers that follow run on the chunk's edge bound).  The centres mu_k are torch.linspace(0, rc, NB)'s
 // fp32 values (step k from the start in the lower half, rc - step (NB - 1 - k) in the upper half) and coeff is the
 // reference's -0.5 / (2 (mu_1 - mu_0))^2 rounded to fp32 (equiformer_v2_oc20.py:54-62): the basis is sharply peaked
-// (d exp / d d up to 30 per Angstrom), so a centre that is one ulp off moves a basis value by 1e-5 relative.
+// (d exp / d d up to 30 per Angstrom), so a centre that is one ulp off moves a basis value by 1e-5 relative.  The basis
+// itself (distance, centres, coeff, window, value) is eqv2_gauss.h's, shared with the training operators.
 #define EQ_RL_EPW 4
 template <int NCH>
 __global__ __launch_bounds__(256) void eq_radial_live_kernel(const float* __restrict__ e_vec, const int32_t* __restrict__ e_src,
@@ -397,7 +399,7 @@ __global__ __launch_bounds__(256) void eq_radial_live_kernel(const float* __rest
                                                              float* __restrict__ out, int32_t* flags) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const long long e0 = eptr[n0], e1 = eptr[n1];
-    const float tmax = sqrtf(104.0f / -coeff);
+    const float tmax = eq_gauss_tmax(coeff);
     for (int i = 0; i < EQ_RL_EPW; ++i) {
         const long long slot = ((long long)blockIdx.x * 4 + wave) * EQ_RL_EPW + i;
         if (slot >= Eub) return;
@@ -418,17 +420,11 @@ __global__ __launch_bounds__(256) void eq_radial_live_kernel(const float* __rest
             continue;
         }
         const float vx = e_vec[3 * e], vy = e_vec[3 * e + 1], vz = e_vec[3 * e + 2];
-        const float dist = sqrtf(vx * vx + vy * vy + vz * vz);
-        int k0 = (int)ceilf((dist - tmax) / delta), k1 = (int)floorf((dist + tmax) / delta);
-        k0 = max(k0, 0); k1 = min(k1, NB - 1);
-        k1 = min(k1, k0 + 63);   // (the window holds at most 58 functions)
+        const float dist = eq_gauss_dist(vx, vy, vz);
+        int k0, k1;
+        eq_gauss_window(dist, delta, tmax, NB, k0, k1);   // (the window holds at most 58 functions)
         float gl = 0.f;
-        if (k0 + lane <= k1) {
-            const int k = k0 + lane;
-            const float mu = k < NB / 2 ? delta * (float)k : rc - delta * (float)(NB - 1 - k);
-            const float t = dist - mu;
-            gl = expf(coeff * (t * t));
-        }
+        if (k0 + lane <= k1) gl = eq_gauss_value(dist, k0 + lane, NB, rc, delta, coeff);
         const float* pr = pair0 + ((size_t)zs * NE + zt) * EC;
         float acc[NCH];
 #pragma unroll
@@ -463,8 +459,8 @@ int32_t eq_launch_radial_live_raw(const float* e_vec, const int32_t* e_src, cons
     if (!r->pair0 || !r->w0t) { adf_set_error("eqv2: the first radial layer's pair table is not bound"); return ADF_EINVAL; }
     const dim3 grid((unsigned)((Eub + 4 * EQ_RL_EPW - 1) / (4 * EQ_RL_EPW))), block(256);
     const int nch = (EC + 63) / 64;
-    const float delta = rc / (float)(NB - 1);   // mu_1 - mu_0 of torch.linspace in fp32
-    const float coeff = (float)(-0.5 / (((double)(2.0f * delta)) * ((double)(2.0f * delta))));
+    const float delta = eq_gauss_delta(rc, NB);   // mu_1 - mu_0 of torch.linspace in fp32
+    const float coeff = eq_gauss_coeff(delta);
 #define EQ_RL_LAUNCH(NCH_)                                                                                               \
     hipLaunchKernelGGL(eq_radial_live_kernel<NCH_>, grid, block, 0, s, e_vec, e_src, e_dst, eptr, Z, r->w0t, r->pair0,   \
                        r->ln1_w, r->ln1_b, n0, n1, EC, NB, NE, rc, delta, coeff, Eub, out, flags)

@@ -80,6 +80,8 @@ class EquiformerV2_OC20(_ed.EqV2Host):
         self.lmax_list, self.mmax_list, self.grid_resolution = list(lmax_list), list(mmax_list), grid_resolution
         self.edge_channels, self.num_distance_basis = edge_channels, num_distance_basis
         self.weight_init = weight_init
+        # read by the training step alone (eqv2_train_step.EqV2S2EFTrainStep); the inference forward has no dropout
+        self.alpha_drop, self.drop_path_rate, self.proj_drop = float(alpha_drop), float(drop_path_rate), float(proj_drop)
         self.avg_num_nodes = avg_num_nodes or _AVG_NUM_NODES
         self.avg_degree = avg_degree or _AVG_DEGREE
         self.use_energy_lin_ref, self.load_energy_lin_ref = use_energy_lin_ref, load_energy_lin_ref

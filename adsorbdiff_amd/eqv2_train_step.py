@@ -1,19 +1,22 @@
-"""Score-matching training step of the EquiformerV2 denoiser on the device.
+"""Training steps of the two EquiformerV2 mirrors on the device.
 
-The counterpart of ``train_step.PaiNNTrainStep`` for ``EquiformerV2S_OC20_DenoisingPos``: the same contract
-(``zero_grad``, ``loss_and_grad(batch, targets, grads_ready)`` accumulating into ``param.grad``, ``last_outputs``), so the
-trainer, the optimizers, the EMA, the gradient reducer and the checkpoints work on it unchanged.
+``EqV2TrainStep``: the score-matching step of the denoiser ``EquiformerV2S_OC20_DenoisingPos``, the counterpart of
+``train_step.PaiNNTrainStep`` (``zero_grad``, ``loss_and_grad(batch, targets, grads_ready)`` accumulating into ``param.grad``,
+``last_outputs``).  ``EqV2S2EFTrainStep``: the S2EF step of the force field ``EquiformerV2_OC20``, the counterpart of
+``train_step.PaiNNS2EFTrainStep``.  Both keep their PaiNN twin's contract, so the trainers, the optimizers, the EMA, the
+gradient reducer and the checkpoints work on them unchanged; what they share - embedding, block loop, masks, ``groups``, the
+``grads_ready`` hooks - is ``_EqV2StepBase``.
 
 Where the arithmetic runs:
 
 * EDGE side (E rows; everything ``oracle/eqv2_oracle.py::attention_block`` does per edge, and the edge-degree embedding):
-  hand-written HIP behind the stateless ``adf_op_eq_*`` entries (csrc/eqv2_train.hip), forward and backward, on the
-  graph ``EqV2Engine.export_graph`` hands out.  Each entry is wrapped here in a ``torch.autograd.Function`` that owns its
-  saved activations; torch only chains them.
+  hand-written HIP behind the stateless ``adf_op_eq_*`` entries (csrc/eqv2_train.hip; the S2EF model's live Gaussian basis:
+  csrc/eqv2_s2ef_train.hip), forward and backward, on the graph ``EqV2Engine.export_graph`` hands out.  Each entry is
+  wrapped here in a ``torch.autograd.Function`` that owns its saved activations; torch only chains them.
 * NODE side (N rows: ``norm_sh``, SO(3) linears, the feed-forward network, the element embedding, the conditional
-  model's energy term): plain torch operations on the device under autograd, written so that no backward uses a float
-  atomic (no gather by index: per-degree slices, a one-hot product for the per-system term, the ordered embedding
-  backward ``adf_op_embed_bwd_ordered``).
+  model's energy term, the S2EF model's energy head): plain torch operations on the device under autograd, written so that
+  no backward uses a float atomic (no gather by index: per-degree slices, a one-hot product for the per-system terms, the
+  ordered embedding backward ``adf_op_embed_bwd_ordered``).
 
 Exact f32 throughout, no float atomics: two calls on the same input give the same bits.
 """
@@ -47,6 +50,7 @@ class EqGraph:
         self.zs1 = (self.Z[self.src.long()] + 1).contiguous()
         self.zt1 = (self.Z[self.dst.long()] + 1).contiguous()
         self.ones = None
+        self.dist = self.dperm = None   # EqOps.edge_distances (the S2EF model's live basis)
 
 
 class EqOps:
@@ -141,12 +145,69 @@ class EqOps:
                                                    semb.data_ptr(), temb.data_ptr(), g.E, out.data_ptr(), self.s()))
         return out
 
+    # ---- the live Gaussian basis of the S2EF model (csrc/eqv2_s2ef_train.h)
+    def edge_distances(self, g: EqGraph):
+        """(dist [E], perm [E]) of the graph, formed once per step: the kernels' |vec| and the edges sorted by it (stable:
+        ties in list order), the one order adf_op_eq_radial_gauss_bwd sums a column in."""
+        if g.dist is None:
+            g.dist = self.new(g.E)
+            if g.E:
+                _lib.check(self.lib.adf_op_eq_edge_dist(_c(g.vec).data_ptr(), g.E, g.dist.data_ptr(), self.s()))
+            g.dperm = torch.sort(g.dist, stable=True).indices.to(torch.int32).contiguous()
+        return g.dist, g.dperm
+
+    def gauss_fwd(self, g: EqGraph, W0, h0):
+        dist, _ = self.edge_distances(g)
+        sc = self.scratch(self.NB * self.EC)
+        if g.E:
+            _lib.check(self.lib.adf_op_eq_radial_gauss_fwd(self.h, dist.data_ptr(), W0.data_ptr(), W0.stride(0), g.E,
+                                                           h0.data_ptr(), sc.data_ptr(), sc.numel(), self.s()))
+        return h0
+
+    def gauss_bwd(self, g: EqGraph, dh0, dW0):
+        dist, perm = self.edge_distances(g)
+        sc = self.scratch(4 * g.E)
+        if g.E:
+            _lib.check(self.lib.adf_op_eq_radial_gauss_bwd(self.h, dist.data_ptr(), perm.data_ptr(), dh0.data_ptr(), g.E,
+                                                           dW0.data_ptr(), dW0.stride(0), sc.data_ptr(), sc.numel(), self.s()))
+        return dW0
+
 
 def _c(t: torch.Tensor) -> torch.Tensor:
     return t if t.is_contiguous() else t.contiguous()
 
 
 # ------------------------------------------------------------------------------------------------------- edge operators
+def _radial_tail_fwd(ops: EqOps, E, pad, h0, w1, b1, W3, b3, w4, b4, W6, b6):
+    """LayerNorm, SiLU, Linear, LayerNorm, SiLU, Linear behind a radial MLP's first layer h0 [E, EC] -> (out, its row
+    stride, the activations the backward reads)."""
+    EC, OUT = ops.EC, W6.shape[0]
+    y1, st1 = ops.layernorm(h0, w1, b1)
+    a1 = ops.silu(y1)
+    h3 = ops.linear(a1, W3, b3, ops.new(E, EC), E, EC, EC)
+    y4, st4 = ops.layernorm(h3, w4, b4)
+    a4 = ops.silu(y4)
+    ld = int(pad) if pad else OUT
+    out = ops.zeros(E, ld) if ld > OUT else ops.new(E, ld)
+    ops.linear(a4, W6, b6, out, E, OUT, EC, ldc=ld)
+    return out, ld, (st1, y1, a1, h3, st4, y4, a4)
+
+
+def _radial_tail_bwd(ops: EqOps, E, ld, dout, w1, W3, w4, W6, h0, st1, y1, a1, h3, st4, y4, a4):
+    """-> dh0 and the gradients of net.1 .. net.6 (dw1, db1, dW3, db3, dw4, db4, dW6, db6)."""
+    EC, OUT = ops.EC, W6.shape[0]
+    dout = _c(dout)
+    dW6, db6 = torch.zeros_like(W6), ops.zeros(OUT)
+    da4 = ops.new(E, EC)
+    ops.linear_bwd(a4, W6, dout, E, OUT, EC, dA=da4, dW=dW6, db=db6, ldc=ld)
+    dh3, dw4, db4 = ops.layernorm_bwd(h3, w4, st4, ops.silu_bwd(y4, da4))
+    dW3, db3 = torch.zeros_like(W3), ops.zeros(EC)
+    da1 = ops.new(E, EC)
+    ops.linear_bwd(a1, W3, dh3, E, EC, EC, dA=da1, dW=dW3, db=db3)
+    dh0, dw1, db1 = ops.layernorm_bwd(h0, w1, st1, ops.silu_bwd(y1, da1))
+    return dh0, dw1, db1, dW3, db3, dw4, db4, dW6, db6
+
+
 class RadialMLP(torch.autograd.Function):
     """Linear, LayerNorm, SiLU, Linear, LayerNorm, SiLU, Linear on the E rows [basis | semb[Z_src] | temb[Z_dst]]
     (oracle ``radial_mlp``); ``pad``: row stride of the output (> its width: the columns behind it are zero)."""
@@ -156,14 +217,7 @@ class RadialMLP(torch.autograd.Function):
         E, EC, IN, OUT = g.E, ops.EC, ops.NB + 2 * ops.EC, W6.shape[0]
         scal = ops.edge_scalars(g, semb, temb)
         h0 = ops.linear(scal, W0, b0, ops.new(E, EC), E, EC, IN)
-        y1, st1 = ops.layernorm(h0, w1, b1)
-        a1 = ops.silu(y1)
-        h3 = ops.linear(a1, W3, b3, ops.new(E, EC), E, EC, EC)
-        y4, st4 = ops.layernorm(h3, w4, b4)
-        a4 = ops.silu(y4)
-        ld = int(pad) if pad else OUT
-        out = ops.zeros(E, ld) if ld > OUT else ops.new(E, ld)
-        ops.linear(a4, W6, b6, out, E, OUT, EC, ldc=ld)
+        out, ld, (st1, y1, a1, h3, st4, y4, a4) = _radial_tail_fwd(ops, E, pad, h0, w1, b1, W3, b3, w4, b4, W6, b6)
         ctx.ops, ctx.g, ctx.ld = ops, g, ld
         ctx.save_for_backward(semb, temb, W0, w1, W3, w4, W6, h0, st1, y1, a1, h3, st4, y4, a4)
         return out
@@ -172,17 +226,10 @@ class RadialMLP(torch.autograd.Function):
     def backward(ctx, dout):
         ops, g, ld = ctx.ops, ctx.g, ctx.ld
         semb, temb, W0, w1, W3, w4, W6, h0, st1, y1, a1, h3, st4, y4, a4 = ctx.saved_tensors
-        E, EC, NB, OUT = g.E, ops.EC, ops.NB, W6.shape[0]
+        E, EC, NB = g.E, ops.EC, ops.NB
         IN = NB + 2 * EC
-        dout = _c(dout)
-        dW6, db6 = torch.zeros_like(W6), ops.zeros(OUT)
-        da4 = ops.new(E, EC)
-        ops.linear_bwd(a4, W6, dout, E, OUT, EC, dA=da4, dW=dW6, db=db6, ldc=ld)
-        dh3, dw4, db4 = ops.layernorm_bwd(h3, w4, st4, ops.silu_bwd(y4, da4))
-        dW3, db3 = torch.zeros_like(W3), ops.zeros(EC)
-        da1 = ops.new(E, EC)
-        ops.linear_bwd(a1, W3, dh3, E, EC, EC, dA=da1, dW=dW3, db=db3)
-        dh0, dw1, db1 = ops.layernorm_bwd(h0, w1, st1, ops.silu_bwd(y1, da1))
+        dh0, dw1, db1, dW3, db3, dw4, db4, dW6, db6 = _radial_tail_bwd(ops, E, ld, dout, w1, W3, w4, W6, h0, st1, y1, a1, h3, st4,
+                                                                       y4, a4)
         scal = ops.edge_scalars(g, semb, temb)            # formed again, not kept: 4 (NB + 2 EC) bytes per edge
         dW0, db0 = torch.zeros_like(W0), ops.zeros(EC)
         ops.linear_bwd(scal, W0, dh0, E, EC, IN, dW=dW0, db=db0)
@@ -191,6 +238,41 @@ class RadialMLP(torch.autograd.Function):
         dsemb = ops.embed_bwd(_c(demb[:, :EC]), g.zs1, ops.NE)
         dtemb = ops.embed_bwd(_c(demb[:, EC:]), g.zt1, ops.NE)
         return None, None, None, dsemb, dtemb, dW0, db0, dw1, db1, dW3, db3, dw4, db4, dW6, db6
+
+
+class RadialMLPLive(torch.autograd.Function):
+    """``RadialMLP`` for the S2EF model: the Gaussian basis of the plain distance is live on every edge and
+    is the inference forward's (csrc/eqv2_gauss.h).  The first layer is never formed as an [E, NB + 2 EC] product:
+    h0 = b0 + Ps[Z_src] + Pt[Z_dst] + (the Gaussian window, ``adf_op_eq_radial_gauss_fwd``) with the element-sized tables
+    Ps = semb W0[:, NB:NB+EC]^T and Pt = temb W0[:, NB+EC:]^T.  Backward: the window's weight gradient
+    (``adf_op_eq_radial_gauss_bwd``), the gather's through ``adf_op_embed_bwd_ordered``, db0 a column sum in row order."""
+
+    @staticmethod
+    def forward(ctx, ops: EqOps, g: EqGraph, pad, semb, temb, W0, b0, w1, b1, W3, b3, w4, b4, W6, b6):
+        E, EC, NB = g.E, ops.EC, ops.NB
+        Ps, Pt = semb @ W0[:, NB:NB + EC].t(), temb @ W0[:, NB + EC:].t()        # [max_num_elements, EC]
+        h0 = _c(b0[None, :] + Ps[g.zs1.long() - 1] + Pt[g.zt1.long() - 1])
+        ops.gauss_fwd(g, W0, h0)
+        out, ld, (st1, y1, a1, h3, st4, y4, a4) = _radial_tail_fwd(ops, E, pad, h0, w1, b1, W3, b3, w4, b4, W6, b6)
+        ctx.ops, ctx.g, ctx.ld = ops, g, ld
+        ctx.save_for_backward(semb, temb, W0, w1, W3, w4, W6, h0, st1, y1, a1, h3, st4, y4, a4)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        ops, g, ld = ctx.ops, ctx.g, ctx.ld
+        semb, temb, W0, w1, W3, w4, W6, h0, st1, y1, a1, h3, st4, y4, a4 = ctx.saved_tensors
+        E, EC, NB = g.E, ops.EC, ops.NB
+        dh0, dw1, db1, dW3, db3, dw4, db4, dW6, db6 = _radial_tail_bwd(ops, E, ld, dout, w1, W3, w4, W6, h0, st1, y1, a1, h3, st4,
+                                                                       y4, a4)
+        dW0, db0 = torch.zeros_like(W0), ops.zeros(EC)
+        ops.gauss_bwd(g, dh0, dW0)
+        ops.linear_bwd(None, None, dh0, E, EC, 1, db=db0)
+        dPs, dPt = ops.embed_bwd(dh0, g.zs1, ops.NE), ops.embed_bwd(dh0, g.zt1, ops.NE)
+        Ws, Wt = W0[:, NB:NB + EC], W0[:, NB + EC:]
+        dW0[:, NB:NB + EC] = dPs.t() @ semb
+        dW0[:, NB + EC:] = dPt.t() @ temb
+        return None, None, None, dPs @ Ws, dPt @ Wt, dW0, db0, dw1, db1, dW3, db3, dw4, db4, dW6, db6
 
 
 class RotateIn(torch.autograd.Function):
@@ -415,26 +497,26 @@ def mask_generator(device, seed: int, step: int) -> torch.Generator:
     return gen
 
 
-class EqV2TrainStep:
-    """loss + gradients of the score-matching objective for a mirror ``EquiformerV2S_OC20_DenoisingPos`` on a ROCm device."""
+class _EqV2StepBase:
+    """What the training steps of both EquiformerV2 mirrors share: the element embedding, the edge-degree embedding, the
+    block loop and the final norm as a graph of the operators above (``_trunk``), an attention block and a feed-forward
+    network, the dropout / drop-path masks, ``zero_grad``, ``groups`` and the backward with its ``grads_ready`` hooks.  A
+    subclass adds its heads and its objective."""
 
-    # no path to the loss (equiformer_v2_denoising.py:300-318): the reference's autograd leaves them at None
-    UNUSED_PREFIXES = ("energy_block.",)
+    # no path to the loss: the reference's autograd leaves them at None
+    UNUSED_PREFIXES: tuple = ()
+    # the parameters whose gradients are final first (``groups``): the heads and the final norm
+    HEAD_PREFIXES: tuple = ()
+    # the radial MLP of this model: a basis that is identically zero (the denoiser, RadialMLP) or live (RadialMLPLive)
+    radial = RadialMLP
 
-    def __init__(self, model, device="cuda:0", igso3: Optional[Igso3Tables] = None) -> None:
-        from .equiformer_v2_denoising import EquiformerV2S_OC20_DenoisingPos
-
-        if not isinstance(model, EquiformerV2S_OC20_DenoisingPos):
-            raise NotImplementedError(f"EqV2TrainStep trains EquiformerV2S_OC20_DenoisingPos, got {type(model).__name__} "
-                                      "(training the EquiformerV2 S2EF force field is not offered)")
+    def _setup(self, model, device) -> None:
         self.model = model
         self.dev = torch.device(device)
         if self.dev.type != "cuda":
-            raise RuntimeError("EqV2TrainStep needs a ROCm device (the HIP path has no CPU fallback)")
+            raise RuntimeError(f"{type(self).__name__} needs a ROCm device (the HIP path has no CPU fallback)")
         if float(getattr(model, "proj_drop", 0.0)) != 0.0:
             raise NotImplementedError("proj_drop != 0 is not offered by the EquiformerV2 training step")
-        self.two_heads = bool(model.so3_denoising)
-        self.igso3 = (igso3 or Igso3Tables.shared()) if self.two_heads else igso3
         self.lib = _lib.load()
         self.ordered_embedding_backward = True   # always: kept for the trainer, which sets it on every step object
         self.mask_seed, self.mask_step = 0, 0
@@ -448,9 +530,12 @@ class EqV2TrainStep:
 
     # ------------------------------------------------------------------ helpers
     def _unused(self, name: str) -> bool:
-        if name.startswith(self.UNUSED_PREFIXES) or name == "atom_radii":
-            return True
-        return not self.two_heads and name.startswith("force_block2.")
+        return bool(self.UNUSED_PREFIXES) and name.startswith(self.UNUSED_PREFIXES)
+
+    def _final_from_start(self, name: str) -> bool:
+        """Parameters the graph never reaches although they count as used: their gradient is the zero tensor ``zero_grad``
+        left.  A force block's output is its l = 1 rows, which proj.bias (l = 0) never reaches."""
+        return name.startswith("force_block") and name.endswith("proj.bias")
 
     def zero_grad(self) -> None:
         for name, p in self.model.named_parameters():
@@ -466,7 +551,7 @@ class EqV2TrainStep:
     def groups(self) -> List[List[str]]:
         """Parameter names in the order their gradients become final: force blocks, blocks last to first, embeddings."""
         names = [n for n, p in self.model.named_parameters() if p.requires_grad and not self._unused(n)]
-        out = [[n for n in names if n.startswith(("force_block.", "force_block2.", "norm."))]]
+        out = [[n for n in names if n.startswith(self.HEAD_PREFIXES)]]
         for i in range(self.model.num_layers - 1, -1, -1):
             out.append([n for n in names if n.startswith(f"blocks.{i}.")])
         seen = {n for grp in out for n in grp}
@@ -490,8 +575,8 @@ class EqV2TrainStep:
     def _attention(self, ops: EqOps, g: EqGraph, P, pre: str, x, mask, only_l: int):
         """SO2EquivariantGraphAttention (oracle ``attention_block``) -> [N, S, out_channels]."""
         NH, A, V, Hd = ops.NH, ops.A, ops.V, ops.Hd
-        radial = RadialMLP.apply(ops, g, 0, P[pre + "source_embedding.weight"], P[pre + "target_embedding.weight"],
-                                 *_rad_params(P, pre + "so2_conv_1.rad_func."))
+        radial = self.radial.apply(ops, g, 0, P[pre + "source_embedding.weight"], P[pre + "target_embedding.weight"],
+                                   *_rad_params(P, pre + "so2_conv_1.rad_func."))
         msg = RotateIn.apply(ops, g, x, radial)
         extra = NH * A + Hd
         msg, ex = SO2Conv.apply(ops, msg, extra, Hd, P[pre + "so2_conv_1.fc_m0.weight"], P[pre + "so2_conv_1.fc_m0.bias"],
@@ -516,6 +601,130 @@ class EqV2TrainStep:
         h = torch.einsum("gi,ngc->nic", self._from_full, gr)
         h = torch.cat([gate, h[:, 1:]], 1)
         return so3_linear(P[pre + "so3_linear_2.weight"], P[pre + "so3_linear_2.bias"], h, ops.L)
+
+    def _node_term(self, P, batch, prep):
+        """What joins the element embedding on l = 0 ([N, C]), or None."""
+        return None
+
+    def _trunk(self, batch, masks=None):
+        """Embedding, blocks and the final norm of the training forward -> (x [N, S, C], ops, graph, prep, P)."""
+        m = self.model
+        eng = m.engine(self.dev, refresh=False)
+        ops = EqOps(eng)
+        prep = eng.prepare(batch)
+        g = EqGraph(eng, batch, prep)
+        P = dict(m.named_parameters())
+        N, B, L, C_ = g.N, prep.num_systems, ops.L, ops.C
+        training = bool(m.training)
+        if not training:
+            masks = None
+        elif masks is None:
+            masks = self.draw_masks(g, B)
+        pa, pp = float(getattr(m, "alpha_drop", 0.0)), float(getattr(m, "drop_path_rate", 0.0))
+        self.last_masks = masks
+        # node embedding: element embedding (+ a subclass's term) on l = 0, plus the edge-degree embedding
+        x0 = OrderedEmbedding.apply(ops, P["sphere_embedding.weight"], g.Z)
+        term = self._node_term(P, batch, prep)
+        if term is not None:
+            x0 = x0 + term
+        pre = "edge_degree_embedding."
+        m0 = self.radial.apply(ops, g, ops.Sr * C_, P[pre + "source_embedding.weight"], P[pre + "target_embedding.weight"],
+                               *_rad_params(P, pre + "rad_func."))
+        if g.ones is None:
+            g.ones = torch.ones(g.E, 1, device=self.dev)
+        deg = RotateOut.apply(ops, g, m0.reshape(g.E, ops.Sr, C_), g.ones, 1, C_, -1) / float(m.avg_degree)
+        x = torch.cat([deg[:, :1] + x0[:, None, :], deg[:, 1:]], 1)
+        sysidx = prep.batch.long()
+        for i in range(m.num_layers):
+            p = f"blocks.{i}."
+            amask = None
+            if masks is not None and pa > 0.0:
+                amask = masks["alpha"][i].to(self.dev, torch.float32) / (1.0 - pa)
+            y = self._attention(ops, g, P, p + "ga.", norm_sh(P[p + "norm_1.affine_weight"], P[p + "norm_1.norm_l0.weight"],
+                                                              P[p + "norm_1.norm_l0.bias"], x, L), amask, -1)
+            if masks is not None and pp > 0.0:
+                y = y * (masks["path"][i, 0].to(self.dev, torch.float32) / (1.0 - pp))[sysidx][:, None, None]
+            x = x + y
+            y = self._feed_forward(ops, P, p + "ffn.", norm_sh(P[p + "norm_2.affine_weight"], P[p + "norm_2.norm_l0.weight"],
+                                                               P[p + "norm_2.norm_l0.bias"], x, L))
+            if masks is not None and pp > 0.0:
+                y = y * (masks["path"][i, 1].to(self.dev, torch.float32) / (1.0 - pp))[sysidx][:, None, None]
+            x = x + y
+        x = norm_sh(P["norm.affine_weight"], P["norm.norm_l0.weight"], P["norm.norm_l0.bias"], x, L)
+        return x, ops, g, prep, P
+
+    def _force_head(self, ops: EqOps, g: EqGraph, P, hname: str, x):
+        """A force block: the l = 1 rows of its attention, one channel -> [N, 3]."""
+        return self._attention(ops, g, P, hname, x, None, 1)[:, :, 0].contiguous()
+
+    def _require_zeroed(self) -> None:
+        for name, p in self.model.named_parameters():
+            if p.requires_grad and not self._unused(name) and p.grad is None:
+                raise RuntimeError("call zero_grad() before loss_and_grad()")
+
+    def _backward(self, outs, douts, grads_ready=None) -> None:
+        """The operators' own backwards chained by autograd, seeded with ``douts``; a group of ``groups()`` is announced to
+        ``grads_ready`` when its last gradient landed."""
+        hooks = []
+        if grads_ready is not None:
+            P = dict(self.model.named_parameters())
+            groups = self.groups()
+            pending = [{n for n in grp if not self._final_from_start(n)} for grp in groups]
+            state = {"next": 0}
+
+            def landed(name):
+                def hook(_):
+                    for s in pending:
+                        s.discard(name)
+                    while state["next"] < len(groups) and not pending[state["next"]]:
+                        grads_ready(list(groups[state["next"]]))
+                        state["next"] += 1
+                return hook
+
+            for grp in groups:
+                for name in grp:
+                    hooks.append(P[name].register_post_accumulate_grad_hook(landed(name)))
+        try:
+            torch.autograd.backward(outs, douts)
+        except torch.OutOfMemoryError as e:
+            raise RuntimeError(f"HIP out of memory: {e}") from e
+        finally:
+            for hk in hooks:
+                hk.remove()
+        if grads_ready is not None:
+            while state["next"] < len(groups):   # a group none of whose parameters the graph reached (no edges at all)
+                grads_ready(list(groups[state["next"]]))
+                state["next"] += 1
+        if self.model.training:
+            self.mask_step += 1
+
+
+class EqV2TrainStep(_EqV2StepBase):
+    """loss + gradients of the score-matching objective for a mirror ``EquiformerV2S_OC20_DenoisingPos`` on a ROCm device."""
+
+    # no path to the loss (equiformer_v2_denoising.py:300-318): the reference's autograd leaves them at None
+    UNUSED_PREFIXES = ("energy_block.",)
+    HEAD_PREFIXES = ("force_block.", "force_block2.", "norm.")
+
+    def __init__(self, model, device="cuda:0", igso3: Optional[Igso3Tables] = None) -> None:
+        from .equiformer_v2_denoising import EquiformerV2S_OC20_DenoisingPos
+
+        if not isinstance(model, EquiformerV2S_OC20_DenoisingPos):
+            raise NotImplementedError(f"EqV2TrainStep trains EquiformerV2S_OC20_DenoisingPos, got {type(model).__name__} "
+                                      "(the EquiformerV2 S2EF force field's step is EqV2S2EFTrainStep)")
+        self._setup(model, device)
+        self.two_heads = bool(model.so3_denoising)
+        self.igso3 = (igso3 or Igso3Tables.shared()) if self.two_heads else igso3
+
+    def _unused(self, name: str) -> bool:
+        if name.startswith(self.UNUSED_PREFIXES) or name == "atom_radii":
+            return True
+        return not self.two_heads and name.startswith("force_block2.")
+
+    def _node_term(self, P, batch, prep):
+        if getattr(self.model, "energy_embedding", None) is None:
+            return None
+        return self._energy_term(P, batch, prep)
 
     def _energy_term(self, P, batch, prep):
         """The conditional model's per-atom term (equiformer_v2_denoising.py:258-264): the layer runs in fp16 in the
@@ -543,51 +752,9 @@ class EqV2TrainStep:
 
     def forward(self, batch, masks=None):
         """The training forward -> (outputs [(N,3)] per head, graph, masks in force)."""
-        m = self.model
-        eng = m.engine(self.dev, refresh=False)
-        ops = EqOps(eng)
-        prep = eng.prepare(batch)
-        g = EqGraph(eng, batch, prep)
-        P = dict(m.named_parameters())
-        N, B, L, C_ = g.N, prep.num_systems, ops.L, ops.C
-        training = bool(m.training)
-        if not training:
-            masks = None
-        elif masks is None:
-            masks = self.draw_masks(g, B)
-        pa, pp = float(getattr(m, "alpha_drop", 0.0)), float(getattr(m, "drop_path_rate", 0.0))
-        self.last_masks = masks
-        # node embedding: element embedding (+ energy term) on l = 0, plus the edge-degree embedding
-        x0 = OrderedEmbedding.apply(ops, P["sphere_embedding.weight"], g.Z)
-        if getattr(m, "energy_embedding", None) is not None:
-            x0 = x0 + self._energy_term(P, batch, prep)
-        pre = "edge_degree_embedding."
-        m0 = RadialMLP.apply(ops, g, ops.Sr * C_, P[pre + "source_embedding.weight"], P[pre + "target_embedding.weight"],
-                             *_rad_params(P, pre + "rad_func."))
-        if g.ones is None:
-            g.ones = torch.ones(g.E, 1, device=self.dev)
-        deg = RotateOut.apply(ops, g, m0.reshape(g.E, ops.Sr, C_), g.ones, 1, C_, -1) / float(m.avg_degree)
-        x = torch.cat([deg[:, :1] + x0[:, None, :], deg[:, 1:]], 1)
-        sysidx = prep.batch.long()
-        for i in range(m.num_layers):
-            p = f"blocks.{i}."
-            amask = None
-            if masks is not None and pa > 0.0:
-                amask = masks["alpha"][i].to(self.dev, torch.float32) / (1.0 - pa)
-            y = self._attention(ops, g, P, p + "ga.", norm_sh(P[p + "norm_1.affine_weight"], P[p + "norm_1.norm_l0.weight"],
-                                                              P[p + "norm_1.norm_l0.bias"], x, L), amask, -1)
-            if masks is not None and pp > 0.0:
-                y = y * (masks["path"][i, 0].to(self.dev, torch.float32) / (1.0 - pp))[sysidx][:, None, None]
-            x = x + y
-            y = self._feed_forward(ops, P, p + "ffn.", norm_sh(P[p + "norm_2.affine_weight"], P[p + "norm_2.norm_l0.weight"],
-                                                               P[p + "norm_2.norm_l0.bias"], x, L))
-            if masks is not None and pp > 0.0:
-                y = y * (masks["path"][i, 1].to(self.dev, torch.float32) / (1.0 - pp))[sysidx][:, None, None]
-            x = x + y
-        x = norm_sh(P["norm.affine_weight"], P["norm.norm_l0.weight"], P["norm.norm_l0.bias"], x, L)
-        outs = []
-        for hname in (("force_block.", "force_block2.") if self.two_heads else ("force_block.",)):
-            outs.append(self._attention(ops, g, P, hname, x, None, 1)[:, :, 0].contiguous())
+        x, ops, g, prep, P = self._trunk(batch, masks)
+        outs = [self._force_head(ops, g, P, hname, x)
+                for hname in (("force_block.", "force_block2.") if self.two_heads else ("force_block.",))]
         return outs, g, prep
 
     # ------------------------------------------------------------------ the step
@@ -597,9 +764,7 @@ class EqV2TrainStep:
         drop-path draws (``draw_masks``'s layout).  ``grads_ready(names)`` is called as soon as a group of parameters is
         final: the force blocks (with the final norm), then the blocks from the last to the first, then the embeddings."""
         lib = self.lib
-        for name, p in self.model.named_parameters():
-            if p.requires_grad and not self._unused(name) and p.grad is None:
-                raise RuntimeError("call zero_grad() before loss_and_grad()")
+        self._require_zeroed()
         if getattr(batch, "tags", None) is None:
             raise ValueError("batch.tags is required (tag 2 marks the adsorbate)")
         try:
@@ -632,40 +797,117 @@ class EqV2TrainStep:
                 _lib.check(lib.adf_op_score_loss_tr(f[0].data_ptr(), prep.tags.data_ptr(), prep.atom_offset.data_ptr(),
                                                     t["tr_sigma"].data_ptr(), t["tr_score"].data_ptr(), loss.data_ptr(),
                                                     douts[0].data_ptr(), B, scratch.data_ptr(), stream))
-        # backward: the operators' own backwards chained by autograd; a group is announced when its last gradient landed
-        hooks = []
-        if grads_ready is not None:
-            P = dict(self.model.named_parameters())
-            groups = self.groups()
-            # a force block's output is its l = 1 rows, which proj.bias (l = 0) never reaches: its gradient is the zero
-            # tensor zero_grad left, final from the start
-            pending = [{n for n in grp if not (n.startswith("force_block") and n.endswith("proj.bias"))} for grp in groups]
-            state = {"next": 0}
-
-            def landed(name):
-                def hook(_):
-                    for s in pending:
-                        s.discard(name)
-                    while state["next"] < len(groups) and not pending[state["next"]]:
-                        grads_ready(list(groups[state["next"]]))
-                        state["next"] += 1
-                return hook
-
-            for grp in groups:
-                for name in grp:
-                    hooks.append(P[name].register_post_accumulate_grad_hook(landed(name)))
-        try:
-            torch.autograd.backward(outs, douts)
-        except torch.OutOfMemoryError as e:
-            raise RuntimeError(f"HIP out of memory: {e}") from e
-        finally:
-            for hk in hooks:
-                hk.remove()
-        if grads_ready is not None:
-            while state["next"] < len(groups):   # a group none of whose parameters the graph reached (no edges at all)
-                grads_ready(list(groups[state["next"]]))
-                state["next"] += 1
-        if self.model.training:
-            self.mask_step += 1
+        self._backward(outs, douts, grads_ready)
         self.last_outputs = tuple(f)
+        return loss
+
+
+class EqV2S2EFTrainStep(_EqV2StepBase):
+    """loss + gradients of the S2EF objective for a mirror ``equiformer_v2_oc20.EquiformerV2_OC20`` on a ROCm device
+    (DESIGN.md 6h): ``PaiNNS2EFTrainStep``'s contract, so ``ForcesTrainer`` works on it unchanged.  The model's own forward
+    (equiformer_v2_oc20.py:415-562) as a training graph: raw atomic numbers, the graph of the model's S2EF handle, the
+    Gaussian basis live in all 1 + num_layers + 1 radial functions (``RadialMLPLive``), the energy head on the final-normed
+    l = 0 row, one force block.  Energy loss "mae", force loss "l2mae" (``adf_op_s2ef_loss``); dE and dF seed the backward.
+
+    Every parameter counts as used.  The parts of ``energy_block`` the l = 0 output does not depend on with the shipped
+    switches (``so3_linear_1.*``, ``grid_mlp.*``, rows l >= 1 of ``so3_linear_2.weight``) take part in the reference's graph
+    and get zero tensors there; here they keep the zeros ``zero_grad`` wrote - nothing is evaluated through the grid - so the
+    optimizer's weight decay acts on them as it does in the reference."""
+
+    HEAD_PREFIXES = ("force_block.", "energy_block.", "norm.")
+    radial = RadialMLPLive
+    _ENERGY_DEAD = ("energy_block.so3_linear_1.", "energy_block.grid_mlp.")
+
+    def __init__(self, model, device="cuda:0", normalizers: Optional[dict] = None, energy_coefficient: float = 1,
+                 force_coefficient: float = 30, train_on_free_atoms: bool = True) -> None:
+        from .equiformer_v2_oc20 import EquiformerV2_OC20
+
+        if not isinstance(model, EquiformerV2_OC20):
+            raise NotImplementedError(f"EqV2S2EFTrainStep trains equiformer_v2_oc20.EquiformerV2_OC20, got {type(model).__name__}")
+        self._setup(model, device)
+        self.energy_coefficient, self.force_coefficient = float(energy_coefficient), float(force_coefficient)
+        self.train_on_free_atoms = bool(train_on_free_atoms)
+        self.norm = {}
+        for key in ("energy", "forces"):
+            nz = (normalizers or {}).get(key)
+            if nz is None or nz is False:
+                self.norm[key] = (0.0, 1.0)
+            elif isinstance(nz, dict):
+                self.norm[key] = (float(nz.get("mean", 0.0)), float(nz.get("stdev", nz.get("std", 1.0))))
+            else:
+                self.norm[key] = (float(nz.mean), float(nz.std))
+        self.metrics = None
+
+    def _final_from_start(self, name: str) -> bool:
+        return name.startswith(self._ENERGY_DEAD) or super()._final_from_start(name)
+
+    def _energy(self, P, x, g: EqGraph, prep):
+        """Per-system energies [B] from the final-normed embedding (the formula ``adf_eqv2_set_energy_head`` documents): per
+        atom so3_linear_2.weight[0, 0] . SiLU(scalar_mlp.0(x[:, 0, :])) + so3_linear_2.bias, summed per system as a product
+        with the one-hot membership (its backward needs no float atomic), divided by avg_num_nodes, plus the frozen
+        energy_lin_ref[Z] with use_energy_lin_ref."""
+        m = self.model
+        N, B = g.N, prep.num_systems
+        hid = torch.nn.functional.silu(x[:, 0, :] @ P["energy_block.scalar_mlp.0.weight"].t() + P["energy_block.scalar_mlp.0.bias"])
+        e_atom = hid @ P["energy_block.so3_linear_2.weight"][0, 0] + P["energy_block.so3_linear_2.bias"]
+        onehot = torch.zeros(B, N, device=self.dev)
+        onehot[prep.batch.long(), torch.arange(N, device=self.dev)] = 1.0
+        energy = (onehot @ e_atom) / float(m.avg_num_nodes)
+        if m.use_energy_lin_ref:
+            energy = energy + onehot @ m.energy_lin_ref.detach().to(self.dev, torch.float32)[g.Z.long()]
+        return energy
+
+    def forward(self, batch, masks=None):
+        """The training forward -> (energy [B], forces [N, 3] | None, graph, prep)."""
+        x, ops, g, prep, P = self._trunk(batch, masks)
+        energy = self._energy(P, x, g, prep)
+        forces = self._force_head(ops, g, P, "force_block.", x) if self.model.regress_forces else None
+        return energy, forces, g, prep
+
+    def loss_and_grad(self, batch, grads_ready=None, counts: Optional[torch.Tensor] = None, masks=None) -> torch.Tensor:
+        """``PaiNNS2EFTrainStep.loss_and_grad``'s contract: ``batch`` carries pos, atomic_numbers, batch, natoms, cell and the
+        targets energy [B], forces [N,3], fixed [N]; accumulates into ``param.grad`` (call ``zero_grad`` first) and returns
+        the device tensor (loss, energy term, force term); ``metrics``: (energy MAE, force MAE per component over the free
+        atoms) in target units.  ``counts``: device int64 ``[B_glob, M_glob, W]`` of a multi-rank step.  ``masks``: replaces
+        the dropout / drop-path draws.  ``grads_ready(names)``: ``force_block.``, ``energy_block.`` and ``norm.`` first, then
+        the blocks from the last to the first, then the embeddings."""
+        m, lib = self.model, self.lib
+        self._require_zeroed()
+        forces_on = bool(m.regress_forces)
+        for key in ("energy",) + (("forces",) if forces_on else ()):
+            if getattr(batch, key, None) is None:
+                raise ValueError(f"batch.{key} is required (the S2EF target)")
+        if self.train_on_free_atoms and forces_on and getattr(batch, "fixed", None) is None:
+            raise ValueError("batch.fixed is required with train_on_free_atoms")
+        if counts is not None and (counts.dtype != torch.int64 or counts.numel() != 3 or not counts.is_cuda):
+            raise ValueError("counts: a device int64 tensor [B_glob, M_glob, W]")
+        try:
+            with torch.enable_grad():
+                energy, forces, g, prep = self.forward(batch, masks)
+        except torch.OutOfMemoryError as e:   # as the rest of the library: an allocation failure is a RuntimeError
+            raise RuntimeError(f"HIP out of memory: {e}") from e
+        N, B = g.N, prep.num_systems
+        e_pred = energy.detach().contiguous()
+        f_pred = forces.detach() if forces_on else None
+        e_tgt = batch.energy.to(self.dev, torch.float32).reshape(-1).contiguous()
+        f_tgt = batch.forces.to(self.dev, torch.float32).reshape(N, 3).contiguous() if forces_on else None
+        if e_tgt.numel() != B:
+            raise ValueError(f"batch.energy has {e_tgt.numel()} entries for {B} systems")
+        loss, metrics = torch.empty(3, device=self.dev), torch.empty(2, device=self.dev)
+        dE = torch.empty(B, device=self.dev)
+        dF = torch.empty(N, 3, device=self.dev) if forces_on else None
+        scratch = torch.empty(int(lib.adf_op_s2ef_loss_scratch(B)), device=self.dev)
+        (mean_e, std_e), (mean_f, std_f) = self.norm["energy"], self.norm["forces"]
+        with torch.cuda.device(self.dev):
+            _lib.check(lib.adf_op_s2ef_loss(
+                e_pred.data_ptr(), f_pred.data_ptr() if forces_on else None, e_tgt.data_ptr(),
+                f_tgt.data_ptr() if forces_on else None, prep.fixed.data_ptr() if prep.fixed is not None else None,
+                prep.atom_offset.data_ptr(), B, 1 if self.train_on_free_atoms else 0, C.c_float(mean_e), C.c_float(std_e),
+                C.c_float(mean_f), C.c_float(std_f), C.c_float(self.energy_coefficient), C.c_float(self.force_coefficient),
+                counts.data_ptr() if counts is not None else None, loss.data_ptr(), dE.data_ptr(),
+                dF.data_ptr() if forces_on else None, metrics.data_ptr(), scratch.data_ptr(),
+                C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)))
+        self._backward([energy, forces] if forces_on else [energy], [dE, dF] if forces_on else [dE], grads_ready)
+        self.metrics = metrics
+        self.last_outputs = (e_pred, f_pred)
         return loss

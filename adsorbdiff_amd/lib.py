@@ -160,6 +160,12 @@ TRAIN_HEADER = Path(__file__).resolve().parent / "csrc" / "eqv2_train.h"
 TRAIN_SIGNATURES = {name: sig for name, sig in parse_header(HEADER.read_text() + "\n" + TRAIN_HEADER.read_text()).items()
                     if name not in SIGNATURES}
 
+# the S2EF training operators of EquiformerV2 (csrc/eqv2_s2ef_train.h): the same parser, a table of their own
+S2EF_TRAIN_HEADER = Path(__file__).resolve().parent / "csrc" / "eqv2_s2ef_train.h"
+S2EF_TRAIN_SIGNATURES = {name: sig
+                         for name, sig in parse_header(HEADER.read_text() + "\n" + S2EF_TRAIN_HEADER.read_text()).items()
+                         if name not in SIGNATURES}
+
 _LIB = None
 
 
@@ -184,7 +190,7 @@ def load():
             "(the HIP path has no CPU fallback)"
         )
     lib = C.CDLL(str(path))
-    for name, (restype, argtypes) in {**SIGNATURES, **TRAIN_SIGNATURES}.items():
+    for name, (restype, argtypes) in {**SIGNATURES, **TRAIN_SIGNATURES, **S2EF_TRAIN_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     _LIB = lib

@@ -383,13 +383,18 @@ class ForcesTrainer(TrainLoopMixin):
     # ---------------------------------------------------------------- training
     def setup_training(self, lr: float, weight_decay: float = 0.001, clip_grad_norm: float = 10.0, ema_decay: float = 0.999,
                        energy_coefficient: float = 1, force_coefficient: float = 30, loss_energy: str = "mae",
-                       loss_force: str = "l2mae", train_on_free_atoms: bool = True, reproducible: bool = False) -> None:
+                       loss_force: str = "l2mae", train_on_free_atoms: bool = True, reproducible: bool = False,
+                       mask_seed: int = 0) -> None:
         """Optimizer / EMA / objective of ``train_step``.  AdamW with weight decay except ``no_weight_decay()`` names;
         clip 10 and EMA 0.999 as configs/relaxation/gemnet_oc/gemnet_relax.yml:107-108; coefficients and
         ``train_on_free_atoms`` as the reference's defaults (utils/utils.py:1227,1257, base_trainer.py:382-390; the shipped
         YAMLs pass force_coefficient 100).  The targets are normalised with this trainer's ``normalizers``.  Only the loss
         names the shipped configs use are offered (energy "mae", forces "l2mae"); any other name is refused here.
-        ``reproducible``: as ``DenoisingTrainer.setup_training``."""
+        ``reproducible``: as ``DenoisingTrainer.setup_training``.  An ``EquiformerV2_OC20`` trains through
+        ``EqV2S2EFTrainStep``, everything else through ``PaiNNS2EFTrainStep``; ``mask_seed`` keys the
+        EquiformerV2 step's dropout / drop-path masks together with the trainer's step counter, so a resumed run draws the
+        masks of the uninterrupted one."""
+        from .equiformer_v2_oc20 import EquiformerV2_OC20
         from .exponential_moving_average import ExponentialMovingAverage
         from .train_step import FusedAdamW, MultiTensorAdamW, PaiNNS2EFTrainStep
 
@@ -397,9 +402,14 @@ class ForcesTrainer(TrainLoopMixin):
             raise NotImplementedError(
                 f"the S2EF step offers energy loss 'mae' with force loss 'l2mae', got {loss_energy!r} / {loss_force!r} "
                 "(mse, atomwisel2 and torch module names are not offered)")
-        self.train_engine = PaiNNS2EFTrainStep(self._unwrapped_model, self.device, normalizers=self.normalizers,
-                                               energy_coefficient=energy_coefficient, force_coefficient=force_coefficient,
-                                               train_on_free_atoms=train_on_free_atoms)
+        step_class = PaiNNS2EFTrainStep
+        if isinstance(self._unwrapped_model, EquiformerV2_OC20):
+            from .eqv2_train_step import EqV2S2EFTrainStep as step_class
+        self.train_engine = step_class(self._unwrapped_model, self.device, normalizers=self.normalizers,
+                                       energy_coefficient=energy_coefficient, force_coefficient=force_coefficient,
+                                       train_on_free_atoms=train_on_free_atoms)
+        if hasattr(self.train_engine, "mask_seed"):
+            self.train_engine.mask_seed = int(mask_seed)
         self.train_engine.ordered_embedding_backward = bool(reproducible)
         # a falsy ema_decay trains without an EMA: one that was loaded or set up earlier is dropped, not updated on
         self.ema = ExponentialMovingAverage(self._unwrapped_model.parameters(), ema_decay) if ema_decay else None
@@ -422,6 +432,8 @@ class ForcesTrainer(TrainLoopMixin):
         eng = self.train_engine
         self.model.train()
         batch = batch.to(self.device)
+        if hasattr(eng, "mask_step"):
+            eng.mask_step = int(self.step)
         eng.zero_grad()
         world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         counts = None
