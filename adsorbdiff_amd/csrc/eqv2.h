@@ -82,6 +82,7 @@ struct adf_eqv2 {
     float* fold_arena; size_t fold_floats;
     // constants (device)
     float *jd, *to_red, *from_red, *to_full, *from_full;
+    float* kgen;      // [3][j_off[L + 1]]: the generators K_x, K_y, K_z of D_l in J's layout, built from jd (eqv2_geo.hip)
     // weights
     const float* atom_radii;
     const float* sphere_emb;
@@ -155,7 +156,7 @@ struct adf_eqv2 {
     adf_prof prof;
     // ---- owners of the device buffers above, one per set that lives and dies together
     adf_pool m_life;    // creation to destruction: flags, d_dev
-    adf_pool m_const;   // adf_eqv2_set_constants: jd, to_* / from_*, s2tab, gtab_*
+    adf_pool m_const;   // adf_eqv2_set_constants: jd, kgen, to_* / from_*, s2tab, gtab_*
     adf_pool m_w;       // images of the bound weights: w16_*, wfrag_arena, wt_arena, rtab_arena, fold_arena, pair0_arena, eh_*
     adf_pool m_ws;      // the workspaces sized by capN / capB / capE
     adf_pool m_inc;     // incremental blocks: inc_*

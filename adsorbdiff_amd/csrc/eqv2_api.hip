@@ -128,6 +128,34 @@ extern "C" int32_t adf_eqv2_set_constants(adf_eqv2_t h, const float* jd, const f
     ADF_TRY(m.alloc(&h->jd, nj)); ADF_TRY(m.alloc(&h->to_red, nr)); ADF_TRY(m.alloc(&h->from_red, nr));
     ADF_TRY(m.alloc(&h->to_full, nf)); ADF_TRY(m.alloc(&h->from_full, nf));
     ADF_HIP_CHECK(hipMemcpy(h->jd, jd, nj * 4, hipMemcpyHostToDevice));
+    {   // generators of D_l (the geometric gradient, eqv2_geo.hip): D_l(exp(t [e_k])) = 1 + t K_k + ...  K_y = Z_l'(0), f_i = l - i
+        // on the anti-diagonal; D_l(Rx(b)) = J Z(b) J gives K_x = J K_y J; K_z = K_x K_y - K_y K_x.  Formed in double.
+        std::vector<float> kg(3 * nj, 0.f);
+        for (int l = 0; l <= d.L; ++l) {
+            const int n = 2 * l + 1;
+            const float* J = jd + d.j_off[l];
+            std::vector<double> ky((size_t)n * n, 0.0), t((size_t)n * n, 0.0), kx((size_t)n * n, 0.0);
+            for (int i = 0; i < n; ++i) ky[(size_t)i * n + (n - 1 - i)] = (double)(l - i);
+            for (int i = 0; i < n; ++i)
+                for (int j = 0; j < n; ++j) t[(size_t)i * n + j] = (double)J[i * n + (n - 1 - j)] * ky[(size_t)(n - 1 - j) * n + j];
+            for (int i = 0; i < n; ++i)
+                for (int j = 0; j < n; ++j) {
+                    double a = 0.0;
+                    for (int b = 0; b < n; ++b) a += t[(size_t)i * n + b] * (double)J[b * n + j];
+                    kx[(size_t)i * n + j] = a;
+                }
+            for (int i = 0; i < n; ++i)
+                for (int j = 0; j < n; ++j) {
+                    // (K_x K_y)[i][j] = K_x[i][n-1-j] f_{n-1-j};  (K_y K_x)[i][j] = f_i K_x[n-1-i][j]
+                    const double kz = kx[(size_t)i * n + (n - 1 - j)] * (double)(l - (n - 1 - j)) - (double)(l - i) * kx[(size_t)(n - 1 - i) * n + j];
+                    kg[0 * nj + d.j_off[l] + i * n + j] = (float)kx[(size_t)i * n + j];
+                    kg[1 * nj + d.j_off[l] + i * n + j] = (float)ky[(size_t)i * n + j];
+                    kg[2 * nj + d.j_off[l] + i * n + j] = (float)kz;
+                }
+        }
+        ADF_TRY(m.alloc(&h->kgen, 3 * nj));
+        ADF_HIP_CHECK(hipMemcpy(h->kgen, kg.data(), 3 * nj * 4, hipMemcpyHostToDevice));
+    }
     ADF_HIP_CHECK(hipMemcpy(h->to_red, to_red, nr * 4, hipMemcpyHostToDevice));
     ADF_HIP_CHECK(hipMemcpy(h->from_red, from_red, nr * 4, hipMemcpyHostToDevice));
     ADF_HIP_CHECK(hipMemcpy(h->to_full, to_full, nf * 4, hipMemcpyHostToDevice));

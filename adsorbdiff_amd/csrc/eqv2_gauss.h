@@ -43,3 +43,9 @@ __device__ __forceinline__ float eq_gauss_value(float dist, int k, int NB, float
     const float t = dist - eq_gauss_centre(k, NB, rc, delta);
     return expf(coeff * (t * t));
 }
+
+// d g_k / d dist at `dist`: g_k(d) 2 coeff (d - mu_k), the factors of eq_gauss_value (the geometric gradient, eqv2_geo.hip)
+__device__ __forceinline__ float eq_gauss_dvalue(float dist, int k, int NB, float rc, float delta, float coeff) {
+    const float t = dist - eq_gauss_centre(k, NB, rc, delta);
+    return expf(coeff * (t * t)) * (2.0f * coeff * t);
+}

@@ -71,7 +71,8 @@ int32_t adf_op_eq_alpha_fwd(adf_eqv2_t h, const float* a_in, int32_t lda, const 
                             float* alpha, void* stream);
 /* Its backward from dalpha [E, NH]: da_in (row stride ldda) is written; d_ln_w, d_ln_b [A] and d_alpha_dot [NH, A] are ADDED
  * into: per chunk of 256 edges one partial row (edges in list order), then the chunks in index order.  scratch: at least
- * 3 E NH + (3 ceil(E / 256) + 2) NH A floats; scratch_floats says what it holds (less: ADF_EINVAL). */
+ * 3 E NH + (3 ceil(E / 256) + 2) NH A floats; scratch_floats says what it holds (less: ADF_EINVAL).  d_ln_w, d_ln_b and
+ * d_alpha_dot may be NULL together: the parameter pass is then not run (the geometric gradient, csrc/eqv2_geo.h). */
 int32_t adf_op_eq_alpha_bwd(adf_eqv2_t h, const float* a_in, int32_t lda, const float* ln_w, const float* ln_b,
                             const float* alpha_dot, const int32_t* eptr, const float* mask, const float* soft,
                             const float* dalpha, int32_t N, int64_t E, float* da_in, int32_t ldda, float* d_ln_w,

@@ -655,7 +655,8 @@ extern "C" int32_t adf_op_eq_alpha_bwd(adf_eqv2_t h, const float* a_in, int32_t 
                                        float* d_ln_b, float* d_alpha_dot, float* scratch, int64_t scratch_floats, void* stream) {
     ADF_TRY(eqt_handle(h, "eq_alpha_bwd"));
     const int NH = h->d.NH, A = h->d.A, HA = NH * A;
-    if (!a_in || !ln_w || !ln_b || !alpha_dot || !eptr || !soft || !dalpha || !da_in || !d_ln_w || !d_ln_b || !d_alpha_dot ||
+    const bool params = d_ln_w || d_ln_b || d_alpha_dot;   // all three or none: none skips the parameter pass
+    if (!a_in || !ln_w || !ln_b || !alpha_dot || !eptr || !soft || !dalpha || !da_in || (params && (!d_ln_w || !d_ln_b || !d_alpha_dot)) ||
         !scratch || N <= 0 || E < 0 || lda < HA || ldda < HA) {
         adf_set_error("eq_alpha_bwd: bad argument");
         return ADF_EINVAL;
@@ -673,10 +674,12 @@ extern "C" int32_t adf_op_eq_alpha_bwd(adf_eqv2_t h, const float* a_in, int32_t 
                        NH, dl);
     hipLaunchKernelGGL(eqt_alpha_dx_kernel, dim3(eqt_grid((long long)E * NH)), dim3(256), 0, s, a_in, lda, ln_w, ln_b, alpha_dot,
                        dl, NH, A, (long long)E, da_in, ldda, stats);
-    hipLaunchKernelGGL(eqt_alpha_wpart_kernel, dim3((unsigned)chunks), dim3(eqt_block(HA)), 0, s, a_in, lda, ln_w, ln_b,
-                       alpha_dot, dl, stats, NH, A, (long long)E, part);
-    hipLaunchKernelGGL(eqt_alpha_wsum_kernel, dim3(1), dim3(256), 0, s, part, (int)chunks, NH, A, tmp, d_alpha_dot, d_ln_w,
-                       d_ln_b);
+    if (params) {
+        hipLaunchKernelGGL(eqt_alpha_wpart_kernel, dim3((unsigned)chunks), dim3(eqt_block(HA)), 0, s, a_in, lda, ln_w, ln_b,
+                           alpha_dot, dl, stats, NH, A, (long long)E, part);
+        hipLaunchKernelGGL(eqt_alpha_wsum_kernel, dim3(1), dim3(256), 0, s, part, (int)chunks, NH, A, tmp, d_alpha_dot, d_ln_w,
+                           d_ln_b);
+    }
     EQT_LAUNCHED();
     return ADF_OK;
 }

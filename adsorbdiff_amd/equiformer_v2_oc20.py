@@ -22,6 +22,14 @@ reach the energy (transformer_block.py:473-530): ``so3_linear_1``, ``grid_mlp.*`
 ``so3_linear_2.weight`` are dead parameters; they exist and load, the library reads ``scalar_mlp.0`` and row 0 of
 ``so3_linear_2.weight[0]`` only.
 
+Forces come in two ways, chosen by ``force_mode`` (as ``painn.PaiNN``): ``"direct"`` (default) returns the force block's
+output as before; ``"energy_gradient"`` returns ``-dE/dpos`` of the energy the same call reports, with the edge set held
+fixed - what ``torch.autograd.grad(energy.sum(), pos)`` gives on the reference model with a frozen graph
+(``EqV2Engine.forward_energy_gradient``, ``eqv2_train_step.EqV2EnergyGradient``, csrc/eqv2_geo.hip).  It works
+with ``regress_forces=False``: the force block is neither needed nor evaluated.  The energy that mode reports is the energy
+of the graph it differentiates - the exact-f32 training forward in ``eval()``, no dropout - which lies within 1.3e-6 of
+max|E| of the direct mode's (whose products run in f16x3).  Training with it needs a second-order backward and is refused.
+
 Supported configuration: what the denoiser mirror accepts, with ``use_pbc = otf_graph = True`` and ``mmax_list = [m]``,
 m <= 2 (no kernel of this library has been run against a reference at m = 3); anything else raises ``ValueError``.
 """
@@ -43,6 +51,7 @@ class EquiformerV2_OC20(_ed.EqV2Host):
 
     s2ef = True           # EqV2Engine binds the S2EF table and the energy head and offers forward_energy
     so3_denoising = False
+    FORCE_MODES = ("direct", "energy_gradient")
 
     def __init__(
         self,
@@ -109,6 +118,18 @@ class EquiformerV2_OC20(_ed.EqV2Host):
         self.apply(self._uniform_init_rad_func_linear_weights)    # :412, 584-593
         self._engine = None
         self._engine_key = None
+        self._force_mode = "direct"
+
+    @property
+    def force_mode(self) -> str:
+        """``"direct"``: forces from the force block; ``"energy_gradient"``: forces = -dE/dpos of the reported energy."""
+        return self._force_mode
+
+    @force_mode.setter
+    def force_mode(self, mode: str) -> None:
+        if mode not in self.FORCE_MODES:
+            raise ValueError(f"force_mode must be one of {self.FORCE_MODES}, got {mode!r}")
+        self._force_mode = mode
 
     def _init_weights(self, m) -> None:
         if isinstance(m, (nn.Linear, _ed.SO3_LinearV2)):
@@ -131,7 +152,11 @@ class EquiformerV2_OC20(_ed.EqV2Host):
 
     def forward(self, data):
         """data: pos [N,3] f32, atomic_numbers [N], batch [N], natoms [B], cell [B,3,3]
-        -> {"energy": [B], "forces": [N,3]} ({"energy"} only with regress_forces=False)."""
+        -> {"energy": [B], "forces": [N,3]} ({"energy"} only with regress_forces=False and force_mode "direct")."""
+        if self._force_mode == "energy_gradient":
+            # the graph and the constant tables come from the handle, the weights are read where they live
+            energy, forces = self.engine(data.pos.device, refresh=False).forward_energy_gradient(data)
+            return {"energy": energy, "forces": forces}
         eng = self.engine(data.pos.device)
         energy, forces = eng.forward_energy(data)
         out = {"energy": energy}

@@ -98,6 +98,7 @@ class EqV2Engine(Engine):
         self._ext_edges = 0        # edges of the list set_edges last handed over (0: the engine builds its own graph)
         self._energy_keepalive = None
         self._energy_mode = None   # what adf_eqv2_set_system_energy last received: None (never), "zeros", "given"
+        self._energy_gradient = None   # eqv2_train_step.EqV2EnergyGradient, made by the first forward_energy_gradient
         self.bind_weights()
 
     # ------------------------------------------------------------------ weights
@@ -271,6 +272,19 @@ class EqV2Engine(Engine):
         self.forward_energy_prepared(prep, pos, energy, forces, xb)
         self.check_flags()
         return (energy, forces, xb) if return_blocks else (energy, forces)
+
+    def forward_energy_gradient(self, data):
+        """-> (energy [B], forces [N,3] = -dE/dpos of that energy, the edge set held fixed).  Works without a force block.
+        The energy is the exact-f32 training forward's in ``eval()`` (``EqV2EnergyGradient``), within 1.3e-6 of max|E| of
+        ``forward_energy``'s.  Out of memory is a ``RuntimeError`` (``ml_relax`` then halves the batch): this forward holds
+        the activations of every block until its backward has run."""
+        if not self.s2ef:
+            raise RuntimeError("forward_energy_gradient: this engine is bound to the denoiser (no energy head)")
+        if self._energy_gradient is None:
+            from .eqv2_train_step import EqV2EnergyGradient
+
+            self._energy_gradient = EqV2EnergyGradient(self.model, self.device)
+        return self._energy_gradient(data)
 
     def forward(self, data, return_blocks: bool = False):
         if self.s2ef:

@@ -5,7 +5,9 @@
 ``last_outputs``).  ``EqV2S2EFTrainStep``: the S2EF step of the force field ``EquiformerV2_OC20``, the counterpart of
 ``train_step.PaiNNS2EFTrainStep``.  Both keep their PaiNN twin's contract, so the trainers, the optimizers, the EMA, the
 gradient reducer and the checkpoints work on them unchanged; what they share - embedding, block loop, masks, ``groups``, the
-``grads_ready`` hooks - is ``_EqV2StepBase``.
+``grads_ready`` hooks - is ``_EqV2StepBase``.  ``EqV2EnergyGradient`` is its third user: the S2EF model's energy
+and forces = -dE/dpos of that energy, the backward taken with respect to the edge geometry instead of the weights
+(csrc/eqv2_geo.hip).
 
 Where the arithmetic runs:
 
@@ -51,6 +53,10 @@ class EqGraph:
         self.zt1 = (self.Z[self.dst.long()] + 1).contiguous()
         self.ones = None
         self.dist = self.dperm = None   # EqOps.edge_distances (the S2EF model's live basis)
+        # accumulators of the geometric gradient, dE/dwig [E, DR] and dE/d|vec| [E]: present only while EqV2EnergyGradient
+        # differentiates with respect to the edge vectors; the backward of RotateIn, RotateOut and RadialMLPLive adds into them
+        self.dwig = self.ddist = None
+        self.geo = None                 # the leaf that makes autograd walk a graph none of whose parameters asks for a gradient
 
 
 class EqOps:
@@ -173,6 +179,26 @@ class EqOps:
         return dW0
 
 
+    # ---- the geometric gradient (csrc/eqv2_geo.h)
+    def gauss_dgrad(self, g: EqGraph, W0, dh0):
+        dist, _ = self.edge_distances(g)
+        sc = self.scratch(self.NB * self.EC)
+        if g.E:
+            _lib.check(self.lib.adf_op_eq_radial_gauss_dgrad(self.h, dist.data_ptr(), W0.data_ptr(), W0.stride(0), dh0.data_ptr(),
+                                                             g.E, g.ddist.data_ptr(), sc.data_ptr(), sc.numel(), self.s()))
+
+    def geometry_to_forces(self, g: EqGraph):
+        """forces [N, 3] = -dE/dpos from the graph's accumulators (``adf_op_eq_wigner_bwd``, ``adf_op_eq_edge_grad_to_atoms``)."""
+        dvec, forces = self.new(g.E, 3), self.new(g.N, 3)
+        if g.E:
+            _lib.check(self.lib.adf_op_eq_wigner_bwd(self.h, _c(g.vec).data_ptr(), _c(g.wig).data_ptr(), g.dwig.data_ptr(),
+                                                     g.ddist.data_ptr(), g.E, dvec.data_ptr(), self.s()))
+        _lib.check(self.lib.adf_op_eq_edge_grad_to_atoms(self._p(dvec) if g.E else None, g.eptr.data_ptr(), g.sptr.data_ptr(),
+                                                         g.sperm.data_ptr() if g.E else None, g.N, g.E, forces.data_ptr(),
+                                                         self.s()))
+        return forces
+
+
 def _c(t: torch.Tensor) -> torch.Tensor:
     return t if t.is_contiguous() else t.contiguous()
 
@@ -193,15 +219,16 @@ def _radial_tail_fwd(ops: EqOps, E, pad, h0, w1, b1, W3, b3, w4, b4, W6, b6):
     return out, ld, (st1, y1, a1, h3, st4, y4, a4)
 
 
-def _radial_tail_bwd(ops: EqOps, E, ld, dout, w1, W3, w4, W6, h0, st1, y1, a1, h3, st4, y4, a4):
-    """-> dh0 and the gradients of net.1 .. net.6 (dw1, db1, dW3, db3, dw4, db4, dW6, db6)."""
+def _radial_tail_bwd(ops: EqOps, E, ld, dout, w1, W3, w4, W6, h0, st1, y1, a1, h3, st4, y4, a4, wgrad=True):
+    """-> dh0 and the gradients of net.1 .. net.6 (dw1, db1, dW3, db3, dw4, db4, dW6, db6); ``wgrad`` off: the data path
+    alone, the two weight products are not formed (dW6, db6, dW3, db3 are None)."""
     EC, OUT = ops.EC, W6.shape[0]
     dout = _c(dout)
-    dW6, db6 = torch.zeros_like(W6), ops.zeros(OUT)
+    dW6, db6 = (torch.zeros_like(W6), ops.zeros(OUT)) if wgrad else (None, None)
     da4 = ops.new(E, EC)
     ops.linear_bwd(a4, W6, dout, E, OUT, EC, dA=da4, dW=dW6, db=db6, ldc=ld)
     dh3, dw4, db4 = ops.layernorm_bwd(h3, w4, st4, ops.silu_bwd(y4, da4))
-    dW3, db3 = torch.zeros_like(W3), ops.zeros(EC)
+    dW3, db3 = (torch.zeros_like(W3), ops.zeros(EC)) if wgrad else (None, None)
     da1 = ops.new(E, EC)
     ops.linear_bwd(a1, W3, dh3, E, EC, EC, dA=da1, dW=dW3, db=db3)
     dh0, dw1, db1 = ops.layernorm_bwd(h0, w1, st1, ops.silu_bwd(y1, da1))
@@ -245,10 +272,12 @@ class RadialMLPLive(torch.autograd.Function):
     is the inference forward's (csrc/eqv2_gauss.h).  The first layer is never formed as an [E, NB + 2 EC] product:
     h0 = b0 + Ps[Z_src] + Pt[Z_dst] + (the Gaussian window, ``adf_op_eq_radial_gauss_fwd``) with the element-sized tables
     Ps = semb W0[:, NB:NB+EC]^T and Pt = temb W0[:, NB+EC:]^T.  Backward: the window's weight gradient
-    (``adf_op_eq_radial_gauss_bwd``), the gather's through ``adf_op_embed_bwd_ordered``, db0 a column sum in row order."""
+    (``adf_op_eq_radial_gauss_bwd``), the gather's through ``adf_op_embed_bwd_ordered``, db0 a column sum in row order.
+    ``geo`` (optional; ``EqGraph.geo``): when no parameter asks for a gradient, the backward takes the data path alone and
+    adds d/d|vec| of the Gaussian window into ``g.ddist`` (``adf_op_eq_radial_gauss_dgrad``)."""
 
     @staticmethod
-    def forward(ctx, ops: EqOps, g: EqGraph, pad, semb, temb, W0, b0, w1, b1, W3, b3, w4, b4, W6, b6):
+    def forward(ctx, ops: EqOps, g: EqGraph, pad, semb, temb, W0, b0, w1, b1, W3, b3, w4, b4, W6, b6, geo=None):
         E, EC, NB = g.E, ops.EC, ops.NB
         Ps, Pt = semb @ W0[:, NB:NB + EC].t(), temb @ W0[:, NB + EC:].t()        # [max_num_elements, EC]
         h0 = _c(b0[None, :] + Ps[g.zs1.long() - 1] + Pt[g.zt1.long() - 1])
@@ -263,8 +292,13 @@ class RadialMLPLive(torch.autograd.Function):
         ops, g, ld = ctx.ops, ctx.g, ctx.ld
         semb, temb, W0, w1, W3, w4, W6, h0, st1, y1, a1, h3, st4, y4, a4 = ctx.saved_tensors
         E, EC, NB = g.E, ops.EC, ops.NB
+        wgrad = any(ctx.needs_input_grad[3:15])
         dh0, dw1, db1, dW3, db3, dw4, db4, dW6, db6 = _radial_tail_bwd(ops, E, ld, dout, w1, W3, w4, W6, h0, st1, y1, a1, h3, st4,
-                                                                       y4, a4)
+                                                                       y4, a4, wgrad)
+        if getattr(g, "ddist", None) is not None:      # (a graph stand-in of a test carries no accumulators)
+            ops.gauss_dgrad(g, W0, dh0)
+        if not wgrad:
+            return (None,) * 16
         dW0, db0 = torch.zeros_like(W0), ops.zeros(EC)
         ops.gauss_bwd(g, dh0, dW0)
         ops.linear_bwd(None, None, dh0, E, EC, 1, db=db0)
@@ -272,7 +306,7 @@ class RadialMLPLive(torch.autograd.Function):
         Ws, Wt = W0[:, NB:NB + EC], W0[:, NB + EC:]
         dW0[:, NB:NB + EC] = dPs.t() @ semb
         dW0[:, NB + EC:] = dPt.t() @ temb
-        return None, None, None, dPs @ Ws, dPt @ Wt, dW0, db0, dw1, db1, dW3, db3, dw4, db4, dW6, db6
+        return None, None, None, dPs @ Ws, dPt @ Wt, dW0, db0, dw1, db1, dW3, db3, dw4, db4, dW6, db6, None
 
 
 class RotateIn(torch.autograd.Function):
@@ -297,6 +331,9 @@ class RotateIn(torch.autograd.Function):
         _lib.check(ops.lib.adf_op_eq_rotate_in_bwd(
             ops.h, x.data_ptr(), g.eptr.data_ptr(), g.src.data_ptr(), g.dst.data_ptr(), g.wig.data_ptr(), radial.data_ptr(),
             dout.data_ptr(), g.sptr.data_ptr(), g.sperm.data_ptr(), g.N, g.E, dradial.data_ptr(), dx.data_ptr(), ops.s()))
+        if getattr(g, "dwig", None) is not None:
+            _lib.check(ops.lib.adf_op_eq_rotate_in_bwd_wig(ops.h, x.data_ptr(), g.src.data_ptr(), g.dst.data_ptr(),
+                                                           radial.data_ptr(), dout.data_ptr(), g.E, g.dwig.data_ptr(), ops.s()))
         return None, None, dx, dradial
 
 
@@ -344,7 +381,8 @@ class SO2Conv(torch.autograd.Function):
         K0 = (L + 1) * cin
         dout = _c(dout)
         dx = torch.empty_like(x)
-        dW0, db0 = torch.zeros_like(W0), ops.zeros(W0.shape[0])
+        wgrad = any(ctx.needs_input_grad[4:])     # off: the data gradient alone, no weight product is formed
+        dW0, db0 = (torch.zeros_like(W0), ops.zeros(W0.shape[0])) if wgrad else (None, None)
         ops.linear_bwd(x, W0, dout, E, (L + 1) * cout, K0, dA=dx, dW=dW0, db=db0, lda=Sr * cin, w_off=extra * K0, ldc=Sr * cout,
                        ldda=Sr * cin, dw_off=extra * K0, db_off=extra)
         if extra and dex is not None:
@@ -354,10 +392,10 @@ class SO2Conv(torch.autograd.Function):
         for mm in range(1, M + 1):
             nm = L - mm + 1
             h, k = nm * cout, nm * cin
-            dWb = torch.zeros_like(Wbs[mm - 1])
+            dWb = torch.zeros_like(Wbs[mm - 1]) if wgrad else None
             ops.linear_bwd(x, Wbs[mm - 1], dout, E, 2 * h, 2 * k, dA=dx, dW=dWb, a_off=ops.rbase[mm] * cin, lda=Sr * cin,
                            c_off=ops.rbase[mm] * cout, ldc=Sr * cout, da_off=ops.rbase[mm] * cin, ldda=Sr * cin)
-            dWm.append(torch.cat([dWb[:h, :k] + dWb[h:, k:], dWb[h:, :k] - dWb[:h, k:]], 0))
+            dWm.append(torch.cat([dWb[:h, :k] + dWb[h:, k:], dWb[h:, :k] - dWb[:h, k:]], 0) if wgrad else None)
         return (None, dx, None, None, dW0, db0, *dWm)
 
 
@@ -410,13 +448,16 @@ class AttnWeights(torch.autograd.Function):
         dalpha = _c(dalpha)
         HA = ops.NH * ops.A
         dex = torch.zeros_like(ex)
-        dw, db, dadot = torch.zeros_like(ln_w), torch.zeros_like(ln_b), torch.zeros_like(adot)
+        if any(ctx.needs_input_grad[3:6]):
+            dw, db, dadot = torch.zeros_like(ln_w), torch.zeros_like(ln_b), torch.zeros_like(adot)
+        else:
+            dw = db = dadot = None     # the entry then skips its parameter pass
         need = 3 * g.E * ops.NH + (3 * ((g.E + 255) // 256) + 2) * HA
         sc = ops.scratch(need)
         _lib.check(ops.lib.adf_op_eq_alpha_bwd(
             ops.h, ex.data_ptr(), ex.shape[1], ln_w.data_ptr(), ln_b.data_ptr(), adot.data_ptr(), g.eptr.data_ptr(),
-            ops._p(mask), soft.data_ptr(), dalpha.data_ptr(), g.N, g.E, dex.data_ptr(), ex.shape[1], dw.data_ptr(),
-            db.data_ptr(), dadot.data_ptr(), sc.data_ptr(), sc.numel(), ops.s()))
+            ops._p(mask), soft.data_ptr(), dalpha.data_ptr(), g.N, g.E, dex.data_ptr(), ex.shape[1], ops._p(dw),
+            ops._p(db), ops._p(dadot), sc.data_ptr(), sc.numel(), ops.s()))
         return None, None, dex, dw, db, dadot, None
 
 
@@ -442,6 +483,9 @@ class RotateOut(torch.autograd.Function):
         _lib.check(ops.lib.adf_op_eq_rotate_out_bwd(ops.h, z.data_ptr(), alpha.data_ptr(), NH, V, g.dst.data_ptr(),
                                                     g.wig.data_ptr(), dagg.data_ptr(), only_l, g.E, dz.data_ptr(),
                                                     dalpha.data_ptr(), ops.s()))
+        if getattr(g, "dwig", None) is not None:
+            _lib.check(ops.lib.adf_op_eq_rotate_out_bwd_wig(ops.h, z.data_ptr(), alpha.data_ptr(), NH, V, g.dst.data_ptr(),
+                                                            dagg.data_ptr(), only_l, g.E, g.dwig.data_ptr(), ops.s()))
         return None, None, dz, dalpha, None, None, None
 
 
@@ -461,11 +505,22 @@ class OrderedEmbedding(torch.autograd.Function):
 
 
 # ------------------------------------------------------------------------------------------------------- node side (torch)
-def so3_linear(weight, bias, x, L: int):
+def _mm(x, W, fold: bool = False):
+    """x [..., K] @ W^T.  ``fold`` off (the training steps): torch.matmul as ever.  ``fold`` on (``EqV2EnergyGradient``, whose
+    weights ask for no gradient): ONE product on the rows of x, written out.  That is what torch.matmul itself runs for a weight
+    that asks for a gradient - it folds the leading dimensions and calls mm - while for one that asks for none it may run a
+    batched product with other bits; folded, the energy-gradient forward reproduces the training forward's bits
+    (tests/test_gpu_eqv2_grad_forces.py::test_reported_energy)."""
+    if not fold:
+        return x @ W.t()
+    return (x.reshape(-1, x.shape[-1]) @ W.t()).reshape(*x.shape[:-1], W.shape[0])
+
+
+def so3_linear(weight, bias, x, L: int, fold: bool = False):
     """One weight matrix per degree, bias on l = 0 (so3.py:694-745); per-degree slices, no gather."""
     out = []
     for l in range(L + 1):
-        y = x[:, l * l:(l + 1) ** 2] @ weight[l].t()
+        y = _mm(x[:, l * l:(l + 1) ** 2], weight[l], fold)
         out.append(y + bias if l == 0 else y)
     return torch.cat(out, 1)
 
@@ -509,6 +564,21 @@ class _EqV2StepBase:
     HEAD_PREFIXES: tuple = ()
     # the radial MLP of this model: a basis that is identically zero (the denoiser, RadialMLP) or live (RadialMLPLive)
     radial = RadialMLP
+    # False: the forward is the one of eval() whatever model.training says (no dropout, no drop path)
+    stochastic = True
+    # True: the node side's products are written as one folded product (``_mm``); the training steps keep torch.matmul
+    fold_products = False
+
+    def _params(self) -> dict:
+        """name -> tensor the forward reads."""
+        return dict(self.model.named_parameters())
+
+    def _graph(self, eng, batch, prep) -> EqGraph:
+        return EqGraph(eng, batch, prep)
+
+    def _rows(self, fn, x):
+        """``fn`` on the node rows ``x`` [N, ...] -> [N, ...] (``fn`` maps every atom's row on its own)."""
+        return fn(x)
 
     def _setup(self, model, device) -> None:
         self.model = model
@@ -572,11 +642,16 @@ class _EqV2StepBase:
         return {"alpha": alpha, "path": path}
 
     # ------------------------------------------------------------------ forward pieces
+    def _radial(self, ops: EqOps, g: EqGraph, pad, P, emb_pre: str, rad_pre: str):
+        """The radial MLP of one attention block or of the edge-degree embedding on the graph's edges."""
+        geo = () if getattr(g, "geo", None) is None else (g.geo,)
+        return self.radial.apply(ops, g, pad, P[emb_pre + "source_embedding.weight"], P[emb_pre + "target_embedding.weight"],
+                                 *_rad_params(P, rad_pre), *geo)
+
     def _attention(self, ops: EqOps, g: EqGraph, P, pre: str, x, mask, only_l: int):
         """SO2EquivariantGraphAttention (oracle ``attention_block``) -> [N, S, out_channels]."""
         NH, A, V, Hd = ops.NH, ops.A, ops.V, ops.Hd
-        radial = self.radial.apply(ops, g, 0, P[pre + "source_embedding.weight"], P[pre + "target_embedding.weight"],
-                                   *_rad_params(P, pre + "so2_conv_1.rad_func."))
+        radial = self._radial(ops, g, 0, P, pre, pre + "so2_conv_1.rad_func.")
         msg = RotateIn.apply(ops, g, x, radial)
         extra = NH * A + Hd
         msg, ex = SO2Conv.apply(ops, msg, extra, Hd, P[pre + "so2_conv_1.fc_m0.weight"], P[pre + "so2_conv_1.fc_m0.bias"],
@@ -590,17 +665,19 @@ class _EqV2StepBase:
         if only_l >= 0:   # the force blocks: the l = 1 rows alone reach the output
             sl = slice(only_l * only_l, (only_l + 1) ** 2)
             return agg[:, sl] @ P[pre + "proj.weight"][only_l].t()
-        return so3_linear(P[pre + "proj.weight"], P[pre + "proj.bias"], agg, ops.L)
+        return self._rows(lambda a: so3_linear(P[pre + "proj.weight"], P[pre + "proj.bias"], a, ops.L, self.fold_products), agg)
 
     def _feed_forward(self, ops: EqOps, P, pre: str, x):
         F = torch.nn.functional
-        gate = F.silu(x[:, :1] @ P[pre + "scalar_mlp.0.weight"].t() + P[pre + "scalar_mlp.0.bias"])
-        h = so3_linear(P[pre + "so3_linear_1.weight"], P[pre + "so3_linear_1.bias"], x, ops.L)
+        fold = self.fold_products
+        gate = F.silu(_mm(x[:, :1], P[pre + "scalar_mlp.0.weight"], fold) + P[pre + "scalar_mlp.0.bias"])
+        h = so3_linear(P[pre + "so3_linear_1.weight"], P[pre + "so3_linear_1.bias"], x, ops.L, fold)
         gr = torch.einsum("gi,nic->ngc", self._to_full, h)
-        gr = F.silu(F.silu(gr @ P[pre + "grid_mlp.0.weight"].t()) @ P[pre + "grid_mlp.2.weight"].t()) @ P[pre + "grid_mlp.4.weight"].t()
+        gr = _mm(F.silu(_mm(F.silu(_mm(gr, P[pre + "grid_mlp.0.weight"], fold)), P[pre + "grid_mlp.2.weight"], fold)),
+                 P[pre + "grid_mlp.4.weight"], fold)
         h = torch.einsum("gi,ngc->nic", self._from_full, gr)
         h = torch.cat([gate, h[:, 1:]], 1)
-        return so3_linear(P[pre + "so3_linear_2.weight"], P[pre + "so3_linear_2.bias"], h, ops.L)
+        return so3_linear(P[pre + "so3_linear_2.weight"], P[pre + "so3_linear_2.bias"], h, ops.L, fold)
 
     def _node_term(self, P, batch, prep):
         """What joins the element embedding on l = 0 ([N, C]), or None."""
@@ -612,10 +689,10 @@ class _EqV2StepBase:
         eng = m.engine(self.dev, refresh=False)
         ops = EqOps(eng)
         prep = eng.prepare(batch)
-        g = EqGraph(eng, batch, prep)
-        P = dict(m.named_parameters())
+        g = self._graph(eng, batch, prep)
+        P = self._params()
         N, B, L, C_ = g.N, prep.num_systems, ops.L, ops.C
-        training = bool(m.training)
+        training = bool(m.training) and self.stochastic
         if not training:
             masks = None
         elif masks is None:
@@ -628,8 +705,7 @@ class _EqV2StepBase:
         if term is not None:
             x0 = x0 + term
         pre = "edge_degree_embedding."
-        m0 = self.radial.apply(ops, g, ops.Sr * C_, P[pre + "source_embedding.weight"], P[pre + "target_embedding.weight"],
-                               *_rad_params(P, pre + "rad_func."))
+        m0 = self._radial(ops, g, ops.Sr * C_, P, pre, pre + "rad_func.")
         if g.ones is None:
             g.ones = torch.ones(g.E, 1, device=self.dev)
         deg = RotateOut.apply(ops, g, m0.reshape(g.E, ops.Sr, C_), g.ones, 1, C_, -1) / float(m.avg_degree)
@@ -640,17 +716,18 @@ class _EqV2StepBase:
             amask = None
             if masks is not None and pa > 0.0:
                 amask = masks["alpha"][i].to(self.dev, torch.float32) / (1.0 - pa)
-            y = self._attention(ops, g, P, p + "ga.", norm_sh(P[p + "norm_1.affine_weight"], P[p + "norm_1.norm_l0.weight"],
-                                                              P[p + "norm_1.norm_l0.bias"], x, L), amask, -1)
+            y = self._attention(ops, g, P, p + "ga.", self._rows(
+                lambda r: norm_sh(P[p + "norm_1.affine_weight"], P[p + "norm_1.norm_l0.weight"], P[p + "norm_1.norm_l0.bias"], r, L),
+                x), amask, -1)
             if masks is not None and pp > 0.0:
                 y = y * (masks["path"][i, 0].to(self.dev, torch.float32) / (1.0 - pp))[sysidx][:, None, None]
             x = x + y
-            y = self._feed_forward(ops, P, p + "ffn.", norm_sh(P[p + "norm_2.affine_weight"], P[p + "norm_2.norm_l0.weight"],
-                                                               P[p + "norm_2.norm_l0.bias"], x, L))
+            y = self._rows(lambda r: self._feed_forward(ops, P, p + "ffn.", norm_sh(
+                P[p + "norm_2.affine_weight"], P[p + "norm_2.norm_l0.weight"], P[p + "norm_2.norm_l0.bias"], r, L)), x)
             if masks is not None and pp > 0.0:
                 y = y * (masks["path"][i, 1].to(self.dev, torch.float32) / (1.0 - pp))[sysidx][:, None, None]
             x = x + y
-        x = norm_sh(P["norm.affine_weight"], P["norm.norm_l0.weight"], P["norm.norm_l0.bias"], x, L)
+        x = self._rows(lambda r: norm_sh(P["norm.affine_weight"], P["norm.norm_l0.weight"], P["norm.norm_l0.bias"], r, L), x)
         return x, ops, g, prep, P
 
     def _force_head(self, ops: EqOps, g: EqGraph, P, hname: str, x):
@@ -824,6 +901,10 @@ class EqV2S2EFTrainStep(_EqV2StepBase):
 
         if not isinstance(model, EquiformerV2_OC20):
             raise NotImplementedError(f"EqV2S2EFTrainStep trains equiformer_v2_oc20.EquiformerV2_OC20, got {type(model).__name__}")
+        if getattr(model, "force_mode", "direct") == "energy_gradient":
+            raise NotImplementedError(
+                "training with force_mode='energy_gradient' needs a second-order backward, which is not offered: "
+                "train with force_mode='direct'")
         self._setup(model, device)
         self.energy_coefficient, self.force_coefficient = float(energy_coefficient), float(force_coefficient)
         self.train_on_free_atoms = bool(train_on_free_atoms)
@@ -846,15 +927,19 @@ class EqV2S2EFTrainStep(_EqV2StepBase):
         atom so3_linear_2.weight[0, 0] . SiLU(scalar_mlp.0(x[:, 0, :])) + so3_linear_2.bias, summed per system as a product
         with the one-hot membership (its backward needs no float atomic), divided by avg_num_nodes, plus the frozen
         energy_lin_ref[Z] with use_energy_lin_ref."""
+        return self._energy_of(P, x, g.Z, prep.batch.long(), prep.num_systems)
+
+    def _energy_of(self, P, x, Z, sysidx, B: int):
+        """``_energy`` on the rows ``x`` [n, S, C] of the atoms ``Z`` [n] that belong to the systems ``sysidx`` [n] of ``B``."""
         m = self.model
-        N, B = g.N, prep.num_systems
+        N = int(x.shape[0])
         hid = torch.nn.functional.silu(x[:, 0, :] @ P["energy_block.scalar_mlp.0.weight"].t() + P["energy_block.scalar_mlp.0.bias"])
         e_atom = hid @ P["energy_block.so3_linear_2.weight"][0, 0] + P["energy_block.so3_linear_2.bias"]
         onehot = torch.zeros(B, N, device=self.dev)
-        onehot[prep.batch.long(), torch.arange(N, device=self.dev)] = 1.0
+        onehot[sysidx, torch.arange(N, device=self.dev)] = 1.0
         energy = (onehot @ e_atom) / float(m.avg_num_nodes)
         if m.use_energy_lin_ref:
-            energy = energy + onehot @ m.energy_lin_ref.detach().to(self.dev, torch.float32)[g.Z.long()]
+            energy = energy + onehot @ m.energy_lin_ref.detach().to(self.dev, torch.float32)[Z.long()]
         return energy
 
     def forward(self, batch, masks=None):
@@ -911,3 +996,69 @@ class EqV2S2EFTrainStep(_EqV2StepBase):
         self.metrics = metrics
         self.last_outputs = (e_pred, f_pred)
         return loss
+
+
+class EqV2EnergyGradient(_EqV2StepBase):
+    """Energy and forces = -dE/dpos of that energy for a mirror ``equiformer_v2_oc20.EquiformerV2_OC20`` on a ROCm device
+    (DESIGN.md 6i): what ``torch.autograd.grad(energy.sum(), pos)`` gives on the reference model with the edge set held fixed.
+
+    The graph is ``EqV2S2EFTrainStep.forward``'s in ``eval()`` - exact f32, no dropout, trunk, final norm, energy head; the
+    force block is neither needed nor evaluated - so the energy reported is bit for bit that forward's, and within 1.3e-6 of
+    max|E| of the inference forward's (f16x3 products, README).  No parameter asks for a gradient: the operators' backwards
+    take their data paths alone (``needs_input_grad``), and RotateIn, RotateOut and RadialMLPLive add what they owe to the
+    Wigner rows and to the distances into ``EqGraph.dwig`` / ``EqGraph.ddist``.  Two launches then turn (dwig, ddist, vec) into
+    dE/dvec and into forces (``EqOps.geometry_to_forces``).  ``energy_lin_ref[Z]`` does not depend on the positions.
+
+    The node side (torch) runs system by system: the dense products torch picks depend on the number of rows, so only then
+    does a system get the same bits alone and among batch mates (the edge side's kernels treat every edge and every atom on
+    its own).  Each system's rows are what the training forward computes for that system alone."""
+
+    radial = RadialMLPLive
+    stochastic = False
+    fold_products = True
+
+    def __init__(self, model, device="cuda:0") -> None:
+        from .equiformer_v2_oc20 import EquiformerV2_OC20
+
+        if not isinstance(model, EquiformerV2_OC20):
+            raise NotImplementedError(f"EqV2EnergyGradient differentiates equiformer_v2_oc20.EquiformerV2_OC20, got "
+                                      f"{type(model).__name__}")
+        self._setup(model, device)
+
+    _energy_of = EqV2S2EFTrainStep._energy_of
+
+    def _rows(self, fn, x):
+        # one system goes through split and cat too: the order in which autograd adds the gradients of a tensor with
+        # several uses depends on the graph's shape, and a system alone must build the graph it builds among batch mates
+        return torch.cat([fn(part) for part in torch.split(x, self._sizes, 0)], 0)
+
+    def _energy(self, P, x, g: EqGraph, prep):
+        parts = zip(torch.split(x, self._sizes, 0), torch.split(g.Z, self._sizes, 0))
+        return torch.cat([self._energy_of(P, xb, zb, torch.zeros(xb.shape[0], dtype=torch.long, device=self.dev), 1)
+                          for xb, zb in parts], 0)
+
+    def _params(self) -> dict:
+        return {k: v.detach() for k, v in self.model.named_parameters()}
+
+    def _graph(self, eng, batch, prep) -> EqGraph:
+        g = EqGraph(eng, batch, prep)
+        self._sizes = [int(n) for n in batch.natoms.tolist()]     # atoms per system: the node side's row blocks
+        DR = int(g.wig.shape[1])
+        g.dwig = torch.zeros(g.E, DR, dtype=torch.float32, device=self.dev)
+        g.ddist = torch.zeros(g.E, dtype=torch.float32, device=self.dev)
+        g.geo = torch.zeros((), dtype=torch.float32, device=self.dev, requires_grad=True)
+        return g
+
+    def __call__(self, batch):
+        """-> (energy [B], forces [N, 3]); an allocation failure is a ``RuntimeError`` (``ml_relax`` then halves the batch)."""
+        try:
+            with torch.enable_grad():
+                x, ops, g, prep, P = self._trunk(batch)
+                energy = self._energy(P, x, g, prep)
+                if energy.requires_grad:   # (a graph without edges has no path to the geometry)
+                    torch.autograd.backward([energy], [torch.ones_like(energy)])
+            with torch.no_grad(), torch.cuda.device(self.dev):
+                forces = ops.geometry_to_forces(g)
+        except torch.OutOfMemoryError as e:
+            raise RuntimeError(f"HIP out of memory: {e}") from e
+        return energy.detach(), forces

@@ -166,6 +166,11 @@ S2EF_TRAIN_SIGNATURES = {name: sig
                          for name, sig in parse_header(HEADER.read_text() + "\n" + S2EF_TRAIN_HEADER.read_text()).items()
                          if name not in SIGNATURES}
 
+# the geometric gradient of the EquiformerV2 training graph (csrc/eqv2_geo.h): the same parser, a table of their own
+GEO_HEADER = Path(__file__).resolve().parent / "csrc" / "eqv2_geo.h"
+GEO_SIGNATURES = {name: sig for name, sig in parse_header(HEADER.read_text() + "\n" + GEO_HEADER.read_text()).items()
+                  if name not in SIGNATURES}
+
 _LIB = None
 
 
@@ -190,7 +195,7 @@ def load():
             "(the HIP path has no CPU fallback)"
         )
     lib = C.CDLL(str(path))
-    for name, (restype, argtypes) in {**SIGNATURES, **TRAIN_SIGNATURES, **S2EF_TRAIN_SIGNATURES}.items():
+    for name, (restype, argtypes) in {**SIGNATURES, **TRAIN_SIGNATURES, **S2EF_TRAIN_SIGNATURES, **GEO_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     _LIB = lib

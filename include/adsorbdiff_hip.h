@@ -20,6 +20,11 @@
  *   - a handle is bound to the device that was current at adf_painn_create and
  *     is NOT thread-safe.  Work is enqueued on `stream`; nothing synchronises
  *     unless stated.
+ *   - the operators of the EquiformerV2 training graph are declared beside
+ *     their translation units and bound by adsorbdiff_amd/lib.py from that
+ *     text: csrc/eqv2_train.h (edge side, forward and backward),
+ *     csrc/eqv2_s2ef_train.h (the live Gaussian basis), csrc/eqv2_geo.h (the
+ *     gradient with respect to the edge geometry: energy-gradient forces).
  */
 #ifndef ADSORBDIFF_HIP_H
 #define ADSORBDIFF_HIP_H
