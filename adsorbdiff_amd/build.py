@@ -14,7 +14,7 @@ from pathlib import Path
 PKG = Path(__file__).resolve().parent
 CSRC = PKG / "csrc"
 LIB = PKG / "libadsorbdiff_hip.so"
-SOURCES = ["api.hip", "gemm.hip", "gemm16.hip", "graph.hip", "message.hip", "message_bwd.hip", "message_geo.hip", "energy_grad.hip", "rbf_wgrad.hip", "nodewise.hip", "stepper.hip", "peaks.hip", "collect.hip", "frames.hip", "train.hip", "optimizer.hip", "noising.hip", "s2ef_train.hip", "evaluate.hip", "scale_fit.hip", "incremental.hip", "eqv2_kernels.hip", "eqv2_gemm16.hip", "eqv2_api.hip", "eqv2_train.hip", "eqv2_s2ef_train.hip", "eqv2_geo.hip", "lbfgs.hip", "active.hip", "anomaly.hip", "placement.hip", "unique.hip", "symmetry.hip", "sites.hip", "triangulate.hip", "voronoi.hip", "slabcut.hip"]
+SOURCES = ["api.hip", "gemm.hip", "gemm16.hip", "graph.hip", "message.hip", "message_bwd.hip", "message_geo.hip", "energy_grad.hip", "rbf_wgrad.hip", "nodewise.hip", "stepper.hip", "peaks.hip", "collect.hip", "frames.hip", "train.hip", "dual_ops.hip", "message_dual.hip", "optimizer.hip", "noising.hip", "s2ef_train.hip", "evaluate.hip", "scale_fit.hip", "incremental.hip", "eqv2_kernels.hip", "eqv2_gemm16.hip", "eqv2_api.hip", "eqv2_train.hip", "eqv2_s2ef_train.hip", "eqv2_geo.hip", "lbfgs.hip", "active.hip", "anomaly.hip", "placement.hip", "unique.hip", "symmetry.hip", "sites.hip", "triangulate.hip", "voronoi.hip", "slabcut.hip"]
 
 
 def _hipcc() -> str:

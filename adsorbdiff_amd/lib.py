@@ -171,6 +171,12 @@ GEO_HEADER = Path(__file__).resolve().parent / "csrc" / "eqv2_geo.h"
 GEO_SIGNATURES = {name: sig for name, sig in parse_header(HEADER.read_text() + "\n" + GEO_HEADER.read_text()).items()
                   if name not in SIGNATURES}
 
+# the dual operators of the PaiNN step that trains on energy-gradient forces (csrc/dual_ops.h): the same
+# parser, a table of their own
+DUAL_HEADER = Path(__file__).resolve().parent / "csrc" / "dual_ops.h"
+DUAL_SIGNATURES = {name: sig for name, sig in parse_header(HEADER.read_text() + "\n" + DUAL_HEADER.read_text()).items()
+                   if name not in SIGNATURES}
+
 _LIB = None
 
 
@@ -195,7 +201,8 @@ def load():
             "(the HIP path has no CPU fallback)"
         )
     lib = C.CDLL(str(path))
-    for name, (restype, argtypes) in {**SIGNATURES, **TRAIN_SIGNATURES, **S2EF_TRAIN_SIGNATURES, **GEO_SIGNATURES}.items():
+    for name, (restype, argtypes) in {**SIGNATURES, **TRAIN_SIGNATURES, **S2EF_TRAIN_SIGNATURES, **GEO_SIGNATURES,
+                                      **DUAL_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     _LIB = lib

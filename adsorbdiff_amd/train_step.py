@@ -474,7 +474,8 @@ class PaiNNS2EFTrainStep(_PaiNNStepBase):
                 "the denoiser's step is PaiNNTrainStep")
         if model.force_mode == "energy_gradient":
             raise NotImplementedError(
-                "training with force_mode='energy_gradient' needs a second-order backward, which is not offered: "
+                "training with force_mode='energy_gradient' needs a second-order backward, which this direct-force step "
+                "does not have: pass force_objective='energy_gradient' to setup_training (PaiNNGradForceTrainStep), or "
                 "train with force_mode='direct'")
         super().__init__(model, device)
         self.energy_coefficient, self.force_coefficient = float(energy_coefficient), float(force_coefficient)
@@ -562,6 +563,244 @@ class PaiNNS2EFTrainStep(_PaiNNStepBase):
             grads_ready(["out_energy.", "out_forces."])
         # ---------------- backward: layers, last to first, then the embedding
         self._trunk_backward(c, dx, dvec, saved, rbf, grads_ready)
+        self.metrics = metrics
+        self.last_outputs = (e_pred, f_pred)
+        return loss
+
+
+class PaiNNGradForceTrainStep(_PaiNNStepBase):
+    """loss + gradients of the S2EF objective with the forces ``-d(sum_b E_b)/d(pos)`` of ``force_mode="energy_gradient"``
+    in the loss: what the reference does with ``torch.autograd.grad(energy.sum(), pos, create_graph=True)`` followed by
+    ``OCPTrainer._compute_loss`` and ``loss.backward()`` (models/painn/painn.py:417-429 applied to the energy, DESIGN.md 4e /
+    6j).  Same contract as ``PaiNNS2EFTrainStep``; works without a force head, and the parameters of a force head are not part
+    of the objective (``grad`` stays None, both optimizers skip them).
+
+    The predicted forces are the gradient of the model's NORMALISED energy, so the force targets are normalised with mean 0
+    and the ENERGY normaliser's stdev - the pair ``ForcesTrainer.validate`` / ``predict`` denormalise these forces with.  The
+    forces normaliser is not used.
+
+    Four phases.  (1) energy and forces by ``adf_painn_forward_energy_gradient`` as ``model(batch)`` calls it: the reported
+    predictions are that call's bits.  (2) ``adf_op_s2ef_loss``: loss, metrics, w = dL/dE [B], v = dL/dF [N,3], constants of
+    the backward.  (3) the dual forward: with D = d/d eps sum_b E_b(pos + eps v), the force term's parameter gradient is
+    -grad_theta D; every activation carries its tangent, started from the edge tangents (``adf_op_edge_tangent``), primal and
+    tangent rows stacked so that each linear layer is one product over twice the rows, the nonlinear operators in their dual
+    forms (csrc/dual_ops.hip, csrc/message_dual.hip).  (4) one reverse pass through the joint graph, seeded with w on E and
+    -1 on D.  The radial projection rbfh [2E, 3H] is formed again in the backward instead of kept per layer."""
+
+    UNUSED_PREFIXES = ("out_forces.",)
+
+    def __init__(self, model, device="cuda:0", normalizers: Optional[dict] = None, energy_coefficient: float = 1,
+                 force_coefficient: float = 30, train_on_free_atoms: bool = True) -> None:
+        from .painn import PaiNN as S2EFPaiNN
+
+        if not isinstance(model, S2EFPaiNN):
+            raise NotImplementedError(
+                f"PaiNNGradForceTrainStep trains adsorbdiff_amd.painn.PaiNN, got {type(model).__name__}")
+        if model.force_mode != "energy_gradient":
+            raise ValueError(
+                f"force_objective='energy_gradient' trains the forces of model.force_mode='energy_gradient', but "
+                f"model.force_mode is {model.force_mode!r}: set both, so that validate / predict / ml_relax evaluate what was "
+                "trained")
+        super().__init__(model, device)
+        self.energy_coefficient, self.force_coefficient = float(energy_coefficient), float(force_coefficient)
+        self.train_on_free_atoms = bool(train_on_free_atoms)
+        self.norm = {}
+        for key in ("energy", "forces"):
+            nz = (normalizers or {}).get(key)
+            if nz is None or nz is False:
+                self.norm[key] = (0.0, 1.0)
+            elif isinstance(nz, dict):
+                self.norm[key] = (float(nz.get("mean", 0.0)), float(nz.get("stdev", nz.get("std", 1.0))))
+            else:
+                self.norm[key] = (float(nz.mean), float(nz.std))
+        # the objective's force normaliser (what ForcesTrainer.validate reads back for its loss): mean 0, the energy stdev
+        self.norm["forces"] = (0.0, self.norm["energy"][1])
+        self.metrics = None
+        self.last_outputs = None
+
+    # ------------------------------------------------------------------ stacked linear layers
+    def _lin2(self, A2, W, b, M, N, K):
+        """[A; A_dot] W^T over 2M rows; the bias goes to the M primal rows only."""
+        out = self.ops.linear(A2, W, None, 2 * M, N, K)
+        if b is not None:
+            _lib.check(self.lib.adf_op_dual_bias(out.data_ptr(), N, b.data_ptr(), M, N, self.ops.s()))
+        return out
+
+    def _lin2_bwd(self, A2, W, dC2, M, N, K, dW, db, want_dA=True, dA=None, acc_dA=False):
+        """dW += dC^T A + dC_dot^T A_dot in one product; db += the column sums of the primal rows of dC alone."""
+        dA = self.ops.linear_bwd(A2, W, dC2, 2 * M, N, K, dW, None, want_dA=want_dA, dA=dA, acc_dA=acc_dA)
+        if db is not None:
+            self.ops.linear_bwd(None, W, dC2, M, N, K, None, db, want_dA=False)
+        return dA
+
+    # ------------------------------------------------------------------ the step
+    def loss_and_grad(self, batch, grads_ready=None, counts: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """As ``PaiNNS2EFTrainStep.loss_and_grad``: targets ``batch.energy [B]``, ``batch.forces [N,3]``, ``batch.fixed [N]``;
+        returns the device tensor (loss, energy term, force term); ``metrics`` = (energy MAE, force MAE per component over
+        the free atoms) in target units; ``last_outputs = (e_pred, f_pred)``, bit for bit what ``model(batch)`` returns.
+        ``grads_ready(names)``: ``out_energy.`` together with ``out_forces.``, then each layer from the last to the first,
+        then the embedding."""
+        m, ops, lib = self.model, self.ops, self.lib
+        H, L, R = m.hidden_channels, m.num_layers, m.num_rbf
+        H2 = H // 2
+        for key in ("energy", "forces"):
+            if getattr(batch, key, None) is None:
+                raise ValueError(f"batch.{key} is required (the S2EF target)")
+        if counts is not None and (counts.dtype != torch.int64 or counts.numel() != 3 or not counts.is_cuda):
+            raise ValueError("counts: a device int64 tensor [B_glob, M_glob, W]")
+        # ---------------- phase 1: the predictions, as model(batch) forms them (engine with the current weights bound)
+        e_pred, f_pred = m.engine(self.dev).forward_energy_gradient(batch)
+        c = self._begin(batch)
+        prep, N, B, P, E, h = c.prep, c.N, c.B, c.P, c.E, c.h
+        if self.train_on_free_atoms and prep.fixed is None:
+            raise ValueError("batch.fixed is required with train_on_free_atoms")
+        s = ops.s
+        self._bind_gradients(c)
+        G, scales = c.G, c.scales
+
+        # ---------------- phase 2: loss, w = dL/dE, v = dL/dF
+        e_tgt = batch.energy.to(self.dev, torch.float32).reshape(-1).contiguous()
+        f_tgt = batch.forces.to(self.dev, torch.float32).reshape(N, 3).contiguous()
+        if e_tgt.numel() != B:
+            raise ValueError(f"batch.energy has {e_tgt.numel()} entries for {B} systems")
+        loss, metrics = ops.new(3), ops.new(2)
+        dE, dF = ops.new(B), ops.new(N, 3)
+        mean_e, std_e = self.norm["energy"]
+        _lib.check(lib.adf_op_s2ef_loss(
+            e_pred.data_ptr(), f_pred.data_ptr(), e_tgt.data_ptr(), f_tgt.data_ptr(),
+            prep.fixed.data_ptr() if prep.fixed is not None else None, prep.atom_offset.data_ptr(), B,
+            1 if self.train_on_free_atoms else 0, C.c_float(mean_e), C.c_float(std_e), C.c_float(0.0), C.c_float(std_e),
+            C.c_float(self.energy_coefficient), C.c_float(self.force_coefficient),
+            counts.data_ptr() if counts is not None else None, loss.data_ptr(), dE.data_ptr(), dF.data_ptr(),
+            metrics.data_ptr(), ops.scratch(int(lib.adf_op_s2ef_loss_scratch(B))).data_ptr(), s()))
+
+        # ---------------- phase 3: the dual forward along v, keeping what the backward reads
+        e_tan = ops.new(max(E, 1), 4)
+        _lib.check(lib.adf_op_edge_tangent(h, dF.data_ptr(), e_tan.data_ptr(), E, s()))
+        rbf2 = ops.new(2 * E, R)
+        _lib.check(lib.adf_op_rbf_dual(h, e_tan.data_ptr(), rbf2.data_ptr(), E, s()))
+        x2 = torch.zeros(2, N, H, dtype=torch.float32, device=self.dev)   # the embedding does not depend on the positions
+        _lib.check(lib.adf_op_embed_fwd(h, prep.atomic_numbers.data_ptr(), N, x2.data_ptr(), s()))
+        c.eng.check_flags()
+        vec2 = None
+        saved: List[dict] = []
+
+        def rbfh_of(l):
+            mp = f"message_layers.{l}."
+            return self._lin2(rbf2, P[mp + "rbf_proj.weight"], P[mp + "rbf_proj.bias"], E, 3 * H, R)
+
+        for l in range(L):
+            mp, up = f"message_layers.{l}.", f"update_layers.{l}."
+            a = {"x": x2, "vec": vec2}
+            a["y"], a["stats"] = ops.new(2, N, H), ops.new(N, 2)
+            _lib.check(lib.adf_op_layernorm_dual_fwd(x2.data_ptr(), P[mp + "x_layernorm.weight"].data_ptr(),
+                                                     P[mp + "x_layernorm.bias"].data_ptr(), a["y"].data_ptr(),
+                                                     a["stats"].data_ptr(), N, H, s()))
+            a["h0"] = self._lin2(a["y"], P[mp + "x_proj.0.weight"], P[mp + "x_proj.0.bias"], N, H, H)
+            a["c"] = ops.new(2, N, H)
+            _lib.check(lib.adf_op_ssilu_dual_fwd(a["h0"].data_ptr(), a["c"].data_ptr(), N * H, s()))
+            a["xh"] = self._lin2(a["c"], P[mp + "x_proj.2.weight"], P[mp + "x_proj.2.bias"], N, 3 * H, H)
+            rbfh2 = rbfh_of(l)
+            x1, a["vec1"] = ops.new(2, N, H), ops.new(2, N, 3, H)
+            _lib.check(lib.adf_op_message_dual_fwd(h, e_tan.data_ptr(), a["xh"].data_ptr(),
+                                                   vec2.data_ptr() if vec2 is not None else None, rbfh2.data_ptr(),
+                                                   x2.data_ptr(), x1.data_ptr(), a["vec1"].data_ptr(),
+                                                   1 if vec2 is None else 0, E, s()))
+            del rbfh2
+            a["vv"] = self._lin2(a["vec1"], P[up + "vec_proj.weight"], None, 3 * N, 2 * H, H)
+            a["cat"], a["dot"] = ops.new(2, N, 2 * H), ops.new(2, N, H)
+            _lib.check(lib.adf_op_copy_rows(x1.data_ptr(), H, a["cat"].data_ptr(), 2 * H, 2 * N, H, 0, s()))
+            _lib.check(lib.adf_op_vdot_dual_fwd(a["vv"].data_ptr(), a["dot"].data_ptr(), a["cat"].data_ptr() + 4 * H, 2 * H,
+                                                N, H, C.c_float(1e-8), s()))
+            a["u0"] = self._lin2(a["cat"], P[up + "xvec_proj.0.weight"], P[up + "xvec_proj.0.bias"], N, H, 2 * H)
+            a["ua"] = ops.new(2, N, H)
+            _lib.check(lib.adf_op_ssilu_dual_fwd(a["u0"].data_ptr(), a["ua"].data_ptr(), N * H, s()))
+            a["a"] = self._lin2(a["ua"], P[up + "xvec_proj.2.weight"], P[up + "xvec_proj.2.bias"], N, 3 * H, H)
+            xn, vn = ops.new(2, N, H), ops.new(2, N, 3, H)
+            _lib.check(lib.adf_op_update_out_dual_fwd(x1.data_ptr(), a["vec1"].data_ptr(), a["a"].data_ptr(),
+                                                      a["dot"].data_ptr(), a["vv"].data_ptr(), C.c_float(scales[l]),
+                                                      xn.data_ptr(), vn.data_ptr(), N, H, s()))
+            saved.append(a)
+            x2, vec2 = xn, vn
+        he0 = self._lin2(x2, P["out_energy.0.weight"], P["out_energy.0.bias"], N, H2, H)
+        hea = ops.new(2, N, H2)
+        _lib.check(lib.adf_op_ssilu_dual_fwd(he0.data_ptr(), hea.data_ptr(), N * H2, s()))
+
+        # ---------------- phase 4: the joint backward, seeded with w on the atoms' energies and -1 on their tangents
+        seed = torch.cat([dE.index_select(0, prep.batch.long()), torch.full((N,), -1.0, device=self.dev)]).reshape(2 * N, 1)
+        seed = seed.contiguous()
+        dhea = self._lin2_bwd(hea, P["out_energy.2.weight"], seed, N, 1, H2, G["out_energy.2.weight"],
+                              G["out_energy.2.bias"])
+        dhe0 = ops.new(2, N, H2)
+        _lib.check(lib.adf_op_ssilu_dual_bwd(he0.data_ptr(), dhea.data_ptr(), dhe0.data_ptr(), N * H2, s()))
+        dx = self._lin2_bwd(x2, P["out_energy.0.weight"], dhe0, N, H2, H, G["out_energy.0.weight"], G["out_energy.0.bias"])
+        dvec = torch.zeros(2, N, 3, H, dtype=torch.float32, device=self.dev)
+        if grads_ready is not None:
+            grads_ready(["out_energy.", "out_forces."])
+        for l in range(L - 1, -1, -1):
+            a = saved[l]
+            mp, up = f"message_layers.{l}.", f"update_layers.{l}."
+            # update block
+            da, ddot, dv1 = ops.new(2, N, 3 * H), ops.new(2, N, H), ops.new(2, N, 3, H)
+            dx1, dvec1 = ops.new(2, N, H), ops.new(2, N, 3, H)
+            _lib.check(lib.adf_op_update_out_dual_bwd(a["a"].data_ptr(), a["dot"].data_ptr(), a["vv"].data_ptr(),
+                                                      C.c_float(scales[l]), dx.data_ptr(), dvec.data_ptr(), da.data_ptr(),
+                                                      ddot.data_ptr(), dv1.data_ptr(), dx1.data_ptr(), dvec1.data_ptr(), N, H,
+                                                      s()))
+            dua = self._lin2_bwd(a["ua"], P[up + "xvec_proj.2.weight"], da, N, 3 * H, H, G[up + "xvec_proj.2.weight"],
+                                 G[up + "xvec_proj.2.bias"])
+            du0 = ops.new(2, N, H)
+            _lib.check(lib.adf_op_ssilu_dual_bwd(a["u0"].data_ptr(), dua.data_ptr(), du0.data_ptr(), N * H, s()))
+            dcat = self._lin2_bwd(a["cat"], P[up + "xvec_proj.0.weight"], du0, N, H, 2 * H, G[up + "xvec_proj.0.weight"],
+                                  G[up + "xvec_proj.0.bias"])
+            _lib.check(lib.adf_op_copy_rows(dcat.data_ptr(), 2 * H, dx1.data_ptr(), H, 2 * N, H, 1, s()))
+            dvv = ops.new(2, N, 3, 2 * H)
+            _lib.check(lib.adf_op_vdot_dual_bwd(a["vv"].data_ptr(), a["cat"].data_ptr() + 4 * H, 2 * H, ddot.data_ptr(),
+                                                dcat.data_ptr() + 4 * H, 2 * H, dv1.data_ptr(), dvv.data_ptr(), N, H, s()))
+            self._lin2_bwd(a["vec1"], P[up + "vec_proj.weight"], dvv, 3 * N, 2 * H, H, G[up + "vec_proj.weight"], None,
+                           dA=dvec1, acc_dA=True)
+            # message block
+            first = a["vec"] is None
+            rbfh2 = rbfh_of(l)
+            dxh, drbfh = ops.new(2, N, 3 * H), ops.new(2 * E, 3 * H)
+            dvec_in = None if first else ops.new(2, N, 3, H)
+            dx_in = ops.new(2, N, H)
+            _lib.check(lib.adf_op_message_dual_bwd(h, e_tan.data_ptr(), a["xh"].data_ptr(),
+                                                   a["vec"].data_ptr() if not first else None, rbfh2.data_ptr(),
+                                                   dx1.data_ptr(), dvec1.data_ptr(), dxh.data_ptr(), drbfh.data_ptr(),
+                                                   dvec_in.data_ptr() if not first else None, dx_in.data_ptr(),
+                                                   1 if first else 0, E, s()))
+            del rbfh2
+            self._lin2_bwd(rbf2, P[mp + "rbf_proj.weight"], drbfh, E, 3 * H, R, G[mp + "rbf_proj.weight"],
+                           G[mp + "rbf_proj.bias"], want_dA=False)
+            del drbfh
+            dc = self._lin2_bwd(a["c"], P[mp + "x_proj.2.weight"], dxh, N, 3 * H, H, G[mp + "x_proj.2.weight"],
+                                G[mp + "x_proj.2.bias"])
+            dh0 = ops.new(2, N, H)
+            _lib.check(lib.adf_op_ssilu_dual_bwd(a["h0"].data_ptr(), dc.data_ptr(), dh0.data_ptr(), N * H, s()))
+            dy = self._lin2_bwd(a["y"], P[mp + "x_proj.0.weight"], dh0, N, H, H, G[mp + "x_proj.0.weight"],
+                                G[mp + "x_proj.0.bias"])
+            dlw, dlb = ops.new(H), ops.new(H)
+            _lib.check(lib.adf_op_layernorm_dual_bwd(a["x"].data_ptr(), P[mp + "x_layernorm.weight"].data_ptr(),
+                                                     a["stats"].data_ptr(), dy.data_ptr(), dx_in.data_ptr(), dlw.data_ptr(),
+                                                     dlb.data_ptr(), N, H, ops.scratch(512 * 2 * H + 16).data_ptr(), s()))
+            _lib.check(lib.adf_op_copy_rows(dlw.data_ptr(), H, G[mp + "x_layernorm.weight"].data_ptr(), H, 1, H, 1, s()))
+            _lib.check(lib.adf_op_copy_rows(dlb.data_ptr(), H, G[mp + "x_layernorm.bias"].data_ptr(), H, 1, H, 1, s()))
+            saved[l] = None
+            dx, dvec = dx_in, dvec_in
+            if grads_ready is not None:
+                grads_ready([mp, up])
+        # the embedding: the primal block of dx (the tangent of the embedding rows is zero, a constant)
+        demb = G["atom_emb.embeddings.weight"]
+        if self.ordered_embedding_backward:
+            rows = int(demb.shape[0])
+            sc = ops.scratch(int(lib.adf_op_embed_bwd_ordered_scratch(N, H, rows)))
+            _lib.check(lib.adf_op_embed_bwd_ordered(dx.data_ptr(), prep.atomic_numbers.data_ptr(), demb.data_ptr(), N, H, rows,
+                                                    sc.data_ptr(), s()))
+        else:
+            _lib.check(lib.adf_op_embed_bwd(dx.data_ptr(), prep.atomic_numbers.data_ptr(), demb.data_ptr(), N, H, s()))
+        if grads_ready is not None:
+            grads_ready(["atom_emb."])
         self.metrics = metrics
         self.last_outputs = (e_pred, f_pred)
         return loss

@@ -384,7 +384,7 @@ class ForcesTrainer(TrainLoopMixin):
     def setup_training(self, lr: float, weight_decay: float = 0.001, clip_grad_norm: float = 10.0, ema_decay: float = 0.999,
                        energy_coefficient: float = 1, force_coefficient: float = 30, loss_energy: str = "mae",
                        loss_force: str = "l2mae", train_on_free_atoms: bool = True, reproducible: bool = False,
-                       mask_seed: int = 0) -> None:
+                       mask_seed: int = 0, force_objective: str = "direct") -> None:
         """Optimizer / EMA / objective of ``train_step``.  AdamW with weight decay except ``no_weight_decay()`` names;
         clip 10 and EMA 0.999 as configs/relaxation/gemnet_oc/gemnet_relax.yml:107-108; coefficients and
         ``train_on_free_atoms`` as the reference's defaults (utils/utils.py:1227,1257, base_trainer.py:382-390; the shipped
@@ -393,10 +393,17 @@ class ForcesTrainer(TrainLoopMixin):
         ``reproducible``: as ``DenoisingTrainer.setup_training``.  An ``EquiformerV2_OC20`` trains through
         ``EqV2S2EFTrainStep``, everything else through ``PaiNNS2EFTrainStep``; ``mask_seed`` keys the
         EquiformerV2 step's dropout / drop-path masks together with the trainer's step counter, so a resumed run draws the
-        masks of the uninterrupted one."""
+        masks of the uninterrupted one.  ``force_objective``: ``"direct"`` puts the force head's output into the loss;
+        ``"energy_gradient"`` puts ``-d(energy.sum())/d(pos)`` there (``PaiNNGradForceTrainStep``, DESIGN.md 6j: the force
+        targets are then normalised with mean 0 and the energy normaliser's stdev) and requires
+        ``model.force_mode == "energy_gradient"``, so that ``validate`` / ``predict`` / ``ml_relax`` evaluate what was
+        trained; it is not offered for EquiformerV2."""
         from .equiformer_v2_oc20 import EquiformerV2_OC20
         from .exponential_moving_average import ExponentialMovingAverage
-        from .train_step import FusedAdamW, MultiTensorAdamW, PaiNNS2EFTrainStep
+        from .train_step import FusedAdamW, MultiTensorAdamW, PaiNNGradForceTrainStep, PaiNNS2EFTrainStep
+
+        if force_objective not in ("direct", "energy_gradient"):
+            raise ValueError(f"force_objective is 'direct' or 'energy_gradient', got {force_objective!r}")
 
         if loss_energy != "mae" or loss_force != "l2mae":
             raise NotImplementedError(
@@ -404,7 +411,16 @@ class ForcesTrainer(TrainLoopMixin):
                 "(mse, atomwisel2 and torch module names are not offered)")
         step_class = PaiNNS2EFTrainStep
         if isinstance(self._unwrapped_model, EquiformerV2_OC20):
+            if force_objective == "energy_gradient":
+                raise NotImplementedError("force_objective='energy_gradient' is not offered for EquiformerV2")
             from .eqv2_train_step import EqV2S2EFTrainStep as step_class
+        elif force_objective == "energy_gradient":
+            if getattr(self._unwrapped_model, "force_mode", "direct") != "energy_gradient":
+                raise ValueError(
+                    "force_objective='energy_gradient' requires model.force_mode='energy_gradient' (it is "
+                    f"{getattr(self._unwrapped_model, 'force_mode', 'direct')!r}): set both switches, so that validate / "
+                    "predict / ml_relax evaluate the forces that were trained")
+            step_class = PaiNNGradForceTrainStep
         self.train_engine = step_class(self._unwrapped_model, self.device, normalizers=self.normalizers,
                                        energy_coefficient=energy_coefficient, force_coefficient=force_coefficient,
                                        train_on_free_atoms=train_on_free_atoms)

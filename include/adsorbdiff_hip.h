@@ -25,6 +25,8 @@
  *     text: csrc/eqv2_train.h (edge side, forward and backward),
  *     csrc/eqv2_s2ef_train.h (the live Gaussian basis), csrc/eqv2_geo.h (the
  *     gradient with respect to the edge geometry: energy-gradient forces).
+ *     So are the dual operators of the PaiNN step that trains on
+ *     energy-gradient forces: csrc/dual_ops.h.
  */
 #ifndef ADSORBDIFF_HIP_H
 #define ADSORBDIFF_HIP_H
